@@ -7,7 +7,9 @@ one forward model per rank through the fused CIRSrad path (ck_overlap + thermal_
 every input already resident in HBM.  N>1: one process per GPU, independent forward models per
 rank (the jacobian_nemesis fan-out), no data-path collective in the timed steps ("weak").
 
-After the timed steps rank 0 also reports (extra keys, outside the timed region):
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes the last timed
+step's spectrum to DIR/spectrum.npy (seeded inputs: the same arguments give the same inputs on every run).
+With --full, after the timed steps rank 0 also reports (extra keys, outside the timed region; null without --full):
   jacobian: wall time of a 201-forward-model numerical Jacobian (C3) sharded over the N ranks with
             one all_gather (RCCL) of the spectra.
   cpu_baseline: the CPU oracle ("port") on a bounded sample of the same workload.
@@ -364,6 +366,11 @@ def main():
     ap.add_argument("--no-jacobian", action="store_true")
     ap.add_argument("--cpu-sample-waves", type=int, default=10000)
     ap.add_argument("--no-extras", action="store_true", help="skip the extra keys (S=20 variant, gradients, C4, C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure and check the rest: roofline, CPU baseline, Jacobian, extras "
+                         "(--no-cpu-baseline, --no-jacobian and --no-extras trim this); without it only the headline runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
 
     # stdout carries ONE JSON line and nothing else: native libraries write there too (RCCL prints a version banner at the
@@ -427,12 +434,13 @@ def main():
     torch.cuda.synchronize()
     table_relayout_s = time.time() - t0
     Wc = min(args.cpu_sample_waves, W)
-    do_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline      # contract: rank 0 at N = 1 only
+    do_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline      # contract: rank 0 at N = 1 only
+    do_jac = args.full and not args.no_jacobian
     K_sample = Kdev[:Wc].cpu().numpy() if do_cpu else None
     # N > 1: the Jacobian is sharded over the spectral axis (jacobian_nemesis_batched, shard = "wavenumbers"): a second
     # context on this GPU holds this rank's slice chunk_range(W, N, rank) of the same table -- 1/N of it, not a replica
     eng_j, wj0, wj1 = eng, 0, W
-    if world > 1 and not args.no_jacobian:
+    if world > 1 and do_jac:
         wj0, wj1 = chunk_range(W, world, rank)
         eng_j = pkg.AnsfmEngine(local_rank)
         eng_j.set_stream(stream.cuda_stream)
@@ -474,13 +482,18 @@ def main():
         step(i % nj)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # SPECOUT of the last timed step, model (steps - 1) % jac_models: (1 path, W wavenumbers, P geometries), f64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "spectrum.npy"), d_out1.cpu().numpy())
     # per-kernel duration measured live with hipEvents on the stream the kernels run on:
     # a few extra (untimed) steps, one event pair per launch
     rt_ms = []
-    for i in range(min(args.steps, 10)):
-        step(i % nj)
-        k = eng.last_kernel_ms()
-        ov_ms.append(k["overlap_ms"]); rt_ms.append(k["rt_ms"])
+    if args.full:
+        for i in range(min(args.steps, 10)):
+            step(i % nj)
+            k = eng.last_kernel_ms()
+            ov_ms.append(k["overlap_ms"]); rt_ms.append(k["rt_ms"])
     if use_dist:
         t = torch.tensor([elapsed], dtype=f8, device="cpu" if rehearsal else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -495,7 +508,7 @@ def main():
     # (`layer_opacities_computed`).  Measured twice: with and without that de-duplication (same KK to the last bit).
     jac = None
     model = None
-    if not args.no_jacobian:
+    if do_jac:
         from archnemesis_dist_amd.jacobian import jacobian_nemesis_batched
         from archnemesis_dist_amd.profile_state import ContinuousProfileState, BatchedCKThermalModel
         npro = (nj - 1) // 2
@@ -586,36 +599,38 @@ def main():
         return
 
     # ---- roofline of the dominant kernel -------------------------------------------------------------
-    ov = float(np.mean(ov_ms)) * 1e-3
-    abytes = algorithmic_bytes(W, G, S, L, NP, NT, P, 1)
-    traffic = None
-    valu = None
-    traffic_src = None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            key = f"W{W}_G{G}_S{S}_L{L}"
-            traffic = tj.get(key, {}).get("ck_overlap_hbm_bytes_per_launch")
-            valu = tj.get(key, {}).get("valu_insts_per_launch")
-            traffic_src = ("profiles/pmc_traffic.json: committed rocprofv3 --pmc pass (run %s), NOT measured in this run"
-                           % tj.get(key, {}).get("profile", "?"))
-        except Exception:
-            traffic = None
-    roof = {"bound": "hbm", "kernel": "k_ck_overlap", "achieved": abytes / ov / 1e9, "peak": HBM_PEAK_GBS,
-            "unit": "GB/s", "frac": abytes / ov / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-            "algorithmic_bytes_per_launch": abytes, "kernel_ms": ov * 1e3, "rt_kernel_ms": float(np.mean(rt_ms)),
-            "note": "second bound (fp64 VALU of the per-lane G-way merge) dominates; see second_bound and DESIGN.md 4.1"}
-    if valu:
-        # the kernel's own limit: wave64 VALU instructions issued (SQ_INSTS_VALU of the committed PMC pass, per launch)
-        # against what the chip can issue -- one wave64 fp64 instruction per SIMD every 4 clocks
-        props = torch.cuda.get_device_properties(dev)
-        n_simd = props.multi_processor_count * 4
-        clk_hz = 2.4e9                                                    # MI355X peak engine clock (MI355X_MICROARCH.md)
-        peak = n_simd * clk_hz / 4.0
-        roof["second_bound"] = {"bound": "valu_issue", "insts_per_launch": valu, "achieved": valu / ov / 1e9,
-                                "peak": peak / 1e9, "unit": "G wave-instructions/s", "frac": valu / ov / peak,
-                                "source": "SQ_INSTS_VALU of the committed rocprofv3 --pmc pass (profiles/pmc_traffic.json, not this run) / live kernel time"}
+    roof = None
+    if args.full:
+        ov = float(np.mean(ov_ms)) * 1e-3
+        abytes = algorithmic_bytes(W, G, S, L, NP, NT, P, 1)
+        traffic = None
+        valu = None
+        traffic_src = None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                key = f"W{W}_G{G}_S{S}_L{L}"
+                traffic = tj.get(key, {}).get("ck_overlap_hbm_bytes_per_launch")
+                valu = tj.get(key, {}).get("valu_insts_per_launch")
+                traffic_src = ("profiles/pmc_traffic.json: committed rocprofv3 --pmc pass (run %s), NOT measured in this run"
+                               % tj.get(key, {}).get("profile", "?"))
+            except Exception:
+                traffic = None
+        roof = {"bound": "hbm", "kernel": "k_ck_overlap", "achieved": abytes / ov / 1e9, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": abytes / ov / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": abytes, "kernel_ms": ov * 1e3, "rt_kernel_ms": float(np.mean(rt_ms)),
+                "note": "second bound (fp64 VALU of the per-lane G-way merge) dominates; see second_bound and DESIGN.md 4.1"}
+        if valu:
+            # the kernel's own limit: wave64 VALU instructions issued (SQ_INSTS_VALU of the committed PMC pass, per launch)
+            # against what the chip can issue -- one wave64 fp64 instruction per SIMD every 4 clocks
+            props = torch.cuda.get_device_properties(dev)
+            n_simd = props.multi_processor_count * 4
+            clk_hz = 2.4e9                                                    # MI355X peak engine clock (AMD's published figure)
+            peak = n_simd * clk_hz / 4.0
+            roof["second_bound"] = {"bound": "valu_issue", "insts_per_launch": valu, "achieved": valu / ov / 1e9,
+                                    "peak": peak / 1e9, "unit": "G wave-instructions/s", "frac": valu / ov / peak,
+                                    "source": "SQ_INSTS_VALU of the committed rocprofv3 --pmc pass (profiles/pmc_traffic.json, not this run) / live kernel time"}
 
     # ---- CPU baseline: the oracle (port) on a bounded sample, rank 0 only ---------------------------------
     cpu = None
@@ -657,7 +672,7 @@ def main():
                                 f"{Wc} wavenumbers, {time.perf_counter() - t0:.1f} s); error relative to each column's maximum")
 
     extras = None
-    if world == 1 and not args.no_extras and (W, G, S, L) == (10000, 20, 8, 100):
+    if args.full and world == 1 and not args.no_extras and (W, G, S, L) == (10000, 20, 8, 100):
         extras = run_extras(torch, dev, eng, syn, atm, NLAYIN, LAYINC, SCALE, EMTEMP, WAVE, delg, do_cpu, K_sample, PRESS, TEMP, model)
 
     line = {

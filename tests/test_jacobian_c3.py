@@ -505,7 +505,7 @@ def test_bench_prints_one_json_line_under_torch_distributed_run():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr", "127.0.0.1", "--master-port", "29641", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
+                        "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline",
                         "--waves", "2048", "--jac-models", "21"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -530,7 +530,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", ANSFM_BENCH_REHEARSAL="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", "29643", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline",
                         "--waves", "2000", "--jac-models", "21"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -541,3 +541,46 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
     j = d["jacobian"]
     assert j["kk_shape"] == [2000, 20] and "spectral axis" in j["sharding"] and "REHEARSAL" in j["collective"]
     assert j["dedup_bit_identical"] is True and j["layer_opacities_computed_rank0"] < j["layer_opacities_all_rank0"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_spectrum_of_its_last_step(tmp_path):
+    """bench.py without --full: the headline keys only (the measurements --full adds are null), and --dump-outputs writes the
+    spectrum of the last timed step -- the same bits on a second run with the same arguments, and the spectrum the engine
+    gives for that step's model (index (steps - 1) % jac_models) through its host entry point."""
+    import json
+    import torch
+    import archnemesis_dist_amd as pkg
+    from archnemesis_dist_amd import synthetic as syn
+    sys.path.insert(0, ROOT)
+    from bench import torch_ktable
+    W, steps, nj = 2048, 3, 21
+    spec = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--waves", str(W), "--jac-models", str(nj), "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:2000]
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["jacobian"] is None and d["extras"] is None
+        spec.append(np.load(tmp_path / run / "spectrum.npy"))
+    assert spec[0].shape == (1, W, 1) and spec[0].dtype == np.float64 and np.all(spec[0] > 0)
+    assert np.array_equal(spec[0], spec[1])
+    # the inputs of that step, as bench.py builds them
+    G, S, L, NP, NT = 20, 8, 100, 20, 15
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    PRESS, TEMP, K = torch_ktable(torch, torch.device("cuda", 0), W, G, NP, NT, S, seed=20260704)
+    atm = syn.synth_atmosphere(L, S, seed=7, n_models=nj, perturb=0.05)
+    NLAYIN, LAYINC, SCALE = syn.nadir_path(L)
+    EMTEMP = atm["lay_temp"][:, LAYINC[:, 0]][:, :, None]
+    m = (steps - 1) % nj
+    eng = pkg.AnsfmEngine(0)
+    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), 200.0 + 0.1 * np.arange(W),
+                      delg.astype(np.float32))
+    ref = eng.cirsrad_ck_thermal(0, atm["lay_press_pa"][m], atm["lay_temp"][m], atm["amount"][m], syn.synth_continuum(W, L)[0],
+                                 NLAYIN, LAYINC, SCALE, EMTEMP[m], -1.0)
+    eng.close()
+    np.testing.assert_allclose(spec[0][0], ref, rtol=1e-12, atol=0)
