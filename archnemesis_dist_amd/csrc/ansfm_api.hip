@@ -85,12 +85,14 @@ struct ansfm_ctx {
     DevBuf ms_taus, ms_omegas, ms_bnu;   // scattering branch of CIRSrad: TAUTOT / OMEGA (W,G,L) and BB (W,L) in HBM
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
+    long ms_windows = 0, ms_window_w = 0;          // spectral windows of phase matrices / Hansen factors of the last scattering call, their size
     DevBuf hb[24];  // staging buffers of the host-pointer entry points
     int last_n = 0, last_L = 0;
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;
     hipStream_t ms_stream2 = nullptr;   // chains of the odd g-ordinates: consecutive chain launches overlap their tails
+    hipStream_t ms_stream3 = nullptr;   // G = 1 windows: phase matrices two windows ahead of the chains
     std::vector<hipEvent_t> ms_ev;
     // timing of the last cirsrad call
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -166,6 +168,7 @@ void ansfm_destroy(ansfm_ctx *ctx)
     for (auto &e : ctx->ms_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->ms_stream) (void)hipStreamDestroy(ctx->ms_stream);
     if (ctx->ms_stream2) (void)hipStreamDestroy(ctx->ms_stream2);
+    if (ctx->ms_stream3) (void)hipStreamDestroy(ctx->ms_stream3);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -592,6 +595,19 @@ static int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W,
 
 static int lbl_prep_fwd(ansfm_ctx *ctx, int n_layers, const double *lay_press, const double *lay_temp, double press_div,
                         int with_grad);
+
+// ILBL = LINE_BY_LINE_TABLES in the scattering entries: tau[rows][1][Wpad] = sum_gas k*amount (:3795-3817), the layout
+// launch_overlap leaves for G = 1; amount [S][rows] (device, device pointers throughout)
+static int lbl_tau_rows(ansfm_ctx *ctx, int rows, const double *press, const double *temp, const double *amount)
+{
+    int rc;
+    if ((rc = lbl_prep_fwd(ctx, rows, press, temp, 101325.0, 0))) return rc;
+    hipLaunchKernelGGL(k_lbl_tau, dim3(nblk((size_t)rows * ctx->Wpad, 256)), dim3(256), 0, ctx->stream, ctx->lnK.as<double>(),
+                       ctx->Wpad, ctx->NT, ctx->S, rows, 1, ctx->lbl_li.as<LblInterp>(), amount, ctx->tau.as<double>(),
+                       (double *)nullptr);
+    HIPCHK(hipGetLastError());
+    return ANSFM_OK;
+}
 
 // src[W][X1][X2] -> dst[(x1, x2) or, swap12, (x2, x1)][Wpad] through a 32 x 32 LDS tile (k_transpose_w_last): both sides move
 // whole 256-byte segments.  The element-per-thread version read with a stride of X1 * X2 doubles: 0.18 TB/s, 17.7 of the
@@ -1119,7 +1135,6 @@ int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_singlescatt: upload a k-table first");
-    if (ctx->is_lbl) FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_singlescatt: k-tables only (ILBL = K_TABLES)");
     if (L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !tausca || !phase || !NLAYIN || !LAYINC ||
         !SCALE || !EMTEMP || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT || (ISPACE != 0 && ISPACE != 1) ||
         (TSURF > 0.0 && !EMISSIVITY))
@@ -1153,7 +1168,10 @@ int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     HIPCHK(ctx->li.reserve((size_t)L * sizeof(LayerInterp)));
     HIPCHK(ctx->tau.reserve((size_t)L * G * Wpad * D));
-    for (int pass = 0; pass < 2; ++pass) {
+    if (ctx->is_lbl) {   // LBL tables: G = 1, DELG = {1}
+        if ((rc = lbl_tau_rows(ctx, L, (const double *)d[0], (const double *)d[1], (const double *)d[2]))) return rc;
+    }
+    for (int pass = 0; pass < 2 && !ctx->is_lbl; ++pass) {
         ctx->force_generic = pass;
         hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)L, 128)), dim3(128), 0, ctx->stream, L, (const double *)d[0],
                            (const double *)d[1], ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
@@ -2226,6 +2244,73 @@ static int ms_pad_inputs(ansfm_ctx *ctx, int nmu, size_t radg_rows, size_t W, in
     return ANSFM_OK;
 }
 
+// G = 1 (LBL tables, or a k-table of one g-ordinate): wavenumbers per window of phase matrices and Hansen factors.  The larger
+// of 4096 and W / 16, in tiles of 64 (the lane kernels'), at most what keeps one window's buffers under kMsWindowBudget;
+// ANSFM_MS_WINDOW=<wavenumbers> overrides (tests, A/B timing).  >= W: one window, the schedule of a single g-ordinate.
+static const size_t kMsWindowBudget = (size_t)2 << 30;
+static long ms_window_size(long W, int nf, int ncomp, int nmu)
+{
+    const size_t per_w = (size_t)(2 * (nf + 1) + 1) * ncomp * nmu * nmu * sizeof(double);   // ppl + pmi + fc of one wavenumber
+    long nwin = std::max<long>(4096, (W + 15) / 16);
+    nwin = (nwin + 63) / 64 * 64;
+    nwin = std::min(nwin, std::max<long>(64, (long)(kMsWindowBudget / per_w) / 64 * 64));
+    if (const char *ev = getenv("ANSFM_MS_WINDOW")) { const long v = atol(ev); if (v >= 1) nwin = v; }
+    return std::min(nwin, W);
+}
+
+// the walk's kernel by quadrature size: 16 (the matrix-core chain's), 5 (the reference's default, Scatter_0.py:59), 4, 6, 8;
+// any other size takes the run-time build.  One block per scattering component in use.
+static void ms_launch_hansen(hipStream_t st, const MsParams &pp)
+{
+    const dim3 hg((unsigned)(pp.ncont + (pp.iray > 0 ? 1 : 0))), hb(64);
+    switch (pp.nmu) {
+    case 16: hipLaunchKernelGGL(k_ms_hansen_seq<16>, hg, hb, 0, st, pp); break;
+    case 4: hipLaunchKernelGGL(k_ms_hansen_seq<4>, hg, hb, 0, st, pp); break;
+    case 5: hipLaunchKernelGGL(k_ms_hansen_seq<5>, hg, hb, 0, st, pp); break;
+    case 6: hipLaunchKernelGGL(k_ms_hansen_seq<6>, hg, hb, 0, st, pp); break;
+    case 8: hipLaunchKernelGGL(k_ms_hansen_seq<8>, hg, hb, 0, st, pp); break;
+    default: hipLaunchKernelGGL(k_ms_hansen_seq<0>, hg, hb, 0, st, pp); break;
+    }
+}
+
+// phase matrices of the wavenumbers [pw.pw0, pw.pw0 + pw.nwin) (Rayleigh in slot ncont even when there are no aerosols)
+static void ms_launch_phase(hipStream_t st, const MsParams &pw)
+{
+    const size_t lds = pw.phase_tab ? (size_t)(pw.nf + 2) * (pw.nphi + 1) * sizeof(double) : 0;
+    if (pw.ncont > 0) hipLaunchKernelGGL(k_ms_phase, dim3((unsigned)pw.nwin, (unsigned)pw.ncont), dim3(256), lds, st, pw);
+    if (pw.iray > 0) {
+        MsParams pr = pw;
+        pr.phase_comp0 = pw.ncont;
+        hipLaunchKernelGGL(k_ms_phase, dim3((unsigned)pw.nwin, 1), dim3(256), lds, st, pr);
+    }
+}
+
+// whatever way a scheduling function is left -- an error return of any launch included -- the main stream waits for the two
+// side streams, so that the next entry point cannot reuse ctx->misc / tmp_* while a side stream still reads or writes them
+struct MsRejoin {
+    ansfm_ctx *c; int e1, e2, e3 = -1; bool done = false;      // e3 >= 0: ms_stream3 too
+    void now()
+    {
+        if (done) return;
+        done = true;
+        if (hipEventRecord(c->ms_ev[e1], c->ms_stream) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ms_ev[e1], 0);
+        if (hipEventRecord(c->ms_ev[e2], c->ms_stream2) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ms_ev[e2], 0);
+        if (e3 >= 0 && hipEventRecord(c->ms_ev[e3], c->ms_stream3) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ms_ev[e3], 0);
+    }
+    ~MsRejoin() { now(); }
+};
+static int ms_side_streams(ansfm_ctx *ctx, int nev)
+{
+    if (!ctx->ms_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->ms_stream, hipStreamNonBlocking));
+    if (!ctx->ms_stream2) HIPCHK(hipStreamCreateWithFlags(&ctx->ms_stream2, hipStreamNonBlocking));
+    while ((int)ctx->ms_ev.size() < nev) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->ms_ev.push_back(e);
+    }
+    return ANSFM_OK;
+}
+
 static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth, int ngeom, const double *sol_angs,
                      const double *emiss_angs, const double *aphis, int lowbc, int nmu, const double *mu1, const double *wt1,
                      int nf, int ng, int nlay, int nphi, int iray, int imie, bool prepare_only = false)
@@ -2253,75 +2338,106 @@ static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth,
     const size_t nn = (size_t)nmu * nmu;
     const size_t nph = (size_t)nwave * (nf + 1) * p.ncomp * nn;
     const size_t nfc = (size_t)ng * nwave * p.ncomp * nn;
-    HIPCHK(ctx->misc.reserve((2 * nph + nfc) * D));
-    HIPCHK(ctx->tmp_in2.reserve((size_t)nwave * ng * (nf + 1) * ngeom * D));
-    HIPCHK(ctx->tmp_out.reserve((size_t)ngeom * ng * nwave * D));
-    // reuse: the models of a batch run one by one (ansfm_cirsrad_ck_scatter_batch without the layer cache) share the phase
-    // functions, so the phase matrices and the Hansen factors the first model left in ctx->misc stand for the others -- the
-    // walk is sequential and, at few streams, most of a call
-    const bool reuse = ctx->ms_reuse_walk != 0 && !prepare_only;
-    if (!reuse) HIPCHK(hipMemsetAsync(ctx->misc.p, 0, (2 * nph + nfc) * D, ctx->stream));
-    p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph; p.fc = p.pmi + nph;
-    p.drad = ctx->tmp_in2.as<double>();
-    p.rad = ctx->tmp_out.as<double>();
     const int ncomp_run = ncont + (iray > 0 ? 1 : 0);
     p.ig0 = 0; p.ng_launch = ng;
+    p.pw0 = 0; p.nwin = nwave; p.carry_in = 0; p.carry = nullptr;      // one window: the whole axis
     size_t phase_lds_bytes = (size_t)(nf + 2) * (nphi + 1) * D;       // cos(ic phi_k) for every order and azimuth point
     p.phase_tab = phase_lds_bytes <= 48 * 1024 ? 1 : 0;
     if (!p.phase_tab) phase_lds_bytes = 0;
-    if (ncomp_run > 0 && !reuse) {
-        // Rayleigh lives in slot ncont even when there are no aerosols
-        if (ncont > 0)
-            hipLaunchKernelGGL(k_ms_phase, dim3((unsigned)nwave, (unsigned)ncont), dim3(256), phase_lds_bytes, ctx->stream, p);
-        if (iray > 0) {
-            MsParams pr = p;
-            pr.phase_comp0 = ncont;
-            hipLaunchKernelGGL(k_ms_phase, dim3((unsigned)nwave, 1), dim3(256), phase_lds_bytes, ctx->stream, pr);
-        }
+    p.hansen_comp0 = 0;
+    HIPCHK(ctx->tmp_in2.reserve((size_t)nwave * ng * (nf + 1) * ngeom * D));
+    HIPCHK(ctx->tmp_out.reserve((size_t)ngeom * ng * nwave * D));
+    p.drad = ctx->tmp_in2.as<double>();
+    p.rad = ctx->tmp_out.as<double>();
+    // G = 1: the phase matrices and Hansen factors of a window of wavenumbers at a time (ms_window_size).  The
+    // batch path (prepare_only) makes its spectral slabs the windows and launches their phase matrices and walk itself.
+    const long nwin = (ng == 1) ? ms_window_size(nwave, nf, p.ncomp, nmu) : nwave;
+    if (ng == 1 && prepare_only) return ANSFM_OK;
+    const bool windowed = nwin < nwave;
+    ctx->ms_windows = (nwave + nwin - 1) / nwin; ctx->ms_window_w = nwin;
+    // reuse: the models of a batch run one by one (ansfm_cirsrad_ck_scatter_batch without the layer cache) share the phase
+    // functions, so the phase matrices and the Hansen factors the first model left in ctx->misc stand for the others -- the
+    // walk is sequential and, at few streams, most of a call.  Not with several windows: ctx->misc holds the last two only.
+    const bool reuse = ctx->ms_reuse_walk != 0 && !prepare_only && !windowed;
+    // three windows in rotation and the carry of the walk between them, or the whole axis
+    const size_t nph_w = (size_t)nwin * (nf + 1) * p.ncomp * nn, nfc_w = (size_t)nwin * p.ncomp * nn;
+    const size_t per_buf = 2 * nph_w + nfc_w;
+    const size_t misc_n = windowed ? 3 * per_buf + (size_t)p.ncomp * nn : 2 * nph + nfc;
+    HIPCHK(ctx->misc.reserve(misc_n * D));
+    if (!reuse) HIPCHK(hipMemsetAsync(ctx->misc.p, 0, misc_n * D, ctx->stream));
+    p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph; p.fc = p.pmi + nph;
+    if (ncomp_run > 0 && !reuse && !windowed) {
+        ms_launch_phase(ctx->stream, p);
         HIPCHK(hipGetLastError());
     }
-    p.hansen_comp0 = 0;
-    // the walk's kernel by quadrature size: 16 (the matrix-core chain's), 5 (the reference's default, Scatter_0.py:59), 4, 6, 8;
-    // any other size takes the run-time build
-    auto launch_hansen = [&](hipStream_t st, const MsParams &pp) {
-        const dim3 hg((unsigned)ncomp_run), hb(64);
-        switch (nmu) {
-        case 16: hipLaunchKernelGGL(k_ms_hansen_seq<16>, hg, hb, 0, st, pp); break;
-        case 4: hipLaunchKernelGGL(k_ms_hansen_seq<4>, hg, hb, 0, st, pp); break;
-        case 5: hipLaunchKernelGGL(k_ms_hansen_seq<5>, hg, hb, 0, st, pp); break;
-        case 6: hipLaunchKernelGGL(k_ms_hansen_seq<6>, hg, hb, 0, st, pp); break;
-        case 8: hipLaunchKernelGGL(k_ms_hansen_seq<8>, hg, hb, 0, st, pp); break;
-        default: hipLaunchKernelGGL(k_ms_hansen_seq<0>, hg, hb, 0, st, pp); break;
+    auto launch_hansen = [&](hipStream_t st, const MsParams &pp) { ms_launch_hansen(st, pp); };
+    // window k of a windowed call: buffer k % 3, chains over [pw0, pw0 + wc) read taus / omegas / bnu relative to w0
+    auto window_params = [&](int k) {
+        MsParams pw = p;
+        const int b = k % 3;
+        pw.pw0 = (int)(k * nwin); pw.nwin = (int)std::min<long>(nwin, nwave - (long)k * nwin);
+        pw.ppl = ctx->misc.as<double>() + b * per_buf; pw.pmi = pw.ppl + nph_w; pw.fc = pw.pmi + nph_w;
+        pw.carry = ctx->misc.as<double>() + 3 * per_buf; pw.carry_in = k > 0 ? 1 : 0;
+        pw.w0 = pw.pw0; pw.wcount = pw.nwin;
+        pw.taus = p.taus + (size_t)pw.pw0 * ng * nlay; pw.omegas = p.omegas + (size_t)pw.pw0 * ng * nlay;
+        pw.bnu = p.bnu + (size_t)pw.pw0 * nlay;
+        return pw;
+    };
+    // G = 1, several windows, three stages in flight: window k's chains (main stream or beside it, alternating as the
+    // g-ordinates of per_g_ordinate), window k + 1's walk (side stream) and window k + 2's phase matrices (third stream).  The
+    // walk never queues behind phase matrices: those share the chip with the chains and take about as long.  Events, buffer
+    // b = k % 3: ev[b] walked, ev[3 + b] chains done (window k + 3's phase matrices overwrite the buffer only then),
+    // ev[6 + b] phase matrices done; ev[9] inputs ready; ev[10 .. 12] rejoin.
+    auto by_window = [&](auto chain_of) -> int {
+        int rc = ms_side_streams(ctx, 13);
+        if (rc) return rc;
+        if (!ctx->ms_stream3) HIPCHK(hipStreamCreateWithFlags(&ctx->ms_stream3, hipStreamNonBlocking));
+        HIPCHK(hipEventRecord(ctx->ms_ev[9], ctx->stream));
+        HIPCHK(hipStreamWaitEvent(ctx->ms_stream, ctx->ms_ev[9], 0));
+        HIPCHK(hipStreamWaitEvent(ctx->ms_stream2, ctx->ms_ev[9], 0));
+        HIPCHK(hipStreamWaitEvent(ctx->ms_stream3, ctx->ms_ev[9], 0));
+        MsRejoin rejoin{ctx, 10, 11, 12};
+        const int nw = (int)ctx->ms_windows;
+        auto phase = [&](int k) -> int {
+            const int b = k % 3;
+            if (k >= 3) HIPCHK(hipStreamWaitEvent(ctx->ms_stream3, ctx->ms_ev[3 + b], 0));
+            if (ncomp_run > 0) ms_launch_phase(ctx->ms_stream3, window_params(k));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->ms_ev[6 + b], ctx->ms_stream3));
+            return ANSFM_OK;
+        };
+        auto walk = [&](int k) -> int {
+            const int b = k % 3;
+            HIPCHK(hipStreamWaitEvent(ctx->ms_stream, ctx->ms_ev[6 + b], 0));
+            if (ncomp_run > 0) ms_launch_hansen(ctx->ms_stream, window_params(k));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->ms_ev[b], ctx->ms_stream));
+            return ANSFM_OK;
+        };
+        if ((rc = phase(0)) || (nw > 1 && (rc = phase(1))) || (rc = walk(0))) return rc;
+        for (int k = 0; k < nw; ++k) {
+            if (k + 1 < nw && (rc = walk(k + 1))) return rc;
+            if (k + 2 < nw && (rc = phase(k + 2))) return rc;
+            hipStream_t cs = (k & 1) ? ctx->ms_stream2 : ctx->stream;
+            HIPCHK(hipStreamWaitEvent(cs, ctx->ms_ev[k % 3], 0));
+            chain_of(cs, window_params(k));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ctx->ms_ev[3 + k % 3], cs));
         }
+        rejoin.now();
+        return ANSFM_OK;
     };
     // The Hansen walk is sequential over (g, wave) -- two waves on the whole chip -- so it is cut into one launch per
     // g-ordinate on a second stream and the chains of g start as soon as its factors exist: the walk of g + 1 hides behind
     // them.  chain_of(g, stream, params of that g-ordinate) launches the chains of one g-ordinate.
     auto per_g_ordinate = [&](auto chain_of) -> int {
-        if (!ctx->ms_stream) HIPCHK(hipStreamCreateWithFlags(&ctx->ms_stream, hipStreamNonBlocking));
-        if (!ctx->ms_stream2) HIPCHK(hipStreamCreateWithFlags(&ctx->ms_stream2, hipStreamNonBlocking));
-        while ((int)ctx->ms_ev.size() < ng + 3) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ctx->ms_ev.push_back(e);
-        }
+        const int rc = ms_side_streams(ctx, ng + 3);
+        if (rc) return rc;
         HIPCHK(hipEventRecord(ctx->ms_ev[ng], ctx->stream));                    // phase matrices (and every input) ready
         HIPCHK(hipStreamWaitEvent(ctx->ms_stream, ctx->ms_ev[ng], 0));
         HIPCHK(hipStreamWaitEvent(ctx->ms_stream2, ctx->ms_ev[ng], 0));
-        // from here on work is queued on the side streams: whatever way this function is left -- an error return of any
-        // launch below included -- the main stream waits for them, so the next entry point cannot reuse ctx->misc / tmp_*
-        // while a side stream still reads or writes them
-        struct Rejoin {
-            ansfm_ctx *c; int ng; bool done = false;
-            void now()
-            {
-                if (done) return;
-                done = true;
-                if (hipEventRecord(c->ms_ev[ng + 1], c->ms_stream) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ms_ev[ng + 1], 0);
-                if (hipEventRecord(c->ms_ev[ng + 2], c->ms_stream2) == hipSuccess) (void)hipStreamWaitEvent(c->stream, c->ms_ev[ng + 2], 0);
-            }
-            ~Rejoin() { now(); }
-        } rejoin{ctx, ng};
+        // from here on work is queued on the side streams: the main stream waits for them however this function is left
+        MsRejoin rejoin{ctx, ng + 1, ng + 2};
         for (int g = 0; g < ng; ++g) {
             MsParams ph = p;
             ph.ig0 = g; ph.ng_launch = 1;
@@ -2370,7 +2486,10 @@ static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth,
             if (pp.phase_lds) hipLaunchKernelGGL(k_ms_chain16<true>, dim3(grid), dim3(64), lds16, st, pp);
             else hipLaunchKernelGGL(k_ms_chain16<false>, dim3(grid), dim3(64), lds16, st, pp);
         };
-        if (ncomp_run > 0 && !reuse) {
+        if (windowed) {
+            const int rc = by_window([&](hipStream_t cs, const MsParams &pc) { launch_chain((unsigned)pc.wcount, cs, pc); });
+            if (rc != ANSFM_OK) return rc;
+        } else if (ncomp_run > 0 && !reuse) {
             const int rc = per_g_ordinate([&](hipStream_t cs, const MsParams &pc) { launch_chain((unsigned)nwave, cs, pc); });
             if (rc != ANSFM_OK) return rc;
         } else {
@@ -2386,10 +2505,11 @@ static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth,
         const bool lane_off = lane_env && lane_env[0] == '0';
         const bool by_lane = !lane_off && (nmu == 4 || nmu == 5 || nmu == 6);
         const size_t ldsl = (size_t)(2 * nn + nmu) * 64 * D;
-        auto launch_chain_n = [&](dim3 grid, hipStream_t st, const MsParams &pp) {
+        // the chains of wc wavenumbers (pp.w0 ..) and ngl g-ordinates (pp.ig0 ..)
+        auto launch_chain_n = [&](size_t wc, unsigned ngl, hipStream_t st, const MsParams &pp) {
+            const dim3 grid((unsigned)(wc * ngl * (nf + 1)));
             if (by_lane) {
-                const unsigned ngl = (unsigned)(grid.x / ((unsigned)nwave * (unsigned)(nf + 1)));      // g-ordinates of this launch
-                const dim3 gl((unsigned)((nwave + 63) / 64) * ngl * (unsigned)(nf + 1));
+                const dim3 gl((unsigned)((wc + 63) / 64) * ngl * (unsigned)(nf + 1));
                 switch (nmu) {
                 case 4: hipLaunchKernelGGL(k_ms_chain_lane<4>, gl, dim3(64), ldsl, st, pp); break;
                 case 5: hipLaunchKernelGGL(k_ms_chain_lane<5>, gl, dim3(64), ldsl, st, pp); break;
@@ -2403,13 +2523,14 @@ static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth,
             default: hipLaunchKernelGGL(k_ms_chain<0>, grid, dim3(64), ldsg, st, pp); break;
             }
         };
-        if (ncomp_run > 0 && !reuse) {
-            const int rc = per_g_ordinate([&](hipStream_t cs, const MsParams &pc) {
-                launch_chain_n(dim3((unsigned)((size_t)nwave * (nf + 1))), cs, pc);
-            });
+        if (windowed) {
+            const int rc = by_window([&](hipStream_t cs, const MsParams &pc) { launch_chain_n((size_t)pc.wcount, 1, cs, pc); });
+            if (rc != ANSFM_OK) return rc;
+        } else if (ncomp_run > 0 && !reuse) {
+            const int rc = per_g_ordinate([&](hipStream_t cs, const MsParams &pc) { launch_chain_n((size_t)nwave, 1, cs, pc); });
             if (rc != ANSFM_OK) return rc;
         } else {
-            launch_chain_n(dim3((unsigned)((size_t)nwave * ng * (nf + 1))), ctx->stream, p);
+            launch_chain_n((size_t)nwave, (unsigned)ng, ctx->stream, p);
             HIPCHK(hipGetLastError());
         }
         const size_t tot = (size_t)nwave * ng * ngeom;
@@ -2470,7 +2591,6 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter: upload a k-table first");
-    if (ctx->is_lbl) FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter: k-tables only (ILBL = K_TABLES)");
     if (L <= 0 || !lay_press_pa || !lay_temp || !amount || ncont < 0 || ngeom <= 0 || nmu < 2 || nf < 0 || nphi <= 0 || !radg ||
         !sol_angs || !emiss_angs || !aphis || !solar || !brdf_matrix || !mu1 || !wt1 || !SPECOUT ||
         (ISPACE != 0 && ISPACE != 1) || (ncont > 0 && (!phasarr || !lfrac || nth < 3)))
@@ -2509,7 +2629,10 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
         HIPCHK(hipMemsetAsync(ctx->cont_t.p, 0, WL * D, ctx->stream));
         d_tauray = ctx->cont_t.as<double>();
     }
-    for (int pass = 0; pass < 2; ++pass) {
+    if (ctx->is_lbl) {   // LBL tables: G = 1, DELG = {1}
+        if ((rc = lbl_tau_rows(ctx, L, (const double *)d[0], (const double *)d[1], (const double *)d[2]))) return rc;
+    }
+    for (int pass = 0; pass < 2 && !ctx->is_lbl; ++pass) {
         ctx->force_generic = pass;       // pass 1 only if the fast merge met an unsorted k-distribution
         hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)L, 128)), dim3(128), 0, ctx->stream, L, (const double *)d[0],
                            (const double *)d[1], ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
@@ -2572,7 +2695,6 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter_batch: upload a k-table first");
-    if (ctx->is_lbl) FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter_batch: k-tables only (ILBL = K_TABLES)");
     if (n_models <= 0 || L <= 0 || !lay_press_pa || !lay_temp || !amount || ncont < 0 || ngeom <= 0 || nmu < 2 || nf < 0 ||
         nphi <= 0 || !radg || !sol_angs || !emiss_angs || !aphis || !solar || !brdf_matrix || !mu1 || !wt1 || !SPECOUT ||
         (ISPACE != 0 && ISPACE != 1) || (ncont > 0 && (!phasarr || !lfrac || nth < 3)))
@@ -2647,7 +2769,10 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     HIPCHK(hipGetLastError());
     HIPCHK(ctx->li.reserve((size_t)rows * sizeof(LayerInterp)));
     HIPCHK(ctx->tau.reserve((size_t)rows * G * Wpad * D));
-    for (int pass = 0; pass < 2; ++pass) {
+    if (ctx->is_lbl) {   // LBL tables: G = 1, DELG = {1}; the distinct rows only
+        if ((rc = lbl_tau_rows(ctx, rows, pw, tw, aw))) return rc;
+    }
+    for (int pass = 0; pass < 2 && !ctx->is_lbl; ++pass) {
         ctx->force_generic = pass;
         HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
         hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream, rows, (const double *)pw,
@@ -2722,6 +2847,32 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
                         imie, true)))
         return rc;
     const int nmu_k = pad16 ? 16 : nmu;                         // the stream count the kernels run with
+    // G = 1: the slabs of the spectral axis are the windows of phase matrices and Hansen factors (ms_window_size): a slab's
+    // phase matrices and walk -- continuing from the carry of the slab before -- go in front of its chains, model 0's first
+    const bool win = G == 1;
+    const long nwin_b = win ? ms_window_size(W, nf, p.ncomp, nmu_k) : W;
+    const int ncomp_run = ncont + (iray > 0 ? 1 : 0);
+    auto window_buffers = [&](long Ws) -> int {
+        ctx->ms_windows = (W + Ws - 1) / Ws; ctx->ms_window_w = Ws;
+        if (!win) return ANSFM_OK;
+        const size_t nn = (size_t)nmu_k * nmu_k;
+        const size_t nph_w = (size_t)Ws * (nf + 1) * p.ncomp * nn, n_all = 2 * nph_w + (size_t)Ws * p.ncomp * nn + p.ncomp * nn;
+        HIPCHK(ctx->misc.reserve(n_all * D));
+        HIPCHK(hipMemsetAsync(ctx->misc.p, 0, n_all * D, ctx->stream));
+        p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph_w; p.fc = p.pmi + nph_w; p.carry = p.fc + (size_t)Ws * p.ncomp * nn;
+        return ANSFM_OK;
+    };
+    auto slab_window = [&](long w0, int wc) -> int {
+        if (!win) return ANSFM_OK;
+        p.pw0 = (int)w0; p.nwin = wc; p.carry_in = w0 > 0 ? 1 : 0;
+        p.ig0 = 0; p.ng_launch = 1;
+        if (ncomp_run > 0) {
+            ms_launch_phase(ctx->stream, p);
+            ms_launch_hansen(ctx->stream, p);
+        }
+        HIPCHK(hipGetLastError());
+        return ANSFM_OK;
+    };
     if (nmu_k != 16) {
         // ---- other stream counts.  Few streams (4 / 5 / 6): one lane per chain (ansfm_ms_lane.hip.h), the cache per tile of
         //      64 wavenumbers; otherwise the wavefront-per-chain kernel (k_ms_chain<N, CACHE>), the cache per wavenumber.
@@ -2738,7 +2889,8 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         long tiles = (long)(budget / per_tile);
         if (const char *ev = getenv("ANSFM_MS_SLAB")) { const long v = atol(ev); if (v >= 1) tiles = std::min(tiles, (v + 63) / 64); }
         if (tiles < 1) FAIL(ANSFM_ERR_HIP, "cirsrad_ck_scatter_batch: no memory for the layer cache of one tile of wavenumbers");
-        const long Ws = std::min<long>((long)W, tiles * 64);
+        const long Ws = std::min<long>(std::min<long>((long)W, tiles * 64), nwin_b);
+        if ((rc = window_buffers(Ws))) return rc;
         int mchunk = std::min(n_models - 1, 64);
         if (const char *ev = getenv("ANSFM_MS_CHUNK")) { const int v = atoi(ev); if (v >= 1) mchunk = std::min(n_models - 1, v); }
         HIPCHK(ctx->ms_cache.reserve((size_t)((Ws + 63) / 64) * per_tile));
@@ -2778,6 +2930,7 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         for (long w0 = 0; w0 < W; w0 += Ws) {
             const int wc = (int)std::min<long>(Ws, W - w0);
             const size_t per_model = (lane_n ? (size_t)((wc + 63) / 64) : (size_t)wc) * G * (nf + 1);
+            if ((rc = slab_window(w0, wc))) return rc;
             p.w0 = (int)w0; p.wcount = wc;
             o.w0 = (int)w0; o.wcount = wc;
             o.m0 = 0; o.nm = 1; o.model_ids = nullptr;
@@ -2822,6 +2975,8 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     if (const char *ev = getenv("ANSFM_MS_SLAB")) { const long v = atol(ev); if (v >= 1) Ws = std::min(Ws, v); }
     if (Ws < 1) FAIL(ANSFM_ERR_HIP, "cirsrad_ck_scatter_batch: no memory for the layer cache of one wavenumber");
     if (Ws > W) Ws = W;
+    Ws = std::min(Ws, nwin_b);
+    if ((rc = window_buffers(Ws))) return rc;
     int mchunk = std::min(n_models - 1, 64);
     if (const char *ev = getenv("ANSFM_MS_CHUNK")) { const int v = atoi(ev); if (v >= 1) mchunk = std::min(n_models - 1, v); }
     HIPCHK(ctx->ms_cache.reserve((size_t)Ws * per_w_layers));
@@ -2849,6 +3004,7 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     const size_t lds16 = (4 * 16 * 17 + 5 * 16) * D;
     for (long w0 = 0; w0 < W; w0 += Ws) {
         const int wc = (int)std::min<long>(Ws, W - w0);
+        if ((rc = slab_window(w0, wc))) return rc;
         p.w0 = (int)w0; p.wcount = wc;
         o.w0 = (int)w0; o.wcount = wc;
         // model 0: the ordinary chain, which also fills the cache
@@ -2888,6 +3044,14 @@ int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, i
     if (!ctx) return ANSFM_ERR_INVALID;
     if (layers_from_cache) *layers_from_cache = ctx->ms_cache_hits;
     if (layers_total) *layers_total = ctx->ms_cache_layers;
+    return ANSFM_OK;
+}
+
+int ansfm_last_scatter_windows(const ansfm_ctx *ctx, int64_t *windows, int64_t *window_wavenumbers)
+{
+    if (!ctx) return ANSFM_ERR_INVALID;
+    if (windows) *windows = ctx->ms_windows;
+    if (window_wavenumbers) *window_wavenumbers = ctx->ms_window_w;
     return ANSFM_OK;
 }
 

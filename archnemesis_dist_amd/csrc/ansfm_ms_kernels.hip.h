@@ -39,8 +39,8 @@ struct MsParams {
     const double *omegas;    // [nwave][ng][nlay]
     const double *lfrac;     // [nwave][ncont][nlay]
     // workspaces / outputs
-    double *ppl, *pmi;       // [nwave][nf+1][ncomp][nmu*nmu]   raw azimuth integrals
-    double *fc;              // [ng][nwave][ncomp][nmu*nmu]     Hansen factors in the reference's loop order
+    double *ppl, *pmi;       // [nwin][nf+1][ncomp][nmu*nmu]    raw azimuth integrals   (wavenumbers pw0 .. pw0 + nwin - 1)
+    double *fc;              // [ng][nwin][ncomp][nmu*nmu]      Hansen factors in the reference's loop order
     double *drad;            // [nwave][ng][nf+1][ngeom]
     double *rad;             // [ngeom][ng][nwave]
     int ncont, ncomp, nwave, nth, ngeom, lowbc, nmu, nf, ng, nlay, nphi, iray, imie;
@@ -71,6 +71,12 @@ struct MsParams {
     // 1 / 0, the phase matrices, the surface operator and the boundary radiance zero there: every operator is block diagonal with
     // the quadrature's block in front and a block that couples to nothing behind it
     int nmu_real;
+    // Spectral window (G = 1, ms_launch): ppl / pmi / fc hold the wavenumbers [pw0, pw0 + nwin) only and every reader indexes
+    // them relative to pw0 (pw0 = 0, nwin = nwave: the whole axis).  k_ms_hansen_seq continues from carry [ncomp][nmu*nmu] --
+    // the factors of the last step of the previous window -- when carry_in is set, and leaves its own last factors there when
+    // carry is set.
+    int pw0, nwin, carry_in;
+    double *carry;
 };
 
 // radg [rows][nr] -> [rows][16]: the chain kernels read it back to front (radg[:, ::-1], :765), so the quadrature's values go to
@@ -114,7 +120,7 @@ constexpr int kMsPhaseOrders = 9;     // Fourier orders accumulated per pass ove
 __global__ __launch_bounds__(256) void k_ms_phase(MsParams p)
 {
     extern __shared__ double ctab[];            // [nf + 2][nphi + 1]: cos(ic phi_k); the last row is cos(phi_k)
-    const int widx = blockIdx.x, comp = blockIdx.y + p.phase_comp0;  // comp == ncont -> Rayleigh
+    const int wl = blockIdx.x, widx = p.pw0 + wl, comp = blockIdx.y + p.phase_comp0;  // comp == ncont -> Rayleigh; wl: in the window
     const int n = p.nmu, nn = n * n, tid = threadIdx.x;
     const double pi = 3.141592653589793;
     const double dphi = 2.0 * pi / p.nphi;
@@ -138,8 +144,8 @@ __global__ __launch_bounds__(256) void k_ms_phase(MsParams p)
         const int i = e / n, j = e % n;
         if (i >= nr || j >= nr) {               // beyond the quadrature (a smaller one padded to 16 streams): nothing scatters there
             for (int ic = 0; ic <= p.nf; ++ic) {
-                p.ppl[(((size_t)widx * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
-                p.pmi[(((size_t)widx * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
+                p.ppl[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
+                p.pmi[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
             }
             continue;
         }
@@ -187,8 +193,8 @@ __global__ __launch_bounds__(256) void k_ms_phase(MsParams p)
             for (int o = 0; o < kMsPhaseOrders; ++o) {
                 const int ic = ic0 + o;
                 if (ic <= p.nf) {
-                    p.ppl[(((size_t)widx * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = spl[o];
-                    p.pmi[(((size_t)widx * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = smi[o];
+                    p.ppl[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = spl[o];
+                    p.pmi[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = smi[o];
                 }
             }
         }
@@ -295,17 +301,21 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
             if (FULL || CLAMP || e < nn) { ppl_s[e] = ring[d][r]; pmi_s[e] = ring[d][NE + r]; }
         }
     };
-    // the walk of this launch: g-ordinates [ig0, ig0 + ng_launch), continuing from the factors the previous launch left
-    // for its last (g, wave) -- a launch per g-ordinate lets the chains of g run beside the walk of g + 1
-    if (p.ig0 == 0) { for (int e = tid; e < nn; e += 64) fc[e] = 1.0; }
+    // the walk of this launch: g-ordinates [ig0, ig0 + ng_launch) over the window's wavenumbers, continuing from the factors
+    // the previous launch left for its last (g, wave) -- a launch per g-ordinate lets the chains of g run beside the walk of
+    // g + 1; at G = 1 a launch per window, which continues from the carry of the previous window
+    if (p.carry_in) {
+        const double *pfc = p.carry + (size_t)comp * nn;
+        for (int e = tid; e < nn; e += 64) fc[e] = pfc[e];
+    } else if (p.ig0 == 0) { for (int e = tid; e < nn; e += 64) fc[e] = 1.0; }
     else {
-        const double *pfc = p.fc + (((size_t)(p.ig0 - 1) * p.nwave + (p.nwave - 1)) * p.ncomp + comp) * nn;
+        const double *pfc = p.fc + (((size_t)(p.ig0 - 1) * p.nwin + (p.nwin - 1)) * p.ncomp + comp) * nn;
         for (int e = tid; e < nn; e += 64) fc[e] = pfc[e];
     }
-    const long total = (long)p.ng_launch * p.nwave;
+    const long total = (long)p.ng_launch * p.nwin;
     int wf = 0;                                                  // wavenumber of the next fetch (wraps around: see below)
 #pragma unroll
-    for (int d = 0; d < D; ++d) { fetch(d, wf); if (++wf == p.nwave) wf = 0; }
+    for (int d = 0; d < D; ++d) { fetch(d, wf); if (++wf == p.nwin) wf = 0; }
     int ig = p.ig0, widx = 0;
     for (long iter0 = 0; iter0 < total; iter0 += D) {
 #pragma unroll
@@ -317,7 +327,7 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
         // always issued (beyond the end of the walk it re-reads a matrix that is there): a fetch under a condition leaves the
         // number of loads in flight unknown to the compiler, which then waits for all of them
         fetch(d, wf);
-        if (++wf == p.nwave) wf = 0;
+        if (++wf == p.nwin) wf = 0;
         MS_WAVE_SYNC();
         double rs = 0.0;
         if (tid < nr) {
@@ -354,15 +364,19 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
             }
             MS_WAVE_SYNC();
         }
-        double *ofc = p.fc + (((size_t)ig * p.nwave + widx) * p.ncomp + comp) * nn;
+        double *ofc = p.fc + (((size_t)ig * p.nwin + widx) * p.ncomp + comp) * nn;
 #pragma unroll
         for (int r = 0; r < NE; ++r) {           // a fixed number of stores per step (the waits before the ring's slots count them)
             const int e = CLAMP ? min(tid + 64 * r, nn - 1) : tid + 64 * r;
             if (FULL || CLAMP || e < nn) ofc[e] = fc[e];
         }
-        if (++widx == p.nwave) { widx = 0; ++ig; }
+        if (++widx == p.nwin) { widx = 0; ++ig; }
         MS_WAVE_SYNC();
     }
+    }
+    if (p.carry) {                               // the last step's factors, bit for bit: the next window starts from them
+        double *cfc = p.carry + (size_t)comp * nn;
+        for (int e = tid; e < nn; e += 64) cfc[e] = fc[e];
     }
 }
 
@@ -495,9 +509,10 @@ __global__ __launch_bounds__(64) void k_ms_chain(MsParams p)
         defined = true;
         MS_WAVE_SYNC();
     }
-    const double *PPL = p.ppl + (((size_t)widx * (p.nf + 1) + ic) * p.ncomp) * nn;
-    const double *PMI = p.pmi + (((size_t)widx * (p.nf + 1) + ic) * p.ncomp) * nn;
-    const double *FC = p.fc + (((size_t)ig * p.nwave + widx) * p.ncomp) * nn;   // ppl *= fc (:232)
+    const size_t wpw = (size_t)(widx - p.pw0);                              // in the window of phase matrices / factors
+    const double *PPL = p.ppl + ((wpw * (p.nf + 1) + ic) * p.ncomp) * nn;
+    const double *PMI = p.pmi + ((wpw * (p.nf + 1) + ic) * p.ncomp) * nn;
+    const double *FC = p.fc + (((size_t)ig * p.nwin + wpw) * p.ncomp) * nn;   // ppl *= fc (:232)
 
     for (int l = 0; l < p.nlay; ++l) {
         const int k = lookup ? p.nlay - 1 - l : l;  // look-down: bottom layer first (:842-845)
@@ -940,9 +955,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         defined = true;
     }
     MS16_FENCE();
-    const double *PPL = p.ppl + (((size_t)widx * (p.nf + 1) + ic) * p.ncomp) * nn;
-    const double *PMI = p.pmi + (((size_t)widx * (p.nf + 1) + ic) * p.ncomp) * nn;
-    const double *FC = p.fc + (((size_t)ig * p.nwave + widx) * p.ncomp) * nn;   // ppl *= fc (:232)
+    const size_t wpw = (size_t)(widx - p.pw0);                              // in the window of phase matrices / factors
+    const double *PPL = p.ppl + ((wpw * (p.nf + 1) + ic) * p.ncomp) * nn;
+    const double *PMI = p.pmi + ((wpw * (p.nf + 1) + ic) * p.ncomp) * nn;
+    const double *FC = p.fc + (((size_t)ig * p.nwin + wpw) * p.ncomp) * nn;   // ppl *= fc (:232)
     const int ncu = p.ncont + (p.iray > 0 ? 1 : 0);      // components in use: the aerosols, then Rayleigh
     if constexpr (PHASE_LDS) {
         for (int cc = 0; cc < ncu; ++cc)

@@ -152,9 +152,10 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
         for (int i = 0; i < N; ++i) LS(jc, i) = radg[i];
         defined = true;
     }
-    const double *PPL = p.ppl + (((size_t)widx * (p.nf + 1) + ic) * p.ncomp) * NN;
-    const double *PMI = p.pmi + (((size_t)widx * (p.nf + 1) + ic) * p.ncomp) * NN;
-    const double *FC = p.fc + (((size_t)ig * p.nwave + widx) * p.ncomp) * NN;   // ppl *= fc (:232)
+    const size_t wpw = (size_t)(widx - p.pw0);                              // in the window of phase matrices / factors
+    const double *PPL = p.ppl + ((wpw * (p.nf + 1) + ic) * p.ncomp) * NN;
+    const double *PMI = p.pmi + ((wpw * (p.nf + 1) + ic) * p.ncomp) * NN;
+    const double *FC = p.fc + (((size_t)ig * p.nwin + wpw) * p.ncomp) * NN;   // ppl *= fc (:232)
 
     typename M::Mat r1, t1, m0, m2, m3;
     typename M::Vec j1, v0, v1;

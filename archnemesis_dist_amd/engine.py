@@ -551,6 +551,13 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_last_scatter_cache(self._ctx, C.byref(a), C.byref(b)), "last_scatter_cache")
         return int(a.value), int(b.value)
 
+    def last_scatter_windows(self):
+        """(spectral windows of phase matrices / Hansen factors, wavenumbers per window) of the last scattering call: more
+        than one window only at G = 1 (LBL tables) when the axis is longer than a window (ANSFM_MS_WINDOW overrides its size)"""
+        a = C.c_int64(); b = C.c_int64()
+        self._check(self._lib.ansfm_last_scatter_windows(self._ctx, C.byref(a), C.byref(b)), "last_scatter_windows")
+        return int(a.value), int(b.value)
+
     def add_line_set_monochromatic_absorption(self, wn_grid, lineshape_id, t_calc, t_ref, p_calc, p_ref, q_ratio,
                                               isotopic_abundance, isotopic_mass, mol_mix_frac, broadening_params, nu, sw,
                                               e_lower, stimulated_emission_at_t_ref, out, store=None, s_floor=0.0,

@@ -194,10 +194,11 @@ class CIRSradGPU:
             return False           # calculate_absorption_spectrum (:4133) lacks `self` in the reference: never callable
         if imod & IMOD_THERMAL_EMISSION:
             return True
+        # the scattering branches: k-tables or LBL tables (G = 1), without gradients -- the reference has none there either
         if imod & IMOD_SINGLE_SCATTERING_PLANE_PARALLEL:
-            return (not return_grad) and int(S.ILBL) == ILBL_K_TABLES
+            return not return_grad
         if self._ansfm_scatter_branch(imod):
-            return (not return_grad) and int(S.ILBL) == ILBL_K_TABLES      # the reference has no gradients there either
+            return not return_grad
         return False
 
     @staticmethod

@@ -18,7 +18,8 @@ override keeps the method's signature, state-vector arithmetic (:2234-2242), NUM
              CIRSrad (:490-516); what CIRSrad would read is kept, and the states of one (geometry, averaging point) go
              to the GPU as ONE batched call (layers bit-identical to the unperturbed state's are not recomputed,
              DESIGN.md 4.1d); the second half of nemesisfm (FOV weights, convolution, subspecret, :531-587) then runs
-             per state.  read_tables runs once per geometry instead of once per forward model.
+             per state.  read_tables runs once per geometry instead of once per forward model.  The multiple-scattering
+             branch takes k-tables or LBL tables (ILBL = 2, one g-ordinate): the states go to cirsrad_ck_scatter_batch.
              With nemesisL = True the same is done for nemesisLfm (:1254-1368: all tangent paths of a state in one CIRSrad
              call, then the interpolation to the measurement's tangent heights and the convolution over all geometries), with
              nemesisSO = True for nemesisSOfm's plain branch (:909-978: calc_path_SO, CIRSrad's transmission branch).

@@ -170,7 +170,8 @@ int ansfm_singlescatt_plane_spectrum(ansfm_ctx *ctx, int ISPACE, int W, int G, i
  * calculate_single_scattering_plane_parallel_spectrum :4251-4336) fused with the opacity assembly: the albedo
  * OMEGA = (TAURAY + TAUSCAT) / TAUTOT of every (wavenumber, g, layer) is formed in the RT kernel from the vertical opacities.
  * Host pointers: taucont[W][L] = TAUCIA + TAUDUST + TAURAY, tausca[W][L] = TAURAY + TAUSCAT, phase[P][W][L] = the layer-mean
- * phase function at each path's scattering angle (:4318-4322), BRDF[W][P], SOLFLUX[W], angles [P] -> SPECOUT[W][P]. */
+ * phase function at each path's scattering angle (:4318-4322), BRDF[W][P], SOLFLUX[W], angles [P] -> SPECOUT[W][P].
+ * The uploaded table is a k-table (calc_k + k_overlap) or an LBL table (ILBL = LINE_BY_LINE_TABLES: calc_klbl, G = 1). */
 int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
                                  const double *amount, const double *taucont, const double *tausca, const double *phase, int P,
                                  int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
@@ -308,15 +309,19 @@ int ansfm_scloud11wave_core(ansfm_ctx *ctx, int ncont, int nwave, int nth, const
                             const double *taus, const double *tauray, const double *omegas_s,
                             int nphi, int iray, int imie, const double *lfrac, double *rad);
 
-/* CIRSrad, scattering branch (ILBL = K_TABLES, IMOD & MULTIPLE_SCATTERING; ForwardModel_0.py:4478-4501 ->
- * calculate_multiple_scattering_spectrum :4343 -> scloud11wave :5018-5165) with everything that has a g axis on the
- * device: calc_k + k_overlap give the VERTICAL gas opacities (not LAYINC-scaled: scloud11wave reads LayerX.TAUTOT),
+/* CIRSrad, scattering branch (ILBL = K_TABLES or LINE_BY_LINE_TABLES, IMOD & MULTIPLE_SCATTERING; ForwardModel_0.py:4478-4501
+ * -> calculate_multiple_scattering_spectrum :4343 -> scloud11wave :5018-5165) with everything that has a g axis on the
+ * device: calc_k + k_overlap (k-tables) or calc_klbl (LBL tables, G = 1, DELG = {1}; :3795-3817) give the VERTICAL gas
+ * opacities (not LAYINC-scaled: scloud11wave reads LayerX.TAUTOT),
  * TAUTOT = TAUGAS + TAUCIA + TAUDUST + TAURAY (:3989), OMEGA = (TAURAY + TAUSCAT) / TAUTOT and BB = planck(TEMP) (:5099-5119)
  * are formed in HBM and feed the doubling / adding kernels directly; the g-quadrature with DELG (:4504) ends the call.
  * Host pointers, reference layouts: taucia / taudust (summed over populations) / tauray / tauscat [W][L] (NULL = zeros),
  * lfrac[W][ncont][L] = TAUCLSCAT / TAUSCAT, the remaining scloud11wave_core arguments as above (W = the table's wavenumber
  * grid, ng = its g-ordinates), xfac[W] or NULL -> SPECOUT[W][ngeom]; SPEC_G[W][G][ngeom] (what scloud11wave returns, before
- * the quadrature) when not NULL.  ansfm_get_taugas returns the TAUGAS side product afterwards. */
+ * the quadrature) when not NULL.  ansfm_get_taugas returns the TAUGAS side product afterwards.
+ * G = 1 (every LBL table): the phase matrices and Hansen factors are held for a window of wavenumbers at a time (default the
+ * larger of 4096 and W / 16, rounded up to 64, one window's buffers under 2 GB; ANSFM_MS_WINDOW=<wavenumbers> overrides);
+ * the walk of window k + 1 runs beside the chains of window k.  The window size changes no bit of the result. */
 int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
                              const double *amount, const double *taucia, const double *taudust, const double *tauray,
                              const double *tauscat, int ncont, int nth, const double *phasarr, const double *lfrac,
@@ -337,7 +342,9 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
  * (addp :481-533) over them and recomputes only the layers whose inputs differ from model 0's in any bit -- the same
  * numbers as n_models separate calls, bit for bit.  ansfm_set_layer_dedup(ctx, 0) (or another stream count) runs the
  * models one after the other through ansfm_cirsrad_ck_scatter.  ansfm_last_scatter_cache: (model, layer) pairs taken
- * from the cache / all pairs of models 1..n-1 in the last call; ansfm_last_layer_rows: gas opacity rows computed. */
+ * from the cache / all pairs of models 1..n-1 in the last call; ansfm_last_layer_rows: gas opacity rows computed.
+ * LBL tables: the distinct (model, layer) rows through calc_klbl; at G = 1 the slabs of the spectral axis are the windows
+ * of phase matrices and Hansen factors (as in ansfm_cirsrad_ck_scatter), the walk continuing from slab to slab. */
 int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
                                    const double *lay_temp, const double *amount, const double *taucia, const double *taudust,
                                    const double *tauray, const double *tauscat, int ncont, int nth, const double *phasarr,
@@ -346,6 +353,9 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
                                    const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
                                    int iray, int imie, const double *xfac, double *SPECOUT);
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total);
+/* Spectral windows of phase matrices / Hansen factors in the last scattering call (ansfm_cirsrad_ck_scatter(_batch),
+ * ansfm_scloud11wave_core) and the wavenumbers per window: 1 and W when one window covers the axis (always at G > 1). */
+int ansfm_last_scatter_windows(const ansfm_ctx *ctx, int64_t *windows, int64_t *window_wavenumbers);
 
 /* ---- runtime line-by-line (ILBL = LINE_BY_LINE_RUNTIME) -------------------------------------------
  * LineData_0.add_line_set_monochromatic_absorption (LineData_0.py:280-357), batched over L (T,p) points
