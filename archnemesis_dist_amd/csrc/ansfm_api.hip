@@ -32,6 +32,10 @@ namespace {
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n)
     {
         if (n <= bytes) return hipSuccess;
@@ -57,11 +61,9 @@ struct ansfm_ctx {
     int W = 0, Wpad = 0, G = 0, NP = 0, NT = 0, S = 0;
     int monotone = 0;
     std::vector<double> h_wave, h_press, h_temp;   // host copies of the grids of the table in HBM
-    int force_generic = 0;   // rerun of a call whose k-distributions turned out not to be sorted in g
     DevBuf dcont_gas;                       // ansfm_set_shared_gas_gradient: [L][Wpad], consumed by the next cirsradg call
     int dcont_gas_L = 0;                    // 0: none pending
     unsigned grad_gas_mask = 0xFFFFFFFFu;   // ansfm_set_gradient_gases: gases whose amount gradients cirsradg computes
-    int rt_mode = 0;         // 1: the next cirsrad_ck_thermal call returns the path transmission (ansfm_cirsrad_ck_transmission)
     int merge_keys = 64;     // 32: run the forward merge on k_ck_overlap32's float32 keys (ansfm_set_merge_keys)
     bool have_table = false;
     int grid_f32 = 0, delg_f32 = 0;
@@ -74,7 +76,6 @@ struct ansfm_ctx {
     DevBuf dspec_ref, map_out, map_b, map_batch;
     DevBuf dd_slot, dd_work, dd_in;      // layer de-duplication: row map [n][L], work list, packed inputs
     DevBuf ms_radg16, ms_brdf16;         // 7 .. 15 streams padded to the 16-stream kernels' layout
-    int ms_reuse_walk = 0;               // scattering, model-by-model batches: phase matrices + Hansen factors of the previous call stand
     DevBuf rt_prefix, rt_same;           // thermal RT of a batch: state 0's records along every path; same flags [n][L] + jstart [n][P]
     int last_rt_shared = 0;
     int dedup = 1;                       // ansfm_set_layer_dedup
@@ -98,6 +99,14 @@ struct ansfm_ctx {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double overlap_ms = 0, rt_ms = 0;
     int overlap_launches = 0, rt_launches = 0;
+
+    // the buffers free themselves (DevBuf); streams and events go here
+    ~ansfm_ctx()
+    {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
+    }
 };
 
 #define CHECK_CTX(ctx) do { if (!(ctx)) return ANSFM_ERR_INVALID; } while (0)
@@ -156,20 +165,8 @@ void ansfm_destroy(ansfm_ctx *ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->lnK, &ctx->d_press, &ctx->d_temp, &ctx->d_wave, &ctx->d_delg, &ctx->d_flag,
-                      &ctx->li, &ctx->tau, &ctx->scratch, &ctx->cont_t, &ctx->tmp_in, &ctx->tmp_out,
-                      &ctx->misc, &ctx->gscratch, &ctx->dkbuf, &ctx->trold_ws, &ctx->dspec_i, &ctx->dcont_t,
-                      &ctx->tmp_in2, &ctx->tmp_out2, &ctx->lbl_li, &ctx->ms_taus, &ctx->ms_omegas, &ctx->ms_bnu, &ctx->dcont_gas,
-                      &ctx->ms_cache, &ctx->ms_orders, &ctx->ms_same, &ctx->ms_pcache, &ctx->ms_lstart};
-    for (auto *b : bufs) b->release();
-    for (auto &b : ctx->hb) b.release();
-    for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->ms_ev) if (e) (void)hipEventDestroy(e);
-    if (ctx->ms_stream) (void)hipStreamDestroy(ctx->ms_stream);
-    if (ctx->ms_stream2) (void)hipStreamDestroy(ctx->ms_stream2);
-    if (ctx->ms_stream3) (void)hipStreamDestroy(ctx->ms_stream3);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+    for (hipStream_t s : {ctx->stream, ctx->own_stream, ctx->ms_stream, ctx->ms_stream2, ctx->ms_stream3})
+        if (s) (void)hipStreamSynchronize(s);
     delete ctx;
 }
 
@@ -504,12 +501,11 @@ int ansfm_ktable_info(const ansfm_ctx *ctx, int64_t dims[5], int *monotone)
 /* ------------------------------------------------------------------------------------------ */
 static int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wpad, int G, int S,
                           int L, int n_models, const LayerInterp *li, const double *amount,
-                          const double *del_g_dev, const double *del_g_host, double *tau)
+                          const double *del_g_dev, const double *del_g_host, double *tau, bool generic)
 {
     // fast path: every k(g) non-decreasing (checked at upload for tables, in the kernel otherwise); generic path:
-    // per-lane sort of each gas first (k_ck_overlap<..., SORTED = false>)
-    const bool sorted = !ctx->force_generic && (from_k || ctx->monotone);
-    ctx->force_generic = 0;            // one-shot request of the rerun wrappers: never survives an error return
+    // per-lane sort of each gas first (k_ck_overlap<..., SORTED = false>), also on request (the rerun of an unsorted call)
+    const bool sorted = !generic && (from_k || ctx->monotone);
     OverlapParams p;
     memset(&p, 0, sizeof p);
     p.lnK = ctx->lnK.as<double>();
@@ -593,22 +589,6 @@ static int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W,
     return ANSFM_OK;
 }
 
-static int lbl_prep_fwd(ansfm_ctx *ctx, int n_layers, const double *lay_press, const double *lay_temp, double press_div,
-                        int with_grad);
-
-// ILBL = LINE_BY_LINE_TABLES in the scattering entries: tau[rows][1][Wpad] = sum_gas k*amount (:3795-3817), the layout
-// launch_overlap leaves for G = 1; amount [S][rows] (device, device pointers throughout)
-static int lbl_tau_rows(ansfm_ctx *ctx, int rows, const double *press, const double *temp, const double *amount)
-{
-    int rc;
-    if ((rc = lbl_prep_fwd(ctx, rows, press, temp, 101325.0, 0))) return rc;
-    hipLaunchKernelGGL(k_lbl_tau, dim3(nblk((size_t)rows * ctx->Wpad, 256)), dim3(256), 0, ctx->stream, ctx->lnK.as<double>(),
-                       ctx->Wpad, ctx->NT, ctx->S, rows, 1, ctx->lbl_li.as<LblInterp>(), amount, ctx->tau.as<double>(),
-                       (double *)nullptr);
-    HIPCHK(hipGetLastError());
-    return ANSFM_OK;
-}
-
 // src[W][X1][X2] -> dst[(x1, x2) or, swap12, (x2, x1)][Wpad] through a 32 x 32 LDS tile (k_transpose_w_last): both sides move
 // whole 256-byte segments.  The element-per-thread version read with a stride of X1 * X2 doubles: 0.18 TB/s, 17.7 of the
 // 58 ms of a C3 Jacobian call for the continuum of its 201 states.
@@ -681,9 +661,154 @@ static int check_unsorted(ansfm_ctx *ctx)
     return ANSFM_OK;
 }
 
+}  // extern "C": the helpers of the entry points below are templates in places
+
+static int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double *dkin, int W, int Wpad, int G, int S,
+                           int L, int n_models, const LayerInterp *li, const double *amount, const double *del_g_dev,
+                           const double *del_g_host, double *tau, double *dk, bool generic);
+
+// Runs run(generic = false) and, if the fast merge met a k-distribution that is not non-decreasing in g, once more with
+// run(generic = true): the one rerun policy of the entry points.  The caller cleared the flag before the first pass; the rerun
+// clears it again.  Synchronises after each pass.
+template <class Run> static int rerun_unsorted(ansfm_ctx *ctx, Run run)
+{
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+        int flag = 0, rc = run(pass == 1);
+        if (rc || (rc = read_unsorted(ctx, &flag))) return rc;
+        if (!flag) break;
+    }
+    return ANSFM_OK;
+}
+
+// LBL tables: the interpolation records of n_layers layers in ctx->lbl_li
+static int lbl_prep(ansfm_ctx *ctx, int n_layers, const double *lay_press, const double *lay_temp, double press_div,
+                    int with_grad)
+{
+    HIPCHK(ctx->lbl_li.reserve((size_t)n_layers * sizeof(LblInterp)));
+    hipLaunchKernelGGL(k_layer_prep_lbl, dim3(nblk(n_layers, 128)), dim3(128), 0, ctx->stream, n_layers, lay_press,
+                       lay_temp, ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(), ctx->temp2d,
+                       press_div, ctx->grid_f32, with_grad, ctx->lbl_li.as<LblInterp>());
+    HIPCHK(hipGetLastError());
+    return ANSFM_OK;
+}
+
+/* ---- gas opacities of a set of layer rows: calc_k + k_overlap (:3855-3874), or sum_gas k*amount of the LBL tables ------- */
+// The rows are device arrays press / temp [n L] and amount [n][S][L], which the merge kernel sees as n models of L layers.
+// Two steps, so that the rerun of an unsorted call repeats the merge only.  gas_prep reserves ctx->li / ctx->tau for the rows
+// and, for a k-table, interpolates them in its grids (k_layer_prep).
+static int gas_prep(ansfm_ctx *ctx, int rows, const double *press, const double *temp)
+{
+    HIPCHK(ctx->li.reserve((size_t)rows * sizeof(LayerInterp)));
+    HIPCHK(ctx->tau.reserve((size_t)rows * ctx->G * ctx->Wpad * sizeof(double)));
+    if (ctx->is_lbl) return ANSFM_OK;
+    hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream, rows, press, temp, ctx->NP,
+                       ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(), 101325.0, ctx->grid_f32,
+                       ctx->li.as<LayerInterp>());
+    HIPCHK(hipGetLastError());
+    return ANSFM_OK;
+}
+
+// gas_tau fills ctx->tau [n L][G][Wpad] by the table's route: k_ck_overlap (generic: every k-distribution sorted first), or
+// k_layer_prep_lbl + k_lbl_tau (LBL tables, G = 1, :3795-3817).  dk: the gradient route (k_ck_overlapg / calc_klblg) also
+// writes the derivatives [n L][S + 1][G][Wpad] there.
+static int gas_tau(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount, bool generic,
+                   double *dk = nullptr)
+{
+    if (ctx->is_lbl) {
+        const int rows = n * L;
+        const int rc = lbl_prep(ctx, rows, press, temp, 101325.0, dk != nullptr);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_lbl_tau, dim3(nblk((size_t)rows * ctx->Wpad, 256)), dim3(256), 0, ctx->stream, ctx->lnK.as<double>(),
+                           ctx->Wpad, ctx->NT, ctx->S, L, n, ctx->lbl_li.as<LblInterp>(), amount, ctx->tau.as<double>(), dk);
+        HIPCHK(hipGetLastError());
+        return ANSFM_OK;
+    }
+    if (dk)
+        return launch_overlapg(ctx, false, nullptr, nullptr, ctx->W, ctx->Wpad, ctx->G, ctx->S, L, n, ctx->li.as<LayerInterp>(),
+                               amount, ctx->d_delg.as<double>(), ctx->h_delg.data(), ctx->tau.as<double>(), dk, generic);
+    return launch_overlap(ctx, false, nullptr, ctx->W, ctx->Wpad, ctx->G, ctx->S, L, n, ctx->li.as<LayerInterp>(), amount,
+                          ctx->d_delg.as<double>(), ctx->h_delg.data(), ctx->tau.as<double>(), generic);
+}
+
+// The whole stage for `rows` layers of one model, synchronised: a k-table reruns an unsorted call on the generic path; an LBL
+// table has no merge and leaves the flag alone
+static int gas_opacity(ansfm_ctx *ctx, int rows, const double *press, const double *temp, const double *amount)
+{
+    if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+    int rc = gas_prep(ctx, rows, press, temp);
+    if (rc) return rc;
+    if (ctx->is_lbl) return gas_tau(ctx, 1, rows, press, temp, amount, false);
+    return rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, 1, rows, press, temp, amount, generic); });
+}
+
+// Layer de-duplication of a batch of n models x L layers (device rows as above): k_dedup_mark maps every (model, layer) to its
+// row in ctx->dd_slot [n][L] -- model 0's L rows first, then the layers in which another model differs (the Rayleigh columns
+// ray_totam / ray_f4 take part in the comparison when given) -- the row count is read back (synchronises), and k_dedup_gather
+// packs the distinct rows' press, temp [rows] and amount [S][rows] into ctx->dd_in.
+struct DedupRows {
+    int rows;
+    const double *press, *temp, *amount;
+};
+static int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
+                      const double *ray_totam, const double *ray_f4, DedupRows *out)
+{
+    const int S = ctx->S;
+    const size_t nl = (size_t)n * L;
+    HIPCHK(ctx->dd_slot.reserve(nl * sizeof(int32_t)));
+    HIPCHK(ctx->dd_work.reserve(nl * sizeof(int32_t)));
+    int *counter = ctx->d_flag.as<int>() + 12;
+    HIPCHK(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_dedup_mark, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n, L, S, press, temp, amount,
+                       ctx->dd_slot.as<int32_t>(), ctx->dd_work.as<int32_t>(), counter, ray_totam, ray_f4);
+    HIPCHK(hipGetLastError());
+    int extra = 0;
+    HIPCHK(hipMemcpyAsync(&extra, counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int rows = L + extra;
+    HIPCHK(ctx->dd_in.reserve((size_t)rows * (S + 2) * sizeof(double)));
+    double *pw = ctx->dd_in.as<double>(), *tw = pw + rows, *aw = tw + rows;
+    hipLaunchKernelGGL(k_dedup_gather, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream, rows, L, S,
+                       ctx->dd_work.as<int32_t>(), press, temp, amount, pw, tw, aw);
+    HIPCHK(hipGetLastError());
+    *out = DedupRows{rows, pw, tw, aw};
+    return ANSFM_OK;
+}
+
+/* ---- host -> device staging of the host-pointer entry points --------------------------------------------------------- */
+static int h2d(ansfm_ctx *ctx, DevBuf &b, const void *src, size_t bytes, const void **out)
+{
+    *out = nullptr;
+    if (!src || bytes == 0) return ANSFM_OK;
+    HIPCHK(b.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *out = b.p;
+    return ANSFM_OK;
+}
+
+// The k-th up() of an entry point copies `count` elements into ctx->hb[slot + k] and returns the device copy; a null pointer
+// or a zero count gives nullptr.  After an error up() stages nothing more and rc holds its code.  An entry point that stages
+// calls no other that stages while its staged pointers are in use.
+struct Stager {
+    ansfm_ctx *ctx;
+    int slot = 0;
+    int rc = ANSFM_OK;
+    template <class T> const T *up(const T *src, size_t count)
+    {
+        const void *d = nullptr;
+        if (rc == ANSFM_OK) rc = h2d(ctx, ctx->hb[slot++], src, count * sizeof(T), &d);
+        return static_cast<const T *>(d);
+    }
+};
+
+extern "C" {
+
 /* ------------------------------------------------------------------------------------------ */
 /* fused CIRSrad (device pointers)                                                             */
 /* ------------------------------------------------------------------------------------------ */
+// ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); rt_mode 1:
+// the path transmission (ansfm_cirsrad_ck_transmission); generic: the merge sorts every k-distribution first (the rerun of a
+// call whose table turned out not to be sorted in g)
 static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L,
                                  const double *lay_press_pa, const double *lay_temp,
                                  const double *amount, const double *taucont, int P, int LIMAX,
@@ -691,44 +816,7 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models,
                                  const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
                                  const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
                                  const double *EMISS_ANG, const double *xfac, double *SPECOUT,
-                                 int ray_mode, const double *ray_totam, const double *ray_f4);
-
-int ansfm_cirsrad_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L,
-                                 const double *lay_press_pa, const double *lay_temp,
-                                 const double *amount, const double *taucont, int P, int LIMAX,
-                                 const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                 const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                 const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
-                                 const double *EMISS_ANG, const double *xfac, double *SPECOUT)
-{
-    return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC,
-                                       SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT, 0,
-                                       nullptr, nullptr);
-}
-
-int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                     const double *lay_temp, const double *amount, int ray_mode, const double *TOTAM,
-                                     const double *f4, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
-                                     const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                     const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
-                                     const double *EMISS_ANG, const double *xfac, double *SPECOUT)
-{
-    CHECK_CTX(ctx);
-    if ((ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || !TOTAM || (ray_mode == 4 && !f4))
-        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_ray_dev: bad argument (ray_mode = IRAY 1, 2, 4 or 12 for calc_tau_rayleighv)");
-    return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, P, LIMAX, NLAYIN, LAYINC,
-                                       SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT,
-                                       ray_mode, TOTAM, ray_mode == 4 ? f4 : nullptr);
-}
-
-static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L,
-                                 const double *lay_press_pa, const double *lay_temp,
-                                 const double *amount, const double *taucont, int P, int LIMAX,
-                                 const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                 const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                 const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
-                                 const double *EMISS_ANG, const double *xfac, double *SPECOUT,
-                                 int ray_mode, const double *ray_totam, const double *ray_f4)
+                                 int ray_mode, const double *ray_totam, const double *ray_f4, int rt_mode, bool generic)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
@@ -736,42 +824,23 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models,
         !LAYINC || !SCALE || !EMTEMP || !TSURF || !SPECOUT || (ISPACE != 0 && ISPACE != 1))
         FAIL(ANSFM_ERR_INVALID, "cirsrad: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
+    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G;
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     // ---- which (model, layer) opacities have to be computed: all of them, or (batches) the distinct ones -------
-    int rows = n_models * L;                       // rows of the opacity buffer = layers handed to the merge kernel
-    const double *press_k = lay_press_pa, *temp_k = lay_temp, *amount_k = amount;
-    int n_k = n_models, L_k = L;                   // the merge kernel's view: n_k models of L_k layers
+    DedupRows k{n_models * L, lay_press_pa, lay_temp, amount};   // the rows handed to the merge kernel
+    int n_k = n_models;                                         // its view: n_k models of k.rows / n_k layers
     const int32_t *tau_slot = nullptr;
-    if (ctx->dedup && n_models > 1) {
-        const size_t nl = (size_t)n_models * L;
-        HIPCHK(ctx->dd_slot.reserve(nl * sizeof(int32_t)));
-        HIPCHK(ctx->dd_work.reserve(nl * sizeof(int32_t)));
-        int *counter = ctx->d_flag.as<int>() + 12;
-        HIPCHK(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(k_dedup_mark, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, S, lay_press_pa,
-                           lay_temp, amount, ctx->dd_slot.as<int32_t>(), ctx->dd_work.as<int32_t>(), counter,
-                           ray_mode ? ray_totam : nullptr, ray_mode ? ray_f4 : nullptr);
-        HIPCHK(hipGetLastError());
-        int extra = 0;
-        HIPCHK(hipMemcpyAsync(&extra, counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));         // the only synchronisation of this entry point (batches only)
-        rows = L + extra;
-        HIPCHK(ctx->dd_in.reserve((size_t)rows * (S + 2) * sizeof(double)));
-        double *pw = ctx->dd_in.as<double>(), *tw = pw + rows, *aw = tw + rows;
-        hipLaunchKernelGGL(k_dedup_gather, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream, rows, L, S,
-                           ctx->dd_work.as<int32_t>(), lay_press_pa, lay_temp, amount, pw, tw, aw);
-        HIPCHK(hipGetLastError());
-        press_k = pw; temp_k = tw; amount_k = aw; n_k = 1; L_k = rows;
+    int rc;
+    if (ctx->dedup && n_models > 1) {   // the only synchronisation of this entry point (batches only)
+        if ((rc = dedup_rows(ctx, n_models, L, lay_press_pa, lay_temp, amount, ray_mode ? ray_totam : nullptr,
+                             ray_mode ? ray_f4 : nullptr, &k)))
+            return rc;
+        n_k = 1;
         tau_slot = ctx->dd_slot.as<int32_t>();
     }
+    const int rows = k.rows;
     ctx->last_rows = rows; ctx->last_dedup = tau_slot != nullptr;
-    HIPCHK(ctx->li.reserve((size_t)rows * sizeof(LayerInterp)));
-    HIPCHK(ctx->tau.reserve((size_t)rows * G * Wpad * sizeof(double)));
-    hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream,
-                       rows, press_k, temp_k, ctx->NP, ctx->d_press.as<double>(), ctx->NT,
-                       ctx->d_temp.as<double>(), 101325.0, ctx->grid_f32, ctx->li.as<LayerInterp>());
-    HIPCHK(hipGetLastError());
+    if ((rc = gas_prep(ctx, rows, k.press, k.temp))) return rc;
     const double *cont_t = nullptr;
     if (ray_mode) {
         // the Rayleigh continuum of the rows that are computed (the distinct layers of the batch), straight in the layout the RT
@@ -789,18 +858,7 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models,
         cont_t = ctx->cont_t.as<double>();
     }
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    int rc;
-    if (ctx->is_lbl) {   // ILBL = LINE_BY_LINE_TABLES: tau = sum_gas k*amount (:3795-3817), NG = 1
-        if ((rc = lbl_prep_fwd(ctx, rows, press_k, temp_k, 101325.0, 0))) return rc;
-        hipLaunchKernelGGL(k_lbl_tau, dim3(nblk((size_t)rows * Wpad, 256)), dim3(256), 0, ctx->stream,
-                           ctx->lnK.as<double>(), Wpad, ctx->NT, S, L_k, n_k, ctx->lbl_li.as<LblInterp>(), amount_k,
-                           ctx->tau.as<double>(), (double *)nullptr);
-        HIPCHK(hipGetLastError());
-    } else {
-        rc = launch_overlap(ctx, false, nullptr, W, Wpad, G, S, L_k, n_k, ctx->li.as<LayerInterp>(), amount_k,
-                            ctx->d_delg.as<double>(), ctx->h_delg.data(), ctx->tau.as<double>());
-        if (rc != ANSFM_OK) return rc;
-    }
+    if ((rc = gas_tau(ctx, n_k, rows / n_k, k.press, k.temp, k.amount, generic))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
     RtParams r;
     memset(&r, 0, sizeof r);
@@ -817,7 +875,7 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models,
     r.sol_ang = SOL_ANG; r.emiss_ang = EMISS_ANG;
     r.out = SPECOUT;
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0;
-    r.mode = ctx->rt_mode;
+    r.mode = rt_mode;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     rc = launch_rt(ctx, r, n_models);
     if (rc != ANSFM_OK) return rc;
@@ -827,6 +885,34 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models,
     ctx->overlap_ms = -1.0;  // resolved lazily in ansfm_last_kernel_ms
     ctx->last_n = n_models; ctx->last_L = L;
     return ANSFM_OK;
+}
+
+int ansfm_cirsrad_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L,
+                                 const double *lay_press_pa, const double *lay_temp,
+                                 const double *amount, const double *taucont, int P, int LIMAX,
+                                 const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                 const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                 const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
+                                 const double *EMISS_ANG, const double *xfac, double *SPECOUT)
+{
+    return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC,
+                                       SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT, 0,
+                                       nullptr, nullptr, 0, false);
+}
+
+int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                     const double *lay_temp, const double *amount, int ray_mode, const double *TOTAM,
+                                     const double *f4, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                     const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                     const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
+                                     const double *EMISS_ANG, const double *xfac, double *SPECOUT)
+{
+    CHECK_CTX(ctx);
+    if ((ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || !TOTAM || (ray_mode == 4 && !f4))
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_ray_dev: bad argument (ray_mode = IRAY 1, 2, 4 or 12 for calc_tau_rayleighv)");
+    return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, P, LIMAX, NLAYIN, LAYINC,
+                                       SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT,
+                                       ray_mode, TOTAM, ray_mode == 4 ? f4 : nullptr, 0, false);
 }
 
 int ansfm_set_layer_dedup(ansfm_ctx *ctx, int enable)
@@ -894,13 +980,36 @@ int ansfm_last_kernel_ms(const ansfm_ctx *cctx, double *overlap_ms, int *overlap
 /* ------------------------------------------------------------------------------------------ */
 /* host-pointer wrappers                                                                       */
 /* ------------------------------------------------------------------------------------------ */
-static int h2d(ansfm_ctx *ctx, DevBuf &b, const void *src, size_t bytes, const void **out)
+static int cirsrad_ck_thermal_host(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                   const double *lay_temp, const double *amount, const double *taucont, int P, int LIMAX,
+                                   const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP,
+                                   const double *TSURF, const double *EMISSIVITY, const double *SOLFLUX,
+                                   const double *REFLECTANCE, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                   double *SPECOUT, int rt_mode)
 {
-    *out = nullptr;
-    if (!src || bytes == 0) return ANSFM_OK;
-    HIPCHK(b.reserve(bytes));
-    HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *out = b.p;
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
+    if (n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !SPECOUT) FAIL(ANSFM_ERR_INVALID, "cirsrad: bad argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int W = ctx->W, S = ctx->S;
+    const size_t D = sizeof(double), nl = (size_t)n_models * L, nlp = (size_t)n_models * LIMAX * P;
+    Stager st{ctx};
+    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
+                 *cont = st.up(taucont, nl * W);
+    const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
+    const double *scale = st.up(SCALE, nlp), *emtemp = st.up(EMTEMP, nlp), *tsurf = st.up(TSURF, n_models),
+                 *emis = st.up(EMISSIVITY, W), *solflux = st.up(SOLFLUX, W), *refl = st.up(REFLECTANCE, W),
+                 *sol_ang = st.up(SOL_ANG, P), *emiss_ang = st.up(EMISS_ANG, P), *xf = st.up(xfac, W);
+    if (st.rc) return st.rc;
+    HIPCHK(ctx->tmp_out.reserve((size_t)n_models * W * P * D));
+    const int rc = rerun_unsorted(ctx, [&](bool generic) {
+        return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, press, temp, am, cont, P, LIMAX, nlayin, layinc, scale, emtemp,
+                                           tsurf, emis, solflux, refl, sol_ang, emiss_ang, xf, ctx->tmp_out.as<double>(), 0, nullptr,
+                                           nullptr, rt_mode, generic);
+    });
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)n_models * W * P * D, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return ANSFM_OK;
 }
 
@@ -911,49 +1020,8 @@ int ansfm_cirsrad_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, co
                              const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
                              const double *EMISS_ANG, const double *xfac, double *SPECOUT)
 {
-    CHECK_CTX(ctx);
-    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
-    if (n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !SPECOUT) FAIL(ANSFM_ERR_INVALID, "cirsrad: bad argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, S = ctx->S;
-    const size_t D = sizeof(double);
-    const void *d[18];
-    int i = 0, rc;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(lay_press_pa, (size_t)n_models * L * D);            // 0
-    UP(lay_temp, (size_t)n_models * L * D);                // 1
-    UP(amount, (size_t)n_models * S * L * D);              // 2
-    UP(taucont, (size_t)n_models * W * L * D);             // 3
-    UP(NLAYIN, (size_t)P * sizeof(int32_t));               // 4
-    UP(LAYINC, (size_t)LIMAX * P * sizeof(int32_t));       // 5
-    UP(SCALE, (size_t)n_models * LIMAX * P * D);           // 6
-    UP(EMTEMP, (size_t)n_models * LIMAX * P * D);          // 7
-    UP(TSURF, (size_t)n_models * D);                       // 8
-    UP(EMISSIVITY, (size_t)W * D);                         // 9
-    UP(SOLFLUX, (size_t)W * D);                            // 10
-    UP(REFLECTANCE, (size_t)W * D);                        // 11
-    UP(SOL_ANG, (size_t)P * D);                            // 12
-    UP(EMISS_ANG, (size_t)P * D);                          // 13
-    UP(xfac, (size_t)W * D);                               // 14
-#undef UP
-    HIPCHK(ctx->tmp_out.reserve((size_t)n_models * W * P * D));
-    for (int pass = 0; pass < 2; ++pass) {
-        ctx->force_generic = pass;       // pass 1 only if the fast merge met an unsorted k-distribution
-        rc = ansfm_cirsrad_ck_thermal_dev(
-            ctx, ISPACE, n_models, L, (const double *)d[0], (const double *)d[1], (const double *)d[2],
-            (const double *)d[3], P, LIMAX, (const int32_t *)d[4], (const int32_t *)d[5], (const double *)d[6],
-            (const double *)d[7], (const double *)d[8], (const double *)d[9], (const double *)d[10],
-            (const double *)d[11], (const double *)d[12], (const double *)d[13], (const double *)d[14],
-            ctx->tmp_out.as<double>());
-        ctx->force_generic = 0;
-        if (rc) return rc;
-        int flag = 0;
-        if ((rc = read_unsorted(ctx, &flag))) return rc;
-        if (!flag) break;
-    }
-    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)n_models * W * P * D, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return ANSFM_OK;
+    return cirsrad_ck_thermal_host(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC, SCALE,
+                                   EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT, 0);
 }
 
 int ansfm_cirsrad_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp,
@@ -963,13 +1031,9 @@ int ansfm_cirsrad_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const dou
     CHECK_CTX(ctx);
     if (n_models <= 0 || !SCALE) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_transmission: bad argument");
     std::vector<double> tsurf((size_t)n_models, -1.0);
-    ctx->rt_mode = 1;
     // the emission temperatures are not used by the transmission epilogue: SCALE stands in for the array
-    const int rc = ansfm_cirsrad_ck_thermal(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN,
-                                            LAYINC, SCALE, SCALE, tsurf.data(), nullptr, nullptr, nullptr, nullptr, nullptr, xfac,
-                                            SPECOUT);
-    ctx->rt_mode = 0;
-    return rc;
+    return cirsrad_ck_thermal_host(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC, SCALE,
+                                   SCALE, tsurf.data(), nullptr, nullptr, nullptr, nullptr, nullptr, xfac, SPECOUT, 1);
 }
 
 int ansfm_get_taugas(ansfm_ctx *ctx, int model, double *TAUGAS)
@@ -1002,13 +1066,11 @@ int ansfm_calc_k(ansfm_ctx *ctx, int L, const double *press, const double *temp,
     if (L <= 0 || !press || !temp || !k_out) FAIL(ANSFM_ERR_INVALID, "calc_k: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
-    const void *dp, *dt;
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], press, L * sizeof(double), &dp))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], temp, L * sizeof(double), &dt))) return rc;
+    Stager st{ctx};
+    const double *dp = st.up(press, L), *dt = st.up(temp, L);
+    if (st.rc) return st.rc;
     HIPCHK(ctx->li.reserve((size_t)L * sizeof(LayerInterp)));
-    hipLaunchKernelGGL(k_layer_prep, dim3(nblk(L, 128)), dim3(128), 0, ctx->stream, L, (const double *)dp,
-                       (const double *)dt, ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
+    hipLaunchKernelGGL(k_layer_prep, dim3(nblk(L, 128)), dim3(128), 0, ctx->stream, L, dp, dt, ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
                        1.0, ctx->grid_f32, ctx->li.as<LayerInterp>());
     const size_t n = (size_t)W * G * L * S;
     HIPCHK(ctx->tmp_out.reserve(n * sizeof(double) * (dkdT_out ? 2 : 1)));
@@ -1031,31 +1093,23 @@ int ansfm_k_overlap(ansfm_ctx *ctx, int W, int G, int L, int S, const double *de
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave);
     const size_t nk = (size_t)W * G * L * S;
-    const void *dk, *dam, *ddg;
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], k, nk * sizeof(double), &dk))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], amount, (size_t)S * L * sizeof(double), &dam))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], del_g, (size_t)G * sizeof(double), &ddg))) return rc;
+    Stager st{ctx};
+    const double *dk = st.up(k, nk), *dam = st.up(amount, (size_t)S * L), *ddg = st.up(del_g, G);
+    if (st.rc) return st.rc;
     HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     const size_t nkin = (size_t)S * L * G * Wpad;
     HIPCHK(ctx->tmp_in.reserve(nkin * sizeof(double)));
-    hipLaunchKernelGGL(k_kin_permute, dim3(nblk(nkin, 256)), dim3(256), 0, ctx->stream, (const double *)dk,
-                       ctx->tmp_in.as<double>(), W, Wpad, G, L, S);
+    hipLaunchKernelGGL(k_kin_permute, dim3(nblk(nkin, 256)), dim3(256), 0, ctx->stream, dk, ctx->tmp_in.as<double>(), W, Wpad, G,
+                       L, S);
     HIPCHK(hipGetLastError());
     const size_t ntau = (size_t)L * G * Wpad;
     HIPCHK(ctx->misc.reserve(ntau * sizeof(double)));
-    for (int pass = 0; pass < 2; ++pass) {
-        ctx->force_generic = pass;       // pass 1 only if the fast merge met an unsorted k-distribution
-        if (pass) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-        rc = launch_overlap(ctx, true, ctx->tmp_in.as<double>(), W, Wpad, G, S, L, 1, nullptr, (const double *)dam,
-                            (const double *)ddg, del_g, ctx->misc.as<double>());
-        ctx->force_generic = 0;
-        if (rc) return rc;
-        int flag = 0;
-        if ((rc = read_unsorted(ctx, &flag))) return rc;
-        if (!flag) break;
-    }
+    const int rc = rerun_unsorted(ctx, [&](bool generic) {
+        return launch_overlap(ctx, true, ctx->tmp_in.as<double>(), W, Wpad, G, S, L, 1, nullptr, dam, ddg, del_g,
+                              ctx->misc.as<double>(), generic);
+    });
+    if (rc) return rc;
     const size_t nout = (size_t)W * G * L;
     HIPCHK(ctx->tmp_out.reserve(nout * sizeof(double)));
     hipLaunchKernelGGL(k_w_to_first, dim3(nblk(nout, 256)), dim3(256), 0, ctx->stream, ctx->misc.as<double>(),
@@ -1078,48 +1132,40 @@ int ansfm_singlescatt_plane_spectrum(ansfm_ctx *ctx, int ISPACE, int W, int G, i
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave), Li = NLAYIN;
     const size_t D = sizeof(double);
-    const void *d[10];
-    int rc, i = 0;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(TAUTOT_PATH, (size_t)W * G * Li * D);  // 0
-    UP(OMEGA, (size_t)W * G * Li * D);        // 1
-    UP(PHASE, (size_t)W * Li * D);            // 2
-    UP(TEMP, (size_t)Li * D);                 // 3
-    UP(WAVE, (size_t)W * D);                  // 4
-    UP(EMISSIVITY, (size_t)W * D);            // 5
-    UP(SOLFLUX, (size_t)W * D);               // 6
-    UP(BRDF, (size_t)W * D);                  // 7
-#undef UP
     std::vector<int32_t> hi(1 + Li);
     hi[0] = Li;
     for (int j = 0; j < Li; ++j) hi[1 + j] = j;
     std::vector<double> hd(Li + 3, 1.0);
     hd[Li] = TSURF; hd[Li + 1] = SOL_ANG; hd[Li + 2] = EMISS_ANG;
-    const void *di, *dd;
-    if ((rc = h2d(ctx, ctx->hb[8], hi.data(), hi.size() * sizeof(int32_t), &di))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[9], hd.data(), hd.size() * D, &dd))) return rc;
+    Stager st{ctx};
+    const double *tau = st.up(TAUTOT_PATH, (size_t)W * G * Li), *omega = st.up(OMEGA, (size_t)W * G * Li),
+                 *phase = st.up(PHASE, (size_t)W * Li), *temp = st.up(TEMP, Li), *wave = st.up(WAVE, W),
+                 *emis = st.up(EMISSIVITY, W), *solflux = st.up(SOLFLUX, W), *brdf = st.up(BRDF, W);
+    const int32_t *di = st.up(hi.data(), hi.size());
+    const double *dd = st.up(hd.data(), hd.size());
+    if (st.rc) return st.rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     const size_t ntau = (size_t)Li * G * Wpad;
     HIPCHK(ctx->misc.reserve(2 * ntau * D));
     HIPCHK(ctx->cont_t.reserve((size_t)Li * Wpad * D));
     double *tau_t = ctx->misc.as<double>(), *om_t = tau_t + ntau;
-    launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[0], tau_t, W, Wpad, G, Li, 1, 0.0);
-    launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[1], om_t, W, Wpad, G, Li, 1, 0.0);
-    launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[2], ctx->cont_t.as<double>(), W, Wpad, 1, Li, 0, 0.0);
+    launch_w_to_last(ctx->stream, (unsigned)1, tau, tau_t, W, Wpad, G, Li, 1, 0.0);
+    launch_w_to_last(ctx->stream, (unsigned)1, omega, om_t, W, Wpad, G, Li, 1, 0.0);
+    launch_w_to_last(ctx->stream, (unsigned)1, phase, ctx->cont_t.as<double>(), W, Wpad, 1, Li, 0, 0.0);
     HIPCHK(hipGetLastError());
     HIPCHK(ctx->tmp_out.reserve((size_t)W * G * D));
     RtParams r;
     memset(&r, 0, sizeof r);
     r.tau = tau_t; r.omega = om_t; r.phase = ctx->cont_t.as<double>();
-    r.wave = (const double *)d[4];
-    r.nlayin = (const int32_t *)di; r.layinc = (const int32_t *)di + 1;
-    r.scale = (const double *)dd; r.emtemp = (const double *)d[3]; r.lay_press = (const double *)d[3];
-    r.tsurf = (const double *)dd + Li;
-    r.emissivity = (const double *)d[5]; r.solflux = (const double *)d[6]; r.brdf = (const double *)d[7];
-    r.sol_ang = (const double *)dd + Li + 1; r.emiss_ang = (const double *)dd + Li + 2;
+    r.wave = wave;
+    r.nlayin = di; r.layinc = di + 1;
+    r.scale = dd; r.emtemp = temp; r.lay_press = temp;
+    r.tsurf = dd + Li;
+    r.emissivity = emis; r.solflux = solflux; r.brdf = brdf;
+    r.sol_ang = dd + Li + 1; r.emiss_ang = dd + Li + 2;
     r.out = ctx->tmp_out.as<double>();
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = Li; r.P = 1; r.LIMAX = Li; r.ispace = ISPACE; r.per_g = 1; r.mode = 2;
-    rc = launch_rt(ctx, r, 1);
+    const int rc = launch_rt(ctx, r, 1);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)W * G * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1142,72 +1188,40 @@ int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
     const size_t D = sizeof(double), WL = (size_t)W * L;
-    const void *d[18];
-    int i = 0, rc;
     const double tsurf1 = TSURF;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(lay_press_pa, (size_t)L * D);                 // 0
-    UP(lay_temp, (size_t)L * D);                     // 1
-    UP(amount, (size_t)S * L * D);                   // 2
-    UP(taucont, WL * D);                             // 3
-    UP(tausca, WL * D);                              // 4
-    UP(phase, (size_t)P * WL * D);                   // 5
-    UP(NLAYIN, (size_t)P * sizeof(int32_t));         // 6
-    UP(LAYINC, (size_t)LIMAX * P * sizeof(int32_t)); // 7
-    UP(SCALE, (size_t)LIMAX * P * D);                // 8
-    UP(EMTEMP, (size_t)LIMAX * P * D);               // 9
-    UP(&tsurf1, D);                                  // 10
-    UP(EMISSIVITY, (size_t)W * D);                   // 11
-    UP(BRDF, (size_t)W * P * D);                     // 12
-    UP(SOLFLUX, (size_t)W * D);                      // 13
-    UP(SOL_ANG, (size_t)P * D);                      // 14
-    UP(EMISS_ANG, (size_t)P * D);                    // 15
-    UP(xfac, (size_t)W * D);                         // 16
-#undef UP
+    Stager st{ctx};
+    const double *press = st.up(lay_press_pa, L), *temp = st.up(lay_temp, L), *am = st.up(amount, (size_t)S * L),
+                 *cont = st.up(taucont, WL), *sca = st.up(tausca, WL), *ph = st.up(phase, (size_t)P * WL);
+    const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
+    const double *scale = st.up(SCALE, (size_t)LIMAX * P), *emtemp = st.up(EMTEMP, (size_t)LIMAX * P), *tsurf = st.up(&tsurf1, 1),
+                 *emis = st.up(EMISSIVITY, W), *brdf = st.up(BRDF, (size_t)W * P), *solflux = st.up(SOLFLUX, W),
+                 *sol_ang = st.up(SOL_ANG, P), *emiss_ang = st.up(EMISS_ANG, P), *xf = st.up(xfac, W);
+    if (st.rc) return st.rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));       // tsurf1 is a stack variable
-    HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    HIPCHK(ctx->li.reserve((size_t)L * sizeof(LayerInterp)));
-    HIPCHK(ctx->tau.reserve((size_t)L * G * Wpad * D));
-    if (ctx->is_lbl) {   // LBL tables: G = 1, DELG = {1}
-        if ((rc = lbl_tau_rows(ctx, L, (const double *)d[0], (const double *)d[1], (const double *)d[2]))) return rc;
-    }
-    for (int pass = 0; pass < 2 && !ctx->is_lbl; ++pass) {
-        ctx->force_generic = pass;
-        hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)L, 128)), dim3(128), 0, ctx->stream, L, (const double *)d[0],
-                           (const double *)d[1], ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
-                           101325.0, ctx->grid_f32, ctx->li.as<LayerInterp>());
-        HIPCHK(hipGetLastError());
-        if (pass) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-        rc = launch_overlap(ctx, false, nullptr, W, Wpad, G, S, L, 1, ctx->li.as<LayerInterp>(), (const double *)d[2],
-                            ctx->d_delg.as<double>(), ctx->h_delg.data(), ctx->tau.as<double>());
-        ctx->force_generic = 0;
-        if (rc) return rc;
-        int flag = 0;
-        if ((rc = read_unsorted(ctx, &flag))) return rc;
-        if (!flag) break;
-    }
+    int rc;
+    if ((rc = gas_opacity(ctx, L, press, temp, am))) return rc;
     ctx->last_n = 1; ctx->last_L = L; ctx->last_rows = L; ctx->last_dedup = 0;
     // reference layouts [W][L] -> [L][Wpad] (continuum, scattering opacity) and [P][W][L] -> [P][L][Wpad] (phase)
     HIPCHK(ctx->cont_t.reserve((size_t)L * Wpad * D));
     HIPCHK(ctx->misc.reserve((size_t)(1 + P) * L * Wpad * D));
     double *sca_t = ctx->misc.as<double>(), *ph_t = sca_t + (size_t)L * Wpad;
     const double *cont_t = nullptr;
-    if (d[3]) {
-        launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[3], ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0);
+    if (cont) {
+        launch_w_to_last(ctx->stream, (unsigned)1, cont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0);
         cont_t = ctx->cont_t.as<double>();
     }
-    launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[4], sca_t, W, Wpad, 1, L, 0, 0.0);
-    launch_w_to_last(ctx->stream, (unsigned)P, (const double *)d[5], ph_t, W, Wpad, 1, L, 0, 0.0, WL, (size_t)L * Wpad);
+    launch_w_to_last(ctx->stream, (unsigned)1, sca, sca_t, W, Wpad, 1, L, 0, 0.0);
+    launch_w_to_last(ctx->stream, (unsigned)P, ph, ph_t, W, Wpad, 1, L, 0, 0.0, WL, (size_t)L * Wpad);
     HIPCHK(hipGetLastError());
     HIPCHK(ctx->tmp_out.reserve((size_t)W * P * D));
     RtParams r;
     memset(&r, 0, sizeof r);
     r.tau = ctx->tau.as<double>(); r.cont = cont_t; r.sca = sca_t; r.phase = ph_t;
     r.wave = ctx->d_wave.as<double>(); r.delg = ctx->d_delg.as<double>();
-    r.nlayin = (const int32_t *)d[6]; r.layinc = (const int32_t *)d[7]; r.scale = (const double *)d[8];
-    r.emtemp = (const double *)d[9]; r.lay_press = (const double *)d[0]; r.tsurf = (const double *)d[10];
-    r.emissivity = (const double *)d[11]; r.brdf = (const double *)d[12]; r.solflux = (const double *)d[13];
-    r.sol_ang = (const double *)d[14]; r.emiss_ang = (const double *)d[15]; r.xfac = (const double *)d[16];
+    r.nlayin = nlayin; r.layinc = layinc; r.scale = scale;
+    r.emtemp = emtemp; r.lay_press = press; r.tsurf = tsurf;
+    r.emissivity = emis; r.brdf = brdf; r.solflux = solflux;
+    r.sol_ang = sol_ang; r.emiss_ang = emiss_ang; r.xfac = xf;
     r.out = ctx->tmp_out.as<double>();
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0; r.mode = 2;
     if ((rc = launch_rt(ctx, r, 1))) return rc;
@@ -1227,17 +1241,14 @@ int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR,
         FAIL(ANSFM_ERR_INVALID, "thermal_emission_g: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double), WG = (size_t)W * G, Li = NLAYIN;
-    const void *d[6];
-    int rc, i = 0;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(WAVE, (size_t)W * D); UP(TAUTOT_PATH, WG * Li * D); UP(dTAUTOT_PATH, WG * NPAR * Li * D);
-    UP(TEMP, Li * D); UP(PRESS, Li * D); UP(EMISSIVITY, (size_t)W * D);
-#undef UP
+    Stager st{ctx};
+    const double *wave = st.up(WAVE, W), *tau = st.up(TAUTOT_PATH, WG * Li), *dtau = st.up(dTAUTOT_PATH, WG * NPAR * Li),
+                 *temp = st.up(TEMP, Li), *press = st.up(PRESS, Li), *emis = st.up(EMISSIVITY, W);
+    if (st.rc) return st.rc;
     HIPCHK(ctx->tmp_out.reserve(WG * (2 + (size_t)NPAR * Li) * D));
     double *o_spec = ctx->tmp_out.as<double>(), *o_dts = o_spec + WG, *o_dspec = o_dts + WG;
     hipLaunchKernelGGL(k_thermal_emission_g_seam, dim3(nblk(WG, 128)), dim3(128), 0, ctx->stream, ISPACE, W, G, NPAR, NLAYIN, NVMR,
-                       (const double *)d[0], (const double *)d[1], (const double *)d[2], (const double *)d[3],
-                       (const double *)d[4], TSURF, (const double *)d[5], o_spec, o_dspec, o_dts);
+                       wave, tau, dtau, temp, press, TSURF, emis, o_spec, o_dspec, o_dts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(SPECOUT, o_spec, WG * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(dTSURF, o_dts, WG * D, hipMemcpyDeviceToHost, ctx->stream));
@@ -1258,36 +1269,29 @@ int ansfm_thermal_emission(ansfm_ctx *ctx, int ISPACE, int W, int G, int NLAYIN,
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave), Li = NLAYIN;
     const size_t D = sizeof(double);
-    const void *d[10];
-    int rc, i = 0;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(TAUTOT_PATH, (size_t)W * G * Li * D);  // 0
-    UP(EMITOT_PATH, (size_t)W * Li * D);      // 1
-    UP(TEMP, (size_t)Li * D);                 // 2  (EMTEMP[Li][P=1])
-    UP(PRESS, (size_t)Li * D);                // 3  (lay_press[L=Li])
-    UP(WAVE, (size_t)W * D);                  // 4
-    UP(EMISSIVITY, (size_t)W * D);            // 5
-    UP(SOLFLUX, (size_t)W * D);               // 6
-    UP(REFLECTANCE, (size_t)W * D);           // 7
-#undef UP
     // small path vectors: NLAYIN[1], LAYINC[Li] = identity, SCALE[Li] = 1, TSURF, angles
     std::vector<int32_t> hi(1 + Li);
     hi[0] = Li;
     for (int j = 0; j < Li; ++j) hi[1 + j] = j;
     std::vector<double> hd(Li + 3, 1.0);
     hd[Li] = TSURF; hd[Li + 1] = SOL_ANG; hd[Li + 2] = EMISS_ANG;
-    const void *di, *dd;
-    if ((rc = h2d(ctx, ctx->hb[8], hi.data(), hi.size() * sizeof(int32_t), &di))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[9], hd.data(), hd.size() * D, &dd))) return rc;
+    Stager st{ctx};
+    const double *tau = st.up(TAUTOT_PATH, (size_t)W * G * Li), *emi = st.up(EMITOT_PATH, (size_t)W * Li),
+                 *temp = st.up(TEMP, Li),      // EMTEMP[Li][P=1]
+                 *press = st.up(PRESS, Li),    // lay_press[L=Li]
+                 *wave = st.up(WAVE, W), *emis = st.up(EMISSIVITY, W), *solflux = st.up(SOLFLUX, W), *refl = st.up(REFLECTANCE, W);
+    const int32_t *di = st.up(hi.data(), hi.size());
+    const double *dd = st.up(hd.data(), hd.size());
+    if (st.rc) return st.rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));  // hi/hd are stack-lifetime host buffers
     // TAUTOT_PATH[W][G][Li] -> tau[Li][G][Wpad]
     const size_t ntau = (size_t)Li * G * Wpad;
     HIPCHK(ctx->misc.reserve(ntau * D));
-    launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[0], ctx->misc.as<double>(), W, Wpad, G, Li, 1, 0.0);
+    launch_w_to_last(ctx->stream, (unsigned)1, tau, ctx->misc.as<double>(), W, Wpad, G, Li, 1, 0.0);
     const double *emi_t = nullptr;
-    if (d[1]) {
+    if (emi) {
         HIPCHK(ctx->cont_t.reserve((size_t)Li * Wpad * D));
-        launch_w_to_last(ctx->stream, (unsigned)1, (const double *)d[1], ctx->cont_t.as<double>(), W, Wpad, 1, Li, 0, 0.0);
+        launch_w_to_last(ctx->stream, (unsigned)1, emi, ctx->cont_t.as<double>(), W, Wpad, 1, Li, 0, 0.0);
         emi_t = ctx->cont_t.as<double>();
     }
     HIPCHK(hipGetLastError());
@@ -1297,20 +1301,20 @@ int ansfm_thermal_emission(ansfm_ctx *ctx, int ISPACE, int W, int G, int NLAYIN,
     r.tau = ctx->misc.as<double>();
     r.cont = nullptr;
     r.emi = emi_t;
-    r.wave = (const double *)d[4];
+    r.wave = wave;
     r.delg = nullptr;
-    r.nlayin = (const int32_t *)di;
-    r.layinc = (const int32_t *)di + 1;
-    r.scale = (const double *)dd;
-    r.emtemp = (const double *)d[2];
-    r.lay_press = (const double *)d[3];
-    r.tsurf = (const double *)dd + Li;
-    r.emissivity = (const double *)d[5]; r.solflux = (const double *)d[6]; r.reflectance = (const double *)d[7];
+    r.nlayin = di;
+    r.layinc = di + 1;
+    r.scale = dd;
+    r.emtemp = temp;
+    r.lay_press = press;
+    r.tsurf = dd + Li;
+    r.emissivity = emis; r.solflux = solflux; r.reflectance = refl;
     r.xfac = nullptr;
-    r.sol_ang = (const double *)dd + Li + 1; r.emiss_ang = (const double *)dd + Li + 2;
+    r.sol_ang = dd + Li + 1; r.emiss_ang = dd + Li + 2;
     r.out = ctx->tmp_out.as<double>();
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = Li; r.P = 1; r.LIMAX = Li; r.ispace = ISPACE; r.per_g = 1;
-    rc = launch_rt(ctx, r, 1);
+    const int rc = launch_rt(ctx, r, 1);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)W * G * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1323,7 +1327,7 @@ int ansfm_thermal_emission(ansfm_ctx *ctx, int ISPACE, int W, int G, int NLAYIN,
 /* ------------------------------------------------------------------------------------------ */
 static int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double *dkin, int W, int Wpad,
                            int G, int S, int L, int n_models, const LayerInterp *li, const double *amount,
-                           const double *del_g_dev, const double *del_g_host, double *tau, double *dk)
+                           const double *del_g_dev, const double *del_g_host, double *tau, double *dk, bool generic)
 {
     OverlapGParams pg;
     memset(&pg, 0, sizeof pg);
@@ -1355,8 +1359,7 @@ static int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const
     // the gas selection mask (ansfm_set_gradient_gases) has one bit per gas and bit 31 for temperature
     if (NP1 > 32) FAIL(ANSFM_ERR_UNSUPPORTED, "gradient path supports at most 31 spectroscopic gases");
     // fast path: every k(g) non-decreasing (tables: checked at upload; array-level seam: in the kernel, rerun otherwise)
-    const bool sorted = !ctx->force_generic && (from_k || ctx->monotone);
-    ctx->force_generic = 0;            // one-shot request of the rerun wrappers: never survives an error return
+    const bool sorted = !generic && (from_k || ctx->monotone);
     const size_t lds = (size_t)(2 * G + 1) * kWave * sizeof(double) + (size_t)(2 * kMaxG + 2) * sizeof(double) + kMaxG * sizeof(float) +
                        (sorted ? 0 : (size_t)2 * G * kWave);
     int per_cu = (int)((160 * 1024) / lds);
@@ -1408,23 +1411,24 @@ int ansfm_set_shared_gas_gradient(ansfm_ctx *ctx, int L, const double *dTAU_WL)
     if (!ctx->have_table || L <= 0) FAIL(ANSFM_ERR_INVALID, "set_shared_gas_gradient: upload a table first; L > 0");
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad;
-    const void *d;
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[12], dTAU_WL, (size_t)W * L * sizeof(double), &d))) return rc;
+    Stager st{ctx, 12};
+    const double *d = st.up(dTAU_WL, (size_t)W * L);
+    if (st.rc) return st.rc;
     HIPCHK(ctx->dcont_gas.reserve((size_t)L * Wpad * sizeof(double)));
-    launch_w_to_last(ctx->stream, 1u, (const double *)d, ctx->dcont_gas.as<double>(), W, Wpad, 1, L, 0, 0.0);
+    launch_w_to_last(ctx->stream, 1u, d, ctx->dcont_gas.as<double>(), W, Wpad, 1, L, 0, 0.0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));      // the staging buffer is reused
     ctx->dcont_gas_L = L;
     return ANSFM_OK;
 }
 
-int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                  const double *lay_temp, const double *amount, const double *taucont,
-                                  const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map_host, int P,
-                                  int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                  const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                  const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF)
+// transmission: the path transmission and its gradients (ansfm_cirsradg_ck_transmission)
+static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                        const double *lay_temp, const double *amount, const double *taucont,
+                                        const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map_host, int P,
+                                        int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                        const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                        const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF, bool transmission)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg: upload a k-table first");
@@ -1434,16 +1438,12 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
         FAIL(ANSFM_ERR_INVALID, "cirsradg: bad argument (NPAR <= 256)");
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, NP1 = S + 1;
-    HIPCHK(ctx->li.reserve((size_t)n_models * L * sizeof(LayerInterp)));
-    HIPCHK(ctx->tau.reserve((size_t)n_models * L * G * Wpad * sizeof(double)));
     HIPCHK(ctx->dkbuf.reserve((size_t)n_models * L * NP1 * G * Wpad * sizeof(double)));
     HIPCHK(ctx->trold_ws.reserve((size_t)n_models * P * (LIMAX + 1) * G * Wpad * sizeof(double)));
     HIPCHK(ctx->dspec_i.reserve((size_t)n_models * P * NPAR * LIMAX * Wpad * sizeof(double)));
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)n_models * L, 128)), dim3(128), 0, ctx->stream, n_models * L,
-                       lay_press_pa, lay_temp, ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
-                       101325.0, ctx->grid_f32, ctx->li.as<LayerInterp>());
-    HIPCHK(hipGetLastError());
+    int rc;
+    if ((rc = gas_prep(ctx, n_models * L, lay_press_pa, lay_temp))) return rc;
     const double *cont_t = nullptr, *dcont_t = nullptr;
     if (taucont) {
         HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
@@ -1457,18 +1457,8 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    int rc;
-    if (ctx->is_lbl) {   // calc_klblg + :3812-3814
-        if ((rc = lbl_prep_fwd(ctx, n_models * L, lay_press_pa, lay_temp, 101325.0, 1))) return rc;
-        hipLaunchKernelGGL(k_lbl_tau, dim3(nblk((size_t)n_models * L * Wpad, 256)), dim3(256), 0, ctx->stream,
-                           ctx->lnK.as<double>(), Wpad, ctx->NT, S, L, n_models, ctx->lbl_li.as<LblInterp>(), amount,
-                           ctx->tau.as<double>(), ctx->dkbuf.as<double>());
-        HIPCHK(hipGetLastError());
-    } else {
-        rc = launch_overlapg(ctx, false, nullptr, nullptr, W, Wpad, G, S, L, n_models, ctx->li.as<LayerInterp>(), amount,
-                             ctx->d_delg.as<double>(), ctx->h_delg.data(), ctx->tau.as<double>(), ctx->dkbuf.as<double>());
-        if (rc != ANSFM_OK) return rc;
-    }
+    // calc_klblg + :3812-3814 for LBL tables
+    if ((rc = gas_tau(ctx, n_models, L, lay_press_pa, lay_temp, amount, false, ctx->dkbuf.as<double>()))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
     RtGParams q;
     memset(&q, 0, sizeof q);
@@ -1482,7 +1472,7 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
     r.emissivity = EMISSIVITY; r.xfac = xfac;
     r.out = SPECOUT;
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0;
-    r.mode = ctx->rt_mode == 1 ? 1 : 0;      // 1: path transmission and its gradients (ansfm_cirsradg_ck_transmission)
+    r.mode = transmission ? 1 : 0;
     q.dk = ctx->dkbuf.as<double>();
     q.dcont = dcont_t;
     q.dcont_gas = nullptr;
@@ -1534,12 +1524,24 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
     return ANSFM_OK;
 }
 
-int ansfm_cirsradg_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                              const double *lay_temp, const double *amount, const double *taucont,
-                              const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P, int LIMAX,
-                              const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP,
-                              const double *TSURF, const double *EMISSIVITY, const double *xfac, double *SPECOUT,
-                              double *dSPECOUT, double *dTSURF)
+int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                  const double *lay_temp, const double *amount, const double *taucont,
+                                  const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map_host, int P,
+                                  int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                  const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                  const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF)
+{
+    return cirsradg_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR,
+                                        igas_map_host, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, xfac, SPECOUT,
+                                        dSPECOUT, dTSURF, false);
+}
+
+static int cirsradg_ck_thermal_host(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                    const double *lay_temp, const double *amount, const double *taucont, const double *dtaucon,
+                                    int NVMR, int NPAR, const int32_t *igas_map, int P, int LIMAX, const int32_t *NLAYIN,
+                                    const int32_t *LAYINC, const double *SCALE, const double *EMTEMP, const double *TSURF,
+                                    const double *EMISSIVITY, const double *xfac, double *SPECOUT, double *dSPECOUT,
+                                    double *dTSURF, bool transmission)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg: upload a k-table first");
@@ -1548,40 +1550,40 @@ int ansfm_cirsradg_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, c
                                 "device for ansfm_map2pro)");
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, S = ctx->S;
-    const size_t D = sizeof(double);
-    const void *d[16];
-    int i = 0, rc;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(lay_press_pa, (size_t)n_models * L * D);            // 0
-    UP(lay_temp, (size_t)n_models * L * D);                // 1
-    UP(amount, (size_t)n_models * S * L * D);              // 2
-    UP(taucont, (size_t)n_models * W * L * D);             // 3
-    UP(dtaucon, (size_t)n_models * W * NPAR * L * D);      // 4
-    UP(NLAYIN, (size_t)P * sizeof(int32_t));               // 5
-    UP(LAYINC, (size_t)LIMAX * P * sizeof(int32_t));       // 6
-    UP(SCALE, (size_t)n_models * LIMAX * P * D);           // 7
-    UP(EMTEMP, (size_t)n_models * LIMAX * P * D);          // 8
-    UP(TSURF, (size_t)n_models * D);                       // 9
-    UP(EMISSIVITY, (size_t)W * D);                         // 10
-    UP(xfac, (size_t)W * D);                               // 11
-#undef UP
+    const size_t D = sizeof(double), nl = (size_t)n_models * L, nlp = (size_t)n_models * LIMAX * P;
+    Stager st{ctx};
+    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
+                 *cont = st.up(taucont, nl * W), *dcont = st.up(dtaucon, nl * W * NPAR);
+    const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
+    const double *scale = st.up(SCALE, nlp), *emtemp = st.up(EMTEMP, nlp), *tsurf = st.up(TSURF, n_models),
+                 *emis = st.up(EMISSIVITY, W), *xf = st.up(xfac, W);
+    if (st.rc) return st.rc;
     const size_t nsp = (size_t)n_models * W * P, ndsp = (size_t)n_models * W * NPAR * LIMAX * P;
     HIPCHK(ctx->tmp_out.reserve((2 * nsp) * D));
     HIPCHK(ctx->dspec_ref.reserve(ndsp * D));     // kept on the device for ansfm_map2pro(dSPECIN = NULL)
     ctx->dspec_dims[0] = 0;
     double *o_spec = ctx->tmp_out.as<double>(), *o_dts = o_spec + nsp;
-    rc = ansfm_cirsradg_ck_thermal_dev(ctx, ISPACE, n_models, L, (const double *)d[0], (const double *)d[1],
-                                       (const double *)d[2], (const double *)d[3], (const double *)d[4], NVMR, NPAR,
-                                       igas_map, P, LIMAX, (const int32_t *)d[5], (const int32_t *)d[6],
-                                       (const double *)d[7], (const double *)d[8], (const double *)d[9],
-                                       (const double *)d[10], (const double *)d[11], o_spec, ctx->dspec_ref.as<double>(),
-                                       o_dts);
+    const int rc = cirsradg_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, press, temp, am, cont, dcont, NVMR, NPAR, igas_map, P,
+                                                LIMAX, nlayin, layinc, scale, emtemp, tsurf, emis, xf, o_spec,
+                                                ctx->dspec_ref.as<double>(), o_dts, transmission);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(SPECOUT, o_spec, nsp * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(dTSURF, o_dts, nsp * D, hipMemcpyDeviceToHost, ctx->stream));
     if (dSPECOUT) HIPCHK(hipMemcpyAsync(dSPECOUT, ctx->dspec_ref.p, ndsp * D, hipMemcpyDeviceToHost, ctx->stream));
     if (n_models == 1) { ctx->dspec_dims[0] = ctx->W; ctx->dspec_dims[1] = NPAR; ctx->dspec_dims[2] = LIMAX; ctx->dspec_dims[3] = P; }
     return check_unsorted(ctx);
+}
+
+int ansfm_cirsradg_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                              const double *lay_temp, const double *amount, const double *taucont,
+                              const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P, int LIMAX,
+                              const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP,
+                              const double *TSURF, const double *EMISSIVITY, const double *xfac, double *SPECOUT,
+                              double *dSPECOUT, double *dTSURF)
+{
+    return cirsradg_ck_thermal_host(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
+                                    P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, xfac, SPECOUT, dSPECOUT, dTSURF,
+                                    false);
 }
 
 int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa,
@@ -1593,13 +1595,10 @@ int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const do
     CHECK_CTX(ctx);
     if (n_models <= 0 || P <= 0 || !SCALE || !SPECOUT || !dSPECOUT) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transmission: bad argument");
     std::vector<double> tsurf((size_t)n_models, -1.0), dts((size_t)n_models * ctx->W * P);
-    ctx->rt_mode = 1;
     // no emission in this branch: SCALE stands in for the (unused) emission temperatures, dTSURF is identically zero
-    const int rc = ansfm_cirsradg_ck_thermal(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR,
-                                             igas_map, P, LIMAX, NLAYIN, LAYINC, SCALE, SCALE, tsurf.data(), nullptr, xfac,
-                                             SPECOUT, dSPECOUT, dts.data());
-    ctx->rt_mode = 0;
-    return rc;
+    return cirsradg_ck_thermal_host(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, P,
+                                    LIMAX, NLAYIN, LAYINC, SCALE, SCALE, tsurf.data(), nullptr, xfac, SPECOUT, dSPECOUT, dts.data(),
+                                    true);
 }
 
 int ansfm_k_overlapg(ansfm_ctx *ctx, int W, int G, int L, int S, const double *del_g, const double *k,
@@ -1611,35 +1610,26 @@ int ansfm_k_overlapg(ansfm_ctx *ctx, int W, int G, int L, int S, const double *d
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave), NP1 = S + 1;
     const size_t nk = (size_t)W * G * L * S;
-    const void *dkk, *ddk, *dam, *ddg;
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], k, nk * sizeof(double), &dkk))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[3], dkdT, nk * sizeof(double), &ddk))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], amount, (size_t)S * L * sizeof(double), &dam))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], del_g, (size_t)G * sizeof(double), &ddg))) return rc;
+    Stager st{ctx};
+    const double *dkk = st.up(k, nk), *dam = st.up(amount, (size_t)S * L), *ddg = st.up(del_g, G), *ddk = st.up(dkdT, nk);
+    if (st.rc) return st.rc;
     HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     const size_t nkin = (size_t)S * L * G * Wpad;
     HIPCHK(ctx->tmp_in.reserve(nkin * sizeof(double)));
     HIPCHK(ctx->tmp_in2.reserve(nkin * sizeof(double)));
-    hipLaunchKernelGGL(k_kin_permute, dim3(nblk(nkin, 256)), dim3(256), 0, ctx->stream, (const double *)dkk,
-                       ctx->tmp_in.as<double>(), W, Wpad, G, L, S);
-    hipLaunchKernelGGL(k_kin_permute, dim3(nblk(nkin, 256)), dim3(256), 0, ctx->stream, (const double *)ddk,
-                       ctx->tmp_in2.as<double>(), W, Wpad, G, L, S);
+    hipLaunchKernelGGL(k_kin_permute, dim3(nblk(nkin, 256)), dim3(256), 0, ctx->stream, dkk, ctx->tmp_in.as<double>(), W, Wpad, G,
+                       L, S);
+    hipLaunchKernelGGL(k_kin_permute, dim3(nblk(nkin, 256)), dim3(256), 0, ctx->stream, ddk, ctx->tmp_in2.as<double>(), W, Wpad, G,
+                       L, S);
     HIPCHK(hipGetLastError());
     HIPCHK(ctx->misc.reserve((size_t)L * G * Wpad * sizeof(double)));
     HIPCHK(ctx->dkbuf.reserve((size_t)L * NP1 * G * Wpad * sizeof(double)));
-    for (int pass = 0; pass < 2; ++pass) {
-        ctx->force_generic = pass;       // pass 1 only if the fast merge met an unsorted k-distribution
-        HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-        rc = launch_overlapg(ctx, true, ctx->tmp_in.as<double>(), ctx->tmp_in2.as<double>(), W, Wpad, G, S, L, 1, nullptr,
-                             (const double *)dam, (const double *)ddg, del_g, ctx->misc.as<double>(), ctx->dkbuf.as<double>());
-        ctx->force_generic = 0;
-        if (rc) return rc;
-        int flag = 0;
-        if ((rc = read_unsorted(ctx, &flag))) return rc;
-        if (!flag) break;
-    }
+    const int rc = rerun_unsorted(ctx, [&](bool generic) {
+        return launch_overlapg(ctx, true, ctx->tmp_in.as<double>(), ctx->tmp_in2.as<double>(), W, Wpad, G, S, L, 1, nullptr, dam, ddg,
+                               del_g, ctx->misc.as<double>(), ctx->dkbuf.as<double>(), generic);
+    });
+    if (rc) return rc;
     const size_t nout = (size_t)W * G * L, ndk = nout * NP1;
     HIPCHK(ctx->tmp_out.reserve(nout * sizeof(double)));
     HIPCHK(ctx->tmp_out2.reserve(ndk * sizeof(double)));
@@ -1816,22 +1806,16 @@ static int ils_conv_impl(ansfm_ctx *ctx, int nwave, const double *vwave, int ny,
         }
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double);
-    const void *d[8] = {nullptr};
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], vwave, nwave * D, &d[0]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], y, (size_t)nwave * ny * D, &d[1]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], dydx, (size_t)nwave * nx * D, &d[2]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[3], vconv, nconv * D, &d[3]))) return rc;
-    if (filter) {
-        if ((rc = h2d(ctx, ctx->hb[4], nfil, nconv * sizeof(int32_t), &d[4]))) return rc;
-        if ((rc = h2d(ctx, ctx->hb[5], vfil, (size_t)nfilmax * nconv * D, &d[5]))) return rc;
-        if ((rc = h2d(ctx, ctx->hb[6], afil, (size_t)nfilmax * nconv * D, &d[6]))) return rc;
-    }
-    HIPCHK(ctx->tmp_out.reserve(((size_t)nconv * (nx + ny)) * D));
     ConvParams p;
     memset(&p, 0, sizeof p);
-    p.vwave = (const double *)d[0]; p.y = (const double *)d[1]; p.dydx = (const double *)d[2]; p.vconv = (const double *)d[3];
-    p.nfil = (const int32_t *)d[4]; p.vfil = (const double *)d[5]; p.afil = (const double *)d[6];
+    Stager st{ctx};
+    p.vwave = st.up(vwave, nwave); p.y = st.up(y, (size_t)nwave * ny); p.dydx = st.up(dydx, (size_t)nwave * nx);
+    p.vconv = st.up(vconv, nconv);
+    if (filter) {
+        p.nfil = st.up(nfil, nconv); p.vfil = st.up(vfil, (size_t)nfilmax * nconv); p.afil = st.up(afil, (size_t)nfilmax * nconv);
+    }
+    if (st.rc) return st.rc;
+    HIPCHK(ctx->tmp_out.reserve(((size_t)nconv * (nx + ny)) * D));
     p.yout = ctx->tmp_out.as<double>(); p.gradout = p.yout + (size_t)nconv * ny;
     p.nwave = nwave; p.nx = nx; p.ny = ny; p.nconv = nconv; p.ishape = ishape; p.hamming_rule = hamming_rule;
     p.filter = filter ? (integrate ? 3 : bracket ? 2 : 1) : 0;
@@ -1959,29 +1943,20 @@ int ansfm_calc_tau_cia(ansfm_ctx *ctx, int W, const double *WAVEN, int NWC, cons
     }
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double);
-    const void *d[12] = {nullptr};
-    int rc;
     double cmin = cia_waven[0], cmax = cia_waven[0];
     for (int i = 1; i < NWC; ++i) { cmin = std::min(cmin, cia_waven[i]); cmax = std::max(cmax, cia_waven[i]); }
     const int covers = (cmin <= WAVEN[0] && cmax >= WAVEN[W - 1]) ? 1 : 0;      // :4671
-    if ((rc = h2d(ctx, ctx->hb[0], WAVEN, W * D, &d[0]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], cia_waven, NWC * D, &d[1]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], K_CIA, (size_t)NPAIR * NPE * NT * NWC * D, &d[2]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[3], lay.data(), L * sizeof(CiaLayer), &d[3]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[4], igas1, NPAIR * sizeof(int32_t), &d[4]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[5], igas2, NPAIR * sizeof(int32_t), &d[5]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[6], q, (size_t)L * NVMR * D, &d[6]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[7], ico2 >= 0 ? k_co2 : nullptr, W * D, &d[7]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[8], in2 >= 0 ? k_n2n2 : nullptr, W * D, &d[8]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[9], (in2 >= 0 && ih2 >= 0) ? k_n2h2 : nullptr, W * D, &d[9]))) return rc;
+    CiaParams p;
+    memset(&p, 0, sizeof p);
+    Stager st{ctx};
+    p.waven = st.up(WAVEN, W); p.cia_waven = st.up(cia_waven, NWC); p.K = st.up(K_CIA, (size_t)NPAIR * NPE * NT * NWC);
+    p.lay = st.up(lay.data(), L); p.g1 = st.up(igas1, NPAIR); p.g2 = st.up(igas2, NPAIR); p.q = st.up(q, (size_t)L * NVMR);
+    p.k_co2 = st.up(ico2 >= 0 ? k_co2 : nullptr, W); p.k_n2n2 = st.up(in2 >= 0 ? k_n2n2 : nullptr, W);
+    p.k_n2h2 = st.up((in2 >= 0 && ih2 >= 0) ? k_n2h2 : nullptr, W);
+    if (st.rc) return st.rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));                     // `lay` is a host temporary
     const size_t nt = (size_t)W * L, nd = dTAUCIA ? nt * (NVMR + 2) : 0;
     HIPCHK(ctx->tmp_out.reserve((nt + nd) * D));
-    CiaParams p;
-    memset(&p, 0, sizeof p);
-    p.waven = (const double *)d[0]; p.cia_waven = (const double *)d[1]; p.K = (const double *)d[2];
-    p.lay = (const CiaLayer *)d[3]; p.g1 = (const int32_t *)d[4]; p.g2 = (const int32_t *)d[5]; p.q = (const double *)d[6];
-    p.k_co2 = (const double *)d[7]; p.k_n2n2 = (const double *)d[8]; p.k_n2h2 = (const double *)d[9];
     p.tau = ctx->tmp_out.as<double>(); p.dtau = dTAUCIA ? p.tau + nt : nullptr;
     p.W = W; p.NWC = NWC; p.NPAIR = NPAIR; p.NPE = NPE; p.NT = NT; p.L = L; p.NVMR = NVMR; p.covers = covers;
     p.ico2 = ico2; p.in2 = in2; p.ih2 = ih2;
@@ -2006,15 +1981,12 @@ int ansfm_calc_tau_rayleigh(ansfm_ctx *ctx, int mode, int ISPACE, int W, const d
         FAIL(ANSFM_ERR_INVALID, "calc_tau_rayleigh: bad argument (mode = IRAY 1, 2, 4 or 12 for calc_tau_rayleighv)");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double), nt = (size_t)W * L;
-    const void *d[3] = {nullptr};
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], WAVEC, W * D, &d[0]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], TOTAM, L * D, &d[1]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], f4, mode == 4 ? (size_t)L * 4 * D : 0, &d[2]))) return rc;
-    HIPCHK(ctx->tmp_out.reserve(2 * nt * D));
     RayParams p;
     memset(&p, 0, sizeof p);
-    p.wavec = (const double *)d[0]; p.totam = (const double *)d[1]; p.f4 = (const double *)d[2];
+    Stager st{ctx};
+    p.wavec = st.up(WAVEC, W); p.totam = st.up(TOTAM, L); p.f4 = st.up(f4, mode == 4 ? (size_t)L * 4 : 0);
+    if (st.rc) return st.rc;
+    HIPCHK(ctx->tmp_out.reserve(2 * nt * D));
     p.tau = ctx->tmp_out.as<double>(); p.dtau = p.tau + nt;
     p.W = W; p.L = L; p.mode = mode; p.ispace = ISPACE;
     hipLaunchKernelGGL(k_tau_rayleigh, dim3(nblk((size_t)W * L, 128)), dim3(128), 0, ctx->stream, p);
@@ -2050,16 +2022,15 @@ static int rayleigh_batch_impl(ansfm_ctx *ctx, int mode, int ISPACE, int n_model
         FAIL(ANSFM_ERR_INVALID, "calc_tau_rayleigh_batch_dev: bad argument (mode = IRAY 1, 2, 4 or 12 for calc_tau_rayleighv)");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double), nl = (size_t)n_models * L;
-    const void *d[2] = {nullptr, nullptr};
-    int rc;
-    if (dev_in) { d[0] = TOTAM; d[1] = (mode == 4) ? f4 : nullptr; }
-    else {
-        if ((rc = h2d(ctx, ctx->hb[1], TOTAM, nl * D, &d[0]))) return rc;
-        if ((rc = h2d(ctx, ctx->hb[2], f4, mode == 4 ? nl * 4 * D : 0, &d[1]))) return rc;
-    }
     RayParams p;
     memset(&p, 0, sizeof p);
-    p.wavec = ctx->d_wave.as<double>(); p.totam = (const double *)d[0]; p.f4 = (const double *)d[1];
+    if (dev_in) { p.totam = TOTAM; p.f4 = (mode == 4) ? f4 : nullptr; }
+    else {
+        Stager st{ctx, 1};
+        p.totam = st.up(TOTAM, nl); p.f4 = st.up(f4, mode == 4 ? nl * 4 : 0);
+        if (st.rc) return st.rc;
+    }
+    p.wavec = ctx->d_wave.as<double>();
     p.tau = TAURAY_dev; p.dtau = nullptr;
     p.W = ctx->W; p.L = (int)nl; p.mode = mode; p.ispace = ISPACE; p.Lm = L;
     hipLaunchKernelGGL(k_tau_rayleigh, dim3(nblk((size_t)ctx->W * nl, 128)), dim3(128), 0, ctx->stream, p);
@@ -2130,20 +2101,15 @@ int ansfm_calc_tau_dust(ansfm_ctx *ctx, int W, const double *WAVEC, int NWS, con
             notaknot_coeffs(NWS, SWAVE, KSCA + i, NDUST, coef.data() + ((size_t)NDUST + i) * (NWS - 1) * 3);
         }
     }
-    const void *d[6] = {nullptr};
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], WAVEC, W * D, &d[0]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], SWAVE, NWS * D, &d[1]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], KEXT, (size_t)NWS * NDUST * D, &d[2]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[3], KSCA, (size_t)NWS * NDUST * D, &d[3]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[4], CONT, (size_t)L * NDUST * D, &d[4]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[5], cubic ? coef.data() : nullptr, coef.size() * D, &d[5]))) return rc;
-    HIPCHK(ctx->tmp_out.reserve(4 * nt * D));
     DustParams p;
     memset(&p, 0, sizeof p);
-    p.wavec = (const double *)d[0]; p.swave = (const double *)d[1]; p.kext = (const double *)d[2]; p.ksca = (const double *)d[3];
-    p.cont = (const double *)d[4];
-    p.cext = (const double *)d[5]; p.csca = p.cext ? p.cext + (size_t)NDUST * (NWS - 1) * 3 : nullptr;
+    Stager st{ctx};
+    p.wavec = st.up(WAVEC, W); p.swave = st.up(SWAVE, NWS); p.kext = st.up(KEXT, (size_t)NWS * NDUST);
+    p.ksca = st.up(KSCA, (size_t)NWS * NDUST); p.cont = st.up(CONT, (size_t)L * NDUST);
+    p.cext = st.up(cubic ? coef.data() : nullptr, coef.size());
+    if (st.rc) return st.rc;
+    HIPCHK(ctx->tmp_out.reserve(4 * nt * D));
+    p.csca = p.cext ? p.cext + (size_t)NDUST * (NWS - 1) * 3 : nullptr;
     p.taudust = ctx->tmp_out.as<double>(); p.tauclscat = p.taudust + nt; p.dtaudust = p.tauclscat + nt; p.dtauclscat = p.dtaudust + nt;
     p.W = W; p.NWS = NWS; p.NDUST = NDUST; p.L = L; p.cubic = cubic;
     hipLaunchKernelGGL(k_tau_dust, dim3(nblk((size_t)W, 128), (unsigned)NDUST), dim3(128), 0, ctx->stream, p);
@@ -2184,27 +2150,19 @@ int ansfm_kdist_bins(ansfm_ctx *ctx, int ncalc, const double *wavecalc, const do
     if (total > 0x7fffffffLL) FAIL(ANSFM_ERR_UNSUPPORTED, "kdist_bins: more than 2^31 points in one call; split the bins");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double);
-    const void *d[10] = {nullptr};
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], wavecalc, ncalc * D, &d[0]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], kabs, ncalc * D, &d[1]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], i0.data(), nbin * sizeof(int32_t), &d[2]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[3], off.data(), (nbin + 1) * sizeof(int64_t), &d[3]))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[4], g_ord, NG * D, &d[4]))) return rc;
+    KdistParams p;
+    memset(&p, 0, sizeof p);
+    Stager st{ctx};
+    p.wavecalc = st.up(wavecalc, ncalc); p.kabs = st.up(kabs, ncalc); p.i0 = st.up(i0.data(), nbin);
+    p.off = st.up(off.data(), nbin + 1); p.g_ord = st.up(g_ord, NG);
     if (nfil) {
-        if ((rc = h2d(ctx, ctx->hb[5], wcen, nbin * D, &d[5]))) return rc;
-        if ((rc = h2d(ctx, ctx->hb[6], nfil, nbin * sizeof(int32_t), &d[6]))) return rc;
-        if ((rc = h2d(ctx, ctx->hb[7], dfil, (size_t)nfilmax * nbin * D, &d[7]))) return rc;
-        if ((rc = h2d(ctx, ctx->hb[8], afil, (size_t)nfilmax * nbin * D, &d[8]))) return rc;
+        p.wcen = st.up(wcen, nbin); p.nfil = st.up(nfil, nbin); p.dfil = st.up(dfil, (size_t)nfilmax * nbin);
+        p.afil = st.up(afil, (size_t)nfilmax * nbin);
     }
+    if (st.rc) return st.rc;
     HIPCHK(ctx->tmp_in.reserve((size_t)total * D));
     HIPCHK(ctx->tmp_in2.reserve((size_t)total * D));
     HIPCHK(ctx->tmp_out.reserve((size_t)nbin * NG * D));
-    KdistParams p;
-    memset(&p, 0, sizeof p);
-    p.wavecalc = (const double *)d[0]; p.kabs = (const double *)d[1]; p.i0 = (const int32_t *)d[2]; p.off = (const int64_t *)d[3];
-    p.g_ord = (const double *)d[4]; p.wcen = (const double *)d[5]; p.nfil = (const int32_t *)d[6];
-    p.dfil = (const double *)d[7]; p.afil = (const double *)d[8];
     p.keys = ctx->tmp_in.as<double>(); p.vals = ctx->tmp_in2.as<double>(); p.kout = ctx->tmp_out.as<double>();
     p.dv = wavecalc[1] - wavecalc[0];                                     // delvarray (:3647)
     p.nbin = nbin; p.NG = NG;
@@ -2311,10 +2269,16 @@ static int ms_side_streams(ansfm_ctx *ctx, int nev)
     return ANSFM_OK;
 }
 
+// What ms_launch runs: everything; everything but the phase matrices and Hansen factors, which the previous call left in
+// ctx->misc (the models of a batch one by one: ansfm_cirsrad_ck_scatter_batch without the layer cache); or those two alone (the
+// batch path, which launches its own chains)
+enum class MsRun { all, reuse_walk, prepare_only };
+
 static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth, int ngeom, const double *sol_angs,
                      const double *emiss_angs, const double *aphis, int lowbc, int nmu, const double *mu1, const double *wt1,
-                     int nf, int ng, int nlay, int nphi, int iray, int imie, bool prepare_only = false)
+                     int nf, int ng, int nlay, int nphi, int iray, int imie, MsRun run)
 {
+    const bool prepare_only = run == MsRun::prepare_only;
     if (nmu > kMsMaxMu || ngeom > kMsMaxPath || ncont > 60)
         FAIL(ANSFM_ERR_UNSUPPORTED, "scloud11wave_core: nmu <= 32, npath <= 16 per call supported");
     int nless = 0, nmore = 0;
@@ -2355,10 +2319,10 @@ static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth,
     if (ng == 1 && prepare_only) return ANSFM_OK;
     const bool windowed = nwin < nwave;
     ctx->ms_windows = (nwave + nwin - 1) / nwin; ctx->ms_window_w = nwin;
-    // reuse: the models of a batch run one by one (ansfm_cirsrad_ck_scatter_batch without the layer cache) share the phase
-    // functions, so the phase matrices and the Hansen factors the first model left in ctx->misc stand for the others -- the
-    // walk is sequential and, at few streams, most of a call.  Not with several windows: ctx->misc holds the last two only.
-    const bool reuse = ctx->ms_reuse_walk != 0 && !prepare_only && !windowed;
+    // reuse: the models of a batch run one by one share the phase functions, so the phase matrices and the Hansen factors the
+    // first model left in ctx->misc stand for the others -- the walk is sequential and, at few streams, most of a call.  Not
+    // with several windows: ctx->misc holds the last two only.
+    const bool reuse = run == MsRun::reuse_walk && !windowed;
     // three windows in rotation and the carry of the walk between them, or the whole axis
     const size_t nph_w = (size_t)nwin * (nf + 1) * p.ncomp * nn, nfc_w = (size_t)nwin * p.ncomp * nn;
     const size_t per_buf = 2 * nph_w + nfc_w;
@@ -2555,39 +2519,30 @@ int ansfm_scloud11wave_core(ansfm_ctx *ctx, int ncont, int nwave, int nth, const
     HIPCHK(hipSetDevice(ctx->device));
     MsParams p;
     memset(&p, 0, sizeof p);
-    const size_t D = sizeof(double);
-    const void *d[10];
-    int i = 0, rc;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(phasarr, (size_t)ncont * nwave * 2 * nth * D);           // 0
-    UP(radg, (size_t)nwave * nmu * D);                          // 1
-    UP(solar, (size_t)nwave * D);                               // 2
-    UP(brdf_matrix, (size_t)nwave * nmu * nmu * (nf + 1) * D);  // 3
-    UP(bnu, (size_t)nwave * nlay * D);                          // 4
-    UP(taus, (size_t)nwave * ng * nlay * D);                    // 5
-    UP(tauray, (size_t)nwave * nlay * D);                       // 6
-    UP(omegas_s, (size_t)nwave * ng * nlay * D);                // 7
-    UP(lfrac, (size_t)nwave * ncont * nlay * D);                // 8
-#undef UP
-    p.phasarr = (const double *)d[0]; p.radg = (const double *)d[1]; p.solar = (const double *)d[2];
-    p.brdf = (const double *)d[3]; p.bnu = (const double *)d[4]; p.taus = (const double *)d[5];
-    p.tauray = (const double *)d[6]; p.omegas = (const double *)d[7]; p.lfrac = (const double *)d[8];
+    const size_t D = sizeof(double), nw = nwave;
+    Stager st{ctx};
+    p.phasarr = st.up(phasarr, (size_t)ncont * nw * 2 * nth); p.radg = st.up(radg, nw * nmu); p.solar = st.up(solar, nw);
+    p.brdf = st.up(brdf_matrix, nw * nmu * nmu * (nf + 1)); p.bnu = st.up(bnu, nw * nlay); p.taus = st.up(taus, nw * ng * nlay);
+    p.tauray = st.up(tauray, nw * nlay); p.omegas = st.up(omegas_s, nw * ng * nlay); p.lfrac = st.up(lfrac, nw * ncont * nlay);
+    int rc = st.rc;
+    if (rc) return rc;
     if (ms_pad16(nmu) && (rc = ms_pad_inputs(ctx, nmu, (size_t)nwave, (size_t)nwave, nf, &p.radg, &p.brdf))) return rc;
     if ((rc = ms_launch(ctx, p, ncont, nwave, nth, ngeom, sol_angs, emiss_angs, aphis, lowbc, nmu, mu1, wt1, nf, ng, nlay,
-                        nphi, iray, imie)))
+                        nphi, iray, imie, MsRun::all)))
         return rc;
     HIPCHK(hipMemcpyAsync(rad, ctx->tmp_out.p, (size_t)ngeom * ng * nwave * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return ANSFM_OK;
 }
 
-int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
-                             const double *amount, const double *taucia, const double *taudust, const double *tauray,
-                             const double *tauscat, int ncont, int nth, const double *phasarr, const double *lfrac,
-                             const double *radg, int ngeom, const double *sol_angs, const double *emiss_angs,
-                             const double *aphis, const double *solar, int lowbc, const double *brdf_matrix, int nmu,
-                             const double *mu1, const double *wt1, int nf, int nphi, int iray, int imie, const double *xfac,
-                             double *SPECOUT, double *SPEC_G)
+// reuse_walk: the phase matrices and Hansen factors of the previous call stand (the models of a batch one by one)
+static int cirsrad_ck_scatter_impl(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
+                                   const double *amount, const double *taucia, const double *taudust, const double *tauray,
+                                   const double *tauscat, int ncont, int nth, const double *phasarr, const double *lfrac,
+                                   const double *radg, int ngeom, const double *sol_angs, const double *emiss_angs,
+                                   const double *aphis, const double *solar, int lowbc, const double *brdf_matrix, int nmu,
+                                   const double *mu1, const double *wt1, int nf, int nphi, int iray, int imie, const double *xfac,
+                                   double *SPECOUT, double *SPEC_G, bool reuse_walk)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter: upload a k-table first");
@@ -2598,62 +2553,32 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
     const size_t D = sizeof(double), WL = (size_t)W * L;
-    const void *d[14];
-    int i = 0, rc;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(lay_press_pa, (size_t)L * D);                            // 0
-    UP(lay_temp, (size_t)L * D);                                // 1
-    UP(amount, (size_t)S * L * D);                              // 2
-    UP(taucia, WL * D);                                         // 3
-    UP(taudust, WL * D);                                        // 4
-    UP(tauray, WL * D);                                         // 5
-    UP(tauscat, WL * D);                                        // 6
-    UP(phasarr, (size_t)ncont * W * 2 * nth * D);               // 7
-    UP(lfrac, (size_t)W * ncont * L * D);                       // 8
-    UP(radg, (size_t)W * nmu * D);                              // 9
-    UP(solar, (size_t)W * D);                                   // 10
-    UP(brdf_matrix, (size_t)W * nmu * nmu * (nf + 1) * D);      // 11
-    UP(xfac, (size_t)W * D);                                    // 12
-#undef UP
+    Stager st{ctx};
+    const double *press = st.up(lay_press_pa, L), *temp = st.up(lay_temp, L), *am = st.up(amount, (size_t)S * L),
+                 *cia = st.up(taucia, WL), *dust = st.up(taudust, WL), *ray = st.up(tauray, WL), *sca = st.up(tauscat, WL),
+                 *phas = st.up(phasarr, (size_t)ncont * W * 2 * nth), *lf = st.up(lfrac, WL * ncont), *rg = st.up(radg, (size_t)W * nmu),
+                 *sol = st.up(solar, W), *brdf = st.up(brdf_matrix, (size_t)W * nmu * nmu * (nf + 1)), *xf = st.up(xfac, W);
+    int rc = st.rc;
+    if (rc) return rc;
     // ---- vertical gas opacities: calc_k + k_overlap (:3855-3874), as in the thermal branch --------------------------
-    HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    HIPCHK(ctx->li.reserve((size_t)L * sizeof(LayerInterp)));
-    HIPCHK(ctx->tau.reserve((size_t)L * G * Wpad * D));
     HIPCHK(ctx->ms_taus.reserve(WL * G * D));
     HIPCHK(ctx->ms_omegas.reserve(WL * G * D));
     HIPCHK(ctx->ms_bnu.reserve(WL * D));
     // the chain kernels read TAURAY per (wavenumber, layer) even when there is none
-    const double *d_tauray = (const double *)d[5];
+    const double *d_tauray = ray;
     if (!d_tauray) {
         HIPCHK(ctx->cont_t.reserve(WL * D));
         HIPCHK(hipMemsetAsync(ctx->cont_t.p, 0, WL * D, ctx->stream));
         d_tauray = ctx->cont_t.as<double>();
     }
-    if (ctx->is_lbl) {   // LBL tables: G = 1, DELG = {1}
-        if ((rc = lbl_tau_rows(ctx, L, (const double *)d[0], (const double *)d[1], (const double *)d[2]))) return rc;
-    }
-    for (int pass = 0; pass < 2 && !ctx->is_lbl; ++pass) {
-        ctx->force_generic = pass;       // pass 1 only if the fast merge met an unsorted k-distribution
-        hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)L, 128)), dim3(128), 0, ctx->stream, L, (const double *)d[0],
-                           (const double *)d[1], ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(),
-                           101325.0, ctx->grid_f32, ctx->li.as<LayerInterp>());
-        HIPCHK(hipGetLastError());
-        if (pass) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-        rc = launch_overlap(ctx, false, nullptr, W, Wpad, G, S, L, 1, ctx->li.as<LayerInterp>(), (const double *)d[2],
-                            ctx->d_delg.as<double>(), ctx->h_delg.data(), ctx->tau.as<double>());
-        ctx->force_generic = 0;
-        if (rc) return rc;
-        int flag = 0;
-        if ((rc = read_unsorted(ctx, &flag))) return rc;
-        if (!flag) break;
-    }
+    if ((rc = gas_opacity(ctx, L, press, temp, am))) return rc;
     ctx->last_n = 1; ctx->last_L = L; ctx->last_rows = L; ctx->last_dedup = 0;
     // ---- TAUTOT, OMEGA, BB -----------------------------------------------------------------------------------------
     MsOpticsParams o;
     memset(&o, 0, sizeof o);
-    o.taugas = ctx->tau.as<double>(); o.taucia = (const double *)d[3]; o.taudust = (const double *)d[4];
-    o.tauray = (const double *)d[5]; o.tauscat = (const double *)d[6];
-    o.wave = ctx->d_wave.as<double>(); o.lay_temp = (const double *)d[1];
+    o.taugas = ctx->tau.as<double>(); o.taucia = cia; o.taudust = dust;
+    o.tauray = ray; o.tauscat = sca;
+    o.wave = ctx->d_wave.as<double>(); o.lay_temp = temp;
     o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
     o.W = W; o.Wpad = Wpad; o.G = G; o.L = L; o.ispace = ISPACE;
     hipLaunchKernelGGL(k_ms_optics, dim3(nblk((size_t)W, 128), (unsigned)L), dim3(128), 0, ctx->stream, o);
@@ -2661,19 +2586,19 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
     // ---- doubling / adding ------------------------------------------------------------------------------------------
     MsParams p;
     memset(&p, 0, sizeof p);
-    p.phasarr = (const double *)d[7]; p.radg = (const double *)d[9]; p.solar = (const double *)d[10];
-    p.brdf = (const double *)d[11]; p.bnu = o.bnu; p.taus = o.taus; p.tauray = d_tauray; p.omegas = o.omegas;
-    p.lfrac = (const double *)d[8];
+    p.phasarr = phas; p.radg = rg; p.solar = sol;
+    p.brdf = brdf; p.bnu = o.bnu; p.taus = o.taus; p.tauray = d_tauray; p.omegas = o.omegas;
+    p.lfrac = lf;
     if (ms_pad16(nmu) && (rc = ms_pad_inputs(ctx, nmu, (size_t)W, (size_t)W, nf, &p.radg, &p.brdf))) return rc;
     if ((rc = ms_launch(ctx, p, ncont, W, nth, ngeom, sol_angs, emiss_angs, aphis, lowbc, nmu, mu1, wt1, nf, G, L, nphi,
-                        iray, imie)))
+                        iray, imie, reuse_walk ? MsRun::reuse_walk : MsRun::all)))
         return rc;
     // ---- g-quadrature (:4504) ----------------------------------------------------------------------------------------
     const size_t nspec = (size_t)W * ngeom;
     HIPCHK(ctx->tmp_out2.reserve(nspec * (1 + (size_t)G) * D));
     double *d_spec = ctx->tmp_out2.as<double>(), *d_specg = SPEC_G ? d_spec + nspec : nullptr;
     hipLaunchKernelGGL(k_ms_gquad, dim3(nblk(nspec, 128)), dim3(128), 0, ctx->stream, ctx->tmp_out.as<double>(),
-                       ctx->d_delg.as<double>(), (const double *)d[12], d_spec, d_specg, W, G, ngeom);
+                       ctx->d_delg.as<double>(), xf, d_spec, d_specg, W, G, ngeom);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(SPECOUT, d_spec, nspec * D, hipMemcpyDeviceToHost, ctx->stream));
     if (SPEC_G) HIPCHK(hipMemcpyAsync(SPEC_G, d_specg, nspec * G * D, hipMemcpyDeviceToHost, ctx->stream));
@@ -2681,6 +2606,19 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
     return ANSFM_OK;
 }
 
+
+int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
+                             const double *amount, const double *taucia, const double *taudust, const double *tauray,
+                             const double *tauscat, int ncont, int nth, const double *phasarr, const double *lfrac,
+                             const double *radg, int ngeom, const double *sol_angs, const double *emiss_angs,
+                             const double *aphis, const double *solar, int lowbc, const double *brdf_matrix, int nmu,
+                             const double *mu1, const double *wt1, int nf, int nphi, int iray, int imie, const double *xfac,
+                             double *SPECOUT, double *SPEC_G)
+{
+    return cirsrad_ck_scatter_impl(ctx, ISPACE, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat, ncont, nth,
+                                   phasarr, lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1,
+                                   wt1, nf, nphi, iray, imie, xfac, SPECOUT, SPEC_G, false);
+}
 
 /* ------------------------------------------------------------------------------------------ */
 /* batched scattering branch: the forward models of a numerical Jacobian (jacobian_nemesis :2251-2252)   */
@@ -2710,38 +2648,29 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         // other stream counts, a single model, or de-duplication switched off (ansfm_set_layer_dedup): model by model
         for (int m = 0; m < n_models; ++m) {
             auto at = [&](const double *a, size_t per) { return a ? a + (size_t)m * per : nullptr; };
-            ctx->ms_reuse_walk = (m > 0) ? 1 : 0;       // same phase functions, quadrature, orders: model 0's walk stands
-            const int rc = ansfm_cirsrad_ck_scatter(ctx, ISPACE, L, lay_press_pa + (size_t)m * L, lay_temp + (size_t)m * L,
-                                                    amount + (size_t)m * S * L, at(taucia, WL), at(taudust, WL), at(tauray, WL),
-                                                    at(tauscat, WL), ncont, nth, phasarr, at(lfrac, WL * ncont),
-                                                    radg + (size_t)m * W * nmu, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc,
-                                                    brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac,
-                                                    SPECOUT + (size_t)m * W * ngeom, nullptr);
-            ctx->ms_reuse_walk = 0;
+            // m > 0: same phase functions, quadrature, orders -- model 0's walk stands
+            const int rc = cirsrad_ck_scatter_impl(ctx, ISPACE, L, lay_press_pa + (size_t)m * L, lay_temp + (size_t)m * L,
+                                                   amount + (size_t)m * S * L, at(taucia, WL), at(taudust, WL), at(tauray, WL),
+                                                   at(tauscat, WL), ncont, nth, phasarr, at(lfrac, WL * ncont),
+                                                   radg + (size_t)m * W * nmu, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc,
+                                                   brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac,
+                                                   SPECOUT + (size_t)m * W * ngeom, nullptr, m > 0);
             if (rc) return rc;
         }
         ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = n_models * L; ctx->last_dedup = 0;
         return ANSFM_OK;
     }
     HIPCHK(hipSetDevice(ctx->device));
-    const void *d[16];
-    int i = 0, rc;
-#define UP(ptr, bytes) do { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; ++i; } while (0)
-    UP(lay_press_pa, (size_t)n_models * L * D);                 // 0
-    UP(lay_temp, (size_t)n_models * L * D);                     // 1
-    UP(amount, (size_t)n_models * S * L * D);                   // 2
-    UP(taucia, (size_t)n_models * WL * D);                      // 3
-    UP(taudust, (size_t)n_models * WL * D);                     // 4
-    UP(tauray, (size_t)n_models * WL * D);                      // 5
-    UP(tauscat, (size_t)n_models * WL * D);                     // 6
-    UP(phasarr, (size_t)ncont * W * 2 * nth * D);               // 7
-    UP(lfrac, (size_t)n_models * W * ncont * L * D);            // 8
-    UP(radg, (size_t)n_models * W * nmu * D);                   // 9
-    UP(solar, (size_t)W * D);                                   // 10
-    UP(brdf_matrix, (size_t)W * nmu * nmu * (nf + 1) * D);      // 11
-    UP(xfac, (size_t)W * D);                                    // 12
-#undef UP
-    const double *d_tauray = (const double *)d[5];
+    const size_t nl = (size_t)n_models * L;
+    Stager st{ctx};
+    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
+                 *cia = st.up(taucia, n_models * WL), *dust = st.up(taudust, n_models * WL), *ray = st.up(tauray, n_models * WL),
+                 *sca = st.up(tauscat, n_models * WL), *phas = st.up(phasarr, (size_t)ncont * W * 2 * nth),
+                 *lf = st.up(lfrac, n_models * WL * ncont), *rg = st.up(radg, (size_t)n_models * W * nmu), *sol = st.up(solar, W),
+                 *brdf = st.up(brdf_matrix, (size_t)W * nmu * nmu * (nf + 1)), *xf = st.up(xfac, W);
+    int rc = st.rc;
+    if (rc) return rc;
+    const double *d_tauray = ray;
     size_t st_wl = WL;
     if (!d_tauray) {                                            // the chain kernels read TAURAY even when there is none
         HIPCHK(ctx->cont_t.reserve(WL * D));
@@ -2750,55 +2679,21 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         st_wl = 0;
     }
     // ---- vertical gas opacities of the distinct (model, layer) rows: calc_k + k_overlap ---------------------------------
-    const size_t nl = (size_t)n_models * L;
-    HIPCHK(ctx->dd_slot.reserve(nl * sizeof(int32_t)));
-    HIPCHK(ctx->dd_work.reserve(nl * sizeof(int32_t)));
-    int *counter = ctx->d_flag.as<int>() + 12;
-    HIPCHK(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_dedup_mark, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, S, (const double *)d[0],
-                       (const double *)d[1], (const double *)d[2], ctx->dd_slot.as<int32_t>(), ctx->dd_work.as<int32_t>(), counter);
-    HIPCHK(hipGetLastError());
-    int extra = 0;
-    HIPCHK(hipMemcpyAsync(&extra, counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const int rows = L + extra;
-    HIPCHK(ctx->dd_in.reserve((size_t)rows * (S + 2) * D));
-    double *pw = ctx->dd_in.as<double>(), *tw = pw + rows, *aw = tw + rows;
-    hipLaunchKernelGGL(k_dedup_gather, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream, rows, L, S,
-                       ctx->dd_work.as<int32_t>(), (const double *)d[0], (const double *)d[1], (const double *)d[2], pw, tw, aw);
-    HIPCHK(hipGetLastError());
-    HIPCHK(ctx->li.reserve((size_t)rows * sizeof(LayerInterp)));
-    HIPCHK(ctx->tau.reserve((size_t)rows * G * Wpad * D));
-    if (ctx->is_lbl) {   // LBL tables: G = 1, DELG = {1}; the distinct rows only
-        if ((rc = lbl_tau_rows(ctx, rows, pw, tw, aw))) return rc;
-    }
-    for (int pass = 0; pass < 2 && !ctx->is_lbl; ++pass) {
-        ctx->force_generic = pass;
-        HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(k_layer_prep, dim3(nblk((size_t)rows, 128)), dim3(128), 0, ctx->stream, rows, (const double *)pw,
-                           (const double *)tw, ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(), 101325.0,
-                           ctx->grid_f32, ctx->li.as<LayerInterp>());
-        HIPCHK(hipGetLastError());
-        rc = launch_overlap(ctx, false, nullptr, W, Wpad, G, S, rows, 1, ctx->li.as<LayerInterp>(), aw, ctx->d_delg.as<double>(),
-                            ctx->h_delg.data(), ctx->tau.as<double>());
-        ctx->force_generic = 0;
-        if (rc) return rc;
-        int flag = 0;
-        if ((rc = read_unsorted(ctx, &flag))) return rc;
-        if (!flag) break;
-    }
-    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = rows; ctx->last_dedup = 1;
+    DedupRows k;
+    if ((rc = dedup_rows(ctx, n_models, L, press, temp, am, nullptr, nullptr, &k)) || (rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount)))
+        return rc;
+    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = k.rows; ctx->last_dedup = 1;
     // ---- which layers equal model 0's in EVERY input --------------------------------------------------------------------
     HIPCHK(ctx->ms_same.reserve(nl));
     unsigned char *same = ctx->ms_same.as<unsigned char>();
     hipLaunchKernelGGL(k_ms_same_init, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), same);
-    for (int a = 3; a <= 6; ++a)
-        if (d[a])
+    for (const double *col : {cia, dust, ray, sca})
+        if (col)
             hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W, 128)), dim3(128), 0, ctx->stream, n_models, W,
-                               1, L, (const double *)d[a], same);
-    if (d[8] && ncont > 0)
+                               1, L, col, same);
+    if (lf && ncont > 0)
         hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W * ncont, 128)), dim3(128), 0, ctx->stream,
-                           n_models, W, ncont, L, (const double *)d[8], same);
+                           n_models, W, ncont, L, lf, same);
     HIPCHK(hipGetLastError());
     // where a model's adding sweep may start: below its first changed layer (in sweep order: bottom first when the paths look
     // down, top first when they look up) the stack equals model 0's, kept after every kMsPrefixStep-th layer
@@ -2839,12 +2734,12 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     // ---- phase matrices and Hansen factors: once, they do not depend on the model -----------------------------------------
     MsParams p;
     memset(&p, 0, sizeof p);
-    p.phasarr = (const double *)d[7]; p.radg = (const double *)d[9]; p.solar = (const double *)d[10];
-    p.brdf = (const double *)d[11]; p.tauray = d_tauray; p.lfrac = (const double *)d[8];
+    p.phasarr = phas; p.radg = rg; p.solar = sol;
+    p.brdf = brdf; p.tauray = d_tauray; p.lfrac = lf;
     const bool pad16 = ms_pad16(nmu);
     if (pad16 && (rc = ms_pad_inputs(ctx, nmu, (size_t)n_models * W, (size_t)W, nf, &p.radg, &p.brdf))) return rc;
     if ((rc = ms_launch(ctx, p, ncont, W, nth, ngeom, sol_angs, emiss_angs, aphis, lowbc, nmu, mu1, wt1, nf, G, L, nphi, iray,
-                        imie, true)))
+                        imie, MsRun::prepare_only)))
         return rc;
     const int nmu_k = pad16 ? 16 : nmu;                         // the stream count the kernels run with
     // G = 1: the slabs of the spectral axis are the windows of phase matrices and Hansen factors (ms_window_size): a slab's
@@ -2911,8 +2806,8 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         MsOpticsBatchParams o;
         memset(&o, 0, sizeof o);
         o.taugas = ctx->tau.as<double>(); o.slot = ctx->dd_slot.as<int32_t>();
-        o.taucia = (const double *)d[3]; o.taudust = (const double *)d[4]; o.tauray = (const double *)d[5]; o.tauscat = (const double *)d[6];
-        o.wave = ctx->d_wave.as<double>(); o.lay_temp = (const double *)d[1];
+        o.taucia = cia; o.taudust = dust; o.tauray = ray; o.tauscat = sca;
+        o.wave = ctx->d_wave.as<double>(); o.lay_temp = temp;
         o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
         o.W = W; o.Wpad = Wpad; o.G = G; o.L = L; o.ispace = ISPACE;
         const size_t ldsl = (size_t)(2 * nn + nmu) * 64 * D, ldsg = (12 * (size_t)nn + 6 * kMsMaxMu + 2) * D;
@@ -2956,7 +2851,7 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
             pf.drad = p.drad + (size_t)m * st_drad; pf.rad = p.rad + (size_t)m * p.st_rad;
             hipLaunchKernelGGL(k_ms_fourier, dim3(nblk((size_t)W * G * ngeom, 128)), dim3(128), 0, ctx->stream, pf);
             hipLaunchKernelGGL(k_ms_gquad, dim3(nblk(nspec, 128)), dim3(128), 0, ctx->stream,
-                               ctx->tmp_out.as<double>() + (size_t)m * p.st_rad, ctx->d_delg.as<double>(), (const double *)d[12],
+                               ctx->tmp_out.as<double>() + (size_t)m * p.st_rad, ctx->d_delg.as<double>(), xf,
                                ctx->tmp_out2.as<double>() + (size_t)m * nspec, (double *)nullptr, W, G, ngeom);
         }
         HIPCHK(hipGetLastError());
@@ -2997,8 +2892,8 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     MsOpticsBatchParams o;
     memset(&o, 0, sizeof o);
     o.taugas = ctx->tau.as<double>(); o.slot = ctx->dd_slot.as<int32_t>();
-    o.taucia = (const double *)d[3]; o.taudust = (const double *)d[4]; o.tauray = (const double *)d[5]; o.tauscat = (const double *)d[6];
-    o.wave = ctx->d_wave.as<double>(); o.lay_temp = (const double *)d[1];
+    o.taucia = cia; o.taudust = dust; o.tauray = ray; o.tauscat = sca;
+    o.wave = ctx->d_wave.as<double>(); o.lay_temp = temp;
     o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
     o.W = W; o.Wpad = Wpad; o.G = G; o.L = L; o.ispace = ISPACE;
     const size_t lds16 = (4 * 16 * 17 + 5 * 16) * D;
@@ -3031,7 +2926,7 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     HIPCHK(ctx->tmp_out2.reserve((size_t)n_models * nspec * D));
     for (int m = 0; m < n_models; ++m)
         hipLaunchKernelGGL(k_ms_gquad, dim3(nblk(nspec, 128)), dim3(128), 0, ctx->stream,
-                           ctx->tmp_out.as<double>() + (size_t)m * p.st_rad, ctx->d_delg.as<double>(), (const double *)d[12],
+                           ctx->tmp_out.as<double>() + (size_t)m * p.st_rad, ctx->d_delg.as<double>(), xf,
                            ctx->tmp_out2.as<double>() + (size_t)m * nspec, (double *)nullptr, W, G, ngeom);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out2.p, (size_t)n_models * nspec * D, hipMemcpyDeviceToHost, ctx->stream));
@@ -3086,24 +2981,6 @@ int ansfm_upload_lbltable(ansfm_ctx *ctx, int W, int NP, int NT, int S, const do
     return ANSFM_OK;
 }
 
-static int lbl_prep(ansfm_ctx *ctx, int n_layers, const double *lay_press, const double *lay_temp, double press_div,
-                    int with_grad);
-static int lbl_prep_fwd(ansfm_ctx *ctx, int n_layers, const double *lay_press, const double *lay_temp, double press_div,
-                        int with_grad)
-{
-    return lbl_prep(ctx, n_layers, lay_press, lay_temp, press_div, with_grad);
-}
-static int lbl_prep(ansfm_ctx *ctx, int n_layers, const double *lay_press, const double *lay_temp, double press_div,
-                    int with_grad)
-{
-    HIPCHK(ctx->lbl_li.reserve((size_t)n_layers * sizeof(LblInterp)));
-    hipLaunchKernelGGL(k_layer_prep_lbl, dim3(nblk(n_layers, 128)), dim3(128), 0, ctx->stream, n_layers, lay_press,
-                       lay_temp, ctx->NP, ctx->d_press.as<double>(), ctx->NT, ctx->d_temp.as<double>(), ctx->temp2d,
-                       press_div, ctx->grid_f32, with_grad, ctx->lbl_li.as<LblInterp>());
-    HIPCHK(hipGetLastError());
-    return ANSFM_OK;
-}
-
 int ansfm_calc_klbl(ansfm_ctx *ctx, int L, const double *press, const double *temp, double *k_out, double *dkdT_out)
 {
     CHECK_CTX(ctx);
@@ -3111,11 +2988,10 @@ int ansfm_calc_klbl(ansfm_ctx *ctx, int L, const double *press, const double *te
     if (L <= 0 || !press || !temp || !k_out) FAIL(ANSFM_ERR_INVALID, "calc_klbl: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, S = ctx->S;
-    const void *dp, *dt;
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], press, L * sizeof(double), &dp))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], temp, L * sizeof(double), &dt))) return rc;
-    if ((rc = lbl_prep(ctx, L, (const double *)dp, (const double *)dt, 1.0, dkdT_out != nullptr))) return rc;
+    Stager st{ctx};
+    const double *dp = st.up(press, L), *dt = st.up(temp, L);
+    int rc = st.rc;
+    if (rc || (rc = lbl_prep(ctx, L, dp, dt, 1.0, dkdT_out != nullptr))) return rc;
     const size_t n = (size_t)W * L * S;
     HIPCHK(ctx->tmp_out.reserve(n * sizeof(double) * (dkdT_out ? 2 : 1)));
     double *dk = dkdT_out ? ctx->tmp_out.as<double>() + n : nullptr;
@@ -3170,26 +3046,19 @@ int ansfm_add_line_set_monochromatic_absorption(
     double pmax = 0.0;
     for (int l = 0; l < L; ++l) if (fabs(p_calc[l] / p_ref) > pmax) pmax = fabs(p_calc[l] / p_ref);
     const size_t D = sizeof(double);
-    const void *d_lines, *d_grid, *d_mmf, *d_t, *d_p, *d_q, *d_out;
-    int rc;
-    if ((rc = h2d(ctx, ctx->hb[0], h.data(), h.size() * D, &d_lines))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[1], wn_grid, (size_t)nw * D, &d_grid))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[2], mol_mix_frac, (size_t)M * D, &d_mmf))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[3], t_calc, (size_t)L * D, &d_t))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[4], p_calc, (size_t)L * D, &d_p))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[5], q_ratio, (size_t)L * D, &d_q))) return rc;
-    if ((rc = h2d(ctx, ctx->hb[6], out, (size_t)L * nw * D, &d_out))) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));   // h is a local buffer
-    HIPCHK(ctx->misc.reserve((size_t)L * (kLblRows + 1) * N * D));
     LblParams p;
     memset(&p, 0, sizeof p);
-    const double *dl = (const double *)d_lines;
-    p.wn_grid = (const double *)d_grid;
+    Stager st{ctx};
+    const double *dl = st.up(h.data(), h.size());
+    p.wn_grid = st.up(wn_grid, nw); p.mmf = st.up(mol_mix_frac, M);
+    p.t_calc = st.up(t_calc, L); p.p_calc = st.up(p_calc, L); p.q_ratio = st.up(q_ratio, L);
+    p.out = const_cast<double *>(st.up(out, (size_t)L * nw));     // accumulated onto
+    if (st.rc) return st.rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // h is a local buffer
+    HIPCHK(ctx->misc.reserve((size_t)L * (kLblRows + 1) * N * D));
     p.nu = dl; p.sw = dl + N; p.e_lower = dl + 2 * (size_t)N; p.stim_ref = dl + 3 * (size_t)N; p.bparams = dl + 4 * (size_t)N;
-    p.mmf = (const double *)d_mmf; p.t_calc = (const double *)d_t; p.p_calc = (const double *)d_p; p.q_ratio = (const double *)d_q;
     p.store = ctx->misc.as<double>();
     p.shift = p.store + (size_t)L * kLblRows * N;
-    p.out = (double *)const_cast<void *>(d_out);
     p.nw = nw; p.N = N; p.M = M; p.L = L; p.lineshape_id = lineshape_id;
     p.t_ref = t_ref; p.p_ref = p_ref; p.iso_abundance = isotopic_abundance; p.iso_mass = isotopic_mass; p.s_floor = s_floor;
     p.wn_calc_window = wn_calc_window; p.wn_approx_window = wn_approx_window;
@@ -3256,26 +3125,20 @@ static int layer_average_impl(ansfm_ctx *ctx, int n_models, double RADIUS, int N
             if (DUST_UNITS[j] == -1) FAIL(ANSFM_ERR_INVALID, "if DUST_UNITS=-1 (particles per gram of atm), the XMOLWT must be defined");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t D = sizeof(double), n = n_models;
-    const void *d[10];
-    int i = 0, rc;
-#define UP(ptr, bytes) do { if (dev) d[i] = ptr; else { rc = h2d(ctx, ctx->hb[i], ptr, bytes, &d[i]); if (rc) return rc; } ++i; } while (0)
-    UP(H, n * NPRO * D); UP(P, n * NPRO * D); UP(T, n * NPRO * D);              // 0 1 2
-    UP(VMR, n * NPRO * NVMR * D);                                               // 3
-    UP(DUST, n * NPRO * NDUST * D);                                             // 4
-    UP(PARAH2, n * NPRO * D);                                                   // 5
-    UP(XMOLWT, n * NPRO * D);                                                   // 6
-    UP(BASEH, n * NLAY * D);                                                    // 7
-#undef UP
-    rc = h2d(ctx, ctx->hb[8], DUST_UNITS, (size_t)NDUST * sizeof(int32_t), &d[8]); if (rc) return rc;   // always a host array
+    LayerAvgParams p;
+    memset(&p, 0, sizeof p);
+    Stager st{ctx};
+    auto in = [&](const double *a, size_t count) { return dev ? a : st.up(a, count); };   // device arrays stay where they are
+    p.H = in(H, n * NPRO); p.P = in(P, n * NPRO); p.T = in(T, n * NPRO); p.VMR = in(VMR, n * NPRO * NVMR);
+    p.DUST = in(DUST, n * NPRO * NDUST); p.PARAH2 = in(PARAH2, n * NPRO); p.XMOLWT = in(XMOLWT, n * NPRO);
+    p.BASEH = in(BASEH, n * NLAY);
+    st.slot = 8;                                                                    // the device route stages from here only
+    p.dust_units = st.up(DUST_UNITS, NDUST);                                        // always a host array
+    if (st.rc) return st.rc;
     const size_t nl = n * NLAY;
     const size_t tot = nl * (8 + 2 * (size_t)NVMR + NDUST) + (with_grad ? 4 * nl * NPRO : 0);
     if (!dev) HIPCHK(ctx->tmp_out.reserve(tot * D));
     double *o = dev ? dev_out : ctx->tmp_out.as<double>();
-    LayerAvgParams p;
-    memset(&p, 0, sizeof p);
-    p.H = (const double *)d[0]; p.P = (const double *)d[1]; p.T = (const double *)d[2]; p.VMR = (const double *)d[3];
-    p.DUST = (const double *)d[4]; p.PARAH2 = (const double *)d[5]; p.XMOLWT = (const double *)d[6];
-    p.BASEH = (const double *)d[7]; p.dust_units = (const int32_t *)d[8];
     p.HEIGHT = o; p.PRESS = o + nl; p.TEMP = o + 2 * nl; p.TOTAM = o + 3 * nl; p.FRAC = o + 4 * nl; p.DELH = o + 5 * nl;
     p.BASET = o + 6 * nl; p.LAYSF = o + 7 * nl; p.AMOUNT = o + 8 * nl; p.PP = p.AMOUNT + nl * NVMR; p.CONT = p.PP + nl * NVMR;
     p.RADIUS = RADIUS; p.LAYANG = LAYANG; p.LAYHT = LAYHT;

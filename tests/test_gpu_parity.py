@@ -1235,11 +1235,25 @@ def _scatter_oracle(oracle, z, sol, emi, azi, lowbc, NF, nphi, iray, imie):
 def test_cirsrad_scatter_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowbc, up):
     """ansfm_cirsrad_ck_scatter (gas opacities, TAUTOT, OMEGA, BB formed on the device, straight into the doubling /
     adding kernels) vs the same chain through the oracle: radiances before and after the g-quadrature and TAUGAS."""
+    _scatter_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowbc, up, unsorted=False)
+
+
+@pytest.mark.parametrize("NMU,NF,ncont,imie,iray,lowbc,up", [(5, 2, 2, 0, 1, 0, False), (16, 3, 1, 1, 1, 1, False),
+                                                             (12, 2, 2, 1, 1, 0, True)])
+def test_cirsrad_scatter_unsorted_table_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowbc, up):
+    """The same with a k-table that is not monotone in g: the scattering branch takes the generic merge."""
+    _scatter_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowbc, up, unsorted=True)
+
+
+def _scatter_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowbc, up, unsorted):
     rng = np.random.default_rng(900 + NMU + NF + ncont)
     W, G, L, S = 24, 6, 7, 3
     z = _scatter_inputs(rng, W, G, L, S, NMU, NF, ncont, imie, iray, lowbc)
+    if unsorted:
+        z["K"] = z["K"][:, np.random.default_rng(6).permutation(G)]     # scramble the g axis
     sol = np.array([30.0, 120.0]); emi = np.array([160.0, 130.0]) if up else np.array([20.0, 50.0]); azi = np.array([45.0, 0.0])
     eng.upload_ktable(z["K"], z["TPRESS"], z["TTEMP"], z["WAVE"], z["DELG"])
+    assert eng.ktable_info()[1] is (not unsorted)
     ph = z["phasarr"] if ncont else None
     out, spec_g = eng.cirsrad_ck_scatter(0, z["lay_p"], z["lay_t"], z["amount"], z["TAUCIA"], z["TAUDUST"],
                                          z["TAURAY"] if iray else None, z["TAUSCAT"], ph, z["lfrac"] if ncont else None,
@@ -1345,6 +1359,40 @@ def test_cirsrad_scatter_batch_other_stream_counts_equal_separate_calls(eng, mon
     finally:
         eng.set_layer_dedup(True)
     assert not np.array_equal(ref[1], ref[0]) and not np.array_equal(ref[3], ref[0])
+
+
+@pytest.mark.parametrize("NMU", [16, 5])
+def test_cirsrad_scatter_batch_unsorted_table_equals_separate_calls(eng, NMU):
+    """A k-table that is not monotone in g through the batched scattering branch: the de-duplicated gas opacity rows take the
+    generic merge, the layer cache serves the other models -- every spectrum bit-identical to a call of its own, with the
+    de-duplication on and off."""
+    rng = np.random.default_rng(9300 + NMU)
+    W, G, L, S, NF = 30, 5, 8, 3, 2
+    z = _scatter_inputs(rng, W, G, L, S, NMU, NF, 1, 1, 1, 1)
+    z["K"] = z["K"][:, np.random.default_rng(7).permutation(G)]         # scramble the g axis
+    sol = np.array([30.0, 75.0]); emi = np.array([20.0, 50.0]); azi = np.array([45.0, 10.0])
+    eng.upload_ktable(z["K"], z["TPRESS"], z["TTEMP"], z["WAVE"], z["DELG"])
+    assert eng.ktable_info()[1] is False
+    n = 4
+    rep = lambda a: np.repeat(np.asarray(a)[None], n, 0).copy()
+    lp, lt, am = rep(z["lay_p"]), rep(z["lay_t"]), rep(z["amount"])
+    cia, dust, ray, sca = rep(z["TAUCIA"]), rep(z["TAUDUST"]), rep(z["TAURAY"]), rep(z["TAUSCAT"])
+    lf, rg = rep(z["lfrac"]), rep(z["radg"])
+    lt[1, 4] *= 1.05; am[2, 1, 6] *= 1.05; sca[3, :, 3] *= 1.05; dust[3, :, 3] *= 1.05
+    tail = (sol, emi, azi, z["solar"], 1, z["brdf"], z["MU"], z["WT"], NF, 101, 1, 1)
+    one = lambda m: eng.cirsrad_ck_scatter(0, lp[m], lt[m], am[m], cia[m], dust[m], ray[m], sca[m], z["phasarr"], lf[m], rg[m], *tail)
+    ref = np.stack([one(m) for m in range(n)])
+    batch = lambda: eng.cirsrad_ck_scatter_batch(0, lp, lt, am, cia, dust, ray, sca, z["phasarr"], lf, rg, *tail)
+    assert np.array_equal(batch(), ref)
+    hits, total = eng.last_scatter_cache()
+    assert total == (n - 1) * L and hits == total - 3
+    assert eng.last_layer_rows() == (L + 2, n * L)
+    eng.set_layer_dedup(False)
+    try:
+        assert np.array_equal(batch(), ref)
+    finally:
+        eng.set_layer_dedup(True)
+    assert not np.array_equal(ref[1], ref[0])
 
 
 def test_cirsrad_scatter_more_than_sixteen_paths(eng):
@@ -1773,13 +1821,25 @@ def test_cirsrad_singlescatt_vs_oracle(eng, oracle):
     """CIRSrad's single-scattering branch fused with the opacity assembly (ansfm_cirsrad_ck_singlescatt) vs the reference's
     recipe on the oracle's pieces: calc_k + k_overlap, TAUTOT (:3989), OMEGA (:4276-4283), LAYINC x SCALE (:4006),
     calc_singlescatt_plane_spectrum per path, xfac, g-quadrature (:4504).  Two paths of different length and geometry."""
+    _singlescatt_vs_oracle(eng, oracle, unsorted=False)
+
+
+def test_cirsrad_singlescatt_unsorted_table_vs_oracle(eng, oracle):
+    """The same with a k-table that is not monotone in g: the single-scattering branch takes the generic merge."""
+    _singlescatt_vs_oracle(eng, oracle, unsorted=True)
+
+
+def _singlescatt_vs_oracle(eng, oracle, unsorted):
     from archnemesis_dist_amd import synthetic as syn
     rng = np.random.default_rng(88)
     W, G, S, L = 100, 10, 3, 9
     PRESS, TEMP, K = syn.synth_ktable(W, G, 8, 6, S, seed=31)
+    if unsorted:
+        K = K[:, np.random.default_rng(5).permutation(G)]          # scramble the g axis
     _, delg = syn.gauss_legendre_01(G)
     WAVE = 2000.0 + 3.0 * np.arange(W)
     eng.upload_ktable(K, PRESS, TEMP, WAVE, delg)
+    assert eng.ktable_info()[1] is (not unsorted)
     lp = np.logspace(5.0, 1.0, L); lt = np.linspace(230.0, 150.0, L)
     am = 10.0 ** rng.uniform(17, 19.5, (S, L)) * (lp[None, :] / lp[0])
     TAURAY = 10.0 ** rng.uniform(-4, -2, (W, L)); TAUSCAT = 10.0 ** rng.uniform(-3, -1, (W, L)); TAUSCAT[:, 4] = 0.0
@@ -1809,3 +1869,51 @@ def test_cirsrad_singlescatt_vs_oracle(eng, oracle):
                                                         EMIS, BRDF[:, ip], SOLF, sol[ip], emi[ip])
             ref[:, ip] = np.tensordot(sp * xfac[:, None], delg, axes=([1], [0]))
         np.testing.assert_allclose(got, ref, rtol=1e-11)
+
+
+def test_closing_an_engine_returns_its_device_memory():
+    """Every buffer, stream and event an engine holds goes when it is closed.  Engines run a batched thermal call at C2 size
+    that takes the prefix route of the RT (its state-0 records: about 1 GB with two paths) and a 12-stream scattering call
+    (padded to the 16-stream kernels), then close: device free memory comes back each time, to well within one prefix
+    buffer.  The first engine and the first full round are warm-up: code objects and the runtime's own allocations."""
+    import torch
+    import archnemesis_dist_amd as pkg
+    from archnemesis_dist_amd import synthetic as syn
+    W, G, S, L, n = 10000, 20, 8, 100, 4
+    _, delg = syn.gauss_legendre_01(G, as_float32=False)
+    PRESS, TEMP, K = syn.synth_ktable(W, G, 6, 5, S)
+    WAVE = 200.0 + 0.1 * np.arange(W)
+    atm = syn.synth_atmosphere(L, S, n_models=n)
+    lp, lt, am = atm["lay_press_pa"].copy(), atm["lay_temp"].copy(), atm["amount"].copy()
+    lt[1, 60] *= 1.01; am[2, 3, 20] *= 1.05; lt[3, 10] *= 0.99
+    NLAYIN = np.array([L, L], dtype=np.int32)
+    LAYINC = np.repeat(np.arange(L - 1, -1, -1, dtype=np.int32)[:, None], 2, 1)
+    SCALE = np.repeat((1.0 / np.cos(np.deg2rad([0.0, 30.0])))[None, :], L, 0)
+    EMTEMP = lt[:, LAYINC]
+    rng = np.random.default_rng(1212)
+    zs = _scatter_inputs(rng, 24, 6, 7, 3, 12, 2, 1, 1, 1, 1)
+    sol = np.array([30.0, 120.0]); emi = np.array([20.0, 50.0]); azi = np.array([45.0, 0.0])
+
+    def one_round():
+        e = pkg.AnsfmEngine(0)
+        try:
+            e.upload_ktable(K, PRESS, TEMP, WAVE, delg)
+            spec = e.cirsrad_ck_thermal(0, lp, lt, am, None, NLAYIN, LAYINC, np.repeat(SCALE[None], n, 0), EMTEMP, np.full(n, -1.0))
+            assert spec.shape == (n, W, 2) and e.last_rt_shared()
+            e.upload_ktable(zs["K"], zs["TPRESS"], zs["TTEMP"], zs["WAVE"], zs["DELG"])
+            e.cirsrad_ck_scatter(0, zs["lay_p"], zs["lay_t"], zs["amount"], zs["TAUCIA"], zs["TAUDUST"], zs["TAURAY"], zs["TAUSCAT"],
+                                 zs["phasarr"], zs["lfrac"], zs["radg"], sol, emi, azi, zs["solar"], 1, zs["brdf"], zs["MU"], zs["WT"],
+                                 2, 101, 1, 1)
+        finally:
+            e.close()
+
+    pkg.AnsfmEngine(0).close()
+    one_round()
+    torch.cuda.synchronize(0)
+    free0 = torch.cuda.mem_get_info(0)[0]
+    drops = []
+    for _ in range(3):
+        one_round()
+        torch.cuda.synchronize(0)
+        drops.append((free0 - torch.cuda.mem_get_info(0)[0]) / 2**20)
+    assert max(drops) < 256.0, f"device free memory lost after each round (MiB): {drops}"
