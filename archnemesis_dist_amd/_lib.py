@@ -29,7 +29,7 @@ EXPORTS = [
     "ansfm_upload_lbltable_files", "ansfm_kdist_bins", "ansfm_calc_tau_cia", "ansfm_set_merge_keys", "ansfm_merge_redo_count", "ansfm_calc_tau_rayleigh_batch_dev", "ansfm_cirsrad_ck_scatter", "ansfm_thermal_emission_g", "ansfm_cirsrad_ck_transmission", "ansfm_cirsradg_ck_transmission", "ansfm_set_gradient_gases", "ansfm_set_shared_gas_gradient", "ansfm_singlescatt_plane_spectrum",
     "ansfm_cirsrad_ck_singlescatt", "ansfm_cirsrad_ck_scatter_batch", "ansfm_last_scatter_cache",
     "ansfm_layer_average_dev", "ansfm_calc_tau_rayleigh_batch_dev_in", "ansfm_last_rt_shared",
-    "ansfm_cirsrad_ck_thermal_ray_dev", "ansfm_last_scatter_windows",
+    "ansfm_cirsrad_ck_thermal_ray_dev", "ansfm_last_scatter_windows", "ansfm_cirsrad_ck_scatter_batch_slice",
 ]
 
 _lib = None
@@ -145,6 +145,8 @@ def load():
     #  solar, lowbc, brdf, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT)
     lib.ansfm_cirsrad_ck_scatter_batch.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci,
                                                    vp, ci, vp, vp, ci, ci, ci, ci, vp, vp]
+    # ... + (W_full, w_begin)
+    lib.ansfm_cirsrad_ck_scatter_batch_slice.argtypes = lib.ansfm_cirsrad_ck_scatter_batch.argtypes + [ci, ci]
     lib.ansfm_last_scatter_cache.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ansfm_last_scatter_windows.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ansfm_upload_lbltable.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp]

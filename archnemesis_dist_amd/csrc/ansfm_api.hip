@@ -2271,12 +2271,14 @@ static int ms_side_streams(ansfm_ctx *ctx, int nev)
 
 // What ms_launch runs: everything; everything but the phase matrices and Hansen factors, which the previous call left in
 // ctx->misc (the models of a batch one by one: ansfm_cirsrad_ck_scatter_batch without the layer cache); or those two alone (the
-// batch path, which launches its own chains)
+// batch path, which launches its own chains).  prepare_only with w_full > nwave (the batch over a slice [w_begin, w_begin +
+// nwave) of a w_full axis, G > 1): phase matrices of the whole axis, the whole walk, the factors of the slice kept; p.ppl /
+// p.pmi / p.fc are left pointing at the slice's first wavenumber.
 enum class MsRun { all, reuse_walk, prepare_only };
 
 static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth, int ngeom, const double *sol_angs,
                      const double *emiss_angs, const double *aphis, int lowbc, int nmu, const double *mu1, const double *wt1,
-                     int nf, int ng, int nlay, int nphi, int iray, int imie, MsRun run)
+                     int nf, int ng, int nlay, int nphi, int iray, int imie, MsRun run, int w_begin = 0, int w_full = 0)
 {
     const bool prepare_only = run == MsRun::prepare_only;
     if (nmu > kMsMaxMu || ngeom > kMsMaxPath || ncont > 60)
@@ -2317,6 +2319,26 @@ static int ms_launch(ansfm_ctx *ctx, MsParams &p, int ncont, int nwave, int nth,
     // batch path (prepare_only) makes its spectral slabs the windows and launches their phase matrices and walk itself.
     const long nwin = (ng == 1) ? ms_window_size(nwave, nf, p.ncomp, nmu) : nwave;
     if (ng == 1 && prepare_only) return ANSFM_OK;
+    if (prepare_only && w_full > nwave) {
+        // the walk continues from g to g + 1 over the whole axis, so every rank walks all of it: the whole axis's phase matrices
+        // (a one-GPU call of w_full holds them too), the factors of the slice only, the rest of the steps into a sink
+        const size_t per_w = (size_t)(nf + 1) * p.ncomp * nn, nph_f = (size_t)w_full * per_w;
+        const size_t misc_f = 2 * nph_f + nfc + (size_t)p.ncomp * nn;
+        HIPCHK(ctx->misc.reserve(misc_f * D));
+        HIPCHK(hipMemsetAsync(ctx->misc.p, 0, misc_f * D, ctx->stream));
+        p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph_f; p.fc = p.pmi + nph_f;
+        ctx->ms_windows = 1; ctx->ms_window_w = nwave;
+        if (ncomp_run > 0) {
+            MsParams pw = p;
+            pw.nwave = w_full; pw.nwin = w_full;
+            ms_launch_phase(ctx->stream, pw);
+            pw.st0 = w_begin; pw.stn = nwave; pw.sink = p.fc + nfc;
+            ms_launch_hansen(ctx->stream, pw);
+            HIPCHK(hipGetLastError());
+        }
+        p.ppl += (size_t)w_begin * per_w; p.pmi += (size_t)w_begin * per_w;
+        return ANSFM_OK;
+    }
     const bool windowed = nwin < nwave;
     ctx->ms_windows = (nwave + nwin - 1) / nwin; ctx->ms_window_w = nwin;
     // reuse: the models of a batch run one by one share the phase functions, so the phase matrices and the Hansen factors the
@@ -2623,13 +2645,16 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
 /* ------------------------------------------------------------------------------------------ */
 /* batched scattering branch: the forward models of a numerical Jacobian (jacobian_nemesis :2251-2252)   */
 /* ------------------------------------------------------------------------------------------ */
-int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                   const double *lay_temp, const double *amount, const double *taucia, const double *taudust,
-                                   const double *tauray, const double *tauscat, int ncont, int nth, const double *phasarr,
-                                   const double *lfrac, const double *radg, int ngeom, const double *sol_angs,
-                                   const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
-                                   const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
-                                   int iray, int imie, const double *xfac, double *SPECOUT)
+// W_full / w_begin: the context's table is the slice [w_begin, w_begin + ctx->W) of a W_full axis; phasarr covers W_full, every
+// other per-wavenumber input and SPECOUT the slice.  W_full = ctx->W, w_begin = 0: the whole axis, the launches of the unsliced
+// call.
+static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                         const double *lay_temp, const double *amount, const double *taucia, const double *taudust,
+                                         const double *tauray, const double *tauscat, int ncont, int nth, const double *phasarr,
+                                         const double *lfrac, const double *radg, int ngeom, const double *sol_angs,
+                                         const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                         const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter_batch: upload a k-table first");
@@ -2638,12 +2663,15 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         (ISPACE != 0 && ISPACE != 1) || (ncont > 0 && (!phasarr || !lfrac || nth < 3)))
         FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch: bad argument");
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
+    const bool sliced = W_full != W;
     const size_t D = sizeof(double), WL = (size_t)W * L;
     ctx->ms_cache_hits = 0; ctx->ms_cache_layers = (long)n_models * L;
     const char *ev_off = getenv("ANSFM_MS_LAYER_CACHE");
     const char *ev_lane = getenv("ANSFM_MS_LANE");
     const bool lane_n = (nmu == 4 || nmu == 5 || nmu == 6) && !(ev_lane && ev_lane[0] == '0');   // k_ms_chain_lane<N, CACHE>
     const bool use_cache = n_models > 1 && ctx->dedup && !(ev_off && atoi(ev_off) == 0);      // any stream count
+    if (!use_cache && sliced)
+        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter_batch_slice: a slice needs the layer cache (n_models > 1, layer de-duplication on)");
     if (!use_cache) {
         // other stream counts, a single model, or de-duplication switched off (ansfm_set_layer_dedup): model by model
         for (int m = 0; m < n_models; ++m) {
@@ -2665,7 +2693,7 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     Stager st{ctx};
     const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
                  *cia = st.up(taucia, n_models * WL), *dust = st.up(taudust, n_models * WL), *ray = st.up(tauray, n_models * WL),
-                 *sca = st.up(tauscat, n_models * WL), *phas = st.up(phasarr, (size_t)ncont * W * 2 * nth),
+                 *sca = st.up(tauscat, n_models * WL), *phas = st.up(phasarr, (size_t)ncont * W_full * 2 * nth),
                  *lf = st.up(lfrac, n_models * WL * ncont), *rg = st.up(radg, (size_t)n_models * W * nmu), *sol = st.up(solar, W),
                  *brdf = st.up(brdf_matrix, (size_t)W * nmu * nmu * (nf + 1)), *xf = st.up(xfac, W);
     int rc = st.rc;
@@ -2739,13 +2767,13 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     const bool pad16 = ms_pad16(nmu);
     if (pad16 && (rc = ms_pad_inputs(ctx, nmu, (size_t)n_models * W, (size_t)W, nf, &p.radg, &p.brdf))) return rc;
     if ((rc = ms_launch(ctx, p, ncont, W, nth, ngeom, sol_angs, emiss_angs, aphis, lowbc, nmu, mu1, wt1, nf, G, L, nphi, iray,
-                        imie, MsRun::prepare_only)))
+                        imie, MsRun::prepare_only, w_begin, W_full)))
         return rc;
     const int nmu_k = pad16 ? 16 : nmu;                         // the stream count the kernels run with
     // G = 1: the slabs of the spectral axis are the windows of phase matrices and Hansen factors (ms_window_size): a slab's
     // phase matrices and walk -- continuing from the carry of the slab before -- go in front of its chains, model 0's first
     const bool win = G == 1;
-    const long nwin_b = win ? ms_window_size(W, nf, p.ncomp, nmu_k) : W;
+    const long nwin_b = win ? ms_window_size(W_full, nf, p.ncomp, nmu_k) : W;
     const int ncomp_run = ncont + (iray > 0 ? 1 : 0);
     auto window_buffers = [&](long Ws) -> int {
         ctx->ms_windows = (W + Ws - 1) / Ws; ctx->ms_window_w = Ws;
@@ -2755,14 +2783,27 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
         HIPCHK(ctx->misc.reserve(n_all * D));
         HIPCHK(hipMemsetAsync(ctx->misc.p, 0, n_all * D, ctx->stream));
         p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph_w; p.fc = p.pmi + nph_w; p.carry = p.fc + (size_t)Ws * p.ncomp * nn;
+        // a slice: the walk of the wavenumbers in front of it, in windows of Ws whose factors only feed the carry
+        for (long a = 0; a < w_begin && ncomp_run > 0; a += Ws) {
+            MsParams pw = p;
+            pw.nwave = W_full; pw.pw0 = (int)a; pw.nwin = (int)std::min<long>(Ws, w_begin - a); pw.carry_in = a > 0 ? 1 : 0;
+            pw.ig0 = 0; pw.ng_launch = 1;
+            ms_launch_phase(ctx->stream, pw);
+            ms_launch_hansen(ctx->stream, pw);
+            HIPCHK(hipGetLastError());
+        }
         return ANSFM_OK;
     };
+    // the phase matrices of a slab are those of the wavenumbers w_begin + [w0, w0 + wc) of phasarr; chains and walk index the
+    // window relative to w0
     auto slab_window = [&](long w0, int wc) -> int {
         if (!win) return ANSFM_OK;
-        p.pw0 = (int)w0; p.nwin = wc; p.carry_in = w0 > 0 ? 1 : 0;
+        p.pw0 = (int)w0; p.nwin = wc; p.carry_in = w_begin + w0 > 0 ? 1 : 0;
         p.ig0 = 0; p.ng_launch = 1;
         if (ncomp_run > 0) {
-            ms_launch_phase(ctx->stream, p);
+            MsParams pw = p;
+            pw.nwave = W_full; pw.pw0 = w_begin + (int)w0;
+            ms_launch_phase(ctx->stream, pw);
             ms_launch_hansen(ctx->stream, p);
         }
         HIPCHK(hipGetLastError());
@@ -2932,6 +2973,37 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
     HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out2.p, (size_t)n_models * nspec * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return ANSFM_OK;
+}
+
+int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                   const double *lay_temp, const double *amount, const double *taucia, const double *taudust,
+                                   const double *tauray, const double *tauscat, int ncont, int nth, const double *phasarr,
+                                   const double *lfrac, const double *radg, int ngeom, const double *sol_angs,
+                                   const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                   const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                   int iray, int imie, const double *xfac, double *SPECOUT)
+{
+    CHECK_CTX(ctx);
+    return cirsrad_ck_scatter_batch_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat,
+                                         ncont, nth, phasarr, lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc,
+                                         brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT, ctx->W, 0);
+}
+
+int ansfm_cirsrad_ck_scatter_batch_slice(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                         const double *lay_temp, const double *amount, const double *taucia, const double *taudust,
+                                         const double *tauray, const double *tauscat, int ncont, int nth, const double *phasarr,
+                                         const double *lfrac, const double *radg, int ngeom, const double *sol_angs,
+                                         const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                         const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter_batch_slice: upload a k-table first");
+    if (w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_slice: the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
+    return cirsrad_ck_scatter_batch_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat,
+                                         ncont, nth, phasarr, lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc,
+                                         brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT, W_full, w_begin);
 }
 
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total)

@@ -77,6 +77,11 @@ struct MsParams {
     // carry is set.
     int pw0, nwin, carry_in;
     double *carry;
+    // Store range of the walk (ansfm_cirsrad_ck_scatter_batch_slice at G > 1): stn > 0 -- only the steps of the window's
+    // wavenumbers [st0, st0 + stn) keep their factors, at fc[g][w - st0] (stride stn); the other steps run the same arithmetic
+    // and store to sink [ncomp][nmu*nmu].  stn = 0: every step, stride nwin.
+    int st0, stn;
+    double *sink;
 };
 
 // radg [rows][nr] -> [rows][16]: the chain kernels read it back to front (radg[:, ::-1], :765), so the quadrature's values go to
@@ -313,7 +318,8 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
         for (int e = tid; e < nn; e += 64) fc[e] = pfc[e];
     }
     const long total = (long)p.ng_launch * p.nwin;
-    int wf = 0;                                                  // wavenumber of the next fetch (wraps around: see below)
+    const int sn = p.stn ? p.stn : p.nwin;
+    int wf = 0;                                                 // wavenumber of the next fetch (wraps around: see below)
 #pragma unroll
     for (int d = 0; d < D; ++d) { fetch(d, wf); if (++wf == p.nwin) wf = 0; }
     int ig = p.ig0, widx = 0;
@@ -364,7 +370,9 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
             }
             MS_WAVE_SYNC();
         }
-        double *ofc = p.fc + (((size_t)ig * p.nwin + widx) * p.ncomp + comp) * nn;
+        // outside the store range: the same store to the sink (an address select; the step's arithmetic does not change)
+        const int ws = widx - p.st0;
+        double *ofc = (unsigned)ws < (unsigned)sn ? p.fc + (((size_t)ig * sn + ws) * p.ncomp + comp) * nn : p.sink + (size_t)comp * nn;
 #pragma unroll
         for (int r = 0; r < NE; ++r) {           // a fixed number of stores per step (the waits before the ring's slots count them)
             const int e = CLAMP ? min(tid + 64 * r, nn - 1) : tid + 64 * r;

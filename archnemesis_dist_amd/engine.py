@@ -516,11 +516,16 @@ class AnsfmEngine:
 
     def cirsrad_ck_scatter_batch(self, ISPACE, lay_press_pa, lay_temp, amount, TAUCIA, TAUDUST, TAURAY, TAUSCAT, phasarr, lfrac,
                                  radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie,
-                                 xfac=None):
+                                 xfac=None, wave_slice=None):
         """The scattering branch of CIRSrad for the n forward models of a numerical Jacobian (ansfm_cirsrad_ck_scatter_batch):
         lay_press_pa / lay_temp (n, NLAY), amount (n, NGAS, NLAY), TAUCIA / TAUDUST / TAURAY / TAUSCAT (n, NWAVE, NLAY) or None,
         lfrac (n, NWAVE, NDUST, NLAY), radg (n, NWAVE, NMU); the rest as `cirsrad_ck_scatter` -> SPECOUT (n, NWAVE, NPATH).
-        Layers whose inputs equal model 0's are taken from model 0's doubling results (`last_scatter_cache()`)."""
+        Layers whose inputs equal model 0's are taken from model 0's doubling results (`last_scatter_cache()`).
+
+        wave_slice = (w_begin, W_full): the uploaded table is the slice [w_begin, w_begin + NWAVE) of a W_full axis
+        (ansfm_cirsrad_ck_scatter_batch_slice).  phasarr then covers the whole axis, (NDUST, W_full, 2, NTHETA); every other
+        per-wavenumber input and the result cover the slice.  The slices side by side equal the call over the whole axis, bit
+        for bit."""
         dims, _ = self.ktable_info()
         W, G, S = dims[0], dims[1], dims[4]
         lp = _np(lay_press_pa); n, L = lp.shape
@@ -537,12 +542,17 @@ class AnsfmEngine:
         lf = None if lfrac is None else _np(lfrac).reshape(n, W, ncont, L)
         rg = _np(radg).reshape(n, W, nmu)
         out = np.empty((n, W, P))
-        rc = self._lib.ansfm_cirsrad_ck_scatter_batch(
-            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(_np(lay_temp).reshape(n, L)), _ptr(am), _ptr(nwl(TAUCIA)), _ptr(nwl(TAUDUST)),
-            _ptr(nwl(TAURAY)), _ptr(nwl(TAUSCAT)), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph),
-            _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray),
-            int(imie), _ptr(_np(xfac)), _ptr(out))
-        self._check(rc, "cirsrad_ck_scatter_batch")
+        args = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(_np(lay_temp).reshape(n, L)), _ptr(am), _ptr(nwl(TAUCIA)),
+                _ptr(nwl(TAUDUST)), _ptr(nwl(TAURAY)), _ptr(nwl(TAUSCAT)), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol),
+                _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf),
+                int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out))
+        if wave_slice is None:
+            self._check(self._lib.ansfm_cirsrad_ck_scatter_batch(*args), "cirsrad_ck_scatter_batch")
+            return out
+        w_begin, W_full = (int(v) for v in wave_slice)
+        if phasarr is not None and phasarr.shape[1] != W_full:
+            raise ValueError("cirsrad_ck_scatter_batch: with wave_slice, phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
+        self._check(self._lib.ansfm_cirsrad_ck_scatter_batch_slice(*args, W_full, w_begin), "cirsrad_ck_scatter_batch_slice")
         return out
 
     def last_scatter_cache(self):

@@ -199,6 +199,54 @@ def jacobian_nemesis_batched(model, rank=0, world_size=1, group=None, force_coll
     return finite_difference_jacobian_dev(allY, XN, inum, FIX=np.asarray(V.FIX))
 
 
+# cirsrad_ck_scatter_batch's per-wavenumber inputs and their wavenumber axis (the model axis comes first where there is one);
+# phasarr is not among them: the Hansen walk of every slice runs over the whole axis
+_SCATTER_WAVE_AXIS = {"TAUCIA": 1, "TAUDUST": 1, "TAURAY": 1, "TAUSCAT": 1, "lfrac": 1, "radg": 1, "solar": 0, "brdf_matrix": 0,
+                      "xfac": 0}
+
+
+def scatter_slice_inputs(inputs, w_begin, w_end):
+    """The keyword arguments of `cirsrad_ck_scatter_batch` over the whole spectral axis -> those of the slice [w_begin, w_end):
+    every per-wavenumber input cut, phasarr and the rest as they are."""
+    out = dict(inputs)
+    for k, ax in _SCATTER_WAVE_AXIS.items():
+        if inputs.get(k) is not None:
+            a = np.asarray(inputs[k])
+            out[k] = np.ascontiguousarray(a[(slice(None),) * ax + (slice(w_begin, w_end),)])
+    return out
+
+
+def jacobian_scatter_sharded(eng, inputs, XN, inum, rank=0, world_size=1, group=None, FIX=None, device="cpu",
+                             force_collective=False):
+    """Numerical Jacobian of a scattering batch with the spectral axis sharded over ranks: jacobian_nemesis_batched(shard=
+    "wavenumbers") for `cirsrad_ck_scatter_batch`.
+
+    inputs: its keyword arguments over the whole axis of W_full wavenumbers for the nfm forward models, row 0 the unperturbed
+    state and row 1 + i the state with element inum[i] of XN perturbed.  `eng` holds rank r's slice chunk_range(W_full, n, r)
+    of the table; the rank runs every model on its slice (wave_slice), and one all_gather puts the (nfm, W_local * NPATH)
+    blocks -- wavenumber-major within a block -- side by side in rank order: (nfm, W_full, NPATH).  A rank with an empty
+    slice (more ranks than wavenumbers) joins the gather with an empty block.  -> YN (NPATH * W_full,), KK (NPATH * W_full,
+    NX) on every rank, rows path-major (path outer, wavenumber inner) as the measurement vector of jacobian_nemesis.
+    device: where the gathered spectra live (the rank's GPU with the nccl backend)."""
+    import torch
+    W_full = np.asarray(inputs["solar"]).shape[0]
+    nfm = np.asarray(inputs["lay_press_pa"]).shape[0]
+    P = np.atleast_1d(inputs["sol_angs"]).shape[0]
+    if len(inum) != nfm - 1:
+        raise ValueError("jacobian_scatter_sharded: one perturbed element per forward model after the first")
+    parts = [chunk_range(W_full, world_size, r) for r in range(world_size)]
+    s, e = parts[rank]
+    if e > s:
+        spec = eng.cirsrad_ck_scatter_batch(**scatter_slice_inputs(inputs, s, e), wave_slice=(s, W_full))    # (nfm, W_local, P)
+    else:
+        spec = np.zeros((nfm, 0, P))
+    block = torch.as_tensor(np.ascontiguousarray(spec).reshape(nfm, (e - s) * P), dtype=torch.float64, device=device)
+    allY = gather_wavenumber_blocks(block, [(e_ - s_) * P for s_, e_ in parts], rank, world_size, group=group,
+                                    force=force_collective)
+    allY = allY.reshape(nfm, W_full, P).transpose(1, 2).reshape(nfm, P * W_full)
+    return finite_difference_jacobian_dev(allY, XN, inum, FIX=FIX)
+
+
 def jacobian_nemesis_sharded(fm, rank=0, world_size=1, device=None, analytical_gradient=False, group=None, **flags):
     """Numerical Jacobian with the forward models sharded over ranks (one process per GPU).
 

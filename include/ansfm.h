@@ -352,6 +352,21 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
                                    const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
                                    const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
                                    int iray, int imie, const double *xfac, double *SPECOUT);
+/* The same batch on a slice of the spectral axis (one rank of a wavenumber-sharded Jacobian): the context holds the slice
+ * [w_begin, w_begin + W_local) of a W_full axis (W_local = the uploaded table's width).  phasarr covers the whole axis,
+ * [ncont][W_full][2][nth]; taucia / taudust / tauray / tauscat, lfrac, radg, solar, brdf_matrix, xfac and SPECOUT
+ * [n][W_local][ngeom] cover the slice.  The Hansen factors depend on every earlier (g, wavenumber) of the walk, so the walk
+ * runs over the whole axis (up to the slice's end at G = 1) and keeps the slice's factors: the slices, side by side, are
+ * bit-identical to ansfm_cirsrad_ck_scatter_batch over the whole axis; W_full = W_local, w_begin = 0 is that call.  A slice
+ * needs the layer cache (n_models > 1, layer de-duplication on): ANSFM_ERR_UNSUPPORTED otherwise.  ANSFM_ERR_INVALID when
+ * w_begin < 0, w_begin + W_local > W_full or phasarr is NULL with ncont > 0. */
+int ansfm_cirsrad_ck_scatter_batch_slice(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                         const double *lay_temp, const double *amount, const double *taucia, const double *taudust,
+                                         const double *tauray, const double *tauscat, int ncont, int nth, const double *phasarr,
+                                         const double *lfrac, const double *radg, int ngeom, const double *sol_angs,
+                                         const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                         const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total);
 /* Spectral windows of phase matrices / Hansen factors in the last scattering call (ansfm_cirsrad_ck_scatter(_batch),
  * ansfm_scloud11wave_core) and the wavenumbers per window: 1 and W when one window covers the axis (always at G > 1). */

@@ -1,5 +1,7 @@
 """Batched numerical Jacobian of the scattering configuration at BASELINE configs[3] size (ansfm_cirsrad_ck_scatter_batch):
-    python tools/c4_jacobian.py [--nx 20] [--waves 10000] [--check]"""
+    python tools/c4_jacobian.py [--nx 20] [--waves 10000] [--check]
+One rank's share of the wavenumber-sharded Jacobian (ansfm_cirsrad_ck_scatter_batch_slice) on one GPU:
+    python tools/c4_jacobian.py --nx 200 --rank-of 8 [--rank 7]"""
 import argparse
 import os
 import sys
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--forward", type=int, default=0, help="only time this many calls of ONE forward model (C4 size)")
     ap.add_argument("--nmu", type=int, default=16, help="zenith quadrature points (16: the matrix-core chain; the reference's default is 5)")
     ap.add_argument("--nf", type=int, default=8, help="Fourier orders - 1 (the reference's default is 2)")
+    ap.add_argument("--rank-of", type=int, default=0, help="time one rank's slice chunk_range(waves, N, rank) of the axis")
+    ap.add_argument("--rank", type=int, default=0)
     args = ap.parse_args()
     import torch
     import archnemesis_dist_amd as pkg
@@ -44,7 +48,14 @@ def main():
     _, delg = syn.gauss_legendre_01(G, as_float32=True)
     PRESS, TEMP, K = torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
     WAVE = 200.0 + 0.1 * np.arange(W)
-    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32))
+    if args.rank_of:                            # the rank's slice of the table only
+        from archnemesis_dist_amd.jacobian import chunk_range
+        ws, we = chunk_range(W, args.rank_of, args.rank)
+        K = K[ws:we].contiguous()
+        torch.cuda.empty_cache()
+        eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE[ws:we], delg.astype(np.float32))
+    else:
+        eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32))
     del K
     npro = max(args.nx // 2, 2)
     pr = syn.synth_profiles(100, S + 2, seed=11)
@@ -60,6 +71,9 @@ def main():
     radg = np.stack([np.repeat((c1 * WAVE ** 3 / (np.exp(c2 * WAVE / lay["TEMP"][m, 0]) - 1.0))[:, None], NMU, 1) for m in range(n)])
     a = (0, lay["PRESS"], lay["TEMP"], lay["amount"], None, rep(TAUDUST), rep(TAURAY), rep(TAUSCAT), ph, rep(np.ones((W, 1, L))), radg,
          [30.0], [20.0], [45.0], np.full(W, 1e-8), 0, np.zeros((W, NMU, NMU, NF + 1)), MU, WT, NF, 101, 1, 1)
+    if args.rank_of:
+        rank_share(args, eng, a, W, ws, we, n, PRESS, TEMP, WAVE, delg)
+        return
     if args.forward:
         ts = []
         for it in range(args.forward):
@@ -86,6 +100,49 @@ def main():
         print("every state equals a call of its own, bit for bit")
     kk = (spec[1:, :, 0] - spec[0:1, :, 0])
     print("max |dY| / |Y| per column:", np.max(np.abs(kk) / np.abs(spec[0:1, :, 0]), axis=1)[:6])
+
+
+def rank_share(args, eng, a, W, ws, we, n, PRESS, TEMP, WAVE, delg):
+    """wall time of the rank's batch, the share of it every rank repeats (phase matrices and the Hansen walk over the whole
+    axis: the same call on a slice of ONE wavenumber, whose chains cost next to nothing) and the device memory the call adds"""
+    import torch
+    import archnemesis_dist_amd as pkg
+    from archnemesis_dist_amd.jacobian import scatter_slice_inputs
+    names = ("ISPACE lay_press_pa lay_temp amount TAUCIA TAUDUST TAURAY TAUSCAT phasarr lfrac radg sol_angs emiss_angs aphis "
+             "solar lowbc brdf_matrix mu1 wt1 nf nphi iray imie").split()
+    full = dict(zip(names, a))
+    for k in ("TAUDUST", "TAURAY", "TAUSCAT", "lfrac", "radg", "solar", "brdf_matrix"):
+        full[k] = np.asarray(full[k])
+    mine = scatter_slice_inputs(full, ws, we)
+    free0 = torch.cuda.mem_get_info(0)[0]
+    ts = []
+    for it in range(3):
+        t0 = time.perf_counter()
+        spec = eng.cirsrad_ck_scatter_batch(**mine, wave_slice=(ws, W))
+        ts.append(time.perf_counter() - t0)
+    scratch = free0 - torch.cuda.mem_get_info(0)[0]           # buffers the context grew to (it keeps them)
+    # the replicated part: a slice of one wavenumber (the last) -- the walk covers the whole axis whatever the slice
+    one = pkg.AnsfmEngine(0)
+    from bench import torch_ktable
+    dev = torch.device("cuda", 0)
+    G, S, NP, NT = 20, 8, 20, 15
+    _, _, K = torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+    K1 = K[W - 1:W].contiguous()
+    del K
+    torch.cuda.empty_cache()
+    one.upload_ktable(K1, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE[W - 1:W], delg.astype(np.float32))
+    tw = []
+    for it in range(3):
+        t0 = time.perf_counter()
+        one.cirsrad_ck_scatter_batch(**scatter_slice_inputs(full, W - 1, W), wave_slice=(W - 1, W))
+        tw.append(time.perf_counter() - t0)
+    one.close()
+    t, w = min(ts[1:]), min(tw[1:])
+    print("rank %d of %d: wavenumbers [%d, %d) of %d, n = %d forward models, nmu %d / NF %d: %.3f s (calls %s); walk and phase "
+          "matrices over the whole axis (a one-wavenumber slice) %.3f s = %.0f %%; device memory the call holds %.2f GB; cache %s"
+          % (args.rank, args.rank_of, ws, we, W, n, args.nmu, args.nf, t, " ".join("%.3f" % x for x in ts), w, 100.0 * w / t,
+             scratch / 1e9, eng.last_scatter_cache()))
+    print("checksum %.17g" % float(spec.sum()))
 
 
 if __name__ == "__main__":
