@@ -71,7 +71,7 @@ struct MsParams {
     // 1 / 0, the phase matrices, the surface operator and the boundary radiance zero there: every operator is block diagonal with
     // the quadrature's block in front and a block that couples to nothing behind it
     int nmu_real;
-    // Spectral window (G = 1, ms_launch): ppl / pmi / fc hold the wavenumbers [pw0, pw0 + nwin) only and every reader indexes
+    // Spectral window (G = 1, ms_single): ppl / pmi / fc hold the wavenumbers [pw0, pw0 + nwin) only and every reader indexes
     // them relative to pw0 (pw0 = 0, nwin = nwave: the whole axis).  k_ms_hansen_seq continues from carry [ncomp][nmu*nmu] --
     // the factors of the last step of the previous window -- when carry_in is set, and leaves its own last factors there when
     // carry is set.
