@@ -30,6 +30,7 @@ EXPORTS = [
     "ansfm_cirsrad_ck_singlescatt", "ansfm_cirsrad_ck_scatter_batch", "ansfm_last_scatter_cache",
     "ansfm_layer_average_dev", "ansfm_calc_tau_rayleigh_batch_dev_in", "ansfm_last_rt_shared",
     "ansfm_cirsrad_ck_thermal_ray_dev", "ansfm_last_scatter_windows", "ansfm_cirsrad_ck_scatter_batch_slice",
+    "ansfm_cirsrad_ck_singlescatt_batch",
 ]
 
 _lib = None
@@ -136,6 +137,7 @@ def load():
     lib.ansfm_cirsradg_ck_transmission.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]
     lib.ansfm_singlescatt_plane_spectrum.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, cd, vp, vp, vp, cd, cd, vp]
     lib.ansfm_cirsrad_ck_singlescatt.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp]
+    lib.ansfm_cirsrad_ck_singlescatt_batch.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci] + [vp] * 12
     lib.ansfm_get_taugas.argtypes = [vp, ci, vp]
     lib.ansfm_scloud11wave_core.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, ci, ci,
                                             vp, vp, vp, ci, ci, ci, vp, vp]

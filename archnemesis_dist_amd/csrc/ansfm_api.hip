@@ -76,7 +76,7 @@ struct ansfm_ctx {
     DevBuf dspec_ref, map_out, map_b, map_batch;
     DevBuf dd_slot, dd_work, dd_in;      // layer de-duplication: row map [n][L], work list, packed inputs
     DevBuf ms_radg16, ms_brdf16;         // 7 .. 15 streams padded to the 16-stream kernels' layout
-    DevBuf rt_prefix, rt_same;           // thermal RT of a batch: state 0's records along every path; same flags [n][L] + jstart [n][P]
+    DevBuf rt_prefix, rt_same;           // thermal RT of a batch: state 0's records along every path; same flags [n][L] (single scattering: [n][P][L]) + jstart [n][P]
     int last_rt_shared = 0;
     int dedup = 1;                       // ansfm_set_layer_dedup
     int last_rows = 0, last_dedup = 0;   // opacity rows computed by the last cirsrad call / whether tau_slot applies
@@ -609,31 +609,48 @@ static int launch_rt(ansfm_ctx *ctx, const RtParams &p_in, int n_models)
     if (p.LIMAX > 1500) FAIL(ANSFM_ERR_UNSUPPORTED, "thermal RT: at most 1500 layers along a path");
     if (p.P > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, "thermal RT: at most 65535 paths per call");
     ctx->last_rt_shared = 0;
-    // a de-duplicated batch (the states of a numerical Jacobian) in thermal emission: every state starts each path from the
-    // record state 0 left after the last layer the two have in common
+    // single scattering on the vertical opacities (CIRSrad's branch; the array-level seam hands omega in and keeps the run-time mode)
+    const bool ss = p.mode == 2 && p.sca && !p.omega;
+    // a de-duplicated batch (the states of a numerical Jacobian) in thermal emission or single scattering: every state starts
+    // each path from the record state 0 left after the last layer the two have in common
     static const bool prefix_off = [] { const char *e = getenv("ANSFM_RT_PREFIX"); return e && e[0] == '0'; }();
     const size_t rec = (size_t)p.P * p.LIMAX * 3 * p.G * p.Wpad * sizeof(double);
-    if (!prefix_off && n_models >= 4 && n_models <= 65536 && p.tau_slot && p.mode == 0 && !p.emi && !p.per_g && rec <= ((size_t)4 << 30)) {
+    if (!prefix_off && n_models >= 4 && n_models <= 65536 && p.tau_slot && (p.mode == 0 || ss) && !p.emi && !p.per_g && rec <= ((size_t)4 << 30)) {
         HIPCHK(ctx->rt_prefix.reserve(rec));
-        const size_t nl = (size_t)n_models * p.L, np = (size_t)n_models * p.P;
+        const size_t nl = (size_t)n_models * p.L * (ss ? p.P : 1), np = (size_t)n_models * p.P;   // ss: flags per path
         const size_t off_j = (nl + 15) & ~(size_t)15;
         HIPCHK(ctx->rt_same.reserve(off_j + np * sizeof(int32_t)));
         unsigned char *same = ctx->rt_same.as<unsigned char>();
         int32_t *jstart = reinterpret_cast<int32_t *>(same + off_j);
-        hipLaunchKernelGGL(k_rt_same, dim3((unsigned)p.L, (unsigned)(n_models - 1)), dim3(256), 0, ctx->stream, p.L, p.Wpad, p.tau_slot,
-                           p.cont_by_row ? nullptr : p.cont, same);      // a continuum stored by row is the row's
+        if (ss)
+            hipLaunchKernelGGL(k_rt_same_ss, dim3((unsigned)p.L, (unsigned)(n_models - 1)), dim3(256), 0, ctx->stream, p.L, p.Wpad, p.P,
+                               p.tau_slot, p.cont, p.sca, p.phase, same);
+        else
+            hipLaunchKernelGGL(k_rt_same, dim3((unsigned)p.L, (unsigned)(n_models - 1)), dim3(256), 0, ctx->stream, p.L, p.Wpad, p.tau_slot,
+                               p.cont_by_row ? nullptr : p.cont, same);      // a continuum stored by row is the row's
         hipLaunchKernelGGL(k_rt_jstart, dim3((unsigned)np), dim3(64), 0, ctx->stream, n_models, p.L, p.P, p.LIMAX, p.nlayin, p.layinc,
-                           p.scale, p.emtemp, same, jstart);
+                           p.scale, p.emtemp, same, jstart, ss ? 1 : 0);
         p.prefix = ctx->rt_prefix.as<double>(); p.jstart = jstart; p.m0 = 0;
         const size_t lds = (size_t)4 * p.LIMAX * sizeof(double);
-        hipLaunchKernelGGL((k_thermal_rt<false, 1>), dim3(1u, grid.y, grid.z), dim3(kWave, kGY), lds, ctx->stream, p);
-        p.m0 = 1;
-        hipLaunchKernelGGL((k_thermal_rt<true, 2>), dim3((unsigned)(n_models - 1), grid.y, grid.z), dim3(kWave, kGY), lds, ctx->stream, p);
+        const dim3 g0(1u, grid.y, grid.z), g1((unsigned)(n_models - 1), grid.y, grid.z), blk(kWave, kGY);
+        if (ss) {
+            hipLaunchKernelGGL((k_thermal_rt<false, 1, true>), g0, blk, lds, ctx->stream, p);
+            p.m0 = 1;
+            hipLaunchKernelGGL((k_thermal_rt<true, 2, true>), g1, blk, lds, ctx->stream, p);
+        } else {
+            hipLaunchKernelGGL((k_thermal_rt<false, 1>), g0, blk, lds, ctx->stream, p);
+            p.m0 = 1;
+            hipLaunchKernelGGL((k_thermal_rt<true, 2>), g1, blk, lds, ctx->stream, p);
+        }
         HIPCHK(hipGetLastError());
         ctx->last_rt_shared = 1;
         return ANSFM_OK;
     }
-    if (n_models >= 4)
+    if (ss && n_models >= 4)
+        hipLaunchKernelGGL((k_thermal_rt<true, 0, true>), grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
+    else if (ss)
+        hipLaunchKernelGGL((k_thermal_rt<false, 0, true>), grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
+    else if (n_models >= 4)
         hipLaunchKernelGGL(k_thermal_rt<true>, grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
     else
         hipLaunchKernelGGL(k_thermal_rt<false>, grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
@@ -1172,51 +1189,69 @@ int ansfm_singlescatt_plane_spectrum(ansfm_ctx *ctx, int ISPACE, int W, int G, i
     return ANSFM_OK;
 }
 
-int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
-                                 const double *amount, const double *taucont, const double *tausca, const double *phase, int P,
-                                 int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                 const double *EMTEMP, double TSURF, const double *EMISSIVITY, const double *BRDF,
-                                 const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
-                                 double *SPECOUT)
+// CIRSrad's single-scattering branch for n_models states (host pointers; TSURF [n]): the gas opacities of the distinct (model,
+// layer) rows, then mode 2 of k_thermal_rt with the model axis -- the prefix records of state 0 when the batch is de-duplicated
+static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const char *fn, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, const double *taucont, const double *tausca,
+                                       const double *phase, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                       const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                       const double *BRDF, const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG,
+                                       const double *xfac, double *SPECOUT)
 {
     CHECK_CTX(ctx);
-    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_singlescatt: upload a k-table first");
-    if (L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !tausca || !phase || !NLAYIN || !LAYINC ||
-        !SCALE || !EMTEMP || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT || (ISPACE != 0 && ISPACE != 1) ||
-        (TSURF > 0.0 && !EMISSIVITY))
-        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_singlescatt: bad argument");
+    if (!ctx->have_table) { ctx->err = std::string(fn) + ": upload a k-table first"; return ANSFM_ERR_NOTABLE; }
+    bool bad = n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !tausca || !phase ||
+               !NLAYIN || !LAYINC || !SCALE || !EMTEMP || !TSURF || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT ||
+               (ISPACE != 0 && ISPACE != 1);
+    for (int m = 0; !bad && m < n_models; ++m) bad = TSURF[m] > 0.0 && !EMISSIVITY;
+    if (bad) { ctx->err = std::string(fn) + ": bad argument"; return ANSFM_ERR_INVALID; }
+    if ((size_t)n_models * P > 65535) { ctx->err = std::string(fn) + ": at most 65535 (model, path) pairs per call"; return ANSFM_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
-    const size_t D = sizeof(double), WL = (size_t)W * L;
-    const double tsurf1 = TSURF;
+    const size_t D = sizeof(double), WL = (size_t)W * L, nl = (size_t)n_models * L, nlp = (size_t)n_models * LIMAX * P;
     Stager st{ctx};
-    const double *press = st.up(lay_press_pa, L), *temp = st.up(lay_temp, L), *am = st.up(amount, (size_t)S * L),
-                 *cont = st.up(taucont, WL), *sca = st.up(tausca, WL), *ph = st.up(phase, (size_t)P * WL);
+    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
+                 *cont = st.up(taucont, n_models * WL), *sca = st.up(tausca, n_models * WL), *ph = st.up(phase, (size_t)n_models * P * WL);
     const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
-    const double *scale = st.up(SCALE, (size_t)LIMAX * P), *emtemp = st.up(EMTEMP, (size_t)LIMAX * P), *tsurf = st.up(&tsurf1, 1),
+    const double *scale = st.up(SCALE, nlp), *emtemp = st.up(EMTEMP, nlp), *tsurf = st.up(TSURF, n_models),
                  *emis = st.up(EMISSIVITY, W), *brdf = st.up(BRDF, (size_t)W * P), *solflux = st.up(SOLFLUX, W),
                  *sol_ang = st.up(SOL_ANG, P), *emiss_ang = st.up(EMISS_ANG, P), *xf = st.up(xfac, W);
     if (st.rc) return st.rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));       // tsurf1 is a stack variable
-    int rc;
-    if ((rc = gas_opacity(ctx, L, press, temp, am))) return rc;
-    ctx->last_n = 1; ctx->last_L = L; ctx->last_rows = L; ctx->last_dedup = 0;
-    // reference layouts [W][L] -> [L][Wpad] (continuum, scattering opacity) and [P][W][L] -> [P][L][Wpad] (phase)
-    HIPCHK(ctx->cont_t.reserve((size_t)L * Wpad * D));
-    HIPCHK(ctx->misc.reserve((size_t)(1 + P) * L * Wpad * D));
-    double *sca_t = ctx->misc.as<double>(), *ph_t = sca_t + (size_t)L * Wpad;
+    if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+    // ---- which (model, layer) opacities have to be computed: all of them, or (batches) the distinct ones -------
+    DedupRows k{n_models * L, press, temp, am};
+    int n_k = n_models, rc;
+    const int32_t *tau_slot = nullptr;
+    if (ctx->dedup && n_models > 1) {
+        if ((rc = dedup_rows(ctx, n_models, L, press, temp, am, nullptr, nullptr, &k))) return rc;
+        n_k = 1;
+        tau_slot = ctx->dd_slot.as<int32_t>();
+    }
+    const int rows = k.rows;
+    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = rows; ctx->last_dedup = tau_slot != nullptr;
+    if ((rc = gas_prep(ctx, rows, k.press, k.temp))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    if (ctx->is_lbl) rc = gas_tau(ctx, n_k, rows / n_k, k.press, k.temp, k.amount, false);
+    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, n_k, rows / n_k, k.press, k.temp, k.amount, generic); });
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    // reference layouts [n][W][L] -> [n][L][Wpad] (continuum, scattering opacity) and [n][P][W][L] -> [n][P][L][Wpad] (phase)
+    const size_t LW = (size_t)L * Wpad;
+    HIPCHK(ctx->cont_t.reserve(nl * Wpad * D));
+    HIPCHK(ctx->misc.reserve((size_t)n_models * (1 + P) * LW * D));
+    double *sca_t = ctx->misc.as<double>(), *ph_t = sca_t + (size_t)n_models * LW;
     const double *cont_t = nullptr;
     if (cont) {
-        launch_w_to_last(ctx->stream, (unsigned)1, cont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0);
+        launch_w_to_last(ctx->stream, (unsigned)n_models, cont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, WL, LW);
         cont_t = ctx->cont_t.as<double>();
     }
-    launch_w_to_last(ctx->stream, (unsigned)1, sca, sca_t, W, Wpad, 1, L, 0, 0.0);
-    launch_w_to_last(ctx->stream, (unsigned)P, ph, ph_t, W, Wpad, 1, L, 0, 0.0, WL, (size_t)L * Wpad);
+    launch_w_to_last(ctx->stream, (unsigned)n_models, sca, sca_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
+    launch_w_to_last(ctx->stream, (unsigned)(n_models * P), ph, ph_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
     HIPCHK(hipGetLastError());
-    HIPCHK(ctx->tmp_out.reserve((size_t)W * P * D));
+    HIPCHK(ctx->tmp_out.reserve((size_t)n_models * W * P * D));
     RtParams r;
     memset(&r, 0, sizeof r);
-    r.tau = ctx->tau.as<double>(); r.cont = cont_t; r.sca = sca_t; r.phase = ph_t;
+    r.tau = ctx->tau.as<double>(); r.tau_slot = tau_slot; r.cont = cont_t; r.sca = sca_t; r.phase = ph_t;
     r.wave = ctx->d_wave.as<double>(); r.delg = ctx->d_delg.as<double>();
     r.nlayin = nlayin; r.layinc = layinc; r.scale = scale;
     r.emtemp = emtemp; r.lay_press = press; r.tsurf = tsurf;
@@ -1224,10 +1259,37 @@ int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double
     r.sol_ang = sol_ang; r.emiss_ang = emiss_ang; r.xfac = xf;
     r.out = ctx->tmp_out.as<double>();
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0; r.mode = 2;
-    if ((rc = launch_rt(ctx, r, 1))) return rc;
-    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)W * P * D, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+    if ((rc = launch_rt(ctx, r, n_models))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->overlap_launches = 1; ctx->rt_launches = 1; ctx->overlap_ms = -1.0;
+    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)n_models * W * P * D, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // also: the staged host arrays (TSURF of the single entry) are consumed
     return ANSFM_OK;
+}
+
+int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
+                                 const double *amount, const double *taucont, const double *tausca, const double *phase, int P,
+                                 int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                 const double *EMTEMP, double TSURF, const double *EMISSIVITY, const double *BRDF,
+                                 const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                 double *SPECOUT)
+{
+    return cirsrad_ck_singlescatt_impl(ctx, "cirsrad_ck_singlescatt", ISPACE, 1, L, lay_press_pa, lay_temp, amount, taucont, tausca,
+                                       phase, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, &TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG,
+                                       EMISS_ANG, xfac, SPECOUT);
+}
+
+int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, const double *taucont, const double *tausca,
+                                       const double *phase, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                       const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                       const double *BRDF, const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG,
+                                       const double *xfac, double *SPECOUT)
+{
+    return cirsrad_ck_singlescatt_impl(ctx, "cirsrad_ck_singlescatt_batch", ISPACE, n_models, L, lay_press_pa, lay_temp, amount,
+                                       taucont, tausca, phase, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF,
+                                       SOLFLUX, SOL_ANG, EMISS_ANG, xfac, SPECOUT);
 }
 
 int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR, int NLAYIN, const double *WAVE,

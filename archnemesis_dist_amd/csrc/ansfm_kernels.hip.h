@@ -1331,13 +1331,14 @@ struct RtParams {
     // mode 2: single-scattering albedo of every layer, either given per g (array-level seam) or formed from the vertical
     // opacities as (TAURAY + TAUSCAT) / TAUTOT where TAUTOT > 0 (:4276-4283); layer-mean phase function per path; BRDF
     const double *omega;    // [Li][G][Wpad] along the path, or nullptr
-    const double *sca;      // [L][Wpad] TAURAY + TAUSCAT of the layers, or nullptr
-    const double *phase;    // [P][L][Wpad] (by layer; the array-level seam passes L = Li, identity LAYINC)
+    const double *sca;      // [n][L][Wpad] TAURAY + TAUSCAT of the layers, or nullptr
+    const double *phase;    // [n][P][L][Wpad] (by layer; the array-level seam passes n = 1, L = Li, identity LAYINC)
     const double *brdf;     // [W][P] or nullptr
     // The states of a numerical Jacobian share the top of every path with state 0 (k_thermal_rt<.., PREFIX>): state 0's
     // launch (PREFIX 1, m0 = 0) leaves (taud, trold, spec) after every layer of the path in `prefix`
     // [P][LIMAX][3][G][Wpad]; the launch of the states m0 .. (PREFIX 2) starts state m's path ip at layer jstart[m][ip] --
-    // the first one whose opacity row, continuum, SCALE or EMTEMP is not state 0's -- from that record.  Same bits.
+    // the first one whose opacity row, continuum, SCALE or EMTEMP (mode 2 from the vertical opacities: or scattering opacity,
+    // or phase function of that path) is not state 0's -- from that record.  Same bits.
     double *prefix;
     const int32_t *jstart;  // [n][P]
     int m0;
@@ -1359,11 +1360,40 @@ __global__ void k_rt_same(int L, int Wpad, const int32_t *__restrict__ slot, con
     if (threadIdx.x == 0) same[(size_t)m * L + lay] = differs ? 0 : 1;
 }
 
+// Single scattering (mode 2 on sca / phase): same[m][ip][lay] = as k_rt_same, and the scattering opacity of (m, lay) and the
+// phase function of path ip there are state 0's as well, bit for bit.  cont / sca [n][L][Wpad], phase [n][P][L][Wpad].
+// grid (L, n - 1), block 256
+__global__ void k_rt_same_ss(int L, int Wpad, int P, const int32_t *__restrict__ slot, const double *__restrict__ cont,
+                             const double *__restrict__ sca, const double *__restrict__ phase, unsigned char *same)
+{
+    const int lay = blockIdx.x, m = blockIdx.y + 1;
+    int differs = slot[(size_t)m * L + lay] != slot[lay];
+    for (int c = 0; c < 2 && !differs; ++c) {
+        const double *arr = c ? sca : cont;
+        if (!arr) continue;
+        const long long *a = reinterpret_cast<const long long *>(arr + ((size_t)m * L + lay) * Wpad);
+        const long long *b = reinterpret_cast<const long long *>(arr + (size_t)lay * Wpad);
+        for (int i = threadIdx.x; i < Wpad; i += blockDim.x) differs |= (a[i] != b[i]);
+    }
+    differs = __syncthreads_or(differs);               // block-uniform from here on
+    for (int ip = 0; ip < P; ++ip) {
+        int d = differs;
+        if (!d) {
+            const long long *a = reinterpret_cast<const long long *>(phase + (((size_t)m * P + ip) * L + lay) * Wpad);
+            const long long *b = reinterpret_cast<const long long *>(phase + ((size_t)ip * L + lay) * Wpad);
+            for (int i = threadIdx.x; i < Wpad; i += blockDim.x) d |= (a[i] != b[i]);
+            d = __syncthreads_or(d);
+        }
+        if (threadIdx.x == 0) same[((size_t)m * P + ip) * L + lay] = d ? 0 : 1;
+    }
+}
+
 // jstart[m][ip] = number of leading layers of path ip that state m shares with state 0 (one wave per (m, ip); m = 0: 0)
+// per_path: same is k_rt_same_ss's [n][P][L], not k_rt_same's [n][L]
 __global__ __launch_bounds__(64) void k_rt_jstart(int n, int L, int P, int LIMAX, const int32_t *__restrict__ nlayin,
                                                   const int32_t *__restrict__ layinc, const double *__restrict__ scale,
                                                   const double *__restrict__ emtemp, const unsigned char *__restrict__ same,
-                                                  int32_t *jstart)
+                                                  int32_t *jstart, int per_path)
 {
     const int idx = blockIdx.x, lane = threadIdx.x;
     const int m = idx / P, ip = idx % P;
@@ -1371,13 +1401,14 @@ __global__ __launch_bounds__(64) void k_rt_jstart(int n, int L, int P, int LIMAX
     if (m > 0) {
         const int nl = nlayin[ip];
         const size_t pm = (size_t)m * LIMAX * P + ip, p0 = ip;
+        const unsigned char *same_m = same + (per_path ? ((size_t)m * P + ip) * L : (size_t)m * L);
         first = nl;
         for (int j0 = 0; j0 < nl; j0 += 64) {
             const int j = j0 + lane;
             bool bad = false;
             if (j < nl) {
                 const int lay = layinc[(size_t)j * P + ip];
-                bad = !same[(size_t)m * L + lay] ||
+                bad = !same_m[lay] ||
                       __double_as_longlong(scale[pm + (size_t)j * P]) != __double_as_longlong(scale[p0 + (size_t)j * P]) ||
                       __double_as_longlong(emtemp[pm + (size_t)j * P]) != __double_as_longlong(emtemp[p0 + (size_t)j * P]);
             }
@@ -1397,7 +1428,10 @@ __device__ __forceinline__ double planck_bb(double a, double c2y, double T)
 // kernel's natural 142 registers a second block does not fit on the CU, and a batch has the blocks to fill it: capped at 128
 // (14 spilled) the 201 states of a C3 Jacobian take 9.2 instead of 11.4 ms.  A single model has 157 blocks for 256 CUs and
 // only pays for the spills (0.093 -> 0.107 ms): it keeps the uncapped build.
-template <bool BATCH, int PREFIX = 0>
+// SS: the build for mode 2 on the vertical opacities (p.sca, p.phase with a model axis; CIRSrad's single-scattering branch):
+// the scattering opacity and the phase function of layer j + 1 are fetched with its opacities, ahead of layer j's arithmetic.
+// The other builds keep the run-time p.mode (the array-level seam's p.omega among them) and are not touched by it.
+template <bool BATCH, int PREFIX = 0, bool SS = false>
 __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATCH ? 4 : 1, BATCH ? 4 : 8))) void k_thermal_rt(RtParams p)
 {
     __shared__ double red[kGY][kWave];
@@ -1451,19 +1485,25 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
     // mode 2 (single scattering): ssfac = mu0 / (mu0 + mu) and the solar flux over 4 pi, wave-uniform per path (:6557-6559)
     const double PI_ = 3.141592653589793;
     double ssfac = 0.0, mu0s = 0.0, sflux = 0.0;
-    if (p.mode == 2) {
+    if (SS || p.mode == 2) {
         const double mu = cos(p.emiss_ang[ip] / 180. * PI_);
         mu0s = cos(p.sol_ang[ip] / 180. * PI_);
         ssfac = mu0s / (mu0s + mu);
         sflux = p.solflux ? p.solflux[nuc] : 0.0;
     }
+    // SS: the scattering opacity and the phase function of layer j, fetched with its opacities
+    auto fetch_ss = [&](int j, double sp[2]) {
+        const int lay = (int)m_lay[j];
+        sp[0] = p.sca[((size_t)m * p.L + lay) * p.Wpad + nu];
+        sp[1] = p.phase[(((size_t)m * p.P + ip) * p.L + lay) * p.Wpad + nu];
+    };
     auto scatter_term = [&](int j, int k, double tvk, double tc, double dtr) -> double {
         // (trold - tr) * ssfac * omega * phase * SOLFLUX / (4 pi), in the reference's order of operations (:6577)
         const int lay = (int)m_lay[j];
         const int g = gy + k * kGY;
         double om;
         if (p.omega) om = p.omega[((size_t)j * G + g) * p.Wpad + nu];
-        else {
+        else {              // one model; launch_rt sends p.sca to the SS builds.  Kept: without it the mode-0 builds compile differently
             const double tt = tvk + tc;                                   // vertical TAUTOT of the layer (:3989)
             om = (tt > 0.0) ? p.sca[(size_t)lay * p.Wpad + nu] / tt : 0.0;
         }
@@ -1471,6 +1511,8 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
         return dtr * ssfac * om * ph * sflux / (4. * PI_);
     };
     double tvA[kGPer], tvB[kGPer], tcA = 0.0, tcB = 0.0, emA = 0.0, emB = 0.0;
+    double ssA[2], ssB[2];                               // SS: fetch_ss's values beside tvA / tvB
+    const double *ss = ssA;                              // ... of the layer being integrated
     auto integrate = [&](int j, const double tv[kGPer], double tc, double em) {
         const double sc = m_sc[j];
         const double bb = planck_bb(a, c2y, m_T[j]);
@@ -1481,7 +1523,11 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
                 const double t = (tv[k] + tc) * sc;  // :3989, :4006
                 taud[k] += t;
                 const double tr = exp(-taud[k]);
-                if (p.mode == 2) spec[k] += scatter_term(j, k, tv[k], tc, trold[k] - tr);   // before the thermal term (:6577-6581)
+                if constexpr (SS) {                  // scatter_term on the fetched values, the same order of operations
+                    const double tt = tv[k] + tc;
+                    const double om = (tt > 0.0) ? ss[0] / tt : 0.0;
+                    spec[k] += (trold[k] - tr) * ssfac * om * ss[1] * sflux / (4. * PI_);
+                } else if (p.mode == 2) spec[k] += scatter_term(j, k, tv[k], tc, trold[k] - tr);   // before the thermal term (:6577-6581)
                 spec[k] += (trold[k] - tr) * bb;  // :6345-6348
                 if (p.emi) spec[k] += em * tr;
                 trold[k] = tr;
@@ -1517,14 +1563,18 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
         }
     }
     if (j < nl) fetch(j, tvA, tcA, emA);
+    if constexpr (SS) { if (j < nl) fetch_ss(j, ssA); }
     for (; j + 1 < nl; j += 2) {                         // ping-pong buffers: no register rotation
         fetch(j + 1, tvB, tcB, emB);
+        if constexpr (SS) { fetch_ss(j + 1, ssB); ss = ssA; }
         integrate(j, tvA, tcA, emA);
         leave(j);
         if (j + 2 < nl) fetch(j + 2, tvA, tcA, emA);
+        if constexpr (SS) { if (j + 2 < nl) fetch_ss(j + 2, ssA); ss = ssB; }
         integrate(j + 1, tvB, tcB, emB);
         leave(j + 1);
     }
+    if constexpr (SS) ss = ssA;
     if (j < nl) { integrate(j, tvA, tcA, emA); leave(j); }
     // surface / bottom-of-atmosphere term  (:6354-6365)
     int i1 = (int)(nl / 2.0) - 1;
@@ -1557,7 +1607,7 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
         if (g < G) {
             double s = spec[k];
             if (p.mode == 1) s = exp(-taud[k]);                               // :4116, xfac = solar flux when IFORM = 4 (:4119-4127)
-            else if (p.mode == 2) {                                           // :6585-6596: lower boundary whatever the geometry
+            else if (SS || p.mode == 2) {                                     // :6585-6596: lower boundary whatever the geometry
                 const double ts = p.tsurf[m];
                 double rg;
                 if (ts <= 0.0) rg = planck_bb(a, c2y, p.emtemp[pathbase + (size_t)(nl - 1) * p.P]);

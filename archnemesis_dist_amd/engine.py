@@ -306,6 +306,40 @@ class AnsfmEngine:
         self._check(rc, "cirsrad_ck_singlescatt")
         return out
 
+    def cirsrad_ck_singlescatt_batch(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, tausca, phase, NLAYIN, LAYINC, SCALE,
+                                     EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG, EMISS_ANG, xfac=None):
+        """The single-scattering branch of CIRSrad for the n forward models of a numerical Jacobian
+        (ansfm_cirsrad_ck_singlescatt_batch): lay_press_pa / lay_temp (n, NLAY), amount (n, NGAS, NLAY), taucont / tausca
+        (n, NWAVE, NLAY) (taucont may be None), phase (n, NPATH, NWAVE, NLAY), SCALE / EMTEMP (n, LIMAX, NPATH), TSURF (n,); the
+        rest as `cirsrad_ck_singlescatt`, shared by the models -> SPECOUT (n, NWAVE, NPATH).
+        Only the distinct (model, layer) gas opacities are computed (`last_layer_rows()`), and every state starts each path
+        from the record model 0 left after the last layer the two have in common (`last_rt_shared()`).  The same numbers as n
+        `cirsrad_ck_singlescatt` calls, bit for bit."""
+        W, G, NP, NT, S = self.dims
+        lp = _np(lay_press_pa)
+        if lp.ndim != 2:
+            raise ValueError("lay_press_pa must be (n_models, NLAY)")
+        n, L = lp.shape
+        am = _np(amount)
+        if am.shape != (n, S, L):
+            raise ValueError("amount must be (n_models, NGAS, NLAY)")
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        TS = _np(np.atleast_1d(TSURF))
+        if TS.shape != (n,):
+            raise ValueError("TSURF must be (n_models,)")
+        out = np.empty((n, W, P))
+        rc = self._lib.ansfm_cirsrad_ck_singlescatt_batch(
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(_np(lay_temp).reshape(n, L)), _ptr(am),
+            _ptr(None if taucont is None else _np(taucont).reshape(n, W, L)), _ptr(_np(tausca).reshape(n, W, L)),
+            _ptr(_np(phase).reshape(n, P, W, L)), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(_np(SCALE).reshape(n, LIMAX, P)),
+            _ptr(_np(EMTEMP).reshape(n, LIMAX, P)), _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(BRDF).reshape(W, P)),
+            _ptr(_np(SOLFLUX)), _ptr(_np(np.atleast_1d(SOL_ANG))), _ptr(_np(np.atleast_1d(EMISS_ANG))), _ptr(_np(xfac)), _ptr(out))
+        self._check(rc, "cirsrad_ck_singlescatt_batch")
+        return out
+
     def cirsrad_ck_transmission(self, lay_press_pa, lay_temp, amount, taucont, NLAYIN, LAYINC, SCALE, xfac=None):
         """CIRSrad, pure-transmission branch (calculate_transmission_spectrum :4110): SPECOUT (n, W, P) (or (W, P)) =
         xfac * sum_g DELG exp(-sum over the path's layers of TAUTOT_LAYINC)."""
@@ -964,7 +998,7 @@ class AnsfmEngine:
         return int(n.value)
 
     def last_rt_shared(self):
-        """True when the last thermal-emission batch started its states' paths from state 0's records (ansfm_last_rt_shared)."""
+        """True when the last thermal-emission or single-scattering batch started its states' paths from state 0's records (ansfm_last_rt_shared)."""
         v = C.c_int(0)
         self._check(self._lib.ansfm_last_rt_shared(self._ctx, C.byref(v)), "last_rt_shared")
         return bool(v.value)

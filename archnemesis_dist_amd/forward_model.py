@@ -302,10 +302,11 @@ class CIRSradGPU:
         return f_gas
 
     # ---- single-scattering branch: host preparation of :4251-4336 for what has no g axis ---------------------------
-    def _ansfm_cirsrad_singlescatt(self, eng, taucont, TAURAY, f_gas):
+    def _ansfm_cirsrad_singlescatt(self, eng=None, taucont=None, TAURAY=None, f_gas=None):
         """calculate_single_scattering_plane_parallel_spectrum (:4251-4336): scattering angle, phase functions of the aerosols
         and of Rayleigh scattering, their opacity-weighted mean per layer, solar flux, units, emissivity and BRDF on the host;
-        OMEGA and the layer loop (calc_singlescatt_plane_spectrum :6509) on the device.  -> SPECOUT (NWAVE, NPATH)."""
+        OMEGA and the layer loop (calc_singlescatt_plane_spectrum :6509) on the device.  -> SPECOUT (NWAVE, NPATH); without an
+        engine, the prepared arguments."""
         import scipy.interpolate
         S, L, P, Sc, Su, M = self.SpectroscopyX, self.LayerX, self.PathX, self.ScatterX, self.SurfaceX, self.MeasurementX
         WAVE = np.asarray(S.WAVE, dtype=np.float64)
@@ -340,11 +341,22 @@ class CIRSradGPU:
         else:
             BRDF = np.zeros((W, len(sol)))
         NPATH = len(sol)
-        return eng.cirsrad_ck_singlescatt(
-            int(M.ISPACE), np.asarray(L.PRESS, dtype=np.float64), np.asarray(L.TEMP, dtype=np.float64), f_gas, taucont, tsca,
-            phase, np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH), np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH),
-            np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH), np.asarray(P.EMTEMP, dtype=np.float64).reshape(-1, NPATH),
-            float(Su.TSURF), emissivity, BRDF, solar, sol, emi, xfac=xfac)
+        args = dict(ISPACE=int(M.ISPACE), lp=np.array(L.PRESS, dtype=np.float64), lt=np.array(L.TEMP, dtype=np.float64), f_gas=f_gas,
+                    taucont=np.asarray(taucont, dtype=np.float64), tausca=tsca, phase=phase,
+                    NLAYIN=np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH), LAYINC=np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH),
+                    SCALE=np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH),
+                    EMTEMP=np.asarray(P.EMTEMP, dtype=np.float64).reshape(-1, NPATH), TSURF=float(Su.TSURF), emissivity=emissivity,
+                    BRDF=np.asarray(BRDF, dtype=np.float64).reshape(W, NPATH), solar=solar, SOL_ANG=sol.reshape(NPATH),
+                    EMISS_ANG=emi.reshape(NPATH), xfac=xfac)
+        if eng is None:                  # the staged Jacobian route keeps the arguments and batches the call
+            return args
+        return self._ansfm_singlescatt_call(eng, args)
+
+    @staticmethod
+    def _ansfm_singlescatt_call(eng, a):
+        return eng.cirsrad_ck_singlescatt(a["ISPACE"], a["lp"], a["lt"], a["f_gas"], a["taucont"], a["tausca"], a["phase"], a["NLAYIN"],
+                                          a["LAYINC"], a["SCALE"], a["EMTEMP"], a["TSURF"], a["emissivity"], a["BRDF"], a["solar"],
+                                          a["SOL_ANG"], a["EMISS_ANG"], xfac=a["xfac"])
 
     # ---- scattering branch: host preparation of scloud11wave (:5018-5165) for what has no g axis ----------------
     def _ansfm_cirsrad_scatter(self, eng, TAUCIA, TAUDUST, TAURAY, f_gas):

@@ -234,6 +234,8 @@ class JacobianGPU:
                     rec = self._ansfm_thermal_inputs()
                     if rec is None:
                         rec = self._ansfm_scatter_inputs()
+                    if rec is None:
+                        rec = self._ansfm_singlescatt_inputs(eng)
                     if rec is None:                  # a CIRSrad branch without a batch axis: this state runs on its own
                         rec = dict(alone=self.CIRSrad())
                     staged[k][IAV] = rec
@@ -505,6 +507,29 @@ class JacobianGPU:
                 b(r["AZI_ANG"]), b(r["solar"]), r["LOWBC"], b(r["BRDF"]), b(r["MU"]), b(r["WTMU"]), r["NF"], r["NPHI"], r["IRAY"],
                 r["IMIE"])
 
+    def _ansfm_singlescatt_inputs(self, eng):
+        """What CIRSrad's single-scattering branch hands to the engine (CIRSradGPU._ansfm_cirsrad_singlescatt), kept instead of
+        run; None when the staged state is not on that branch, or the engine has no batched entry for it."""
+        if not self._ansfm_supported(False) or not hasattr(eng, "cirsrad_ck_singlescatt_batch"):
+            return None
+        imod = int(np.unique(np.asarray(self.PathX.IMOD).astype(int))[0])
+        if self._ansfm_scatter_branch(imod) or self._ansfm_transmission_branch(imod):
+            return None
+        if not (imod & _fm.IMOD_SINGLE_SCATTERING_PLANE_PARALLEL) or (imod & _fm.IMOD_THERMAL_EMISSION):   # dispatch order :4487-4493
+            return None
+        TAUCIA, TAUDUST, TAURAY, _ = self._ansfm_continuum(False)
+        rec = self._ansfm_cirsrad_singlescatt(None, TAUCIA + TAUDUST + TAURAY, TAURAY, self._ansfm_layer_inputs())
+        rec["singlescatt"] = True
+        return rec
+
+    @staticmethod
+    def _ansfm_singlescatt_key(r):
+        """States that may share one batched single-scattering call: everything without a model axis in
+        ansfm_cirsrad_ck_singlescatt_batch"""
+        b = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
+        return ("singlescatt", r["ISPACE"], r["lp"].shape, r["LAYINC"].shape, r["NLAYIN"].tobytes(), r["LAYINC"].tobytes(),
+                b(r["emissivity"]), b(r["BRDF"]), b(r["solar"]), b(r["SOL_ANG"]), b(r["EMISS_ANG"]), b(r["xfac"]))
+
     @staticmethod
     def _ansfm_batch_key(r):
         """States that may share one batched call: same path structure and same per-wavenumber boundary vectors."""
@@ -523,6 +548,8 @@ class JacobianGPU:
                 groups.setdefault(self._ansfm_scatter_key(r), []).append(k)
             elif r.get("transmission"):
                 groups.setdefault(self._ansfm_transmission_key(r), []).append(k)
+            elif r.get("singlescatt"):
+                groups.setdefault(self._ansfm_singlescatt_key(r), []).append(k)
             else:
                 groups.setdefault(self._ansfm_batch_key(r), []).append(k)
         self._ansfm_upload_table(eng)
@@ -547,6 +574,18 @@ class JacobianGPU:
             if key[0] == "transmission":
                 spec = eng.cirsrad_ck_transmission(st("lp"), st("lt"), st("f_gas"), st("taucont"), r0["NLAYIN"], r0["LAYINC"],
                                                    st("SCALE"), xfac=r0["xfac"])
+                spec = np.asarray(spec).reshape(len(ks), W, -1)
+                if hasattr(eng, "last_layer_rows"):
+                    a, b = eng.last_layer_rows()
+                    rc += a; rt += b
+                for j, k in enumerate(ks):
+                    out[k] = spec[j]
+                continue
+            if key[0] == "singlescatt":
+                spec = eng.cirsrad_ck_singlescatt_batch(r0["ISPACE"], st("lp"), st("lt"), st("f_gas"), st("taucont"), st("tausca"),
+                                                        st("phase"), r0["NLAYIN"], r0["LAYINC"], st("SCALE"), st("EMTEMP"),
+                                                        np.array([recs[k]["TSURF"] for k in ks]), r0["emissivity"], r0["BRDF"],
+                                                        r0["solar"], r0["SOL_ANG"], r0["EMISS_ANG"], xfac=r0["xfac"])
                 spec = np.asarray(spec).reshape(len(ks), W, -1)
                 if hasattr(eng, "last_layer_rows"):
                     a, b = eng.last_layer_rows()

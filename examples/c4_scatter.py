@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Multiple scattering without the reference: CIRSrad's doubling / adding branch on a synthetic atmosphere, at the reference's
 default quadrature (5 streams, NF = 2) and at 16 streams, then the forward models of a numerical Jacobian as ONE batched call
-(model 0's doubled layers are cached, the perturbed states run the adding sweep over them).
+(model 0's doubled layers are cached, the perturbed states run the adding sweep over them), and the single-scattering branch
+for the same states in one call.
 
     python examples/c4_scatter.py            # needs an MI355X and a built libansfm.so
 """
@@ -61,6 +62,25 @@ def main():
               f"{bool(np.array_equal(spec[0], spec0))}")
         print("    spectrum [W cm-2 sr-1 (cm-1)-1]:", spec0[:3, 0], " largest response to a 5 % layer perturbation:",
               float(np.max(np.abs(spec[1:] - spec[0]) / np.abs(spec[0]))))
+    # ... and the single-scattering branch (ISCAT = 3: plane parallel, the layer-mean phase function at the scattering angle)
+    # for the same 21 states in one call
+    _, _, _, TAURAY, TAUSCAT, TAUDUST, _ = scattering_inputs(W, L, WAVE, atm["lay_temp"][0], 5)
+    NLAYIN, LAYINC, SCALE = syn.nadir_path(L, 20.0)
+    EMTEMP = atm["lay_temp"][:, LAYINC[:, 0]][:, :, None]
+    phase = np.full((1, W, L), 0.08)
+    tail = (np.ones(W), np.full((W, 1), 0.05), np.full(W, 1e-8), [30.0], [20.0])
+    one = lambda m: eng.cirsrad_ck_singlescatt(0, atm["lay_press_pa"][m], atm["lay_temp"][m], atm["amount"][m], TAUDUST + TAURAY,
+                                               TAURAY + TAUSCAT, phase, NLAYIN, LAYINC, SCALE, EMTEMP[m], -1.0, *tail)
+    one(0)
+    t = time.perf_counter(); singles = np.stack([one(m) for m in range(n)]); t1 = time.perf_counter() - t
+    args = (0, atm["lay_press_pa"], atm["lay_temp"], atm["amount"], rep(TAUDUST + TAURAY), rep(TAURAY + TAUSCAT), rep(phase), NLAYIN,
+            LAYINC, rep(SCALE), EMTEMP, np.full(n, -1.0))
+    eng.cirsrad_ck_singlescatt_batch(*args, *tail)
+    t = time.perf_counter(); spec = eng.cirsrad_ck_singlescatt_batch(*args, *tail); tb = time.perf_counter() - t
+    rows, total = eng.last_layer_rows()
+    print(f"single scattering: {n} calls {t1 * 1e3:7.1f} ms; {n} forward models in one call {tb * 1e3:7.1f} ms ({rows} of {total} gas "
+          f"opacity rows computed, paths started from state 0's records: {eng.last_rt_shared()}); equal to the separate calls: "
+          f"{bool(np.array_equal(spec, singles))}")
 
 
 if __name__ == "__main__":

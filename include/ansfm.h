@@ -179,6 +179,21 @@ int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double
                                  const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
                                  double *SPECOUT);
 
+/* The same branch for the n_models states of a numerical Jacobian (jacobian_nemesis takes the numerical route whenever ISCAT is
+ * not thermal emission, ForwardModel_0.py:2251-2252).  Arrays that depend on the state carry a leading model axis:
+ * lay_press_pa / lay_temp [n][L], amount [n][S][L], taucont / tausca [n][W][L], phase [n][P][W][L], SCALE / EMTEMP
+ * [n][LIMAX][P], TSURF [n]; the paths, EMISSIVITY, BRDF, SOLFLUX, the angles and xfac are shared -> SPECOUT [n][W][P].
+ * Only the distinct (model, layer) gas opacities are computed (ansfm_set_layer_dedup, ansfm_last_layer_rows), and with at
+ * least 4 states every state starts each path from the record state 0 left after the last layer whose opacity row, continuum,
+ * scattering opacity, phase function of that path, SCALE and EMTEMP are all state 0's (ansfm_last_rt_shared).  The same
+ * numbers as n_models calls of ansfm_cirsrad_ck_singlescatt, bit for bit, with and without the sharing.  n_models * P <= 65535. */
+int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, const double *taucont, const double *tausca,
+                                       const double *phase, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                       const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                       const double *BRDF, const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG,
+                                       const double *xfac, double *SPECOUT);
+
 /* ---- fused seam: CIRSrad, ILBL=K_TABLES, IMOD=THERMAL_EMISSION ------------------------------
  * ForwardModel_0.CIRSrad (ForwardModel_0.py:4376-4511) =
  *   calculate_gaseous_line_opacity (:3850-3877: calc_k -> k_overlap)
@@ -540,7 +555,7 @@ int ansfm_calc_tau_dust(ansfm_ctx *ctx, int W, const double *WAVEC, int NWS, con
 int ansfm_set_layer_dedup(ansfm_ctx *ctx, int enable);
 int ansfm_last_layer_rows(const ansfm_ctx *ctx, int *rows_computed, int *rows_total);
 
-/* *shared = 1 when the last thermal-emission batch started the paths of its states from the records state 0 left behind
+/* *shared = 1 when the last thermal-emission or single-scattering batch started the paths of its states from the records state 0 left behind
  * (a de-duplicated batch of at least 4 states: every state shares the top of each path with state 0 up to the first layer
  * whose opacity row, continuum, SCALE or EMTEMP differs; bit-identical; ANSFM_RT_PREFIX=0 switches it off). */
 int ansfm_last_rt_shared(const ansfm_ctx *ctx, int *shared);

@@ -18,7 +18,7 @@ def timeit(f, n=3):
 
 
 def main():
-    only = sys.argv[1] if len(sys.argv) > 1 else None       # "grad" | "ms" | "lbl" | "layer"
+    only = sys.argv[1] if len(sys.argv) > 1 else None       # "grad" | "ms" | "lbl" | "layer" | "ss"
     eng = pkg.AnsfmEngine(0)
     out = {}
     rng = np.random.default_rng(0)
@@ -36,6 +36,8 @@ def main():
         bench_maps(eng, out, rng)
     if only in (None, "next"):
         bench_next(eng, out, rng)
+    if only == "ss":                                        # 10 GB of host arrays: on request only
+        bench_ss(eng, out, rng)
     print(json.dumps(out, indent=1))
 
 
@@ -73,6 +75,79 @@ def bench_next(eng, out, rng):
     tk = timeit(lambda: eng.kdist_bins(w, k, cen - half, cen + half, g), 2)
     t0 = time.perf_counter(); orc.kdist_bins(w, k, cen - half, cen + half, g); tko = time.perf_counter() - t0
     out["kdist_200bins_2.5e4pts"] = {"gpu_wall_s_host_arrays": tk, "numpy_oracle_s": tko}
+
+
+def bench_ss(eng, out, rng, runs=5):
+    """Numerical Jacobian of a single-scattering configuration (ISCAT = 3) at C2 size: 201 forward models (T and ln VMR of one
+    absorber at 100 levels through Curtis-Godson layer_average, as the c4 / grad workloads build them), the synthetic scattering
+    inputs of tests/test_gpu_parity.py::_singlescatt_vs_oracle at 1e4 wavenumbers x 100 layers.  (a) one
+    cirsrad_ck_singlescatt call per state against (b) ONE cirsrad_ck_singlescatt_batch call; host arrays in / out, medians of
+    `runs` rounds after a warm-up, the order of (a) and (b) swapped from round to round."""
+    import torch
+    from archnemesis_dist_amd.jacobian import perturbed_states
+    from archnemesis_dist_amd.profile_state import ContinuousProfileState, BatchedCKThermalModel
+    from bench import torch_ktable
+    W, G, S, L, NP, NT = 10000, 20, 8, 100, 20, 15
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    PRESS, TEMP, K = torch_ktable(torch, torch.device("cuda", 0), W, G, NP, NT, S, seed=20260704)
+    WAVE = 200.0 + 0.1 * np.arange(W)
+    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+    pr = syn.synth_profiles(100, S + 2, seed=11)
+    st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T", ("VMR", 2)])
+    model = BatchedCKThermalModel(eng, st, pr["RADIUS"], pr["ID"], pr["ISO"], list(range(2, S + 2)),
+                                  layering_args=dict(NLAY=L, LAYINT=1, NINT=101))
+    X = perturbed_states(st.XN, 0.05 * st.XN).T
+    lay = model.layers(X)
+    lp, lt, am = (np.ascontiguousarray(lay[k]) for k in ("PRESS", "TEMP", "amount"))
+    n = X.shape[0]
+    TAURAY = 10.0 ** rng.uniform(-4, -2, (W, L)); TAUSCAT = 10.0 ** rng.uniform(-3, -1, (W, L)); TAUSCAT[:, 4] = 0.0
+    cont = 10.0 ** rng.uniform(-5, -3, (W, L)) + 1.2 * TAUSCAT + TAURAY
+    sca = TAURAY + TAUSCAT
+    phase = 10.0 ** rng.uniform(-1.5, 0.3, (1, W, L))
+    NLAYIN, LAYINC, SCALE = syn.nadir_path(L, 20.0)
+    EMTEMP = lt[:, LAYINC[:, 0]][:, :, None]
+    EMIS = rng.uniform(0.7, 1.0, W); BRDF = rng.uniform(0.0, 0.15, (W, 1)); SOLF = 10.0 ** rng.uniform(-8, -7, W)
+    tail = (EMIS, BRDF, SOLF, [30.0], [20.0])
+    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a[None], (n,) + a.shape))
+
+    def separate():
+        return np.stack([eng.cirsrad_ck_singlescatt(0, lp[m], lt[m], am[m], cont, sca, phase, NLAYIN, LAYINC, SCALE, EMTEMP[m], -1.0, *tail)
+                         for m in range(n)])
+    res = {"what": "numerical Jacobian, single scattering (ISCAT = 3) at C2 size: %d forward models, W=1e4, L=100, S=8, G=20, one "
+                   "path; host arrays in / out" % n, "forward_models": n, "runs": runs}
+    batched = None
+    if hasattr(eng, "cirsrad_ck_singlescatt_batch"):
+        contn, scan, phasen, scalen = rep(cont), rep(sca), rep(phase), rep(SCALE)
+        tsurf = np.full(n, -1.0)
+        batched = lambda: eng.cirsrad_ck_singlescatt_batch(0, lp, lt, am, contn, scan, phasen, NLAYIN, LAYINC, scalen, EMTEMP, tsurf, *tail)
+    ref = separate()                                            # warm-up of both
+    ta, tb, parts = [], [], []
+    if batched:
+        res["bit_identical_to_separate_calls"] = bool(np.array_equal(batched(), ref))
+    for r in range(runs):
+        for which in (("a", "b") if r % 2 == 0 else ("b", "a")):
+            if which == "b" and not batched:
+                continue
+            t = time.perf_counter(); (separate if which == "a" else batched)(); dt = time.perf_counter() - t
+            (ta if which == "a" else tb).append(dt)
+            if which == "b":
+                parts.append(eng.last_kernel_ms())
+    res["separate_calls_wall_s"] = float(np.median(ta)); res["separate_calls_wall_s_all"] = ta
+    if batched:
+        res["batch_wall_s"] = float(np.median(tb)); res["batch_wall_s_all"] = tb
+        res["speedup"] = res["separate_calls_wall_s"] / res["batch_wall_s"]
+        res["batch_gas_opacity_kernel_ms"] = float(np.median([k["overlap_ms"] for k in parts]))
+        res["batch_rt_kernel_ms"] = float(np.median([k["rt_ms"] for k in parts]))      # flags, state 0's pass, the other states
+        res["gas_opacity_rows"] = list(eng.last_layer_rows()); res["rt_shared"] = bool(eng.last_rt_shared())
+        nbytes = contn.nbytes + scan.nbytes + phasen.nbytes
+        th = []
+        for _ in range(3):                                      # what the upload of one per-model array costs, pageable host memory
+            torch.cuda.synchronize(); t = time.perf_counter(); d = torch.from_numpy(contn).to("cuda:0"); torch.cuda.synchronize()
+            th.append(time.perf_counter() - t); del d
+        res["per_model_arrays_GB"] = nbytes / 1e9
+        res["h2d_pageable_GB_per_s"] = contn.nbytes / 1e9 / float(np.median(th))
+        res["upload_estimate_s"] = nbytes / 1e9 / res["h2d_pageable_GB_per_s"]
+    out["singlescatt_jacobian_C2"] = res
 
 
 def bench_maps(eng, out, rng):
