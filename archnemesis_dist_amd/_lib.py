@@ -30,7 +30,7 @@ EXPORTS = [
     "ansfm_cirsrad_ck_singlescatt", "ansfm_cirsrad_ck_scatter_batch", "ansfm_last_scatter_cache",
     "ansfm_layer_average_dev", "ansfm_calc_tau_rayleigh_batch_dev_in", "ansfm_last_rt_shared",
     "ansfm_cirsrad_ck_thermal_ray_dev", "ansfm_last_scatter_windows", "ansfm_cirsrad_ck_scatter_batch_slice",
-    "ansfm_cirsrad_ck_singlescatt_batch",
+    "ansfm_cirsrad_ck_singlescatt_batch", "ansfm_cirsrad_ck_scatter_batch_rows",
 ]
 
 _lib = None
@@ -149,6 +149,9 @@ def load():
                                                    vp, ci, vp, vp, ci, ci, ci, ci, vp, vp]
     # ... + (W_full, w_begin)
     lib.ansfm_cirsrad_ck_scatter_batch_slice.argtypes = lib.ansfm_cirsrad_ck_scatter_batch.argtypes + [ci, ci]
+    # the slice entry's list with (R, cont_row) in front of the four opacities, which are rows then
+    lib.ansfm_cirsrad_ck_scatter_batch_rows.argtypes = ([vp, ci, ci, ci, vp, vp, vp, ci, vp]
+                                                        + lib.ansfm_cirsrad_ck_scatter_batch_slice.argtypes[7:])
     lib.ansfm_last_scatter_cache.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ansfm_last_scatter_windows.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ansfm_upload_lbltable.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp]

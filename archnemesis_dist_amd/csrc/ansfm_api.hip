@@ -84,6 +84,7 @@ struct ansfm_ctx {
     int map_dims[4] = {0, 0, 0, 0};     // W, NPAR, NPRO, P of map_out
     DevBuf gscratch, perm, dkbuf, trold_ws, dspec_i, dcont_t, tmp_in2, tmp_out2, lbl_li;
     DevBuf ms_taus, ms_omegas, ms_bnu;   // scattering branch of CIRSrad: TAUTOT / OMEGA (W,G,L) and BB (W,L) in HBM
+    DevBuf ms_tauray_l, ms_lfrac_l;      // the continuum by rows: TAURAY / aerosol fractions of a launch's models (the model-by-model route: one model's dense arrays)
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
     long ms_windows = 0, ms_window_w = 0;          // spectral windows of phase matrices / Hansen factors of the last scattering call, their size
@@ -2277,7 +2278,13 @@ struct MsCall {
     int nf, nphi, iray, imie; const double *xfac;
     double *SPECOUT, *SPEC_G;
     int W_full, w_begin;
+    // the continuum once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows): cont_row [n][L] into R rows; taucia / taudust /
+    // tauray / tauscat are then [R][W] and lfrac [R][ncont][W].  cont_row = nullptr: the dense arrays
+    int R; const int32_t *cont_row;
 };
+
+// one model's continuum already on the device, [W][L] / [W][ncont][L] (null = zeros): cirsrad_ck_scatter_impl stages none then
+struct MsDevCont { const double *cia, *dust, *ray, *sca, *lf; };
 
 static int ms_check(ansfm_ctx *ctx, const MsCall &c, const char *fn)
 {
@@ -2658,8 +2665,8 @@ int ansfm_scloud11wave_core(ansfm_ctx *ctx, int ncont, int nwave, int nth, const
     return ANSFM_OK;
 }
 
-// one model; reuse_walk: ms_single's
-static int cirsrad_ck_scatter_impl(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, bool reuse_walk)
+// one model; reuse_walk: ms_single's; dc: its continuum on the device instead of c's host arrays
+static int cirsrad_ck_scatter_impl(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, bool reuse_walk, const MsDevCont *dc = nullptr)
 {
     int rc = ms_check(ctx, c, "cirsrad_ck_scatter");
     if (rc) return rc;
@@ -2671,11 +2678,13 @@ static int cirsrad_ck_scatter_impl(ansfm_ctx *ctx, const MsCall &c, const MsKnob
     const size_t D = sizeof(double), WL = (size_t)W * L;
     Stager st{ctx};
     const double *press = st.up(c.lay_press_pa, L), *temp = st.up(c.lay_temp, L), *am = st.up(c.amount, (size_t)S * L),
-                 *cia = st.up(c.taucia, WL), *dust = st.up(c.taudust, WL), *ray = st.up(c.tauray, WL), *sca = st.up(c.tauscat, WL),
-                 *phas = st.up(c.phasarr, (size_t)c.ncont * W * 2 * c.nth), *lf = st.up(c.lfrac, WL * c.ncont),
+                 *cia = st.up(dc ? nullptr : c.taucia, WL), *dust = st.up(dc ? nullptr : c.taudust, WL),
+                 *ray = st.up(dc ? nullptr : c.tauray, WL), *sca = st.up(dc ? nullptr : c.tauscat, WL),
+                 *phas = st.up(c.phasarr, (size_t)c.ncont * W * 2 * c.nth), *lf = st.up(dc ? nullptr : c.lfrac, WL * c.ncont),
                  *rg = st.up(c.radg, (size_t)W * c.nmu), *sol = st.up(c.solar, W),
                  *brdf = st.up(c.brdf_matrix, (size_t)W * c.nmu * c.nmu * (c.nf + 1)), *xf = st.up(c.xfac, W);
     if ((rc = st.rc)) return rc;
+    if (dc) { cia = dc->cia; dust = dc->dust; ray = dc->ray; sca = dc->sca; lf = dc->lf; }
     // ---- vertical gas opacities: calc_k + k_overlap (:3855-3874), as in the thermal branch --------------------------
     HIPCHK(ctx->ms_taus.reserve(WL * G * D));
     HIPCHK(ctx->ms_omegas.reserve(WL * G * D));
@@ -2728,6 +2737,15 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     const int ncont = c.ncont, ngeom = c.ngeom, nmu = c.nmu, nf = c.nf, w_begin = c.w_begin;
     const bool sliced = c.W_full != W;
     const size_t D = sizeof(double), WL = (size_t)W * L;
+    const bool by_rows = c.cont_row != nullptr;
+    const size_t RW = by_rows ? (size_t)c.R * W : 0;
+    if (by_rows) {                                              // before anything is launched
+        if (c.R <= 0) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: R must be positive");
+        for (size_t i = 0; i < (size_t)n_models * L; ++i)
+            if (c.cont_row[i] < 0 || c.cont_row[i] >= c.R)
+                FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: cont_row[" + std::to_string(i / L) + "][" + std::to_string(i % L) +
+                                            "] = " + std::to_string(c.cont_row[i]) + " is outside [0, R = " + std::to_string(c.R) + ")");
+    }
     ctx->ms_cache_hits = 0; ctx->ms_cache_layers = (long)n_models * L;
     const bool use_cache = n_models > 1 && ctx->dedup && kn.layer_cache;      // any stream count
     if (!use_cache && sliced)
@@ -2735,14 +2753,41 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     if (!use_cache) {
         // a single model, or de-duplication switched off (ansfm_set_layer_dedup): model by model; m > 0: same phase functions,
         // quadrature, orders -- model 0's walk stands
+        // by rows: the rows go up once, behind the staging slots of the single-model entry; a model's dense arrays are formed
+        // from them on the device, one model at a time in one buffer
+        HIPCHK(hipSetDevice(ctx->device));
+        Stager sr{ctx, 14};
+        const int32_t *d_crow = by_rows ? sr.up(c.cont_row, (size_t)n_models * L) : nullptr;
+        const double *rsrc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (by_rows) {
+            rsrc[0] = sr.up(c.taucia, RW); rsrc[1] = sr.up(c.taudust, RW); rsrc[2] = sr.up(c.tauray, RW); rsrc[3] = sr.up(c.tauscat, RW);
+            rsrc[4] = sr.up(c.lfrac, RW * ncont);
+            if ((rc = sr.rc)) return rc;
+            HIPCHK(ctx->ms_tauray_l.reserve((4 + (size_t)ncont) * WL * D));
+        }
         for (int m = 0; m < n_models; ++m) {
             const size_t mm = m;
             MsCall cm = c;
             cm.n_models = 1;
             cm.lay_press_pa += mm * L; cm.lay_temp += mm * L; cm.amount += mm * S * L;
+            cm.radg += mm * W * nmu; cm.SPECOUT += mm * W * ngeom;
+            if (by_rows) {
+                const double *dense[5];
+                for (int a = 0; a < 5; ++a) {
+                    const int X = a < 4 ? 1 : ncont;
+                    double *dst = ctx->ms_tauray_l.as<double>() + (size_t)a * WL;
+                    dense[a] = (rsrc[a] && X > 0) ? dst : nullptr;
+                    if (dense[a])
+                        hipLaunchKernelGGL(k_ms_rows_expand, dim3(nblk((size_t)W, 128), (unsigned)L, (unsigned)X), dim3(128), 0, ctx->stream,
+                                           W, X, L, d_crow + mm * L, rsrc[a], dst);
+                }
+                HIPCHK(hipGetLastError());
+                const MsDevCont dc{dense[0], dense[1], dense[2], dense[3], dense[4]};
+                if ((rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0, &dc))) return rc;
+                continue;
+            }
             for (const double **a : {&cm.taucia, &cm.taudust, &cm.tauray, &cm.tauscat}) if (*a) *a += mm * WL;
             if (cm.lfrac) cm.lfrac += mm * WL * ncont;
-            cm.radg += mm * W * nmu; cm.SPECOUT += mm * W * ngeom;
             if ((rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0))) return rc;
         }
         ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = n_models * L; ctx->last_dedup = 0;
@@ -2753,15 +2798,17 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     MsRoute r;
     if ((rc = ms_setup(ctx, p, c, W, G, L, kn, r))) return rc;
     const size_t nl = (size_t)n_models * L;
+    const size_t CN = by_rows ? RW : n_models * WL;            // elements of a continuum array: rows, or dense
     Stager st{ctx};
     const double *press = st.up(c.lay_press_pa, nl), *temp = st.up(c.lay_temp, nl), *am = st.up(c.amount, nl * S),
-                 *cia = st.up(c.taucia, n_models * WL), *dust = st.up(c.taudust, n_models * WL), *ray = st.up(c.tauray, n_models * WL),
-                 *sca = st.up(c.tauscat, n_models * WL), *phas = st.up(c.phasarr, (size_t)ncont * c.W_full * 2 * c.nth),
-                 *lf = st.up(c.lfrac, n_models * WL * ncont), *rg = st.up(c.radg, (size_t)n_models * W * nmu), *sol = st.up(c.solar, W),
+                 *cia = st.up(c.taucia, CN), *dust = st.up(c.taudust, CN), *ray = st.up(c.tauray, CN),
+                 *sca = st.up(c.tauscat, CN), *phas = st.up(c.phasarr, (size_t)ncont * c.W_full * 2 * c.nth),
+                 *lf = st.up(c.lfrac, CN * ncont), *rg = st.up(c.radg, (size_t)n_models * W * nmu), *sol = st.up(c.solar, W),
                  *brdf = st.up(c.brdf_matrix, (size_t)W * nmu * nmu * (nf + 1)), *xf = st.up(c.xfac, W);
+    const int32_t *d_crow = st.up(c.cont_row, by_rows ? nl : 0);
     if ((rc = st.rc)) return rc;
     const double *d_tauray = ray;                               // no TAURAY: every model reads the same zeros
-    if ((rc = ms_zero_tauray(ctx, WL, &d_tauray))) return rc;
+    if (!by_rows && (rc = ms_zero_tauray(ctx, WL, &d_tauray))) return rc;     // (by rows: the optics stage writes the slab's copy)
     // ---- vertical gas opacities of the distinct (model, layer) rows: calc_k + k_overlap ---------------------------------
     DedupRows k;
     if ((rc = dedup_rows(ctx, n_models, L, press, temp, am, nullptr, nullptr, &k)) || (rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount)))
@@ -2770,12 +2817,16 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     // ---- which layers equal model 0's in EVERY input --------------------------------------------------------------------
     HIPCHK(ctx->ms_same.reserve(nl));
     unsigned char *same = ctx->ms_same.as<unsigned char>();
-    hipLaunchKernelGGL(k_ms_same_init, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), same);
+    if (by_rows)                                                // from the two index maps: no data is compared
+        hipLaunchKernelGGL(k_ms_same_index, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), d_crow,
+                           same);
+    else
+        hipLaunchKernelGGL(k_ms_same_init, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), same);
     for (const double *col : {cia, dust, ray, sca})
-        if (col)
+        if (col && !by_rows)
             hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W, 128)), dim3(128), 0, ctx->stream, n_models, W,
                                1, L, col, same);
-    if (lf && ncont > 0)
+    if (lf && ncont > 0 && !by_rows)
         hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W * ncont, 128)), dim3(128), 0, ctx->stream,
                            n_models, W, ncont, L, lf, same);
     HIPCHK(hipGetLastError());
@@ -2881,6 +2932,11 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     HIPCHK(ctx->ms_taus.reserve(opt_models * Ws * G * L * D));
     HIPCHK(ctx->ms_omegas.reserve(opt_models * Ws * G * L * D));
     HIPCHK(ctx->ms_bnu.reserve(opt_models * Ws * L * D));
+    if (by_rows) {
+        HIPCHK(ctx->ms_tauray_l.reserve(opt_models * Ws * L * D));
+        HIPCHK(ctx->ms_lfrac_l.reserve(std::max<size_t>(opt_models * Ws * ncont * L * D, 8)));
+        p.tauray = ctx->ms_tauray_l.as<double>(); p.lfrac = ctx->ms_lfrac_l.as<double>(); p.cont_local = 1;
+    }
     if (!m16) {                                                 // the orders, for k_ms_fourier
         p.st_drad = (size_t)W * G * (nf + 1) * ngeom;
         HIPCHK(ctx->tmp_in2.reserve((size_t)n_models * p.st_drad * D));
@@ -2896,6 +2952,14 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     p.model_ids = ctx->ms_lstart.as<int>() + n_models;
     p.st_wl = ray ? WL : 0; p.st_wcl = (size_t)W * ncont * L; p.st_wm = (size_t)W * nmu_k; p.st_rad = (size_t)ngeom * G * W;
     p.ig0 = 0; p.ng_launch = G;
+    MsOpticsRowsParams orw;
+    memset(&orw, 0, sizeof orw);
+    orw.taugas = ctx->tau.as<double>(); orw.slot = ctx->dd_slot.as<int32_t>(); orw.cont_row = d_crow;
+    orw.taucia = cia; orw.taudust = dust; orw.tauray = ray; orw.tauscat = sca; orw.lfrac = lf;
+    orw.wave = ctx->d_wave.as<double>(); orw.lay_temp = temp;
+    orw.taus = ctx->ms_taus.as<double>(); orw.omegas = ctx->ms_omegas.as<double>(); orw.bnu = ctx->ms_bnu.as<double>();
+    orw.tauray_l = ctx->ms_tauray_l.as<double>(); orw.lfrac_l = ctx->ms_lfrac_l.as<double>();
+    orw.W = W; orw.Wpad = Wpad; orw.G = G; orw.L = L; orw.ncont = lf ? ncont : 0; orw.ispace = c.ISPACE;
     MsOpticsBatchParams o;
     memset(&o, 0, sizeof o);
     o.taugas = ctx->tau.as<double>(); o.slot = ctx->dd_slot.as<int32_t>();
@@ -2903,6 +2967,17 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     o.wave = ctx->d_wave.as<double>(); o.lay_temp = temp;
     o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
     o.W = W; o.Wpad = Wpad; o.G = G; o.L = L; o.ispace = c.ISPACE;
+    // TAUTOT, OMEGA, BB (by rows: and the slab's TAURAY / fractions) of the models [m0, m0 + nm) of the launch order on the slab
+    auto optics = [&](int w0, int wc, int m0, int nm, const int *ids) {
+        const dim3 grid(nblk((size_t)wc, 128), (unsigned)L, (unsigned)nm);
+        if (by_rows) {
+            orw.w0 = w0; orw.wcount = wc; orw.m0 = m0; orw.nm = nm; orw.model_ids = ids;
+            hipLaunchKernelGGL(k_ms_optics_rows, grid, dim3(128), 0, ctx->stream, orw);
+        } else {
+            o.w0 = w0; o.wcount = wc; o.m0 = m0; o.nm = nm; o.model_ids = ids;
+            hipLaunchKernelGGL(k_ms_optics_batch, grid, dim3(128), 0, ctx->stream, o);
+        }
+    };
     for (long w0 = 0; w0 < W; w0 += Ws) {
         const int wc = (int)std::min<long>(Ws, W - w0);
         if (win) {
@@ -2919,17 +2994,15 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
             HIPCHK(hipGetLastError());
         }
         p.w0 = (int)w0; p.wcount = wc;
-        o.w0 = (int)w0; o.wcount = wc;
+        if (by_rows) { p.st_wl = (size_t)wc * L; p.st_wcl = (size_t)wc * ncont * L; }       // between launch positions
         // model 0: the ordinary chain, which also fills the cache
-        o.m0 = 0; o.nm = 1; o.model_ids = nullptr;
-        hipLaunchKernelGGL(k_ms_optics_batch, dim3(nblk((size_t)wc, 128), (unsigned)L, 1), dim3(128), 0, ctx->stream, o);
+        optics((int)w0, wc, 0, 1, nullptr);
         p.m0 = 0; p.n_launch = 1;
         if ((rc = ms_launch_chain<1>(ctx, r.chain, ctx->stream, p))) return rc;
         // models 1 .. n-1 in chunks: the adding sweep over cached layers, changed layers computed in place
         for (int m0 = 1; m0 < n_models; m0 += mchunk) {
             const int nm = std::min(mchunk, n_models - m0);
-            o.m0 = m0; o.nm = nm; o.model_ids = p.model_ids;
-            hipLaunchKernelGGL(k_ms_optics_batch, dim3(nblk((size_t)wc, 128), (unsigned)L, (unsigned)nm), dim3(128), 0, ctx->stream, o);
+            optics((int)w0, wc, m0, nm, p.model_ids);
             p.m0 = m0; p.n_launch = nm;
             if ((rc = ms_launch_chain<2>(ctx, r.chain, ctx->stream, p))) return rc;
         }
@@ -2968,6 +3041,25 @@ int ansfm_cirsrad_ck_scatter_batch_slice(ansfm_ctx *ctx, int ISPACE, int n_model
     const MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat, ncont, nth, phasarr,
                    lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray,
                    imie, xfac, SPECOUT, nullptr, W_full, w_begin};
+    return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
+}
+
+int ansfm_cirsrad_ck_scatter_batch_rows(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                        const double *lay_temp, const double *amount, int R, const int32_t *cont_row,
+                                        const double *taucia_rows, const double *taudust_rows, const double *tauray_rows,
+                                        const double *tauscat_rows, int ncont, int nth, const double *phasarr,
+                                        const double *lfrac_rows, const double *radg, int ngeom, const double *sol_angs,
+                                        const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                        const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                        int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter_batch_rows: upload a k-table first");
+    if (!cont_row || w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: no cont_row, the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
+    const MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia_rows, taudust_rows, tauray_rows, tauscat_rows, ncont,
+                   nth, phasarr, lfrac_rows, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf,
+                   nphi, iray, imie, xfac, SPECOUT, nullptr, W_full, w_begin, R, cont_row};
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 

@@ -67,6 +67,10 @@ struct MsParams {
     int npre;
     size_t st_wl, st_wcl, st_wm, st_rad;   // strides between models: tauray [W][L], lfrac [W][ncont][L], radg [W][nmu], rad
     size_t st_drad;                        // ... and drad (k_ms_chain_lane<N, CACHE> leaves the orders to k_ms_fourier)
+    // The continuum by rows (ansfm_cirsrad_ck_scatter_batch_rows): tauray / lfrac are the slab's copies k_ms_optics_rows wrote
+    // beside taus / omegas / bnu, [model of the launch][wcount][..] relative to w0, st_wl / st_wcl the strides between launch
+    // positions.  0: the batch's input arrays, by model over the whole axis.
+    int cont_local;
     // 7 .. 15 streams on the 16-stream kernels: nmu = 16, nmu_real = the quadrature's size (0 = nmu).  mu / wtmu beyond it are
     // 1 / 0, the phase matrices, the surface operator and the boundary radiance zero there: every operator is block diagonal with
     // the quadrature's block in front and a block that couples to nothing behind it
@@ -491,8 +495,9 @@ __global__ __launch_bounds__(64) void k_ms_chain(MsParams p)
     // taus / omegas / bnu: [model of the launch][wavenumber of the slab]; the other per-wavenumber arrays keep the whole axis
     const size_t wrow = (size_t)ml * p.wcount + wl;
     const double *taus_w = p.taus + (wrow * p.ng + ig) * p.nlay, *omegas_w = p.omegas + (wrow * p.ng + ig) * p.nlay;
-    const double *bnu_w = p.bnu + wrow * p.nlay, *tauray_w = p.tauray + (size_t)mg * p.st_wl + (size_t)widx * p.nlay;
-    const double *lfrac_m = p.lfrac + (size_t)mg * p.st_wcl;
+    const int mc = p.cont_local ? ml : mg, wcn = p.cont_local ? wl : widx;     // tauray / lfrac: by model, or by launch position
+    const double *bnu_w = p.bnu + wrow * p.nlay, *tauray_w = p.tauray + (size_t)mc * p.st_wl + (size_t)wcn * p.nlay;
+    const double *lfrac_m = p.lfrac + (size_t)mc * p.st_wcl;
     const double *radg_m = p.radg + (size_t)mg * p.st_wm;
     const size_t centry = (size_t)(2 * nn + n);
     // LDS carve-up
@@ -564,7 +569,7 @@ __global__ __launch_bounds__(64) void k_ms_chain(MsParams p)
                 double a = (p.iray > 0) ? fr * (PPL[(size_t)p.ncont * nn + e] * FC[(size_t)p.ncont * nn + e]) : 0.0;
                 double b = (p.iray > 0) ? fr * PMI[(size_t)p.ncont * nn + e] : 0.0;
                 for (int c = 0; c < p.ncont; ++c) {
-                    const double f = lfrac_m[((size_t)widx * p.ncont + c) * p.nlay + k];
+                    const double f = lfrac_m[((size_t)wcn * p.ncont + c) * p.nlay + k];
                     a += fs * (PPL[(size_t)c * nn + e] * FC[(size_t)c * nn + e]) * f;
                     b += fs * PMI[(size_t)c * nn + e] * f;
                 }
@@ -982,8 +987,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     // the layer's scalars are fetched one layer ahead
     const size_t wrow = (size_t)ml * p.wcount + wl;       // taus / omegas / bnu: [model of the launch][wavenumber of the slab]
     const double *taus_w = p.taus + (wrow * p.ng + ig) * p.nlay, *omegas_w = p.omegas + (wrow * p.ng + ig) * p.nlay;
-    const double *bnu_w = p.bnu + wrow * p.nlay, *tauray_w = p.tauray + (size_t)mg * p.st_wl + (size_t)widx * p.nlay;
-    const double *lfrac_m = p.lfrac + (size_t)mg * p.st_wcl;
+    const int mc = p.cont_local ? ml : mg, wcn = p.cont_local ? wl : widx;     // tauray / lfrac: by model, or by launch position
+    const double *bnu_w = p.bnu + wrow * p.nlay, *tauray_w = p.tauray + (size_t)mc * p.st_wl + (size_t)wcn * p.nlay;
+    const double *lfrac_m = p.lfrac + (size_t)mc * p.st_wcl;
     // CACHE = 2: every layer of the sweep below lstart is model 0's, and so is the stack they add up to (the lower boundary
     // included: the host leaves lstart at 0 when the boundary radiance differs) -- take it from model 0's pass and start there
     int lbeg = 0;
@@ -1002,8 +1008,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
             defined = true;
         }
     }
+    // (a model that shares every layer with model 0 starts at lbeg = nlay when nlay is a multiple of kMsPrefixStep: no layer is
+    // left, and kfirst would be one element outside the rows)
     const int kfirst = lookup ? p.nlay - 1 - lbeg : lbeg;
-    double n_taut = taus_w[kfirst], n_bc = bnu_w[kfirst], n_omega = omegas_w[kfirst], n_taur = tauray_w[kfirst];
+    double n_taut = 0.0, n_bc = 0.0, n_omega = 0.0, n_taur = 0.0;
+    if (lbeg < p.nlay) { n_taut = taus_w[kfirst]; n_bc = bnu_w[kfirst]; n_omega = omegas_w[kfirst]; n_taur = tauray_w[kfirst]; }
     for (int l = lbeg; l < p.nlay; ++l) {
         const int k = lookup ? p.nlay - 1 - l : l;  // look-down: bottom layer first (:842-845)
         const double taut = n_taut, bc = n_bc;
@@ -1062,7 +1071,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
                     a = (p.iray > 0) ? fr * phl[((p.ncont * 2 + 0) * 4 + r) * 64 + lane] : 0.0;
                     b = (p.iray > 0) ? fr * phl[((p.ncont * 2 + 1) * 4 + r) * 64 + lane] : 0.0;
                     for (int cc = 0; cc < p.ncont; ++cc) {
-                        const double f = lfrac_m[((size_t)widx * p.ncont + cc) * p.nlay + k];
+                        const double f = lfrac_m[((size_t)wcn * p.ncont + cc) * p.nlay + k];
                         a += fs * phl[((cc * 2 + 0) * 4 + r) * 64 + lane] * f;
                         b += fs * phl[((cc * 2 + 1) * 4 + r) * 64 + lane] * f;
                     }
@@ -1075,7 +1084,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
                     a = (p.iray > 0) ? fr * (at(PPL, p.ncont) * at(FC, p.ncont)) : 0.0;
                     b = (p.iray > 0) ? fr * at(PMI, p.ncont) : 0.0;
                     for (int cc = 0; cc < p.ncont; ++cc) {
-                        const double f = lfrac_m[((size_t)widx * p.ncont + cc) * p.nlay + k];
+                        const double f = lfrac_m[((size_t)wcn * p.ncont + cc) * p.nlay + k];
                         a += fs * (at(PPL, cc) * at(FC, cc)) * f;
                         b += fs * at(PMI, cc) * f;
                     }
@@ -1400,6 +1409,72 @@ __global__ void k_ms_same_cols(int n_models, int W, int X, int L, const double *
     const double *a = arr + (m * per + r) * L, *b = arr + r * L;
     for (int l = 0; l < L; ++l)
         if (__double_as_longlong(a[l]) != __double_as_longlong(b[l])) same[m * L + l] = 0;
+}
+
+// The continuum handed over once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows): rows [R][W] of TAUCIA / TAUDUST /
+// TAURAY / TAUSCAT and [R][ncont][W] of the aerosol fractions, wavenumber fastest, and cont_row [n][L], the row of layer l of
+// model m.  k_ms_optics_batch's job from them -- the same arithmetic per (wavenumber, g, layer) -- and the slab's copies of
+// TAURAY and the fractions the chain kernels read (MsParams::cont_local).  One thread per wavenumber of the slab: the row
+// index is uniform per (model, layer), so a wavefront reads 64 consecutive doubles of every row.
+struct MsOpticsRowsParams {
+    const double *taugas;       // [rows][G][Wpad]
+    const int32_t *slot;        // [n][L]
+    const int32_t *cont_row;    // [n][L]
+    const double *taucia, *taudust, *tauray, *tauscat;   // [R][W] or null
+    const double *lfrac;        // [R][ncont][W] (ncont > 0)
+    const double *wave;         // [W]
+    const double *lay_temp;     // [n][L]
+    double *taus, *omegas;      // [nm][wcount][G][L]
+    double *bnu, *tauray_l;     // [nm][wcount][L]
+    double *lfrac_l;            // [nm][wcount][ncont][L]
+    const int *model_ids;       // launch position -> model (null: position m0 + ml is the model)
+    int W, Wpad, G, L, ncont, ispace, w0, wcount, m0, nm;
+};
+__global__ __launch_bounds__(128) void k_ms_optics_rows(MsOpticsRowsParams p)
+{
+    const int wl = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y, ml = blockIdx.z;
+    if (wl >= p.wcount) return;
+    const int w = p.w0 + wl, m = p.model_ids ? p.model_ids[p.m0 + ml] : p.m0 + ml;
+    const size_t ml_l = (size_t)m * p.L + l;
+    const size_t cr = (size_t)p.cont_row[ml_l];
+    const size_t in = cr * p.W + w;
+    const double cia = p.taucia ? p.taucia[in] : 0.0, dust = p.taudust ? p.taudust[in] : 0.0;
+    const double ray = p.tauray ? p.tauray[in] : 0.0, sca = p.tauscat ? p.tauscat[in] : 0.0;
+    const size_t row = (size_t)p.slot[ml_l];
+    const size_t wrow = (size_t)ml * p.wcount + wl;
+    for (int g = 0; g < p.G; ++g) {
+        const double tt = ((p.taugas[(row * p.G + g) * p.Wpad + w] + cia) + dust) + ray;             // the sum order of :3989
+        const size_t o = (wrow * p.G + g) * p.L + l;
+        p.taus[o] = tt;
+        p.omegas[o] = (tt > 0.0) ? (ray + sca) / tt : 0.0;
+    }
+    p.tauray_l[wrow * p.L + l] = ray;
+    for (int c = 0; c < p.ncont; ++c) p.lfrac_l[(wrow * p.ncont + c) * p.L + l] = p.lfrac[(cr * p.ncont + c) * p.W + w];
+    const double c1 = 1.1911e-12, c2 = 1.439;
+    const double wv = p.wave[w];
+    double y, a;
+    if (p.ispace == 0) { y = wv; a = c1 * (y * y * y); }
+    else { y = 1.0e4 / wv; a = c1 * (y * y * y * y * y) / 1.0e4; }
+    p.bnu[wrow * p.L + l] = a / (exp(c2 * y / p.lay_temp[ml_l]) - 1.0);
+}
+
+// same[m][l] from the two index maps: the gas-opacity row is model 0's and so is the continuum row.  No data is compared: equal
+// content under two indices counts as different (the layer is recomputed, with the bits of a separate call).
+__global__ void k_ms_same_index(int n_models, int L, const int32_t *__restrict__ slot, const int32_t *__restrict__ cont_row,
+                                unsigned char *__restrict__ same)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_models * L) same[i] = (slot[i] == i % L && cont_row[i] == cont_row[i % L]) ? 1 : 0;
+}
+
+// One model's dense array from the rows, for the model-by-model route: dst [W][X][L] = rows [R][X][W] at cont_row[l] (X = 1:
+// an opacity, ncont: the fractions).  One thread per (wavenumber, layer, x).
+__global__ __launch_bounds__(128) void k_ms_rows_expand(int W, int X, int L, const int32_t *__restrict__ cont_row_m,
+                                                       const double *__restrict__ rows, double *__restrict__ dst)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y, x = blockIdx.z;
+    if (w >= W) return;
+    dst[((size_t)w * X + x) * L + l] = rows[((size_t)cont_row_m[l] * X + x) * W + w];
 }
 
 // CIRSrad's g-quadrature of the scattering branch (:4504): SPECOUT[w][path] = xfac[w] * sum_g rad[path][g][w] * DELG[g];

@@ -162,8 +162,9 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
     // taus / omegas / bnu: [model of the launch][wavenumber of the slab]; the other per-wavenumber arrays keep the whole axis
     const size_t wrow = (size_t)ml * p.wcount + wl;
     const double *taus_w = p.taus + (wrow * p.ng + ig) * p.nlay, *omegas_w = p.omegas + (wrow * p.ng + ig) * p.nlay;
-    const double *bnu_w = p.bnu + wrow * p.nlay, *tauray_w = p.tauray + (size_t)mg * p.st_wl + (size_t)widx * p.nlay;
-    const double *lfrac_m = p.lfrac + (size_t)mg * p.st_wcl;
+    const int mc = p.cont_local ? ml : mg, wcn = p.cont_local ? wl : widx;     // tauray / lfrac: by model, or by launch position
+    const double *bnu_w = p.bnu + wrow * p.nlay, *tauray_w = p.tauray + (size_t)mc * p.st_wl + (size_t)wcn * p.nlay;
+    const double *lfrac_m = p.lfrac + (size_t)mc * p.st_wcl;
     for (int l = 0; l < p.nlay; ++l) {
         const int k = lookup ? p.nlay - 1 - l : l;  // look-down: bottom layer first (:842-845)
         const double taut = taus_w[k];
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
                     double a = (p.iray > 0) ? fr * (PPL[(size_t)p.ncont * NN + e] * FC[(size_t)p.ncont * NN + e]) : 0.0;
                     double b = (p.iray > 0) ? fr * PMI[(size_t)p.ncont * NN + e] : 0.0;
                     for (int c = 0; c < p.ncont; ++c) {
-                        const double f = lfrac_m[((size_t)widx * p.ncont + c) * p.nlay + k];
+                        const double f = lfrac_m[((size_t)wcn * p.ncont + c) * p.nlay + k];
                         a += fs * (PPL[(size_t)c * NN + e] * FC[(size_t)c * NN + e]) * f;
                         b += fs * PMI[(size_t)c * NN + e] * f;
                     }

@@ -589,6 +589,62 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_cirsrad_ck_scatter_batch_slice(*args, W_full, w_begin), "cirsrad_ck_scatter_batch_slice")
         return out
 
+    def cirsrad_ck_scatter_batch_rows(self, ISPACE, lay_press_pa, lay_temp, amount, cont_row, TAUCIA_rows, TAUDUST_rows, TAURAY_rows,
+                                      TAUSCAT_rows, phasarr, lfrac_rows, radg, sol_angs, emiss_angs, aphis, solar, lowbc,
+                                      brdf_matrix, mu1, wt1, nf, nphi, iray, imie, xfac=None, wave_slice=None):
+        """`cirsrad_ck_scatter_batch` with the continuum once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows):
+        cont_row (n, NLAY) int, the continuum row of every (model, layer); TAUCIA_rows / TAUDUST_rows / TAURAY_rows / TAUSCAT_rows
+        (R, NWAVE) or None and lfrac_rows (R, NDUST, NWAVE), wavenumber fastest (`continuum_rows.ContinuumRows` packs them).
+        The rest, wave_slice included, as `cirsrad_ck_scatter_batch` -> SPECOUT (n, NWAVE, NPATH), bit-identical to that call
+        with the expanded arrays.  A layer is taken from model 0's doubling results when its gas inputs are model 0's and
+        cont_row[m, l] == cont_row[0, l]."""
+        dims, _ = self.ktable_info()
+        W, G, S = dims[0], dims[1], dims[4]
+        lp = _np(lay_press_pa)
+        if lp.ndim != 2:
+            raise ValueError("lay_press_pa must be (n_models, NLAY)")
+        n, L = lp.shape
+        am = _np(amount)
+        if am.shape != (n, S, L):
+            raise ValueError("amount must be (n_models, NGAS, NLAY)")
+        lt = _np(lay_temp)
+        if lt.shape != (n, L):
+            raise ValueError("lay_temp must be (n_models, NLAY)")
+        cr = np.asarray(cont_row)
+        if cr.shape != (n, L) or cr.dtype.kind not in "iu":
+            raise ValueError("cont_row must be an integer array (n_models, NLAY)")
+        cr = _np(cr, np.int32)
+        phasarr = None if phasarr is None else _np(phasarr)
+        ncont = 0 if phasarr is None else phasarr.shape[0]
+        nth = 0 if phasarr is None else phasarr.shape[3]
+        rows = [None if a is None else _np(a) for a in (TAUCIA_rows, TAUDUST_rows, TAURAY_rows, TAUSCAT_rows)]
+        lf = None if lfrac_rows is None or ncont == 0 else _np(lfrac_rows)
+        if ncont > 0 and lf is None:
+            raise ValueError("lfrac_rows is needed with aerosols (phasarr given)")
+        R = next((a.shape[0] for a in rows + [lf] if a is not None and a.ndim >= 1), max(int(cr.max()) + 1, 1))   # no array at all: any R serves
+        for name, a in zip(("TAUCIA_rows", "TAUDUST_rows", "TAURAY_rows", "TAUSCAT_rows"), rows):
+            if a is not None and a.shape != (R, W):
+                raise ValueError(f"{name} must be (R, NWAVE) = ({R}, {W}), got {a.shape}")
+        if lf is not None and lf.shape != (R, ncont, W):
+            raise ValueError(f"lfrac_rows must be (R, NDUST, NWAVE) = ({R}, {ncont}, {W}), got {lf.shape}")
+        sol = _np(np.atleast_1d(sol_angs)); emi = _np(np.atleast_1d(emiss_angs)); aph = _np(np.atleast_1d(aphis))
+        P = sol.shape[0]
+        mu1 = _np(mu1); nmu = mu1.shape[0]
+        rg = _np(radg)
+        if rg.size != n * W * nmu:
+            raise ValueError("radg must be (n_models, NWAVE, NMU)")
+        w_begin, W_full = (0, W) if wave_slice is None else (int(v) for v in wave_slice)
+        if phasarr is not None and phasarr.shape[1] != W_full:
+            raise ValueError("cirsrad_ck_scatter_batch_rows: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
+        out = np.empty((n, W, P))
+        rc = self._lib.ansfm_cirsrad_ck_scatter_batch_rows(
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(R), _ptr(cr), _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
+            _ptr(rows[3]), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)),
+            int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie),
+            _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
+        self._check(rc, "cirsrad_ck_scatter_batch_rows")
+        return out
+
     def last_scatter_cache(self):
         """(layers of models 1..n-1 taken from model 0's doubling results, all such layers) of the last batched scatter call"""
         a = C.c_int64(); b = C.c_int64()

@@ -203,12 +203,18 @@ def jacobian_nemesis_batched(model, rank=0, world_size=1, group=None, force_coll
 # phasarr is not among them: the Hansen walk of every slice runs over the whole axis
 _SCATTER_WAVE_AXIS = {"TAUCIA": 1, "TAUDUST": 1, "TAURAY": 1, "TAUSCAT": 1, "lfrac": 1, "radg": 1, "solar": 0, "brdf_matrix": 0,
                       "xfac": 0}
+# ... and of cirsrad_ck_scatter_batch_rows, whose continuum comes once per distinct layer, wavenumber fastest (the last axis)
+_SCATTER_ROWS_KEYS = ("TAUCIA_rows", "TAUDUST_rows", "TAURAY_rows", "TAUSCAT_rows", "lfrac_rows")
 
 
 def scatter_slice_inputs(inputs, w_begin, w_end):
     """The keyword arguments of `cirsrad_ck_scatter_batch` over the whole spectral axis -> those of the slice [w_begin, w_end):
-    every per-wavenumber input cut, phasarr and the rest as they are."""
+    every per-wavenumber input cut, phasarr and the rest as they are.  The rows form (`cirsrad_ck_scatter_batch_rows`: cont_row
+    and the *_rows arrays in place of the dense continuum) is cut along the rows' wavenumber axis; cont_row stays as it is."""
     out = dict(inputs)
+    for k in _SCATTER_ROWS_KEYS:
+        if inputs.get(k) is not None:
+            out[k] = np.ascontiguousarray(np.asarray(inputs[k])[..., w_begin:w_end])
     for k, ax in _SCATTER_WAVE_AXIS.items():
         if inputs.get(k) is not None:
             a = np.asarray(inputs[k])
@@ -219,7 +225,8 @@ def scatter_slice_inputs(inputs, w_begin, w_end):
 def jacobian_scatter_sharded(eng, inputs, XN, inum, rank=0, world_size=1, group=None, FIX=None, device="cpu",
                              force_collective=False):
     """Numerical Jacobian of a scattering batch with the spectral axis sharded over ranks: jacobian_nemesis_batched(shard=
-    "wavenumbers") for `cirsrad_ck_scatter_batch`.
+    "wavenumbers") for `cirsrad_ck_scatter_batch`, or -- inputs with cont_row and the *_rows arrays -- for
+    `cirsrad_ck_scatter_batch_rows`.
 
     inputs: its keyword arguments over the whole axis of W_full wavenumbers for the nfm forward models, row 0 the unperturbed
     state and row 1 + i the state with element inum[i] of XN perturbed.  `eng` holds rank r's slice chunk_range(W_full, n, r)
@@ -237,7 +244,8 @@ def jacobian_scatter_sharded(eng, inputs, XN, inum, rank=0, world_size=1, group=
     parts = [chunk_range(W_full, world_size, r) for r in range(world_size)]
     s, e = parts[rank]
     if e > s:
-        spec = eng.cirsrad_ck_scatter_batch(**scatter_slice_inputs(inputs, s, e), wave_slice=(s, W_full))    # (nfm, W_local, P)
+        call = eng.cirsrad_ck_scatter_batch_rows if "cont_row" in inputs else eng.cirsrad_ck_scatter_batch
+        spec = call(**scatter_slice_inputs(inputs, s, e), wave_slice=(s, W_full))                            # (nfm, W_local, P)
     else:
         spec = np.zeros((nfm, 0, P))
     block = torch.as_tensor(np.ascontiguousarray(spec).reshape(nfm, (e - s) * P), dtype=torch.float64, device=device)

@@ -224,6 +224,7 @@ class JacobianGPU:
             W = int(self.SpectroscopyX.NWAVE)
             NAV = int(M.NAV[IGEOM])
             staged = [[None] * NAV for _ in states]
+            packers = [{} for _ in range(NAV)]       # the continuum of the scattering groups by distinct layer (_ansfm_pack_scatter)
             for k, col in enumerate(states):
                 V.XN = xnx[:, col]                                                  # execute_fm :2154
                 for IAV in range(NAV):
@@ -234,6 +235,8 @@ class JacobianGPU:
                     rec = self._ansfm_thermal_inputs()
                     if rec is None:
                         rec = self._ansfm_scatter_inputs()
+                        if rec is not None and hasattr(eng, "cirsrad_ck_scatter_batch_rows"):
+                            self._ansfm_pack_scatter(rec, packers[IAV])
                     if rec is None:
                         rec = self._ansfm_singlescatt_inputs(eng)
                     if rec is None:                  # a CIRSrad branch without a batch axis: this state runs on its own
@@ -507,6 +510,21 @@ class JacobianGPU:
                 b(r["AZI_ANG"]), b(r["solar"]), r["LOWBC"], b(r["BRDF"]), b(r["MU"]), b(r["WTMU"]), r["NF"], r["NPHI"], r["IRAY"],
                 r["IMIE"])
 
+    _SCATTER_CONTINUUM = ("TAUCIA", "TAUDUST", "TAURAY", "TAUSCAT", "FRAC")
+
+    def _ansfm_pack_scatter(self, rec, packers):
+        """A staged scattering record joins the packer of its group (`packers`: group key -> ContinuumRows, one dict per
+        batched call): its five continuum arrays are kept once per distinct layer and leave the record, which remembers the
+        packer and its position in it.  The group then goes through cirsrad_ck_scatter_batch_rows."""
+        from .continuum_rows import ContinuumRows
+        key = self._ansfm_scatter_key(rec)
+        pk = packers.get(key)
+        if pk is None:
+            pk = packers[key] = ContinuumRows(rec["lp"].shape[0], rec["PHASE"].shape[0])
+        rec["rows"] = (pk, pk.n_states)
+        pk.add_state(*(rec.pop(name) for name in self._SCATTER_CONTINUUM))
+        rec["key"] = key
+
     def _ansfm_singlescatt_inputs(self, eng):
         """What CIRSrad's single-scattering branch hands to the engine (CIRSradGPU._ansfm_cirsrad_singlescatt), kept instead of
         run; None when the staged state is not on that branch, or the engine has no batched entry for it."""
@@ -545,7 +563,7 @@ class JacobianGPU:
             if "alone" in r:
                 out[k] = np.asarray(r["alone"]).reshape(W, -1)
             elif r.get("scatter"):
-                groups.setdefault(self._ansfm_scatter_key(r), []).append(k)
+                groups.setdefault(r.get("key") or self._ansfm_scatter_key(r), []).append(k)
             elif r.get("transmission"):
                 groups.setdefault(self._ansfm_transmission_key(r), []).append(k)
             elif r.get("singlescatt"):
@@ -559,10 +577,20 @@ class JacobianGPU:
             st = lambda name: np.stack([recs[k][name] for k in ks])
             if key[0] == "scatter":
                 # the NX + 1 multiple-scattering forward models the reference runs when ISCAT != THERMAL_EMISSION (:2251-2252)
-                spec = eng.cirsrad_ck_scatter_batch(r0["ISPACE"], st("lp"), st("lt"), st("f_gas"), st("TAUCIA"), st("TAUDUST"),
-                                                    st("TAURAY"), st("TAUSCAT"), r0["PHASE"], st("FRAC"), st("RADGROUND"), r0["SOL_ANG"],
-                                                    r0["EMISS_ANG"], r0["AZI_ANG"], r0["solar"], r0["LOWBC"], r0["BRDF"], r0["MU"],
-                                                    r0["WTMU"], r0["NF"], r0["NPHI"], r0["IRAY"], r0["IMIE"])
+                if "rows" in r0:             # packed while staged (_ansfm_pack_scatter): the group is the packer's states, in order
+                    pk = r0["rows"][0]
+                    if [recs[k]["rows"] for k in ks] != [(pk, j) for j in range(pk.n_states)]:
+                        raise RuntimeError("staged scattering records and their packer disagree")
+                    cont_row, cia, dust, ray, sca, frac = pk.rows()
+                    spec = eng.cirsrad_ck_scatter_batch_rows(r0["ISPACE"], st("lp"), st("lt"), st("f_gas"), cont_row, cia, dust, ray, sca,
+                                                             r0["PHASE"], frac, st("RADGROUND"), r0["SOL_ANG"], r0["EMISS_ANG"], r0["AZI_ANG"], r0["solar"],
+                                                             r0["LOWBC"], r0["BRDF"], r0["MU"], r0["WTMU"], r0["NF"], r0["NPHI"],
+                                                             r0["IRAY"], r0["IMIE"])
+                else:
+                    spec = eng.cirsrad_ck_scatter_batch(r0["ISPACE"], st("lp"), st("lt"), st("f_gas"), st("TAUCIA"), st("TAUDUST"),
+                                                        st("TAURAY"), st("TAUSCAT"), r0["PHASE"], st("FRAC"), st("RADGROUND"),
+                                                        r0["SOL_ANG"], r0["EMISS_ANG"], r0["AZI_ANG"], r0["solar"], r0["LOWBC"], r0["BRDF"],
+                                                        r0["MU"], r0["WTMU"], r0["NF"], r0["NPHI"], r0["IRAY"], r0["IMIE"])
                 spec = np.asarray(spec).reshape(len(ks), W, -1)
                 if hasattr(eng, "last_scatter_cache"):
                     a, b = eng.last_scatter_cache()           # layers of models 1.. taken from model 0's doublings / all of them

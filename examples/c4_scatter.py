@@ -62,6 +62,19 @@ def main():
               f"{bool(np.array_equal(spec[0], spec0))}")
         print("    spectrum [W cm-2 sr-1 (cm-1)-1]:", spec0[:3, 0], " largest response to a 5 % layer perturbation:",
               float(np.max(np.abs(spec[1:] - spec[0]) / np.abs(spec[0]))))
+        # the same Jacobian with the continuum handed over once per distinct layer: the packer keeps the first state's layers
+        # and, of every later state, the layers whose continuum differs in any bit (here: none), state by state
+        from archnemesis_dist_amd.continuum_rows import ContinuumRows
+        t = time.perf_counter()
+        pk = ContinuumRows(L, 1)
+        for m in range(n):
+            pk.add_state(None, TAUDUST, TAURAY, TAUSCAT, np.ones((W, 1, L)))
+        cont_row, cia, dust, ray, sca, frac = pk.rows()
+        rows = eng.cirsrad_ck_scatter_batch_rows(*args[:4], cont_row, cia, dust, ray, sca, ph, frac, args[10], *tail)
+        tr = time.perf_counter() - t
+        dense_bytes = sum(x.nbytes for x in args[5:8]) + args[9].nbytes
+        print(f"    by rows (R = {pk.R} of {n * L} layers, {pk.nbytes / 1e6:.1f} MB of continuum instead of {dense_bytes / 1e6:.1f} MB): "
+              f"{tr * 1e3:7.1f} ms with the packer; same bits: {bool(np.array_equal(rows, spec))}")
     # ... and the single-scattering branch (ISCAT = 3: plane parallel, the layer-mean phase function at the scattering angle)
     # for the same 21 states in one call
     _, _, _, TAURAY, TAUSCAT, TAUDUST, _ = scattering_inputs(W, L, WAVE, atm["lay_temp"][0], 5)

@@ -382,6 +382,28 @@ int ansfm_cirsrad_ck_scatter_batch_slice(ansfm_ctx *ctx, int ISPACE, int n_model
                                          const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
                                          const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
                                          int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
+/* The same batch (whole axis: W_full = W_local, w_begin = 0; or one slice) with the continuum handed over once per distinct
+ * layer instead of once per (model, layer): cont_row [n][L] (host) is the continuum row of layer l of model m,
+ * 0 <= cont_row < R; taucia_rows / taudust_rows / tauray_rows / tauscat_rows [R][W_local] (host, wavenumber fastest, NULL =
+ * zeros) and lfrac_rows [R][ncont][W_local] hold the rows -- one map serves all five, a row is "the continuum of one distinct
+ * layer".  Every other argument is ansfm_cirsrad_ck_scatter_batch_slice's.  The result is bit-identical to that entry called
+ * with the expanded arrays, dense[m][w][l] = rows[cont_row[m][l]][w]: the arithmetic per (wavenumber, g, layer) is the same.
+ * Layer (m, l) counts as model 0's -- and is taken from the layer cache -- when its gas-opacity row is model 0's and
+ * cont_row[m][l] == cont_row[0][l]; no array is compared.  Equal content under two different indices therefore loses cache
+ * hits for that layer, never bits: a recomputed layer gives the bits of a separate call.  The dense arrays exist nowhere:
+ * the rows are uploaded, and the chain kernels read copies of TAURAY and the fractions of one launch's models on one slab;
+ * the model-by-model route (n_models = 1, ansfm_set_layer_dedup(ctx, 0), ANSFM_MS_LAYER_CACHE=0) forms one model's arrays
+ * on the device at a time.  ANSFM_ERR_INVALID, before anything is launched, when cont_row is NULL, R <= 0 or an index is
+ * outside [0, R), and for the slice entry's reasons.  ansfm_last_scatter_cache / ansfm_last_layer_rows /
+ * ansfm_last_scatter_windows report as for the dense call. */
+int ansfm_cirsrad_ck_scatter_batch_rows(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                        const double *lay_temp, const double *amount, int R, const int32_t *cont_row,
+                                        const double *taucia_rows, const double *taudust_rows, const double *tauray_rows,
+                                        const double *tauscat_rows, int ncont, int nth, const double *phasarr,
+                                        const double *lfrac_rows, const double *radg, int ngeom, const double *sol_angs,
+                                        const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                        const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                        int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total);
 /* Spectral windows of phase matrices / Hansen factors in the last scattering call (ansfm_cirsrad_ck_scatter(_batch),
  * ansfm_scloud11wave_core) and the wavenumbers per window: 1 and W when one window covers the axis (always at G > 1). */

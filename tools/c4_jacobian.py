@@ -1,7 +1,12 @@
 """Batched numerical Jacobian of the scattering configuration at BASELINE configs[3] size (ansfm_cirsrad_ck_scatter_batch):
     python tools/c4_jacobian.py [--nx 20] [--waves 10000] [--check]
 One rank's share of the wavenumber-sharded Jacobian (ansfm_cirsrad_ck_scatter_batch_slice) on one GPU:
-    python tools/c4_jacobian.py --nx 200 --rank-of 8 [--rank 7]"""
+    python tools/c4_jacobian.py --nx 200 --rank-of 8 [--rank 7]
+The same Jacobian with the continuum packed once per distinct layer (continuum_rows.ContinuumRows ->
+ansfm_cirsrad_ck_scatter_batch_rows), dense and rows forms alternating in one process:
+    python tools/c4_jacobian.py --nx 200 --rows [--nmu 5 --nf 2] [--repeats 3] [--check-models 5]
+... and at a size whose dense continuum fits nowhere -- an LBL table (G = 1) of 2e5 wavenumbers, the rows form alone:
+    python tools/c4_jacobian.py --nx 200 --lbl --waves 200000 --rows --rows-only --repeats 1 --check-models 5"""
 import argparse
 import os
 import sys
@@ -35,6 +40,11 @@ def main():
     ap.add_argument("--nf", type=int, default=8, help="Fourier orders - 1 (the reference's default is 2)")
     ap.add_argument("--rank-of", type=int, default=0, help="time one rank's slice chunk_range(waves, N, rank) of the axis")
     ap.add_argument("--rank", type=int, default=0)
+    ap.add_argument("--rows", action="store_true", help="time the dense form and the rows form (packer included), alternating")
+    ap.add_argument("--repeats", type=int, default=3, help="--rows: timed calls of each form after the first")
+    ap.add_argument("--check-models", type=int, default=0, help="--rows: compare this many models with calls of their own")
+    ap.add_argument("--rows-only", action="store_true", help="--rows: never build the dense continuum (sizes at which it does not fit)")
+    ap.add_argument("--lbl", action="store_true", help="an LBL table (G = 1, two gases, 0.01 cm-1 grid) instead of the k-table")
     args = ap.parse_args()
     import torch
     import archnemesis_dist_amd as pkg
@@ -46,16 +56,26 @@ def main():
     W, G, S, L, NP, NT, NMU, NF = args.waves, 20, 8, 100, 20, 15, args.nmu, args.nf
     eng = pkg.AnsfmEngine(0)
     _, delg = syn.gauss_legendre_01(G, as_float32=True)
-    PRESS, TEMP, K = torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
-    WAVE = 200.0 + 0.1 * np.arange(W)
-    if args.rank_of:                            # the rank's slice of the table only
-        from archnemesis_dist_amd.jacobian import chunk_range
-        ws, we = chunk_range(W, args.rank_of, args.rank)
-        K = K[ws:we].contiguous()
-        torch.cuda.empty_cache()
-        eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE[ws:we], delg.astype(np.float32))
+    if args.lbl:                                # the table of tools/c4_lbl_run.py
+        if args.rank_of:
+            ap.error("--lbl times the whole axis")
+        S, NP, NT = 2, 6, 4
+        rng = np.random.default_rng(3)
+        PRESS = np.logspace(-5, 1, NP); TEMP = np.linspace(90.0, 300.0, NT)
+        K = (10.0 ** rng.uniform(-25, -21, (W, 1, 1, S))) * PRESS[None, :, None, None] ** 0.15 * (TEMP[None, None, :, None] / 150.0) ** 0.8
+        WAVE = 200.0 + 0.01 * np.arange(W)
+        eng.upload_lbltable(K, PRESS, TEMP, WAVE)
     else:
-        eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32))
+        PRESS, TEMP, K = torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+        WAVE = 200.0 + 0.1 * np.arange(W)
+        if args.rank_of:                        # the rank's slice of the table only
+            from archnemesis_dist_amd.jacobian import chunk_range
+            ws, we = chunk_range(W, args.rank_of, args.rank)
+            K = K[ws:we].contiguous()
+            torch.cuda.empty_cache()
+            eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE[ws:we], delg.astype(np.float32))
+        else:
+            eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32))
     del K
     npro = max(args.nx // 2, 2)
     pr = syn.synth_profiles(100, S + 2, seed=11)
@@ -66,13 +86,18 @@ def main():
     lay = model.layers(X)
     n = X.shape[0]
     MU, WT, ph, TAURAY, TAUSCAT, TAUDUST = c4_case(W, L, NMU, NF)
-    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a[None], (n,) + a.shape))
+    if args.rows_only and not args.rows:
+        ap.error("--rows-only goes with --rows")
+    rep = lambda a: None if args.rows_only else np.ascontiguousarray(np.broadcast_to(a[None], (n,) + a.shape))
     c1, c2 = 1.1911e-12, 1.439
     radg = np.stack([np.repeat((c1 * WAVE ** 3 / (np.exp(c2 * WAVE / lay["TEMP"][m, 0]) - 1.0))[:, None], NMU, 1) for m in range(n)])
     a = (0, lay["PRESS"], lay["TEMP"], lay["amount"], None, rep(TAUDUST), rep(TAURAY), rep(TAUSCAT), ph, rep(np.ones((W, 1, L))), radg,
          [30.0], [20.0], [45.0], np.full(W, 1e-8), 0, np.zeros((W, NMU, NMU, NF + 1)), MU, WT, NF, 101, 1, 1)
     if args.rank_of:
         rank_share(args, eng, a, W, ws, we, n, PRESS, TEMP, WAVE, delg)
+        return
+    if args.rows:
+        rows_against_dense(args, eng, a, lay, n, (TAUDUST, TAURAY, TAUSCAT, np.ones((W, 1, L))))
         return
     if args.forward:
         ts = []
@@ -100,6 +125,65 @@ def main():
         print("every state equals a call of its own, bit for bit")
     kk = (spec[1:, :, 0] - spec[0:1, :, 0])
     print("max |dY| / |Y| per column:", np.max(np.abs(kk) / np.abs(spec[0:1, :, 0]), axis=1)[:6])
+
+
+def rows_against_dense(args, eng, a, lay, n, state_cont):
+    """The Jacobian through the dense entry and through the packer + the rows entry on one context, alternating; the first
+    call of each form is the cold one (the context grows its buffers), the later ones are the steady state.  The rows form's
+    time includes packing the n states one by one, as a caller that builds them state by state would."""
+    import torch
+    from archnemesis_dist_amd.continuum_rows import ContinuumRows
+    TAUDUST, TAURAY, TAUSCAT, FRAC = state_cont
+    L, ncont = TAUDUST.shape[1], FRAC.shape[1]
+    dense_bytes = n * sum(x.nbytes for x in state_cont)
+
+    def by_rows():
+        pk = ContinuumRows(L, ncont)
+        for m in range(n):                       # (in this synthetic case no state changes the continuum: R = L)
+            pk.add_state(None, TAUDUST, TAURAY, TAUSCAT, FRAC)
+        t1 = time.perf_counter()
+        out = eng.cirsrad_ck_scatter_batch_rows(*a[:4], *pk.rows()[:5], a[8], pk.lfrac_rows, *a[10:])
+        return out, pk, t1
+
+    free0 = torch.cuda.mem_get_info(0)[0]
+    td, tr, tp = [], [], []
+    held = {}
+    for it in range(1 + args.repeats):
+        t0 = time.perf_counter()
+        rows, pk, t1 = by_rows()
+        tr.append(time.perf_counter() - t0); tp.append(t1 - t0)
+        info_r = (eng.last_scatter_cache(), eng.last_layer_rows(), eng.last_scatter_windows())
+        if it == 0:
+            held["rows"] = free0 - torch.cuda.mem_get_info(0)[0]
+        if args.rows_only:
+            info_d = info_r
+            continue
+        t0 = time.perf_counter()
+        dense = eng.cirsrad_ck_scatter_batch(*a)
+        td.append(time.perf_counter() - t0)
+        info_d = (eng.last_scatter_cache(), eng.last_layer_rows(), eng.last_scatter_windows())
+        if it == 0:
+            held["both"] = free0 - torch.cuda.mem_get_info(0)[0]
+        assert np.array_equal(rows, dense) and info_r == info_d, (info_r, info_d)
+    fmt = lambda ts: " ".join("%.3f" % x for x in ts)
+    print("n = %d forward models, nmu %d / NF %d, %d wavenumbers; cache %s, gas rows %s, slabs %s%s"
+          % (n, args.nmu, args.nf, a[14].shape[0], *info_d, "" if args.rows_only else "; rows == dense bit for bit in every call"))
+    if not args.rows_only:
+        print("dense form: calls %s s  (first: cold);  steady min %.3f median %.3f spread %.3f s"
+              % (fmt(td), min(td[1:]), float(np.median(td[1:])), max(td[1:]) - min(td[1:])))
+    print("rows form, packer included: calls %s s (packer %s s);  steady min %.3f median %.3f spread %.3f s"
+          % (fmt(tr), fmt(tp), min(tr[1:]), float(np.median(tr[1:])), max(tr[1:]) - min(tr[1:])))
+    print("host bytes of the continuum inputs: dense %.3f GB%s, rows %.4f GB (R = %d of %d (model, layer) pairs)"
+          % (dense_bytes / 1e9, " (not built)" if args.rows_only else "", pk.nbytes / 1e9, pk.R, n * L))
+    print("device memory the context holds: %.2f GB after the rows form alone" % (held["rows"] / 1e9)
+          + ("" if args.rows_only else ", %.2f GB once the dense form has run too" % (held["both"] / 1e9)))
+    print("checksum %.17g" % float(rows.sum()))
+    for m in np.linspace(0, n - 1, args.check_models).astype(int) if args.check_models else []:
+        o = eng.cirsrad_ck_scatter(0, lay["PRESS"][m], lay["TEMP"][m], lay["amount"][m], None, TAUDUST, TAURAY, TAUSCAT, a[8], FRAC,
+                                   a[10][m], *a[11:])
+        assert np.array_equal(o, rows[m]), m
+    if args.check_models:
+        print("%d models equal calls of their own, bit for bit" % args.check_models)
 
 
 def rank_share(args, eng, a, W, ws, we, n, PRESS, TEMP, WAVE, delg):
