@@ -31,6 +31,8 @@ EXPORTS = [
     "ansfm_layer_average_dev", "ansfm_calc_tau_rayleigh_batch_dev_in", "ansfm_last_rt_shared",
     "ansfm_cirsrad_ck_thermal_ray_dev", "ansfm_last_scatter_windows", "ansfm_cirsrad_ck_scatter_batch_slice",
     "ansfm_cirsrad_ck_singlescatt_batch", "ansfm_cirsrad_ck_scatter_batch_rows",
+    "ansfm_add_pseudo_continuum_monochromatic_absorption", "ansfm_lbl_accum_begin", "ansfm_lbl_accum_add_lines",
+    "ansfm_lbl_accum_add_pseudo_continuum", "ansfm_lbl_accum_read", "ansfm_lbl_accum_device_ptr",
 ]
 
 _lib = None
@@ -158,6 +160,13 @@ def load():
     lib.ansfm_calc_klbl.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.ansfm_add_line_set_monochromatic_absorption.argtypes = [vp, ci, vp, ci, ci, vp, cd, vp, cd, vp, cd, cd, ci, vp, ci, vp,
                                                                 vp, vp, vp, vp, vp, vp, cd, cd, cd]
+    lib.ansfm_add_pseudo_continuum_monochromatic_absorption.argtypes = [vp, ci, vp, ci, ci, vp, cd, vp, cd, vp, cd, cd, ci, vp, ci,
+                                                                        vp, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.ansfm_lbl_accum_begin.argtypes = [vp, ci, vp, ci, vp, vp]
+    lib.ansfm_lbl_accum_add_lines.argtypes = [vp, ci, cd, cd, vp, cd, cd, ci, vp, ci, vp, vp, vp, vp, vp, vp, cd, cd, cd]
+    lib.ansfm_lbl_accum_add_pseudo_continuum.argtypes = [vp, ci, cd, cd, vp, cd, cd, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.ansfm_lbl_accum_read.argtypes = [vp, vp]
+    lib.ansfm_lbl_accum_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci)]
     lib.ansfm_layer_average.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 11
     lib.ansfm_layer_average_dev.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp, vp]
     lib.ansfm_layer_averageg.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 15

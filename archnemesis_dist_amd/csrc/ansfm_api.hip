@@ -4,6 +4,7 @@
 #include "ansfm_ms_kernels.hip.h"
 #include "ansfm_ms_lane.hip.h"
 #include "ansfm_lbl_kernels.hip.h"
+#include "ansfm_lbl_pc_kernels.hip.h"
 #include "ansfm_layer_kernels.hip.h"
 #include "ansfm_map_kernels.hip.h"
 #include "ansfm_conv_kernels.hip.h"
@@ -89,6 +90,10 @@ struct ansfm_ctx {
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
     long ms_windows = 0, ms_window_w = 0;          // spectral windows of phase matrices / Hansen factors of the last scattering call, their size
     DevBuf hb[24];  // staging buffers of the host-pointer entry points
+    // runtime line-by-line: the opacity of a gas, summed in HBM (ansfm_lbl_accum_*); its grid and (T, p) points [2][L]
+    DevBuf acc, acc_grid, acc_tp;
+    int acc_nw = 0, acc_L = 0;           // 0: no accumulator begun
+    std::vector<double> acc_h_grid, acc_h_p;
     int last_n = 0, last_L = 0;
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
@@ -3137,23 +3142,31 @@ int ansfm_calc_klbl(ansfm_ctx *ctx, int L, const double *press, const double *te
 /* ------------------------------------------------------------------------------------------ */
 /* runtime line-by-line                                                                        */
 /* ------------------------------------------------------------------------------------------ */
-int ansfm_add_line_set_monochromatic_absorption(
-    ansfm_ctx *ctx, int nw, const double *wn_grid, int lineshape_id, int L, const double *t_calc, double t_ref,
-    const double *p_calc, double p_ref, const double *q_ratio, double isotopic_abundance, double isotopic_mass, int M,
-    const double *mol_mix_frac, int N, const double *broadening_params, const double *nu, const double *sw,
-    const double *e_lower, const double *stim_ref, double *out, double *store, double s_floor, double wn_calc_window,
-    double wn_approx_window)
+} // extern "C"
+
+static int lbl_shape_built(ansfm_ctx *ctx, int lineshape_id)
 {
-    CHECK_CTX(ctx);
-    if (nw <= 0 || L <= 0 || M <= 0 || N < 0 || !wn_grid || !t_calc || !p_calc || !q_ratio || !mol_mix_frac || !out ||
-        (N > 0 && (!broadening_params || !nu || !sw || !e_lower || !stim_ref)))
-        FAIL(ANSFM_ERR_INVALID, "add_line_set_monochromatic_absorption: bad argument");
     if (lineshape_id != 0 && lineshape_id != 4 && lineshape_id != 12)
         FAIL(ANSFM_ERR_UNSUPPORTED, "lineshape: VOIGT (0), LORENTZ (4), DOPPLER (12) are built");   // enum map raises NotImplementedError
+    return ANSFM_OK;
+}
+
+static int lbl_grid_ascending(ansfm_ctx *ctx, int nw, const double *wn_grid)
+{
     for (int j = 1; j < nw; ++j)
         if (wn_grid[j] < wn_grid[j - 1]) FAIL(ANSFM_ERR_INVALID, "wn_grid must be ascending (LineData_0.py:230)");
-    if (N == 0) return ANSFM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
+    return ANSFM_OK;
+}
+
+// The lines of one isotopologue onto d_out[L][nw] in HBM.  d_grid / d_t / d_p: device copies of the grid and the (T, p)
+// points (h_p: the pressures on the host); everything else is staged here, from st's next slot on.  Arguments are checked.
+static int lbl_lines_dev(ansfm_ctx *ctx, Stager &st, int nw, const double *d_grid, int lineshape_id, int L, const double *d_t,
+                         double t_ref, const double *d_p, const double *h_p, double p_ref, const double *q_ratio,
+                         double isotopic_abundance, double isotopic_mass, int M, const double *mol_mix_frac, int N,
+                         const double *broadening_params, const double *nu, const double *sw, const double *e_lower,
+                         const double *stim_ref, double *d_out, double *store, double s_floor, double wn_calc_window,
+                         double wn_approx_window)
+{
     // lines sorted by wavenumber for the windowed gather (the reference accepts any order; summation order then
     // differs from it only in rounding)
     std::vector<int> ord(N);
@@ -3173,18 +3186,17 @@ int ansfm_add_line_set_monochromatic_absorption(
         if (d > dmax) dmax = d;
     }
     double pmax = 0.0;
-    for (int l = 0; l < L; ++l) if (fabs(p_calc[l] / p_ref) > pmax) pmax = fabs(p_calc[l] / p_ref);
+    for (int l = 0; l < L; ++l) if (fabs(h_p[l] / p_ref) > pmax) pmax = fabs(h_p[l] / p_ref);
     const size_t D = sizeof(double);
     LblParams p;
     memset(&p, 0, sizeof p);
-    Stager st{ctx};
     const double *dl = st.up(h.data(), h.size());
-    p.wn_grid = st.up(wn_grid, nw); p.mmf = st.up(mol_mix_frac, M);
-    p.t_calc = st.up(t_calc, L); p.p_calc = st.up(p_calc, L); p.q_ratio = st.up(q_ratio, L);
-    p.out = const_cast<double *>(st.up(out, (size_t)L * nw));     // accumulated onto
+    p.mmf = st.up(mol_mix_frac, M);
+    p.q_ratio = st.up(q_ratio, L);
     if (st.rc) return st.rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));   // h is a local buffer
     HIPCHK(ctx->misc.reserve((size_t)L * (kLblRows + 1) * N * D));
+    p.wn_grid = d_grid; p.t_calc = d_t; p.p_calc = d_p; p.out = d_out;
     p.nu = dl; p.sw = dl + N; p.e_lower = dl + 2 * (size_t)N; p.stim_ref = dl + 3 * (size_t)N; p.bparams = dl + 4 * (size_t)N;
     p.store = ctx->misc.as<double>();
     p.shift = p.store + (size_t)L * kLblRows * N;
@@ -3196,14 +3208,10 @@ int ansfm_add_line_set_monochromatic_absorption(
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_lbl_accumulate, dim3(nblk(nw, 256 * kLblPts), (unsigned)L), dim3(256), 0, ctx->stream, p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, p.out, (size_t)L * nw * D, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<double> hst;
-    if (store) {
-        hst.resize((size_t)L * (kLblRows + 1) * N);
-        HIPCHK(hipMemcpyAsync(hst.data(), p.store, hst.size() * D, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     if (store) {   // store[L][4][N] = strength, alpha_d, gamma_l, shift in the caller's line order
+        std::vector<double> hst((size_t)L * (kLblRows + 1) * N);
+        HIPCHK(hipMemcpyAsync(hst.data(), p.store, hst.size() * D, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
         static const int src[3] = {0, 6, 7};
         const double *hsh = hst.data() + (size_t)L * kLblRows * N;
         for (int l = 0; l < L; ++l)
@@ -3213,6 +3221,224 @@ int ansfm_add_line_set_monochromatic_absorption(
                 store[((size_t)l * 4 + 3) * N + ord[i]] = hsh[(size_t)l * N + i];
             }
     }
+    return ANSFM_OK;
+}
+
+// The pseudo-continuum of one isotopologue onto d_out[L][nw] in HBM; h_grid: the grid on the host, for the bin geometry.
+static int lbl_pc_dev(ansfm_ctx *ctx, Stager &st, int nw, const double *d_grid, const double *h_grid, int lineshape_id, int L,
+                      const double *d_t, double t_ref, const double *d_p, double p_ref, const double *q_ratio,
+                      double isotopic_abundance, double isotopic_mass, int M, const double *mol_mix_frac, int N,
+                      const double *bparams, const double *centers, const double *widths, const double *sw_sum,
+                      const double *e_lower, double *d_out, double *store, double *store_x, int nb)
+{
+    // the geometry of the bins, with the reference's expressions: first / last (:399-416), the largest touched grid point
+    // (j_max :463; the touched points of a bin are a run, because (wn - c)/w does not decrease along an ascending grid)
+    std::vector<double> lo(N);
+    int first = -1, last = -1, jmax = 0;
+    double wmax = 0.0;
+    for (int i = 0; i < N; ++i) {
+        const double c = centers[i], w = widths[i];
+        if (!(w > 0.0)) FAIL(ANSFM_ERR_INVALID, "pseudo-continuum: bin widths must be positive");
+        const double bin_min = c - w / 2.0, bin_max = c + w / 2.0;
+        if (i > 0 && !(bin_min >= lo[i - 1]))
+            FAIL(ANSFM_ERR_INVALID, "pseudo-continuum: the lower bin edges centre - width / 2 must be ascending");
+        lo[i] = bin_min;
+        if (first == -1 && bin_min <= h_grid[0]) first = i;
+        if (last == -1 && bin_max > h_grid[nw - 1]) last = i;
+        if (w > wmax) wmax = w;
+        int a = 0, b = nw;      // first j with (wn_j - c)/w >= 0.5
+        while (a < b) { const int mid = (a + b) >> 1; if ((h_grid[mid] - c) / w < 0.5) a = mid + 1; else b = mid; }
+        if (a > 0 && (h_grid[a - 1] - c) / w >= -0.5 && a - 1 > jmax) jmax = a - 1;
+    }
+    if (first == -1) first = N;
+    if (last == -1) last = N;
+    const size_t D = sizeof(double), LN = (size_t)L * N;
+    PcParams p;
+    memset(&p, 0, sizeof p);
+    p.centers = st.up(centers, N); p.widths = st.up(widths, N); p.sw = st.up(sw_sum, N); p.e_lower = st.up(e_lower, N);
+    p.lo = st.up(lo.data(), N); p.bparams = st.up(bparams, (size_t)3 * M * N);
+    p.mmf = st.up(mol_mix_frac, M); p.q_ratio = st.up(q_ratio, L);
+    if (st.rc) return st.rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // lo is a local buffer
+    HIPCHK(ctx->misc.reserve(LN * (size_t)(3 + (2 * nb + 1) + 2) * D));
+    p.wn_grid = d_grid; p.t_calc = d_t; p.p_calc = d_p; p.out = d_out;
+    p.store = ctx->misc.as<double>();
+    p.x = p.store + 3 * LN; p.ysum = p.x + LN; p.y = p.ysum + LN;
+    p.nw = nw; p.N = N; p.M = M; p.L = L; p.lineshape_id = lineshape_id; p.nb = nb;
+    p.first = first; p.last = last; p.jmax = jmax;
+    p.t_ref = t_ref; p.p_ref = p_ref; p.iso_abundance = isotopic_abundance; p.iso_mass = isotopic_mass; p.wmax = wmax;
+    hipLaunchKernelGGL(k_pc_params, dim3(nblk(LN, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pc_shapes, dim3(nblk(LN, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pc_gather, dim3(nblk(LN, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    if (jmax > 0) {
+        hipLaunchKernelGGL(k_pc_interp, dim3(nblk((size_t)jmax, 256), nblk((size_t)L, kPcLayers)), dim3(256), 0, ctx->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    if (store) HIPCHK(hipMemcpyAsync(store, p.store, 3 * LN * D, hipMemcpyDeviceToHost, ctx->stream));
+    if (store_x) HIPCHK(hipMemcpyAsync(store_x, p.x, LN * D, hipMemcpyDeviceToHost, ctx->stream));
+    if (store || store_x) HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
+static int lbl_pc_args(ansfm_ctx *ctx, int lineshape_id, int M, int N, const double *q_ratio, const double *mol_mix_frac,
+                       const double *bparams, const double *centers, const double *widths, const double *sw_sum,
+                       const double *e_lower, int nb)
+{
+    if (M <= 0 || N < 0 || nb < 0 || !q_ratio || !mol_mix_frac || (N > 0 && (!bparams || !centers || !widths || !sw_sum || !e_lower)))
+        FAIL(ANSFM_ERR_INVALID, "add_pseudo_continuum_monochromatic_absorption: bad argument");
+    if (nb > kPcMaxNeighbours) FAIL(ANSFM_ERR_UNSUPPORTED, "pseudo-continuum: n_neighbour_bins 0 .. 8 are built");
+    return lbl_shape_built(ctx, lineshape_id);
+}
+
+extern "C" {
+
+int ansfm_add_line_set_monochromatic_absorption(
+    ansfm_ctx *ctx, int nw, const double *wn_grid, int lineshape_id, int L, const double *t_calc, double t_ref,
+    const double *p_calc, double p_ref, const double *q_ratio, double isotopic_abundance, double isotopic_mass, int M,
+    const double *mol_mix_frac, int N, const double *broadening_params, const double *nu, const double *sw,
+    const double *e_lower, const double *stim_ref, double *out, double *store, double s_floor, double wn_calc_window,
+    double wn_approx_window)
+{
+    CHECK_CTX(ctx);
+    if (nw <= 0 || L <= 0 || M <= 0 || N < 0 || !wn_grid || !t_calc || !p_calc || !q_ratio || !mol_mix_frac || !out ||
+        (N > 0 && (!broadening_params || !nu || !sw || !e_lower || !stim_ref)))
+        FAIL(ANSFM_ERR_INVALID, "add_line_set_monochromatic_absorption: bad argument");
+    int rc = lbl_shape_built(ctx, lineshape_id);
+    if (rc || (rc = lbl_grid_ascending(ctx, nw, wn_grid))) return rc;
+    if (N == 0) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Stager st{ctx};
+    const double *d_grid = st.up(wn_grid, nw), *d_t = st.up(t_calc, L), *d_p = st.up(p_calc, L);
+    double *d_out = const_cast<double *>(st.up(out, (size_t)L * nw));     // accumulated onto
+    if (st.rc) return st.rc;
+    rc = lbl_lines_dev(ctx, st, nw, d_grid, lineshape_id, L, d_t, t_ref, d_p, p_calc, p_ref, q_ratio, isotopic_abundance,
+                       isotopic_mass, M, mol_mix_frac, N, broadening_params, nu, sw, e_lower, stim_ref, d_out, store, s_floor,
+                       wn_calc_window, wn_approx_window);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)L * nw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
+int ansfm_add_pseudo_continuum_monochromatic_absorption(
+    ansfm_ctx *ctx, int nw, const double *wn_grid, int lineshape_id, int L, const double *t_calc, double t_ref,
+    const double *p_calc, double p_ref, const double *q_ratio, double isotopic_abundance, double isotopic_mass, int M,
+    const double *mol_mix_frac, int N, const double *lsw_mean_broadening_params, const double *wn_bin_centers,
+    const double *wn_bin_widths, const double *sw_sum, const double *lsw_mean_e_lower, double *out, double *store,
+    double *store_x, int n_neighbour_bins)
+{
+    CHECK_CTX(ctx);
+    if (nw <= 0 || L <= 0 || !wn_grid || !t_calc || !p_calc || !out)
+        FAIL(ANSFM_ERR_INVALID, "add_pseudo_continuum_monochromatic_absorption: bad argument");
+    int rc = lbl_pc_args(ctx, lineshape_id, M, N, q_ratio, mol_mix_frac, lsw_mean_broadening_params, wn_bin_centers,
+                         wn_bin_widths, sw_sum, lsw_mean_e_lower, n_neighbour_bins);
+    if (rc || (rc = lbl_grid_ascending(ctx, nw, wn_grid))) return rc;
+    if (N == 0) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Stager st{ctx};
+    const double *d_grid = st.up(wn_grid, nw), *d_t = st.up(t_calc, L), *d_p = st.up(p_calc, L);
+    double *d_out = const_cast<double *>(st.up(out, (size_t)L * nw));     // accumulated onto
+    if (st.rc) return st.rc;
+    rc = lbl_pc_dev(ctx, st, nw, d_grid, wn_grid, lineshape_id, L, d_t, t_ref, d_p, p_ref, q_ratio, isotopic_abundance,
+                    isotopic_mass, M, mol_mix_frac, N, lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum,
+                    lsw_mean_e_lower, d_out, store, store_x, n_neighbour_bins);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)L * nw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
+/* ---- the opacity of a gas in HBM: the sum over its isotopologues of lines and pseudo-continuum -------------------------- */
+int ansfm_lbl_accum_begin(ansfm_ctx *ctx, int nw, const double *wn_grid, int L, const double *t_calc, const double *p_calc)
+{
+    CHECK_CTX(ctx);
+    ctx->acc_nw = ctx->acc_L = 0;
+    if (nw <= 0 || L <= 0 || !wn_grid || !t_calc || !p_calc) FAIL(ANSFM_ERR_INVALID, "lbl_accum_begin: bad argument");
+    const int rc = lbl_grid_ascending(ctx, nw, wn_grid);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t D = sizeof(double);
+    HIPCHK(ctx->acc.reserve((size_t)L * nw * D));
+    HIPCHK(ctx->acc_grid.reserve((size_t)nw * D));
+    HIPCHK(ctx->acc_tp.reserve((size_t)2 * L * D));
+    ctx->acc_h_grid.assign(wn_grid, wn_grid + nw);
+    ctx->acc_h_p.assign(p_calc, p_calc + L);
+    HIPCHK(hipMemsetAsync(ctx->acc.p, 0, (size_t)L * nw * D, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->acc_grid.p, ctx->acc_h_grid.data(), (size_t)nw * D, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->acc_tp.p, t_calc, (size_t)L * D, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->acc_tp.as<double>() + L, p_calc, (size_t)L * D, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // t_calc / p_calc are the caller's
+    ctx->acc_nw = nw; ctx->acc_L = L;
+    return ANSFM_OK;
+}
+
+int ansfm_lbl_accum_add_lines(ansfm_ctx *ctx, int lineshape_id, double t_ref, double p_ref, const double *q_ratio,
+                              double isotopic_abundance, double isotopic_mass, int M, const double *mol_mix_frac, int N,
+                              const double *broadening_params, const double *nu, const double *sw, const double *e_lower,
+                              const double *stim_ref, double *store, double s_floor, double wn_calc_window,
+                              double wn_approx_window)
+{
+    CHECK_CTX(ctx);
+    if (ctx->acc_nw <= 0) FAIL(ANSFM_ERR_INVALID, "lbl_accum_add_lines: call ansfm_lbl_accum_begin first");
+    if (M <= 0 || N < 0 || !q_ratio || !mol_mix_frac || (N > 0 && (!broadening_params || !nu || !sw || !e_lower || !stim_ref)))
+        FAIL(ANSFM_ERR_INVALID, "lbl_accum_add_lines: bad argument");
+    const int rc = lbl_shape_built(ctx, lineshape_id);
+    if (rc) return rc;
+    if (N == 0) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Stager st{ctx};
+    const int L = ctx->acc_L;
+    return lbl_lines_dev(ctx, st, ctx->acc_nw, ctx->acc_grid.as<double>(), lineshape_id, L, ctx->acc_tp.as<double>(), t_ref,
+                         ctx->acc_tp.as<double>() + L, ctx->acc_h_p.data(), p_ref, q_ratio, isotopic_abundance, isotopic_mass, M,
+                         mol_mix_frac, N, broadening_params, nu, sw, e_lower, stim_ref, ctx->acc.as<double>(), store, s_floor,
+                         wn_calc_window, wn_approx_window);
+}
+
+int ansfm_lbl_accum_add_pseudo_continuum(ansfm_ctx *ctx, int lineshape_id, double t_ref, double p_ref, const double *q_ratio,
+                                         double isotopic_abundance, double isotopic_mass, int M, const double *mol_mix_frac,
+                                         int N, const double *lsw_mean_broadening_params, const double *wn_bin_centers,
+                                         const double *wn_bin_widths, const double *sw_sum, const double *lsw_mean_e_lower,
+                                         double *store, double *store_x, int n_neighbour_bins)
+{
+    CHECK_CTX(ctx);
+    if (ctx->acc_nw <= 0) FAIL(ANSFM_ERR_INVALID, "lbl_accum_add_pseudo_continuum: call ansfm_lbl_accum_begin first");
+    const int rc = lbl_pc_args(ctx, lineshape_id, M, N, q_ratio, mol_mix_frac, lsw_mean_broadening_params, wn_bin_centers,
+                               wn_bin_widths, sw_sum, lsw_mean_e_lower, n_neighbour_bins);
+    if (rc) return rc;
+    if (N == 0) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    Stager st{ctx};
+    const int L = ctx->acc_L;
+    return lbl_pc_dev(ctx, st, ctx->acc_nw, ctx->acc_grid.as<double>(), ctx->acc_h_grid.data(), lineshape_id, L,
+                      ctx->acc_tp.as<double>(), t_ref, ctx->acc_tp.as<double>() + L, p_ref, q_ratio, isotopic_abundance,
+                      isotopic_mass, M, mol_mix_frac, N, lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum,
+                      lsw_mean_e_lower, ctx->acc.as<double>(), store, store_x, n_neighbour_bins);
+}
+
+int ansfm_lbl_accum_read(ansfm_ctx *ctx, double *out)
+{
+    CHECK_CTX(ctx);
+    if (ctx->acc_nw <= 0) FAIL(ANSFM_ERR_INVALID, "lbl_accum_read: call ansfm_lbl_accum_begin first");
+    if (!out) FAIL(ANSFM_ERR_INVALID, "lbl_accum_read: bad argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(out, ctx->acc.p, (size_t)ctx->acc_L * ctx->acc_nw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
+int ansfm_lbl_accum_device_ptr(ansfm_ctx *ctx, double **dev, int *L, int *nw)
+{
+    CHECK_CTX(ctx);
+    if (ctx->acc_nw <= 0) FAIL(ANSFM_ERR_INVALID, "lbl_accum_device_ptr: call ansfm_lbl_accum_begin first");
+    if (!dev) FAIL(ANSFM_ERR_INVALID, "lbl_accum_device_ptr: bad argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the caller may read the buffer from another stream
+    *dev = ctx->acc.as<double>();
+    if (L) *L = ctx->acc_L;
+    if (nw) *nw = ctx->acc_nw;
     return ANSFM_OK;
 }
 

@@ -130,6 +130,50 @@ struct LblParams {
     double t_ref, p_ref, iso_abundance, iso_mass, s_floor, wn_calc_window, wn_approx_window, max_shift;
 };
 
+// The parameter expressions of LineData_0.py: line_strength :206 (stim_ref = the stimulated-emission factor at t_ref),
+// doppler_width :144, lorentz_width :159 with line_shift :189 -- shared by the line kernel and the pseudo-continuum of the
+// weak lines, same association as the reference's expressions
+struct LblTp {
+    double c2_cgs, boltz, dconst, t_ratio, p_ratio;
+};
+
+__device__ __forceinline__ LblTp lbl_tp(double t_calc, double t_ref, double p_calc, double p_ref)
+{
+    const double c_light_cgs = 2.99792458E10, h_planck_cgs = 6.62607015E-27, k_boltzmann_cgs = 1.380649E-16,
+                 N_avogadro = 6.02214129E+23;
+    LblTp c;
+    c.c2_cgs = c_light_cgs * h_planck_cgs / k_boltzmann_cgs;
+    c.boltz = c.c2_cgs * (t_calc - t_ref) / (t_calc * t_ref);
+    c.dconst = (1.0 / c_light_cgs) * sqrt(2 * log(2.0) * N_avogadro * k_boltzmann_cgs);
+    c.t_ratio = t_ref / t_calc;
+    c.p_ratio = p_calc / p_ref;
+    return c;
+}
+
+__device__ __forceinline__ double lbl_strength(const LblTp &c, double t_calc, double q_ratio, double nu, double sw,
+                                               double e_lower, double stim_ref)
+{
+    return sw * ((1 - exp(-c.c2_cgs * nu / t_calc)) / stim_ref) * exp(c.boltz * e_lower) * q_ratio;
+}
+
+__device__ __forceinline__ double lbl_doppler_width(const LblTp &c, double t_calc, double iso_mass, double nu)
+{
+    return c.dconst * nu * sqrt(t_calc / iso_mass);
+}
+
+// bparams[3M][N]: (gamma, n, delta) per broadener; *shift = the pressure shift of column i
+__device__ __forceinline__ double lbl_lorentz_width(const LblTp &c, const double *bparams, const double *mmf, int M, int N,
+                                                    int i, double *shift)
+{
+    double g = 0, sh = 0;
+    for (int j = 0; j < M; ++j) {
+        g += (pow(c.t_ratio, bparams[(size_t)(3 * j + 1) * N + i])) * bparams[(size_t)(3 * j) * N + i] * mmf[j] * c.p_ratio;
+        sh += (c.p_ratio * bparams[(size_t)(3 * j + 2) * N + i]) * mmf[j];
+    }
+    *shift = sh;
+    return g;
+}
+
 // per (layer, line): strength, alpha_d, gamma_l, shift exactly as the reference fills them (:306-341) + the wing term's
 // numerator (:261, :270)
 __global__ void k_lbl_line_params(LblParams p)
@@ -137,21 +181,13 @@ __global__ void k_lbl_line_params(LblParams p)
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)p.L * p.N) return;
     const int i = (int)(idx % p.N), l = (int)(idx / p.N);
-    const double c_light_cgs = 2.99792458E10, h_planck_cgs = 6.62607015E-27, k_boltzmann_cgs = 1.380649E-16,
-                 N_avogadro = 6.02214129E+23;
-    const double c2_cgs = c_light_cgs * h_planck_cgs / k_boltzmann_cgs;
-    const double t_calc = p.t_calc[l], p_calc = p.p_calc[l];
-    const double boltz = c2_cgs * (t_calc - p.t_ref) / (t_calc * p.t_ref);
-    const double dconst = (1.0 / c_light_cgs) * sqrt(2 * log(2.0) * N_avogadro * k_boltzmann_cgs);
-    const double t_ratio = p.t_ref / t_calc, p_ratio = p_calc / p.p_ref;
+    const double t_calc = p.t_calc[l];
+    const LblTp c = lbl_tp(t_calc, p.t_ref, p.p_calc[l], p.p_ref);
     const double nu = p.nu[i];
-    const double strength = p.sw[i] * ((1 - exp(-c2_cgs * nu / t_calc)) / p.stim_ref[i]) * exp(boltz * p.e_lower[i]) * p.q_ratio[l];
-    const double alpha_d = dconst * nu * sqrt(t_calc / p.iso_mass);
-    double g = 0, sh = 0;
-    for (int j = 0; j < p.M; ++j) {
-        g += (pow(t_ratio, p.bparams[(size_t)(3 * j + 1) * p.N + i])) * p.bparams[(size_t)(3 * j) * p.N + i] * p.mmf[j] * p_ratio;
-        sh += (p_ratio * p.bparams[(size_t)(3 * j + 2) * p.N + i]) * p.mmf[j];
-    }
+    const double strength = lbl_strength(c, t_calc, p.q_ratio[l], nu, p.sw[i], p.e_lower[i], p.stim_ref[i]);
+    const double alpha_d = lbl_doppler_width(c, t_calc, p.iso_mass, nu);
+    double sh;
+    const double g = lbl_lorentz_width(c, p.bparams, p.mmf, p.M, p.N, i, &sh);
     double *st = p.store + ((size_t)l * p.N + i) * kLblRows;      // one line's constants are contiguous (64 bytes)
     st[0] = strength;
     st[1] = nu + sh;                                              // :264

@@ -39,6 +39,23 @@ def _fingerprint(a):
     return (a.ctypes.data, a.shape, a.strides, flat[idx].tobytes())
 
 
+class _PcArgs:
+    """the per-isotopologue arrays of a pseudo-continuum call, contiguous float64 and checked against each other"""
+
+    def __init__(self, L, q_ratio, mol_mix_frac, bparams, centers, widths, sw_sum, e_lower, store, store_x):
+        self.q = _np(np.atleast_1d(q_ratio)); self.mmf = _np(mol_mix_frac); self.bp = _np(bparams)
+        self.c = _np(centers); self.w = _np(widths); self.sw = _np(sw_sum); self.el = _np(e_lower)
+        self.N = N = self.c.shape[0]; self.M = M = self.mmf.shape[0]
+        if self.q.shape != (L,):
+            raise ValueError("q_ratio must have one value per (T,p) point")
+        if self.bp.size != 3 * M * N or any(a.shape != (N,) for a in (self.w, self.sw, self.el)):
+            raise ValueError("bin arrays must have shape (N,) and the broadening parameters (3M,N)")
+        if store is not None and (store.dtype != np.float64 or not store.flags.c_contiguous or store.size != L * 3 * N):
+            raise ValueError("store must be a C-contiguous float64 array of shape (3,N) or (L,3,N)")
+        if store_x is not None and (store_x.dtype != np.float64 or not store_x.flags.c_contiguous or store_x.size != L * N):
+            raise ValueError("store_x must be a C-contiguous float64 array of shape (N,) or (L,N)")
+
+
 class AnsfmEngine:
     def __init__(self, device=0):
         self._lib = _lib.load()
@@ -681,6 +698,34 @@ class AnsfmEngine:
         self._check(rc, "add_line_set_monochromatic_absorption")
         return out
 
+    def add_pseudo_continuum_monochromatic_absorption(self, wn_grid, lineshape_id, t_calc, t_ref, p_calc, p_ref, q_ratio,
+                                                      isotopic_abundance, isotopic_mass, mol_mix_frac,
+                                                      lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum,
+                                                      lsw_mean_e_lower, out, store=None, store_x=None, n_neighbour_bins=3):
+        """LineData_0.add_pseudo_continuum_monochromatic_absorption (:486): the pseudo-continuum of the weak lines.  Scalars
+        t_calc/p_calc/q_ratio = the reference call (out (nw,), store (3,N), store_x (N,)); 1-D arrays of length L = batched
+        over (T,p) points (out (L,nw), store (L,3,N), store_x (L,N)).  `out` (float64, C-contiguous) is added to in place
+        and returned.  The lower bin edges must be ascending (ValueError otherwise); the reference's store_y / store_z
+        scratch arrays are not part of the call."""
+        wn_grid = _np(wn_grid)
+        t = _np(np.atleast_1d(t_calc)); p = _np(np.atleast_1d(p_calc))
+        L = t.shape[0]
+        a = _PcArgs(L, q_ratio, mol_mix_frac, lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum,
+                     lsw_mean_e_lower, store, store_x)
+        if out.dtype != np.float64 or not out.flags.c_contiguous or out.size != L * wn_grid.shape[0]:
+            raise ValueError("out must be a C-contiguous float64 array of shape (nw,) or (L,nw)")
+        rc = self._lib.ansfm_add_pseudo_continuum_monochromatic_absorption(
+            self._ctx, wn_grid.shape[0], _ptr(wn_grid), int(lineshape_id), L, _ptr(t), float(t_ref), _ptr(p), float(p_ref),
+            _ptr(a.q), float(isotopic_abundance), float(isotopic_mass), a.M, _ptr(a.mmf), a.N, _ptr(a.bp), _ptr(a.c), _ptr(a.w),
+            _ptr(a.sw), _ptr(a.el), _ptr(out), _ptr(store), _ptr(store_x), int(n_neighbour_bins))
+        self._check(rc, "add_pseudo_continuum_monochromatic_absorption")
+        return out
+
+    def lbl_accumulator(self, wn_grid, t_calc, p_calc):
+        """The runtime line-by-line opacity of a gas summed in HBM: a zeroed (L, nw) accumulator on this engine's device for
+        the grid and the (T,p) points given (see LblAccumulator).  The engine owns one; a new one starts over."""
+        return LblAccumulator(self, wn_grid, t_calc, p_calc)
+
     def layer_average(self, RADIUS, H, P, T, ID, VMR, DUST, PARAH2, BASEH, BASEP=None, LAYANG=0.0, LAYINT=0, LAYHT=0.0,
                       NINT=101, DUST_UNITS=None, XMOLWT=None):
         """Layer_0.layer_average (:755), same argument order (ID and BASEP are unused there too).  A leading
@@ -1070,3 +1115,87 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_last_kernel_ms(self._ctx, C.byref(a), C.byref(na), C.byref(b), C.byref(nb)),
                     "last_kernel_ms")
         return {"overlap_ms": a.value, "overlap_launches": na.value, "rt_ms": b.value, "rt_launches": nb.value}
+
+
+class _DeviceArray:
+    """a device buffer described by the CUDA array interface, so that torch.as_tensor views it without a copy"""
+
+    def __init__(self, ptr, shape, owner):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
+
+
+class LblAccumulator:
+    """The runtime line-by-line opacity of a gas, summed over its isotopologues in HBM (ansfm_lbl_accum_*): the grid and the
+    (T,p) points go up once, every add leaves its term on the device, and the (L, nw) sum comes back once -- `numpy()` -- or
+    stays there -- `torch()`.  The adds run the kernels of AnsfmEngine.add_line_set_monochromatic_absorption and
+    add_pseudo_continuum_monochromatic_absorption and take their arguments without wn_grid, t_calc, p_calc and out: the
+    sum equals the same calls on a zeroed host `out`, bit for bit.  The buffer belongs to the engine's context; the engine's
+    next accumulator starts over in it, and this object then raises ValueError."""
+
+    def __init__(self, eng, wn_grid, t_calc, p_calc):
+        self._eng = eng
+        wn_grid = _np(wn_grid); t = _np(np.atleast_1d(t_calc)); p = _np(np.atleast_1d(p_calc))
+        if t.shape != p.shape or t.ndim != 1:
+            raise ValueError("t_calc and p_calc must be 1-D arrays of one length")
+        self.L, self.nw = t.shape[0], wn_grid.shape[0]
+        eng._check(eng._lib.ansfm_lbl_accum_begin(eng._ctx, self.nw, _ptr(wn_grid), self.L, _ptr(t), _ptr(p)), "lbl_accum_begin")
+        eng._lbl_accumulator = self
+
+    def _live(self):
+        if getattr(self._eng, "_lbl_accumulator", None) is not self:
+            raise ValueError("this accumulator was replaced by a newer one of the same engine")
+
+    def add_lines(self, lineshape_id, t_ref, p_ref, q_ratio, isotopic_abundance, isotopic_mass, mol_mix_frac,
+                  broadening_params, nu, sw, e_lower, stimulated_emission_at_t_ref, store=None, s_floor=0.0,
+                  wn_calc_window=25.0, wn_approx_window=75.0):
+        self._live()
+        eng = self._eng
+        q = _np(np.atleast_1d(q_ratio)); mmf = _np(mol_mix_frac); nu = _np(nu)
+        N, M = nu.shape[0], mmf.shape[0]
+        if q.shape != (self.L,):
+            raise ValueError("q_ratio must have one value per (T,p) point")
+        if store is not None and (store.dtype != np.float64 or not store.flags.c_contiguous or store.size != self.L * 4 * N):
+            raise ValueError("store must be a C-contiguous float64 array of shape (L,4,N)")
+        rc = eng._lib.ansfm_lbl_accum_add_lines(
+            eng._ctx, int(lineshape_id), float(t_ref), float(p_ref), _ptr(q), float(isotopic_abundance), float(isotopic_mass), M,
+            _ptr(mmf), N, _ptr(_np(broadening_params)), _ptr(nu), _ptr(_np(sw)), _ptr(_np(e_lower)),
+            _ptr(_np(stimulated_emission_at_t_ref)), _ptr(store), float(s_floor), float(wn_calc_window), float(wn_approx_window))
+        eng._check(rc, "lbl_accum_add_lines")
+        return self
+
+    def add_pseudo_continuum(self, lineshape_id, t_ref, p_ref, q_ratio, isotopic_abundance, isotopic_mass, mol_mix_frac,
+                             lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum, lsw_mean_e_lower, store=None,
+                             store_x=None, n_neighbour_bins=3):
+        self._live()
+        eng = self._eng
+        a = _PcArgs(self.L, q_ratio, mol_mix_frac, lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum,
+                     lsw_mean_e_lower, store, store_x)
+        rc = eng._lib.ansfm_lbl_accum_add_pseudo_continuum(
+            eng._ctx, int(lineshape_id), float(t_ref), float(p_ref), _ptr(a.q), float(isotopic_abundance), float(isotopic_mass),
+            a.M, _ptr(a.mmf), a.N, _ptr(a.bp), _ptr(a.c), _ptr(a.w), _ptr(a.sw), _ptr(a.el), _ptr(store), _ptr(store_x),
+            int(n_neighbour_bins))
+        eng._check(rc, "lbl_accum_add_pseudo_continuum")
+        return self
+
+    def numpy(self):
+        """the sum as a new (L, nw) host array"""
+        self._live()
+        out = np.empty((self.L, self.nw))
+        self._eng._check(self._eng._lib.ansfm_lbl_accum_read(self._eng._ctx, _ptr(out)), "lbl_accum_read")
+        return out
+
+    def device_ptr(self):
+        """address of the (L, nw) float64 buffer in HBM, after the adds queued so far have finished"""
+        self._live()
+        ptr = C.c_void_p(); L = C.c_int(); nw = C.c_int()
+        self._eng._check(self._eng._lib.ansfm_lbl_accum_device_ptr(self._eng._ctx, C.byref(ptr), C.byref(L), C.byref(nw)),
+                         "lbl_accum_device_ptr")
+        return int(ptr.value)
+
+    def torch(self):
+        """the buffer itself as a torch tensor (L, nw) on the engine's device: no copy, so a later add shows in it (once the
+        engine's stream has finished it: `eng.synchronize()`), and it is valid only until the engine's next accumulator"""
+        import torch
+        return torch.as_tensor(_DeviceArray(self.device_ptr(), (self.L, self.nw), self), device="cuda:%d" % self._eng.device)

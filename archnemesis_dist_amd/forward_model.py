@@ -610,6 +610,62 @@ def install_gpu_line_kernel(device=0):
     return add_line_set_monochromatic_absorption
 
 
+PC_MAX_NEIGHBOUR_BINS = 8              # kPcMaxNeighbours of the pseudo-continuum kernels
+
+
+def install_gpu_pseudo_continuum(device=0):
+    """Route LineData_0.add_pseudo_continuum_monochromatic_absorption (LineData_0.py:486; the class method resolves the
+    module attribute at call time, :1378) -- the pseudo-continuum of the weak lines, the second term of every default
+    runtime line-by-line opacity -- through the GPU.  To the reference's own function go: line shapes that are not built,
+    an `out` / `store` / `store_x` that is not a contiguous float64 array, bins whose lower edges are not ascending (or whose
+    widths are not positive), more than 8 neighbour bins, and `store_x is None` with fewer grid points than bins (where
+    the reference raises IndexError).  The reference's scratch arrays store_y / store_z are left as they are."""
+    import importlib
+    ld = importlib.import_module("archnemesis.LineData_0")
+    ls = importlib.import_module("archnemesis.lineshape")
+    eng = get_engine(device)
+    ref_fn = getattr(ld, "_ansfm_reference_pseudo_continuum", None) or ld.add_pseudo_continuum_monochromatic_absorption
+    ids = {id(ls.voigt): 0, id(ls.lorentz): 4, id(ls.gaussian): 12}
+
+    def _f8c(a, size):
+        return isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.size == size
+
+    def add_pseudo_continuum_monochromatic_absorption(wn_grid, lineshape_fn, t_calc, t_ref, p_calc, p_ref, q_ratio,
+                                                      isotopic_abundance, isotopic_mass, mol_mix_frac,
+                                                      lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum,
+                                                      lsw_mean_e_lower, out, store=None, store_x=None, store_y=None,
+                                                      store_z=None, n_neighbour_bins=3):
+        lid = ids.get(id(lineshape_fn))
+        c, w = np.asarray(wn_bin_centers, dtype=np.float64), np.asarray(wn_bin_widths, dtype=np.float64)
+        N, nw = c.shape[0], np.shape(wn_grid)[0]
+        why = None
+        if lid is None:
+            why = "line shape of add_pseudo_continuum_monochromatic_absorption"
+        elif not (_f8c(out, nw) and out.ndim == 1 and (store is None or _f8c(store, 3 * N))
+                  and (store_x is None or _f8c(store_x, N))):
+            why = "buffer layout of add_pseudo_continuum_monochromatic_absorption"
+        elif not (np.all(w > 0.0) and np.all(np.diff(c - w / 2.0) >= 0.0)):
+            why = "pseudo-continuum bins whose lower edges are not ascending"
+        elif int(n_neighbour_bins) > PC_MAX_NEIGHBOUR_BINS or int(n_neighbour_bins) < 0:
+            why = "pseudo-continuum with more than %d neighbour bins" % PC_MAX_NEIGHBOUR_BINS
+        elif store_x is None and nw < N:
+            why = "pseudo-continuum without store_x on a grid shorter than the bins"
+        if why is not None:
+            _delegate(why)
+            return ref_fn(wn_grid, lineshape_fn, t_calc, t_ref, p_calc, p_ref, q_ratio, isotopic_abundance, isotopic_mass,
+                          mol_mix_frac, lsw_mean_broadening_params, wn_bin_centers, wn_bin_widths, sw_sum, lsw_mean_e_lower,
+                          out, store, store_x, store_y, store_z, n_neighbour_bins)
+        eng.add_pseudo_continuum_monochromatic_absorption(wn_grid, lid, t_calc, t_ref, p_calc, p_ref, q_ratio,
+                                                          isotopic_abundance, isotopic_mass, mol_mix_frac,
+                                                          lsw_mean_broadening_params, c, w, sw_sum, lsw_mean_e_lower, out,
+                                                          store, store_x, int(n_neighbour_bins))
+        return
+
+    ld._ansfm_reference_pseudo_continuum = ref_fn
+    ld.add_pseudo_continuum_monochromatic_absorption = add_pseudo_continuum_monochromatic_absorption
+    return add_pseudo_continuum_monochromatic_absorption
+
+
 def install_gpu_gradient_maps(device=0):
     """Route ForwardModel_0.map2pro / map2xvec (ForwardModel_0.py:5319, :5387) -- the layer -> profile -> state-vector
     gradient maps nemesisfmg applies right after CIRSrad(return_grad=True) (:704-711) -- through the GPU.  The arrays
@@ -913,8 +969,8 @@ def install_all(device=0, oe_linalg=True, ktable_generator=True, forward_model=T
     done = Installed()
     if forward_model:
         install_gpu_forward_model(device); done.append("install_gpu_forward_model")
-    for f in (install_gpu_gradient_maps, install_gpu_scattering_core, install_gpu_line_kernel, install_gpu_layering,
-              install_gpu_convolution, install_gpu_continuum, install_gpu_table_reader):
+    for f in (install_gpu_gradient_maps, install_gpu_scattering_core, install_gpu_line_kernel, install_gpu_pseudo_continuum,
+              install_gpu_layering, install_gpu_convolution, install_gpu_continuum, install_gpu_table_reader):
         f(device); done.append(f.__name__)
     if oe_linalg:
         from .oe_linalg import install_gpu_oe_linalg

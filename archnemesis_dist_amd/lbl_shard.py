@@ -6,7 +6,12 @@ the lines whose +-wn_approx_window reaches it.  A rank that owns the grid points
 within the window of ITS range (plus the largest pressure shift); handing it that sub-list in the same order gives the
 same additions in the same order, i.e. the rank's slab is bit-identical to the same rows of the one-GPU result.  The slabs
 are brought together by one all_gather of the (layers, points_per_rank) blocks (RCCL over xGMI when the backend is nccl)
--- or left where they are when the next step (ILS convolution per rank) wants them there."""
+-- or left where they are when the next step (ILS convolution per rank) wants them there.
+
+Lines only: the pseudo-continuum of the weak lines (add_pseudo_continuum_monochromatic_absorption) is not sharded.  Which
+bins spread (`first`, `last`) and which grid point is the last to receive depend on the first and last point of the WHOLE
+grid, so a rank's slab of it is not the result of the same call on the rank's range; it costs milliseconds on one GPU
+ and is added there."""
 import numpy as np
 
 from .jacobian import chunk_range

@@ -113,3 +113,34 @@ def synth_profiles(NPRO, NVMR, seed=11, p_bottom_bar=10.0, p_top_bar=1.0e-6):
     VMR[:, 1] = 0.136 * rest
     return dict(H=H, P=p_bar * 1.0e5, T=T, VMR=VMR, ID=PROFILE_GAS_ID[:NVMR].copy(), ISO=np.zeros(NVMR, dtype=np.int32),
                 RADIUS=7.1492e7)
+
+
+def synth_lbl_gas(wn_lo, wn_hi, n_iso, lines, L, seed=0, bin_width=1.0, margin=150.0):
+    """Runtime line-by-line data of a synthetic gas of n_iso isotopologues between wn_lo and wn_hi (cm-1): per isotopologue
+    `lines` strong lines and the weak-line bins of width bin_width, both out to `margin` beyond the interval, one broadener.
+    Returns a list of (line_args, continuum_args): the arguments of AnsfmEngine.add_line_set_monochromatic_absorption from
+    t_ref on without p_calc (lineshape_id first) and of add_pseudo_continuum_monochromatic_absorption likewise -- what
+    LblAccumulator.add_lines / add_pseudo_continuum take."""
+    rng = np.random.default_rng(seed)
+    c2 = 2.99792458E10 * 6.62607015E-27 / 1.380649E-16
+    t_ref, p_ref, mmf = 296.0, 1.0, np.array([1.0])
+    nbin = int(round((wn_hi - wn_lo + 2 * margin) / bin_width))
+    centers = wn_lo - margin + bin_width * (np.arange(nbin) + 0.5)
+    widths = np.full(nbin, float(bin_width))
+
+    def broadening(n):
+        bp = np.zeros((3, n))
+        bp[0] = rng.uniform(0.02, 0.1, n); bp[1] = rng.uniform(0.5, 0.8, n); bp[2] = rng.uniform(-0.01, 0.01, n)
+        return bp
+
+    out = []
+    for iso in range(n_iso):
+        abundance, mass = (0.98, 0.011, 0.004, 0.002)[iso % 4], 28.0 + iso
+        q = np.linspace(1.8, 1.0, L) * (1.0 + 0.05 * iso)
+        nu = np.sort(rng.uniform(wn_lo - 75.0, wn_hi + 75.0, lines))
+        line_args = (0, t_ref, p_ref, q, abundance, mass, mmf, broadening(lines), nu, 10.0 ** rng.uniform(-28, -19, lines),
+                     rng.uniform(0, 3000, lines), 1 - np.exp(-c2 * nu / t_ref))
+        cont_args = (0, t_ref, p_ref, q, abundance, mass, mmf, broadening(nbin), centers, widths,
+                     10.0 ** rng.uniform(-27, -23, nbin), rng.uniform(0, 3000, nbin))
+        out.append((line_args, cont_args))
+    return out

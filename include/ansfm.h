@@ -424,6 +424,43 @@ int ansfm_add_line_set_monochromatic_absorption(
     const double *nu, const double *sw, const double *e_lower, const double *stim_ref, double *out,
     double *store, double s_floor, double wn_calc_window, double wn_approx_window);
 
+/* LineData_0.add_pseudo_continuum_monochromatic_absorption (LineData_0.py:486-572): the pseudo-continuum of the weak
+ * lines in N bins, batched over L (T,p) points like the line entry (same line shapes, same error codes).  The
+ * stimulated-emission factor at t_ref is computed at the bin centres; there is no pressure shift.
+ *   lsw_mean_broadening_params[3M][N]; wn_bin_centers/wn_bin_widths/sw_sum/lsw_mean_e_lower[N];
+ *   out[L][nw] is ADDED to; store[L][3][N] (strength, alpha_d, gamma_l) or NULL; store_x[L][N] (the spread continuum per
+ *   unit wavenumber) or NULL.  The reference's scratch arrays store_y / store_z are not filled: they hold the last source
+ *   bin's shapes and the interpolation's sums and counts, which no caller reads.
+ *   n_neighbour_bins 0 .. 8 (the reference's call sites pass 3); more -> ANSFM_ERR_UNSUPPORTED.
+ * The widths must be positive and the lower edges centre - width/2 ascending (the reference's j_start shortcut
+ * :451-457 equals the plain definition of a touched grid point exactly then), else ANSFM_ERR_INVALID, as for a descending
+ * grid.  N == 0 is a no-op. */
+int ansfm_add_pseudo_continuum_monochromatic_absorption(
+    ansfm_ctx *ctx, int nw, const double *wn_grid, int lineshape_id, int L, const double *t_calc, double t_ref,
+    const double *p_calc, double p_ref, const double *q_ratio, double isotopic_abundance,
+    double isotopic_mass, int M, const double *mol_mix_frac, int N, const double *lsw_mean_broadening_params,
+    const double *wn_bin_centers, const double *wn_bin_widths, const double *sw_sum, const double *lsw_mean_e_lower,
+    double *out, double *store, double *store_x, int n_neighbour_bins);
+
+/* The opacity of a gas summed in HBM: the context owns a zeroed [L][nw] accumulator between `begin` and the next `begin`.
+ * The two add calls take the arguments of the host entries without grid, (T,p) points and `out`, run the same kernels and
+ * leave the sum on the device: after any sequence of adds it equals the same sequence of host-`out` calls started from
+ * zeros, bit for bit.  An add, read or device_ptr before begin -> ANSFM_ERR_INVALID; a second begin starts over.
+ * device_ptr: the buffer ([*L][*nw] float64, valid until the next begin or ansfm_destroy), synchronised. */
+int ansfm_lbl_accum_begin(ansfm_ctx *ctx, int nw, const double *wn_grid, int L, const double *t_calc, const double *p_calc);
+int ansfm_lbl_accum_add_lines(ansfm_ctx *ctx, int lineshape_id, double t_ref, double p_ref, const double *q_ratio,
+                              double isotopic_abundance, double isotopic_mass, int M, const double *mol_mix_frac, int N,
+                              const double *broadening_params, const double *nu, const double *sw, const double *e_lower,
+                              const double *stim_ref, double *store, double s_floor, double wn_calc_window,
+                              double wn_approx_window);
+int ansfm_lbl_accum_add_pseudo_continuum(ansfm_ctx *ctx, int lineshape_id, double t_ref, double p_ref, const double *q_ratio,
+                                         double isotopic_abundance, double isotopic_mass, int M, const double *mol_mix_frac,
+                                         int N, const double *lsw_mean_broadening_params, const double *wn_bin_centers,
+                                         const double *wn_bin_widths, const double *sw_sum, const double *lsw_mean_e_lower,
+                                         double *store, double *store_x, int n_neighbour_bins);
+int ansfm_lbl_accum_read(ansfm_ctx *ctx, double *out);
+int ansfm_lbl_accum_device_ptr(ansfm_ctx *ctx, double **dev, int *L, int *nw);
+
 /* ---- layering ---------------------------------------------------------------------------------------
  * Layer_0.layer_average (Layer_0.py:755-1030), batched over n_models atmospheric states (the states of a
  * numerical Jacobian): LAYINT 0 = MID_PATH, 1 = ABSORBER_WEIGHTED_AVERAGE (Curtis-Godson, :949-1010).

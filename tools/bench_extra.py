@@ -30,6 +30,8 @@ def main():
         bench_lbl(eng, out, rng)
     if only == "lbl_c5":
         bench_lbl(eng, out, rng, full=True)
+    if only == "lbl_pc":                                    # C5 size: 400 MB of opacities per host array, on request only
+        bench_lbl_pc(eng, out)
     if only in (None, "layer"):
         bench_layer(eng, out)
     if only in (None, "maps"):
@@ -240,6 +242,48 @@ def bench_lbl(eng, out, rng, full=False):
     evals = float(N) * (150.0 / 1e-3) * Ll * (span / (span + 150.0))     # lines whose window overlaps the grid, roughly
     out["lbl_runtime_C5" if full else "lbl_runtime_reducedC5"] = {"wall_s": t, "grid": nw, "lines": N, "layers": Ll, "approx_profile_evals": evals,
                                     "Gevals_per_s": evals / t / 1e9}
+
+
+def bench_lbl_pc(eng, out, nw=1000000, Ll=50, lines=100000, n_iso=3, n=5):
+    """the pseudo-continuum of the weak lines at C5 size (1e6 points x 50 layers, 1 cm-1 bins over the grid +- 150 cm-1) beside
+    the line call of the same process, and a gas of three isotopologues (lines + pseudo-continuum each) through the
+    accumulator against the same six host-array calls; medians of n after one warm-up"""
+    if len(sys.argv) > 2:                                    # reduced sizes for a quick look: lbl_pc <points> <layers>
+        nw, Ll = int(sys.argv[2]), int(sys.argv[3])
+        lines = max(nw // 10, 100)
+    wn = 2000.0 + 1e-3 * np.arange(nw)
+    tt = np.linspace(150, 300, Ll); pp = np.logspace(-4, 0, Ll)
+    gas = syn.synth_lbl_gas(wn[0], wn[-1], n_iso, lines, Ll, seed=0)
+    o = np.zeros((Ll, nw))
+    ln, ct = gas[0]
+    t_pc = timeit(lambda: eng.add_pseudo_continuum_monochromatic_absorption(wn, ct[0], tt, ct[1], pp, *ct[2:], o), n)
+    t_ln = timeit(lambda: eng.add_line_set_monochromatic_absorption(wn, ln[0], tt, ln[1], pp, *ln[2:], o), n)
+
+    def host_chain():
+        o[...] = 0.0
+        for a, b in gas:
+            eng.add_line_set_monochromatic_absorption(wn, a[0], tt, a[1], pp, *a[2:], o)
+            eng.add_pseudo_continuum_monochromatic_absorption(wn, b[0], tt, b[1], pp, *b[2:], o)
+        return o
+
+    def accumulated(read=True):
+        acc = eng.lbl_accumulator(wn, tt, pp)
+        for a, b in gas:
+            acc.add_lines(*a)
+            acc.add_pseudo_continuum(*b)
+        if read:
+            return acc.numpy()
+        eng.synchronize()
+
+    t_host = timeit(host_chain, n)
+    t_acc = timeit(accumulated, n)
+    t_dev = timeit(lambda: accumulated(False), n)
+    same = bool(np.array_equal(accumulated(), host_chain()))
+    out["lbl_pc_C5" if (nw, Ll) == (1000000, 50) else "lbl_pc_reduced"] = {
+        "grid": nw, "layers": Ll, "bins": int(ct[8].size), "lines": lines, "isotopologues": n_iso, "median_of": n,
+        "pseudo_continuum_call_wall_s": t_pc, "line_call_wall_s": t_ln,
+        "gas_host_array_calls_wall_s": t_host, "gas_accumulator_wall_s": t_acc, "gas_accumulator_left_in_hbm_wall_s": t_dev,
+        "accumulator_equals_host_calls": same}
 
 
 def bench_layer(eng, out):
