@@ -33,6 +33,7 @@ EXPORTS = [
     "ansfm_cirsrad_ck_singlescatt_batch", "ansfm_cirsrad_ck_scatter_batch_rows",
     "ansfm_add_pseudo_continuum_monochromatic_absorption", "ansfm_lbl_accum_begin", "ansfm_lbl_accum_add_lines",
     "ansfm_lbl_accum_add_pseudo_continuum", "ansfm_lbl_accum_read", "ansfm_lbl_accum_device_ptr",
+    "ansfm_ktable_has_boxed",
 ]
 
 _lib = None
@@ -125,6 +126,7 @@ def load():
     lib.ansfm_upload_ktable.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.ansfm_upload_ktable_dev.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.ansfm_ktable_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(ci)]
+    lib.ansfm_ktable_has_boxed.argtypes = [vp, C.POINTER(ci)]
     lib.ansfm_calc_k.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.ansfm_k_overlap.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp]
     lib.ansfm_thermal_emission.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, cd, vp, vp, vp, cd, cd, vp]

@@ -61,6 +61,7 @@ struct ansfm_ctx {
     // k-table
     int W = 0, Wpad = 0, G = 0, NP = 0, NT = 0, S = 0;
     int monotone = 0;
+    int has_boxed = 1;        // some table entry is <= 0 or NaN (stored NaN-boxed, encode_lnk); 0 selects the box-free load path
     std::vector<double> h_wave, h_press, h_temp;   // host copies of the grids of the table in HBM
     DevBuf dcont_gas;                       // ansfm_set_shared_gas_gradient: [L][Wpad], consumed by the next cirsradg call
     int dcont_gas_L = 0;                    // 0: none pending
@@ -246,6 +247,7 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->W = W; ctx->Wpad = Wpad; ctx->G = G; ctx->NP = NP; ctx->NT = NT; ctx->S = S;
     ctx->monotone = (flag & 1) ? 0 : 1;
+    ctx->has_boxed = (flag & 2) ? 1 : 0;
     ctx->h_delg.assign(DELG, DELG + G);
     ctx->h_wave.assign(WAVE, WAVE + W); ctx->h_press.assign(PRESS, PRESS + NP); ctx->h_temp.assign(TEMP, TEMP + NT);
     ctx->have_table = true;
@@ -463,6 +465,7 @@ static int upload_table_files(ansfm_ctx *ctx, int S, const char *const *paths, d
     ctx->tmp_in.release();
     ctx->W = W; ctx->Wpad = Wpad; ctx->G = G; ctx->NP = NP; ctx->NT = NT; ctx->S = S;
     ctx->monotone = (flag & 1) ? 0 : 1;
+    ctx->has_boxed = (flag & 2) ? 1 : 0;
     ctx->h_delg = DELG; ctx->h_wave = WAVE; ctx->h_press = PRESS; ctx->h_temp = TEMP;
     ctx->have_table = true;
     ctx->is_lbl = lta ? 1 : 0; ctx->temp2d = (lta && hl.temp2d) ? 1 : 0;
@@ -499,6 +502,14 @@ int ansfm_ktable_info(const ansfm_ctx *ctx, int64_t dims[5], int *monotone)
     if (!ctx->have_table) return ANSFM_ERR_NOTABLE;
     if (dims) { dims[0] = ctx->W; dims[1] = ctx->G; dims[2] = ctx->NP; dims[3] = ctx->NT; dims[4] = ctx->S; }
     if (monotone) *monotone = ctx->monotone;
+    return ANSFM_OK;
+}
+
+int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed)
+{
+    if (!ctx || !has_boxed) return ANSFM_ERR_INVALID;
+    if (!ctx->have_table) return ANSFM_ERR_NOTABLE;
+    *has_boxed = ctx->has_boxed;
     return ANSFM_OK;
 }
 
@@ -546,6 +557,9 @@ static int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W,
         if (!(w00 < p.g_ord[1])) nodiv = false;
     }
     if (const char *ev = getenv("ANSFM_MERGE_WALK")) { if (!strcmp(ev, "records")) nodiv = false; }
+    // a table without a boxed entry is read without the box tests (fast path only; ANSFM_LOAD_BOXTESTS=1 keeps them)
+    bool nobox = kLoadNoBox && nodiv && !from_k && !ctx->has_boxed;
+    if (const char *ev = getenv("ANSFM_LOAD_BOXTESTS")) { if (ev[0] == '1') nobox = false; }
     bool keys32 = nodiv && ctx->merge_keys == 32;
     if (const char *ev = getenv("ANSFM_MERGE_KEYS")) { keys32 = nodiv && atoi(ev) == 32; }
     const size_t lds = keys32 ? (size_t)overlap32_lds_bytes(G, ctx->delg_f32 != 0)
@@ -568,7 +582,9 @@ static int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W,
     }
 #define LAUNCH_OV2(D, FK, W32)                                                                                      \
     do {                                                                                                            \
-        if (nodiv)                                                                                                  \
+        if (nodiv && nobox)                                                                                         \
+            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+        else if (nodiv)                                                                                             \
             hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
         else if (sorted)                                                                                            \
             hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p);  \

@@ -90,8 +90,8 @@ __global__ void k_layer_prep(int n_layers_total, const double *__restrict__ lay_
 // ------------------------------------------------------------------------------------------------
 // Table upload: K[W][G][NP][NT][S] (reference layout) -> lnK[NP][NT][S][G][Wpad].
 // For every g this is a transpose between w and q = (p, t, s): 64 x 64 tiles through LDS, reads coalesced along q,
-// writes coalesced along w.  k_table_check flags k < 0 / NaN or k decreasing in g (flag[0] |= 1), reading the source
-// coalesced as well (one thread per (w, q), g sequential).
+// writes coalesced along w.  k_table_check flags k < 0 / NaN or k decreasing in g (flag[0] |= 1) and any entry that
+// encode_lnk boxes, k <= 0 or NaN (flag[0] |= 2), reading the source coalesced as well (one thread per (w, q), g sequential).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_table_relayout(const double *__restrict__ K, double *__restrict__ lnK, int W,
                                                         int Wpad, int G, int Q)
@@ -117,14 +117,16 @@ __global__ void k_table_check(const double *__restrict__ K, int W, int G, int Q,
     const int q = (int)(idx % Q);
     const size_t w = idx / Q;
     const double *src = K + w * (size_t)G * Q + q;
-    bool bad = false;
+    bool bad = false, boxed = false;
     double prev = 0.0;
     for (int g = 0; g < G; ++g) {
         const double k = src[(size_t)g * Q];
         bad |= !(k >= 0.0) || (g > 0 && k < prev);
+        boxed |= !(k > 0.0);
         prev = k;
     }
     if (bad) atomicOr(flag, 1);
+    if (boxed) atomicOr(flag, 2);
 }
 
 // Array-level seam calc_k / calc_kg: writes the reference layout k[W][G][L][S] directly.
@@ -183,6 +185,25 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 // out as two wide stores.  Same-box comparisons: gradient kernel 25.7 -> 23.7 ms against six 8-byte rows; forward kernel
 // within +-1 % of five 8-byte rows and of three pairs (it is not store-bound at this level).  The gradient kernel's resolve rewrites the
 // pairs as (frac, 1/weight-sum) and (weight, code) for its replay passes.
+// Switches of the forward merge kernel's instruction trims (every one leaves the results bit for bit):
+//   kMergePeel      the last G - 1 steps of a merge pass over a shrinking list (merge_peel)
+//   kWalkOneOffset  merge_walk_nodiv keeps one running offset instead of two
+//   kMergeUnroll4   four steps per trip of the merge loop instead of two
+//   kLoadNoBox      tables without a boxed entry are interpolated without the box tests (interp_k_nobox)
+#ifndef ANSFM_MERGE_PEEL
+#define ANSFM_MERGE_PEEL 1
+#endif
+#ifndef ANSFM_WALK_ONE_OFFSET
+#define ANSFM_WALK_ONE_OFFSET 1
+#endif
+#ifndef ANSFM_MERGE_UNROLL4
+#define ANSFM_MERGE_UNROLL4 0
+#endif
+#ifndef ANSFM_LOAD_NOBOX
+#define ANSFM_LOAD_NOBOX 1
+#endif
+constexpr bool kMergePeel = ANSFM_MERGE_PEEL != 0, kWalkOneOffset = ANSFM_WALK_ONE_OFFSET != 0, kMergeUnroll4 = ANSFM_MERGE_UNROLL4 != 0,
+               kLoadNoBox = ANSFM_LOAD_NOBOX != 0;
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 constexpr unsigned kRecRow = 64u * 16u, kRecBin = 2u * kRecRow;
 
@@ -241,6 +262,7 @@ struct WalkState {
     double gd, kacc, sum1, gnext;
     unsigned roff;      // byte offset of this lane's first pair in the record of the bin being filled: ig * kRecBin + lane * 16
     unsigned gaddr;     // LDS byte address of GORD[ig + 1]
+    unsigned rbase;     // merge_walk_nodiv: lane * 8 - (address of GORD[1] << 6), see there (roff is unused in that walk)
 };
 __device__ __forceinline__ WalkState walk_begin(const double *GORD, int lane)
 {
@@ -249,6 +271,7 @@ __device__ __forceinline__ WalkState walk_begin(const double *GORD, int lane)
     ws.gaddr = lds_addr(GORD + 1);
     ws.gnext = lds_ld(ws.gaddr);
     ws.roff = (unsigned)lane * 16u;
+    ws.rbase = (unsigned)lane * 8u - (ws.gaddr << 6);
     return ws;
 }
 // number of bins closed so far
@@ -297,11 +320,22 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
     double kn = fma(cv, w, ws.kacc);
     const bool cross = (gdn >= ws.gnext);       // ordered: GORD[G+1] is NaN
     if (cross) {
-        gst<double>(rec, ws.roff, fma(ws.gnext - ws.gd, cv, ws.kacc));
-        kn = (gdn - ws.gnext) * cv;
-        ws.roff += kWave * 8u;
-        ws.gaddr += 8u;
-        ws.gnext = lds_ld(ws.gaddr);
+        if constexpr (kWalkOneOffset) {
+            // The closed bin's slot, ig * 512 + lane * 8, is formed from the one running offset the walk keeps (gaddr, +8 per
+            // bin; 512 = 8 << 6): one shift-add here, where a second running offset cost an add AND, as a second value that
+            // lives across the branch and the e0 / e1 ping-pong, a register copy at the end of the branch body.  The
+            // boundary is read at gaddr + 8 (an immediate offset of the LDS read) and gaddr is stepped in place last.
+            gst<double>(rec, (ws.gaddr << 6) + ws.rbase, fma(ws.gnext - ws.gd, cv, ws.kacc));
+            kn = (gdn - ws.gnext) * cv;
+            ws.gnext = lds_ld(ws.gaddr + 8u);
+            ws.gaddr += 8u;
+        } else {
+            gst<double>(rec, ws.roff, fma(ws.gnext - ws.gd, cv, ws.kacc));
+            kn = (gdn - ws.gnext) * cv;
+            ws.roff += kWave * 8u;
+            ws.gaddr += 8u;
+            ws.gnext = lds_ld(ws.gaddr);
+        }
     }
     ws.kacc = kn;
     ws.gd = gdn;
@@ -315,33 +349,40 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
 // (compile time, >= G; unused entries hold "huge" keys).
 // Returns the consumed element's (row, column) and whether it closed a bin, as 16 bits: the gradient kernel
 // records them and replays the sorted order for the gradient rows.
-template <int NR, bool W32, bool REC_CODE = false, bool SORTED = true, bool NODIV = false>
+template <int NR, bool W32, bool REC_CODE = false, bool SORTED = true, bool NODIV = false, int NP = NR>
 __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, MergeElem &en, WalkState &ws,
                                                int lane, const double *A, const double *B,
                                                const double *DG, const double *GORD, double *rec,
                                                const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
 {
+    static_assert(NP >= 1 && NP <= NR, "pass length");
     // 1. the popped row's next element x enters the list s_1 <= s_2 <= ... (s_0 was popped):
-    //        t_0 = min(x, s_1),   t_k = min(max(x, s_k), s_{k+1}),   t_{NR-1} = max(x, s_{NR-1})
+    //        t_0 = min(x, s_1),   t_k = min(max(x, s_k), s_{k+1}),   t_{NP-1} = max(x, s_{NP-1})
     //    -- every output independent of the others (no carry chain), in place in ascending k.
+    //    NP = pass length: the pass reads and writes R[0..NP) only, which is the full pass whenever R[NP..NR) hold nothing
+    //    but "huge" keys (see the peeled steps of k_ck_overlap for when that is known without looking).
     const double x = pack_key11(e.ai + e.bn, e.ci, e.np);
+    if constexpr (NP == 1) {
+        R[0] = x;                               // the last element's step: its row's next key is a sentinel, nothing follows
+    } else {
     asm("v_min_f64 %0, %1, %2" : "=v"(R[0]) : "v"(x), "v"(R[1]));
     // 2. fetch the operands of the new winner (LDS reads in flight during the rest of the pass and the walk)
     merge_fetch<W32, SORTED>(R[0], lane, A, B, DG, en, PA, PB);
     // 3. finish the insertion: every max first, then every min -- no result is consumed by a neighbouring instruction
     //    (6.40 -> 6.32 ms against blocks of 6, same box)
-    constexpr int kBlk = NR;
+    constexpr int kBlk = NP;
 #pragma unroll
-    for (int k0 = 1; k0 < NR - 1; k0 += kBlk) {
+    for (int k0 = 1; k0 < NP - 1; k0 += kBlk) {
         double mk[kBlk];
 #pragma unroll
         for (int j = 0; j < kBlk; ++j)
-            if (k0 + j < NR - 1) asm("v_max_f64 %0, %1, %2" : "=v"(mk[j]) : "v"(x), "v"(R[k0 + j]));
+            if (k0 + j < NP - 1) asm("v_max_f64 %0, %1, %2" : "=v"(mk[j]) : "v"(x), "v"(R[k0 + j]));
 #pragma unroll
         for (int j = 0; j < kBlk; ++j)
-            if (k0 + j < NR - 1) asm("v_min_f64 %0, %1, %2" : "=v"(R[k0 + j]) : "v"(mk[j]), "v"(R[k0 + j + 1]));
+            if (k0 + j < NP - 1) asm("v_min_f64 %0, %1, %2" : "=v"(R[k0 + j]) : "v"(mk[j]), "v"(R[k0 + j + 1]));
     }
-    asm("v_max_f64 %0, %1, %2" : "=v"(R[NR - 1]) : "v"(x), "v"(R[NR - 1]));
+    asm("v_max_f64 %0, %1, %2" : "=v"(R[NP - 1]) : "v"(x), "v"(R[NP - 1]));
+    }
     // 4. rank walk on the element just consumed
     bool cross;
     if constexpr (NODIV) cross = merge_walk_nodiv(e, ws, rec);
@@ -349,6 +390,38 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
     // step code of the gradient replay, 12 bits: row (0-4), column (5-9), "the element closed a bin" (10); kCodesPerWord of
     // them to a 64-bit word of the stream
     return (unsigned)(e.ci | ((e.np - 1) << 5) | (cross ? 0x400 : 0));
+}
+
+// The last G - 1 steps of a merge, with the list pass shrinking by one entry per step.
+//
+// Every row has exactly one entry in the list: the key of its next element, or -- once its last element has been popped --
+// the key formed from B[G] = "huge" (merge_fetch: an exhausted row re-enters as a sentinel, not as a live key).  The list is
+// sorted and every sentinel is above every live key, so the live keys are a prefix of it.  When step t (0-based) begins,
+// R[0] is element t itself and G*G - t elements are left including it; each live entry is the head of a different row with at
+// least one of them, so at most min(G, G*G - t) entries are live and R[j] is a sentinel for every j >= G*G - t.  Step t pops
+// R[0] and inserts x into R[1..): a pass over R[0 .. G*G - t) sees every live key, and what it leaves out it would have
+// reproduced (min / max of sentinels among themselves -- which sentinel ends where may differ, none is ever consumed).
+// The bound depends on t alone: no test, no ballot.  R[j] can first be dropped at step t = G*G - j, i.e. the steps
+// t <= G*G - G need all G entries and step t = G*G - NP, NP = G-1 ... 1, needs NP of them.  (Entries G .. NR-1 of a launch with
+// G < NR are sentinels from the start; the main loop still passes over them, its length being a template constant.)
+// The bodies are instantiated for NP = NR-1 ... 1 and the first NR - G of them are skipped (G is wave-uniform).  Which of
+// e0 / e1 holds the current element alternates per step; the caller hands it over in e1 when G and NR have the same parity
+// and in e0 when not (swap_elems), so the choice is a compile-time one here.
+template <int NP, int NR, bool W32, bool SORTED, bool NODIV>
+__device__ __forceinline__ void merge_peel(double (&R)[NR], MergeElem &e0, MergeElem &e1, WalkState &ws, int G,
+                                           int lane, const double *A, const double *B, const double *DG,
+                                           const double *GORD, double *rec, const unsigned char *PA,
+                                           const unsigned char *PB)
+{
+    if constexpr (NP >= 1) {
+        if (NP < G) {
+            if constexpr (((NR - NP) & 1) != 0)
+                merge_step<NR, W32, false, SORTED, NODIV, NP>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+            else
+                merge_step<NR, W32, false, SORTED, NODIV, NP>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+        }
+        merge_peel<NP - 1, NR, W32, SORTED, NODIV>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+    }
 }
 
 // R[i] = head of row i = a_i + b_0: ascending in i when a is.  A loaded gas is (fast path: by precondition; generic: sorted
@@ -404,7 +477,8 @@ __device__ __forceinline__ void sort_column(double *X, unsigned char *P, int G, 
 // (product, weight) is unchanged, so rank()'s walk sees the same sequence up to the order of exact ties -- and the
 // skip rules keep looking at the LAST g-ordinate in the original order (:6075-6102).  A spectrum that passes through
 // unmerged comes out in its original order.
-template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false>
+// NOBOX: the table was found free of boxed entries at upload, load_gas interpolates without the box tests.
+template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_ck_overlap(OverlapParams p)
 {
     extern __shared__ double smem[];
@@ -442,11 +516,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
         if constexpr (!FROM_K) q = p.li[(size_t)m * p.L + l];
         bool unsorted = false;
 
-        load_gas<FROM_K>(p, q, m, l, 0, nu, A, lane, unsorted);
+        load_gas<FROM_K, false, NOBOX>(p, q, m, l, 0, nu, A, lane, unsorted);
         double alast = A[(G - 1) * kWave + lane];       // last g-ordinate in the ORIGINAL order
         if constexpr (!SORTED) sort_column(A, PA, G, lane);
         for (int s = 1; s < p.S; ++s) {
-            load_gas<FROM_K>(p, q, m, l, s, nu, B, lane, unsorted);
+            load_gas<FROM_K, false, NOBOX>(p, q, m, l, s, nu, B, lane, unsorted);
             if constexpr (SORTED)                       // the call is rerun on the generic path: no point in merging
                 if (__builtin_amdgcn_ballot_w64(unsorted) != 0) break;
             const double blast = B[(G - 1) * kWave + lane];
@@ -472,13 +546,29 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
                 merge_fetch<W32, SORTED>(R[0], lane, A, B, DG, e0, PA, PB);
                 WalkState ws = walk_begin(GORD, lane);
                 if constexpr (NODIV) ws.roff = (unsigned)lane * 8u;
-                const int nloop = G * G;
-                int it = 0;
-                for (; it + 1 < nloop; it += 2) {   // ping-pong: no register rotation
+                // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
+                const int nloop = kMergePeel ? G * G - (G - 1) : G * G;
+                // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
+                constexpr int kPer = kMergeUnroll4 ? 4 : 2;
+                for (int n = nloop / kPer; n > 0; --n) {
                     merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
                     merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    if constexpr (kMergeUnroll4) {
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    }
                 }
-                if (it < nloop) merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                if constexpr (kMergeUnroll4)
+                    if ((nloop & 2) != 0) {
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    }
+                if (kMergePeel || (nloop & 1) != 0)
+                    merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                if constexpr (kMergePeel) {
+                    if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
+                    merge_peel<NR - 1, NR, W32, SORTED, NODIV>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+                }
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
                     const int ig = walk_bins(ws, GORD);
@@ -1077,7 +1167,8 @@ __global__ void k_dk_to_ref(const double *__restrict__ src, double *__restrict__
 // ------------------------------------------------------------------------------------------------
 // .kta file block -> lnK.  The file stores k * 1e20 as float32 in the order [wave][press][temp][g] (Spectroscopy_0
 // .read_ktable :2829-2850); the reader divides the float32 array by the Python float 1e20, which NumPy does in float32.
-// One gas per launch: kf = the selected wavenumbers' block, as read.  Pad lanes (w >= W) get k = 0.
+// One gas per launch: kf = the selected wavenumbers' block, as read.  Pad lanes (w >= W) get k = 0.  flag[0] |= 1: an entry
+// < 0 / NaN or decreasing in g; |= 2: an entry that encode_lnk boxes (k <= 0 or NaN).
 // ------------------------------------------------------------------------------------------------
 __global__ void k_kta_relayout(const float *__restrict__ kf, double *__restrict__ lnK, int W, int Wpad, int G, int NP,
                                int NT, int S, int s, int *flag)
@@ -1098,6 +1189,7 @@ __global__ void k_kta_relayout(const float *__restrict__ kf, double *__restrict_
         bool bad = !(k >= 0.0);
         if (g > 0 && q < kf[src - 1] / 1.0e20f) bad = true;
         if (bad) atomicOr(flag, 1);
+        if (!(k > 0.0)) atomicOr(flag, 2);          // a boxed entry (pad lanes do not count)
     }
     lnK[((((size_t)p * NT + t) * S + s) * G + g) * Wpad + w] = encode_lnk(k);
 }

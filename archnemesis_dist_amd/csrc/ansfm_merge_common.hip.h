@@ -40,6 +40,15 @@ struct LayerInterp {
 };
 
 
+// The bilinear form in ln k of the merge kernels' table reads, (1-v)(1-u) l1 + v(1-u) h1 + v u h2 + (1-v) u l2, with the
+// multiply-adds written out: left to the compiler's contraction, the sum of four products came out in different orders in
+// interp_k and in interp_k_nobox (which product is the plain multiply), i.e. with different last bits.  The order is the
+// one the compiler had chosen for interp_k.
+__device__ __forceinline__ double interp_lnk(double l1, double l2, double h1, double h2, double v, double u)
+{
+    return fma((1.0 - v) * u, l2, fma(v * u, h2, fma((1.0 - v) * (1.0 - u), l1, (v * (1.0 - u)) * h1)));
+}
+
 // k for one (corner set, u, v): Spectroscopy_0.py:2391-2403 (+ dk/dT :2241-2247 when wanted)
 __device__ __forceinline__ double interp_k(double l1, double l2, double h1, double h2, double v,
                                            double u)
@@ -48,12 +57,25 @@ __device__ __forceinline__ double interp_k(double l1, double l2, double h1, doub
     bool b1 = lnk_is_boxed(l1), b2 = lnk_is_boxed(l2), b3 = lnk_is_boxed(h1), b4 = lnk_is_boxed(h2);
     double kk = 0.0;
     if (!(b1 | b2 | b3 | b4)) {
-        double x = (1.0 - v) * (1.0 - u) * l1 + v * (1.0 - u) * h1 + v * u * h2 + (1.0 - v) * u * l2;
+        const double x = interp_lnk(l1, l2, h1, h2, v, u);
         kk = exp(x);
     } else if (b1 & b2 & b3 & b4) {
         double klo1 = lnk_unbox(l1), klo2 = lnk_unbox(l2), khi1 = lnk_unbox(h1), khi2 = lnk_unbox(h2);
         kk = (1.0 - v) * (1.0 - u) * klo1 + v * (1.0 - u) * khi1 + v * u * khi2 + (1.0 - v) * u * klo2;
     }
+    return kk;
+}
+// interp_k for a table without a boxed entry (OverlapParams / ansfm_ktable_has_boxed: none of its W * G * NP * NT * S values
+// is <= 0 or NaN): only the first branch of interp_k can be taken, so the four tests, their reduction and the two exec-mask
+// regions go -- interp_lnk and exp() are interp_k's, the result is the same double.  The pad lanes of the last
+// wavenumber tile (w >= W) still hold the boxed 0 the relayout kernels write there: x and exp(x) are NaN in them and one
+// v_max_f64 against 0 returns the 0 that interp_k gives (the instruction returns its other operand for a NaN; exp() of a
+// real entry is > 0 or +0 and passes unchanged).
+__device__ __forceinline__ double interp_k_nobox(double l1, double l2, double h1, double h2, double v, double u)
+{
+    const double ex = exp(interp_lnk(l1, l2, h1, h2, v, u));
+    double kk;
+    asm("v_max_f64 %0, %1, 0" : "=v"(kk) : "v"(ex));
     return kk;
 }
 __device__ __forceinline__ void interp_kg(double l1, double l2, double h1, double h2, double v,
@@ -98,7 +120,8 @@ constexpr int kLoadBatch = 10;
 
 // NONNEG (the 32-bit-key merge kernel, ansfm_merge32.hip.h): a negative value counts as "unsorted" too (that kernel
 // orders float32 bit patterns as unsigned integers) and -0.0 is stored as +0.0.
-template <bool FROM_K, bool NONNEG = false>
+// NOBOX: the table holds no boxed entry (interp_k_nobox).
+template <bool FROM_K, bool NONNEG = false, bool NOBOX = false>
 __device__ __forceinline__ void load_gas(const OverlapParams &p, const LayerInterp &q, int m, int l,
                                          int s, int nu, double *DST, int lane, bool &unsorted)
 {
@@ -146,7 +169,8 @@ __device__ __forceinline__ void load_gas(const OverlapParams &p, const LayerInte
 #pragma unroll
             for (int k = 0; k < kLoadBatch; ++k)
                 if (g0 + k < G) {
-                    double kk = interp_k(r1[k], r2[k], r3[k], r4[k], q.v, q.u) * amt;
+                    double kk = (NOBOX ? interp_k_nobox(r1[k], r2[k], r3[k], r4[k], q.v, q.u)
+                                       : interp_k(r1[k], r2[k], r3[k], r4[k], q.v, q.u)) * amt;
                     if constexpr (NONNEG) kk += 0.0;
                     DST[(g0 + k) * kWave + lane] = kk;
                     unsorted |= (kk < prev);

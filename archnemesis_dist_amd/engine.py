@@ -206,6 +206,12 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_ktable_info(self._ctx, dims, C.byref(mono)), "ktable_info")
         return tuple(int(d) for d in dims), bool(mono.value)
 
+    def ktable_has_boxed(self):
+        """True when some entry of the uploaded table is <= 0 or NaN (the merge then keeps its box tests)."""
+        b = C.c_int()
+        self._check(self._lib.ansfm_ktable_has_boxed(self._ctx, C.byref(b)), "ktable_has_boxed")
+        return bool(b.value)
+
     # ---- array-level seams --------------------------------------------------------------------
     def calc_k(self, press, temp, grad=False):
         press = _np(press); temp = _np(temp)

@@ -74,6 +74,9 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
 /* dims = {W,G,NP,NT,S}; monotone = 1 when every k(g) column of the table is >=0 and
  * non-decreasing in g (precondition of the merge kernel's fast path). */
 int ansfm_ktable_info(const ansfm_ctx *ctx, int64_t dims[5], int *monotone);
+/* has_boxed = 1 when some entry of the table is <= 0 or NaN (such entries are stored NaN-boxed and every interpolation
+ * tests for them); 0 for an all-positive table, whose forward merge reads it without those tests. */
+int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed);
 
 /* ---- LBL tables (ILBL = LINE_BY_LINE_TABLES) ------------------------------------------------------
  * State of Spectroscopy_0 after read_tables on .lta / HDF5 LBL tables: K[W][NP][|NT|][S] (NG = 1),
