@@ -34,6 +34,9 @@ EXPORTS = [
     "ansfm_add_pseudo_continuum_monochromatic_absorption", "ansfm_lbl_accum_begin", "ansfm_lbl_accum_add_lines",
     "ansfm_lbl_accum_add_pseudo_continuum", "ansfm_lbl_accum_read", "ansfm_lbl_accum_device_ptr",
     "ansfm_ktable_has_boxed",
+    "ansfm_lblrt_begin", "ansfm_lblrt_add_isotopologue", "ansfm_lblrt_commit", "ansfm_lblrt_set_state",
+    "ansfm_lblrt_set_scratch_bytes", "ansfm_lblrt_last", "ansfm_calc_klbl_online", "ansfm_calc_klblg_online",
+    "ansfm_get_dtaugas",
 ]
 
 _lib = None
@@ -169,6 +172,16 @@ def load():
     lib.ansfm_lbl_accum_add_pseudo_continuum.argtypes = [vp, ci, cd, cd, vp, cd, cd, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
     lib.ansfm_lbl_accum_read.argtypes = [vp, vp]
     lib.ansfm_lbl_accum_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci)]
+    lib.ansfm_get_dtaugas.argtypes = [vp, ci, vp]
+    lib.ansfm_lblrt_begin.argtypes = [vp, ci, vp, ci, ci]
+    lib.ansfm_lblrt_add_isotopologue.argtypes = [vp, ci, ci, cd, cd, ci, ci, cd, cd, vp, vp, vp, vp, vp, cd, cd, cd, ci, ci, cd, cd,
+                                                 vp, vp, vp, vp, vp, ci]
+    lib.ansfm_lblrt_commit.argtypes = [vp]
+    lib.ansfm_lblrt_set_state.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ansfm_lblrt_set_scratch_bytes.argtypes = [vp, C.c_int64]
+    lib.ansfm_lblrt_last.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    lib.ansfm_calc_klbl_online.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.ansfm_calc_klblg_online.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ansfm_layer_average.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 11
     lib.ansfm_layer_average_dev.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp, vp]
     lib.ansfm_layer_averageg.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 15

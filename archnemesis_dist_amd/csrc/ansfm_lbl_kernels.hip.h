@@ -118,7 +118,7 @@ struct LblParams {
     const double *wn_grid;  // [nw] ascending
     const double *nu, *sw, *e_lower, *stim_ref;  // [N], nu ascending
     const double *bparams;  // [3M][N]
-    const double *mmf;      // [M]
+    const double *mmf;      // [M], or [L][M] with mmf_stride = M: the mix fractions of every (T, p) point
     const double *t_calc, *p_calc, *q_ratio;  // [L]
     double *store;          // [L][N][kLblRows]: strength, shifted centre nu + shift, wing numerator (iso * strength *
                             // line_approx_const * cmax^2), the Voigt constants of the line 1/(sigma sqrt 2), y = gamma/(sigma
@@ -127,6 +127,7 @@ struct LblParams {
     double *shift;          // [L][N] pressure shift (only the caller's `store` wants it)
     double *out;            // [L][nw]  (added to)
     int nw, N, M, L, lineshape_id;
+    int mmf_stride;         // 0: one mmf[M] for all points (fills the padding after lineshape_id: no other member moves)
     double t_ref, p_ref, iso_abundance, iso_mass, s_floor, wn_calc_window, wn_approx_window, max_shift;
 };
 
@@ -187,7 +188,7 @@ __global__ void k_lbl_line_params(LblParams p)
     const double strength = lbl_strength(c, t_calc, p.q_ratio[l], nu, p.sw[i], p.e_lower[i], p.stim_ref[i]);
     const double alpha_d = lbl_doppler_width(c, t_calc, p.iso_mass, nu);
     double sh;
-    const double g = lbl_lorentz_width(c, p.bparams, p.mmf, p.M, p.N, i, &sh);
+    const double g = lbl_lorentz_width(c, p.bparams, p.mmf + (size_t)l * p.mmf_stride, p.M, p.N, i, &sh);
     double *st = p.store + ((size_t)l * p.N + i) * kLblRows;      // one line's constants are contiguous (64 bytes)
     st[0] = strength;
     st[1] = nu + sh;                                              // :264

@@ -33,7 +33,7 @@ struct PcParams {
     const double *centers, *widths, *sw, *e_lower;  // [N]
     const double *lo;                            // [N] centers - widths / 2, non-decreasing
     const double *bparams;                       // [3M][N]
-    const double *mmf;                           // [M]
+    const double *mmf;                           // [M], or [L][M] with mmf_stride = M
     const double *t_calc, *p_calc, *q_ratio;     // [L]
     double *store;                               // [L][3][N] strength, alpha_d, gamma_l
     double *y;                                   // [L][N][2 nb + 1] shapes of source bin i at its neighbours
@@ -41,6 +41,7 @@ struct PcParams {
     double *x;                                   // [L][N] spread continuum per unit wavenumber
     double *out;                                 // [L][nw] (added to)
     int nw, N, M, L, lineshape_id, nb;
+    int mmf_stride;                              // 0: one mmf[M] for all points
     int first, last;                             // source bins [first, last) spread (:399-416)
     int jmax;                                    // largest touched grid point: points below it receive (:476)
     double t_ref, p_ref, iso_abundance, iso_mass, wmax;
@@ -59,7 +60,7 @@ __global__ void k_pc_params(PcParams p)
     double *st = p.store + (size_t)l * 3 * p.N + i;
     st[0] = lbl_strength(c, t_calc, p.q_ratio[l], nu, p.sw[i], p.e_lower[i], stim_ref);
     st[p.N] = lbl_doppler_width(c, t_calc, p.iso_mass, nu);
-    st[2 * (size_t)p.N] = lbl_lorentz_width(c, p.bparams, p.mmf, p.M, p.N, i, &sh);
+    st[2 * (size_t)p.N] = lbl_lorentz_width(c, p.bparams, p.mmf + (size_t)l * p.mmf_stride, p.M, p.N, i, &sh);
 }
 
 __global__ void k_pc_shapes(PcParams p)

@@ -200,6 +200,71 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_calc_klbl(self._ctx, L, _ptr(press), _ptr(temp), _ptr(k), _ptr(dk)), "calc_klbl")
         return (k, dk) if grad else k
 
+    # ---- runtime line-by-line (ILBL = 1): the line source resident in the context ---------------------------------------
+    def upload_line_source(self, source):
+        """`line_source.LineSource` -> HBM (ansfm_lblrt_begin / add_isotopologue / commit): lines sorted and uploaded once.
+        The engine then answers like an LBL table with G = 1 and W = nw, its gas opacities coming from the lines; every CIRSrad
+        call needs a state first (`set_line_state`).  Uploading a table leaves the mode."""
+        g = source.wn_grid
+        self._check(self._lib.ansfm_lblrt_begin(self._ctx, source.nw, _ptr(g), source.S, source.M), "lblrt_begin")
+        for s, isos in enumerate(source.gases):
+            for iso in isos:
+                rc = self._lib.ansfm_lblrt_add_isotopologue(
+                    self._ctx, s, iso.lineshape_id, iso.abundance, iso.mass, int(iso.include_lines), iso.N, iso.t_ref, iso.p_ref,
+                    _ptr(iso.bparams), _ptr(iso.nu), _ptr(iso.sw), _ptr(iso.e_lower), _ptr(iso.stim_ref), iso.s_floor,
+                    iso.wn_calc_window, iso.wn_approx_window, int(iso.include_continuum), iso.Nb, iso.t_cont, iso.p_cont,
+                    _ptr(iso.pc_bparams), _ptr(iso.centers), _ptr(iso.widths), _ptr(iso.sw_sum), _ptr(iso.pc_e_lower),
+                    iso.n_neighbour_bins)
+                self._check(rc, "lblrt_add_isotopologue")
+        self._check(self._lib.ansfm_lblrt_commit(self._ctx), "lblrt_commit")
+        self.dims = (source.nw, 1, 2, 2, source.S)
+        self.WAVE, self.DELG = g, np.array([1.0])
+        self._line_source = source
+
+    def set_line_state(self, state):
+        """`line_source.LineState` (see `line_source.pack_line_state`) -> ansfm_lblrt_set_state: the distinct k-rows are computed
+        now and stand for the CIRSrad calls that follow, whose (n_models, L) must be the state's."""
+        st = state
+        rc = self._lib.ansfm_lblrt_set_state(self._ctx, st.n, st.L, st.R, _ptr(st.krow), _ptr(st.row_gas), _ptr(st.row_p_atm),
+                                             _ptr(st.row_t), _ptr(st.row_mix), _ptr(st.row_q_lines), _ptr(st.row_q_cont),
+                                             _ptr(st.row_q_lines_dT), _ptr(st.row_q_cont_dT))
+        self._check(rc, "lblrt_set_state")
+
+    def set_line_scratch_bytes(self, nbytes):
+        """byte budget of the per-(row, line) constants: the rows of a state run in chunks that fit it (no bit depends on it)"""
+        self._check(self._lib.ansfm_lblrt_set_scratch_bytes(self._ctx, int(nbytes)), "lblrt_set_scratch_bytes")
+
+    def last_line_rows(self):
+        """(rows, (T, p) points, chunks) of the last k-row computation"""
+        r, p, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self._lib.ansfm_lblrt_last(self._ctx, C.byref(r), C.byref(p), C.byref(c)), "lblrt_last")
+        return r.value, p.value, c.value
+
+    def calc_klbl_online(self, press, temp, amb_frac, grad=False):
+        """Spectroscopy_0.calc_klbl_online (:2046) / calc_klblg_online (:1922) on the uploaded line source: press (atm), temp
+        (L,); amb_frac (S, M - 1) or (M - 1,) -> k (nw, L, S) [, dkdT].  Both run calc_klblg_online's summation order."""
+        from . import line_source as lsrc
+        src = self._line_source
+        press = _np(press); temp = _np(temp)
+        L = press.shape[0]
+        amb = _np(amb_frac)
+        mix = lsrc.mix_fractions(np.broadcast_to(amb, (src.S, src.M - 1)))
+        def q(t):        # [isotopologues of gas 0, of gas 1, ...][L]
+            ql, qc = zip(*(lsrc.q_ratios(src, np.full(L, s), t) for s in range(src.S)))
+            return [np.ascontiguousarray(np.concatenate([a.reshape(L, -1).T for a in x], axis=0)) for x in (ql, qc)]
+        ql, qc = q(temp)
+        k = np.empty((src.nw, L, src.S))
+        if grad:
+            qld, qcd = q(temp + 5.0)
+            dk = np.empty_like(k)
+            rc = self._lib.ansfm_calc_klblg_online(self._ctx, L, _ptr(press), _ptr(temp), _ptr(mix), _ptr(ql), _ptr(qc), _ptr(qld),
+                                                   _ptr(qcd), _ptr(k), _ptr(dk))
+            self._check(rc, "calc_klblg_online")
+            return k, dk
+        self._check(self._lib.ansfm_calc_klbl_online(self._ctx, L, _ptr(press), _ptr(temp), _ptr(mix), _ptr(ql), _ptr(qc), _ptr(k)),
+                    "calc_klbl_online")
+        return k
+
     def ktable_info(self):
         dims = (C.c_int64 * 5)()
         mono = C.c_int()
@@ -1088,6 +1153,14 @@ class AnsfmEngine:
         W, G = self.dims[0], self.dims[1]
         out = np.empty((W, G, L))
         self._check(self._lib.ansfm_get_taugas(self._ctx, int(model), _ptr(out)), "get_taugas")
+        return out
+
+    def get_dtaugas(self, L, model=0):
+        """Side product of the last gradient CIRSrad call: (NWAVE, NG, NGAS + 1, L) -- slot s = the cross-section of gas s (times
+        1e-4: the reference's dTAUGAS of that gas), slot NGAS = d tau / dT."""
+        W, G, S = self.dims[0], self.dims[1], self.dims[4]
+        out = np.empty((W, G, S + 1, L))
+        self._check(self._lib.ansfm_get_dtaugas(self._ctx, int(model), _ptr(out)), "get_dtaugas")
         return out
 
     def set_layer_dedup(self, enable=True):

@@ -2,8 +2,8 @@
 
 `make_gpu_forward_model(ForwardModel_0)` returns a subclass of the reference's own class
 (ForwardModel_0.py:87) whose `CIRSrad` (ForwardModel_0.py:4376-4511) runs on the MI355X through
-libansfm.so for the supported cases (ILBL = K_TABLES or LINE_BY_LINE_TABLES, IMOD = THERMAL_EMISSION, no layer emissions,
-with or without analytic gradients) and whose `jacobian_nemesis` fan-out can batch the independent forward models.
+libansfm.so for the supported cases (ILBL = K_TABLES, LINE_BY_LINE_TABLES or LINE_BY_LINE_RUNTIME with line data in
+SpectroscopyX, IMOD = THERMAL_EMISSION, no layer emissions, with or without analytic gradients) and whose `jacobian_nemesis` fan-out can batch the independent forward models.
 Everything else (subprofretg, calc_path, conv, ...) is the reference's own host code.
 
 `CIRSradGPU` is the mixin with the seam itself; it only needs the `*X` attributes CIRSrad reads
@@ -21,6 +21,7 @@ from .engine import AnsfmEngine
 # IntEnum / IntFlag values of the reference (archnemesis/enum/*.py) kept as plain ints at the seam
 ILBL_K_TABLES = 0                      # SpectralCalculationModeEnum.K_TABLES
 ILBL_LBL_TABLES = 2                    # SpectralCalculationModeEnum.LINE_BY_LINE_TABLES
+ILBL_LBL_RUNTIME = 1                   # SpectralCalculationModeEnum.LINE_BY_LINE_RUNTIME
 IMOD_THERMAL_EMISSION = 64             # PathCalcEnum.THERMAL_EMISSION
 IMOD_MULTIPLE_SCATTERING = 256
 IMOD_DOWNWARD_FLUX = 16
@@ -90,16 +91,25 @@ def _note(what):
     NOTES[what] = NOTES.get(what, 0) + 1
 
 
+ROUTES = {}
+
+
+def _route(what):
+    """A GPU route that a run may want to see it took (counted in ROUTES, not announced): e.g. CIRSrad on the line source."""
+    ROUTES[what] = ROUTES.get(what, 0) + 1
+
+
 def summary():
-    """What left the GPU path (DELEGATED: case -> count) and what was done differently on purpose (NOTES) since the
-    process started or `reset_summary()`; `install_all()` returns the same object, so a caller can print it after a
-    retrieval."""
-    return {"delegated": dict(DELEGATED), "notes": dict(NOTES), "strict": STRICT}
+    """What left the GPU path (DELEGATED: case -> count), what was done differently on purpose (NOTES) and which of the
+    counted GPU routes ran (ROUTES) since the process started or `reset_summary()`; `install_all()` returns the same
+    object, so a caller can print it after a retrieval."""
+    return {"delegated": dict(DELEGATED), "notes": dict(NOTES), "routes": dict(ROUTES), "strict": STRICT}
 
 
 def reset_summary():
     DELEGATED.clear()
     NOTES.clear()
+    ROUTES.clear()
 
 
 class KtaTableOnDevice:
@@ -176,7 +186,10 @@ class CIRSradGPU:
     # ---- what is supported -----------------------------------------------------------------------
     def _ansfm_supported(self, return_grad):
         S = self.SpectroscopyX
-        if S.NGAS <= 0 or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES) or S.K is None:
+        if S.NGAS > 0 and int(S.ILBL) == ILBL_LBL_RUNTIME:
+            if self._ansfm_line_source()[0] is None:      # the cases of the line source that are built, nothing else
+                return False
+        elif S.NGAS <= 0 or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES) or S.K is None:
             return False
         if return_grad and (self.AtmosphereX.NVMR + 2 + self.ScatterX.NDUST > 256 or S.NGAS > 31):
             return False                   # kMaxPar of the gradient kernels' slot table; one mask bit per gas
@@ -200,6 +213,38 @@ class CIRSradGPU:
         if self._ansfm_scatter_branch(imod):
             return not return_grad
         return False
+
+    # ---- runtime line-by-line (ILBL = 1): the line source and the state of a call -------------------------------------
+    def _ansfm_line_source(self):
+        """(LineSource, None) when the runtime line-by-line opacity of this model is built on the device, else (None, why):
+        SpectroscopyX carries LINE_DATA / LINE_DATA_PARAMS, every line shape is built, the bins pass the pseudo-continuum
+        entry's tests, the spectral axis is wavenumber."""
+        from . import line_source as lsrc
+        S = self.SpectroscopyX
+        ld, prm = getattr(S, "LINE_DATA", None), getattr(S, "LINE_DATA_PARAMS", None)
+        if not ld or not prm or len(ld) != S.NGAS or len(prm) != S.NGAS:
+            return None, "no LINE_DATA / LINE_DATA_PARAMS for every gas"
+        if int(getattr(S, "ISPACE", 0)) != 0:
+            return None, "a wavelength grid"
+        try:
+            src = lsrc.LineSource.from_spectroscopy(S)
+        except (AttributeError, TypeError, ValueError, IndexError) as e:
+            return None, "line data this adapter cannot read (%s)" % e
+        why = src.unsupported()
+        return (None, why) if why else (src, None)
+
+    def _ansfm_line_state(self, eng, src, return_grad):
+        """amb_frac as :3822-3827, the q ratios from partition_fn_data at t_ref / t_cont against T (and T + 5 K), the distinct
+        k-rows of the layers -> the engine's state for the call that follows"""
+        from . import line_source as lsrc
+        S, L, A = self.SpectroscopyX, self.LayerX, self.AtmosphereX
+        amb = lsrc.ambient_fractions(L.PP, L.PRESS, A.ID, S.ID)
+        if src.M != 2:
+            raise ValueError("ILBL = 1 in CIRSrad: amb_frac has one ambient gas (ForwardModel_0.py:3823), the line data %d" % (src.M - 1))
+        st = lsrc.pack_line_state(src, np.asarray(L.PRESS, dtype=np.float64) / lsrc.ATM_TO_PASCAL, L.TEMP, lsrc.mix_fractions(amb),
+                                  grad=return_grad)
+        eng.set_line_state(st)
+        return st
 
     @staticmethod
     def _ansfm_transmission_branch(imod):
@@ -280,6 +325,13 @@ class CIRSradGPU:
 
     def _ansfm_upload_table(self, eng):
         S = self.SpectroscopyX
+        if int(S.ILBL) == ILBL_LBL_RUNTIME:           # the line source, once per fingerprint of the line data and parameters
+            src = self._ansfm_line_source()[0]
+            fp = "lines:" + src.fingerprint()
+            if getattr(eng, "_table_fp", None) != fp:
+                eng.upload_line_source(src)
+                eng._table_fp = fp
+            return src
         fp = _table_fingerprint(S)
         if getattr(eng, "_table_fp", None) != fp:
             if isinstance(S.K, KtaTableOnDevice):   # .kta / .lta files -> HBM without a host array (install_gpu_table_reader)
@@ -419,14 +471,19 @@ class CIRSradGPU:
     # ---- the seam ---------------------------------------------------------------------------------
     def CIRSrad(self, return_grad=False):
         if not self._ansfm_supported(return_grad):
-            _delegate("CIRSrad case (IMOD / ILBL / emissions)")
+            S = self.SpectroscopyX
+            why = self._ansfm_line_source()[1] if (S.NGAS > 0 and int(S.ILBL) == ILBL_LBL_RUNTIME) else None
+            _delegate("CIRSrad on runtime line-by-line opacities with " + why if why else "CIRSrad case (IMOD / ILBL / emissions)")
             base = super()
             if hasattr(base, "CIRSrad"):
                 return base.CIRSrad(return_grad)      # the reference's own implementation, in its process
             raise NotImplementedError("CIRSrad: only ILBL=K_TABLES, IMOD=THERMAL_EMISSION run on the GPU so far")
         eng = get_engine(self.ansfm_device)
         S, L, P = self.SpectroscopyX, self.LayerX, self.PathX
-        self._ansfm_upload_table(eng)
+        src = self._ansfm_upload_table(eng)
+        if src is not None:                           # ILBL = 1: the k-rows of this call's layers
+            self._ansfm_line_state(eng, src, return_grad)
+            _route("CIRSrad on runtime line-by-line opacities (ILBL = 1, line source in HBM)")
         TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(return_grad)
         taucont = TAUCIA + TAUDUST + TAURAY                                  # :3989 (g-independent part)
         f_gas = self._ansfm_layer_inputs()

@@ -144,3 +144,45 @@ def synth_lbl_gas(wn_lo, wn_hi, n_iso, lines, L, seed=0, bin_width=1.0, margin=1
                      10.0 ** rng.uniform(-27, -23, nbin), rng.uniform(0, 3000, nbin))
         out.append((line_args, cont_args))
     return out
+
+
+class PowerLawQ:
+    """partition function Q(T) = a T^b, the stand-in of the synthetic line sources"""
+
+    def __init__(self, a, b):
+        self.a, self.b = float(a), float(b)
+
+    def __call__(self, t):
+        return self.a * t ** self.b
+
+
+def synth_line_source(wn_grid, n_iso=(3,), lines=1000, seed=0, bin_width=1.0, margin=150.0):
+    """A `line_source.LineSource` of synthetic gases on wn_grid (ascending cm-1): n_iso[s] isotopologues of gas s, each with
+    `lines` Voigt lines and the weak-line bins of width bin_width out to `margin` beyond the grid, broadened by "self" and one
+    ambient gas (M = 2), partition functions Q = a T^b."""
+    from .line_source import Isotopologue, LineSource
+    rng = np.random.default_rng(seed)
+    c2 = 2.99792458E10 * 6.62607015E-27 / 1.380649E-16
+    lo, hi = float(wn_grid[0]), float(wn_grid[-1])
+    nbin = int(round((hi - lo + 2 * margin) / bin_width))
+    centers = lo - margin + bin_width * (np.arange(nbin) + 0.5)
+
+    def broadening(n):
+        bp = np.zeros((6, n))
+        bp[0] = rng.uniform(0.05, 0.12, n); bp[1] = rng.uniform(0.5, 0.8, n)                                     # self: no shift
+        bp[3] = rng.uniform(0.02, 0.1, n); bp[4] = rng.uniform(0.5, 0.8, n); bp[5] = rng.uniform(-0.01, 0.01, n)
+        return bp
+
+    gases = []
+    for s, n in enumerate(n_iso):
+        isos = []
+        for i in range(n):
+            nu = np.sort(rng.uniform(lo - 75.0, hi + 75.0, lines))
+            pcb = broadening(nbin); pcb[5] = 0.0
+            isos.append(Isotopologue(0, (0.98, 0.011, 0.004, 0.002)[i % 4], 28.0 + i + 4 * s, PowerLawQ(2.0 + i, 1.5 + 0.1 * s), 2,
+                                     bparams=broadening(lines), nu=nu, sw=10.0 ** rng.uniform(-28, -19, lines),
+                                     e_lower=rng.uniform(0, 3000, lines), stim_ref=1 - np.exp(-c2 * nu / 296.0), pc_bparams=pcb,
+                                     centers=centers, widths=np.full(nbin, float(bin_width)), sw_sum=10.0 ** rng.uniform(-27, -23, nbin),
+                                     pc_e_lower=rng.uniform(0, 3000, nbin)))
+        gases.append(isos)
+    return LineSource(wn_grid, gases, 2)

@@ -464,6 +464,84 @@ int ansfm_lbl_accum_add_pseudo_continuum(ansfm_ctx *ctx, int lineshape_id, doubl
 int ansfm_lbl_accum_read(ansfm_ctx *ctx, double *out);
 int ansfm_lbl_accum_device_ptr(ansfm_ctx *ctx, double **dev, int *L, int *nw);
 
+/* Side product of the last gradient CIRSrad call (ansfm_cirsradg_ck_thermal / _transmission), like ansfm_get_taugas of a
+ * forward call: the derivatives of the vertical gas opacity of model `model`, dTAUGAS[W][G][S + 1][L] -- slot s = the
+ * derivative with respect to the amount of gas s as the kernels keep it (the reference's dTAUGAS[:, :, IGAS, :] is this times
+ * SQ_CM_TO_SQ_METER = 1e-4, :3813, :3844), slot S = d tau / dT (:3814, :3845).  No gradient call yet, or a gas-overlap seam since -> ANSFM_ERR_INVALID. */
+int ansfm_get_dtaugas(ansfm_ctx *ctx, int model, double *dTAUGAS);
+
+/* ---- runtime line-by-line as the context's opacity source ------------------------------------------------------------
+ * The ILBL = LINE_BY_LINE_RUNTIME branch of ForwardModel_0.calculate_gaseous_line_opacity (ForwardModel_0.py:3819-3848) with
+ * Spectroscopy_0.calc_klbl_online (:2046) / calc_klblg_online (:1922): the line data of S gases stay in HBM, and every entry
+ * that computes gas opacities (thermal and its gradient, transmission and its gradient, single and multiple scattering,
+ * ansfm_get_taugas) takes them from the lines instead of a table.
+ *
+ * begin: wn_grid[nw] ascending (else ANSFM_ERR_INVALID), S gases, M broadeners ("self" first, then the ambient gases).  A
+ * source committed earlier is taken apart.
+ * add_isotopologue: everything of one isotopologue of gas `gas` that stays fixed over a retrieval, in the order the
+ * reference walks LineData_0.line_data / continuum_data.  The caller has applied the reference's host-side selections: the
+ * inclusive wn_calc_range masks (LineData_0.py:882, :1376) and the zeroed shift rows of include_pressure_shift = False
+ * (:886-888).  Lines: N, t_ref, p_ref, broadening_params[3M][N], nu / sw / e_lower / stim_ref[N] in any order (sorted here,
+ * once), s_floor and the two windows, as in ansfm_add_line_set_monochromatic_absorption.  Bins: N_bins, t_cont, p_cont,
+ * lsw_mean_broadening_params[3M][N_bins], wn_bin_centers / wn_bin_widths / sw_sum / lsw_mean_e_lower[N_bins],
+ * n_neighbour_bins, as in ansfm_add_pseudo_continuum_monochromatic_absorption.  include_lines / include_continuum: the
+ * reference's switches.  Error codes are those entries': a shape that is not built -> ANSFM_ERR_UNSUPPORTED, bin widths
+ * that are not positive or lower edges that do not ascend -> ANSFM_ERR_INVALID, more than 8 neighbour bins ->
+ * ANSFM_ERR_UNSUPPORTED.  N == 0, or sw_sum all zero, is the reference's has_data == False: that part adds nothing.
+ * commit: every gas has an isotopologue, else ANSFM_ERR_INVALID.  The context then answers like an uploaded LBL table with
+ * G = 1 and W = nw (ansfm_ktable_info), and stays so until a table is uploaded; a commit after an upload takes the table's
+ * place.  Layer de-duplication and the scattering batch's layer cache are not applied in this mode (their comparison of
+ * pressure, temperature and amounts does not see the mix fractions; the distinct rows of set_state take their place), so
+ * ansfm_cirsrad_ck_scatter_batch runs its models one by one and ansfm_cirsrad_ck_scatter_batch_slice is
+ * ANSFM_ERR_UNSUPPORTED.  ansfm_calc_k / ansfm_calc_klbl -> ANSFM_ERR_NOTABLE. */
+int ansfm_lblrt_begin(ansfm_ctx *ctx, int nw, const double *wn_grid, int S, int M);
+int ansfm_lblrt_add_isotopologue(ansfm_ctx *ctx, int gas, int lineshape_id, double isotopic_abundance, double isotopic_mass,
+                                 int include_lines, int N, double t_ref, double p_ref, const double *broadening_params,
+                                 const double *nu, const double *sw, const double *e_lower, const double *stim_ref, double s_floor,
+                                 double wn_calc_window, double wn_approx_window, int include_continuum, int N_bins, double t_cont,
+                                 double p_cont, const double *lsw_mean_broadening_params, const double *wn_bin_centers,
+                                 const double *wn_bin_widths, const double *sw_sum, const double *lsw_mean_e_lower,
+                                 int n_neighbour_bins);
+int ansfm_lblrt_commit(ansfm_ctx *ctx);
+
+/* The state of the next CIRSrad calls, by distinct k-row: the cross-section of gas s in a layer depends on (p, T, the mix
+ * fractions of gas s) only, so the caller hands over the R distinct rows and krow[n][S][L] (int32), the row of every (model,
+ * gas, layer) -- as cont_row does in ansfm_cirsrad_ck_scatter_batch_rows.
+ *   row_gas[R] (int32, ascending: the rows are grouped by gas); row_p_atm[R] (atm: PRESS / ATM_TO_PASCAL as the reference
+ *   divides); row_t[R]; row_mix[R][M] (1 - sum amb_frac, amb_frac...: LineData_0.py:2342-2345); row_q_lines / row_q_cont: the
+ *   partition-function ratios Q(t_ref) / Q(T) and Q(t_cont) / Q(T) of the isotopologues of the row's gas, one row after the
+ *   other ([R][isotopologues of that gas]); row_q_*_dT: the same at T + 5 K, both or neither -- NULL when no gradient is
+ *   asked for.  The ratios come from the caller because the reference's partition_fn_data[i] is a Python callable.
+ * The maps are checked on the host before anything launches: a krow entry outside [0, R) or naming a row of another gas, a
+ * row_gas outside [0, S) or descending -> ANSFM_ERR_INVALID.  The rows' spectra are computed here, per gas as one batch of
+ * (T, p) points with the (T + 5 K, p) points in the same launches, in chunks of rows whose scratch fits
+ * ansfm_lblrt_set_scratch_bytes (default 256 MiB; the chunk size changes no bit of the result).  Per row the
+ * isotopologues add lines_0, continuum_0, lines_1, ... onto one zeroed buffer: calc_klblg_online's order and the order of
+ * ansfm_lbl_accum_*, to which the rows are bit-identical.  calc_klbl_online forms (sum lines) + (sum continuum)
+ * (LineData_0.py:2255-2279): the forward seam agrees with the reference to rounding only.
+ * The state stands until the next set_state, commit, table upload or ansfm_calc_klbl(g)_online.  A CIRSrad call whose
+ * (n_models, L) differs from the state's, a call before any state, and a gradient call on a state without the _dT ratios
+ * -> ANSFM_ERR_INVALID.  tau = sum_s k[krow] * amount in ascending s (:3841, :3848); the temperature slot of the gradient is
+ * sum_s dkdt_s * amount (:3845) with the reference's dkdt: calc_klblg_online clears its T + 5 K buffer once per gas, not per
+ * point (Spectroscopy_0.py:1987), so dkdt of layer l is (sum_{j <= l} k(T_j + 5) - k(T_l)) / 5 (:2041), and so it is here.
+ * last: the rows and (T, p) points of the last computation and the chunks they ran in. */
+int ansfm_lblrt_set_state(ansfm_ctx *ctx, int n_models, int L, int R, const int32_t *krow, const int32_t *row_gas,
+                          const double *row_p_atm, const double *row_t, const double *row_mix, const double *row_q_lines,
+                          const double *row_q_cont, const double *row_q_lines_dT, const double *row_q_cont_dT);
+int ansfm_lblrt_set_scratch_bytes(ansfm_ctx *ctx, int64_t bytes);
+int ansfm_lblrt_last(const ansfm_ctx *ctx, int *rows, int *points, int *chunks);
+
+/* Array-level seams, mirroring ansfm_calc_klbl: Spectroscopy_0.calc_klbl_online / calc_klblg_online on the committed source.
+ *   press[L] (atm), temp[L]; mol_mix_frac[S][M] per gas; q_lines / q_cont (and _dT at T + 5 K): [isotopologues of gas 0, of
+ *   gas 1, ...][L] -> k_out[nw][L][S], dkdT_out[nw][L][S] = (sum_{j <= l} k(T_j + 5) - k(T_l)) / 5 (see above).
+ * Both run the order of calc_klblg_online (see above).  No committed source -> ANSFM_ERR_NOTABLE.  A pending state of
+ * ansfm_lblrt_set_state is dropped. */
+int ansfm_calc_klbl_online(ansfm_ctx *ctx, int L, const double *press, const double *temp, const double *mol_mix_frac,
+                           const double *q_lines, const double *q_cont, double *k_out);
+int ansfm_calc_klblg_online(ansfm_ctx *ctx, int L, const double *press, const double *temp, const double *mol_mix_frac,
+                            const double *q_lines, const double *q_cont, const double *q_lines_dT, const double *q_cont_dT,
+                            double *k_out, double *dkdT_out);
+
 /* ---- layering ---------------------------------------------------------------------------------------
  * Layer_0.layer_average (Layer_0.py:755-1030), batched over n_models atmospheric states (the states of a
  * numerical Jacobian): LAYINT 0 = MID_PATH, 1 = ABSORBER_WEIGHTED_AVERAGE (Curtis-Godson, :949-1010).

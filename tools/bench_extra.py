@@ -18,7 +18,7 @@ def timeit(f, n=3):
 
 
 def main():
-    only = sys.argv[1] if len(sys.argv) > 1 else None       # "grad" | "ms" | "lbl" | "layer" | "ss"
+    only = sys.argv[1] if len(sys.argv) > 1 else None       # "grad" | "ms" | "lbl" | "lblrt" | "layer" | "ss"
     eng = pkg.AnsfmEngine(0)
     out = {}
     rng = np.random.default_rng(0)
@@ -32,6 +32,8 @@ def main():
         bench_lbl(eng, out, rng, full=True)
     if only == "lbl_pc":                                    # C5 size: 400 MB of opacities per host array, on request only
         bench_lbl_pc(eng, out)
+    if only == "lblrt":                                     # C5 size: 400 MB of opacities per state, on request only
+        bench_lblrt(eng, out)
     if only in (None, "layer"):
         bench_layer(eng, out)
     if only in (None, "maps"):
@@ -284,6 +286,64 @@ def bench_lbl_pc(eng, out, nw=1000000, Ll=50, lines=100000, n_iso=3, n=5):
         "pseudo_continuum_call_wall_s": t_pc, "line_call_wall_s": t_ln,
         "gas_host_array_calls_wall_s": t_host, "gas_accumulator_wall_s": t_acc, "gas_accumulator_left_in_hbm_wall_s": t_dev,
         "accumulator_equals_host_calls": same}
+
+
+def bench_lblrt(eng, out, nw=1000000, Ll=50, lines=100000, n_iso=3, n=3):
+    """CIRSrad's thermal branch on runtime line-by-line opacities at C5 size (1e6 points x 50 layers, one gas of three
+    isotopologues with 1e5 lines each), end to end: the line source resident in HBM (pack the rows, set the state, the call)
+    beside what the same opacities cost through the per-call entries -- 2 n_iso accumulator adds that stage the line list
+    each time, the read-back, an LBL-table-style upload of the result and the same call on it.  Medians of n after one
+    warm-up; `lblrt <points> <layers>` for a quick look."""
+    from archnemesis_dist_amd import line_source as ls
+    if len(sys.argv) > 3:
+        nw, Ll = int(sys.argv[2]), int(sys.argv[3])
+        lines = max(nw // 10, 100)
+    wn = 2000.0 + 1e-3 * np.arange(nw)
+    src = syn.synth_line_source(wn, (n_iso,), lines, seed=0)
+    lp = 101325.0 * np.logspace(-4, 0, Ll)[::-1].copy(); lt = np.linspace(300.0, 150.0, Ll)
+    am = np.full((1, Ll), 1.0e22) * (lp / lp[0])[None, :]
+    mix = np.array([[0.05, 0.95]])
+    NLAYIN, LAYINC, SCALE = syn.nadir_path(Ll, 10.0)
+    EMTEMP = lt[LAYINC[:, 0]][:, None]
+    cont = np.zeros((nw, Ll))
+    thermal = lambda: eng.cirsrad_ck_thermal(0, lp, lt, am, cont, NLAYIN, LAYINC, SCALE, EMTEMP, -1.0)
+    t_up = timeit(lambda: eng.upload_line_source(src), 1)
+
+    def resident(grad=False):
+        eng.set_line_state(ls.pack_line_state(src, lp / 101325.0, lt, mix, grad=grad))
+        return thermal()
+
+    def state_only():
+        eng.set_line_state(ls.pack_line_state(src, lp / 101325.0, lt, mix))
+        eng.synchronize()
+
+    t_res = timeit(resident, n)
+    t_state = timeit(state_only, n)
+    spec = resident()
+    t_res_g = timeit(lambda: resident(True), 1)
+    ql, qc = ls.q_ratios(src, np.zeros(Ll, dtype=int), lt)
+    ql, qc = ql.reshape(Ll, -1), qc.reshape(Ll, -1)
+
+    def per_call_entries():
+        acc = eng.lbl_accumulator(wn, lt, lp / 101325.0)
+        for i, iso in enumerate(src.gases[0]):
+            acc.add_lines(0, iso.t_ref, iso.p_ref, ql[:, i], iso.abundance, iso.mass, mix[0], iso.bparams, iso.nu, iso.sw, iso.e_lower,
+                          iso.stim_ref)
+            acc.add_pseudo_continuum(0, iso.t_cont, iso.p_cont, qc[:, i], iso.abundance, iso.mass, mix[0], iso.pc_bparams, iso.centers,
+                                     iso.widths, iso.sw_sum, iso.pc_e_lower)
+        k = acc.numpy()                                                             # (L, nw)
+        K = np.ascontiguousarray(np.repeat(k.T[:, :, None, None], 2, axis=2))       # (W, NP = L, NT = 2, S = 1)
+        eng.upload_lbltable(K, (lp / 101325.0)[::-1].copy(), np.array([100.0, 400.0]), wn)
+        return thermal()
+
+    t_old = timeit(per_call_entries, n)
+    eng.upload_line_source(src)
+    out["lblrt_C5" if (nw, Ll) == (1000000, 50) else "lblrt_reduced"] = {
+        "grid": nw, "layers": Ll, "lines": lines, "isotopologues": n_iso, "median_of": n,
+        "line_source_upload_wall_s": t_up, "cirsrad_thermal_on_line_source_wall_s": t_res,
+        "of_which_pack_and_set_state_wall_s": t_state, "with_T_plus_5_rows_wall_s": t_res_g,
+        "per_call_entries_readback_table_upload_wall_s": t_old, "ratio": t_old / t_res,
+        "spectrum_finite": bool(np.all(np.isfinite(spec)))}
 
 
 def bench_layer(eng, out):
