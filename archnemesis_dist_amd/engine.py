@@ -792,6 +792,40 @@ class AnsfmEngine:
         self._check(rc, "add_pseudo_continuum_monochromatic_absorption")
         return out
 
+    def mie_makephase(self, wavel, iscat, dsize, rs, refindx, theta, radius_block=None, return_counts=False, radius_cap=None):
+        """Scatter_0.makephase (module level, :1828) for iscat 1 .. 4: Mie theory integrated over a size distribution.
+        wavel (nwave,) um, dsize (3,), rs (3,) = first radius, last radius, step (rs[1] < rs[0]: open range), refindx (nwave,2),
+        theta (ntheta,) within [0, 90] -> (xscat, xext, thetax, phas) as the reference returns them: cross-sections in cm2,
+        thetax (nphas,) the angles out to 180 degrees, phas (nwave,nphas) before the class method divides by 4 pi; with
+        return_counts the radii each wavelength integrated over as a fifth item.  radius_block (a multiple of 64 radii) and
+        radius_cap (radii of an open range before "did not terminate") hold for this call; neither changes a bit of the
+        result.  ValueError where the reference gives up (the text names wavelength and radius), for an angle outside
+        [0, 90] and for another iscat."""
+        wavel = _np(np.atleast_1d(wavel)); theta = _np(np.atleast_1d(theta))
+        dsize = _np(dsize); rs = _np(rs); refindx = _np(refindx)
+        nwave, ntheta = wavel.shape[0], theta.shape[0]
+        if wavel.ndim != 1 or theta.ndim != 1 or dsize.shape != (3,) or rs.shape != (3,) or refindx.shape != (nwave, 2):
+            raise ValueError("mie_makephase: wavel (nwave,), dsize (3,), rs (3,), refindx (nwave,2), theta (ntheta,)")
+        nphas = 2 * ntheta - 1 if np.count_nonzero(theta == 90.0) == 1 else 2 * ntheta
+        thetax = np.zeros(nphas)
+        thetax[:ntheta] = theta
+        for i in range(ntheta, nphas):
+            thetax[i] = 180.0 - thetax[nphas - i - 1]
+        xscat, xext, phas = np.empty(nwave), np.empty(nwave), np.empty((nwave, nphas))
+        counts = np.zeros(nwave, dtype=np.int32)
+        self._check(self._lib.ansfm_mie_set_radius_block(self._ctx, int(radius_block or 0)), "mie_set_radius_block")
+        self._check(self._lib.ansfm_mie_set_radius_cap(self._ctx, int(radius_cap or 0)), "mie_set_radius_cap")
+        rc = self._lib.ansfm_mie_makephase(self._ctx, nwave, _ptr(wavel), int(iscat), _ptr(dsize), _ptr(rs), _ptr(refindx), ntheta,
+                                           _ptr(theta), _ptr(xscat), _ptr(xext), _ptr(phas), _ptr(counts))
+        self._check(rc, "mie_makephase")
+        return (xscat, xext, thetax, phas, counts) if return_counts else (xscat, xext, thetax, phas)
+
+    def mie_last(self):
+        """(kernel milliseconds, blocks of radii, radii of the largest block) of the last mie_makephase call"""
+        ms, nb, nr = C.c_double(), C.c_int32(), C.c_int32()
+        self._check(self._lib.ansfm_mie_last(self._ctx, C.byref(ms), C.byref(nb), C.byref(nr)), "mie_last")
+        return ms.value, nb.value, nr.value
+
     def lbl_accumulator(self, wn_grid, t_calc, p_calc):
         """The runtime line-by-line opacity of a gas summed in HBM: a zeroed (L, nw) accumulator on this engine's device for
         the grid and the (T,p) points given (see LblAccumulator).  The engine owns one; a new one starts over."""

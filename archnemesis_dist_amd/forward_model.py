@@ -723,6 +723,52 @@ def install_gpu_pseudo_continuum(device=0):
     return add_pseudo_continuum_monochromatic_absorption
 
 
+MIE_MEMO_ENTRIES = 8                   # size distributions the Mie hook remembers (a Jacobian perturbs one parameter at a time)
+
+
+def install_gpu_mie(device=0):
+    """Route the module-level Scatter_0.makephase (Scatter_0.py:1828; the class method resolves the module attribute at call
+    time, :1340) -- Mie theory integrated over a particle size distribution, which model 444 recomputes in every forward
+    model -- through the GPU for iscat 1 .. 4.  iscat 5 / 6 / 7 (isotropic, Henyey-Greenstein, dipole) are closed forms and
+    are forwarded to the reference's function; that is no delegation.  A call the engine refuses (a Mie series the reference
+    gives up on, an open range that does not end, an angle outside [0, 90]) is delegated, so that the reference fails its
+    own way.  The hook remembers the last MIE_MEMO_ENTRIES results under the bytes of every argument: the NX + 1 states of a
+    staged Jacobian repeat all but a few size distributions bit for bit.  A remembered call returns copies, because the class
+    method scales and permutes `phas` in place (:1343-1344).  summary()["routes"] counts `mie` and `mie (memo)`."""
+    import importlib
+    from collections import OrderedDict
+    from ._lib import AnsfmError
+    sc = importlib.import_module("archnemesis.Scatter_0")
+    eng = get_engine(device)
+    ref_fn = getattr(sc, "_ansfm_reference_makephase", None) or sc.makephase
+    memo = OrderedDict()
+
+    def makephase(wavel, iscat, dsize, rs, refindx, theta):
+        if int(iscat) not in (1, 2, 3, 4):
+            return ref_fn(wavel, iscat, dsize, rs, refindx, theta)
+        args = [np.ascontiguousarray(a, dtype=np.float64) for a in (wavel, dsize, rs, refindx, theta)]
+        key = (int(iscat),) + tuple((a.shape, a.tobytes()) for a in args)
+        hit = memo.get(key)
+        if hit is not None:
+            memo.move_to_end(key)
+            _route("mie (memo)")
+            return tuple(a.copy() for a in hit)
+        try:
+            out = eng.mie_makephase(args[0], int(iscat), args[1], args[2], args[3], args[4])
+        except (ValueError, NotImplementedError, AnsfmError):
+            _delegate("makephase: a Mie integration the engine gives up on")
+            return ref_fn(wavel, iscat, dsize, rs, refindx, theta)
+        _route("mie")
+        memo[key] = tuple(np.array(a, dtype=np.float64) for a in out[:4])
+        while len(memo) > MIE_MEMO_ENTRIES:
+            memo.popitem(last=False)
+        return tuple(a.copy() for a in memo[key])
+
+    sc._ansfm_reference_makephase = ref_fn
+    sc.makephase = makephase
+    return makephase
+
+
 def install_gpu_gradient_maps(device=0):
     """Route ForwardModel_0.map2pro / map2xvec (ForwardModel_0.py:5319, :5387) -- the layer -> profile -> state-vector
     gradient maps nemesisfmg applies right after CIRSrad(return_grad=True) (:704-711) -- through the GPU.  The arrays
@@ -1027,7 +1073,7 @@ def install_all(device=0, oe_linalg=True, ktable_generator=True, forward_model=T
     if forward_model:
         install_gpu_forward_model(device); done.append("install_gpu_forward_model")
     for f in (install_gpu_gradient_maps, install_gpu_scattering_core, install_gpu_line_kernel, install_gpu_pseudo_continuum,
-              install_gpu_layering, install_gpu_convolution, install_gpu_continuum, install_gpu_table_reader):
+              install_gpu_mie, install_gpu_layering, install_gpu_convolution, install_gpu_continuum, install_gpu_table_reader):
         f(device); done.append(f.__name__)
     if oe_linalg:
         from .oe_linalg import install_gpu_oe_linalg

@@ -716,6 +716,29 @@ int ansfm_merge_redo_count(ansfm_ctx *ctx, int64_t *count);
  * (what CIRSrad leaves in LayerX.TAUGAS, ForwardModel_0.py:3925) -- host pointer out. */
 int ansfm_get_taugas(ansfm_ctx *ctx, int model, double *TAUGAS);
 
+/* ---- Mie theory over a particle size distribution ------------------------------------------------------------------------
+ * Scatter_0.makephase (module level, Scatter_0.py:1828) = miescat (:1600) over dmie (:1399) for iscat 1 gamma, 2 log-normal,
+ * 3 MCS modified gamma, 4 single size: what model 444 recomputes in every forward model.  wavel_um[nwave], dsize[3], rs[3] =
+ * first radius, last radius, step (um; rs[1] < rs[0]: open range, ended -- that radius included -- by the first radius at or
+ * beyond the distribution's peak whose n(r) Q_sca is at most 1e-6 of its running maximum), refindx[nwave][2] = real and
+ * imaginary part, theta_deg[ntheta] within [0, 90] ascending -> xscat / xext[nwave] (cm2) and phas[nwave][nphas] =
+ * lambda^2 sum / (pi k_sca) over the angles theta followed by 180 - theta in ascending order (nphas = 2 ntheta - 1 when
+ * 90 degrees is among them, else 2 ntheta): what miescat returns, before the class method divides by 4 pi.
+ * n_radii[nwave] (may be NULL): the radii each wavelength integrated over.
+ * The radii are processed in blocks (ansfm_mie_set_radius_block: a multiple of 64, 0 = the default 512); the sum over radii
+ * has one order -- chunks of 64 radii from radius 0, a fixed tree inside a chunk, chunks in ascending order -- so the block
+ * size changes no bit.  An open range that has not ended after the cap (ansfm_mie_set_radius_cap, 0 = the default 2^20
+ * radii) is ANSFM_ERR_INVALID "size integration did not terminate" (the reference would loop to 10^9).
+ * ANSFM_ERR_INVALID with the wavelength and radius in the text also where the reference gives up: nmx1 = int(1.1 |m| x) >=
+ * 29999, or a series that needs more than nmx2 = max(135, int(|m| x)) terms; and for an angle outside [0, 90] or iscat
+ * outside 1 .. 4.  ansfm_mie_last: kernel milliseconds, blocks and the largest block of the last call. */
+int ansfm_mie_makephase(ansfm_ctx *ctx, int nwave, const double *wavel_um, int iscat, const double dsize[3], const double rs[3],
+                        const double *refindx, int ntheta, const double *theta_deg, double *xscat, double *xext, double *phas,
+                        int32_t *n_radii);
+int ansfm_mie_set_radius_block(ansfm_ctx *ctx, int radii);
+int ansfm_mie_set_radius_cap(ansfm_ctx *ctx, int radii);
+int ansfm_mie_last(const ansfm_ctx *ctx, double *kernel_ms, int32_t *blocks, int32_t *block_radii);
+
 /* ---- measurement helpers (bench.py / profiling) -------------------------------------------
  * Time of the dominant kernel (ck_overlap) measured with hipEvents on the ctx stream around
  * the launches of the last cirsrad call: total milliseconds and number of launches. */

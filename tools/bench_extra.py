@@ -40,6 +40,8 @@ def main():
         bench_maps(eng, out, rng)
     if only in (None, "next"):
         bench_next(eng, out, rng)
+    if only == "mie":
+        bench_mie(eng, out)
     if only == "ss":                                        # 10 GB of host arrays: on request only
         bench_ss(eng, out, rng)
     print(json.dumps(out, indent=1))
@@ -344,6 +346,37 @@ def bench_lblrt(eng, out, nw=1000000, Ll=50, lines=100000, n_iso=3, n=3):
         "of_which_pack_and_set_state_wall_s": t_state, "with_T_plus_5_rows_wall_s": t_res_g,
         "per_call_entries_readback_table_upload_wall_s": t_old, "ratio": t_old / t_res,
         "spectrum_finite": bool(np.all(np.isfinite(spec)))}
+
+
+def bench_mie(eng, out, nwave=64, n=5):
+    """Scatter_0.makephase for one size distribution: 64 wavelengths over 0.4 - 5 um, log-normal (1.0, 0.4), m = 1.4 - 0.01i, the
+    reference's default 41 angles folded to <= 90 degrees (21), open range at the default step 0.015 lambda_min.  Kernel time
+    (hipEvents around each block's launches), the call end to end, the radii per wavelength, and the NumPy restatement of
+    tests/mie_cases.py on 4 of the wavelengths -- NOT a comparator: the reference runs numba-compiled loops, the
+    restatement is pure NumPy."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mie_cases as mc
+    wavel = np.exp(np.linspace(np.log(0.4), np.log(5.0), nwave))
+    theta = np.array([0, 1, 2, 3, 4, 5, 7.5, 10, 12.5, 15, 17.5, 20, 25, 30, 35, 40, 50, 60, 70, 80, 90.0])
+    dsize, rs = np.array([1.0, 0.4, 0.0]), np.array([0.015 * wavel.min(), 0.0, 0.015 * wavel.min()])
+    refindx = np.tile([1.4, 0.01], (nwave, 1))
+    res = {}
+    for block in (None, 64, 2048):
+        run = lambda: eng.mie_makephase(wavel, 2, dsize, rs, refindx, theta, radius_block=block, return_counts=True)
+        wall = timeit(run, n)
+        ms, blocks, radii = eng.mie_last()
+        res["block %s" % (block or "default")] = {"end_to_end_ms": 1e3 * wall, "kernel_ms": ms, "blocks": blocks, "block_radii": radii}
+    xs, xe, thetax, ph, counts = eng.mie_makephase(wavel, 2, dsize, rs, refindx, theta, return_counts=True)
+    pick = [0, nwave // 3, 2 * nwave // 3, nwave - 1]
+    t = time.perf_counter()
+    hs, he, _, hp, hc = mc.makephase_np(wavel[pick], 2, dsize, rs, refindx[pick], theta, chunk_order=True, return_counts=True)
+    host = time.perf_counter() - t
+    res["radii_min_max"] = [int(counts.min()), int(counts.max())]
+    res["radii_total"] = int(counts.sum())
+    res["host_restatement_s_per_wavelength_not_representative"] = host / len(pick)
+    res["host_vs_gpu"] = {"counts_equal": bool(np.array_equal(hc, counts[pick])),
+                          "xext_rel": float(np.max(np.abs(xe[pick] / he - 1))), "phas_rel": float(np.max(np.abs(ph[pick] / hp - 1)))}
+    out["mie_lognormal_64_wavelengths"] = res
 
 
 def bench_layer(eng, out):
