@@ -56,7 +56,7 @@ def hipcc_path():
 
 def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into lib/libansfm.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, "ansfm_api.hip"), os.path.join(CSRC, "ansfm_kdist.hip"), os.path.join(CSRC, "ansfm_merge32.hip")]
+    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(INCLUDE, "ansfm.h")]
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(d) for d in deps)
@@ -75,7 +75,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd))
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=len(srcs)) as pool:
+    with ThreadPoolExecutor(max_workers=min(len(srcs), 8)) as pool:
         list(pool.map(compile_one, zip(srcs, objs)))
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
     if verbose:

@@ -1,0 +1,210 @@
+// ansfm_ctx.hip.h -- what the host translation units of libansfm.so share: the context, the error macros, the staging of
+// host pointers and the declarations of the host helpers that one unit defines and another calls.  No kernel lives here, and
+// no kernel header is included: a header that defines kernels belongs to exactly one .hip.
+//   ansfm_api.hip      lifecycle, tables, the gas-opacity stage, thermal / transmission / single-scattering RT and gradients
+//   ansfm_scatter.hip  multiple scattering
+//   ansfm_lbl.hip      runtime line-by-line
+//   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
+//   ansfm_mie.hip      Mie theory over size distributions
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(default)
+#include "../../include/ansfm.h"
+#pragma GCC visibility pop
+
+namespace ansfm {
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t n)
+    {
+        if (n <= bytes) return hipSuccess;
+        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; bytes = 0; }
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// One isotopologue of the runtime line source (ansfm_lblrt_*): everything that stays fixed over a retrieval, in HBM
+struct LblrtIso {
+    int lineshape_id = 0, include_lines = 0, include_continuum = 0;
+    double abundance = 0, mass = 0;
+    int N = 0;                           // lines, sorted by wavenumber: lines = nu, sw, e_lower, stim_ref [N], bparams [3M][N]
+    double t_ref = 0, p_ref = 0, s_floor = 0, wn_calc_window = 0, wn_approx_window = 0;
+    DevBuf lines;
+    std::vector<double> dabs;            // [M] the largest |delta| of a broadener over the lines: bounds the pressure shift
+    int Nb = 0, nb = 0;                  // pseudo-continuum bins: bins = centers, widths, sw_sum, e_lower, lo [Nb], bparams [3M][Nb]
+    int first = 0, last = 0, jmax = 0;
+    double t_cont = 0, p_cont = 0, wmax = 0;
+    DevBuf bins;
+};
+
+}  // namespace ansfm
+
+using ansfm::DevBuf;
+using ansfm::LblrtIso;
+
+struct ansfm_ctx {
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    std::string err;
+    int num_cus = 256;
+
+    // k-table
+    int W = 0, Wpad = 0, G = 0, NP = 0, NT = 0, S = 0;
+    int monotone = 0;
+    int has_boxed = 1;        // some table entry is <= 0 or NaN (stored NaN-boxed, encode_lnk); 0 selects the box-free load path
+    std::vector<double> h_wave, h_press, h_temp;   // host copies of the grids of the table in HBM
+    DevBuf dcont_gas;                       // ansfm_set_shared_gas_gradient: [L][Wpad], consumed by the next cirsradg call
+    int dcont_gas_L = 0;                    // 0: none pending
+    unsigned grad_gas_mask = 0xFFFFFFFFu;   // ansfm_set_gradient_gases: gases whose amount gradients cirsradg computes
+    int merge_keys = 64;     // 32: run the forward merge on k_ck_overlap32's float32 keys (ansfm_set_merge_keys)
+    bool have_table = false;
+    int grid_f32 = 0, delg_f32 = 0;
+    int is_lbl = 0, temp2d = 0;   // LBL-table mode (ILBL=2): G = 1, TEMP may be [NP][NT]
+    DevBuf lnK, d_press, d_temp, d_wave, d_delg, d_flag;
+    std::vector<double> h_delg;
+
+    // workspaces
+    DevBuf li, tau, scratch, cont_t, tmp_in, tmp_out, misc;
+    DevBuf dspec_ref, map_out, map_b, map_batch;
+    DevBuf dd_slot, dd_work, dd_in;      // layer de-duplication: row map [n][L], work list, packed inputs
+    DevBuf ms_radg16, ms_brdf16;         // 7 .. 15 streams padded to the 16-stream kernels' layout
+    DevBuf rt_prefix, rt_same;           // thermal RT of a batch: state 0's records along every path; same flags [n][L] (single scattering: [n][P][L]) + jstart [n][P]
+    int last_rt_shared = 0;
+    int dedup = 1;                       // ansfm_set_layer_dedup
+    int last_rows = 0, last_dedup = 0;   // opacity rows computed by the last cirsrad call / whether tau_slot applies
+    int dspec_dims[4] = {0, 0, 0, 0};   // W, NPAR, LIMAX, P of dspec_ref (single-model cirsradg result)
+    int map_dims[4] = {0, 0, 0, 0};     // W, NPAR, NPRO, P of map_out
+    DevBuf gscratch, perm, dkbuf, trold_ws, dspec_i, dcont_t, tmp_in2, tmp_out2, lbl_li;
+    DevBuf ms_taus, ms_omegas, ms_bnu;   // scattering branch of CIRSrad: TAUTOT / OMEGA (W,G,L) and BB (W,L) in HBM
+    DevBuf ms_tauray_l, ms_lfrac_l;      // the continuum by rows: TAURAY / aerosol fractions of a launch's models (the model-by-model route: one model's dense arrays)
+    DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
+    long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
+    long ms_windows = 0, ms_window_w = 0;          // spectral windows of phase matrices / Hansen factors of the last scattering call, their size
+    DevBuf hb[24];  // staging buffers of the host-pointer entry points
+    // runtime line-by-line: the opacity of a gas, summed in HBM (ansfm_lbl_accum_*); its grid and (T, p) points [2][L]
+    DevBuf acc, acc_grid, acc_tp;
+    int acc_nw = 0, acc_L = 0;           // 0: no accumulator begun
+    std::vector<double> acc_h_grid, acc_h_p;
+    int last_n = 0, last_L = 0;
+    int dk_n = 0, dk_L = 0;              // models / layers of the gas-opacity derivatives in dkbuf (ansfm_get_dtaugas); 0: none
+    // runtime line-by-line as the context's opacity source (ansfm_lblrt_*): 0 none, 1 begun, 2 committed; lblrt: the
+    // committed source stands in for the table (is_lbl = 1, G = 1, W = nw) until a table is uploaded
+    int rt_stage = 0, lblrt = 0, rt_nw = 0, rt_S = 0, rt_M = 0;
+    std::vector<double> rt_h_grid;
+    DevBuf rt_grid, rt_k, rt_pts, rt_scratch, rt_krow;   // grid; k rows [R][H][nw]; staged points; line / bin constants; krow [n][S][L]
+    std::vector<std::vector<std::unique_ptr<LblrtIso>>> rt_gas;   // [S][isotopologues]
+    size_t rt_budget = (size_t)256 << 20;                // bytes of rt_scratch a chunk of rows may take
+    int st_n = 0, st_L = 0, st_R = 0, st_H = 0;          // the state of ansfm_lblrt_set_state; st_n = 0: none
+    int st_m0 = -1;                                      // >= 0: the model-by-model loop of a batch is at this model
+    int rt_last_rows = 0, rt_last_points = 0, rt_last_chunks = 0;
+    // Mie theory over a size distribution (ansfm_mie_makephase): D_n and the series coefficients of a block of radii; inputs,
+    // per-thread and per-wavelength state, chunk sums, totals and outputs
+    DevBuf mie_ws, mie_st;
+    int mie_block = 0, mie_cap = 0;                      // 0: the defaults (kMieBlockDefault radii, 2^20 radii)
+    double mie_ms = 0;                                   // kernel time, blocks and the largest block of the last call
+    int mie_blocks = 0, mie_block_radii = 0;
+
+    // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
+    hipStream_t ms_stream = nullptr;
+    hipStream_t ms_stream2 = nullptr;   // chains of the odd g-ordinates: consecutive chain launches overlap their tails
+    hipStream_t ms_stream3 = nullptr;   // G = 1 windows: phase matrices two windows ahead of the chains
+    std::vector<hipEvent_t> ms_ev;
+    // timing of the last cirsrad call
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double overlap_ms = 0, rt_ms = 0;
+    int overlap_launches = 0, rt_launches = 0;
+
+    // the buffers free themselves (DevBuf); streams and events go here
+    ~ansfm_ctx()
+    {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+#define CHECK_CTX(ctx) do { if (!(ctx)) return ANSFM_ERR_INVALID; } while (0)
+#define HIPCHK(expr)                                                                          \
+    do {                                                                                      \
+        hipError_t e__ = (expr);                                                              \
+        if (e__ != hipSuccess) {                                                              \
+            char b__[512];                                                                    \
+            snprintf(b__, sizeof b__, "%s:%d: %s -> %s", __FILE__, __LINE__, #expr,           \
+                     hipGetErrorString(e__));                                                 \
+            ctx->err = b__;                                                                   \
+            return ANSFM_ERR_HIP;                                                             \
+        }                                                                                     \
+    } while (0)
+#define FAIL(code, msg) do { ctx->err = (msg); return (code); } while (0)
+
+namespace ansfm {
+
+static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+static inline unsigned nblk(size_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+/* ---- helpers that one translation unit defines and another calls ------------------------------------------------------- */
+// ansfm_api.hip, the gas-opacity stage (described where they are defined)
+int gas_tau(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount, bool generic,
+            double *dk = nullptr);
+int gas_opacity(ansfm_ctx *ctx, int rows, const double *press, const double *temp, const double *amount);
+struct DedupRows {
+    int rows;
+    const double *press, *temp, *amount;
+};
+int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
+               const double *ray_totam, const double *ray_f4, DedupRows *out);
+// ansfm_lbl.hip: k_lblrt_tau for gas_tau, on the n models from m0 of the state of ansfm_lblrt_set_state
+void launch_lblrt_tau(ansfm_ctx *ctx, int n, int L, int m0, const double *amount, double *dk);
+// ansfm_ops.hip: k_tau_rayleigh_rows for the thermal branch, into ctx->cont_t [rows][Wpad]; slot_rows: the de-duplication's work
+// list, or nullptr for every (model, layer) in order
+void launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int ISPACE, const int32_t *slot_rows, const double *ray_totam,
+                              const double *ray_f4);
+
+/* ---- host -> device staging of the host-pointer entry points --------------------------------------------------------- */
+inline int h2d(ansfm_ctx *ctx, DevBuf &b, const void *src, size_t bytes, const void **out)
+{
+    *out = nullptr;
+    if (!src || bytes == 0) return ANSFM_OK;
+    HIPCHK(b.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *out = b.p;
+    return ANSFM_OK;
+}
+
+// The k-th up() of an entry point copies `count` elements into ctx->hb[slot + k] and returns the device copy; a null pointer
+// or a zero count gives nullptr.  After an error up() stages nothing more and rc holds its code.  An entry point that stages
+// calls no other that stages while its staged pointers are in use.
+struct Stager {
+    ansfm_ctx *ctx;
+    int slot = 0;
+    int rc = ANSFM_OK;
+    template <class T> const T *up(const T *src, size_t count)
+    {
+        const void *d = nullptr;
+        if (rc == ANSFM_OK) rc = h2d(ctx, ctx->hb[slot++], src, count * sizeof(T), &d);
+        return static_cast<const T *>(d);
+    }
+};
+
+}  // namespace ansfm

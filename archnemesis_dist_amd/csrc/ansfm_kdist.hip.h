@@ -1,4 +1,4 @@
-// ansfm_kdist.hip.h -- parameters shared by the k-distribution generator (ansfm_kdist.hip) and the C-ABI (ansfm_api.hip)
+// ansfm_kdist.hip.h -- parameters shared by the k-distribution generator (ansfm_kdist.hip) and the C-ABI (ansfm_ops.hip)
 #pragma once
 #include <stdint.h>
 

@@ -27,6 +27,35 @@ def test_library_exports_every_declared_symbol():
     assert lib.ansfm_abi_version() == 1
 
 
+def test_every_kernel_header_has_one_translation_unit(tmp_path, monkeypatch):
+    """A header that defines a __global__ function is compiled into exactly one object: a second one would collide at link
+    (plain kernels) or instantiate and ship the same template kernels twice.  Source text only."""
+    from archnemesis_dist_amd import _lib
+    units = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith(".hip"))
+    headers = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith(".h"))
+
+    def reached(name, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(_lib.CSRC, name)).read(), flags=re.M):
+            if os.path.dirname(inc) == "" and inc not in seen and os.path.exists(os.path.join(_lib.CSRC, inc)):
+                seen.add(inc)
+                reached(inc, seen)
+        return seen
+
+    owners = {h: [u for u in units if h in reached(u, set())] for h in headers}
+    kernel_headers = [h for h in headers if re.search(r"\b__global__\b", open(os.path.join(_lib.CSRC, h)).read())]
+    assert len(kernel_headers) >= 11
+    for h in kernel_headers:
+        assert len(owners[h]) == 1, f"{h} is reached from {owners[h]}"
+
+    # what build() compiles: its commands, recorded instead of run
+    cmds = []
+    monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "lib" / "libansfm.so"))
+    monkeypatch.setattr(_lib.subprocess, "check_call", lambda cmd, **kw: cmds.append(cmd))
+    _lib.build(force=True)
+    compiled = sorted(os.path.basename(c[c.index("-c") + 1]) for c in cmds if "-c" in c)
+    assert compiled == units
+
+
 def test_no_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():

@@ -1871,6 +1871,66 @@ def _singlescatt_vs_oracle(eng, oracle, unsorted):
         np.testing.assert_allclose(got, ref, rtol=1e-11)
 
 
+def test_entry_points_of_every_translation_unit_share_one_context(eng, oracle, golden_dir):
+    """The entry points live in several translation units (csrc/ansfm_api, _scatter, _mie, _ops) over one context and its
+    workspaces.  A de-duplicated thermal batch, then a scattering call, a Mie call and a layering call on the same engine,
+    then the thermal batch again: the same bits and the same opacity rows as the first time, and every call in between
+    within the bound of its own test (test_cirsrad_scatter_vs_oracle, test_mie_gpu.test_golden_cases,
+    test_layer_average_golden)."""
+    import mie_cases as mc
+    from archnemesis_dist_amd import synthetic as syn
+    from test_layer_oracle import NAMES, CASES
+    from test_mie_gpu import BOUNDS as MIE_BOUNDS
+    from test_scatter_wavenumber_shard import _ktable_case
+    W, G, S, L, NP, NT = 96, 20, 4, 12, 6, 5
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    PRESS, TEMP, K = syn.synth_ktable(W, G, NP, NT, S, seed=1)
+    WAVE = 300.0 + np.arange(W) * 1.0
+    atm = syn.synth_atmosphere(L, S, seed=2)
+    lp = np.repeat(atm["lay_press_pa"], 3, 0); lt = np.repeat(atm["lay_temp"], 3, 0); am = np.repeat(atm["amount"], 3, 0)
+    lt[1, 4] *= 1.01; lt[2, 9] *= 0.99
+    NLAYIN, LAYINC, SCALE = syn.nadir_path(L, 10.0)
+    EMTEMP = lt[:, LAYINC[:, 0]][:, :, None]
+    cont = np.repeat(syn.synth_continuum(W, L), 3, 0)
+    thermal = (0, lp, lt, am, cont, NLAYIN, LAYINC, np.repeat(SCALE[None], 3, 0), EMTEMP, np.full(3, -1.0))
+    eng.set_layer_dedup(True)
+    eng.upload_ktable(K, PRESS, TEMP, WAVE, delg)
+    first = eng.cirsrad_ck_thermal(*thermal)
+    rows_first = eng.last_layer_rows()
+    assert rows_first == (L + 2, 3 * L)
+
+    # 5 streams, NF = 2, one aerosol and Rayleigh, two geometries, on the table in the context
+    NMU, NF, lowbc = 5, 2, 0
+    z = _ktable_case(NMU, NF, lowbc, W=W, G=G, L=L, S=S)
+    z.update(K=K, TPRESS=PRESS, TTEMP=TEMP, WAVE=WAVE, DELG=delg)
+    sol = np.array([30.0, 120.0]); emi = np.array([20.0, 50.0]); azi = np.array([45.0, 0.0])
+    out, spec_g = eng.cirsrad_ck_scatter(0, z["lay_p"], z["lay_t"], z["amount"], z["TAUCIA"], z["TAUDUST"], z["TAURAY"], z["TAUSCAT"],
+                                         z["phasarr"], z["lfrac"], z["radg"], sol, emi, azi, z["solar"], lowbc, z["brdf"], z["MU"], z["WT"],
+                                         NF, 101, 1, 1, return_spec_g=True)
+    ref, ref_g, taugas = _scatter_oracle(oracle, z, sol, emi, azi, lowbc, NF, 101, 1, 1)
+    np.testing.assert_allclose(eng.get_taugas(L, 0), taugas, rtol=1e-11, atol=0)
+    assert np.max(np.abs(spec_g - ref_g)) / np.max(np.abs(ref_g)) < 1e-8
+    assert np.max(np.abs(out - ref)) / np.max(np.abs(ref)) < 1e-8
+
+    name = min(mc.EXPECTED_RADII, key=mc.EXPECTED_RADII.get)
+    m = mc.load_golden(os.path.join(golden_dir, "mie.npz"))[name]
+    xs, xe, thetax, ph, counts = eng.mie_makephase(m["wavel"], int(m["iscat"]), m["dsize"], m["rs"], m["refindx"], m["theta"],
+                                                   return_counts=True)
+    assert np.array_equal(counts, m["n_radii"]) and np.array_equal(thetax, m["thetax"])
+    assert all(d <= b for d, b in zip(mc.deviations((xs, xe, ph), m), MIE_BOUNDS))
+
+    y = _load(golden_dir, "layer_average")
+    r = eng.layer_average(float(y["RADIUS"]), y["H"], y["P"], y["T"], None, y["VMR"], y["DUST"], y["PARAH2"], y["split1_BASEH"],
+                          y["split1_BASEP"], LAYHT=-6.0e4, NINT=101, DUST_UNITS=None, XMOLWT=None, **CASES["cg_nadir"])
+    for n, v in zip(NAMES, r):
+        np.testing.assert_allclose(v, y[f"cg_nadir_{n}"], rtol=1e-10, err_msg=n)
+
+    again = eng.cirsrad_ck_thermal(*thermal)
+    assert np.array_equal(again, first)
+    assert eng.last_layer_rows() == rows_first
+    assert not np.array_equal(first[0], first[1]) and not np.array_equal(first[0], first[2])
+
+
 def test_closing_an_engine_returns_its_device_memory():
     """Every buffer, stream and event an engine holds goes when it is closed.  Engines run a batched thermal call at C2 size
     that takes the prefix route of the RT (its state-0 records: about 1 GB with two paths) and a 12-stream scattering call
