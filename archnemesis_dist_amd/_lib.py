@@ -38,6 +38,7 @@ EXPORTS = [
     "ansfm_lblrt_set_scratch_bytes", "ansfm_lblrt_last", "ansfm_calc_klbl_online", "ansfm_calc_klblg_online",
     "ansfm_get_dtaugas",
     "ansfm_mie_makephase", "ansfm_mie_set_radius_block", "ansfm_mie_set_radius_cap", "ansfm_mie_last",
+    "ansfm_surface_brdf", "ansfm_brdf_matrix", "ansfm_brdf_last",
 ]
 
 _lib = None
@@ -187,6 +188,9 @@ def load():
     lib.ansfm_mie_set_radius_block.argtypes = [vp, ci]
     lib.ansfm_mie_set_radius_cap.argtypes = [vp, ci]
     lib.ansfm_mie_last.argtypes = [vp, C.POINTER(cd), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ansfm_surface_brdf.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp]
+    lib.ansfm_brdf_matrix.argtypes = [vp, ci, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.ansfm_brdf_last.argtypes = [vp, C.POINTER(cd)]
     lib.ansfm_layer_average.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 11
     lib.ansfm_layer_average_dev.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp, vp]
     lib.ansfm_layer_averageg.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 15

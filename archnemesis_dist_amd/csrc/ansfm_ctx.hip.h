@@ -6,6 +6,7 @@
 //   ansfm_lbl.hip      runtime line-by-line
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
+//   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -124,6 +125,9 @@ struct ansfm_ctx {
     int mie_block = 0, mie_cap = 0;                      // 0: the defaults (kMieBlockDefault radii, 2^20 radii)
     double mie_ms = 0;                                   // kernel time, blocks and the largest block of the last call
     int mie_blocks = 0, mie_block_radii = 0;
+    // surface reflection (ansfm_surface_brdf, ansfm_brdf_matrix): the result, the per-azimuth table, kernel time of the last call
+    DevBuf brdf_out, brdf_azi;
+    double brdf_ms = 0;
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;

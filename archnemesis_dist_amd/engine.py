@@ -826,6 +826,75 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_mie_last(self._ctx, C.byref(ms), C.byref(nb), C.byref(nr)), "mie_last")
         return ms.value, nb.value, nr.value
 
+    SURFACE_NPAR = {1: 1, 2: 10, 3: 2}     # rows of `params` per LowerBoundaryConditionEnum value
+
+    def _surface_params(self, what, lowbc, params, zero_ok=False):
+        lowbc = int(lowbc)
+        if lowbc not in self.SURFACE_NPAR and not (zero_ok and lowbc == 0):
+            raise ValueError("%s: lowbc %d is not 1 LAMBERTIAN, 2 HAPKE or 3 OREN_NAYAR%s" % (what, lowbc, ", or 0" if zero_ok else ""))
+        params = np.atleast_2d(_np(params))
+        if params.ndim != 2 or params.shape[1] < 1 or (lowbc and params.shape[0] != self.SURFACE_NPAR[lowbc]):
+            raise ValueError("%s: params must be (%s, nwave) for lowbc %d, got %s"
+                             % (what, self.SURFACE_NPAR.get(lowbc, "any"), lowbc, params.shape))
+        return lowbc, params
+
+    def surface_brdf(self, lowbc, params, SOL_ANG, EMISS_ANG, AZI_ANG):
+        """Surface_0.calc_BRDF (:916) after its interpolation onto the wavenumbers: params (npar, nwave) -- LOWBC 1 the albedo,
+        2 the ten arguments of calc_Hapke_BRDF in its order, 3 (A, ROUGHNESS) -- at the angle triples SOL_ANG, EMISS_ANG,
+        AZI_ANG (NTHETA,) in degrees -> BRDF (nwave, NTHETA)."""
+        lowbc, params = self._surface_params("surface_brdf", lowbc, params)
+        sol, emi, azi = (_np(np.atleast_1d(a)) for a in (SOL_ANG, EMISS_ANG, AZI_ANG))
+        if sol.ndim != 1 or sol.shape[0] < 1 or emi.shape != sol.shape or azi.shape != sol.shape:
+            raise ValueError("surface_brdf: SOL_ANG, EMISS_ANG and AZI_ANG must be 1-D of one length, got %s %s %s"
+                             % (sol.shape, emi.shape, azi.shape))
+        nwave, ntheta = params.shape[1], sol.shape[0]
+        out = np.empty((nwave, ntheta))
+        rc = self._lib.ansfm_surface_brdf(self._ctx, lowbc, nwave, _ptr(params), ntheta, _ptr(sol), _ptr(emi), _ptr(azi), _ptr(out))
+        self._check(rc, "surface_brdf")
+        return out
+
+    @staticmethod
+    def brdf_tables(MU, NPHI, NF):
+        """The tables of ansfm_brdf_matrix that depend on the quadrature alone, in calc_brdf_matrix's own expressions
+        (ForwardModel_0.py:5198-5245) so that they carry its bits: MU as Scatter stores it -> the angles of MU[::-1], the
+        azimuths k dphi in degrees, their fold into [0, 180] (Surface_0.py:1363-1381), wphi and cos(ic k dphi)."""
+        mu = np.zeros(len(MU))
+        mu[:] = np.asarray(MU, dtype=_f8)[::-1]
+        dphi = 2.0 * np.pi / NPHI
+        k = np.arange(NPHI + 1)
+        ang = np.arccos(mu) * 180.0 / np.pi
+        azi = (k * dphi) * 180.0 / np.pi
+        phi = 180. - azi
+        phix = np.where(phi > 180., 180. - (phi - 180.), np.where(phi < 0., -phi, phi))
+        wphi = np.full(NPHI + 1, (1.0 * dphi) / (2.0 * np.pi))
+        wphi[0] = wphi[NPHI] = (0.5 * dphi) / (2.0 * np.pi)
+        cosk = np.cos(np.arange(NF + 1)[:, None] * (k * dphi)[None, :])
+        return ang, azi, phix, wphi, np.ascontiguousarray(cosk)
+
+    def brdf_matrix(self, lowbc, params, MU, NPHI, NF):
+        """ForwardModel_0.calc_brdf_matrix (:5168) after the interpolation of the surface parameters onto the wavenumbers:
+        params as for surface_brdf, MU = Scatter.MU as stored (it is reversed here, as there) -> BRDF_mat (nwave, NMU, NMU,
+        NF + 1).  LOWBC 2 is integrated over azimuth on the device; 1 gives albedo / pi in plane 0; 0 and 3 give zeros."""
+        lowbc, params = self._surface_params("brdf_matrix", lowbc, params, zero_ok=True)
+        MU = _np(np.atleast_1d(MU))
+        NPHI, NF = int(NPHI), int(NF)
+        if MU.ndim != 1 or MU.shape[0] < 1 or NPHI < 1 or NF < 0:
+            raise ValueError("brdf_matrix: nmu >= 1, nphi >= 1 and nf >= 0 are needed, got nmu %s, nphi %d, nf %d"
+                             % (MU.shape, NPHI, NF))
+        ang, azi, phix, wphi, cosk = self.brdf_tables(MU, NPHI, NF)
+        nwave, nmu = params.shape[1], MU.shape[0]
+        out = np.empty((nwave, nmu, nmu, NF + 1))
+        rc = self._lib.ansfm_brdf_matrix(self._ctx, lowbc, nwave, _ptr(params), nmu, _ptr(ang), NPHI, NF, _ptr(azi), _ptr(phix),
+                                         _ptr(wphi), _ptr(cosk), _ptr(out))
+        self._check(rc, "brdf_matrix")
+        return out
+
+    def brdf_last(self):
+        """kernel milliseconds of the last surface_brdf / brdf_matrix call"""
+        ms = C.c_double()
+        self._check(self._lib.ansfm_brdf_last(self._ctx, C.byref(ms)), "brdf_last")
+        return ms.value
+
     def lbl_accumulator(self, wn_grid, t_calc, p_calc):
         """The runtime line-by-line opacity of a gas summed in HBM: a zeroed (L, nw) accumulator on this engine's device for
         the grid and the (T,p) points given (see LblAccumulator).  The engine owns one; a new one starts over."""

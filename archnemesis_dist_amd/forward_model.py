@@ -769,6 +769,89 @@ def install_gpu_mie(device=0):
     return makephase
 
 
+BRDF_MEMO_ENTRIES = 2                  # BRDF matrices the surface hook remembers: no model of the reference retrieves a Hapke
+                                       # parameter, and one matrix is 0.18 GB at W = 10^4, NMU = 16, NF = 8
+HAPKE_ATTRS = ("SGLALB", "K", "BS0", "hs", "BC0", "hc", "ROUGHNESS", "G1", "G2", "F")   # calc_Hapke_BRDF's order
+
+
+def install_gpu_surface(device=0):
+    """Route surface reflection through the GPU.
+
+    The module-level Surface_0.calc_Hapke_BRDF (Surface_0.py:1292) and calc_OrenNayar_BRDF (:1743) are replaced: the class
+    method Surface_0.calc_BRDF (:916) resolves them by global name at call time, which also routes the single-scattering
+    branch's calc_BRDF(WAVE, SOL_ANG, EMISS_ANG, AZI_ANG) (ForwardModel_0.py:4307).  ForwardModel_0.calc_brdf_matrix
+    (:5168) -- for LOWBC = HAPKE NMU^2 (NPHI + 1) BRDF evaluations per wavenumber and a four-deep interpreter loop over
+    them -- becomes one engine call: the np.interp of the ten parameters onto WAVEC stays on the host, as in calc_BRDF
+    (:952-961); every other LOWBC goes to the reference's method unchanged, which is no delegation.  The GPU forward-model
+    class inherits the override.  The hook remembers the last BRDF_MEMO_ENTRIES matrices under the bytes of every argument
+    and returns copies: the NX + 1 states of a staged Jacobian then cost one evaluation.  A call the engine refuses is
+    delegated.  summary()["routes"] counts `brdf matrix`, `brdf matrix (memo)` and `brdf points`."""
+    import importlib
+    from collections import OrderedDict
+    from ._lib import AnsfmError
+    su = importlib.import_module("archnemesis.Surface_0")
+    fm = importlib.import_module("archnemesis.ForwardModel_0")
+    eng = get_engine(device)
+    cls = fm.ForwardModel_0
+    ref_hapke = getattr(su, "_ansfm_reference_calc_Hapke_BRDF", None) or su.calc_Hapke_BRDF
+    ref_oren = getattr(su, "_ansfm_reference_calc_OrenNayar_BRDF", None) or su.calc_OrenNayar_BRDF
+    ref_matrix = getattr(cls, "_ansfm_reference_calc_brdf_matrix", None) or cls.calc_brdf_matrix
+    refused = (ValueError, NotImplementedError, AnsfmError)
+    memo = OrderedDict()
+
+    def calc_Hapke_BRDF(w, K, BS0, hs, BC0, hc, ROUGHNESS, G1, G2, F, i, e, phi):
+        try:
+            out = eng.surface_brdf(2, np.stack([np.asarray(a, dtype=np.float64) for a in (w, K, BS0, hs, BC0, hc, ROUGHNESS, G1, G2, F)]),
+                                   i, e, phi)
+        except refused:
+            _delegate("calc_Hapke_BRDF: arguments the engine refuses")
+            return ref_hapke(w, K, BS0, hs, BC0, hc, ROUGHNESS, G1, G2, F, i, e, phi)
+        _route("brdf points")
+        return out
+
+    def calc_OrenNayar_BRDF(A, ROUGHNESS, i, e, phi):
+        try:
+            out = eng.surface_brdf(3, np.stack([np.asarray(a, dtype=np.float64) for a in (A, ROUGHNESS)]), i, e, phi)
+        except refused:
+            _delegate("calc_OrenNayar_BRDF: arguments the engine refuses")
+            return ref_oren(A, ROUGHNESS, i, e, phi)
+        _route("brdf points")
+        return out
+
+    def calc_brdf_matrix(self, WAVEC=None, Scatter=None, Surface=None):
+        WAVEC = self.SpectroscopyX.WAVE if WAVEC is None else WAVEC
+        Sc = self.ScatterX if Scatter is None else Scatter
+        Su = self.SurfaceX if Surface is None else Surface
+        if int(Su.LOWBC) != 2:
+            return ref_matrix(self, WAVEC, Sc, Su)
+        params = np.stack([np.interp(WAVEC, Su.VEM, getattr(Su, name)) for name in HAPKE_ATTRS])
+        MU = np.ascontiguousarray(Sc.MU, dtype=np.float64)[:int(Sc.NMU)]
+        key = (int(Sc.NPHI), int(Sc.NF), params.shape, params.tobytes(), MU.tobytes())
+        hit = memo.get(key)
+        if hit is not None:
+            memo.move_to_end(key)
+            _route("brdf matrix (memo)")
+            return hit.copy()
+        try:
+            out = eng.brdf_matrix(2, params, MU, int(Sc.NPHI), int(Sc.NF))
+        except refused:
+            _delegate("calc_brdf_matrix: a quadrature the engine refuses")
+            return ref_matrix(self, WAVEC, Sc, Su)
+        _route("brdf matrix")
+        memo[key] = np.array(out, dtype=np.float64)
+        while len(memo) > BRDF_MEMO_ENTRIES:
+            memo.popitem(last=False)
+        return memo[key].copy()
+
+    su._ansfm_reference_calc_Hapke_BRDF = ref_hapke
+    su._ansfm_reference_calc_OrenNayar_BRDF = ref_oren
+    cls._ansfm_reference_calc_brdf_matrix = ref_matrix
+    su.calc_Hapke_BRDF = calc_Hapke_BRDF
+    su.calc_OrenNayar_BRDF = calc_OrenNayar_BRDF
+    cls.calc_brdf_matrix = calc_brdf_matrix
+    return calc_brdf_matrix
+
+
 def install_gpu_gradient_maps(device=0):
     """Route ForwardModel_0.map2pro / map2xvec (ForwardModel_0.py:5319, :5387) -- the layer -> profile -> state-vector
     gradient maps nemesisfmg applies right after CIRSrad(return_grad=True) (:704-711) -- through the GPU.  The arrays
@@ -1073,7 +1156,8 @@ def install_all(device=0, oe_linalg=True, ktable_generator=True, forward_model=T
     if forward_model:
         install_gpu_forward_model(device); done.append("install_gpu_forward_model")
     for f in (install_gpu_gradient_maps, install_gpu_scattering_core, install_gpu_line_kernel, install_gpu_pseudo_continuum,
-              install_gpu_mie, install_gpu_layering, install_gpu_convolution, install_gpu_continuum, install_gpu_table_reader):
+              install_gpu_mie, install_gpu_surface, install_gpu_layering, install_gpu_convolution, install_gpu_continuum,
+              install_gpu_table_reader):
         f(device); done.append(f.__name__)
     if oe_linalg:
         from .oe_linalg import install_gpu_oe_linalg

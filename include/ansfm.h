@@ -739,6 +739,35 @@ int ansfm_mie_set_radius_block(ansfm_ctx *ctx, int radii);
 int ansfm_mie_set_radius_cap(ansfm_ctx *ctx, int radii);
 int ansfm_mie_last(const ansfm_ctx *ctx, double *kernel_ms, int32_t *blocks, int32_t *block_radii);
 
+/* ---- Surface reflection ----------------------------------------------------------------------------------------------------
+ * lowbc takes the values of LowerBoundaryConditionEnum and decides the rows of params[npar][nwave]:
+ *   1 LAMBERTIAN  the albedo
+ *   2 HAPKE       the ten arguments of calc_Hapke_BRDF (Surface_0.py:1292) in its order: w, K, BS0, hs, BC0, hc, ROUGHNESS,
+ *                 G1, G2, F
+ *   3 OREN_NAYAR  A, ROUGHNESS (calc_OrenNayar_BRDF :1743)
+ * -- the parameters on the calculation wavenumbers, i.e. after the np.interp of Surface_0.calc_BRDF (:944-971).
+ *
+ * ansfm_surface_brdf: Surface_0.calc_BRDF (:916) at ntheta angle triples (solar zenith, emission, azimuth; degrees, the
+ * azimuth in the reference's convention: 180 is backscattering) -> brdf[nwave][ntheta].  Hapke: 0 where an angle is >= 90.
+ *
+ * ansfm_brdf_matrix: ForwardModel_0.calc_brdf_matrix (ForwardModel_0.py:5168) -> brdf_mat[nwave][nmu][nmu][nf + 1], indexed
+ * [w][emission i][solar j][Fourier order]: for HAPKE the sum over the azimuth nodes k = 0 .. nphi, in that order, of
+ * wphi[k] BRDF(ang[j], ang[i], azi[k]) cos(ic k dphi); for LAMBERTIAN plane 0 = albedo / pi and zeros above; for 0 and 3 zeros
+ * (params and the tables may be NULL then), as the reference returns.  The tables are the caller's, in the reference's own
+ * expressions, so that the exact comparisons of the point function see the reference's bits:
+ *   ang_deg[nmu]         arccos(MU[::-1]) * 180 / pi
+ *   azi_deg[nphi + 1]    (k dphi) * 180 / pi, dphi = 2 pi / nphi  (with nphi = 100 the last one is 360.00000000000006)
+ *   phix_deg[nphi + 1]   180 - azi_deg folded into [0, 180] (:1363-1381); checked against azi_deg
+ *   wphi[nphi + 1]       dphi / (2 pi), (0.5 dphi) / (2 pi) at both ends
+ *   cosk[nf + 1][nphi + 1]  cos(ic (k dphi))
+ * nf <= 32.  ANSFM_ERR_INVALID, before anything is launched, for an unknown lowbc, sizes out of range, a null pointer or a
+ * phix that is not the fold of its azimuth.  ansfm_brdf_last: kernel milliseconds of the last call of either. */
+int ansfm_surface_brdf(ansfm_ctx *ctx, int lowbc, int nwave, const double *params, int ntheta, const double *sol_ang,
+                       const double *emiss_ang, const double *azi_ang, double *brdf);
+int ansfm_brdf_matrix(ansfm_ctx *ctx, int lowbc, int nwave, const double *params, int nmu, const double *ang_deg, int nphi, int nf,
+                      const double *azi_deg, const double *phix_deg, const double *wphi, const double *cosk, double *brdf_mat);
+int ansfm_brdf_last(const ansfm_ctx *ctx, double *kernel_ms);
+
 /* ---- measurement helpers (bench.py / profiling) -------------------------------------------
  * Time of the dominant kernel (ck_overlap) measured with hipEvents on the ctx stream around
  * the launches of the last cirsrad call: total milliseconds and number of launches. */

@@ -42,6 +42,8 @@ def main():
         bench_next(eng, out, rng)
     if only == "mie":
         bench_mie(eng, out)
+    if only == "brdf":                                      # 0.18 GB of matrix back over PCIe: on request only
+        bench_brdf(eng, out)
     if only == "ss":                                        # 10 GB of host arrays: on request only
         bench_ss(eng, out, rng)
     print(json.dumps(out, indent=1))
@@ -377,6 +379,29 @@ def bench_mie(eng, out, nwave=64, n=5):
     res["host_vs_gpu"] = {"counts_equal": bool(np.array_equal(hc, counts[pick])),
                           "xext_rel": float(np.max(np.abs(xe[pick] / he - 1))), "phas_rel": float(np.max(np.abs(ph[pick] / hp - 1)))}
     out["mie_lognormal_64_wavelengths"] = res
+
+
+def bench_brdf(eng, out, W=10000, NMU=16, NPHI=101, NF=8, n=3, slice_w=16):
+    """ForwardModel_0.calc_brdf_matrix for a Hapke surface at the C4 size: W wavenumbers, NMU^2 (NPHI + 1) BRDF evaluations
+    each.  Kernel time (hipEvents around the two launches), the call end to end (tables, staging, the matrix back to the
+    host), and the NumPy restatement of tests/brdf_cases.py on the first 16 wavenumbers -- a SLICE, and NOT a comparator: the
+    reference runs a numba-compiled point function under an interpreter loop, the restatement is vectorised NumPy."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import brdf_cases as bc
+    rng = np.random.default_rng(7)
+    P = bc.hapke_params(rng, W, 0.6)
+    MU = bc.gauss_mu(NMU)
+    wall = timeit(lambda: eng.brdf_matrix(2, P, MU, NPHI, NF), n)
+    got = eng.brdf_matrix(2, P, MU, NPHI, NF)
+    ms = eng.brdf_last()
+    t = time.perf_counter()
+    host = bc.brdf_matrix_np(2, P[:, :slice_w], MU, NPHI, NF)
+    t_host = time.perf_counter() - t
+    evals = W * NMU * NMU * (NPHI + 1)
+    out["brdf_matrix_hapke_W%d_nmu%d_nphi%d_nf%d" % (W, NMU, NPHI, NF)] = {
+        "kernel_ms": ms, "end_to_end_ms": 1e3 * wall, "hapke_evaluations": evals, "evaluations_per_s_kernel": evals / (1e-3 * ms),
+        "matrix_bytes": int(got.nbytes), "numpy_restatement_s_on_a_slice_of_%d_wavenumbers" % slice_w: t_host,
+        "slice_vs_gpu_rel_plane_max": bc.deviation(got[:slice_w], host)}
 
 
 def bench_layer(eng, out):
