@@ -1,20 +1,13 @@
 // ansfm_api.hip -- C-ABI of libansfm.so (include/ansfm.h): lifecycle of the context, tables, the gas-opacity stage and the
 // thermal / transmission / single-scattering radiative transfer with its gradients.  The other entry points are in
 // ansfm_scatter.hip, ansfm_lbl.hip, ansfm_ops.hip and ansfm_mie.hip; ansfm_ctx.hip.h is what they share.
+// The merge and RT kernels behind these entry points are launched from ansfm_overlap.hip, ansfm_overlapg.hip and ansfm_rt.hip.
 // gfx950 only.  No CPU fallback: every entry point needs a live HIP device.
-#include "ansfm_kernels.hip.h"
-#include "ansfm_merge32_launch.h"
+#include "ansfm_table_kernels.hip.h"
+#include "ansfm_rt_params.h"
 #include "ansfm_ctx.hip.h"
 
 using namespace ansfm;
-
-// length of the register-resident row-head list of the merge kernels: smallest instantiated size >= G
-static int merge_list_len(int G)
-{
-    static const int sizes[] = {8, 10, 16, 20, 32};
-    for (int v : sizes) if (v >= G) return v;
-    return 32;
-}
 
 extern "C" {
 
@@ -393,101 +386,6 @@ int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed)
 /* ------------------------------------------------------------------------------------------ */
 /* launches                                                                                    */
 /* ------------------------------------------------------------------------------------------ */
-static int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wpad, int G, int S,
-                          int L, int n_models, const LayerInterp *li, const double *amount,
-                          const double *del_g_dev, const double *del_g_host, double *tau, bool generic)
-{
-    // fast path: every k(g) non-decreasing (checked at upload for tables, in the kernel otherwise); generic path:
-    // per-lane sort of each gas first (k_ck_overlap<..., SORTED = false>), also on request (the rerun of an unsorted call)
-    const bool sorted = !generic && (from_k || ctx->monotone);
-    OverlapParams p;
-    memset(&p, 0, sizeof p);
-    p.lnK = ctx->lnK.as<double>();
-    p.kin = kin;
-    p.li = li;
-    p.amount = amount;
-    p.del_g = del_g_dev;
-    p.tau = tau;
-    p.err_flag = ctx->d_flag.as<int>() + 1;
-    p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + 4);
-    HIPCHK(hipMemsetAsync(p.tile_counter, 0, 8 * sizeof(unsigned int), ctx->stream));
-    p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
-    p.delg_f32 = ctx->delg_f32;
-    {   // g_ord = [0, cumsum(del_g)], g_ord[ng] = 1 (ForwardModel_0.py:6141-6143); float32 cumsum when DELG is
-        double acc = 0.0;
-        float accf = 0.0f;
-        p.g_ord[0] = 0.0;
-        for (int g = 0; g < G; ++g) {
-            if (ctx->delg_f32) { accf += (float)del_g_host[g]; p.g_ord[g + 1] = (double)accf; }
-            else { acc += del_g_host[g]; p.g_ord[g + 1] = acc; }
-        }
-        p.g_ord[G] = 1.0;
-        p.g_ord[G + 1] = __builtin_nan("");        // never crossed: merge_walk compares with an ordered >=
-    }
-    // The division-free walk (merge_walk_nodiv) and the 32-bit-key kernel (ansfm_merge32.hip.h, opt-in) need sorted,
-    // non-negative input and a first element of the merged order that does not close a bin (rank()'s python [-1] wrap,
-    // which only the recorded walk reproduces).  A negative value raises the same flag as an unsorted one in the 32-bit
-    // kernel and the call is rerun on the generic path.
-    bool nodiv = sorted && G >= 2;
-    if (nodiv) {
-        const double w00 = ctx->delg_f32 ? (double)((float)del_g_host[0] * (float)del_g_host[0]) : del_g_host[0] * del_g_host[0];
-        if (!(w00 < p.g_ord[1])) nodiv = false;
-    }
-    if (const char *ev = getenv("ANSFM_MERGE_WALK")) { if (!strcmp(ev, "records")) nodiv = false; }
-    // a table without a boxed entry is read without the box tests (fast path only; ANSFM_LOAD_BOXTESTS=1 keeps them)
-    bool nobox = kLoadNoBox && nodiv && !from_k && !ctx->has_boxed;
-    if (const char *ev = getenv("ANSFM_LOAD_BOXTESTS")) { if (ev[0] == '1') nobox = false; }
-    bool keys32 = nodiv && ctx->merge_keys == 32;
-    if (const char *ev = getenv("ANSFM_MERGE_KEYS")) { keys32 = nodiv && atoi(ev) == 32; }
-    const size_t lds = keys32 ? (size_t)overlap32_lds_bytes(G, ctx->delg_f32 != 0)
-                              : (size_t)(2 * G + 1) * kWave * sizeof(double) + (size_t)(2 * kMaxG + 2) * sizeof(double) +
-                                    kMaxG * sizeof(float) + (sorted ? 0 : (size_t)2 * G * kWave);
-    const size_t lds_alloc = (lds + 127) / 128 * 128;      // measured (tools/calib/lds_granule.hip): 7 blocks up to 23 360 bytes
-    int per_cu = (int)((160 * 1024) / lds_alloc);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > 8) per_cu = 8;
-    if (const char *ev = getenv("ANSFM_WAVES_PER_CU")) { int v = atoi(ev); if (v >= 1 && v < per_cu) per_cu = v; }
-    const long ntiles = (long)n_models * (Wpad / kWave) * L;
-    long grid = (long)ctx->num_cus * per_cu;
-    if (grid > ntiles) grid = ntiles;
-    if (grid < 1) grid = 1;
-    HIPCHK(ctx->scratch.reserve((size_t)grid * 6 * G * kWave * sizeof(double)));
-    p.scratch = ctx->scratch.as<double>();
-    if (keys32) {
-        HIPCHK(launch_overlap32(p, from_k, merge_list_len(G), (unsigned)grid, ctx->stream));
-        return ANSFM_OK;
-    }
-#define LAUNCH_OV2(D, FK, W32)                                                                                      \
-    do {                                                                                                            \
-        if (nodiv && nobox)                                                                                         \
-            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
-        else if (nodiv)                                                                                             \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
-        else if (sorted)                                                                                            \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p);  \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
-    } while (0)
-#define LAUNCH_OV(D, FK)                                                                              \
-    do {                                                                                              \
-        if (ctx->delg_f32) LAUNCH_OV2(D, FK, true); else LAUNCH_OV2(D, FK, false);                    \
-    } while (0)
-#define LAUNCH_OVN(FK)                                                \
-    switch (merge_list_len(G)) {                                      \
-        case 8: LAUNCH_OV(8, FK); break;                              \
-        case 10: LAUNCH_OV(10, FK); break;                            \
-        case 16: LAUNCH_OV(16, FK); break;                            \
-        case 20: LAUNCH_OV(20, FK); break;                            \
-        default: LAUNCH_OV(32, FK); break;                            \
-    }
-    if (from_k) { LAUNCH_OVN(true); } else { LAUNCH_OVN(false); }
-#undef LAUNCH_OVN
-#undef LAUNCH_OV
-#undef LAUNCH_OV2
-    HIPCHK(hipGetLastError());
-    return ANSFM_OK;
-}
-
 // src[W][X1][X2] -> dst[(x1, x2) or, swap12, (x2, x1)][Wpad] through a 32 x 32 LDS tile (k_transpose_w_last): both sides move
 // whole 256-byte segments.  The element-per-thread version read with a stride of X1 * X2 doubles: 0.18 TB/s, 17.7 of the
 // 58 ms of a C3 Jacobian call for the continuum of its 201 states.
@@ -498,63 +396,6 @@ static void launch_w_to_last(hipStream_t st, unsigned n_batch, const double *src
     dim3 grid((unsigned)(Wpad / 32), (unsigned)((X + 31) / 32), n_batch);
     hipLaunchKernelGGL(k_transpose_w_last, grid, dim3(32, 8), 0, st, src, dst, W, Wpad, X1, X2, swap12, padval, src_stride,
                        dst_stride);
-}
-
-static int launch_rt(ansfm_ctx *ctx, const RtParams &p_in, int n_models)
-{
-    RtParams p = p_in;
-    dim3 grid((unsigned)n_models, (unsigned)p.P, (unsigned)(p.Wpad / kWave));
-    if (p.Wpad / kWave > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, "thermal RT: more than 65535 wavenumber tiles (4.19e6 wavenumbers)");
-    if (p.LIMAX > 1500) FAIL(ANSFM_ERR_UNSUPPORTED, "thermal RT: at most 1500 layers along a path");
-    if (p.P > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, "thermal RT: at most 65535 paths per call");
-    ctx->last_rt_shared = 0;
-    // single scattering on the vertical opacities (CIRSrad's branch; the array-level seam hands omega in and keeps the run-time mode)
-    const bool ss = p.mode == 2 && p.sca && !p.omega;
-    // a de-duplicated batch (the states of a numerical Jacobian) in thermal emission or single scattering: every state starts
-    // each path from the record state 0 left after the last layer the two have in common
-    static const bool prefix_off = [] { const char *e = getenv("ANSFM_RT_PREFIX"); return e && e[0] == '0'; }();
-    const size_t rec = (size_t)p.P * p.LIMAX * 3 * p.G * p.Wpad * sizeof(double);
-    if (!prefix_off && n_models >= 4 && n_models <= 65536 && p.tau_slot && (p.mode == 0 || ss) && !p.emi && !p.per_g && rec <= ((size_t)4 << 30)) {
-        HIPCHK(ctx->rt_prefix.reserve(rec));
-        const size_t nl = (size_t)n_models * p.L * (ss ? p.P : 1), np = (size_t)n_models * p.P;   // ss: flags per path
-        const size_t off_j = (nl + 15) & ~(size_t)15;
-        HIPCHK(ctx->rt_same.reserve(off_j + np * sizeof(int32_t)));
-        unsigned char *same = ctx->rt_same.as<unsigned char>();
-        int32_t *jstart = reinterpret_cast<int32_t *>(same + off_j);
-        if (ss)
-            hipLaunchKernelGGL(k_rt_same_ss, dim3((unsigned)p.L, (unsigned)(n_models - 1)), dim3(256), 0, ctx->stream, p.L, p.Wpad, p.P,
-                               p.tau_slot, p.cont, p.sca, p.phase, same);
-        else
-            hipLaunchKernelGGL(k_rt_same, dim3((unsigned)p.L, (unsigned)(n_models - 1)), dim3(256), 0, ctx->stream, p.L, p.Wpad, p.tau_slot,
-                               p.cont_by_row ? nullptr : p.cont, same);      // a continuum stored by row is the row's
-        hipLaunchKernelGGL(k_rt_jstart, dim3((unsigned)np), dim3(64), 0, ctx->stream, n_models, p.L, p.P, p.LIMAX, p.nlayin, p.layinc,
-                           p.scale, p.emtemp, same, jstart, ss ? 1 : 0);
-        p.prefix = ctx->rt_prefix.as<double>(); p.jstart = jstart; p.m0 = 0;
-        const size_t lds = (size_t)4 * p.LIMAX * sizeof(double);
-        const dim3 g0(1u, grid.y, grid.z), g1((unsigned)(n_models - 1), grid.y, grid.z), blk(kWave, kGY);
-        if (ss) {
-            hipLaunchKernelGGL((k_thermal_rt<false, 1, true>), g0, blk, lds, ctx->stream, p);
-            p.m0 = 1;
-            hipLaunchKernelGGL((k_thermal_rt<true, 2, true>), g1, blk, lds, ctx->stream, p);
-        } else {
-            hipLaunchKernelGGL((k_thermal_rt<false, 1>), g0, blk, lds, ctx->stream, p);
-            p.m0 = 1;
-            hipLaunchKernelGGL((k_thermal_rt<true, 2>), g1, blk, lds, ctx->stream, p);
-        }
-        HIPCHK(hipGetLastError());
-        ctx->last_rt_shared = 1;
-        return ANSFM_OK;
-    }
-    if (ss && n_models >= 4)
-        hipLaunchKernelGGL((k_thermal_rt<true, 0, true>), grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
-    else if (ss)
-        hipLaunchKernelGGL((k_thermal_rt<false, 0, true>), grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
-    else if (n_models >= 4)
-        hipLaunchKernelGGL(k_thermal_rt<true>, grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
-    else
-        hipLaunchKernelGGL(k_thermal_rt<false>, grid, dim3(kWave, kGY), (size_t)4 * p.LIMAX * sizeof(double), ctx->stream, p);
-    HIPCHK(hipGetLastError());
-    return ANSFM_OK;
 }
 
 // Synchronises; *flag = 1 when the fast merge kernel met a k-distribution that is not non-decreasing in g (its
@@ -578,10 +419,6 @@ static int check_unsorted(ansfm_ctx *ctx)
 }
 
 }  // extern "C": the helpers of the entry points below are templates in places
-
-static int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double *dkin, int W, int Wpad, int G, int S,
-                           int L, int n_models, const LayerInterp *li, const double *amount, const double *del_g_dev,
-                           const double *del_g_host, double *tau, double *dk, bool generic);
 
 // Runs run(generic = false) and, if the fast merge met a k-distribution that is not non-decreasing in g, once more with
 // run(generic = true): the one rerun policy of the entry points.  The caller cleared the flag before the first pass; the rerun
@@ -1192,8 +1029,8 @@ int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR,
     if (st.rc) return st.rc;
     HIPCHK(ctx->tmp_out.reserve(WG * (2 + (size_t)NPAR * Li) * D));
     double *o_spec = ctx->tmp_out.as<double>(), *o_dts = o_spec + WG, *o_dspec = o_dts + WG;
-    hipLaunchKernelGGL(k_thermal_emission_g_seam, dim3(nblk(WG, 128)), dim3(128), 0, ctx->stream, ISPACE, W, G, NPAR, NLAYIN, NVMR,
-                       wave, tau, dtau, temp, press, TSURF, emis, o_spec, o_dspec, o_dts);
+    launch_thermal_emission_g_seam(ctx, ISPACE, W, G, NPAR, NLAYIN, NVMR, wave, tau, dtau, temp, press, TSURF, emis, o_spec, o_dspec,
+                                   o_dts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(SPECOUT, o_spec, WG * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(dTSURF, o_dts, WG * D, hipMemcpyDeviceToHost, ctx->stream));
@@ -1270,84 +1107,6 @@ int ansfm_thermal_emission(ansfm_ctx *ctx, int ISPACE, int W, int G, int NLAYIN,
 /* ------------------------------------------------------------------------------------------ */
 /* gradient path                                                                               */
 /* ------------------------------------------------------------------------------------------ */
-static int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double *dkin, int W, int Wpad,
-                           int G, int S, int L, int n_models, const LayerInterp *li, const double *amount,
-                           const double *del_g_dev, const double *del_g_host, double *tau, double *dk, bool generic)
-{
-    OverlapGParams pg;
-    memset(&pg, 0, sizeof pg);
-    OverlapParams &p = pg.o;
-    p.lnK = ctx->lnK.as<double>();
-    p.kin = kin;
-    p.li = li;
-    p.amount = amount;
-    p.del_g = del_g_dev;
-    p.tau = tau;
-    p.err_flag = ctx->d_flag.as<int>() + 1;
-    p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
-    p.delg_f32 = ctx->delg_f32;
-    {
-        double acc = 0.0;
-        float accf = 0.0f;
-        p.g_ord[0] = 0.0;
-        for (int g = 0; g < G; ++g) {
-            if (ctx->delg_f32) { accf += (float)del_g_host[g]; p.g_ord[g + 1] = (double)accf; }
-            else { acc += del_g_host[g]; p.g_ord[g + 1] = acc; }
-        }
-        p.g_ord[G] = 1.0;
-        p.g_ord[G + 1] = __builtin_nan("");        // never crossed: merge_walk compares with an ordered >=
-    }
-    pg.dkin = dkin;
-    pg.dk = dk;
-    pg.gas_mask = from_k ? 0xFFFFFFFFu : ctx->grad_gas_mask;      // the array-level seam returns every slot
-    const int NP1 = S + 1;
-    // the gas selection mask (ansfm_set_gradient_gases) has one bit per gas and bit 31 for temperature
-    if (NP1 > 32) FAIL(ANSFM_ERR_UNSUPPORTED, "gradient path supports at most 31 spectroscopic gases");
-    // fast path: every k(g) non-decreasing (tables: checked at upload; array-level seam: in the kernel, rerun otherwise)
-    const bool sorted = !generic && (from_k || ctx->monotone);
-    const size_t lds = (size_t)(2 * G + 1) * kWave * sizeof(double) + (size_t)(2 * kMaxG + 2) * sizeof(double) + kMaxG * sizeof(float) +
-                       (sorted ? 0 : (size_t)2 * G * kWave);
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > 8) per_cu = 8;
-    const long ntiles = (long)n_models * (Wpad / kWave) * L;
-    long grid = (long)ctx->num_cus * per_cu;
-    if (grid > ntiles) grid = ntiles;
-    if (grid < 1) grid = 1;
-    HIPCHK(ctx->scratch.reserve((size_t)grid * 6 * (G + 1) * kWave * sizeof(double)));
-    HIPCHK(ctx->gscratch.reserve((size_t)grid * (3 + 2 * (size_t)NP1) * G * kWave * sizeof(double)));
-    HIPCHK(ctx->perm.reserve((size_t)grid * ((G * G + kCodesPerWord - 1) / kCodesPerWord) * kWave * sizeof(unsigned long long)));
-    p.scratch = ctx->scratch.as<double>();
-    pg.gscratch = ctx->gscratch.as<double>();
-    pg.perm = ctx->perm.as<unsigned long long>();
-    p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + 4);
-    HIPCHK(hipMemsetAsync(p.tile_counter, 0, 8 * sizeof(unsigned int), ctx->stream));
-#define LAUNCH_OVG(D, FK)                                                                                           \
-    do {                                                                                                            \
-        if (ctx->delg_f32) {                                                                                        \
-            if (sorted) hipLaunchKernelGGL((k_ck_overlapg<D, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);   \
-            else hipLaunchKernelGGL((k_ck_overlapg<D, true, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);         \
-        } else {                                                                                                    \
-            if (sorted) hipLaunchKernelGGL((k_ck_overlapg<D, false, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);  \
-            else hipLaunchKernelGGL((k_ck_overlapg<D, false, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);        \
-        }                                                                                                           \
-    } while (0)
-#define LAUNCH_OVG_D(FK)                                              \
-    switch (merge_list_len(G)) {                                      \
-        case 8: LAUNCH_OVG(8, FK); break;                             \
-        case 10: LAUNCH_OVG(10, FK); break;                           \
-        case 16: LAUNCH_OVG(16, FK); break;                           \
-        case 20: LAUNCH_OVG(20, FK); break;                           \
-        default: LAUNCH_OVG(32, FK); break;                           \
-    }
-    (void)from_k;                     // the kernel tests p.kin (run-time flag, see load_gas_g)
-    LAUNCH_OVG_D(false);
-#undef LAUNCH_OVG_D
-#undef LAUNCH_OVG
-    HIPCHK(hipGetLastError());
-    return ANSFM_OK;
-}
-
 int ansfm_set_shared_gas_gradient(ansfm_ctx *ctx, int L, const double *dTAU_WL)
 {
     CHECK_CTX(ctx);
@@ -1443,24 +1202,11 @@ static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models
     }
     q.slot_of_param[NVMR] = (q.gas_mask >> 31) ? (signed char)S : (signed char)-1;   // :3872 (written last)
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-    {
-        dim3 grid((unsigned)n_models, (unsigned)P, (unsigned)(Wpad / kWave));
-        if (Wpad / kWave > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, "thermal RT: more than 65535 wavenumber tiles (4.19e6 wavenumbers)");
-        // reduction buffer [NP1+2][GY][64] doubles: the largest GY that leaves room for one block per CU
-        const size_t per_gy = (size_t)(NP1 + 2) * kWave * sizeof(double);
-        if (16 * per_gy <= 128 * 1024)
-            hipLaunchKernelGGL(k_thermal_rtg<16>, grid, dim3(kWave, 16), 16 * per_gy, ctx->stream, q);
-        else if (8 * per_gy <= 128 * 1024)
-            hipLaunchKernelGGL(k_thermal_rtg<8>, grid, dim3(kWave, 8), 8 * per_gy, ctx->stream, q);
-        else
-            hipLaunchKernelGGL(k_thermal_rtg<4>, grid, dim3(kWave, 4), 4 * per_gy, ctx->stream, q);
-        HIPCHK(hipGetLastError());
-    }
+    if ((rc = launch_rtg(ctx, q, n_models))) return rc;
     for (int m = 0; m < n_models; ++m) {
         const size_t nout = (size_t)W * NPAR * LIMAX * P;
-        hipLaunchKernelGGL(k_dspec_to_ref, dim3(nblk(nout, 256)), dim3(256), 0, ctx->stream,
-                           ctx->dspec_i.as<double>() + (size_t)m * P * NPAR * LIMAX * Wpad, dSPECOUT + (size_t)m * nout, W,
-                           Wpad, NPAR, LIMAX, P, NLAYIN);
+        launch_dspec_to_ref(ctx, ctx->dspec_i.as<double>() + (size_t)m * P * NPAR * LIMAX * Wpad, dSPECOUT + (size_t)m * nout, W, Wpad,
+                            NPAR, LIMAX, P, NLAYIN);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));

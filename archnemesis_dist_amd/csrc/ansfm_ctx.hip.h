@@ -1,7 +1,11 @@
 // ansfm_ctx.hip.h -- what the host translation units of libansfm.so share: the context, the error macros, the staging of
 // host pointers and the declarations of the host helpers that one unit defines and another calls.  No kernel lives here, and
 // no kernel header is included: a header that defines kernels belongs to exactly one .hip.
-//   ansfm_api.hip      lifecycle, tables, the gas-opacity stage, thermal / transmission / single-scattering RT and gradients
+//   ansfm_api.hip      lifecycle, tables, the gas-opacity stage, the entry points of thermal / transmission / single-scattering
+//                      RT and its gradients
+//   ansfm_overlap.hip  forward merge of the correlated-k path (64-bit keys); ansfm_merge32.hip: the 32-bit-key merge
+//   ansfm_overlapg.hip gradient merge
+//   ansfm_rt.hip       thermal / transmission / single-scattering RT kernels and their gradients
 //   ansfm_scatter.hip  multiple scattering
 //   ansfm_lbl.hip      runtime line-by-line
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
@@ -15,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -184,6 +189,48 @@ void launch_lblrt_tau(ansfm_ctx *ctx, int n, int L, int m0, const double *amount
 // list, or nullptr for every (model, layer) in order
 void launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int ISPACE, const int32_t *slot_rows, const double *ray_totam,
                               const double *ray_f4);
+
+// ansfm_overlap.hip / ansfm_overlapg.hip: k_ck_overlap (or k_ck_overlap32) and k_ck_overlapg over n_models x L layers into tau
+// (and dk); from_k: the array-level seams' k (and dkdT) instead of the table; generic: per-lane sort first (rerun of an unsorted call)
+struct LayerInterp;
+struct OverlapParams;
+int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wpad, int G, int S, int L, int n_models,
+                   const LayerInterp *li, const double *amount, const double *del_g_dev, const double *del_g_host, double *tau,
+                   bool generic);
+int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double *dkin, int W, int Wpad, int G, int S, int L,
+                    int n_models, const LayerInterp *li, const double *amount, const double *del_g_dev, const double *del_g_host,
+                    double *tau, double *dk, bool generic);
+// length of the register-resident row-head list of the merge kernels: smallest instantiated size >= G
+inline int merge_list_len(int G)
+{
+    static const int sizes[] = {8, 10, 16, 20, 32};
+    for (int v : sizes) if (v >= G) return v;
+    return 32;
+}
+// ansfm_overlap.hip: what the two 64-bit-key merge launches set up alike, in two calls because the forward launch picks its
+// kernel, and with it the LDS size, from g_ord.  merge_params: the fields of p both kernels read, the g_ord table (float32
+// cumulative sum when DELG is float32, NaN after the last boundary) and the tile counter's address; p was zeroed by the caller.
+void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, int Wpad, int G, int S, int L, int n_models,
+                  const LayerInterp *li, const double *amount, const double *del_g_dev, const double *del_g_host, double *tau);
+// merge_launch_begin: grid = min(tiles, CUs x blocks per CU), blocks per CU = 160 KiB / block_bytes within [1, max_per_cu];
+// reserves grid x bytes_per_block of every workspace, then clears the tile counter on the stream.  The kernel launch follows.
+struct MergeWorkspace {
+    DevBuf *buf;
+    size_t bytes_per_block;
+};
+int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, size_t block_bytes, int max_per_cu,
+                       std::initializer_list<MergeWorkspace> workspaces, long *grid_out);
+// ansfm_rt.hip: k_thermal_rt by mode, batch size and prefix sharing; k_thermal_rtg with the largest reduction buffer that fits;
+// the array-level gradient seam; dspec [P][NPAR][LIMAX][Wpad] -> dSPECOUT [W][NPAR][LIMAX][P] of one model
+struct RtParams;
+struct RtGParams;
+int launch_rt(ansfm_ctx *ctx, const RtParams &p_in, int n_models);
+int launch_rtg(ansfm_ctx *ctx, const RtGParams &q, int n_models);
+void launch_thermal_emission_g_seam(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR, int NLAYIN, int NVMR, const double *wave,
+                                    const double *tau, const double *dtau, const double *temp, const double *press, double TSURF,
+                                    const double *emis, double *o_spec, double *o_dspec, double *o_dts);
+void launch_dspec_to_ref(ansfm_ctx *ctx, const double *src, double *dst, int W, int Wpad, int NPAR, int LIMAX, int P,
+                         const int32_t *nlayin);
 
 /* ---- host -> device staging of the host-pointer entry points --------------------------------------------------------- */
 inline int h2d(ansfm_ctx *ctx, DevBuf &b, const void *src, size_t bytes, const void **out)

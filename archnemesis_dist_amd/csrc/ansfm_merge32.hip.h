@@ -1,7 +1,7 @@
 // ansfm_merge32.hip.h -- k_ck_overlap32: calc_k + k_overlap / rank (Spectroscopy_0.py:2298, ForwardModel_0.py:6029-6173)
 // with the row heads of the G-way merge ordered on 32-BIT KEYS.
 //
-// Same decomposition as k_ck_overlap (ansfm_kernels.hip.h): one lane per (wavenumber, layer) cell, a[G] / b[G+1] per lane in
+// Same decomposition as k_ck_overlap (ansfm_overlap_kernels.hip.h): one lane per (wavenumber, layer) cell, a[G] / b[G+1] per lane in
 // LDS as [index][lane], the sorted sequence of the G*G sums a_i + b_j produced by a G-way streaming merge whose row heads
 // are a sorted list in registers, rank()'s walk consuming it on the fly.  What is different:
 //

@@ -1,0 +1,314 @@
+// ansfm_merge64.hip.h -- device code of the 64-bit-key merge that the forward kernel (ansfm_overlap_kernels.hip.h) and the
+// gradient kernel (ansfm_overlapg_kernels.hip.h) share: the LDS layout, the switches of the instruction trims, the list keys,
+// the rank walk, the register-list step with its peeled tail, and the per-lane sort of the generic path.  No kernel is
+// defined here, so both units include it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "ansfm_merge_common.hip.h"
+
+namespace ansfm {
+
+// LDS byte offsets of the tables that open the merge kernels' dynamic LDS block (the kernels have no static LDS, so the
+// block starts at address 0 -- checked once per launch): reads become `ds_read vaddr = index << k, offset:const`.
+constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) * 8, kLdsA = kLdsDGF + kMaxG * 4;
+
+// One popped element of the merge with everything the rank walk and the row's next key need, fetched from LDS
+// as soon as the winner key is known (software pipelining: the walk of element t and the rest of the insertion
+// pass run while the operands of element t+1 are in flight).
+// Bin records, per block [bin][2][lane] pairs of doubles: pair 0 = (kacc, sum1), pair 1 = (gd, code of the element that
+// closed the bin: row | column << 5), each pair one 16-byte store per lane, the lanes of a pair contiguous (1 KiB rows).
+// The stores sit in the merge loop's crossing branch, which runs in about every second step, and every store
+// traffic there is not free (doubling five 8-byte row stores: +29 % on the forward kernel) -- so the closing element's
+// value and weight are not stored, the resolve loop recomputes them from LDS (same operations), and what is stored goes
+// out as two wide stores.  Same-box comparisons: gradient kernel 25.7 -> 23.7 ms against six 8-byte rows; forward kernel
+// within +-1 % of five 8-byte rows and of three pairs (it is not store-bound at this level).  The gradient kernel's resolve rewrites the
+// pairs as (frac, 1/weight-sum) and (weight, code) for its replay passes.
+// Switches of the forward merge kernel's instruction trims (every one leaves the results bit for bit):
+//   kMergePeel      the last G - 1 steps of a merge pass over a shrinking list (merge_peel)
+//   kWalkOneOffset  merge_walk_nodiv keeps one running offset instead of two
+//   kMergeUnroll4   four steps per trip of the merge loop instead of two
+//   kLoadNoBox      tables without a boxed entry are interpolated without the box tests (interp_k_nobox)
+#ifndef ANSFM_MERGE_PEEL
+#define ANSFM_MERGE_PEEL 1
+#endif
+#ifndef ANSFM_WALK_ONE_OFFSET
+#define ANSFM_WALK_ONE_OFFSET 1
+#endif
+#ifndef ANSFM_MERGE_UNROLL4
+#define ANSFM_MERGE_UNROLL4 0
+#endif
+#ifndef ANSFM_LOAD_NOBOX
+#define ANSFM_LOAD_NOBOX 1
+#endif
+constexpr bool kMergePeel = ANSFM_MERGE_PEEL != 0, kWalkOneOffset = ANSFM_WALK_ONE_OFFSET != 0, kMergeUnroll4 = ANSFM_MERGE_UNROLL4 != 0,
+               kLoadNoBox = ANSFM_LOAD_NOBOX != 0;
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+constexpr unsigned kRecRow = 64u * 16u, kRecBin = 2u * kRecRow;
+
+struct MergeElem {
+    double ai, bc, bn, w;
+    int ci, np;
+};
+
+// Weight of element (i, j) = del_g[i] * del_g[j].  DELG float32 (W32): NumPy forms the float32 product, which is one
+// v_mul_f32 of the float32 copies kept behind the double tables (DG, GORD) in LDS.
+__device__ __forceinline__ const float *delg_f32_table(const double *DG) { return reinterpret_cast<const float *>(DG + 2 * kMaxG + 2); }
+template <bool W32>
+__device__ __forceinline__ double pair_weight(const double *DG, int i, int j)
+{
+    if constexpr (W32) {
+        const float *DGF = delg_f32_table(DG);
+        return (double)(DGF[i] * DGF[j]);
+    } else
+        return DG[i] * DG[j];
+}
+
+// SORTED = false (generic path): the rows / columns were sorted per lane beforehand; PA / PB give the original
+// g-ordinate of each sorted position, which is the one whose weight applies.
+template <bool W32, bool SORTED = true>
+__device__ __forceinline__ void merge_fetch(double key, int lane, const double *A, const double *B,
+                                            const double *DG, MergeElem &e,
+                                            const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
+{
+    const unsigned kb = (unsigned)__double_as_longlong(key);
+    const int ci = kb & 31, cp = (kb >> 5) & 63;
+    e.ci = ci;
+    e.np = cp + 1;
+    e.ai = A[ci * kWave + lane];
+    const unsigned ab = lds_addr(B + lane) + ((unsigned)cp << 9);
+    e.bc = lds_ld(ab);
+    e.bn = lds_ld(ab + 512);                    // B[G] = sentinel column: an exhausted row re-enters as "huge"
+    if constexpr (SORTED) e.w = pair_weight<W32>(DG, ci, cp);
+    else e.w = pair_weight<W32>(DG, PA[ci * kWave + lane], PB[cp * kWave + lane]);
+}
+
+// List keys: the element value a_i + b_j with the low 11 mantissa bits replaced by (col << 5) | row  (col <= 32,
+// row <= 31).  Keys compare like the values except among values closer than 2^-41 relative (treated as ties, which
+// rank() orders arbitrarily anyway); the exact value is recomputed from a_i + b_j when the element is consumed, so the
+// sums are the reference's.
+__device__ __forceinline__ double pack_key11(double v, int row, int col)
+{
+    unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    b = (b & ~0x7FFULL) | (unsigned long long)((col << 5) | row);
+    return __longlong_as_double((long long)b);
+}
+
+// rank() walk state of one lane (ForwardModel_0.py:6155-6170).  Bin boundaries are recorded and resolved
+// after the loop: frac needs a division, and the next bin's (1-frac) share is added there too -- the same
+// sums in a different association.
+struct WalkState {
+    double gd, kacc, sum1, gnext;
+    unsigned roff;      // byte offset of this lane's first pair in the record of the bin being filled: ig * kRecBin + lane * 16
+    unsigned gaddr;     // LDS byte address of GORD[ig + 1]
+    unsigned rbase;     // merge_walk_nodiv: lane * 8 - (address of GORD[1] << 6), see there (roff is unused in that walk)
+};
+__device__ __forceinline__ WalkState walk_begin(const double *GORD, int lane)
+{
+    WalkState ws;
+    ws.gd = 0.0; ws.kacc = 0.0; ws.sum1 = 0.0;
+    ws.gaddr = lds_addr(GORD + 1);
+    ws.gnext = lds_ld(ws.gaddr);
+    ws.roff = (unsigned)lane * 16u;
+    ws.rbase = (unsigned)lane * 8u - (ws.gaddr << 6);
+    return ws;
+}
+// number of bins closed so far
+__device__ __forceinline__ int walk_bins(const WalkState &ws, const double *GORD) { return (int)((ws.gaddr - lds_addr(GORD + 1)) >> 3); }
+
+template <bool REC_CODE>
+__device__ __forceinline__ bool merge_walk(const MergeElem &e, WalkState &ws, double *rec, const double *GORD,
+                                           int lane)
+{
+    const double cv = e.ai + e.bc;
+    const double w = e.w;
+    const double gdn = ws.gd + w;
+    double kn = ws.kacc + cv * w, sn = ws.sum1 + w;
+    // ordered >= : GORD[G+1] is NaN, so nothing crosses after the last bin whatever gdn is (garbage weights of a call
+    // that is going to be rerun on the generic path, NaN / inf input) -- the record index stays <= G
+    const bool cross = (gdn >= ws.gnext);
+    if (cross) {                                // this element straddles the bin boundary
+        // The branch runs in about every second step (some lane of the 64 crosses), so it is kept to four stores and two
+        // adds: the record slot is a running 32-bit byte offset onto the wave-uniform base (no 64-bit index arithmetic).
+        gst<dbl2>(rec, ws.roff, dbl2{ws.kacc, ws.sum1});
+        gst<dbl2>(rec, ws.roff + kRecRow, dbl2{ws.gd, __longlong_as_double((long long)(e.ci | ((e.np - 1) << 5)))});
+        kn = 0.0; sn = 0.0;
+        ws.roff += kRecBin;
+        ws.gaddr += 8u;
+        ws.gnext = lds_ld(ws.gaddr);            // GORD[G+1] = NaN: nothing crosses after the last bin
+    }
+    ws.kacc = kn; ws.sum1 = sn;
+    ws.gd = gdn;
+    return cross;
+}
+
+// Division-free form of the walk (forward kernel, NODIV).  rank()'s boundary element contributes frac * cont * w to the bin
+// it closes and (1 - frac) * cont * w to the next one, frac = (g_ord[ig+1] - gdist_prev) / w: that is
+// (g_ord[ig+1] - gdist_prev) * cont and (gdist - g_ord[ig+1]) * cont -- no division -- and the bin's weight sum (carry
+// (1-frac) w of the previous boundary element, the weights inside, frac w) telescopes to g_ord[ig+1] - g_ord[ig].  A closed
+// bin is then ONE 8-byte store of its un-normalised sum (rec = [bin][lane] doubles) instead of a 32-byte record, and the
+// resolve pass is a division by the bin width when the merged spectrum is read back.  Differs from the recorded form
+// in the last bits only (the reference itself forms frac from a difference of cumulative sums, good to ~1e-12).
+// Precondition (checked at launch): the first element of the merged order does not close a bin -- rank()'s python
+// gdist[-1] wrap, which only the recorded form reproduces.
+__device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &ws, double *rec)
+{
+    const double cv = e.ai + e.bc;
+    const double w = e.w;
+    const double gdn = ws.gd + w;
+    double kn = fma(cv, w, ws.kacc);
+    const bool cross = (gdn >= ws.gnext);       // ordered: GORD[G+1] is NaN
+    if (cross) {
+        if constexpr (kWalkOneOffset) {
+            // The closed bin's slot, ig * 512 + lane * 8, is formed from the one running offset the walk keeps (gaddr, +8 per
+            // bin; 512 = 8 << 6): one shift-add here, where a second running offset cost an add AND, as a second value that
+            // lives across the branch and the e0 / e1 ping-pong, a register copy at the end of the branch body.  The
+            // boundary is read at gaddr + 8 (an immediate offset of the LDS read) and gaddr is stepped in place last.
+            gst<double>(rec, (ws.gaddr << 6) + ws.rbase, fma(ws.gnext - ws.gd, cv, ws.kacc));
+            kn = (gdn - ws.gnext) * cv;
+            ws.gnext = lds_ld(ws.gaddr + 8u);
+            ws.gaddr += 8u;
+        } else {
+            gst<double>(rec, ws.roff, fma(ws.gnext - ws.gd, cv, ws.kacc));
+            kn = (gdn - ws.gnext) * cv;
+            ws.roff += kWave * 8u;
+            ws.gaddr += 8u;
+            ws.gnext = lds_ld(ws.gaddr);
+        }
+    }
+    ws.kacc = kn;
+    ws.gd = gdn;
+    return cross;
+}
+
+// The heads of the G rows are kept as a SORTED LIST IN REGISTERS (R[0] = the current winner): popping is free and the
+// row's next key is inserted by one pass of v_max_f64 + v_min_f64 pairs over statically indexed
+// registers -- no tree in LDS, no lane-dependent addressing, and the next winner is known after the FIRST
+// compare-exchange, so its operands' LDS reads are hidden behind the rest of the pass and the walk.  NR = list length
+// (compile time, >= G; unused entries hold "huge" keys).
+// Returns the consumed element's (row, column) and whether it closed a bin, as 16 bits: the gradient kernel
+// records them and replays the sorted order for the gradient rows.
+template <int NR, bool W32, bool REC_CODE = false, bool SORTED = true, bool NODIV = false, int NP = NR>
+__device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, MergeElem &en, WalkState &ws,
+                                               int lane, const double *A, const double *B,
+                                               const double *DG, const double *GORD, double *rec,
+                                               const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
+{
+    static_assert(NP >= 1 && NP <= NR, "pass length");
+    // 1. the popped row's next element x enters the list s_1 <= s_2 <= ... (s_0 was popped):
+    //        t_0 = min(x, s_1),   t_k = min(max(x, s_k), s_{k+1}),   t_{NP-1} = max(x, s_{NP-1})
+    //    -- every output independent of the others (no carry chain), in place in ascending k.
+    //    NP = pass length: the pass reads and writes R[0..NP) only, which is the full pass whenever R[NP..NR) hold nothing
+    //    but "huge" keys (see the peeled steps of k_ck_overlap for when that is known without looking).
+    const double x = pack_key11(e.ai + e.bn, e.ci, e.np);
+    if constexpr (NP == 1) {
+        R[0] = x;                               // the last element's step: its row's next key is a sentinel, nothing follows
+    } else {
+    asm("v_min_f64 %0, %1, %2" : "=v"(R[0]) : "v"(x), "v"(R[1]));
+    // 2. fetch the operands of the new winner (LDS reads in flight during the rest of the pass and the walk)
+    merge_fetch<W32, SORTED>(R[0], lane, A, B, DG, en, PA, PB);
+    // 3. finish the insertion: every max first, then every min -- no result is consumed by a neighbouring instruction
+    //    (6.40 -> 6.32 ms against blocks of 6, same box)
+    constexpr int kBlk = NP;
+#pragma unroll
+    for (int k0 = 1; k0 < NP - 1; k0 += kBlk) {
+        double mk[kBlk];
+#pragma unroll
+        for (int j = 0; j < kBlk; ++j)
+            if (k0 + j < NP - 1) asm("v_max_f64 %0, %1, %2" : "=v"(mk[j]) : "v"(x), "v"(R[k0 + j]));
+#pragma unroll
+        for (int j = 0; j < kBlk; ++j)
+            if (k0 + j < NP - 1) asm("v_min_f64 %0, %1, %2" : "=v"(R[k0 + j]) : "v"(mk[j]), "v"(R[k0 + j + 1]));
+    }
+    asm("v_max_f64 %0, %1, %2" : "=v"(R[NP - 1]) : "v"(x), "v"(R[NP - 1]));
+    }
+    // 4. rank walk on the element just consumed
+    bool cross;
+    if constexpr (NODIV) cross = merge_walk_nodiv(e, ws, rec);
+    else cross = merge_walk<REC_CODE>(e, ws, rec, GORD, lane);
+    // step code of the gradient replay, 12 bits: row (0-4), column (5-9), "the element closed a bin" (10); kCodesPerWord of
+    // them to a 64-bit word of the stream
+    return (unsigned)(e.ci | ((e.np - 1) << 5) | (cross ? 0x400 : 0));
+}
+
+// The last G - 1 steps of a merge, with the list pass shrinking by one entry per step.
+//
+// Every row has exactly one entry in the list: the key of its next element, or -- once its last element has been popped --
+// the key formed from B[G] = "huge" (merge_fetch: an exhausted row re-enters as a sentinel, not as a live key).  The list is
+// sorted and every sentinel is above every live key, so the live keys are a prefix of it.  When step t (0-based) begins,
+// R[0] is element t itself and G*G - t elements are left including it; each live entry is the head of a different row with at
+// least one of them, so at most min(G, G*G - t) entries are live and R[j] is a sentinel for every j >= G*G - t.  Step t pops
+// R[0] and inserts x into R[1..): a pass over R[0 .. G*G - t) sees every live key, and what it leaves out it would have
+// reproduced (min / max of sentinels among themselves -- which sentinel ends where may differ, none is ever consumed).
+// The bound depends on t alone: no test, no ballot.  R[j] can first be dropped at step t = G*G - j, i.e. the steps
+// t <= G*G - G need all G entries and step t = G*G - NP, NP = G-1 ... 1, needs NP of them.  (Entries G .. NR-1 of a launch with
+// G < NR are sentinels from the start; the main loop still passes over them, its length being a template constant.)
+// The bodies are instantiated for NP = NR-1 ... 1 and the first NR - G of them are skipped (G is wave-uniform).  Which of
+// e0 / e1 holds the current element alternates per step; the caller hands it over in e1 when G and NR have the same parity
+// and in e0 when not (swap_elems), so the choice is a compile-time one here.
+template <int NP, int NR, bool W32, bool SORTED, bool NODIV>
+__device__ __forceinline__ void merge_peel(double (&R)[NR], MergeElem &e0, MergeElem &e1, WalkState &ws, int G,
+                                           int lane, const double *A, const double *B, const double *DG,
+                                           const double *GORD, double *rec, const unsigned char *PA,
+                                           const unsigned char *PB)
+{
+    if constexpr (NP >= 1) {
+        if (NP < G) {
+            if constexpr (((NR - NP) & 1) != 0)
+                merge_step<NR, W32, false, SORTED, NODIV, NP>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+            else
+                merge_step<NR, W32, false, SORTED, NODIV, NP>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+        }
+        merge_peel<NP - 1, NR, W32, SORTED, NODIV>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+    }
+}
+
+// R[i] = head of row i = a_i + b_0: ascending in i when a is.  A loaded gas is (fast path: by precondition; generic: sorted
+// first); a MERGED spectrum is non-decreasing only up to the rounding of its bin averages, and two neighbours that
+// rounding has swapped can fall on either side of a key boundary (seen with k(g) flat to 1e-9: an unsorted list loses an
+// entry in the insertion network and a sentinel is consumed).  So the keys are checked, and when some lane's are not
+// ascending the heads are put in order one by one (the merge itself only needs every ROW ascending, i.e. b sorted).
+template <int NR>
+__device__ __forceinline__ void merge_init(double (&R)[NR], int G, int lane, const double *A, double b0, double huge)
+{
+#pragma unroll
+    for (int i = 0; i < NR; ++i) R[i] = (i < G) ? pack_key11(A[(i < G ? i : 0) * kWave + lane] + b0, i, 0) : huge;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i + 1 < NR; ++i) bad |= (R[i + 1] < R[i]);
+    if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+        double T[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) { T[i] = R[i]; R[i] = huge; }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (i < G) {
+                const double x = T[i];
+#pragma unroll
+                for (int k = NR - 1; k >= 1; --k) R[k] = fmin(fmax(x, R[k - 1]), R[k]);
+                R[0] = fmin(x, R[0]);
+            }
+        }
+    }
+}
+
+// Per-lane insertion sort of one LDS column (values ascending, stable) carrying the original index of every
+// position in P.  Only the generic path (k not sorted in g) uses it.
+__device__ __forceinline__ void sort_column(double *X, unsigned char *P, int G, int lane)
+{
+    for (int g = 0; g < G; ++g) P[g * kWave + lane] = (unsigned char)g;
+    for (int i = 1; i < G; ++i) {
+        const double key = X[i * kWave + lane];
+        const unsigned char pk = P[i * kWave + lane];
+        int j = i - 1;
+        while (j >= 0 && X[j * kWave + lane] > key) {
+            X[(j + 1) * kWave + lane] = X[j * kWave + lane];
+            P[(j + 1) * kWave + lane] = P[j * kWave + lane];
+            --j;
+        }
+        X[(j + 1) * kWave + lane] = key;
+        P[(j + 1) * kWave + lane] = pk;
+    }
+}
+
+}  // namespace ansfm

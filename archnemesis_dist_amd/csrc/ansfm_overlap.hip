@@ -1,0 +1,121 @@
+// ansfm_overlap.hip -- translation unit of k_ck_overlap (ansfm_overlap_kernels.hip.h): the instantiations of the forward merge,
+// their launcher, and the launch set-up it shares with the gradient merge (ansfm_overlapg.hip).
+#include "ansfm_overlap_kernels.hip.h"
+#include "ansfm_merge32_launch.h"
+#include "ansfm_ctx.hip.h"
+
+namespace ansfm {
+
+void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, int Wpad, int G, int S, int L, int n_models,
+                  const LayerInterp *li, const double *amount, const double *del_g_dev, const double *del_g_host, double *tau)
+{
+    p.lnK = ctx->lnK.as<double>();
+    p.kin = kin;
+    p.li = li;
+    p.amount = amount;
+    p.del_g = del_g_dev;
+    p.tau = tau;
+    p.err_flag = ctx->d_flag.as<int>() + 1;
+    p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + 4);
+    p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
+    p.delg_f32 = ctx->delg_f32;
+    // g_ord = [0, cumsum(del_g)], g_ord[ng] = 1 (ForwardModel_0.py:6141-6143); float32 cumsum when DELG is
+    double acc = 0.0;
+    float accf = 0.0f;
+    p.g_ord[0] = 0.0;
+    for (int g = 0; g < G; ++g) {
+        if (ctx->delg_f32) { accf += (float)del_g_host[g]; p.g_ord[g + 1] = (double)accf; }
+        else { acc += del_g_host[g]; p.g_ord[g + 1] = acc; }
+    }
+    p.g_ord[G] = 1.0;
+    p.g_ord[G + 1] = __builtin_nan("");        // never crossed: merge_walk compares with an ordered >=
+}
+
+int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, size_t block_bytes, int max_per_cu,
+                       std::initializer_list<MergeWorkspace> workspaces, long *grid_out)
+{
+    int per_cu = (int)((160 * 1024) / block_bytes);
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > max_per_cu) per_cu = max_per_cu;
+    const long ntiles = (long)p.n_models * (p.Wpad / kWave) * p.L;
+    long grid = (long)ctx->num_cus * per_cu;
+    if (grid > ntiles) grid = ntiles;
+    if (grid < 1) grid = 1;
+    for (const MergeWorkspace &w : workspaces) HIPCHK(w.buf->reserve((size_t)grid * w.bytes_per_block));
+    HIPCHK(hipMemsetAsync(p.tile_counter, 0, 8 * sizeof(unsigned int), ctx->stream));
+    *grid_out = grid;
+    return ANSFM_OK;
+}
+
+int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wpad, int G, int S,
+                   int L, int n_models, const LayerInterp *li, const double *amount,
+                   const double *del_g_dev, const double *del_g_host, double *tau, bool generic)
+{
+    // fast path: every k(g) non-decreasing (checked at upload for tables, in the kernel otherwise); generic path:
+    // per-lane sort of each gas first (k_ck_overlap<..., SORTED = false>), also on request (the rerun of an unsorted call)
+    const bool sorted = !generic && (from_k || ctx->monotone);
+    OverlapParams p;
+    memset(&p, 0, sizeof p);
+    merge_params(ctx, p, kin, W, Wpad, G, S, L, n_models, li, amount, del_g_dev, del_g_host, tau);
+    // The division-free walk (merge_walk_nodiv) and the 32-bit-key kernel (ansfm_merge32.hip.h, opt-in) need sorted,
+    // non-negative input and a first element of the merged order that does not close a bin (rank()'s python [-1] wrap,
+    // which only the recorded walk reproduces).  A negative value raises the same flag as an unsorted one in the 32-bit
+    // kernel and the call is rerun on the generic path.
+    bool nodiv = sorted && G >= 2;
+    if (nodiv) {
+        const double w00 = ctx->delg_f32 ? (double)((float)del_g_host[0] * (float)del_g_host[0]) : del_g_host[0] * del_g_host[0];
+        if (!(w00 < p.g_ord[1])) nodiv = false;
+    }
+    if (const char *ev = getenv("ANSFM_MERGE_WALK")) { if (!strcmp(ev, "records")) nodiv = false; }
+    // a table without a boxed entry is read without the box tests (fast path only; ANSFM_LOAD_BOXTESTS=1 keeps them)
+    bool nobox = kLoadNoBox && nodiv && !from_k && !ctx->has_boxed;
+    if (const char *ev = getenv("ANSFM_LOAD_BOXTESTS")) { if (ev[0] == '1') nobox = false; }
+    bool keys32 = nodiv && ctx->merge_keys == 32;
+    if (const char *ev = getenv("ANSFM_MERGE_KEYS")) { keys32 = nodiv && atoi(ev) == 32; }
+    const size_t lds = keys32 ? (size_t)overlap32_lds_bytes(G, ctx->delg_f32 != 0)
+                              : (size_t)(2 * G + 1) * kWave * sizeof(double) + (size_t)(2 * kMaxG + 2) * sizeof(double) +
+                                    kMaxG * sizeof(float) + (sorted ? 0 : (size_t)2 * G * kWave);
+    const size_t lds_alloc = (lds + 127) / 128 * 128;      // measured (tools/calib/lds_granule.hip): 7 blocks up to 23 360 bytes
+    int max_per_cu = 8;
+    if (const char *ev = getenv("ANSFM_WAVES_PER_CU")) { int v = atoi(ev); if (v >= 1 && v < max_per_cu) max_per_cu = v; }
+    // blocks per CU: by the LDS size rounded up to the 128-byte granule, and no more than ANSFM_WAVES_PER_CU
+    long grid = 0;
+    const int rc = merge_launch_begin(ctx, p, lds_alloc, max_per_cu, {{&ctx->scratch, (size_t)6 * G * kWave * sizeof(double)}}, &grid);
+    if (rc) return rc;
+    p.scratch = ctx->scratch.as<double>();
+    if (keys32) {
+        HIPCHK(launch_overlap32(p, from_k, merge_list_len(G), (unsigned)grid, ctx->stream));
+        return ANSFM_OK;
+    }
+#define LAUNCH_OV2(D, FK, W32)                                                                                      \
+    do {                                                                                                            \
+        if (nodiv && nobox)                                                                                         \
+            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+        else if (nodiv)                                                                                             \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+        else if (sorted)                                                                                            \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p);  \
+        else                                                                                                        \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+    } while (0)
+#define LAUNCH_OV(D, FK)                                                                              \
+    do {                                                                                              \
+        if (ctx->delg_f32) LAUNCH_OV2(D, FK, true); else LAUNCH_OV2(D, FK, false);                    \
+    } while (0)
+#define LAUNCH_OVN(FK)                                                \
+    switch (merge_list_len(G)) {                                      \
+        case 8: LAUNCH_OV(8, FK); break;                              \
+        case 10: LAUNCH_OV(10, FK); break;                            \
+        case 16: LAUNCH_OV(16, FK); break;                            \
+        case 20: LAUNCH_OV(20, FK); break;                            \
+        default: LAUNCH_OV(32, FK); break;                            \
+    }
+    if (from_k) { LAUNCH_OVN(true); } else { LAUNCH_OVN(false); }
+#undef LAUNCH_OVN
+#undef LAUNCH_OV
+#undef LAUNCH_OV2
+    HIPCHK(hipGetLastError());
+    return ANSFM_OK;
+}
+
+}  // namespace ansfm

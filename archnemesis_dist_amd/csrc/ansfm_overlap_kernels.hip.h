@@ -1,0 +1,213 @@
+// ansfm_overlap_kernels.hip.h -- k_ck_overlap, the forward merge kernel of the correlated-k path (unit: ansfm_overlap.hip).
+#pragma once
+#include "ansfm_merge64.hip.h"
+
+namespace ansfm {
+
+// ------------------------------------------------------------------------------------------------
+// K1+K2 fused: (P,T) interpolation + random-overlap merge.   "ck_overlap"
+//
+// One LANE per (wavenumber, layer) cell; a wavefront = 64 consecutive wavenumbers of ONE layer, so
+// corner indices, u, v and gas amounts are wave-uniform (SGPRs) and every table access is one
+// 512-byte coalesced row.  The reference sorts the G*G sums tau_i + k_j*amount (argsort) and
+// walks the sorted list once to re-bin it (rank, ForwardModel_0.py:6117-6173).  Both inputs are
+// already sorted in g, so the sorted sequence is produced by a G-way streaming merge of the rows
+// (a_i + b_0..b_{G-1}) -- the row heads held as a sorted list in registers, see merge_step -- and rank's walk
+// consumes it on the fly: nothing of size G*G is ever stored.  The per-lane arrays a[G], b[G+1] live in LDS as
+// [index][lane], so a lane-dependent index never causes a bank conflict (bank depends on the lane only).
+//
+// LDS per wave: (2G+1)*64*8 bytes (+ shared del_g / g_ord tables)  -> 21.1 KiB at G=20, 7 waves per CU.
+// ------------------------------------------------------------------------------------------------
+
+// SORTED = false: generic path for k-distributions that are not non-decreasing in g (the reference sorts the G*G
+// products itself, :6150).  Each gas's (k, weight) pairs are sorted per lane first -- the multiset of
+// (product, weight) is unchanged, so rank()'s walk sees the same sequence up to the order of exact ties -- and the
+// skip rules keep looking at the LAST g-ordinate in the original order (:6075-6102).  A spectrum that passes through
+// unmerged comes out in its original order.
+// NOBOX: the table was found free of boxed entries at upload, load_gas interpolates without the box tests.
+template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_ck_overlap(OverlapParams p)
+{
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x;
+    const int G = p.G;
+    // tables first: their LDS addresses are compile-time constants (dynamic LDS starts at 0), so a table read is
+    // `ds_read vaddr = index << k, offset:const` with no base add
+    double *DG = smem;                           // [kMaxG] doubles, then GORD [kMaxG + 2], then the float32 copy of DG
+    double *GORD = DG + kMaxG;
+    double *A = reinterpret_cast<double *>(reinterpret_cast<char *>(GORD + kMaxG + 2) + kMaxG * sizeof(float));
+    double *B = A + G * kWave;                   // G+1 rows
+    unsigned char *PA = reinterpret_cast<unsigned char *>(B + (G + 1) * kWave);   // SORTED = false only
+    unsigned char *PB = PA + G * kWave;
+    if (lane < G) {
+        DG[lane] = p.del_g[lane];
+        const_cast<float *>(delg_f32_table(DG))[lane] = (float)p.del_g[lane];
+    }
+    if (lane < G + 2) GORD[lane] = p.g_ord[lane];
+    const double HUGE_KEY = __longlong_as_double(0x7FE0000000000000LL);   // finite, above any optical depth
+    B[G * kWave + lane] = HUGE_KEY;
+    __syncthreads();
+    double wsum = 0.0;
+    for (int g = 0; g < G; ++g) wsum += DG[g];
+    const double wtot = wsum * wsum;  // stands in for gdist[-1] (python wrap at iloop==0)
+
+    // per-block scratch: closed-bin records, see kRecBin
+    double *rec = p.scratch + (size_t)blockIdx.x * 6 * G * kWave;
+    TileQueue tq;
+    tq.init();
+    for (;;) {
+        int vt = 0, m = 0, l = 0;
+        if (!tq.next(p, lane, vt, m, l)) break;
+        const int nu = vt * kWave + lane;
+        LayerInterp q;
+        if constexpr (!FROM_K) q = p.li[(size_t)m * p.L + l];
+        bool unsorted = false;
+
+        load_gas<FROM_K, false, NOBOX>(p, q, m, l, 0, nu, A, lane, unsorted);
+        double alast = A[(G - 1) * kWave + lane];       // last g-ordinate in the ORIGINAL order
+        if constexpr (!SORTED) sort_column(A, PA, G, lane);
+        for (int s = 1; s < p.S; ++s) {
+            load_gas<FROM_K, false, NOBOX>(p, q, m, l, s, nu, B, lane, unsorted);
+            if constexpr (SORTED)                       // the call is rerun on the generic path: no point in merging
+                if (__builtin_amdgcn_ballot_w64(unsorted) != 0) break;
+            const double blast = B[(G - 1) * kWave + lane];
+            if constexpr (!SORTED) sort_column(B, PB, G, lane);
+            if constexpr (SORTED) alast = A[(G - 1) * kWave + lane];
+            // skip rules, cutoff = 0  (ForwardModel_0.py:6073-6102)
+            bool takeB, keepA;
+            if (s == 1) { takeB = (alast <= 0.0); keepA = !takeB && (blast <= 0.0); }
+            else { keepA = (blast <= 0.0); takeB = !keepA && (alast <= 0.0); }
+            const bool do_merge = !(takeB | keepA);
+            if (takeB) {
+                for (int g = 0; g < G; ++g) A[g * kWave + lane] = B[g * kWave + lane];
+                if constexpr (!SORTED) {
+                    for (int g = 0; g < G; ++g) PA[g * kWave + lane] = PB[g * kWave + lane];
+                    alast = blast;
+                }
+            }
+            if (do_merge) {
+                // ---- sorted list of the G row heads (row i = a_i + b_j, j ascending) -------------
+                double R[NR];
+                merge_init<NR>(R, G, lane, A, B[lane], HUGE_KEY);
+                MergeElem e0, e1;
+                merge_fetch<W32, SORTED>(R[0], lane, A, B, DG, e0, PA, PB);
+                WalkState ws = walk_begin(GORD, lane);
+                if constexpr (NODIV) ws.roff = (unsigned)lane * 8u;
+                // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
+                const int nloop = kMergePeel ? G * G - (G - 1) : G * G;
+                // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
+                constexpr int kPer = kMergeUnroll4 ? 4 : 2;
+                for (int n = nloop / kPer; n > 0; --n) {
+                    merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    if constexpr (kMergeUnroll4) {
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    }
+                }
+                if constexpr (kMergeUnroll4)
+                    if ((nloop & 2) != 0) {
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    }
+                if (kMergePeel || (nloop & 1) != 0)
+                    merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                if constexpr (kMergePeel) {
+                    if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
+                    merge_peel<NR - 1, NR, W32, SORTED, NODIV>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+                }
+                if constexpr (NODIV) {
+                    // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
+                    const int ig = walk_bins(ws, GORD);
+                    for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
+                        double r[kLoadBatch];
+#pragma unroll
+                        for (int k = 0; k < kLoadBatch; ++k)
+                            r[k] = gld<double>(rec, (unsigned)((g0 + k < G) ? g0 + k : G - 1) * (kWave * 8u) + (unsigned)lane * 8u);
+#pragma unroll
+                        for (int k = 0; k < kLoadBatch; ++k) {
+                            const int b = g0 + k;
+                            if (b < G) {
+                                double outv = 0.0;
+                                if (b < ig) outv = fast_div(r[k], GORD[b + 1] - GORD[b]);
+                                else if (b == ig) outv = (b == G - 1) ? fast_div(ws.kacc, ws.gd - GORD[G - 1]) : ws.kacc;
+                                A[b * kWave + lane] = outv;
+                            }
+                        }
+                    }
+                } else {
+                // ---- resolve the bins --------------------------------------------------------------------
+                // The closing element of every bin is re-formed from LDS (a[row] + b[col], its weight) exactly as the
+                // walk formed it, so `a` must stay intact until the last bin is done: the outputs go to row 0 of the bin
+                // records (full-wave coalesced stores) and come back into A afterwards.
+                double ck = 0.0, cs = 0.0;   // (1-frac) share carried into the next bin
+                const int ig = walk_bins(ws, GORD);
+                constexpr int kRB = 5;       // records of kRB bins are fetched together (one round trip)
+                for (int b0 = 0; b0 < G; b0 += kRB) {
+                    double rka[kRB], rs1[kRB], rgd[kRB];
+                    unsigned rcd[kRB];
+#pragma unroll
+                    for (int k = 0; k < kRB; ++k) {
+                        const int bi = (b0 + k < G) ? b0 + k : G - 1;
+                        const unsigned ro = (unsigned)bi * kRecBin + (unsigned)lane * 16u;
+                        const dbl2 v0 = gld<dbl2>(rec, ro), v1 = gld<dbl2>(rec, ro + kRecRow);
+                        rka[k] = v0.x; rs1[k] = v0.y; rgd[k] = v1.x; rcd[k] = (unsigned)__double_as_longlong(v1.y);
+                    }
+#pragma unroll
+                    for (int k = 0; k < kRB; ++k) {
+                        const int b = b0 + k;
+                        if (b < G) {
+                            double outv = 0.0;
+                            if (b < ig) {
+                                const int crow = rcd[k] & 31, ccol = (rcd[k] >> 5) & 63;
+                                const double cv = A[crow * kWave + lane] + B[ccol * kWave + lane];
+                                double w;
+                                if constexpr (SORTED) w = pair_weight<W32>(DG, crow, ccol);
+                                else w = pair_weight<W32>(DG, PA[crow * kWave + lane], PB[ccol * kWave + lane]);
+                                const double ka = rka[k], s1 = rs1[k], cw = cv * w;
+                                // a crossing at the very first element (nothing accumulated yet) sees python's gdist[-1]
+                                const double gd0 = rgd[k];
+                                const double gprev = (b == 0 && s1 == 0.0) ? wtot : gd0;
+                                const double gdn = gd0 + w;                 // the same add the walk made
+                                const double frac = fast_div(GORD[b + 1] - gprev, gdn - gprev);     // <= 1 ulp, as every division of the resolve
+                                const double kb = (ck + ka) + frac * cw;
+                                const double sb = (cs + s1) + frac * w;
+                                outv = fast_div(kb, sb);
+                                ck = (1.0 - frac) * cw;
+                                cs = (1.0 - frac) * w;
+                            } else if (b == ig) {
+                                // trailing `if ig == ng-1` (:6171); an unfinished earlier bin stays un-normalised
+                                const double kb = ck + ws.kacc, sb = cs + ws.sum1;
+                                outv = (b == G - 1) ? fast_div(kb, sb) : kb;
+                            }
+                            gst<double>(rec, (unsigned)b * kRecBin + (unsigned)lane * 16u, outv);
+                        }
+                    }
+                }
+                for (int g0 = 0; g0 < G; g0 += kLoadBatch) {          // merged spectrum: records' row 0 -> A
+                    double r[kLoadBatch];
+#pragma unroll
+                    for (int k = 0; k < kLoadBatch; ++k)
+                        r[k] = gld<double>(rec, (unsigned)((g0 + k < G) ? g0 + k : G - 1) * kRecBin + (unsigned)lane * 16u);
+#pragma unroll
+                    for (int k = 0; k < kLoadBatch; ++k)
+                        if (g0 + k < G) A[(g0 + k) * kWave + lane] = r[k];
+                }
+                }
+                if constexpr (!SORTED) {   // the merged spectrum is ascending with the plain del_g weights
+                    for (int g = 0; g < G; ++g) PA[g * kWave + lane] = (unsigned char)g;
+                    alast = A[(G - 1) * kWave + lane];
+                }
+            }
+        }
+        double *out = p.tau + (((size_t)m * p.L + l) * G) * p.Wpad + nu;
+        if constexpr (SORTED) {
+            if (unsorted) atomicOr(p.err_flag, 1);
+            for (int g = 0; g < G; ++g) out[(size_t)g * p.Wpad] = A[g * kWave + lane];
+        } else {
+            for (int g = 0; g < G; ++g) out[(size_t)PA[g * kWave + lane] * p.Wpad] = A[g * kWave + lane];
+        }
+    }
+}
+
+}  // namespace ansfm

@@ -1873,10 +1873,11 @@ def _singlescatt_vs_oracle(eng, oracle, unsorted):
 
 def test_entry_points_of_every_translation_unit_share_one_context(eng, oracle, golden_dir):
     """The entry points live in several translation units (csrc/ansfm_api, _scatter, _mie, _ops) over one context and its
-    workspaces.  A de-duplicated thermal batch, then a scattering call, a Mie call and a layering call on the same engine,
+    workspaces, and so do the merge and RT kernels behind them (_overlap, _overlapg, _rt).  A de-duplicated thermal batch, then
+    a scattering call, a Mie call, a layering call and a gradient call (gradient merge, RT gradient) on the same engine,
     then the thermal batch again: the same bits and the same opacity rows as the first time, and every call in between
     within the bound of its own test (test_cirsrad_scatter_vs_oracle, test_mie_gpu.test_golden_cases,
-    test_layer_average_golden)."""
+    test_layer_average_golden, test_cirsradg_vs_oracle)."""
     import mie_cases as mc
     from archnemesis_dist_amd import synthetic as syn
     from test_layer_oracle import NAMES, CASES
@@ -1924,6 +1925,26 @@ def test_entry_points_of_every_translation_unit_share_one_context(eng, oracle, g
                           y["split1_BASEP"], LAYHT=-6.0e4, NINT=101, DUST_UNITS=None, XMOLWT=None, **CASES["cg_nadir"])
     for n, v in zip(NAMES, r):
         np.testing.assert_allclose(v, y[f"cg_nadir_{n}"], rtol=1e-10, err_msg=n)
+
+    # CIRSrad(return_grad=True) of the unperturbed model on the nadir path, same table: ctx->scratch, d_flag, tau and li are
+    # the forward units' too
+    NVMR = S + 2
+    NPAR = NVMR + 3
+    rng = np.random.default_rng(3)
+    igas_map = rng.permutation(NVMR)[:S].astype(np.int32)
+    cont1 = syn.synth_continuum(W, L)
+    dcont = cont1[:, :, None, :] * rng.uniform(0.0, 1e-22, size=(1, W, NPAR, L))
+    EMTEMP1 = atm["lay_temp"][:, LAYINC[:, 0]][:, :, None]
+    TSURF, EMIS, xfac = np.array([280.0]), np.linspace(0.8, 1.0, W), np.linspace(1.0, 1.5, W)
+    spec, dspec, dts = eng.cirsradg_ck_thermal(0, atm["lay_press_pa"], atm["lay_temp"], atm["amount"], cont1, dcont, NVMR, NPAR,
+                                               igas_map, NLAYIN, LAYINC, SCALE, EMTEMP1, TSURF, EMISSIVITY=EMIS, xfac=xfac)
+    rs, rd, rt = oracle.cirsradg_ck_thermal(0, K, PRESS, TEMP, WAVE, delg, atm["lay_press_pa"][0], atm["lay_temp"][0],
+                                            atm["amount"][0], cont1[0], dcont[0], NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
+                                            EMTEMP1[0], TSURF[0], EMISSIVITY=EMIS, xfac=xfac)
+    np.testing.assert_allclose(spec[0], rs, rtol=1e-10)
+    np.testing.assert_allclose(dts[0], rt, rtol=1e-10, atol=0)
+    gscale = np.abs(rd).max(axis=(0, 2, 3), keepdims=True) + 1e-300
+    assert np.max(np.abs(dspec[0] - rd) / gscale) < 1e-9
 
     again = eng.cirsrad_ck_thermal(*thermal)
     assert np.array_equal(again, first)

@@ -1,4 +1,4 @@
-"""A model of the merge kernels' register list (merge_step / merge_peel in csrc/ansfm_kernels.hip.h) in plain Python: the
+"""A model of the merge kernels' register list (merge_step / merge_peel in csrc/ansfm_merge64.hip.h) in plain Python: the
 order in which the G * G sums are popped with full-length passes throughout against the order with the last G - 1 passes
 shortened by one entry per step, for every G of every instantiated list length -- flat input (keys that tie), zeros and
 list entries beyond G included.  It also checks the compile-time choice of which of e0 / e1 holds the current element in
