@@ -39,6 +39,7 @@ EXPORTS = [
     "ansfm_get_dtaugas",
     "ansfm_mie_makephase", "ansfm_mie_set_radius_block", "ansfm_mie_set_radius_cap", "ansfm_mie_last",
     "ansfm_surface_brdf", "ansfm_brdf_matrix", "ansfm_brdf_last",
+    "ansfm_cirsradg_ck_transit", "ansfm_transit_last",
 ]
 
 _lib = None
@@ -191,6 +192,8 @@ def load():
     lib.ansfm_surface_brdf.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp]
     lib.ansfm_brdf_matrix.argtypes = [vp, ci, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.ansfm_brdf_last.argtypes = [vp, C.POINTER(cd)]
+    lib.ansfm_cirsradg_ck_transit.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.ansfm_transit_last.argtypes = [vp, C.POINTER(cd * 3)]
     lib.ansfm_layer_average.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 11
     lib.ansfm_layer_average_dev.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp, vp]
     lib.ansfm_layer_averageg.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 15

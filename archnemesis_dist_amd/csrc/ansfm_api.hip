@@ -1,7 +1,8 @@
 // ansfm_api.hip -- C-ABI of libansfm.so (include/ansfm.h): lifecycle of the context, tables, the gas-opacity stage and the
 // thermal / transmission / single-scattering radiative transfer with its gradients.  The other entry points are in
-// ansfm_scatter.hip, ansfm_lbl.hip, ansfm_ops.hip and ansfm_mie.hip; ansfm_ctx.hip.h is what they share.
-// The merge and RT kernels behind these entry points are launched from ansfm_overlap.hip, ansfm_overlapg.hip and ansfm_rt.hip.
+// ansfm_scatter.hip, ansfm_lbl.hip, ansfm_ops.hip, ansfm_mie.hip and ansfm_surface.hip; ansfm_ctx.hip.h is what they share.
+// The merge, RT and transit kernels behind these entry points are launched from ansfm_overlap.hip, ansfm_overlapg.hip,
+// ansfm_rt.hip and ansfm_transit.hip.
 // gfx950 only.  No CPU fallback: every entry point needs a live HIP device.
 #include "ansfm_table_kernels.hip.h"
 #include "ansfm_rt_params.h"
@@ -1126,6 +1127,52 @@ int ansfm_set_shared_gas_gradient(ansfm_ctx *ctx, int L, const double *dTAU_WL)
     return ANSFM_OK;
 }
 
+// Which slot of the gradient merge (gas i: slot i, temperature: slot S) feeds parameter k of dSPECOUT, for the gradient RT
+// kernels and the transit kernels alike; -1: none
+static int fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int NVMR, int NPAR, unsigned gas_mask,
+                              signed char *slot_of_param)
+{
+    const int S = ctx->S;
+    for (int k = 0; k < kMaxPar; ++k) slot_of_param[k] = -1;
+    for (int i = 0; i < S; ++i) {   // assignment order of :3868-3870: a later gas overwrites an earlier one
+        if (igas_map_host[i] < 0 || igas_map_host[i] >= NPAR) FAIL(ANSFM_ERR_INVALID, "cirsradg: igas_map out of range");
+        // a gas that is not selected leaves the parameter to an earlier selected gas of the same column (isotopologues)
+        if ((gas_mask >> i) & 1u) slot_of_param[igas_map_host[i]] = (signed char)i;
+    }
+    slot_of_param[NVMR] = (gas_mask >> 31) ? (signed char)S : (signed char)-1;   // :3872 (written last)
+    return ANSFM_OK;
+}
+
+// The gas stage of a gradient call on device arrays, for the gradient RT kernels and the transit kernels alike: tau and the
+// derivatives of the gradient merge (ctx->tau, ctx->dkbuf; calc_klblg + :3812-3814 for LBL tables) between ev[0] and ev[1], the
+// continuum and its gradients transposed to the wave-fastest layouts (cont_t [n][L][Wpad], dcont_t [n][NPAR][L][Wpad], or nullptr)
+static int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp,
+                          const double *amount, const double *taucont, const double *dtaucon, int NPAR, const double **cont_t,
+                          const double **dcont_t)
+{
+    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, NP1 = ctx->S + 1;
+    *cont_t = *dcont_t = nullptr;
+    HIPCHK(ctx->dkbuf.reserve((size_t)n_models * L * NP1 * G * Wpad * sizeof(double)));
+    HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+    int rc;
+    if ((rc = gas_prep(ctx, n_models * L, lay_press_pa, lay_temp))) return rc;
+    if (taucont) {
+        HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
+        launch_w_to_last(ctx->stream, (unsigned)n_models, taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
+        *cont_t = ctx->cont_t.as<double>();
+    }
+    if (dtaucon) {
+        HIPCHK(ctx->dcont_t.reserve((size_t)n_models * NPAR * L * Wpad * sizeof(double)));
+        launch_w_to_last(ctx->stream, (unsigned)n_models, dtaucon, ctx->dcont_t.as<double>(), W, Wpad, NPAR, L, 0, 0.0, (size_t)W * NPAR * L, (size_t)NPAR * L * Wpad);
+        *dcont_t = ctx->dcont_t.as<double>();
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    if ((rc = gas_tau(ctx, n_models, L, lay_press_pa, lay_temp, amount, false, ctx->dkbuf.as<double>()))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    return ANSFM_OK;
+}
+
 // transmission: the path transmission and its gradients (ansfm_cirsradg_ck_transmission)
 static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
                                         const double *lay_temp, const double *amount, const double *taucont,
@@ -1142,28 +1189,11 @@ static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models
         FAIL(ANSFM_ERR_INVALID, "cirsradg: bad argument (NPAR <= 256)");
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, NP1 = S + 1;
-    HIPCHK(ctx->dkbuf.reserve((size_t)n_models * L * NP1 * G * Wpad * sizeof(double)));
     HIPCHK(ctx->trold_ws.reserve((size_t)n_models * P * (LIMAX + 1) * G * Wpad * sizeof(double)));
     HIPCHK(ctx->dspec_i.reserve((size_t)n_models * P * NPAR * LIMAX * Wpad * sizeof(double)));
-    HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     int rc;
-    if ((rc = gas_prep(ctx, n_models * L, lay_press_pa, lay_temp))) return rc;
     const double *cont_t = nullptr, *dcont_t = nullptr;
-    if (taucont) {
-        HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
-        launch_w_to_last(ctx->stream, (unsigned)n_models, taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
-        cont_t = ctx->cont_t.as<double>();
-    }
-    if (dtaucon) {
-        HIPCHK(ctx->dcont_t.reserve((size_t)n_models * NPAR * L * Wpad * sizeof(double)));
-        launch_w_to_last(ctx->stream, (unsigned)n_models, dtaucon, ctx->dcont_t.as<double>(), W, Wpad, NPAR, L, 0, 0.0, (size_t)W * NPAR * L, (size_t)NPAR * L * Wpad);
-        dcont_t = ctx->dcont_t.as<double>();
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    // calc_klblg + :3812-3814 for LBL tables
-    if ((rc = gas_tau(ctx, n_models, L, lay_press_pa, lay_temp, amount, false, ctx->dkbuf.as<double>()))) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    if ((rc = grad_gas_stage(ctx, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, &cont_t, &dcont_t))) return rc;
     RtGParams q;
     memset(&q, 0, sizeof q);
     RtParams &r = q.r;
@@ -1194,13 +1224,7 @@ static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models
     q.dtsurf = dTSURF;
     q.NPAR = NPAR; q.NVMR = NVMR; q.NP1 = NP1;
     q.gas_mask = ctx->is_lbl ? 0xFFFFFFFFu : ctx->grad_gas_mask;
-    for (int k = 0; k < kMaxPar; ++k) q.slot_of_param[k] = -1;
-    for (int i = 0; i < S; ++i) {   // assignment order of :3868-3870: a later gas overwrites an earlier one
-        if (igas_map_host[i] < 0 || igas_map_host[i] >= NPAR) FAIL(ANSFM_ERR_INVALID, "cirsradg: igas_map out of range");
-        // a gas that is not selected leaves the parameter to an earlier selected gas of the same column (isotopologues)
-        if ((q.gas_mask >> i) & 1u) q.slot_of_param[igas_map_host[i]] = (signed char)i;
-    }
-    q.slot_of_param[NVMR] = (q.gas_mask >> 31) ? (signed char)S : (signed char)-1;   // :3872 (written last)
+    if ((rc = fill_slot_of_param(ctx, igas_map_host, NVMR, NPAR, q.gas_mask, q.slot_of_param))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     if ((rc = launch_rtg(ctx, q, n_models))) return rc;
     for (int m = 0; m < n_models; ++m) {
@@ -1290,6 +1314,125 @@ int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const do
     return cirsradg_ck_thermal_host(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, P,
                                     LIMAX, NLAYIN, LAYINC, SCALE, SCALE, tsurf.data(), nullptr, xfac, SPECOUT, dSPECOUT, dts.data(),
                                     true);
+}
+
+// Primary-transit depth with gradients of one model (nemesisPTfm, ForwardModel_0.py:1838-1995), collapsed over the paths on the
+// device: the gas stage of cirsradg_ck_thermal_dev_impl, then k_transit_sens and k_transit_grad on the path matrix
+// Sm[l][p] = sum of SCALE over the entries j < NLAYIN[p] of path p with LAYINC[j][p] = l, built here.  Neither trold_ws nor
+// dspec_i is reserved; dAREA (W, NPAR, L, 1) stays in dspec_ref for ansfm_map2pro(dSPECIN = NULL).
+int ansfm_cirsradg_ck_transit(ansfm_ctx *ctx, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
+                              const double *taucont, const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P,
+                              int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                              const double *path_weight, double *AREA, double *TRANS, double *dAREA)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg_ck_transit: upload a k-table first");
+    if (L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN || !LAYINC || !SCALE || !path_weight ||
+        !AREA || !igas_map || NPAR <= 0 || NPAR > kMaxPar || NVMR < 0 || NVMR >= NPAR)
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: bad argument (NPAR <= 256)");
+    if (L > kTransitMaxRows || P > kTransitMaxRows)
+        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsradg_ck_transit: at most 320 layers and 320 paths (the 160 KiB LDS tile of k_transit_sens)");
+    // the path matrix, compressed by path and by layer; an entry is what some j < NLAYIN[p] touched, padding is never read
+    std::vector<double> Sm((size_t)L * P, 0.0);
+    std::vector<char> hit((size_t)L * P, 0);
+    for (int p = 0; p < P; ++p) {
+        if (NLAYIN[p] < 0 || NLAYIN[p] > LIMAX) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: NLAYIN outside 0 .. LIMAX");
+        for (int j = 0; j < NLAYIN[p]; ++j) {
+            const int l = LAYINC[(size_t)j * P + p];
+            if (l < 0 || l >= L) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: LAYINC outside 0 .. L - 1");
+            Sm[(size_t)l * P + p] += SCALE[(size_t)j * P + p];
+            hit[(size_t)l * P + p] = 1;
+        }
+    }
+    size_t nnz = 0;
+    for (char h : hit) nnz += h;
+    std::vector<int32_t> hi((size_t)P + 1 + L + 1 + 2 * nnz);
+    std::vector<double> hd((size_t)P + 2 * nnz);
+    int32_t *col_ptr = hi.data(), *col_lay = col_ptr + P + 1, *row_ptr = col_lay + nnz, *row_path = row_ptr + L + 1;
+    double *col_val = hd.data() + P, *row_val = col_val + nnz;
+    std::copy(path_weight, path_weight + P, hd.data());
+    int32_t n = 0;
+    for (int p = 0; p < P; ++p) {
+        col_ptr[p] = n;
+        for (int l = 0; l < L; ++l)
+            if (hit[(size_t)l * P + p]) { col_lay[n] = l; col_val[n++] = Sm[(size_t)l * P + p]; }
+    }
+    col_ptr[P] = n;
+    n = 0;
+    for (int l = 0; l < L; ++l) {
+        row_ptr[l] = n;
+        for (int p = 0; p < P; ++p)
+            if (hit[(size_t)l * P + p]) { row_path[n] = p; row_val[n++] = Sm[(size_t)l * P + p]; }
+    }
+    row_ptr[L] = n;
+
+    // everything that can refuse the arguments comes before the first copy is queued
+    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, NP1 = S + 1;
+    const size_t D = sizeof(double);
+    TransitParams q;
+    memset(&q, 0, sizeof q);
+    q.gas_mask = ctx->is_lbl ? 0xFFFFFFFFu : ctx->grad_gas_mask;
+    int rc;
+    if ((rc = fill_slot_of_param(ctx, igas_map, NVMR, NPAR, q.gas_mask, q.slot_of_param))) return rc;
+    if (ctx->dcont_gas_L && ctx->dcont_gas_L != L) {
+        ctx->dcont_gas_L = 0;
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: the pending shared gas gradient (ansfm_set_shared_gas_gradient) is for a "
+                                "different number of layers");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    ctx->dspec_dims[0] = 0;
+    ctx->transit_recorded = 0;
+    // hd / hi are staged from this frame: from here on no return before the stream has been synchronised
+    auto on_device = [&]() -> int {
+        Stager st{ctx};
+        const double *press = st.up(lay_press_pa, L), *temp = st.up(lay_temp, L), *am = st.up(amount, (size_t)L * S),
+                     *cont = st.up(taucont, (size_t)L * W), *dcont = st.up(dtaucon, (size_t)L * W * NPAR),
+                     *dd = st.up(hd.data(), hd.size());
+        const int32_t *di = st.up(hi.data(), hi.size());
+        if (st.rc) return st.rc;
+        int rc2;
+        const double *cont_t = nullptr, *dcont_t = nullptr;
+        if ((rc2 = grad_gas_stage(ctx, 1, L, press, temp, am, cont, dcont, NPAR, &cont_t, &dcont_t))) return rc2;
+        // scratch beyond the gas stage: A [L][G][Wpad], exp(-tau_path) [P][G][Wpad], AREA [W], T [W][P]
+        const size_t n_sens = (size_t)L * G * Wpad, n_tpart = (size_t)P * G * Wpad, n_out = (size_t)W * (1 + P);
+        ctx->transit_scratch_bytes = (n_sens + n_tpart + n_out) * D;
+        HIPCHK(ctx->transit_ws.reserve(ctx->transit_scratch_bytes));
+        HIPCHK(ctx->dspec_ref.reserve((size_t)W * NPAR * L * D));
+        q.tau = ctx->tau.as<double>();
+        q.cont = cont_t;
+        q.delg = ctx->d_delg.as<double>();
+        q.weight = dd; q.col_val = dd + P; q.row_val = dd + P + nnz;
+        q.col_ptr = di; q.col_lay = di + P + 1; q.row_ptr = di + P + 1 + nnz; q.row_path = di + P + 1 + nnz + L + 1;
+        q.sens = ctx->transit_ws.as<double>();
+        q.tpart = q.sens + n_sens;
+        q.area = q.tpart + n_tpart;
+        q.trans = q.area + W;
+        q.darea = ctx->dspec_ref.as<double>();
+        q.dk = ctx->dkbuf.as<double>();
+        q.dcont = dcont_t;
+        if (ctx->dcont_gas_L) {
+            q.dcont_gas = ctx->dcont_gas.as<double>();
+            ctx->dcont_gas_L = 0;               // one call only
+        }
+        q.W = W; q.Wpad = Wpad; q.G = G; q.L = L; q.P = P;
+        q.NPAR = NPAR; q.NVMR = NVMR; q.NP1 = NP1;
+        HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+        if ((rc2 = launch_transit(ctx, q))) return rc2;
+        HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+        ctx->overlap_launches = 1; ctx->rt_launches = 1;
+        ctx->last_n = 1; ctx->last_L = L;
+        HIPCHK(hipMemcpyAsync(AREA, q.area, (size_t)W * D, hipMemcpyDeviceToHost, ctx->stream));
+        if (TRANS) HIPCHK(hipMemcpyAsync(TRANS, q.trans, (size_t)W * P * D, hipMemcpyDeviceToHost, ctx->stream));
+        if (dAREA) HIPCHK(hipMemcpyAsync(dAREA, q.darea, (size_t)W * NPAR * L * D, hipMemcpyDeviceToHost, ctx->stream));
+        return check_unsorted(ctx);             // synchronises
+    };
+    if ((rc = on_device())) {
+        (void)hipStreamSynchronize(ctx->stream);   // whatever was queued from hd / hi has run before they go
+        return rc;
+    }
+    ctx->dspec_dims[0] = W; ctx->dspec_dims[1] = NPAR; ctx->dspec_dims[2] = L; ctx->dspec_dims[3] = 1;
+    ctx->transit_recorded = 1;
+    return ANSFM_OK;
 }
 
 int ansfm_k_overlapg(ansfm_ctx *ctx, int W, int G, int L, int S, const double *del_g, const double *k,

@@ -11,6 +11,7 @@
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
+//   ansfm_transit.hip  primary-transit depth with gradients, collapsed over paths on the device
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -133,6 +134,12 @@ struct ansfm_ctx {
     // surface reflection (ansfm_surface_brdf, ansfm_brdf_matrix): the result, the per-azimuth table, kernel time of the last call
     DevBuf brdf_out, brdf_azi;
     double brdf_ms = 0;
+    // primary transit (ansfm_cirsradg_ck_transit): A [L][G][Wpad] + exp(-tau_path) [P][G][Wpad]; the compressed path matrix; the
+    // bytes of the first the last call needed; events around k_transit_sens and k_transit_grad (created at the first call)
+    DevBuf transit_ws;
+    size_t transit_scratch_bytes = 0;
+    int transit_recorded = 0;
+    hipEvent_t transit_ev[3] = {nullptr, nullptr, nullptr};
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;
@@ -148,6 +155,7 @@ struct ansfm_ctx {
     ~ansfm_ctx()
     {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : transit_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
@@ -231,6 +239,9 @@ void launch_thermal_emission_g_seam(ansfm_ctx *ctx, int ISPACE, int W, int G, in
                                     const double *emis, double *o_spec, double *o_dspec, double *o_dts);
 void launch_dspec_to_ref(ansfm_ctx *ctx, const double *src, double *dst, int W, int Wpad, int NPAR, int LIMAX, int P,
                          const int32_t *nlayin);
+// ansfm_transit.hip: k_transit_sens + k_transit_grad of one model; ANSFM_ERR_UNSUPPORTED above kTransitMaxRows layers or paths
+struct TransitParams;
+int launch_transit(ansfm_ctx *ctx, const TransitParams &q);
 
 /* ---- host -> device staging of the host-pointer entry points --------------------------------------------------------- */
 inline int h2d(ansfm_ctx *ctx, DevBuf &b, const void *src, size_t bytes, const void **out)

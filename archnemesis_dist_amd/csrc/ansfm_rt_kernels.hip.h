@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ansfm_merge_common.hip.h"
+#include "ansfm_grad_slots.hip.h"
 #include "ansfm_rt_params.h"
 
 namespace ansfm {
@@ -475,15 +476,12 @@ __global__ __launch_bounds__(kWave *GY) void k_thermal_rtg(RtGParams q)
         for (int k = 0; k < GY; ++k) { Xs += rb[(0 * GY + k) * kWave + lane]; Zs += rb[(1 * GY + k) * kWave + lane]; }
         for (int kpar = gy; kpar < q.NPAR; kpar += GY) {
             const int slot = q.slot_of_param[kpar];
-            double v = 0.0;
+            double ys = 0.0;
             if (slot >= 0) {
-                double ys = 0.0;
 #pragma unroll
                 for (int k = 0; k < GY; ++k) ys += rb[((2 + slot) * GY + k) * kWave + lane];
-                v = ys * ((slot == NP1 - 1) ? 1.0 : 1.0e-4);      // :3870 / :3872
             }
-            if (q.dcont) v += q.dcont[(((size_t)m * q.NPAR + kpar) * p.L + lay) * p.Wpad + nu] * Xs;
-            if (q.dcont_gas && kpar < q.NVMR) v += q.dcont_gas[(size_t)lay * p.Wpad + nu] * Xs;
+            double v = dtau_param_gsum(slot, ys, Xs, NP1, q.dcont, q.dcont_gas, (size_t)m, q.NPAR, q.NVMR, kpar, p.L, lay, p.Wpad, nu);
             v *= sc;                                               // :4012
             if (kpar == q.NVMR && !transmission) v += Zs * dB;     // :6467-6468
             v *= xf;                                               // :4247

@@ -1,5 +1,6 @@
-// ansfm_rt_params.h -- arguments of the thermal / transmission / single-scattering RT kernels (ansfm_rt_kernels.hip.h).  The
-// entry points fill them and ansfm_rt.hip launches with them; no kernel and no device code here.
+// ansfm_rt_params.h -- arguments of the thermal / transmission / single-scattering RT kernels (ansfm_rt_kernels.hip.h) and of the
+// transit kernels (ansfm_transit_kernels.hip.h).  The entry points fill them and ansfm_rt.hip / ansfm_transit.hip launch with
+// them; no kernel and no device code here.
 #pragma once
 #include <stdint.h>
 
@@ -55,5 +56,34 @@ struct RtGParams {
     unsigned gas_mask;                    // as OverlapGParams::gas_mask: the slots of the other gases are zero and not read
     signed char slot_of_param[kMaxPar];   // -1 none, 0..S-1 gas slot (x1e-4), S = temperature slot
 };
+
+// Primary-transit depth with gradients (ansfm_transit_kernels.hip.h): the limb paths enter as the path matrix
+// Sm[l][p] = sum of SCALE over the entries of path p that lie in layer l, compressed by path and by layer
+struct TransitParams {
+    const double *tau;       // [L][G][Wpad]
+    const double *cont;      // [L][Wpad] or nullptr
+    const double *delg;      // [G]
+    const double *weight;    // [P] c_p: the annulus weight of path p in AREA = sum_p c_p (1 - T_p)
+    const int32_t *col_ptr;  // [P + 1] entries of path p: col_ptr[p] .. col_ptr[p + 1]
+    const int32_t *col_lay;  // [nnz] their layers
+    const double *col_val;   // [nnz] Sm[l][p]
+    const int32_t *row_ptr;  // [L + 1] entries of layer l
+    const int32_t *row_path; // [nnz] their paths
+    const double *row_val;   // [nnz] Sm[l][p]
+    double *sens;            // [L][G][Wpad] A = sum_p c_p exp(-tau_path) Sm[l][p]
+    double *tpart;           // [P][G][Wpad] exp(-tau_path) of every g-ordinate
+    double *area;            // [W]
+    double *trans;           // [W][P]
+    double *darea;           // [W][NPAR][L]
+    const double *dk;        // [L][NP1][G][Wpad]
+    const double *dcont;     // [NPAR][L][Wpad] or nullptr
+    const double *dcont_gas; // [L][Wpad] or nullptr (as RtGParams)
+    int W, Wpad, G, L, P;
+    int NPAR, NVMR, NP1;
+    unsigned gas_mask;
+    signed char slot_of_param[kMaxPar];
+};
+// rows of the 64-lane LDS tile of k_transit_sens that one workgroup may take (160 KiB / 512 B): the cap on layers and on paths
+constexpr int kTransitMaxRows = 320;
 
 }  // namespace ansfm

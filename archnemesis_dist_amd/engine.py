@@ -479,6 +479,60 @@ class AnsfmEngine:
             self._chain_dspec = _fingerprint(dspec[0])
         return (spec[0], dspec[0]) if single else (spec, dspec)
 
+    def cirsradg_ck_transit(self, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
+                            path_weight, gradients_on_device=False, dtau_every_gas=None):
+        """Primary-transit depth with analytic gradients of one model (nemesisPTfm :1838-1995), collapsed over the limb paths
+        on the device: AREA (W,) = sum_p path_weight[p] (1 - TRANS[:, p]), TRANS (W, P) the path transmissions, and
+        dAREA (W, NPAR, L) = d AREA / d (layer property) with dTAUTOT assembled as in `cirsradg_ck_thermal`.  lay_press_pa,
+        lay_temp (L,), amount (NGAS, L), taucont (W, L) or None, dtaucon (W, NPAR, L) or None, NLAYIN (P,), LAYINC / SCALE
+        (LIMAX, P), path_weight (P,) the annulus weights c_p (`transit.path_weights`).  gradients_on_device=True: dAREA is not
+        copied to the host (None in its place) and `map2pro(None, ...)` with LAYINC = arange(L), NPATH = 1 continues from the
+        device copy; only this arms the chain -- after a call that returned dAREA, `map2pro(None, ...)` raises ValueError.  dtau_every_gas as in `cirsradg_ck_thermal`.  NotImplementedError above
+        320 layers or paths."""
+        W, G, NP, NT, S = self.dims
+        lp = _np(lay_press_pa)
+        if lp.ndim != 1:
+            raise ValueError("cirsradg_ck_transit: one model, lay_press_pa (NLAY,)")
+        L = lp.shape[0]
+        lt = _np(lay_temp).reshape(L)
+        am = _np(amount).reshape(S, L)
+        tc = None if taucont is None else _np(taucont).reshape(W, L)
+        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, NPAR, L)
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        SC = _np(SCALE).reshape(LIMAX, P)
+        cw = _np(path_weight).reshape(P)
+        if NLAYIN.shape != (P,):
+            raise ValueError("cirsradg_ck_transit: NLAYIN must be (NPATH,)")
+        ig = _np(igas_map, np.int32)
+        if dtau_every_gas is not None:
+            dg = _np(dtau_every_gas)
+            if dg.shape != (W, L):
+                raise ValueError("cirsradg_ck_transit: dtau_every_gas must be (NWAVE, NLAY)")
+            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
+        area = np.empty(W); trans = np.empty((W, P))
+        darea = None if gradients_on_device else np.empty((W, int(NPAR), L))
+        self._chain_dspec = None
+        try:
+            rc = self._lib.ansfm_cirsradg_ck_transit(
+                self._ctx, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
+                _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(cw), _ptr(area), _ptr(trans), _ptr(darea))
+        finally:
+            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
+                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
+        self._check(rc, "cirsradg_ck_transit")
+        if gradients_on_device:
+            self._chain_dspec = ("device", W, int(NPAR), L, 1)
+        return area, trans, darea
+
+    def transit_last(self):
+        """(scratch bytes beyond the gas stage, k_transit_sens ms, k_transit_grad ms) of the last cirsradg_ck_transit call"""
+        info = (C.c_double * 3)()
+        self._check(self._lib.ansfm_transit_last(self._ctx, C.byref(info)), "transit_last")
+        return int(info[0]), info[1], info[2]
+
     def cirsradg_ck_thermal(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
                             NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None, gradients_on_device=False,
                             dtau_every_gas=None):

@@ -563,6 +563,95 @@ class CIRSradGPU:
             return SPECOUT, dSPECOUT, dTSURF          # (NWAVE,NPATH), (NWAVE,NPAR,NLAYINmax,NPATH), (NWAVE,NPATH)
         return SPECOUT                                                        # (NWAVE, NPATH)
 
+    # ---- primary transit with gradients: the depth and its layer gradients collapsed on the device ------------------
+    def nemesisPTfm(self, gradients=False):
+        """nemesisPTfm (ForwardModel_0.py:1838-1995).  Without gradients: the reference's method, whose CIRSrad is the seam
+        above.  With gradients the reference asks CIRSrad for dSPECOUT (NWAVE, NPAR, 2 NLAY, NLAY - 1), maps it to the state
+        vector and only then sums the annuli; here `AnsfmEngine.cirsradg_ck_transit` sums the annuli first (the absorbing area
+        and its gradient with respect to every layer property), and map2pro / map2xvec run on that (NWAVE, NPAR, NLAY, 1)
+        array on the device.  The same steps as the reference's otherwise; its own method takes over for a Telluric object,
+        a case CIRSrad would delegate, and more layers than the fused call takes."""
+        from copy import deepcopy
+        if gradients is False:
+            return super().nemesisPTfm(False)
+        if getattr(self, "Telluric", None) is not None:
+            return super().nemesisPTfm(gradients)
+        eng = get_engine(self.ansfm_device)
+        if not hasattr(eng, "cirsradg_ck_transit"):
+            return super().nemesisPTfm(gradients)
+        from . import transit as _transit
+        self.Variables1 = deepcopy(self.Variables)                              # :1868-1876
+        self.MeasurementX = deepcopy(self.Measurement)
+        self.AtmosphereX = deepcopy(self.Atmosphere)
+        self.ScatterX = deepcopy(self.Scatter)
+        self.StellarX = deepcopy(self.Stellar)
+        self.SurfaceX = deepcopy(self.Surface)
+        self.LayerX = deepcopy(self.Layer)
+        self.SpectroscopyX = deepcopy(self.Spectroscopy)
+        self.CIAX = deepcopy(self.CIA)
+        self.check_gas_spec_atm()
+        self.check_wave_range_consistency()
+        if int(self.MeasurementX.IFORM) != IFORM_TRANSIT_DEPTH:
+            raise ValueError('error in nemesisPTfm :: Measurement unit must be set to TransitDepth (IFORM=2) for primary transit observations')
+        if self.MeasurementX.NGEOM != 1:
+            raise ValueError('error in nemesisPTfm :: Only one geometry is allowed for primary transit observations (NGEOM=1)')
+        self.Measurement.build_ils(IGEOM=0)                                     # :1890-1895
+        wavecalc_min, wavecalc_max = self.Measurement.calc_wave_range(apply_doppler=True, IGEOM=None)
+        if self.SpectroscopyX.NGAS > 0:
+            self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
+        self.adjust_hydrostat = True
+        xmap = self.subprofretg()
+        self.LayerX.DUST_UNITS_FLAG = self.AtmosphereX.DUST_UNITS_FLAG
+        self.calc_path_PT()
+        S, L, P, A = self.SpectroscopyX, self.LayerX, self.PathX, self.AtmosphereX
+        imod = np.unique(np.asarray(P.IMOD).astype(int))
+        if (not self._ansfm_supported(True) or not self._ansfm_transmission_branch(int(imod[0]))
+                or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)):
+            return super().nemesisPTfm(gradients)
+        NPATH = int(P.NPATH)
+        NLAYIN = np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH)
+        LAYINC = np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH)
+        SCALE = np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH)
+        BASEH_TANHE = _transit.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)      # :1906-1908
+        weights = _transit.path_weights(BASEH_TANHE, A.RADIUS)                  # the trapezoid of :1949-1954, by path
+        self._ansfm_upload_table(eng)
+        TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(True)
+        taucont = TAUCIA + TAUDUST + TAURAY                                     # :3989
+        f_gas = self._ansfm_layer_inputs()
+        NVMR, NDUST, NPRO, NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
+        NPAR = NVMR + 2 + int(self.ScatterX.NDUST)
+        igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
+        try:
+            AREA, SPECOUT, _ = eng.cirsradg_ck_transit(np.asarray(L.PRESS, dtype=np.float64), np.asarray(L.TEMP, dtype=np.float64), f_gas,
+                                                       taucont, dTAUCON, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE, weights,
+                                                       gradients_on_device=True)
+        except NotImplementedError:                 # more layers or paths than the fused call takes
+            _note("nemesisPTfm with gradients: more layers or paths than the fused transit call takes; the reference's method runs "
+                  "over CIRSrad(return_grad=True) instead")
+            return super().nemesisPTfm(gradients)
+        _route("nemesisPTfm with gradients: transit depth collapsed over the paths on the device")
+        if self.ansfm_keep_side_products:
+            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
+            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, TAUCIA, TAUDUST, TAURAY)
+        incpar = [i for i in range(NVMR + 2 + NDUST) if np.mean(xmap[:, i, :]) != 0.0]   # :1925-1928
+        eng.map2pro(None, S.NWAVE, NVMR, NDUST, NPRO, 1, np.array([NLAY]), np.arange(NLAY), L.DTE, L.DAM, L.DCO, INCPAR=incpar,
+                    to_host=False)
+        dAREA = eng.map2xvec(None, S.NWAVE, NVMR, NDUST, NPRO, 1, self.Variables.NX, xmap)      # (NWAVE, 1, NX)
+        area_star = np.pi * ((self.StellarX.RADIUS * 1.0e3) ** 2)               # :1941-1944
+        area_planet_disk = np.pi * ((A.RADIUS + BASEH_TANHE[0] * 1.0e3) ** 2)
+        SPECMOD = np.zeros((S.NWAVE, self.MeasurementX.NGEOM))
+        dSPECMOD = np.zeros((S.NWAVE, self.MeasurementX.NGEOM, self.Variables.NX))
+        SPECMOD[:, 0] = AREA
+        dSPECMOD[:, 0, :] = dAREA[:, 0, :]
+        SPECMOD = (SPECMOD + area_planet_disk) / area_star * 100.               # :1963-1966
+        dSPECMOD = dSPECMOD / area_star * 100.
+        if int(S.ILBL) == ILBL_K_TABLES:                                        # :1986-1994
+            SPECONV, dSPECONV = self.MeasurementX.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        else:
+            SPECONV, dSPECONV = self.MeasurementX.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)
+        return SPECONV, dSPECONV
+
 
 def make_gpu_forward_model(reference_forward_model_cls, device=0):
     """Subclass of the reference's ForwardModel_0 with the GPU CIRSrad seam and `jacobian_nemesis` without the joblib

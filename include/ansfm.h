@@ -263,6 +263,28 @@ int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const do
                                    const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *xfac,
                                    double *SPECOUT, double *dSPECOUT);
 
+/* Primary-transit depth with analytic gradients of ONE model (nemesisPTfm, ForwardModel_0.py:1838-1995), collapsed over the
+ * paths on the device instead of through dSPECOUT (W, NPAR, LIMAX, P).  All pointers are host pointers.  With
+ * Sm[l][p] = sum of SCALE[j][p] over j < NLAYIN[p] with LAYINC[j][p] = l (padding beyond NLAYIN[p] is never read) and the annulus
+ * weights path_weight[P] = c_p of the trapezoid of :1949-1954:
+ *   tau_path[w][g][p] = sum_l Sm[l][p] (TAUGAS[w][g][l] + taucont[w][l])      TRANS[w][p] = sum_g DELG[g] exp(-tau_path)
+ *   AREA[w] = sum_p c_p (1 - TRANS[w][p])
+ *   dAREA[w][k][l] = sum_g DELG[g] (sum_p c_p exp(-tau_path) Sm[l][p]) dTAUTOT[w][g][k][l]
+ * with dTAUTOT assembled as in ansfm_cirsradg_ck_thermal before its x SCALE (gas slots x 1e-4 through igas_map, temperature slot
+ * at NVMR, dtaucon, a pending ansfm_set_shared_gas_gradient, ansfm_set_gradient_gases honoured).  nan_to_num (:4507) acts on
+ * each dAREA element (the reference applies it per path entry; the two agree whenever its dSPECOUT is finite).
+ * TRANS[W][P] and dAREA[W][NPAR][L] may be NULL; dAREA always stays on the device as a (W, NPAR, L, 1) result for
+ * ansfm_map2pro(dSPECIN = NULL) with LAYINC = 0 .. L - 1.  Device scratch beyond the gas stage is 8 (L + P) G Wpad bytes plus
+ * the outputs; ANSFM_ERR_UNSUPPORTED above 320 layers or 320 paths (a 64-lane LDS tile with one row per layer or path, 160 KiB).
+ * ANSFM_ERR_INVALID for NLAYIN[p] > LIMAX or a LAYINC[j][p], j < NLAYIN[p], outside 0 .. L - 1.
+ * ansfm_transit_last: info[0] the bytes of that scratch in the last call, info[1] / info[2] the milliseconds of k_transit_sens /
+ * k_transit_grad. */
+int ansfm_cirsradg_ck_transit(ansfm_ctx *ctx, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
+                              const double *taucont, const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P,
+                              int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                              const double *path_weight, double *AREA, double *TRANS, double *dAREA);
+int ansfm_transit_last(const ansfm_ctx *ctx, double info[3]);
+
 /* ---- analytic-gradient seams ---------------------------------------------------------------
  * ForwardModel_0.k_overlapg (ForwardModel_0.py:5842): + dkdT[W][G][L][S] -> tau[W][G][L],
  * dk[W][G][L][S+1] (slots 0..S-1 = d tau/d amount_gas, slot S = d tau/dT). */

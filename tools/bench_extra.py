@@ -44,6 +44,8 @@ def main():
         bench_mie(eng, out)
     if only == "brdf":                                      # 0.18 GB of matrix back over PCIe: on request only
         bench_brdf(eng, out)
+    if only == "transit":                                   # 1.6 GB dSPECOUT on the host for the un-collapsed route: on request only
+        bench_transit(eng, out)
     if only == "ss":                                        # 10 GB of host arrays: on request only
         bench_ss(eng, out, rng)
     print(json.dumps(out, indent=1))
@@ -402,6 +404,77 @@ def bench_brdf(eng, out, W=10000, NMU=16, NPHI=101, NF=8, n=3, slice_w=16):
         "kernel_ms": ms, "end_to_end_ms": 1e3 * wall, "hapke_evaluations": evals, "evaluations_per_s_kernel": evals / (1e-3 * ms),
         "matrix_bytes": int(got.nbytes), "numpy_restatement_s_on_a_slice_of_%d_wavenumbers" % slice_w: t_host,
         "slice_vs_gpu_rel_plane_max": bc.deviation(got[:slice_w], host)}
+
+
+def bench_transit(eng, out, W=1024, n=5):
+    """nemesisPTfm(gradients=True) at the C2 atmosphere as a transit (G = 20, S = 8, L = 100 -> P = 99 limb paths, LIMAX = 200,
+    NPAR = 10, NPRO = 100, NX = 200): the fused call + map2pro + map2xvec on (W, NPAR, L, 1) beside the un-collapsed route --
+    cirsradg_ck_transmission, map2pro and map2xvec on (W, NPAR, LIMAX, P), the trapezoid on the host -- alternated in one process,
+    medians of n after one warm-up each.  `transit <W>`: another width; `transit <W> fused`: the fused route alone (W = 10000:
+    the un-collapsed route would need 63 GB of device scratch) with its kernel times and the device memory it left reserved."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import transit_cases as tc
+    from archnemesis_dist_amd import transit
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    fused_only = len(sys.argv) > 3 and sys.argv[3] == "fused"
+    G, S, L, NP, NT, NPRO, NX = 20, 8, 100, 20, 15, 100, 200
+    _, delg = syn.gauss_legendre_01(G, True)
+    PRESS, TEMP, K = syn.synth_ktable(W, G, NP, NT, S)
+    free0 = torch.cuda.mem_get_info(0)[0]
+    eng.upload_ktable(K, PRESS, TEMP, 200.0 + 0.1 * np.arange(W), delg); del K
+    atm = syn.synth_atmosphere(L, S)
+    rng = np.random.default_rng(4)
+    NLAYIN, LAYINC, SCALE = tc.limb_paths(L, rng)
+    SCALE = SCALE / 30.0
+    BASEH = np.linspace(0.0, 4.0e5, L)
+    RADIUS, RSTAR = 7.0e7, 7.0e5
+    tan = transit.tangent_heights_km(BASEH, NLAYIN, LAYINC)
+    c = transit.path_weights(tan, RADIUS)
+    NVMR, NDUST = S, 0
+    NPAR = NVMR + 2 + NDUST
+    ig = np.arange(S, dtype=np.int32)
+    DTE, DAM, DCO = (rng.uniform(0, 1, (L, NPRO)) for _ in range(3))
+    xmap = rng.normal(size=(NX, NPAR, NPRO))
+    lp, lt, am = atm["lay_press_pa"][0], atm["lay_temp"][0], atm["amount"][0]
+    area_star = np.pi * (RSTAR * 1.0e3) ** 2
+    P = NLAYIN.size
+
+    def fused():
+        AREA, _, _ = eng.cirsradg_ck_transit(lp, lt, am, None, None, NVMR, NPAR, ig, NLAYIN, LAYINC, SCALE, c, gradients_on_device=True)
+        eng.map2pro(None, W, NVMR, NDUST, NPRO, 1, np.array([L]), np.arange(L), DTE, DAM, DCO, to_host=False)
+        d = eng.map2xvec(None, W, NVMR, NDUST, NPRO, 1, NX, xmap)
+        return (AREA + np.pi * (RADIUS + tan[0] * 1.0e3) ** 2) / area_star * 100., d[:, 0, :] / area_star * 100.
+
+    def uncollapsed():
+        SPECOUT, dS = eng.cirsradg_ck_transmission(lp, lt, am, None, None, NVMR, NPAR, ig, NLAYIN, LAYINC, SCALE)
+        pro = eng.map2pro(dS, W, NVMR, NDUST, NPRO, P, NLAYIN, LAYINC, DTE, DAM, DCO)
+        d = eng.map2xvec(pro, W, NVMR, NDUST, NPRO, P, NX, xmap)                     # (W, P, NX)
+        return ((1. - SPECOUT) @ c + np.pi * (RADIUS + tan[0] * 1.0e3) ** 2) / area_star * 100., -np.einsum("wpx,p->wx", d, c) / area_star * 100.
+
+    res = {"W": W, "G": G, "S": S, "L": L, "P": int(P), "NPAR": NPAR, "NPRO": NPRO, "NX": NX, "median_of": n}
+    a = fused()
+    tf, tu, kf, ku = [], [], [], []
+    if not fused_only:
+        b = uncollapsed()
+        res["depth_max_rel_diff"] = float(np.max(np.abs(a[0] / b[0] - 1.0)))
+        res["gradient_max_diff_over_max"] = float(np.max(np.abs(a[1] - b[1])) / np.max(np.abs(b[1])))
+    for _ in range(n):
+        t = time.perf_counter(); fused(); tf.append(time.perf_counter() - t)
+        kf.append(eng.last_kernel_ms()["overlap_ms"])
+        if not fused_only:
+            t = time.perf_counter(); uncollapsed(); tu.append(time.perf_counter() - t)
+            ku.append(eng.last_kernel_ms()["overlap_ms"])
+    scratch, ms_sens, ms_grad = eng.transit_last()
+    res.update(fused_wall_s=float(np.median(tf)), fused_overlapg_kernel_ms=float(np.median(kf)), k_transit_sens_ms=ms_sens,
+               k_transit_grad_ms=ms_grad, transit_scratch_bytes=scratch,
+               device_bytes_reserved_since_start=int(free0 - torch.cuda.mem_get_info(0)[0]))
+    if not fused_only:
+        res.update(uncollapsed_wall_s=float(np.median(tu)), uncollapsed_overlapg_kernel_ms=float(np.median(ku)),
+                   overlapg_share_of_fused=float(np.median(kf)) * 1e-3 / float(np.median(tf)),
+                   overlapg_share_of_uncollapsed=float(np.median(ku)) * 1e-3 / float(np.median(tu)))
+    out["transit_C2_W%d" % W] = res
 
 
 def bench_layer(eng, out):
