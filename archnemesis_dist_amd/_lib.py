@@ -6,6 +6,7 @@ is usable, this module raises -- product code never routes through the CPU oracl
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,36 +18,44 @@ ANSFM_OK = 0
 ERR_NAMES = {1: "ANSFM_ERR_INVALID", 2: "ANSFM_ERR_HIP", 3: "ANSFM_ERR_NOTABLE", 4: "ANSFM_ERR_UNSORTED",
              5: "ANSFM_ERR_UNSUPPORTED"}
 
-# every symbol include/ansfm.h declares (tests check the library exports all of them)
-EXPORTS = [
-    "ansfm_abi_version", "ansfm_create", "ansfm_destroy", "ansfm_last_error", "ansfm_set_stream",
-    "ansfm_synchronize", "ansfm_set_f32_semantics", "ansfm_upload_ktable", "ansfm_upload_ktable_dev", "ansfm_ktable_info",
-    "ansfm_calc_k", "ansfm_k_overlap", "ansfm_thermal_emission", "ansfm_cirsrad_ck_thermal",
-    "ansfm_cirsrad_ck_thermal_dev", "ansfm_get_taugas", "ansfm_last_kernel_ms",
-    "ansfm_k_overlapg", "ansfm_cirsradg_ck_thermal", "ansfm_cirsradg_ck_thermal_dev", "ansfm_scloud11wave_core", "ansfm_upload_lbltable", "ansfm_calc_klbl", "ansfm_add_line_set_monochromatic_absorption", "ansfm_layer_average",
-    "ansfm_map2pro", "ansfm_map2xvec", "ansfm_layer_averageg", "ansfm_lblconv", "ansfm_lblconv_fil", "ansfm_lblconv_ngeom", "ansfm_lblconv_fil_ngeom", "ansfm_conv_fil", "ansfm_integrate_filter", "ansfm_calc_tau_rayleigh", "ansfm_calc_tau_dust", "ansfm_set_layer_dedup", "ansfm_last_layer_rows",
-    "ansfm_ktable_file_header", "ansfm_upload_ktable_files", "ansfm_ktable_grids", "ansfm_lbltable_file_header",
-    "ansfm_upload_lbltable_files", "ansfm_kdist_bins", "ansfm_calc_tau_cia", "ansfm_set_merge_keys", "ansfm_merge_redo_count", "ansfm_calc_tau_rayleigh_batch_dev", "ansfm_cirsrad_ck_scatter", "ansfm_thermal_emission_g", "ansfm_cirsrad_ck_transmission", "ansfm_cirsradg_ck_transmission", "ansfm_set_gradient_gases", "ansfm_set_shared_gas_gradient", "ansfm_singlescatt_plane_spectrum",
-    "ansfm_cirsrad_ck_singlescatt", "ansfm_cirsrad_ck_scatter_batch", "ansfm_last_scatter_cache",
-    "ansfm_layer_average_dev", "ansfm_calc_tau_rayleigh_batch_dev_in", "ansfm_last_rt_shared",
-    "ansfm_cirsrad_ck_thermal_ray_dev", "ansfm_last_scatter_windows", "ansfm_cirsrad_ck_scatter_batch_slice",
-    "ansfm_cirsrad_ck_singlescatt_batch", "ansfm_cirsrad_ck_scatter_batch_rows",
-    "ansfm_add_pseudo_continuum_monochromatic_absorption", "ansfm_lbl_accum_begin", "ansfm_lbl_accum_add_lines",
-    "ansfm_lbl_accum_add_pseudo_continuum", "ansfm_lbl_accum_read", "ansfm_lbl_accum_device_ptr",
-    "ansfm_ktable_has_boxed",
-    "ansfm_lblrt_begin", "ansfm_lblrt_add_isotopologue", "ansfm_lblrt_commit", "ansfm_lblrt_set_state",
-    "ansfm_lblrt_set_scratch_bytes", "ansfm_lblrt_last", "ansfm_calc_klbl_online", "ansfm_calc_klblg_online",
-    "ansfm_get_dtaugas",
-    "ansfm_mie_makephase", "ansfm_mie_set_radius_block", "ansfm_mie_set_radius_cap", "ansfm_mie_last",
-    "ansfm_surface_brdf", "ansfm_brdf_matrix", "ansfm_brdf_last",
-    "ansfm_cirsradg_ck_transit", "ansfm_transit_last",
-]
+_BY_VALUE = {"int": C.c_int, "unsigned int": C.c_uint, "double": C.c_double, "int64_t": C.c_int64}
+_RETURNS = {"int": C.c_int, "void": None, "const char *": C.c_char_p}
 
-_lib = None
+
+def prototypes(header):
+    """{name: (restype, argtypes)} of every `ret ansfm_name(args);` in the text of include/ansfm.h, in its order.  A pointer or
+    array parameter is a c_void_p (a plain `const char *`: c_char_p); int, unsigned int, double and int64_t go by value.
+    Anything else raises, with the prototype named: the header has grown a type this table does not know."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)        # comments
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)                  # preprocessor lines
+    norm = lambda d: " ".join(d.replace("*", " * ").split())              # one blank between tokens, `*` a token
+    out = {}
+    for ret, name, args in re.findall(r"([^;{}()]*?)\b(ansfm_\w+)\s*\(([^()]*)\)\s*;", text):
+        proto = f"{norm(ret)} {name}({norm(args)})"
+        if norm(ret) not in _RETURNS:
+            raise AnsfmError(f"include/ansfm.h: unknown return type in `{proto}`")
+        argtypes = []
+        for decl in ([] if norm(args) in ("", "void") else [norm(d) for d in args.split(",")]):
+            if "*" in decl or "[" in decl:
+                argtypes.append(C.c_char_p if re.fullmatch(r"const char \* \w+", decl) else C.c_void_p)
+                continue
+            by_value = " ".join(w for w in decl.split()[:-1] if w != "const")     # without the parameter's name
+            if by_value not in _BY_VALUE:
+                raise AnsfmError(f"include/ansfm.h: unknown type of parameter `{decl}` in `{proto}`")
+            argtypes.append(_BY_VALUE[by_value])
+        out[name] = (_RETURNS[norm(ret)], argtypes)
+    return out
 
 
 class AnsfmError(RuntimeError):
     pass
+
+
+# the one statement of the C-ABI is include/ansfm.h: the ctypes prototypes and the list of symbols are read from it
+PROTOTYPES = prototypes(open(os.path.join(INCLUDE, "ansfm.h")).read())
+EXPORTS = list(PROTOTYPES)
+
+_lib = None
 
 
 def hipcc_path():
@@ -119,118 +128,9 @@ def load():
                          "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    vp, ci, cd = C.c_void_p, C.c_int, C.c_double
-    lib.ansfm_abi_version.restype = ci
-    lib.ansfm_create.argtypes = [ci, C.POINTER(vp)]
-    lib.ansfm_destroy.argtypes = [vp]
-    lib.ansfm_destroy.restype = None
-    lib.ansfm_last_error.argtypes = [vp]
-    lib.ansfm_last_error.restype = C.c_char_p
-    lib.ansfm_set_stream.argtypes = [vp, vp]
-    lib.ansfm_synchronize.argtypes = [vp]
-    lib.ansfm_set_f32_semantics.argtypes = [vp, ci, ci]
-    lib.ansfm_upload_ktable.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_upload_ktable_dev.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_ktable_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(ci)]
-    lib.ansfm_ktable_has_boxed.argtypes = [vp, C.POINTER(ci)]
-    lib.ansfm_calc_k.argtypes = [vp, ci, vp, vp, vp, vp]
-    lib.ansfm_k_overlap.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp]
-    lib.ansfm_thermal_emission.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, cd, vp, vp, vp, cd, cd, vp]
-    lib.ansfm_thermal_emission_g.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, cd, vp, vp, vp, vp]
-    cirs = [vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_cirsrad_ck_thermal.argtypes = cirs
-    lib.ansfm_cirsrad_ck_thermal_dev.argtypes = cirs
-    lib.ansfm_cirsrad_ck_thermal_ray_dev.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, ci] + [vp] * 12
-    lib.ansfm_cirsrad_ck_transmission.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_set_gradient_gases.argtypes = [vp, C.c_uint]
-    lib.ansfm_set_shared_gas_gradient.argtypes = [vp, ci, vp]
-    lib.ansfm_cirsradg_ck_transmission.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_singlescatt_plane_spectrum.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, cd, vp, vp, vp, cd, cd, vp]
-    lib.ansfm_cirsrad_ck_singlescatt.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_cirsrad_ck_singlescatt_batch.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci] + [vp] * 12
-    lib.ansfm_get_taugas.argtypes = [vp, ci, vp]
-    lib.ansfm_scloud11wave_core.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, ci, ci,
-                                            vp, vp, vp, ci, ci, ci, vp, vp]
-    lib.ansfm_cirsrad_ck_scatter.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, ci,
-                                             vp, vp, ci, ci, ci, ci, vp, vp, vp]
-    # (ctx, ISPACE, n_models, L, press, temp, amount, cia, dust, ray, scat, ncont, nth, phasarr, lfrac, radg, ngeom, sol, emi, aphi,
-    #  solar, lowbc, brdf, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT)
-    lib.ansfm_cirsrad_ck_scatter_batch.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci,
-                                                   vp, ci, vp, vp, ci, ci, ci, ci, vp, vp]
-    # ... + (W_full, w_begin)
-    lib.ansfm_cirsrad_ck_scatter_batch_slice.argtypes = lib.ansfm_cirsrad_ck_scatter_batch.argtypes + [ci, ci]
-    # the slice entry's list with (R, cont_row) in front of the four opacities, which are rows then
-    lib.ansfm_cirsrad_ck_scatter_batch_rows.argtypes = ([vp, ci, ci, ci, vp, vp, vp, ci, vp]
-                                                        + lib.ansfm_cirsrad_ck_scatter_batch_slice.argtypes[7:])
-    lib.ansfm_last_scatter_cache.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.ansfm_last_scatter_windows.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.ansfm_upload_lbltable.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, ci, vp]
-    lib.ansfm_calc_klbl.argtypes = [vp, ci, vp, vp, vp, vp]
-    lib.ansfm_add_line_set_monochromatic_absorption.argtypes = [vp, ci, vp, ci, ci, vp, cd, vp, cd, vp, cd, cd, ci, vp, ci, vp,
-                                                                vp, vp, vp, vp, vp, vp, cd, cd, cd]
-    lib.ansfm_add_pseudo_continuum_monochromatic_absorption.argtypes = [vp, ci, vp, ci, ci, vp, cd, vp, cd, vp, cd, cd, ci, vp, ci,
-                                                                        vp, vp, vp, vp, vp, vp, vp, vp, ci]
-    lib.ansfm_lbl_accum_begin.argtypes = [vp, ci, vp, ci, vp, vp]
-    lib.ansfm_lbl_accum_add_lines.argtypes = [vp, ci, cd, cd, vp, cd, cd, ci, vp, ci, vp, vp, vp, vp, vp, vp, cd, cd, cd]
-    lib.ansfm_lbl_accum_add_pseudo_continuum.argtypes = [vp, ci, cd, cd, vp, cd, cd, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
-    lib.ansfm_lbl_accum_read.argtypes = [vp, vp]
-    lib.ansfm_lbl_accum_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci)]
-    lib.ansfm_get_dtaugas.argtypes = [vp, ci, vp]
-    lib.ansfm_lblrt_begin.argtypes = [vp, ci, vp, ci, ci]
-    lib.ansfm_lblrt_add_isotopologue.argtypes = [vp, ci, ci, cd, cd, ci, ci, cd, cd, vp, vp, vp, vp, vp, cd, cd, cd, ci, ci, cd, cd,
-                                                 vp, vp, vp, vp, vp, ci]
-    lib.ansfm_lblrt_commit.argtypes = [vp]
-    lib.ansfm_lblrt_set_state.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_lblrt_set_scratch_bytes.argtypes = [vp, C.c_int64]
-    lib.ansfm_lblrt_last.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
-    lib.ansfm_calc_klbl_online.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_calc_klblg_online.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_mie_makephase.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_mie_set_radius_block.argtypes = [vp, ci]
-    lib.ansfm_mie_set_radius_cap.argtypes = [vp, ci]
-    lib.ansfm_mie_last.argtypes = [vp, C.POINTER(cd), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.ansfm_surface_brdf.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp]
-    lib.ansfm_brdf_matrix.argtypes = [vp, ci, ci, vp, ci, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_brdf_last.argtypes = [vp, C.POINTER(cd)]
-    lib.ansfm_cirsradg_ck_transit.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_transit_last.argtypes = [vp, C.POINTER(cd * 3)]
-    lib.ansfm_layer_average.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 11
-    lib.ansfm_layer_average_dev.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp, vp]
-    lib.ansfm_layer_averageg.argtypes = [vp, ci, cd, ci, vp, vp, vp, ci, vp, ci, vp, vp, ci, vp, cd, ci, cd, ci, vp, vp] + [vp] * 15
-    lib.ansfm_calc_tau_cia.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, vp,
-                                       ci, vp, vp, vp]
-    lib.ansfm_ktable_file_header.argtypes = [C.c_char_p, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_upload_ktable_files.argtypes = [vp, ci, C.POINTER(C.c_char_p), cd, cd]
-    lib.ansfm_ktable_grids.argtypes = [vp, vp, vp, vp, vp]
-    lib.ansfm_kdist_bins.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp]
-    lib.ansfm_lbltable_file_header.argtypes = [C.c_char_p, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_upload_lbltable_files.argtypes = [vp, ci, C.POINTER(C.c_char_p), cd, cd]
-    lib.ansfm_set_layer_dedup.argtypes = [vp, ci]
-    lib.ansfm_set_merge_keys.argtypes = [vp, ci]
-    lib.ansfm_merge_redo_count.argtypes = [vp, C.POINTER(C.c_int64)]
-    lib.ansfm_last_layer_rows.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
-    lib.ansfm_lblconv.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, ci, cd, vp, vp]
-    lib.ansfm_lblconv_fil.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_calc_tau_rayleigh.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, vp, vp]
-    lib.ansfm_calc_tau_rayleigh_batch_dev.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
-    lib.ansfm_calc_tau_rayleigh_batch_dev_in.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
-    lib.ansfm_last_rt_shared.argtypes = [vp, vp]
-    lib.ansfm_calc_tau_dust.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_integrate_filter.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_conv_fil.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_lblconv_ngeom.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, cd, vp, vp]
-    lib.ansfm_lblconv_fil_ngeom.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
-    lib.ansfm_map2pro.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp]
-    lib.ansfm_map2xvec.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp]
-    lib.ansfm_k_overlapg.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
-    cirsg = [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ansfm_cirsradg_ck_thermal.argtypes = cirsg
-    lib.ansfm_cirsradg_ck_thermal_dev.argtypes = cirsg
-    lib.ansfm_last_kernel_ms.argtypes = [vp, C.POINTER(cd), C.POINTER(ci), C.POINTER(cd), C.POINTER(ci)]
-    for name in EXPORTS:
-        fn = getattr(lib, name)
-        if name not in ("ansfm_destroy", "ansfm_last_error"):
-            fn.restype = ci
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)                        # AttributeError: the library lacks a symbol the header declares
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

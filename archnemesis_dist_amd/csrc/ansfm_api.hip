@@ -1,8 +1,8 @@
 // ansfm_api.hip -- C-ABI of libansfm.so (include/ansfm.h): lifecycle of the context, tables, the gas-opacity stage and the
 // thermal / transmission / single-scattering radiative transfer with its gradients.  The other entry points are in
 // ansfm_scatter.hip, ansfm_lbl.hip, ansfm_ops.hip, ansfm_mie.hip and ansfm_surface.hip; ansfm_ctx.hip.h is what they share.
-// The merge, RT and transit kernels behind these entry points are launched from ansfm_overlap.hip, ansfm_overlapg.hip,
-// ansfm_rt.hip and ansfm_transit.hip.
+// The merge and RT kernels behind these entry points are launched from ansfm_overlap.hip, ansfm_overlapg.hip and ansfm_rt.hip;
+// the transit entry point, which shares the gas stage of the gradient entries, is in ansfm_transit.hip.
 // gfx950 only.  No CPU fallback: every entry point needs a live HIP device.
 #include "ansfm_table_kernels.hip.h"
 #include "ansfm_rt_params.h"
@@ -410,14 +410,6 @@ static int read_unsorted(ansfm_ctx *ctx, int *flag)
     *flag &= 1;
     return ANSFM_OK;
 }
-static int check_unsorted(ansfm_ctx *ctx)
-{
-    int flag = 0, rc = read_unsorted(ctx, &flag);
-    if (rc) return rc;
-    if (flag)
-        FAIL(ANSFM_ERR_UNSORTED, "k-distribution not non-decreasing in g although the table was flagged monotone at upload");
-    return ANSFM_OK;
-}
 
 }  // extern "C": the helpers of the entry points below are templates in places
 
@@ -432,6 +424,17 @@ template <class Run> static int rerun_unsorted(ansfm_ctx *ctx, Run run)
         if (rc || (rc = read_unsorted(ctx, &flag))) return rc;
         if (!flag) break;
     }
+    return ANSFM_OK;
+}
+
+// The end of an entry point that has no generic path to rerun on: synchronises, ANSFM_ERR_UNSORTED if the fast merge met such a
+// k-distribution
+int ansfm::check_unsorted(ansfm_ctx *ctx)
+{
+    int flag = 0, rc = read_unsorted(ctx, &flag);
+    if (rc) return rc;
+    if (flag)
+        FAIL(ANSFM_ERR_UNSORTED, "k-distribution not non-decreasing in g although the table was flagged monotone at upload");
     return ANSFM_OK;
 }
 
@@ -539,88 +542,197 @@ int ansfm::dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const d
     return ANSFM_OK;
 }
 
+// Which slot of the gradient merge (gas i: slot i, temperature: slot S) feeds parameter k of dSPECOUT, for the gradient RT
+// kernels and the transit kernels alike; -1: none
+int ansfm::fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int NVMR, int NPAR, unsigned gas_mask,
+                              signed char *slot_of_param)
+{
+    const int S = ctx->S;
+    for (int k = 0; k < kMaxPar; ++k) slot_of_param[k] = -1;
+    for (int i = 0; i < S; ++i) {   // assignment order of :3868-3870: a later gas overwrites an earlier one
+        if (igas_map_host[i] < 0 || igas_map_host[i] >= NPAR) FAIL(ANSFM_ERR_INVALID, "cirsradg: igas_map out of range");
+        // a gas that is not selected leaves the parameter to an earlier selected gas of the same column (isotopologues)
+        if ((gas_mask >> i) & 1u) slot_of_param[igas_map_host[i]] = (signed char)i;
+    }
+    slot_of_param[NVMR] = (gas_mask >> 31) ? (signed char)S : (signed char)-1;   // :3872 (written last)
+    return ANSFM_OK;
+}
+
+// The gas stage of a gradient call on device arrays, for the gradient RT kernels and the transit kernels alike: tau and the
+// derivatives of the gradient merge (ctx->tau, ctx->dkbuf; calc_klblg + :3812-3814 for LBL tables) between ev[0] and ev[1], the
+// continuum and its gradients transposed to the wave-fastest layouts (cont_t [n][L][Wpad], dcont_t [n][NPAR][L][Wpad], or nullptr)
+int ansfm::grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp,
+                          const double *amount, const double *taucont, const double *dtaucon, int NPAR, const double **cont_t,
+                          const double **dcont_t)
+{
+    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, NP1 = ctx->S + 1;
+    *cont_t = *dcont_t = nullptr;
+    HIPCHK(ctx->dkbuf.reserve((size_t)n_models * L * NP1 * G * Wpad * sizeof(double)));
+    HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+    int rc;
+    if ((rc = gas_prep(ctx, n_models * L, lay_press_pa, lay_temp))) return rc;
+    if (taucont) {
+        HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
+        launch_w_to_last(ctx->stream, (unsigned)n_models, taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
+        *cont_t = ctx->cont_t.as<double>();
+    }
+    if (dtaucon) {
+        HIPCHK(ctx->dcont_t.reserve((size_t)n_models * NPAR * L * Wpad * sizeof(double)));
+        launch_w_to_last(ctx->stream, (unsigned)n_models, dtaucon, ctx->dcont_t.as<double>(), W, Wpad, NPAR, L, 0, 0.0, (size_t)W * NPAR * L, (size_t)NPAR * L * Wpad);
+        *dcont_t = ctx->dcont_t.as<double>();
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    if ((rc = gas_tau(ctx, n_models, L, lay_press_pa, lay_temp, amount, false, ctx->dkbuf.as<double>()))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    return ANSFM_OK;
+}
+
+/* ---- the call record of the CIRSrad entry points ---------------------------------------------------------------------- */
+namespace {
+// What the thermal, transmission, single-scattering and gradient entry points take, under the names and in the layouts of
+// include/ansfm.h.  The extern "C" function fills it once and everything below reads it (as MsCall in ansfm_scatter.hip); what
+// an entry does not take stays null or 0.  The arrays are host or device pointers as the entry says; igas_map is a host
+// pointer always, ray_totam / ray_f4 device pointers always.
+struct RtCall {
+    int ISPACE = 0, n_models = 1, L = 0;
+    const double *lay_press_pa = nullptr, *lay_temp = nullptr, *amount = nullptr;
+    const double *taucont = nullptr, *tausca = nullptr, *phase = nullptr, *dtaucon = nullptr;
+    int ray_mode = 0;                       // != 0: the continuum is Rayleigh scattering alone, formed from the two arrays
+    const double *ray_totam = nullptr, *ray_f4 = nullptr;
+    int NVMR = 0, NPAR = 0;
+    const int32_t *igas_map = nullptr;
+    int P = 0, LIMAX = 0;
+    const int32_t *NLAYIN = nullptr, *LAYINC = nullptr;
+    const double *SCALE = nullptr, *EMTEMP = nullptr;
+    const double *TSURF = nullptr;          // [n_models]
+    const double *EMISSIVITY = nullptr, *SOLFLUX = nullptr, *REFLECTANCE = nullptr, *BRDF = nullptr, *SOL_ANG = nullptr,
+                 *EMISS_ANG = nullptr, *xfac = nullptr;
+    double *SPECOUT = nullptr, *dSPECOUT = nullptr, *dTSURF = nullptr;
+    int rt_mode = 0;                        // RtParams::mode: 0 thermal emission, 1 transmission, 2 single scattering
+};
+
+// The host arrays of a call through ctx->hb[], always in this order (an array the entry does not take uploads nothing and
+// passes its buffer by): the record returned has the device copies in their place, a null pointer stays null.  igas_map, the
+// outputs and the scalars are the caller's.  *rc: the first error.
+RtCall stage_call(ansfm_ctx *ctx, const RtCall &h, int *rc)
+{
+    const size_t W = ctx->W, nl = (size_t)h.n_models * h.L, nlp = (size_t)h.n_models * h.LIMAX * h.P;
+    Stager st{ctx};
+    RtCall d = h;
+    d.lay_press_pa = st.up(h.lay_press_pa, nl); d.lay_temp = st.up(h.lay_temp, nl); d.amount = st.up(h.amount, nl * ctx->S);
+    d.taucont = st.up(h.taucont, nl * W); d.tausca = st.up(h.tausca, nl * W); d.phase = st.up(h.phase, nl * W * h.P);
+    d.dtaucon = st.up(h.dtaucon, nl * W * h.NPAR);
+    d.NLAYIN = st.up(h.NLAYIN, h.P); d.LAYINC = st.up(h.LAYINC, (size_t)h.LIMAX * h.P);
+    d.SCALE = st.up(h.SCALE, nlp); d.EMTEMP = st.up(h.EMTEMP, nlp); d.TSURF = st.up(h.TSURF, h.n_models);
+    d.EMISSIVITY = st.up(h.EMISSIVITY, W); d.SOLFLUX = st.up(h.SOLFLUX, W); d.REFLECTANCE = st.up(h.REFLECTANCE, W);
+    d.BRDF = st.up(h.BRDF, W * h.P); d.SOL_ANG = st.up(h.SOL_ANG, h.P); d.EMISS_ANG = st.up(h.EMISS_ANG, h.P);
+    d.xfac = st.up(h.xfac, W);
+    *rc = st.rc;
+    return d;
+}
+
+// Which (model, layer) opacities a forward call computes: all of them, or (a batch, with de-duplication on) the distinct ones;
+// the Rayleigh columns are part of a layer's identity only where the call forms its continuum from them.  De-duplicating
+// synchronises.  Records the outcome for ansfm_last_layer_rows / ansfm_get_taugas.
+struct GasRows {
+    DedupRows k;               // the rows handed to the merge kernel
+    int n_k;                   // its view: n_k models of k.rows / n_k layers
+    const int32_t *tau_slot;   // [n][L] row of every (model, layer), or nullptr: its own
+};
+int gas_rows(ansfm_ctx *ctx, const RtCall &c, GasRows *g)
+{
+    *g = GasRows{DedupRows{c.n_models * c.L, c.lay_press_pa, c.lay_temp, c.amount}, c.n_models, nullptr};
+    if (ctx->dedup && c.n_models > 1 && !ctx->lblrt) {
+        const int rc = dedup_rows(ctx, c.n_models, c.L, c.lay_press_pa, c.lay_temp, c.amount, c.ray_mode ? c.ray_totam : nullptr,
+                                  c.ray_mode ? c.ray_f4 : nullptr, &g->k);
+        if (rc) return rc;
+        g->n_k = 1;
+        g->tau_slot = ctx->dd_slot.as<int32_t>();
+    }
+    ctx->last_rows = g->k.rows; ctx->last_dedup = g->tau_slot != nullptr;
+    return ANSFM_OK;
+}
+
+// The fields of the RT kernels' arguments that come straight from the record (device pointers) and the context, the rest
+// zero.  The caller adds what is its own: tau_slot, cont, cont_by_row, sca, phase, mode.
+void rt_params_of_call(ansfm_ctx *ctx, const RtCall &c, RtParams &r)
+{
+    memset(&r, 0, sizeof r);
+    r.tau = ctx->tau.as<double>();
+    r.wave = ctx->d_wave.as<double>();
+    r.delg = ctx->d_delg.as<double>();
+    r.nlayin = c.NLAYIN; r.layinc = c.LAYINC; r.scale = c.SCALE; r.emtemp = c.EMTEMP;
+    r.lay_press = c.lay_press_pa; r.tsurf = c.TSURF;
+    r.emissivity = c.EMISSIVITY; r.solflux = c.SOLFLUX; r.reflectance = c.REFLECTANCE; r.brdf = c.BRDF; r.xfac = c.xfac;
+    r.sol_ang = c.SOL_ANG; r.emiss_ang = c.EMISS_ANG;
+    r.out = c.SPECOUT;
+    r.W = ctx->W; r.Wpad = ctx->Wpad; r.G = ctx->G; r.L = c.L; r.P = c.P; r.LIMAX = c.LIMAX; r.ispace = c.ISPACE;
+}
+
+// The one path of the array-level seams (ansfm_thermal_emission, ansfm_singlescatt_plane_spectrum) as two small host vectors
+// for them to stage: hi = NLAYIN[1] = Li, LAYINC[Li] = identity; hd = SCALE[Li] = 1, TSURF, SOL_ANG, EMISS_ANG
+void identity_path(int Li, double TSURF, double SOL_ANG, double EMISS_ANG, std::vector<int32_t> &hi, std::vector<double> &hd)
+{
+    hi.assign(1 + Li, Li);
+    for (int j = 0; j < Li; ++j) hi[1 + j] = j;
+    hd.assign(Li + 3, 1.0);
+    hd[Li] = TSURF; hd[Li + 1] = SOL_ANG; hd[Li + 2] = EMISS_ANG;
+}
+}  // namespace
+
 extern "C" {
 
 /* ------------------------------------------------------------------------------------------ */
 /* fused CIRSrad (device pointers)                                                             */
 /* ------------------------------------------------------------------------------------------ */
-// ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); rt_mode 1:
+// c.ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); c.rt_mode 1:
 // the path transmission (ansfm_cirsrad_ck_transmission); generic: the merge sorts every k-distribution first (the rerun of a
 // call whose table turned out not to be sorted in g)
-static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L,
-                                 const double *lay_press_pa, const double *lay_temp,
-                                 const double *amount, const double *taucont, int P, int LIMAX,
-                                 const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                 const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                 const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
-                                 const double *EMISS_ANG, const double *xfac, double *SPECOUT,
-                                 int ray_mode, const double *ray_totam, const double *ray_f4, int rt_mode, bool generic)
+static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c, bool generic)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
-    if (n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN ||
-        !LAYINC || !SCALE || !EMTEMP || !TSURF || !SPECOUT || (ISPACE != 0 && ISPACE != 1))
+    if (c.n_models <= 0 || c.L <= 0 || c.P <= 0 || c.LIMAX <= 0 || !c.lay_press_pa || !c.lay_temp || !c.amount || !c.NLAYIN ||
+        !c.LAYINC || !c.SCALE || !c.EMTEMP || !c.TSURF || !c.SPECOUT || (c.ISPACE != 0 && c.ISPACE != 1))
         FAIL(ANSFM_ERR_INVALID, "cirsrad: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G;
+    const int W = ctx->W, Wpad = ctx->Wpad, L = c.L;
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    // ---- which (model, layer) opacities have to be computed: all of them, or (batches) the distinct ones -------
-    DedupRows k{n_models * L, lay_press_pa, lay_temp, amount};   // the rows handed to the merge kernel
-    int n_k = n_models;                                         // its view: n_k models of k.rows / n_k layers
-    const int32_t *tau_slot = nullptr;
+    GasRows g;
     int rc;
-    if (ctx->dedup && n_models > 1 && !ctx->lblrt) {   // the only synchronisation of this entry point (batches only)
-        if ((rc = dedup_rows(ctx, n_models, L, lay_press_pa, lay_temp, amount, ray_mode ? ray_totam : nullptr,
-                             ray_mode ? ray_f4 : nullptr, &k)))
-            return rc;
-        n_k = 1;
-        tau_slot = ctx->dd_slot.as<int32_t>();
-    }
-    const int rows = k.rows;
-    ctx->last_rows = rows; ctx->last_dedup = tau_slot != nullptr;
-    if ((rc = gas_prep(ctx, rows, k.press, k.temp))) return rc;
+    if ((rc = gas_rows(ctx, c, &g))) return rc;        // the only synchronisation of this entry point (batches only)
+    const int rows = g.k.rows;
+    if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
     const double *cont_t = nullptr;
-    if (ray_mode) {
+    if (c.ray_mode) {
         // the Rayleigh continuum of the rows that are computed (the distinct layers of the batch), straight in the layout the RT
         // reads: the 201 states of a C3 Jacobian have 696 of them, not 20 100
         HIPCHK(ctx->cont_t.reserve((size_t)rows * Wpad * sizeof(double)));
-        launch_tau_rayleigh_rows(ctx, rows, ray_mode, ISPACE, tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, ray_totam,
-                                 ray_f4);
+        launch_tau_rayleigh_rows(ctx, rows, c.ray_mode, c.ISPACE, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr,
+                                 c.ray_totam, c.ray_f4);
         HIPCHK(hipGetLastError());
         cont_t = ctx->cont_t.as<double>();
-    } else if (taucont) {
-        HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
-        launch_w_to_last(ctx->stream, (unsigned)n_models, taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
+    } else if (c.taucont) {
+        HIPCHK(ctx->cont_t.reserve((size_t)c.n_models * L * Wpad * sizeof(double)));
+        launch_w_to_last(ctx->stream, (unsigned)c.n_models, c.taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
         HIPCHK(hipGetLastError());
         cont_t = ctx->cont_t.as<double>();
     }
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    if ((rc = gas_tau(ctx, n_k, rows / n_k, k.press, k.temp, k.amount, generic))) return rc;
+    if ((rc = gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, generic))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
     RtParams r;
-    memset(&r, 0, sizeof r);
-    r.tau = ctx->tau.as<double>();
-    r.tau_slot = tau_slot;
+    rt_params_of_call(ctx, c, r);
+    r.tau_slot = g.tau_slot;
     r.cont = cont_t;
-    r.cont_by_row = (ray_mode && tau_slot) ? 1 : 0;
-    r.emi = nullptr;
-    r.wave = ctx->d_wave.as<double>();
-    r.delg = ctx->d_delg.as<double>();
-    r.nlayin = NLAYIN; r.layinc = LAYINC; r.scale = SCALE; r.emtemp = EMTEMP;
-    r.lay_press = lay_press_pa; r.tsurf = TSURF;
-    r.emissivity = EMISSIVITY; r.solflux = SOLFLUX; r.reflectance = REFLECTANCE; r.xfac = xfac;
-    r.sol_ang = SOL_ANG; r.emiss_ang = EMISS_ANG;
-    r.out = SPECOUT;
-    r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0;
-    r.mode = rt_mode;
+    r.cont_by_row = (c.ray_mode && g.tau_slot) ? 1 : 0;
+    r.mode = c.rt_mode;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-    rc = launch_rt(ctx, r, n_models);
+    rc = launch_rt(ctx, r, c.n_models);
     if (rc != ANSFM_OK) return rc;
     HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->overlap_launches = 1;
-    ctx->rt_launches = 1;
-    ctx->overlap_ms = -1.0;  // resolved lazily in ansfm_last_kernel_ms
-    ctx->last_n = n_models; ctx->last_L = L;
+    call_recorded(ctx, c.n_models, L);
     return ANSFM_OK;
 }
 
@@ -632,9 +744,12 @@ int ansfm_cirsrad_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L
                                  const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
                                  const double *EMISS_ANG, const double *xfac, double *SPECOUT)
 {
-    return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC,
-                                       SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT, 0,
-                                       nullptr, nullptr, 0, false);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.taucont = taucont; c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
+    c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
+    c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;
+    return cirsrad_ck_thermal_dev_impl(ctx, c, false);
 }
 
 int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
@@ -647,9 +762,13 @@ int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, i
     CHECK_CTX(ctx);
     if ((ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || !TOTAM || (ray_mode == 4 && !f4))
         FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_ray_dev: bad argument (ray_mode = IRAY 1, 2, 4 or 12 for calc_tau_rayleighv)");
-    return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, P, LIMAX, NLAYIN, LAYINC,
-                                       SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT,
-                                       ray_mode, TOTAM, ray_mode == 4 ? f4 : nullptr, 0, false);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.ray_mode = ray_mode; c.ray_totam = TOTAM; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
+    c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
+    c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;
+    return cirsrad_ck_thermal_dev_impl(ctx, c, false);
 }
 
 int ansfm_set_layer_dedup(ansfm_ctx *ctx, int enable)
@@ -717,35 +836,21 @@ int ansfm_last_kernel_ms(const ansfm_ctx *cctx, double *overlap_ms, int *overlap
 /* ------------------------------------------------------------------------------------------ */
 /* host-pointer wrappers                                                                       */
 /* ------------------------------------------------------------------------------------------ */
-static int cirsrad_ck_thermal_host(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                   const double *lay_temp, const double *amount, const double *taucont, int P, int LIMAX,
-                                   const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP,
-                                   const double *TSURF, const double *EMISSIVITY, const double *SOLFLUX,
-                                   const double *REFLECTANCE, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
-                                   double *SPECOUT, int rt_mode)
+static int cirsrad_ck_thermal_host(ansfm_ctx *ctx, const RtCall &h)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
-    if (n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !SPECOUT) FAIL(ANSFM_ERR_INVALID, "cirsrad: bad argument");
+    if (h.n_models <= 0 || h.L <= 0 || h.P <= 0 || h.LIMAX <= 0 || !h.SPECOUT) FAIL(ANSFM_ERR_INVALID, "cirsrad: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, S = ctx->S;
-    const size_t D = sizeof(double), nl = (size_t)n_models * L, nlp = (size_t)n_models * LIMAX * P;
-    Stager st{ctx};
-    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
-                 *cont = st.up(taucont, nl * W);
-    const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
-    const double *scale = st.up(SCALE, nlp), *emtemp = st.up(EMTEMP, nlp), *tsurf = st.up(TSURF, n_models),
-                 *emis = st.up(EMISSIVITY, W), *solflux = st.up(SOLFLUX, W), *refl = st.up(REFLECTANCE, W),
-                 *sol_ang = st.up(SOL_ANG, P), *emiss_ang = st.up(EMISS_ANG, P), *xf = st.up(xfac, W);
-    if (st.rc) return st.rc;
-    HIPCHK(ctx->tmp_out.reserve((size_t)n_models * W * P * D));
-    const int rc = rerun_unsorted(ctx, [&](bool generic) {
-        return cirsrad_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, press, temp, am, cont, P, LIMAX, nlayin, layinc, scale, emtemp,
-                                           tsurf, emis, solflux, refl, sol_ang, emiss_ang, xf, ctx->tmp_out.as<double>(), 0, nullptr,
-                                           nullptr, rt_mode, generic);
-    });
+    int rc;
+    RtCall d = stage_call(ctx, h, &rc);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)n_models * W * P * D, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t nout = (size_t)h.n_models * ctx->W * h.P * sizeof(double);
+    HIPCHK(ctx->tmp_out.reserve(nout));
+    d.SPECOUT = ctx->tmp_out.as<double>();
+    rc = rerun_unsorted(ctx, [&](bool generic) { return cirsrad_ck_thermal_dev_impl(ctx, d, generic); });
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h.SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return ANSFM_OK;
 }
@@ -757,8 +862,12 @@ int ansfm_cirsrad_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, co
                              const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
                              const double *EMISS_ANG, const double *xfac, double *SPECOUT)
 {
-    return cirsrad_ck_thermal_host(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC, SCALE,
-                                   EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG, EMISS_ANG, xfac, SPECOUT, 0);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.taucont = taucont; c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
+    c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
+    c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;
+    return cirsrad_ck_thermal_host(ctx, c);
 }
 
 int ansfm_cirsrad_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp,
@@ -768,9 +877,12 @@ int ansfm_cirsrad_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const dou
     CHECK_CTX(ctx);
     if (n_models <= 0 || !SCALE) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_transmission: bad argument");
     std::vector<double> tsurf((size_t)n_models, -1.0);
-    // the emission temperatures are not used by the transmission epilogue: SCALE stands in for the array
-    return cirsrad_ck_thermal_host(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX, NLAYIN, LAYINC, SCALE,
-                                   SCALE, tsurf.data(), nullptr, nullptr, nullptr, nullptr, nullptr, xfac, SPECOUT, 1);
+    RtCall c;
+    c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount; c.taucont = taucont;
+    c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE;
+    c.EMTEMP = SCALE;   // the emission temperatures are not used by the transmission epilogue: SCALE stands in for the array
+    c.TSURF = tsurf.data(); c.xfac = xfac; c.SPECOUT = SPECOUT; c.rt_mode = 1;
+    return cirsrad_ck_thermal_host(ctx, c);
 }
 
 int ansfm_get_taugas(ansfm_ctx *ctx, int model, double *TAUGAS)
@@ -870,11 +982,9 @@ int ansfm_singlescatt_plane_spectrum(ansfm_ctx *ctx, int ISPACE, int W, int G, i
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave), Li = NLAYIN;
     const size_t D = sizeof(double);
-    std::vector<int32_t> hi(1 + Li);
-    hi[0] = Li;
-    for (int j = 0; j < Li; ++j) hi[1 + j] = j;
-    std::vector<double> hd(Li + 3, 1.0);
-    hd[Li] = TSURF; hd[Li + 1] = SOL_ANG; hd[Li + 2] = EMISS_ANG;
+    std::vector<int32_t> hi;
+    std::vector<double> hd;
+    identity_path(Li, TSURF, SOL_ANG, EMISS_ANG, hi, hd);
     Stager st{ctx};
     const double *tau = st.up(TAUTOT_PATH, (size_t)W * G * Li), *omega = st.up(OMEGA, (size_t)W * G * Li),
                  *phase = st.up(PHASE, (size_t)W * Li), *temp = st.up(TEMP, Li), *wave = st.up(WAVE, W),
@@ -912,48 +1022,31 @@ int ansfm_singlescatt_plane_spectrum(ansfm_ctx *ctx, int ISPACE, int W, int G, i
 
 // CIRSrad's single-scattering branch for n_models states (host pointers; TSURF [n]): the gas opacities of the distinct (model,
 // layer) rows, then mode 2 of k_thermal_rt with the model axis -- the prefix records of state 0 when the batch is de-duplicated
-static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const char *fn, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                       const double *lay_temp, const double *amount, const double *taucont, const double *tausca,
-                                       const double *phase, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
-                                       const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                       const double *BRDF, const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG,
-                                       const double *xfac, double *SPECOUT)
+static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const RtCall &h, const char *fn)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) { ctx->err = std::string(fn) + ": upload a k-table first"; return ANSFM_ERR_NOTABLE; }
-    bool bad = n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !tausca || !phase ||
-               !NLAYIN || !LAYINC || !SCALE || !EMTEMP || !TSURF || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT ||
-               (ISPACE != 0 && ISPACE != 1);
-    for (int m = 0; !bad && m < n_models; ++m) bad = TSURF[m] > 0.0 && !EMISSIVITY;
+    bool bad = h.n_models <= 0 || h.L <= 0 || h.P <= 0 || h.LIMAX <= 0 || !h.lay_press_pa || !h.lay_temp || !h.amount || !h.tausca ||
+               !h.phase || !h.NLAYIN || !h.LAYINC || !h.SCALE || !h.EMTEMP || !h.TSURF || !h.SOLFLUX || !h.SOL_ANG || !h.EMISS_ANG ||
+               !h.SPECOUT || (h.ISPACE != 0 && h.ISPACE != 1);
+    for (int m = 0; !bad && m < h.n_models; ++m) bad = h.TSURF[m] > 0.0 && !h.EMISSIVITY;
     if (bad) { ctx->err = std::string(fn) + ": bad argument"; return ANSFM_ERR_INVALID; }
-    if ((size_t)n_models * P > 65535) { ctx->err = std::string(fn) + ": at most 65535 (model, path) pairs per call"; return ANSFM_ERR_UNSUPPORTED; }
+    if ((size_t)h.n_models * h.P > 65535) { ctx->err = std::string(fn) + ": at most 65535 (model, path) pairs per call"; return ANSFM_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S;
-    const size_t D = sizeof(double), WL = (size_t)W * L, nl = (size_t)n_models * L, nlp = (size_t)n_models * LIMAX * P;
-    Stager st{ctx};
-    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
-                 *cont = st.up(taucont, n_models * WL), *sca = st.up(tausca, n_models * WL), *ph = st.up(phase, (size_t)n_models * P * WL);
-    const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
-    const double *scale = st.up(SCALE, nlp), *emtemp = st.up(EMTEMP, nlp), *tsurf = st.up(TSURF, n_models),
-                 *emis = st.up(EMISSIVITY, W), *brdf = st.up(BRDF, (size_t)W * P), *solflux = st.up(SOLFLUX, W),
-                 *sol_ang = st.up(SOL_ANG, P), *emiss_ang = st.up(EMISS_ANG, P), *xf = st.up(xfac, W);
-    if (st.rc) return st.rc;
+    const int W = ctx->W, Wpad = ctx->Wpad, n_models = h.n_models, L = h.L, P = h.P;
+    const size_t D = sizeof(double), WL = (size_t)W * L, nl = (size_t)n_models * L;
+    int rc;
+    RtCall d = stage_call(ctx, h, &rc);
+    if (rc) return rc;
     if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    // ---- which (model, layer) opacities have to be computed: all of them, or (batches) the distinct ones -------
-    DedupRows k{n_models * L, press, temp, am};
-    int n_k = n_models, rc;
-    const int32_t *tau_slot = nullptr;
-    if (ctx->dedup && n_models > 1 && !ctx->lblrt) {
-        if ((rc = dedup_rows(ctx, n_models, L, press, temp, am, nullptr, nullptr, &k))) return rc;
-        n_k = 1;
-        tau_slot = ctx->dd_slot.as<int32_t>();
-    }
-    const int rows = k.rows;
-    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = rows; ctx->last_dedup = tau_slot != nullptr;
-    if ((rc = gas_prep(ctx, rows, k.press, k.temp))) return rc;
+    GasRows g;
+    if ((rc = gas_rows(ctx, d, &g))) return rc;
+    const int rows = g.k.rows;
+    ctx->last_n = n_models; ctx->last_L = L;
+    if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    if (ctx->is_lbl) rc = gas_tau(ctx, n_k, rows / n_k, k.press, k.temp, k.amount, false);
-    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, n_k, rows / n_k, k.press, k.temp, k.amount, generic); });
+    if (ctx->is_lbl) rc = gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, false);
+    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, generic); });
     if (rc) return rc;
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
     // reference layouts [n][W][L] -> [n][L][Wpad] (continuum, scattering opacity) and [n][P][W][L] -> [n][P][L][Wpad] (phase)
@@ -962,29 +1055,25 @@ static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const char *fn, int ISPAC
     HIPCHK(ctx->misc.reserve((size_t)n_models * (1 + P) * LW * D));
     double *sca_t = ctx->misc.as<double>(), *ph_t = sca_t + (size_t)n_models * LW;
     const double *cont_t = nullptr;
-    if (cont) {
-        launch_w_to_last(ctx->stream, (unsigned)n_models, cont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, WL, LW);
+    if (d.taucont) {
+        launch_w_to_last(ctx->stream, (unsigned)n_models, d.taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, WL, LW);
         cont_t = ctx->cont_t.as<double>();
     }
-    launch_w_to_last(ctx->stream, (unsigned)n_models, sca, sca_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
-    launch_w_to_last(ctx->stream, (unsigned)(n_models * P), ph, ph_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
+    launch_w_to_last(ctx->stream, (unsigned)n_models, d.tausca, sca_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
+    launch_w_to_last(ctx->stream, (unsigned)(n_models * P), d.phase, ph_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
     HIPCHK(hipGetLastError());
-    HIPCHK(ctx->tmp_out.reserve((size_t)n_models * W * P * D));
+    const size_t nout = (size_t)n_models * W * P * D;
+    HIPCHK(ctx->tmp_out.reserve(nout));
+    d.SPECOUT = ctx->tmp_out.as<double>();
     RtParams r;
-    memset(&r, 0, sizeof r);
-    r.tau = ctx->tau.as<double>(); r.tau_slot = tau_slot; r.cont = cont_t; r.sca = sca_t; r.phase = ph_t;
-    r.wave = ctx->d_wave.as<double>(); r.delg = ctx->d_delg.as<double>();
-    r.nlayin = nlayin; r.layinc = layinc; r.scale = scale;
-    r.emtemp = emtemp; r.lay_press = press; r.tsurf = tsurf;
-    r.emissivity = emis; r.brdf = brdf; r.solflux = solflux;
-    r.sol_ang = sol_ang; r.emiss_ang = emiss_ang; r.xfac = xf;
-    r.out = ctx->tmp_out.as<double>();
-    r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0; r.mode = 2;
+    rt_params_of_call(ctx, d, r);
+    r.tau_slot = g.tau_slot; r.cont = cont_t; r.sca = sca_t; r.phase = ph_t;
+    r.mode = d.rt_mode;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     if ((rc = launch_rt(ctx, r, n_models))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->overlap_launches = 1; ctx->rt_launches = 1; ctx->overlap_ms = -1.0;
-    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, (size_t)n_models * W * P * D, hipMemcpyDeviceToHost, ctx->stream));
+    call_recorded(ctx, n_models, L);
+    HIPCHK(hipMemcpyAsync(h.SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));      // also: the staged host arrays (TSURF of the single entry) are consumed
     return ANSFM_OK;
 }
@@ -996,9 +1085,12 @@ int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double
                                  const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
                                  double *SPECOUT)
 {
-    return cirsrad_ck_singlescatt_impl(ctx, "cirsrad_ck_singlescatt", ISPACE, 1, L, lay_press_pa, lay_temp, amount, taucont, tausca,
-                                       phase, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, &TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG,
-                                       EMISS_ANG, xfac, SPECOUT);
+    RtCall c;
+    c.ISPACE = ISPACE; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount; c.taucont = taucont;
+    c.tausca = tausca; c.phase = phase; c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE;
+    c.EMTEMP = EMTEMP; c.TSURF = &TSURF; c.EMISSIVITY = EMISSIVITY; c.BRDF = BRDF; c.SOLFLUX = SOLFLUX; c.SOL_ANG = SOL_ANG;
+    c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT; c.rt_mode = 2;
+    return cirsrad_ck_singlescatt_impl(ctx, c, "cirsrad_ck_singlescatt");
 }
 
 int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
@@ -1008,9 +1100,12 @@ int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models,
                                        const double *BRDF, const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG,
                                        const double *xfac, double *SPECOUT)
 {
-    return cirsrad_ck_singlescatt_impl(ctx, "cirsrad_ck_singlescatt_batch", ISPACE, n_models, L, lay_press_pa, lay_temp, amount,
-                                       taucont, tausca, phase, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF,
-                                       SOLFLUX, SOL_ANG, EMISS_ANG, xfac, SPECOUT);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.taucont = taucont; c.tausca = tausca; c.phase = phase; c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC;
+    c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.BRDF = BRDF; c.SOLFLUX = SOLFLUX;
+    c.SOL_ANG = SOL_ANG; c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT; c.rt_mode = 2;
+    return cirsrad_ck_singlescatt_impl(ctx, c, "cirsrad_ck_singlescatt_batch");
 }
 
 int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR, int NLAYIN, const double *WAVE,
@@ -1052,12 +1147,9 @@ int ansfm_thermal_emission(ansfm_ctx *ctx, int ISPACE, int W, int G, int NLAYIN,
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave), Li = NLAYIN;
     const size_t D = sizeof(double);
-    // small path vectors: NLAYIN[1], LAYINC[Li] = identity, SCALE[Li] = 1, TSURF, angles
-    std::vector<int32_t> hi(1 + Li);
-    hi[0] = Li;
-    for (int j = 0; j < Li; ++j) hi[1 + j] = j;
-    std::vector<double> hd(Li + 3, 1.0);
-    hd[Li] = TSURF; hd[Li + 1] = SOL_ANG; hd[Li + 2] = EMISS_ANG;
+    std::vector<int32_t> hi;
+    std::vector<double> hd;
+    identity_path(Li, TSURF, SOL_ANG, EMISS_ANG, hi, hd);
     Stager st{ctx};
     const double *tau = st.up(TAUTOT_PATH, (size_t)W * G * Li), *emi = st.up(EMITOT_PATH, (size_t)W * Li),
                  *temp = st.up(TEMP, Li),      // EMTEMP[Li][P=1]
@@ -1082,18 +1174,12 @@ int ansfm_thermal_emission(ansfm_ctx *ctx, int ISPACE, int W, int G, int NLAYIN,
     RtParams r;
     memset(&r, 0, sizeof r);
     r.tau = ctx->misc.as<double>();
-    r.cont = nullptr;
     r.emi = emi_t;
     r.wave = wave;
-    r.delg = nullptr;
-    r.nlayin = di;
-    r.layinc = di + 1;
-    r.scale = dd;
-    r.emtemp = temp;
-    r.lay_press = press;
+    r.nlayin = di; r.layinc = di + 1;
+    r.scale = dd; r.emtemp = temp; r.lay_press = press;
     r.tsurf = dd + Li;
     r.emissivity = emis; r.solflux = solflux; r.reflectance = refl;
-    r.xfac = nullptr;
     r.sol_ang = dd + Li + 1; r.emiss_ang = dd + Li + 2;
     r.out = ctx->tmp_out.as<double>();
     r.W = W; r.Wpad = Wpad; r.G = G; r.L = Li; r.P = 1; r.LIMAX = Li; r.ispace = ISPACE; r.per_g = 1;
@@ -1127,89 +1213,29 @@ int ansfm_set_shared_gas_gradient(ansfm_ctx *ctx, int L, const double *dTAU_WL)
     return ANSFM_OK;
 }
 
-// Which slot of the gradient merge (gas i: slot i, temperature: slot S) feeds parameter k of dSPECOUT, for the gradient RT
-// kernels and the transit kernels alike; -1: none
-static int fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int NVMR, int NPAR, unsigned gas_mask,
-                              signed char *slot_of_param)
-{
-    const int S = ctx->S;
-    for (int k = 0; k < kMaxPar; ++k) slot_of_param[k] = -1;
-    for (int i = 0; i < S; ++i) {   // assignment order of :3868-3870: a later gas overwrites an earlier one
-        if (igas_map_host[i] < 0 || igas_map_host[i] >= NPAR) FAIL(ANSFM_ERR_INVALID, "cirsradg: igas_map out of range");
-        // a gas that is not selected leaves the parameter to an earlier selected gas of the same column (isotopologues)
-        if ((gas_mask >> i) & 1u) slot_of_param[igas_map_host[i]] = (signed char)i;
-    }
-    slot_of_param[NVMR] = (gas_mask >> 31) ? (signed char)S : (signed char)-1;   // :3872 (written last)
-    return ANSFM_OK;
-}
-
-// The gas stage of a gradient call on device arrays, for the gradient RT kernels and the transit kernels alike: tau and the
-// derivatives of the gradient merge (ctx->tau, ctx->dkbuf; calc_klblg + :3812-3814 for LBL tables) between ev[0] and ev[1], the
-// continuum and its gradients transposed to the wave-fastest layouts (cont_t [n][L][Wpad], dcont_t [n][NPAR][L][Wpad], or nullptr)
-static int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp,
-                          const double *amount, const double *taucont, const double *dtaucon, int NPAR, const double **cont_t,
-                          const double **dcont_t)
-{
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, NP1 = ctx->S + 1;
-    *cont_t = *dcont_t = nullptr;
-    HIPCHK(ctx->dkbuf.reserve((size_t)n_models * L * NP1 * G * Wpad * sizeof(double)));
-    HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    int rc;
-    if ((rc = gas_prep(ctx, n_models * L, lay_press_pa, lay_temp))) return rc;
-    if (taucont) {
-        HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
-        launch_w_to_last(ctx->stream, (unsigned)n_models, taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
-        *cont_t = ctx->cont_t.as<double>();
-    }
-    if (dtaucon) {
-        HIPCHK(ctx->dcont_t.reserve((size_t)n_models * NPAR * L * Wpad * sizeof(double)));
-        launch_w_to_last(ctx->stream, (unsigned)n_models, dtaucon, ctx->dcont_t.as<double>(), W, Wpad, NPAR, L, 0, 0.0, (size_t)W * NPAR * L, (size_t)NPAR * L * Wpad);
-        *dcont_t = ctx->dcont_t.as<double>();
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    if ((rc = gas_tau(ctx, n_models, L, lay_press_pa, lay_temp, amount, false, ctx->dkbuf.as<double>()))) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-    return ANSFM_OK;
-}
-
-// transmission: the path transmission and its gradients (ansfm_cirsradg_ck_transmission)
-static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                        const double *lay_temp, const double *amount, const double *taucont,
-                                        const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map_host, int P,
-                                        int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                        const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
-                                        const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF, bool transmission)
+// c.rt_mode 1: the path transmission and its gradients (ansfm_cirsradg_ck_transmission)
+static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg: upload a k-table first");
-    if (n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN || !LAYINC ||
-        !SCALE || !EMTEMP || !TSURF || !SPECOUT || !dSPECOUT || !dTSURF || !igas_map_host || NPAR <= 0 ||
-        NPAR > kMaxPar || NVMR < 0 || NVMR >= NPAR || (ISPACE != 0 && ISPACE != 1))
+    if (c.n_models <= 0 || c.L <= 0 || c.P <= 0 || c.LIMAX <= 0 || !c.lay_press_pa || !c.lay_temp || !c.amount || !c.NLAYIN ||
+        !c.LAYINC || !c.SCALE || !c.EMTEMP || !c.TSURF || !c.SPECOUT || !c.dSPECOUT || !c.dTSURF || !c.igas_map || c.NPAR <= 0 ||
+        c.NPAR > kMaxPar || c.NVMR < 0 || c.NVMR >= c.NPAR || (c.ISPACE != 0 && c.ISPACE != 1))
         FAIL(ANSFM_ERR_INVALID, "cirsradg: bad argument (NPAR <= 256)");
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, NP1 = S + 1;
+    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, n_models = c.n_models, L = c.L, P = c.P, LIMAX = c.LIMAX, NPAR = c.NPAR;
     HIPCHK(ctx->trold_ws.reserve((size_t)n_models * P * (LIMAX + 1) * G * Wpad * sizeof(double)));
     HIPCHK(ctx->dspec_i.reserve((size_t)n_models * P * NPAR * LIMAX * Wpad * sizeof(double)));
     int rc;
     const double *cont_t = nullptr, *dcont_t = nullptr;
-    if ((rc = grad_gas_stage(ctx, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, &cont_t, &dcont_t))) return rc;
+    if ((rc = grad_gas_stage(ctx, n_models, L, c.lay_press_pa, c.lay_temp, c.amount, c.taucont, c.dtaucon, NPAR, &cont_t, &dcont_t))) return rc;
     RtGParams q;
     memset(&q, 0, sizeof q);
-    RtParams &r = q.r;
-    r.tau = ctx->tau.as<double>();
-    r.cont = cont_t;
-    r.wave = ctx->d_wave.as<double>();
-    r.delg = ctx->d_delg.as<double>();
-    r.nlayin = NLAYIN; r.layinc = LAYINC; r.scale = SCALE; r.emtemp = EMTEMP;
-    r.lay_press = lay_press_pa; r.tsurf = TSURF;
-    r.emissivity = EMISSIVITY; r.xfac = xfac;
-    r.out = SPECOUT;
-    r.W = W; r.Wpad = Wpad; r.G = G; r.L = L; r.P = P; r.LIMAX = LIMAX; r.ispace = ISPACE; r.per_g = 0;
-    r.mode = transmission ? 1 : 0;
+    rt_params_of_call(ctx, c, q.r);
+    q.r.cont = cont_t;
+    q.r.mode = c.rt_mode;
     q.dk = ctx->dkbuf.as<double>();
     q.dcont = dcont_t;
-    q.dcont_gas = nullptr;
     if (ctx->dcont_gas_L) {
         if (ctx->dcont_gas_L != L || n_models != 1) {
             ctx->dcont_gas_L = 0;
@@ -1221,21 +1247,20 @@ static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, int ISPACE, int n_models
     }
     q.trold_ws = ctx->trold_ws.as<double>();
     q.dspec = ctx->dspec_i.as<double>();
-    q.dtsurf = dTSURF;
-    q.NPAR = NPAR; q.NVMR = NVMR; q.NP1 = NP1;
+    q.dtsurf = c.dTSURF;
+    q.NPAR = NPAR; q.NVMR = c.NVMR; q.NP1 = ctx->S + 1;
     q.gas_mask = ctx->is_lbl ? 0xFFFFFFFFu : ctx->grad_gas_mask;
-    if ((rc = fill_slot_of_param(ctx, igas_map_host, NVMR, NPAR, q.gas_mask, q.slot_of_param))) return rc;
+    if ((rc = fill_slot_of_param(ctx, c.igas_map, c.NVMR, NPAR, q.gas_mask, q.slot_of_param))) return rc;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     if ((rc = launch_rtg(ctx, q, n_models))) return rc;
     for (int m = 0; m < n_models; ++m) {
         const size_t nout = (size_t)W * NPAR * LIMAX * P;
-        launch_dspec_to_ref(ctx, ctx->dspec_i.as<double>() + (size_t)m * P * NPAR * LIMAX * Wpad, dSPECOUT + (size_t)m * nout, W, Wpad,
-                            NPAR, LIMAX, P, NLAYIN);
+        launch_dspec_to_ref(ctx, ctx->dspec_i.as<double>() + (size_t)m * P * NPAR * LIMAX * Wpad, c.dSPECOUT + (size_t)m * nout, W, Wpad,
+                            NPAR, LIMAX, P, c.NLAYIN);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->overlap_launches = 1; ctx->rt_launches = 1;
-    ctx->last_n = n_models; ctx->last_L = L;
+    call_recorded(ctx, n_models, L);
     return ANSFM_OK;
 }
 
@@ -1246,46 +1271,36 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
                                   const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
                                   const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF)
 {
-    return cirsradg_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR,
-                                        igas_map_host, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, xfac, SPECOUT,
-                                        dSPECOUT, dTSURF, false);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.taucont = taucont; c.dtaucon = dtaucon; c.NVMR = NVMR; c.NPAR = NPAR; c.igas_map = igas_map_host; c.P = P; c.LIMAX = LIMAX;
+    c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY;
+    c.xfac = xfac; c.SPECOUT = SPECOUT; c.dSPECOUT = dSPECOUT; c.dTSURF = dTSURF;
+    return cirsradg_ck_thermal_dev_impl(ctx, c);
 }
 
-static int cirsradg_ck_thermal_host(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                    const double *lay_temp, const double *amount, const double *taucont, const double *dtaucon,
-                                    int NVMR, int NPAR, const int32_t *igas_map, int P, int LIMAX, const int32_t *NLAYIN,
-                                    const int32_t *LAYINC, const double *SCALE, const double *EMTEMP, const double *TSURF,
-                                    const double *EMISSIVITY, const double *xfac, double *SPECOUT, double *dSPECOUT,
-                                    double *dTSURF, bool transmission)
+static int cirsradg_ck_thermal_host(ansfm_ctx *ctx, const RtCall &h)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg: upload a k-table first");
-    if (n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || NPAR <= 0 || !SPECOUT || !dTSURF || (!dSPECOUT && n_models != 1))
+    if (h.n_models <= 0 || h.L <= 0 || h.P <= 0 || h.LIMAX <= 0 || h.NPAR <= 0 || !h.SPECOUT || !h.dTSURF ||
+        (!h.dSPECOUT && h.n_models != 1))
         FAIL(ANSFM_ERR_INVALID, "cirsradg: bad argument (dSPECOUT may be NULL for a single model: the gradients then stay on the "
                                 "device for ansfm_map2pro)");
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, S = ctx->S;
-    const size_t D = sizeof(double), nl = (size_t)n_models * L, nlp = (size_t)n_models * LIMAX * P;
-    Stager st{ctx};
-    const double *press = st.up(lay_press_pa, nl), *temp = st.up(lay_temp, nl), *am = st.up(amount, nl * S),
-                 *cont = st.up(taucont, nl * W), *dcont = st.up(dtaucon, nl * W * NPAR);
-    const int32_t *nlayin = st.up(NLAYIN, P), *layinc = st.up(LAYINC, (size_t)LIMAX * P);
-    const double *scale = st.up(SCALE, nlp), *emtemp = st.up(EMTEMP, nlp), *tsurf = st.up(TSURF, n_models),
-                 *emis = st.up(EMISSIVITY, W), *xf = st.up(xfac, W);
-    if (st.rc) return st.rc;
-    const size_t nsp = (size_t)n_models * W * P, ndsp = (size_t)n_models * W * NPAR * LIMAX * P;
+    int rc;
+    RtCall d = stage_call(ctx, h, &rc);
+    if (rc) return rc;
+    const size_t D = sizeof(double), nsp = (size_t)h.n_models * ctx->W * h.P, ndsp = nsp * h.NPAR * h.LIMAX;
     HIPCHK(ctx->tmp_out.reserve((2 * nsp) * D));
     HIPCHK(ctx->dspec_ref.reserve(ndsp * D));     // kept on the device for ansfm_map2pro(dSPECIN = NULL)
     ctx->dspec_dims[0] = 0;
-    double *o_spec = ctx->tmp_out.as<double>(), *o_dts = o_spec + nsp;
-    const int rc = cirsradg_ck_thermal_dev_impl(ctx, ISPACE, n_models, L, press, temp, am, cont, dcont, NVMR, NPAR, igas_map, P,
-                                                LIMAX, nlayin, layinc, scale, emtemp, tsurf, emis, xf, o_spec,
-                                                ctx->dspec_ref.as<double>(), o_dts, transmission);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(SPECOUT, o_spec, nsp * D, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dTSURF, o_dts, nsp * D, hipMemcpyDeviceToHost, ctx->stream));
-    if (dSPECOUT) HIPCHK(hipMemcpyAsync(dSPECOUT, ctx->dspec_ref.p, ndsp * D, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_models == 1) { ctx->dspec_dims[0] = ctx->W; ctx->dspec_dims[1] = NPAR; ctx->dspec_dims[2] = LIMAX; ctx->dspec_dims[3] = P; }
+    d.SPECOUT = ctx->tmp_out.as<double>(); d.dTSURF = d.SPECOUT + nsp; d.dSPECOUT = ctx->dspec_ref.as<double>();
+    if ((rc = cirsradg_ck_thermal_dev_impl(ctx, d))) return rc;
+    HIPCHK(hipMemcpyAsync(h.SPECOUT, d.SPECOUT, nsp * D, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(h.dTSURF, d.dTSURF, nsp * D, hipMemcpyDeviceToHost, ctx->stream));
+    if (h.dSPECOUT) HIPCHK(hipMemcpyAsync(h.dSPECOUT, ctx->dspec_ref.p, ndsp * D, hipMemcpyDeviceToHost, ctx->stream));
+    if (h.n_models == 1) { ctx->dspec_dims[0] = ctx->W; ctx->dspec_dims[1] = h.NPAR; ctx->dspec_dims[2] = h.LIMAX; ctx->dspec_dims[3] = h.P; }
     return check_unsorted(ctx);
 }
 
@@ -1296,9 +1311,12 @@ int ansfm_cirsradg_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, c
                               const double *TSURF, const double *EMISSIVITY, const double *xfac, double *SPECOUT,
                               double *dSPECOUT, double *dTSURF)
 {
-    return cirsradg_ck_thermal_host(ctx, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
-                                    P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, xfac, SPECOUT, dSPECOUT, dTSURF,
-                                    false);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.taucont = taucont; c.dtaucon = dtaucon; c.NVMR = NVMR; c.NPAR = NPAR; c.igas_map = igas_map; c.P = P; c.LIMAX = LIMAX;
+    c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY;
+    c.xfac = xfac; c.SPECOUT = SPECOUT; c.dSPECOUT = dSPECOUT; c.dTSURF = dTSURF;
+    return cirsradg_ck_thermal_host(ctx, c);
 }
 
 int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa,
@@ -1310,129 +1328,14 @@ int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const do
     CHECK_CTX(ctx);
     if (n_models <= 0 || P <= 0 || !SCALE || !SPECOUT || !dSPECOUT) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transmission: bad argument");
     std::vector<double> tsurf((size_t)n_models, -1.0), dts((size_t)n_models * ctx->W * P);
+    RtCall c;
+    c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount; c.taucont = taucont;
+    c.dtaucon = dtaucon; c.NVMR = NVMR; c.NPAR = NPAR; c.igas_map = igas_map; c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN;
+    c.LAYINC = LAYINC; c.SCALE = SCALE;
     // no emission in this branch: SCALE stands in for the (unused) emission temperatures, dTSURF is identically zero
-    return cirsradg_ck_thermal_host(ctx, 0, n_models, L, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, P,
-                                    LIMAX, NLAYIN, LAYINC, SCALE, SCALE, tsurf.data(), nullptr, xfac, SPECOUT, dSPECOUT, dts.data(),
-                                    true);
-}
-
-// Primary-transit depth with gradients of one model (nemesisPTfm, ForwardModel_0.py:1838-1995), collapsed over the paths on the
-// device: the gas stage of cirsradg_ck_thermal_dev_impl, then k_transit_sens and k_transit_grad on the path matrix
-// Sm[l][p] = sum of SCALE over the entries j < NLAYIN[p] of path p with LAYINC[j][p] = l, built here.  Neither trold_ws nor
-// dspec_i is reserved; dAREA (W, NPAR, L, 1) stays in dspec_ref for ansfm_map2pro(dSPECIN = NULL).
-int ansfm_cirsradg_ck_transit(ansfm_ctx *ctx, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
-                              const double *taucont, const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P,
-                              int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                              const double *path_weight, double *AREA, double *TRANS, double *dAREA)
-{
-    CHECK_CTX(ctx);
-    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg_ck_transit: upload a k-table first");
-    if (L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN || !LAYINC || !SCALE || !path_weight ||
-        !AREA || !igas_map || NPAR <= 0 || NPAR > kMaxPar || NVMR < 0 || NVMR >= NPAR)
-        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: bad argument (NPAR <= 256)");
-    if (L > kTransitMaxRows || P > kTransitMaxRows)
-        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsradg_ck_transit: at most 320 layers and 320 paths (the 160 KiB LDS tile of k_transit_sens)");
-    // the path matrix, compressed by path and by layer; an entry is what some j < NLAYIN[p] touched, padding is never read
-    std::vector<double> Sm((size_t)L * P, 0.0);
-    std::vector<char> hit((size_t)L * P, 0);
-    for (int p = 0; p < P; ++p) {
-        if (NLAYIN[p] < 0 || NLAYIN[p] > LIMAX) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: NLAYIN outside 0 .. LIMAX");
-        for (int j = 0; j < NLAYIN[p]; ++j) {
-            const int l = LAYINC[(size_t)j * P + p];
-            if (l < 0 || l >= L) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: LAYINC outside 0 .. L - 1");
-            Sm[(size_t)l * P + p] += SCALE[(size_t)j * P + p];
-            hit[(size_t)l * P + p] = 1;
-        }
-    }
-    size_t nnz = 0;
-    for (char h : hit) nnz += h;
-    std::vector<int32_t> hi((size_t)P + 1 + L + 1 + 2 * nnz);
-    std::vector<double> hd((size_t)P + 2 * nnz);
-    int32_t *col_ptr = hi.data(), *col_lay = col_ptr + P + 1, *row_ptr = col_lay + nnz, *row_path = row_ptr + L + 1;
-    double *col_val = hd.data() + P, *row_val = col_val + nnz;
-    std::copy(path_weight, path_weight + P, hd.data());
-    int32_t n = 0;
-    for (int p = 0; p < P; ++p) {
-        col_ptr[p] = n;
-        for (int l = 0; l < L; ++l)
-            if (hit[(size_t)l * P + p]) { col_lay[n] = l; col_val[n++] = Sm[(size_t)l * P + p]; }
-    }
-    col_ptr[P] = n;
-    n = 0;
-    for (int l = 0; l < L; ++l) {
-        row_ptr[l] = n;
-        for (int p = 0; p < P; ++p)
-            if (hit[(size_t)l * P + p]) { row_path[n] = p; row_val[n++] = Sm[(size_t)l * P + p]; }
-    }
-    row_ptr[L] = n;
-
-    // everything that can refuse the arguments comes before the first copy is queued
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, NP1 = S + 1;
-    const size_t D = sizeof(double);
-    TransitParams q;
-    memset(&q, 0, sizeof q);
-    q.gas_mask = ctx->is_lbl ? 0xFFFFFFFFu : ctx->grad_gas_mask;
-    int rc;
-    if ((rc = fill_slot_of_param(ctx, igas_map, NVMR, NPAR, q.gas_mask, q.slot_of_param))) return rc;
-    if (ctx->dcont_gas_L && ctx->dcont_gas_L != L) {
-        ctx->dcont_gas_L = 0;
-        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_transit: the pending shared gas gradient (ansfm_set_shared_gas_gradient) is for a "
-                                "different number of layers");
-    }
-    HIPCHK(hipSetDevice(ctx->device));
-    ctx->dspec_dims[0] = 0;
-    ctx->transit_recorded = 0;
-    // hd / hi are staged from this frame: from here on no return before the stream has been synchronised
-    auto on_device = [&]() -> int {
-        Stager st{ctx};
-        const double *press = st.up(lay_press_pa, L), *temp = st.up(lay_temp, L), *am = st.up(amount, (size_t)L * S),
-                     *cont = st.up(taucont, (size_t)L * W), *dcont = st.up(dtaucon, (size_t)L * W * NPAR),
-                     *dd = st.up(hd.data(), hd.size());
-        const int32_t *di = st.up(hi.data(), hi.size());
-        if (st.rc) return st.rc;
-        int rc2;
-        const double *cont_t = nullptr, *dcont_t = nullptr;
-        if ((rc2 = grad_gas_stage(ctx, 1, L, press, temp, am, cont, dcont, NPAR, &cont_t, &dcont_t))) return rc2;
-        // scratch beyond the gas stage: A [L][G][Wpad], exp(-tau_path) [P][G][Wpad], AREA [W], T [W][P]
-        const size_t n_sens = (size_t)L * G * Wpad, n_tpart = (size_t)P * G * Wpad, n_out = (size_t)W * (1 + P);
-        ctx->transit_scratch_bytes = (n_sens + n_tpart + n_out) * D;
-        HIPCHK(ctx->transit_ws.reserve(ctx->transit_scratch_bytes));
-        HIPCHK(ctx->dspec_ref.reserve((size_t)W * NPAR * L * D));
-        q.tau = ctx->tau.as<double>();
-        q.cont = cont_t;
-        q.delg = ctx->d_delg.as<double>();
-        q.weight = dd; q.col_val = dd + P; q.row_val = dd + P + nnz;
-        q.col_ptr = di; q.col_lay = di + P + 1; q.row_ptr = di + P + 1 + nnz; q.row_path = di + P + 1 + nnz + L + 1;
-        q.sens = ctx->transit_ws.as<double>();
-        q.tpart = q.sens + n_sens;
-        q.area = q.tpart + n_tpart;
-        q.trans = q.area + W;
-        q.darea = ctx->dspec_ref.as<double>();
-        q.dk = ctx->dkbuf.as<double>();
-        q.dcont = dcont_t;
-        if (ctx->dcont_gas_L) {
-            q.dcont_gas = ctx->dcont_gas.as<double>();
-            ctx->dcont_gas_L = 0;               // one call only
-        }
-        q.W = W; q.Wpad = Wpad; q.G = G; q.L = L; q.P = P;
-        q.NPAR = NPAR; q.NVMR = NVMR; q.NP1 = NP1;
-        HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-        if ((rc2 = launch_transit(ctx, q))) return rc2;
-        HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-        ctx->overlap_launches = 1; ctx->rt_launches = 1;
-        ctx->last_n = 1; ctx->last_L = L;
-        HIPCHK(hipMemcpyAsync(AREA, q.area, (size_t)W * D, hipMemcpyDeviceToHost, ctx->stream));
-        if (TRANS) HIPCHK(hipMemcpyAsync(TRANS, q.trans, (size_t)W * P * D, hipMemcpyDeviceToHost, ctx->stream));
-        if (dAREA) HIPCHK(hipMemcpyAsync(dAREA, q.darea, (size_t)W * NPAR * L * D, hipMemcpyDeviceToHost, ctx->stream));
-        return check_unsorted(ctx);             // synchronises
-    };
-    if ((rc = on_device())) {
-        (void)hipStreamSynchronize(ctx->stream);   // whatever was queued from hd / hi has run before they go
-        return rc;
-    }
-    ctx->dspec_dims[0] = W; ctx->dspec_dims[1] = NPAR; ctx->dspec_dims[2] = L; ctx->dspec_dims[3] = 1;
-    ctx->transit_recorded = 1;
-    return ANSFM_OK;
+    c.EMTEMP = SCALE; c.TSURF = tsurf.data(); c.xfac = xfac; c.SPECOUT = SPECOUT; c.dSPECOUT = dSPECOUT; c.dTSURF = dts.data();
+    c.rt_mode = 1;
+    return cirsradg_ck_thermal_host(ctx, c);
 }
 
 int ansfm_k_overlapg(ansfm_ctx *ctx, int W, int G, int L, int S, const double *del_g, const double *k,

@@ -2,7 +2,7 @@
 // host pointers and the declarations of the host helpers that one unit defines and another calls.  No kernel lives here, and
 // no kernel header is included: a header that defines kernels belongs to exactly one .hip.
 //   ansfm_api.hip      lifecycle, tables, the gas-opacity stage, the entry points of thermal / transmission / single-scattering
-//                      RT and its gradients
+//                      RT and its gradients (their arguments travel as one record, RtCall)
 //   ansfm_overlap.hip  forward merge of the correlated-k path (64-bit keys); ansfm_merge32.hip: the 32-bit-key merge
 //   ansfm_overlapg.hip gradient merge
 //   ansfm_rt.hip       thermal / transmission / single-scattering RT kernels and their gradients
@@ -11,7 +11,8 @@
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
-//   ansfm_transit.hip  primary-transit depth with gradients, collapsed over paths on the device
+//   ansfm_transit.hip  primary-transit depth with gradients, collapsed over paths on the device: the entry point, its
+//                      path-matrix build and its kernels
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -191,6 +192,13 @@ struct DedupRows {
 };
 int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
                const double *ray_totam, const double *ray_f4, DedupRows *out);
+// ansfm_api.hip, what the gradient RT entries and the transit entry (ansfm_transit.hip) share (described where they are
+// defined): the gas stage of a gradient call, the merge slot behind every parameter, the end of a call without a generic rerun
+int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
+                   const double *taucont, const double *dtaucon, int NPAR, const double **cont_t, const double **dcont_t);
+int fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int NVMR, int NPAR, unsigned gas_mask,
+                       signed char *slot_of_param);
+int check_unsorted(ansfm_ctx *ctx);
 // ansfm_lbl.hip: k_lblrt_tau for gas_tau, on the n models from m0 of the state of ansfm_lblrt_set_state
 void launch_lblrt_tau(ansfm_ctx *ctx, int n, int L, int m0, const double *amount, double *dk);
 // ansfm_ops.hip: k_tau_rayleigh_rows for the thermal branch, into ctx->cont_t [rows][Wpad]; slot_rows: the de-duplication's work
@@ -239,9 +247,16 @@ void launch_thermal_emission_g_seam(ansfm_ctx *ctx, int ISPACE, int W, int G, in
                                     const double *emis, double *o_spec, double *o_dspec, double *o_dts);
 void launch_dspec_to_ref(ansfm_ctx *ctx, const double *src, double *dst, int W, int Wpad, int NPAR, int LIMAX, int P,
                          const int32_t *nlayin);
-// ansfm_transit.hip: k_transit_sens + k_transit_grad of one model; ANSFM_ERR_UNSUPPORTED above kTransitMaxRows layers or paths
-struct TransitParams;
-int launch_transit(ansfm_ctx *ctx, const TransitParams &q);
+
+// What every CIRSrad entry point leaves behind after its last launch, for ansfm_last_kernel_ms, ansfm_get_taugas and
+// ansfm_last_layer_rows: one merge and one RT launch between the events, of n_models x L layers
+inline void call_recorded(ansfm_ctx *ctx, int n_models, int L)
+{
+    ctx->overlap_launches = 1;
+    ctx->rt_launches = 1;
+    ctx->overlap_ms = -1.0;  // resolved lazily in ansfm_last_kernel_ms
+    ctx->last_n = n_models; ctx->last_L = L;
+}
 
 /* ---- host -> device staging of the host-pointer entry points --------------------------------------------------------- */
 inline int h2d(ansfm_ctx *ctx, DevBuf &b, const void *src, size_t bytes, const void **out)

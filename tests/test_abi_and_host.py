@@ -27,6 +27,42 @@ def test_library_exports_every_declared_symbol():
     assert lib.ansfm_abi_version() == 1
 
 
+def test_ctypes_prototypes_are_derived_from_the_header():
+    """_lib.PROTOTYPES is include/ansfm.h read by _lib.prototypes: every declared name and no other, as many argtypes as the
+    prototype has parameters (counted here with a regular expression of the test's own), a few signatures written out by
+    hand, and an error at load for a parameter type the parser does not know."""
+    import ctypes as C
+    from archnemesis_dist_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "ansfm.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = sorted(set(re.findall(r"\b(ansfm_[a-z0-9_]+)\s*\(", hdr)))
+    assert sorted(_lib.PROTOTYPES) == declared and _lib.EXPORTS == list(_lib.PROTOTYPES)
+    for name, (_, argtypes) in _lib.PROTOTYPES.items():
+        (params,) = re.findall(r"\b%s\s*\(([^)]*)\)" % name, hdr)
+        n = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert len(argtypes) == n, name
+    vp, ci, cd = C.c_void_p, C.c_int, C.c_double
+    P = _lib.PROTOTYPES
+    ss = P["ansfm_cirsrad_ck_singlescatt"][1]
+    assert len(ss) == 23 and ss[15] is cd and [i for i, t in enumerate(ss) if t is cd] == [15]       # TSURF by value
+    assert P["ansfm_ktable_file_header"][1] == [C.c_char_p] + [vp] * 8
+    assert P["ansfm_set_gradient_gases"] == (ci, [vp, C.c_uint])
+    assert P["ansfm_lblrt_set_scratch_bytes"] == (ci, [vp, C.c_int64])
+    assert P["ansfm_destroy"] == (None, [vp])
+    assert P["ansfm_last_error"] == (C.c_char_p, [vp])
+    assert P["ansfm_upload_ktable_files"][1] == [vp, ci, vp, cd, cd]                                   # const char *const *paths
+    assert P["ansfm_abi_version"] == (ci, [])
+    lib = _lib.load()
+    assert lib.ansfm_destroy.restype is None and lib.ansfm_last_error.restype is C.c_char_p
+    assert list(lib.ansfm_cirsrad_ck_singlescatt.argtypes) == ss
+    assert _lib.prototypes("int ansfm_x(ansfm_ctx *ctx, int n);\nvoid ansfm_y(void);") == {"ansfm_x": (ci, [vp, ci]),
+                                                                                           "ansfm_y": (None, [])}
+    with pytest.raises(_lib.AnsfmError, match="ansfm_new_entry"):
+        _lib.prototypes("int ansfm_new_entry(ansfm_ctx *ctx, float x);")
+    with pytest.raises(_lib.AnsfmError, match="ansfm_new_entry"):
+        _lib.prototypes("float ansfm_new_entry(ansfm_ctx *ctx);")
+
+
 def test_every_kernel_header_has_one_translation_unit(tmp_path, monkeypatch):
     """A header that defines a __global__ function is compiled into exactly one object: a second one would collide at link
     (plain kernels) or instantiate and ship the same template kernels twice.  Source text only."""

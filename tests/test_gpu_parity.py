@@ -1998,3 +1998,157 @@ def test_closing_an_engine_returns_its_device_memory():
         torch.cuda.synchronize(0)
         drops.append((free0 - torch.cuda.mem_get_info(0)[0]) / 2**20)
     assert max(drops) < 256.0, f"device free memory lost after each round (MiB): {drops}"
+
+
+def test_cirsrad_entry_points_refuse_bad_arguments():
+    """The thermal, transmission, gradient, transit and single-scattering entry points called through the C-ABI with one broken
+    argument each: the return code and the ansfm_last_error text of every refusal.  On the table of smoke(); nothing but the
+    upload and the gas stage of the one call that is refused after it (the pending shared gas gradient) runs on the device."""
+    import ctypes as C
+    import torch
+    import archnemesis_dist_amd as pkg
+    from archnemesis_dist_amd import synthetic as syn
+    W, G, S, L, NP, NT = 96, 20, 4, 12, 6, 5
+    NVMR, NPAR, P, LIMAX = 4, 7, 1, L
+    atm = syn.synth_atmosphere(L, S, seed=2)
+    lp, lt, am = atm["lay_press_pa"], atm["lay_temp"], atm["amount"]
+    NLAYIN, LAYINC, SCALE = syn.nadir_path(L, 10.0)
+    SC = np.ascontiguousarray(SCALE[None]); ET = np.ascontiguousarray(lt[:, LAYINC[:, 0]][:, :, None])
+    cont = syn.synth_continuum(W, L); sca = 0.5 * cont; phase = np.full((1, P, W, L), 0.1)
+    ts = np.array([-1.0]); ig = np.array([2, 0, 3, 1], dtype=np.int32); weight = np.array([1.0e10])
+    flux = np.ones(W); ang = np.zeros(P)
+    spec = np.empty((1, W, P)); dspec = np.empty((1, W, NPAR, LIMAX, P)); dts = np.empty((1, W, P))
+    dev = {k: torch.as_tensor(v).cuda() for k, v in dict(lp=lp, lt=lt, am=am, NLAYIN=NLAYIN, LAYINC=LAYINC, SC=SC, ET=ET, ts=ts,
+                                                          spec=spec, dspec=dspec, dts=dts, totam=np.ones((1, L))).items()}
+
+    def p(a):
+        if a is None:
+            return None
+        return C.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
+
+    eng = pkg.AnsfmEngine(0)
+    lib, ctx = eng._lib, eng._ctx
+
+    # every entry point with sound arguments by default; a keyword replaces one of them
+    def thermal(ISPACE=0, n=1, out=spec):
+        return lib.ansfm_cirsrad_ck_thermal(ctx, ISPACE, n, L, p(lp), p(lt), p(am), p(cont), P, LIMAX, p(NLAYIN), p(LAYINC), p(SC),
+                                            p(ET), p(ts), None, None, None, None, None, None, p(out))
+
+    def thermal_dev(ISPACE=0, n=1, out=dev["spec"]):
+        d = dev
+        return lib.ansfm_cirsrad_ck_thermal_dev(ctx, ISPACE, n, L, p(d["lp"]), p(d["lt"]), p(d["am"]), None, P, LIMAX, p(d["NLAYIN"]),
+                                                p(d["LAYINC"]), p(d["SC"]), p(d["ET"]), p(d["ts"]), None, None, None, None, None, None,
+                                                p(out))
+
+    def thermal_ray_dev(ISPACE=0, n=1, out=dev["spec"]):
+        d = dev
+        return lib.ansfm_cirsrad_ck_thermal_ray_dev(ctx, ISPACE, n, L, p(d["lp"]), p(d["lt"]), p(d["am"]), 1, p(d["totam"]), None, P,
+                                                    LIMAX, p(d["NLAYIN"]), p(d["LAYINC"]), p(d["SC"]), p(d["ET"]), p(d["ts"]), None, None,
+                                                    None, None, None, None, p(out))
+
+    def transmission(n=1, out=spec):
+        return lib.ansfm_cirsrad_ck_transmission(ctx, n, L, p(lp), p(lt), p(am), p(cont), P, LIMAX, p(NLAYIN), p(LAYINC), p(SC), None,
+                                                 p(out))
+
+    def thermalg(ISPACE=0, n=1, out=spec, nvmr=NVMR, npar=NPAR):
+        return lib.ansfm_cirsradg_ck_thermal(ctx, ISPACE, n, L, p(lp), p(lt), p(am), p(cont), None, nvmr, npar, p(ig), P, LIMAX,
+                                             p(NLAYIN), p(LAYINC), p(SC), p(ET), p(ts), None, None, p(out), p(dspec), p(dts))
+
+    def thermalg_dev(ISPACE=0, n=1, out=dev["spec"], nvmr=NVMR, npar=NPAR):
+        d = dev
+        return lib.ansfm_cirsradg_ck_thermal_dev(ctx, ISPACE, n, L, p(d["lp"]), p(d["lt"]), p(d["am"]), None, None, nvmr, npar, p(ig), P,
+                                                 LIMAX, p(d["NLAYIN"]), p(d["LAYINC"]), p(d["SC"]), p(d["ET"]), p(d["ts"]), None, None,
+                                                 p(out), p(d["dspec"]), p(d["dts"]))
+
+    def transmissiong(n=1, out=spec, nvmr=NVMR, npar=NPAR):
+        return lib.ansfm_cirsradg_ck_transmission(ctx, n, L, p(lp), p(lt), p(am), p(cont), None, nvmr, npar, p(ig), P, LIMAX, p(NLAYIN),
+                                                  p(LAYINC), p(SC), None, p(out), p(dspec))
+
+    def transit(out=spec, nvmr=NVMR, npar=NPAR, layers=L):
+        big = np.ones(S * layers)                      # stands for every layer array when `layers` is not L
+        a = (lp, lt, am) if layers == L else (big, big, big)
+        return lib.ansfm_cirsradg_ck_transit(ctx, layers, p(a[0]), p(a[1]), p(a[2]), None, None, nvmr, npar, p(ig), P, LIMAX, p(NLAYIN),
+                                             p(LAYINC), p(SC), p(weight), p(out), None, None)
+
+    def singlescatt(ISPACE=0, out=spec, tsurf=-1.0, emis=None):
+        return lib.ansfm_cirsrad_ck_singlescatt(ctx, ISPACE, L, p(lp), p(lt), p(am), p(cont), p(sca), p(phase), P, LIMAX, p(NLAYIN),
+                                                p(LAYINC), p(SC), p(ET), tsurf, p(emis), p(flux), p(flux), p(ang), p(ang), None, p(out))
+
+    def singlescatt_batch(ISPACE=0, n=1, out=spec, tsurf=ts, emis=None):
+        return lib.ansfm_cirsrad_ck_singlescatt_batch(ctx, ISPACE, n, L, p(lp), p(lt), p(am), p(cont), p(sca), p(phase), P, LIMAX,
+                                                      p(NLAYIN), p(LAYINC), p(SC), p(ET), p(tsurf), p(emis), p(flux), p(flux), p(ang),
+                                                      p(ang), None, p(out))
+
+    INVALID, NOTABLE, UNSUPPORTED = 1, 3, 5
+    CIRS, CIRSG_HOST, CIRSG_DEV = "cirsrad: bad argument", ("cirsradg: bad argument (dSPECOUT may be NULL for a single model: the "
+                                                            "gradients then stay on the device for ansfm_map2pro)"), \
+        "cirsradg: bad argument (NPAR <= 256)"
+    TRANSIT = "cirsradg_ck_transit: bad argument (NPAR <= 256)"
+    SS, SSB = "cirsrad_ck_singlescatt", "cirsrad_ck_singlescatt_batch"
+    PENDING = "cirsradg: the pending shared gas gradient (ansfm_set_shared_gas_gradient) is for one model with a different number of layers"
+    seen = []
+
+    def refused(what, rc, code, text):
+        got = (rc, lib.ansfm_last_error(ctx).decode())
+        seen.append((what, got))
+        print(what, got)
+        assert got == (code, text), what
+
+    try:
+        # ---- no table uploaded
+        for what, fn, text in [("thermal", thermal, "cirsrad"), ("thermal_dev", thermal_dev, "cirsrad"),
+                               ("thermal_ray_dev", thermal_ray_dev, "cirsrad"), ("transmission", transmission, "cirsrad"),
+                               ("thermalg", thermalg, "cirsradg"), ("thermalg_dev", thermalg_dev, "cirsradg"),
+                               ("transmissiong", transmissiong, "cirsradg"), ("transit", transit, "cirsradg_ck_transit"),
+                               ("singlescatt", singlescatt, SS), ("singlescatt_batch", singlescatt_batch, SSB)]:
+            refused("no table: " + what, fn(), NOTABLE, text + ": upload a k-table first")
+        _, delg = syn.gauss_legendre_01(G, as_float32=True)
+        PRESS, TEMP, K = syn.synth_ktable(W, G, NP, NT, S, seed=1)
+        eng.upload_ktable(K, PRESS, TEMP, 300.0 + np.arange(W) * 1.0, delg)
+        # ---- n_models = 0
+        for what, fn, text in [("thermal", thermal, CIRS), ("thermal_dev", thermal_dev, CIRS), ("thermal_ray_dev", thermal_ray_dev, CIRS),
+                               ("transmission", transmission, "cirsrad_ck_transmission: bad argument"), ("thermalg", thermalg, CIRSG_HOST),
+                               ("thermalg_dev", thermalg_dev, CIRSG_DEV),
+                               ("transmissiong", transmissiong, "cirsradg_ck_transmission: bad argument"),
+                               ("singlescatt_batch", singlescatt_batch, SSB + ": bad argument")]:
+            refused("n_models = 0: " + what, fn(n=0), INVALID, text)
+        # ---- null SPECOUT (AREA of the transit entry)
+        for what, fn, text in [("thermal", thermal, CIRS), ("thermal_dev", thermal_dev, CIRS), ("thermal_ray_dev", thermal_ray_dev, CIRS),
+                               ("transmission", transmission, CIRS), ("thermalg", thermalg, CIRSG_HOST), ("thermalg_dev", thermalg_dev, CIRSG_DEV),
+                               ("transmissiong", transmissiong, "cirsradg_ck_transmission: bad argument"), ("transit", transit, TRANSIT),
+                               ("singlescatt", singlescatt, SS + ": bad argument"), ("singlescatt_batch", singlescatt_batch, SSB + ": bad argument")]:
+            refused("null SPECOUT: " + what, fn(out=None), INVALID, text)
+        # ---- ISPACE = 2
+        for what, fn, text in [("thermal", thermal, CIRS), ("thermal_dev", thermal_dev, CIRS), ("thermal_ray_dev", thermal_ray_dev, CIRS),
+                               ("thermalg", thermalg, CIRSG_DEV), ("thermalg_dev", thermalg_dev, CIRSG_DEV),
+                               ("singlescatt", singlescatt, SS + ": bad argument"), ("singlescatt_batch", singlescatt_batch, SSB + ": bad argument")]:
+            refused("ISPACE = 2: " + what, fn(ISPACE=2), INVALID, text)
+        # ---- NPAR = 0, NVMR = NPAR
+        for what, fn, text0, text1 in [("thermalg", thermalg, CIRSG_HOST, CIRSG_DEV), ("thermalg_dev", thermalg_dev, CIRSG_DEV, CIRSG_DEV),
+                                       ("transmissiong", transmissiong, CIRSG_HOST, CIRSG_DEV), ("transit", transit, TRANSIT, TRANSIT)]:
+            refused("NPAR = 0: " + what, fn(nvmr=0, npar=0), INVALID, text0)
+            refused("NVMR = NPAR: " + what, fn(nvmr=NPAR), INVALID, text1)
+        # ---- more layers than the transit kernels take
+        refused("L = 321: transit", transit(layers=321), UNSUPPORTED,
+                "cirsradg_ck_transit: at most 320 layers and 320 paths (the 160 KiB LDS tile of k_transit_sens)")
+        # ---- a pending shared gas gradient for another number of layers
+        shared = np.full((W, L - 1), 1.0e-3)
+        for what, fn, text in [("thermalg", thermalg, PENDING), ("transmissiong", transmissiong, PENDING),
+                               ("transit", transit, "cirsradg_ck_transit: the pending shared gas gradient "
+                                                    "(ansfm_set_shared_gas_gradient) is for a different number of layers")]:
+            assert lib.ansfm_set_shared_gas_gradient(ctx, L - 1, p(shared)) == 0
+            refused("pending shared gas gradient: " + what, fn(), INVALID, text)
+        # ---- a surface without its emissivity in the single-scattering entries
+        refused("TSURF > 0, null EMISSIVITY: singlescatt", singlescatt(tsurf=150.0), INVALID, SS + ": bad argument")
+        refused("TSURF > 0, null EMISSIVITY: singlescatt_batch", singlescatt_batch(tsurf=np.array([150.0])), INVALID, SSB + ": bad argument")
+        tau = np.full((W, G, L), 0.1); one = np.ones(W)
+        rc = lib.ansfm_singlescatt_plane_spectrum(ctx, 0, W, G, L, p(one), p(tau), p(lt), p(tau), p(cont), 150.0, None, p(one), p(one), 0.0,
+                                                  0.0, p(np.empty((W, G))))
+        refused("TSURF > 0, null EMISSIVITY: singlescatt_plane_spectrum", rc, INVALID, "singlescatt_plane_spectrum: bad argument")
+        rc = lib.ansfm_thermal_emission(ctx, 2, W, G, L, p(one), p(tau), None, p(lt), p(lp), -1.0, None, None, None, 0.0, 0.0,
+                                        p(np.empty((W, G))))
+        refused("ISPACE = 2: thermal_emission", rc, INVALID, "thermal_emission: bad argument")
+        eng.synchronize()                              # the stream is sound after all of it
+        assert len(seen) == 51
+    finally:
+        eng.close()
