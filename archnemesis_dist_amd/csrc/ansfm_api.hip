@@ -384,6 +384,14 @@ int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed)
     return ANSFM_OK;
 }
 
+int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *trims)
+{
+    if (!ctx || !waves_per_block || !trims) return ANSFM_ERR_INVALID;
+    *waves_per_block = ctx->merge_block_waves;
+    *trims = ctx->merge_trims;
+    return ANSFM_OK;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* launches                                                                                    */
 /* ------------------------------------------------------------------------------------------ */

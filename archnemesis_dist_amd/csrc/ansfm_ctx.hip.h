@@ -24,6 +24,7 @@
 #include <initializer_list>
 #include <memory>
 #include <string>
+#include <map>
 #include <vector>
 
 #pragma GCC visibility push(default)
@@ -85,6 +86,8 @@ struct ansfm_ctx {
     DevBuf dcont_gas;                       // ansfm_set_shared_gas_gradient: [L][Wpad], consumed by the next cirsradg call
     int dcont_gas_L = 0;                    // 0: none pending
     unsigned grad_gas_mask = 0xFFFFFFFFu;   // ansfm_set_gradient_gases: gases whose amount gradients cirsradg computes
+    std::map<const void *, size_t> merge_lds_allowed;   // dynamic LDS each merge kernel has been allowed on this device
+    int merge_block_waves = 0, merge_trims = 0;   // the last forward merge launch (ansfm_last_merge_launch)
     int merge_keys = 64;     // 32: run the forward merge on k_ck_overlap32's float32 keys (ansfm_set_merge_keys)
     bool have_table = false;
     int grid_f32 = 0, delg_f32 = 0;

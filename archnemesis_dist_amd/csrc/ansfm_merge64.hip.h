@@ -29,6 +29,13 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 //   kWalkOneOffset  merge_walk_nodiv keeps one running offset instead of two
 //   kMergeUnroll4   four steps per trip of the merge loop instead of two
 //   kLoadNoBox      tables without a boxed entry are interpolated without the box tests (interp_k_nobox)
+// and of the three that only the division-free fast path (SORTED, NODIV) of the forward kernel takes, as the bits of its
+// template parameter OPT (0 = the code before them, which every other user of merge_fetch / merge_step keeps):
+//   kWeightTable    the pair weight is one ds_read_b64 of a product table WT[(col << 5) | row] that the waves of one block
+//                   per CU share (kOptTable; the launch is one block of several waves per CU instead of one-wave blocks).
+//                   float32 weights only: with float64 weights the walk's gd + DG[i] * DG[j] is compiled as one fma
+//   kKeyBfi         the popped row's next key is the winner's low word + 32 inserted under the 11-bit mask (kOptBfi)
+//   kLateBinWait    the boundary after next is read at the top of every step, the crossing branch only moves it (kOptLate)
 #ifndef ANSFM_MERGE_PEEL
 #define ANSFM_MERGE_PEEL 1
 #endif
@@ -41,14 +48,31 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 #ifndef ANSFM_LOAD_NOBOX
 #define ANSFM_LOAD_NOBOX 1
 #endif
+#ifndef ANSFM_WEIGHT_TABLE
+#define ANSFM_WEIGHT_TABLE 1
+#endif
+#ifndef ANSFM_KEY_BFI
+#define ANSFM_KEY_BFI 1
+#endif
+#ifndef ANSFM_LATE_BIN_WAIT
+#define ANSFM_LATE_BIN_WAIT 0       // measured slower than the read inside the branch: kept, switched off
+#endif
 constexpr bool kMergePeel = ANSFM_MERGE_PEEL != 0, kWalkOneOffset = ANSFM_WALK_ONE_OFFSET != 0, kMergeUnroll4 = ANSFM_MERGE_UNROLL4 != 0,
-               kLoadNoBox = ANSFM_LOAD_NOBOX != 0;
+               kLoadNoBox = ANSFM_LOAD_NOBOX != 0, kWeightTable = ANSFM_WEIGHT_TABLE != 0, kKeyBfi = ANSFM_KEY_BFI != 0,
+               kLateBinWait = ANSFM_LATE_BIN_WAIT != 0;
+constexpr int kOptTable = 1, kOptBfi = 2, kOptLate = 4;
+constexpr int kMergeOpt = (kWeightTable ? kOptTable : 0) | (kKeyBfi ? kOptBfi : 0) | (kLateBinWait ? kOptLate : 0);
+// The product table follows the float32 copy of DG; (col << 5) | row with col <= G (an exhausted row's sentinel key names
+// column G; its entry is read and never used), so (G + 1) * 32 doubles.  The per-wave rows come after it.
+constexpr unsigned kLdsWT = kLdsA;
+constexpr int kMaxBlockWaves = 8;
+__host__ __device__ constexpr unsigned weight_table_bytes(int G) { return (unsigned)(G + 1) * 32u * 8u; }
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 constexpr unsigned kRecRow = 64u * 16u, kRecBin = 2u * kRecRow;
 
 struct MergeElem {
     double ai, bc, bn, w;
-    int ci, np;
+    int ci, np;         // np = column + 1; with kOptBfi the winner key's low word instead (the fetch decodes ci and the column)
 };
 
 // Weight of element (i, j) = del_g[i] * del_g[j].  DELG float32 (W32): NumPy forms the float32 product, which is one
@@ -66,20 +90,32 @@ __device__ __forceinline__ double pair_weight(const double *DG, int i, int j)
 
 // SORTED = false (generic path): the rows / columns were sorted per lane beforehand; PA / PB give the original
 // g-ordinate of each sorted position, which is the one whose weight applies.
-template <bool W32, bool SORTED = true>
+template <bool W32, bool SORTED = true, int OPT = 0>
 __device__ __forceinline__ void merge_fetch(double key, int lane, const double *A, const double *B,
                                             const double *DG, MergeElem &e,
                                             const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
 {
+    static_assert(OPT == 0 || SORTED, "the trims of the fast path");
     const unsigned kb = (unsigned)__double_as_longlong(key);
-    const int ci = kb & 31, cp = (kb >> 5) & 63;
+    int ci, cp;
+    if constexpr (OPT != 0) {
+        // the two fields as one instruction each, so that every row address is one v_lshl_add on top: with the low word kept
+        // in a register (kw) the compiler otherwise forms (kw << k) & mask + base, three instructions per address
+        asm("v_and_b32 %0, 31, %1" : "=v"(ci) : "v"(kb));
+        asm("v_bfe_u32 %0, %1, 5, 6" : "=v"(cp) : "v"(kb));
+    } else {
+        ci = kb & 31; cp = (kb >> 5) & 63;
+    }
     e.ci = ci;
-    e.np = cp + 1;
+    if constexpr ((OPT & kOptBfi) != 0) e.np = (int)kb;
+    else e.np = cp + 1;
+    if constexpr ((OPT & kOptTable) != 0) e.w = lds_ld(kLdsWT + ((kb & 0x7FFu) << 3));
     e.ai = A[ci * kWave + lane];
     const unsigned ab = lds_addr(B + lane) + ((unsigned)cp << 9);
     e.bc = lds_ld(ab);
     e.bn = lds_ld(ab + 512);                    // B[G] = sentinel column: an exhausted row re-enters as "huge"
-    if constexpr (SORTED) e.w = pair_weight<W32>(DG, ci, cp);
+    if constexpr ((OPT & kOptTable) != 0) ;
+    else if constexpr (SORTED) e.w = pair_weight<W32>(DG, ci, cp);
     else e.w = pair_weight<W32>(DG, PA[ci * kWave + lane], PB[cp * kWave + lane]);
 }
 
@@ -93,6 +129,15 @@ __device__ __forceinline__ double pack_key11(double v, int row, int col)
     b = (b & ~0x7FFULL) | (unsigned long long)((col << 5) | row);
     return __longlong_as_double((long long)b);
 }
+// The next key of a popped row from the winner's low word kw = ... | col << 5 | row: col + 1 is kw + 32, and the 11 bits go
+// into the value's low word under the mask (v_add_u32 + v_bfi_b32).  col <= 32, so the add does not leave the 11 bits for
+// any key that is consumed; the same double as pack_key11(v, row, col + 1).
+__device__ __forceinline__ double pack_key11_next(double v, unsigned kw)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = ((kw + 32u) & 0x7FFu) | ((unsigned)b & ~0x7FFu);
+    return __longlong_as_double((long long)((b & 0xFFFFFFFF00000000ULL) | lo));
+}
 
 // rank() walk state of one lane (ForwardModel_0.py:6155-6170).  Bin boundaries are recorded and resolved
 // after the loop: frac needs a division, and the next bin's (1-frac) share is added there too -- the same
@@ -103,18 +148,25 @@ struct WalkState {
     unsigned gaddr;     // LDS byte address of GORD[ig + 1]
     unsigned rbase;     // merge_walk_nodiv: lane * 8 - (address of GORD[1] << 6), see there (roff is unused in that walk)
 };
+// LATE (kOptLate, merge_walk_nodiv): gaddr runs one boundary ahead, at GORD[ig + 2], the address the step reads.
+template <bool LATE = false>
 __device__ __forceinline__ WalkState walk_begin(const double *GORD, int lane)
 {
     WalkState ws;
     ws.gd = 0.0; ws.kacc = 0.0; ws.sum1 = 0.0;
     ws.gaddr = lds_addr(GORD + 1);
     ws.gnext = lds_ld(ws.gaddr);
+    if constexpr (LATE) ws.gaddr += 8u;
     ws.roff = (unsigned)lane * 16u;
     ws.rbase = (unsigned)lane * 8u - (ws.gaddr << 6);
     return ws;
 }
 // number of bins closed so far
-__device__ __forceinline__ int walk_bins(const WalkState &ws, const double *GORD) { return (int)((ws.gaddr - lds_addr(GORD + 1)) >> 3); }
+template <bool LATE = false>
+__device__ __forceinline__ int walk_bins(const WalkState &ws, const double *GORD)
+{
+    return (int)((ws.gaddr - lds_addr(GORD + (LATE ? 2 : 1))) >> 3);
+}
 
 template <bool REC_CODE>
 __device__ __forceinline__ bool merge_walk(const MergeElem &e, WalkState &ws, double *rec, const double *GORD,
@@ -151,7 +203,14 @@ __device__ __forceinline__ bool merge_walk(const MergeElem &e, WalkState &ws, do
 // in the last bits only (the reference itself forms frac from a difference of cumulative sums, good to ~1e-12).
 // Precondition (checked at launch): the first element of the merged order does not close a bin -- rank()'s python
 // gdist[-1] wrap, which only the recorded form reproduces.
-__device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &ws, double *rec)
+// LATE (kOptLate): gnn = the boundary after next, GORD[ig + 2], read at the top of the step -- before the next element's
+// operands are fetched, so the branch waits for it without waiting for them and leaves no LDS read of its own behind: the
+// two sides of the branch join with the same reads outstanding and the next step starts waiting for nothing but its own
+// operands, issued a list pass earlier.  gaddr is the address that read uses (GORD[ig + 2], walk_begin<true>) and is stepped
+// in place, so an element that closes a bin right after another sees the right boundary: its step's read is issued at
+// gaddr as the branch of the step before left it.  Past the NaN the read returns what follows GORD and is never moved into gnext.
+template <bool LATE = false>
+__device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &ws, double *rec, double gnn = 0.0)
 {
     const double cv = e.ai + e.bc;
     const double w = e.w;
@@ -159,7 +218,12 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
     double kn = fma(cv, w, ws.kacc);
     const bool cross = (gdn >= ws.gnext);       // ordered: GORD[G+1] is NaN
     if (cross) {
-        if constexpr (kWalkOneOffset) {
+        if constexpr (LATE) {
+            gst<double>(rec, (ws.gaddr << 6) + ws.rbase, fma(ws.gnext - ws.gd, cv, ws.kacc));
+            kn = (gdn - ws.gnext) * cv;
+            ws.gnext = gnn;
+            ws.gaddr += 8u;
+        } else if constexpr (kWalkOneOffset) {
             // The closed bin's slot, ig * 512 + lane * 8, is formed from the one running offset the walk keeps (gaddr, +8 per
             // bin; 512 = 8 << 6): one shift-add here, where a second running offset cost an add AND, as a second value that
             // lives across the branch and the e0 / e1 ping-pong, a register copy at the end of the branch body.  The
@@ -188,25 +252,28 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
 // (compile time, >= G; unused entries hold "huge" keys).
 // Returns the consumed element's (row, column) and whether it closed a bin, as 16 bits: the gradient kernel
 // records them and replays the sorted order for the gradient rows.
-template <int NR, bool W32, bool REC_CODE = false, bool SORTED = true, bool NODIV = false, int NP = NR>
+template <int NR, bool W32, bool REC_CODE = false, bool SORTED = true, bool NODIV = false, int NP = NR, int OPT = 0>
 __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, MergeElem &en, WalkState &ws,
                                                int lane, const double *A, const double *B,
                                                const double *DG, const double *GORD, double *rec,
                                                const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
 {
     static_assert(NP >= 1 && NP <= NR, "pass length");
+    static_assert(OPT == 0 || (SORTED && NODIV && !REC_CODE), "the trims of the fast path");
+    double gnn = 0.0;
+    if constexpr ((OPT & kOptLate) != 0) gnn = lds_ld_fixed(ws.gaddr);
     // 1. the popped row's next element x enters the list s_1 <= s_2 <= ... (s_0 was popped):
     //        t_0 = min(x, s_1),   t_k = min(max(x, s_k), s_{k+1}),   t_{NP-1} = max(x, s_{NP-1})
     //    -- every output independent of the others (no carry chain), in place in ascending k.
     //    NP = pass length: the pass reads and writes R[0..NP) only, which is the full pass whenever R[NP..NR) hold nothing
     //    but "huge" keys (see the peeled steps of k_ck_overlap for when that is known without looking).
-    const double x = pack_key11(e.ai + e.bn, e.ci, e.np);
+    const double x = (OPT & kOptBfi) != 0 ? pack_key11_next(e.ai + e.bn, (unsigned)e.np) : pack_key11(e.ai + e.bn, e.ci, e.np);
     if constexpr (NP == 1) {
         R[0] = x;                               // the last element's step: its row's next key is a sentinel, nothing follows
     } else {
     asm("v_min_f64 %0, %1, %2" : "=v"(R[0]) : "v"(x), "v"(R[1]));
     // 2. fetch the operands of the new winner (LDS reads in flight during the rest of the pass and the walk)
-    merge_fetch<W32, SORTED>(R[0], lane, A, B, DG, en, PA, PB);
+    merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, en, PA, PB);
     // 3. finish the insertion: every max first, then every min -- no result is consumed by a neighbouring instruction
     //    (6.40 -> 6.32 ms against blocks of 6, same box)
     constexpr int kBlk = NP;
@@ -224,7 +291,7 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
     }
     // 4. rank walk on the element just consumed
     bool cross;
-    if constexpr (NODIV) cross = merge_walk_nodiv(e, ws, rec);
+    if constexpr (NODIV) cross = merge_walk_nodiv<(OPT & kOptLate) != 0>(e, ws, rec, gnn);
     else cross = merge_walk<REC_CODE>(e, ws, rec, GORD, lane);
     // step code of the gradient replay, 12 bits: row (0-4), column (5-9), "the element closed a bin" (10); kCodesPerWord of
     // them to a 64-bit word of the stream
@@ -246,7 +313,7 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
 // The bodies are instantiated for NP = NR-1 ... 1 and the first NR - G of them are skipped (G is wave-uniform).  Which of
 // e0 / e1 holds the current element alternates per step; the caller hands it over in e1 when G and NR have the same parity
 // and in e0 when not (swap_elems), so the choice is a compile-time one here.
-template <int NP, int NR, bool W32, bool SORTED, bool NODIV>
+template <int NP, int NR, bool W32, bool SORTED, bool NODIV, int OPT = 0>
 __device__ __forceinline__ void merge_peel(double (&R)[NR], MergeElem &e0, MergeElem &e1, WalkState &ws, int G,
                                            int lane, const double *A, const double *B, const double *DG,
                                            const double *GORD, double *rec, const unsigned char *PA,
@@ -255,11 +322,11 @@ __device__ __forceinline__ void merge_peel(double (&R)[NR], MergeElem &e0, Merge
     if constexpr (NP >= 1) {
         if (NP < G) {
             if constexpr (((NR - NP) & 1) != 0)
-                merge_step<NR, W32, false, SORTED, NODIV, NP>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                merge_step<NR, W32, false, SORTED, NODIV, NP, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
             else
-                merge_step<NR, W32, false, SORTED, NODIV, NP>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                merge_step<NR, W32, false, SORTED, NODIV, NP, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
         }
-        merge_peel<NP - 1, NR, W32, SORTED, NODIV>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+        merge_peel<NP - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
     }
 }
 

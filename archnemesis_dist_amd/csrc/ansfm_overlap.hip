@@ -31,10 +31,12 @@ void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, in
     p.g_ord[G + 1] = __builtin_nan("");        // never crossed: merge_walk compares with an ordered >=
 }
 
+constexpr size_t kCuLdsBytes = (size_t)160 * 1024;      // LDS of one CU (MI355X)
+
 int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, size_t block_bytes, int max_per_cu,
                        std::initializer_list<MergeWorkspace> workspaces, long *grid_out)
 {
-    int per_cu = (int)((160 * 1024) / block_bytes);
+    int per_cu = (int)(kCuLdsBytes / block_bytes);
     if (per_cu < 1) per_cu = 1;
     if (per_cu > max_per_cu) per_cu = max_per_cu;
     const long ntiles = (long)p.n_models * (p.Wpad / kWave) * p.L;
@@ -46,6 +48,9 @@ int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, size_t block_byte
     *grid_out = grid;
     return ANSFM_OK;
 }
+
+// the trims an instantiation of the fast path carries: the weight table only with float32 weights (see launch_overlap)
+static constexpr int merge_opt_of(bool w32) { return w32 ? kMergeOpt : (kMergeOpt & ~kOptTable); }
 
 int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wpad, int G, int S,
                    int L, int n_models, const LayerInterp *li, const double *amount,
@@ -70,26 +75,67 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     // a table without a boxed entry is read without the box tests (fast path only; ANSFM_LOAD_BOXTESTS=1 keeps them)
     bool nobox = kLoadNoBox && nodiv && !from_k && !ctx->has_boxed;
     if (const char *ev = getenv("ANSFM_LOAD_BOXTESTS")) { if (ev[0] == '1') nobox = false; }
+    // the trims of the division-free fast path (kMergeOpt); ANSFM_MERGE_LEGACY=1 runs the code without them: one-wave blocks,
+    // the weight from its two factors, the key repacked field by field, the boundary read inside the crossing branch
+    int opt = nodiv ? kMergeOpt : 0;
+    if (const char *ev = getenv("ANSFM_MERGE_LEGACY")) { if (ev[0] == '1') opt = 0; }
     bool keys32 = nodiv && ctx->merge_keys == 32;
     if (const char *ev = getenv("ANSFM_MERGE_KEYS")) { keys32 = nodiv && atoi(ev) == 32; }
-    const size_t lds = keys32 ? (size_t)overlap32_lds_bytes(G, ctx->delg_f32 != 0)
-                              : (size_t)(2 * G + 1) * kWave * sizeof(double) + (size_t)(2 * kMaxG + 2) * sizeof(double) +
-                                    kMaxG * sizeof(float) + (sorted ? 0 : (size_t)2 * G * kWave);
+    if (keys32) opt = 0;
+    // float64 weights keep the two-factor weight: the compiler contracts gd + DG[i] * DG[j] of the walk into one fma, which no
+    // table of rounded products reproduces bit for bit (the float32 product is rounded before it is widened, so its table is exact)
+    if (!ctx->delg_f32) opt &= ~kOptTable;
+    const size_t wave_bytes = (size_t)(2 * G + 1) * kWave * sizeof(double);
+    const size_t table_bytes = (size_t)(2 * kMaxG + 2) * sizeof(double) + kMaxG * sizeof(float);
+    size_t lds = keys32 ? (size_t)overlap32_lds_bytes(G, ctx->delg_f32 != 0)
+                        : wave_bytes + table_bytes + (sorted ? 0 : (size_t)2 * G * kWave);
     const size_t lds_alloc = (lds + 127) / 128 * 128;      // measured (tools/calib/lds_granule.hip): 7 blocks up to 23 360 bytes
     int max_per_cu = 8;
     if (const char *ev = getenv("ANSFM_WAVES_PER_CU")) { int v = atoi(ev); if (v >= 1 && v < max_per_cu) max_per_cu = v; }
     // blocks per CU: by the LDS size rounded up to the 128-byte granule, and no more than ANSFM_WAVES_PER_CU
     long grid = 0;
-    const int rc = merge_launch_begin(ctx, p, lds_alloc, max_per_cu, {{&ctx->scratch, (size_t)6 * G * kWave * sizeof(double)}}, &grid);
-    if (rc) return rc;
+    int nwaves = 1;
+    if ((opt & kOptTable) != 0) {
+        // one block per CU: the tables once, then as many waves' rows as the CU's 160 KiB hold (7 at G = 20), no more than
+        // ANSFM_WAVES_PER_CU or the kernel's launch bound; no more blocks than the tiles need
+        const size_t shared_bytes = table_bytes + weight_table_bytes(G);
+        nwaves = (int)((kCuLdsBytes - shared_bytes) / wave_bytes);
+        if (nwaves > max_per_cu) nwaves = max_per_cu;
+        if (nwaves > kMaxBlockWaves) nwaves = kMaxBlockWaves;
+        lds = shared_bytes + (size_t)nwaves * wave_bytes;
+        const int rc = merge_launch_begin(ctx, p, lds, 1, {{&ctx->scratch, (size_t)nwaves * 6 * G * kWave * sizeof(double)}}, &grid);
+        if (rc) return rc;
+        const long ntiles = (long)n_models * (Wpad / kWave) * L;
+        if (grid > (ntiles + nwaves - 1) / nwaves) grid = (ntiles + nwaves - 1) / nwaves;
+    } else {
+        const int rc = merge_launch_begin(ctx, p, lds_alloc, max_per_cu, {{&ctx->scratch, (size_t)6 * G * kWave * sizeof(double)}}, &grid);
+        if (rc) return rc;
+    }
     p.scratch = ctx->scratch.as<double>();
+    ctx->merge_block_waves = nwaves;
+    ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0);
     if (keys32) {
         HIPCHK(launch_overlap32(p, from_k, merge_list_len(G), (unsigned)grid, ctx->stream));
         return ANSFM_OK;
     }
+    // a block of several waves asks for more than the 64 KiB of dynamic LDS a kernel may have without the attribute
+#define LAUNCH_OPT(...)                                                                                             \
+    do {                                                                                                            \
+        auto kern = __VA_ARGS__;                                                                                    \
+        size_t &lds_allowed = ctx->merge_lds_allowed[reinterpret_cast<const void *>(kern)];   /* 0 at first: 64 KiB */  \
+        if (lds > (size_t)64 * 1024 && lds > lds_allowed) {     /* once per context (device) and instantiation */     \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            lds_allowed = lds;                                                                                      \
+        }                                                                                                           \
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p);                  \
+    } while (0)
 #define LAUNCH_OV2(D, FK, W32)                                                                                      \
     do {                                                                                                            \
-        if (nodiv && nobox)                                                                                         \
+        if (opt != 0 && nobox)                                                                                      \
+            LAUNCH_OPT(k_ck_overlap<D, false, W32, true, true, true, merge_opt_of(W32)>);                           \
+        else if (opt != 0)                                                                                          \
+            LAUNCH_OPT(k_ck_overlap<D, FK, W32, true, true, false, merge_opt_of(W32)>);                             \
+        else if (nodiv && nobox)                                                                                         \
             hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
         else if (nodiv)                                                                                             \
             hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
@@ -114,6 +160,7 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
 #undef LAUNCH_OVN
 #undef LAUNCH_OV
 #undef LAUNCH_OV2
+#undef LAUNCH_OPT
     HIPCHK(hipGetLastError());
     return ANSFM_OK;
 }

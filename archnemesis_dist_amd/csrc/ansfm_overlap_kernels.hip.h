@@ -25,25 +25,46 @@ namespace ansfm {
 // skip rules keep looking at the LAST g-ordinate in the original order (:6075-6102).  A spectrum that passes through
 // unmerged comes out in its original order.
 // NOBOX: the table was found free of boxed entries at upload, load_gas interpolates without the box tests.
-template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_ck_overlap(OverlapParams p)
+// OPT: the trims of the division-free fast path (kOptTable / kOptBfi / kOptLate, ansfm_merge64.hip.h).  With kOptTable the
+// launch is ONE BLOCK OF SEVERAL WAVES PER CU (as many as the LDS holds, blockDim.x / 64) that share DG / GORD and the weight
+// product table WT; rows, tile queue, bin records and the sentinel row stay per wave and there is no barrier after the one
+// that publishes the tables, so the waves run and leave independently as the one-wave blocks do.
+template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false, int OPT = 0>
+__global__ __launch_bounds__((OPT & kOptTable) != 0 ? kWave * kMaxBlockWaves : kWave) __attribute__((amdgpu_waves_per_eu(1, 2)))
+void k_ck_overlap(OverlapParams p)
 {
+    static_assert(OPT == 0 || (SORTED && NODIV), "the trims of the fast path");
+    constexpr bool kTable = (OPT & kOptTable) != 0;
+    static_assert(!kTable || W32, "the weight table holds float32 products only (launch_overlap)");
     extern __shared__ double smem[];
-    const int lane = threadIdx.x;
+    const int lane = kTable ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
+    const int wv = kTable ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;     // wave of the block
+    const int nwv = kTable ? (int)(blockDim.x >> 6) : 1;
     const int G = p.G;
     // tables first: their LDS addresses are compile-time constants (dynamic LDS starts at 0), so a table read is
     // `ds_read vaddr = index << k, offset:const` with no base add
     double *DG = smem;                           // [kMaxG] doubles, then GORD [kMaxG + 2], then the float32 copy of DG
     double *GORD = DG + kMaxG;
     double *A = reinterpret_cast<double *>(reinterpret_cast<char *>(GORD + kMaxG + 2) + kMaxG * sizeof(float));
+    if constexpr (kTable) {
+        // WT[(col << 5) | row] = the very double pair_weight<true> forms (DGF[i] = (float)del_g[i]); 0 outside
+        double *WT = A;
+        for (int idx = (int)threadIdx.x; idx < (G + 1) * 32; idx += (int)blockDim.x) {
+            const int row = idx & 31, col = idx >> 5;
+            double w = 0.0;
+            if (row < G && col < G) w = (double)((float)p.del_g[row] * (float)p.del_g[col]);
+            WT[idx] = w;
+        }
+        A = WT + (G + 1) * 32 + (size_t)wv * (2 * G + 1) * kWave;
+    }
     double *B = A + G * kWave;                   // G+1 rows
     unsigned char *PA = reinterpret_cast<unsigned char *>(B + (G + 1) * kWave);   // SORTED = false only
     unsigned char *PB = PA + G * kWave;
-    if (lane < G) {
+    if (wv == 0 && lane < G) {
         DG[lane] = p.del_g[lane];
         const_cast<float *>(delg_f32_table(DG))[lane] = (float)p.del_g[lane];
     }
-    if (lane < G + 2) GORD[lane] = p.g_ord[lane];
+    if (wv == 0 && lane < G + 2) GORD[lane] = p.g_ord[lane];
     const double HUGE_KEY = __longlong_as_double(0x7FE0000000000000LL);   // finite, above any optical depth
     B[G * kWave + lane] = HUGE_KEY;
     __syncthreads();
@@ -52,7 +73,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
     const double wtot = wsum * wsum;  // stands in for gdist[-1] (python wrap at iloop==0)
 
     // per-block scratch: closed-bin records, see kRecBin
-    double *rec = p.scratch + (size_t)blockIdx.x * 6 * G * kWave;
+    double *rec = p.scratch + ((size_t)blockIdx.x * nwv + wv) * 6 * G * kWave;
     TileQueue tq;
     tq.init();
     for (;;) {
@@ -90,35 +111,35 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
                 double R[NR];
                 merge_init<NR>(R, G, lane, A, B[lane], HUGE_KEY);
                 MergeElem e0, e1;
-                merge_fetch<W32, SORTED>(R[0], lane, A, B, DG, e0, PA, PB);
-                WalkState ws = walk_begin(GORD, lane);
+                merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB);
+                WalkState ws = walk_begin<(OPT & kOptLate) != 0>(GORD, lane);
                 if constexpr (NODIV) ws.roff = (unsigned)lane * 8u;
                 // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
                 const int nloop = kMergePeel ? G * G - (G - 1) : G * G;
                 // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
                 constexpr int kPer = kMergeUnroll4 ? 4 : 2;
                 for (int n = nloop / kPer; n > 0; --n) {
-                    merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
-                    merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
                     if constexpr (kMergeUnroll4) {
-                        merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
-                        merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
                     }
                 }
                 if constexpr (kMergeUnroll4)
                     if ((nloop & 2) != 0) {
-                        merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
-                        merge_step<NR, W32, false, SORTED, NODIV>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
                     }
                 if (kMergePeel || (nloop & 1) != 0)
-                    merge_step<NR, W32, false, SORTED, NODIV>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
                 if constexpr (kMergePeel) {
                     if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
-                    merge_peel<NR - 1, NR, W32, SORTED, NODIV>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
                 }
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
-                    const int ig = walk_bins(ws, GORD);
+                    const int ig = walk_bins<(OPT & kOptLate) != 0>(ws, GORD);
                     for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
                         double r[kLoadBatch];
 #pragma unroll
@@ -141,7 +162,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 2))) v
                 // walk formed it, so `a` must stay intact until the last bin is done: the outputs go to row 0 of the bin
                 // records (full-wave coalesced stores) and come back into A afterwards.
                 double ck = 0.0, cs = 0.0;   // (1-frac) share carried into the next bin
-                const int ig = walk_bins(ws, GORD);
+                const int ig = walk_bins<(OPT & kOptLate) != 0>(ws, GORD);
                 constexpr int kRB = 5;       // records of kRB bins are fetched together (one round trip)
                 for (int b0 = 0; b0 < G; b0 += kRB) {
                     double rka[kRB], rs1[kRB], rgd[kRB];

@@ -277,6 +277,12 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_ktable_has_boxed(self._ctx, C.byref(b)), "ktable_has_boxed")
         return bool(b.value)
 
+    def last_merge_launch(self):
+        """(waves per block, trim bits) of the last forward merge launch: bits 1 weight table, 2 key repack, 4 late bin read."""
+        w, t = C.c_int(), C.c_int()
+        self._check(self._lib.ansfm_last_merge_launch(self._ctx, C.byref(w), C.byref(t)), "last_merge_launch")
+        return int(w.value), int(t.value)
+
     # ---- array-level seams --------------------------------------------------------------------
     def calc_k(self, press, temp, grad=False):
         press = _np(press); temp = _np(temp)

@@ -77,6 +77,10 @@ int ansfm_ktable_info(const ansfm_ctx *ctx, int64_t dims[5], int *monotone);
 /* has_boxed = 1 when some entry of the table is <= 0 or NaN (such entries are stored NaN-boxed and every interpolation
  * tests for them); 0 for an all-positive table, whose forward merge reads it without those tests. */
 int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed);
+/* How the last forward merge (k_overlap, cirsrad_ck_thermal, ...) was launched: waves per block (1: one-wave blocks) and the
+ * trims of the division-free fast path its kernel carried, as bits (1 weight product table, 2 two-instruction key repack,
+ * 4 bin boundary read a step ahead; 0: the code without them, or another path of the merge). */
+int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *trims);
 
 /* ---- LBL tables (ILBL = LINE_BY_LINE_TABLES) ------------------------------------------------------
  * State of Spectroscopy_0 after read_tables on .lta / HDF5 LBL tables: K[W][NP][|NT|][S] (NG = 1),
