@@ -13,6 +13,8 @@
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
 //   ansfm_transit.hip  primary-transit depth with gradients, collapsed over paths on the device: the entry point, its
 //                      path-matrix build and its kernels
+//   ansfm_occultation.hip  solar occultation with gradients, the tangent paths mixed to the geometries on the device: the
+//                      entry point, its compressed matrices and its kernels
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -144,6 +146,12 @@ struct ansfm_ctx {
     size_t transit_scratch_bytes = 0;
     int transit_recorded = 0;
     hipEvent_t transit_ev[3] = {nullptr, nullptr, nullptr};
+    // solar occultation (ansfm_cirsradg_ck_occultation): exp(-tau_path) [P][G][Wpad] + MOD [W][Q] + T [W][P]; their bytes in the
+    // last call; events around k_occ_paths and k_occ_grad (created at the first call)
+    DevBuf occ_ws;
+    size_t occ_scratch_bytes = 0;
+    int occ_recorded = 0;
+    hipEvent_t occ_ev[3] = {nullptr, nullptr, nullptr};
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;
@@ -160,6 +168,7 @@ struct ansfm_ctx {
     {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : transit_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : occ_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
     }

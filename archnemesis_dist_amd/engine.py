@@ -539,6 +539,76 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_transit_last(self._ctx, C.byref(info)), "transit_last")
         return int(info[0]), info[1], info[2]
 
+    def cirsradg_ck_occultation(self, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
+                                mix, xfac=None, gradients_on_device=False, dtau_every_gas=None):
+        """Solar occultation with analytic gradients of one model (nemesisSOfmg :983-1249), the limb paths mixed to the
+        geometries on the device: MOD (W, Q) = xfac * TRANS @ C.T, TRANS (W, P) the path transmissions, and dMOD (W, NPAR, L, Q)
+        = d MOD / d (layer property), in the layout of the reference's dSPECOUT with the layers in place of the path entries and
+        the geometries in place of the paths; dTAUTOT assembled as in `cirsradg_ck_thermal`.  mix: the mixing matrix C, dense
+        (Q, P) (its zeros are dropped) or a triple (ptr (Q + 1,), path (nnz,), val (nnz,)) of compressed rows
+        (`occultation.tangent_mix`); a geometry with an empty row gives zeros.  The other arguments as `cirsradg_ck_transit`;
+        xfac (W,) the solar flux or None.  gradients_on_device=True: dMOD is not copied to the host (None in its place) and
+        `map2pro(None, ...)` with NPATH = Q, NLAYIN = [L] * Q, LAYINC[:, q] = arange(L) continues from the device copy; only this
+        arms the chain.  dMOD takes 8 W NPAR L Q bytes on the device.  NotImplementedError above 320 layers or paths, or when
+        dMOD cannot be reserved."""
+        W, G, NP, NT, S = self.dims
+        lp = _np(lay_press_pa)
+        if lp.ndim != 1:
+            raise ValueError("cirsradg_ck_occultation: one model, lay_press_pa (NLAY,)")
+        L = lp.shape[0]
+        lt = _np(lay_temp).reshape(L)
+        am = _np(amount).reshape(S, L)
+        tc = None if taucont is None else _np(taucont).reshape(W, L)
+        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, NPAR, L)
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        SC = _np(SCALE).reshape(LIMAX, P)
+        if NLAYIN.shape != (P,):
+            raise ValueError("cirsradg_ck_occultation: NLAYIN must be (NPATH,)")
+        if isinstance(mix, tuple):
+            mptr, mpath, mval = _np(mix[0], np.int32), _np(mix[1], np.int32).reshape(-1), _np(mix[2]).reshape(-1)
+            if mptr.ndim != 1 or mptr.size < 2 or mpath.size != mval.size or mptr[-1] != mpath.size:
+                raise ValueError("cirsradg_ck_occultation: mix must be (ptr (Q + 1,), path (nnz,), val (nnz,)) with ptr[-1] = nnz")
+        else:
+            Cm = _np(mix)
+            if Cm.ndim != 2 or Cm.shape[1] != P or Cm.shape[0] < 1:
+                raise ValueError("cirsradg_ck_occultation: a dense mix must be (NGEOM, NPATH)")
+            nz = Cm != 0.0
+            mptr = _np(np.concatenate([[0], np.cumsum(nz.sum(axis=1))]), np.int32)
+            mpath = _np(np.nonzero(nz)[1], np.int32)
+            mval = _np(Cm[nz])
+        Q = mptr.size - 1
+        xf = None if xfac is None else _np(xfac).reshape(W)
+        ig = _np(igas_map, np.int32)
+        if dtau_every_gas is not None:
+            dg = _np(dtau_every_gas)
+            if dg.shape != (W, L):
+                raise ValueError("cirsradg_ck_occultation: dtau_every_gas must be (NWAVE, NLAY)")
+            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
+        mod = np.empty((W, Q)); trans = np.empty((W, P))
+        dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
+        self._chain_dspec = None
+        try:
+            rc = self._lib.ansfm_cirsradg_ck_occultation(
+                self._ctx, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
+                _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf), _ptr(mod), _ptr(trans),
+                _ptr(dmod))
+        finally:
+            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
+                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
+        self._check(rc, "cirsradg_ck_occultation")
+        if gradients_on_device:
+            self._chain_dspec = ("device", W, int(NPAR), L, Q)
+        return mod, trans, dmod
+
+    def occultation_last(self):
+        """(scratch bytes beyond the gas stage and dMOD, k_occ_paths ms, k_occ_grad ms) of the last cirsradg_ck_occultation call"""
+        info = (C.c_double * 3)()
+        self._check(self._lib.ansfm_occultation_last(self._ctx, C.byref(info)), "occultation_last")
+        return int(info[0]), info[1], info[2]
+
     def cirsradg_ck_thermal(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
                             NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None, gradients_on_device=False,
                             dtau_every_gas=None):

@@ -652,6 +652,89 @@ class CIRSradGPU:
         SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)
         return SPECONV, dSPECONV
 
+    # ---- solar occultation with gradients: the tangent paths mixed to the geometries on the device ------------------
+    def nemesisSOfmg(self):
+        """nemesisSOfmg (ForwardModel_0.py:983-1249), plain branch (:1160-1247).  The reference asks CIRSrad for dSPECOUT
+        (NWAVE, NPAR, LIMAX, NPATH), maps it to the state vector path by path and only then interpolates the paths to the
+        tangent heights of the measurement (:1208-1232); every step after the transmission is linear, so here ONE
+        `AnsfmEngine.cirsradg_ck_occultation` call applies the interpolation first (`occultation.tangent_mix`) and map2pro /
+        map2xvec run on that (NWAVE, NPAR, NLAY, NGEOM) array on the device.  The same steps as the reference's otherwise.  Its
+        own method, whose CIRSrad(return_grad=True) is the seam above, takes over for the AOTF branch, a Telluric object,
+        runtime line-by-line, a case CIRSrad would delegate, an engine without the call and one that refuses it."""
+        from copy import deepcopy
+        if getattr(self.Measurement, "NORDERS_AOTF", None) is not None or getattr(self, "Telluric", None) is not None:
+            return super().nemesisSOfmg()
+        eng = get_engine(self.ansfm_device)
+        if not hasattr(eng, "cirsradg_ck_occultation"):
+            return super().nemesisSOfmg()
+        from . import occultation as _occ
+        self.Variables1 = deepcopy(self.Variables)                              # :1024-1032
+        self.MeasurementX = deepcopy(self.Measurement)
+        self.AtmosphereX = deepcopy(self.Atmosphere)
+        self.ScatterX = deepcopy(self.Scatter)
+        self.StellarX = deepcopy(self.Stellar)
+        self.SurfaceX = deepcopy(self.Surface)
+        self.LayerX = deepcopy(self.Layer)
+        self.SpectroscopyX = deepcopy(self.Spectroscopy)
+        self.CIAX = deepcopy(self.CIA)
+        self.check_gas_spec_atm()                                               # :1036-1037
+        self.check_wave_range_consistency()
+        self.Measurement.build_ils(IGEOM=0)                                     # :1165-1170
+        wavecalc_min, wavecalc_max = self.Measurement.calc_wave_range(apply_doppler=True, IGEOM=None)
+        if self.SpectroscopyX.NGAS > 0:
+            self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
+        self.adjust_hydrostat = False
+        xmap = self.subprofretg()
+        self.calc_pathg_SO()
+        S, L, P, A, M = self.SpectroscopyX, self.LayerX, self.PathX, self.AtmosphereX, self.MeasurementX
+        imod = np.unique(np.asarray(P.IMOD).astype(int))
+        if (not self._ansfm_supported(True) or not self._ansfm_transmission_branch(int(imod[0]))
+                or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)):
+            return super().nemesisSOfmg()
+        NPATH = int(P.NPATH)
+        NLAYIN = np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH)
+        LAYINC = np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH)
+        SCALE = np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH)
+        BASEH_TANHE = _occ.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)         # :1180-1182
+        mix = _occ.tangent_mix(BASEH_TANHE, M.TANHE)                            # :1211-1232
+        NGEOM = int(M.NGEOM)
+        self._ansfm_upload_table(eng)
+        TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(True)
+        taucont = TAUCIA + TAUDUST + TAURAY                                     # :3989
+        f_gas = self._ansfm_layer_inputs()
+        xf = None
+        if int(M.IFORM) == IFORM_ATMOSPHERIC_TRANSMISSION:                      # :4119-4127: times the solar flux
+            import scipy.interpolate
+            self.StellarX.calc_solar_flux()
+            xf = scipy.interpolate.interp1d(self.StellarX.WAVE, self.StellarX.SOLFLUX)(S.WAVE)
+        NVMR, NDUST, NPRO, NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
+        NPAR = NVMR + 2 + int(self.ScatterX.NDUST)
+        igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
+        try:
+            MOD, SPECOUT, _ = eng.cirsradg_ck_occultation(np.asarray(L.PRESS, dtype=np.float64), np.asarray(L.TEMP, dtype=np.float64),
+                                                          f_gas, taucont, dTAUCON, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
+                                                          mix=mix, xfac=xf, gradients_on_device=True)
+        except NotImplementedError:                 # more layers or paths than the fused call takes, or no room for dMOD
+            _note("nemesisSOfmg: the fused occultation call refused the case (layers, paths or the size of dMOD); the reference's "
+                  "method runs over CIRSrad(return_grad=True) instead")
+            return super().nemesisSOfmg()
+        _route("nemesisSOfmg: tangent paths mixed to the geometries on the device")
+        if self.ansfm_keep_side_products:
+            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
+            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, TAUCIA, TAUDUST, TAURAY)
+        incpar = [i for i in range(NVMR + 2 + NDUST) if np.mean(xmap[:, i, :]) != 0.0]   # :1193-1196
+        eng.map2pro(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, np.array([NLAY] * NGEOM), np.tile(np.arange(NLAY)[:, None], (1, NGEOM)),
+                    L.DTE, L.DAM, L.DCO, INCPAR=incpar, to_host=False)
+        dSPECMOD = eng.map2xvec(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, self.Variables.NX, xmap)      # (NWAVE, NGEOM, NX)
+        SPECMOD = np.array(MOD)
+        if int(S.ILBL) == ILBL_K_TABLES:                                        # :1236-1241
+            SPECONV, dSPECONV = M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        else:
+            SPECONV, dSPECONV = M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        dSPECONV = self.subspeconv(S.WAVE, SPECMOD, dSPECONV)                   # :1244
+        SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1247
+        return SPECONV, dSPECONV
+
 
 def make_gpu_forward_model(reference_forward_model_cls, device=0):
     """Subclass of the reference's ForwardModel_0 with the GPU CIRSrad seam and `jacobian_nemesis` without the joblib

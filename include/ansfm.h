@@ -289,6 +289,32 @@ int ansfm_cirsradg_ck_transit(ansfm_ctx *ctx, int L, const double *lay_press_pa,
                               const double *path_weight, double *AREA, double *TRANS, double *dAREA);
 int ansfm_transit_last(const ansfm_ctx *ctx, double info[3]);
 
+/* Solar occultation with analytic gradients of ONE model (nemesisSOfmg, ForwardModel_0.py:983-1249): the limb paths are mixed to
+ * the Q geometries of the measurement on the device -- the interpolation to the tangent heights (:1208-1232) as a sparse matrix
+ * C (Q, P), rows mix_ptr[q] .. mix_ptr[q + 1] of (mix_path, mix_val) -- instead of through dSPECOUT (W, NPAR, LIMAX, P).  All
+ * pointers are host pointers.  With Sm and tau_path as for ansfm_cirsradg_ck_transit and xfac[W] the solar flux of :4119-4127
+ * (NULL: 1):
+ *   TRANS[w][p] = sum_g DELG[g] exp(-tau_path[w][g][p])          MOD[w][q] = xfac[w] sum_p C[q][p] TRANS[w][p]
+ *   dMOD[w][k][l][q] = - xfac[w] sum_g DELG[g] (sum_p C[q][p] Sm[l][p] exp(-tau_path[w][g][p])) dTAUTOT[w][g][k][l]
+ * with dTAUTOT assembled as in ansfm_cirsradg_ck_thermal before its x SCALE (gas slots x 1e-4 through igas_map, temperature slot
+ * at NVMR, dtaucon, a pending ansfm_set_shared_gas_gradient, ansfm_set_gradient_gases honoured).  dMOD has the layout of the
+ * reference's dSPECOUT with LIMAX -> L and NPATH -> Q; nan_to_num (:4507) acts on each dMOD element (the reference applies it per
+ * path entry; the two agree whenever its dSPECOUT is finite).  A geometry with an empty row gives zeros.  TRANS[W][P] and
+ * dMOD[W][NPAR][L][Q] may be NULL; dMOD always stays on the device as a (W, NPAR, L, Q) result for ansfm_map2pro(dSPECIN = NULL)
+ * with NLAYIN = L and LAYINC = 0 .. L - 1 for every geometry.  dMOD is held as a whole, 8 W NPAR L Q bytes (the spectral axis is
+ * not slabbed): ANSFM_ERR_UNSUPPORTED when that cannot be reserved, so that the caller can take the un-collapsed route.  Device
+ * scratch beyond the gas stage and dMOD is 8 P G Wpad bytes plus MOD and TRANS.  ANSFM_ERR_UNSUPPORTED above 320 layers or 320
+ * paths (a 64-lane LDS tile with one row per layer, 160 KiB).  ANSFM_ERR_INVALID for NLAYIN[p] > LIMAX, a LAYINC[j][p],
+ * j < NLAYIN[p], outside 0 .. L - 1, a mix_ptr that does not start at 0 or decreases, a mix_path outside 0 .. P - 1.
+ * ansfm_occultation_last: info[0] the bytes of that scratch in the last call, info[1] / info[2] the milliseconds of k_occ_paths /
+ * k_occ_grad. */
+int ansfm_cirsradg_ck_occultation(ansfm_ctx *ctx, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
+                                  const double *taucont, const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P,
+                                  int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, int Q,
+                                  const int32_t *mix_ptr, const int32_t *mix_path, const double *mix_val, const double *xfac,
+                                  double *MOD, double *TRANS, double *dMOD);
+int ansfm_occultation_last(const ansfm_ctx *ctx, double info[3]);
+
 /* ---- analytic-gradient seams ---------------------------------------------------------------
  * ForwardModel_0.k_overlapg (ForwardModel_0.py:5842): + dkdT[W][G][L][S] -> tau[W][G][L],
  * dk[W][G][L][S+1] (slots 0..S-1 = d tau/d amount_gas, slot S = d tau/dT). */
