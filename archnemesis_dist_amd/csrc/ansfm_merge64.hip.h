@@ -36,6 +36,10 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 //                   float32 weights only: with float64 weights the walk's gd + DG[i] * DG[j] is compiled as one fma
 //   kKeyBfi         the popped row's next key is the winner's low word + 32 inserted under the 11-bit mask (kOptBfi)
 //   kLateBinWait    the boundary after next is read at the top of every step, the crossing branch only moves it (kOptLate)
+//   kMergeExit      the list pass of a step ends at the first chunk boundary c with no lane's x above R[c] (kOptExit,
+//                   merge_pass_exit).  Slower than the full pass on its own; a gain together with kMergeOrient
+//   kMergeOrient    per lane and merge, the rows are the operand with the larger top ordinate, so that the popped row's next
+//                   key re-enters near the front of the list (kOptOrient, MergeOrient; needs kKeyBfi)
 #ifndef ANSFM_MERGE_PEEL
 #define ANSFM_MERGE_PEEL 1
 #endif
@@ -57,11 +61,30 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 #ifndef ANSFM_LATE_BIN_WAIT
 #define ANSFM_LATE_BIN_WAIT 0       // measured slower than the read inside the branch: kept, switched off
 #endif
+#ifndef ANSFM_MERGE_EXIT
+#define ANSFM_MERGE_EXIT 1
+#endif
+#ifndef ANSFM_MERGE_ORIENT
+#define ANSFM_MERGE_ORIENT 1
+#endif
+#ifndef ANSFM_MERGE_EXIT_FORM
+#define ANSFM_MERGE_EXIT_FORM 0     // 0: a test between chunks; 1: every test first, then one straight-line pass
+#endif
+// chunk boundaries of kMergeExit, ascending.  Two tests per step measured faster than four: every test is a
+// scalar branch that the wave waits for, and a wave alone on its SIMD has nobody to hide it behind
+#ifndef ANSFM_MERGE_EXIT_BOUNDS
+#define ANSFM_MERGE_EXIT_BOUNDS 4, 10
+#endif
 constexpr bool kMergePeel = ANSFM_MERGE_PEEL != 0, kWalkOneOffset = ANSFM_WALK_ONE_OFFSET != 0, kMergeUnroll4 = ANSFM_MERGE_UNROLL4 != 0,
                kLoadNoBox = ANSFM_LOAD_NOBOX != 0, kWeightTable = ANSFM_WEIGHT_TABLE != 0, kKeyBfi = ANSFM_KEY_BFI != 0,
-               kLateBinWait = ANSFM_LATE_BIN_WAIT != 0;
-constexpr int kOptTable = 1, kOptBfi = 2, kOptLate = 4;
-constexpr int kMergeOpt = (kWeightTable ? kOptTable : 0) | (kKeyBfi ? kOptBfi : 0) | (kLateBinWait ? kOptLate : 0);
+               kLateBinWait = ANSFM_LATE_BIN_WAIT != 0, kMergeExit = ANSFM_MERGE_EXIT != 0,
+               kMergeOrient = ANSFM_MERGE_ORIENT != 0 && kKeyBfi;
+constexpr int kOptTable = 1, kOptBfi = 2, kOptLate = 4, kOptExit = 8, kOptOrient = 16;
+constexpr int kMergeOpt = (kWeightTable ? kOptTable : 0) | (kKeyBfi ? kOptBfi : 0) | (kLateBinWait ? kOptLate : 0) |
+                          (kMergeExit ? kOptExit : 0) | (kMergeOrient ? kOptOrient : 0);
+// Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
+// lane whose columns are a.  One block's waves still fit the CU's LDS as before at every instantiated list length.
+__host__ __device__ constexpr int merge_wave_rows(int G, int opt) { return 2 * G + ((opt & kOptOrient) != 0 ? 2 : 1); }
 // The product table follows the float32 copy of DG; (col << 5) | row with col <= G (an exhausted row's sentinel key names
 // column G; its entry is read and never used), so (G + 1) * 32 doubles.  The per-wave rows come after it.
 constexpr unsigned kLdsWT = kLdsA;
@@ -74,6 +97,27 @@ struct MergeElem {
     double ai, bc, bn, w;
     int ci, np;         // np = column + 1; with kOptBfi the winner key's low word instead (the fetch decodes ci and the column)
 };
+
+// kOptOrient: which operand supplies the rows is a per-lane choice, made once per merge.  The merge is symmetric in its operands
+// (a_i + b_j, del_g[i] * del_g[j] as a float32 or float64 product), and with the larger operand as the rows the sorted order
+// runs row by row: the popped row's next key re-enters the list near its front, where kOptExit ends the pass.  A lane whose
+// rows are b ("swapped") needs its columns, a, ascending; a merged spectrum is that only up to rounding (merge_init), so such
+// a lane is swapped only if its a is non-decreasing.  A swapped lane packs the low 11 key bits as (row << 6) | col instead of
+// (col << 5) | row: both are (b-index major, a-index minor), so keys whose top 53 bits tie pop in the same order whichever
+// way a lane is oriented, and the popped sequence of (a-index, b-index) pairs is the unswapped one's.  Rows stay below 32;
+// the 6-bit column field holds the sentinel index G <= 32.
+struct MergeOrient {
+    unsigned rbase, cbase;  // LDS byte address of this lane's entry of row 0 / column 0
+    unsigned rsh, csh;      // bit offset of the row / column field in the key's low word: 0, 5 or (swapped) 6, 0
+    unsigned inc;           // column + 1 in the low word: 32 or (swapped) 1
+};
+__device__ __forceinline__ MergeOrient merge_orient(unsigned a_addr, unsigned b_addr, bool swapped)
+{
+    MergeOrient mo;
+    mo.rbase = swapped ? b_addr : a_addr; mo.cbase = swapped ? a_addr : b_addr;
+    mo.rsh = swapped ? 6u : 0u; mo.csh = swapped ? 0u : 5u; mo.inc = swapped ? 1u : 32u;
+    return mo;
+}
 
 // Weight of element (i, j) = del_g[i] * del_g[j].  DELG float32 (W32): NumPy forms the float32 product, which is one
 // v_mul_f32 of the float32 copies kept behind the double tables (DG, GORD) in LDS.
@@ -93,11 +137,28 @@ __device__ __forceinline__ double pair_weight(const double *DG, int i, int j)
 template <bool W32, bool SORTED = true, int OPT = 0>
 __device__ __forceinline__ void merge_fetch(double key, int lane, const double *A, const double *B,
                                             const double *DG, MergeElem &e,
-                                            const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
+                                            const unsigned char *PA = nullptr, const unsigned char *PB = nullptr,
+                                            const MergeOrient &mo = MergeOrient{})
 {
     static_assert(OPT == 0 || SORTED, "the trims of the fast path");
+    static_assert((OPT & kOptOrient) == 0 || (OPT & kOptBfi) != 0, "the oriented key is repacked from its low word");
     const unsigned kb = (unsigned)__double_as_longlong(key);
     int ci, cp;
+    if constexpr ((OPT & kOptOrient) != 0) {
+        // the fields at per-lane bit offsets, the addresses on per-lane bases: the instruction count of the unoriented fetch.
+        // The table index is formed from the decoded fields (WT is symmetric: the product of the two float32 weights)
+        asm("v_bfe_u32 %0, %1, %2, 5" : "=v"(ci) : "v"(kb), "v"(mo.rsh));
+        asm("v_bfe_u32 %0, %1, %2, 6" : "=v"(cp) : "v"(kb), "v"(mo.csh));
+        e.ci = ci;
+        e.np = (int)kb;
+        if constexpr ((OPT & kOptTable) != 0) e.w = lds_ld(kLdsWT + ((unsigned)cp << 8) + ((unsigned)ci << 3));
+        e.ai = lds_ld(mo.rbase + ((unsigned)ci << 9));
+        const unsigned ab = mo.cbase + ((unsigned)cp << 9);
+        e.bc = lds_ld(ab);
+        e.bn = lds_ld(ab + 512);                // column G of either operand is its sentinel row
+        if constexpr ((OPT & kOptTable) == 0) e.w = pair_weight<W32>(DG, ci, cp);
+        return;
+    }
     if constexpr (OPT != 0) {
         // the two fields as one instruction each, so that every row address is one v_lshl_add on top: with the low word kept
         // in a register (kw) the compiler otherwise forms (kw << k) & mask + base, three instructions per address
@@ -132,10 +193,11 @@ __device__ __forceinline__ double pack_key11(double v, int row, int col)
 // The next key of a popped row from the winner's low word kw = ... | col << 5 | row: col + 1 is kw + 32, and the 11 bits go
 // into the value's low word under the mask (v_add_u32 + v_bfi_b32).  col <= 32, so the add does not leave the 11 bits for
 // any key that is consumed; the same double as pack_key11(v, row, col + 1).
-__device__ __forceinline__ double pack_key11_next(double v, unsigned kw)
+// inc: 32, or 1 in a lane whose key holds the column in its low six bits (MergeOrient; col + 1 <= 33 stays inside them).
+__device__ __forceinline__ double pack_key11_next(double v, unsigned kw, unsigned inc = 32u)
 {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = ((kw + 32u) & 0x7FFu) | ((unsigned)b & ~0x7FFu);
+    const unsigned lo = ((kw + inc) & 0x7FFu) | ((unsigned)b & ~0x7FFu);
     return __longlong_as_double((long long)((b & 0xFFFFFFFF00000000ULL) | lo));
 }
 
@@ -245,6 +307,73 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
     return cross;
 }
 
+// kOptExit: the rest of the list pass of merge_step, entries K0 .. NP-1, in chunks that end at compile-time boundaries.  A chunk
+// over [K0, K1) writes t_k = min(max(x, s_k), s_{k+1}) for its entries, reading R[K1] as the pass found it (in place, in
+// ascending k).  If no lane has x > R[K1] -- an ordered compare whose 64-bit result is the ballot, and a scalar branch --
+// then t_k = s_k for every k >= K1 in every lane: the list is sorted, so x <= s_k <= s_{k+1}.  The pass stops there, exactly,
+// ties included.  A sentinel x (the popped row is exhausted) is above every live key and runs to the end of the live
+// prefix like any other.  The last chunk closes with t_{NP-1} = max(x, s_{NP-1}) as the full pass does.
+constexpr int kExitBounds[] = {ANSFM_MERGE_EXIT_BOUNDS};
+constexpr int kNoExitBound = 1000;
+// the first boundary above k0
+__host__ __device__ constexpr int merge_exit_bound(int k0)
+{
+    for (int b : kExitBounds)
+        if (b > k0) return b;
+    return kNoExitBound;
+}
+template <int K0, int NP, int NR>
+__device__ __forceinline__ void merge_pass_exit(double (&R)[NR], double x)
+{
+    // the last boundary leaves at least two entries to the closing chunk
+    constexpr int K1 = merge_exit_bound(K0) < NP - 2 ? merge_exit_bound(K0) : NP - 1;
+    double mk[K1 - K0 > 0 ? K1 - K0 : 1];
+#pragma unroll
+    for (int k = K0; k < K1; ++k) asm("v_max_f64 %0, %1, %2" : "=v"(mk[k - K0]) : "v"(x), "v"(R[k]));
+#pragma unroll
+    for (int k = K0; k < K1; ++k) asm("v_min_f64 %0, %1, %2" : "=v"(R[k]) : "v"(mk[k - K0]), "v"(R[k + 1]));
+    if constexpr (K1 == NP - 1) {
+        asm("v_max_f64 %0, %1, %2" : "=v"(R[NP - 1]) : "v"(x), "v"(R[NP - 1]));
+    } else {
+        if (__builtin_amdgcn_ballot_w64(x > R[K1]) != 0) merge_pass_exit<K1, NP>(R, x);
+    }
+}
+
+// The other form (ANSFM_MERGE_EXIT_FORM 1): every boundary compare first, then one descent to a straight-line pass of the
+// length found, "every max before every min" inside it -- the pass of merge_step with NP = the boundary.
+template <int NP, int NR>
+__device__ __forceinline__ void merge_pass_straight(double (&R)[NR], double x)
+{
+    double mk[NP];
+#pragma unroll
+    for (int k = 1; k < NP - 1; ++k) asm("v_max_f64 %0, %1, %2" : "=v"(mk[k]) : "v"(x), "v"(R[k]));
+#pragma unroll
+    for (int k = 1; k < NP - 1; ++k) asm("v_min_f64 %0, %1, %2" : "=v"(R[k]) : "v"(mk[k]), "v"(R[k + 1]));
+    asm("v_max_f64 %0, %1, %2" : "=v"(R[NP - 1]) : "v"(x), "v"(R[NP - 1]));
+}
+template <int I, int K, int NP, int NR, int NB>
+__device__ __forceinline__ void merge_pass_pick(double (&R)[NR], double x, const unsigned long long (&m)[NB])
+{
+    if constexpr (K >= NP - 2) merge_pass_straight<NP>(R, x);
+    else {
+        if (m[I] == 0) merge_pass_straight<K>(R, x);
+        else merge_pass_pick<I + 1, merge_exit_bound(K), NP>(R, x, m);
+    }
+}
+template <int NP, int NR>
+__device__ __forceinline__ void merge_pass_upfront(double (&R)[NR], double x)
+{
+    constexpr int kMaxB = (int)(sizeof(kExitBounds) / sizeof(kExitBounds[0]));
+    unsigned long long m[kMaxB];
+    int c = merge_exit_bound(1);
+#pragma unroll
+    for (int i = 0; i < kMaxB; ++i) {
+        m[i] = (c < NP - 2) ? __builtin_amdgcn_ballot_w64(x > R[c < NR ? c : 0]) : 0ull;    // c: a constant once unrolled
+        c = merge_exit_bound(c);
+    }
+    merge_pass_pick<0, merge_exit_bound(1), NP>(R, x, m);
+}
+
 // The heads of the G rows are kept as a SORTED LIST IN REGISTERS (R[0] = the current winner): popping is free and the
 // row's next key is inserted by one pass of v_max_f64 + v_min_f64 pairs over statically indexed
 // registers -- no tree in LDS, no lane-dependent addressing, and the next winner is known after the FIRST
@@ -256,7 +385,8 @@ template <int NR, bool W32, bool REC_CODE = false, bool SORTED = true, bool NODI
 __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, MergeElem &en, WalkState &ws,
                                                int lane, const double *A, const double *B,
                                                const double *DG, const double *GORD, double *rec,
-                                               const unsigned char *PA = nullptr, const unsigned char *PB = nullptr)
+                                               const unsigned char *PA = nullptr, const unsigned char *PB = nullptr,
+                                               const MergeOrient &mo = MergeOrient{})
 {
     static_assert(NP >= 1 && NP <= NR, "pass length");
     static_assert(OPT == 0 || (SORTED && NODIV && !REC_CODE), "the trims of the fast path");
@@ -267,13 +397,19 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
     //    -- every output independent of the others (no carry chain), in place in ascending k.
     //    NP = pass length: the pass reads and writes R[0..NP) only, which is the full pass whenever R[NP..NR) hold nothing
     //    but "huge" keys (see the peeled steps of k_ck_overlap for when that is known without looking).
-    const double x = (OPT & kOptBfi) != 0 ? pack_key11_next(e.ai + e.bn, (unsigned)e.np) : pack_key11(e.ai + e.bn, e.ci, e.np);
+    const double x = (OPT & kOptOrient) != 0 ? pack_key11_next(e.ai + e.bn, (unsigned)e.np, mo.inc)
+                   : (OPT & kOptBfi) != 0    ? pack_key11_next(e.ai + e.bn, (unsigned)e.np)
+                                             : pack_key11(e.ai + e.bn, e.ci, e.np);
     if constexpr (NP == 1) {
         R[0] = x;                               // the last element's step: its row's next key is a sentinel, nothing follows
     } else {
     asm("v_min_f64 %0, %1, %2" : "=v"(R[0]) : "v"(x), "v"(R[1]));
     // 2. fetch the operands of the new winner (LDS reads in flight during the rest of the pass and the walk)
-    merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, en, PA, PB);
+    merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, en, PA, PB, mo);
+    if constexpr ((OPT & kOptExit) != 0) {
+        if constexpr (ANSFM_MERGE_EXIT_FORM == 1) merge_pass_upfront<NP>(R, x);
+        else merge_pass_exit<1, NP>(R, x);
+    } else {
     // 3. finish the insertion: every max first, then every min -- no result is consumed by a neighbouring instruction
     //    (6.40 -> 6.32 ms against blocks of 6, same box)
     constexpr int kBlk = NP;
@@ -288,6 +424,7 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
             if (k0 + j < NP - 1) asm("v_min_f64 %0, %1, %2" : "=v"(R[k0 + j]) : "v"(mk[j]), "v"(R[k0 + j + 1]));
     }
     asm("v_max_f64 %0, %1, %2" : "=v"(R[NP - 1]) : "v"(x), "v"(R[NP - 1]));
+    }
     }
     // 4. rank walk on the element just consumed
     bool cross;
@@ -317,16 +454,16 @@ template <int NP, int NR, bool W32, bool SORTED, bool NODIV, int OPT = 0>
 __device__ __forceinline__ void merge_peel(double (&R)[NR], MergeElem &e0, MergeElem &e1, WalkState &ws, int G,
                                            int lane, const double *A, const double *B, const double *DG,
                                            const double *GORD, double *rec, const unsigned char *PA,
-                                           const unsigned char *PB)
+                                           const unsigned char *PB, const MergeOrient &mo = MergeOrient{})
 {
     if constexpr (NP >= 1) {
         if (NP < G) {
             if constexpr (((NR - NP) & 1) != 0)
-                merge_step<NR, W32, false, SORTED, NODIV, NP, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                merge_step<NR, W32, false, SORTED, NODIV, NP, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
             else
-                merge_step<NR, W32, false, SORTED, NODIV, NP, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                merge_step<NR, W32, false, SORTED, NODIV, NP, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
         }
-        merge_peel<NP - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+        merge_peel<NP - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB, mo);
     }
 }
 
@@ -335,6 +472,29 @@ __device__ __forceinline__ void merge_peel(double (&R)[NR], MergeElem &e0, Merge
 // rounding has swapped can fall on either side of a key boundary (seen with k(g) flat to 1e-9: an unsorted list loses an
 // entry in the insertion network and a sentinel is consumed).  So the keys are checked, and when some lane's are not
 // ascending the heads are put in order one by one (the merge itself only needs every ROW ascending, i.e. b sorted).
+// (the same check and reorder for the oriented heads below; merge_init keeps its own copy, so that the instantiations without
+// kOptOrient are compiled from the text they always had)
+template <int NR>
+__device__ __forceinline__ void merge_init_order(double (&R)[NR], int G, double huge)
+{
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i + 1 < NR; ++i) bad |= (R[i + 1] < R[i]);
+    if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+        double T[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) { T[i] = R[i]; R[i] = huge; }
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (i < G) {
+                const double x = T[i];
+#pragma unroll
+                for (int k = NR - 1; k >= 1; --k) R[k] = fmin(fmax(x, R[k - 1]), R[k]);
+                R[0] = fmin(x, R[0]);
+            }
+        }
+    }
+}
 template <int NR>
 __device__ __forceinline__ void merge_init(double (&R)[NR], int G, int lane, const double *A, double b0, double huge)
 {
@@ -357,6 +517,18 @@ __device__ __forceinline__ void merge_init(double (&R)[NR], int G, int lane, con
             }
         }
     }
+}
+// kOptOrient: the heads of this lane's rows, the row index at this lane's bit offset (column 0 in either packing)
+template <int NR>
+__device__ __forceinline__ void merge_init(double (&R)[NR], int G, const MergeOrient &mo, double huge)
+{
+    const double c0 = lds_ld(mo.cbase);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(lds_ld(mo.rbase + (unsigned)(i < G ? i : 0) * 512u) + c0);
+        R[i] = (i < G) ? __longlong_as_double((long long)((b & ~0x7FFULL) | (unsigned long long)((unsigned)i << mo.rsh))) : huge;
+    }
+    merge_init_order<NR>(R, G, huge);
 }
 
 // Per-lane insertion sort of one LDS column (values ascending, stable) carrying the original index of every

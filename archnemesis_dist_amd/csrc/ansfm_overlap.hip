@@ -85,7 +85,7 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     // float64 weights keep the two-factor weight: the compiler contracts gd + DG[i] * DG[j] of the walk into one fma, which no
     // table of rounded products reproduces bit for bit (the float32 product is rounded before it is widened, so its table is exact)
     if (!ctx->delg_f32) opt &= ~kOptTable;
-    const size_t wave_bytes = (size_t)(2 * G + 1) * kWave * sizeof(double);
+    const size_t wave_bytes = (size_t)merge_wave_rows(G, opt) * kWave * sizeof(double);
     const size_t table_bytes = (size_t)(2 * kMaxG + 2) * sizeof(double) + kMaxG * sizeof(float);
     size_t lds = keys32 ? (size_t)overlap32_lds_bytes(G, ctx->delg_f32 != 0)
                         : wave_bytes + table_bytes + (sorted ? 0 : (size_t)2 * G * kWave);

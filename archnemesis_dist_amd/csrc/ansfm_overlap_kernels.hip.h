@@ -28,13 +28,14 @@ namespace ansfm {
 // OPT: the trims of the division-free fast path (kOptTable / kOptBfi / kOptLate, ansfm_merge64.hip.h).  With kOptTable the
 // launch is ONE BLOCK OF SEVERAL WAVES PER CU (as many as the LDS holds, blockDim.x / 64) that share DG / GORD and the weight
 // product table WT; rows, tile queue, bin records and the sentinel row stay per wave and there is no barrier after the one
-// that publishes the tables, so the waves run and leave independently as the one-wave blocks do.
+// that publishes the tables, so the waves run and leave independently as the one-wave blocks do.  With kOptOrient a wave's
+// rows are a[G], a "huge" row, b[G], a "huge" row (merge_wave_rows): column G of either operand is a sentinel.
 template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false, int OPT = 0>
 __global__ __launch_bounds__((OPT & kOptTable) != 0 ? kWave * kMaxBlockWaves : kWave) __attribute__((amdgpu_waves_per_eu(1, 2)))
 void k_ck_overlap(OverlapParams p)
 {
     static_assert(OPT == 0 || (SORTED && NODIV), "the trims of the fast path");
-    constexpr bool kTable = (OPT & kOptTable) != 0;
+    constexpr bool kTable = (OPT & kOptTable) != 0, kOrient = (OPT & kOptOrient) != 0;
     static_assert(!kTable || W32, "the weight table holds float32 products only (launch_overlap)");
     extern __shared__ double smem[];
     const int lane = kTable ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
@@ -55,9 +56,9 @@ void k_ck_overlap(OverlapParams p)
             if (row < G && col < G) w = (double)((float)p.del_g[row] * (float)p.del_g[col]);
             WT[idx] = w;
         }
-        A = WT + (G + 1) * 32 + (size_t)wv * (2 * G + 1) * kWave;
+        A = WT + (G + 1) * 32 + (size_t)wv * merge_wave_rows(G, OPT) * kWave;
     }
-    double *B = A + G * kWave;                   // G+1 rows
+    double *B = A + (kOrient ? G + 1 : G) * kWave;   // G+1 rows
     unsigned char *PA = reinterpret_cast<unsigned char *>(B + (G + 1) * kWave);   // SORTED = false only
     unsigned char *PB = PA + G * kWave;
     if (wv == 0 && lane < G) {
@@ -67,6 +68,7 @@ void k_ck_overlap(OverlapParams p)
     if (wv == 0 && lane < G + 2) GORD[lane] = p.g_ord[lane];
     const double HUGE_KEY = __longlong_as_double(0x7FE0000000000000LL);   // finite, above any optical depth
     B[G * kWave + lane] = HUGE_KEY;
+    if constexpr (kOrient) A[G * kWave + lane] = HUGE_KEY;
     __syncthreads();
     double wsum = 0.0;
     for (int g = 0; g < G; ++g) wsum += DG[g];
@@ -109,9 +111,24 @@ void k_ck_overlap(OverlapParams p)
             if (do_merge) {
                 // ---- sorted list of the G row heads (row i = a_i + b_j, j ascending) -------------
                 double R[NR];
-                merge_init<NR>(R, G, lane, A, B[lane], HUGE_KEY);
+                MergeOrient mo{};
+                if constexpr (kOrient) {
+                    // rows = the operand with the larger top ordinate; b can be the rows only where a ascends (MergeOrient)
+                    bool swapped = blast > alast;
+                    if (__builtin_amdgcn_ballot_w64(swapped) != 0) {
+                        double prev = A[lane];
+                        for (int g = 1; g < G; ++g) {
+                            const double v = A[g * kWave + lane];
+                            swapped &= (v >= prev);
+                            prev = v;
+                        }
+                    }
+                    mo = merge_orient(lds_addr(A + lane), lds_addr(B + lane), swapped);
+                    merge_init<NR>(R, G, mo, HUGE_KEY);
+                } else
+                    merge_init<NR>(R, G, lane, A, B[lane], HUGE_KEY);
                 MergeElem e0, e1;
-                merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB);
+                merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB, mo);
                 WalkState ws = walk_begin<(OPT & kOptLate) != 0>(GORD, lane);
                 if constexpr (NODIV) ws.roff = (unsigned)lane * 8u;
                 // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
@@ -119,23 +136,23 @@ void k_ck_overlap(OverlapParams p)
                 // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
                 constexpr int kPer = kMergeUnroll4 ? 4 : 2;
                 for (int n = nloop / kPer; n > 0; --n) {
-                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
-                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                     if constexpr (kMergeUnroll4) {
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                     }
                 }
                 if constexpr (kMergeUnroll4)
                     if ((nloop & 2) != 0) {
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                     }
                 if (kMergePeel || (nloop & 1) != 0)
-                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                 if constexpr (kMergePeel) {
                     if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
-                    merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB);
+                    merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB, mo);
                 }
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
