@@ -15,6 +15,8 @@
 //                      path-matrix build and its kernels
 //   ansfm_occultation.hip  solar occultation with gradients, the tangent paths mixed to the geometries on the device: the
 //                      entry point, its compressed matrices and its kernels
+//   ansfm_limb.hip     limb thermal emission with gradients, the tangent paths mixed to the geometries on the device: the
+//                      entry point, its index arrays and its kernels
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -152,6 +154,13 @@ struct ansfm_ctx {
     size_t occ_scratch_bytes = 0;
     int occ_recorded = 0;
     hipEvent_t occ_ev[3] = {nullptr, nullptr, nullptr};
+    // limb emission (ansfm_cirsradg_ck_limb): the Planck tables [2][NT][Wpad] + spec [P][G][Wpad] + dg E [Q][L][G][Wpad] + the
+    // partial sums of Z [GS][Q][L][Wpad] + MOD [W][Q] + SPEC [W][P]; their bytes in the last call; events around k_limb_planck
+    // with k_limb_sens and around k_limb_grad (created at the first call)
+    DevBuf limb_ws;
+    size_t limb_scratch_bytes = 0;
+    int limb_recorded = 0;
+    hipEvent_t limb_ev[3] = {nullptr, nullptr, nullptr};
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;
@@ -169,6 +178,7 @@ struct ansfm_ctx {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : transit_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : occ_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : limb_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
     }

@@ -1,6 +1,7 @@
 // ansfm_grad_slots.hip.h -- how the g-contracted derivative of a layer's total opacity with respect to one parameter of
 // dSPECOUT is put together (ForwardModel_0.py:3868-3872, :3989): the one device function the gradient kernels of
-// ansfm_rt_kernels.hip.h, ansfm_transit_kernels.hip.h and ansfm_occultation_kernels.hip.h share.  No kernel here.
+// ansfm_rt_kernels.hip.h, ansfm_transit_kernels.hip.h, ansfm_occultation_kernels.hip.h and ansfm_limb_kernels.hip.h share.  No
+// kernel here.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -609,6 +609,76 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_occultation_last(self._ctx, C.byref(info)), "occultation_last")
         return int(info[0]), info[1], info[2]
 
+    def cirsradg_ck_limb(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
+                         EMTEMP, mix, xfac=None, gradients_on_device=False, dtau_every_gas=None):
+        """Limb thermal emission with analytic gradients of one model (nemesisLfmg :1372-1521), the limb paths mixed to the
+        geometries on the device: MOD (W, Q) = xfac * SPEC @ C.T, SPEC (W, P) the path radiances before xfac, and
+        dMOD (W, NPAR, L, Q) = d MOD / d (layer property), in the layout of the reference's dSPECOUT with the layers in place of
+        the path entries and the geometries in place of the paths; dTAUTOT assembled as in `cirsradg_ck_thermal`.  EMTEMP
+        (LIMAX, P) as SCALE; mix, xfac, gradients_on_device and dtau_every_gas as `cirsradg_ck_occultation` takes them
+        (`limb.tangent_mix`); xfac (W,) the factor of :4158-4168 or None.  dMOD takes 8 W NPAR L Q bytes on the device.
+        NotImplementedError above 160 layers, for a path that ends at the lower boundary (limb paths only), or when dMOD or the
+        scratch cannot be reserved."""
+        W, G, NP, NT, S = self.dims
+        lp = _np(lay_press_pa)
+        if lp.ndim != 1:
+            raise ValueError("cirsradg_ck_limb: one model, lay_press_pa (NLAY,)")
+        L = lp.shape[0]
+        lt = _np(lay_temp).reshape(L)
+        am = _np(amount).reshape(S, L)
+        tc = None if taucont is None else _np(taucont).reshape(W, L)
+        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, NPAR, L)
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        SC = _np(SCALE).reshape(LIMAX, P)
+        ET = _np(EMTEMP).reshape(LIMAX, P)
+        if NLAYIN.shape != (P,):
+            raise ValueError("cirsradg_ck_limb: NLAYIN must be (NPATH,)")
+        if isinstance(mix, tuple):
+            mptr, mpath, mval = _np(mix[0], np.int32), _np(mix[1], np.int32).reshape(-1), _np(mix[2]).reshape(-1)
+            if mptr.ndim != 1 or mptr.size < 2 or mpath.size != mval.size or mptr[-1] != mpath.size:
+                raise ValueError("cirsradg_ck_limb: mix must be (ptr (Q + 1,), path (nnz,), val (nnz,)) with ptr[-1] = nnz")
+        else:
+            Cm = _np(mix)
+            if Cm.ndim != 2 or Cm.shape[1] != P or Cm.shape[0] < 1:
+                raise ValueError("cirsradg_ck_limb: a dense mix must be (NGEOM, NPATH)")
+            nz = Cm != 0.0
+            mptr = _np(np.concatenate([[0], np.cumsum(nz.sum(axis=1))]), np.int32)
+            mpath = _np(np.nonzero(nz)[1], np.int32)
+            mval = _np(Cm[nz])
+        Q = mptr.size - 1
+        xf = None if xfac is None else _np(xfac).reshape(W)
+        ig = _np(igas_map, np.int32)
+        if dtau_every_gas is not None:
+            dg = _np(dtau_every_gas)
+            if dg.shape != (W, L):
+                raise ValueError("cirsradg_ck_limb: dtau_every_gas must be (NWAVE, NLAY)")
+            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
+        mod = np.empty((W, Q)); spec = np.empty((W, P))
+        dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
+        self._chain_dspec = None
+        try:
+            rc = self._lib.ansfm_cirsradg_ck_limb(
+                self._ctx, int(ISPACE), L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
+                _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf), _ptr(mod),
+                _ptr(spec), _ptr(dmod))
+        finally:
+            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
+                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
+        self._check(rc, "cirsradg_ck_limb")
+        if gradients_on_device:
+            self._chain_dspec = ("device", W, int(NPAR), L, Q)
+        return mod, spec, dmod
+
+    def limb_last(self):
+        """(scratch bytes beyond the gas stage and dMOD, k_limb_planck + k_limb_sens ms, k_limb_grad ms) of the last
+        cirsradg_ck_limb call"""
+        info = (C.c_double * 3)()
+        self._check(self._lib.ansfm_limb_last(self._ctx, C.byref(info)), "limb_last")
+        return int(info[0]), info[1], info[2]
+
     def cirsradg_ck_thermal(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
                             NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None, gradients_on_device=False,
                             dtau_every_gas=None):

@@ -30,6 +30,7 @@ IMOD_ABSORBTION = 4096
 IFORM_FLUXRATIO = 1                    # SpectraUnitEnum.FluxRatio
 IFORM_TRANSIT_DEPTH = 2                # SpectraUnitEnum.TransitDepth
 IFORM_ATMOSPHERIC_TRANSMISSION = 4     # SpectraUnitEnum.Atmospheric_transmission
+IFORM_INTEGRATED_RADIANCE = 6          # SpectraUnitEnum.Integrated_radiance
 ATM_TO_PASCAL = 101325.0               # ForwardModel_0.py:61
 SQ_CM_TO_SQ_METER = 1.0e-4             # ForwardModel_0.py:66
 
@@ -733,6 +734,93 @@ class CIRSradGPU:
             SPECONV, dSPECONV = M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
         dSPECONV = self.subspeconv(S.WAVE, SPECMOD, dSPECONV)                   # :1244
         SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1247
+        return SPECONV, dSPECONV
+
+    # ---- limb thermal emission with gradients: the tangent paths mixed to the geometries on the device ---------------
+    def nemesisLfmg(self):
+        """nemesisLfmg (ForwardModel_0.py:1372-1521).  The reference asks CIRSrad for dSPECOUT (NWAVE, NPAR, LIMAX, NPATH) of
+        the thermal-emission branch, maps it to the state vector path by path and only then interpolates the paths to the
+        tangent heights of the measurement (:1475-1496); every step after the radiative transfer is linear, so here ONE
+        `AnsfmEngine.cirsradg_ck_limb` call applies the interpolation first (`limb.tangent_mix`) and map2pro / map2xvec run on
+        that (NWAVE, NPAR, NLAY, NGEOM) array on the device.  The same steps as the reference's otherwise.  Its own method,
+        whose CIRSrad(return_grad=True) is the seam above, takes over for a Telluric object, runtime line-by-line, a case
+        CIRSrad would delegate, a path calculation that is not thermal emission, a path that ends at the lower boundary, an
+        engine without the call and one that refuses it."""
+        from copy import deepcopy
+        if getattr(self, "Telluric", None) is not None:
+            return super().nemesisLfmg()
+        eng = get_engine(self.ansfm_device)
+        if not hasattr(eng, "cirsradg_ck_limb"):
+            return super().nemesisLfmg()
+        from . import limb as _limb
+        self.Variables1 = deepcopy(self.Variables)                              # :1413-1421
+        self.MeasurementX = deepcopy(self.Measurement)
+        self.AtmosphereX = deepcopy(self.Atmosphere)
+        self.ScatterX = deepcopy(self.Scatter)
+        self.StellarX = deepcopy(self.Stellar)
+        self.SurfaceX = deepcopy(self.Surface)
+        self.LayerX = deepcopy(self.Layer)
+        self.SpectroscopyX = deepcopy(self.Spectroscopy)
+        self.CIAX = deepcopy(self.CIA)
+        self.check_gas_spec_atm()                                               # :1425-1426
+        self.check_wave_range_consistency()
+        self.Measurement.build_ils(IGEOM=0)                                     # :1429-1434
+        wavecalc_min, wavecalc_max = self.Measurement.calc_wave_range(apply_doppler=True, IGEOM=None)
+        if self.SpectroscopyX.NGAS > 0:
+            self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
+        self.adjust_hydrostat = False
+        xmap = self.subprofretg()
+        self.calc_pathg_L()
+        S, L, P, A, M = self.SpectroscopyX, self.LayerX, self.PathX, self.AtmosphereX, self.MeasurementX
+        imod = np.unique(np.asarray(P.IMOD).astype(int))
+        if (not self._ansfm_supported(True) or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)
+                or self._ansfm_transmission_branch(int(imod[0])) or (int(imod[0]) & IMOD_ABSORBTION)
+                or not (int(imod[0]) & IMOD_THERMAL_EMISSION)):                 # dispatch order :4478-4489
+            return super().nemesisLfmg()
+        NPATH = int(P.NPATH)
+        NLAYIN = np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH)
+        LAYINC = np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH)
+        SCALE = np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH)
+        EMTEMP = np.asarray(P.EMTEMP, dtype=np.float64).reshape(-1, NPATH)
+        press = np.asarray(L.PRESS, dtype=np.float64)
+        BASEH_TANHE = _limb.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)        # :1444-1446
+        mix = _limb.tangent_mix(BASEH_TANHE, M.TANHE)                           # :1475-1496
+        NGEOM = int(M.NGEOM)
+        self._ansfm_upload_table(eng)
+        TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(True)
+        taucont = TAUCIA + TAUDUST + TAURAY                                     # :3989
+        f_gas = self._ansfm_layer_inputs()
+        xf, _ = self._ansfm_units_and_surface()                                 # :4158-4168
+        NVMR, NDUST, NPRO, NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
+        NPAR = NVMR + 2 + int(self.ScatterX.NDUST)
+        igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
+        try:
+            MOD, SPECOUT, _ = eng.cirsradg_ck_limb(int(M.ISPACE), press, np.asarray(L.TEMP, dtype=np.float64), f_gas, taucont, dTAUCON,
+                                                   NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE, EMTEMP, mix=mix, xfac=xf,
+                                                   gradients_on_device=True)
+        except NotImplementedError:                 # more layers than the fused call takes, a path that ends at the lower boundary
+            #                                         (:6479-6483: the engine makes that test), or no room for dMOD or the scratch
+            _note("nemesisLfmg: the fused limb call refused the case (layers, a path to the lower boundary, the size of dMOD or of "
+                  "the scratch); the reference's method runs over CIRSrad(return_grad=True) instead")
+            return super().nemesisLfmg()
+        _route("nemesisLfmg: tangent paths mixed to the geometries on the device")
+        if self.ansfm_keep_side_products:
+            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
+            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, TAUCIA, TAUDUST, TAURAY)
+        incpar = [i for i in range(NVMR + 2 + NDUST) if np.mean(xmap[:, i, :]) != 0.0]   # :1457-1460
+        eng.map2pro(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, np.array([NLAY] * NGEOM), np.tile(np.arange(NLAY)[:, None], (1, NGEOM)),
+                    L.DTE, L.DAM, L.DCO, INCPAR=incpar, to_host=False)
+        dSPECMOD = eng.map2xvec(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, self.Variables.NX, xmap)      # (NWAVE, NGEOM, NX)
+        SPECMOD = np.array(MOD)
+        if int(M.IFORM) == IFORM_INTEGRATED_RADIANCE:                           # :1500-1504
+            SPECONV, dSPECONV = M.integrate_filterg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        else:
+            if int(S.ILBL) == ILBL_K_TABLES:                                    # :1510-1513
+                SPECONV, dSPECONV = M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+            else:
+                SPECONV, dSPECONV = M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+            dSPECONV = self.subspeconv(S.WAVE, SPECMOD, dSPECONV)               # :1516
+        SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1519
         return SPECONV, dSPECONV
 
 

@@ -316,6 +316,41 @@ int ansfm_cirsradg_ck_occultation(ansfm_ctx *ctx, int L, const double *lay_press
                                   double *MOD, double *TRANS, double *dMOD);
 int ansfm_occultation_last(const ansfm_ctx *ctx, double info[3]);
 
+/* Limb thermal emission with analytic gradients of ONE model (nemesisLfmg, ForwardModel_0.py:1372-1521): the limb paths are mixed
+ * to the Q geometries of the measurement on the device -- the interpolation to the tangent heights (:1475-1496) as a sparse matrix
+ * C (Q, P), rows mix_ptr[q] .. mix_ptr[q + 1] of (mix_path, mix_val) -- instead of through dSPECOUT (W, NPAR, LIMAX, P).  All
+ * pointers are host pointers.  Path p has the entries j < NLAYIN[p] (padding beyond is never read) with l_j = LAYINC[j][p],
+ * s_j = SCALE[j][p], B and dB/dT the Planck function of :6274-6281 at EMTEMP[j][p] in the units of ISPACE (0 wavenumber, 1
+ * wavelength), xfac[W] the factor of :4158-4168 (NULL: 1):
+ *   tau_j[w][g] = s_j (TAUGAS[w][g][l_j] + taucont[w][l_j])      T_-1 = 1, T_j = T_{j-1} exp(-tau_j)
+ *   spec[w][g][p] = sum_j (T_{j-1} - T_j) B_j                     SPEC[w][p] = sum_g DELG[g] spec[w][g][p]
+ *   MOD[w][q] = xfac[w] sum_p C[q][p] SPEC[w][p]
+ *   A_j = T_j B_j - sum_{m > j} (T_{m-1} - T_m) B_m               E[w][g][l][q] = sum_p C[q][p] sum_{j: l_j = l} s_j A_j
+ *   Z[w][l][q] = sum_g DELG[g] sum_p C[q][p] sum_{j: l_j = l} (T_{j-1} - T_j) dB/dT_j
+ *   dMOD[w][k][l][q] = xfac[w] (sum_g DELG[g] E[w][g][l][q] dTAUTOT[w][g][k][l] + [k == NVMR] Z[w][l][q])
+ * with dTAUTOT assembled as in ansfm_cirsradg_ck_thermal before its x SCALE (gas slots x 1e-4 through igas_map, temperature slot
+ * at NVMR, dtaucon, a pending ansfm_set_shared_gas_gradient, ansfm_set_gradient_gases honoured).  dMOD has the layout of the
+ * reference's dSPECOUT with LIMAX -> L and NPATH -> Q; nan_to_num (:4507) acts on each dMOD element (the reference applies it per
+ * path entry; the two agree whenever its dSPECOUT is finite).  A geometry with an empty row gives zeros.  SPEC[W][P] and
+ * dMOD[W][NPAR][L][Q] may be NULL; dMOD always stays on the device as a (W, NPAR, L, Q) result for ansfm_map2pro(dSPECIN = NULL)
+ * with NLAYIN = L and LAYINC = 0 .. L - 1 for every geometry.  Limb paths only: a path whose last layer lies at a higher pressure
+ * than its middle one (the lower boundary would contribute, :6479-6496) is ANSFM_ERR_UNSUPPORTED, so that the caller can take the
+ * un-collapsed route; so are more than 160 layers (two 64-lane LDS rows per layer, 160 KiB) and a dMOD (8 W NPAR L Q bytes, held
+ * as a whole) or a scratch that cannot be reserved.  Device scratch beyond the gas stage and dMOD is 8 Wpad (Q L (G + min(G, 4)) +
+ * P G + 2 NT) bytes, NT the number of bit-distinct EMTEMP values, plus MOD and SPEC.  That is less than the 8 W NPAR LIMAX P bytes of
+ * the dSPECOUT the call replaces where NPAR LIMAX P W exceeds (G + 4) Q L Wpad or so (W 1024, G 20, L 100, P 20, LIMAX 200,
+ * NPAR 10, Q 10: 202 MB against 328 MB); it is not for a handful of wavenumbers (Wpad pads W to a multiple of 64) or few parameters,
+ * and the entry does not refuse such shapes.  ANSFM_ERR_INVALID for NLAYIN[p] > LIMAX, a
+ * LAYINC[j][p], j < NLAYIN[p], outside 0 .. L - 1, a mix_ptr that does not start at 0 or decreases, a mix_path outside
+ * 0 .. P - 1.  ansfm_limb_last: info[0] the bytes of that scratch in the last call, info[1] / info[2] the milliseconds of
+ * k_limb_planck with k_limb_sens / of k_limb_grad. */
+int ansfm_cirsradg_ck_limb(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
+                           const double *taucont, const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int P, int LIMAX,
+                           const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP, int Q,
+                           const int32_t *mix_ptr, const int32_t *mix_path, const double *mix_val, const double *xfac, double *MOD,
+                           double *SPEC, double *dMOD);
+int ansfm_limb_last(const ansfm_ctx *ctx, double info[3]);
+
 /* ---- analytic-gradient seams ---------------------------------------------------------------
  * ForwardModel_0.k_overlapg (ForwardModel_0.py:5842): + dkdT[W][G][L][S] -> tau[W][G][L],
  * dk[W][G][L][S+1] (slots 0..S-1 = d tau/d amount_gas, slot S = d tau/dT). */

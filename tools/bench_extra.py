@@ -48,6 +48,8 @@ def main():
         bench_transit(eng, out)
     if only == "so":                                        # 0.33 GB dSPECOUT on the host for the un-collapsed route: on request only
         bench_so(eng, out)
+    if only == "limb":                                      # 0.33 GB dSPECOUT on the device for the un-collapsed route: on request only
+        bench_limb(eng, out)
     if only == "ss":                                        # 10 GB of host arrays: on request only
         bench_ss(eng, out, rng)
     print(json.dumps(out, indent=1))
@@ -539,6 +541,74 @@ def bench_so(eng, out, W=1024, n=5):
                dSPECOUT_bytes=8 * W * NPAR * int(LAYINC.shape[0]) * int(P), uncollapsed_wall_s=float(np.median(tu)),
                uncollapsed_overlapg_kernel_ms=float(np.median(ku)))
     out["occultation_C2_W%d" % W] = res
+
+
+def bench_limb(eng, out, W=1024, n=5):
+    """nemesisLfmg at the C2 atmosphere as a limb observation, at the shape of the `so` mode (G = 20, S = 8, L = 100, Q = 10 tangent
+    heights on the P = 20 limb paths that bracket them, LIMAX = 200, NPAR = 10, NPRO = 100, NX = 200, EMTEMP the layers'
+    temperatures): the fused call + map2pro + map2xvec on (W, NPAR, L, Q) beside the un-collapsed device route --
+    cirsradg_ck_thermal with dSPECOUT left on the device, map2pro and map2xvec on (W, NPAR, LIMAX, P), the mix of the paths on
+    the host -- alternated in one process, medians (and extremes) of n after one warm-up each.  `limb <W>`: another width."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import occultation_cases as oc
+    from archnemesis_dist_amd import limb
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    G, S, L, Q, NP, NT, NPRO, NX = 20, 8, 100, 10, 20, 15, 100, 200
+    _, delg = syn.gauss_legendre_01(G, True)
+    PRESS, TEMP, K = syn.synth_ktable(W, G, NP, NT, S)
+    eng.upload_ktable(K, PRESS, TEMP, 200.0 + 0.1 * np.arange(W), delg); del K
+    atm = syn.synth_atmosphere(L, S)
+    rng = np.random.default_rng(4)
+    NLAYIN, LAYINC, SCALE, bottoms = oc.occultation_paths(L, Q, rng)
+    SCALE = SCALE / 30.0
+    BASEH = np.linspace(0.0, 4.0e5, L)
+    tan = limb.tangent_heights_km(BASEH, NLAYIN, LAYINC)
+    TANHE = 0.5 * (tan[0::2] + tan[1::2]) + rng.uniform(-0.4, 0.4, Q) * (tan[1::2] - tan[0::2])
+    C = limb.tangent_mix(tan, TANHE)
+    P = NLAYIN.size
+    NVMR, NDUST = S, 0
+    NPAR = NVMR + 2 + NDUST
+    ig = np.arange(S, dtype=np.int32)
+    DTE, DAM, DCO = (rng.uniform(0, 1, (L, NPRO)) for _ in range(3))
+    xmap = rng.normal(size=(NX, NPAR, NPRO))
+    lp, lt, am = atm["lay_press_pa"][0], atm["lay_temp"][0], atm["amount"][0]
+    EMTEMP = np.where(np.arange(LAYINC.shape[0])[:, None] < NLAYIN[None, :], lt[LAYINC], 0.0)
+    nlay_q, layinc_q = np.array([L] * Q), np.ascontiguousarray(np.tile(np.arange(L)[:, None], (1, Q)))
+
+    def fused():
+        MOD, _, _ = eng.cirsradg_ck_limb(0, lp, lt, am, None, None, NVMR, NPAR, ig, NLAYIN, LAYINC, SCALE, EMTEMP, C,
+                                         gradients_on_device=True)
+        eng.map2pro(None, W, NVMR, NDUST, NPRO, Q, nlay_q, layinc_q, DTE, DAM, DCO, to_host=False)
+        return MOD, eng.map2xvec(None, W, NVMR, NDUST, NPRO, Q, NX, xmap)
+
+    def uncollapsed():
+        SPECOUT, _, _ = eng.cirsradg_ck_thermal(0, lp, lt, am, None, None, NVMR, NPAR, ig, NLAYIN, LAYINC, SCALE, EMTEMP, -1.0,
+                                                gradients_on_device=True)
+        eng.map2pro(None, W, NVMR, NDUST, NPRO, P, NLAYIN, LAYINC, DTE, DAM, DCO, to_host=False)
+        d = eng.map2xvec(None, W, NVMR, NDUST, NPRO, P, NX, xmap)                    # (W, P, NX)
+        return SPECOUT @ C.T, np.einsum("wpx,qp->wqx", d, C)
+
+    res = {"W": W, "G": G, "S": S, "L": L, "Q": Q, "P": int(P), "LIMAX": int(LAYINC.shape[0]), "NPAR": NPAR, "NPRO": NPRO, "NX": NX,
+           "median_of": n, "entries_per_row_of_C": [int(v) for v in np.unique((C != 0).sum(axis=1))]}
+    a, b = fused(), uncollapsed()
+    res["spectrum_max_rel_diff"] = float(np.max(np.abs(a[0] / b[0] - 1.0)))
+    res["gradient_max_diff_over_max"] = float(np.max(np.abs(a[1] - b[1])) / np.max(np.abs(b[1])))
+    tf, tu, kf, ku, rf, ru = [], [], [], [], [], []
+    for _ in range(n):
+        t = time.perf_counter(); fused(); tf.append(time.perf_counter() - t)
+        k = eng.last_kernel_ms(); kf.append(k["overlap_ms"]); rf.append(k["rt_ms"])
+        t = time.perf_counter(); uncollapsed(); tu.append(time.perf_counter() - t)
+        k = eng.last_kernel_ms(); ku.append(k["overlap_ms"]); ru.append(k["rt_ms"])
+    fused()
+    scratch, ms_sens, ms_grad = eng.limb_last()
+    res.update(fused_wall_s=float(np.median(tf)), fused_wall_s_min_max=[float(min(tf)), float(max(tf))],
+               fused_overlapg_kernel_ms=float(np.median(kf)), fused_rt_ms=float(np.median(rf)), k_limb_planck_and_sens_ms=ms_sens,
+               k_limb_grad_ms=ms_grad, limb_scratch_bytes=scratch, dMOD_bytes=8 * W * NPAR * L * Q,
+               dSPECOUT_bytes=8 * W * NPAR * int(LAYINC.shape[0]) * int(P), uncollapsed_wall_s=float(np.median(tu)),
+               uncollapsed_wall_s_min_max=[float(min(tu)), float(max(tu))], uncollapsed_overlapg_kernel_ms=float(np.median(ku)),
+               uncollapsed_rt_ms=float(np.median(ru)))
+    out["limb_C2_W%d" % W] = res
 
 
 def bench_layer(eng, out):
