@@ -11,12 +11,11 @@
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
-//   ansfm_transit.hip  primary-transit depth with gradients, collapsed over paths on the device: the entry point, its
-//                      path-matrix build and its kernels
-//   ansfm_occultation.hip  solar occultation with gradients, the tangent paths mixed to the geometries on the device: the
-//                      entry point, its compressed matrices and its kernels
-//   ansfm_limb.hip     limb thermal emission with gradients, the tangent paths mixed to the geometries on the device: the
-//                      entry point, its index arrays and its kernels
+//   ansfm_transit.hip, ansfm_occultation.hip, ansfm_limb.hip  the fused gradient routes, collapsed over the paths (transit) or
+//                      with the tangent paths mixed to the geometries (occultation, limb) on the device: each its entry point,
+//                      its index and matrix build, its scratch layout and its launcher.  What they share is in
+//                      ansfm_pathmix.hip.h (host: checks, path matrix, prologue, staged call, *_last) and
+//                      ansfm_pathmix_kernels.hip.h (device functions: path pass, contraction, sums over g)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -70,9 +69,19 @@ struct LblrtIso {
     DevBuf bins;
 };
 
+// What a fused gradient route (transit, occultation, limb) keeps between calls: its scratch beyond the gas stage, the bytes of
+// it the last call needed, whether a call is recorded, and the events around its two kernel stages (created at the first call)
+struct FusedRoute {
+    DevBuf ws;
+    size_t scratch_bytes = 0;
+    int recorded = 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
 }  // namespace ansfm
 
 using ansfm::DevBuf;
+using ansfm::FusedRoute;
 using ansfm::LblrtIso;
 
 struct ansfm_ctx {
@@ -142,25 +151,12 @@ struct ansfm_ctx {
     // surface reflection (ansfm_surface_brdf, ansfm_brdf_matrix): the result, the per-azimuth table, kernel time of the last call
     DevBuf brdf_out, brdf_azi;
     double brdf_ms = 0;
-    // primary transit (ansfm_cirsradg_ck_transit): A [L][G][Wpad] + exp(-tau_path) [P][G][Wpad]; the compressed path matrix; the
-    // bytes of the first the last call needed; events around k_transit_sens and k_transit_grad (created at the first call)
-    DevBuf transit_ws;
-    size_t transit_scratch_bytes = 0;
-    int transit_recorded = 0;
-    hipEvent_t transit_ev[3] = {nullptr, nullptr, nullptr};
-    // solar occultation (ansfm_cirsradg_ck_occultation): exp(-tau_path) [P][G][Wpad] + MOD [W][Q] + T [W][P]; their bytes in the
-    // last call; events around k_occ_paths and k_occ_grad (created at the first call)
-    DevBuf occ_ws;
-    size_t occ_scratch_bytes = 0;
-    int occ_recorded = 0;
-    hipEvent_t occ_ev[3] = {nullptr, nullptr, nullptr};
-    // limb emission (ansfm_cirsradg_ck_limb): the Planck tables [2][NT][Wpad] + spec [P][G][Wpad] + dg E [Q][L][G][Wpad] + the
-    // partial sums of Z [GS][Q][L][Wpad] + MOD [W][Q] + SPEC [W][P]; their bytes in the last call; events around k_limb_planck
-    // with k_limb_sens and around k_limb_grad (created at the first call)
-    DevBuf limb_ws;
-    size_t limb_scratch_bytes = 0;
-    int limb_recorded = 0;
-    hipEvent_t limb_ev[3] = {nullptr, nullptr, nullptr};
+    // the fused gradient routes; ws holds
+    //   transit (ansfm_cirsradg_ck_transit): A [L][G][Wpad] + exp(-tau_path) [P][G][Wpad] + AREA [W] + T [W][P]
+    //   occ (ansfm_cirsradg_ck_occultation): exp(-tau_path) [P][G][Wpad] + MOD [W][Q] + T [W][P]
+    //   limb (ansfm_cirsradg_ck_limb): the Planck tables [2][NT][Wpad] + spec [P][G][Wpad] + dg E [Q][L][G][Wpad] + the partial
+    //   sums of Z [GS][Q][L][Wpad] + MOD [W][Q] + SPEC [W][P]
+    FusedRoute transit, occ, limb;
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;
@@ -176,9 +172,8 @@ struct ansfm_ctx {
     ~ansfm_ctx()
     {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : transit_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : occ_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : limb_ev) if (e) (void)hipEventDestroy(e);
+        for (FusedRoute *r : {&transit, &occ, &limb})
+            for (hipEvent_t e : r->ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
     }

@@ -1,7 +1,7 @@
-// ansfm_grad_slots.hip.h -- how the g-contracted derivative of a layer's total opacity with respect to one parameter of
-// dSPECOUT is put together (ForwardModel_0.py:3868-3872, :3989): the one device function the gradient kernels of
-// ansfm_rt_kernels.hip.h, ansfm_transit_kernels.hip.h, ansfm_occultation_kernels.hip.h and ansfm_limb_kernels.hip.h share.  No
-// kernel here.
+// ansfm_grad_slots.hip.h -- the device functions the gradient kernels of ansfm_rt_kernels.hip.h, ansfm_transit_kernels.hip.h,
+// ansfm_occultation_kernels.hip.h and ansfm_limb_kernels.hip.h share: how the g-contracted derivative of a layer's total
+// opacity with respect to one parameter of dSPECOUT is put together (ForwardModel_0.py:3868-3872, :3989), and the Planck
+// function with its temperature derivative (:6274-6281).  No kernel here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,20 @@ __device__ __forceinline__ double dtau_param_gsum(int slot, double ys, double Xs
     if (dcont) v += dcont[((m * NPAR + kpar) * L + lay) * Wpad + nu] * Xs;
     if (dcont_gas && kpar < NVMR) v += dcont_gas[(size_t)lay * Wpad + nu] * Xs;
     return v;
+}
+
+// B and dB/dT of the Planck function at y (wavenumber, or wavelength when ispace != 0) and temperature T
+// (ForwardModel_0.py:6274-6281), for k_thermal_rtg, the gradient seam and k_limb_planck
+__device__ __forceinline__ void planckg_dev(int ispace, double y, double T, double &bb, double &dBdT)
+{
+    const double c1 = 1.1911e-12, c2 = 1.439;
+    double a, ap;
+    if (ispace == 0) { a = c1 * (y * y * y); ap = c1 * c2 * (y * y * y * y) / (T * T); }
+    else { a = c1 * (y * y * y * y * y) / 1.0e4; ap = c1 * c2 * (y * y * y * y * y * y) / 1.0e4 / (T * T); }
+    const double e = exp(c2 * y / T);
+    const double b = e - 1.0;
+    bb = a / b;
+    dBdT = e * ap / (b * b);
 }
 
 }  // namespace ansfm

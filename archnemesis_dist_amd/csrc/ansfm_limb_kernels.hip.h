@@ -35,27 +35,18 @@
 // a wave and its write and read.  The second pass repeats the first's operations in order, so its T_j are the first's bit for
 // bit.
 //
-// LDS budget of k_limb_grad, as k_occ_grad (ansfm_occultation_kernels.hip.h): a block of 4 waves serves one (tile, layer).  Its
-// LDS holds a chunk of SC slots of the layer's slab of dk, SC x G x 512 B, read from HBM once per block and shared by every
-// geometry, and one column set dg E [G][64] per wave, 4 x G x 512 B.  The block is held to 80 KiB so that two blocks are
-// resident per CU; the slot-chunk rule is the largest chunk that fits beside the columns, evened out over the chunks it takes
-// (G = 20, S = 8: 9 slots in 3 chunks of 3, 70 KiB a block).  Where 80 KiB hold no slot beside the columns the block takes up
-// to 160 KiB.  The contraction is k_occ_grad's restated, not shared: that kernel forms its columns from exp(-tau_path) inside
-// the loop and has no Z term, and its compiled code stays what it is.
+// The contraction of k_limb_grad and its block-row-0 sums are ansfm_pathmix_kernels.hip.h's, with their LDS budget; this header
+// binds them to the limb's columns and its Z term.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "ansfm_merge_common.hip.h"
-#include "ansfm_grad_slots.hip.h"
+#include "ansfm_pathmix_kernels.hip.h"
 #include "ansfm_rt_params.h"
 
 namespace ansfm {
 
-constexpr int kLimbWaves = 4;                       // waves of a k_limb_grad block
 constexpr int kLimbGroups = 4;                      // g-groups of k_limb_sens at most
 constexpr int kLimbMaxLayers = 160;                 // 2 L x 512 B of LDS in k_limb_sens
-constexpr size_t kLimbLdsTwoBlocks = 80 * 1024;     // LDS of a k_limb_grad block when two are to share a CU
-constexpr size_t kLimbLdsOneBlock = 160 * 1024;
 
 struct LimbParams {
     const double *tau;        // [L][G][Wpad]
@@ -92,27 +83,13 @@ struct LimbParams {
     signed char slot_of_param[kMaxPar];
 };
 
-// planckg_dev of ansfm_rt_kernels.hip.h (ForwardModel_0.py:6274-6281) restated operation for operation: that header defines
-// kernels and belongs to ansfm_rt.hip alone
-__device__ __forceinline__ void limb_planckg(int ispace, double y, double T, double &bb, double &dBdT)
-{
-    const double c1 = 1.1911e-12, c2 = 1.439;
-    double a, ap;
-    if (ispace == 0) { a = c1 * (y * y * y); ap = c1 * c2 * (y * y * y * y) / (T * T); }
-    else { a = c1 * (y * y * y * y * y) / 1.0e4; ap = c1 * c2 * (y * y * y * y * y * y) / 1.0e4 / (T * T); }
-    const double e = exp(c2 * y / T);
-    const double b = e - 1.0;
-    bb = a / b;
-    dBdT = e * ap / (b * b);
-}
-
 // grid (Wpad / 64, NT), block 64: B and dB/dT of distinct temperature t at every wavenumber (padding lanes: the last one's)
 __global__ __launch_bounds__(kWave) void k_limb_planck(LimbParams q)
 {
     const size_t nu = (size_t)blockIdx.x * kWave + threadIdx.x;
     const double wv = q.wave[nu < (size_t)q.W ? nu : (size_t)q.W - 1];
     double bb, dB;
-    limb_planckg(q.ispace, q.ispace == 0 ? wv : 1.0e4 / wv, q.tvals[blockIdx.y], bb, dB);
+    planckg_dev(q.ispace, q.ispace == 0 ? wv : 1.0e4 / wv, q.tvals[blockIdx.y], bb, dB);
     q.btab[(size_t)blockIdx.y * q.Wpad + nu] = bb;
     q.dbtab[(size_t)blockIdx.y * q.Wpad + nu] = dB;
 }
@@ -189,88 +166,35 @@ __global__ __launch_bounds__(kWave) void k_limb_sens(LimbParams q)
         if (q.hit[(size_t)l * Q + iq]) q.Zp[(((size_t)gs * Q + iq) * L + l) * q.Wpad + nu] = Zt[l * kWave];
 }
 
-// One block of kLimbWaves waves per (wavenumber tile, layer l); lanes run over wavenumbers.  The slots of the layer's slab of dk
-// are staged in LDS in chunks of q.SC (slots the gas selection leaves out are neither staged nor read).  The geometries that
-// have an entry in layer l are dealt to the waves in turn; for each of its geometries a wave copies dg E[g] into its own LDS
-// columns, with their sum over g for the continuum terms, contracts every parameter whose slot lies in the chunk against the
-// staged slab, goes through dtau_param_gsum, adds Z (the GS partial sums in order) at k == NVMR, multiplies by xfac and writes
-// dMOD[w][k][l][q].  Parameters without a slot are written with the first chunk.  A geometry without an entry in the layer
-// gets zeros without a read of E.  Block row 0 also writes SPEC[w][p] and MOD[w][q].
-// grid (Wpad / 64, L), block 256, LDS (SC + kLimbWaves) x G x 512 B.
-__global__ __launch_bounds__(kLimbWaves * kWave) void k_limb_grad(LimbParams q)
+// mix_contract with the columns dg E[g] copied from k_limb_sens's rows and the value finished as (v + Z at k == NVMR, the GS
+// partial sums in order) xfac; block row 0 also writes SPEC[w][p] and MOD[w][q].
+// grid (Wpad / 64, L), block 256, LDS (SC + kMixWaves) x G x 512 B.
+__global__ __launch_bounds__(kMixWaves * kWave) void k_limb_grad(LimbParams q)
 {
     extern __shared__ double lds[];
-    const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), l = blockIdx.y;
-    const int G = q.G, NP1 = q.NP1, Q = q.Q;
+    const int lane = threadIdx.x & (kWave - 1), l = blockIdx.y;
     const size_t nu = (size_t)blockIdx.x * kWave + lane;
-    const size_t GWp = (size_t)G * q.Wpad;
-    const bool live = nu < (size_t)q.W;
-    const double xf = live ? (q.xfac ? q.xfac[nu] : 1.0) : 0.0;
-    double *slab = lds, *wg = lds + (size_t)q.SC * G * kWave + (size_t)wave * G * kWave;
-    const double *dkl = q.dk + (size_t)l * NP1 * GWp + (size_t)blockIdx.x * kWave;
-    const int32_t *hit = q.hit + (size_t)l * Q;
-
-    for (int c0 = 0; c0 < NP1; c0 += q.SC) {
-        const int cn = min(q.SC, NP1 - c0);
-        if (c0) __syncthreads();                                   // every wave is done with the chunk before
-        for (int row = wave; row < cn * G; row += kLimbWaves) {     // row = (slot - c0) G + g: 512 B of dk each
-            const int s = c0 + row / G;
-            if ((q.gas_mask >> (s == NP1 - 1 ? 31 : s)) & 1u)
-                slab[row * kWave + lane] = dkl[((size_t)c0 * G + row) * q.Wpad + lane];
-        }
-        __syncthreads();
-        int n = 0;
-        for (int iq = 0; iq < Q; ++iq) {
-            if (!hit[iq]) {                                        // no path of this geometry crosses the layer
-                if (c0 == 0 && iq % kLimbWaves == wave && live)
-                    for (int kpar = 0; kpar < q.NPAR; ++kpar) q.dmod[((nu * q.NPAR + kpar) * q.L + l) * Q + iq] = 0.0;
-                continue;
-            }
-            if (n++ % kLimbWaves != wave) continue;
-            const double *El = q.E + (((size_t)iq * q.L + l) * G) * q.Wpad + nu;
-            double Xs = 0.0;
-            for (int g = 0; g < G; ++g) {
+    const double xf = mix_factor(q.xfac, nu, q.W);
+    const int32_t *hit = q.hit + (size_t)l * q.Q;
+    mix_contract(
+        q, lds, [&](int, int iq) { return hit[iq] != 0; },
+        [&](int iq, double *wg, double &Xs) {
+            const double *El = q.E + (((size_t)iq * q.L + l) * q.G) * q.Wpad + nu;
+            for (int g = 0; g < q.G; ++g) {
                 const double b = El[(size_t)g * q.Wpad];
                 wg[g * kWave + lane] = b;
                 Xs += b;
             }
-            for (int kpar = 0; kpar < q.NPAR; ++kpar) {
-                const int slot = q.slot_of_param[kpar];
-                if (slot < 0 ? c0 != 0 : (slot < c0 || slot >= c0 + cn)) continue;
-                double ys = 0.0;
-                if (slot >= 0) {
-                    const double *sl = slab + (size_t)(slot - c0) * G * kWave + lane;
-                    for (int g = 0; g < G; ++g) ys += wg[g * kWave + lane] * sl[g * kWave];
-                }
-                double v = dtau_param_gsum(slot, ys, Xs, NP1, q.dcont, q.dcont_gas, (size_t)0, q.NPAR, q.NVMR, kpar, q.L, l, q.Wpad,
-                                           (int)nu);
-                if (kpar == q.NVMR) {                              // :6467-6468
-                    double Z = 0.0;
-                    for (int gs = 0; gs < q.GS; ++gs) Z += q.Zp[(((size_t)gs * Q + iq) * q.L + l) * q.Wpad + nu];
-                    v += Z;
-                }
-                v *= xf;                                           // :4247
-                if (v != v) v = 0.0;                               // nan_to_num :4507
-                if (live) q.dmod[((nu * q.NPAR + kpar) * q.L + l) * Q + iq] = v;
+        },
+        [&](double v, int kpar, int iq) {
+            if (kpar == q.NVMR) {                                  // :6467-6468
+                double Z = 0.0;
+                for (int gs = 0; gs < q.GS; ++gs) Z += q.Zp[(((size_t)gs * q.Q + iq) * q.L + l) * q.Wpad + nu];
+                v += Z;
             }
-        }
-    }
-    if (l == 0) {
-        for (int p = wave; p < q.P; p += kLimbWaves) {
-            double s = 0.0;
-            for (int g = 0; g < G; ++g) s += q.delg[g] * q.spec[(size_t)p * GWp + (size_t)g * q.Wpad + nu];
-            if (live) q.specout[nu * q.P + p] = s;
-        }
-        for (int iq = wave; iq < Q; iq += kLimbWaves) {
-            double m = 0.0;
-            for (int i = q.mix_ptr[iq]; i < q.mix_ptr[iq + 1]; ++i) {
-                double s = 0.0;
-                for (int g = 0; g < G; ++g) s += q.delg[g] * q.spec[(size_t)q.mix_path[i] * GWp + (size_t)g * q.Wpad + nu];
-                m += q.mix_val[i] * s;
-            }
-            if (live) q.mod[nu * Q + iq] = xf * m;
-        }
-    }
+            return v * xf;                                         // :4247
+        });
+    if (l == 0) mix_path_sums(q, q.spec, xf, q.specout);
 }
 
 }  // namespace ansfm

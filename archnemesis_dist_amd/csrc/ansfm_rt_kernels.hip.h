@@ -320,19 +320,9 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
 //     out[k,m] = xfac * ( SCALE_m * ( fac_k * sum_g dg c_g dk[slot_k][g] + dcont_k * sum_g dg c_g )
 //                         + [k==NVMR] dBdT_m * sum_g dg (trold_m - tr_m)_g )
 // so neither dTAUTOT_LAYINC (W,G,NPAR,Li,P) nor dSPECOUT (W,G,NPAR,Li) is materialised.
-// Block = 64 wavenumbers x 4 g-groups; pass 1 stores trold_j per (g) to a workspace.
+// Block = 64 wavenumbers x 4 g-groups; pass 1 stores trold_j per (g) to a workspace.  B and dB/dT: planckg_dev of
+// ansfm_grad_slots.hip.h.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void planckg_dev(int ispace, double y, double T, double &bb, double &dBdT)
-{
-    const double c1 = 1.1911e-12, c2 = 1.439;
-    double a, ap;
-    if (ispace == 0) { a = c1 * (y * y * y); ap = c1 * c2 * (y * y * y * y) / (T * T); }
-    else { a = c1 * (y * y * y * y * y) / 1.0e4; ap = c1 * c2 * (y * y * y * y * y * y) / 1.0e4 / (T * T); }
-    const double e = exp(c2 * y / T);
-    const double b = e - 1.0;
-    bb = a / b;
-    dBdT = e * ap / (b * b);   // ForwardModel_0.py:6274-6281
-}
 
 // GY = g-groups (waves) per wavenumber tile: the kernel streams (S+1) gradient rows per layer and C2 has only 157 tiles,
 // so the launch picks the largest GY whose reduction buffer fits in LDS (16 up to S = 12).

@@ -11,32 +11,22 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "ansfm_merge_common.hip.h"
-#include "ansfm_grad_slots.hip.h"
+#include "ansfm_pathmix_kernels.hip.h"
 #include "ansfm_rt_params.h"
 
 namespace ansfm {
 
 // One wave per (wavenumber tile of 64, g).  The LDS tile [max(L, P)][64] holds the total opacity of every layer while the paths
-// are summed, then c_p exp(-tau_path) of every path while the layers are: each pass is a gather through one compressed form of
-// Sm, whose indices and values are uniform over the wave: the compiler fetches the indices with scalar loads and the values with
-// vector loads from a scalar base (one address for all lanes).  A lane touches its own column of the tile and its own elements of
-// tpart only, so no barrier is needed.  grid (Wpad / 64, G), block 64, LDS max(L, P) x 512 B.
+// are summed (path_pass), then c_p exp(-tau_path) of every path while the layers are: a gather through Sm compressed by layer,
+// whose indices and values are uniform over the wave as in the path pass.  A lane touches its own column of the tile and its own
+// elements of tpart only, so no barrier is needed.  grid (Wpad / 64, G), block 64, LDS max(L, P) x 512 B.
 __global__ __launch_bounds__(kWave) void k_transit_sens(TransitParams q)
 {
     extern __shared__ double tile[];
     const int lane = threadIdx.x, g = blockIdx.y, G = q.G;
     const size_t nu = (size_t)blockIdx.x * kWave + lane;      // < Wpad: every array read or written here is padded to it
     const size_t GWp = (size_t)G * q.Wpad, at = (size_t)g * q.Wpad + nu;
-    for (int l = 0; l < q.L; ++l)
-        tile[l * kWave + lane] = q.tau[(size_t)l * GWp + at] + (q.cont ? q.cont[(size_t)l * q.Wpad + nu] : 0.0);
-    for (int p = 0; p < q.P; ++p) {
-        const int i1 = q.col_ptr[p + 1];
-        double t = 0.0;
-#pragma unroll 4
-        for (int i = q.col_ptr[p]; i < i1; ++i) t += q.col_val[i] * tile[q.col_lay[i] * kWave + lane];
-        q.tpart[(size_t)p * GWp + at] = exp(-t);
-    }
+    path_pass(q, tile);
     for (int p = 0; p < q.P; ++p) tile[p * kWave + lane] = q.weight[p] * q.tpart[(size_t)p * GWp + at];
     for (int l = 0; l < q.L; ++l) {
         const int i1 = q.row_ptr[l + 1];

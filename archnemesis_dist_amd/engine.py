@@ -4,6 +4,7 @@ Host-array methods take/return NumPy arrays in the reference's layouts (drop-in 
 seams); `*_dev` methods take torch CUDA(HIP) tensors already resident in HBM and run
 asynchronously on the engine's stream.  torch is plumbing only (device memory, streams).
 """
+import contextlib
 import ctypes as C
 import os
 import numpy as np
@@ -485,20 +486,13 @@ class AnsfmEngine:
             self._chain_dspec = _fingerprint(dspec[0])
         return (spec[0], dspec[0]) if single else (spec, dspec)
 
-    def cirsradg_ck_transit(self, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
-                            path_weight, gradients_on_device=False, dtau_every_gas=None):
-        """Primary-transit depth with analytic gradients of one model (nemesisPTfm :1838-1995), collapsed over the limb paths
-        on the device: AREA (W,) = sum_p path_weight[p] (1 - TRANS[:, p]), TRANS (W, P) the path transmissions, and
-        dAREA (W, NPAR, L) = d AREA / d (layer property) with dTAUTOT assembled as in `cirsradg_ck_thermal`.  lay_press_pa,
-        lay_temp (L,), amount (NGAS, L), taucont (W, L) or None, dtaucon (W, NPAR, L) or None, NLAYIN (P,), LAYINC / SCALE
-        (LIMAX, P), path_weight (P,) the annulus weights c_p (`transit.path_weights`).  gradients_on_device=True: dAREA is not
-        copied to the host (None in its place) and `map2pro(None, ...)` with LAYINC = arange(L), NPATH = 1 continues from the
-        device copy; only this arms the chain -- after a call that returned dAREA, `map2pro(None, ...)` raises ValueError.  dtau_every_gas as in `cirsradg_ck_thermal`.  NotImplementedError above
-        320 layers or paths."""
+    def _one_model_layers(self, what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE):
+        """The layer and path arrays of a fused one-model call as the library takes them:
+        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC."""
         W, G, NP, NT, S = self.dims
         lp = _np(lay_press_pa)
         if lp.ndim != 1:
-            raise ValueError("cirsradg_ck_transit: one model, lay_press_pa (NLAY,)")
+            raise ValueError(what + ": one model, lay_press_pa (NLAY,)")
         L = lp.shape[0]
         lt = _np(lay_temp).reshape(L)
         am = _np(amount).reshape(S, L)
@@ -509,35 +503,77 @@ class AnsfmEngine:
             LAYINC = LAYINC[:, None]
         LIMAX, P = LAYINC.shape
         SC = _np(SCALE).reshape(LIMAX, P)
-        cw = _np(path_weight).reshape(P)
         if NLAYIN.shape != (P,):
-            raise ValueError("cirsradg_ck_transit: NLAYIN must be (NPATH,)")
+            raise ValueError(what + ": NLAYIN must be (NPATH,)")
+        return lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC
+
+    @staticmethod
+    def _mix_rows(what, mix, P):
+        """The mixing matrix C (Q, P), dense or a triple of compressed rows, as compressed rows: mptr, mpath, mval."""
+        if isinstance(mix, tuple):
+            mptr, mpath, mval = _np(mix[0], np.int32), _np(mix[1], np.int32).reshape(-1), _np(mix[2]).reshape(-1)
+            if mptr.ndim != 1 or mptr.size < 2 or mpath.size != mval.size or mptr[-1] != mpath.size:
+                raise ValueError(what + ": mix must be (ptr (Q + 1,), path (nnz,), val (nnz,)) with ptr[-1] = nnz")
+            return mptr, mpath, mval
+        Cm = _np(mix)
+        if Cm.ndim != 2 or Cm.shape[1] != P or Cm.shape[0] < 1:
+            raise ValueError(what + ": a dense mix must be (NGEOM, NPATH)")
+        nz = Cm != 0.0
+        return _np(np.concatenate([[0], np.cumsum(nz.sum(axis=1))]), np.int32), _np(np.nonzero(nz)[1], np.int32), _np(Cm[nz])
+
+    @contextlib.contextmanager
+    def _shared_gas_gradient(self, what, dtau_every_gas, L, n=1, only=""):
+        """Arms dtau_every_gas (W, L), or nothing for None, for the gradient call made inside the block: a successful call
+        consumes it, and leaving the block cancels it if the call failed before that."""
+        if dtau_every_gas is None:
+            yield
+            return
+        dg = _np(dtau_every_gas)
+        if n != 1 or dg.shape != (self.dims[0], L):
+            raise ValueError(what + ": dtau_every_gas must be (NWAVE, NLAY)" + only)
+        self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
+        try:
+            yield
+        finally:
+            self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
+
+    def _last3(self, fn, what):
+        info = (C.c_double * 3)()
+        self._check(fn(self._ctx, C.byref(info)), what)
+        return int(info[0]), info[1], info[2]
+
+    def cirsradg_ck_transit(self, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
+                            path_weight, gradients_on_device=False, dtau_every_gas=None):
+        """Primary-transit depth with analytic gradients of one model (nemesisPTfm :1838-1995), collapsed over the limb paths
+        on the device: AREA (W,) = sum_p path_weight[p] (1 - TRANS[:, p]), TRANS (W, P) the path transmissions, and
+        dAREA (W, NPAR, L) = d AREA / d (layer property) with dTAUTOT assembled as in `cirsradg_ck_thermal`.  lay_press_pa,
+        lay_temp (L,), amount (NGAS, L), taucont (W, L) or None, dtaucon (W, NPAR, L) or None, NLAYIN (P,), LAYINC / SCALE
+        (LIMAX, P), path_weight (P,) the annulus weights c_p (`transit.path_weights`).  gradients_on_device=True: dAREA is not
+        copied to the host (None in its place) and `map2pro(None, ...)` with LAYINC = arange(L), NPATH = 1 continues from the
+        device copy; only this arms the chain -- after a call that returned dAREA, `map2pro(None, ...)` raises ValueError.  dtau_every_gas as in `cirsradg_ck_thermal`.  NotImplementedError above
+        320 layers or paths."""
+        what = "cirsradg_ck_transit"
+        W = self.dims[0]
+        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC = self._one_model_layers(
+            what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE)
+        L = lp.shape[0]
+        cw = _np(path_weight).reshape(P)
         ig = _np(igas_map, np.int32)
-        if dtau_every_gas is not None:
-            dg = _np(dtau_every_gas)
-            if dg.shape != (W, L):
-                raise ValueError("cirsradg_ck_transit: dtau_every_gas must be (NWAVE, NLAY)")
-            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
         area = np.empty(W); trans = np.empty((W, P))
         darea = None if gradients_on_device else np.empty((W, int(NPAR), L))
-        self._chain_dspec = None
-        try:
+        with self._shared_gas_gradient(what, dtau_every_gas, L):
+            self._chain_dspec = None
             rc = self._lib.ansfm_cirsradg_ck_transit(
                 self._ctx, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
                 _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(cw), _ptr(area), _ptr(trans), _ptr(darea))
-        finally:
-            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
-                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
-        self._check(rc, "cirsradg_ck_transit")
+        self._check(rc, what)
         if gradients_on_device:
             self._chain_dspec = ("device", W, int(NPAR), L, 1)
         return area, trans, darea
 
     def transit_last(self):
         """(scratch bytes beyond the gas stage, k_transit_sens ms, k_transit_grad ms) of the last cirsradg_ck_transit call"""
-        info = (C.c_double * 3)()
-        self._check(self._lib.ansfm_transit_last(self._ctx, C.byref(info)), "transit_last")
-        return int(info[0]), info[1], info[2]
+        return self._last3(self._lib.ansfm_transit_last, "transit_last")
 
     def cirsradg_ck_occultation(self, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
                                 mix, xfac=None, gradients_on_device=False, dtau_every_gas=None):
@@ -551,63 +587,31 @@ class AnsfmEngine:
         `map2pro(None, ...)` with NPATH = Q, NLAYIN = [L] * Q, LAYINC[:, q] = arange(L) continues from the device copy; only this
         arms the chain.  dMOD takes 8 W NPAR L Q bytes on the device.  NotImplementedError above 320 layers or paths, or when
         dMOD cannot be reserved."""
-        W, G, NP, NT, S = self.dims
-        lp = _np(lay_press_pa)
-        if lp.ndim != 1:
-            raise ValueError("cirsradg_ck_occultation: one model, lay_press_pa (NLAY,)")
+        what = "cirsradg_ck_occultation"
+        W = self.dims[0]
+        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC = self._one_model_layers(
+            what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE)
         L = lp.shape[0]
-        lt = _np(lay_temp).reshape(L)
-        am = _np(amount).reshape(S, L)
-        tc = None if taucont is None else _np(taucont).reshape(W, L)
-        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, NPAR, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(SCALE).reshape(LIMAX, P)
-        if NLAYIN.shape != (P,):
-            raise ValueError("cirsradg_ck_occultation: NLAYIN must be (NPATH,)")
-        if isinstance(mix, tuple):
-            mptr, mpath, mval = _np(mix[0], np.int32), _np(mix[1], np.int32).reshape(-1), _np(mix[2]).reshape(-1)
-            if mptr.ndim != 1 or mptr.size < 2 or mpath.size != mval.size or mptr[-1] != mpath.size:
-                raise ValueError("cirsradg_ck_occultation: mix must be (ptr (Q + 1,), path (nnz,), val (nnz,)) with ptr[-1] = nnz")
-        else:
-            Cm = _np(mix)
-            if Cm.ndim != 2 or Cm.shape[1] != P or Cm.shape[0] < 1:
-                raise ValueError("cirsradg_ck_occultation: a dense mix must be (NGEOM, NPATH)")
-            nz = Cm != 0.0
-            mptr = _np(np.concatenate([[0], np.cumsum(nz.sum(axis=1))]), np.int32)
-            mpath = _np(np.nonzero(nz)[1], np.int32)
-            mval = _np(Cm[nz])
+        mptr, mpath, mval = self._mix_rows(what, mix, P)
         Q = mptr.size - 1
         xf = None if xfac is None else _np(xfac).reshape(W)
         ig = _np(igas_map, np.int32)
-        if dtau_every_gas is not None:
-            dg = _np(dtau_every_gas)
-            if dg.shape != (W, L):
-                raise ValueError("cirsradg_ck_occultation: dtau_every_gas must be (NWAVE, NLAY)")
-            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
         mod = np.empty((W, Q)); trans = np.empty((W, P))
         dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
-        self._chain_dspec = None
-        try:
+        with self._shared_gas_gradient(what, dtau_every_gas, L):
+            self._chain_dspec = None
             rc = self._lib.ansfm_cirsradg_ck_occultation(
                 self._ctx, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
                 _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf), _ptr(mod), _ptr(trans),
                 _ptr(dmod))
-        finally:
-            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
-                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
-        self._check(rc, "cirsradg_ck_occultation")
+        self._check(rc, what)
         if gradients_on_device:
             self._chain_dspec = ("device", W, int(NPAR), L, Q)
         return mod, trans, dmod
 
     def occultation_last(self):
         """(scratch bytes beyond the gas stage and dMOD, k_occ_paths ms, k_occ_grad ms) of the last cirsradg_ck_occultation call"""
-        info = (C.c_double * 3)()
-        self._check(self._lib.ansfm_occultation_last(self._ctx, C.byref(info)), "occultation_last")
-        return int(info[0]), info[1], info[2]
+        return self._last3(self._lib.ansfm_occultation_last, "occultation_last")
 
     def cirsradg_ck_limb(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
                          EMTEMP, mix, xfac=None, gradients_on_device=False, dtau_every_gas=None):
@@ -619,55 +623,25 @@ class AnsfmEngine:
         (`limb.tangent_mix`); xfac (W,) the factor of :4158-4168 or None.  dMOD takes 8 W NPAR L Q bytes on the device.
         NotImplementedError above 160 layers, for a path that ends at the lower boundary (limb paths only), or when dMOD or the
         scratch cannot be reserved."""
-        W, G, NP, NT, S = self.dims
-        lp = _np(lay_press_pa)
-        if lp.ndim != 1:
-            raise ValueError("cirsradg_ck_limb: one model, lay_press_pa (NLAY,)")
+        what = "cirsradg_ck_limb"
+        W = self.dims[0]
+        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC = self._one_model_layers(
+            what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE)
         L = lp.shape[0]
-        lt = _np(lay_temp).reshape(L)
-        am = _np(amount).reshape(S, L)
-        tc = None if taucont is None else _np(taucont).reshape(W, L)
-        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, NPAR, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(SCALE).reshape(LIMAX, P)
         ET = _np(EMTEMP).reshape(LIMAX, P)
-        if NLAYIN.shape != (P,):
-            raise ValueError("cirsradg_ck_limb: NLAYIN must be (NPATH,)")
-        if isinstance(mix, tuple):
-            mptr, mpath, mval = _np(mix[0], np.int32), _np(mix[1], np.int32).reshape(-1), _np(mix[2]).reshape(-1)
-            if mptr.ndim != 1 or mptr.size < 2 or mpath.size != mval.size or mptr[-1] != mpath.size:
-                raise ValueError("cirsradg_ck_limb: mix must be (ptr (Q + 1,), path (nnz,), val (nnz,)) with ptr[-1] = nnz")
-        else:
-            Cm = _np(mix)
-            if Cm.ndim != 2 or Cm.shape[1] != P or Cm.shape[0] < 1:
-                raise ValueError("cirsradg_ck_limb: a dense mix must be (NGEOM, NPATH)")
-            nz = Cm != 0.0
-            mptr = _np(np.concatenate([[0], np.cumsum(nz.sum(axis=1))]), np.int32)
-            mpath = _np(np.nonzero(nz)[1], np.int32)
-            mval = _np(Cm[nz])
+        mptr, mpath, mval = self._mix_rows(what, mix, P)
         Q = mptr.size - 1
         xf = None if xfac is None else _np(xfac).reshape(W)
         ig = _np(igas_map, np.int32)
-        if dtau_every_gas is not None:
-            dg = _np(dtau_every_gas)
-            if dg.shape != (W, L):
-                raise ValueError("cirsradg_ck_limb: dtau_every_gas must be (NWAVE, NLAY)")
-            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
         mod = np.empty((W, Q)); spec = np.empty((W, P))
         dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
-        self._chain_dspec = None
-        try:
+        with self._shared_gas_gradient(what, dtau_every_gas, L):
+            self._chain_dspec = None
             rc = self._lib.ansfm_cirsradg_ck_limb(
                 self._ctx, int(ISPACE), L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
                 _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf), _ptr(mod),
                 _ptr(spec), _ptr(dmod))
-        finally:
-            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
-                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
-        self._check(rc, "cirsradg_ck_limb")
+        self._check(rc, what)
         if gradients_on_device:
             self._chain_dspec = ("device", W, int(NPAR), L, Q)
         return mod, spec, dmod
@@ -675,9 +649,7 @@ class AnsfmEngine:
     def limb_last(self):
         """(scratch bytes beyond the gas stage and dMOD, k_limb_planck + k_limb_sens ms, k_limb_grad ms) of the last
         cirsradg_ck_limb call"""
-        info = (C.c_double * 3)()
-        self._check(self._lib.ansfm_limb_last(self._ctx, C.byref(info)), "limb_last")
-        return int(info[0]), info[1], info[2]
+        return self._last3(self._lib.ansfm_limb_last, "limb_last")
 
     def cirsradg_ck_thermal(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
                             NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None, gradients_on_device=False,
@@ -703,21 +675,13 @@ class AnsfmEngine:
         TS = _np(np.broadcast_to(np.atleast_1d(_np(TSURF)), (n,)))
         ig = _np(igas_map, np.int32)
         on_dev = bool(gradients_on_device) and n == 1
-        if dtau_every_gas is not None:
-            dg = _np(dtau_every_gas)
-            if n != 1 or dg.shape != (W, L):
-                raise ValueError("cirsradg_ck_thermal: dtau_every_gas must be (NWAVE, NLAY) for a single model")
-            self._check(self._lib.ansfm_set_shared_gas_gradient(self._ctx, L, _ptr(dg)), "set_shared_gas_gradient")
         spec = np.empty((n, W, P)); dts = np.empty((n, W, P))
         dspec = None if on_dev else np.empty((n, W, NPAR, LIMAX, P))
-        try:
+        with self._shared_gas_gradient("cirsradg_ck_thermal", dtau_every_gas, L, n, " for a single model"):
             rc = self._lib.ansfm_cirsradg_ck_thermal(
                 self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR),
                 _ptr(ig), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), _ptr(TS), _ptr(_np(EMISSIVITY)),
                 _ptr(_np(xfac)), _ptr(spec), _ptr(dspec), _ptr(dts))
-        finally:
-            if dtau_every_gas is not None:           # consumed by a successful call; cancelled if the call failed before that
-                self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
         self._check(rc, "cirsradg_ck_thermal")
         self._chain_dspec = None
         if on_dev:

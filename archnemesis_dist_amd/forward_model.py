@@ -564,24 +564,20 @@ class CIRSradGPU:
             return SPECOUT, dSPECOUT, dTSURF          # (NWAVE,NPATH), (NWAVE,NPAR,NLAYINmax,NPATH), (NWAVE,NPATH)
         return SPECOUT                                                        # (NWAVE, NPATH)
 
-    # ---- primary transit with gradients: the depth and its layer gradients collapsed on the device ------------------
-    def nemesisPTfm(self, gradients=False):
-        """nemesisPTfm (ForwardModel_0.py:1838-1995).  Without gradients: the reference's method, whose CIRSrad is the seam
-        above.  With gradients the reference asks CIRSrad for dSPECOUT (NWAVE, NPAR, 2 NLAY, NLAY - 1), maps it to the state
-        vector and only then sums the annuli; here `AnsfmEngine.cirsradg_ck_transit` sums the annuli first (the absorbing area
-        and its gradient with respect to every layer property), and map2pro / map2xvec run on that (NWAVE, NPAR, NLAY, 1)
-        array on the device.  The same steps as the reference's otherwise; its own method takes over for a Telluric object,
-        a case CIRSrad would delegate, and more layers than the fused call takes."""
+    # ---- what the three fused gradient routes below share.  Lines of ForwardModel_0.py behind each step:
+    #                                                nemesisPTfm    nemesisSOfmg    nemesisLfmg
+    #   _fused_setup    copies of the inputs         :1868-1876     :1024-1032      :1413-1421
+    #                   consistency checks           (after them)   :1036-1037      :1425-1426
+    #                   ILS, wave range, tables      :1890-1895     :1165-1170      :1429-1434
+    #   _fused_paths    tangent heights from         :1906-1908     :1180-1182      :1444-1446
+    #   _fused_inputs   taucont                      :3989          :3989           :3989
+    #   _fused_tail     incpar                       :1925-1928     :1193-1196      :1457-1460
+    #   _fused_convg    convolution                  :1986-1994     :1236-1241      :1510-1513
+    def _fused_setup(self, adjust_hydrostat, checks=None):
+        """The preamble of a forward-model method with gradients: the X copies of the inputs, the consistency checks (then
+        `checks()`, the method's own), the ILS, the calculation range, the tables read over it and the profiles: xmap."""
         from copy import deepcopy
-        if gradients is False:
-            return super().nemesisPTfm(False)
-        if getattr(self, "Telluric", None) is not None:
-            return super().nemesisPTfm(gradients)
-        eng = get_engine(self.ansfm_device)
-        if not hasattr(eng, "cirsradg_ck_transit"):
-            return super().nemesisPTfm(gradients)
-        from . import transit as _transit
-        self.Variables1 = deepcopy(self.Variables)                              # :1868-1876
+        self.Variables1 = deepcopy(self.Variables)
         self.MeasurementX = deepcopy(self.Measurement)
         self.AtmosphereX = deepcopy(self.Atmosphere)
         self.ScatterX = deepcopy(self.Scatter)
@@ -592,16 +588,80 @@ class CIRSradGPU:
         self.CIAX = deepcopy(self.CIA)
         self.check_gas_spec_atm()
         self.check_wave_range_consistency()
-        if int(self.MeasurementX.IFORM) != IFORM_TRANSIT_DEPTH:
-            raise ValueError('error in nemesisPTfm :: Measurement unit must be set to TransitDepth (IFORM=2) for primary transit observations')
-        if self.MeasurementX.NGEOM != 1:
-            raise ValueError('error in nemesisPTfm :: Only one geometry is allowed for primary transit observations (NGEOM=1)')
-        self.Measurement.build_ils(IGEOM=0)                                     # :1890-1895
+        if checks is not None:
+            checks()
+        self.Measurement.build_ils(IGEOM=0)
         wavecalc_min, wavecalc_max = self.Measurement.calc_wave_range(apply_doppler=True, IGEOM=None)
         if self.SpectroscopyX.NGAS > 0:
             self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
-        self.adjust_hydrostat = True
-        xmap = self.subprofretg()
+        self.adjust_hydrostat = adjust_hydrostat
+        return self.subprofretg()
+
+    def _fused_paths(self, emtemp=False):
+        """NLAYIN (NPATH,), LAYINC, SCALE (LIMAX, NPATH) of PathX, and EMTEMP on request"""
+        P = self.PathX
+        NPATH = int(P.NPATH)
+        out = (np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH), np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH),
+               np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH))
+        return out + (np.asarray(P.EMTEMP, dtype=np.float64).reshape(-1, NPATH),) if emtemp else out
+
+    def _fused_inputs(self, eng):
+        """The table on the engine and what a fused call takes of the layers: the continuum (its parts for the side products),
+        the gas amounts, the sizes and igas_map."""
+        from types import SimpleNamespace
+        S, L, A = self.SpectroscopyX, self.LayerX, self.AtmosphereX
+        self._ansfm_upload_table(eng)
+        c = SimpleNamespace()
+        c.TAUCIA, c.TAUDUST, c.TAURAY, c.dTAUCON = self._ansfm_continuum(True)
+        c.taucont = c.TAUCIA + c.TAUDUST + c.TAURAY
+        c.f_gas = self._ansfm_layer_inputs()
+        c.press, c.temp = np.asarray(L.PRESS, dtype=np.float64), np.asarray(L.TEMP, dtype=np.float64)
+        c.NVMR, c.NDUST, c.NPRO, c.NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
+        c.NPAR = c.NVMR + 2 + int(self.ScatterX.NDUST)
+        c.igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
+        return c
+
+    def _fused_tail(self, eng, c, xmap, NGEOM):
+        """After the fused call: the side products, then its gradients (NWAVE, NPAR, NLAY, NGEOM) on the device through
+        map2pro and map2xvec: dSPECMOD (NWAVE, NGEOM, NX)."""
+        S, L = self.SpectroscopyX, self.LayerX
+        if self.ansfm_keep_side_products:
+            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
+            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, c.TAUCIA, c.TAUDUST, c.TAURAY)
+        incpar = [i for i in range(c.NVMR + 2 + c.NDUST) if np.mean(xmap[:, i, :]) != 0.0]
+        eng.map2pro(None, S.NWAVE, c.NVMR, c.NDUST, c.NPRO, NGEOM, np.array([c.NLAY] * NGEOM),
+                    np.tile(np.arange(c.NLAY)[:, None], (1, NGEOM)), L.DTE, L.DAM, L.DCO, INCPAR=incpar, to_host=False)
+        return eng.map2xvec(None, S.NWAVE, c.NVMR, c.NDUST, c.NPRO, NGEOM, self.Variables.NX, xmap)
+
+    def _fused_convg(self, SPECMOD, dSPECMOD):
+        S, M = self.SpectroscopyX, self.MeasurementX
+        if int(S.ILBL) == ILBL_K_TABLES:
+            return M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        return M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+
+    # ---- primary transit with gradients: the depth and its layer gradients collapsed on the device ------------------
+    def nemesisPTfm(self, gradients=False):
+        """nemesisPTfm (ForwardModel_0.py:1838-1995).  Without gradients: the reference's method, whose CIRSrad is the seam
+        above.  With gradients the reference asks CIRSrad for dSPECOUT (NWAVE, NPAR, 2 NLAY, NLAY - 1), maps it to the state
+        vector and only then sums the annuli; here `AnsfmEngine.cirsradg_ck_transit` sums the annuli first (the absorbing area
+        and its gradient with respect to every layer property), and map2pro / map2xvec run on that (NWAVE, NPAR, NLAY, 1)
+        array on the device.  The same steps as the reference's otherwise; its own method takes over for a Telluric object,
+        a case CIRSrad would delegate, and more layers than the fused call takes."""
+        if gradients is False:
+            return super().nemesisPTfm(False)
+        if getattr(self, "Telluric", None) is not None:
+            return super().nemesisPTfm(gradients)
+        eng = get_engine(self.ansfm_device)
+        if not hasattr(eng, "cirsradg_ck_transit"):
+            return super().nemesisPTfm(gradients)
+        from . import transit as _transit
+
+        def one_transit_geometry():
+            if int(self.MeasurementX.IFORM) != IFORM_TRANSIT_DEPTH:
+                raise ValueError('error in nemesisPTfm :: Measurement unit must be set to TransitDepth (IFORM=2) for primary transit observations')
+            if self.MeasurementX.NGEOM != 1:
+                raise ValueError('error in nemesisPTfm :: Only one geometry is allowed for primary transit observations (NGEOM=1)')
+        xmap = self._fused_setup(True, one_transit_geometry)
         self.LayerX.DUST_UNITS_FLAG = self.AtmosphereX.DUST_UNITS_FLAG
         self.calc_path_PT()
         S, L, P, A = self.SpectroscopyX, self.LayerX, self.PathX, self.AtmosphereX
@@ -609,35 +669,19 @@ class CIRSradGPU:
         if (not self._ansfm_supported(True) or not self._ansfm_transmission_branch(int(imod[0]))
                 or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)):
             return super().nemesisPTfm(gradients)
-        NPATH = int(P.NPATH)
-        NLAYIN = np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH)
-        LAYINC = np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH)
-        SCALE = np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH)
-        BASEH_TANHE = _transit.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)      # :1906-1908
+        NLAYIN, LAYINC, SCALE = self._fused_paths()
+        BASEH_TANHE = _transit.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)
         weights = _transit.path_weights(BASEH_TANHE, A.RADIUS)                  # the trapezoid of :1949-1954, by path
-        self._ansfm_upload_table(eng)
-        TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(True)
-        taucont = TAUCIA + TAUDUST + TAURAY                                     # :3989
-        f_gas = self._ansfm_layer_inputs()
-        NVMR, NDUST, NPRO, NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
-        NPAR = NVMR + 2 + int(self.ScatterX.NDUST)
-        igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
+        c = self._fused_inputs(eng)
         try:
-            AREA, SPECOUT, _ = eng.cirsradg_ck_transit(np.asarray(L.PRESS, dtype=np.float64), np.asarray(L.TEMP, dtype=np.float64), f_gas,
-                                                       taucont, dTAUCON, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE, weights,
-                                                       gradients_on_device=True)
+            AREA, SPECOUT, _ = eng.cirsradg_ck_transit(c.press, c.temp, c.f_gas, c.taucont, c.dTAUCON, c.NVMR, c.NPAR, c.igas_map,
+                                                       NLAYIN, LAYINC, SCALE, weights, gradients_on_device=True)
         except NotImplementedError:                 # more layers or paths than the fused call takes
             _note("nemesisPTfm with gradients: more layers or paths than the fused transit call takes; the reference's method runs "
                   "over CIRSrad(return_grad=True) instead")
             return super().nemesisPTfm(gradients)
         _route("nemesisPTfm with gradients: transit depth collapsed over the paths on the device")
-        if self.ansfm_keep_side_products:
-            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
-            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, TAUCIA, TAUDUST, TAURAY)
-        incpar = [i for i in range(NVMR + 2 + NDUST) if np.mean(xmap[:, i, :]) != 0.0]   # :1925-1928
-        eng.map2pro(None, S.NWAVE, NVMR, NDUST, NPRO, 1, np.array([NLAY]), np.arange(NLAY), L.DTE, L.DAM, L.DCO, INCPAR=incpar,
-                    to_host=False)
-        dAREA = eng.map2xvec(None, S.NWAVE, NVMR, NDUST, NPRO, 1, self.Variables.NX, xmap)      # (NWAVE, 1, NX)
+        dAREA = self._fused_tail(eng, c, xmap, 1)                               # (NWAVE, 1, NX)
         area_star = np.pi * ((self.StellarX.RADIUS * 1.0e3) ** 2)               # :1941-1944
         area_planet_disk = np.pi * ((A.RADIUS + BASEH_TANHE[0] * 1.0e3) ** 2)
         SPECMOD = np.zeros((S.NWAVE, self.MeasurementX.NGEOM))
@@ -646,10 +690,7 @@ class CIRSradGPU:
         dSPECMOD[:, 0, :] = dAREA[:, 0, :]
         SPECMOD = (SPECMOD + area_planet_disk) / area_star * 100.               # :1963-1966
         dSPECMOD = dSPECMOD / area_star * 100.
-        if int(S.ILBL) == ILBL_K_TABLES:                                        # :1986-1994
-            SPECONV, dSPECONV = self.MeasurementX.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
-        else:
-            SPECONV, dSPECONV = self.MeasurementX.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        SPECONV, dSPECONV = self._fused_convg(SPECMOD, dSPECMOD)
         SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)
         return SPECONV, dSPECONV
 
@@ -662,76 +703,38 @@ class CIRSradGPU:
         map2xvec run on that (NWAVE, NPAR, NLAY, NGEOM) array on the device.  The same steps as the reference's otherwise.  Its
         own method, whose CIRSrad(return_grad=True) is the seam above, takes over for the AOTF branch, a Telluric object,
         runtime line-by-line, a case CIRSrad would delegate, an engine without the call and one that refuses it."""
-        from copy import deepcopy
         if getattr(self.Measurement, "NORDERS_AOTF", None) is not None or getattr(self, "Telluric", None) is not None:
             return super().nemesisSOfmg()
         eng = get_engine(self.ansfm_device)
         if not hasattr(eng, "cirsradg_ck_occultation"):
             return super().nemesisSOfmg()
         from . import occultation as _occ
-        self.Variables1 = deepcopy(self.Variables)                              # :1024-1032
-        self.MeasurementX = deepcopy(self.Measurement)
-        self.AtmosphereX = deepcopy(self.Atmosphere)
-        self.ScatterX = deepcopy(self.Scatter)
-        self.StellarX = deepcopy(self.Stellar)
-        self.SurfaceX = deepcopy(self.Surface)
-        self.LayerX = deepcopy(self.Layer)
-        self.SpectroscopyX = deepcopy(self.Spectroscopy)
-        self.CIAX = deepcopy(self.CIA)
-        self.check_gas_spec_atm()                                               # :1036-1037
-        self.check_wave_range_consistency()
-        self.Measurement.build_ils(IGEOM=0)                                     # :1165-1170
-        wavecalc_min, wavecalc_max = self.Measurement.calc_wave_range(apply_doppler=True, IGEOM=None)
-        if self.SpectroscopyX.NGAS > 0:
-            self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
-        self.adjust_hydrostat = False
-        xmap = self.subprofretg()
+        xmap = self._fused_setup(False)
         self.calc_pathg_SO()
-        S, L, P, A, M = self.SpectroscopyX, self.LayerX, self.PathX, self.AtmosphereX, self.MeasurementX
+        S, L, P, M = self.SpectroscopyX, self.LayerX, self.PathX, self.MeasurementX
         imod = np.unique(np.asarray(P.IMOD).astype(int))
         if (not self._ansfm_supported(True) or not self._ansfm_transmission_branch(int(imod[0]))
                 or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)):
             return super().nemesisSOfmg()
-        NPATH = int(P.NPATH)
-        NLAYIN = np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH)
-        LAYINC = np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH)
-        SCALE = np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH)
-        BASEH_TANHE = _occ.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)         # :1180-1182
-        mix = _occ.tangent_mix(BASEH_TANHE, M.TANHE)                            # :1211-1232
-        NGEOM = int(M.NGEOM)
-        self._ansfm_upload_table(eng)
-        TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(True)
-        taucont = TAUCIA + TAUDUST + TAURAY                                     # :3989
-        f_gas = self._ansfm_layer_inputs()
+        NLAYIN, LAYINC, SCALE = self._fused_paths()
+        mix = _occ.tangent_mix(_occ.tangent_heights_km(L.BASEH, NLAYIN, LAYINC), M.TANHE)      # :1211-1232
+        c = self._fused_inputs(eng)
         xf = None
         if int(M.IFORM) == IFORM_ATMOSPHERIC_TRANSMISSION:                      # :4119-4127: times the solar flux
             import scipy.interpolate
             self.StellarX.calc_solar_flux()
             xf = scipy.interpolate.interp1d(self.StellarX.WAVE, self.StellarX.SOLFLUX)(S.WAVE)
-        NVMR, NDUST, NPRO, NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
-        NPAR = NVMR + 2 + int(self.ScatterX.NDUST)
-        igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
         try:
-            MOD, SPECOUT, _ = eng.cirsradg_ck_occultation(np.asarray(L.PRESS, dtype=np.float64), np.asarray(L.TEMP, dtype=np.float64),
-                                                          f_gas, taucont, dTAUCON, NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE,
-                                                          mix=mix, xfac=xf, gradients_on_device=True)
+            MOD, SPECOUT, _ = eng.cirsradg_ck_occultation(c.press, c.temp, c.f_gas, c.taucont, c.dTAUCON, c.NVMR, c.NPAR, c.igas_map,
+                                                          NLAYIN, LAYINC, SCALE, mix=mix, xfac=xf, gradients_on_device=True)
         except NotImplementedError:                 # more layers or paths than the fused call takes, or no room for dMOD
             _note("nemesisSOfmg: the fused occultation call refused the case (layers, paths or the size of dMOD); the reference's "
                   "method runs over CIRSrad(return_grad=True) instead")
             return super().nemesisSOfmg()
         _route("nemesisSOfmg: tangent paths mixed to the geometries on the device")
-        if self.ansfm_keep_side_products:
-            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
-            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, TAUCIA, TAUDUST, TAURAY)
-        incpar = [i for i in range(NVMR + 2 + NDUST) if np.mean(xmap[:, i, :]) != 0.0]   # :1193-1196
-        eng.map2pro(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, np.array([NLAY] * NGEOM), np.tile(np.arange(NLAY)[:, None], (1, NGEOM)),
-                    L.DTE, L.DAM, L.DCO, INCPAR=incpar, to_host=False)
-        dSPECMOD = eng.map2xvec(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, self.Variables.NX, xmap)      # (NWAVE, NGEOM, NX)
+        dSPECMOD = self._fused_tail(eng, c, xmap, int(M.NGEOM))                 # (NWAVE, NGEOM, NX)
         SPECMOD = np.array(MOD)
-        if int(S.ILBL) == ILBL_K_TABLES:                                        # :1236-1241
-            SPECONV, dSPECONV = M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
-        else:
-            SPECONV, dSPECONV = M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        SPECONV, dSPECONV = self._fused_convg(SPECMOD, dSPECMOD)
         dSPECONV = self.subspeconv(S.WAVE, SPECMOD, dSPECONV)                   # :1244
         SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1247
         return SPECONV, dSPECONV
@@ -746,57 +749,27 @@ class CIRSradGPU:
         whose CIRSrad(return_grad=True) is the seam above, takes over for a Telluric object, runtime line-by-line, a case
         CIRSrad would delegate, a path calculation that is not thermal emission, a path that ends at the lower boundary, an
         engine without the call and one that refuses it."""
-        from copy import deepcopy
         if getattr(self, "Telluric", None) is not None:
             return super().nemesisLfmg()
         eng = get_engine(self.ansfm_device)
         if not hasattr(eng, "cirsradg_ck_limb"):
             return super().nemesisLfmg()
         from . import limb as _limb
-        self.Variables1 = deepcopy(self.Variables)                              # :1413-1421
-        self.MeasurementX = deepcopy(self.Measurement)
-        self.AtmosphereX = deepcopy(self.Atmosphere)
-        self.ScatterX = deepcopy(self.Scatter)
-        self.StellarX = deepcopy(self.Stellar)
-        self.SurfaceX = deepcopy(self.Surface)
-        self.LayerX = deepcopy(self.Layer)
-        self.SpectroscopyX = deepcopy(self.Spectroscopy)
-        self.CIAX = deepcopy(self.CIA)
-        self.check_gas_spec_atm()                                               # :1425-1426
-        self.check_wave_range_consistency()
-        self.Measurement.build_ils(IGEOM=0)                                     # :1429-1434
-        wavecalc_min, wavecalc_max = self.Measurement.calc_wave_range(apply_doppler=True, IGEOM=None)
-        if self.SpectroscopyX.NGAS > 0:
-            self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
-        self.adjust_hydrostat = False
-        xmap = self.subprofretg()
+        xmap = self._fused_setup(False)
         self.calc_pathg_L()
-        S, L, P, A, M = self.SpectroscopyX, self.LayerX, self.PathX, self.AtmosphereX, self.MeasurementX
+        S, L, P, M = self.SpectroscopyX, self.LayerX, self.PathX, self.MeasurementX
         imod = np.unique(np.asarray(P.IMOD).astype(int))
         if (not self._ansfm_supported(True) or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)
                 or self._ansfm_transmission_branch(int(imod[0])) or (int(imod[0]) & IMOD_ABSORBTION)
                 or not (int(imod[0]) & IMOD_THERMAL_EMISSION)):                 # dispatch order :4478-4489
             return super().nemesisLfmg()
-        NPATH = int(P.NPATH)
-        NLAYIN = np.asarray(P.NLAYIN, dtype=np.int32).reshape(NPATH)
-        LAYINC = np.asarray(P.LAYINC, dtype=np.int32).reshape(-1, NPATH)
-        SCALE = np.asarray(P.SCALE, dtype=np.float64).reshape(-1, NPATH)
-        EMTEMP = np.asarray(P.EMTEMP, dtype=np.float64).reshape(-1, NPATH)
-        press = np.asarray(L.PRESS, dtype=np.float64)
-        BASEH_TANHE = _limb.tangent_heights_km(L.BASEH, NLAYIN, LAYINC)        # :1444-1446
-        mix = _limb.tangent_mix(BASEH_TANHE, M.TANHE)                           # :1475-1496
-        NGEOM = int(M.NGEOM)
-        self._ansfm_upload_table(eng)
-        TAUCIA, TAUDUST, TAURAY, dTAUCON = self._ansfm_continuum(True)
-        taucont = TAUCIA + TAUDUST + TAURAY                                     # :3989
-        f_gas = self._ansfm_layer_inputs()
+        NLAYIN, LAYINC, SCALE, EMTEMP = self._fused_paths(emtemp=True)
+        mix = _limb.tangent_mix(_limb.tangent_heights_km(L.BASEH, NLAYIN, LAYINC), M.TANHE)    # :1475-1496
+        c = self._fused_inputs(eng)
         xf, _ = self._ansfm_units_and_surface()                                 # :4158-4168
-        NVMR, NDUST, NPRO, NLAY = int(A.NVMR), int(A.NDUST), int(A.NP), int(L.NLAY)
-        NPAR = NVMR + 2 + int(self.ScatterX.NDUST)
-        igas_map = np.array([A.locate_gas(S.ID[i], S.ISO[i]) for i in range(S.NGAS)], dtype=np.int32)
         try:
-            MOD, SPECOUT, _ = eng.cirsradg_ck_limb(int(M.ISPACE), press, np.asarray(L.TEMP, dtype=np.float64), f_gas, taucont, dTAUCON,
-                                                   NVMR, NPAR, igas_map, NLAYIN, LAYINC, SCALE, EMTEMP, mix=mix, xfac=xf,
+            MOD, SPECOUT, _ = eng.cirsradg_ck_limb(int(M.ISPACE), c.press, c.temp, c.f_gas, c.taucont, c.dTAUCON, c.NVMR, c.NPAR,
+                                                   c.igas_map, NLAYIN, LAYINC, SCALE, EMTEMP, mix=mix, xfac=xf,
                                                    gradients_on_device=True)
         except NotImplementedError:                 # more layers than the fused call takes, a path that ends at the lower boundary
             #                                         (:6479-6483: the engine makes that test), or no room for dMOD or the scratch
@@ -804,21 +777,12 @@ class CIRSradGPU:
                   "the scratch); the reference's method runs over CIRSrad(return_grad=True) instead")
             return super().nemesisLfmg()
         _route("nemesisLfmg: tangent paths mixed to the geometries on the device")
-        if self.ansfm_keep_side_products:
-            L.TAUGAS = eng.get_taugas(L.NLAY, 0)
-            L.TAUTOT = self._ansfm_total_opacity(L.TAUGAS, TAUCIA, TAUDUST, TAURAY)
-        incpar = [i for i in range(NVMR + 2 + NDUST) if np.mean(xmap[:, i, :]) != 0.0]   # :1457-1460
-        eng.map2pro(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, np.array([NLAY] * NGEOM), np.tile(np.arange(NLAY)[:, None], (1, NGEOM)),
-                    L.DTE, L.DAM, L.DCO, INCPAR=incpar, to_host=False)
-        dSPECMOD = eng.map2xvec(None, S.NWAVE, NVMR, NDUST, NPRO, NGEOM, self.Variables.NX, xmap)      # (NWAVE, NGEOM, NX)
+        dSPECMOD = self._fused_tail(eng, c, xmap, int(M.NGEOM))                 # (NWAVE, NGEOM, NX)
         SPECMOD = np.array(MOD)
         if int(M.IFORM) == IFORM_INTEGRATED_RADIANCE:                           # :1500-1504
             SPECONV, dSPECONV = M.integrate_filterg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
         else:
-            if int(S.ILBL) == ILBL_K_TABLES:                                    # :1510-1513
-                SPECONV, dSPECONV = M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
-            else:
-                SPECONV, dSPECONV = M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+            SPECONV, dSPECONV = self._fused_convg(SPECMOD, dSPECMOD)
             dSPECONV = self.subspeconv(S.WAVE, SPECMOD, dSPECONV)               # :1516
         SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1519
         return SPECONV, dSPECONV

@@ -306,6 +306,41 @@ def test_limb_chain_to_the_state_vector_on_the_device(eng, oracle):
     np.testing.assert_allclose(xv, xv_o, rtol=0, atol=1e-13 * np.max(np.abs(xv_o)))
 
 
+def test_last_of_each_fused_route_keeps_its_own_call():
+    """transit, occultation and limb keep separate records on one engine: after one call of each (W = 130, L = 12, the `pairs`
+    case of each file), every *_last returns the scratch bytes its call reported on an engine of its own, and times >= 0; on the
+    engine that ran the limb call only, the other two still have nothing recorded."""
+    import archnemesis_dist_amd as pkg
+    import test_occultation_gpu as tog
+    import test_transit_gpu as ttg
+    routes = [("transit", _transit_case(130), ttg._fused), ("occultation", tog._case(130), tog._fused), ("limb", _case(130), _fused)]
+    alone = {}
+    for name, c, call in routes:
+        e = pkg.AnsfmEngine(0)
+        try:
+            _upload(e, c)
+            call(e, c)
+            alone[name] = getattr(e, name + "_last")()[0]
+            if name == "limb":
+                for other in (e.occultation_last, e.transit_last):
+                    with pytest.raises(ValueError, match="call recorded yet"):
+                        other()
+        finally:
+            e.close()
+    assert len(set(alone.values())) == 3 and min(alone.values()) > 0
+    e = pkg.AnsfmEngine(0)
+    try:
+        for name, c, call in routes:
+            _upload(e, c)
+            call(e, c)
+        for name, c, call in routes:
+            scratch, ms_a, ms_b = getattr(e, name + "_last")()
+            assert scratch == alone[name], name
+            assert ms_a >= 0.0 and ms_b >= 0.0, name
+    finally:
+        e.close()
+
+
 def test_limb_conditions(eng, oracle):
     """Equal inputs, equal bits; an un-collapsed call before and after a fused call returns equal bits (no scratch of the one is
     the other's); the scratch beyond the gas stage and dMOD is exactly what include/ansfm.h states.  That formula stays below the
