@@ -1,7 +1,20 @@
 // ansfm_merge64.hip.h -- device code of the 64-bit-key merge that the forward kernel (ansfm_overlap_kernels.hip.h) and the
-// gradient kernel (ansfm_overlapg_kernels.hip.h) share: the LDS layout, the switches of the instruction trims, the list keys,
-// the rank walk, the register-list step with its peeled tail, and the per-lane sort of the generic path.  No kernel is
-// defined here, so both units include it.
+// gradient kernel (ansfm_overlapg_kernels.hip.h) share: the LDS layout, the list keys, the rank walk, the register-list step
+// with its peeled tail, and the per-lane sort of the generic path.  No kernel is defined here, so both units include it.
+//
+// The code comes in two forms, chosen by the template parameter OPT of merge_fetch / merge_step / merge_peel:
+//   OPT = 0   the plain form: the weight from its two factors, the key packed field by field, a full list pass per step.  The
+//             gradient kernel, the generic (SORTED = false) and the recorded (NODIV = false) forward paths and
+//             ANSFM_MERGE_LEGACY=1 run it.
+//   OPT != 0  the division-free fast path of the forward kernel (SORTED, NODIV).  Three things that only pay together: the
+//             popped row's next key is the winner's low word + 1 column inserted under the 11-bit mask (kOptBfi), the list
+//             pass of a step ends at the first chunk boundary that no lane's key reaches beyond (kOptExit, merge_pass_exit),
+//             and per lane and merge the rows are the operand with the larger top ordinate, so that the next key re-enters
+//             near the front of the list (kOptOrient, MergeOrient).  With float32 weights the pair weight is in addition one
+//             ds_read_b64 of a product table WT[(col << 5) | row] that the waves of one block per CU share (kOptTable); with
+//             float64 weights the walk's gd + DG[i] * DG[j] is compiled as one fma, which no table of products reproduces.
+// Both forms give the same results bit for bit (tests/test_merge_*.py).  What each piece bought, and the variants that were
+// measured and lost (tools/experiments/r07_merge_retired_variants.patch), is in DESIGN.md section 4.1.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,64 +37,12 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 // out as two wide stores.  Same-box comparisons: gradient kernel 25.7 -> 23.7 ms against six 8-byte rows; forward kernel
 // within +-1 % of five 8-byte rows and of three pairs (it is not store-bound at this level).  The gradient kernel's resolve rewrites the
 // pairs as (frac, 1/weight-sum) and (weight, code) for its replay passes.
-// Switches of the forward merge kernel's instruction trims (every one leaves the results bit for bit):
-//   kMergePeel      the last G - 1 steps of a merge pass over a shrinking list (merge_peel)
-//   kWalkOneOffset  merge_walk_nodiv keeps one running offset instead of two
-//   kMergeUnroll4   four steps per trip of the merge loop instead of two
-//   kLoadNoBox      tables without a boxed entry are interpolated without the box tests (interp_k_nobox)
-// and of the three that only the division-free fast path (SORTED, NODIV) of the forward kernel takes, as the bits of its
-// template parameter OPT (0 = the code before them, which every other user of merge_fetch / merge_step keeps):
-//   kWeightTable    the pair weight is one ds_read_b64 of a product table WT[(col << 5) | row] that the waves of one block
-//                   per CU share (kOptTable; the launch is one block of several waves per CU instead of one-wave blocks).
-//                   float32 weights only: with float64 weights the walk's gd + DG[i] * DG[j] is compiled as one fma
-//   kKeyBfi         the popped row's next key is the winner's low word + 32 inserted under the 11-bit mask (kOptBfi)
-//   kLateBinWait    the boundary after next is read at the top of every step, the crossing branch only moves it (kOptLate)
-//   kMergeExit      the list pass of a step ends at the first chunk boundary c with no lane's x above R[c] (kOptExit,
-//                   merge_pass_exit).  Slower than the full pass on its own; a gain together with kMergeOrient
-//   kMergeOrient    per lane and merge, the rows are the operand with the larger top ordinate, so that the popped row's next
-//                   key re-enters near the front of the list (kOptOrient, MergeOrient; needs kKeyBfi)
-#ifndef ANSFM_MERGE_PEEL
-#define ANSFM_MERGE_PEEL 1
-#endif
-#ifndef ANSFM_WALK_ONE_OFFSET
-#define ANSFM_WALK_ONE_OFFSET 1
-#endif
-#ifndef ANSFM_MERGE_UNROLL4
-#define ANSFM_MERGE_UNROLL4 0
-#endif
-#ifndef ANSFM_LOAD_NOBOX
-#define ANSFM_LOAD_NOBOX 1
-#endif
-#ifndef ANSFM_WEIGHT_TABLE
-#define ANSFM_WEIGHT_TABLE 1
-#endif
-#ifndef ANSFM_KEY_BFI
-#define ANSFM_KEY_BFI 1
-#endif
-#ifndef ANSFM_LATE_BIN_WAIT
-#define ANSFM_LATE_BIN_WAIT 0       // measured slower than the read inside the branch: kept, switched off
-#endif
-#ifndef ANSFM_MERGE_EXIT
-#define ANSFM_MERGE_EXIT 1
-#endif
-#ifndef ANSFM_MERGE_ORIENT
-#define ANSFM_MERGE_ORIENT 1
-#endif
-#ifndef ANSFM_MERGE_EXIT_FORM
-#define ANSFM_MERGE_EXIT_FORM 0     // 0: a test between chunks; 1: every test first, then one straight-line pass
-#endif
-// chunk boundaries of kMergeExit, ascending.  Two tests per step measured faster than four: every test is a
-// scalar branch that the wave waits for, and a wave alone on its SIMD has nobody to hide it behind
-#ifndef ANSFM_MERGE_EXIT_BOUNDS
-#define ANSFM_MERGE_EXIT_BOUNDS 4, 10
-#endif
-constexpr bool kMergePeel = ANSFM_MERGE_PEEL != 0, kWalkOneOffset = ANSFM_WALK_ONE_OFFSET != 0, kMergeUnroll4 = ANSFM_MERGE_UNROLL4 != 0,
-               kLoadNoBox = ANSFM_LOAD_NOBOX != 0, kWeightTable = ANSFM_WEIGHT_TABLE != 0, kKeyBfi = ANSFM_KEY_BFI != 0,
-               kLateBinWait = ANSFM_LATE_BIN_WAIT != 0, kMergeExit = ANSFM_MERGE_EXIT != 0,
-               kMergeOrient = ANSFM_MERGE_ORIENT != 0 && kKeyBfi;
-constexpr int kOptTable = 1, kOptBfi = 2, kOptLate = 4, kOptExit = 8, kOptOrient = 16;
-constexpr int kMergeOpt = (kWeightTable ? kOptTable : 0) | (kKeyBfi ? kOptBfi : 0) | (kLateBinWait ? kOptLate : 0) |
-                          (kMergeExit ? kOptExit : 0) | (kMergeOrient ? kOptOrient : 0);
+
+// The bits of OPT as ansfm_last_merge_launch reports them.  Value 4 (a late read of the bin boundary, retired) stays unused.
+constexpr int kOptTable = 1, kOptBfi = 2, kOptExit = 8, kOptOrient = 16;
+constexpr int kMergeOpt = kOptTable | kOptBfi | kOptExit | kOptOrient;
+// The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
+__host__ __device__ constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
 // Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
 // lane whose columns are a.  One block's waves still fit the CU's LDS as before at every instantiated list length.
 __host__ __device__ constexpr int merge_wave_rows(int G, int opt) { return 2 * G + ((opt & kOptOrient) != 0 ? 2 : 1); }
@@ -95,7 +56,7 @@ constexpr unsigned kRecRow = 64u * 16u, kRecBin = 2u * kRecRow;
 
 struct MergeElem {
     double ai, bc, bn, w;
-    int ci, np;         // np = column + 1; with kOptBfi the winner key's low word instead (the fetch decodes ci and the column)
+    int ci, np;         // np = column + 1; on the fast path the winner key's low word instead (the fetch decodes ci and the column)
 };
 
 // kOptOrient: which operand supplies the rows is a per-lane choice, made once per merge.  The merge is symmetric in its operands
@@ -140,13 +101,14 @@ __device__ __forceinline__ void merge_fetch(double key, int lane, const double *
                                             const unsigned char *PA = nullptr, const unsigned char *PB = nullptr,
                                             const MergeOrient &mo = MergeOrient{})
 {
-    static_assert(OPT == 0 || SORTED, "the trims of the fast path");
-    static_assert((OPT & kOptOrient) == 0 || (OPT & kOptBfi) != 0, "the oriented key is repacked from its low word");
+    static_assert(OPT == 0 || SORTED, "the fast path");
+    static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
     const unsigned kb = (unsigned)__double_as_longlong(key);
-    int ci, cp;
-    if constexpr ((OPT & kOptOrient) != 0) {
-        // the fields at per-lane bit offsets, the addresses on per-lane bases: the instruction count of the unoriented fetch.
+    if constexpr (OPT != 0) {
+        // the fields at per-lane bit offsets, one instruction each, and the addresses on per-lane bases, so that every row
+        // address is one v_lshl_add on top (the compiler otherwise forms (kw << k) & mask + base, three instructions).
         // The table index is formed from the decoded fields (WT is symmetric: the product of the two float32 weights)
+        int ci, cp;
         asm("v_bfe_u32 %0, %1, %2, 5" : "=v"(ci) : "v"(kb), "v"(mo.rsh));
         asm("v_bfe_u32 %0, %1, %2, 6" : "=v"(cp) : "v"(kb), "v"(mo.csh));
         e.ci = ci;
@@ -157,27 +119,17 @@ __device__ __forceinline__ void merge_fetch(double key, int lane, const double *
         e.bc = lds_ld(ab);
         e.bn = lds_ld(ab + 512);                // column G of either operand is its sentinel row
         if constexpr ((OPT & kOptTable) == 0) e.w = pair_weight<W32>(DG, ci, cp);
-        return;
-    }
-    if constexpr (OPT != 0) {
-        // the two fields as one instruction each, so that every row address is one v_lshl_add on top: with the low word kept
-        // in a register (kw) the compiler otherwise forms (kw << k) & mask + base, three instructions per address
-        asm("v_and_b32 %0, 31, %1" : "=v"(ci) : "v"(kb));
-        asm("v_bfe_u32 %0, %1, 5, 6" : "=v"(cp) : "v"(kb));
     } else {
-        ci = kb & 31; cp = (kb >> 5) & 63;
+        const int ci = kb & 31, cp = (kb >> 5) & 63;
+        e.ci = ci;
+        e.np = cp + 1;
+        e.ai = A[ci * kWave + lane];
+        const unsigned ab = lds_addr(B + lane) + ((unsigned)cp << 9);
+        e.bc = lds_ld(ab);
+        e.bn = lds_ld(ab + 512);                // B[G] = sentinel column: an exhausted row re-enters as "huge"
+        if constexpr (SORTED) e.w = pair_weight<W32>(DG, ci, cp);
+        else e.w = pair_weight<W32>(DG, PA[ci * kWave + lane], PB[cp * kWave + lane]);
     }
-    e.ci = ci;
-    if constexpr ((OPT & kOptBfi) != 0) e.np = (int)kb;
-    else e.np = cp + 1;
-    if constexpr ((OPT & kOptTable) != 0) e.w = lds_ld(kLdsWT + ((kb & 0x7FFu) << 3));
-    e.ai = A[ci * kWave + lane];
-    const unsigned ab = lds_addr(B + lane) + ((unsigned)cp << 9);
-    e.bc = lds_ld(ab);
-    e.bn = lds_ld(ab + 512);                    // B[G] = sentinel column: an exhausted row re-enters as "huge"
-    if constexpr ((OPT & kOptTable) != 0) ;
-    else if constexpr (SORTED) e.w = pair_weight<W32>(DG, ci, cp);
-    else e.w = pair_weight<W32>(DG, PA[ci * kWave + lane], PB[cp * kWave + lane]);
 }
 
 // List keys: the element value a_i + b_j with the low 11 mantissa bits replaced by (col << 5) | row  (col <= 32,
@@ -194,7 +146,7 @@ __device__ __forceinline__ double pack_key11(double v, int row, int col)
 // into the value's low word under the mask (v_add_u32 + v_bfi_b32).  col <= 32, so the add does not leave the 11 bits for
 // any key that is consumed; the same double as pack_key11(v, row, col + 1).
 // inc: 32, or 1 in a lane whose key holds the column in its low six bits (MergeOrient; col + 1 <= 33 stays inside them).
-__device__ __forceinline__ double pack_key11_next(double v, unsigned kw, unsigned inc = 32u)
+__device__ __forceinline__ double pack_key11_next(double v, unsigned kw, unsigned inc)
 {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     const unsigned lo = ((kw + inc) & 0x7FFu) | ((unsigned)b & ~0x7FFu);
@@ -210,24 +162,20 @@ struct WalkState {
     unsigned gaddr;     // LDS byte address of GORD[ig + 1]
     unsigned rbase;     // merge_walk_nodiv: lane * 8 - (address of GORD[1] << 6), see there (roff is unused in that walk)
 };
-// LATE (kOptLate, merge_walk_nodiv): gaddr runs one boundary ahead, at GORD[ig + 2], the address the step reads.
-template <bool LATE = false>
 __device__ __forceinline__ WalkState walk_begin(const double *GORD, int lane)
 {
     WalkState ws;
     ws.gd = 0.0; ws.kacc = 0.0; ws.sum1 = 0.0;
     ws.gaddr = lds_addr(GORD + 1);
     ws.gnext = lds_ld(ws.gaddr);
-    if constexpr (LATE) ws.gaddr += 8u;
     ws.roff = (unsigned)lane * 16u;
     ws.rbase = (unsigned)lane * 8u - (ws.gaddr << 6);
     return ws;
 }
 // number of bins closed so far
-template <bool LATE = false>
 __device__ __forceinline__ int walk_bins(const WalkState &ws, const double *GORD)
 {
-    return (int)((ws.gaddr - lds_addr(GORD + (LATE ? 2 : 1))) >> 3);
+    return (int)((ws.gaddr - lds_addr(GORD + 1)) >> 3);
 }
 
 template <bool REC_CODE>
@@ -265,14 +213,7 @@ __device__ __forceinline__ bool merge_walk(const MergeElem &e, WalkState &ws, do
 // in the last bits only (the reference itself forms frac from a difference of cumulative sums, good to ~1e-12).
 // Precondition (checked at launch): the first element of the merged order does not close a bin -- rank()'s python
 // gdist[-1] wrap, which only the recorded form reproduces.
-// LATE (kOptLate): gnn = the boundary after next, GORD[ig + 2], read at the top of the step -- before the next element's
-// operands are fetched, so the branch waits for it without waiting for them and leaves no LDS read of its own behind: the
-// two sides of the branch join with the same reads outstanding and the next step starts waiting for nothing but its own
-// operands, issued a list pass earlier.  gaddr is the address that read uses (GORD[ig + 2], walk_begin<true>) and is stepped
-// in place, so an element that closes a bin right after another sees the right boundary: its step's read is issued at
-// gaddr as the branch of the step before left it.  Past the NaN the read returns what follows GORD and is never moved into gnext.
-template <bool LATE = false>
-__device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &ws, double *rec, double gnn = 0.0)
+__device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &ws, double *rec)
 {
     const double cv = e.ai + e.bc;
     const double w = e.w;
@@ -280,27 +221,14 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
     double kn = fma(cv, w, ws.kacc);
     const bool cross = (gdn >= ws.gnext);       // ordered: GORD[G+1] is NaN
     if (cross) {
-        if constexpr (LATE) {
-            gst<double>(rec, (ws.gaddr << 6) + ws.rbase, fma(ws.gnext - ws.gd, cv, ws.kacc));
-            kn = (gdn - ws.gnext) * cv;
-            ws.gnext = gnn;
-            ws.gaddr += 8u;
-        } else if constexpr (kWalkOneOffset) {
-            // The closed bin's slot, ig * 512 + lane * 8, is formed from the one running offset the walk keeps (gaddr, +8 per
-            // bin; 512 = 8 << 6): one shift-add here, where a second running offset cost an add AND, as a second value that
-            // lives across the branch and the e0 / e1 ping-pong, a register copy at the end of the branch body.  The
-            // boundary is read at gaddr + 8 (an immediate offset of the LDS read) and gaddr is stepped in place last.
-            gst<double>(rec, (ws.gaddr << 6) + ws.rbase, fma(ws.gnext - ws.gd, cv, ws.kacc));
-            kn = (gdn - ws.gnext) * cv;
-            ws.gnext = lds_ld(ws.gaddr + 8u);
-            ws.gaddr += 8u;
-        } else {
-            gst<double>(rec, ws.roff, fma(ws.gnext - ws.gd, cv, ws.kacc));
-            kn = (gdn - ws.gnext) * cv;
-            ws.roff += kWave * 8u;
-            ws.gaddr += 8u;
-            ws.gnext = lds_ld(ws.gaddr);
-        }
+        // The closed bin's slot, ig * 512 + lane * 8, is formed from the one running offset the walk keeps (gaddr, +8 per
+        // bin; 512 = 8 << 6): one shift-add here, where a second running offset cost an add AND, as a second value that
+        // lives across the branch and the e0 / e1 ping-pong, a register copy at the end of the branch body.  The
+        // boundary is read at gaddr + 8 (an immediate offset of the LDS read) and gaddr is stepped in place last.
+        gst<double>(rec, (ws.gaddr << 6) + ws.rbase, fma(ws.gnext - ws.gd, cv, ws.kacc));
+        kn = (gdn - ws.gnext) * cv;
+        ws.gnext = lds_ld(ws.gaddr + 8u);
+        ws.gaddr += 8u;
     }
     ws.kacc = kn;
     ws.gd = gdn;
@@ -313,7 +241,9 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
 // then t_k = s_k for every k >= K1 in every lane: the list is sorted, so x <= s_k <= s_{k+1}.  The pass stops there, exactly,
 // ties included.  A sentinel x (the popped row is exhausted) is above every live key and runs to the end of the live
 // prefix like any other.  The last chunk closes with t_{NP-1} = max(x, s_{NP-1}) as the full pass does.
-constexpr int kExitBounds[] = {ANSFM_MERGE_EXIT_BOUNDS};
+// Two tests per step measured faster than four: every test is a scalar branch that the wave waits for, and a
+// wave alone on its SIMD has nobody to hide it behind
+constexpr int kExitBounds[] = {4, 10};
 constexpr int kNoExitBound = 1000;
 // the first boundary above k0
 __host__ __device__ constexpr int merge_exit_bound(int k0)
@@ -339,41 +269,6 @@ __device__ __forceinline__ void merge_pass_exit(double (&R)[NR], double x)
     }
 }
 
-// The other form (ANSFM_MERGE_EXIT_FORM 1): every boundary compare first, then one descent to a straight-line pass of the
-// length found, "every max before every min" inside it -- the pass of merge_step with NP = the boundary.
-template <int NP, int NR>
-__device__ __forceinline__ void merge_pass_straight(double (&R)[NR], double x)
-{
-    double mk[NP];
-#pragma unroll
-    for (int k = 1; k < NP - 1; ++k) asm("v_max_f64 %0, %1, %2" : "=v"(mk[k]) : "v"(x), "v"(R[k]));
-#pragma unroll
-    for (int k = 1; k < NP - 1; ++k) asm("v_min_f64 %0, %1, %2" : "=v"(R[k]) : "v"(mk[k]), "v"(R[k + 1]));
-    asm("v_max_f64 %0, %1, %2" : "=v"(R[NP - 1]) : "v"(x), "v"(R[NP - 1]));
-}
-template <int I, int K, int NP, int NR, int NB>
-__device__ __forceinline__ void merge_pass_pick(double (&R)[NR], double x, const unsigned long long (&m)[NB])
-{
-    if constexpr (K >= NP - 2) merge_pass_straight<NP>(R, x);
-    else {
-        if (m[I] == 0) merge_pass_straight<K>(R, x);
-        else merge_pass_pick<I + 1, merge_exit_bound(K), NP>(R, x, m);
-    }
-}
-template <int NP, int NR>
-__device__ __forceinline__ void merge_pass_upfront(double (&R)[NR], double x)
-{
-    constexpr int kMaxB = (int)(sizeof(kExitBounds) / sizeof(kExitBounds[0]));
-    unsigned long long m[kMaxB];
-    int c = merge_exit_bound(1);
-#pragma unroll
-    for (int i = 0; i < kMaxB; ++i) {
-        m[i] = (c < NP - 2) ? __builtin_amdgcn_ballot_w64(x > R[c < NR ? c : 0]) : 0ull;    // c: a constant once unrolled
-        c = merge_exit_bound(c);
-    }
-    merge_pass_pick<0, merge_exit_bound(1), NP>(R, x, m);
-}
-
 // The heads of the G rows are kept as a SORTED LIST IN REGISTERS (R[0] = the current winner): popping is free and the
 // row's next key is inserted by one pass of v_max_f64 + v_min_f64 pairs over statically indexed
 // registers -- no tree in LDS, no lane-dependent addressing, and the next winner is known after the FIRST
@@ -389,26 +284,22 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
                                                const MergeOrient &mo = MergeOrient{})
 {
     static_assert(NP >= 1 && NP <= NR, "pass length");
-    static_assert(OPT == 0 || (SORTED && NODIV && !REC_CODE), "the trims of the fast path");
-    double gnn = 0.0;
-    if constexpr ((OPT & kOptLate) != 0) gnn = lds_ld_fixed(ws.gaddr);
+    static_assert(OPT == 0 || (SORTED && NODIV && !REC_CODE), "the fast path");
+    static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
     // 1. the popped row's next element x enters the list s_1 <= s_2 <= ... (s_0 was popped):
     //        t_0 = min(x, s_1),   t_k = min(max(x, s_k), s_{k+1}),   t_{NP-1} = max(x, s_{NP-1})
     //    -- every output independent of the others (no carry chain), in place in ascending k.
     //    NP = pass length: the pass reads and writes R[0..NP) only, which is the full pass whenever R[NP..NR) hold nothing
     //    but "huge" keys (see the peeled steps of k_ck_overlap for when that is known without looking).
-    const double x = (OPT & kOptOrient) != 0 ? pack_key11_next(e.ai + e.bn, (unsigned)e.np, mo.inc)
-                   : (OPT & kOptBfi) != 0    ? pack_key11_next(e.ai + e.bn, (unsigned)e.np)
-                                             : pack_key11(e.ai + e.bn, e.ci, e.np);
+    const double x = OPT != 0 ? pack_key11_next(e.ai + e.bn, (unsigned)e.np, mo.inc) : pack_key11(e.ai + e.bn, e.ci, e.np);
     if constexpr (NP == 1) {
         R[0] = x;                               // the last element's step: its row's next key is a sentinel, nothing follows
     } else {
     asm("v_min_f64 %0, %1, %2" : "=v"(R[0]) : "v"(x), "v"(R[1]));
     // 2. fetch the operands of the new winner (LDS reads in flight during the rest of the pass and the walk)
     merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, en, PA, PB, mo);
-    if constexpr ((OPT & kOptExit) != 0) {
-        if constexpr (ANSFM_MERGE_EXIT_FORM == 1) merge_pass_upfront<NP>(R, x);
-        else merge_pass_exit<1, NP>(R, x);
+    if constexpr (OPT != 0) {
+        merge_pass_exit<1, NP>(R, x);
     } else {
     // 3. finish the insertion: every max first, then every min -- no result is consumed by a neighbouring instruction
     //    (6.40 -> 6.32 ms against blocks of 6, same box)
@@ -428,7 +319,7 @@ __device__ __forceinline__ unsigned merge_step(double (&R)[NR], MergeElem &e, Me
     }
     // 4. rank walk on the element just consumed
     bool cross;
-    if constexpr (NODIV) cross = merge_walk_nodiv<(OPT & kOptLate) != 0>(e, ws, rec, gnn);
+    if constexpr (NODIV) cross = merge_walk_nodiv(e, ws, rec);
     else cross = merge_walk<REC_CODE>(e, ws, rec, GORD, lane);
     // step code of the gradient replay, 12 bits: row (0-4), column (5-9), "the element closed a bin" (10); kCodesPerWord of
     // them to a 64-bit word of the stream

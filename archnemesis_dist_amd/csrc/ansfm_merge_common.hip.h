@@ -195,8 +195,6 @@ __device__ __forceinline__ double fast_div(double n, double d)
 typedef __attribute__((address_space(3))) double lds_double;
 __device__ __forceinline__ unsigned lds_addr(const double *p) { return (unsigned)(size_t)(const lds_double *)p; }
 __device__ __forceinline__ double lds_ld(unsigned a) { return *(const lds_double *)(size_t)a; }
-// a read that stays where it is written (the compiler neither sinks it into a branch nor merges it with another)
-__device__ __forceinline__ double lds_ld_fixed(unsigned a) { return *(const volatile lds_double *)(size_t)a; }
 __device__ __forceinline__ void lds_st(unsigned a, double v) { *(lds_double *)(size_t)a = v; }
 // Global access as wave-uniform base + 32-bit byte offset: the compiler emits `global_load/store v_off, s[base]` and the
 // per-access address arithmetic stays 32-bit (64-bit pointer adds are multi-pass VALU instructions).

@@ -73,10 +73,10 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     }
     if (const char *ev = getenv("ANSFM_MERGE_WALK")) { if (!strcmp(ev, "records")) nodiv = false; }
     // a table without a boxed entry is read without the box tests (fast path only; ANSFM_LOAD_BOXTESTS=1 keeps them)
-    bool nobox = kLoadNoBox && nodiv && !from_k && !ctx->has_boxed;
+    bool nobox = nodiv && !from_k && !ctx->has_boxed;
     if (const char *ev = getenv("ANSFM_LOAD_BOXTESTS")) { if (ev[0] == '1') nobox = false; }
-    // the trims of the division-free fast path (kMergeOpt); ANSFM_MERGE_LEGACY=1 runs the code without them: one-wave blocks,
-    // the weight from its two factors, the key repacked field by field, the boundary read inside the crossing branch
+    // the division-free fast path in its trimmed form (kMergeOpt); ANSFM_MERGE_LEGACY=1 runs the plain form (OPT = 0): one-wave
+    // blocks, the weight from its two factors, the key repacked field by field, a full list pass, the rows always a
     int opt = nodiv ? kMergeOpt : 0;
     if (const char *ev = getenv("ANSFM_MERGE_LEGACY")) { if (ev[0] == '1') opt = 0; }
     bool keys32 = nodiv && ctx->merge_keys == 32;

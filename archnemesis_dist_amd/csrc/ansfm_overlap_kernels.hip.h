@@ -25,7 +25,7 @@ namespace ansfm {
 // skip rules keep looking at the LAST g-ordinate in the original order (:6075-6102).  A spectrum that passes through
 // unmerged comes out in its original order.
 // NOBOX: the table was found free of boxed entries at upload, load_gas interpolates without the box tests.
-// OPT: the trims of the division-free fast path (kOptTable / kOptBfi / kOptLate, ansfm_merge64.hip.h).  With kOptTable the
+// OPT: 0, or the division-free fast path's kOptBfi | kOptExit | kOptOrient with or without kOptTable (ansfm_merge64.hip.h).  With kOptTable the
 // launch is ONE BLOCK OF SEVERAL WAVES PER CU (as many as the LDS holds, blockDim.x / 64) that share DG / GORD and the weight
 // product table WT; rows, tile queue, bin records and the sentinel row stay per wave and there is no barrier after the one
 // that publishes the tables, so the waves run and leave independently as the one-wave blocks do.  With kOptOrient a wave's
@@ -34,7 +34,8 @@ template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false,
 __global__ __launch_bounds__((OPT & kOptTable) != 0 ? kWave * kMaxBlockWaves : kWave) __attribute__((amdgpu_waves_per_eu(1, 2)))
 void k_ck_overlap(OverlapParams p)
 {
-    static_assert(OPT == 0 || (SORTED && NODIV), "the trims of the fast path");
+    static_assert(OPT == 0 || (SORTED && NODIV), "the fast path");
+    static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
     constexpr bool kTable = (OPT & kOptTable) != 0, kOrient = (OPT & kOptOrient) != 0;
     static_assert(!kTable || W32, "the weight table holds float32 products only (launch_overlap)");
     extern __shared__ double smem[];
@@ -129,34 +130,23 @@ void k_ck_overlap(OverlapParams p)
                     merge_init<NR>(R, G, lane, A, B[lane], HUGE_KEY);
                 MergeElem e0, e1;
                 merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB, mo);
-                WalkState ws = walk_begin<(OPT & kOptLate) != 0>(GORD, lane);
-                if constexpr (NODIV) ws.roff = (unsigned)lane * 8u;
+                WalkState ws = walk_begin(GORD, lane);
                 // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
-                const int nloop = kMergePeel ? G * G - (G - 1) : G * G;
+                const int nloop = G * G - (G - 1);
                 // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
-                constexpr int kPer = kMergeUnroll4 ? 4 : 2;
+                // (kPer is a named local on purpose: with a literal 2 the compiler orders the scalar code of the skip rules
+                // above differently in the OPT = 0 instantiations -- same results, other instructions)
+                constexpr int kPer = 2;         // steps per trip
                 for (int n = nloop / kPer; n > 0; --n) {
                     merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                     merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                    if constexpr (kMergeUnroll4) {
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                    }
                 }
-                if constexpr (kMergeUnroll4)
-                    if ((nloop & 2) != 0) {
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                        merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                    }
-                if (kMergePeel || (nloop & 1) != 0)
-                    merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                if constexpr (kMergePeel) {
-                    if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
-                    merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB, mo);
-                }
+                merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
+                merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB, mo);
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
-                    const int ig = walk_bins<(OPT & kOptLate) != 0>(ws, GORD);
+                    const int ig = walk_bins(ws, GORD);
                     for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
                         double r[kLoadBatch];
 #pragma unroll
@@ -179,7 +169,7 @@ void k_ck_overlap(OverlapParams p)
                 // walk formed it, so `a` must stay intact until the last bin is done: the outputs go to row 0 of the bin
                 // records (full-wave coalesced stores) and come back into A afterwards.
                 double ck = 0.0, cs = 0.0;   // (1-frac) share carried into the next bin
-                const int ig = walk_bins<(OPT & kOptLate) != 0>(ws, GORD);
+                const int ig = walk_bins(ws, GORD);
                 constexpr int kRB = 5;       // records of kRB bins are fetched together (one round trip)
                 for (int b0 = 0; b0 < G; b0 += kRB) {
                     double rka[kRB], rs1[kRB], rgd[kRB];

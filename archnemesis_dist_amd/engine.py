@@ -279,7 +279,8 @@ class AnsfmEngine:
         return bool(b.value)
 
     def last_merge_launch(self):
-        """(waves per block, trim bits) of the last forward merge launch: bits 1 weight table, 2 key repack, 4 late bin read."""
+        """(waves per block, trim bits) of the last forward merge launch: bits 1 weight table, 2 key repack,
+        8 list pass that ends at the insertion point, 16 per-lane row operand (4: retired, never set)."""
         w, t = C.c_int(), C.c_int()
         self._check(self._lib.ansfm_last_merge_launch(self._ctx, C.byref(w), C.byref(t)), "last_merge_launch")
         return int(w.value), int(t.value)

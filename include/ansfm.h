@@ -79,7 +79,7 @@ int ansfm_ktable_info(const ansfm_ctx *ctx, int64_t dims[5], int *monotone);
 int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed);
 /* How the last forward merge (k_overlap, cirsrad_ck_thermal, ...) was launched: waves per block (1: one-wave blocks) and the
  * trims of the division-free fast path its kernel carried, as bits (1 weight product table, 2 two-instruction key repack,
- * 4 bin boundary read a step ahead, 8 list pass that ends at the insertion point, 16 per-lane choice of the row operand;
+ * 4 retired, never set, 8 list pass that ends at the insertion point, 16 per-lane choice of the row operand;
  * 0: the code without them, or another path of the merge). */
 int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *trims);
 

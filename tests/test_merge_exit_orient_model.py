@@ -54,7 +54,7 @@ def swap_choice(a, b):
     return b[-1] > a[-1] and all(a[g + 1] >= a[g] for g in range(len(a) - 1))
 
 
-BOUNDS = (4, 10)                               # ANSFM_MERGE_EXIT_BOUNDS as committed
+BOUNDS = (4, 10)                               # kExitBounds (ansfm_merge64.hip.h) as committed
 OTHER_BOUNDS = [(4, 8, 12, 16, 20, 24, 28), (2, 5, 9, 14, 20, 27), (3, 7, 12, 18, 25), (8,)]
 
 
