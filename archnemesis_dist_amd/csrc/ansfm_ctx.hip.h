@@ -11,8 +11,9 @@
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
-//   ansfm_transit.hip, ansfm_occultation.hip, ansfm_limb.hip  the fused gradient routes, collapsed over the paths (transit) or
-//                      with the tangent paths mixed to the geometries (occultation, limb) on the device: each its entry point,
+//   ansfm_transit.hip, ansfm_occultation.hip, ansfm_limb.hip, ansfm_disc.hip  the fused gradient routes, collapsed over the
+//                      paths (transit), with the tangent paths mixed to the geometries (occultation, limb) or with the averaging
+//                      points of a disc mixed to the geometries (disc) on the device: each its entry point,
 //                      its index and matrix build, its scratch layout and its launcher.  What they share is in
 //                      ansfm_pathmix.hip.h (host: checks, path matrix, prologue, staged call, *_last) and
 //                      ansfm_pathmix_kernels.hip.h (device functions: path pass, contraction, sums over g)
@@ -69,13 +70,14 @@ struct LblrtIso {
     DevBuf bins;
 };
 
-// What a fused gradient route (transit, occultation, limb) keeps between calls: its scratch beyond the gas stage, the bytes of
+// What a fused gradient route (transit, occultation, limb, disc) keeps between calls: its scratch beyond the gas stage, the bytes of
 // it the last call needed, whether a call is recorded, and the events around its two kernel stages (created at the first call)
 struct FusedRoute {
     DevBuf ws;
     size_t scratch_bytes = 0;
     int recorded = 0;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    double ms[2] = {0.0, 0.0};   // disc: the times between the events, read once when the call ends (the others query in *_last)
 };
 
 }  // namespace ansfm
@@ -156,7 +158,9 @@ struct ansfm_ctx {
     //   occ (ansfm_cirsradg_ck_occultation): exp(-tau_path) [P][G][Wpad] + MOD [W][Q] + T [W][P]
     //   limb (ansfm_cirsradg_ck_limb): the Planck tables [2][NT][Wpad] + spec [P][G][Wpad] + dg E [Q][L][G][Wpad] + the partial
     //   sums of Z [GS][Q][L][Wpad] + MOD [W][Q] + SPEC [W][P]
-    FusedRoute transit, occ, limb;
+    //   disc (ansfm_cirsradg_ck_disc): the Planck tables [2][NT + 1][Wpad] + spec [P][G][Wpad] + dg E [Q][L][G][Wpad] + the
+    //   partial sums of Z [GS][Q][L][Wpad] + the ground's sums [Q][G][Wpad] + MOD, dTSMOD [W][Q] + SPEC [W][P]
+    FusedRoute transit, occ, limb, disc;
 
     // scattering core: the Hansen walk of g-ordinate g + 1 runs on a second stream beside the chains of g
     hipStream_t ms_stream = nullptr;
@@ -172,7 +176,7 @@ struct ansfm_ctx {
     ~ansfm_ctx()
     {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        for (FusedRoute *r : {&transit, &occ, &limb})
+        for (FusedRoute *r : {&transit, &occ, &limb, &disc})
             for (hipEvent_t e : r->ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);

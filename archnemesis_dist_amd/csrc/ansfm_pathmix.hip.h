@@ -1,5 +1,5 @@
-// ansfm_pathmix.hip.h -- the host side the three fused gradient entries share (ansfm_transit.hip, ansfm_occultation.hip,
-// ansfm_limb.hip): the checks of the paths and of the mixing matrix, the path matrix, the prologue of a call, the reservation
+// ansfm_pathmix.hip.h -- the host side the fused gradient entries share (ansfm_transit.hip, ansfm_occultation.hip,
+// ansfm_limb.hip, ansfm_disc.hip): the checks of the paths and of the mixing matrix, the path matrix, the prologue of a call, the reservation
 // of dMOD, the staged call around an entry's own launcher, and what stands behind ansfm_*_last.  A helper that can refuse takes
 // the entry's name (`what`, "cirsradg_ck_...") and formats it into the message.  Inline functions only; no kernel here.
 #pragma once

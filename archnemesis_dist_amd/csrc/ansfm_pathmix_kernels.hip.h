@@ -1,8 +1,9 @@
-// ansfm_pathmix_kernels.hip.h -- the device code the three fused gradient routes share (transit, occultation, limb; kernels in
-// ansfm_transit_kernels.hip.h, ansfm_occultation_kernels.hip.h, ansfm_limb_kernels.hip.h): the path pass exp(-tau_path), the
+// ansfm_pathmix_kernels.hip.h -- the device code the fused gradient routes share (transit, occultation, limb, disc; kernels in
+// ansfm_transit_kernels.hip.h, ansfm_occultation_kernels.hip.h, ansfm_limb_kernels.hip.h, ansfm_disc_kernels.hip.h): the path
+// pass exp(-tau_path), the
 // contraction of the columns of a (layer, geometry) against the opacity derivatives of the gradient merge, and the sums over
 // g that give the per-path spectra and MOD.  Device functions only, inlined into the kernels that call them; no kernel here.
-// The functions read their arguments from the calling kernel's own params struct (OccParams, LimbParams, TransitParams) by
+// The functions read their arguments from the calling kernel's own params struct (OccParams, LimbParams, TransitParams, DiscParams) by
 // field name; each says which fields.  Sums run in a fixed order and nothing is accumulated atomically: equal inputs, equal bits.
 //
 // LDS budget of the contraction (design statements, not measurements).  A block of 4 waves serves one (64-wavenumber tile,
@@ -23,7 +24,7 @@
 
 namespace ansfm {
 
-constexpr int kMixWaves = 4;                       // waves of a contraction block (k_occ_grad, k_limb_grad)
+constexpr int kMixWaves = 4;                       // waves of a contraction block (k_occ_grad, k_limb_grad, k_disc_grad)
 constexpr size_t kMixLdsTwoBlocks = 80 * 1024;     // LDS of a block when two are to share a CU
 constexpr size_t kMixLdsOneBlock = 160 * 1024;
 

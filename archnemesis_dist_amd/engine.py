@@ -652,6 +652,60 @@ class AnsfmEngine:
         cirsradg_ck_limb call"""
         return self._last3(self._lib.ansfm_limb_last, "limb_last")
 
+    def cirsradg_ck_disc(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, LAYINC, SCALE, EMTEMP,
+                         TSURF, EMISSIVITY=None, mix=None, xfac=None, gradients_on_device=False, dtau_every_gas=None):
+        """Disc-averaged thermal emission with analytic gradients of one model (nemesisdiscfmg :1719-1834), the averaging points
+        mixed to the geometries on the device.  The points are P paths through ONE layer sequence: LAYINC (N,), EMTEMP (N,),
+        SCALE (N, P); unlike `cirsradg_ck_limb` the sequence may end at the lower boundary, with TSURF and EMISSIVITY (W,) as
+        `cirsradg_ck_thermal` takes them (:6479-6498).  Returns MOD (W, Q) = xfac * SPEC @ C.T, SPEC (W, P) the path radiances
+        before xfac, dTSMOD (W, Q) = xfac * sum_p C[q, p] dTSURF_p and dMOD (W, NPAR, L, Q) in the layout of `cirsradg_ck_limb`.
+        mix (`disc.average_mix`), xfac, gradients_on_device and dtau_every_gas as `cirsradg_ck_limb` takes them.  dMOD takes
+        8 W NPAR L Q bytes on the device.  ValueError for TSURF > 0 without EMISSIVITY, a LAYINC outside the layers or a bad mix;
+        NotImplementedError above 160 layers or when dMOD or the scratch cannot be reserved."""
+        what = "cirsradg_ck_disc"
+        W, G, NP, NT, S = self.dims
+        lp = _np(lay_press_pa)
+        if lp.ndim != 1:
+            raise ValueError(what + ": one model, lay_press_pa (NLAY,)")
+        L = lp.shape[0]
+        lt = _np(lay_temp).reshape(L)
+        am = _np(amount).reshape(S, L)
+        tc = None if taucont is None else _np(taucont).reshape(W, L)
+        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, int(NPAR), L)
+        LAYINC = _np(LAYINC, np.int32).reshape(-1)
+        N = LAYINC.shape[0]
+        ET = _np(EMTEMP).reshape(-1)
+        SC = _np(SCALE)
+        if SC.ndim == 1:
+            SC = _np(SC[:, None])
+        if N < 1 or SC.ndim != 2 or SC.shape[0] != N or SC.shape[1] < 1 or ET.shape[0] != N:
+            raise ValueError(what + ": LAYINC (N,), EMTEMP (N,) and SCALE (N, NPATH) with N, NPATH >= 1")
+        P = SC.shape[1]
+        if mix is None:
+            raise ValueError(what + ": mix is required (disc.average_mix)")
+        mptr, mpath, mval = self._mix_rows(what, mix, P)
+        Q = mptr.size - 1
+        xf = None if xfac is None else _np(xfac).reshape(W)
+        em = None if EMISSIVITY is None else _np(EMISSIVITY).reshape(W)
+        ig = _np(igas_map, np.int32)
+        mod = np.empty((W, Q)); spec = np.empty((W, P)); dts = np.empty((W, Q))
+        dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
+        with self._shared_gas_gradient(what, dtau_every_gas, L):
+            self._chain_dspec = None
+            rc = self._lib.ansfm_cirsradg_ck_disc(
+                self._ctx, int(ISPACE), L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), N,
+                _ptr(LAYINC), _ptr(ET), P, _ptr(SC), float(TSURF), _ptr(em), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf),
+                _ptr(mod), _ptr(spec), _ptr(dts), _ptr(dmod))
+        self._check(rc, what)
+        if gradients_on_device:
+            self._chain_dspec = ("device", W, int(NPAR), L, Q)
+        return mod, spec, dts, dmod
+
+    def disc_last(self):
+        """(scratch bytes beyond the gas stage and dMOD, k_disc_planck + k_disc_sens ms, k_disc_grad ms) of the last
+        cirsradg_ck_disc call"""
+        return self._last3(self._lib.ansfm_disc_last, "disc_last")
+
     def cirsradg_ck_thermal(self, ISPACE, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map,
                             NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None, gradients_on_device=False,
                             dtau_every_gas=None):

@@ -573,6 +573,8 @@ class CIRSradGPU:
     #   _fused_inputs   taucont                      :3989          :3989           :3989
     #   _fused_tail     incpar                       :1925-1928     :1193-1196      :1457-1460
     #   _fused_convg    convolution                  :1986-1994     :1236-1241      :1510-1513
+    # nemesisdiscfmg takes _fused_inputs, _fused_tail and _fused_convg(IGEOM=i, :1815-1826) per geometry; its preamble is the
+    # reference's own per averaging point (process_IAV :2004-2036).
     def _fused_setup(self, adjust_hydrostat, checks=None):
         """The preamble of a forward-model method with gradients: the X copies of the inputs, the consistency checks (then
         `checks()`, the method's own), the ILS, the calculation range, the tables read over it and the profiles: xmap."""
@@ -633,11 +635,20 @@ class CIRSradGPU:
                     np.tile(np.arange(c.NLAY)[:, None], (1, NGEOM)), L.DTE, L.DAM, L.DCO, INCPAR=incpar, to_host=False)
         return eng.map2xvec(None, S.NWAVE, c.NVMR, c.NDUST, c.NPRO, NGEOM, self.Variables.NX, xmap)
 
-    def _fused_convg(self, SPECMOD, dSPECMOD):
-        S, M = self.SpectroscopyX, self.MeasurementX
-        if int(S.ILBL) == ILBL_K_TABLES:
-            return M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
-        return M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+    def _fused_convg(self, SPECMOD, dSPECMOD, IGEOM=None):
+        """IGEOM None: every geometry at once on MeasurementX.  IGEOM = i: geometry i of Measurement, SPECMOD (NWAVE,) and
+        dSPECMOD (NWAVE, NX), with the .fwh file where there is one (:1815-1826)."""
+        S = self.SpectroscopyX
+        if IGEOM is None:
+            M = self.MeasurementX
+            if int(S.ILBL) == ILBL_K_TABLES:
+                return M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+            return M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM='All')
+        M = self.Measurement
+        if int(self.Spectroscopy.ILBL) == ILBL_K_TABLES:
+            FWHMEXIST = self.runname if os.path.exists(self.runname + '.fwh') else ''
+            return M.convg(S.WAVE, SPECMOD, dSPECMOD, IGEOM=IGEOM, FWHMEXIST=FWHMEXIST)
+        return M.lblconvg(S.WAVE, SPECMOD, dSPECMOD, IGEOM=IGEOM)
 
     # ---- primary transit with gradients: the depth and its layer gradients collapsed on the device ------------------
     def nemesisPTfm(self, gradients=False):
@@ -785,6 +796,124 @@ class CIRSradGPU:
             SPECONV, dSPECONV = self._fused_convg(SPECMOD, dSPECMOD)
             dSPECONV = self.subspeconv(S.WAVE, SPECMOD, dSPECONV)               # :1516
         SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1519
+        return SPECONV, dSPECONV
+
+    # ---- disc average with gradients: the averaging points mixed on the device ----------------------------------------
+    def _ansfm_disc_point(self, IGEOM, IAV):
+        """process_IAV(return_grad=True) up to calc_pathg (:2004-2036): xmap"""
+        from copy import deepcopy
+        self.select_Measurement(IGEOM, IAV)
+        self.AtmosphereX = deepcopy(self.Atmosphere)
+        self.ScatterX = deepcopy(self.Scatter)
+        self.StellarX = deepcopy(self.Stellar)
+        self.SurfaceX = deepcopy(self.Surface)
+        self.LayerX = deepcopy(self.Layer)
+        self.CIAX = deepcopy(self.CIA)
+        self.TelluricX = deepcopy(self.Telluric)
+        MX = self.MeasurementX
+        if MX.EMISS_ANG[0, 0] >= 0.0:
+            self.ScatterX.SOL_ANG = MX.SOL_ANG[0, 0]
+            self.ScatterX.EMISS_ANG = MX.EMISS_ANG[0, 0]
+            self.ScatterX.AZI_ANG = MX.AZI_ANG[0, 0]
+        else:
+            self.ScatterX.SOL_ANG = MX.TANHE[0, 0]
+            self.ScatterX.EMISS_ANG = MX.EMISS_ANG[0, 0]
+        xmap = self.subprofretg()
+        self.LayerX.DUST_UNITS_FLAG = self.AtmosphereX.DUST_UNITS_FLAG
+        self.calc_pathg()
+        return xmap
+
+    def _ansfm_disc_fused(self, eng, IGEOM, NAV):
+        """One geometry through ONE `cirsradg_ck_disc` call: SPEC (NWAVE,), dSPEC (NWAVE, NX), or None where the fused call does
+        not take the geometry (the caller then runs the points through process_IAV)."""
+        from . import disc as _disc
+        M = self.Measurement
+        if np.any(np.asarray(M.EMISS_ANG)[IGEOM, :NAV] < 0.0):                  # limb points: other layers per point
+            return None
+        points = []
+        for IAV in range(NAV):
+            xmap = self._ansfm_disc_point(IGEOM, IAV)
+            points.append((self.LayerX, self.PathX, self.SurfaceX, xmap))
+            if IAV == 0:                            # what declines the geometry shows at its first point: the others are spared
+                S = self.SpectroscopyX
+                imod = np.unique(np.asarray(self.PathX.IMOD).astype(int))
+                if (not self._ansfm_supported(True) or int(S.ILBL) not in (ILBL_K_TABLES, ILBL_LBL_TABLES)
+                        or self._ansfm_transmission_branch(int(imod[0])) or (int(imod[0]) & IMOD_ABSORBTION)
+                        or not (int(imod[0]) & IMOD_THERMAL_EMISSION)):         # dispatch order :4478-4489
+                    return None
+        seq = _disc.shared_sequence(points)
+        imod0 = np.asarray(points[0][1].IMOD)       # the first point's was tested above; the others must name the same calculation
+        if seq is None or any(not np.array_equal(np.asarray(P.IMOD), imod0) for _, P, _, _ in points[1:]):
+            return None
+        LAYINC, EMTEMP, SCALE = seq
+        c = self._fused_inputs(eng)
+        xf, emissivity = self._ansfm_units_and_surface()                        # :4158-4189
+        try:
+            MOD, _, dTSMOD, _ = eng.cirsradg_ck_disc(int(self.MeasurementX.ISPACE), c.press, c.temp, c.f_gas, c.taucont, c.dTAUCON,
+                                                     c.NVMR, c.NPAR, c.igas_map, LAYINC, SCALE, EMTEMP, float(self.SurfaceX.TSURF),
+                                                     EMISSIVITY=emissivity, mix=_disc.average_mix(np.asarray(M.WGEOM)[IGEOM, :NAV]),
+                                                     xfac=xf, gradients_on_device=True)
+        except NotImplementedError:                 # more layers than the fused call takes, or no room for dMOD or the scratch
+            _note("nemesisdiscfmg: the fused disc call refused the case (layers, the size of dMOD or of the scratch); the averaging "
+                  "points run one by one over CIRSrad(return_grad=True) instead")
+            return None
+        _route("nemesisdiscfmg: averaging points mixed on the device")
+        dSPEC = np.array(self._fused_tail(eng, c, xmap, 1)[:, 0, :])             # (NWAVE, NX)
+        if self.Variables.JSURF >= 0:                                           # :2062-2063 carried through the sum
+            dSPEC[:, self.Variables.JSURF] = dTSMOD[:, 0]
+        return np.array(MOD[:, 0]), dSPEC
+
+    def nemesisdiscfmg(self):
+        """nemesisdiscfmg (ForwardModel_0.py:1719-1834).  For every averaging point of a geometry the reference runs
+        process_IAV(return_grad=True) -- paths, CIRSrad with dSPECOUT (NWAVE, NPAR, NLAYIN, 1), map2pro, map2xvec -- and only then
+        forms the weighted sum with WGEOM (:1789-1794).  Every step after the radiative transfer is linear and the points of a
+        geometry are paths through one layer sequence that differ in SCALE only, so here ONE `AnsfmEngine.cirsradg_ck_disc` call
+        per geometry forms the sum first (`disc.average_mix`); the gas stage and the gradient merge run once, and map2pro /
+        map2xvec run on that (NWAVE, NPAR, NLAY, 1) array on the device.  The same steps as the reference's otherwise.  A geometry
+        the fused call does not take -- a point with EMISS_ANG < 0, points whose layers or paths differ in any bit
+        (`disc.shared_sequence`), runtime line-by-line, a case CIRSrad would delegate, a path calculation that is not thermal
+        emission, an engine that refuses -- runs its points through process_IAV in this process, whose CIRSrad(return_grad=True)
+        is the seam above, and weights them as the reference does.  NCores is not used: no joblib workers on one GPU.  The
+        reference's method takes over for a Telluric object and an engine without the call."""
+        from copy import deepcopy
+        if getattr(self, "Telluric", None) is not None:
+            return super().nemesisdiscfmg()
+        eng = get_engine(self.ansfm_device)
+        if not hasattr(eng, "cirsradg_ck_disc"):
+            return super().nemesisdiscfmg()
+        if self.Atmosphere.NLOCATIONS > 1:                                      # :1750-1758
+            raise ValueError('error in nemesisdiscfmg :: archNEMESIS has not been setup for dealing with multiple locations yet')
+        if self.Surface.NLOCATIONS > 1:
+            raise ValueError('error in nemesisdiscfmg :: archNEMESIS has not been setup for dealing with multiple locations yet')
+        self.check_gas_spec_atm()
+        self.check_wave_range_consistency()
+        if getattr(self, "NCores", None) is not None and int(self.NCores) > 1:
+            _note("nemesisdiscfmg(NCores > 1): the averaging points are mixed in one call on the GPU (or run one after the other in "
+                  "this process), not in joblib workers")
+        M = self.Measurement
+        SPECONV = np.zeros(M.MEAS.shape)
+        dSPECONV = np.zeros((M.NCONV.max(), M.NGEOM, self.Variables.NX))
+        for IGEOM in range(M.NGEOM):
+            M.build_ils(IGEOM=IGEOM)                                            # :1767-1773
+            wavecalc_min, wavecalc_max = M.calc_wave_range(apply_doppler=True, IGEOM=IGEOM)
+            self.SpectroscopyX = deepcopy(self.Spectroscopy)
+            if self.SpectroscopyX.NGAS > 0:
+                self.SpectroscopyX.read_tables(wavemin=wavecalc_min, wavemax=wavecalc_max)
+            NAV = int(M.NAV[IGEOM])
+            fused = self._ansfm_disc_fused(eng, IGEOM, NAV)
+            if fused is not None:
+                SPEC, dSPEC = fused
+            else:                                                               # :1776-1794, in this process
+                SPEC, dSPEC = 0.0, 0.0
+                for IAV in range(NAV):
+                    s1, d1 = self.process_IAV(IAV, IGEOM, return_grad=True)
+                    SPEC = SPEC + s1 * M.WGEOM[IGEOM, IAV]
+                    dSPEC = dSPEC + d1 * M.WGEOM[IGEOM, IAV]
+            SPECONV1, dSPECONV1 = self._fused_convg(SPEC, dSPEC, IGEOM=IGEOM)  # :1815-1826
+            n = M.NCONV[IGEOM]
+            SPECONV[0:n, IGEOM] = SPECONV1[0:n]
+            dSPECONV[0:n, IGEOM, :] = dSPECONV1[0:n, :]
+        SPECONV, dSPECONV = self.subspecret(SPECONV, dSPECONV)                  # :1832
         return SPECONV, dSPECONV
 
 

@@ -351,6 +351,40 @@ int ansfm_cirsradg_ck_limb(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_
                            double *SPEC, double *dMOD);
 int ansfm_limb_last(const ansfm_ctx *ctx, double info[3]);
 
+/* Disc-averaged thermal emission with analytic gradients of ONE model (nemesisdiscfmg, ForwardModel_0.py:1719-1834): the P
+ * averaging points of an unresolved planet are mixed to Q geometries on the device -- the weighted sum with WGEOM (:1789-1794) as
+ * a sparse matrix C (Q, P), rows mix_ptr[q] .. mix_ptr[q + 1] of (mix_path, mix_val) -- instead of through one dSPECOUT
+ * (W, NPAR, NLAYIN, 1) per point.  All pointers are host pointers.  The points are paths through ONE layer sequence of N entries j
+ * with l_j = LAYINC[j] and B, dB/dT the Planck function of :6274-6281 at EMTEMP[j] in the units of ISPACE; they differ in
+ * s_jp = SCALE[j][p] only.  Unlike ansfm_cirsradg_ck_limb the sequence may end at the lower boundary (:6479-6498):
+ *   tau_jp[w][g] = s_jp (TAUGAS[w][g][l_j] + taucont[w][l_j])     T_-1,p = 1, T_jp = T_{j-1,p} exp(-tau_jp)
+ *   ground = lay_press_pa[l_{N-1}] > lay_press_pa[l_{int(N/2)-1}]   (index -1 is N - 1)
+ *   R, dR = TSURF <= 0 ? B, dB/dT at EMTEMP[N-1] : EMISSIVITY[w] x (B, dB/dT at TSURF)
+ *   spec[w][g][p] = sum_j (T_{j-1,p} - T_jp) B_j + [ground] T_{N-1,p} R       SPEC[w][p] = sum_g DELG[g] spec[w][g][p]
+ *   MOD[w][q] = xfac[w] sum_p C[q][p] SPEC[w][p]
+ *   dTSMOD[w][q] = xfac[w] sum_g DELG[g] sum_p C[q][p] [ground] T_{N-1,p} dR
+ *   A_jp = T_jp B_j - sum_{m > j} (T_{m-1,p} - T_mp) B_m - [ground] T_{N-1,p} R
+ *   E[w][g][l][q] = sum_p C[q][p] sum_{j: l_j = l} s_jp A_jp
+ *   Z[w][l][q] = sum_g DELG[g] sum_p C[q][p] sum_{j: l_j = l} (T_{j-1,p} - T_jp) dB/dT_j
+ *   dMOD[w][k][l][q] = xfac[w] (sum_g DELG[g] E[w][g][l][q] dTAUTOT[w][g][k][l] + [k == NVMR] Z[w][l][q])
+ * with dTAUTOT, nan_to_num, the layout of dMOD and its stay on the device for ansfm_map2pro(dSPECIN = NULL) as for
+ * ansfm_cirsradg_ck_limb.  As in the reference, dTSMOD with TSURF <= 0 is still T_end dB/dT at EMTEMP[N-1], and the bottom
+ * layer's temperature column of dMOD gets no dR term.  SPEC[W][P], dTSMOD[W][Q] and dMOD[W][NPAR][L][Q] may be NULL; EMISSIVITY[W]
+ * may be NULL where TSURF <= 0.  ANSFM_ERR_UNSUPPORTED above 160 layers (two 64-lane LDS rows per layer, 160 KiB) and for a dMOD
+ * (8 W NPAR L Q bytes, held as a whole) or a scratch that cannot be reserved.  Device scratch beyond the gas stage and dMOD is
+ *   8 Wpad (Q L (G + GS) + (P + Q) G + 2 (NT + 1)) + 8 W (2 Q + P) bytes,
+ *   GS = min(G, max(4, ceil(256 / ((Wpad / 64) (Q + u))))),  u = 1 if some path is named by no geometry, else 0,
+ * NT the number of bit-distinct EMTEMP values and GS the groups of g-ordinates the sensitivity kernel puts on its grid.
+ * ANSFM_ERR_INVALID for N, P or Q <= 0, a LAYINC[j] outside 0 .. L - 1, TSURF > 0 with EMISSIVITY == NULL, a mix_ptr that does not
+ * start at 0 or decreases, a mix_path outside 0 .. P - 1.  ansfm_disc_last: info[0] the bytes of that scratch in the last call,
+ * info[1] / info[2] the milliseconds of k_disc_planck with k_disc_sens / of k_disc_grad. */
+int ansfm_cirsradg_ck_disc(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
+                           const double *taucont, const double *dtaucon, int NVMR, int NPAR, const int32_t *igas_map, int N,
+                           const int32_t *LAYINC, const double *EMTEMP, int P, const double *SCALE, double TSURF,
+                           const double *EMISSIVITY, int Q, const int32_t *mix_ptr, const int32_t *mix_path, const double *mix_val,
+                           const double *xfac, double *MOD, double *SPEC, double *dTSMOD, double *dMOD);
+int ansfm_disc_last(const ansfm_ctx *ctx, double info[3]);
+
 /* ---- analytic-gradient seams ---------------------------------------------------------------
  * ForwardModel_0.k_overlapg (ForwardModel_0.py:5842): + dkdT[W][G][L][S] -> tau[W][G][L],
  * dk[W][G][L][S+1] (slots 0..S-1 = d tau/d amount_gas, slot S = d tau/dT). */

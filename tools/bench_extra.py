@@ -50,6 +50,8 @@ def main():
         bench_so(eng, out)
     if only == "limb":                                      # 0.33 GB dSPECOUT on the device for the un-collapsed route: on request only
         bench_limb(eng, out)
+    if only == "disc":                                      # NAV dSPECOUT arrays on the host for today's route: on request only
+        bench_disc(eng, out)
     if only == "ss":                                        # 10 GB of host arrays: on request only
         bench_ss(eng, out, rng)
     print(json.dumps(out, indent=1))
@@ -609,6 +611,94 @@ def bench_limb(eng, out, W=1024, n=5):
                uncollapsed_wall_s_min_max=[float(min(tu)), float(max(tu))], uncollapsed_overlapg_kernel_ms=float(np.median(ku)),
                uncollapsed_rt_ms=float(np.median(ru)))
     out["limb_C2_W%d" % W] = res
+
+
+def bench_disc(eng, out, W=1024, n=5):
+    """nemesisdiscfmg at the C2 atmosphere as one geometry of an unresolved planet (G = 20, S = 8, L = 100, NPAR = 10, NPRO = 100,
+    NX = 200, a sequence from the top layer to the ground, EMTEMP the layers' temperatures) with NAV = 3 and 8 averaging points:
+    the fused call + map2pro + map2xvec on (W, NPAR, L, 1) beside what runs without it -- NAV single-path cirsradg_ck_thermal
+    calls with dSPECOUT brought to the host, the host maps (the CPU oracle's, standing in for the reference's) and the weighted
+    sum -- alternated in one process, medians (and extremes) of n after one warm-up each.  Then k_disc_sens against k_limb_sens on
+    the same paths: a sequence down to the bottom layer and up again (it does not reach the ground, as the limb entry requires).
+    `disc <W>`: another width."""
+    from oracle import oracle as orc
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    G, S, L, NP, NT, NPRO, NX = 20, 8, 100, 20, 15, 100, 200
+    _, delg = syn.gauss_legendre_01(G, True)
+    PRESS, TEMP, K = syn.synth_ktable(W, G, NP, NT, S)
+    eng.upload_ktable(K, PRESS, TEMP, 200.0 + 0.1 * np.arange(W), delg); del K
+    atm = syn.synth_atmosphere(L, S)
+    rng = np.random.default_rng(5)
+    NVMR, NDUST = S, 0
+    NPAR = NVMR + 2 + NDUST
+    ig = np.arange(S, dtype=np.int32)
+    DTE, DAM, DCO = (rng.uniform(0, 1, (L, NPRO)) for _ in range(3))
+    xmap = rng.normal(size=(NX, NPAR, NPRO))
+    lp, lt, am = atm["lay_press_pa"][0], atm["lay_temp"][0], atm["amount"][0]
+    deep_first = lp[0] > lp[-1]
+    down = np.arange(L - 1, -1, -1) if deep_first else np.arange(L)             # from the top layer to the deepest
+    nlay_1, layinc_1 = np.array([L]), np.arange(L)[:, None]
+    for NAV in (3, 8):
+        LAYINC = down.astype(np.int32)
+        EMTEMP = lt[LAYINC]
+        SCALE = np.ascontiguousarray(np.repeat((1.0 / np.cos(np.radians(np.linspace(0.0, 70.0, NAV))))[None, :], L, axis=0))
+        C = rng.uniform(0.5, 1.0, (1, NAV)); C /= C.sum()
+
+        def fused():
+            MOD, _, dTS, _ = eng.cirsradg_ck_disc(0, lp, lt, am, None, None, NVMR, NPAR, ig, LAYINC, SCALE, EMTEMP, -1.0, mix=C,
+                                                  gradients_on_device=True)
+            eng.map2pro(None, W, NVMR, NDUST, NPRO, 1, nlay_1, layinc_1, DTE, DAM, DCO, to_host=False)
+            return MOD[:, 0], eng.map2xvec(None, W, NVMR, NDUST, NPRO, 1, NX, xmap)[:, 0, :]
+
+        def point_by_point():
+            spec, dspec = 0.0, 0.0
+            for p in range(NAV):
+                s1, d3, _ = eng.cirsradg_ck_thermal(0, lp, lt, am, None, None, NVMR, NPAR, ig, nlay_1, LAYINC[:, None],
+                                                    SCALE[:, p:p + 1], EMTEMP[:, None], -1.0)
+                d2 = orc.map2pro(d3, W, NVMR, NDUST, NPRO, 1, nlay_1, LAYINC[:, None], DTE, DAM, DCO)
+                d1 = orc.map2xvec(d2, W, NVMR, NDUST, NPRO, 1, NX, xmap)
+                spec = spec + C[0, p] * s1[:, 0]
+                dspec = dspec + C[0, p] * d1[:, 0, :]
+            return spec, dspec
+
+        res = {"W": W, "G": G, "S": S, "L": L, "NAV": NAV, "N": int(L), "NPAR": NPAR, "NPRO": NPRO, "NX": NX, "median_of": n}
+        a, b = fused(), point_by_point()
+        res["spectrum_max_rel_diff"] = float(np.max(np.abs(a[0] / b[0] - 1.0)))
+        res["gradient_max_diff_over_max"] = float(np.max(np.abs(a[1] - b[1])) / np.max(np.abs(b[1])))
+        tf, tu, kf, ku = [], [], [], []
+        for _ in range(n):
+            t = time.perf_counter(); fused(); tf.append(time.perf_counter() - t)
+            kf.append(eng.last_kernel_ms()["overlap_ms"])
+            t = time.perf_counter(); point_by_point(); tu.append(time.perf_counter() - t)
+            ku.append(eng.last_kernel_ms()["overlap_ms"])
+        tc = []
+        for _ in range(n):                                  # the fused call alone, without the maps
+            t = time.perf_counter()
+            eng.cirsradg_ck_disc(0, lp, lt, am, None, None, NVMR, NPAR, ig, LAYINC, SCALE, EMTEMP, -1.0, mix=C, gradients_on_device=True)
+            tc.append(time.perf_counter() - t)
+        scratch, ms_sens, ms_grad = eng.disc_last()
+        res.update(fused_wall_s=float(np.median(tf)), fused_wall_s_min_max=[float(min(tf)), float(max(tf))],
+                   fused_call_alone_wall_s=float(np.median(tc)), fused_overlapg_kernel_ms=float(np.median(kf)),
+                   k_disc_planck_and_sens_ms=ms_sens, k_disc_grad_ms=ms_grad, disc_scratch_bytes=scratch, dMOD_bytes=8 * W * NPAR * L,
+                   dSPECOUT_bytes_per_point=8 * W * NPAR * L, point_by_point_wall_s=float(np.median(tu)),
+                   point_by_point_wall_s_min_max=[float(min(tu)), float(max(tu))],
+                   point_by_point_overlapg_kernel_ms_per_call=float(np.median(ku)))
+        # the same paths through both sensitivity kernels: down and up again, no ground
+        LI2 = np.concatenate([LAYINC, LAYINC[::-1]]).astype(np.int32)
+        SC2 = np.ascontiguousarray(np.concatenate([SCALE, SCALE[::-1]]))
+        ET2 = lt[LI2]
+        ms_d, ms_l = [], []
+        for _ in range(n + 1):
+            eng.cirsradg_ck_disc(0, lp, lt, am, None, None, NVMR, NPAR, ig, LI2, SC2, ET2, -1.0, mix=C, gradients_on_device=True)
+            ms_d.append(eng.disc_last()[1])
+            eng.cirsradg_ck_limb(0, lp, lt, am, None, None, NVMR, NPAR, ig, np.full(NAV, 2 * L, dtype=np.int32),
+                                 np.ascontiguousarray(np.tile(LI2[:, None], (1, NAV))), SC2,
+                                 np.ascontiguousarray(np.tile(ET2[:, None], (1, NAV))), C, gradients_on_device=True)
+            ms_l.append(eng.limb_last()[1])
+        res.update(down_and_up_k_disc_planck_and_sens_ms=float(np.median(ms_d[1:])),
+                   down_and_up_k_limb_planck_and_sens_ms=float(np.median(ms_l[1:])))
+        out["disc_C2_W%d_NAV%d" % (W, NAV)] = res
 
 
 def bench_layer(eng, out):
