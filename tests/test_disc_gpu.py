@@ -64,6 +64,15 @@ def _mix(P, Q, rng):
     if Q == 1:
         w = rng.uniform(0.1, 1.0, (1, P))
         return w / w.sum()
+    if Q == 9:
+        # more geometries than the kMixWaves = 4 waves of a contraction block: rows of two or three weights on successive averaging
+        # points, row 4 empty -- every geometry with a weight has an entry in every layer of the sequence, so each wave serves two
+        assert P == 9
+        C = np.zeros((Q, P))
+        for q in (0, 1, 2, 3, 5, 6, 7, 8):
+            n = 2 + q % 2
+            C[q, (q + np.arange(n)) % P] = rng.uniform(0.1, 1.0, n)
+        return C / np.where(C.sum(axis=1, keepdims=True) > 0, C.sum(axis=1, keepdims=True), 1.0)
     # neighbouring geometries share path 1, the last path is named by no geometry, the third row is empty, a negative weight
     assert Q == 3 and P == 4
     return np.array([[0.3, 0.7, 0.0, 0.0], [0.0, -0.55, 1.45, 0.0], [0.0, 0.0, 0.0, 0.0]])
@@ -83,10 +92,10 @@ def _case(W, L=12, lbl=False, P=3, Q=1, kind="ground"):
 
 
 @functools.lru_cache(maxsize=None)
-def _wide_case():
-    """G = 20, S = 16, L = 4, W = 64 of test_limb_gpu.py (17 slots of 10 KiB beside 40 KiB of columns, more than one LDS stage
-    holds), with a sequence to the ground and three paths"""
-    w = _limb_wide_case()
+def _wide_case(G=20, S=16):
+    """_wide_case of test_limb_gpu.py (L = 4, W = 64; G = 20, S = 16: 17 slots of 10 KiB beside 40 KiB of columns, more than one
+    LDS stage holds; any other (G, S): a size case, its amounts scaled there), with a sequence to the ground and three paths"""
+    w = _limb_wide_case(G, S)
     c = {k: v for k, v in w.items() if k not in ("NLAYIN", "LAYINC", "SCALE", "EMTEMP", "C")}
     rng = np.random.default_rng(93)
     c["lp"] = np.array(w["lp"])
@@ -259,6 +268,28 @@ def test_disc_slab_beyond_one_lds_stage(eng, oracle):
     c = _wide_case()
     got = _check_case(eng, oracle, c, tsurf=180.0)
     assert np.all(np.abs(got[3]).max(axis=(0, 2, 3)) > 0)
+
+
+@pytest.mark.parametrize("G,S", [(32, 3), (27, 5), (20, 31), (32, 31)])
+def test_disc_at_the_size_limits(eng, oracle, G, S):
+    """The chunk rule at its edges (SIZE_CASES of test_limb_gpu.py; the restated slab_chunk keeps each case on its edge): 32
+    g-ordinates, where the waves' columns and one slot are the two-block budget exactly; 31 gases, the 32 slots in 8 chunks of 4
+    and in 32 chunks of 1, gas 30 and the temperature on bits 30 and 31 of the mask.  Same references and bounds as every case of
+    this file."""
+    from test_limb_gpu import assert_size_case
+    assert_size_case(G, S)
+    got = _check_case(eng, oracle, _wide_case(G, S), tsurf=180.0)
+    assert np.all(np.abs(got[3]).max(axis=(0, 2, 3)) > 0)
+
+
+def test_disc_more_geometries_than_waves(eng, oracle):
+    """P = 9 averaging points mixed to Q = 9 geometries by rows of two or three weights, row 4 empty: the 8 geometries with a weight
+    have an entry in every layer, so every wave of the block serves two and fills its LDS columns again for the second"""
+    c = _case(130, P=9, Q=9)
+    n = (c["C"] != 0).sum(axis=1)
+    assert c["C"].shape == (9, 9) and n[4] == 0 and set(np.delete(n, 4)) == {2, 3} and np.count_nonzero(n) >= 6
+    got = _check_case(eng, oracle, c, tsurf=180.0)
+    assert np.all(got[0][:, 4] == 0.0) and np.all(got[2][:, 4] == 0.0) and np.all(got[3][..., 4] == 0.0)
 
 
 def test_disc_conditions(eng, oracle):

@@ -76,6 +76,8 @@ def _case(W, L=12, lbl=False, kind="pairs"):
         C[1] = rng.uniform(-1.0, 1.0, P0)
         C[3, P0 - 1] = 0.75                                   # row 2 stays empty
         C[4, [0, 3, 4]] = [-0.5, 2.0, 0.25]
+    elif kind == "many":
+        keep, C = np.arange(P0), many_geometries(P0, rng)
     else:                                                     # cap
         keep = np.linspace(0, L - 2, 4).astype(int)
         C = np.array([[0.3, 0.7, 0.0, 0.0], [0.0, 0.0, 0.6, 0.4]])
@@ -90,27 +92,79 @@ def _case(W, L=12, lbl=False, kind="pairs"):
     return _freeze(c)
 
 
+def many_geometries(P0, rng):
+    """C (9, P0), P0 >= 9: geometry q mixes the successive tangent paths q and q + 1 (paths 4 and 5 go to geometry 5, and so on
+    past the gap) and row 4 is empty.  Path p turns in layer p, so the geometries with an entry in a layer fall from 8 in the top
+    layers to 1 in layer 0: more than the kMixWaves = 4 waves of a contraction block, which then serve two geometries each, and
+    behind the empty row the geometry's index and its turn among the waves differ."""
+    C = np.zeros((9, P0))
+    for q in (0, 1, 2, 3, 5, 6, 7, 8):
+        f = rng.uniform(0.1, 0.9)
+        j = q if q < 4 else q - 1
+        C[q, j], C[q, j + 1] = 1.0 - f, f
+    return C
+
+
+# --- the slot chunk of the contraction, restated (slab_chunk of csrc/ansfm_pathmix_kernels.hip.h) ---------------------------------
+MIX_WAVES, MIX_LDS_TWO_BLOCKS, MIX_LDS_ONE_BLOCK = 4, 80 * 1024, 160 * 1024
+
+
+def slab_chunk(G, NP1):
+    """(slots a chunk, LDS bytes of a block): a row is one g-ordinate's 512 B per slot, the waves' columns take MIX_WAVES rows of G"""
+    row = G * 512
+    budget = MIX_LDS_TWO_BLOCKS if MIX_LDS_TWO_BLOCKS >= (MIX_WAVES + 1) * row else MIX_LDS_ONE_BLOCK
+    chunks = -(-NP1 // min((budget - MIX_WAVES * row) // row, NP1))
+    return -(-NP1 // chunks), (MIX_WAVES + -(-NP1 // chunks)) * row
+
+
+# (G, S) -> (slots a chunk, chunks, LDS bytes) the size cases of the four fused routes are meant to reach
+SIZE_CASES = {(32, 3): (1, 4, 80 * 1024),        # no slot to spare: cols + row is the two-block budget exactly
+              (27, 5): (1, 6, 67.5 * 1024),      # one slot a chunk with 12.5 KiB left over
+              (20, 31): (4, 8, 80 * 1024),       # 32 slots in 8 chunks of 4
+              (32, 31): (1, 32, 80 * 1024)}      # 32 chunks of 1
+
+
+def assert_size_case(G, S):
+    sc, lds = slab_chunk(G, S + 1)
+    assert (sc, -(-(S + 1) // sc), lds) == SIZE_CASES[(G, S)]
+    return sc, lds
+
+
 @functools.lru_cache(maxsize=None)
-def _wide_case():
-    """G = 20, S = 16, L = 4, W = 64: 17 slots of 10 KiB beside 40 KiB of columns, more than one LDS stage holds"""
+def _wide_case(G=20, S=16, kind="two", seed=92, emtemp=True):
+    """L = 4, W = 64, NVMR = S + 2.  G = 20, S = 16: 17 slots of 10 KiB beside 40 KiB of columns, more than one LDS stage holds.
+    Any other (G, S) is a size case (SIZE_CASES): its amounts are scaled by one factor so that the gas opacity along a path at
+    g = 3 G // 4, median over wavenumbers and paths, is 1 -- unscaled, 31 gases leave exp(-tau_path) = 0 at the upper g-ordinates,
+    and their weights and register slots would test nothing.  kind "two": Q = 2 geometries on the 3 limb paths.  seed and emtemp
+    are for the occultation and transit files, which draw the same arrays from a seed of their own without EMTEMP."""
     from archnemesis_dist_amd import synthetic as syn
-    W, L, S, G = 64, 4, 16, 20
-    rng = np.random.default_rng(92)
-    c = dict(W=W, L=L, S=S, lbl=False, G=G)
+    assert kind == "two"
+    W, L = 64, 4
+    default = (G, S) == (20, 16)
+    rng = np.random.default_rng(seed if default else [seed, G, S])
+    c = dict(W=W, L=L, S=S, lbl=False, G=G, tag=("wide", seed))
     c["PRESS"], c["TEMP"], c["K"] = syn.synth_ktable(W, G, 6, 5, S, seed=23)
     c["delg"] = syn.gauss_legendre_01(G)[1]
     c["WAVE"] = 900.0 + 0.7 * np.arange(W)
     c["lp"] = np.logspace(4.5, 2.5, L); c["lt"] = np.linspace(200, 160, L)
     c["am"] = 10.0 ** rng.uniform(17, 18.5, (S, L)) * (c["lp"][None, :] / c["lp"][:1])
     c["cont"] = 10.0 ** rng.uniform(-4, -1, (W, L))
-    c["NVMR"] = 18
-    c["NPAR"] = 18 + 2 + NDUST
-    c["igas_map"] = rng.permutation(18)[:S].astype(np.int32)
+    c["NVMR"] = S + 2
+    c["NPAR"] = S + 2 + 2 + NDUST
+    c["igas_map"] = rng.permutation(S + 2)[:S].astype(np.int32)
     c["dcont"] = 10.0 ** rng.uniform(-24, -22, (W, c["NPAR"], L))
     c["NLAYIN"], c["LAYINC"], c["SCALE"] = tc.limb_paths(L, rng)
-    c["EMTEMP"] = _emtemp(c, rng)
+    if emtemp:
+        c["EMTEMP"] = _emtemp(c, rng)
     c["C"] = np.array([[0.4, 0.6, 0.0], [0.0, 0.2, 0.8]])
     c["xfac"] = rng.uniform(0.5, 2.0, W)
+    if not default:
+        from oracle import oracle as orc
+        orc.build()
+        k = orc.calc_k(c["K"], c["PRESS"], c["TEMP"], c["lp"] / 101325.0, c["lt"])
+        along = np.einsum("wl,lp->wp", orc.k_overlap(c["delg"], k, c["am"])[:, 3 * G // 4, :],
+                          tc.path_matrix(L, c["NLAYIN"], c["LAYINC"], c["SCALE"]))
+        c["am"] = c["am"] / np.median(along)
     return _freeze(c)
 
 
@@ -118,8 +172,9 @@ _ORACLE = {}
 
 
 def _opacities(oracle, c):
-    """tautot (W, G, L) and the gradient merge's dk (W, G, L, S + 1) of a case by the CPU oracle, once"""
-    key = (c["W"], c["L"], c["lbl"], c["S"])
+    """tautot (W, G, L) and the gradient merge's dk (W, G, L, S + 1) of a case by the CPU oracle, once.  The key names everything
+    a generator's arrays depend on: two cases that differ in G or in the generator's seed alone do not share an entry."""
+    key = (c["W"], c["L"], c["lbl"], c["S"], c["G"], c.get("tag"))
     if key not in _ORACLE:
         if c["lbl"]:
             k, dkdT = oracle.calc_klbl(c["K"], c["PRESS"], c["TEMP"], c["lp"] / 101325.0, c["lt"], grad=True)       # (W, L, S)
@@ -277,6 +332,28 @@ def test_limb_slab_beyond_one_lds_stage(eng, oracle):
     c = _wide_case()
     got = _check_case(eng, oracle, c)
     assert np.all(np.abs(got[2]).max(axis=(0, 2, 3)) > 0)
+
+
+@pytest.mark.parametrize("G,S", sorted(SIZE_CASES))
+def test_limb_at_the_size_limits(eng, oracle, G, S):
+    """The chunk rule at its edges (SIZE_CASES; the restated slab_chunk keeps each case on its edge): 32 g-ordinates, where the
+    waves' columns and one slot are the two-block budget exactly; 31 gases, the 32 slots in 8 chunks of 4 and in 32 chunks of 1,
+    gas 30 and the temperature on bits 30 and 31 of the mask.  Same references and bounds as every case of this file."""
+    assert_size_case(G, S)
+    c = _wide_case(G, S)
+    got = _check_case(eng, oracle, c)
+    assert np.all(np.abs(got[2]).max(axis=(0, 2, 3)) > 0)
+
+
+def test_limb_more_geometries_than_waves(eng, oracle):
+    """Q = 9 on the 11 tangent paths (many_geometries): in the top layers 8 geometries have an entry and every wave of the block
+    serves two, filling its LDS columns again for the second; row 4 is empty."""
+    c = _case(130, kind="many")
+    Sm = tc.path_matrix(c["L"], c["NLAYIN"], c["LAYINC"], c["SCALE"])
+    entries = ((Sm != 0.0).astype(float) @ (c["C"] != 0.0).T.astype(float) > 0).sum(axis=1)          # geometries by layer
+    assert c["C"].shape == (9, 11) and entries.max() >= 6 and entries.min() == 1 and not np.any(c["C"][4])
+    got = _check_case(eng, oracle, c)
+    assert np.all(got[0][:, 4] == 0.0) and np.all(got[2][..., 4] == 0.0)
 
 
 def test_limb_chain_to_the_state_vector_on_the_device(eng, oracle):

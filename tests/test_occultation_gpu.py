@@ -68,6 +68,9 @@ def _case(W, L=12, lbl=False, kind="pairs"):
     elif kind == "transit":
         keep = np.arange(P0)
         C = np.array(t["weight"])[None, :]
+    elif kind == "many":
+        from test_limb_gpu import many_geometries
+        keep, C = np.arange(P0), many_geometries(P0, rng)
     else:                                                     # cap
         keep = np.linspace(0, L - 2, 4).astype(int)
         C = np.array([[0.3, 0.7, 0.0, 0.0], [0.0, 0.0, 0.6, 0.4]])
@@ -81,35 +84,20 @@ def _case(W, L=12, lbl=False, kind="pairs"):
     return _freeze(c)
 
 
-@functools.lru_cache(maxsize=None)
-def _wide_case():
-    """G = 20, S = 16, L = 4, W = 64: 17 slots of 10 KiB beside 40 KiB of columns, more than one LDS stage holds"""
-    from archnemesis_dist_amd import synthetic as syn
-    W, L, S, G = 64, 4, 16, 20
-    rng = np.random.default_rng(91)
-    c = dict(W=W, L=L, S=S, lbl=False, G=G)
-    c["PRESS"], c["TEMP"], c["K"] = syn.synth_ktable(W, G, 6, 5, S, seed=23)
-    c["delg"] = syn.gauss_legendre_01(G)[1]
-    c["WAVE"] = 900.0 + 0.7 * np.arange(W)
-    c["lp"] = np.logspace(4.5, 2.5, L); c["lt"] = np.linspace(200, 160, L)
-    c["am"] = 10.0 ** rng.uniform(17, 18.5, (S, L)) * (c["lp"][None, :] / c["lp"][:1])
-    c["cont"] = 10.0 ** rng.uniform(-4, -1, (W, L))
-    c["NVMR"] = 18
-    c["NPAR"] = 18 + 2 + NDUST
-    c["igas_map"] = rng.permutation(18)[:S].astype(np.int32)
-    c["dcont"] = 10.0 ** rng.uniform(-24, -22, (W, c["NPAR"], L))
-    c["NLAYIN"], c["LAYINC"], c["SCALE"] = tc.limb_paths(L, rng)
-    c["C"] = np.array([[0.4, 0.6, 0.0], [0.0, 0.2, 0.8]])
-    c["xfac"] = rng.uniform(0.5, 2.0, W)
-    return _freeze(c)
+def _wide_case(G=20, S=16):
+    """test_limb_gpu._wide_case (L = 4, W = 64; G = 20, S = 16: 17 slots of 10 KiB beside 40 KiB of columns, more than one LDS
+    stage holds) drawn from this file's seed and without EMTEMP"""
+    from test_limb_gpu import _wide_case as limb_wide_case
+    return limb_wide_case(G, S, "two", seed=91, emtemp=False)
 
 
 _ORACLE = {}
 
 
 def _opacities(oracle, c):
-    """tautot (W, G, L) and the gradient merge's dk (W, G, L, S + 1) of a case by the CPU oracle, once"""
-    key = (c["W"], c["L"], c["lbl"], c["S"])
+    """tautot (W, G, L) and the gradient merge's dk (W, G, L, S + 1) of a case by the CPU oracle, once.  The key names everything
+    a generator's arrays depend on: two cases that differ in G or in the generator's seed alone do not share an entry."""
+    key = (c["W"], c["L"], c["lbl"], c["S"], c["G"], c.get("tag"))
     if key not in _ORACLE:
         if c["lbl"]:
             k, dkdT = oracle.calc_klbl(c["K"], c["PRESS"], c["TEMP"], c["lp"] / 101325.0, c["lt"], grad=True)       # (W, L, S)
@@ -249,6 +237,30 @@ def test_occultation_slab_beyond_one_lds_stage(eng, oracle):
     c = _wide_case()
     got = _check_case(eng, oracle, c)
     assert np.all(np.abs(got[2]).max(axis=(0, 2, 3)) > 0)
+
+
+@pytest.mark.parametrize("G,S", [(32, 3), (27, 5), (20, 31), (32, 31)])
+def test_occultation_at_the_size_limits(eng, oracle, G, S):
+    """The chunk rule at its edges (SIZE_CASES of test_limb_gpu.py; the restated slab_chunk keeps each case on its edge): 32
+    g-ordinates, where the waves' columns and one slot are the two-block budget exactly; 31 gases, the 32 slots in 8 chunks of 4
+    and in 32 chunks of 1, gas 30 and the temperature on bits 30 and 31 of the mask.  Same references and bounds as every case of
+    this file."""
+    from test_limb_gpu import assert_size_case
+    assert_size_case(G, S)
+    c = _wide_case(G, S)
+    got = _check_case(eng, oracle, c)
+    assert np.all(np.abs(got[2]).max(axis=(0, 2, 3)) > 0)
+
+
+def test_occultation_more_geometries_than_waves(eng, oracle):
+    """Q = 9 on the 11 tangent paths (many_geometries of test_limb_gpu.py): in the top layers 8 geometries have an entry and every
+    wave of the block serves two, filling its LDS columns again for the second; row 4 is empty."""
+    c = _case(130, kind="many")
+    Sm = tc.path_matrix(c["L"], c["NLAYIN"], c["LAYINC"], c["SCALE"])
+    entries = ((Sm != 0.0).astype(float) @ (c["C"] != 0.0).T.astype(float) > 0).sum(axis=1)          # geometries by layer
+    assert c["C"].shape == (9, 11) and entries.max() >= 6 and entries.min() == 1 and not np.any(c["C"][4])
+    got = _check_case(eng, oracle, c)
+    assert np.all(got[0][:, 4] == 0.0) and np.all(got[2][..., 4] == 0.0)
 
 
 def test_occultation_with_transit_weights_equals_the_transit_entry(eng, oracle):

@@ -68,12 +68,24 @@ def _case(W, L=12, lbl=False, P=None):
     return c
 
 
+@functools.lru_cache(maxsize=None)
+def _wide_case(G=20, S=16):
+    """test_limb_gpu._wide_case (L = 4, W = 64, NVMR = S + 2, the 3 limb paths; the amounts of a size case scaled as there) drawn
+    from this file's seed, without EMTEMP and the mix, with annulus weights"""
+    from test_limb_gpu import _wide_case as limb_wide_case
+    c = {k: v for k, v in limb_wide_case(G, S, "two", seed=90, emtemp=False).items() if k not in ("C", "xfac")}
+    c["weight"] = np.random.default_rng(90).uniform(1e9, 1e11, c["NLAYIN"].size)
+    c["weight"].flags.writeable = False
+    return c
+
+
 _ORACLE = {}
 
 
 def _opacities(oracle, c):
-    """tautot (W, G, L) and the gradient merge's dk (W, G, L, S + 1) of a case by the CPU oracle, once"""
-    key = (c["W"], c["L"], c["lbl"])
+    """tautot (W, G, L) and the gradient merge's dk (W, G, L, S + 1) of a case by the CPU oracle, once.  The key names everything
+    a generator's arrays depend on: two cases that differ in S, in G or in the generator's seed alone do not share an entry."""
+    key = (c["W"], c["L"], c["lbl"], c["S"], c.get("G"), c.get("tag"))
     if key not in _ORACLE:
         if c["lbl"]:
             k, dkdT = oracle.calc_klbl(c["K"], c["PRESS"], c["TEMP"], c["lp"] / 101325.0, c["lt"], grad=True)       # (W, L, S)
@@ -93,13 +105,19 @@ def _upload(eng, c):
         eng.upload_ktable(c["K"], c["PRESS"], c["TEMP"], c["WAVE"], c["delg"])
 
 
+def _dims(c):
+    return c.get("NVMR", NVMR), c.get("NPAR", NPAR), c.get("igas_map", IGAS_MAP)
+
+
 def _fused(eng, c, dcont="dcont", **kw):
-    return eng.cirsradg_ck_transit(c["lp"], c["lt"], c["am"], c["cont"], None if dcont is None else c[dcont], NVMR, NPAR, IGAS_MAP,
+    nvmr, npar, ig = _dims(c)
+    return eng.cirsradg_ck_transit(c["lp"], c["lt"], c["am"], c["cont"], None if dcont is None else c[dcont], nvmr, npar, ig,
                                    c["NLAYIN"], c["LAYINC"], c["SCALE"], c["weight"], **kw)
 
 
 def _uncollapsed_on_engine(eng, c, dcont):
-    spec, dspec = eng.cirsradg_ck_transmission(c["lp"], c["lt"], c["am"], c["cont"], dcont, NVMR, NPAR, IGAS_MAP, c["NLAYIN"],
+    nvmr, npar, ig = _dims(c)
+    spec, dspec = eng.cirsradg_ck_transmission(c["lp"], c["lt"], c["am"], c["cont"], dcont, nvmr, npar, ig, c["NLAYIN"],
                                                c["LAYINC"], c["SCALE"])
     AREA, dAREA = tc.area_from_paths(spec, dspec, c["weight"], c["NLAYIN"], c["LAYINC"], c["L"])
     return AREA, spec, dAREA
@@ -118,11 +136,12 @@ def _compare(what, got, ref, weight):
 
 
 def _check_case(eng, oracle, c, dcont="dcont", gases=None, temperature=True, every_gas=False):
+    nvmr, npar, ig = _dims(c)
     _upload(eng, c)
     got = _fused(eng, c, dcont, dtau_every_gas=c["dray"] if every_gas else None)
-    assert got[0].shape == (c["W"],) and got[1].shape == (c["W"], c["NLAYIN"].size) and got[2].shape == (c["W"], NPAR, c["L"])
+    assert got[0].shape == (c["W"],) and got[1].shape == (c["W"], c["NLAYIN"].size) and got[2].shape == (c["W"], npar, c["L"])
     tautot, dk = _opacities(oracle, c)
-    dtau = tc.dtautot(dk, IGAS_MAP, NVMR, NPAR, None if dcont is None else c[dcont], c["dray"] if every_gas else None,
+    dtau = tc.dtautot(dk, ig, nvmr, npar, None if dcont is None else c[dcont], c["dray"] if every_gas else None,
                       gases=gases, temperature=temperature)
     Sm = tc.path_matrix(c["L"], c["NLAYIN"], c["LAYINC"], c["SCALE"])
     ref = tc.collapsed(tautot, np.asarray(c["delg"], dtype=np.float64), Sm, c["weight"], dtau)
@@ -130,8 +149,8 @@ def _check_case(eng, oracle, c, dcont="dcont", gases=None, temperature=True, eve
     _compare("oracle, collapsed", got, ref, c["weight"])
     dc = None if dcont is None else np.array(c[dcont])
     if every_gas:                                        # the un-collapsed call takes the shared term inside dtaucon
-        dc = np.zeros((c["W"], NPAR, c["L"])) if dc is None else dc
-        dc[:, :NVMR, :] += c["dray"][:, None, :]
+        dc = np.zeros((c["W"], npar, c["L"])) if dc is None else dc
+        dc[:, :nvmr, :] += c["dray"][:, None, :]
     _compare("same engine, un-collapsed", got, _uncollapsed_on_engine(eng, c, dc), c["weight"])
     return got
 
@@ -147,6 +166,25 @@ def test_transit_vs_oracle_and_vs_uncollapsed_route(eng, oracle):
 @pytest.mark.parametrize("W", [64, 1])
 def test_transit_whole_tile_and_single_wavenumber(eng, oracle, W):
     _check_case(eng, oracle, _case(W))
+
+
+def test_transit_slab_of_seventeen_slots(eng, oracle):
+    """G = 20, S = 16 of the other fused routes' wide case: k_transit_grad's LDS [G + NP1][64] with 17 slots, NVMR = 18, a
+    permuted gas map"""
+    got = _check_case(eng, oracle, _wide_case())
+    assert np.all(np.abs(got[2]).max(axis=(0, 2)) > 0)
+
+
+@pytest.mark.parametrize("G,S", [(32, 3), (27, 5), (20, 31), (32, 31)])
+def test_transit_at_the_size_limits(eng, oracle, G, S):
+    """The (G, S) of the other fused routes' size cases (SIZE_CASES of test_limb_gpu.py).  This route has no chunk rule:
+    k_transit_grad holds [G + NP1][64] doubles, 32 KiB at G = 32, S = 31, and reads gas 30 and the temperature from bits 30 and
+    31 of the mask.  Same references and bounds as every case of this file."""
+    from test_limb_gpu import assert_size_case
+    assert_size_case(G, S)
+    assert (G + S + 1) * 512 <= 64 * 1024
+    got = _check_case(eng, oracle, _wide_case(G, S))
+    assert np.all(np.abs(got[2]).max(axis=(0, 2)) > 0)
 
 
 def test_transit_on_lbl_table(eng, oracle):
