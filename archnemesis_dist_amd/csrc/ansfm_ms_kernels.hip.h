@@ -67,7 +67,7 @@ struct MsParams {
     int npre;
     size_t st_wl, st_wcl, st_wm, st_rad;   // strides between models: tauray [W][L], lfrac [W][ncont][L], radg [W][nmu], rad
     size_t st_drad;                        // ... and drad (k_ms_chain_lane<N, CACHE> leaves the orders to k_ms_fourier)
-    // The continuum by rows (ansfm_cirsrad_ck_scatter_batch_rows): tauray / lfrac are the slab's copies k_ms_optics_rows wrote
+    // The continuum by rows (ansfm_cirsrad_ck_scatter_batch_rows): tauray / lfrac are the slab's copies k_ms_optics<true> wrote
     // beside taus / omegas / bnu, [model of the launch][wcount][..] relative to w0, st_wl / st_wcl the strides between launch
     // positions.  0: the batch's input arrays, by model over the whole axis.
     int cont_local;
@@ -1317,65 +1317,56 @@ __global__ void k_ms_fourier(MsParams p)
 // ---- scattering branch of CIRSrad on the device -----------------------------------------------------------------------
 // calculate_layer_opacity (ForwardModel_0.py:3989) and the host preparation of scloud11wave (:5099-5119) for the arrays that
 // have a g axis: TAUTOT = TAUGAS + TAUCIA + TAUDUST + TAURAY, OMEGA = (TAURAY + TAUSCAT) / TAUTOT where TAUTOT > 0, and
-// BB = planck(TEMP) -- from the merge kernel's [L][G][Wpad] gas opacities straight into the layouts the chain kernels
-// read, so that TAUGAS / TAUTOT / OMEGA (NWAVE x NG x NLAY each) never leave HBM.  One thread per (wavenumber, layer).
+// BB = planck(TEMP) -- from the merge kernel's [rows][G][Wpad] gas opacities straight into the layouts the chain kernels
+// read, so that TAUGAS / TAUTOT / OMEGA (NWAVE x NG x NLAY each) never leave HBM.
+// For the models [m0, m0 + nm) of a batch on the wavenumbers [w0, w0 + wcount): the gas opacity of (model, layer) is row
+// slot[model][layer] of the merge kernel's output (rows shared with model 0 where the layer inputs are identical), the outputs
+// are laid out [model of the launch][wavenumber of the slab][..].  One model per call is the batch of one over the whole
+// axis: slot = model_ids = nullptr, w0 = m0 = 0, wcount = W, nm = 1.
+// The continuum is dense, [n][W][L], or (ROWS) handed over once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows): rows
+// [R][W] of TAUCIA / TAUDUST / TAURAY / TAUSCAT and [R][ncont][W] of the aerosol fractions, wavenumber fastest, and cont_row
+// [n][L], the row of layer l of model m.  The ROWS build also writes the slab's copies of TAURAY and the fractions the chain
+// kernels read (MsParams::cont_local).
 struct MsOpticsParams {
-    const double *taugas;       // [L][G][Wpad]
-    const double *taucia;       // [W][L] or null
-    const double *taudust;      // [W][L] aerosol extinction summed over the populations, or null
-    const double *tauray;       // [W][L] or null
-    const double *tauscat;      // [W][L] or null
-    const double *wave;         // [W]
-    const double *lay_temp;     // [L]
-    double *taus, *omegas;      // [W][G][L]
-    double *bnu;                // [W][L]
-    int W, Wpad, G, L, ispace;
-};
-
-__global__ __launch_bounds__(128) void k_ms_optics(MsOpticsParams p)
-{
-    const int w = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
-    if (w >= p.W) return;
-    const size_t wl = (size_t)w * p.L + l;
-    const double cia = p.taucia ? p.taucia[wl] : 0.0, dust = p.taudust ? p.taudust[wl] : 0.0;
-    const double ray = p.tauray ? p.tauray[wl] : 0.0, sca = p.tauscat ? p.tauscat[wl] : 0.0;
-    for (int g = 0; g < p.G; ++g) {
-        const double tt = ((p.taugas[((size_t)l * p.G + g) * p.Wpad + w] + cia) + dust) + ray;      // the sum order of :3989
-        const size_t o = ((size_t)w * p.G + g) * p.L + l;
-        p.taus[o] = tt;
-        p.omegas[o] = (tt > 0.0) ? (ray + sca) / tt : 0.0;
-    }
-    const double c1 = 1.1911e-12, c2 = 1.439;                     // ForwardModel_0.py:6214-6215
-    const double wv = p.wave[w];
-    double y, a;
-    if (p.ispace == 0) { y = wv; a = c1 * (y * y * y); }
-    else { y = 1.0e4 / wv; a = c1 * (y * y * y * y * y) / 1.0e4; }
-    p.bnu[wl] = a / (exp(c2 * y / p.lay_temp[l]) - 1.0);
-}
-
-// The same for the models [m0, m0 + nm) of a batch on the wavenumbers [w0, w0 + wcount): the gas opacity of (model, layer)
-// is row slot[model][layer] of the merge kernel's output (rows shared with model 0 where the layer inputs are identical),
-// the continuum arrays carry a model axis, the outputs are laid out [model of the launch][wavenumber of the slab][..].
-struct MsOpticsBatchParams {
     const double *taugas;       // [rows][G][Wpad]
-    const int32_t *slot;        // [n][L]
-    const double *taucia, *taudust, *tauray, *tauscat;   // [n][W][L] or null
+    const int32_t *slot;        // [n][L], or null: layer l reads row l
+    const int32_t *cont_row;    // ROWS: [n][L]
+    const double *taucia, *taudust, *tauray, *tauscat;   // [n][W][L], ROWS: [R][W]; or null
+    const double *lfrac;        // ROWS: [R][ncont][W] (ncont > 0)
     const double *wave;         // [W]
     const double *lay_temp;     // [n][L]
     double *taus, *omegas;      // [nm][wcount][G][L]
     double *bnu;                // [nm][wcount][L]
+    double *tauray_l;           // ROWS: [nm][wcount][L]
+    double *lfrac_l;            // ROWS: [nm][wcount][ncont][L]
     const int *model_ids;       // launch position -> model (null: position m0 + ml is the model)
-    int W, Wpad, G, L, ispace, w0, wcount, m0, nm;
+    int W, Wpad, G, L, ncont, ispace, w0, wcount, m0, nm;
 };
-__global__ __launch_bounds__(128) void k_ms_optics_batch(MsOpticsBatchParams p)
+
+// planck_wave (ForwardModel_0.py:6214-6215): v a wavenumber (ispace = 0) or a wavelength in micron
+__device__ __forceinline__ double ms_planck(int ispace, double v, double T)
+{
+    const double c1 = 1.1911e-12, c2 = 1.439;
+    double y, a;
+    if (ispace == 0) { y = v; a = c1 * (y * y * y); }
+    else { y = 1.0e4 / v; a = c1 * (y * y * y * y * y) / 1.0e4; }
+    return a / (exp(c2 * y / T) - 1.0);
+}
+
+// One thread per wavenumber of the slab, one block row per layer, one block plane per model of the launch.  Dense: a thread
+// reads [m][W][L] at stride L.  ROWS: the row index is uniform per (model, layer), so a wavefront reads 64 consecutive doubles
+// of every row.
+template <bool ROWS> __global__ __launch_bounds__(128) void k_ms_optics(MsOpticsParams p)
 {
     const int wl = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y, ml = blockIdx.z;
     if (wl >= p.wcount) return;
     const int w = p.w0 + wl, m = p.model_ids ? p.model_ids[p.m0 + ml] : p.m0 + ml;
-    const size_t in = ((size_t)m * p.W + w) * p.L + l;
+    const size_t ml_l = (size_t)m * p.L + l;
+    const size_t cr = ROWS ? (size_t)p.cont_row[ml_l] : 0;
+    const size_t in = ROWS ? cr * p.W + w : ((size_t)m * p.W + w) * p.L + l;
     const double cia = p.taucia ? p.taucia[in] : 0.0, dust = p.taudust ? p.taudust[in] : 0.0;
     const double ray = p.tauray ? p.tauray[in] : 0.0, sca = p.tauscat ? p.tauscat[in] : 0.0;
-    const size_t row = (size_t)p.slot[(size_t)m * p.L + l];
+    const size_t row = p.slot ? (size_t)p.slot[ml_l] : (size_t)l;
     const size_t wrow = (size_t)ml * p.wcount + wl;
     for (int g = 0; g < p.G; ++g) {
         const double tt = ((p.taugas[(row * p.G + g) * p.Wpad + w] + cia) + dust) + ray;             // the sum order of :3989
@@ -1383,23 +1374,25 @@ __global__ __launch_bounds__(128) void k_ms_optics_batch(MsOpticsBatchParams p)
         p.taus[o] = tt;
         p.omegas[o] = (tt > 0.0) ? (ray + sca) / tt : 0.0;
     }
-    const double c1 = 1.1911e-12, c2 = 1.439;
-    const double wv = p.wave[w];
-    double y, a;
-    if (p.ispace == 0) { y = wv; a = c1 * (y * y * y); }
-    else { y = 1.0e4 / wv; a = c1 * (y * y * y * y * y) / 1.0e4; }
-    p.bnu[wrow * p.L + l] = a / (exp(c2 * y / p.lay_temp[(size_t)m * p.L + l]) - 1.0);
+    if constexpr (ROWS) {
+        p.tauray_l[wrow * p.L + l] = ray;
+        for (int c = 0; c < p.ncont; ++c) p.lfrac_l[(wrow * p.ncont + c) * p.L + l] = p.lfrac[(cr * p.ncont + c) * p.W + w];
+    }
+    p.bnu[wrow * p.L + l] = ms_planck(p.ispace, p.wave[w], p.lay_temp[ml_l]);
 }
 
-// same[m][l] = 1 when every input of layer l of model m is bit-identical to model 0's: the gas opacity row is shared (which
-// covers pressure, temperature and the gas amounts) ...
-__global__ void k_ms_same_init(int n_models, int L, const int32_t *__restrict__ slot, unsigned char *__restrict__ same)
+// same[m][l] = 1 when every input of layer l of model m is model 0's.  From the index maps: the gas-opacity row is shared
+// (which covers pressure, temperature and the gas amounts) and, with cont_row, so is the continuum row -- no data is compared
+// there: equal content under two indices counts as different (the layer is recomputed, with the bits of a separate call).
+// cont_row = nullptr, the dense continuum: k_ms_same_cols compares its columns next.
+__global__ void k_ms_same_index(int n_models, int L, const int32_t *__restrict__ slot, const int32_t *__restrict__ cont_row,
+                                unsigned char *__restrict__ same)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_models * L) same[i] = (slot[i] == i % L) ? 1 : 0;
+    if (i < n_models * L) same[i] = (slot[i] == i % L && (!cont_row || cont_row[i] == cont_row[i % L])) ? 1 : 0;
 }
-// ... and so are its columns of the (wavenumber, layer) arrays: arr [n][W][X][L] (X = 1 for the continuum opacities, ncont
-// for the aerosol fractions).  One thread per (model, wavenumber, x); a differing element clears the layer's flag.
+// arr [n][W][X][L] (X = 1 for the continuum opacities, ncont for the aerosol fractions).  One thread per (model, wavenumber, x);
+// a differing element clears the layer's flag.
 __global__ void k_ms_same_cols(int n_models, int W, int X, int L, const double *__restrict__ arr, unsigned char *__restrict__ same)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1409,62 +1402,6 @@ __global__ void k_ms_same_cols(int n_models, int W, int X, int L, const double *
     const double *a = arr + (m * per + r) * L, *b = arr + r * L;
     for (int l = 0; l < L; ++l)
         if (__double_as_longlong(a[l]) != __double_as_longlong(b[l])) same[m * L + l] = 0;
-}
-
-// The continuum handed over once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows): rows [R][W] of TAUCIA / TAUDUST /
-// TAURAY / TAUSCAT and [R][ncont][W] of the aerosol fractions, wavenumber fastest, and cont_row [n][L], the row of layer l of
-// model m.  k_ms_optics_batch's job from them -- the same arithmetic per (wavenumber, g, layer) -- and the slab's copies of
-// TAURAY and the fractions the chain kernels read (MsParams::cont_local).  One thread per wavenumber of the slab: the row
-// index is uniform per (model, layer), so a wavefront reads 64 consecutive doubles of every row.
-struct MsOpticsRowsParams {
-    const double *taugas;       // [rows][G][Wpad]
-    const int32_t *slot;        // [n][L]
-    const int32_t *cont_row;    // [n][L]
-    const double *taucia, *taudust, *tauray, *tauscat;   // [R][W] or null
-    const double *lfrac;        // [R][ncont][W] (ncont > 0)
-    const double *wave;         // [W]
-    const double *lay_temp;     // [n][L]
-    double *taus, *omegas;      // [nm][wcount][G][L]
-    double *bnu, *tauray_l;     // [nm][wcount][L]
-    double *lfrac_l;            // [nm][wcount][ncont][L]
-    const int *model_ids;       // launch position -> model (null: position m0 + ml is the model)
-    int W, Wpad, G, L, ncont, ispace, w0, wcount, m0, nm;
-};
-__global__ __launch_bounds__(128) void k_ms_optics_rows(MsOpticsRowsParams p)
-{
-    const int wl = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y, ml = blockIdx.z;
-    if (wl >= p.wcount) return;
-    const int w = p.w0 + wl, m = p.model_ids ? p.model_ids[p.m0 + ml] : p.m0 + ml;
-    const size_t ml_l = (size_t)m * p.L + l;
-    const size_t cr = (size_t)p.cont_row[ml_l];
-    const size_t in = cr * p.W + w;
-    const double cia = p.taucia ? p.taucia[in] : 0.0, dust = p.taudust ? p.taudust[in] : 0.0;
-    const double ray = p.tauray ? p.tauray[in] : 0.0, sca = p.tauscat ? p.tauscat[in] : 0.0;
-    const size_t row = (size_t)p.slot[ml_l];
-    const size_t wrow = (size_t)ml * p.wcount + wl;
-    for (int g = 0; g < p.G; ++g) {
-        const double tt = ((p.taugas[(row * p.G + g) * p.Wpad + w] + cia) + dust) + ray;             // the sum order of :3989
-        const size_t o = (wrow * p.G + g) * p.L + l;
-        p.taus[o] = tt;
-        p.omegas[o] = (tt > 0.0) ? (ray + sca) / tt : 0.0;
-    }
-    p.tauray_l[wrow * p.L + l] = ray;
-    for (int c = 0; c < p.ncont; ++c) p.lfrac_l[(wrow * p.ncont + c) * p.L + l] = p.lfrac[(cr * p.ncont + c) * p.W + w];
-    const double c1 = 1.1911e-12, c2 = 1.439;
-    const double wv = p.wave[w];
-    double y, a;
-    if (p.ispace == 0) { y = wv; a = c1 * (y * y * y); }
-    else { y = 1.0e4 / wv; a = c1 * (y * y * y * y * y) / 1.0e4; }
-    p.bnu[wrow * p.L + l] = a / (exp(c2 * y / p.lay_temp[ml_l]) - 1.0);
-}
-
-// same[m][l] from the two index maps: the gas-opacity row is model 0's and so is the continuum row.  No data is compared: equal
-// content under two indices counts as different (the layer is recomputed, with the bits of a separate call).
-__global__ void k_ms_same_index(int n_models, int L, const int32_t *__restrict__ slot, const int32_t *__restrict__ cont_row,
-                                unsigned char *__restrict__ same)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_models * L) same[i] = (slot[i] == i % L && cont_row[i] == cont_row[i % L]) ? 1 : 0;
 }
 
 // One model's dense array from the rows, for the model-by-model route: dst [W][X][L] = rows [R][X][W] at cont_row[l] (X = 1:

@@ -437,50 +437,86 @@ int ansfm_scloud11wave_core(ansfm_ctx *ctx, int ncont, int nwave, int nth, const
     return ANSFM_OK;
 }
 
+// The host arrays of a scattering call on the device (null: not given).  The continuum of one model is [W][L] / [W][ncont][L], of
+// a batch [n][W][L] / [n][W][ncont][L] or, by rows, [R][W] / [R][ncont][W] with d_crow [n][L].
+struct MsStaged {
+    const double *press, *temp, *am, *cia, *dust, *ray, *sca, *phas, *lf, *rg, *sol, *brdf, *xf;
+    const int32_t *d_crow;
+};
+
+// Reads c's host pointers; leaves their device copies in s (staging slots 0 .. 13, copies queued on ctx->stream).  CN: elements
+// of one continuum array (lfrac: CN * ncont); 0: the continuum and cont_row stay null (they are on the device already).
+static int ms_stage(ansfm_ctx *ctx, const MsCall &c, size_t CN, MsStaged &s)
+{
+    const size_t W = ctx->W, nl = (size_t)c.n_models * c.L;
+    Stager st{ctx};
+    s.press = st.up(c.lay_press_pa, nl); s.temp = st.up(c.lay_temp, nl); s.am = st.up(c.amount, nl * ctx->S);
+    s.cia = st.up(c.taucia, CN); s.dust = st.up(c.taudust, CN); s.ray = st.up(c.tauray, CN); s.sca = st.up(c.tauscat, CN);
+    s.phas = st.up(c.phasarr, (size_t)c.ncont * c.W_full * 2 * c.nth); s.lf = st.up(c.lfrac, CN * c.ncont);
+    s.rg = st.up(c.radg, c.n_models * W * c.nmu); s.sol = st.up(c.solar, W);
+    s.brdf = st.up(c.brdf_matrix, W * c.nmu * c.nmu * (c.nf + 1)); s.xf = st.up(c.xfac, W);
+    s.d_crow = st.up(c.cont_row, CN ? nl : 0);
+    return st.rc;
+}
+
+// The optics stage's parameters from the staged inputs and the context's buffers (reserve ms_taus / ms_omegas / ms_bnu and, by
+// rows, ms_tauray_l / ms_lfrac_l first).  slot: the gas row of every (model, layer), null for one model.  The launch fills in
+// the slab and the models.
+static MsOpticsParams ms_optics_params(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, const int32_t *slot)
+{
+    MsOpticsParams o;
+    memset(&o, 0, sizeof o);
+    o.taugas = ctx->tau.as<double>(); o.slot = slot; o.cont_row = s.d_crow;
+    o.taucia = s.cia; o.taudust = s.dust; o.tauray = s.ray; o.tauscat = s.sca; o.lfrac = s.lf;
+    o.wave = ctx->d_wave.as<double>(); o.lay_temp = s.temp;
+    o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
+    o.tauray_l = ctx->ms_tauray_l.as<double>(); o.lfrac_l = ctx->ms_lfrac_l.as<double>();
+    o.W = ctx->W; o.Wpad = ctx->Wpad; o.G = ctx->G; o.L = c.L; o.ncont = s.lf ? c.ncont : 0; o.ispace = c.ISPACE;
+    return o;
+}
+
+// TAUTOT, OMEGA, BB (by rows: and the slab's TAURAY / fractions) of the models [m0, m0 + nm) of the launch order ids (null:
+// position = model) on the wavenumbers [w0, w0 + wc)
+static void ms_launch_optics(hipStream_t st, MsOpticsParams &o, int w0, int wc, int m0, int nm, const int *ids)
+{
+    o.w0 = w0; o.wcount = wc; o.m0 = m0; o.nm = nm; o.model_ids = ids;
+    const dim3 grid(nblk((size_t)wc, 128), (unsigned)o.L, (unsigned)nm);
+    if (o.cont_row) hipLaunchKernelGGL(k_ms_optics<true>, grid, dim3(128), 0, st, o);
+    else hipLaunchKernelGGL(k_ms_optics<false>, grid, dim3(128), 0, st, o);
+}
+
 // one model; reuse_walk: ms_single's; dc: its continuum on the device instead of c's host arrays
 static int cirsrad_ck_scatter_impl(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, bool reuse_walk, const MsDevCont *dc = nullptr)
 {
     int rc = ms_check(ctx, c, "cirsrad_ck_scatter");
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, L = c.L;
+    const int W = ctx->W, G = ctx->G, L = c.L;
     MsParams p;
     MsRoute r;
     if ((rc = ms_setup(ctx, p, c, W, G, L, kn, r))) return rc;
     const size_t D = sizeof(double), WL = (size_t)W * L;
-    Stager st{ctx};
-    const double *press = st.up(c.lay_press_pa, L), *temp = st.up(c.lay_temp, L), *am = st.up(c.amount, (size_t)S * L),
-                 *cia = st.up(dc ? nullptr : c.taucia, WL), *dust = st.up(dc ? nullptr : c.taudust, WL),
-                 *ray = st.up(dc ? nullptr : c.tauray, WL), *sca = st.up(dc ? nullptr : c.tauscat, WL),
-                 *phas = st.up(c.phasarr, (size_t)c.ncont * W * 2 * c.nth), *lf = st.up(dc ? nullptr : c.lfrac, WL * c.ncont),
-                 *rg = st.up(c.radg, (size_t)W * c.nmu), *sol = st.up(c.solar, W),
-                 *brdf = st.up(c.brdf_matrix, (size_t)W * c.nmu * c.nmu * (c.nf + 1)), *xf = st.up(c.xfac, W);
-    if ((rc = st.rc)) return rc;
-    if (dc) { cia = dc->cia; dust = dc->dust; ray = dc->ray; sca = dc->sca; lf = dc->lf; }
+    MsStaged s;
+    if ((rc = ms_stage(ctx, c, dc ? 0 : WL, s))) return rc;
+    if (dc) { s.cia = dc->cia; s.dust = dc->dust; s.ray = dc->ray; s.sca = dc->sca; s.lf = dc->lf; }
     // ---- vertical gas opacities: calc_k + k_overlap (:3855-3874), as in the thermal branch --------------------------
     HIPCHK(ctx->ms_taus.reserve(WL * G * D));
     HIPCHK(ctx->ms_omegas.reserve(WL * G * D));
     HIPCHK(ctx->ms_bnu.reserve(WL * D));
-    const double *d_tauray = ray;
-    if ((rc = ms_zero_tauray(ctx, WL, &d_tauray)) || (rc = gas_opacity(ctx, L, press, temp, am))) return rc;
+    const double *d_tauray = s.ray;
+    if ((rc = ms_zero_tauray(ctx, WL, &d_tauray)) || (rc = gas_opacity(ctx, L, s.press, s.temp, s.am))) return rc;
     ctx->last_n = 1; ctx->last_L = L; ctx->last_rows = L; ctx->last_dedup = 0;
     // ---- TAUTOT, OMEGA, BB -----------------------------------------------------------------------------------------
-    MsOpticsParams o;
-    memset(&o, 0, sizeof o);
-    o.taugas = ctx->tau.as<double>(); o.taucia = cia; o.taudust = dust;
-    o.tauray = ray; o.tauscat = sca;
-    o.wave = ctx->d_wave.as<double>(); o.lay_temp = temp;
-    o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
-    o.W = W; o.Wpad = Wpad; o.G = G; o.L = L; o.ispace = c.ISPACE;
-    hipLaunchKernelGGL(k_ms_optics, dim3(nblk((size_t)W, 128), (unsigned)L), dim3(128), 0, ctx->stream, o);
+    MsOpticsParams o = ms_optics_params(ctx, c, s, nullptr);
+    ms_launch_optics(ctx->stream, o, 0, W, 0, 1, nullptr);
     HIPCHK(hipGetLastError());
     // ---- doubling / adding, g-quadrature ------------------------------------------------------------------------------
-    p.phasarr = phas; p.radg = rg; p.solar = sol;
-    p.brdf = brdf; p.bnu = o.bnu; p.taus = o.taus; p.tauray = d_tauray; p.omegas = o.omegas;
-    p.lfrac = lf;
+    p.phasarr = s.phas; p.radg = s.rg; p.solar = s.sol;
+    p.brdf = s.brdf; p.bnu = o.bnu; p.taus = o.taus; p.tauray = d_tauray; p.omegas = o.omegas;
+    p.lfrac = s.lf;
     if (p.nmu_real && (rc = ms_pad_inputs(ctx, c.nmu, (size_t)W, (size_t)W, c.nf, &p.radg, &p.brdf))) return rc;
     if ((rc = ms_single(ctx, p, r, kn, reuse_walk))) return rc;
-    return ms_gquad(ctx, 1, c.ngeom, xf, c.SPECOUT, c.SPEC_G, nullptr);
+    return ms_gquad(ctx, 1, c.ngeom, s.xf, c.SPECOUT, c.SPEC_G, nullptr);
 }
 
 int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
@@ -501,189 +537,185 @@ int ansfm_cirsrad_ck_scatter(ansfm_ctx *ctx, int ISPACE, int L, const double *la
 /* ------------------------------------------------------------------------------------------ */
 /* batched scattering branch: the forward models of a numerical Jacobian (jacobian_nemesis :2251-2252)   */
 /* ------------------------------------------------------------------------------------------ */
-static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
+// The stages of cirsrad_ck_scatter_batch_impl, in the order it calls them.
+
+// Reads c.R and c.cont_row (host); launches nothing.  Dense calls pass.
+static int ms_check_rows(ansfm_ctx *ctx, const MsCall &c)
 {
-    int rc = ms_check(ctx, c, "cirsrad_ck_scatter_batch");
-    if (rc) return rc;
-    const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, S = ctx->S, L = c.L, n_models = c.n_models;
-    const int ncont = c.ncont, ngeom = c.ngeom, nmu = c.nmu, nf = c.nf, w_begin = c.w_begin;
-    const bool sliced = c.W_full != W;
+    if (!c.cont_row) return ANSFM_OK;
+    const int L = c.L;
+    if (c.R <= 0) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: R must be positive");
+    for (size_t i = 0; i < (size_t)c.n_models * L; ++i)
+        if (c.cont_row[i] < 0 || c.cont_row[i] >= c.R)
+            FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: cont_row[" + std::to_string(i / L) + "][" + std::to_string(i % L) +
+                                        "] = " + std::to_string(c.cont_row[i]) + " is outside [0, R = " + std::to_string(c.R) + ")");
+    return ANSFM_OK;
+}
+
+// The whole call without the layer cache -- a single model, de-duplication switched off (ansfm_set_layer_dedup),
+// ANSFM_MS_LAYER_CACHE=0 or a runtime line source: model by model through cirsrad_ck_scatter_impl; m > 0: same phase functions,
+// quadrature, orders -- model 0's walk stands.  Reads c; leaves every model's SPECOUT and the last_* counters.
+// By rows: the rows go up once, behind the staging slots of the single-model entry; a model's dense arrays are formed from them
+// on the device, one model at a time in one buffer (ctx->ms_tauray_l).
+static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
+{
+    const int W = ctx->W, S = ctx->S, L = c.L, n_models = c.n_models, ncont = c.ncont;
     const size_t D = sizeof(double), WL = (size_t)W * L;
     const bool by_rows = c.cont_row != nullptr;
     const size_t RW = by_rows ? (size_t)c.R * W : 0;
-    if (by_rows) {                                              // before anything is launched
-        if (c.R <= 0) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: R must be positive");
-        for (size_t i = 0; i < (size_t)n_models * L; ++i)
-            if (c.cont_row[i] < 0 || c.cont_row[i] >= c.R)
-                FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: cont_row[" + std::to_string(i / L) + "][" + std::to_string(i % L) +
-                                            "] = " + std::to_string(c.cont_row[i]) + " is outside [0, R = " + std::to_string(c.R) + ")");
+    int rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    Stager sr{ctx, 14};
+    const int32_t *d_crow = by_rows ? sr.up(c.cont_row, (size_t)n_models * L) : nullptr;
+    const double *rsrc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (by_rows) {
+        rsrc[0] = sr.up(c.taucia, RW); rsrc[1] = sr.up(c.taudust, RW); rsrc[2] = sr.up(c.tauray, RW); rsrc[3] = sr.up(c.tauscat, RW);
+        rsrc[4] = sr.up(c.lfrac, RW * ncont);
+        if ((rc = sr.rc)) return rc;
+        HIPCHK(ctx->ms_tauray_l.reserve((4 + (size_t)ncont) * WL * D));
     }
-    ctx->ms_cache_hits = 0; ctx->ms_cache_layers = (long)n_models * L;
-    // (a runtime line source has its own row map, which the (p, T, amount) comparison of the layer cache does not see)
-    const bool use_cache = n_models > 1 && ctx->dedup && kn.layer_cache && !ctx->lblrt;      // any stream count
-    if (!use_cache && sliced)
-        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter_batch_slice: a slice needs the layer cache (n_models > 1, layer de-duplication on)");
-    if (!use_cache) {
-        // a single model, or de-duplication switched off (ansfm_set_layer_dedup): model by model; m > 0: same phase functions,
-        // quadrature, orders -- model 0's walk stands
-        // by rows: the rows go up once, behind the staging slots of the single-model entry; a model's dense arrays are formed
-        // from them on the device, one model at a time in one buffer
-        HIPCHK(hipSetDevice(ctx->device));
-        Stager sr{ctx, 14};
-        const int32_t *d_crow = by_rows ? sr.up(c.cont_row, (size_t)n_models * L) : nullptr;
-        const double *rsrc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int m = 0; m < n_models; ++m) {
+        const size_t mm = m;
+        MsCall cm = c;
+        cm.n_models = 1;
+        cm.lay_press_pa += mm * L; cm.lay_temp += mm * L; cm.amount += mm * S * L;
+        cm.radg += mm * W * c.nmu; cm.SPECOUT += mm * W * c.ngeom;
+        if (ctx->lblrt) ctx->st_m0 = m;                      // gas_tau reads this model's rows of the state
         if (by_rows) {
-            rsrc[0] = sr.up(c.taucia, RW); rsrc[1] = sr.up(c.taudust, RW); rsrc[2] = sr.up(c.tauray, RW); rsrc[3] = sr.up(c.tauscat, RW);
-            rsrc[4] = sr.up(c.lfrac, RW * ncont);
-            if ((rc = sr.rc)) return rc;
-            HIPCHK(ctx->ms_tauray_l.reserve((4 + (size_t)ncont) * WL * D));
-        }
-        for (int m = 0; m < n_models; ++m) {
-            const size_t mm = m;
-            MsCall cm = c;
-            cm.n_models = 1;
-            cm.lay_press_pa += mm * L; cm.lay_temp += mm * L; cm.amount += mm * S * L;
-            cm.radg += mm * W * nmu; cm.SPECOUT += mm * W * ngeom;
-            if (ctx->lblrt) ctx->st_m0 = m;                      // gas_tau reads this model's rows of the state
-            if (by_rows) {
-                const double *dense[5];
-                for (int a = 0; a < 5; ++a) {
-                    const int X = a < 4 ? 1 : ncont;
-                    double *dst = ctx->ms_tauray_l.as<double>() + (size_t)a * WL;
-                    dense[a] = (rsrc[a] && X > 0) ? dst : nullptr;
-                    if (dense[a])
-                        hipLaunchKernelGGL(k_ms_rows_expand, dim3(nblk((size_t)W, 128), (unsigned)L, (unsigned)X), dim3(128), 0, ctx->stream,
-                                           W, X, L, d_crow + mm * L, rsrc[a], dst);
-                }
-                HIPCHK(hipGetLastError());
-                const MsDevCont dc{dense[0], dense[1], dense[2], dense[3], dense[4]};
-                rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0, &dc);
-                ctx->st_m0 = -1;
-                if (rc) return rc;
-                continue;
+            const double *dense[5];
+            for (int a = 0; a < 5; ++a) {
+                const int X = a < 4 ? 1 : ncont;
+                double *dst = ctx->ms_tauray_l.as<double>() + (size_t)a * WL;
+                dense[a] = (rsrc[a] && X > 0) ? dst : nullptr;
+                if (dense[a])
+                    hipLaunchKernelGGL(k_ms_rows_expand, dim3(nblk((size_t)W, 128), (unsigned)L, (unsigned)X), dim3(128), 0, ctx->stream,
+                                       W, X, L, d_crow + mm * L, rsrc[a], dst);
             }
+            HIPCHK(hipGetLastError());
+            const MsDevCont dc{dense[0], dense[1], dense[2], dense[3], dense[4]};
+            rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0, &dc);
+        } else {
             for (const double **a : {&cm.taucia, &cm.taudust, &cm.tauray, &cm.tauscat}) if (*a) *a += mm * WL;
             if (cm.lfrac) cm.lfrac += mm * WL * ncont;
             rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0);
-            ctx->st_m0 = -1;
-            if (rc) return rc;
         }
-        ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = n_models * L; ctx->last_dedup = 0;
-        return ANSFM_OK;
+        ctx->st_m0 = -1;
+        if (rc) return rc;
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    MsParams p;
-    MsRoute r;
-    if ((rc = ms_setup(ctx, p, c, W, G, L, kn, r))) return rc;
+    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = n_models * L; ctx->last_dedup = 0;
+    return ANSFM_OK;
+}
+
+// Which layers equal model 0's in EVERY input, and where a model's adding sweep may start.  Reads ctx->dd_slot (dedup_rows), the
+// staged continuum or cont_row, and c.radg on the host.  Leaves same[n][L] in ctx->ms_same (*same), the sweep starts [n] and the
+// launch order [n] in ctx->ms_lstart, the ms_cache_* counters and *npre, the prefix stacks per model; synchronises the stream.
+static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, const MsStaged &s, bool lookup, unsigned char **same_out,
+                          int *npre_out)
+{
+    const int W = ctx->W, L = c.L, n_models = c.n_models, ncont = c.ncont;
     const size_t nl = (size_t)n_models * L;
-    const size_t CN = by_rows ? RW : n_models * WL;            // elements of a continuum array: rows, or dense
-    Stager st{ctx};
-    const double *press = st.up(c.lay_press_pa, nl), *temp = st.up(c.lay_temp, nl), *am = st.up(c.amount, nl * S),
-                 *cia = st.up(c.taucia, CN), *dust = st.up(c.taudust, CN), *ray = st.up(c.tauray, CN),
-                 *sca = st.up(c.tauscat, CN), *phas = st.up(c.phasarr, (size_t)ncont * c.W_full * 2 * c.nth),
-                 *lf = st.up(c.lfrac, CN * ncont), *rg = st.up(c.radg, (size_t)n_models * W * nmu), *sol = st.up(c.solar, W),
-                 *brdf = st.up(c.brdf_matrix, (size_t)W * nmu * nmu * (nf + 1)), *xf = st.up(c.xfac, W);
-    const int32_t *d_crow = st.up(c.cont_row, by_rows ? nl : 0);
-    if ((rc = st.rc)) return rc;
-    const double *d_tauray = ray;                               // no TAURAY: every model reads the same zeros
-    if (!by_rows && (rc = ms_zero_tauray(ctx, WL, &d_tauray))) return rc;     // (by rows: the optics stage writes the slab's copy)
-    // ---- vertical gas opacities of the distinct (model, layer) rows: calc_k + k_overlap ---------------------------------
-    DedupRows k;
-    if ((rc = dedup_rows(ctx, n_models, L, press, temp, am, nullptr, nullptr, &k)) || (rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount)))
-        return rc;
-    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = k.rows; ctx->last_dedup = 1;
-    // ---- which layers equal model 0's in EVERY input --------------------------------------------------------------------
+    const bool by_rows = c.cont_row != nullptr;
     HIPCHK(ctx->ms_same.reserve(nl));
-    unsigned char *same = ctx->ms_same.as<unsigned char>();
-    if (by_rows)                                                // from the two index maps: no data is compared
-        hipLaunchKernelGGL(k_ms_same_index, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), d_crow,
-                           same);
-    else
-        hipLaunchKernelGGL(k_ms_same_init, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), same);
-    for (const double *col : {cia, dust, ray, sca})
+    unsigned char *same = *same_out = ctx->ms_same.as<unsigned char>();
+    // by rows: from the two index maps alone; dense: the gas rows, then the columns of every continuum array
+    hipLaunchKernelGGL(k_ms_same_index, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n_models, L, ctx->dd_slot.as<int32_t>(), s.d_crow,
+                       same);
+    for (const double *col : {s.cia, s.dust, s.ray, s.sca})
         if (col && !by_rows)
             hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W, 128)), dim3(128), 0, ctx->stream, n_models, W,
                                1, L, col, same);
-    if (lf && ncont > 0 && !by_rows)
+    if (s.lf && ncont > 0 && !by_rows)
         hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W * ncont, 128)), dim3(128), 0, ctx->stream,
-                           n_models, W, ncont, L, lf, same);
+                           n_models, W, ncont, L, s.lf, same);
     HIPCHK(hipGetLastError());
     // where a model's adding sweep may start: below its first changed layer (in sweep order: bottom first when the paths look
     // down, top first when they look up) the stack equals model 0's, kept after every kMsPrefixStep-th layer
-    const bool lookup = p.lookup;
-    const int npre = L / kMsPrefixStep;
-    {
-        std::vector<unsigned char> hs(nl);
-        HIPCHK(hipMemcpyAsync(hs.data(), same, nl, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        long hits = 0;
-        for (size_t k = (size_t)L; k < nl; ++k) hits += hs[k];
-        ctx->ms_cache_hits = hits; ctx->ms_cache_layers = (long)(n_models - 1) * L;
-        std::vector<int> lstart((size_t)n_models, 0);
-        for (int m = 1; m < n_models && kn.prefix; ++m) {
-            int lf = 0;
-            while (lf < L && hs[(size_t)m * L + (lookup ? L - 1 - lf : lf)]) ++lf;
-            // the lower boundary sits at the bottom of a look-down stack: its radiance must be model 0's too
-            if (c.lowbc > 0 && !lookup &&
-                memcmp(c.radg + (size_t)m * W * nmu, c.radg, (size_t)W * nmu * D) != 0)
-                lf = 0;
-            lstart[m] = std::min(lf / kMsPrefixStep, npre) * kMsPrefixStep;
-        }
-        // launch order of models 1 .. n-1: by sweep start, so that the blocks of one launch read the same layers of the cache at
-        // about the same time (position 0 of the list is unused: model 0 has its own launch)
-        std::vector<int> ids((size_t)n_models, 0);
-        for (int m = 0; m < n_models; ++m) ids[m] = m;
-        std::stable_sort(ids.begin() + 1, ids.end(), [&](int a, int b) { return lstart[a] < lstart[b]; });
-        HIPCHK(ctx->ms_lstart.reserve((size_t)2 * n_models * sizeof(int)));
-        HIPCHK(hipMemcpyAsync(ctx->ms_lstart.p, lstart.data(), (size_t)n_models * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(ctx->ms_lstart.as<int>() + n_models, ids.data(), (size_t)n_models * sizeof(int), hipMemcpyHostToDevice,
-                              ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int npre = *npre_out = L / kMsPrefixStep;
+    std::vector<unsigned char> hs(nl);
+    HIPCHK(hipMemcpyAsync(hs.data(), same, nl, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    long hits = 0;
+    for (size_t k = (size_t)L; k < nl; ++k) hits += hs[k];
+    ctx->ms_cache_hits = hits; ctx->ms_cache_layers = (long)(n_models - 1) * L;
+    std::vector<int> lstart((size_t)n_models, 0);
+    for (int m = 1; m < n_models && kn.prefix; ++m) {
+        int lf = 0;
+        while (lf < L && hs[(size_t)m * L + (lookup ? L - 1 - lf : lf)]) ++lf;
+        // the lower boundary sits at the bottom of a look-down stack: its radiance must be model 0's too
+        if (c.lowbc > 0 && !lookup &&
+            memcmp(c.radg + (size_t)m * W * c.nmu, c.radg, (size_t)W * c.nmu * sizeof(double)) != 0)
+            lf = 0;
+        lstart[m] = std::min(lf / kMsPrefixStep, npre) * kMsPrefixStep;
     }
-    // ---- phase matrices and Hansen factors: once, they do not depend on the model -----------------------------------------
-    p.phasarr = phas; p.radg = rg; p.solar = sol;
-    p.brdf = brdf; p.tauray = d_tauray; p.lfrac = lf;
-    if (p.nmu_real && (rc = ms_pad_inputs(ctx, nmu, (size_t)n_models * W, (size_t)W, nf, &p.radg, &p.brdf))) return rc;
-    const int nmu_k = p.nmu, ncomp = p.ncomp, ncomp_run = r.ncomp_run;    // nmu_k: the stream count the kernels run with
-    const size_t nn = (size_t)nmu_k * nmu_k;
-    const bool win = G == 1;
-    if (!win) {
-        // G > 1: the phase matrices of the whole axis and the whole walk in one launch, ahead of the slabs.  The walk continues
-        // from g to g + 1 over the whole axis, so a slice walks all of it too: its factors kept, the rest of the steps into a sink
-        const size_t per_w = (size_t)(nf + 1) * ncomp * nn, nph = (size_t)c.W_full * per_w, nfc = (size_t)G * W * ncomp * nn;
-        const size_t misc_n = 2 * nph + nfc + (sliced ? (size_t)ncomp * nn : 0);
-        HIPCHK(ctx->misc.reserve(misc_n * D));
-        HIPCHK(hipMemsetAsync(ctx->misc.p, 0, misc_n * D, ctx->stream));
-        p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph; p.fc = p.pmi + nph;
-        if (ncomp_run > 0) {
-            MsParams pw = p;
-            pw.nwave = c.W_full; pw.nwin = c.W_full;
-            ms_launch_phase(ctx->stream, pw);
-            if (sliced) { pw.st0 = w_begin; pw.stn = W; pw.sink = p.fc + nfc; }
-            ms_launch_hansen(ctx->stream, pw);
-            HIPCHK(hipGetLastError());
-        }
-        p.ppl += (size_t)w_begin * per_w; p.pmi += (size_t)w_begin * per_w;
+    // launch order of models 1 .. n-1: by sweep start, so that the blocks of one launch read the same layers of the cache at
+    // about the same time (position 0 of the list is unused: model 0 has its own launch)
+    std::vector<int> ids((size_t)n_models, 0);
+    for (int m = 0; m < n_models; ++m) ids[m] = m;
+    std::stable_sort(ids.begin() + 1, ids.end(), [&](int a, int b) { return lstart[a] < lstart[b]; });
+    HIPCHK(ctx->ms_lstart.reserve((size_t)2 * n_models * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(ctx->ms_lstart.p, lstart.data(), (size_t)n_models * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ctx->ms_lstart.as<int>() + n_models, ids.data(), (size_t)n_models * sizeof(int), hipMemcpyHostToDevice,
+                          ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
+// G > 1: the phase matrices of the whole axis and the whole walk in one launch, ahead of the slabs -- they do not depend on the
+// model.  The walk continues from g to g + 1 over the whole axis, so a slice walks all of it too: its factors kept, the rest of
+// the steps into a sink.  Reads p (sizes, phasarr); leaves ctx->misc zeroed and filled, p.ppl / p.pmi at the slice's first
+// wavenumber and p.fc.
+static int ms_walk_axis(ansfm_ctx *ctx, const MsCall &c, const MsRoute &r, MsParams &p)
+{
+    const int W = ctx->W, G = ctx->G;
+    const bool sliced = c.W_full != W;
+    const size_t D = sizeof(double), nn = (size_t)p.nmu * p.nmu;
+    const size_t per_w = (size_t)(c.nf + 1) * p.ncomp * nn, nph = (size_t)c.W_full * per_w, nfc = (size_t)G * W * p.ncomp * nn;
+    const size_t misc_n = 2 * nph + nfc + (sliced ? (size_t)p.ncomp * nn : 0);
+    HIPCHK(ctx->misc.reserve(misc_n * D));
+    HIPCHK(hipMemsetAsync(ctx->misc.p, 0, misc_n * D, ctx->stream));
+    p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph; p.fc = p.pmi + nph;
+    if (r.ncomp_run > 0) {
+        MsParams pw = p;
+        pw.nwave = c.W_full; pw.nwin = c.W_full;
+        ms_launch_phase(ctx->stream, pw);
+        if (sliced) { pw.st0 = c.w_begin; pw.stn = W; pw.sink = p.fc + nfc; }
+        ms_launch_hansen(ctx->stream, pw);
+        HIPCHK(hipGetLastError());
     }
-    // ---- slabs of the spectral axis sized by the layer cache ----------------------------------------------------------------
-    // 16 streams: the cache per wavenumber, and prefix stacks beside it.  Fewer: no prefix stacks (the adding sweep is a few per
-    // cent of a chain there), the cache per tile of 64 wavenumbers (the lane kernel's; the wavefront kernel keeps the layout).
-    const bool m16 = r.chain == MsChain::mfma16;
-    const long unit = m16 ? 1 : 64;
+    p.ppl += (size_t)c.w_begin * per_w; p.pmi += (size_t)c.w_begin * per_w;
+    return ANSFM_OK;
+}
+
+// The slabs of the spectral axis: Ws wavenumbers each, in units of `unit`, with per_unit bytes of layer cache and per_unit_pre
+// of prefix stacks per unit; at most mchunk models per launch of the cached chains.
+struct MsSlabs { long unit, Ws; size_t per_unit, per_unit_pre; int mchunk; };
+
+// Slabs sized by the layer cache.  16 streams: the cache per wavenumber, and prefix stacks beside it.  Fewer: no prefix stacks
+// (the adding sweep is a few per cent of a chain there), the cache per tile of 64 wavenumbers (the lane kernel's; the wavefront
+// kernel keeps the layout).  Reads the free device memory and the ANSFM_MS_SLAB / CHUNK / WINDOW switches; leaves sl and
+// ctx->ms_windows / ms_window_w.  G = 1: the slabs are the windows of phase matrices and Hansen factors (ms_window_size): a
+// slab's phase matrices and walk -- continuing from the carry of the slab before -- go in front of its chains, model 0's first;
+// this reserves and zeroes one window in ctx->misc, sets p.ppl / pmi / fc / carry and, for a slice, walks the wavenumbers in front
+// of it.
+static int ms_plan_slabs(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, const MsRoute &r, int npre, MsParams &p, MsSlabs &sl)
+{
+    const int W = ctx->W, G = ctx->G, L = c.L, nmu = c.nmu, nf = c.nf, ncomp = p.ncomp;
+    const size_t D = sizeof(double), nn = (size_t)p.nmu * p.nmu;
+    const bool m16 = r.chain == MsChain::mfma16, win = G == 1;
+    const long unit = sl.unit = m16 ? 1 : 64;
     const size_t entry = m16 ? (size_t)kMsCacheEntry : (2 * (size_t)nmu * nmu + nmu) * 64;  // doubles per (unit, g, order, layer)
-    const size_t per_unit = (size_t)G * (nf + 1) * L * entry * D, per_unit_pre = m16 ? (size_t)G * (nf + 1) * npre * entry * D : 0;
+    sl.per_unit = (size_t)G * (nf + 1) * L * entry * D;
+    sl.per_unit_pre = m16 ? (size_t)G * (nf + 1) * npre * entry * D : 0;
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     free_b += ctx->ms_cache.bytes + (m16 ? ctx->ms_pcache.bytes : 0);
     const size_t budget = std::min<size_t>(free_b / 2, (size_t)96 << 30);
-    long units = (long)(budget / (per_unit + per_unit_pre));
+    long units = (long)(budget / (sl.per_unit + sl.per_unit_pre));
     if (kn.slab) units = std::min(units, (kn.slab + unit - 1) / unit);
     if (units < 1)
         FAIL(ANSFM_ERR_HIP, m16 ? "cirsrad_ck_scatter_batch: no memory for the layer cache of one wavenumber"
                                 : "cirsrad_ck_scatter_batch: no memory for the layer cache of one tile of wavenumbers");
-    // G = 1: the slabs are the windows of phase matrices and Hansen factors (ms_window_size): a slab's phase matrices and walk
-    // -- continuing from the carry of the slab before -- go in front of its chains, model 0's first
-    const long Ws = std::min(std::min<long>(W, units * unit), win ? ms_window_size(c.W_full, nf, ncomp, nmu_k, kn) : (long)W);
+    const long Ws = sl.Ws = std::min(std::min<long>(W, units * unit), win ? ms_window_size(c.W_full, nf, ncomp, p.nmu, kn) : (long)W);
     ctx->ms_windows = (W + Ws - 1) / Ws; ctx->ms_window_w = Ws;
     if (win) {
         const size_t nph_w = (size_t)Ws * (nf + 1) * ncomp * nn, n_all = 2 * nph_w + (size_t)Ws * ncomp * nn + ncomp * nn;
@@ -691,26 +723,38 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
         HIPCHK(hipMemsetAsync(ctx->misc.p, 0, n_all * D, ctx->stream));
         p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph_w; p.fc = p.pmi + nph_w; p.carry = p.fc + (size_t)Ws * ncomp * nn;
         // a slice: the walk of the wavenumbers in front of it, in windows of Ws whose factors only feed the carry
-        for (long a = 0; a < w_begin && ncomp_run > 0; a += Ws) {
+        for (long a = 0; a < c.w_begin && r.ncomp_run > 0; a += Ws) {
             MsParams pw = p;
-            pw.nwave = c.W_full; pw.pw0 = (int)a; pw.nwin = (int)std::min<long>(Ws, w_begin - a); pw.carry_in = a > 0 ? 1 : 0;
+            pw.nwave = c.W_full; pw.pw0 = (int)a; pw.nwin = (int)std::min<long>(Ws, c.w_begin - a); pw.carry_in = a > 0 ? 1 : 0;
             pw.ig0 = 0; pw.ng_launch = 1;
             ms_launch_phase(ctx->stream, pw);
             ms_launch_hansen(ctx->stream, pw);
             HIPCHK(hipGetLastError());
         }
     }
-    const int mchunk = std::min(n_models - 1, kn.chunk ? kn.chunk : 64);
-    HIPCHK(ctx->ms_cache.reserve((size_t)((Ws + unit - 1) / unit) * per_unit));
+    sl.mchunk = std::min(c.n_models - 1, kn.chunk ? kn.chunk : 64);
+    return ANSFM_OK;
+}
+
+// Reserves the layer cache, the prefix stacks, the optics outputs of one launch (by rows: and its TAURAY / fractions), the
+// orders and the radiances, and points p at them and at same / the sweep starts / the launch order.  Leaves p ready for the
+// slab loop but for the slab and the models of a launch.
+static int ms_wire_batch(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, const MsRoute &r, unsigned char *same, int npre,
+                         const MsSlabs &sl, MsParams &p)
+{
+    const int W = ctx->W, G = ctx->G, L = c.L, n_models = c.n_models, ncont = c.ncont, nf = c.nf, ngeom = c.ngeom;
+    const size_t D = sizeof(double), Ws = (size_t)sl.Ws;
+    const bool m16 = r.chain == MsChain::mfma16;
+    HIPCHK(ctx->ms_cache.reserve((size_t)((sl.Ws + sl.unit - 1) / sl.unit) * sl.per_unit));
     if (m16) {
-        HIPCHK(ctx->ms_pcache.reserve(std::max<size_t>((size_t)Ws * per_unit_pre, 8)));
-        HIPCHK(ctx->ms_orders.reserve((size_t)Ws * G * sizeof(int)));
+        HIPCHK(ctx->ms_pcache.reserve(std::max<size_t>(Ws * sl.per_unit_pre, 8)));
+        HIPCHK(ctx->ms_orders.reserve(Ws * G * sizeof(int)));
     }
-    const size_t opt_models = (size_t)std::max(1, mchunk);
+    const size_t opt_models = (size_t)std::max(1, sl.mchunk);
     HIPCHK(ctx->ms_taus.reserve(opt_models * Ws * G * L * D));
     HIPCHK(ctx->ms_omegas.reserve(opt_models * Ws * G * L * D));
     HIPCHK(ctx->ms_bnu.reserve(opt_models * Ws * L * D));
-    if (by_rows) {
+    if (c.cont_row) {
         HIPCHK(ctx->ms_tauray_l.reserve(opt_models * Ws * L * D));
         HIPCHK(ctx->ms_lfrac_l.reserve(std::max<size_t>(opt_models * Ws * ncont * L * D, 8)));
         p.tauray = ctx->ms_tauray_l.as<double>(); p.lfrac = ctx->ms_lfrac_l.as<double>(); p.cont_local = 1;
@@ -728,42 +772,27 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
         p.cache_orders = ctx->ms_orders.as<int>(); p.pcache = ctx->ms_pcache.as<double>(); p.lstart = ctx->ms_lstart.as<int>(); p.npre = npre;
     }
     p.model_ids = ctx->ms_lstart.as<int>() + n_models;
-    p.st_wl = ray ? WL : 0; p.st_wcl = (size_t)W * ncont * L; p.st_wm = (size_t)W * nmu_k; p.st_rad = (size_t)ngeom * G * W;
+    p.st_wl = s.ray ? (size_t)W * L : 0; p.st_wcl = (size_t)W * ncont * L; p.st_wm = (size_t)W * p.nmu; p.st_rad = (size_t)ngeom * G * W;
     p.ig0 = 0; p.ng_launch = G;
-    MsOpticsRowsParams orw;
-    memset(&orw, 0, sizeof orw);
-    orw.taugas = ctx->tau.as<double>(); orw.slot = ctx->dd_slot.as<int32_t>(); orw.cont_row = d_crow;
-    orw.taucia = cia; orw.taudust = dust; orw.tauray = ray; orw.tauscat = sca; orw.lfrac = lf;
-    orw.wave = ctx->d_wave.as<double>(); orw.lay_temp = temp;
-    orw.taus = ctx->ms_taus.as<double>(); orw.omegas = ctx->ms_omegas.as<double>(); orw.bnu = ctx->ms_bnu.as<double>();
-    orw.tauray_l = ctx->ms_tauray_l.as<double>(); orw.lfrac_l = ctx->ms_lfrac_l.as<double>();
-    orw.W = W; orw.Wpad = Wpad; orw.G = G; orw.L = L; orw.ncont = lf ? ncont : 0; orw.ispace = c.ISPACE;
-    MsOpticsBatchParams o;
-    memset(&o, 0, sizeof o);
-    o.taugas = ctx->tau.as<double>(); o.slot = ctx->dd_slot.as<int32_t>();
-    o.taucia = cia; o.taudust = dust; o.tauray = ray; o.tauscat = sca;
-    o.wave = ctx->d_wave.as<double>(); o.lay_temp = temp;
-    o.taus = ctx->ms_taus.as<double>(); o.omegas = ctx->ms_omegas.as<double>(); o.bnu = ctx->ms_bnu.as<double>();
-    o.W = W; o.Wpad = Wpad; o.G = G; o.L = L; o.ispace = c.ISPACE;
-    // TAUTOT, OMEGA, BB (by rows: and the slab's TAURAY / fractions) of the models [m0, m0 + nm) of the launch order on the slab
-    auto optics = [&](int w0, int wc, int m0, int nm, const int *ids) {
-        const dim3 grid(nblk((size_t)wc, 128), (unsigned)L, (unsigned)nm);
-        if (by_rows) {
-            orw.w0 = w0; orw.wcount = wc; orw.m0 = m0; orw.nm = nm; orw.model_ids = ids;
-            hipLaunchKernelGGL(k_ms_optics_rows, grid, dim3(128), 0, ctx->stream, orw);
-        } else {
-            o.w0 = w0; o.wcount = wc; o.m0 = m0; o.nm = nm; o.model_ids = ids;
-            hipLaunchKernelGGL(k_ms_optics_batch, grid, dim3(128), 0, ctx->stream, o);
-        }
-    };
-    for (long w0 = 0; w0 < W; w0 += Ws) {
-        const int wc = (int)std::min<long>(Ws, W - w0);
-        if (win) {
+    return ANSFM_OK;
+}
+
+// Slab by slab (G = 1: its phase matrices and walk first): the optics and the ordinary chain of model 0, which also fills the
+// cache, then models 1 .. n-1 in chunks: the adding sweep over cached layers, changed layers computed in place.  Leaves
+// rad [model][ngeom][G][W] in ctx->tmp_out or, below 16 streams, every order in ctx->tmp_in2.
+static int ms_run_slabs(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, const MsRoute &r, const MsSlabs &sl, MsParams &p)
+{
+    const int W = ctx->W, L = c.L, n_models = c.n_models, w_begin = c.w_begin;
+    int rc;
+    MsOpticsParams o = ms_optics_params(ctx, c, s, ctx->dd_slot.as<int32_t>());
+    for (long w0 = 0; w0 < W; w0 += sl.Ws) {
+        const int wc = (int)std::min<long>(sl.Ws, W - w0);
+        if (ctx->G == 1) {
             // the phase matrices of the slab are those of the wavenumbers w_begin + [w0, w0 + wc) of phasarr; chains and walk
             // index the window relative to w0
             p.pw0 = (int)w0; p.nwin = wc; p.carry_in = w_begin + w0 > 0 ? 1 : 0;
             p.ig0 = 0; p.ng_launch = 1;
-            if (ncomp_run > 0) {
+            if (r.ncomp_run > 0) {
                 MsParams pw = p;
                 pw.nwave = c.W_full; pw.pw0 = w_begin + (int)w0;
                 ms_launch_phase(ctx->stream, pw);
@@ -772,21 +801,59 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
             HIPCHK(hipGetLastError());
         }
         p.w0 = (int)w0; p.wcount = wc;
-        if (by_rows) { p.st_wl = (size_t)wc * L; p.st_wcl = (size_t)wc * ncont * L; }       // between launch positions
-        // model 0: the ordinary chain, which also fills the cache
-        optics((int)w0, wc, 0, 1, nullptr);
+        if (c.cont_row) { p.st_wl = (size_t)wc * L; p.st_wcl = (size_t)wc * c.ncont * L; }       // between launch positions
+        ms_launch_optics(ctx->stream, o, (int)w0, wc, 0, 1, nullptr);
         p.m0 = 0; p.n_launch = 1;
         if ((rc = ms_launch_chain<1>(ctx, r.chain, ctx->stream, p))) return rc;
-        // models 1 .. n-1 in chunks: the adding sweep over cached layers, changed layers computed in place
-        for (int m0 = 1; m0 < n_models; m0 += mchunk) {
-            const int nm = std::min(mchunk, n_models - m0);
-            optics((int)w0, wc, m0, nm, p.model_ids);
+        for (int m0 = 1; m0 < n_models; m0 += sl.mchunk) {
+            const int nm = std::min(sl.mchunk, n_models - m0);
+            ms_launch_optics(ctx->stream, o, (int)w0, wc, m0, nm, p.model_ids);
             p.m0 = m0; p.n_launch = nm;
             if ((rc = ms_launch_chain<2>(ctx, r.chain, ctx->stream, p))) return rc;
         }
     }
+    return ANSFM_OK;
+}
+
+static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
+{
+    int rc = ms_check(ctx, c, "cirsrad_ck_scatter_batch");
+    if (rc || (rc = ms_check_rows(ctx, c))) return rc;           // before anything is launched
+    const int W = ctx->W, G = ctx->G, L = c.L, n_models = c.n_models;
+    const bool by_rows = c.cont_row != nullptr;
+    ctx->ms_cache_hits = 0; ctx->ms_cache_layers = (long)n_models * L;
+    // (a runtime line source has its own row map, which the (p, T, amount) comparison of the layer cache does not see)
+    const bool use_cache = n_models > 1 && ctx->dedup && kn.layer_cache && !ctx->lblrt;      // any stream count
+    if (!use_cache && c.W_full != W)
+        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter_batch_slice: a slice needs the layer cache (n_models > 1, layer de-duplication on)");
+    if (!use_cache) return ms_batch_by_model(ctx, c, kn);
+    HIPCHK(hipSetDevice(ctx->device));
+    MsParams p;
+    MsRoute r;
+    if ((rc = ms_setup(ctx, p, c, W, G, L, kn, r))) return rc;
+    MsStaged s;
+    if ((rc = ms_stage(ctx, c, by_rows ? (size_t)c.R * W : (size_t)n_models * W * L, s))) return rc;
+    const double *d_tauray = s.ray;                             // no TAURAY: every model reads the same zeros
+    if (!by_rows && (rc = ms_zero_tauray(ctx, (size_t)W * L, &d_tauray))) return rc;     // (by rows: the optics stage writes the slab's copy)
+    // vertical gas opacities of the distinct (model, layer) rows: calc_k + k_overlap
+    DedupRows k;
+    if ((rc = dedup_rows(ctx, n_models, L, s.press, s.temp, s.am, nullptr, nullptr, &k)) ||
+        (rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount)))
+        return rc;
+    ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = k.rows; ctx->last_dedup = 1;
+    unsigned char *same;
+    int npre;
+    if ((rc = ms_same_layers(ctx, c, kn, s, p.lookup, &same, &npre))) return rc;
+    p.phasarr = s.phas; p.radg = s.rg; p.solar = s.sol;
+    p.brdf = s.brdf; p.tauray = d_tauray; p.lfrac = s.lf;
+    if (p.nmu_real && (rc = ms_pad_inputs(ctx, c.nmu, (size_t)n_models * W, (size_t)W, c.nf, &p.radg, &p.brdf))) return rc;
+    if (G > 1 && (rc = ms_walk_axis(ctx, c, r, p))) return rc;
+    MsSlabs sl;
+    if ((rc = ms_plan_slabs(ctx, c, kn, r, npre, p, sl)) || (rc = ms_wire_batch(ctx, c, s, r, same, npre, sl, p)) ||
+        (rc = ms_run_slabs(ctx, c, s, r, sl, p)))
+        return rc;
     // below 16 streams every Fourier order was worked through: k_ms_fourier applies the reference's convergence break per model
-    return ms_gquad(ctx, n_models, ngeom, xf, c.SPECOUT, nullptr, m16 ? nullptr : &p);
+    return ms_gquad(ctx, n_models, c.ngeom, s.xf, c.SPECOUT, nullptr, r.chain == MsChain::mfma16 ? nullptr : &p);
 }
 
 int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,

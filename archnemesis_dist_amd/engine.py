@@ -817,6 +817,15 @@ class AnsfmEngine:
         n = self.MS_PATHS_PER_CALL
         return [slice(i, min(i + n, ngeom)) for i in range(0, ngeom, n)]
 
+    @staticmethod
+    def _scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1):
+        """What the scattering wrappers share -> ((phasarr or None, ncont, nth), (sol, emi, aph, P), (mu1, nmu))"""
+        phasarr = None if phasarr is None else _np(phasarr)
+        ncont, nth = (0, 0) if phasarr is None else (phasarr.shape[0], phasarr.shape[3])
+        sol = _np(np.atleast_1d(sol_angs)); emi = _np(np.atleast_1d(emiss_angs)); aph = _np(np.atleast_1d(aphis))
+        mu1 = _np(mu1)
+        return (phasarr, ncont, nth), (sol, emi, aph, sol.shape[0]), (mu1, mu1.shape[0])
+
     def cirsrad_ck_scatter(self, ISPACE, lay_press_pa, lay_temp, amount, TAUCIA, TAUDUST, TAURAY, TAUSCAT, phasarr, lfrac,
                            radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie,
                            xfac=None, return_spec_g=False):
@@ -831,11 +840,7 @@ class AnsfmEngine:
         if amount.shape != (S, L):
             raise ValueError("amount must be (NGAS, NLAY)")
         wl = lambda a: None if a is None else _np(a).reshape(W, L)
-        phasarr = None if phasarr is None else _np(phasarr)
-        ncont = 0 if phasarr is None else phasarr.shape[0]
-        nth = 0 if phasarr is None else phasarr.shape[3]
-        sol = _np(np.atleast_1d(sol_angs)); emi = _np(np.atleast_1d(emiss_angs)); aph = _np(np.atleast_1d(aphis))
-        P = sol.shape[0]
+        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
         if P > self.MS_PATHS_PER_CALL:          # more paths than one call takes: groups of paths, the chains of each re-run
             if not (np.all(emi < 90) or np.all(emi > 90)):
                 raise ValueError("cirsrad_ck_scatter: INVALID: Emission angles are a mix of values above and below 90 degrees.")
@@ -845,7 +850,6 @@ class AnsfmEngine:
             if return_spec_g:
                 return np.concatenate([p_[0] for p_ in parts], axis=1), np.concatenate([p_[1] for p_ in parts], axis=2)
             return np.concatenate(parts, axis=1)
-        mu1 = _np(mu1); nmu = mu1.shape[0]
         out = np.empty((W, P)); spec_g = np.empty((W, G, P)) if return_spec_g else None
         rc = self._lib.ansfm_cirsrad_ck_scatter(
             self._ctx, int(ISPACE), L, _ptr(lay_press_pa), _ptr(_np(lay_temp)), _ptr(amount), _ptr(wl(TAUCIA)), _ptr(wl(TAUDUST)),
@@ -874,13 +878,8 @@ class AnsfmEngine:
         if am.shape != (n, S, L):
             raise ValueError("amount must be (n_models, NGAS, NLAY)")
         nwl = lambda a: None if a is None else _np(a).reshape(n, W, L)
-        phasarr = None if phasarr is None else _np(phasarr)
-        ncont = 0 if phasarr is None else phasarr.shape[0]
-        nth = 0 if phasarr is None else phasarr.shape[3]
-        sol = _np(np.atleast_1d(sol_angs)); emi = _np(np.atleast_1d(emiss_angs)); aph = _np(np.atleast_1d(aphis))
-        P = sol.shape[0]
-        mu1 = _np(mu1); nmu = mu1.shape[0]
-        lf = None if lfrac is None else _np(lfrac).reshape(n, W, ncont, L)
+        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        lf =None if lfrac is None else _np(lfrac).reshape(n, W, ncont, L)
         rg = _np(radg).reshape(n, W, nmu)
         out = np.empty((n, W, P))
         args = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(_np(lay_temp).reshape(n, L)), _ptr(am), _ptr(nwl(TAUCIA)),
@@ -921,10 +920,8 @@ class AnsfmEngine:
         if cr.shape != (n, L) or cr.dtype.kind not in "iu":
             raise ValueError("cont_row must be an integer array (n_models, NLAY)")
         cr = _np(cr, np.int32)
-        phasarr = None if phasarr is None else _np(phasarr)
-        ncont = 0 if phasarr is None else phasarr.shape[0]
-        nth = 0 if phasarr is None else phasarr.shape[3]
-        rows = [None if a is None else _np(a) for a in (TAUCIA_rows, TAUDUST_rows, TAURAY_rows, TAUSCAT_rows)]
+        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        rows =[None if a is None else _np(a) for a in (TAUCIA_rows, TAUDUST_rows, TAURAY_rows, TAUSCAT_rows)]
         lf = None if lfrac_rows is None or ncont == 0 else _np(lfrac_rows)
         if ncont > 0 and lf is None:
             raise ValueError("lfrac_rows is needed with aerosols (phasarr given)")
@@ -934,9 +931,6 @@ class AnsfmEngine:
                 raise ValueError(f"{name} must be (R, NWAVE) = ({R}, {W}), got {a.shape}")
         if lf is not None and lf.shape != (R, ncont, W):
             raise ValueError(f"lfrac_rows must be (R, NDUST, NWAVE) = ({R}, {ncont}, {W}), got {lf.shape}")
-        sol = _np(np.atleast_1d(sol_angs)); emi = _np(np.atleast_1d(emiss_angs)); aph = _np(np.atleast_1d(aphis))
-        P = sol.shape[0]
-        mu1 = _np(mu1); nmu = mu1.shape[0]
         rg = _np(radg)
         if rg.size != n * W * nmu:
             raise ValueError("radg must be (n_models, NWAVE, NMU)")

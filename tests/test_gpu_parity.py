@@ -1205,9 +1205,9 @@ def _scatter_inputs(rng, W, G, L, S, NMU, NF, ncont, imie, iray, lowbc):
                 brdf=brdf, MU=MU, WT=WT)
 
 
-def _scatter_oracle(oracle, z, sol, emi, azi, lowbc, NF, nphi, iray, imie):
+def _scatter_oracle(oracle, z, sol, emi, azi, lowbc, NF, nphi, iray, imie, ISPACE=0):
     """The reference's recipe on the oracle's restatements: calc_k + k_overlap, TAUTOT (:3989), OMEGA / BB (:5099-5119),
-    scloud11wave_core, g-quadrature (:4504)."""
+    scloud11wave_core, g-quadrature (:4504).  ISPACE = 1: WAVE is a wavelength grid in micron."""
     W, L = z["TAUCIA"].shape
     k = oracle.calc_k(z["K"], z["TPRESS"], z["TTEMP"], z["lay_p"] / 101325.0, z["lay_t"])
     taugas = oracle.k_overlap(z["DELG"], k, z["amount"])
@@ -1215,8 +1215,7 @@ def _scatter_oracle(oracle, z, sol, emi, azi, lowbc, NF, nphi, iray, imie):
     omega = np.zeros_like(tautot)
     pos = tautot > 0
     omega[pos] = np.broadcast_to((z["TAURAY"] + z["TAUSCAT"])[:, None, :], tautot.shape)[pos] / tautot[pos]
-    c1, c2 = 1.1911e-12, 1.439
-    bnu = c1 * z["WAVE"][:, None] ** 3 / (np.exp(c2 * z["WAVE"][:, None] / z["lay_t"][None, :]) - 1.0)
+    bnu = oracle.planck(ISPACE, z["WAVE"][:, None], z["lay_t"][None, :])
     rad = oracle.scloud11wave_core(z["phasarr"], z["radg"], sol, emi, z["solar"], azi, lowbc, z["brdf"], z["MU"], z["WT"], NF,
                                    z["WAVE"], bnu, tautot, z["TAURAY"], omega, nphi, iray, imie, z["lfrac"])
     spec = np.transpose(rad, (2, 1, 0))                                     # (W, G, P), :5164
@@ -1236,6 +1235,47 @@ def test_cirsrad_scatter_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowb
     """ansfm_cirsrad_ck_scatter (gas opacities, TAUTOT, OMEGA, BB formed on the device, straight into the doubling /
     adding kernels) vs the same chain through the oracle: radiances before and after the g-quadrature and TAUGAS."""
     _scatter_vs_oracle(eng, oracle, NMU, NF, ncont, imie, iray, lowbc, up, unsorted=False)
+
+
+@pytest.mark.parametrize("NMU,NF", [(5, 2), (16, 2)])               # the lane kernels, the matrix-core chain
+def test_cirsrad_scatter_wavelength_grid_vs_oracle(eng, oracle, NMU, NF):
+    """ISPACE = 1: the Planck function of the optics stage on a wavelength grid (5 .. 25 micron).  W = 70 (two wavefronts, a
+    partial last tile), G = 2, L = 5 (one prefix stack of kMsPrefixStep = 4 layers and a remainder), one aerosol and Rayleigh,
+    a reflecting surface, looking down.  One model against the oracle chain to the bound of ISPACE = 0 (only bnu differs, and
+    the oracle forms it in double precision); three models (a layer's temperature, a layer's dust) through the dense and the
+    rows batch, each equal to the single calls bit for bit -- and not to the same call at ISPACE = 0, where the grid would be
+    read as 5 .. 25 cm-1.  On the oracle side the spectra at ISPACE = 1 and 0 differ by 0.19 (5 streams) and 0.38 (16) of the
+    largest radiance, and nowhere by less than 1e-4 of the element: seven orders above the bound."""
+    from archnemesis_dist_amd.continuum_rows import rows_kwargs
+    rng = np.random.default_rng(1900 + NMU)
+    W, G, L, S = 70, 2, 5, 2
+    z = _scatter_inputs(rng, W, G, L, S, NMU, NF, 1, 1, 1, 1)
+    z["WAVE"] = np.linspace(5.0, 25.0, W)
+    z["radg"] = np.repeat(oracle.planck(1, z["WAVE"], z["lay_t"][0])[:, None], NMU, 1)
+    sol = np.array([30.0, 120.0]); emi = np.array([20.0, 50.0]); azi = np.array([45.0, 0.0])
+    eng.upload_ktable(z["K"], z["TPRESS"], z["TTEMP"], z["WAVE"], z["DELG"])
+    n = 3
+    rep = lambda a: np.repeat(np.asarray(a)[None], n, 0).copy()
+    args = dict(ISPACE=1, lay_press_pa=rep(z["lay_p"]), lay_temp=rep(z["lay_t"]), amount=rep(z["amount"]), TAUCIA=rep(z["TAUCIA"]),
+                TAUDUST=rep(z["TAUDUST"]), TAURAY=rep(z["TAURAY"]), TAUSCAT=rep(z["TAUSCAT"]), phasarr=z["phasarr"],
+                lfrac=rep(z["lfrac"]), radg=rep(z["radg"]), sol_angs=sol, emiss_angs=emi, aphis=azi, solar=z["solar"], lowbc=1,
+                brdf_matrix=z["brdf"], mu1=z["MU"], wt1=z["WT"], nf=NF, nphi=101, iray=1, imie=1)
+    args["lay_temp"][1, 3] *= 1.05
+    args["TAUDUST"][2, :, 1] *= 1.05
+    one = lambda m: eng.cirsrad_ck_scatter(1, args["lay_press_pa"][m], args["lay_temp"][m], args["amount"][m], args["TAUCIA"][m],
+                                           args["TAUDUST"][m], args["TAURAY"][m], args["TAUSCAT"][m], z["phasarr"], args["lfrac"][m],
+                                           args["radg"][m], sol, emi, azi, z["solar"], 1, z["brdf"], z["MU"], z["WT"], NF, 101, 1, 1)
+    singles = np.stack([one(m) for m in range(n)])
+    ref, _, _ = _scatter_oracle(oracle, z, sol, emi, azi, 1, NF, 101, 1, 1, ISPACE=1)
+    err = np.max(np.abs(singles[0] - ref)) / np.max(np.abs(ref))
+    print(f"NMU {NMU}: single model vs oracle at ISPACE = 1: {err:.3e} of the largest radiance")
+    assert err < 1e-8
+    for name, call, kw in (("dense", eng.cirsrad_ck_scatter_batch, args), ("rows", eng.cirsrad_ck_scatter_batch_rows, rows_kwargs(args))):
+        got = call(**kw)
+        for m in range(n):
+            assert np.array_equal(got[m], singles[m]), (name, m)
+        assert eng.last_scatter_cache()[0] > 0, name
+        assert not np.array_equal(call(**dict(kw, ISPACE=0)), got), name
 
 
 @pytest.mark.parametrize("NMU,NF,ncont,imie,iray,lowbc,up", [(5, 2, 2, 0, 1, 0, False), (16, 3, 1, 1, 1, 1, False),
