@@ -41,6 +41,8 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 // The bits of OPT as ansfm_last_merge_launch reports them.  Value 4 (a late read of the bin boundary, retired) stays unused.
 constexpr int kOptTable = 1, kOptBfi = 2, kOptExit = 8, kOptOrient = 16;
 constexpr int kMergeOpt = kOptTable | kOptBfi | kOptExit | kOptOrient;
+// reported beside them, a launch parameter and not a bit of OPT: the lanes of a wave are grouped over rows (k_ck_overlap's argument lane_rows)
+constexpr int kOptLaneRows = 32;
 // The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
 __host__ __device__ constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
 // Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
@@ -241,9 +243,10 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
 // then t_k = s_k for every k >= K1 in every lane: the list is sorted, so x <= s_k <= s_{k+1}.  The pass stops there, exactly,
 // ties included.  A sentinel x (the popped row is exhausted) is above every live key and runs to the end of the live
 // prefix like any other.  The last chunk closes with t_{NP-1} = max(x, s_{NP-1}) as the full pass does.
-// Two tests per step measured faster than four: every test is a scalar branch that the wave waits for, and a
-// wave alone on its SIMD has nobody to hide it behind
-constexpr int kExitBounds[] = {4, 10};
+// Every test is a scalar branch that the wave waits for, and a wave alone on its SIMD has nobody to hide it behind: with 64
+// unrelated wavenumbers per wave two tests (4, 10) measured faster than three or four.  With the lanes grouped over rows
+// (LaneRow) most steps leave at the first test, and three boundaries measured faster than 4/10, 3/9 and 2/5/9/14
+constexpr int kExitBounds[] = {3, 7, 12};
 constexpr int kNoExitBound = 1000;
 // the first boundary above k0
 __host__ __device__ constexpr int merge_exit_bound(int k0)

@@ -180,6 +180,121 @@ __device__ __forceinline__ void load_gas(const OverlapParams &p, const LayerInte
     }
 }
 
+// Layer-grouped lanes (the forward kernel's fast path).  The (model, layer) rows of a launch are one row axis of
+// length R = n_models * L, and the cells of a 64-wavenumber block are numbered (wavenumber / kLaneNV, row, wavenumber % kLaneNV),
+// the last fastest; a tile is 64 consecutive cells of that order: kLaneNV wavenumbers x 64 / kLaneNV consecutive rows, running on
+// into the next wavenumber group at the end of the row axis.  A block holds 64 * R cells, i.e. exactly R tiles, whatever R is.
+// Neighbouring rows of one wavenumber meet the same gases at nearby (p, T), so the lanes of a wave re-enter the head list at
+// similar depths and merge_pass_exit can stop where a wave of 64 unrelated wavenumbers cannot.  What was wave-uniform in the
+// other mapping -- the row's interpolation constants, its amounts, the corner rows of the table -- is per lane here.
+constexpr int kLaneNV = 2;
+constexpr int kLaneRows = kWave / kLaneNV;        // rows of a tile, and wavenumber groups of a 64-wavenumber block
+static_assert(kLaneNV == 2 || kLaneNV == 4 || kLaneNV == 8, "group width");
+
+// Queue order inside a 64-wavenumber block: the u-th tile handed out is tile lane_tile_of(u) of the cell order.  A tile is at
+// "row slot" s when it is the s-th tile that starts in its wavenumber group; the tiles go out slot by slot, group by group
+// within a slot, so that the 16 / kLaneNV tiles that read the same 128-byte table lines (one 16-wavenumber span, one row
+// slot) are neighbours in the queue and one wave's miss serves the others from L2.  Every group has R / kLaneRows such tiles or
+// one more; the i-th group that has one more is group i * kLaneRows / (R % kLaneRows).
+__host__ __device__ constexpr unsigned lane_tile_of(unsigned u, unsigned R)
+{
+    constexpr unsigned Q = kLaneRows;
+    const unsigned fl = R / Q, rem = R % Q;
+    unsigned grp = u % Q, slot = u / Q;
+    if (u >= Q * fl) { slot = fl; grp = (u - Q * fl) * Q / rem; }
+    return (grp * R + Q - 1) / Q + slot;            // the first tile that starts in the group, + slot
+}
+
+struct LaneRow {
+    int nu;                     // wavenumber of the lane's cell; W <= nu < Wpad: a pad cell
+    unsigned row;               // m * L + l: the row of li and of tau
+    unsigned arow, krow;        // index of gas 0's amount, (m * S) * L + l, and (FROM_K) the layer l
+    size_t o1, o2, o3, o4;      // the four corner rows of load_gas as element offsets into lnK, + nu
+    double v, u;
+};
+// the cell of lane `lane` of tile k of wavenumber block vt
+template <bool FROM_K>
+__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane)
+{
+    const unsigned R = (unsigned)p.n_models * (unsigned)p.L;
+    const unsigned c = k * kWave + (unsigned)lane, pair = c / kLaneNV;
+    const unsigned grp = pair / R;
+    LaneRow lr;
+    lr.row = pair - grp * R;
+    lr.nu = vt * kWave + (int)(grp * kLaneNV + c % kLaneNV);
+    const unsigned m = lr.row / (unsigned)p.L;
+    lr.krow = lr.row - m * (unsigned)p.L;
+    lr.arow = m * (unsigned)p.S * (unsigned)p.L + lr.krow;
+    lr.o1 = lr.o2 = lr.o3 = lr.o4 = 0;
+    lr.v = lr.u = 0.0;
+    if constexpr (!FROM_K) {
+        const LayerInterp q = p.li[lr.row];
+        const size_t strideT = (size_t)p.S * p.G * p.Wpad;
+        lr.o1 = ((size_t)q.ipl * p.NT + q.itl) * strideT + lr.nu;
+        lr.o2 = ((size_t)q.ipl * p.NT + q.ith) * strideT + lr.nu;
+        lr.o3 = ((size_t)q.iph * p.NT + q.itl) * strideT + lr.nu;
+        lr.o4 = ((size_t)q.iph * p.NT + q.ith) * strideT + lr.nu;
+        lr.v = q.v; lr.u = q.u;
+    }
+    return lr;
+}
+
+// load_gas for layer-grouped lanes: the same reads, the same interp_k / interp_k_nobox and the same `* amt` per cell, with
+// the row a per-lane value
+template <bool FROM_K, bool NOBOX>
+__device__ __forceinline__ void load_gas_rows(const OverlapParams &p, const LaneRow &lr, int s, double *DST, int lane,
+                                              bool &unsorted)
+{
+    const int G = p.G;
+    const double amt = p.amount[(size_t)lr.arow + (size_t)s * p.L];
+    double prev = -__builtin_inf();
+    if constexpr (FROM_K) {
+        const double *src = p.kin + (((size_t)s * p.L + lr.krow) * G) * p.Wpad + lr.nu;
+        for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
+            double r[kLoadBatch];
+#pragma unroll
+            for (int k = 0; k < kLoadBatch; ++k) {
+                const int gi = (g0 + k < G) ? g0 + k : G - 1;
+                r[k] = src[(size_t)gi * p.Wpad];
+            }
+#pragma unroll
+            for (int k = 0; k < kLoadBatch; ++k)
+                if (g0 + k < G) {
+                    const double kk = r[k] * amt;
+                    DST[(g0 + k) * kWave + lane] = kk;
+                    unsorted |= (kk < prev);
+                    prev = kk;
+                }
+        }
+    } else {
+        const double *base = p.lnK + (size_t)s * G * p.Wpad;
+        const double *c1 = base + lr.o1, *c2 = base + lr.o2, *c3 = base + lr.o3, *c4 = base + lr.o4;
+        for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
+            double r1[kLoadBatch], r2[kLoadBatch], r3[kLoadBatch], r4[kLoadBatch];
+#pragma unroll
+            for (int k = 0; k < kLoadBatch; ++k) {
+                const int gi = (g0 + k < G) ? g0 + k : G - 1;
+                const size_t go = (size_t)gi * p.Wpad;
+                // plain loads, not load_gas's non-temporal ones: a 128-byte table line serves the 16 / kLaneNV tiles of its
+                // 16-wavenumber span, which the queue hands out together (measured: 4.27 -> 4.13 ms at C2)
+                r1[k] = c1[go];
+                r2[k] = c2[go];
+                r3[k] = c3[go];
+                r4[k] = c4[go];
+            }
+#pragma unroll
+            for (int k = 0; k < kLoadBatch; ++k)
+                if (g0 + k < G) {
+                    const double kk = (NOBOX ? interp_k_nobox(r1[k], r2[k], r3[k], r4[k], lr.v, lr.u)
+                                             : interp_k(r1[k], r2[k], r3[k], r4[k], lr.v, lr.u)) * amt;
+                    DST[(g0 + k) * kWave + lane] = kk;
+                    unsorted |= (kk < prev);
+                    prev = kk;
+                }
+        }
+    }
+}
+
 __device__ __forceinline__ double fast_div(double n, double d)
 {   // n/d with v_rcp_f64 + 2 Newton steps + residual correction (<= ~1 ulp; frac of rank()).  One Newton step gives the
     // same quotients (tools/calib/div_check.hip) but k_ck_overlap measured 1.2 % SLOWER with it (5.88 -> 5.95 ms, same box,
@@ -239,6 +354,29 @@ struct TileQueue {
                 const long r = t / p.L;
                 vt = qq + 8 * (int)(r % nvt_q);
                 m = (int)(r / nvt_q);
+                return true;
+            }
+            ++qoff;
+        }
+        return false;
+    }
+    // Layer-grouped lanes: the same eight queues over the 64-wavenumber blocks, so a block's table rows stay on one XCD; a
+    // block's R = n_models * L tiles go out in the order of lane_tile_of.  k = the tile's index in the block's cell order.
+    __device__ __forceinline__ bool next_rows(const OverlapParams &p, int lane, int &vt, unsigned &k)
+    {
+        const int NVT = p.Wpad / kWave;
+        const unsigned R = (unsigned)p.n_models * (unsigned)p.L;
+        while (qoff < 8) {
+            const int qq = (myq + qoff) & 7;
+            const int nvt_q = (NVT - qq + 7) / 8;
+            const long nq = (long)nvt_q * R;
+            unsigned int tq = 0;
+            if (lane == 0 && nq > 0) tq = atomicAdd(p.tile_counter + qq, 1u);
+            const long t = (long)__builtin_amdgcn_readfirstlane(tq);
+            if (nq > 0 && t < nq) {
+                const unsigned b = (unsigned)(t / R);
+                vt = qq + 8 * (int)b;
+                k = lane_tile_of((unsigned)t - b * R, R);
                 return true;
             }
             ++qoff;

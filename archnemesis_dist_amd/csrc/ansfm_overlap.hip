@@ -112,8 +112,13 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
         if (rc) return rc;
     }
     p.scratch = ctx->scratch.as<double>();
+    // the trimmed fast path groups a wave's lanes over rows (LaneRow: the same tiles per 64-wavenumber block, so the grid and the
+    // queues above hold).  64 wavenumbers of one row per wave remain for ANSFM_MERGE_LANES=wavenumbers and for a launch of 2^24
+    // rows or more, whose cell numbers would leave the 32 bits lane_row computes in; bit 32 of the reported trims tells which ran
+    bool lane_rows = opt != 0 && (long)n_models * L < (1L << 24);
+    if (const char *ev = getenv("ANSFM_MERGE_LANES")) { if (!strcmp(ev, "wavenumbers")) lane_rows = false; }
     ctx->merge_block_waves = nwaves;
-    ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0);
+    ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0) | (lane_rows ? kOptLaneRows : 0);
     if (keys32) {
         HIPCHK(launch_overlap32(p, from_k, merge_list_len(G), (unsigned)grid, ctx->stream));
         return ANSFM_OK;
@@ -127,7 +132,7 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             lds_allowed = lds;                                                                                      \
         }                                                                                                           \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p);                  \
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p, lane_rows ? 1 : 0);  \
     } while (0)
 #define LAUNCH_OV2(D, FK, W32)                                                                                      \
     do {                                                                                                            \
@@ -136,13 +141,13 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
         else if (opt != 0)                                                                                          \
             LAUNCH_OPT(k_ck_overlap<D, FK, W32, true, true, false, merge_opt_of(W32)>);                             \
         else if (nodiv && nobox)                                                                                         \
-            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0); \
         else if (nodiv)                                                                                             \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0); \
         else if (sorted)                                                                                            \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p);  \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0);  \
         else                                                                                                        \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p); \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0); \
     } while (0)
 #define LAUNCH_OV(D, FK)                                                                              \
     do {                                                                                              \

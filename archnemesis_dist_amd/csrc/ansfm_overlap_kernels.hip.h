@@ -9,8 +9,9 @@ namespace ansfm {
 //
 // One LANE per (wavenumber, layer) cell; a wavefront = 64 consecutive wavenumbers of ONE layer, so
 // corner indices, u, v and gas amounts are wave-uniform (SGPRs) and every table access is one
-// 512-byte coalesced row.  The reference sorts the G*G sums tau_i + k_j*amount (argsort) and
-// walks the sorted list once to re-bin it (rank, ForwardModel_0.py:6117-6173).  Both inputs are
+// 512-byte coalesced row.  (The fast path, OPT != 0, can instead take kLaneNV wavenumbers x 64 / kLaneNV rows per wave,
+// the argument lane_rows and LaneRow in ansfm_merge_common.hip.h: the merge below does not care which cell a lane holds.)
+// The reference sorts the G*G sums tau_i + k_j*amount (argsort) and walks the sorted list once to re-bin it (rank, ForwardModel_0.py:6117-6173).  Both inputs are
 // already sorted in g, so the sorted sequence is produced by a G-way streaming merge of the rows
 // (a_i + b_0..b_{G-1}) -- the row heads held as a sorted list in registers, see merge_step -- and rank's walk
 // consumes it on the fly: nothing of size G*G is ever stored.  The per-lane arrays a[G], b[G+1] live in LDS as
@@ -30,9 +31,23 @@ namespace ansfm {
 // product table WT; rows, tile queue, bin records and the sentinel row stay per wave and there is no barrier after the one
 // that publishes the tables, so the waves run and leave independently as the one-wave blocks do.  With kOptOrient a wave's
 // rows are a[G], a "huge" row, b[G], a "huge" row (merge_wave_rows): column G of either operand is a sentinel.
+// Gas s of the cell a lane holds, in either mapping: the lane's own row (fast path with lane_rows) or row (m, l) of the wave
+template <bool FROM_K, bool NOBOX, int OPT>
+__device__ __forceinline__ void load_cell(const OverlapParams &p, int lane_rows, const LaneRow &lr, const LayerInterp &q, int m,
+                                          int l, int s, int nu, double *DST, int lane, bool &unsorted)
+{
+    if constexpr (OPT != 0) {
+        if (lane_rows != 0) {
+            load_gas_rows<FROM_K, NOBOX>(p, lr, s, DST, lane, unsorted);
+            return;
+        }
+    }
+    load_gas<FROM_K, false, NOBOX>(p, q, m, l, s, nu, DST, lane, unsorted);
+}
+
 template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false, int OPT = 0>
 __global__ __launch_bounds__((OPT & kOptTable) != 0 ? kWave * kMaxBlockWaves : kWave) __attribute__((amdgpu_waves_per_eu(1, 2)))
-void k_ck_overlap(OverlapParams p)
+void k_ck_overlap(OverlapParams p, int lane_rows)
 {
     static_assert(OPT == 0 || (SORTED && NODIV), "the fast path");
     static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
@@ -81,17 +96,26 @@ void k_ck_overlap(OverlapParams p)
     tq.init();
     for (;;) {
         int vt = 0, m = 0, l = 0;
-        if (!tq.next(p, lane, vt, m, l)) break;
+        LaneRow lr{};                                   // layer-grouped lanes (OPT != 0 and lane_rows): the lane's own row
+        if constexpr (OPT != 0) {
+            if (lane_rows != 0) {
+                unsigned k = 0;
+                if (!tq.next_rows(p, lane, vt, k)) break;
+                lr = lane_row<FROM_K>(p, vt, k, lane);
+            } else if (!tq.next(p, lane, vt, m, l)) break;
+        } else {
+            if (!tq.next(p, lane, vt, m, l)) break;
+        }
         const int nu = vt * kWave + lane;
         LayerInterp q;
         if constexpr (!FROM_K) q = p.li[(size_t)m * p.L + l];
         bool unsorted = false;
 
-        load_gas<FROM_K, false, NOBOX>(p, q, m, l, 0, nu, A, lane, unsorted);
+        load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, lr, q, m, l, 0, nu, A, lane, unsorted);
         double alast = A[(G - 1) * kWave + lane];       // last g-ordinate in the ORIGINAL order
         if constexpr (!SORTED) sort_column(A, PA, G, lane);
         for (int s = 1; s < p.S; ++s) {
-            load_gas<FROM_K, false, NOBOX>(p, q, m, l, s, nu, B, lane, unsorted);
+            load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, lr, q, m, l, s, nu, B, lane, unsorted);
             if constexpr (SORTED)                       // the call is rerun on the generic path: no point in merging
                 if (__builtin_amdgcn_ballot_w64(unsorted) != 0) break;
             const double blast = B[(G - 1) * kWave + lane];
@@ -226,6 +250,14 @@ void k_ck_overlap(OverlapParams p)
                     for (int g = 0; g < G; ++g) PA[g * kWave + lane] = (unsigned char)g;
                     alast = A[(G - 1) * kWave + lane];
                 }
+            }
+        }
+        if constexpr (OPT != 0) {
+            if (lane_rows != 0) {                     // the lane's own row of tau[n][L][G][Wpad]
+                if (unsorted) atomicOr(p.err_flag, 1);
+                double *outr = p.tau + ((size_t)lr.row * G) * p.Wpad + lr.nu;
+                for (int g = 0; g < G; ++g) outr[(size_t)g * p.Wpad] = A[g * kWave + lane];
+                continue;
             }
         }
         double *out = p.tau + (((size_t)m * p.L + l) * G) * p.Wpad + nu;

@@ -280,7 +280,9 @@ class AnsfmEngine:
 
     def last_merge_launch(self):
         """(waves per block, trim bits) of the last forward merge launch: bits 1 weight table, 2 key repack,
-        8 list pass that ends at the insertion point, 16 per-lane row operand (4: retired, never set)."""
+        8 list pass that ends at the insertion point, 16 per-lane row operand, 32 a wave's lanes grouped over rows
+        (clear with ANSFM_MERGE_LANES=wavenumbers and for a launch of 2^24 (model, layer) rows or more, which keeps 64
+        wavenumbers of one row per wave) (4: retired, never set)."""
         w, t = C.c_int(), C.c_int()
         self._check(self._lib.ansfm_last_merge_launch(self._ctx, C.byref(w), C.byref(t)), "last_merge_launch")
         return int(w.value), int(t.value)
