@@ -97,12 +97,12 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
     HIPCHK(ctx->d_temp.reserve(NT * sizeof(double)));
     HIPCHK(ctx->d_wave.reserve((size_t)W * sizeof(double)));
     HIPCHK(ctx->d_delg.reserve(kMaxG * sizeof(double)));
-    HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
+    HIPCHK(ctx->d_flag.reserve(kFlagInts * sizeof(int)));
     HIPCHK(hipMemcpyAsync(ctx->d_press.p, PRESS, NP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_temp.p, TEMP, NT * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_wave.p, WAVE, (size_t)W * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_delg.p, DELG, G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_flag.p, 0, 16 * sizeof(int), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_flag.p, 0, kFlagInts * sizeof(int), ctx->stream));
     {
         const int Q = NP * NT * S;
         hipLaunchKernelGGL(k_table_check, dim3(nblk((size_t)W * Q, 256)), dim3(256), 0, ctx->stream, K_dev, W, G, Q,
@@ -299,12 +299,12 @@ static int upload_table_files(ansfm_ctx *ctx, int S, const char *const *paths, d
     HIPCHK(ctx->d_temp.reserve(TEMP.size() * sizeof(double)));                 // [NP][NT] for a table with NT < 0
     HIPCHK(ctx->d_wave.reserve((size_t)W * sizeof(double)));
     HIPCHK(ctx->d_delg.reserve(kMaxG * sizeof(double)));
-    HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
+    HIPCHK(ctx->d_flag.reserve(kFlagInts * sizeof(int)));
     HIPCHK(hipMemcpyAsync(ctx->d_press.p, PRESS.data(), NP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_temp.p, TEMP.data(), TEMP.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_wave.p, WAVE.data(), (size_t)W * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_delg.p, DELG.data(), G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->d_flag.p, 0, 16 * sizeof(int), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_flag.p, 0, kFlagInts * sizeof(int), ctx->stream));
     const size_t per_wave = (size_t)NP * NT * G;
     std::vector<float> block(per_wave * W);
     HIPCHK(ctx->tmp_in.reserve(block.size() * sizeof(float)));
@@ -389,6 +389,23 @@ int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *tri
     if (!ctx || !waves_per_block || !trims) return ANSFM_ERR_INVALID;
     *waves_per_block = ctx->merge_block_waves;
     *trims = ctx->merge_trims;
+    return ANSFM_OK;
+}
+
+int ansfm_last_merge_rowmajor(const ansfm_ctx *cctx, int64_t *merges, int64_t *merges_total)
+{
+    ansfm_ctx *ctx = const_cast<ansfm_ctx *>(cctx);     // the error text and the stream: nothing of the launch's state changes
+    CHECK_CTX(ctx);
+    if (!merges || !merges_total) FAIL(ANSFM_ERR_INVALID, "last_merge_rowmajor: null argument");
+    *merges = *merges_total = 0;
+    if (ctx->d_flag.bytes < kFlagInts * sizeof(int)) return ANSFM_OK;    // nothing has been launched
+    HIPCHK(hipSetDevice(ctx->device));
+    // the only place the two totals are read: the launch itself gains no stream operation
+    unsigned long long v[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(v, ctx->d_flag.as<int>() + kFlagTileCounter + 8, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *merges = (int64_t)v[0];
+    *merges_total = (int64_t)v[1];
     return ANSFM_OK;
 }
 
@@ -800,7 +817,7 @@ int ansfm_merge_redo_count(ansfm_ctx *ctx, int64_t *count)
     if (!count) FAIL(ANSFM_ERR_INVALID, "merge_redo_count: null argument");
     HIPCHK(hipSetDevice(ctx->device));
     int v = 0;
-    HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
+    HIPCHK(ctx->d_flag.reserve(kFlagInts * sizeof(int)));
     HIPCHK(hipMemcpyAsync(&v, ctx->d_flag.as<int>() + 13, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *count = v;
@@ -954,7 +971,7 @@ int ansfm_k_overlap(ansfm_ctx *ctx, int W, int G, int L, int S, const double *de
     Stager st{ctx};
     const double *dk = st.up(k, nk), *dam = st.up(amount, (size_t)S * L), *ddg = st.up(del_g, G);
     if (st.rc) return st.rc;
-    HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
+    HIPCHK(ctx->d_flag.reserve(kFlagInts * sizeof(int)));
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     const size_t nkin = (size_t)S * L * G * Wpad;
     HIPCHK(ctx->tmp_in.reserve(nkin * sizeof(double)));
@@ -1358,7 +1375,7 @@ int ansfm_k_overlapg(ansfm_ctx *ctx, int W, int G, int L, int S, const double *d
     Stager st{ctx};
     const double *dkk = st.up(k, nk), *dam = st.up(amount, (size_t)S * L), *ddg = st.up(del_g, G), *ddk = st.up(dkdT, nk);
     if (st.rc) return st.rc;
-    HIPCHK(ctx->d_flag.reserve(16 * sizeof(int)));
+    HIPCHK(ctx->d_flag.reserve(kFlagInts * sizeof(int)));
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     const size_t nkin = (size_t)S * L * G * Wpad;
     HIPCHK(ctx->tmp_in.reserve(nkin * sizeof(double)));

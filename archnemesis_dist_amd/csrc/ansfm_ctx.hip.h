@@ -86,6 +86,11 @@ using ansfm::DevBuf;
 using ansfm::FusedRoute;
 using ansfm::LblrtIso;
 
+// ints of ansfm_ctx::d_flag: 0 the upload kernels' flag, 1 "unsorted input", 12 the de-duplication's row counter, 13 the
+// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's two
+// 64-bit totals (row-major merges, all merges), which one memset per launch clears together (merge_launch_begin)
+constexpr int kFlagInts = 32, kFlagTileCounter = 16;
+
 struct ansfm_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;

@@ -13,6 +13,7 @@
 //             near the front of the list (kOptOrient, MergeOrient).  With float32 weights the pair weight is in addition one
 //             ds_read_b64 of a product table WT[(col << 5) | row] that the waves of one block per CU share (kOptTable); with
 //             float64 weights the walk's gd + DG[i] * DG[j] is compiled as one fma, which no table of products reproduces.
+//             With the table, a wave whose lanes' merges all sort row by row walks them without the list (merge_rowmajor).
 // Both forms give the same results bit for bit (tests/test_merge_*.py).  What each piece bought, and the variants that were
 // measured and lost (tools/experiments/r07_merge_retired_variants.patch), is in DESIGN.md section 4.1.
 #pragma once
@@ -43,6 +44,10 @@ constexpr int kOptTable = 1, kOptBfi = 2, kOptExit = 8, kOptOrient = 16;
 constexpr int kMergeOpt = kOptTable | kOptBfi | kOptExit | kOptOrient;
 // reported beside them, a launch parameter and not a bit of OPT: the lanes of a wave are grouped over rows (k_ck_overlap's argument lane_rows)
 constexpr int kOptLaneRows = 32;
+// likewise a launch parameter (bit 1 of the same argument, instantiations with kOptTable only): a wave whose lanes' merges all
+// sort row by row walks them without the head list (merge_rowmajor)
+constexpr int kOptRowMajor = 64;
+constexpr int kFlagLaneRows = 1, kFlagRowMajor = 2;      // k_ck_overlap's argument flags
 // The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
 __host__ __device__ constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
 // Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
@@ -423,6 +428,96 @@ __device__ __forceinline__ void merge_init(double (&R)[NR], int G, const MergeOr
         R[i] = (i < G) ? __longlong_as_double((long long)((b & ~0x7FFULL) | (unsigned long long)((unsigned)i << mo.rsh))) : huge;
     }
     merge_init_order<NR>(R, G, huge);
+}
+
+// ---- row-major merges (kOptRowMajor): the sorted order known before the first step --------------------------------------------
+// With kOptOrient the rows are the operand with the larger top ordinate, and where the other operand is negligible beside it the
+// G x G sums sort row by row: r_0 + c_0 .. r_0 + c_{G-1}, r_1 + c_0, ...  The list merge pops keys in ascending order, and within a
+// row the keys ascend strictly (the sums are monotone in the column, and the column is in the low bits in both packings), so
+// the popped order is row-major iff K(i, G-1) < K(i+1, 0) for every i + 1 < G -- the doubles the list itself compares, ties
+// included.  R holds the heads K(i, 0) as merge_init left them: in a lane whose heads were not ascending they are the sorted
+// heads instead, and such a lane fails by itself (passing would put K(i, 0) < K(i, G-1) < R[i+1] for every i, i.e. row i's
+// head among the i + 1 smallest for every i, i.e. the heads ascending).  True when every active lane of the wave passes.
+template <int NR>
+__device__ __forceinline__ bool merge_rowmajor_test(const double (&R)[NR], int G, const MergeOrient &mo)
+{
+    const double cl = lds_ld(mo.cbase + (unsigned)(G - 1) * 512u);
+    const unsigned lowc = (unsigned)(G - 1) << mo.csh;
+    bool fail = false;
+#pragma unroll
+    for (int i = 0; i + 1 < NR; ++i) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(lds_ld(mo.rbase + (unsigned)(i < G ? i : 0) * 512u) + cl);
+        const double last = __longlong_as_double((long long)((b & ~0x7FFULL) | (unsigned long long)(((unsigned)i << mo.rsh) | lowc)));
+        fail |= (i + 1 < G) & !(last < R[i + 1]);
+    }
+    return __builtin_amdgcn_ballot_w64(fail) == 0;
+}
+// The columns j < merge_rowmajor_sure_cols(NR) exist in every launch of list length NR: the launcher takes the smallest list
+// length >= G (merge_list_len: 8, 10, 16, 20, 32) and the division-free walk needs G >= 2.  Saves the guard j < G, nothing else.
+__host__ __device__ constexpr int merge_rowmajor_sure_cols(int NR)
+{
+    return NR == 10 ? 9 : NR == 16 ? 11 : NR == 20 ? 17 : NR == 32 ? 21 : 2;
+}
+// One row of a row-major merge: the walk over its G elements, the row's entry, the columns and the row of the (symmetric) weight
+// table in registers
+template <int NR>
+__device__ __forceinline__ void merge_rowmajor_row(double ai, const double (&c)[NR], const double (&w)[NR], int G, WalkState &ws,
+                                                   double *rec)
+{
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        if (j < merge_rowmajor_sure_cols(NR) || j < G) {
+            MergeElem e;
+            e.ai = ai; e.bc = c[j]; e.w = w[j];
+            merge_walk_nodiv(e, ws, rec);
+        }
+    }
+}
+template <int NR>
+__device__ __forceinline__ void merge_rowmajor_weights(double (&w)[NR], double &ai, int i, int G, const MergeOrient &mo)
+{
+    // WT[(j << 5) | i]: one address for the whole wave, the column an immediate offset
+    const unsigned wa = kLdsWT + ((unsigned)i << 3);
+    ai = lds_ld(mo.rbase + ((unsigned)i << 9));
+#pragma unroll
+    for (int j = 0; j < NR; ++j) w[j] = lds_ld(wa + (unsigned)(j < merge_rowmajor_sure_cols(NR) || j < G ? j : 0) * 256u);
+}
+// The walk of a merge that merge_rowmajor_test passed, without the list: the same elements in the same order through the same
+// merge_walk_nodiv, so ws ends as the list path leaves it.  Row and column are loop counters, the columns stay in registers
+// (where the list kept its heads), and the weights and the entry of row i + 1 are read while row i is walked -- nothing
+// depends on a value fetched in the step before.  Two rows per trip: the two sets of weights alternate without a copy.
+template <int NR>
+__device__ __forceinline__ void merge_rowmajor(int G, const MergeOrient &mo, WalkState &ws, double *rec)
+{
+    double c[NR], w0[NR], a0;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) c[j] = lds_ld(mo.cbase + (unsigned)(j < G ? j : 0) * 512u);
+    if constexpr (NR > 20) {
+        // arrays of 32 weights beside the 32 columns do not fit the registers of two waves per SIMD: a weight is read for its step
+        for (int i = 0; i < G; ++i) {
+            const unsigned wa = kLdsWT + ((unsigned)i << 3);
+            a0 = lds_ld(mo.rbase + ((unsigned)i << 9));
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                if (j < merge_rowmajor_sure_cols(NR) || j < G) {
+                    MergeElem e;
+                    e.ai = a0; e.bc = c[j]; e.w = lds_ld(wa + (unsigned)j * 256u);
+                    merge_walk_nodiv(e, ws, rec);
+                }
+            }
+        }
+        return;
+    }
+    double w1[NR], a1;
+    merge_rowmajor_weights<NR>(w0, a0, 0, G, mo);
+    for (int i = 0; i < G; i += 2) {
+        merge_rowmajor_weights<NR>(w1, a1, i + 1 < G ? i + 1 : i, G, mo);
+        merge_rowmajor_row<NR>(a0, c, w0, G, ws, rec);
+        if (i + 1 < G) {
+            merge_rowmajor_weights<NR>(w0, a0, i + 2 < G ? i + 2 : i, G, mo);
+            merge_rowmajor_row<NR>(a1, c, w1, G, ws, rec);
+        }
+    }
 }
 
 // Per-lane insertion sort of one LDS column (values ascending, stable) carrying the original index of every

@@ -16,7 +16,8 @@ void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, in
     p.del_g = del_g_dev;
     p.tau = tau;
     p.err_flag = ctx->d_flag.as<int>() + 1;
-    p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + 4);
+    // eight tile queues, then the forward merge's two 64-bit totals (ansfm_last_merge_rowmajor): cleared by one memset
+    p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + kFlagTileCounter);
     p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
     p.delg_f32 = ctx->delg_f32;
     // g_ord = [0, cumsum(del_g)], g_ord[ng] = 1 (ForwardModel_0.py:6141-6143); float32 cumsum when DELG is
@@ -44,7 +45,7 @@ int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, size_t block_byte
     if (grid > ntiles) grid = ntiles;
     if (grid < 1) grid = 1;
     for (const MergeWorkspace &w : workspaces) HIPCHK(w.buf->reserve((size_t)grid * w.bytes_per_block));
-    HIPCHK(hipMemsetAsync(p.tile_counter, 0, 8 * sizeof(unsigned int), ctx->stream));
+    HIPCHK(hipMemsetAsync(p.tile_counter, 0, (8 + 4) * sizeof(unsigned int), ctx->stream));
     *grid_out = grid;
     return ANSFM_OK;
 }
@@ -117,8 +118,13 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     // rows or more, whose cell numbers would leave the 32 bits lane_row computes in; bit 32 of the reported trims tells which ran
     bool lane_rows = opt != 0 && (long)n_models * L < (1L << 24);
     if (const char *ev = getenv("ANSFM_MERGE_LANES")) { if (!strcmp(ev, "wavenumbers")) lane_rows = false; }
+    // the instantiations with the weight table walk a wave's row-major merges without the head list (merge_rowmajor);
+    // ANSFM_MERGE_ROWMAJOR=0 launches the same kernel with the walk off.  Bit 64 of the reported trims, in either lane mapping
+    bool rowmajor = (opt & kOptTable) != 0;
+    if (const char *ev = getenv("ANSFM_MERGE_ROWMAJOR")) { if (ev[0] == '0') rowmajor = false; }
+    const int flags = (lane_rows ? kFlagLaneRows : 0) | (rowmajor ? kFlagRowMajor : 0);
     ctx->merge_block_waves = nwaves;
-    ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0) | (lane_rows ? kOptLaneRows : 0);
+    ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0) | (lane_rows ? kOptLaneRows : 0) | (rowmajor ? kOptRowMajor : 0);
     if (keys32) {
         HIPCHK(launch_overlap32(p, from_k, merge_list_len(G), (unsigned)grid, ctx->stream));
         return ANSFM_OK;
@@ -132,7 +138,7 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             lds_allowed = lds;                                                                                      \
         }                                                                                                           \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p, lane_rows ? 1 : 0);  \
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p, flags);            \
     } while (0)
 #define LAUNCH_OV2(D, FK, W32)                                                                                      \
     do {                                                                                                            \

@@ -10,7 +10,7 @@ namespace ansfm {
 // One LANE per (wavenumber, layer) cell; a wavefront = 64 consecutive wavenumbers of ONE layer, so
 // corner indices, u, v and gas amounts are wave-uniform (SGPRs) and every table access is one
 // 512-byte coalesced row.  (The fast path, OPT != 0, can instead take kLaneNV wavenumbers x 64 / kLaneNV rows per wave,
-// the argument lane_rows and LaneRow in ansfm_merge_common.hip.h: the merge below does not care which cell a lane holds.)
+// bit 0 of the argument flags and LaneRow in ansfm_merge_common.hip.h: the merge below does not care which cell a lane holds.)
 // The reference sorts the G*G sums tau_i + k_j*amount (argsort) and walks the sorted list once to re-bin it (rank, ForwardModel_0.py:6117-6173).  Both inputs are
 // already sorted in g, so the sorted sequence is produced by a G-way streaming merge of the rows
 // (a_i + b_0..b_{G-1}) -- the row heads held as a sorted list in registers, see merge_step -- and rank's walk
@@ -47,12 +47,16 @@ __device__ __forceinline__ void load_cell(const OverlapParams &p, int lane_rows,
 
 template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false, int OPT = 0>
 __global__ __launch_bounds__((OPT & kOptTable) != 0 ? kWave * kMaxBlockWaves : kWave) __attribute__((amdgpu_waves_per_eu(1, 2)))
-void k_ck_overlap(OverlapParams p, int lane_rows)
+void k_ck_overlap(OverlapParams p, int flags)
 {
     static_assert(OPT == 0 || (SORTED && NODIV), "the fast path");
     static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
     constexpr bool kTable = (OPT & kOptTable) != 0, kOrient = (OPT & kOptOrient) != 0;
     static_assert(!kTable || W32, "the weight table holds float32 products only (launch_overlap)");
+    // flags: the row mapping (kFlagLaneRows) and, with kOptTable only, the list-free walk of row-major merges (kFlagRowMajor);
+    // the instantiations without the table are launched with 0 or 1 and test the word as they always did
+    const int lane_rows = kTable ? (flags & kFlagLaneRows) : flags;
+    unsigned n_rowmajor = 0, n_merged = 0;              // kOptTable: the merges of this wave that took the walk / all of them
     extern __shared__ double smem[];
     const int lane = kTable ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
     const int wv = kTable ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;     // wave of the block
@@ -126,6 +130,7 @@ void k_ck_overlap(OverlapParams p, int lane_rows)
             if (s == 1) { takeB = (alast <= 0.0); keepA = !takeB && (blast <= 0.0); }
             else { keepA = (blast <= 0.0); takeB = !keepA && (alast <= 0.0); }
             const bool do_merge = !(takeB | keepA);
+            bool walked = false;                        // kOptTable: the merge was walked row by row (wave-uniform where set)
             if (takeB) {
                 for (int g = 0; g < G; ++g) A[g * kWave + lane] = B[g * kWave + lane];
                 if constexpr (!SORTED) {
@@ -152,9 +157,20 @@ void k_ck_overlap(OverlapParams p, int lane_rows)
                     merge_init<NR>(R, G, mo, HUGE_KEY);
                 } else
                     merge_init<NR>(R, G, lane, A, B[lane], HUGE_KEY);
+                // (declared in this order on purpose: with the walk state first the compiler commutes operands of the walk in
+                // every instantiation -- same results, other instructions)
                 MergeElem e0, e1;
+                WalkState ws;
+                if constexpr (kTable) {
+                    if ((flags & kFlagRowMajor) != 0 && merge_rowmajor_test<NR>(R, G, mo)) {
+                        ws = walk_begin(GORD, lane);
+                        merge_rowmajor<NR>(G, mo, ws, rec);
+                        walked = true;
+                    }
+                }
+                if (!kTable || !walked) {               // (a constant without the table: those instantiations compile as they did)
                 merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB, mo);
-                WalkState ws = walk_begin(GORD, lane);
+                ws = walk_begin(GORD, lane);
                 // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
                 const int nloop = G * G - (G - 1);
                 // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
@@ -168,6 +184,7 @@ void k_ck_overlap(OverlapParams p, int lane_rows)
                 merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                 if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
                 merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                }
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
                     const int ig = walk_bins(ws, GORD);
@@ -251,6 +268,10 @@ void k_ck_overlap(OverlapParams p, int lane_rows)
                     alast = A[(G - 1) * kWave + lane];
                 }
             }
+            if constexpr (kTable) {
+                n_merged += __builtin_amdgcn_ballot_w64(do_merge) != 0 ? 1u : 0u;
+                n_rowmajor += __builtin_amdgcn_ballot_w64(walked) != 0 ? 1u : 0u;
+            }
         }
         if constexpr (OPT != 0) {
             if (lane_rows != 0) {                     // the lane's own row of tau[n][L][G][Wpad]
@@ -266,6 +287,14 @@ void k_ck_overlap(OverlapParams p, int lane_rows)
             for (int g = 0; g < G; ++g) out[(size_t)g * p.Wpad] = A[g * kWave + lane];
         } else {
             for (int g = 0; g < G; ++g) out[(size_t)PA[g * kWave + lane] * p.Wpad] = A[g * kWave + lane];
+        }
+    }
+    if constexpr (kTable) {
+        // the launch's two totals follow the tile counters (merge_params) and are cleared with them; added once per wave
+        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(p.tile_counter + 8);
+        if (lane == 0) {
+            atomicAdd(cnt, (unsigned long long)n_rowmajor);
+            atomicAdd(cnt + 1, (unsigned long long)n_merged);
         }
     }
 }

@@ -282,10 +282,19 @@ class AnsfmEngine:
         """(waves per block, trim bits) of the last forward merge launch: bits 1 weight table, 2 key repack,
         8 list pass that ends at the insertion point, 16 per-lane row operand, 32 a wave's lanes grouped over rows
         (clear with ANSFM_MERGE_LANES=wavenumbers and for a launch of 2^24 (model, layer) rows or more, which keeps 64
-        wavenumbers of one row per wave) (4: retired, never set)."""
+        wavenumbers of one row per wave), 64 row-major merges are walked without the head list (kernels with bit 1; clear with
+        ANSFM_MERGE_ROWMAJOR=0) (4: retired, never set)."""
         w, t = C.c_int(), C.c_int()
         self._check(self._lib.ansfm_last_merge_launch(self._ctx, C.byref(w), C.byref(t)), "last_merge_launch")
         return int(w.value), int(t.value)
+
+    def last_merge_rowmajor(self):
+        """(merges walked row by row, merges) of the last forward merge launch, counted per wave: a wave whose lanes' G x G sums
+        all sort row by row walks that merge without the head list (bit 64 of last_merge_launch's trims; off with
+        ANSFM_MERGE_ROWMAJOR=0).  (0, 0) for a kernel without the weight table, which does not count."""
+        m, t = C.c_int64(), C.c_int64()
+        self._check(self._lib.ansfm_last_merge_rowmajor(self._ctx, C.byref(m), C.byref(t)), "last_merge_rowmajor")
+        return int(m.value), int(t.value)
 
     # ---- array-level seams --------------------------------------------------------------------
     def calc_k(self, press, temp, grad=False):

@@ -82,6 +82,11 @@ int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed);
  * 4 retired, never set, 8 list pass that ends at the insertion point, 16 per-lane choice of the row operand;
  * 0: the code without them, or another path of the merge). */
 int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *trims);
+/* Further bits of trims that are launch parameters, not code variants: 32 a wave's lanes are grouped over rows; 64 a wave whose
+ * lanes' merges all sort row by row walks them without the head list (kernels with bit 1 only; ANSFM_MERGE_ROWMAJOR=0 clears it).
+ * ansfm_last_merge_rowmajor: the (wave, merge) pairs of the last forward merge launch that took that walk, and all pairs that
+ * merged; both 0 for a kernel without bit 1, which does not count.  Copies the two totals from the device (synchronises). */
+int ansfm_last_merge_rowmajor(const ansfm_ctx *ctx, int64_t *merges, int64_t *merges_total);
 
 /* ---- LBL tables (ILBL = LINE_BY_LINE_TABLES) ------------------------------------------------------
  * State of Spectroscopy_0 after read_tables on .lta / HDF5 LBL tables: K[W][NP][|NT|][S] (NG = 1),
