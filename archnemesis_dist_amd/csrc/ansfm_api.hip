@@ -122,6 +122,7 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
     ctx->have_table = true;
     ctx->is_lbl = 0; ctx->temp2d = 0;
     ctx->lblrt = 0; ctx->st_n = 0;       // a table replaces a committed line source
+    clear_continuum_sources(ctx);        // they were evaluated on the old table's grid
     return ANSFM_OK;
 }
 
@@ -340,6 +341,7 @@ static int upload_table_files(ansfm_ctx *ctx, int S, const char *const *paths, d
     ctx->have_table = true;
     ctx->is_lbl = lta ? 1 : 0; ctx->temp2d = (lta && hl.temp2d) ? 1 : 0;
     ctx->lblrt = 0; ctx->st_n = 0;
+    clear_continuum_sources(ctx);
     if (lta) ctx->monotone = 1;
     ctx->grid_f32 = 1; ctx->delg_f32 = lta ? 0 : 1;   // PRESS / TEMP / DELG come out of the file as float32 arrays (:2544-2559)
     return ANSFM_OK;
@@ -539,11 +541,11 @@ int ansfm::gas_opacity(ansfm_ctx *ctx, int rows, const double *press, const doub
 }
 
 // Layer de-duplication of a batch of n models x L layers (device rows as above): k_dedup_mark maps every (model, layer) to its
-// row in ctx->dd_slot [n][L] -- model 0's L rows first, then the layers in which another model differs (the Rayleigh columns
-// ray_totam / ray_f4 take part in the comparison when given) -- the row count is read back (synchronises), and k_dedup_gather
-// packs the distinct rows' press, temp [rows] and amount [S][rows] into ctx->dd_in.
+// row in ctx->dd_slot [n][L] -- model 0's L rows first, then the layers in which another model differs (the columns of
+// `cols`, what a fused continuum is formed from, take part in the comparison when given) -- the row count is read back
+// (synchronises), and k_dedup_gather packs the distinct rows' press, temp [rows] and amount [S][rows] into ctx->dd_in.
 int ansfm::dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
-                      const double *ray_totam, const double *ray_f4, DedupRows *out)
+                      const DedupCols *cols, DedupRows *out)
 {
     const int S = ctx->S;
     const size_t nl = (size_t)n * L;
@@ -552,7 +554,7 @@ int ansfm::dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const d
     int *counter = ctx->d_flag.as<int>() + 12;
     HIPCHK(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_dedup_mark, dim3(nblk(nl, 128)), dim3(128), 0, ctx->stream, n, L, S, press, temp, amount,
-                       ctx->dd_slot.as<int32_t>(), ctx->dd_work.as<int32_t>(), counter, ray_totam, ray_f4);
+                       ctx->dd_slot.as<int32_t>(), ctx->dd_work.as<int32_t>(), counter, cols ? *cols : DedupCols{});
     HIPCHK(hipGetLastError());
     int extra = 0;
     HIPCHK(hipMemcpyAsync(&extra, counter, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -618,13 +620,16 @@ namespace {
 // What the thermal, transmission, single-scattering and gradient entry points take, under the names and in the layouts of
 // include/ansfm.h.  The extern "C" function fills it once and everything below reads it (as MsCall in ansfm_scatter.hip); what
 // an entry does not take stays null or 0.  The arrays are host or device pointers as the entry says; igas_map is a host
-// pointer always, ray_totam / ray_f4 device pointers always.
+// pointer always, ray_totam / ray_f4 and the arrays of a fused continuum device pointers always.
 struct RtCall {
     int ISPACE = 0, n_models = 1, L = 0;
     const double *lay_press_pa = nullptr, *lay_temp = nullptr, *amount = nullptr;
     const double *taucont = nullptr, *tausca = nullptr, *phase = nullptr, *dtaucon = nullptr;
-    int ray_mode = 0;                       // != 0: the continuum is Rayleigh scattering alone, formed from the two arrays
+    int ray_mode = 0;                       // != 0: the continuum has Rayleigh scattering, formed from the two arrays
     const double *ray_totam = nullptr, *ray_f4 = nullptr;
+    // ansfm_cirsrad_ck_thermal_cont_dev: the continuum is (TAUCIA + TAUDUST) + TAURAY from the context's resident sources
+    int fused_cont = 0, use_cia = 0, use_dust = 0;
+    const double *lay_q = nullptr, *lay_frac = nullptr, *lay_delh = nullptr, *lay_cont = nullptr;   // the column: ray_totam
     int NVMR = 0, NPAR = 0;
     const int32_t *igas_map = nullptr;
     int P = 0, LIMAX = 0;
@@ -658,7 +663,8 @@ RtCall stage_call(ansfm_ctx *ctx, const RtCall &h, int *rc)
 }
 
 // Which (model, layer) opacities a forward call computes: all of them, or (a batch, with de-duplication on) the distinct ones;
-// the Rayleigh columns are part of a layer's identity only where the call forms its continuum from them.  De-duplicating
+// the columns a call forms its continuum from (Rayleigh: the column and the composition; CIA: the mixing ratios, the para-H2
+// fraction, the column and the thickness; aerosols: their columns) are part of a layer's identity.  De-duplicating
 // synchronises.  Records the outcome for ansfm_last_layer_rows / ansfm_get_taugas.
 struct GasRows {
     DedupRows k;               // the rows handed to the merge kernel
@@ -669,8 +675,12 @@ int gas_rows(ansfm_ctx *ctx, const RtCall &c, GasRows *g)
 {
     *g = GasRows{DedupRows{c.n_models * c.L, c.lay_press_pa, c.lay_temp, c.amount}, c.n_models, nullptr};
     if (ctx->dedup && c.n_models > 1 && !ctx->lblrt) {
-        const int rc = dedup_rows(ctx, c.n_models, c.L, c.lay_press_pa, c.lay_temp, c.amount, c.ray_mode ? c.ray_totam : nullptr,
-                                  c.ray_mode ? c.ray_f4 : nullptr, &g->k);
+        DedupCols x;
+        if (c.ray_mode || c.use_cia) x.add(c.ray_totam, 1);
+        if (c.ray_mode) x.add(c.ray_f4, 4);
+        if (c.use_cia) { x.add(c.lay_q, ctx->cia_NVMR); x.add(c.lay_frac, 1); x.add(c.lay_delh, 1); }
+        if (c.use_dust) x.add(c.lay_cont, ctx->dust_n);
+        const int rc = dedup_rows(ctx, c.n_models, c.L, c.lay_press_pa, c.lay_temp, c.amount, &x, &g->k);
         if (rc) return rc;
         g->n_k = 1;
         g->tau_slot = ctx->dd_slot.as<int32_t>();
@@ -711,7 +721,8 @@ extern "C" {
 /* ------------------------------------------------------------------------------------------ */
 /* fused CIRSrad (device pointers)                                                             */
 /* ------------------------------------------------------------------------------------------ */
-// c.ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); c.rt_mode 1:
+// c.ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); c.fused_cont:
+// CIA + aerosols + Rayleigh of the computed rows from the resident sources (ansfm_cirsrad_ck_thermal_cont_dev); c.rt_mode 1:
 // the path transmission (ansfm_cirsrad_ck_transmission); generic: the merge sorts every k-distribution first (the rerun of a
 // call whose table turned out not to be sorted in g)
 static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c, bool generic)
@@ -730,7 +741,15 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c, bool gen
     const int rows = g.k.rows;
     if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
     const double *cont_t = nullptr;
-    if (c.ray_mode) {
+    if (c.fused_cont) {
+        // CIA, aerosol and Rayleigh opacity of the rows that are computed, from the resident sources
+        ContCall k;
+        k.ISPACE = c.ISPACE; k.use_cia = c.use_cia; k.use_dust = c.use_dust; k.ray_mode = c.ray_mode;
+        k.temp = c.lay_temp; k.q = c.lay_q; k.frac = c.lay_frac; k.totam = c.ray_totam; k.delh = c.lay_delh; k.cont = c.lay_cont;
+        k.f4 = c.ray_f4;
+        if ((rc = launch_tau_cont_rows(ctx, rows, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, k))) return rc;
+        cont_t = ctx->cont_t.as<double>();
+    } else if (c.ray_mode) {
         // the Rayleigh continuum of the rows that are computed (the distinct layers of the batch), straight in the layout the RT
         // reads: the 201 states of a C3 Jacobian have 696 of them, not 20 100
         HIPCHK(ctx->cont_t.reserve((size_t)rows * Wpad * sizeof(double)));
@@ -751,7 +770,7 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c, bool gen
     rt_params_of_call(ctx, c, r);
     r.tau_slot = g.tau_slot;
     r.cont = cont_t;
-    r.cont_by_row = (c.ray_mode && g.tau_slot) ? 1 : 0;
+    r.cont_by_row = ((c.ray_mode || c.fused_cont) && g.tau_slot) ? 1 : 0;
     r.mode = c.rt_mode;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     rc = launch_rt(ctx, r, c.n_models);
@@ -790,6 +809,39 @@ int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, i
     RtCall c;
     c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
     c.ray_mode = ray_mode; c.ray_totam = TOTAM; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
+    c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
+    c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;
+    return cirsrad_ck_thermal_dev_impl(ctx, c, false);
+}
+
+int ansfm_cirsrad_ck_thermal_cont_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                      const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                      const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                      const double *lay_cont, int ray_mode, const double *f4, int P, int LIMAX,
+                                      const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP,
+                                      const double *TSURF, const double *EMISSIVITY, const double *SOLFLUX,
+                                      const double *REFLECTANCE, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                      double *SPECOUT)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
+    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
+        (!use_cia && !use_dust && !ray_mode) || ((use_cia || ray_mode) && !lay_totam) ||
+        (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont))
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: bad argument (at least one of use_cia, use_dust, ray_mode = IRAY 1, 2, "
+                                "4 or 12; the per-layer arrays of every term that is used)");
+    if (use_cia && !ctx->cia_on)
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: no CIA source on this table's grid (ansfm_upload_cia after the table)");
+    if (use_cia && ctx->cia_ispace != ISPACE)
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: the CIA source was uploaded for the other ISPACE");
+    if (use_dust && !ctx->dust_n)
+        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.fused_cont = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0;
+    c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
+    c.ray_mode = ray_mode; c.ray_totam = lay_totam; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
     c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
     c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
     c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;

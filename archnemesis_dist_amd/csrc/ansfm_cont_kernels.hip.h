@@ -30,14 +30,52 @@ struct CiaParams {
     int W, NWC, NPAIR, NPE, NT, L, NVMR, covers, ico2, in2, ih2;
 };
 
-__global__ __launch_bounds__(128) void k_tau_cia(CiaParams p)
+// The record of one layer (:4588-4666), including the reference's overwrite of temp1 in the upper para-fraction clamp
+// (:4623); comparisons of fabs() values, differences and quotients only, so the host (ansfm_calc_tau_cia) and the device
+// (k_cia_rows_prep) give the same bits.  The caller has made sure that the brackets stay inside K_CIA, or tests them.
+__host__ __device__ inline CiaLayer cia_layer(double temp1, double frac1, double xfac, int NT, const double *cia_temp, int nfrac,
+                                              const double *cia_frac, int NPARA)
 {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
-    if (w >= p.W) return;
-    const CiaLayer c = p.lay[l];
-    const double x = p.waven[w];
-    const double *q = p.q + (size_t)l * p.NVMR;
-    double *d = p.dtau ? p.dtau + ((size_t)w * p.L + l) * (p.NVMR + 2) : nullptr;
+    int it = 0;
+    for (int k = 1; k < NT; ++k) if (fabs(cia_temp[k] - temp1) < fabs(cia_temp[it] - temp1)) it = k;
+    int itl, ithi;
+    if (cia_temp[it] >= temp1) {
+        ithi = it;
+        if (it == 0) { temp1 = cia_temp[0]; itl = 0; ithi = 1; } else itl = it - 1;
+    } else {
+        itl = it;
+        if (it == NT - 1) { temp1 = cia_temp[it]; ithi = NT - 1; itl = NT - 2; } else ithi = it + 1;
+    }
+    int ip = 0;
+    for (int k = 1; k < nfrac; ++k) if (fabs(cia_frac[k] - frac1) < fabs(cia_frac[ip] - frac1)) ip = k;
+    int ipl, iphi;
+    if (cia_frac[ip] >= frac1) {
+        iphi = ip;
+        if (ip == 0) { frac1 = cia_frac[0]; ipl = 0; iphi = 1; } else ipl = ip - 1;
+    } else {
+        ipl = ip;
+        if (ip == NPARA - 1) { temp1 = cia_frac[ip]; iphi = NPARA - 1; ipl = NPARA - 2; } else iphi = ip + 1;
+    }
+    if (NPARA == 0) { ipl = 0; iphi = 0; }
+    CiaLayer c;
+    c.itl = itl; c.ithi = ithi; c.ipl = ipl; c.iphi = iphi;
+    c.fhl_t = (temp1 - cia_temp[itl]) / (cia_temp[ithi] - cia_temp[itl]);
+    c.fhh_t = (cia_temp[ithi] - temp1) / (cia_temp[ithi] - cia_temp[itl]);
+    c.dfhldT = 1.0 / (cia_temp[ithi] - cia_temp[itl]);
+    c.fhl_f = 0.5; c.fhh_f = 0.5;
+    if (nfrac > 1 && ipl >= 0 && iphi >= 0 && ipl < nfrac && iphi < nfrac) {
+        c.fhl_f = (frac1 - cia_frac[ipl]) / (cia_frac[iphi] - cia_frac[ipl]);
+        c.fhh_f = (cia_frac[iphi] - frac1) / (cia_frac[iphi] - cia_frac[ipl]);
+    }
+    c.xfac = xfac;
+    return c;
+}
+
+// sum over the pairs of k_cia q1 q2 at wavenumber x (index w of the k_co2 / k_n2n2 / k_n2h2 vectors) for a layer of record c
+// and mixing ratios q[NVMR]; TAUCIA = the sum * c.xfac.  d: the layer's NVMR + 2 gradient slots (zeroed), or nullptr.  One body
+// for k_tau_cia and k_tau_cont_rows: the two give the same bits.
+__device__ __forceinline__ double cia_sum(const CiaParams &p, const CiaLayer &c, double x, int w, const double *q, double *d)
+{
     double sum1 = 0.0;
     if (p.covers) {
         int lo = 0, hi = p.NWC;          // scipy interp1d: idx = clip(searchsorted(x, xn, 'left'), 1, n-1)
@@ -87,6 +125,16 @@ __global__ __launch_bounds__(128) void k_tau_cia(CiaParams p)
             d[p.in2] = d[p.in2] + q[p.ih2] * k;
         }
     }
+    return sum1;
+}
+
+__global__ __launch_bounds__(128) void k_tau_cia(CiaParams p)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
+    if (w >= p.W) return;
+    const CiaLayer c = p.lay[l];
+    double *d = p.dtau ? p.dtau + ((size_t)w * p.L + l) * (p.NVMR + 2) : nullptr;
+    const double sum1 = cia_sum(p, c, p.waven[w], w, p.q + (size_t)l * p.NVMR, d);
     p.tau[(size_t)w * p.L + l] = sum1 * c.xfac;
     if (d)
         for (int s = 0; s < p.NVMR + 2; ++s) d[s] = d[s] * c.xfac;
@@ -224,11 +272,10 @@ struct DustParams {
     int W, NWS, NDUST, L, cubic;
 };
 
-__global__ __launch_bounds__(128) void k_tau_dust(DustParams p)
+// extinction and scattering cross section of population i at x: the spline or its linear replacement (:4849-4859).  One body
+// for k_tau_dust and k_dust_kext_grid (ansfm_upload_dust).
+__device__ __forceinline__ void dust_k(const DustParams &p, double x, int i, double &kext, double &ksca)
 {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-    if (w >= p.W) return;
-    const double x = p.wavec[w];
     const int n = p.NWS;
     // spline interval: x in [x_a, x_a+1] (the last one closed); interp1d's: searchsorted(left) clipped to [1, n-1], minus 1
     int lo = 0, hi = n;
@@ -240,7 +287,7 @@ __global__ __launch_bounds__(128) void k_tau_dust(DustParams p)
     const double sa = p.ksca[(size_t)a * p.NDUST + i], sb = p.ksca[(size_t)(a + 1) * p.NDUST + i];
     const double lin_e = ((eb - ea) / (xb - xa)) * (x - xa) + ea;
     const double lin_s = ((sb - sa) / (xb - xa)) * (x - xa) + sa;
-    double kext = lin_e, ksca = lin_s;
+    kext = lin_e; ksca = lin_s;
     if (p.cubic) {
         const double t = x - xa;
         const double *ce = p.cext + ((size_t)i * (n - 1) + a) * 3;
@@ -251,6 +298,14 @@ __global__ __launch_bounds__(128) void k_tau_dust(DustParams p)
         kext = (inv_e || inv_b) ? lin_e : se;
         ksca = (inv_s || inv_b) ? lin_s : ss;
     }
+}
+
+__global__ __launch_bounds__(128) void k_tau_dust(DustParams p)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (w >= p.W) return;
+    double kext, ksca;
+    dust_k(p, p.wavec[w], i, kext, ksca);
     const double de = kext * 1.0e-4, ds = ksca * 1.0e-4;
     for (int j = 0; j < p.L; ++j) {
         const double c = p.cont[(size_t)j * p.NDUST + i];
@@ -260,6 +315,90 @@ __global__ __launch_bounds__(128) void k_tau_dust(DustParams p)
         p.dtaudust[o] = de;
         p.dtauclscat[o] = ds;
     }
+}
+
+// ansfm_upload_dust: the extinction cross sections on the table's grid, kext_w[NDUST][Wpad] (zero beyond W), as k_tau_dust
+// evaluates them.  One thread per (wavenumber, population).
+__global__ __launch_bounds__(128) void k_dust_kext_grid(DustParams p, int Wpad, double *__restrict__ kext_w)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (w >= Wpad) return;
+    double kext = 0.0, ksca;
+    if (w < p.W) dust_k(p, p.wavec[w], i, kext, ksca);
+    kext_w[(size_t)i * Wpad + w] = kext;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The continuum of the distinct layers of a batch from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust)
+// and the Rayleigh parametrisations, in the layout the thermal RT reads ([row][Wpad], zero beyond W):
+//     cont[row][w] = (TAUCIA + TAUDUST) + TAURAY          (calculate_layer_opacity :3989; an absent term is left out)
+// Row r is layer work[r] (flattened (state, layer); nullptr: r itself) of the per-layer arrays.  Every term is rounded as the
+// array-level kernels round it to memory before the sums -- no product is fused into a sum here.
+// ------------------------------------------------------------------------------------------------------------------
+struct ContRowsParams {
+    CiaParams cia;              // the resident table (waven, tau, dtau, W, L unused); lay [rows] by k_cia_rows_prep; q [n L][NVMR]
+    const double *cia_temp, *cia_frac;   // [NT], [nfrac]
+    const double *wave;         // [W] the table's grid
+    const int32_t *work;        // [rows] or nullptr
+    const double *temp, *frac, *totam, *delh;   // [n L]
+    const double *kext_w;       // [NDUST][Wpad]
+    const double *cont;         // [n L][NDUST]
+    const double *f4;           // [n L][4], ray_mode 4
+    double *out;                // [rows][Wpad]
+    CiaLayer *lay;              // [rows]
+    int rows, W, Wpad, ispace, use_cia, nfrac, NPARA, NDUST, ray_mode;
+};
+
+// One thread per row: the CIA record of the row's layer (the host loop of ansfm_calc_tau_cia; xfac as calc_tau_cia forms it,
+// (TOTAM 1e-4)^2 / (DELH 1e2))
+__global__ __launch_bounds__(64) void k_cia_rows_prep(ContRowsParams p)
+{
+#pragma clang fp contract(off)
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= p.rows) return;
+    const int l = p.work ? p.work[r] : r;
+    const double t = p.totam[l] * 1.0e-4;
+    const double xfac = (t * t) / (p.delh[l] * 1.0e2);
+    p.lay[r] = cia_layer(p.temp[l], p.frac[l], xfac, p.cia.NT, p.cia_temp, p.nfrac, p.cia_frac, p.NPARA);
+}
+
+// One thread per (row, wavenumber), a block within one row (blockIdx.x), coalesced along the wavenumbers
+__global__ __launch_bounds__(256) void k_tau_cont_rows(ContRowsParams p)
+{
+#pragma clang fp contract(off)
+    const int r = blockIdx.x, w = blockIdx.y * blockDim.x + threadIdx.x;
+    if (w >= p.Wpad) return;
+    double *out = p.out + (size_t)r * p.Wpad + w;
+    if (w >= p.W) { *out = 0.0; return; }
+    const int l = p.work ? p.work[r] : r;
+    const double v = p.wave[w];
+    double tau = 0.0;
+    bool any = false;
+    if (p.use_cia) {
+        const CiaLayer c = p.lay[r];
+        const double x = p.ispace == 0 ? v : 1.e4 / v;             // :4565
+        const double sum1 = cia_sum(p.cia, c, x, w, p.cia.q + (size_t)l * p.cia.NVMR, nullptr);
+        tau = sum1 * c.xfac;
+        any = true;
+    }
+    if (p.NDUST > 0) {
+        double dust = 0.0;
+        for (int d = 0; d < p.NDUST; ++d) {
+            const double de = p.kext_w[(size_t)d * p.Wpad + w] * 1.0e-4;
+            double t = de * p.cont[(size_t)l * p.NDUST + d];
+            t = (t != t) ? 0.0 : t;                                  // np.nan_to_num; +-inf end at the bounds of the clip
+            t = t > 0.0 ? t : 0.0;                                   // np.clip(., 0, 1e20)  (:3966)
+            t = t < 1.0e20 ? t : 1.0e20;
+            dust = d == 0 ? t : dust + t;                            // np.sum over fewer than 8 populations: in order
+        }
+        tau = any ? tau + dust : dust;
+        any = true;
+    }
+    if (p.ray_mode) {
+        const double ray = rayleigh_k(p.ray_mode, p.ispace, v, p.ray_mode == 4 ? p.f4 + (size_t)l * 4 : nullptr) * p.totam[l];
+        tau = any ? tau + ray : ray;
+    }
+    *out = tau;
 }
 
 }  // namespace ansfm

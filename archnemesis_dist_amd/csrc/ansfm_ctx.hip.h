@@ -114,6 +114,13 @@ struct ansfm_ctx {
     int is_lbl = 0, temp2d = 0;   // LBL-table mode (ILBL=2): G = 1, TEMP may be [NP][NT]
     DevBuf lnK, d_press, d_temp, d_wave, d_delg, d_flag;
     std::vector<double> h_delg;
+    // resident continuum sources on the table's grid (ansfm_upload_cia / ansfm_upload_dust; a new table clears them)
+    //   cia_tab: cia_waven [NWC], K_CIA [NPAIR][NPE][NT][NWC], cia_temp [NT], cia_frac [nfrac], k_co2, k_n2n2, k_n2h2 [W] each
+    //   cia_idx: igas1, igas2 [NPAIR];  cia_lay: the CiaLayer records of a call's rows;  dust_kext: kext_w [NDUST][Wpad]
+    DevBuf cia_tab, cia_idx, cia_lay, dust_kext;
+    int cia_on = 0, cia_ispace = 0, cia_NWC = 0, cia_NPAIR = 0, cia_NPE = 0, cia_NT = 0, cia_nfrac = 0, cia_NPARA = 0, cia_NVMR = 0,
+        cia_ico2 = -1, cia_in2 = -1, cia_ih2 = -1, cia_covers = 0;
+    int dust_n = 0;                         // NDUST of the uploaded aerosol source, 0: none
 
     // workspaces
     DevBuf li, tau, scratch, cont_t, tmp_in, tmp_out, misc;
@@ -216,8 +223,12 @@ struct DedupRows {
     int rows;
     const double *press, *temp, *amount;
 };
+// further per-layer inputs that are part of a row's identity: arrays [n L][width] (ansfm_table_kernels.hip.h)
+struct DedupCols;
 int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
-               const double *ray_totam, const double *ray_f4, DedupRows *out);
+               const DedupCols *cols, DedupRows *out);
+// a table has been uploaded: the continuum sources on the old grid go
+inline void clear_continuum_sources(ansfm_ctx *ctx) { ctx->cia_on = 0; ctx->dust_n = 0; }
 // ansfm_api.hip, what the gradient RT entries and the transit entry (ansfm_transit.hip) share (described where they are
 // defined): the gas stage of a gradient call, the merge slot behind every parameter, the end of a call without a generic rerun
 int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
@@ -231,6 +242,13 @@ void launch_lblrt_tau(ansfm_ctx *ctx, int n, int L, int m0, const double *amount
 // list, or nullptr for every (model, layer) in order
 void launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int ISPACE, const int32_t *slot_rows, const double *ray_totam,
                               const double *ray_f4);
+// ansfm_ops.hip: k_cia_rows_prep + k_tau_cont_rows for the thermal branch, into ctx->cont_t [rows][Wpad]: (TAUCIA + TAUDUST) +
+// TAURAY of the rows from the resident sources; the arrays are device pointers over the n * L layers of the call
+struct ContCall {
+    int ISPACE = 0, use_cia = 0, use_dust = 0, ray_mode = 0;
+    const double *temp = nullptr, *q = nullptr, *frac = nullptr, *totam = nullptr, *delh = nullptr, *cont = nullptr, *f4 = nullptr;
+};
+int launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c);
 
 // ansfm_overlap.hip / ansfm_overlapg.hip: k_ck_overlap (or k_ck_overlap32) and k_ck_overlapg over n_models x L layers into tau
 // (and dk); from_k: the array-level seams' k (and dkdT) instead of the table; generic: per-lane sort first (rerun of an unsorted call)

@@ -16,6 +16,39 @@ void ansfm::launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int
                        ray_mode, ISPACE, ctx->d_wave.as<double>(), slot_rows, ray_totam, ray_f4, ctx->cont_t.as<double>());
 }
 
+int ansfm::launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c)
+{
+    const int W = ctx->W, Wpad = ctx->Wpad;
+    HIPCHK(ctx->cont_t.reserve((size_t)rows * Wpad * sizeof(double)));
+    ContRowsParams p;
+    memset(&p, 0, sizeof p);
+    p.wave = ctx->d_wave.as<double>(); p.work = slot_rows; p.out = ctx->cont_t.as<double>();
+    p.rows = rows; p.W = W; p.Wpad = Wpad; p.ispace = c.ISPACE; p.ray_mode = c.ray_mode;
+    p.totam = c.totam; p.f4 = c.f4;
+    if (c.use_dust) { p.kext_w = ctx->dust_kext.as<double>(); p.cont = c.cont; p.NDUST = ctx->dust_n; }
+    if (c.use_cia) {
+        HIPCHK(ctx->cia_lay.reserve((size_t)rows * sizeof(CiaLayer)));
+        const size_t nK = (size_t)ctx->cia_NPAIR * ctx->cia_NPE * ctx->cia_NT * ctx->cia_NWC;
+        const double *t = ctx->cia_tab.as<double>();
+        CiaParams &k = p.cia;
+        k.cia_waven = t; k.K = t + ctx->cia_NWC; p.cia_temp = k.K + nK; p.cia_frac = p.cia_temp + ctx->cia_NT;
+        k.k_co2 = p.cia_frac + ctx->cia_nfrac; k.k_n2n2 = k.k_co2 + W; k.k_n2h2 = k.k_n2n2 + W;
+        k.g1 = ctx->cia_idx.as<int32_t>(); k.g2 = k.g1 + ctx->cia_NPAIR;
+        k.q = c.q;
+        k.W = W; k.NWC = ctx->cia_NWC; k.NPAIR = ctx->cia_NPAIR; k.NPE = ctx->cia_NPE; k.NT = ctx->cia_NT; k.NVMR = ctx->cia_NVMR;
+        k.covers = ctx->cia_covers; k.ico2 = ctx->cia_ico2; k.in2 = ctx->cia_in2; k.ih2 = ctx->cia_ih2;
+        p.use_cia = 1; p.nfrac = ctx->cia_nfrac; p.NPARA = ctx->cia_NPARA;
+        p.temp = c.temp; p.frac = c.frac; p.delh = c.delh;
+        p.lay = ctx->cia_lay.as<CiaLayer>();
+        k.lay = p.lay;
+        hipLaunchKernelGGL(k_cia_rows_prep, dim3(nblk((size_t)rows, 64)), dim3(64), 0, ctx->stream, p);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tau_cont_rows, dim3((unsigned)rows, nblk((size_t)Wpad, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    return ANSFM_OK;
+}
+
 extern "C" {
 
 /* ------------------------------------------------------------------------------------------ */
@@ -277,41 +310,9 @@ int ansfm_calc_tau_cia(ansfm_ctx *ctx, int W, const double *WAVEN, int NWC, cons
     // para-fraction clamp (:4623)
     std::vector<CiaLayer> lay(L);
     for (int l = 0; l < L; ++l) {
-        double temp1 = lay_temp[l];
-        int it = 0;
-        for (int k = 1; k < NT; ++k) if (fabs(cia_temp[k] - temp1) < fabs(cia_temp[it] - temp1)) it = k;
-        int itl, ithi;
-        if (cia_temp[it] >= temp1) {
-            ithi = it;
-            if (it == 0) { temp1 = cia_temp[0]; itl = 0; ithi = 1; } else itl = it - 1;
-        } else {
-            itl = it;
-            if (it == NT - 1) { temp1 = cia_temp[it]; ithi = NT - 1; itl = NT - 2; } else ithi = it + 1;
-        }
-        double frac1 = lay_frac[l];
-        int ip = 0;
-        for (int k = 1; k < nfrac; ++k) if (fabs(cia_frac[k] - frac1) < fabs(cia_frac[ip] - frac1)) ip = k;
-        int ipl, iphi;
-        if (cia_frac[ip] >= frac1) {
-            iphi = ip;
-            if (ip == 0) { frac1 = cia_frac[0]; ipl = 0; iphi = 1; } else ipl = ip - 1;
-        } else {
-            ipl = ip;
-            if (ip == NPARA - 1) { temp1 = cia_frac[ip]; iphi = NPARA - 1; ipl = NPARA - 2; } else iphi = ip + 1;
-        }
-        if (NPARA == 0) { ipl = 0; iphi = 0; }
-        if (ipl < 0 || iphi < 0 || ipl >= NPE || iphi >= NPE || (nfrac > 1 && iphi >= nfrac))
+        const CiaLayer c = cia_layer(lay_temp[l], lay_frac[l], xfac[l], NT, cia_temp, nfrac, cia_frac, NPARA);
+        if (c.ipl < 0 || c.iphi < 0 || c.ipl >= NPE || c.iphi >= NPE || (nfrac > 1 && c.iphi >= nfrac))
             FAIL(ANSFM_ERR_INVALID, "calc_tau_cia: para-H2 bracket outside K_CIA (the reference raises IndexError here)");
-        CiaLayer c;
-        c.itl = itl; c.ithi = ithi; c.ipl = ipl; c.iphi = iphi;
-        c.fhl_t = (temp1 - cia_temp[itl]) / (cia_temp[ithi] - cia_temp[itl]);
-        c.fhh_t = (cia_temp[ithi] - temp1) / (cia_temp[ithi] - cia_temp[itl]);
-        c.dfhldT = 1.0 / (cia_temp[ithi] - cia_temp[itl]);
-        if (nfrac > 1) {
-            c.fhl_f = (frac1 - cia_frac[ipl]) / (cia_frac[iphi] - cia_frac[ipl]);
-            c.fhh_f = (cia_frac[iphi] - frac1) / (cia_frac[iphi] - cia_frac[ipl]);
-        } else { c.fhl_f = 0.5; c.fhh_f = 0.5; }
-        c.xfac = xfac[l];
         lay[l] = c;
     }
     HIPCHK(hipSetDevice(ctx->device));
@@ -492,6 +493,117 @@ int ansfm_calc_tau_dust(ansfm_ctx *ctx, int W, const double *WAVEC, int NWS, con
     HIPCHK(hipMemcpyAsync(dTAUDUSTdq, p.dtaudust, nt * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(dTAUCLSCATdq, p.dtauclscat, nt * D, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* continuum sources resident in the context, on the uploaded table's grid                     */
+/* ------------------------------------------------------------------------------------------ */
+int ansfm_upload_cia(ansfm_ctx *ctx, int ISPACE, int NWC, const double *cia_waven, int NPAIR, int NPE, int NT, const double *K_CIA,
+                     const double *cia_temp, int nfrac, const double *cia_frac, int NPARA, const int32_t *igas1,
+                     const int32_t *igas2, int NVMR, int ico2, const double *k_co2, int in2, const double *k_n2n2, int ih2,
+                     const double *k_n2h2)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "upload_cia: upload a table first (the source lives on its wavenumber grid)");
+    if ((ISPACE != 0 && ISPACE != 1) || NWC < 2 || NPAIR < 0 || NPE < 1 || NT < 2 || nfrac < 1 || NPARA < 0 || NVMR < 2 ||
+        !cia_waven || !K_CIA || !cia_temp || !cia_frac || (NPAIR > 0 && (!igas1 || !igas2)) || (ico2 >= 0 && !k_co2) ||
+        (in2 >= 0 && !k_n2n2) || (in2 >= 0 && ih2 >= 0 && !k_n2h2) || ico2 >= NVMR || in2 >= NVMR || ih2 >= NVMR)
+        FAIL(ANSFM_ERR_INVALID, "upload_cia: bad argument");
+    for (int i = 0; i < NPAIR; ++i)
+        if (igas1[i] >= NVMR || igas2[i] >= NVMR) FAIL(ANSFM_ERR_INVALID, "upload_cia: pair gas index outside the atmosphere");
+    // a layer's para-H2 bracket must stay inside K_CIA whatever its fraction is: the per-layer IndexError of ansfm_calc_tau_cia
+    // then cannot arise on the device
+    if (NPARA > 0 && !(NPARA == nfrac && nfrac == NPE && NPE >= 2))
+        FAIL(ANSFM_ERR_UNSUPPORTED, "upload_cia: a para-H2 table needs NPARA == len(FRAC) == K_CIA.shape[1] >= 2 (use ansfm_calc_tau_cia)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int W = ctx->W;
+    // the table is evaluated at x = WAVE (ISPACE 0) or 1e4 / WAVE (ISPACE 1, :4565); covers (:4671) on the range of that x
+    double xmin = ctx->h_wave[0], xmax = ctx->h_wave[0];
+    for (int w = 0; w < W; ++w) {
+        const double x = ISPACE == 0 ? ctx->h_wave[w] : 1.e4 / ctx->h_wave[w];
+        if (w == 0) { xmin = xmax = x; } else { xmin = std::min(xmin, x); xmax = std::max(xmax, x); }
+    }
+    double cmin = cia_waven[0], cmax = cia_waven[0];
+    for (int i = 1; i < NWC; ++i) { cmin = std::min(cmin, cia_waven[i]); cmax = std::max(cmax, cia_waven[i]); }
+    const size_t nK = (size_t)NPAIR * NPE * NT * NWC, D = sizeof(double);
+    const size_t total = (size_t)NWC + nK + NT + nfrac + 3 * (size_t)W;
+    ctx->cia_on = 0;
+    HIPCHK(ctx->cia_tab.reserve(total * D));
+    HIPCHK(ctx->cia_idx.reserve(std::max<size_t>(1, 2 * (size_t)NPAIR) * sizeof(int32_t)));
+    double *d = ctx->cia_tab.as<double>();
+    auto put = [&](const double *src, size_t count, bool have) -> hipError_t {
+        hipError_t e = have ? hipMemcpyAsync(d, src, count * D, hipMemcpyHostToDevice, ctx->stream)
+                            : hipMemsetAsync(d, 0, count * D, ctx->stream);
+        d += count;
+        return e;
+    };
+    HIPCHK(put(cia_waven, NWC, true)); HIPCHK(put(K_CIA, nK, nK > 0)); HIPCHK(put(cia_temp, NT, true));
+    HIPCHK(put(cia_frac, nfrac, true));
+    HIPCHK(put(k_co2, W, ico2 >= 0)); HIPCHK(put(k_n2n2, W, in2 >= 0)); HIPCHK(put(k_n2h2, W, in2 >= 0 && ih2 >= 0));
+    if (NPAIR > 0) {
+        HIPCHK(hipMemcpyAsync(ctx->cia_idx.p, igas1, NPAIR * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->cia_idx.as<int32_t>() + NPAIR, igas2, NPAIR * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));                     // the caller's arrays are free again
+    ctx->cia_ispace = ISPACE; ctx->cia_NWC = NWC; ctx->cia_NPAIR = NPAIR; ctx->cia_NPE = NPE; ctx->cia_NT = NT;
+    ctx->cia_nfrac = nfrac; ctx->cia_NPARA = NPARA; ctx->cia_NVMR = NVMR; ctx->cia_ico2 = ico2; ctx->cia_in2 = in2; ctx->cia_ih2 = ih2;
+    ctx->cia_covers = (cmin <= xmin && cmax >= xmax) ? 1 : 0;
+    ctx->cia_on = 1;
+    return ANSFM_OK;
+}
+
+int ansfm_upload_dust(ansfm_ctx *ctx, int NWS, const double *SWAVE, int NDUST, const double *KEXT, const double *KSCA)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "upload_dust: upload a table first (the source lives on its wavenumber grid)");
+    if (NWS < 2 || NDUST <= 0 || !SWAVE || !KEXT) FAIL(ANSFM_ERR_INVALID, "upload_dust: bad argument");
+    if (NDUST > 7)
+        FAIL(ANSFM_ERR_UNSUPPORTED, "upload_dust: more than 7 aerosol populations (NumPy sums 8 and more pairwise; use ansfm_calc_tau_dust)");
+    if (NWS == 3) FAIL(ANSFM_ERR_UNSUPPORTED, "upload_dust: three tabulated wavelengths (scipy's cubic interp1d refuses them too)");
+    for (int i = 1; i < NWS; ++i)
+        if (!(SWAVE[i] > SWAVE[i - 1])) FAIL(ANSFM_ERR_UNSORTED, "upload_dust: Scatter.WAVE must be strictly ascending");
+    const int W = ctx->W, Wpad = ctx->Wpad;
+    for (int w = 0; w < W; ++w)      // interp1d(bounds_error=True)
+        if (!(ctx->h_wave[w] >= SWAVE[0] && ctx->h_wave[w] <= SWAVE[NWS - 1]))
+            FAIL(ANSFM_ERR_INVALID, "upload_dust: a wavenumber of the table is outside the range of the aerosol properties");
+    HIPCHK(hipSetDevice(ctx->device));
+    // the scattering cross sections decide where the linear interpolant replaces the spline (:4849-4851); without them: zeros
+    const size_t nk = (size_t)NWS * NDUST;
+    std::vector<double> zeros;
+    if (!KSCA) { zeros.assign(nk, 0.0); KSCA = zeros.data(); }
+    const int cubic = NWS > 2;
+    std::vector<double> coef;
+    if (cubic) {
+        coef.resize((size_t)2 * NDUST * (NWS - 1) * 3);
+        for (int i = 0; i < NDUST; ++i) {
+            notaknot_coeffs(NWS, SWAVE, KEXT + i, NDUST, coef.data() + (size_t)i * (NWS - 1) * 3);
+            notaknot_coeffs(NWS, SWAVE, KSCA + i, NDUST, coef.data() + ((size_t)NDUST + i) * (NWS - 1) * 3);
+        }
+    }
+    ctx->dust_n = 0;
+    DustParams p;
+    memset(&p, 0, sizeof p);
+    Stager st{ctx};
+    p.swave = st.up(SWAVE, NWS); p.kext = st.up(KEXT, nk); p.ksca = st.up(KSCA, nk);
+    p.cext = st.up(cubic ? coef.data() : nullptr, coef.size());
+    if (st.rc) return st.rc;
+    p.csca = p.cext ? p.cext + (size_t)NDUST * (NWS - 1) * 3 : nullptr;
+    p.wavec = ctx->d_wave.as<double>();
+    p.W = W; p.NWS = NWS; p.NDUST = NDUST; p.cubic = cubic;
+    HIPCHK(ctx->dust_kext.reserve((size_t)NDUST * Wpad * sizeof(double)));
+    hipLaunchKernelGGL(k_dust_kext_grid, dim3(nblk((size_t)Wpad, 128), (unsigned)NDUST), dim3(128), 0, ctx->stream, p, Wpad,
+                       ctx->dust_kext.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));                     // the coefficients are host temporaries
+    ctx->dust_n = NDUST;
+    return ANSFM_OK;
+}
+
+int ansfm_clear_continuum_sources(ansfm_ctx *ctx)
+{
+    CHECK_CTX(ctx);
+    clear_continuum_sources(ctx);
     return ANSFM_OK;
 }
 

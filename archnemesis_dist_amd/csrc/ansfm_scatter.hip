@@ -837,7 +837,7 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     if (!by_rows && (rc = ms_zero_tauray(ctx, (size_t)W * L, &d_tauray))) return rc;     // (by rows: the optics stage writes the slab's copy)
     // vertical gas opacities of the distinct (model, layer) rows: calc_k + k_overlap
     DedupRows k;
-    if ((rc = dedup_rows(ctx, n_models, L, s.press, s.temp, s.am, nullptr, nullptr, &k)) ||
+    if ((rc = dedup_rows(ctx, n_models, L, s.press, s.temp, s.am, nullptr, &k)) ||
         (rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount)))
         return rc;
     ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = k.rows; ctx->last_dedup = 1;

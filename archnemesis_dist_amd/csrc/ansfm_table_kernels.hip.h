@@ -212,12 +212,21 @@ __global__ void k_kta_relayout(const float *__restrict__ kf, double *__restrict_
 // so that the merge kernel sees them as the layers of one pseudo-model; k_thermal_rt follows tau_slot.
 // Nothing is approximated: a layer is shared only when all of its S+2 inputs are equal to the last bit.
 // ------------------------------------------------------------------------------------------------
-// x1 [n][L], x4 [n][L][4] (or nullptr): further per-layer inputs that are part of a row's identity (the column and the
-// composition the Rayleigh continuum of a row is formed from, ansfm_cirsrad_ck_thermal_ray_dev).
+// DedupCols: further per-layer inputs that are part of a row's identity, each an array [n][L][width] -- what the continuum of
+// a row is formed from inside the call (ansfm_cirsrad_ck_thermal_ray_dev: the column and the Rayleigh composition;
+// ansfm_cirsrad_ck_thermal_cont_dev: also the mixing ratios, para-H2 fraction and thickness behind the CIA term and the
+// aerosol columns).  A state that perturbs He changes no spectroscopic amount, yet it changes CIA.
+constexpr int kDedupCols = 8;
+struct DedupCols {
+    const double *p[kDedupCols];
+    int width[kDedupCols];
+    int n = 0;
+    void add(const double *x, int w) { if (x && w > 0 && n < kDedupCols) { p[n] = x; width[n] = w; ++n; } }
+};
+
 __global__ void k_dedup_mark(int n_models, int L, int S, const double *__restrict__ press,
                              const double *__restrict__ temp, const double *__restrict__ amount,
-                             int32_t *__restrict__ slot, int32_t *__restrict__ work, int *__restrict__ counter,
-                             const double *__restrict__ x1 = nullptr, const double *__restrict__ x4 = nullptr)
+                             int32_t *__restrict__ slot, int32_t *__restrict__ work, int *__restrict__ counter, DedupCols extra)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_models * L) return;
@@ -225,9 +234,13 @@ __global__ void k_dedup_mark(int n_models, int L, int S, const double *__restric
     if (m == 0) { slot[i] = l; work[l] = i; return; }
     auto bits = [](double x) { return __double_as_longlong(x); };
     bool same = bits(press[i]) == bits(press[l]) && bits(temp[i]) == bits(temp[l]);
-    if (same && x1) same = bits(x1[i]) == bits(x1[l]);
-    if (same && x4)
-        for (int c = 0; c < 4 && same; ++c) same = bits(x4[(size_t)i * 4 + c]) == bits(x4[(size_t)l * 4 + c]);
+#pragma unroll
+    for (int k = 0; k < kDedupCols; ++k) {        // unrolled: the list stays in the kernel's arguments
+        if (k >= extra.n || !same) break;
+        const int wd = extra.width[k];
+        const double *a = extra.p[k] + (size_t)i * wd, *b = extra.p[k] + (size_t)l * wd;
+        for (int c = 0; c < wd && same; ++c) same = bits(a[c]) == bits(b[c]);
+    }
     for (int s = 0; s < S && same; ++s)
         same = bits(amount[((size_t)m * S + s) * L + l]) == bits(amount[(size_t)s * L + l]);
     if (same) { slot[i] = l; return; }

@@ -781,6 +781,27 @@ class AnsfmEngine:
             _ptr(SOLFLUX), _ptr(REFLECTANCE), _ptr(SOL_ANG), _ptr(EMISS_ANG), _ptr(xfac), _ptr(SPECOUT))
         self._check(rc, "cirsrad_ck_thermal_ray_dev")
 
+    def cirsrad_ck_thermal_cont_dev(self, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY,
+                                    f4, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE,
+                                    SOL_ANG, EMISS_ANG, xfac, SPECOUT, variant=None):
+        """cirsrad_ck_thermal_dev for a batch whose continuum is (TAUCIA + TAUDUST) + TAURAY from the resident sources
+        (upload_cia, upload_dust), formed per distinct layer inside the call.  Contiguous float64 device tensors: q (n, L,
+        NVMR) = PP / PRESS with FRAC, DELH (n, L) switch CIA on (None: off); CONT (n, L, NDUST) after any
+        DUST_RENORMALISATION switches the aerosols on (None: off); IRAY 0 or as in cirsrad_ck_thermal_ray_dev with f4 (n,
+        L, 4); TOTAM (n, L) for CIA and Rayleigh."""
+        mode = 12 if variant == "v" else int(IRAY)
+        use_cia, use_dust = q is not None, CONT is not None
+        for a, shape in ((q, (n_models, L, getattr(self, "cia_nvmr", -1))), (FRAC, (n_models, L)), (TOTAM, (n_models, L)),
+                         (DELH, (n_models, L)), (CONT, (n_models, L, getattr(self, "dust_n", -1))), (f4, (n_models, L, 4))):
+            if a is not None and -1 not in shape and (tuple(a.shape) != shape or not a.is_contiguous()):
+                raise ValueError("cirsrad_ck_thermal_cont_dev: expected a contiguous tensor of shape %s, got %s" % (shape, tuple(a.shape)))
+        rc = self._lib.ansfm_cirsrad_ck_thermal_cont_dev(
+            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), int(use_cia), _ptr(q),
+            _ptr(FRAC), _ptr(TOTAM), _ptr(DELH), int(use_dust), _ptr(CONT), mode, _ptr(f4), int(P), int(LIMAX), _ptr(NLAYIN),
+            _ptr(LAYINC), _ptr(SCALE), _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY), _ptr(SOLFLUX), _ptr(REFLECTANCE), _ptr(SOL_ANG),
+            _ptr(EMISS_ANG), _ptr(xfac), _ptr(SPECOUT))
+        self._check(rc, "cirsrad_ck_thermal_cont_dev")
+
     @staticmethod
     def rayleigh_f4(ID, ISO, VMR):
         """calc_tau_rayleighls' composition (:5748-5767): VMR (..., NVMR) numpy array or torch tensor -> (..., 4) mixing
@@ -1266,18 +1287,7 @@ class AnsfmEngine:
         else:                                              # :4565-4568
             WAVEN = 1.e4 / WAVEC; isort = np.argsort(WAVEN); WAVEN = _np(WAVEN[isort])
         K = _np(K_CIA); NPAIR, NPE, NT, NWC = K.shape
-        g1 = np.full(NPAIR, -1, np.int32); g2 = np.full(NPAIR, -1, np.int32)
-        for ip in range(NPAIR):                            # :4676-4701
-            a = np.where(ID == int(IPAIRG1[ip]))[0]; b = np.where(ID == int(IPAIRG2[ip]))[0]
-            if len(a) > 1: a = np.where((ID == int(IPAIRG1[ip])) & (ISO == 1))[0]
-            if len(b) > 1: b = np.where((ID == int(IPAIRG2[ip])) & (ISO == 1))[0]
-            if len(a) == 1 and len(b) == 1 and not (INORMALD[ip] and int(INORMALT[ip]) != int(INORMAL)):
-                g1[ip], g2[ip] = a[0], b[0]
-        ico2 = ih2 = in2 = -1                              # :4545-4561
-        for i in range(NVMR):
-            if ID[i] == 39 and ISO[i] in (0, 1): ih2 = i
-            if ID[i] == 22: in2 = i
-            if ID[i] == 2 and ISO[i] in (0, 1): ico2 = i
+        g1, g2, ico2, in2, ih2 = self._cia_gases(NPAIR, IPAIRG1, IPAIRG2, INORMALT, INORMAL, INORMALD, ID, ISO)
         q = _np((_np(PP).T / _np(PRESS)).T)
         L = q.shape[0]
         xfac = _np((_np(TOTAM) * 1.0e-4) ** 2. / (_np(DELH) * 1.0e2))
@@ -1293,6 +1303,63 @@ class AnsfmEngine:
             tau = tau[isort, :]
             dtau = None if dtau is None else dtau[isort, :, :]
         return (tau, dtau) if with_grad else tau
+
+    @staticmethod
+    def _cia_gases(NPAIR, IPAIRG1, IPAIRG2, INORMALT, INORMAL, INORMALD, ID, ISO):
+        """What calc_tau_cia resolves on the host before any layer: the atmospheric gas of each partner of every pair (-1:
+        pair not used) and the indices of CO2, N2 and H2 (-1: absent)."""
+        g1 = np.full(NPAIR, -1, np.int32); g2 = np.full(NPAIR, -1, np.int32)
+        for ip in range(NPAIR):                            # :4676-4701
+            a = np.where(ID == int(IPAIRG1[ip]))[0]; b = np.where(ID == int(IPAIRG2[ip]))[0]
+            if len(a) > 1: a = np.where((ID == int(IPAIRG1[ip])) & (ISO == 1))[0]
+            if len(b) > 1: b = np.where((ID == int(IPAIRG2[ip])) & (ISO == 1))[0]
+            if len(a) == 1 and len(b) == 1 and not (INORMALD[ip] and int(INORMALT[ip]) != int(INORMAL)):
+                g1[ip], g2[ip] = a[0], b[0]
+        ico2 = ih2 = in2 = -1                              # :4545-4561
+        for i in range(ID.size):
+            if ID[i] == 39 and ISO[i] in (0, 1): ih2 = i
+            if ID[i] == 22: in2 = i
+            if ID[i] == 2 and ISO[i] in (0, 1): ico2 = i
+        return g1, g2, ico2, in2, ih2
+
+    def upload_cia(self, ISPACE, WAVEC, CIA_WAVEN, CIA_TEMP, CIA_FRAC, NPARA, K_CIA, IPAIRG1, IPAIRG2, INORMALT, INORMAL,
+                   INORMALD, ID, ISO, k_co2=None, k_n2n2=None, k_n2h2=None):
+        """Make the CIA table a resident opacity source of the context, on the uploaded table's grid, for
+        cirsrad_ck_thermal_cont_dev: the arguments of calc_tau_cia up to ISO (WAVEC: None or the table's grid, checked) and
+        co2cia / n2n2cia / n2h2cia at x = WAVE (ISPACE 0) or 1e4 / WAVE (ISPACE 1), in the order of the table's grid.
+        NotImplementedError for a para-H2 table whose bracket could leave K_CIA (NPARA > 0 without NPARA == len(FRAC) ==
+        K_CIA.shape[1] >= 2).  A new table clears the source."""
+        ID = np.asarray(ID); ISO = np.asarray(ISO)
+        if WAVEC is not None:
+            (W, G, NP, NT, _), _ = self.ktable_info()
+            WAVE = np.empty(W)
+            self._check(self._lib.ansfm_ktable_grids(self._ctx, _ptr(WAVE), _ptr(np.empty(NP)), _ptr(np.empty(NT)), _ptr(np.empty(G))),
+                        "ktable_grids")
+            if not np.array_equal(_np(WAVEC).reshape(-1), WAVE):
+                raise ValueError("upload_cia: WAVEC is not the grid of the uploaded table")
+        K = _np(K_CIA); NPAIR, NPE, NT, NWC = K.shape
+        g1, g2, ico2, in2, ih2 = self._cia_gases(NPAIR, IPAIRG1, IPAIRG2, INORMALT, INORMAL, INORMALD, ID, ISO)
+        frac = _np(np.asarray(CIA_FRAC, float).reshape(-1))
+        rc = self._lib.ansfm_upload_cia(self._ctx, int(ISPACE), NWC, _ptr(_np(CIA_WAVEN)), NPAIR, NPE, NT, _ptr(K), _ptr(_np(CIA_TEMP)),
+                                        frac.size, _ptr(frac), int(NPARA), _ptr(g1), _ptr(g2), ID.size, ico2, _ptr(_np(k_co2)), in2,
+                                        _ptr(_np(k_n2n2)), ih2, _ptr(_np(k_n2h2)))
+        self._check(rc, "upload_cia")
+        self.cia_nvmr = int(ID.size)
+
+    def upload_dust(self, SWAVE, KEXT, KSCA=None):
+        """Make the aerosol extinction a resident opacity source of the context: KEXT (NWAVE_scatter, NDUST) on SWAVE is
+        evaluated on the uploaded table's grid as calc_tau_dust evaluates it (KSCA decides with KEXT where the linear
+        interpolant replaces the spline; None: zeros).  NotImplementedError for more than 7 populations.  A new table clears
+        the source."""
+        SWAVE = _np(SWAVE); KEXT = _np(KEXT); KSCA = _np(KSCA)
+        if KEXT.ndim != 2 or KEXT.shape[0] != SWAVE.size or (KSCA is not None and KSCA.shape != KEXT.shape):
+            raise ValueError("KEXT / KSCA must be (len(Scatter.WAVE), NDUST)")
+        rc = self._lib.ansfm_upload_dust(self._ctx, SWAVE.size, _ptr(SWAVE), KEXT.shape[1], _ptr(KEXT), _ptr(KSCA))
+        self._check(rc, "upload_dust")
+        self.dust_n = int(KEXT.shape[1])
+
+    def clear_continuum_sources(self):
+        self._check(self._lib.ansfm_clear_continuum_sources(self._ctx), "clear_continuum_sources")
 
     def calc_tau_rayleigh(self, IRAY, ISPACE, WAVEC, TOTAM, ID=None, ISO=None, VMR=None, variant=None):
         """ForwardModel_0.calc_tau_rayleigh (:4869): IRAY 0 -> zeros, 1 -> calc_tau_rayleighj, 2 -> calc_tau_rayleighv2,

@@ -11,8 +11,11 @@ returns an object that does for n state vectors at once what `nemesisfm` (Forwar
                                element is carried as a logarithm)                                   host, O(n NP)
     calc_path (:2948-3065)     layer_split per state (the grid follows the heights), ONE k_layer_average launch for all
                                states, AtmCalc_0's ray geometry per state                           layering.py + GPU
-    calculate_layer_opacity    Rayleigh for all states in HBM; CIA and aerosol opacities through the engine's kernels
-                               with the layers of all states laid end to end (layers are independent there)
+    calculate_layer_opacity    CIA and aerosols are resident sources of the engine (upload_cia / upload_dust, once per
+                               geometry) and, with Rayleigh, formed inside the CIRSrad call per distinct layer; an engine
+                               without cirsrad_ck_thermal_cont_dev, a CIA table upload_cia refuses or more than 7 aerosol
+                               populations: Rayleigh for all states in HBM, CIA and aerosol opacities through the engine's
+                               kernels with the layers of all states laid end to end (layers are independent there)
     CIRSrad (:4376)            ONE batched call, layers equal to the unperturbed state's not recomputed
     conv (:2288)               FWHM = 0: linear interpolation onto VCONV on the device; otherwise Measurement.conv per state
     NGEOM / NAV                one pass per (geometry, averaging point), packed into NY like execute_fm (:2171-2174)
@@ -178,6 +181,7 @@ class ReferenceProfileBatch:
         self._lay = dict(RADIUS=float(L.RADIUS), NLAY=int(L.NLAY), LAYTYP=int(L.LAYTYP), LAYINT=int(L.LAYINT), NINT=int(L.NINT),
                          LAYHT=float(L.LAYHT), H_base=getattr(L, "H_base", None), P_base=getattr(L, "P_base", None))
         self._pending = None
+        self._fused = None          # dict(cia, dust): the continuum sources resident in the engine for the current geometry
 
     # ---- subprofretg for n states -----------------------------------------------------------------------------------
     def profiles(self, X):
@@ -247,7 +251,8 @@ class ReferenceProfileBatch:
         td = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
         W = WAVE.size
         ISPACE = int(fm.Measurement.ISPACE)
-        cont = self._continuum(lay, n, L, WAVE, ISPACE, dev)
+        fused = self._fused is not None and (self._fused["cia"] or self._fused["dust"])
+        cont = None if fused else self._continuum(lay, n, L, WAVE, ISPACE, dev)
         emis = None
         if Su.TSURF > 0.0:
             import scipy.interpolate
@@ -255,13 +260,65 @@ class ReferenceProfileBatch:
         outt = torch.empty((n, W, 1), dtype=torch.float64, device=dev)
         args = (td(lay["PRESS"]), td(lay["TEMP"]), td(amount), cont, 1, p0.LAYINC.shape[0], td(p0.NLAYIN, torch.int32),
                 td(p0.LAYINC, torch.int32), td(SCALE), td(EMTEMP), td(np.full(n, float(Su.TSURF))))
-        if dev.type == "cuda":
-            torch.cuda.current_stream(dev).synchronize()
-        eng.cirsrad_ck_thermal_dev(ISPACE, n, L, *args, emis, None, None, None, None, None, outt)
+        if fused:
+            # the per-state layer arrays the resident sources are evaluated with, inside the call and per distinct layer
+            cia, dust = self._fused["cia"], self._fused["dust"]
+            IRAY = int(Sc.IRAY)
+            VMRLAY = lay["PP"] / lay["PRESS"][:, :, None]
+            f4 = td(eng.rayleigh_f4(A.ID, A.ISO, VMRLAY)) if IRAY == 4 else None
+            cargs = (td(VMRLAY) if cia else None, td(lay["FRAC"]) if cia else None, td(lay["TOTAM"]),
+                     td(lay["DELH"]) if cia else None, td(self._renormalised_cont(lay)) if dust else None, IRAY, f4)
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+            eng.cirsrad_ck_thermal_cont_dev(ISPACE, n, L, *args[:3], *cargs, *args[4:], emis, None, None, None, None, None, outt)
+        else:
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()
+            eng.cirsrad_ck_thermal_dev(ISPACE, n, L, *args, emis, None, None, None, None, None, outt)
         a, b = eng.last_layer_rows()
         self.last_rows = (self.last_rows[0] + a, self.last_rows[1] + b)
         eng.synchronize()
         return outt.reshape(n, W)
+
+    def _renormalised_cont(self, lay):
+        """Layer.CONT of every state after calc_tau_dust's renormalisation (:4833), (n, NLAY, NDUST)"""
+        A, ND = self.fm.Atmosphere, int(self.fm.Scatter.NDUST)
+        CONT = np.array(lay["CONT"][:, :, :ND], float)
+        for i in range(ND):
+            if i in A.DUST_RENORMALISATION.keys():
+                CONT[:, :, i] = CONT[:, :, i] / CONT[:, :, i].sum(axis=1, keepdims=True) * 1e4 * A.DUST_RENORMALISATION[i]
+        return CONT
+
+    def _upload_sources(self, WAVE, ISPACE):
+        """CIA and aerosols as resident sources of the engine on the grid just uploaded -> dict(cia, dust) of what the fused
+        entry is to use, or None: today's route (an engine without the entry, a source the engine refuses, or neither)."""
+        import importlib
+        fm, eng = self.fm, self.eng
+        A, Sc, CIA = fm.Atmosphere, fm.Scatter, fm.CIA
+        if not hasattr(eng, "cirsrad_ck_thermal_cont_dev"):
+            return None
+        ND = int(Sc.NDUST)
+        if CIA is None and ND == 0:
+            return None
+        try:
+            if CIA is not None:
+                ID = np.asarray(A.ID)
+                has = lambda gid: np.any(ID == gid)
+                k = dict(k_co2=None, k_n2n2=None, k_n2h2=None)
+                if has(2) or has(22):
+                    cm = importlib.import_module("archnemesis.CIA_0")
+                    x = WAVE if ISPACE == 0 else 1.e4 / WAVE             # pointwise parametrisations, in the grid's order
+                    k = dict(k_co2=cm.co2cia(x) if has(2) else None, k_n2n2=cm.n2n2cia(x) if has(22) else None,
+                             k_n2h2=cm.n2h2cia(x) if (has(22) and has(39)) else None)
+                eng.upload_cia(ISPACE, WAVE, CIA.WAVEN, CIA.TEMP, CIA.FRAC, int(CIA.NPARA), CIA.K_CIA, [int(g) for g in CIA.IPAIRG1],
+                               [int(g) for g in CIA.IPAIRG2], [int(g) for g in CIA.INORMALT], int(CIA.INORMAL),
+                               CIA.locate_INORMAL_pairs(), ID, np.asarray(A.ISO), **k)
+            if ND > 0:
+                eng.upload_dust(Sc.WAVE, np.asarray(Sc.KEXT)[:, :ND], np.asarray(Sc.KSCA)[:, :ND])
+        except NotImplementedError:
+            eng.clear_continuum_sources()
+            return None
+        return dict(cia=CIA is not None, dust=ND > 0)
 
     def _continuum(self, lay, n, L, WAVE, ISPACE, dev):
         """TAUCIA + TAUDUST + TAURAY of every state, (n, NWAVE, NLAY) on the device (the sum order of :3989 per element)."""
@@ -273,10 +330,10 @@ class ReferenceProfileBatch:
         flat = lambda a: np.ascontiguousarray(a).reshape((n * L,) + a.shape[2:])
         parts = []
         if CIA is not None:
-            cm = importlib.import_module("archnemesis.CIA_0")
             WAVEN = WAVE if ISPACE == 0 else np.sort(1.e4 / WAVE)
             ID = np.asarray(A.ID)
             has = lambda gid: np.any(ID == gid)
+            cm = importlib.import_module("archnemesis.CIA_0") if (has(2) or has(22)) else None     # CO2 / N2 parametrisations
             tau = eng.calc_tau_cia(ISPACE, WAVE, CIA.WAVEN, CIA.TEMP, CIA.FRAC, int(CIA.NPARA), CIA.K_CIA, [int(g) for g in CIA.IPAIRG1],
                                    [int(g) for g in CIA.IPAIRG2], [int(g) for g in CIA.INORMALT], int(CIA.INORMAL),
                                    CIA.locate_INORMAL_pairs(), ID, np.asarray(A.ISO), flat(lay["PP"]), flat(lay["PRESS"]),
@@ -286,10 +343,7 @@ class ReferenceProfileBatch:
             parts.append(np.asarray(tau).reshape(W, n, L))
         if int(Sc.NDUST) > 0:
             ND = int(Sc.NDUST)
-            CONT = np.array(lay["CONT"][:, :, :ND], float)
-            for i in range(ND):                                      # calc_tau_dust's renormalisation of Layer.CONT (:4833)
-                if i in A.DUST_RENORMALISATION.keys():
-                    CONT[:, :, i] = CONT[:, :, i] / CONT[:, :, i].sum(axis=1, keepdims=True) * 1e4 * A.DUST_RENORMALISATION[i]
+            CONT = self._renormalised_cont(lay)
             td1 = eng.calc_tau_dust(WAVE, Sc.WAVE, np.asarray(Sc.KEXT)[:, :ND], np.asarray(Sc.KSCA)[:, :ND], flat(CONT))[0]
             td1 = np.clip(np.nan_to_num(td1), 0, 1e20)               # :3966
             parts.append(np.sum(td1, 2).reshape(W, n, L))
@@ -327,6 +381,7 @@ class ReferenceProfileBatch:
             fm.SpectroscopyX.read_tables(wavemin=wmin, wavemax=wmax)
             fm._ansfm_upload_table(self.eng)
             WAVE = np.asarray(fm.SpectroscopyX.WAVE, dtype=np.float64)
+            self._fused = self._upload_sources(WAVE, int(M.ISPACE))
             spec = None
             for IAV in range(int(M.NAV[IGEOM])):
                 s = self._spectra(H, T, VMR, IGEOM, IAV, WAVE) * float(M.WGEOM[IGEOM, IAV])      # :531

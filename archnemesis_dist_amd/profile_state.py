@@ -5,7 +5,8 @@ nemesisfm (the reference fans them out to joblib workers, :2305-2337).
 
     state vector  --subprofretg / model 0-->  T(level), VMR(level, gas)          host, a few kB per state
                   --calc_path: layer_average (Curtis-Godson) + ray geometry-->   k_layer_average (one launch, all states)
-                  --calculate_layer_opacity: Rayleigh continuum-->               k_tau_rayleigh, stays in HBM
+                  --calculate_layer_opacity: CIA + aerosol + Rayleigh continuum-->  k_tau_cont_rows / k_tau_rayleigh_rows inside
+                                                                                  the CIRSrad call, per distinct layer
                   --CIRSrad: calc_k + k_overlap + thermal emission-->            k_ck_overlap + k_thermal_rt, layers that
                                                                                   equal the first state's are not recomputed
 Supported here: ILBL = K_TABLES, thermal emission, nadir / limb rays through AtmCalc_0's geometry, continuous-profile
@@ -68,10 +69,17 @@ class BatchedCKThermalModel:
     spectroscopic gas of the table (AtmosphereX.locate_gas, ForwardModel_0.py:3860).
     layering: dict(NLAY, LAYTYP, LAYINT, LAYHT, LAYANG, NINT) of Layer_0; geometry: dict(pointing, BOTLAY, ANGLE,
     EMISS_ANG, IPZEN) of AtmCalc_0.  IRAY as in calc_tau_rayleigh (0 = none); extra_continuum (W, L) is added to every
-    state (e.g. a fixed aerosol opacity)."""
+    state (e.g. a fixed aerosol opacity).
+    cia: dict of the arguments of AnsfmEngine.upload_cia by name (CIA_WAVEN, CIA_TEMP, CIA_FRAC, NPARA, K_CIA, IPAIRG1,
+    IPAIRG2, INORMALT, INORMAL, INORMALD and, where the atmosphere has CO2 / N2, k_co2 / k_n2n2 / k_n2h2 on the table's grid;
+    ISPACE, ID and ISO are the model's): collision-induced absorption of every state from ITS layers -- a perturbation of T or
+    of a mixing ratio reaches the CIA term.  dust: dict(SWAVE, KEXT[, KSCA], DUST (NPRO, NDUST) the aerosol profiles): aerosol
+    extinction of every state.  With `fused_continuum` both are resident sources of the engine and the continuum is formed
+    inside the batched call once per distinct layer; the sources are uploaded at the first such call -- `upload_sources()`
+    again after another table has been uploaded."""
 
     def __init__(self, eng, state, RADIUS, ID, ISO, igas_map, layering_args=None, geometry=None, ISPACE=0, IRAY=0,
-                 TSURF=-1.0, extra_continuum=None, DUST=None, PARAH2=None):
+                 TSURF=-1.0, extra_continuum=None, DUST=None, PARAH2=None, cia=None, dust=None):
         self.eng, self.state = eng, state
         self.RADIUS = float(RADIUS)
         self.ID = np.asarray(ID); self.ISO = np.asarray(ISO)
@@ -84,7 +92,12 @@ class BatchedCKThermalModel:
         self.geo = ge
         self.ISPACE, self.IRAY, self.TSURF = int(ISPACE), int(IRAY), float(TSURF)
         self.extra = None if extra_continuum is None else np.asarray(extra_continuum, float)
+        self.cia = None if cia is None else dict(cia)
+        self.dust = None if dust is None else dict(dust)
+        if self.dust is not None and DUST is None:
+            DUST = self.dust["DUST"]
         self.DUST, self.PARAH2 = DUST, PARAH2
+        self._sources_on = False
         dims, _ = eng.ktable_info()
         self.W = int(dims[0])
         # the layer grid is a property of the pressure-height profile, which no supported variable changes
@@ -120,7 +133,13 @@ class BatchedCKThermalModel:
         T, VMR = st.profiles(X)
         n = T.shape[0]
         H = np.repeat(st.H[None], n, 0); P = np.repeat(st.P[None], n, 0)
-        out = self.eng.layer_average(self.RADIUS, H, P, T, self.ID, VMR, self.DUST, self.PARAH2, self.BASEH, self.BASEP,
+        # aerosol and para-H2 profiles without a state axis are every state's
+        DUST = self.DUST
+        if DUST is not None and np.ndim(DUST) == 2 and np.shape(DUST)[0] == st.NPRO and (self.dust is not None or n != st.NPRO):
+            DUST = np.repeat(np.asarray(DUST, float)[None], n, 0)
+        PARAH2 = (self.PARAH2 if self.PARAH2 is None or np.ndim(self.PARAH2) != 1
+                  else np.repeat(np.asarray(self.PARAH2, float)[None], n, 0))
+        out = self.eng.layer_average(self.RADIUS, H, P, T, self.ID, VMR, DUST, PARAH2, self.BASEH, self.BASEP,
                                      LAYANG=la["LAYANG"], LAYINT=la["LAYINT"], LAYHT=la["LAYHT"], NINT=la["NINT"])
         names = ("HEIGHT", "PRESS", "TEMP", "TOTAM", "AMOUNT", "PP", "CONT", "FRAC", "DELH", "BASET", "LAYSF")
         lay = dict(zip(names, out))
@@ -136,6 +155,51 @@ class BatchedCKThermalModel:
     # ---- the same with the layers left in HBM ----------------------------------------------------------------------
     device_layers = True      # False: `layers` (host arrays) feeds spectra_batch, as in rounds 1-2; same numbers bit for bit
     fused_rayleigh = True     # False: the Rayleigh continuum of all n * NLAY layers as an array of its own (same bits)
+    fused_continuum = True    # False: CIA / aerosol opacity of all n * NLAY layers by calc_tau_cia / calc_tau_dust, as a dense
+                              # taucont (same bits)
+
+    # ---- CIA and aerosols ------------------------------------------------------------------------------------------
+    def upload_sources(self):
+        """Make `cia` / `dust` resident sources of the engine, on the grid of the table it holds now."""
+        eng = self.eng
+        if self.cia is not None:
+            c = self.cia
+            eng.upload_cia(self.ISPACE, None, c["CIA_WAVEN"], c["CIA_TEMP"], c["CIA_FRAC"], c["NPARA"], c["K_CIA"], c["IPAIRG1"],
+                           c["IPAIRG2"], c["INORMALT"], c["INORMAL"], c["INORMALD"], self.ID, self.ISO, k_co2=c.get("k_co2"),
+                           k_n2n2=c.get("k_n2n2"), k_n2h2=c.get("k_n2h2"))
+        if self.dust is not None:
+            eng.upload_dust(self.dust["SWAVE"], self.dust["KEXT"], self.dust.get("KSCA"))
+        self._sources_on = True
+
+    def _dense_continuum(self, lay, n, L):
+        """TAUCIA + TAUDUST of all n * L layers by the engine's array-level kernels, host (n, W, L) or None: the route
+        `fused_continuum` replaces.  lay: host arrays PP, PRESS, TEMP, FRAC, TOTAM, DELH, CONT with the state axis first."""
+        eng, W = self.eng, self.W
+        flat = lambda a: np.ascontiguousarray(a).reshape((n * L,) + a.shape[2:])
+        parts = []
+        if self.cia is not None:
+            c = self.cia
+            k = {}
+            for name in ("k_co2", "k_n2n2", "k_n2h2"):            # calc_tau_cia takes them in its own (sorted) order
+                v = c.get(name)
+                k[name] = None if v is None else (np.asarray(v, float) if self.ISPACE == 0 else
+                                                  np.asarray(v, float)[np.argsort(1.e4 / eng.WAVE)])
+            tau = eng.calc_tau_cia(self.ISPACE, eng.WAVE, c["CIA_WAVEN"], c["CIA_TEMP"], c["CIA_FRAC"], c["NPARA"], c["K_CIA"],
+                                   c["IPAIRG1"], c["IPAIRG2"], c["INORMALT"], c["INORMAL"], c["INORMALD"], self.ID, self.ISO,
+                                   flat(lay["PP"]), flat(lay["PRESS"]), flat(lay["TEMP"]), flat(lay["FRAC"]), flat(lay["TOTAM"]),
+                                   flat(lay["DELH"]), with_grad=False, **k)
+            parts.append(np.asarray(tau).reshape(W, n, L))
+        if self.dust is not None:
+            d = self.dust
+            KEXT = np.asarray(d["KEXT"], float)
+            KSCA = np.zeros_like(KEXT) if d.get("KSCA") is None else d["KSCA"]
+            td1 = eng.calc_tau_dust(eng.WAVE, d["SWAVE"], KEXT, KSCA, flat(lay["CONT"]))[0]
+            td1 = np.clip(np.nan_to_num(td1), 0, 1e20)               # ForwardModel_0.py:3966
+            parts.append(np.sum(td1, 2).reshape(W, n, L))
+        if not parts:
+            return None
+        host = parts[0] if len(parts) == 1 else parts[0] + parts[1]   # TAUCIA + TAUDUST
+        return np.ascontiguousarray(np.transpose(host, (1, 0, 2)))
 
     def layers_dev(self, X, dev, order=lambda: None, drain=lambda: None):
         """`layers` without the round trip over PCIe: the profiles of the n states are put together on the device (the
@@ -153,7 +217,8 @@ class BatchedCKThermalModel:
         # meant to be edited in place), the layering, the geometry, the surface temperature
         key = (n, str(dev), id(st), float(st.H.sum()), float(st.P.sum()), float(st.T.sum()), float(st.VMR.sum()), self.TSURF,
                tuple(sorted((k, float(v)) for k, v in la.items())), tuple(sorted((k, float(v)) for k, v in ge.items())),
-               float(self.BASEH.sum()), tuple(int(i) for i in self.igas_map))
+               float(self.BASEH.sum()), tuple(int(i) for i in self.igas_map),
+               None if self.DUST is None else float(np.sum(self.DUST)), None if self.PARAH2 is None else float(np.sum(self.PARAH2)))
         c = getattr(self, "_dev_consts", None)
         if c is None or c["key"] != key:
             rep = lambda a: td(a)[None].expand((n,) + np.shape(a)).contiguous()
@@ -166,7 +231,9 @@ class BatchedCKThermalModel:
             c = dict(key=key, H=rep(st.H), P=rep(st.P), T0=rep(st.T), VMR0=td(st.VMR), BASEH=rep(self.BASEH), path=path,
                      LAYINC=td(path.LAYINC, torch.int64), inside=td(inside, torch.bool), igas=td(self.igas_map, torch.int64),
                      NLAYIN32=td(path.NLAYIN, torch.int32), LAYINC32=td(path.LAYINC, torch.int32),
-                     SCALE=rep(path.SCALE), TSURF=td(np.full(n, self.TSURF)))
+                     SCALE=rep(path.SCALE), TSURF=td(np.full(n, self.TSURF)),
+                     DUST=None if self.DUST is None else rep(np.asarray(self.DUST, float).reshape(st.NPRO, -1)),
+                     PARAH2=None if self.PARAH2 is None else rep(np.asarray(self.PARAH2, float)))
             self._dev_consts = c
         T, VMR = c["T0"], None
         for b, (kind, j) in enumerate(st.blocks):
@@ -180,10 +247,11 @@ class BatchedCKThermalModel:
         if VMR is None:
             VMR = c["VMR0"][None].repeat(n, 1, 1)
         order()
-        lay = self.eng.layer_average_dev(self.RADIUS, c["H"], c["P"], T, VMR, None, None, c["BASEH"], LAYANG=la["LAYANG"],
+        lay = self.eng.layer_average_dev(self.RADIUS, c["H"], c["P"], T, VMR, c["DUST"], c["PARAH2"], c["BASEH"], LAYANG=la["LAYANG"],
                                          LAYINT=la["LAYINT"], LAYHT=la["LAYHT"], NINT=la["NINT"])
         drain()
-        out = dict(PRESS=lay["PRESS"], TEMP=lay["TEMP"], TOTAM=lay["TOTAM"], path=c["path"], consts=c)
+        out = dict(PRESS=lay["PRESS"], TEMP=lay["TEMP"], TOTAM=lay["TOTAM"], path=c["path"], consts=c, PP=lay["PP"],
+                   FRAC=lay["FRAC"], DELH=lay["DELH"], CONT=lay["CONT"])
         out["amount"] = (lay["AMOUNT"][:, :, c["igas"]].transpose(1, 2) * SQ_CM_TO_SQ_METER).contiguous()
         out["VMRLAY"] = lay["PP"] / lay["PRESS"][:, :, None]
         out["EMTEMP"] = torch.where(c["inside"][None], lay["TEMP"][:, c["LAYINC"]], torch.zeros((), dtype=torch.float64, device=dev))
@@ -196,7 +264,8 @@ class BatchedCKThermalModel:
         import torch
         eng = self.eng
         dev = torch.device("cuda", eng.device) if device is None else device
-        if self.device_layers and self.DUST is None and self.PARAH2 is None:
+        if (self.device_layers and (self.DUST is None or self.dust is not None)
+                and (self.PARAH2 is None or self.cia is not None)):
             return self._spectra_batch_dev(X, dev)
         lay = self.layers(X)
         n, L = lay["PRESS"].shape
@@ -210,7 +279,20 @@ class BatchedCKThermalModel:
         shared = cur.cuda_stream != 0 and eng.stream_ptr == cur.cuda_stream
         order = (lambda: None) if shared else cur.synchronize
         cont = None
-        if self.IRAY != 0 or self.extra is not None:
+        dense = self._dense_continuum(lay, n, L)
+        if dense is not None:
+            cont = td(dense)
+            if self.IRAY != 0:
+                ray = torch.empty((n, self.W, L), dtype=torch.float64, device=dev)
+                order()
+                eng.calc_tau_rayleigh_batch_dev(self.IRAY, self.ISPACE, lay["TOTAM"], ray, ID=self.ID, ISO=self.ISO,
+                                                VMR=lay["VMRLAY"])
+                if not shared:
+                    eng.synchronize()
+                cont = cont + ray                                  # (TAUCIA + TAUDUST) + TAURAY
+            if self.extra is not None:
+                cont += td(self.extra)[None]
+        elif self.IRAY != 0 or self.extra is not None:
             if self.IRAY != 0:       # the kernel assigns every element
                 cont = torch.empty((n, self.W, L), dtype=torch.float64, device=dev)
                 order()
@@ -245,7 +327,7 @@ class BatchedCKThermalModel:
         n, L = lay["PRESS"].shape
         P_, LIMAX = path.NPATH, path.LAYINC.shape[0]
         out = torch.empty((n, self.W, P_), dtype=torch.float64, device=dev)
-        if self.IRAY != 0 and self.extra is None and self.fused_rayleigh:
+        if self.IRAY != 0 and self.extra is None and self.fused_rayleigh and self.cia is None and self.dust is None:
             # the Rayleigh continuum is formed inside the call, once per distinct layer of the batch
             f4 = eng.rayleigh_f4(self.ID, self.ISO, lay["VMRLAY"]) if self.IRAY == 4 else None
             args = (lay["PRESS"].contiguous(), lay["TEMP"].contiguous(), lay["amount"], self.IRAY, lay["TOTAM"].contiguous(), f4, P_,
@@ -255,8 +337,38 @@ class BatchedCKThermalModel:
             self.last_rows = eng.last_layer_rows()
             drain()
             return out.reshape(n, self.W * P_)
+        sources = self.cia is not None or self.dust is not None
+        if sources and self.extra is None and self.fused_continuum:
+            # CIA, aerosol and Rayleigh opacity are formed inside the call from the resident sources, once per distinct layer
+            if not self._sources_on:
+                self.upload_sources()
+            cia, dust = self.cia is not None, self.dust is not None
+            f4 = eng.rayleigh_f4(self.ID, self.ISO, lay["VMRLAY"]) if self.IRAY == 4 else None
+            args = (lay["PRESS"].contiguous(), lay["TEMP"].contiguous(), lay["amount"],
+                    lay["VMRLAY"].contiguous() if cia else None, lay["FRAC"].contiguous() if cia else None,
+                    lay["TOTAM"].contiguous(), lay["DELH"].contiguous() if cia else None,
+                    lay["CONT"].contiguous() if dust else None, self.IRAY, f4, P_, LIMAX, c["NLAYIN32"], c["LAYINC32"], c["SCALE"],
+                    lay["EMTEMP"].contiguous(), c["TSURF"])
+            order()
+            eng.cirsrad_ck_thermal_cont_dev(self.ISPACE, n, L, *args, None, None, None, None, None, None, out)
+            self.last_rows = eng.last_layer_rows()
+            drain()
+            return out.reshape(n, self.W * P_)
         cont = None
-        if self.IRAY != 0 or self.extra is not None:
+        if sources:
+            drain()                                                    # the layers go to the host
+            host = {k: lay[k].cpu().numpy() for k in ("PP", "PRESS", "TEMP", "FRAC", "TOTAM", "DELH", "CONT")}
+            cont = torch.as_tensor(self._dense_continuum(host, n, L), dtype=torch.float64, device=dev)
+            if self.IRAY != 0:
+                ray = torch.empty((n, self.W, L), dtype=torch.float64, device=dev)
+                totam, vmrlay = lay["TOTAM"].contiguous(), lay["VMRLAY"]
+                order()
+                eng.calc_tau_rayleigh_batch_dev(self.IRAY, self.ISPACE, totam, ray, ID=self.ID, ISO=self.ISO, VMR=vmrlay)
+                drain()
+                cont = cont + ray                                      # (TAUCIA + TAUDUST) + TAURAY
+            if self.extra is not None:
+                cont += torch.as_tensor(self.extra, dtype=torch.float64, device=dev)[None]
+        elif self.IRAY != 0 or self.extra is not None:
             if self.IRAY != 0:
                 cont = torch.empty((n, self.W, L), dtype=torch.float64, device=dev)
                 totam, vmrlay = lay["TOTAM"].contiguous(), lay["VMRLAY"]
@@ -287,7 +399,11 @@ class BatchedCKThermalModel:
         dependence on the bottom layer's temperature (calc_thermal_emission_spectrumg :6484-6494 differentiates it with
         respect to TSURF only) -- a finite difference through `layer_average` sees both.  The Rayleigh continuum enters the
         gradients the reference's way (calculate_layer_opacity :3952-3957: dTAURAY, the cross section per unit column, is
-        added to EVERY gas's parameter; its dependence on the composition, IRAY = 4, is not differentiated)."""
+        added to EVERY gas's parameter; its dependence on the composition, IRAY = 4, is not differentiated).
+        CIA and aerosol sources (`cia`, `dust`) are not in the analytic route: NotImplementedError when one is set."""
+        if self.cia is not None or self.dust is not None:
+            raise NotImplementedError("jacobian_analytic: CIA and aerosol sources are not part of the analytic gradients; "
+                                      "use the numerical Jacobian (jacobian_nemesis_batched)")
         eng, st, la, ge = self.eng, self.state, self.lay, self.geo
         X0 = st.XN if X0 is None else np.asarray(X0, float)
         T, VMR = st.profiles(X0[None])

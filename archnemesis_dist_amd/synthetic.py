@@ -115,6 +115,22 @@ def synth_profiles(NPRO, NVMR, seed=11, p_bottom_bar=10.0, p_top_bar=1.0e-6):
                 RADIUS=7.1492e7)
 
 
+def synth_cia(NWC=400, NT=10, wn_max=2000.0, seed=13):
+    """Collision-induced absorption table of an H2 / He atmosphere (pairs H2-H2 and H2-He, no ortho/para axis): smooth bands
+    of 1e-46 .. 1e-44 cm^5 molecule^-2 on NWC wavenumbers 0 .. wn_max and NT temperatures 50 .. 500 K, growing with
+    temperature.  Returns the dict `BatchedCKThermalModel(cia=...)` and, by name, `AnsfmEngine.upload_cia` take."""
+    rng = np.random.default_rng(seed)
+    wn = np.linspace(0.0, wn_max, NWC)
+    temp = np.linspace(50.0, 500.0, NT)
+    K = np.empty((2, 1, NT, NWC))
+    for ip in range(2):
+        centre, width = rng.uniform(300.0, 900.0, 3), rng.uniform(150.0, 400.0, 3)
+        band = sum(np.exp(-0.5 * ((wn - c) / w) ** 2) for c, w in zip(centre, width))
+        K[ip, 0] = 10.0 ** rng.uniform(-46, -45) * (1.0 + 9.0 * band[None, :]) * (temp[:, None] / 100.0) ** rng.uniform(0.3, 0.9)
+    return dict(CIA_WAVEN=wn, CIA_TEMP=temp, CIA_FRAC=np.array([0.0]), NPARA=0, K_CIA=K, IPAIRG1=[39, 39], IPAIRG2=[39, 40],
+                INORMALT=[0, 0], INORMAL=0, INORMALD=np.array([False, False]))
+
+
 def synth_lbl_gas(wn_lo, wn_hi, n_iso, lines, L, seed=0, bin_width=1.0, margin=150.0):
     """Runtime line-by-line data of a synthetic gas of n_iso isotopologues between wn_lo and wn_hi (cm-1): per isotopologue
     `lines` strong lines and the weak-line bins of width bin_width, both out to `margin` beyond the interval, one broadener.

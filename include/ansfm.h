@@ -254,6 +254,26 @@ int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, i
                                      const double *SOLFLUX, const double *REFLECTANCE, const double *SOL_ANG,
                                      const double *EMISS_ANG, const double *xfac, double *SPECOUT);
 
+/* The same for a batch whose continuum is collision-induced absorption, aerosol extinction and Rayleigh scattering, any of
+ * the three: cont = (TAUCIA + TAUDUST) + TAURAY (calculate_layer_opacity :3989; an absent term is left out, not added as
+ * zero) is formed inside the call from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust) -- once per
+ * DISTINCT layer of the batch and straight in the layout the RT kernel reads.  DEVICE arrays: use_cia: lay_q[n][L][NVMR] =
+ * PP / PRESS (NVMR as uploaded), lay_frac[n][L] (para-H2 fraction), lay_totam[n][L] (m-2), lay_delh[n][L] (km); use_dust:
+ * lay_cont[n][L][NDUST] (particles m-2 after any DUST_RENORMALISATION, NDUST as uploaded); ray_mode 0 or as in
+ * ansfm_cirsrad_ck_thermal_ray_dev, from lay_totam and f4[n][L][4].  All of them are part of a layer's identity: a state that
+ * perturbs He changes no spectroscopic amount, yet it changes CIA.  Same bits as ansfm_calc_tau_cia + ansfm_calc_tau_dust
+ * (nan_to_num, clip to [0, 1e20], summed over the populations in order) + ansfm_calc_tau_rayleigh_batch_dev over all n * L
+ * layers, summed in that order and passed as taucont.  ANSFM_ERR_INVALID when a source that is used has not been uploaded
+ * since the last table, or the CIA source was uploaded for the other ISPACE. */
+int ansfm_cirsrad_ck_thermal_cont_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                      const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                      const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                      const double *lay_cont, int ray_mode, const double *f4, int P, int LIMAX,
+                                      const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE, const double *EMTEMP,
+                                      const double *TSURF, const double *EMISSIVITY, const double *SOLFLUX,
+                                      const double *REFLECTANCE, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                      double *SPECOUT);
+
 /* CIRSrad, pure-transmission branch (IMOD without ABSORBTION / THERMAL_EMISSION / scattering flags; ForwardModel_0.py:
  * 4478-4481 -> calculate_transmission_spectrum :4110-4131): SPECOUT[n][W][P] = xfac[W] * sum_g DELG[g] exp(-sum_layers
  * TAUTOT_LAYINC) -- the same opacity assembly as the thermal branch, the RT kernel's epilogue switched.  xfac = the
@@ -812,6 +832,25 @@ int ansfm_calc_tau_rayleigh_batch_dev_in(ansfm_ctx *ctx, int mode, int ISPACE, i
 int ansfm_calc_tau_dust(ansfm_ctx *ctx, int W, const double *WAVEC, int NWS, const double *SWAVE, int NDUST,
                         const double *KEXT, const double *KSCA, int L, const double *CONT, double *TAUDUST,
                         double *TAUCLSCAT, double *dTAUDUSTdq, double *dTAUCLSCATdq);
+
+/* Continuum sources resident in the context, like the table and on its wavenumber grid, for
+ * ansfm_cirsrad_ck_thermal_cont_dev.  Uploading a k-table or LBL table (or committing a line source) clears both.
+ * ansfm_upload_cia: everything of ansfm_calc_tau_cia that does not depend on the layers.  The CIA table is evaluated at
+ * x = WAVE[w] (ISPACE 0) or 1e4 / WAVE[w] (ISPACE 1; interp1d is pointwise, so the reference's sort and un-sort :4565-4568 /
+ * :4741-4743 change no value); k_co2 / k_n2n2 / k_n2h2[W] are co2cia / n2n2cia / n2h2cia at that x, in the order of the
+ * table's grid.  The `covers` test (:4671) is made here on the range of x.  ANSFM_ERR_UNSUPPORTED for a table whose para-H2
+ * bracket could leave K_CIA for some layer (NPARA > 0 without NPARA == nfrac == NPE >= 2): the per-layer IndexError of
+ * ansfm_calc_tau_cia cannot arise on the device. */
+int ansfm_upload_cia(ansfm_ctx *ctx, int ISPACE, int NWC, const double *cia_waven, int NPAIR, int NPE, int NT,
+                     const double *K_CIA, const double *cia_temp, int nfrac, const double *cia_frac, int NPARA,
+                     const int32_t *igas1, const int32_t *igas2, int NVMR, int ico2, const double *k_co2, int in2,
+                     const double *k_n2n2, int ih2, const double *k_n2h2);
+/* ansfm_upload_dust: the extinction cross sections KEXT[NWS][NDUST] on SWAVE evaluated on the table's grid exactly as
+ * ansfm_calc_tau_dust evaluates them (KSCA[NWS][NDUST] decides with KEXT where the linear interpolant replaces the spline,
+ * :4849-4859; NULL: zeros) and kept as kext_w[NDUST][Wpad].  NDUST > 7 is ANSFM_ERR_UNSUPPORTED: NumPy sums eight and more
+ * populations pairwise, fewer in order, and the fused entry sums in order. */
+int ansfm_upload_dust(ansfm_ctx *ctx, int NWS, const double *SWAVE, int NDUST, const double *KEXT, const double *KSCA);
+int ansfm_clear_continuum_sources(ansfm_ctx *ctx);
 
 /* Layer de-duplication inside a batch (n_models > 1) of the cirsrad_ck_thermal entry points.  The states of a
  * numerical Jacobian (ForwardModel_0.jacobian_nemesis :2234-2242) differ from the unperturbed one in two or three

@@ -54,6 +54,8 @@ def main():
         bench_disc(eng, out)
     if only == "ss":                                        # 10 GB of host arrays: on request only
         bench_ss(eng, out, rng)
+    if only == "cia":                                       # 1.6 GB continuum array of the dense route: on request only
+        bench_cia(eng, out)
     print(json.dumps(out, indent=1))
 
 
@@ -699,6 +701,50 @@ def bench_disc(eng, out, W=1024, n=5):
         res.update(down_and_up_k_disc_planck_and_sens_ms=float(np.median(ms_d[1:])),
                    down_and_up_k_limb_planck_and_sens_ms=float(np.median(ms_l[1:])))
         out["disc_C2_W%d_NAV%d" % (W, NAV)] = res
+
+
+def bench_cia(eng, out, W=10000, n=5):
+    """C3 (201 states through 100 profile levels, bench.py's table) with the CIA table of a synthetic H2 / He atmosphere: the
+    numerical Jacobian with the continuum formed inside the batched call per distinct layer (fused), next to the same
+    atmosphere without CIA (Rayleigh alone) and to CIA through calc_tau_cia over all layers and a dense taucont."""
+    import torch
+    import bench as B
+    from archnemesis_dist_amd.jacobian import jacobian_nemesis_batched
+    from archnemesis_dist_amd.profile_state import ContinuousProfileState, BatchedCKThermalModel
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    dev = torch.device("cuda", eng.device)
+    G, S, L, NP, NT = 20, 8, 100, 20, 15
+    stream = torch.cuda.Stream(device=dev); torch.cuda.set_stream(stream)
+    eng.set_stream(stream.cuda_stream)
+    PRESS, TEMP, K = B.torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    WAVE = 200.0 + (1000.0 / W) * np.arange(W)
+    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+    pr = syn.synth_profiles(100, S + 2, seed=11)
+    st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T", ("VMR", 2)])
+    mk = lambda cia: BatchedCKThermalModel(eng, st, pr["RADIUS"], pr["ID"], pr["ISO"], list(range(2, S + 2)),
+                                           layering_args=dict(NLAY=L, LAYINT=1, NINT=101), IRAY=4, cia=cia)
+
+    def wall(model, reps):
+        def f():
+            torch.cuda.synchronize(); r = jacobian_nemesis_batched(model); torch.cuda.synchronize(); return r
+        return timeit(f, reps), f()
+
+    res = {"W": W, "G": G, "S": S, "L": L, "states": st.NX + 1}
+    ray = mk(None)
+    res["rayleigh_alone_s"], _ = wall(ray, n)
+    res["rayleigh_alone_rows"] = list(ray.last_rows)
+    model = mk(syn.synth_cia())
+    res["cia_fused_s"], (YN, KK) = wall(model, n)
+    res["cia_fused_rows"] = list(model.last_rows)
+    model.fused_continuum = False
+    res["cia_dense_s"], (YN_d, KK_d) = wall(model, 1)
+    res["cia_dense_rows"] = list(model.last_rows)
+    res["fused_equals_dense"] = bool(np.array_equal(YN, YN_d) and np.array_equal(KK, KK_d))
+    res["median_of"] = n
+    eng.set_stream(None)
+    out["jacobian_C3_cia"] = res
 
 
 def bench_layer(eng, out):
