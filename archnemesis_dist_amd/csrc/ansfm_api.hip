@@ -394,6 +394,13 @@ int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *tri
     return ANSFM_OK;
 }
 
+int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width)
+{
+    if (!ctx || !width) return ANSFM_ERR_INVALID;
+    *width = ctx->merge_group_width;
+    return ANSFM_OK;
+}
+
 int ansfm_last_merge_rowmajor(const ansfm_ctx *cctx, int64_t *merges, int64_t *merges_total)
 {
     ansfm_ctx *ctx = const_cast<ansfm_ctx *>(cctx);     // the error text and the stream: nothing of the launch's state changes

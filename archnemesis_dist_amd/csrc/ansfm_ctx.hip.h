@@ -108,6 +108,7 @@ struct ansfm_ctx {
     unsigned grad_gas_mask = 0xFFFFFFFFu;   // ansfm_set_gradient_gases: gases whose amount gradients cirsradg computes
     std::map<const void *, size_t> merge_lds_allowed;   // dynamic LDS each merge kernel has been allowed on this device
     int merge_block_waves = 0, merge_trims = 0;   // the last forward merge launch (ansfm_last_merge_launch)
+    int merge_group_width = 0;                    // ... and the wavenumbers of its row-mapped tiles (ansfm_last_merge_group_width)
     int merge_keys = 64;     // 32: run the forward merge on k_ck_overlap32's float32 keys (ansfm_set_merge_keys)
     bool have_table = false;
     int grid_f32 = 0, delg_f32 = 0;

@@ -250,8 +250,9 @@ __device__ __forceinline__ bool merge_walk_nodiv(const MergeElem &e, WalkState &
 // prefix like any other.  The last chunk closes with t_{NP-1} = max(x, s_{NP-1}) as the full pass does.
 // Every test is a scalar branch that the wave waits for, and a wave alone on its SIMD has nobody to hide it behind: with 64
 // unrelated wavenumbers per wave two tests (4, 10) measured faster than three or four.  With the lanes grouped over rows
-// (LaneRow) most steps leave at the first test, and three boundaries measured faster than 4/10, 3/9 and 2/5/9/14
-constexpr int kExitBounds[] = {3, 7, 12};
+// (LaneRow) most steps leave at the first test, and three boundaries measured faster than 4/10, 3/9 and 2/5/9/14; with 64 rows
+// of one wavenumber per wave the lanes re-enter shallower still, and 2/6/11 measured faster than 3/7/12 and 3/8
+constexpr int kExitBounds[] = {2, 6, 11};
 constexpr int kNoExitBound = 1000;
 // the first boundary above k0
 __host__ __device__ constexpr int merge_exit_bound(int k0)

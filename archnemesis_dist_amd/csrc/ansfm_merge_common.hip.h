@@ -181,29 +181,90 @@ __device__ __forceinline__ void load_gas(const OverlapParams &p, const LayerInte
 }
 
 // Layer-grouped lanes (the forward kernel's fast path).  The (model, layer) rows of a launch are one row axis of
-// length R = n_models * L, and the cells of a 64-wavenumber block are numbered (wavenumber / kLaneNV, row, wavenumber % kLaneNV),
-// the last fastest; a tile is 64 consecutive cells of that order: kLaneNV wavenumbers x 64 / kLaneNV consecutive rows, running on
-// into the next wavenumber group at the end of the row axis.  A block holds 64 * R cells, i.e. exactly R tiles, whatever R is.
+// length R = n_models * L, and the cells of a 64-wavenumber block are numbered (wavenumber / width, row, wavenumber % width),
+// the last fastest; a tile is 64 consecutive cells of that order: width wavenumbers x 64 / width consecutive rows, running on
+// into the next wavenumber group at the end of the row axis (width: 1 or kLaneNV, see below).  A block holds 64 * R cells,
+// i.e. exactly R tiles, whatever R is.
 // Neighbouring rows of one wavenumber meet the same gases at nearby (p, T), so the lanes of a wave re-enter the head list at
 // similar depths and merge_pass_exit can stop where a wave of 64 unrelated wavenumbers cannot.  What was wave-uniform in the
 // other mapping -- the row's interpolation constants, its amounts, the corner rows of the table -- is per lane here.
 constexpr int kLaneNV = 2;
-constexpr int kLaneRows = kWave / kLaneNV;        // rows of a tile, and wavenumber groups of a 64-wavenumber block
 static_assert(kLaneNV == 2 || kLaneNV == 4 || kLaneNV == 8, "group width");
+// The width a launch runs at is wave-uniform run-time data, 1 or kLaneNV ("pairs"), an argument of k_ck_overlap beside flags: the
+// functions below take its binary logarithm, nvs.  At width 1 a tile is 64 consecutive rows of ONE wavenumber, running on into
+// the next wavenumber at the end of the row axis: whether a merge sorts row by row (merge_rowmajor_test) and how deep a lane
+// re-enters the head list are decided by the gases' magnitudes at the wavenumber, so a second wavenumber in the wave is an
+// independent draw that spoils the first.
+constexpr unsigned kLaneNVShift = (unsigned)__builtin_ctz((unsigned)kLaneNV);
 
 // Queue order inside a 64-wavenumber block: the u-th tile handed out is tile lane_tile_of(u) of the cell order.  A tile is at
 // "row slot" s when it is the s-th tile that starts in its wavenumber group; the tiles go out slot by slot, group by group
-// within a slot, so that the 16 / kLaneNV tiles that read the same 128-byte table lines (one 16-wavenumber span, one row
-// slot) are neighbours in the queue and one wave's miss serves the others from L2.  Every group has R / kLaneRows such tiles or
-// one more; the i-th group that has one more is group i * kLaneRows / (R % kLaneRows).
-__host__ __device__ constexpr unsigned lane_tile_of(unsigned u, unsigned R)
+// within a slot, so that the 16 / width tiles that read the same 128-byte table lines (one 16-wavenumber span, one row
+// slot) are neighbours in the queue and one wave's miss serves the others from L2.  Every group has R / Q such tiles or
+// one more (Q = 64 / width, the rows of a tile and the groups of a block); the i-th group that has one more is group
+// i * Q / (R % Q).
+__host__ __device__ constexpr unsigned lane_tile_of(unsigned u, unsigned R, unsigned nvs)
 {
-    constexpr unsigned Q = kLaneRows;
-    const unsigned fl = R / Q, rem = R % Q;
-    unsigned grp = u % Q, slot = u / Q;
-    if (u >= Q * fl) { slot = fl; grp = (u - Q * fl) * Q / rem; }
-    return (grp * R + Q - 1) / Q + slot;            // the first tile that starts in the group, + slot
+    const unsigned qs = 6u - nvs, Q = 1u << qs;
+    const unsigned fl = R >> qs, rem = R & (Q - 1u);
+    unsigned grp = u & (Q - 1u), slot = u >> qs;
+    if (u >= (fl << qs)) { slot = fl; grp = ((u - (fl << qs)) << qs) / rem; }
+    return ((grp * R + Q - 1u) >> qs) + slot;       // the first tile that starts in the group, + slot
 }
+
+// Cell c of a block's cell order (c = tile * 64 + lane): its wavenumber inside the block and its row
+struct LaneCell { unsigned w, row; };
+__host__ __device__ constexpr LaneCell lane_cell(unsigned c, unsigned R, unsigned nvs)
+{
+    const unsigned pair = c >> nvs;                 // width 1: pair = c, grp = c / R, w = grp
+    const unsigned grp = pair / R;
+    return LaneCell{(grp << nvs) + (c & ((1u << nvs) - 1u)), pair - grp * R};
+}
+
+// The two functions above, checked where they are compiled: at each width the queue order is a permutation of the block's R
+// tiles and the cells of tile k are distinct cells of the 64 x R block (a bijection, since there are 64 * R of them) ...
+__host__ __device__ constexpr bool lane_mapping_holds(unsigned R, unsigned nvs)
+{
+    for (unsigned k = 0; k < R; ++k) {
+        unsigned hits = 0;
+        for (unsigned u = 0; u < R; ++u) hits += lane_tile_of(u, R, nvs) == k ? 1u : 0u;
+        if (hits != 1u) return false;
+    }
+    for (unsigned c = 0; c < 64u * R; ++c) {
+        const LaneCell x = lane_cell(c, R, nvs);
+        if (x.w >= 64u || x.row >= R) return false;
+        if ((((x.w >> nvs) * R + x.row) << nvs) + (x.w & ((1u << nvs) - 1u)) != c) return false;     // the inverse
+    }
+    return true;
+}
+static_assert(lane_mapping_holds(1, 0) && lane_mapping_holds(3, 0) && lane_mapping_holds(33, 0) && lane_mapping_holds(64, 0) &&
+              lane_mapping_holds(100, 0), "width 1");
+static_assert(lane_mapping_holds(1, kLaneNVShift) && lane_mapping_holds(3, kLaneNVShift) && lane_mapping_holds(33, kLaneNVShift) &&
+              lane_mapping_holds(64, kLaneNVShift) && lane_mapping_holds(100, kLaneNVShift), "width kLaneNV");
+// ... and at these spots they give what the plain-Python model of the mapping gives (tests/test_merge_one_wavenumber_model.py
+// reads the two tables and compares them with tests/test_merge_layer_groups_model.py).  {u, R, width, tile} and
+// {tile, lane, R, width, wavenumber in the block, row}
+constexpr unsigned kLaneTileSpots[][4] = {
+    {0, 100, 1, 0}, {1, 100, 1, 2}, {37, 100, 1, 58}, {50, 100, 1, 79}, {64, 100, 1, 1}, {98, 100, 1, 95}, {99, 100, 1, 98},
+    {0, 100, 2, 0}, {1, 100, 2, 4}, {37, 100, 2, 17}, {50, 100, 2, 58}, {64, 100, 2, 2}, {98, 100, 2, 53}, {99, 100, 2, 78},
+    {1, 33, 1, 1}, {16, 33, 1, 16}, {32, 33, 1, 32}, {1, 33, 2, 2}, {16, 33, 2, 17}, {31, 33, 2, 32}, {32, 33, 2, 1},
+    {2, 3, 1, 2}, {1, 696, 1, 11}, {37, 696, 1, 403}, {64, 696, 1, 1}, {348, 696, 1, 310}, {694, 696, 1, 674}, {695, 696, 1, 685}};
+constexpr unsigned kLaneCellSpots[][6] = {
+    {0, 0, 100, 1, 0, 0}, {1, 36, 100, 1, 1, 0}, {99, 63, 100, 1, 63, 99}, {50, 17, 100, 1, 32, 17},
+    {0, 0, 100, 2, 0, 0}, {1, 36, 100, 2, 0, 50}, {99, 63, 100, 2, 63, 99}, {50, 17, 100, 2, 33, 8},
+    {1, 36, 33, 1, 3, 1}, {32, 63, 33, 1, 63, 32}, {16, 17, 33, 1, 31, 18}, {1, 36, 3, 2, 32, 2}, {2, 63, 3, 2, 63, 2}, {1, 17, 3, 2, 27, 1}};
+__host__ __device__ constexpr bool lane_spots_hold()
+{
+    for (const auto &t : kLaneTileSpots)
+        if ((t[2] != 1u && t[2] != (unsigned)kLaneNV) || lane_tile_of(t[0], t[1], t[2] == 1u ? 0u : kLaneNVShift) != t[3]) return false;
+    for (const auto &t : kLaneCellSpots) {
+        if (t[3] != 1u && t[3] != (unsigned)kLaneNV) return false;
+        const LaneCell x = lane_cell(t[0] * 64u + t[1], t[2], t[3] == 1u ? 0u : kLaneNVShift);
+        if (x.w != t[4] || x.row != t[5]) return false;
+    }
+    return true;
+}
+static_assert(lane_spots_hold(), "lane_tile_of / lane_cell against the model's values");
 
 struct LaneRow {
     int nu;                     // wavenumber of the lane's cell; W <= nu < Wpad: a pad cell
@@ -214,14 +275,13 @@ struct LaneRow {
 };
 // the cell of lane `lane` of tile k of wavenumber block vt
 template <bool FROM_K>
-__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane)
+__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane, unsigned nvs)
 {
     const unsigned R = (unsigned)p.n_models * (unsigned)p.L;
-    const unsigned c = k * kWave + (unsigned)lane, pair = c / kLaneNV;
-    const unsigned grp = pair / R;
+    const LaneCell cell = lane_cell(k * kWave + (unsigned)lane, R, nvs);
     LaneRow lr;
-    lr.row = pair - grp * R;
-    lr.nu = vt * kWave + (int)(grp * kLaneNV + c % kLaneNV);
+    lr.row = cell.row;
+    lr.nu = vt * kWave + (int)cell.w;
     const unsigned m = lr.row / (unsigned)p.L;
     lr.krow = lr.row - m * (unsigned)p.L;
     lr.arow = m * (unsigned)p.S * (unsigned)p.L + lr.krow;
@@ -275,8 +335,9 @@ __device__ __forceinline__ void load_gas_rows(const OverlapParams &p, const Lane
             for (int k = 0; k < kLoadBatch; ++k) {
                 const int gi = (g0 + k < G) ? g0 + k : G - 1;
                 const size_t go = (size_t)gi * p.Wpad;
-                // plain loads, not load_gas's non-temporal ones: a 128-byte table line serves the 16 / kLaneNV tiles of its
-                // 16-wavenumber span, which the queue hands out together (measured: 4.27 -> 4.13 ms at C2)
+                // plain loads, not load_gas's non-temporal ones: a 128-byte table line serves the 16 / width tiles of its
+                // 16-wavenumber span, which the queue hands out together (measured at C2: 4.27 -> 4.13 ms at width 2; at width 1,
+                // where a line serves 16 tiles in 8-byte pieces, 3.97 ms non-temporal against 3.55 plain)
                 r1[k] = c1[go];
                 r2[k] = c2[go];
                 r3[k] = c3[go];
@@ -361,8 +422,8 @@ struct TileQueue {
         return false;
     }
     // Layer-grouped lanes: the same eight queues over the 64-wavenumber blocks, so a block's table rows stay on one XCD; a
-    // block's R = n_models * L tiles go out in the order of lane_tile_of.  k = the tile's index in the block's cell order.
-    __device__ __forceinline__ bool next_rows(const OverlapParams &p, int lane, int &vt, unsigned &k)
+    // block's R = n_models * L tiles go out in the order of lane_tile_of at the launch's width.  k = the tile's index in the block's cell order.
+    __device__ __forceinline__ bool next_rows(const OverlapParams &p, int lane, unsigned nvs, int &vt, unsigned &k)
     {
         const int NVT = p.Wpad / kWave;
         const unsigned R = (unsigned)p.n_models * (unsigned)p.L;
@@ -376,7 +437,7 @@ struct TileQueue {
             if (nq > 0 && t < nq) {
                 const unsigned b = (unsigned)(t / R);
                 vt = qq + 8 * (int)b;
-                k = lane_tile_of((unsigned)t - b * R, R);
+                k = lane_tile_of((unsigned)t - b * R, R, nvs);
                 return true;
             }
             ++qoff;

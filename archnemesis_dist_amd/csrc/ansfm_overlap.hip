@@ -117,13 +117,21 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     // queues above hold).  64 wavenumbers of one row per wave remain for ANSFM_MERGE_LANES=wavenumbers and for a launch of 2^24
     // rows or more, whose cell numbers would leave the 32 bits lane_row computes in; bit 32 of the reported trims tells which ran
     bool lane_rows = opt != 0 && (long)n_models * L < (1L << 24);
-    if (const char *ev = getenv("ANSFM_MERGE_LANES")) { if (!strcmp(ev, "wavenumbers")) lane_rows = false; }
+    // the width of a row-mapped tile: 1 wavenumber x 64 rows for every shape (C2, 20 gases, the Jacobian's 696 distinct rows gain,
+    // G = 10 is level: DESIGN.md 4.1), or kLaneNV x 64 / kLaneNV with ANSFM_MERGE_LANES=pairs.  Not a bit of the trims (bit 32 is
+    // set for both): ansfm_last_merge_group_width reports it
+    int lane_nv = 1;
+    if (const char *ev = getenv("ANSFM_MERGE_LANES")) {
+        if (!strcmp(ev, "wavenumbers")) lane_rows = false;
+        else if (!strcmp(ev, "pairs")) lane_nv = kLaneNV;
+    }
     // the instantiations with the weight table walk a wave's row-major merges without the head list (merge_rowmajor);
     // ANSFM_MERGE_ROWMAJOR=0 launches the same kernel with the walk off.  Bit 64 of the reported trims, in either lane mapping
     bool rowmajor = (opt & kOptTable) != 0;
     if (const char *ev = getenv("ANSFM_MERGE_ROWMAJOR")) { if (ev[0] == '0') rowmajor = false; }
     const int flags = (lane_rows ? kFlagLaneRows : 0) | (rowmajor ? kFlagRowMajor : 0);
     ctx->merge_block_waves = nwaves;
+    ctx->merge_group_width = lane_rows ? lane_nv : 0;
     ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0) | (lane_rows ? kOptLaneRows : 0) | (rowmajor ? kOptRowMajor : 0);
     if (keys32) {
         HIPCHK(launch_overlap32(p, from_k, merge_list_len(G), (unsigned)grid, ctx->stream));
@@ -138,7 +146,7 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             lds_allowed = lds;                                                                                      \
         }                                                                                                           \
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p, flags);            \
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave * nwaves), lds, ctx->stream, p, flags, lane_nv);           \
     } while (0)
 #define LAUNCH_OV2(D, FK, W32)                                                                                      \
     do {                                                                                                            \
@@ -147,13 +155,13 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
         else if (opt != 0)                                                                                          \
             LAUNCH_OPT(k_ck_overlap<D, FK, W32, true, true, false, merge_opt_of(W32)>);                             \
         else if (nodiv && nobox)                                                                                         \
-            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0); \
+            hipLaunchKernelGGL((k_ck_overlap<D, false, W32, true, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0, 0); \
         else if (nodiv)                                                                                             \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0); \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0, 0); \
         else if (sorted)                                                                                            \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0);  \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0, 0);  \
         else                                                                                                        \
-            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0); \
+            hipLaunchKernelGGL((k_ck_overlap<D, FK, W32, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, p, 0, 0); \
     } while (0)
 #define LAUNCH_OV(D, FK)                                                                              \
     do {                                                                                              \

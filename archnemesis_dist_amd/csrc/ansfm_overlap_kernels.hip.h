@@ -9,8 +9,8 @@ namespace ansfm {
 //
 // One LANE per (wavenumber, layer) cell; a wavefront = 64 consecutive wavenumbers of ONE layer, so
 // corner indices, u, v and gas amounts are wave-uniform (SGPRs) and every table access is one
-// 512-byte coalesced row.  (The fast path, OPT != 0, can instead take kLaneNV wavenumbers x 64 / kLaneNV rows per wave,
-// bit 0 of the argument flags and LaneRow in ansfm_merge_common.hip.h: the merge below does not care which cell a lane holds.)
+// 512-byte coalesced row.  (The fast path, OPT != 0, can instead take 1 or kLaneNV wavenumbers x 64 or 64 / kLaneNV rows per wave,
+// bit 0 of the argument flags, the argument lane_nv and LaneRow in ansfm_merge_common.hip.h: the merge below does not care which cell a lane holds.)
 // The reference sorts the G*G sums tau_i + k_j*amount (argsort) and walks the sorted list once to re-bin it (rank, ForwardModel_0.py:6117-6173).  Both inputs are
 // already sorted in g, so the sorted sequence is produced by a G-way streaming merge of the rows
 // (a_i + b_0..b_{G-1}) -- the row heads held as a sorted list in registers, see merge_step -- and rank's walk
@@ -47,7 +47,7 @@ __device__ __forceinline__ void load_cell(const OverlapParams &p, int lane_rows,
 
 template <int NR, bool FROM_K, bool W32, bool SORTED = true, bool NODIV = false, bool NOBOX = false, int OPT = 0>
 __global__ __launch_bounds__((OPT & kOptTable) != 0 ? kWave * kMaxBlockWaves : kWave) __attribute__((amdgpu_waves_per_eu(1, 2)))
-void k_ck_overlap(OverlapParams p, int flags)
+void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
 {
     static_assert(OPT == 0 || (SORTED && NODIV), "the fast path");
     static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
@@ -56,6 +56,8 @@ void k_ck_overlap(OverlapParams p, int flags)
     // flags: the row mapping (kFlagLaneRows) and, with kOptTable only, the list-free walk of row-major merges (kFlagRowMajor);
     // the instantiations without the table are launched with 0 or 1 and test the word as they always did
     const int lane_rows = kTable ? (flags & kFlagLaneRows) : flags;
+    // lane_nv: the wavenumbers of a tile of the row mapping, 1 or kLaneNV (LaneRow); unused without lane_rows
+    const unsigned nvs = lane_nv == 1 ? 0u : kLaneNVShift;
     unsigned n_rowmajor = 0, n_merged = 0;              // kOptTable: the merges of this wave that took the walk / all of them
     extern __shared__ double smem[];
     const int lane = kTable ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
@@ -104,8 +106,8 @@ void k_ck_overlap(OverlapParams p, int flags)
         if constexpr (OPT != 0) {
             if (lane_rows != 0) {
                 unsigned k = 0;
-                if (!tq.next_rows(p, lane, vt, k)) break;
-                lr = lane_row<FROM_K>(p, vt, k, lane);
+                if (!tq.next_rows(p, lane, nvs, vt, k)) break;
+                lr = lane_row<FROM_K>(p, vt, k, lane, nvs);
             } else if (!tq.next(p, lane, vt, m, l)) break;
         } else {
             if (!tq.next(p, lane, vt, m, l)) break;

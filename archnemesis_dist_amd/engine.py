@@ -281,12 +281,20 @@ class AnsfmEngine:
     def last_merge_launch(self):
         """(waves per block, trim bits) of the last forward merge launch: bits 1 weight table, 2 key repack,
         8 list pass that ends at the insertion point, 16 per-lane row operand, 32 a wave's lanes grouped over rows
-        (clear with ANSFM_MERGE_LANES=wavenumbers and for a launch of 2^24 (model, layer) rows or more, which keeps 64
+        (at either width, see last_merge_group_width; clear with ANSFM_MERGE_LANES=wavenumbers and for a launch of 2^24 (model, layer) rows or more, which keeps 64
         wavenumbers of one row per wave), 64 row-major merges are walked without the head list (kernels with bit 1; clear with
         ANSFM_MERGE_ROWMAJOR=0) (4: retired, never set)."""
         w, t = C.c_int(), C.c_int()
         self._check(self._lib.ansfm_last_merge_launch(self._ctx, C.byref(w), C.byref(t)), "last_merge_launch")
         return int(w.value), int(t.value)
+
+    def last_merge_group_width(self):
+        """Wavenumbers per wave of the last forward merge launch where its lanes were grouped over rows (bit 32 of
+        last_merge_launch's trims): 1 (64 rows of one wavenumber, the library's choice) or 2 (ANSFM_MERGE_LANES=pairs);
+        0 where a wave held 64 wavenumbers of one row."""
+        w = C.c_int()
+        self._check(self._lib.ansfm_last_merge_group_width(self._ctx, C.byref(w)), "last_merge_group_width")
+        return int(w.value)
 
     def last_merge_rowmajor(self):
         """(merges walked row by row, merges) of the last forward merge launch, counted per wave: a wave whose lanes' G x G sums

@@ -87,6 +87,9 @@ int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *tri
  * ansfm_last_merge_rowmajor: the (wave, merge) pairs of the last forward merge launch that took that walk, and all pairs that
  * merged; both 0 for a kernel without bit 1, which does not count.  Copies the two totals from the device (synchronises). */
 int ansfm_last_merge_rowmajor(const ansfm_ctx *ctx, int64_t *merges, int64_t *merges_total);
+/* The wavenumbers a wave of the last forward merge launch held with bit 32: 1 (64 rows of one wavenumber, the library's choice)
+ * or 2 (2 wavenumbers x 32 rows, ANSFM_MERGE_LANES=pairs); 0 without bit 32 (64 wavenumbers of one row).  Reads the context only. */
+int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width);
 
 /* ---- LBL tables (ILBL = LINE_BY_LINE_TABLES) ------------------------------------------------------
  * State of Spectroscopy_0 after read_tables on .lta / HDF5 LBL tables: K[W][NP][|NT|][S] (NG = 1),
