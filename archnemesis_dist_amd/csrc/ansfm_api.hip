@@ -81,6 +81,32 @@ int ansfm_synchronize(ansfm_ctx *ctx)
 /* ------------------------------------------------------------------------------------------ */
 /* k-table                                                                                     */
 /* ------------------------------------------------------------------------------------------ */
+// The g-fastest copy of the k-table just written to ctx->lnK (k_table_gfast; OverlapParams::lnKg): built at the end of every
+// upload of a k-table, not for one ordinate (G = 1: LBL tables and the line source's stand-in) and not with
+// ANSFM_TABLE_GFAST=0 (DESIGN.md 4.1 has the measurement behind the default).  It doubles the table's memory, so an
+// allocation that fails is no error: the context is left without the copy and the merge reads lnK as before.  An upload that
+// does not build it drops the copy of the table it replaces.
+static constexpr bool kTableGfastDefault = true;
+static int build_table_gfast(ansfm_ctx *ctx, int Wpad, int G, int Q, bool lbl)
+{
+    bool want = kTableGfastDefault;
+    if (const char *ev = getenv("ANSFM_TABLE_GFAST")) want = ev[0] == '1' ? true : (ev[0] == '0' ? false : want);
+    ctx->lnKg_bytes = 0;
+    if (!want || lbl || G < 2 || Wpad / kWave > 65535) { ctx->lnKg.release(); return ANSFM_OK; }
+    const size_t bytes = (size_t)Q * Wpad * gfast_stride(G) * sizeof(double);
+    if (ctx->lnKg.reserve(bytes) != hipSuccess) {
+        (void)hipGetLastError();        // clear it: the next HIPCHK(hipGetLastError()) is not about this
+        ctx->lnKg.release();
+        return ANSFM_OK;
+    }
+    hipLaunchKernelGGL(k_table_gfast, dim3((unsigned)Q, (unsigned)(Wpad / kWave)), dim3(256), 0, ctx->stream,
+                       ctx->lnK.as<double>(), ctx->lnKg.as<double>(), Wpad, G);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->lnKg_bytes = bytes;
+    return ANSFM_OK;
+}
+
 int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S, const double *K_dev,
                             const double *PRESS, const double *TEMP, const double *WAVE,
                             const double *DELG)
@@ -92,6 +118,7 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
     HIPCHK(hipSetDevice(ctx->device));
     const int Wpad = round_up(W, kWave);
     const size_t total = (size_t)NP * NT * S * G * Wpad;
+    ctx->lnKg_bytes = 0;                 // the copy, if any, is of the table that lnK held
     HIPCHK(ctx->lnK.reserve(total * sizeof(double)));
     HIPCHK(ctx->d_press.reserve(NP * sizeof(double)));
     HIPCHK(ctx->d_temp.reserve(NT * sizeof(double)));
@@ -123,7 +150,7 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
     ctx->is_lbl = 0; ctx->temp2d = 0;
     ctx->lblrt = 0; ctx->st_n = 0;       // a table replaces a committed line source
     clear_continuum_sources(ctx);        // they were evaluated on the old table's grid
-    return ANSFM_OK;
+    return build_table_gfast(ctx, Wpad, G, NP * NT * S, false);
 }
 
 int ansfm_upload_ktable(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S, const double *K,
@@ -295,6 +322,7 @@ static int upload_table_files(ansfm_ctx *ctx, int S, const char *const *paths, d
         TEMP(hl.temp.begin(), hl.temp.end()), DELG(hl.del_g.begin(), hl.del_g.end());
     const int Wpad = round_up(W, kWave);
     const size_t total = (size_t)NP * NT * S * G * Wpad;
+    ctx->lnKg_bytes = 0;                 // the copy, if any, is of the table that lnK held
     HIPCHK(ctx->lnK.reserve(total * sizeof(double)));
     HIPCHK(ctx->d_press.reserve(NP * sizeof(double)));
     HIPCHK(ctx->d_temp.reserve(TEMP.size() * sizeof(double)));                 // [NP][NT] for a table with NT < 0
@@ -344,7 +372,7 @@ static int upload_table_files(ansfm_ctx *ctx, int S, const char *const *paths, d
     clear_continuum_sources(ctx);
     if (lta) ctx->monotone = 1;
     ctx->grid_f32 = 1; ctx->delg_f32 = lta ? 0 : 1;   // PRESS / TEMP / DELG come out of the file as float32 arrays (:2544-2559)
-    return ANSFM_OK;
+    return build_table_gfast(ctx, Wpad, G, NP * NT * S, lta);
 }
 
 int ansfm_upload_ktable_files(ansfm_ctx *ctx, int S, const char *const *paths, double wavemin, double wavemax)
@@ -398,6 +426,22 @@ int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width)
 {
     if (!ctx || !width) return ANSFM_ERR_INVALID;
     *width = ctx->merge_group_width;
+    return ANSFM_OK;
+}
+
+int ansfm_last_merge_table_layout(const ansfm_ctx *ctx, int *gfast)
+{
+    if (!ctx || !gfast) return ANSFM_ERR_INVALID;
+    *gfast = ctx->merge_table_gfast;
+    return ANSFM_OK;
+}
+
+int ansfm_ktable_gfast(const ansfm_ctx *ctx, int *present, int64_t *bytes)
+{
+    if (!ctx || !present || !bytes) return ANSFM_ERR_INVALID;
+    if (!ctx->have_table) return ANSFM_ERR_NOTABLE;
+    *present = ctx->lnKg_bytes != 0 ? 1 : 0;
+    *bytes = (int64_t)ctx->lnKg_bytes;
     return ANSFM_OK;
 }
 

@@ -114,6 +114,11 @@ struct ansfm_ctx {
     int grid_f32 = 0, delg_f32 = 0;
     int is_lbl = 0, temp2d = 0;   // LBL-table mode (ILBL=2): G = 1, TEMP may be [NP][NT]
     DevBuf lnK, d_press, d_temp, d_wave, d_delg, d_flag;
+    // the g-fastest copy of lnK, [NP][NT][S][Wpad][Gs] (build_table_gfast, ansfm_ktable_gfast): lnKg_bytes is its size for the
+    // table in lnK, 0 when that table has none (G = 1, an LBL table, ANSFM_TABLE_GFAST=0, a failed allocation)
+    DevBuf lnKg;
+    size_t lnKg_bytes = 0;
+    int merge_table_gfast = 0;                    // the last forward merge launch read it (ansfm_last_merge_table_layout)
     std::vector<double> h_delg;
     // resident continuum sources on the table's grid (ansfm_upload_cia / ansfm_upload_dust; a new table clears them)
     //   cia_tab: cia_waven [NWC], K_CIA [NPAIR][NPE][NT][NWC], cia_temp [NT], cia_frac [nfrac], k_co2, k_n2n2, k_n2h2 [W] each

@@ -48,6 +48,9 @@ constexpr int kOptLaneRows = 32;
 // sort row by row walks them without the head list (merge_rowmajor)
 constexpr int kOptRowMajor = 64;
 constexpr int kFlagLaneRows = 1, kFlagRowMajor = 2;      // k_ck_overlap's argument flags
+// a further bit of flags, set only with kFlagLaneRows and a table launch, reported by ansfm_last_merge_table_layout and not in the
+// trims: the table is read from its g-fastest copy (OverlapParams::lnKg, load_gas_rows)
+constexpr int kFlagTableGfast = 4;
 // The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
 __host__ __device__ constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
 // Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a

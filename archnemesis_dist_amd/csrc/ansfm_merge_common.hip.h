@@ -109,7 +109,13 @@ struct OverlapParams {
     int W, Wpad, G, NT, S, L, n_models;
     int delg_f32;             // DELG is a float32 array: del_g[i]*del_g[j] is a float32 product
     double g_ord[kMaxG + 2];  // [0, cumsum(del_g)] (float32 cumsum when delg_f32), g_ord[G]=1, NaN
+    const double *lnKg;       // [NP][NT][S][Wpad][Gs], Gs = gfast_stride(G): the g-fastest copy of lnK, or null (load_gas_rows)
 };
+// The g-fastest copy of the table (k_table_gfast builds it from lnK): the G ordinates of one (p, T, gas, wavenumber) lie as one
+// run of Gs doubles, G rounded up to even so that every run starts 16-byte aligned and is read as Gs / 2 pairs; the pad
+// ordinate of an odd G holds the boxed 0 and is never consumed.
+__host__ __device__ constexpr int gfast_stride(int G) { return (G + 1) & ~1; }
+typedef double lnk_pair __attribute__((ext_vector_type(2)));
 
 
 // Table reads of one gas for one (64-wavenumber, layer) tile.  The loads of kLoadBatch g-ordinates (4 corner
@@ -270,12 +276,13 @@ struct LaneRow {
     int nu;                     // wavenumber of the lane's cell; W <= nu < Wpad: a pad cell
     unsigned row;               // m * L + l: the row of li and of tau
     unsigned arow, krow;        // index of gas 0's amount, (m * S) * L + l, and (FROM_K) the layer l
-    size_t o1, o2, o3, o4;      // the four corner rows of load_gas as element offsets into lnK, + nu
+    size_t o1, o2, o3, o4;      // the four corner rows of load_gas as element offsets into lnK, + nu; with the g-fastest
+                                // copy: the lane's runs of gas 0 as element offsets into lnKg
     double v, u;
 };
-// the cell of lane `lane` of tile k of wavenumber block vt
+// the cell of lane `lane` of tile k of wavenumber block vt; gfast: the launch reads the g-fastest copy (wave-uniform)
 template <bool FROM_K>
-__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane, unsigned nvs)
+__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane, unsigned nvs, bool gfast)
 {
     const unsigned R = (unsigned)p.n_models * (unsigned)p.L;
     const LaneCell cell = lane_cell(k * kWave + (unsigned)lane, R, nvs);
@@ -289,22 +296,29 @@ __device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsi
     lr.v = lr.u = 0.0;
     if constexpr (!FROM_K) {
         const LayerInterp q = p.li[lr.row];
-        const size_t strideT = (size_t)p.S * p.G * p.Wpad;
-        lr.o1 = ((size_t)q.ipl * p.NT + q.itl) * strideT + lr.nu;
-        lr.o2 = ((size_t)q.ipl * p.NT + q.ith) * strideT + lr.nu;
-        lr.o3 = ((size_t)q.iph * p.NT + q.itl) * strideT + lr.nu;
-        lr.o4 = ((size_t)q.iph * p.NT + q.ith) * strideT + lr.nu;
+        // a (p, T) block holds S * G * Wpad doubles in lnK and S * Wpad * Gs in lnKg, where wavenumber nu starts at nu * Gs
+        const size_t strideT = (size_t)p.S * (gfast ? gfast_stride(p.G) : p.G) * p.Wpad;
+        const size_t own = gfast ? (size_t)lr.nu * gfast_stride(p.G) : (size_t)lr.nu;
+        lr.o1 = ((size_t)q.ipl * p.NT + q.itl) * strideT + own;
+        lr.o2 = ((size_t)q.ipl * p.NT + q.ith) * strideT + own;
+        lr.o3 = ((size_t)q.iph * p.NT + q.itl) * strideT + own;
+        lr.o4 = ((size_t)q.iph * p.NT + q.ith) * strideT + own;
         lr.v = q.v; lr.u = q.u;
     }
     return lr;
 }
 
 // load_gas for layer-grouped lanes: the same reads, the same interp_k / interp_k_nobox and the same `* amt` per cell, with
-// the row a per-lane value
-template <bool FROM_K, bool NOBOX>
+// the row a per-lane value.  gfast (wave-uniform, lr from lane_row with the same value): the table branch reads the g-fastest
+// copy, a lane's ordinates of one corner as consecutive 16-byte pairs of its own run; the same doubles reach the same r1 .. r4.
+// GFAST is a parameter of this function, not of the kernel: the caller branches on the launch's flag around two whole copies of
+// loads + interpolation.  One copy with the branch around the loads alone joins the two kinds of loads in front of the first
+// use, where every load has to have landed: the wave-fastest reads measured 0.08 ms slower at C2 that way.
+template <bool FROM_K, bool NOBOX, bool GFAST>
 __device__ __forceinline__ void load_gas_rows(const OverlapParams &p, const LaneRow &lr, int s, double *DST, int lane,
                                               bool &unsorted)
 {
+    constexpr bool gfast = GFAST && !FROM_K;
     const int G = p.G;
     const double amt = p.amount[(size_t)lr.arow + (size_t)s * p.L];
     double prev = -__builtin_inf();
@@ -327,21 +341,39 @@ __device__ __forceinline__ void load_gas_rows(const OverlapParams &p, const Lane
                 }
         }
     } else {
-        const double *base = p.lnK + (size_t)s * G * p.Wpad;
+        static_assert(kLoadBatch % 2 == 0, "a batch is whole pairs of ordinates");
+        const int Gs = gfast_stride(G);
+        const double *base = gfast ? p.lnKg + (size_t)s * p.Wpad * Gs : p.lnK + (size_t)s * G * p.Wpad;
         const double *c1 = base + lr.o1, *c2 = base + lr.o2, *c3 = base + lr.o3, *c4 = base + lr.o4;
         for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
             double r1[kLoadBatch], r2[kLoadBatch], r3[kLoadBatch], r4[kLoadBatch];
+            if constexpr (gfast) {
 #pragma unroll
-            for (int k = 0; k < kLoadBatch; ++k) {
-                const int gi = (g0 + k < G) ? g0 + k : G - 1;
-                const size_t go = (size_t)gi * p.Wpad;
-                // plain loads, not load_gas's non-temporal ones: a 128-byte table line serves the 16 / width tiles of its
-                // 16-wavenumber span, which the queue hands out together (measured at C2: 4.27 -> 4.13 ms at width 2; at width 1,
-                // where a line serves 16 tiles in 8-byte pieces, 3.97 ms non-temporal against 3.55 plain)
-                r1[k] = c1[go];
-                r2[k] = c2[go];
-                r3[k] = c3[go];
-                r4[k] = c4[go];
+                for (int k = 0; k < kLoadBatch; k += 2) {
+                    // the pair (g0 + k, g0 + k + 1); past the end the last pair, (Gs - 2, Gs - 1), as the last ordinate below
+                    const int gi = (g0 + k < Gs) ? g0 + k : Gs - 2;
+                    const lnk_pair x1 = *reinterpret_cast<const lnk_pair *>(c1 + gi);
+                    const lnk_pair x2 = *reinterpret_cast<const lnk_pair *>(c2 + gi);
+                    const lnk_pair x3 = *reinterpret_cast<const lnk_pair *>(c3 + gi);
+                    const lnk_pair x4 = *reinterpret_cast<const lnk_pair *>(c4 + gi);
+                    r1[k] = x1.x; r1[k + 1] = x1.y;
+                    r2[k] = x2.x; r2[k + 1] = x2.y;
+                    r3[k] = x3.x; r3[k + 1] = x3.y;
+                    r4[k] = x4.x; r4[k + 1] = x4.y;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < kLoadBatch; ++k) {
+                    const int gi = (g0 + k < G) ? g0 + k : G - 1;
+                    const size_t go = (size_t)gi * p.Wpad;
+                    // plain loads, not load_gas's non-temporal ones: a 128-byte table line serves the 16 / width tiles of its
+                    // 16-wavenumber span, which the queue hands out together (measured at C2: 4.27 -> 4.13 ms at width 2; at width 1,
+                    // where a line serves 16 tiles in 8-byte pieces, 3.97 ms non-temporal against 3.55 plain)
+                    r1[k] = c1[go];
+                    r2[k] = c2[go];
+                    r3[k] = c3[go];
+                    r4[k] = c4[go];
+                }
             }
 #pragma unroll
             for (int k = 0; k < kLoadBatch; ++k)

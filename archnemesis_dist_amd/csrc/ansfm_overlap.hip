@@ -129,7 +129,14 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     // ANSFM_MERGE_ROWMAJOR=0 launches the same kernel with the walk off.  Bit 64 of the reported trims, in either lane mapping
     bool rowmajor = (opt & kOptTable) != 0;
     if (const char *ev = getenv("ANSFM_MERGE_ROWMAJOR")) { if (ev[0] == '0') rowmajor = false; }
-    const int flags = (lane_rows ? kFlagLaneRows : 0) | (rowmajor ? kFlagRowMajor : 0);
+    // a row-mapped launch on the context's own table reads the g-fastest copy where the upload built one (build_table_gfast);
+    // ANSFM_TABLE_LAYOUT=wave keeps the reads of lnK.  No bit of the trims: ansfm_last_merge_table_layout reports it
+    bool gfast = lane_rows && !from_k && !keys32 && ctx->lnKg_bytes != 0 && !ctx->is_lbl && W == ctx->W && Wpad == ctx->Wpad &&
+                 G == ctx->G && S == ctx->S;
+    if (const char *ev = getenv("ANSFM_TABLE_LAYOUT")) { if (!strcmp(ev, "wave")) gfast = false; }
+    if (gfast) p.lnKg = ctx->lnKg.as<double>();
+    const int flags = (lane_rows ? kFlagLaneRows : 0) | (rowmajor ? kFlagRowMajor : 0) | (gfast ? kFlagTableGfast : 0);
+    ctx->merge_table_gfast = gfast ? 1 : 0;
     ctx->merge_block_waves = nwaves;
     ctx->merge_group_width = lane_rows ? lane_nv : 0;
     ctx->merge_trims = opt == 0 ? 0 : merge_opt_of(ctx->delg_f32 != 0) | (lane_rows ? kOptLaneRows : 0) | (rowmajor ? kOptRowMajor : 0);

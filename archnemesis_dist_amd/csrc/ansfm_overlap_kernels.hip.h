@@ -33,12 +33,13 @@ namespace ansfm {
 // rows are a[G], a "huge" row, b[G], a "huge" row (merge_wave_rows): column G of either operand is a sentinel.
 // Gas s of the cell a lane holds, in either mapping: the lane's own row (fast path with lane_rows) or row (m, l) of the wave
 template <bool FROM_K, bool NOBOX, int OPT>
-__device__ __forceinline__ void load_cell(const OverlapParams &p, int lane_rows, const LaneRow &lr, const LayerInterp &q, int m,
+__device__ __forceinline__ void load_cell(const OverlapParams &p, int lane_rows, bool gfast, const LaneRow &lr, const LayerInterp &q, int m,
                                           int l, int s, int nu, double *DST, int lane, bool &unsorted)
 {
     if constexpr (OPT != 0) {
         if (lane_rows != 0) {
-            load_gas_rows<FROM_K, NOBOX>(p, lr, s, DST, lane, unsorted);
+            if (!FROM_K && gfast) load_gas_rows<FROM_K, NOBOX, true>(p, lr, s, DST, lane, unsorted);
+            else load_gas_rows<FROM_K, NOBOX, false>(p, lr, s, DST, lane, unsorted);
             return;
         }
     }
@@ -55,7 +56,10 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
     static_assert(!kTable || W32, "the weight table holds float32 products only (launch_overlap)");
     // flags: the row mapping (kFlagLaneRows) and, with kOptTable only, the list-free walk of row-major merges (kFlagRowMajor);
     // the instantiations without the table are launched with 0 or 1 and test the word as they always did
+    // (lane_rows is only ever compared with 0, and kFlagTableGfast is set only together with kFlagLaneRows)
     const int lane_rows = kTable ? (flags & kFlagLaneRows) : flags;
+    // the table is read from its g-fastest copy: table launches of the row mapping only
+    const bool gfast = !FROM_K && OPT != 0 && (flags & kFlagTableGfast) != 0;
     // lane_nv: the wavenumbers of a tile of the row mapping, 1 or kLaneNV (LaneRow); unused without lane_rows
     const unsigned nvs = lane_nv == 1 ? 0u : kLaneNVShift;
     unsigned n_rowmajor = 0, n_merged = 0;              // kOptTable: the merges of this wave that took the walk / all of them
@@ -107,7 +111,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             if (lane_rows != 0) {
                 unsigned k = 0;
                 if (!tq.next_rows(p, lane, nvs, vt, k)) break;
-                lr = lane_row<FROM_K>(p, vt, k, lane, nvs);
+                lr = lane_row<FROM_K>(p, vt, k, lane, nvs, gfast);
             } else if (!tq.next(p, lane, vt, m, l)) break;
         } else {
             if (!tq.next(p, lane, vt, m, l)) break;
@@ -117,11 +121,11 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
         if constexpr (!FROM_K) q = p.li[(size_t)m * p.L + l];
         bool unsorted = false;
 
-        load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, lr, q, m, l, 0, nu, A, lane, unsorted);
+        load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, gfast, lr, q, m, l, 0, nu, A, lane, unsorted);
         double alast = A[(G - 1) * kWave + lane];       // last g-ordinate in the ORIGINAL order
         if constexpr (!SORTED) sort_column(A, PA, G, lane);
         for (int s = 1; s < p.S; ++s) {
-            load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, lr, q, m, l, s, nu, B, lane, unsorted);
+            load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, gfast, lr, q, m, l, s, nu, B, lane, unsorted);
             if constexpr (SORTED)                       // the call is rerun on the generic path: no point in merging
                 if (__builtin_amdgcn_ballot_w64(unsorted) != 0) break;
             const double blast = B[(G - 1) * kWave + lane];

@@ -112,6 +112,27 @@ __global__ __launch_bounds__(256) void k_table_relayout(const double *__restrict
     }
 }
 
+// lnK[Q][G][Wpad] -> lnKg[Q][Wpad][Gs], Q = NP * NT * S and Gs = gfast_stride(G): the g-fastest copy that the forward merge's
+// row-mapped lanes read (load_gas_rows).  The encoded doubles are copied as they are, so both copies agree by construction;
+// the pad ordinate of an odd G gets the boxed 0 that the pad lanes (w >= W) already hold in lnK.  One block per (q, 64
+// wavenumbers): reads coalesced along w, and the 64 * Gs doubles it writes are one contiguous run.  Grid (Q, Wpad / 64).
+__global__ __launch_bounds__(256) void k_table_gfast(const double *__restrict__ lnK, double *__restrict__ lnKg, int Wpad, int G)
+{
+    __shared__ double tile[kMaxG][65];
+    const int Gs = gfast_stride(G);
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;      // 64 x 4
+    const size_t q = blockIdx.x;
+    const int w0 = blockIdx.y * 64;
+    for (int g = ty; g < G; g += 4) tile[g][tx] = lnK[(q * G + g) * Wpad + w0 + tx];
+    __syncthreads();
+    const double boxed0 = __longlong_as_double(0x7FF8000000000000LL);      // encode_lnk(0)
+    double *dst = lnKg + (q * Wpad + w0) * Gs;
+    for (int i = threadIdx.x; i < 64 * Gs; i += 256) {
+        const int w = i / Gs, g = i - w * Gs;
+        dst[i] = g < G ? tile[g][w] : boxed0;
+    }
+}
+
 __global__ void k_table_check(const double *__restrict__ K, int W, int G, int Q, int *flag)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

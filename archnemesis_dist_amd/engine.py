@@ -296,6 +296,20 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_last_merge_group_width(self._ctx, C.byref(w)), "last_merge_group_width")
         return int(w.value)
 
+    def ktable_gfast(self):
+        """(present, bytes) of the g-fastest copy of the uploaded k-table (built at the upload unless ANSFM_TABLE_GFAST=0, not
+        for G = 1 or an LBL table): (False, 0) without it."""
+        p, b = C.c_int(), C.c_int64()
+        self._check(self._lib.ansfm_ktable_gfast(self._ctx, C.byref(p), C.byref(b)), "ktable_gfast")
+        return bool(p.value), int(b.value)
+
+    def last_merge_table_layout(self):
+        """True when the last forward merge launch read the table from its g-fastest copy (ktable_gfast; ANSFM_TABLE_LAYOUT=wave
+        at the call keeps the wave-fastest reads)."""
+        g = C.c_int()
+        self._check(self._lib.ansfm_last_merge_table_layout(self._ctx, C.byref(g)), "last_merge_table_layout")
+        return bool(g.value)
+
     def last_merge_rowmajor(self):
         """(merges walked row by row, merges) of the last forward merge launch, counted per wave: a wave whose lanes' G x G sums
         all sort row by row walks that merge without the head list (bit 64 of last_merge_launch's trims; off with

@@ -90,6 +90,13 @@ int ansfm_last_merge_rowmajor(const ansfm_ctx *ctx, int64_t *merges, int64_t *me
 /* The wavenumbers a wave of the last forward merge launch held with bit 32: 1 (64 rows of one wavenumber, the library's choice)
  * or 2 (2 wavenumbers x 32 rows, ANSFM_MERGE_LANES=pairs); 0 without bit 32 (64 wavenumbers of one row).  Reads the context only. */
 int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width);
+/* The g-fastest copy of the k-table, ln k as [p][T][gas][wave][g] with g padded to an even count, that an upload builds from
+ * the wave-fastest table (not with ANSFM_TABLE_GFAST=0 set at the upload, for G = 1 or an LBL table; a failed allocation
+ * leaves the context without it and is no error): present = 1 and its size, or 0 and 0.  It takes the table's memory again. */
+int ansfm_ktable_gfast(const ansfm_ctx *ctx, int *present, int64_t *bytes);
+/* gfast = 1 when the last forward merge launch read the table from that copy (a launch with bit 32 on a context that holds
+ * it; ANSFM_TABLE_LAYOUT=wave at the call keeps the wave-fastest reads), else 0.  Reads the context only. */
+int ansfm_last_merge_table_layout(const ansfm_ctx *ctx, int *gfast);
 
 /* ---- LBL tables (ILBL = LINE_BY_LINE_TABLES) ------------------------------------------------------
  * State of Spectroscopy_0 after read_tables on .lta / HDF5 LBL tables: K[W][NP][|NT|][S] (NG = 1),
