@@ -417,22 +417,22 @@ int ansfm_ktable_has_boxed(const ansfm_ctx *ctx, int *has_boxed)
 int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *trims)
 {
     if (!ctx || !waves_per_block || !trims) return ANSFM_ERR_INVALID;
-    *waves_per_block = ctx->merge_block_waves;
-    *trims = ctx->merge_trims;
+    *waves_per_block = ctx->last_merge.nwaves;
+    *trims = ctx->last_merge.trims;
     return ANSFM_OK;
 }
 
 int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width)
 {
     if (!ctx || !width) return ANSFM_ERR_INVALID;
-    *width = ctx->merge_group_width;
+    *width = ctx->last_merge.group_width;
     return ANSFM_OK;
 }
 
 int ansfm_last_merge_table_layout(const ansfm_ctx *ctx, int *gfast)
 {
     if (!ctx || !gfast) return ANSFM_ERR_INVALID;
-    *gfast = ctx->merge_table_gfast;
+    *gfast = ctx->last_merge.gfast ? 1 : 0;
     return ANSFM_OK;
 }
 

@@ -3,7 +3,8 @@
 // no kernel header is included: a header that defines kernels belongs to exactly one .hip.
 //   ansfm_api.hip      lifecycle, tables, the gas-opacity stage, the entry points of thermal / transmission / single-scattering
 //                      RT and its gradients (their arguments travel as one record, RtCall)
-//   ansfm_overlap.hip  forward merge of the correlated-k path (64-bit keys); ansfm_merge32.hip: the 32-bit-key merge
+//   ansfm_overlap.hip  forward merge of the correlated-k path (64-bit keys); ansfm_merge32.hip: the 32-bit-key merge;
+//                      what a call launches is planned in ansfm_merge_plan.h (host only, no HIP header)
 //   ansfm_overlapg.hip gradient merge
 //   ansfm_rt.hip       thermal / transmission / single-scattering RT kernels and their gradients
 //   ansfm_scatter.hip  multiple scattering
@@ -34,6 +35,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/ansfm.h"
 #pragma GCC visibility pop
+#include "ansfm_merge_plan.h"
 
 namespace ansfm {
 
@@ -107,8 +109,7 @@ struct ansfm_ctx {
     int dcont_gas_L = 0;                    // 0: none pending
     unsigned grad_gas_mask = 0xFFFFFFFFu;   // ansfm_set_gradient_gases: gases whose amount gradients cirsradg computes
     std::map<const void *, size_t> merge_lds_allowed;   // dynamic LDS each merge kernel has been allowed on this device
-    int merge_block_waves = 0, merge_trims = 0;   // the last forward merge launch (ansfm_last_merge_launch)
-    int merge_group_width = 0;                    // ... and the wavenumbers of its row-mapped tiles (ansfm_last_merge_group_width)
+    ansfm::MergePlan last_merge;    // the last forward merge launch (ansfm_last_merge_launch, _group_width, _table_layout)
     int merge_keys = 64;     // 32: run the forward merge on k_ck_overlap32's float32 keys (ansfm_set_merge_keys)
     bool have_table = false;
     int grid_f32 = 0, delg_f32 = 0;
@@ -118,7 +119,6 @@ struct ansfm_ctx {
     // table in lnK, 0 when that table has none (G = 1, an LBL table, ANSFM_TABLE_GFAST=0, a failed allocation)
     DevBuf lnKg;
     size_t lnKg_bytes = 0;
-    int merge_table_gfast = 0;                    // the last forward merge launch read it (ansfm_last_merge_table_layout)
     std::vector<double> h_delg;
     // resident continuum sources on the table's grid (ansfm_upload_cia / ansfm_upload_dust; a new table clears them)
     //   cia_tab: cia_waven [NWC], K_CIA [NPAIR][NPE][NT][NWC], cia_temp [NT], cia_frac [nfrac], k_co2, k_n2n2, k_n2h2 [W] each
@@ -266,26 +266,18 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
 int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double *dkin, int W, int Wpad, int G, int S, int L,
                     int n_models, const LayerInterp *li, const double *amount, const double *del_g_dev, const double *del_g_host,
                     double *tau, double *dk, bool generic);
-// length of the register-resident row-head list of the merge kernels: smallest instantiated size >= G
-inline int merge_list_len(int G)
-{
-    static const int sizes[] = {8, 10, 16, 20, 32};
-    for (int v : sizes) if (v >= G) return v;
-    return 32;
-}
-// ansfm_overlap.hip: what the two 64-bit-key merge launches set up alike, in two calls because the forward launch picks its
-// kernel, and with it the LDS size, from g_ord.  merge_params: the fields of p both kernels read, the g_ord table (float32
+// ansfm_overlap.hip: what the two 64-bit-key merge launches set up alike, in two calls because the forward launch plans its
+// kernel, and with it the LDS size and the grid (ansfm_merge_plan.h), from g_ord.  merge_params: the fields of p both kernels read, the g_ord table (float32
 // cumulative sum when DELG is float32, NaN after the last boundary) and the tile counter's address; p was zeroed by the caller.
 void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, int Wpad, int G, int S, int L, int n_models,
                   const LayerInterp *li, const double *amount, const double *del_g_dev, const double *del_g_host, double *tau);
-// merge_launch_begin: grid = min(tiles, CUs x blocks per CU), blocks per CU = 160 KiB / block_bytes within [1, max_per_cu];
-// reserves grid x bytes_per_block of every workspace, then clears the tile counter on the stream.  The kernel launch follows.
+// merge_launch_begin: reserves grid x bytes_per_block of every workspace (grid: merge_grid or the plan's), then clears the
+// tile counter on the stream.  The kernel launch follows.
 struct MergeWorkspace {
     DevBuf *buf;
     size_t bytes_per_block;
 };
-int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, size_t block_bytes, int max_per_cu,
-                       std::initializer_list<MergeWorkspace> workspaces, long *grid_out);
+int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, long grid, std::initializer_list<MergeWorkspace> workspaces);
 // ansfm_rt.hip: k_thermal_rt by mode, batch size and prefix sharing; k_thermal_rtg with the largest reduction buffer that fits;
 // the array-level gradient seam; dspec [P][NPAR][LIMAX][Wpad] -> dSPECOUT [W][NPAR][LIMAX][P] of one model
 struct RtParams;

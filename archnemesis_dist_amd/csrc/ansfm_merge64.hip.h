@@ -39,28 +39,11 @@ constexpr unsigned kLdsDG = 0, kLdsGORD = kMaxG * 8, kLdsDGF = (2 * kMaxG + 2) *
 // within +-1 % of five 8-byte rows and of three pairs (it is not store-bound at this level).  The gradient kernel's resolve rewrites the
 // pairs as (frac, 1/weight-sum) and (weight, code) for its replay passes.
 
-// The bits of OPT as ansfm_last_merge_launch reports them.  Value 4 (a late read of the bin boundary, retired) stays unused.
-constexpr int kOptTable = 1, kOptBfi = 2, kOptExit = 8, kOptOrient = 16;
-constexpr int kMergeOpt = kOptTable | kOptBfi | kOptExit | kOptOrient;
-// reported beside them, a launch parameter and not a bit of OPT: the lanes of a wave are grouped over rows (k_ck_overlap's argument lane_rows)
-constexpr int kOptLaneRows = 32;
-// likewise a launch parameter (bit 1 of the same argument, instantiations with kOptTable only): a wave whose lanes' merges all
-// sort row by row walks them without the head list (merge_rowmajor)
-constexpr int kOptRowMajor = 64;
-constexpr int kFlagLaneRows = 1, kFlagRowMajor = 2;      // k_ck_overlap's argument flags
-// a further bit of flags, set only with kFlagLaneRows and a table launch, reported by ansfm_last_merge_table_layout and not in the
-// trims: the table is read from its g-fastest copy (OverlapParams::lnKg, load_gas_rows)
-constexpr int kFlagTableGfast = 4;
-// The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
-__host__ __device__ constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
-// Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
-// lane whose columns are a.  One block's waves still fit the CU's LDS as before at every instantiated list length.
-__host__ __device__ constexpr int merge_wave_rows(int G, int opt) { return 2 * G + ((opt & kOptOrient) != 0 ? 2 : 1); }
-// The product table follows the float32 copy of DG; (col << 5) | row with col <= G (an exhausted row's sentinel key names
-// column G; its entry is read and never used), so (G + 1) * 32 doubles.  The per-wave rows come after it.
+// The bits of OPT (kOpt*, kMergeOpt, merge_opt_valid), the launch flags (kFlag*), the rows per wave (merge_wave_rows) and the
+// weight table's size (weight_table_bytes, kMaxBlockWaves) are in ansfm_merge_plan.h, where the launcher's plan reads them too.
+// The product table follows the float32 copy of DG; the per-wave rows come after it.
 constexpr unsigned kLdsWT = kLdsA;
-constexpr int kMaxBlockWaves = 8;
-__host__ __device__ constexpr unsigned weight_table_bytes(int G) { return (unsigned)(G + 1) * 32u * 8u; }
+static_assert(kLdsA == kMergeLdsTables, "the plan's LDS arithmetic");
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 constexpr unsigned kRecRow = 64u * 16u, kRecBin = 2u * kRecRow;
 

@@ -5,11 +5,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ansfm_merge_plan.h"       // kWave, kMaxG, kLaneNV and the other constants the launch plan shares with the kernels
 
 namespace ansfm {
-
-constexpr int kWave = 64;
-constexpr int kMaxG = 32;
 
 // ------------------------------------------------------------------------------------------------
 // ln-k table encoding.  k > 0  -> ln k (finite double)
@@ -194,7 +192,6 @@ __device__ __forceinline__ void load_gas(const OverlapParams &p, const LayerInte
 // Neighbouring rows of one wavenumber meet the same gases at nearby (p, T), so the lanes of a wave re-enter the head list at
 // similar depths and merge_pass_exit can stop where a wave of 64 unrelated wavenumbers cannot.  What was wave-uniform in the
 // other mapping -- the row's interpolation constants, its amounts, the corner rows of the table -- is per lane here.
-constexpr int kLaneNV = 2;
 static_assert(kLaneNV == 2 || kLaneNV == 4 || kLaneNV == 8, "group width");
 // The width a launch runs at is wave-uniform run-time data, 1 or kLaneNV ("pairs"), an argument of k_ck_overlap beside flags: the
 // functions below take its binary logarithm, nvs.  At width 1 a tile is 64 consecutive rows of ONE wavenumber, running on into

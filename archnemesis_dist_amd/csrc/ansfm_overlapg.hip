@@ -24,39 +24,25 @@ int launch_overlapg(ansfm_ctx *ctx, bool from_k, const double *kin, const double
     const size_t lds = (size_t)(2 * G + 1) * kWave * sizeof(double) + (size_t)(2 * kMaxG + 2) * sizeof(double) + kMaxG * sizeof(float) +
                        (sorted ? 0 : (size_t)2 * G * kWave);
     // blocks per CU: by the LDS size as it is (not rounded to the granule), up to 8; ANSFM_WAVES_PER_CU does not apply here
-    long grid = 0;
+    const long grid = merge_grid(ctx->num_cus, lds, 8, (long)n_models * (Wpad / kWave) * L);
     const int rc = merge_launch_begin(
-        ctx, p, lds, 8,
+        ctx, p, grid,
         {{&ctx->scratch, (size_t)6 * (G + 1) * kWave * sizeof(double)},
          {&ctx->gscratch, (3 + 2 * (size_t)NP1) * G * kWave * sizeof(double)},
-         {&ctx->perm, (size_t)((G * G + kCodesPerWord - 1) / kCodesPerWord) * kWave * sizeof(unsigned long long)}},
-        &grid);
+         {&ctx->perm, (size_t)((G * G + kCodesPerWord - 1) / kCodesPerWord) * kWave * sizeof(unsigned long long)}});
     if (rc) return rc;
     p.scratch = ctx->scratch.as<double>();
     pg.gscratch = ctx->gscratch.as<double>();
     pg.perm = ctx->perm.as<unsigned long long>();
-#define LAUNCH_OVG(D, FK)                                                                                           \
-    do {                                                                                                            \
-        if (ctx->delg_f32) {                                                                                        \
-            if (sorted) hipLaunchKernelGGL((k_ck_overlapg<D, true, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);   \
-            else hipLaunchKernelGGL((k_ck_overlapg<D, true, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);         \
-        } else {                                                                                                    \
-            if (sorted) hipLaunchKernelGGL((k_ck_overlapg<D, false, true>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);  \
-            else hipLaunchKernelGGL((k_ck_overlapg<D, false, false>), dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);        \
-        }                                                                                                           \
-    } while (0)
-#define LAUNCH_OVG_D(FK)                                              \
-    switch (merge_list_len(G)) {                                      \
-        case 8: LAUNCH_OVG(8, FK); break;                             \
-        case 10: LAUNCH_OVG(10, FK); break;                           \
-        case 16: LAUNCH_OVG(16, FK); break;                           \
-        case 20: LAUNCH_OVG(20, FK); break;                           \
-        default: LAUNCH_OVG(32, FK); break;                           \
-    }
     (void)from_k;                     // the kernel tests p.kin (run-time flag, see load_gas_g)
-    LAUNCH_OVG_D(false);
-#undef LAUNCH_OVG_D
-#undef LAUNCH_OVG
+    using GradKernel = void (*)(OverlapGParams);
+    const bool w32 = ctx->delg_f32 != 0;
+    const GradKernel kern = by_list_len(G, [&](auto d) -> GradKernel {
+        constexpr int D = decltype(d)::value;
+        if (w32) return sorted ? k_ck_overlapg<D, true, true> : k_ck_overlapg<D, true, false>;
+        return sorted ? k_ck_overlapg<D, false, true> : k_ck_overlapg<D, false, false>;
+    });
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave), lds, ctx->stream, pg);
     HIPCHK(hipGetLastError());
     return ANSFM_OK;
 }

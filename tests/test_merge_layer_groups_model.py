@@ -54,7 +54,7 @@ def queues(Wpad, R, nv):
 
 
 def test_group_width_in_the_source_is_one_of_the_modelled():
-    src = (Path(__file__).resolve().parents[1] / "archnemesis_dist_amd" / "csrc" / "ansfm_merge_common.hip.h").read_text()
+    src = (Path(__file__).resolve().parents[1] / "archnemesis_dist_amd" / "csrc" / "ansfm_merge_plan.h").read_text()
     nv = int(re.search(r"constexpr int kLaneNV = (\d+);", src).group(1))
     assert nv in NVS
 
