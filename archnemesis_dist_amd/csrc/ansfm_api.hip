@@ -639,9 +639,11 @@ int ansfm::fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int 
 // The gas stage of a gradient call on device arrays, for the gradient RT kernels and the transit kernels alike: tau and the
 // derivatives of the gradient merge (ctx->tau, ctx->dkbuf; calc_klblg + :3812-3814 for LBL tables) between ev[0] and ev[1], the
 // continuum and its gradients transposed to the wave-fastest layouts (cont_t [n][L][Wpad], dcont_t [n][NPAR][L][Wpad], or nullptr)
+// -- or, with `fused`, both formed in those layouts from the context's resident sources (k_tau_cont_rows, k_dtau_cont_rows over
+// all n * L layers; NVMR: the gas parameters of dTAUCON)
 int ansfm::grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp,
                           const double *amount, const double *taucont, const double *dtaucon, int NPAR, const double **cont_t,
-                          const double **dcont_t)
+                          const double **dcont_t, const ContCall *fused, int NVMR)
 {
     const int W = ctx->W, Wpad = ctx->Wpad, G = ctx->G, NP1 = ctx->S + 1;
     *cont_t = *dcont_t = nullptr;
@@ -649,7 +651,12 @@ int ansfm::grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     int rc;
     if ((rc = gas_prep(ctx, n_models * L, lay_press_pa, lay_temp))) return rc;
-    if (taucont) {
+    if (fused) {
+        if ((rc = launch_tau_cont_rows(ctx, n_models * L, nullptr, *fused))) return rc;
+        if ((rc = launch_dtau_cont_rows(ctx, n_models, L, NVMR, NPAR, *fused))) return rc;
+        *cont_t = ctx->cont_t.as<double>();
+        *dcont_t = ctx->dcont_t.as<double>();
+    } else if (taucont) {
         HIPCHK(ctx->cont_t.reserve((size_t)n_models * L * Wpad * sizeof(double)));
         launch_w_to_last(ctx->stream, (unsigned)n_models, taucont, ctx->cont_t.as<double>(), W, Wpad, 1, L, 0, 0.0, (size_t)W * L, (size_t)L * Wpad);
         *cont_t = ctx->cont_t.as<double>();
@@ -671,14 +678,16 @@ namespace {
 // What the thermal, transmission, single-scattering and gradient entry points take, under the names and in the layouts of
 // include/ansfm.h.  The extern "C" function fills it once and everything below reads it (as MsCall in ansfm_scatter.hip); what
 // an entry does not take stays null or 0.  The arrays are host or device pointers as the entry says; igas_map is a host
-// pointer always, ray_totam / ray_f4 and the arrays of a fused continuum device pointers always.
+// pointer always, ray_totam / ray_f4 and the arrays of a fused continuum device pointers in every forward entry (the gradient
+// entry with a fused continuum has a host variant, ansfm_cirsradg_ck_thermal_cont: stage_call uploads them with the rest).
 struct RtCall {
     int ISPACE = 0, n_models = 1, L = 0;
     const double *lay_press_pa = nullptr, *lay_temp = nullptr, *amount = nullptr;
     const double *taucont = nullptr, *tausca = nullptr, *phase = nullptr, *dtaucon = nullptr;
     int ray_mode = 0;                       // != 0: the continuum has Rayleigh scattering, formed from the two arrays
     const double *ray_totam = nullptr, *ray_f4 = nullptr;
-    // ansfm_cirsrad_ck_thermal_cont_dev: the continuum is (TAUCIA + TAUDUST) + TAURAY from the context's resident sources
+    // ansfm_cirsrad_ck_thermal_cont_dev, ansfm_cirsradg_ck_thermal_cont(_dev): the continuum is (TAUCIA + TAUDUST) + TAURAY (and
+    // its gradients dTAUCON) from the context's resident sources
     int fused_cont = 0, use_cia = 0, use_dust = 0;
     const double *lay_q = nullptr, *lay_frac = nullptr, *lay_delh = nullptr, *lay_cont = nullptr;   // the column: ray_totam
     int NVMR = 0, NPAR = 0;
@@ -709,6 +718,8 @@ RtCall stage_call(ansfm_ctx *ctx, const RtCall &h, int *rc)
     d.EMISSIVITY = st.up(h.EMISSIVITY, W); d.SOLFLUX = st.up(h.SOLFLUX, W); d.REFLECTANCE = st.up(h.REFLECTANCE, W);
     d.BRDF = st.up(h.BRDF, W * h.P); d.SOL_ANG = st.up(h.SOL_ANG, h.P); d.EMISS_ANG = st.up(h.EMISS_ANG, h.P);
     d.xfac = st.up(h.xfac, W);
+    d.lay_q = st.up(h.lay_q, nl * h.NVMR); d.lay_frac = st.up(h.lay_frac, nl); d.ray_totam = st.up(h.ray_totam, nl);
+    d.lay_delh = st.up(h.lay_delh, nl); d.lay_cont = st.up(h.lay_cont, nl * ctx->dust_n); d.ray_f4 = st.up(h.ray_f4, nl * 4);
     *rc = st.rc;
     return d;
 }
@@ -1356,7 +1367,16 @@ static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c)
     HIPCHK(ctx->dspec_i.reserve((size_t)n_models * P * NPAR * LIMAX * Wpad * sizeof(double)));
     int rc;
     const double *cont_t = nullptr, *dcont_t = nullptr;
-    if ((rc = grad_gas_stage(ctx, n_models, L, c.lay_press_pa, c.lay_temp, c.amount, c.taucont, c.dtaucon, NPAR, &cont_t, &dcont_t))) return rc;
+    ContCall k;
+    if (c.fused_cont) {
+        // CIA, aerosol and Rayleigh opacity of every layer and their gradients, from the resident sources
+        k.ISPACE = c.ISPACE; k.use_cia = c.use_cia; k.use_dust = c.use_dust; k.ray_mode = c.ray_mode;
+        k.temp = c.lay_temp; k.q = c.lay_q; k.frac = c.lay_frac; k.totam = c.ray_totam; k.delh = c.lay_delh; k.cont = c.lay_cont;
+        k.f4 = c.ray_f4;
+    }
+    if ((rc = grad_gas_stage(ctx, n_models, L, c.lay_press_pa, c.lay_temp, c.amount, c.taucont, c.dtaucon, NPAR, &cont_t, &dcont_t,
+                             c.fused_cont ? &k : nullptr, c.NVMR)))
+        return rc;
     RtGParams q;
     memset(&q, 0, sizeof q);
     rt_params_of_call(ctx, c, q.r);
@@ -1407,6 +1427,46 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
     return cirsradg_ck_thermal_dev_impl(ctx, c);
 }
 
+// What ansfm_cirsradg_ck_thermal_cont and its _dev twin refuse before anything is staged or launched, and the fields of the
+// record that describe the fused continuum
+static int grad_fused_cont(ansfm_ctx *ctx, RtCall &c, int use_cia, const double *lay_q, const double *lay_frac, const double *lay_totam,
+                           const double *lay_delh, int use_dust, const double *lay_cont, int ray_mode, const double *f4)
+{
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsradg: upload a k-table first");
+    if (ctx->dcont_gas_L) {
+        // the Rayleigh term is summed into the dense gradients here, (cia + ray) * X: a shared one would be added as a second
+        // product
+        ctx->dcont_gas_L = 0;
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: a shared gas gradient (ansfm_set_shared_gas_gradient) is pending; the "
+                                "fused continuum forms the Rayleigh term itself (ray_mode).  It has been cancelled.");
+    }
+    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
+        (!use_cia && !use_dust && !ray_mode) || ((use_cia || ray_mode) && !lay_totam) ||
+        (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont) || c.NVMR < 0 || c.NPAR < c.NVMR + 2)
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: bad argument (at least one of use_cia, use_dust, ray_mode = IRAY 1, 2, 4 "
+                                "or 12; the per-layer arrays of every term that is used; NPAR >= NVMR + 2)");
+    if (c.NVMR + 2 > ANSFM_MAX_CONT_GRAD_SLOTS)
+        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsradg_ck_thermal_cont: NVMR + 2 <= " + std::to_string(ANSFM_MAX_CONT_GRAD_SLOTS) +
+                                        " (the gradient slots of a thread are held in LDS)");
+    if (use_cia && !ctx->cia_on)
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: no CIA source on this table's grid (ansfm_upload_cia after the table)");
+    if (use_cia && ctx->cia_ispace != c.ISPACE)
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: the CIA source was uploaded for the other ISPACE");
+    if (use_cia && (c.NVMR != ctx->cia_NVMR || c.NVMR < 2))
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: NVMR is not the number of gases the CIA source was uploaded for (" +
+                                    std::to_string(ctx->cia_NVMR) + "; at least 2: calc_tau_cia writes slot NVMR - 2)");
+    if (use_dust && !ctx->dust_n)
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    if (use_dust && c.NPAR != c.NVMR + 2 + ctx->dust_n)
+        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: NPAR is not NVMR + 2 + NDUST of the uploaded aerosol source (" +
+                                    std::to_string(ctx->dust_n) + " populations)");
+    c.fused_cont = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0;
+    c.lay_q = use_cia ? lay_q : nullptr; c.lay_frac = use_cia ? lay_frac : nullptr; c.lay_delh = use_cia ? lay_delh : nullptr;
+    c.lay_cont = use_dust ? lay_cont : nullptr;
+    c.ray_mode = ray_mode; c.ray_totam = (use_cia || ray_mode) ? lay_totam : nullptr; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    return ANSFM_OK;
+}
+
 static int cirsradg_ck_thermal_host(ansfm_ctx *ctx, const RtCall &h)
 {
     CHECK_CTX(ctx);
@@ -1445,6 +1505,42 @@ int ansfm_cirsradg_ck_thermal(ansfm_ctx *ctx, int ISPACE, int n_models, int L, c
     c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY;
     c.xfac = xfac; c.SPECOUT = SPECOUT; c.dSPECOUT = dSPECOUT; c.dTSURF = dTSURF;
     return cirsradg_ck_thermal_host(ctx, c);
+}
+
+int ansfm_cirsradg_ck_thermal_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                   const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                   const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                   const double *lay_cont, int ray_mode, const double *f4, int NVMR, int NPAR,
+                                   const int32_t *igas_map, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                   const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                   const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF)
+{
+    CHECK_CTX(ctx);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.NVMR = NVMR; c.NPAR = NPAR; c.igas_map = igas_map; c.P = P; c.LIMAX = LIMAX;
+    c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY;
+    c.xfac = xfac; c.SPECOUT = SPECOUT; c.dSPECOUT = dSPECOUT; c.dTSURF = dTSURF;
+    const int rc = grad_fused_cont(ctx, c, use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4);
+    return rc ? rc : cirsradg_ck_thermal_host(ctx, c);
+}
+
+int ansfm_cirsradg_ck_thermal_cont_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                       const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                       const double *lay_cont, int ray_mode, const double *f4, int NVMR, int NPAR,
+                                       const int32_t *igas_map_host, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                       const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                       const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF)
+{
+    CHECK_CTX(ctx);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.NVMR = NVMR; c.NPAR = NPAR; c.igas_map = igas_map_host; c.P = P; c.LIMAX = LIMAX;
+    c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY;
+    c.xfac = xfac; c.SPECOUT = SPECOUT; c.dSPECOUT = dSPECOUT; c.dTSURF = dTSURF;
+    const int rc = grad_fused_cont(ctx, c, use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4);
+    return rc ? rc : cirsradg_ck_thermal_dev_impl(ctx, c);
 }
 
 int ansfm_cirsradg_ck_transmission(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa,

@@ -72,9 +72,10 @@ __host__ __device__ inline CiaLayer cia_layer(double temp1, double frac1, double
 }
 
 // sum over the pairs of k_cia q1 q2 at wavenumber x (index w of the k_co2 / k_n2n2 / k_n2h2 vectors) for a layer of record c
-// and mixing ratios q[NVMR]; TAUCIA = the sum * c.xfac.  d: the layer's NVMR + 2 gradient slots (zeroed), or nullptr.  One body
-// for k_tau_cia and k_tau_cont_rows: the two give the same bits.
-__device__ __forceinline__ double cia_sum(const CiaParams &p, const CiaLayer &c, double x, int w, const double *q, double *d)
+// and mixing ratios q[NVMR]; TAUCIA = the sum * c.xfac.  d: the layer's NVMR + 2 gradient slots (zeroed), ds doubles apart, or
+// nullptr.  One body for k_tau_cia, k_tau_cont_rows and k_dtau_cont_rows: they give the same bits.
+__device__ __forceinline__ double cia_sum(const CiaParams &p, const CiaLayer &c, double x, int w, const double *q, double *d,
+                                          int ds = 1)
 {
     double sum1 = 0.0;
     if (p.covers) {
@@ -101,28 +102,28 @@ __device__ __forceinline__ double cia_sum(const CiaParams &p, const CiaLayer &c,
             const double dkdT = ((dk[1] - dk[0]) / dx) * (x - xlo) + dk[0];
             sum1 = sum1 + k_cia * q[g1] * q[g2];
             if (d) {
-                d[g1] = d[g1] + q[g2] * k_cia;
-                d[g2] = d[g2] + q[g1] * k_cia;
-                d[p.NVMR - 2] = d[p.NVMR - 2] + dkdT * q[g1] * q[g2];      // slot NVMR-2, as the reference (:4695)
+                d[g1 * ds] = d[g1 * ds] + q[g2] * k_cia;
+                d[g2 * ds] = d[g2 * ds] + q[g1] * k_cia;
+                d[(p.NVMR - 2) * ds] = d[(p.NVMR - 2) * ds] + dkdT * q[g1] * q[g2];      // slot NVMR-2, as the reference (:4695)
             }
         }
     }
     if (p.ico2 >= 0) {
         const double k = p.k_co2[w];
         sum1 = sum1 + k * q[p.ico2] * q[p.ico2];
-        if (d) d[p.ico2] = d[p.ico2] + 2. * q[p.ico2] * k;
+        if (d) d[p.ico2 * ds] = d[p.ico2 * ds] + 2. * q[p.ico2] * k;
     }
     if (p.in2 >= 0) {
         const double k = p.k_n2n2[w];
         sum1 = sum1 + k * q[p.in2] * q[p.in2];
-        if (d) d[p.in2] = d[p.in2] + 2. * q[p.in2] * k;
+        if (d) d[p.in2 * ds] = d[p.in2 * ds] + 2. * q[p.in2] * k;
     }
     if (p.in2 >= 0 && p.ih2 >= 0) {
         const double k = p.k_n2h2[w];
         sum1 = sum1 + k * q[p.in2] * q[p.ih2];
         if (d) {
-            d[p.ih2] = d[p.ih2] + q[p.in2] * k;
-            d[p.in2] = d[p.in2] + q[p.ih2] * k;
+            d[p.ih2 * ds] = d[p.ih2 * ds] + q[p.in2] * k;
+            d[p.in2 * ds] = d[p.in2 * ds] + q[p.ih2] * k;
         }
     }
     return sum1;
@@ -399,6 +400,71 @@ __global__ __launch_bounds__(256) void k_tau_cont_rows(ContRowsParams p)
         tau = any ? tau + ray : ray;
     }
     *out = tau;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The gradients of that continuum, dTAUCON of calculate_layer_opacity (:3940-3981), from the same resident sources and
+// straight in the layout the gradient RT reads: dcont[m][kpar][l][w] ([n][NPAR][L][Wpad], zero beyond W), NPAR = NVMR + 2 +
+// NDUST.  Row r = m * L + l is layer r of the per-layer arrays (no work list: a gradient call is one state, or a few).
+//     kpar < NVMR            (d[kpar] * xfac) / TOTAM[l]  (+ the Rayleigh k, dTAURAY, of every gas: :3955-3957)
+//     kpar == NVMR           d[NVMR] * xfac: calc_tau_cia never fills the temperature slot, its dkdT term lands in NVMR - 2 (:4741)
+//     kpar == NVMR + 1 + i   kext_w[i][w] * 1e-4: the raw dTAUDUST1, neither nan_to_num nor clip (:3966 acts on the opacity only)
+//     kpar == NPAR - 1       0 (para-H2, flagh2p = False)
+// d is what cia_sum accumulates for k_tau_cia; every term is rounded as the array-level kernels and NumPy's assembly round it:
+// d * xfac to memory, a true division by TOTAM, then the sum with the Rayleigh term (the first add, to zero, is exact).  An
+// absent term is left out.  cia_sum indexes d by the gas: the thread's NVMR + 2 slots are a column of LDS, blockDim.x doubles
+// apart (a private array would go to scratch memory), so a wave's ds_read_b64 of one slot covers consecutive banks.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kDContBlock = 128;    // threads: (NVMR + 2) * 128 * 8 bytes of dynamic LDS, 48 KiB at ANSFM_MAX_CONT_GRAD_SLOTS
+
+struct DContRowsParams {
+    ContRowsParams c;           // as k_tau_cont_rows takes it (work, out unused); c.lay filled by k_cia_rows_prep for these rows
+    double *dout;               // [n][NPAR][L][Wpad]
+    int L, NVMR, NPAR;
+};
+
+// One thread per (row, wavenumber), a block within one row (blockIdx.x): every parameter's store is coalesced along the wavenumbers
+__global__ __launch_bounds__(kDContBlock) void k_dtau_cont_rows(DContRowsParams p)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double dcont_slots[];                          // [NVMR + 2][blockDim.x]
+    const ContRowsParams &c = p.c;
+    const int r = blockIdx.x, w = blockIdx.y * blockDim.x + threadIdx.x;
+    if (w >= c.Wpad) return;
+    const int m = r / p.L, l = r - m * p.L;
+    const size_t sk = (size_t)p.L * c.Wpad;                          // from one parameter to the next
+    double *out = p.dout + ((size_t)m * p.NPAR * p.L + l) * c.Wpad + w;
+    if (w >= c.W) {
+        for (int k = 0; k < p.NPAR; ++k) out[k * sk] = 0.0;
+        return;
+    }
+    const int ds = blockDim.x;
+    double *d = dcont_slots + threadIdx.x;
+    const double v = c.wave[w];
+    double xfac = 0.0, totam = 1.0;
+    if (c.use_cia) {
+        for (int s = 0; s < p.NVMR + 2; ++s) d[s * ds] = 0.0;
+        const CiaLayer cl = c.lay[r];
+        const double x = c.ispace == 0 ? v : 1.e4 / v;               // :4565
+        cia_sum(c.cia, cl, x, w, c.cia.q + (size_t)r * p.NVMR, d, ds);
+        xfac = cl.xfac;
+        totam = c.totam[r];
+    }
+    const double ray = c.ray_mode ? rayleigh_k(c.ray_mode, c.ispace, v, c.ray_mode == 4 ? c.f4 + (size_t)r * 4 : nullptr) : 0.0;
+    for (int k = 0; k < p.NVMR; ++k) {
+        double g = 0.0;
+        if (c.use_cia) {
+            const double dx = d[k * ds] * xfac;                      // dTAUCIA as k_tau_cia stores it
+            g = dx / totam;
+        }
+        if (c.ray_mode) g = c.use_cia ? g + ray : ray;
+        out[k * sk] = g;
+    }
+    out[p.NVMR * sk] = c.use_cia ? d[p.NVMR * ds] * xfac : 0.0;
+    for (int k = p.NVMR + 1; k < p.NPAR; ++k) {
+        const int i = k - (p.NVMR + 1);
+        out[k * sk] = i < c.NDUST ? c.kext_w[(size_t)i * c.Wpad + w] * 1.0e-4 : 0.0;
+    }
 }
 
 }  // namespace ansfm

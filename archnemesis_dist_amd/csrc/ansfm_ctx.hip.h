@@ -145,7 +145,7 @@ struct ansfm_ctx {
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
     long ms_windows = 0, ms_window_w = 0;          // spectral windows of phase matrices / Hansen factors of the last scattering call, their size
-    DevBuf hb[24];  // staging buffers of the host-pointer entry points
+    DevBuf hb[25];  // staging buffers of the host-pointer entry points
     // runtime line-by-line: the opacity of a gas, summed in HBM (ansfm_lbl_accum_*); its grid and (T, p) points [2][L]
     DevBuf acc, acc_grid, acc_tp;
     int acc_nw = 0, acc_L = 0;           // 0: no accumulator begun
@@ -235,10 +235,17 @@ int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *
                const DedupCols *cols, DedupRows *out);
 // a table has been uploaded: the continuum sources on the old grid go
 inline void clear_continuum_sources(ansfm_ctx *ctx) { ctx->cia_on = 0; ctx->dust_n = 0; }
+// a continuum formed from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust) and the Rayleigh
+// parametrisations: the arrays are device pointers over the n * L layers of the call
+struct ContCall {
+    int ISPACE = 0, use_cia = 0, use_dust = 0, ray_mode = 0;
+    const double *temp = nullptr, *q = nullptr, *frac = nullptr, *totam = nullptr, *delh = nullptr, *cont = nullptr, *f4 = nullptr;
+};
 // ansfm_api.hip, what the gradient RT entries and the transit entry (ansfm_transit.hip) share (described where they are
 // defined): the gas stage of a gradient call, the merge slot behind every parameter, the end of a call without a generic rerun
 int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
-                   const double *taucont, const double *dtaucon, int NPAR, const double **cont_t, const double **dcont_t);
+                   const double *taucont, const double *dtaucon, int NPAR, const double **cont_t, const double **dcont_t,
+                   const ContCall *fused = nullptr, int NVMR = 0);
 int fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int NVMR, int NPAR, unsigned gas_mask,
                        signed char *slot_of_param);
 int check_unsorted(ansfm_ctx *ctx);
@@ -249,12 +256,12 @@ void launch_lblrt_tau(ansfm_ctx *ctx, int n, int L, int m0, const double *amount
 void launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int ISPACE, const int32_t *slot_rows, const double *ray_totam,
                               const double *ray_f4);
 // ansfm_ops.hip: k_cia_rows_prep + k_tau_cont_rows for the thermal branch, into ctx->cont_t [rows][Wpad]: (TAUCIA + TAUDUST) +
-// TAURAY of the rows from the resident sources; the arrays are device pointers over the n * L layers of the call
-struct ContCall {
-    int ISPACE = 0, use_cia = 0, use_dust = 0, ray_mode = 0;
-    const double *temp = nullptr, *q = nullptr, *frac = nullptr, *totam = nullptr, *delh = nullptr, *cont = nullptr, *f4 = nullptr;
-};
+// TAURAY of the rows from the resident sources (ContCall, above)
 int launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c);
+// ansfm_ops.hip: k_dtau_cont_rows for the gradient thermal branch, into ctx->dcont_t [n][NPAR][L][Wpad]: dTAUCON of the n * L
+// layers from the resident sources.  After launch_tau_cont_rows(ctx, n * L, nullptr, c) on the same stream: the CIA records in
+// ctx->cia_lay are that launch's.
+int launch_dtau_cont_rows(ansfm_ctx *ctx, int n_models, int L, int NVMR, int NPAR, const ContCall &c);
 
 // ansfm_overlap.hip / ansfm_overlapg.hip: k_ck_overlap (or k_ck_overlap32) and k_ck_overlapg over n_models x L layers into tau
 // (and dk); from_k: the array-level seams' k (and dkdT) instead of the table; generic: per-lane sort first (rerun of an unsorted call)

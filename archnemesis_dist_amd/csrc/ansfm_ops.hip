@@ -16,13 +16,13 @@ void ansfm::launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int
                        ray_mode, ISPACE, ctx->d_wave.as<double>(), slot_rows, ray_totam, ray_f4, ctx->cont_t.as<double>());
 }
 
-int ansfm::launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c)
+// The arguments of k_cia_rows_prep / k_tau_cont_rows / k_dtau_cont_rows for `rows` rows of the call c, from the context's
+// resident sources; reserves the rows' CIA records
+static int cont_rows_params(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, ContRowsParams &p)
 {
     const int W = ctx->W, Wpad = ctx->Wpad;
-    HIPCHK(ctx->cont_t.reserve((size_t)rows * Wpad * sizeof(double)));
-    ContRowsParams p;
     memset(&p, 0, sizeof p);
-    p.wave = ctx->d_wave.as<double>(); p.work = slot_rows; p.out = ctx->cont_t.as<double>();
+    p.wave = ctx->d_wave.as<double>(); p.work = slot_rows;
     p.rows = rows; p.W = W; p.Wpad = Wpad; p.ispace = c.ISPACE; p.ray_mode = c.ray_mode;
     p.totam = c.totam; p.f4 = c.f4;
     if (c.use_dust) { p.kext_w = ctx->dust_kext.as<double>(); p.cont = c.cont; p.NDUST = ctx->dust_n; }
@@ -41,10 +41,40 @@ int ansfm::launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_ro
         p.temp = c.temp; p.frac = c.frac; p.delh = c.delh;
         p.lay = ctx->cia_lay.as<CiaLayer>();
         k.lay = p.lay;
+    }
+    return ANSFM_OK;
+}
+
+int ansfm::launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c)
+{
+    HIPCHK(ctx->cont_t.reserve((size_t)rows * ctx->Wpad * sizeof(double)));
+    ContRowsParams p;
+    int rc;
+    if ((rc = cont_rows_params(ctx, rows, slot_rows, c, p))) return rc;
+    p.out = ctx->cont_t.as<double>();
+    if (c.use_cia) {
         hipLaunchKernelGGL(k_cia_rows_prep, dim3(nblk((size_t)rows, 64)), dim3(64), 0, ctx->stream, p);
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_tau_cont_rows, dim3((unsigned)rows, nblk((size_t)Wpad, 256)), dim3(256), 0, ctx->stream, p);
+    hipLaunchKernelGGL(k_tau_cont_rows, dim3((unsigned)rows, nblk((size_t)ctx->Wpad, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    return ANSFM_OK;
+}
+
+int ansfm::launch_dtau_cont_rows(ansfm_ctx *ctx, int n_models, int L, int NVMR, int NPAR, const ContCall &c)
+{
+    const int rows = n_models * L;
+    if (NVMR + 2 > ANSFM_MAX_CONT_GRAD_SLOTS)
+        FAIL(ANSFM_ERR_UNSUPPORTED, "the fused continuum gradients hold NVMR + 2 <= " + std::to_string(ANSFM_MAX_CONT_GRAD_SLOTS) +
+                                        " slots per thread in LDS");
+    HIPCHK(ctx->dcont_t.reserve((size_t)n_models * NPAR * L * ctx->Wpad * sizeof(double)));
+    DContRowsParams p;
+    int rc;
+    if ((rc = cont_rows_params(ctx, rows, nullptr, c, p.c))) return rc;
+    p.dout = ctx->dcont_t.as<double>();
+    p.L = L; p.NVMR = NVMR; p.NPAR = NPAR;
+    const size_t lds = c.use_cia ? (size_t)(NVMR + 2) * kDContBlock * sizeof(double) : 0;      // the slots of cia_sum
+    hipLaunchKernelGGL(k_dtau_cont_rows, dim3((unsigned)rows, nblk((size_t)ctx->Wpad, kDContBlock)), dim3(kDContBlock), lds, ctx->stream, p);
     HIPCHK(hipGetLastError());
     return ANSFM_OK;
 }

@@ -780,6 +780,85 @@ class AnsfmEngine:
             self._chain_dspec = _fingerprint(dspec[0])
         return (spec[0], dspec[0], dts[0]) if single else (spec, dspec, dts)
 
+    def cirsradg_ck_thermal_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, NVMR, NPAR,
+                                 igas_map, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None,
+                                 gradients_on_device=False, variant=None):
+        """`cirsradg_ck_thermal` with the continuum and its gradients (dTAUCON of calculate_layer_opacity :3940-3981) formed
+        inside the call from the resident sources (upload_cia, upload_dust) and the Rayleigh parametrisations, in place of
+        taucont / dtaucon / dtau_every_gas: q (n, L, NVMR) = PP / PRESS with FRAC, DELH (n, L) switch CIA on (None: off); CONT
+        (n, L, NDUST) switches the aerosols on (None: off); IRAY 0 or as in calc_tau_rayleigh with f4 (n, L, 4) (rayleigh_f4) for
+        IRAY 4; TOTAM (n, L) for CIA and Rayleigh.  Host arrays, the leading axis optional for one model.  Same bits as
+        calc_tau_cia(with_grad=True) + calc_tau_dust + calc_tau_rayleigh assembled on the host and passed to
+        `cirsradg_ck_thermal`.  Returns what that returns; gradients_on_device as there.  ValueError for a source that is not
+        resident, an NVMR other than the CIA source's, an NPAR other than NVMR + 2 + the aerosol source's NDUST;
+        NotImplementedError for NVMR > 46."""
+        what = "cirsradg_ck_thermal_cont"
+        W, G, NP, NT, S = self.dims
+        lay_press_pa = _np(lay_press_pa)
+        single = lay_press_pa.ndim == 1
+        lp = np.atleast_2d(lay_press_pa); n, L = lp.shape
+        lt = _np(np.atleast_2d(_np(lay_temp)))
+        am = _np(amount).reshape(n, S, L)
+        NVMR, NPAR = int(NVMR), int(NPAR)
+        mode = 12 if variant == "v" else int(IRAY)
+        use_cia, use_dust = q is not None, CONT is not None
+        opt = lambda a, shape: None if a is None else _np(a).reshape(shape)
+        qq = opt(q, (n, L, NVMR)); fr = opt(FRAC, (n, L)); tot = opt(TOTAM, (n, L)); dh = opt(DELH, (n, L))
+        co = None if CONT is None else _np(CONT).reshape(n, L, -1)
+        ff = opt(f4, (n, L, 4)) if mode == 4 else None
+        if use_dust and co.shape[2] != getattr(self, "dust_n", co.shape[2]):
+            raise ValueError(what + ": CONT must be (n, NLAY, NDUST) with the NDUST of upload_dust")
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        SC = _np(np.broadcast_to(_np(SCALE).reshape(-1, LIMAX, P), (n, LIMAX, P)))
+        ET = _np(np.broadcast_to(_np(EMTEMP).reshape(-1, LIMAX, P), (n, LIMAX, P)))
+        TS = _np(np.broadcast_to(np.atleast_1d(_np(TSURF)), (n,)))
+        ig = _np(igas_map, np.int32)
+        on_dev = bool(gradients_on_device) and n == 1
+        spec = np.empty((n, W, P)); dts = np.empty((n, W, P))
+        dspec = None if on_dev else np.empty((n, W, NPAR, LIMAX, P))
+        self._chain_dspec = None
+        rc = self._lib.ansfm_cirsradg_ck_thermal_cont(
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(qq), _ptr(fr), _ptr(tot), _ptr(dh),
+            int(use_dust), _ptr(co), mode, _ptr(ff), NVMR, NPAR, _ptr(ig), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET),
+            _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(xfac)), _ptr(spec), _ptr(dspec), _ptr(dts))
+        self._check(rc, what)
+        if on_dev:
+            self._chain_dspec = ("device", W, NPAR, LIMAX, P)
+            return (spec[0], None, dts[0]) if single else (spec, None, dts)
+        if n == 1:                       # device copy usable by map2pro: hand the host array out read-only
+            dspec.flags.writeable = False
+            self._chain_dspec = _fingerprint(dspec[0])
+        return (spec[0], dspec[0], dts[0]) if single else (spec, dspec, dts)
+
+    def cirsradg_ck_thermal_cont_dev(self, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4,
+                                     NVMR, NPAR, igas_map, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, xfac, SPECOUT,
+                                     dSPECOUT, dTSURF, variant=None):
+        """`cirsradg_ck_thermal_cont` on contiguous float64 torch device tensors (igas_map: a host array; NLAYIN, LAYINC int32
+        tensors); asynchronous.  q, FRAC, TOTAM, DELH, CONT, f4 as `cirsrad_ck_thermal_cont_dev` takes them, with the same shape
+        checks; SPECOUT (n, W, P), dSPECOUT (n, W, NPAR, LIMAX, P), dTSURF (n, W, P) are filled."""
+        what = "cirsradg_ck_thermal_cont_dev"
+        mode = 12 if variant == "v" else int(IRAY)
+        use_cia, use_dust = q is not None, CONT is not None
+        for a, shape in ((q, (n_models, L, getattr(self, "cia_nvmr", -1))), (FRAC, (n_models, L)), (TOTAM, (n_models, L)),
+                         (DELH, (n_models, L)), (CONT, (n_models, L, getattr(self, "dust_n", -1))), (f4, (n_models, L, 4))):
+            if a is not None and -1 not in shape and (tuple(a.shape) != shape or not a.is_contiguous()):
+                raise ValueError(what + ": expected a contiguous tensor of shape %s, got %s" % (shape, tuple(a.shape)))
+        W = self.dims[0]
+        for a, shape in ((SPECOUT, (n_models, W, P)), (dSPECOUT, (n_models, W, int(NPAR), LIMAX, P)), (dTSURF, (n_models, W, P))):
+            if a is None or tuple(a.shape) != shape or not a.is_contiguous():
+                raise ValueError(what + ": the outputs must be contiguous tensors, here of shape %s" % (shape,))
+        ig = _np(igas_map, np.int32)
+        self._chain_dspec = None
+        rc = self._lib.ansfm_cirsradg_ck_thermal_cont_dev(
+            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), int(use_cia), _ptr(q),
+            _ptr(FRAC), _ptr(TOTAM), _ptr(DELH), int(use_dust), _ptr(CONT), mode, _ptr(f4) if mode == 4 else None, int(NVMR), int(NPAR),
+            _ptr(ig), int(P), int(LIMAX), _ptr(NLAYIN), _ptr(LAYINC), _ptr(SCALE), _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY),
+            _ptr(xfac), _ptr(SPECOUT), _ptr(dSPECOUT), _ptr(dTSURF))
+        self._check(rc, what)
+
     def cirsrad_ck_thermal_dev(self, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucont, P, LIMAX,
                                NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, SOLFLUX, REFLECTANCE, SOL_ANG,
                                EMISS_ANG, xfac, SPECOUT):

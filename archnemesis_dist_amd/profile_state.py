@@ -388,7 +388,7 @@ class BatchedCKThermalModel:
         return out.reshape(n, self.W * P_)
 
     # ---- analytic route: nemesisfmg for the same configuration ----------------------------------------------------
-    def jacobian_analytic(self, X0=None):
+    def jacobian_analytic(self, X0=None, sources=False):
         """YN (NY,), KK (NY, NX) at the state X0 (default: the state's own XN) by analytic gradients -- what
         `nemesisfmg` does (ForwardModel_0.py:593-779): `layer_averageg` (layer properties + DTE / DAM / DCO),
         `CIRSrad(return_grad=True)` (k_ck_overlapg + k_thermal_rtg), `map2pro` (layers -> levels, :705) and `map2xvec`
@@ -400,10 +400,19 @@ class BatchedCKThermalModel:
         respect to TSURF only) -- a finite difference through `layer_average` sees both.  The Rayleigh continuum enters the
         gradients the reference's way (calculate_layer_opacity :3952-3957: dTAURAY, the cross section per unit column, is
         added to EVERY gas's parameter; its dependence on the composition, IRAY = 4, is not differentiated).
-        CIA and aerosol sources (`cia`, `dust`) are not in the analytic route: NotImplementedError when one is set."""
-        if self.cia is not None or self.dust is not None:
-            raise NotImplementedError("jacobian_analytic: CIA and aerosol sources are not part of the analytic gradients; "
-                                      "use the numerical Jacobian (jacobian_nemesis_batched)")
+        CIA and aerosol sources (`cia`, `dust`) enter with sources=True: the continuum and its gradients (dTAUCON of
+        calculate_layer_opacity :3940-3981, Rayleigh term included) are formed on the device from the resident sources
+        (`upload_sources`, `AnsfmEngine.cirsradg_ck_thermal_cont`), with the reference's own departures from the true
+        derivative: no temperature gradient of CIA (its dk/dT term lands in the slot of gas NVMR - 2) and the raw cross section
+        for an aerosol population whose opacity the clip to [0, 1e20] has zeroed.  `extra_continuum` cannot be combined with
+        them.  With the default, sources=False, a model that has a source raises NotImplementedError as it always did."""
+        with_sources = self.cia is not None or self.dust is not None
+        if with_sources and not sources:
+            raise NotImplementedError("jacobian_analytic: CIA and aerosol sources enter the analytic gradients with sources=True "
+                                      "only; pass it, or use the numerical Jacobian (jacobian_nemesis_batched)")
+        if with_sources and self.extra is not None:
+            raise NotImplementedError("jacobian_analytic(sources=True): extra_continuum cannot be combined with CIA and aerosol "
+                                      "sources (the fused continuum has no slot for it)")
         eng, st, la, ge = self.eng, self.state, self.lay, self.geo
         X0 = st.XN if X0 is None else np.asarray(X0, float)
         T, VMR = st.profiles(X0[None])
@@ -422,7 +431,10 @@ class BatchedCKThermalModel:
         NPAR = NVMR + 2 + NDUST
         P_ = path.NPATH
         cont, dcont = self.extra, None
-        if self.IRAY != 0:
+        if with_sources:
+            if not self._sources_on:
+                self.upload_sources()
+        elif self.IRAY != 0:
             tauray, dtauray = eng.calc_tau_rayleigh(self.IRAY, self.ISPACE, eng.WAVE, lay["TOTAM"], ID=self.ID, ISO=self.ISO,
                                                     VMR=lay["PP"] / lay["PRESS"][:, None])
             cont = tauray if cont is None else cont + tauray
@@ -433,7 +445,8 @@ class BatchedCKThermalModel:
         eng.set_gradient_gases([i for i, col in enumerate(self.igas_map) if int(col) in wanted],
                                temperature=any(kind == "T" for kind, _ in st.blocks))
         try:
-            spec = self._analytic_chain(eng, lay, amount, path, NVMR, NPAR, NDUST, NPRO, P_)
+            chain = self._analytic_chain_sources if with_sources else self._analytic_chain
+            spec = chain(eng, lay, amount, path, NVMR, NPAR, NDUST, NPRO, P_)
         finally:
             eng.set_gradient_gases(None)
         xmap = np.zeros((st.NX, NPAR, NPRO))
@@ -455,4 +468,16 @@ class BatchedCKThermalModel:
                     to_host=False)
         return spec
 
-
+    def _analytic_chain_sources(self, eng, lay, amount, path, NVMR, NPAR, NDUST, NPRO, P_):
+        # the same with the continuum and dTAUCON formed inside the call from the resident sources
+        cia, dust = self.cia is not None, self.dust is not None
+        q = lay["PP"] / lay["PRESS"][:, None]
+        f4 = eng.rayleigh_f4(self.ID, self.ISO, q) if self.IRAY == 4 else None
+        spec, _, _ = eng.cirsradg_ck_thermal_cont(self.ISPACE, lay["PRESS"], lay["TEMP"], amount, q if cia else None,
+                                                  lay["FRAC"] if cia else None, lay["TOTAM"], lay["DELH"] if cia else None,
+                                                  lay["CONT"] if dust else None, self.IRAY, f4, NVMR, NPAR,
+                                                  self.igas_map.astype(np.int32), path.NLAYIN, path.LAYINC, path.SCALE, path.EMTEMP,
+                                                  self.TSURF, gradients_on_device=True)
+        eng.map2pro(None, self.W, NVMR, NDUST, NPRO, P_, path.NLAYIN, path.LAYINC, lay["DTE"], lay["DAM"], lay["DCO"],
+                    to_host=False)
+        return spec

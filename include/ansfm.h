@@ -37,6 +37,9 @@ extern "C" {
 #define ANSFM_ERR_UNSUPPORTED 5 /* valid in the reference, not built yet                 */
 
 #define ANSFM_MAX_NG 32
+/* ansfm_cirsradg_ck_thermal_cont(_dev): NVMR + 2, the gradient slots of calc_tau_cia a thread keeps in LDS (128 threads x 48 x 8
+ * bytes = 48 KiB of a block at the cap; 8 KiB at NVMR = 6), may not exceed this, i.e. NVMR <= 46 */
+#define ANSFM_MAX_CONT_GRAD_SLOTS 48
 
 typedef struct ansfm_ctx ansfm_ctx;
 
@@ -465,6 +468,43 @@ int ansfm_cirsradg_ck_thermal_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int 
                                   const double *SCALE, const double *EMTEMP, const double *TSURF,
                                   const double *EMISSIVITY, const double *xfac, double *SPECOUT,
                                   double *dSPECOUT, double *dTSURF);
+
+/* The same with the continuum and its gradients formed inside the call from the context's resident sources (ansfm_upload_cia,
+ * ansfm_upload_dust) and the Rayleigh parametrisations, any of the three -- the continuum block of
+ * ansfm_cirsrad_ck_thermal_cont_dev in place of taucont / dtaucon; over all n * L layers (no de-duplication: a gradient call is
+ * one state, or a few).  cont = (TAUCIA + TAUDUST) + TAURAY as there, and dTAUCON of calculate_layer_opacity (:3940-3981)
+ * straight in the layout the gradient RT kernel reads ([n][NPAR][L][Wpad]), NPAR = NVMR + 2 + NDUST:
+ *   kpar < NVMR            (dTAUCIA[kpar] of calc_tau_cia, i.e. its sum * xfac) / TOTAM, a true division, + dTAURAY (the Rayleigh
+ *                          cross section per unit column) when ray_mode != 0.  As in the reference, calc_tau_cia's dk/dT term
+ *                          lands in slot NVMR - 2 (:4741), on top of whatever that gas contributes as a partner
+ *   kpar == NVMR           dTAUCIA[NVMR], which calc_tau_cia never fills: zero
+ *   kpar == NVMR + 1 + i   dTAUDUST1 of population i = kext * 1e-4, raw: nan_to_num and the clip to [0, 1e20] (:3966) act on
+ *                          the opacity only, so a negative population is clipped in cont and not here
+ *   kpar == NPAR - 1       zero (para-H2)
+ * An absent term adds nothing.  Same bits as ansfm_calc_tau_cia (with gradients) + ansfm_calc_tau_dust +
+ * ansfm_calc_tau_rayleigh assembled on the host that way and passed as taucont / dtaucon -- without the 8 W NPAR L bytes per
+ * state crossing PCIe twice.  The Rayleigh term is summed into the dense gradients, not handed over as a shared gas gradient
+ * (which the RT adds as a second product, with other bits): a pending ansfm_set_shared_gas_gradient is ANSFM_ERR_INVALID and is
+ * cancelled.  ANSFM_ERR_INVALID also when a source that is used has not been uploaded since the last table, the CIA source
+ * was uploaded for the other ISPACE, NVMR is not the NVMR of the uploaded CIA source (or < 2) when CIA is used, or NPAR is not
+ * NVMR + 2 + the NDUST of the uploaded aerosol source when aerosols are used.  ANSFM_ERR_UNSUPPORTED for NVMR + 2 >
+ * ANSFM_MAX_CONT_GRAD_SLOTS.  None of the refusals launches a kernel.
+ * Host-pointer version: every array a host pointer, dSPECOUT may be NULL for n_models = 1 as in ansfm_cirsradg_ck_thermal;
+ * `_dev`: device pointers for every array but igas_map, asynchronous on the ctx stream. */
+int ansfm_cirsradg_ck_thermal_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                   const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                   const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                   const double *lay_cont, int ray_mode, const double *f4, int NVMR, int NPAR,
+                                   const int32_t *igas_map, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                   const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                   const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF);
+int ansfm_cirsradg_ck_thermal_cont_dev(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                       const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                       const double *lay_cont, int ray_mode, const double *f4, int NVMR, int NPAR,
+                                       const int32_t *igas_map_host, int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC,
+                                       const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
+                                       const double *xfac, double *SPECOUT, double *dSPECOUT, double *dTSURF);
 
 /* ---- multiple scattering ---------------------------------------------------------------------
  * Multiple_Scattering_Core.scloud11wave_core (Multiple_Scattering_Core.py:651-960): plane-parallel

@@ -56,6 +56,8 @@ def main():
         bench_ss(eng, out, rng)
     if only == "cia":                                       # 1.6 GB continuum array of the dense route: on request only
         bench_cia(eng, out)
+    if only == "grad_cont":                                 # 0.1 GB dTAUCON assembled on the host for the route it replaces: on request only
+        bench_grad_cont(eng, out)
     print(json.dumps(out, indent=1))
 
 
@@ -745,6 +747,81 @@ def bench_cia(eng, out, W=10000, n=5):
     res["median_of"] = n
     eng.set_stream(None)
     out["jacobian_C3_cia"] = res
+
+
+def bench_grad_cont(eng, out, W=10000, n=5):
+    """The gradient CIRSrad call of the analytic Jacobian at C3 size (one state, bench.py's table, 100 layers) with CIA, two
+    aerosol populations and the Rayleigh continuum: the continuum and dTAUCON formed inside the call from the resident sources
+    (cirsradg_ck_thermal_cont), next to the route it replaces -- calc_tau_cia(with_grad), calc_tau_dust, calc_tau_rayleigh, dTAUCON
+    (W, NPAR, L) put together in NumPy and uploaded with cirsradg_ck_thermal.  Both leave dSPECOUT on the device, as
+    jacobian_analytic does.  Wall times of host-pointer entries: PCIe staging included."""
+    import torch
+    import bench as B
+    from archnemesis_dist_amd import layering
+    from archnemesis_dist_amd.profile_state import ContinuousProfileState, BatchedCKThermalModel
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    dev = torch.device("cuda", eng.device)
+    G, S, L, NP, NT, NDUST, IRAY = 20, 8, 100, 20, 15, 2, 4
+    PRESS, TEMP, K = B.torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    WAVE = 200.0 + (1000.0 / W) * np.arange(W)
+    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+    pr = syn.synth_profiles(100, S + 2, seed=11)
+    NPRO, NVMR = pr["VMR"].shape
+    st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T", ("VMR", 2)])
+    cia = syn.synth_cia()
+    SWAVE = np.linspace(150.0, 1300.0, 12)
+    x = np.linspace(0.0, 1.0, 12)[:, None]
+    KEXT = 1.0e-9 * (1.0 + 0.6 * np.sin(5.0 * x + np.arange(NDUST)[None])) * (1.0 + np.arange(NDUST)[None])
+    KSCA = 0.7 * KEXT * (1.0 - 0.5 * x)
+    DUST = 1.0e3 * np.exp(-np.linspace(0.0, 4.0, NPRO))[:, None] * np.array([1.0, 0.3])[None]
+    model = BatchedCKThermalModel(eng, st, pr["RADIUS"], pr["ID"], pr["ISO"], list(range(2, S + 2)),
+                                  layering_args=dict(NLAY=L, LAYINT=1, NINT=101), IRAY=IRAY, cia=cia,
+                                  dust=dict(SWAVE=SWAVE, KEXT=KEXT, KSCA=KSCA, DUST=DUST))
+    res = {"W": W, "G": G, "S": S, "L": L, "NVMR": NVMR, "NDUST": NDUST, "IRAY": IRAY}
+    res["jacobian_analytic_sources_s"] = timeit(lambda: model.jacobian_analytic(sources=True), n)
+    lay = model.last_analytic_layers
+    path = layering.calc_path(model.RADIUS, model.BASEH, lay["DELH"], lay["TEMP"], float(st.H[-1]), **model.geo)
+    amount = np.ascontiguousarray(lay["AMOUNT"][:, model.igas_map].T) * 1.0e-4
+    NPAR = NVMR + 2 + NDUST
+    igas = model.igas_map.astype(np.int32)
+    q = lay["PP"] / lay["PRESS"][:, None]
+    f4 = eng.rayleigh_f4(pr["ID"], pr["ISO"], q)
+    tabs = [cia[k] for k in ("CIA_WAVEN", "CIA_TEMP", "CIA_FRAC", "NPARA", "K_CIA", "IPAIRG1", "IPAIRG2", "INORMALT", "INORMAL",
+                             "INORMALD")]
+    rest = (NVMR, NPAR, igas, path.NLAYIN, path.LAYINC, path.SCALE, path.EMTEMP, -1.0)
+
+    def fused():
+        return eng.cirsradg_ck_thermal_cont(0, lay["PRESS"], lay["TEMP"], amount, q, lay["FRAC"], lay["TOTAM"], lay["DELH"], lay["CONT"],
+                                            IRAY, f4, *rest, gradients_on_device=True)[0]
+
+    def continuum():
+        tcia, dcia = eng.calc_tau_cia(0, WAVE, *tabs, pr["ID"], pr["ISO"], lay["PP"], lay["PRESS"], lay["TEMP"], lay["FRAC"],
+                                      lay["TOTAM"], lay["DELH"])
+        dust4 = eng.calc_tau_dust(WAVE, SWAVE, KEXT, KSCA, lay["CONT"])
+        ray, dray = eng.calc_tau_rayleigh(IRAY, 0, WAVE, lay["TOTAM"], ID=pr["ID"], ISO=pr["ISO"], VMR=q)
+        cont = (tcia + np.sum(np.clip(np.nan_to_num(dust4[0]), 0, 1e20), 2)) + ray
+        dcont = np.zeros((W, NPAR, L))                             # forward_model._ansfm_continuum
+        dcont[:, 0:NVMR, :] += np.moveaxis(dcia[:, :, 0:NVMR], 2, 1) / lay["TOTAM"][None, None, :]
+        dcont[:, NVMR, :] += dcia[:, :, NVMR]
+        for i in range(NVMR):
+            dcont[:, i, :] += dray
+        for i in range(NDUST):
+            dcont[:, NVMR + 1 + i, :] += dust4[2][:, :, i]
+        return cont, dcont
+
+    def host():
+        cont, dcont = continuum()
+        return eng.cirsradg_ck_thermal(0, lay["PRESS"], lay["TEMP"], amount, cont, dcont, *rest, gradients_on_device=True)[0]
+
+    res["fused_entry_s"] = timeit(fused, n)
+    res["host_assembled_route_s"] = timeit(host, n)
+    res["host_continuum_and_assembly_s"] = timeit(continuum, n)
+    res["dtaucon_bytes"] = 8 * W * NPAR * L
+    res["same_spectrum_bits"] = bool(np.array_equal(fused(), host()))
+    res["median_of"] = n
+    out["grad_cont_C3"] = res
 
 
 def bench_layer(eng, out):
