@@ -140,7 +140,7 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
 #pragma unroll
     for (int i = 0; i < N; ++i) radg[i] = p.radg[(size_t)mg * p.st_wm + (size_t)widx * N + (N - 1 - i)];   // radg[:, ::-1] :765
     bool defined = false;
-    if (p.lowbc > 0 && !lookup) {  // surface operator first :824-836
+    if (p.lowbc > 0 && !lookup) {  // surface operator first :824-836 (the element mirrors ms_surface_element, here and in idown below)
 #pragma unroll
         for (int i = 0; i < N; ++i)
 #pragma unroll
@@ -152,6 +152,7 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
         for (int i = 0; i < N; ++i) LS(jc, i) = radg[i];
         defined = true;
     }
+    // (mirrors ms_chain_inputs, with the five pointers in front of the layer loop)
     const size_t wpw = (size_t)(widx - p.pw0);                              // in the window of phase matrices / factors
     const double *PPL = p.ppl + ((wpw * (p.nf + 1) + ic) * p.ncomp) * NN;
     const double *PMI = p.pmi + ((wpw * (p.nf + 1) + ic) * p.ncomp) * NN;
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
         const int k = lookup ? p.nlay - 1 - l : l;  // look-down: bottom layer first (:842-845)
         const double taut = taus_w[k];
         const double bc = bnu_w[k];
-        double omega = omegas_w[k];
+        double omega = omegas_w[k];                 // (the scalars and the three-way decision mirror ms_layer_scalars)
         if (omega < 0) omega = 0.0;
         if (omega > 1) omega = 1.0;
         double tauscat = taut * omega;
@@ -204,17 +205,15 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
             for (int i = 0; i < N; ++i) j1[i] = ce[(size_t)(2 * NN + i) * 64];
         } else {
             iscl = 1;
-            const double fr = taur / (tauscat + taur), fs = tauscat / (tauscat + taur);
             // ---- double1 :321-362 --------------------------------------------------------------------------
-            double con = omega * pi;
-            con *= (ic == 0) ? 2.0 : 1.0;
-            const int nd = (int)(log2(taut) + 12);   // python int(): truncation toward zero
-            const double tau0 = taut * ((nd >= 1) ? 1.0 / exp2((double)nd) : 1.0);
+            const auto [con, tau0, fr, fs, nd] = ms_doubling_start(taut, omega, tauscat, taur, ic, [](double x) { return log2(x); },
+                                                                   [](double x) { return exp2(x); });
 #pragma unroll
             for (int i = 0; i < N; ++i)
 #pragma unroll
                 for (int j = 0; j < N; ++j) {
                     const int e = i * N + j;
+                    // (mirrors ms_phase_mix over MsPhaseGlobal)
                     double a = (p.iray > 0) ? fr * (PPL[(size_t)p.ncont * NN + e] * FC[(size_t)p.ncont * NN + e]) : 0.0;
                     double b = (p.iray > 0) ? fr * PMI[(size_t)p.ncont * NN + e] : 0.0;
                     for (int c = 0; c < p.ncont; ++c) {
@@ -330,6 +329,7 @@ __global__ __launch_bounds__(64) void k_ms_chain_lane(MsParams p)
     M::mv(t1, radg, trad);
     M::mv(r1, radg, rrad);
     // ---- per path: the four (mu0, mu) samples and the bilinear interpolation :886-945 ---------------------------
+    // (mirrors ms_path_angles, ms_bracket, ms_bilinear and ms_azimuth_term; the samples are selects over compile-time positions)
     for (int ipath = 0; ipath < p.ngeom; ++ipath) {
         const double sol_ang = p.sol_ang[ipath];
         const double emiss_ang = lookup ? 180. - p.emiss_ang[ipath] : p.emiss_ang[ipath];   // new_emi :900-903
