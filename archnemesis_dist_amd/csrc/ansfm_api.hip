@@ -147,6 +147,7 @@ int ansfm_upload_ktable_dev(ansfm_ctx *ctx, int W, int G, int NP, int NT, int S,
     ctx->h_delg.assign(DELG, DELG + G);
     ctx->h_wave.assign(WAVE, WAVE + W); ctx->h_press.assign(PRESS, PRESS + NP); ctx->h_temp.assign(TEMP, TEMP + NT);
     ctx->have_table = true;
+    ++ctx->table_generation;
     ctx->is_lbl = 0; ctx->temp2d = 0;
     ctx->lblrt = 0; ctx->st_n = 0;       // a table replaces a committed line source
     clear_continuum_sources(ctx);        // they were evaluated on the old table's grid
@@ -367,6 +368,7 @@ static int upload_table_files(ansfm_ctx *ctx, int S, const char *const *paths, d
     ctx->has_boxed = (flag & 2) ? 1 : 0;
     ctx->h_delg = DELG; ctx->h_wave = WAVE; ctx->h_press = PRESS; ctx->h_temp = TEMP;
     ctx->have_table = true;
+    ++ctx->table_generation;
     ctx->is_lbl = lta ? 1 : 0; ctx->temp2d = (lta && hl.temp2d) ? 1 : 0;
     ctx->lblrt = 0; ctx->st_n = 0;
     clear_continuum_sources(ctx);
@@ -459,6 +461,22 @@ int ansfm_last_merge_rowmajor(const ansfm_ctx *cctx, int64_t *merges, int64_t *m
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *merges = (int64_t)v[0];
     *merges_total = (int64_t)v[1];
+    return ANSFM_OK;
+}
+
+int ansfm_last_merge_order(const ansfm_ctx *cctx, int *applied, int64_t *valid_bytes_nonzero)
+{
+    ansfm_ctx *ctx = const_cast<ansfm_ctx *>(cctx);     // as ansfm_last_merge_rowmajor
+    CHECK_CTX(ctx);
+    if (!applied || !valid_bytes_nonzero) FAIL(ANSFM_ERR_INVALID, "last_merge_order: null argument");
+    *applied = ctx->last_merge_ordered ? 1 : 0;
+    *valid_bytes_nonzero = 0;
+    if (!ctx->last_merge_ordered || ctx->d_flag.bytes < kFlagInts * sizeof(int)) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long v = 0;                           // the third total behind the tile counters
+    HIPCHK(hipMemcpyAsync(&v, ctx->d_flag.as<int>() + kFlagTileCounter + 8 + 4, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *valid_bytes_nonzero = (int64_t)v;
     return ANSFM_OK;
 }
 

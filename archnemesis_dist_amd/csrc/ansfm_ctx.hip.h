@@ -89,9 +89,11 @@ using ansfm::FusedRoute;
 using ansfm::LblrtIso;
 
 // ints of ansfm_ctx::d_flag: 0 the upload kernels' flag, 1 "unsorted input", 12 the de-duplication's row counter, 13 the
-// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's two
-// 64-bit totals (row-major merges, all merges), which one memset per launch clears together (merge_launch_begin)
-constexpr int kFlagInts = 32, kFlagTileCounter = 16;
+// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's three
+// 64-bit totals (row-major merges, all merges, non-zero pattern bytes read), which one memset per launch clears together
+// (merge_launch_begin)
+constexpr int kFlagInts = 32, kFlagTileCounter = 16, kMergeTotals = 3;
+static_assert(kFlagTileCounter + 8 + 2 * kMergeTotals <= kFlagInts, "the totals lie inside d_flag");
 
 struct ansfm_ctx {
     int device = 0;
@@ -111,6 +113,22 @@ struct ansfm_ctx {
     std::map<const void *, size_t> merge_lds_allowed;   // dynamic LDS each merge kernel has been allowed on this device
     ansfm::MergePlan last_merge;    // the last forward merge launch (ansfm_last_merge_launch, _group_width, _table_layout)
     int merge_keys = 64;     // 32: run the forward merge on k_ck_overlap32's float32 keys (ansfm_set_merge_keys)
+    // The wavenumber order of the forward merge (MergePlan::order): two buffers of Wpad pattern bytes, merge_hint [2][Wpad].  A
+    // launch reads buffer merge_hint_parity and writes the other, and the parity flips after it.  The bytes are valid for the
+    // next launch while its key equals the writer's: the source (table_generation, 0 for the seam), W, Wpad, the rows
+    // n_models * L, S and G; any other qualifying launch clears both buffers first and so runs in the identity order.
+    DevBuf merge_hint;
+    int merge_hint_parity = 0;
+    struct MergeHintKey {
+        long source = -1;
+        int W = 0, Wpad = 0, R = 0, S = 0, G = 0;
+        bool operator==(const MergeHintKey &o) const
+        {
+            return source == o.source && W == o.W && Wpad == o.Wpad && R == o.R && S == o.S && G == o.G;
+        }
+    } merge_hint_key;               // source < 0: no launch has written a hint
+    long table_generation = 0;      // counts the uploads of a table (ansfm_upload_ktable*)
+    bool last_merge_ordered = false;   // the last forward merge launch read valid pattern bytes (ansfm_last_merge_order)
     bool have_table = false;
     int grid_f32 = 0, delg_f32 = 0;
     int is_lbl = 0, temp2d = 0;   // LBL-table mode (ILBL=2): G = 1, TEMP may be [NP][NT]

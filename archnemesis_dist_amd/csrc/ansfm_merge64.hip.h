@@ -424,9 +424,10 @@ __device__ __forceinline__ void merge_init(double (&R)[NR], int G, const MergeOr
 // the popped order is row-major iff K(i, G-1) < K(i+1, 0) for every i + 1 < G -- the doubles the list itself compares, ties
 // included.  R holds the heads K(i, 0) as merge_init left them: in a lane whose heads were not ascending they are the sorted
 // heads instead, and such a lane fails by itself (passing would put K(i, 0) < K(i, G-1) < R[i+1] for every i, i.e. row i's
-// head among the i + 1 smallest for every i, i.e. the heads ascending).  True when every active lane of the wave passes.
+// head among the i + 1 smallest for every i, i.e. the heads ascending).  True when every active lane of the wave passes;
+// lane_passes: this lane's own verdict (the pattern bytes of the wavenumber order, merge_order_inverse).
 template <int NR>
-__device__ __forceinline__ bool merge_rowmajor_test(const double (&R)[NR], int G, const MergeOrient &mo)
+__device__ __forceinline__ bool merge_rowmajor_test(const double (&R)[NR], int G, const MergeOrient &mo, bool &lane_passes)
 {
     const double cl = lds_ld(mo.cbase + (unsigned)(G - 1) * 512u);
     const unsigned lowc = (unsigned)(G - 1) << mo.csh;
@@ -437,6 +438,7 @@ __device__ __forceinline__ bool merge_rowmajor_test(const double (&R)[NR], int G
         const double last = __longlong_as_double((long long)((b & ~0x7FFULL) | (unsigned long long)(((unsigned)i << mo.rsh) | lowc)));
         fail |= (i + 1 < G) & !(last < R[i + 1]);
     }
+    lane_passes = !fail;
     return __builtin_amdgcn_ballot_w64(fail) == 0;
 }
 // The columns j < merge_rowmajor_sure_cols(NR) exist in every launch of list length NR: the launcher takes the smallest list

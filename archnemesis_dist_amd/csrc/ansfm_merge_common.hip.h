@@ -108,6 +108,10 @@ struct OverlapParams {
     int delg_f32;             // DELG is a float32 array: del_g[i]*del_g[j] is a float32 product
     double g_ord[kMaxG + 2];  // [0, cumsum(del_g)] (float32 cumsum when delg_f32), g_ord[G]=1, NaN
     const double *lnKg;       // [NP][NT][S][Wpad][Gs], Gs = gfast_stride(G): the g-fastest copy of lnK, or null (load_gas_rows)
+    // [Wpad] each, or both null: a wavenumber's walk pattern of the launch before and of this one (merge_order_inverse);
+    // two buffers, so that no wave reads a byte that a wave of the same launch wrote
+    const unsigned char *hint_in;
+    unsigned char *hint_out;
 };
 // The g-fastest copy of the table (k_table_gfast builds it from lnK): the G ordinates of one (p, T, gas, wavenumber) lie as one
 // run of Gs doubles, G rounded up to even so that every run starts 16-byte aligned and is read as Gs / 2 pairs; the pad
@@ -269,6 +273,56 @@ __host__ __device__ constexpr bool lane_spots_hold()
 }
 static_assert(lane_spots_hold(), "lane_tile_of / lane_cell against the model's values");
 
+// The order of a block's wavenumbers (width 1, the launches of MergePlan::order).  Whether a merge sorts row by row is a
+// property of the wavenumber, and a tile of R % 64 != 0 runs on into the next wavenumber: the 64 wavenumbers of a block are
+// handed out sorted by the pattern byte the launch before wrote for them (k_ck_overlap: the verdicts of merge_rowmajor_test
+// for merges 1 .. 8 at row R / 2, merge 1 in the most significant bit), so that a tile that straddles mostly joins like with like.
+// Lane i of the wave holds the byte of wavenumber i of the block, 0xFF for a pad wavenumber (they stay behind the real ones);
+// the key (byte << 6) | i keeps equal bytes in wavenumber order, so all-zero bytes give the identity.  A wavenumber's position
+// is its rank, the number of smaller keys; lane_cell's group index is a position, and the wavenumber at position q is the
+// inverse permutation at q.  Which cell a lane holds changes nothing in what is computed for the cell.
+__host__ __device__ constexpr unsigned merge_order_key(unsigned byte, unsigned i) { return (byte << 6) | i; }
+// the rank of wavenumber i among the 64 bytes b(0) .. b(63): what merge_order_inverse counts lane by lane
+template <class F>
+__host__ __device__ constexpr unsigned merge_order_rank(F &&b, unsigned i)
+{
+    unsigned r = 0;
+    for (unsigned j = 0; j < 64u; ++j) r += merge_order_key(b(j), j) < merge_order_key(b(i), i) ? 1u : 0u;
+    return r;
+}
+// ... held to the values of the plain-Python model (tests/test_merge_order_model.py reads the table and the formula's constants):
+// the bytes b(i) = (i * 37 + 11) & 0xE0 for i < 58 and 0xFF behind them, {wavenumber of the block, its position}
+constexpr unsigned kOrderSpotReal = 58, kOrderSpotMul = 37, kOrderSpotAdd = 11, kOrderSpotMask = 0xE0;
+__host__ __device__ constexpr unsigned merge_order_spot_byte(unsigned i)
+{
+    return i < kOrderSpotReal ? (i * kOrderSpotMul + kOrderSpotAdd) & kOrderSpotMask : 0xFFu;
+}
+constexpr unsigned kOrderSpots[][2] = {{0, 0}, {1, 7}, {2, 15}, {3, 22}, {6, 50}, {7, 1}, {13, 51}, {31, 31}, {57, 21}, {58, 58}, {63, 63}};
+__host__ __device__ constexpr bool order_spots_hold()
+{
+    for (const auto &t : kOrderSpots)
+        if (merge_order_rank([](unsigned i) { return merge_order_spot_byte(i); }, t[0]) != t[1]) return false;
+    for (unsigned i = 0; i < 64u; ++i)                  // all-zero bytes: the identity
+        if (merge_order_rank([](unsigned) { return 0u; }, i) != i) return false;
+    return true;
+}
+static_assert(order_spots_hold(), "merge_order_rank against the model's values");
+
+// inv, per lane: the wavenumber (of block vt) at position `lane`.  The 64 bytes are read once per tile; every lane is active.
+// nonzero: the lane's wavenumber is a real one and its byte is not 0 (ansfm_last_merge_order counts them).
+__device__ __forceinline__ int merge_order_inverse(const unsigned char *hint_in, int vt, int W, int lane, bool &nonzero)
+{
+    const int nu = vt * kWave + lane;
+    const unsigned byte = nu < W ? (unsigned)hint_in[nu] : 0xFFu;
+    nonzero = nu < W && byte != 0u;
+    const unsigned key = merge_order_key(byte, (unsigned)lane);
+    unsigned rank = 0;
+#pragma unroll
+    for (int j = 0; j < kWave; ++j) rank += (unsigned)__builtin_amdgcn_readlane((int)key, j) < key ? 1u : 0u;
+    // lane i sends i to lane rank(i): the ranks are a permutation of the lanes, every lane receives one value
+    return __builtin_amdgcn_ds_permute((int)(rank << 2), lane);
+}
+
 struct LaneRow {
     int nu;                     // wavenumber of the lane's cell; W <= nu < Wpad: a pad cell
     unsigned row;               // m * L + l: the row of li and of tau
@@ -277,15 +331,17 @@ struct LaneRow {
                                 // copy: the lane's runs of gas 0 as element offsets into lnKg
     double v, u;
 };
-// the cell of lane `lane` of tile k of wavenumber block vt; gfast: the launch reads the g-fastest copy (wave-uniform)
+// the cell of lane `lane` of tile k of wavenumber block vt; gfast: the launch reads the g-fastest copy (wave-uniform);
+// ordered (wave-uniform, width 1): the cell's wavenumber index is a position in the block's order, inv = merge_order_inverse
 template <bool FROM_K>
-__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane, unsigned nvs, bool gfast)
+__device__ __forceinline__ LaneRow lane_row(const OverlapParams &p, int vt, unsigned k, int lane, unsigned nvs, bool gfast,
+                                            bool ordered = false, int inv = 0)
 {
     const unsigned R = (unsigned)p.n_models * (unsigned)p.L;
     const LaneCell cell = lane_cell(k * kWave + (unsigned)lane, R, nvs);
     LaneRow lr;
     lr.row = cell.row;
-    lr.nu = vt * kWave + (int)cell.w;
+    lr.nu = vt * kWave + (ordered ? __builtin_amdgcn_ds_bpermute((int)(cell.w << 2), inv) : (int)cell.w);
     const unsigned m = lr.row / (unsigned)p.L;
     lr.krow = lr.row - m * (unsigned)p.L;
     lr.arow = m * (unsigned)p.S * (unsigned)p.L + lr.krow;

@@ -57,6 +57,8 @@ inline int merge_list_len(int G)
     for (int v : sizes) if (v >= G) return v;
     return 32;
 }
+// the shortest list at which a launch orders a block's wavenumbers (MergePlan::order)
+constexpr int kMergeOrderMinList = 16;
 // f(std::integral_constant<int, D>) at D = merge_list_len(G): how a launcher names the instantiation for a run-time G
 template <class F>
 auto by_list_len(int G, F &&f)
@@ -92,6 +94,7 @@ struct MergeSwitches {
     Lanes lanes = kLanesUnset;      // ANSFM_MERGE_LANES=wavenumbers | pairs
     bool rowmajor_off = false;      // ANSFM_MERGE_ROWMAJOR=0
     bool layout_wave = false;       // ANSFM_TABLE_LAYOUT=wave: read lnK although a g-fastest copy exists
+    bool order_off = false;         // ANSFM_MERGE_ORDER=0: a block's wavenumbers in their own order, no pattern bytes written
 };
 // read per launch: a caller may change the environment between two calls
 inline MergeSwitches merge_switches_from_env()
@@ -108,6 +111,7 @@ inline MergeSwitches merge_switches_from_env()
     else if (is("ANSFM_MERGE_LANES", "pairs")) sw.lanes = MergeSwitches::kLanesPairs;
     sw.rowmajor_off = starts("ANSFM_MERGE_ROWMAJOR", '0');
     sw.layout_wave = is("ANSFM_TABLE_LAYOUT", "wave");
+    sw.order_off = starts("ANSFM_MERGE_ORDER", '0');
     return sw;
 }
 
@@ -137,6 +141,9 @@ struct MergePlan {
     // its arguments: flags (kFlag*) and the width of a row-mapped tile (1 or kLaneNV; 0 for OPT = 0, which does not read it)
     bool lane_rows = false, rowmajor = false, gfast = false;
     int lane_nv = 0, flags = 0;
+    // the launch hands a block's wavenumbers out in the order of their last walk patterns and writes this launch's patterns
+    // (OverlapParams::hint_in / hint_out, which the launcher sets for such a plan only; no bit of flags or trims)
+    bool order = false;
     // its launch: waves per block, dynamic LDS, blocks, and the bytes of ctx->scratch one block needs
     int nwaves = 1;
     size_t lds = 0;
@@ -199,6 +206,10 @@ inline MergePlan merge_plan(const MergeCall &c, const MergeSwitches &sw)
     // a row-mapped launch on the context's own table reads the g-fastest copy where the upload built one
     m.gfast = m.lane_rows && !c.from_k && c.gfast_copy && c.W == c.table_W && c.Wpad == c.table_Wpad && c.G == c.table_G &&
               c.S == c.table_S && !sw.layout_wave;
+    // the walk's kernel at width 1 orders a block's wavenumbers by the pattern bytes of the launch before (merge_order_inverse)
+    // where a list step is dear enough to pay for the ranking and the scattered table runs of every tile: list lengths from 16
+    // (measured at C2: G = 16 -2.3 %, G = 20 -3.0 %, but G = 10 +1.4 % with the order against the same kernel without it)
+    m.order = m.rowmajor && m.lane_rows && m.lane_nv == 1 && merge_list_len(c.G) >= kMergeOrderMinList && !sw.order_off;
     m.flags = (m.lane_rows ? kFlagLaneRows : 0) | (m.rowmajor ? kFlagRowMajor : 0) | (m.gfast ? kFlagTableGfast : 0);
     m.trims = m.opt | (m.lane_rows ? kOptLaneRows : 0) | (m.rowmajor ? kOptRowMajor : 0);
     m.group_width = m.lane_rows ? m.lane_nv : 0;

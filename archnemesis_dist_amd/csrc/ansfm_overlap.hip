@@ -16,7 +16,7 @@ void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, in
     p.del_g = del_g_dev;
     p.tau = tau;
     p.err_flag = ctx->d_flag.as<int>() + 1;
-    // eight tile queues, then the forward merge's two 64-bit totals (ansfm_last_merge_rowmajor): cleared by one memset
+    // eight tile queues, then the forward merge's 64-bit totals (ansfm_last_merge_rowmajor, _order): cleared by one memset
     p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + kFlagTileCounter);
     p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
     p.delg_f32 = ctx->delg_f32;
@@ -35,7 +35,7 @@ void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, in
 int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, long grid, std::initializer_list<MergeWorkspace> workspaces)
 {
     for (const MergeWorkspace &w : workspaces) HIPCHK(w.buf->reserve((size_t)grid * w.bytes_per_block));
-    HIPCHK(hipMemsetAsync(p.tile_counter, 0, (8 + 4) * sizeof(unsigned int), ctx->stream));
+    HIPCHK(hipMemsetAsync(p.tile_counter, 0, (8 + 2 * kMergeTotals) * sizeof(unsigned int), ctx->stream));
     return ANSFM_OK;
 }
 
@@ -93,6 +93,19 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     p.scratch = ctx->scratch.as<double>();
     if (m.gfast) p.lnKg = ctx->lnKg.as<double>();
     ctx->last_merge = m;
+    ctx->last_merge_ordered = false;
+    ansfm_ctx::MergeHintKey key;
+    bool valid = false;
+    if (m.order) {
+        // the pattern bytes of the launch before, if it was a launch of this key; else zeros, which are the identity order
+        key.source = from_k ? 0 : ctx->table_generation;
+        key.W = W; key.Wpad = Wpad; key.R = n_models * L; key.S = S; key.G = G;
+        HIPCHK(ctx->merge_hint.reserve((size_t)2 * Wpad));
+        valid = key == ctx->merge_hint_key;
+        if (!valid) HIPCHK(hipMemsetAsync(ctx->merge_hint.p, 0, (size_t)2 * Wpad, ctx->stream));
+        p.hint_in = ctx->merge_hint.as<unsigned char>() + (size_t)ctx->merge_hint_parity * Wpad;
+        p.hint_out = ctx->merge_hint.as<unsigned char>() + (size_t)(1 - ctx->merge_hint_parity) * Wpad;
+    }
     if (m.keys32) {
         HIPCHK(launch_overlap32(p, from_k, (unsigned)m.grid, ctx->stream));
         return ANSFM_OK;
@@ -110,6 +123,11 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)m.grid), dim3(kWave * m.nwaves), m.lds, ctx->stream, p, m.flags, m.lane_nv);
     HIPCHK(hipGetLastError());
+    if (m.order) {
+        ctx->merge_hint_parity ^= 1;            // the next launch reads what this one writes
+        ctx->merge_hint_key = key;
+        ctx->last_merge_ordered = valid;
+    }
     return ANSFM_OK;
 }
 

@@ -63,6 +63,9 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
     // lane_nv: the wavenumbers of a tile of the row mapping, 1 or kLaneNV (LaneRow); unused without lane_rows
     const unsigned nvs = lane_nv == 1 ? 0u : kLaneNVShift;
     unsigned n_rowmajor = 0, n_merged = 0;              // kOptTable: the merges of this wave that took the walk / all of them
+    // kOptTable: the launch orders a block's wavenumbers by the launch before's pattern bytes and writes its own (MergePlan::order)
+    const bool ordered = kTable && p.hint_in != nullptr;
+    unsigned n_hints = 0;                               // the non-zero pattern bytes this wave read for the blocks whose tile 0 it ran
     extern __shared__ double smem[];
     const int lane = kTable ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
     const int wv = kTable ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;     // wave of the block
@@ -111,6 +114,15 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             if (lane_rows != 0) {
                 unsigned k = 0;
                 if (!tq.next_rows(p, lane, nvs, vt, k)) break;
+                if constexpr (kTable) {
+                    int inv = lane;
+                    if (ordered) {
+                        bool nonzero = false;
+                        inv = merge_order_inverse(p.hint_in, vt, p.W, lane, nonzero);
+                        if (k == 0) n_hints += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(nonzero));
+                    }
+                    lr = lane_row<FROM_K>(p, vt, k, lane, nvs, gfast, ordered, inv);
+                } else
                 lr = lane_row<FROM_K>(p, vt, k, lane, nvs, gfast);
             } else if (!tq.next(p, lane, vt, m, l)) break;
         } else {
@@ -120,6 +132,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
         LayerInterp q;
         if constexpr (!FROM_K) q = p.li[(size_t)m * p.L + l];
         bool unsorted = false;
+        unsigned pattern = 0;                           // ordered: the lane's verdicts of merges 1 .. 8, merge 1 in bit 7
 
         load_cell<FROM_K, NOBOX, OPT>(p, lane_rows, gfast, lr, q, m, l, 0, nu, A, lane, unsorted);
         double alast = A[(G - 1) * kWave + lane];       // last g-ordinate in the ORIGINAL order
@@ -168,11 +181,14 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                 MergeElem e0, e1;
                 WalkState ws;
                 if constexpr (kTable) {
-                    if ((flags & kFlagRowMajor) != 0 && merge_rowmajor_test<NR>(R, G, mo)) {
+                    bool lane_passes = false;
+                    if ((flags & kFlagRowMajor) != 0 && merge_rowmajor_test<NR>(R, G, mo, lane_passes)) {
                         ws = walk_begin(GORD, lane);
                         merge_rowmajor<NR>(G, mo, ws, rec);
                         walked = true;
                     }
+                    // (a skipped merge leaves its bit 0; merges beyond the eighth shift their bit out)
+                    pattern |= lane_passes && s <= 8 ? 0x100u >> s : 0u;
                 }
                 if (!kTable || !walked) {               // (a constant without the table: those instantiations compile as they did)
                 merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB, mo);
@@ -284,6 +300,11 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                 if (unsorted) atomicOr(p.err_flag, 1);
                 double *outr = p.tau + ((size_t)lr.row * G) * p.Wpad + lr.nu;
                 for (int g = 0; g < G; ++g) outr[(size_t)g * p.Wpad] = A[g * kWave + lane];
+                if constexpr (kTable) {
+                    // every cell is in exactly one tile: the wavenumber's byte is written once per launch, by its middle row
+                    if (ordered && lr.row == (((unsigned)p.n_models * (unsigned)p.L) >> 1) && lr.nu < p.W)
+                        p.hint_out[lr.nu] = (unsigned char)pattern;
+                }
                 continue;
             }
         }
@@ -296,11 +317,12 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
         }
     }
     if constexpr (kTable) {
-        // the launch's two totals follow the tile counters (merge_params) and are cleared with them; added once per wave
+        // the launch's three totals follow the tile counters (merge_params) and are cleared with them; added once per wave
         unsigned long long *cnt = reinterpret_cast<unsigned long long *>(p.tile_counter + 8);
         if (lane == 0) {
             atomicAdd(cnt, (unsigned long long)n_rowmajor);
             atomicAdd(cnt + 1, (unsigned long long)n_merged);
+            if (ordered) atomicAdd(cnt + 2, (unsigned long long)n_hints);
         }
     }
 }

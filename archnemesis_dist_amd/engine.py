@@ -318,6 +318,15 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_last_merge_rowmajor(self._ctx, C.byref(m), C.byref(t)), "last_merge_rowmajor")
         return int(m.value), int(t.value)
 
+    def last_merge_order(self):
+        """(applied, non-zero bytes) of the last forward merge launch: applied when it handed the wavenumbers of a block out in
+        the order of the pattern bytes that the launch before wrote (the same table upload or the seam, W, rows, S and G; the
+        library's own launch at group width 1 with the walk on and G > 10; off with ANSFM_MERGE_ORDER=0), and how many of the bytes it
+        read were not 0.  (False, 0) for every other launch."""
+        a, n = C.c_int(), C.c_int64()
+        self._check(self._lib.ansfm_last_merge_order(self._ctx, C.byref(a), C.byref(n)), "last_merge_order")
+        return bool(a.value), int(n.value)
+
     # ---- array-level seams --------------------------------------------------------------------
     def calc_k(self, press, temp, grad=False):
         press = _np(press); temp = _np(temp)

@@ -100,6 +100,16 @@ int ansfm_ktable_gfast(const ansfm_ctx *ctx, int *present, int64_t *bytes);
 /* gfast = 1 when the last forward merge launch read the table from that copy (a launch with bit 32 on a context that holds
  * it; ANSFM_TABLE_LAYOUT=wave at the call keeps the wave-fastest reads), else 0.  Reads the context only. */
 int ansfm_last_merge_table_layout(const ansfm_ctx *ctx, int *gfast);
+/* The wavenumber order of the forward merge.  A launch with bits 1, 32 and 64 at group width 1 and G > 10 (a head list of 16
+ * entries or more; shorter merges do not repay it) writes one byte per wavenumber,
+ * the row-major verdicts of its first eight merges at the middle row, and hands the 64 wavenumbers of a block out sorted by
+ * the bytes that the launch before wrote, so that a wave that holds the end of one wavenumber's rows and the start of the
+ * next ones' mostly holds two of a kind (results do not depend on it, bit for bit).  The bytes are valid while the next such
+ * launch has the same source (the same table upload, or the array-level seam), W, rows n_models * L, S and G; otherwise it
+ * clears them and runs in wavenumber order.  ANSFM_MERGE_ORDER=0 at the call: wavenumber order, nothing written or kept.
+ * applied = 1 when the last forward merge launch read valid bytes, and how many of them were not 0 (all 0: wavenumber order
+ * still); 0 and 0 for every other launch.  Copies the count from the device (synchronises). */
+int ansfm_last_merge_order(const ansfm_ctx *ctx, int *applied, int64_t *valid_bytes_nonzero);
 
 /* ---- LBL tables (ILBL = LINE_BY_LINE_TABLES) ------------------------------------------------------
  * State of Spectroscopy_0 after read_tables on .lta / HDF5 LBL tables: K[W][NP][|NT|][S] (NG = 1),
