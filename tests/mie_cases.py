@@ -22,12 +22,41 @@ open range ends with -- and includes -- the first radius with r >= r_peak and n 
 The order of every operation is the reference's, so that the restatement differs from it by the complex divisions
 (Python's form in places, NumPy's here) and the order of the sum over radii only.  chunk_order=True sums the radii as the
 kernels do: chunks of 64 radii aligned at m = 0, inside a chunk the halving tree v[i] += v[i + s] (s = 32 ... 1), the
-chunks' sums then added in ascending order."""
+chunks' sums then added in ascending order.
+
+edge_cases() (tests/golden/mie_edges.npz) enters what the eight golden cases leave out:
+  perwave-m, waves-130     a refractive index per wavelength; 130 wavelengths are three blocks of k_mie_cutoff
+  nmx150                   50 radii over which 1.1 |m| x runs from 145 to 155, across nmx1's switch at 150
+  x2000-single             x = 2011: D_n downwards from 2940
+  absorbing                m = 2 - 3i and 0.3 - 4i
+  small-x                  10 radii at x from 3.0e-3 to 3.0e-2, where the upward recurrence cancels
+  fail-behind-cut          an open range that ends after 26 radii, with series that fail from radius 93 on in the same block
+  closed-2                 both Simpson end weights side by side
+  theta-0, theta-90, theta-33, theta-33-90      1 and 33 angles, with and without 90 degrees
+  open-64, -65, -128, -129 open ranges that end on the last radius of a chunk or block, and on the first of the next
+  ws-halved                64 wavelengths x 300 radii at x up to 829: the 1 GiB workspace bound halves the block of radii
+The elementary functions the device may round differently (sin, cos, exp, log, pow) can be replaced (`fn`), and
+one_ulp_sensitivity(case) measures how strongly a case amplifies one ulp in them: about 2e-14 / x^2 at small x."""
+import types
+
 import numpy as np
 
 INPUTS = ("wavel", "iscat", "dsize", "rs", "refindx", "theta")
 CHUNK = 64
 RADIUS_CAP = 1 << 20
+
+# the elementary functions of the restatement: what the device is free to round differently (DESIGN.md 4.5e).  `pow` is
+# the operator, whose squares and identities NumPy takes without the library's pow.
+NUMPY_FUNCS = types.SimpleNamespace(sin=np.sin, cos=np.cos, exp=np.exp, log=np.log, pow=lambda a, b: a ** b)
+
+
+def shifted_funcs(direction):
+    """the elementary functions with every cos, exp, log and pow result moved one ulp towards direction * inf and every sin
+    result one ulp the other way"""
+    to = lambda f, d: (lambda *a: np.nextafter(f(*a), d * np.inf))
+    n = NUMPY_FUNCS
+    return types.SimpleNamespace(sin=to(n.sin, -direction), cos=to(n.cos, direction), exp=to(n.exp, direction),
+                                 log=to(n.log, direction), pow=to(n.pow, direction))
 
 
 class MieFailure(ValueError):
@@ -59,7 +88,7 @@ def radius_count(rs):
     return inr
 
 
-def peak_radius(iscat, dsize):
+def peak_radius(iscat, dsize, fn=NUMPY_FUNCS):
     """r_peak of the open range's test (:1693-1709)"""
     if dsize[1] == 0:
         return 0.0
@@ -67,22 +96,22 @@ def peak_radius(iscat, dsize):
     if iscat == 1:
         return dsize[2] * aa * bb
     if iscat == 2:
-        return np.exp(np.log(aa) - bb ** 2)
+        return fn.exp(fn.log(aa) - bb ** 2)
     if iscat == 3:
-        return (aa / (bb * dsize[2])) ** (1.0 / dsize[2])
+        return fn.pow(aa / (bb * dsize[2]), 1.0 / dsize[2])
     return 0.0
 
 
-def size_weight(iscat, dsize, rr):
+def size_weight(iscat, dsize, rr, fn=NUMPY_FUNCS):
     """n(r) (:1758-1773)"""
     if dsize[1] == 0 or iscat == 4:
         return np.ones_like(rr)
     aa, bb = dsize[0], dsize[1]
     if iscat == 1:
-        return rr ** dsize[2] * np.exp(-rr / (aa * bb))
+        return fn.pow(rr, dsize[2]) * fn.exp(-rr / (aa * bb))
     if iscat == 2:
-        return 1. / (rr * bb * np.sqrt(2 * np.pi)) * np.exp(-(np.log(rr) - np.log(aa)) ** 2. / (2. * bb ** 2.))
-    return rr ** aa * np.exp(-bb * rr ** dsize[2])
+        return 1. / (rr * bb * np.sqrt(2 * np.pi)) * fn.exp(-(fn.log(rr) - fn.log(aa)) ** 2. / (2. * bb ** 2.))
+    return fn.pow(rr, aa) * fn.exp(-bb * fn.pow(rr, dsize[2]))
 
 
 def simpson_weight(m, inr, delr):
@@ -92,7 +121,7 @@ def simpson_weight(m, inr, delr):
     return np.where((m == 0) | (m == last), delr / 3.0, vv)
 
 
-def mie_terms(x, rfr, rfi, cstht, si2tht):
+def mie_terms(x, rfr, rfi, cstht, si2tht, fn=NUMPY_FUNCS):
     """dmie for an array of size parameters: Q_ext, Q_sca, the term counts, f at theta and at 180 - theta (R, A), and the
     failure codes (0; 1: nmx1 >= 29999; 2: more than nmx2 terms)"""
     R, A = x.shape[0], cstht.shape[0]
@@ -115,7 +144,7 @@ def mie_terms(x, rfr, rfi, cstht, si2tht):
         cur = np.where(nn <= nmx1, new, 0.0)
         if nn <= nstore:
             D[nn] = cur
-    cx, sx = np.cos(x), np.sin(x)
+    cx, sx = fn.cos(x), fn.sin(x)
     wm1 = cx - 1j * sx
     wfn1 = sx + 1j * cx
     wfn2 = rx * wfn1 - wm1
@@ -141,11 +170,11 @@ def mie_terms(x, rfr, rfi, cstht, si2tht):
         pi2 = (u0 * pi1 * cstht - n * pi0) / u1
         tau2 = cstht * (pi2 - pi0) - u0 * si2tht * pi1 + tau0
         wm1 = wfn1; wfn1 = wfn2
-        wfn2 = u0 * rx * wfn1 - wm1
         Dn = D[min(n, nstore)]
         tc1 = Dn * rrf + n * rx
         tc2 = Dn * rf + n * rx
         with np.errstate(all="ignore"):               # radii that have ended keep running here, unused
+            wfn2 = u0 * rx * wfn1 - wm1
             fna = (tc1 * wfn2.real - wfn1.real) / (tc1 * wfn2 - wfn1)
             fnb = (tc2 * wfn2.real - wfn1.real) / (tc2 * wfn2 - wfn1)
             tb0, tb1, tc0, tc1i = fna.real, fna.imag, fnb.real, fnb.imag
@@ -201,7 +230,9 @@ def _ordered_sum(rows, chunk_order):
     return acc
 
 
-def miescat_np(xlam, iscat, dsize, rs, refindx, theta, chunk_order=False, block=256, cap=RADIUS_CAP, details=None):
+def miescat_np(xlam, iscat, dsize, rs, refindx, theta, chunk_order=False, block=256, cap=RADIUS_CAP, details=None,
+               fn=NUMPY_FUNCS, memo=None):
+    """memo: a dict that keeps mie_terms' results per block of radii, for a second call with the other order of the sum"""
     theta = np.asarray(theta, dtype=np.float64)
     A = theta.shape[0]
     nphas = nphas_of(theta)
@@ -209,7 +240,7 @@ def miescat_np(xlam, iscat, dsize, rs, refindx, theta, chunk_order=False, block=
     si2tht = np.where(theta == 0.0, 0.0, np.where(theta == 90.0, 1.0, 1.0 - cstht * cstht))
     r1, delr = rs[0], rs[2]
     inr = radius_count(rs)
-    rmax = peak_radius(iscat, dsize) if inr is None else 0.0
+    rmax = peak_radius(iscat, dsize, fn) if inr is None else 0.0
     nqmax, m0, mcut = 0.0, 0, None
     rows_f, rows_k, ratios = [], [], []
     while mcut is None:
@@ -218,8 +249,13 @@ def miescat_np(xlam, iscat, dsize, rs, refindx, theta, chunk_order=False, block=
         m = np.arange(m0, min(m0 + block, cap) if inr is None else min(m0 + block, inr), dtype=np.int64)
         rr = r1 + m * delr
         xx = 2.0 * np.pi * rr / xlam
-        qext, qscat, nterm, f_fwd, f_bwd, fail = mie_terms(xx, refindx[0], refindx[1], cstht, si2tht)
-        anr = size_weight(iscat, dsize, rr)
+        terms = None if memo is None else memo.get(m0)
+        if terms is None:
+            terms = mie_terms(xx, refindx[0], refindx[1], cstht, si2tht, fn)
+            if memo is not None:
+                memo[m0] = terms
+        qext, qscat, nterm, f_fwd, f_bwd, fail = terms
+        anr = size_weight(iscat, dsize, rr, fn)
         nq = anr * qscat
         last = m.shape[0] - 1
         for j in range(m.shape[0]):
@@ -257,7 +293,8 @@ def miescat_np(xlam, iscat, dsize, rs, refindx, theta, chunk_order=False, block=
     return xscat, xext, phas, mcut + 1
 
 
-def makephase_np(wavel, iscat, dsize, rs, refindx, theta, chunk_order=False, return_counts=False, cap=RADIUS_CAP, details=None):
+def makephase_np(wavel, iscat, dsize, rs, refindx, theta, chunk_order=False, return_counts=False, cap=RADIUS_CAP, details=None,
+                 fn=NUMPY_FUNCS, memo=None):
     """(xscat, xext, thetax, phas[, n_radii]) of Scatter_0.makephase for iscat 1 .. 4, phas as miescat returns it (before the
     class method divides by 4 pi)"""
     wavel = np.atleast_1d(np.asarray(wavel, dtype=np.float64))
@@ -274,7 +311,8 @@ def makephase_np(wavel, iscat, dsize, rs, refindx, theta, chunk_order=False, ret
     for i in range(nw):
         d = {} if details is not None else None
         xscat[i], xext[i], phas[i], counts[i] = miescat_np(wavel[i], int(iscat), dsize, rs, refindx[i], theta, chunk_order,
-                                                           cap=cap, details=d)
+                                                           cap=cap, details=d, fn=fn,
+                                                           memo=None if memo is None else memo.setdefault(i, {}))
         if details is not None:
             details.setdefault("per_wave", []).append(d)
     out = (xscat, xext, thetax_of(theta), phas)
@@ -284,7 +322,8 @@ def makephase_np(wavel, iscat, dsize, rs, refindx, theta, chunk_order=False, ret
 def _case(wavel, iscat, dsize, rs, m, theta):
     wavel = np.asarray(wavel, dtype=np.float64)
     d3 = np.zeros(3); d3[:len(dsize)] = dsize
-    refindx = np.tile(np.asarray(m, dtype=np.float64), (wavel.shape[0], 1))
+    m = np.asarray(m, dtype=np.float64)
+    refindx = np.tile(m, (wavel.shape[0], 1)) if m.ndim == 1 else m.reshape(wavel.shape[0], 2).copy()
     if rs is None:
         rs = (0.015 * wavel.min(), 0.0, 0.015 * wavel.min())
     return dict(wavel=wavel, iscat=np.int64(iscat), dsize=d3, rs=np.asarray(rs, dtype=np.float64), refindx=refindx,
@@ -309,6 +348,67 @@ def golden_cases():
 
 EXPECTED_RADII = {"closed-even": 10, "closed-bumped": 12, "closed-64": 64, "closed-65": 66, "big-x-single": 1}
 OPEN_CASES = ("lognormal-open-90", "gamma-open-no90", "mcs-open")
+
+# steps of the open ranges that end on the last radius of a chunk or block and on the first radius of the next
+OPEN_STEPS = {"open-64": 0.03317858929464732, "open-65": 0.03267233616808404,
+              "open-128": 0.01658729364682341, "open-129": 0.01647223611805903}
+
+
+def edge_cases():
+    """name -> inputs of tests/golden/mie_edges.npz: the paths of the kernels that golden_cases() does not enter."""
+    closed = lambda n_before_bump, r0=0.05, step=0.02: (r0, r0 + (n_before_bump - 1 + 0.25) * step, step)
+    even = dict(wavel=[1.0], iscat=2, dsize=(0.3, 0.4), rs=closed(10), m=(1.5, 0.1))       # the inputs of closed-even
+    theta33 = np.linspace(0.0, 88.0, 33)
+    w130, w64 = np.linspace(0.8, 5.0, 130), np.linspace(0.5, 0.6, 64)
+    cases = {
+        # a refractive index per wavelength (model 444 retrieves this array)
+        "perwave-m": _case([0.8, 2.0, 5.0], 2, (0.5, 0.3), (0.012, 0.0, 0.012), [[1.4, 0.01], [1.33, 0.0], [1.8, 0.5]],
+                           [0.0, 10.0, 45.0, 90.0]),
+        # 1.1 |m| x from 145 to 155: nmx1 switches from the floor of 150 to int(1.1 |m| x) inside the range
+        "nmx150": _case([1.0], 4, (14.0,), closed(50, 14.0), (1.5, 0.0), [0.0, 30.0, 60.0, 90.0]),
+        # x = 2011: D_n downwards from 2940, 2675 workspace rows
+        "x2000-single": _case([0.5], 4, (160.0,), (160.0, 160.0, 160.0), (1.33, 0.001), [0.0, 30.0, 60.0, 90.0]),
+        # a metal-like index, and n_r < 1
+        "absorbing": _case([1.0, 3.0], 2, (0.5, 0.3), (0.015, 0.0, 0.015), [[2.0, 3.0], [0.3, 4.0]], [0.0, 10.0, 45.0, 90.0]),
+        # x from 3.0e-3 to 3.0e-2, where the upward recurrence cancels; below that see DESIGN.md 4.5e
+        "small-x": _case([10.0], 2, (0.02, 0.4), closed(10, 0.0048, 0.0047), (1.4, 0.01), [0.0, 45.0, 90.0]),
+        # the range ends after 26 radii; from index 93 on the series of the same block's radii fail with code 2
+        "fail-behind-cut": _case([0.5], 2, (0.5, 0.3), (0.1, 0.0, 0.1), (1.05, 0.0), [0.0, 90.0]),
+        "closed-2": _case(even["wavel"], 2, even["dsize"], closed(2), even["m"], [0.0, 90.0]),
+        "theta-0": _case(even["wavel"], 2, even["dsize"], even["rs"], even["m"], [0.0]),
+        "theta-90": _case(even["wavel"], 2, even["dsize"], even["rs"], even["m"], [90.0]),
+        "theta-33": _case(even["wavel"], 2, even["dsize"], even["rs"], even["m"], theta33),
+        "theta-33-90": _case(even["wavel"], 2, even["dsize"], even["rs"], even["m"], np.append(theta33[:32], 90.0)),
+        "waves-130": _case(w130, 2, even["dsize"], closed(12), np.stack([np.linspace(1.3, 1.6, 130), np.linspace(0.0, 0.05, 130)], axis=1),
+                           [0.0, 30.0, 90.0]),
+        # 300 radii, x up to 829: at the default block of 512 radii the workspace would take 1.7 GiB, so the block is halved
+        "ws-halved": _case(w64, 2, (62.0, 0.05), closed(300, 60.0), np.stack([np.linspace(1.33, 1.5, 64), np.linspace(0.0, 0.01, 64)], axis=1),
+                           [0.0, 30.0, 90.0]),
+    }
+    for name, step in OPEN_STEPS.items():
+        cases[name] = _case([0.8], 2, (0.5, 0.3), (step, 0.0, step), (1.4, 0.01), [0.0, 90.0])
+    return cases
+
+
+EDGE_EXPECTED_RADII = {"perwave-m": [177, 208, 209], "nmx150": 50, "x2000-single": 1, "absorbing": [147, 146], "small-x": 10,
+                       "fail-behind-cut": 26, "closed-2": 2, "theta-0": 10, "theta-90": 10, "theta-33": 10, "theta-33-90": 10,
+                       "waves-130": 12, "ws-halved": 300, "open-64": 64, "open-65": 65, "open-128": 128, "open-129": 129}
+EDGE_OPEN_CASES = ("perwave-m", "absorbing", "fail-behind-cut") + tuple(OPEN_STEPS)
+
+
+def one_ulp_sensitivity(case):
+    """how strongly a case amplifies a last-place difference in sin, cos, exp, log and pow: the larger of the deviations
+    of makephase_np from itself with those results shifted by one ulp one way (cos, exp, log, pow up, sin down) and the other"""
+    run = lambda fn: makephase_np(case["wavel"], case["iscat"], case["dsize"], case["rs"], case["refindx"], case["theta"],
+                                  return_counts=True, fn=fn)
+    base = run(NUMPY_FUNCS)
+    g = dict(xscat=base[0], xext=base[1], phas=base[3])
+    devs = []
+    for direction in (1.0, -1.0):
+        got = run(shifted_funcs(direction))
+        assert np.array_equal(got[4], base[4]), (got[4], base[4])
+        devs.append(deviations((got[0], got[1], got[3]), g))
+    return tuple(max(a, b) for a, b in zip(*devs))
 
 
 def load_golden(path):
