@@ -638,6 +638,23 @@ int ansfm::dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const d
     return ANSFM_OK;
 }
 
+// The same with the columns behind the continuum of c (device arrays over the n * L layers).  The para-H2 fraction counts only
+// where cia_layer reads it (a table with a para-H2 axis): the scattering batch takes a layer from model 0's doubling results
+// exactly when its row is model 0's, and a column that changes no opacity must not cost that.
+int ansfm::dedup_rows_cont(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
+                           const ContCall &c, DedupRows *out)
+{
+    DedupCols x;
+    if (c.ray_mode || c.use_cia) x.add(c.totam, 1);
+    if (c.ray_mode == 4) x.add(c.f4, 4);
+    if (c.use_cia) {
+        x.add(c.q, ctx->cia_NVMR); x.add(c.delh, 1);
+        if (ctx->cia_NPARA > 0 || ctx->cia_nfrac > 1) x.add(c.frac, 1);
+    }
+    if (c.use_dust) x.add(c.cont, ctx->dust_n);
+    return dedup_rows(ctx, n, L, press, temp, amount, &x, out);
+}
+
 // Which slot of the gradient merge (gas i: slot i, temperature: slot S) feeds parameter k of dSPECOUT, for the gradient RT
 // kernels and the transit kernels alike; -1: none
 int ansfm::fill_slot_of_param(ansfm_ctx *ctx, const int32_t *igas_map_host, int NVMR, int NPAR, unsigned gas_mask,

@@ -318,15 +318,16 @@ __global__ __launch_bounds__(128) void k_tau_dust(DustParams p)
     }
 }
 
-// ansfm_upload_dust: the extinction cross sections on the table's grid, kext_w[NDUST][Wpad] (zero beyond W), as k_tau_dust
-// evaluates them.  One thread per (wavenumber, population).
-__global__ __launch_bounds__(128) void k_dust_kext_grid(DustParams p, int Wpad, double *__restrict__ kext_w)
+// ansfm_upload_dust: the extinction and scattering cross sections on the table's grid, kext_w / ksca_w [NDUST][Wpad] (zero
+// beyond W), as k_tau_dust evaluates them.  One thread per (wavenumber, population).
+__global__ __launch_bounds__(128) void k_dust_kext_grid(DustParams p, int Wpad, double *__restrict__ kext_w, double *__restrict__ ksca_w)
 {
     const int w = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
     if (w >= Wpad) return;
-    double kext = 0.0, ksca;
+    double kext = 0.0, ksca = 0.0;
     if (w < p.W) dust_k(p, p.wavec[w], i, kext, ksca);
     kext_w[(size_t)i * Wpad + w] = kext;
+    ksca_w[(size_t)i * Wpad + w] = ksca;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -403,7 +404,66 @@ __global__ __launch_bounds__(256) void k_tau_cont_rows(ContRowsParams p)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The gradients of that continuum, dTAUCON of calculate_layer_opacity (:3940-3981), from the same resident sources and
+// The same rows for the multiple-scattering batch (ansfm_cirsrad_ck_scatter_batch_cont), which needs the terms apart and the
+// scattering side of the aerosols: the five arrays of calculate_layer_opacity (:3963-3972) and scloud11wave (:5107-5113) in
+// the layout ansfm_cirsrad_ck_scatter_batch_rows takes, taucia / taudust / tauray / tauscat [rows][W] and lfrac
+// [rows][NDUST][W], wavenumber fastest.  Per population d, rounded as k_tau_dust rounds them to memory,
+//     e_d = (kext_w[d][w] 1e-4) CONT[l][d],   s_d = (ksca_w[d][w] 1e-4) CONT[l][d]
+//     TAUDUST = sum_d clip(nan_to_num(e_d), 0, 1e20)      TAUSCAT = sum_d s_d  (raw: neither clip nor nan_to_num, :3972)
+//     lfrac[d] = s_d / TAUSCAT where TAUSCAT > 0, else 0  (a true division)
+// both sums in the order of d (NumPy adds fewer than 8 terms in order).  TAUCIA and TAURAY as k_tau_cont_rows forms them.  An
+// array whose term is not used is null and not written.
+// ------------------------------------------------------------------------------------------------------------------
+struct MsContRowsParams {
+    ContRowsParams c;           // as k_tau_cont_rows takes it (out unused); c.lay filled by k_cia_rows_prep for these rows
+    const double *ksca_w;       // [NDUST][Wpad]
+    double *taucia, *taudust, *tauray, *tauscat;   // [rows][W]
+    double *lfrac;              // [rows][NDUST][W]
+};
+
+// One thread per (row, wavenumber), a block within one row (blockIdx.x), coalesced along the wavenumbers.  s_d is formed
+// twice, for the sum and for the fractions: no per-thread array, no scratch memory.
+__global__ __launch_bounds__(256) void k_ms_cont_rows(MsContRowsParams p)
+{
+#pragma clang fp contract(off)
+    const ContRowsParams &c = p.c;
+    const int r = blockIdx.x, w = blockIdx.y * blockDim.x + threadIdx.x;
+    if (w >= c.W) return;
+    const int l = c.work ? c.work[r] : r;
+    const size_t o = (size_t)r * c.W + w;
+    const double v = c.wave[w];
+    if (c.use_cia) {
+        const CiaLayer cl = c.lay[r];
+        const double x = c.ispace == 0 ? v : 1.e4 / v;             // :4565
+        const double sum1 = cia_sum(c.cia, cl, x, w, c.cia.q + (size_t)l * c.cia.NVMR, nullptr);
+        p.taucia[o] = sum1 * cl.xfac;
+    }
+    if (c.NDUST > 0) {
+        const double *cont = c.cont + (size_t)l * c.NDUST;
+        double dust = 0.0, sca = 0.0;
+        for (int d = 0; d < c.NDUST; ++d) {
+            const double de = c.kext_w[(size_t)d * c.Wpad + w] * 1.0e-4, ds = p.ksca_w[(size_t)d * c.Wpad + w] * 1.0e-4;
+            double t = de * cont[d];
+            const double s = ds * cont[d];
+            t = (t != t) ? 0.0 : t;                                  // np.nan_to_num; +-inf end at the bounds of the clip
+            t = t > 0.0 ? t : 0.0;                                   // np.clip(., 0, 1e20)  (:3966)
+            t = t < 1.0e20 ? t : 1.0e20;
+            dust = d == 0 ? t : dust + t;
+            sca = d == 0 ? s : sca + s;
+        }
+        p.taudust[o] = dust;
+        p.tauscat[o] = sca;
+        for (int d = 0; d < c.NDUST; ++d) {
+            const double s = (p.ksca_w[(size_t)d * c.Wpad + w] * 1.0e-4) * cont[d];
+            p.lfrac[((size_t)r * c.NDUST + d) * c.W + w] = sca > 0.0 ? s / sca : 0.0;       // :5108-5113
+        }
+    }
+    if (c.ray_mode)
+        p.tauray[o] = rayleigh_k(c.ray_mode, c.ispace, v, c.ray_mode == 4 ? c.f4 + (size_t)l * 4 : nullptr) * c.totam[l];
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The gradients of k_tau_cont_rows' continuum, dTAUCON of calculate_layer_opacity (:3940-3981), from the same resident sources and
 // straight in the layout the gradient RT reads: dcont[m][kpar][l][w] ([n][NPAR][L][Wpad], zero beyond W), NPAR = NVMR + 2 +
 // NDUST.  Row r = m * L + l is layer r of the per-layer arrays (no work list: a gradient call is one state, or a few).
 //     kpar < NVMR            (d[kpar] * xfac) / TOTAM[l]  (+ the Rayleigh k, dTAURAY, of every gas: :3955-3957)

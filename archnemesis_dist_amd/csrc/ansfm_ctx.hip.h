@@ -140,8 +140,9 @@ struct ansfm_ctx {
     std::vector<double> h_delg;
     // resident continuum sources on the table's grid (ansfm_upload_cia / ansfm_upload_dust; a new table clears them)
     //   cia_tab: cia_waven [NWC], K_CIA [NPAIR][NPE][NT][NWC], cia_temp [NT], cia_frac [nfrac], k_co2, k_n2n2, k_n2h2 [W] each
-    //   cia_idx: igas1, igas2 [NPAIR];  cia_lay: the CiaLayer records of a call's rows;  dust_kext: kext_w [NDUST][Wpad]
-    DevBuf cia_tab, cia_idx, cia_lay, dust_kext;
+    //   cia_idx: igas1, igas2 [NPAIR];  cia_lay: the CiaLayer records of a call's rows;  dust_kext: kext_w [NDUST][Wpad];
+    //   dust_ksca: ksca_w [NDUST][Wpad], the scattering cross sections beside it (the multiple-scattering continuum reads them)
+    DevBuf cia_tab, cia_idx, cia_lay, dust_kext, dust_ksca;
     int cia_on = 0, cia_ispace = 0, cia_NWC = 0, cia_NPAIR = 0, cia_NPE = 0, cia_NT = 0, cia_nfrac = 0, cia_NPARA = 0, cia_NVMR = 0,
         cia_ico2 = -1, cia_in2 = -1, cia_ih2 = -1, cia_covers = 0;
     int dust_n = 0;                         // NDUST of the uploaded aerosol source, 0: none
@@ -159,6 +160,7 @@ struct ansfm_ctx {
     int map_dims[4] = {0, 0, 0, 0};     // W, NPAR, NPRO, P of map_out
     DevBuf gscratch, perm, dkbuf, trold_ws, dspec_i, dcont_t, tmp_in2, tmp_out2, lbl_li;
     DevBuf ms_taus, ms_omegas, ms_bnu;   // scattering branch of CIRSrad: TAUTOT / OMEGA (W,G,L) and BB (W,L) in HBM
+    DevBuf ms_cont_rows;                 // ansfm_cirsrad_ck_scatter_batch_cont: the rows k_ms_cont_rows forms, TAUCIA / TAUDUST / TAURAY / TAUSCAT [R][W] and the fractions [R][ncont][W]
     DevBuf ms_tauray_l, ms_lfrac_l;      // the continuum by rows: TAURAY / aerosol fractions of a launch's models (the model-by-model route: one model's dense arrays)
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
@@ -251,7 +253,7 @@ struct DedupRows {
 struct DedupCols;
 int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
                const DedupCols *cols, DedupRows *out);
-// a table has been uploaded: the continuum sources on the old grid go
+// a table has been uploaded: the continuum sources on the old grid go (dust_n = 0: kext_w and ksca_w alike)
 inline void clear_continuum_sources(ansfm_ctx *ctx) { ctx->cia_on = 0; ctx->dust_n = 0; }
 // a continuum formed from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust) and the Rayleigh
 // parametrisations: the arrays are device pointers over the n * L layers of the call
@@ -259,6 +261,11 @@ struct ContCall {
     int ISPACE = 0, use_cia = 0, use_dust = 0, ray_mode = 0;
     const double *temp = nullptr, *q = nullptr, *frac = nullptr, *totam = nullptr, *delh = nullptr, *cont = nullptr, *f4 = nullptr;
 };
+// ansfm_api.hip: dedup_rows with the columns the continuum of c is formed from as part of a layer's identity -- the column
+// (CIA, Rayleigh), the Rayleigh composition (ray_mode 4), the mixing ratios and the thickness (CIA), the para-H2 fraction (a
+// CIA table with a para-H2 axis) and the aerosol columns
+int dedup_rows_cont(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount, const ContCall &c,
+                    DedupRows *out);
 // ansfm_api.hip, what the gradient RT entries and the transit entry (ansfm_transit.hip) share (described where they are
 // defined): the gas stage of a gradient call, the merge slot behind every parameter, the end of a call without a generic rerun
 int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
@@ -276,6 +283,10 @@ void launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int ISPACE
 // ansfm_ops.hip: k_cia_rows_prep + k_tau_cont_rows for the thermal branch, into ctx->cont_t [rows][Wpad]: (TAUCIA + TAUDUST) +
 // TAURAY of the rows from the resident sources (ContCall, above)
 int launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c);
+// ansfm_ops.hip: k_cia_rows_prep + k_ms_cont_rows for the multiple-scattering batch, into ctx->ms_cont_rows: the five arrays of
+// the rows in the layout ansfm_cirsrad_ck_scatter_batch_rows takes, [rows][W] / [rows][NDUST][W]; a term that is not used is null
+struct MsContRows { const double *cia, *dust, *ray, *sca, *lf; };
+int launch_ms_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, MsContRows *out);
 // ansfm_ops.hip: k_dtau_cont_rows for the gradient thermal branch, into ctx->dcont_t [n][NPAR][L][Wpad]: dTAUCON of the n * L
 // layers from the resident sources.  After launch_tau_cont_rows(ctx, n * L, nullptr, c) on the same stream: the CIA records in
 // ctx->cia_lay are that launch's.

@@ -61,6 +61,27 @@ int ansfm::launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_ro
     return ANSFM_OK;
 }
 
+int ansfm::launch_ms_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, MsContRows *out)
+{
+    const size_t RW = (size_t)rows * ctx->W, nd = c.use_dust ? (size_t)ctx->dust_n : 0;
+    HIPCHK(ctx->ms_cont_rows.reserve((4 + nd) * RW * sizeof(double)));
+    MsContRowsParams p;
+    int rc;
+    if ((rc = cont_rows_params(ctx, rows, slot_rows, c, p.c))) return rc;
+    double *b = ctx->ms_cont_rows.as<double>();
+    p.ksca_w = ctx->dust_ksca.as<double>();
+    p.taucia = c.use_cia ? b : nullptr; p.taudust = c.use_dust ? b + RW : nullptr; p.tauray = c.ray_mode ? b + 2 * RW : nullptr;
+    p.tauscat = c.use_dust ? b + 3 * RW : nullptr; p.lfrac = c.use_dust ? b + 4 * RW : nullptr;
+    if (c.use_cia) {
+        hipLaunchKernelGGL(k_cia_rows_prep, dim3(nblk((size_t)rows, 64)), dim3(64), 0, ctx->stream, p.c);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ms_cont_rows, dim3((unsigned)rows, nblk((size_t)ctx->W, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    *out = MsContRows{p.taucia, p.taudust, p.tauray, p.tauscat, p.lfrac};
+    return ANSFM_OK;
+}
+
 int ansfm::launch_dtau_cont_rows(ansfm_ctx *ctx, int n_models, int L, int NVMR, int NPAR, const ContCall &c)
 {
     const int rows = n_models * L;
@@ -622,8 +643,9 @@ int ansfm_upload_dust(ansfm_ctx *ctx, int NWS, const double *SWAVE, int NDUST, c
     p.wavec = ctx->d_wave.as<double>();
     p.W = W; p.NWS = NWS; p.NDUST = NDUST; p.cubic = cubic;
     HIPCHK(ctx->dust_kext.reserve((size_t)NDUST * Wpad * sizeof(double)));
+    HIPCHK(ctx->dust_ksca.reserve((size_t)NDUST * Wpad * sizeof(double)));
     hipLaunchKernelGGL(k_dust_kext_grid, dim3(nblk((size_t)Wpad, 128), (unsigned)NDUST), dim3(128), 0, ctx->stream, p, Wpad,
-                       ctx->dust_kext.as<double>());
+                       ctx->dust_kext.as<double>(), ctx->dust_ksca.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));                     // the coefficients are host temporaries
     ctx->dust_n = NDUST;

@@ -53,6 +53,10 @@ struct MsCall {
     // the continuum once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows): cont_row [n][L] into R rows; taucia / taudust /
     // tauray / tauscat are then [R][W] and lfrac [R][ncont][W].  cont_row = nullptr: the dense arrays
     int R; const int32_t *cont_row;
+    // the continuum formed inside the call from the context's resident sources, once per distinct layer
+    // (ansfm_cirsrad_ck_scatter_batch_cont): the per-layer arrays [n][L] / [n][L][NVMR | ncont | 4] behind it, host pointers;
+    // taucia .. tauscat, lfrac and cont_row are null
+    int fused, use_cia, use_dust, ray_mode; const double *lay_q, *lay_frac, *lay_totam, *lay_delh, *lay_cont, *f4;
 };
 
 // one model's continuum already on the device, [W][L] / [W][ncont][L] (null = zeros): cirsrad_ck_scatter_impl stages none then
@@ -63,7 +67,7 @@ static int ms_check(ansfm_ctx *ctx, const MsCall &c, const char *fn)
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, std::string(fn) + ": upload a k-table first");
     if (c.n_models <= 0 || c.L <= 0 || !c.lay_press_pa || !c.lay_temp || !c.amount || c.ncont < 0 || c.ngeom <= 0 || c.nmu < 2 ||
         c.nf < 0 || c.nphi <= 0 || !c.radg || !c.sol_angs || !c.emiss_angs || !c.aphis || !c.solar || !c.brdf_matrix || !c.mu1 ||
-        !c.wt1 || !c.SPECOUT || (c.ISPACE != 0 && c.ISPACE != 1) || (c.ncont > 0 && (!c.phasarr || !c.lfrac || c.nth < 3)))
+        !c.wt1 || !c.SPECOUT || (c.ISPACE != 0 && c.ISPACE != 1) || (c.ncont > 0 && (!c.phasarr || (!c.lfrac && !c.fused) || c.nth < 3)))
         FAIL(ANSFM_ERR_INVALID, std::string(fn) + ": bad argument");
     return ANSFM_OK;
 }
@@ -459,6 +463,20 @@ static int ms_stage(ansfm_ctx *ctx, const MsCall &c, size_t CN, MsStaged &s)
     return st.rc;
 }
 
+// The per-layer arrays of a fused continuum (c.fused) on the device, staging slots 14 .. 19, as the continuum kernels take them
+// (ContCall); d_temp: the staged layer temperatures [n][L].  An array whose term is not used stays null.
+static int ms_stage_cont(ansfm_ctx *ctx, const MsCall &c, const double *d_temp, ContCall &k)
+{
+    const size_t nl = (size_t)c.n_models * c.L;
+    Stager st{ctx, 14};
+    k.ISPACE = c.ISPACE; k.use_cia = c.use_cia; k.use_dust = c.use_dust; k.ray_mode = c.ray_mode;
+    k.temp = d_temp;
+    k.q = st.up(c.use_cia ? c.lay_q : nullptr, nl * ctx->cia_NVMR); k.frac = st.up(c.use_cia ? c.lay_frac : nullptr, nl);
+    k.totam = st.up(c.use_cia || c.ray_mode ? c.lay_totam : nullptr, nl); k.delh = st.up(c.use_cia ? c.lay_delh : nullptr, nl);
+    k.cont = st.up(c.use_dust ? c.lay_cont : nullptr, nl * ctx->dust_n); k.f4 = st.up(c.ray_mode == 4 ? c.f4 : nullptr, nl * 4);
+    return st.rc;
+}
+
 // The optics stage's parameters from the staged inputs and the context's buffers (reserve ms_taus / ms_omegas / ms_bnu and, by
 // rows, ms_tauray_l / ms_lfrac_l first).  slot: the gas row of every (model, layer), null for one model.  The launch fills in
 // the slab and the models.
@@ -561,19 +579,28 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
 {
     const int W = ctx->W, S = ctx->S, L = c.L, n_models = c.n_models, ncont = c.ncont;
     const size_t D = sizeof(double), WL = (size_t)W * L;
-    const bool by_rows = c.cont_row != nullptr;
-    const size_t RW = by_rows ? (size_t)c.R * W : 0;
+    const bool fused = c.fused != 0, by_rows = c.cont_row != nullptr || fused;
+    const size_t RW = c.cont_row ? (size_t)c.R * W : 0;
     int rc;
     HIPCHK(hipSetDevice(ctx->device));
-    Stager sr{ctx, 14};
-    const int32_t *d_crow = by_rows ? sr.up(c.cont_row, (size_t)n_models * L) : nullptr;
+    Stager sr{ctx, fused ? 20 : 14};
+    const int32_t *d_crow = c.cont_row ? sr.up(c.cont_row, (size_t)n_models * L) : nullptr;
     const double *rsrc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (by_rows) {
+    ContCall k;                                                 // fused: every model's per-layer arrays, staged once
+    if (fused) {
+        // a model's L rows are formed from the resident sources when its turn comes; its row map is the identity
+        std::vector<int32_t> iota((size_t)L);
+        for (int l = 0; l < L; ++l) iota[l] = l;
+        d_crow = sr.up(iota.data(), (size_t)L);
+        const double *d_temp = sr.up(c.lay_temp, (size_t)n_models * L);
+        if ((rc = sr.rc) || (rc = ms_stage_cont(ctx, c, d_temp, k))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));              // iota is a host temporary
+    } else if (by_rows) {
         rsrc[0] = sr.up(c.taucia, RW); rsrc[1] = sr.up(c.taudust, RW); rsrc[2] = sr.up(c.tauray, RW); rsrc[3] = sr.up(c.tauscat, RW);
         rsrc[4] = sr.up(c.lfrac, RW * ncont);
         if ((rc = sr.rc)) return rc;
-        HIPCHK(ctx->ms_tauray_l.reserve((4 + (size_t)ncont) * WL * D));
     }
+    if (by_rows) HIPCHK(ctx->ms_tauray_l.reserve((4 + (size_t)ncont) * WL * D));
     for (int m = 0; m < n_models; ++m) {
         const size_t mm = m;
         MsCall cm = c;
@@ -582,6 +609,17 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
         cm.radg += mm * W * c.nmu; cm.SPECOUT += mm * W * c.ngeom;
         if (ctx->lblrt) ctx->st_m0 = m;                      // gas_tau reads this model's rows of the state
         if (by_rows) {
+            if (fused) {
+                ContCall km = k;                                // this model's layers
+                km.temp += mm * L;
+                if (km.q) km.q += mm * L * ctx->cia_NVMR;
+                for (const double **a : {&km.frac, &km.totam, &km.delh}) if (*a) *a += mm * L;
+                if (km.cont) km.cont += mm * L * ctx->dust_n;
+                if (km.f4) km.f4 += mm * L * 4;
+                MsContRows rw;
+                if ((rc = launch_ms_cont_rows(ctx, L, nullptr, km, &rw))) return rc;
+                rsrc[0] = rw.cia; rsrc[1] = rw.dust; rsrc[2] = rw.ray; rsrc[3] = rw.sca; rsrc[4] = rw.lf;
+            }
             const double *dense[5];
             for (int a = 0; a < 5; ++a) {
                 const int X = a < 4 ? 1 : ncont;
@@ -589,7 +627,7 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
                 dense[a] = (rsrc[a] && X > 0) ? dst : nullptr;
                 if (dense[a])
                     hipLaunchKernelGGL(k_ms_rows_expand, dim3(nblk((size_t)W, 128), (unsigned)L, (unsigned)X), dim3(128), 0, ctx->stream,
-                                       W, X, L, d_crow + mm * L, rsrc[a], dst);
+                                       W, X, L, fused ? d_crow : d_crow + mm * L, rsrc[a], dst);
             }
             HIPCHK(hipGetLastError());
             const MsDevCont dc{dense[0], dense[1], dense[2], dense[3], dense[4]};
@@ -614,7 +652,7 @@ static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, co
 {
     const int W = ctx->W, L = c.L, n_models = c.n_models, ncont = c.ncont;
     const size_t nl = (size_t)n_models * L;
-    const bool by_rows = c.cont_row != nullptr;
+    const bool by_rows = s.d_crow != nullptr;
     HIPCHK(ctx->ms_same.reserve(nl));
     unsigned char *same = *same_out = ctx->ms_same.as<unsigned char>();
     // by rows: from the two index maps alone; dense: the gas rows, then the columns of every continuum array
@@ -754,7 +792,7 @@ static int ms_wire_batch(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, con
     HIPCHK(ctx->ms_taus.reserve(opt_models * Ws * G * L * D));
     HIPCHK(ctx->ms_omegas.reserve(opt_models * Ws * G * L * D));
     HIPCHK(ctx->ms_bnu.reserve(opt_models * Ws * L * D));
-    if (c.cont_row) {
+    if (s.d_crow) {
         HIPCHK(ctx->ms_tauray_l.reserve(opt_models * Ws * L * D));
         HIPCHK(ctx->ms_lfrac_l.reserve(std::max<size_t>(opt_models * Ws * ncont * L * D, 8)));
         p.tauray = ctx->ms_tauray_l.as<double>(); p.lfrac = ctx->ms_lfrac_l.as<double>(); p.cont_local = 1;
@@ -801,7 +839,7 @@ static int ms_run_slabs(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, cons
             HIPCHK(hipGetLastError());
         }
         p.w0 = (int)w0; p.wcount = wc;
-        if (c.cont_row) { p.st_wl = (size_t)wc * L; p.st_wcl = (size_t)wc * c.ncont * L; }       // between launch positions
+        if (s.d_crow) { p.st_wl = (size_t)wc * L; p.st_wcl = (size_t)wc * c.ncont * L; }       // between launch positions
         ms_launch_optics(ctx->stream, o, (int)w0, wc, 0, 1, nullptr);
         p.m0 = 0; p.n_launch = 1;
         if ((rc = ms_launch_chain<1>(ctx, r.chain, ctx->stream, p))) return rc;
@@ -820,7 +858,7 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     int rc = ms_check(ctx, c, "cirsrad_ck_scatter_batch");
     if (rc || (rc = ms_check_rows(ctx, c))) return rc;           // before anything is launched
     const int W = ctx->W, G = ctx->G, L = c.L, n_models = c.n_models;
-    const bool by_rows = c.cont_row != nullptr;
+    const bool by_rows = c.cont_row != nullptr || c.fused;
     ctx->ms_cache_hits = 0; ctx->ms_cache_layers = (long)n_models * L;
     // (a runtime line source has its own row map, which the (p, T, amount) comparison of the layer cache does not see)
     const bool use_cache = n_models > 1 && ctx->dedup && kn.layer_cache && !ctx->lblrt;      // any stream count
@@ -832,14 +870,25 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     MsRoute r;
     if ((rc = ms_setup(ctx, p, c, W, G, L, kn, r))) return rc;
     MsStaged s;
-    if ((rc = ms_stage(ctx, c, by_rows ? (size_t)c.R * W : (size_t)n_models * W * L, s))) return rc;
+    if ((rc = ms_stage(ctx, c, c.fused ? 0 : by_rows ? (size_t)c.R * W : (size_t)n_models * W * L, s))) return rc;
+    ContCall fc;                                                // fused: the per-layer arrays behind the continuum
+    if (c.fused && (rc = ms_stage_cont(ctx, c, s.temp, fc))) return rc;
     const double *d_tauray = s.ray;                             // no TAURAY: every model reads the same zeros
     if (!by_rows && (rc = ms_zero_tauray(ctx, (size_t)W * L, &d_tauray))) return rc;     // (by rows: the optics stage writes the slab's copy)
     // vertical gas opacities of the distinct (model, layer) rows: calc_k + k_overlap
     DedupRows k;
-    if ((rc = dedup_rows(ctx, n_models, L, s.press, s.temp, s.am, nullptr, &k)) ||
-        (rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount)))
+    if (c.fused) {
+        // one map for both: a layer is distinct when it differs from model 0's in a gas input or in a column the continuum is
+        // formed from; the continuum of the distinct rows comes from the resident sources and the row map is the gas rows'
+        MsContRows rw;
+        if ((rc = dedup_rows_cont(ctx, n_models, L, s.press, s.temp, s.am, fc, &k)) ||
+            (rc = launch_ms_cont_rows(ctx, k.rows, ctx->dd_work.as<int32_t>(), fc, &rw)))
+            return rc;
+        s.cia = rw.cia; s.dust = rw.dust; s.ray = rw.ray; s.sca = rw.sca; s.lf = rw.lf;
+        s.d_crow = ctx->dd_slot.as<int32_t>();
+    } else if ((rc = dedup_rows(ctx, n_models, L, s.press, s.temp, s.am, nullptr, &k)))
         return rc;
+    if ((rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount))) return rc;
     ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = k.rows; ctx->last_dedup = 1;
     unsigned char *same;
     int npre;
@@ -905,6 +954,42 @@ int ansfm_cirsrad_ck_scatter_batch_rows(ansfm_ctx *ctx, int ISPACE, int n_models
     const MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia_rows, taudust_rows, tauray_rows, tauscat_rows, ncont,
                    nth, phasarr, lfrac_rows, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf,
                    nphi, iray, imie, xfac, SPECOUT, nullptr, W_full, w_begin, R, cont_row};
+    return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
+}
+
+int ansfm_cirsrad_ck_scatter_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                        const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                        const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                        const double *lay_cont, int ray_mode, const double *f4, int ncont, int nth,
+                                        const double *phasarr, const double *radg, int ngeom, const double *sol_angs,
+                                        const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                        const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                        int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
+{
+    CHECK_CTX(ctx);
+    const char *fn = "cirsrad_ck_scatter_batch_cont: ";
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, std::string(fn) + "upload a k-table first");
+    if (w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
+        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
+    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
+        (!use_cia && !use_dust && !ray_mode) || ((use_cia || ray_mode) && !lay_totam) ||
+        (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont))
+        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "bad argument (at least one of use_cia, use_dust, ray_mode = IRAY 1, 2, 4 or 12; the "
+                                                  "per-layer arrays of every term that is used)");
+    if (use_cia && !ctx->cia_on)
+        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
+    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, std::string(fn) + "the CIA source was uploaded for the other ISPACE");
+    if (use_dust && !ctx->dust_n)
+        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    if (ncont != (use_dust ? ctx->dust_n : 0))
+        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
+                                    std::to_string(use_dust ? ctx->dust_n : 0) + " populations");
+    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, nullptr, nullptr, nullptr, ncont, nth, phasarr, nullptr,
+             radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT,
+             nullptr, W_full, w_begin, 0, nullptr};
+    c.fused = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0; c.ray_mode = ray_mode;
+    c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_totam = lay_totam; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
+    c.f4 = ray_mode == 4 ? f4 : nullptr;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 

@@ -1088,6 +1088,60 @@ class AnsfmEngine:
         self._check(rc, "cirsrad_ck_scatter_batch_rows")
         return out
 
+    def cirsrad_ck_scatter_batch_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phasarr,
+                                      radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie,
+                                      xfac=None, wave_slice=None, variant=None):
+        """`cirsrad_ck_scatter_batch_rows` with the rows formed inside the call from the resident sources (upload_cia,
+        upload_dust) and the Rayleigh parametrisations (ansfm_cirsrad_ck_scatter_batch_cont): q (n, NLAY, NVMR) = PP / PRESS
+        with FRAC, DELH (n, NLAY) switch CIA on (None: off); CONT (n, NLAY, NDUST) after any DUST_RENORMALISATION switches the
+        aerosols on (None: off; NDUST as uploaded = phasarr.shape[0]); IRAY 0, 1, 2 or 4 (variant='v': calc_tau_rayleighv) with
+        f4 (n, NLAY, 4) for IRAY 4 (`rayleigh_f4`); TOTAM (n, NLAY) for CIA and Rayleigh.  Host arrays.  The rest, wave_slice
+        included, as `cirsrad_ck_scatter_batch_rows` -> SPECOUT (n, NWAVE, NPATH), bit-identical to that call on the rows of
+        calc_tau_cia / calc_tau_dust / calc_tau_rayleigh."""
+        dims, _ = self.ktable_info()
+        W, G, S = dims[0], dims[1], dims[4]
+        lp = _np(lay_press_pa)
+        if lp.ndim != 2:
+            raise ValueError("lay_press_pa must be (n_models, NLAY)")
+        n, L = lp.shape
+        am = _np(amount)
+        if am.shape != (n, S, L):
+            raise ValueError("amount must be (n_models, NGAS, NLAY)")
+        lt = _np(lay_temp)
+        if lt.shape != (n, L):
+            raise ValueError("lay_temp must be (n_models, NLAY)")
+        mode = 12 if variant == "v" else int(IRAY)
+        use_cia, use_dust = q is not None, CONT is not None
+        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        arrs = {}
+        for name, a, shape in (("q", q, (n, L, getattr(self, "cia_nvmr", -1))), ("FRAC", FRAC, (n, L)), ("TOTAM", TOTAM, (n, L)),
+                               ("DELH", DELH, (n, L)), ("CONT", CONT, (n, L, ncont)), ("f4", f4, (n, L, 4))):
+            a = arrs[name] = None if a is None else _np(a)
+            if a is not None and -1 not in shape and a.shape != shape:
+                raise ValueError(f"cirsrad_ck_scatter_batch_cont: {name} must be {shape}, got {a.shape}")
+        if use_cia and (arrs["FRAC"] is None or arrs["DELH"] is None):
+            raise ValueError("cirsrad_ck_scatter_batch_cont: CIA (q given) needs FRAC and DELH")
+        if (use_cia or mode) and arrs["TOTAM"] is None:
+            raise ValueError("cirsrad_ck_scatter_batch_cont: CIA and Rayleigh need TOTAM")
+        if mode == 4 and arrs["f4"] is None:
+            raise ValueError("cirsrad_ck_scatter_batch_cont: IRAY 4 needs f4 (rayleigh_f4)")
+        if ncont > 0 and not use_dust:
+            raise ValueError("cirsrad_ck_scatter_batch_cont: CONT is needed with aerosols (phasarr given)")
+        rg = _np(radg)
+        if rg.size != n * W * nmu:
+            raise ValueError("radg must be (n_models, NWAVE, NMU)")
+        w_begin, W_full = (0, W) if wave_slice is None else (int(v) for v in wave_slice)
+        if phasarr is not None and phasarr.shape[1] != W_full:
+            raise ValueError("cirsrad_ck_scatter_batch_cont: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
+        out = np.empty((n, W, P))
+        rc = self._lib.ansfm_cirsrad_ck_scatter_batch_cont(
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
+            _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont, nth,
+            _ptr(phasarr), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu,
+            _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
+        self._check(rc, "cirsrad_ck_scatter_batch_cont")
+        return out
+
     def last_scatter_cache(self):
         """(layers of models 1..n-1 taken from model 0's doubling results, all such layers) of the last batched scatter call"""
         a = C.c_int64(); b = C.c_int64()

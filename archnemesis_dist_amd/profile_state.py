@@ -27,15 +27,24 @@ class ContinuousProfileState:
     (model_0.py from_apr_to_state_vector: x0 = ref for temperature, log(ref) otherwise; subprofretg un-logs it,
     ForwardModel_0.py:2397-2560).
 
-    H (m), P (Pa), T (K): (NPRO,); VMR (NPRO, NVMR); blocks: sequence of "T" or ("VMR", column)."""
+    H (m), P (Pa), T (K): (NPRO,); VMR (NPRO, NVMR); blocks: sequence of "T", ("VMR", column) or ("DUST", column), the last
+    an aerosol profile of DUST (NPRO, NDUST), carried as ln(value) like every non-temperature profile of model 0."""
 
-    def __init__(self, H, P, T, VMR, blocks):
+    def __init__(self, H, P, T, VMR, blocks, DUST=None):
         self.H = np.asarray(H, float); self.P = np.asarray(P, float); self.T = np.asarray(T, float)
         self.VMR = np.asarray(VMR, float)
         self.NPRO = self.H.size
-        self.blocks = [("T", None) if b == "T" else ("VMR", int(b[1])) for b in blocks]
+        self.blocks = [("T", None) if b == "T" else (str(b[0]), int(b[1])) for b in blocks]
+        for kind, j in self.blocks:
+            if kind not in ("T", "VMR", "DUST"):
+                raise ValueError("ContinuousProfileState: a block is \"T\", (\"VMR\", column) or (\"DUST\", column), got %r" % (kind,))
+        self.has_dust = any(kind == "DUST" for kind, _ in self.blocks)
+        self.DUST = None if DUST is None else np.asarray(DUST, float).reshape(self.NPRO, -1)
+        if self.has_dust and (self.DUST is None or max(j for kind, j in self.blocks if kind == "DUST") >= self.DUST.shape[1]):
+            raise ValueError("ContinuousProfileState: a DUST block needs DUST (NPRO, NDUST) with that column")
         self.NX = self.NPRO * len(self.blocks)
-        xs = [self.T if kind == "T" else np.log(self.VMR[:, j]) for kind, j in self.blocks]
+        src = {"VMR": self.VMR, "DUST": self.DUST}
+        xs = [self.T if kind == "T" else np.log(src[kind][:, j]) for kind, j in self.blocks]
         self.XN = np.concatenate(xs) if xs else np.zeros(0)
         self.NUM = np.ones(self.NX, dtype=np.int32)      # jacobian_nemesis treats every element numerically here
         self.FIX = np.zeros(self.NX, dtype=np.int32)
@@ -47,18 +56,22 @@ class ContinuousProfileState:
         return self.DSTEP
 
     def profiles(self, X):
-        """X (n, NX) -> T (n, NPRO), VMR (n, NPRO, NVMR): the model-0 part of subprofretg for n states."""
+        """X (n, NX) -> T (n, NPRO), VMR (n, NPRO, NVMR): the model-0 part of subprofretg for n states.  With a DUST block
+        the aerosol profiles DUST (n, NPRO, NDUST) follow as a third value."""
         X = np.atleast_2d(np.asarray(X, float))
         n = X.shape[0]
         T = np.repeat(self.T[None], n, 0)
         VMR = np.repeat(self.VMR[None], n, 0)
+        DUST = np.repeat(self.DUST[None], n, 0) if self.has_dust else None
         for b, (kind, j) in enumerate(self.blocks):
             xb = X[:, b * self.NPRO:(b + 1) * self.NPRO]
             if kind == "T":
                 T = xb.copy()
+            elif kind == "DUST":
+                DUST[:, :, j] = np.exp(xb)
             else:
                 VMR[:, :, j] = np.exp(xb)
-        return T, VMR
+        return (T, VMR, DUST) if self.has_dust else (T, VMR)
 
 
 class BatchedCKThermalModel:
@@ -81,6 +94,8 @@ class BatchedCKThermalModel:
     def __init__(self, eng, state, RADIUS, ID, ISO, igas_map, layering_args=None, geometry=None, ISPACE=0, IRAY=0,
                  TSURF=-1.0, extra_continuum=None, DUST=None, PARAH2=None, cia=None, dust=None):
         self.eng, self.state = eng, state
+        if getattr(state, "has_dust", False):
+            raise NotImplementedError("BatchedCKThermalModel: a state with a DUST block belongs to scatter_state.BatchedCKScatterModel")
         self.RADIUS = float(RADIUS)
         self.ID = np.asarray(ID); self.ISO = np.asarray(ISO)
         self.igas_map = np.asarray(igas_map, dtype=np.int64)

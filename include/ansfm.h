@@ -614,6 +614,32 @@ int ansfm_cirsrad_ck_scatter_batch_rows(ansfm_ctx *ctx, int ISPACE, int n_models
                                         const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
                                         const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
+/* The same batch with the rows formed inside the call from the context's resident sources (ansfm_upload_cia,
+ * ansfm_upload_dust, which keeps the scattering cross sections too) and the Rayleigh parametrisations: nothing of the
+ * continuum crosses PCIe.  In place of R, cont_row and the five row arrays the entry takes the continuum block of
+ * ansfm_cirsrad_ck_thermal_cont_dev, as host arrays like every other argument: use_cia with lay_q [n][L][NVMR] (NVMR as
+ * uploaded), lay_frac, lay_delh [n][L]; use_dust with lay_cont [n][L][ncont]; ray_mode (0, or IRAY 1, 2, 4, 12) with f4
+ * [n][L][4] for mode 4; lay_totam [n][L] for CIA and Rayleigh.  Per distinct row (k_ms_cont_rows) TAUCIA and TAURAY are what
+ * ansfm_calc_tau_cia / ansfm_calc_tau_rayleigh give; per population d, e_d = (kext 1e-4) CONT and s_d = (ksca 1e-4) CONT as
+ * ansfm_calc_tau_dust rounds them, TAUDUST = sum_d clip(nan_to_num(e_d), 0, 1e20), TAUSCAT = sum_d s_d (raw) and the fraction
+ * of d is s_d / TAUSCAT where TAUSCAT > 0, else 0 (ForwardModel_0.py:3963-3972, :5107-5113) -- the result is bit-identical to
+ * ansfm_cirsrad_ck_scatter_batch_rows on rows formed that way.  A term that is not used is absent (NULL to the optics), not
+ * zeros.  One row map serves gas opacities and continuum: a layer is distinct when it differs from model 0's in pressure,
+ * temperature, an amount or a column its continuum is formed from (lay_totam; f4; lay_q, lay_delh and, for a CIA table with
+ * a para-H2 axis, lay_frac; lay_cont), and counts as model 0's exactly when its row is model 0's row of that layer.  The
+ * model-by-model route (n_models = 1, ansfm_set_layer_dedup(ctx, 0), ANSFM_MS_LAYER_CACHE=0) forms the L rows of one model at
+ * a time.  ANSFM_ERR_INVALID, before anything is launched: a source that is used has not been uploaded since the last table,
+ * the CIA source was uploaded for the other ISPACE, ncont is not the number of populations uploaded (0 without use_dust), no
+ * term is used or one of its arrays is NULL, and for the slice entry's reasons.  ansfm_last_scatter_cache /
+ * ansfm_last_layer_rows / ansfm_last_scatter_windows report as for the rows entry. */
+int ansfm_cirsrad_ck_scatter_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                        const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                        const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                        const double *lay_cont, int ray_mode, const double *f4, int ncont, int nth,
+                                        const double *phasarr, const double *radg, int ngeom, const double *sol_angs,
+                                        const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
+                                        const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
+                                        int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total);
 /* Spectral windows of phase matrices / Hansen factors in the last scattering call (ansfm_cirsrad_ck_scatter(_batch),
  * ansfm_scloud11wave_core) and the wavenumbers per window: 1 and W when one window covers the axis (always at G > 1). */
@@ -907,7 +933,8 @@ int ansfm_upload_cia(ansfm_ctx *ctx, int ISPACE, int NWC, const double *cia_wave
                      const double *k_n2n2, int ih2, const double *k_n2h2);
 /* ansfm_upload_dust: the extinction cross sections KEXT[NWS][NDUST] on SWAVE evaluated on the table's grid exactly as
  * ansfm_calc_tau_dust evaluates them (KSCA[NWS][NDUST] decides with KEXT where the linear interpolant replaces the spline,
- * :4849-4859; NULL: zeros) and kept as kext_w[NDUST][Wpad].  NDUST > 7 is ANSFM_ERR_UNSUPPORTED: NumPy sums eight and more
+ * :4849-4859; NULL: zeros) and kept as kext_w[NDUST][Wpad]; the scattering cross sections, evaluated by the same body in the
+ * same launch, are kept beside them as ksca_w[NDUST][Wpad] for ansfm_cirsrad_ck_scatter_batch_cont.  NDUST > 7 is ANSFM_ERR_UNSUPPORTED: NumPy sums eight and more
  * populations pairwise, fewer in order, and the fused entry sums in order. */
 int ansfm_upload_dust(ansfm_ctx *ctx, int NWS, const double *SWAVE, int NDUST, const double *KEXT, const double *KSCA);
 int ansfm_clear_continuum_sources(ansfm_ctx *ctx);

@@ -58,7 +58,138 @@ def main():
         bench_cia(eng, out)
     if only == "grad_cont":                                 # 0.1 GB dTAUCON assembled on the host for the route it replaces: on request only
         bench_grad_cont(eng, out)
+    if only == "scatter_cont":                              # 13 GB of host arrays in the by-hand route: on request only
+        bench_scatter_cont(eng, out)
     print(json.dumps(out, indent=1))
+
+
+def bench_scatter_cont(eng, out, W=10000, n=5):
+    """C4-size scattering Jacobian (W = 1e4, G = 20, 100 layers, 8 gases, synth_cia, two aerosol populations, IRAY 4; T and one
+    aerosol profile through 100 levels: 201 states) at 5 streams / NF 2 and 16 / NF 8, whole axis and the last eighth of it:
+      (a) fused:   jacobian_nemesis_batched(BatchedCKScatterModel), the continuum formed inside the call;
+      (b) by hand: the same Jacobian written here with what the parent of that entry has -- profiles, layer_average,
+          calc_tau_cia / calc_tau_dust / calc_tau_rayleigh_batch_dev over all 20 100 layers, ContinuumRows,
+          cirsrad_ck_scatter_batch_rows, the quotient.  Runs on a checkout without the fused entry too ((a) is left out).
+        python tools/bench_extra.py scatter_cont [W] [repeats of (b)] [5|16: that stream count only]"""
+    import torch
+    import bench as B
+    from archnemesis_dist_amd import layering
+    from archnemesis_dist_amd.continuum_rows import ContinuumRows
+    from archnemesis_dist_amd.jacobian import chunk_range, finite_difference_jacobian_dev, perturbed_states
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    nb = int(sys.argv[3]) if len(sys.argv) > 3 else n
+    streams = [(5, 2), (16, 8)] if len(sys.argv) <= 4 else [s for s in [(5, 2), (16, 8)] if s[0] == int(sys.argv[4])]
+    dev = torch.device("cuda", eng.device)
+    G, S, L, NP, NT, NPRO, ND = 20, 8, 100, 20, 15, 100, 2
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    WAVE_all = 200.0 + (1000.0 / W) * np.arange(W)
+    pr = syn.synth_profiles(NPRO, S + 2, seed=11)
+    ID, ISO, igas = pr["ID"], pr["ISO"], list(range(2, S + 2))
+    zl = np.linspace(0.0, 1.0, NPRO)
+    DUST = np.stack([2.0e3 * np.exp(-4.0 * zl), 3.0e2 * np.exp(-((zl - 0.4) / 0.1) ** 2) + 1.0e-3], axis=1)
+    SWAVE = np.linspace(0.9 * WAVE_all[0], 1.1 * WAVE_all[-1], 12)
+    xs = np.linspace(0.0, 1.0, 12)[:, None]
+    KEXT = 1.0e-9 * (1.0 + 0.6 * np.sin(5.0 * xs + np.arange(ND)[None])) * (1.0 + np.arange(ND)[None])
+    KSCA = 0.7 * KEXT * (1.0 - 0.5 * xs)
+    cia = syn.synth_cia()
+    TH = np.linspace(0.0, 180.0, 41); cth = np.cos(np.deg2rad(TH))
+    ph = np.zeros((ND, W, 2, TH.size))
+    for d, g in enumerate((0.6, 0.3)):
+        ph[d, :, 0, :] = ((1 - g * g) / (1 + g * g - 2 * g * cth) ** 1.5 / (4 * np.pi))[None]
+        ph[d, :, 1, :] = cth[None]
+    ph = np.ascontiguousarray(ph[:, :, :, ::-1])
+    la = dict(NLAY=L, LAYTYP=layering.EQUAL_LOG_PRESSURE, LAYINT=1, LAYHT=0.0, LAYANG=0.0, NINT=101)
+    BASEH, BASEP = layering.layer_split(pr["RADIUS"], pr["H"], pr["P"], LAYANG=0.0, LAYHT=0.0, NLAY=L, LAYTYP=la["LAYTYP"])
+    XN = np.concatenate([pr["T"], np.log(DUST[:, 0])])
+    inum = np.arange(XN.size)
+    sol, emi, azi = [30.0], [20.0], [45.0]
+    have_fused = hasattr(eng, "cirsrad_ck_scatter_batch_cont")
+    res = {"W": W, "G": G, "S": S, "L": L, "states": XN.size + 1, "median_of_fused": n, "median_of_by_hand": nb}
+
+    def by_hand(WAVE, ws, NMU, NF, MU, WT):
+        """(YN, KK) with entries of the parent commit only"""
+        Wl = WAVE.size
+        X = perturbed_states(XN, 0.05 * XN).T                                 # (201, NX)
+        ns = X.shape[0]
+        T = X[:, :NPRO].copy()
+        D = np.repeat(DUST[None], ns, 0); D[:, :, 0] = np.exp(X[:, NPRO:])
+        rep = lambda a: np.repeat(np.asarray(a, float)[None], ns, 0)
+        o = eng.layer_average(pr["RADIUS"], rep(pr["H"]), rep(pr["P"]), T, ID, rep(pr["VMR"]), D, None, BASEH, BASEP, LAYANG=0.0,
+                              LAYINT=1, LAYHT=0.0, NINT=101)
+        lay = dict(zip(("HEIGHT", "PRESS", "TEMP", "TOTAM", "AMOUNT", "PP", "CONT", "FRAC", "DELH", "BASET", "LAYSF"), o))
+        amount = np.ascontiguousarray(np.transpose(lay["AMOUNT"][:, :, igas], (0, 2, 1))) * 1.0e-4
+        flat = lambda a: np.ascontiguousarray(a).reshape((ns * L,) + a.shape[2:])
+        per_state = lambda a: np.moveaxis(a.reshape((Wl, ns, L) + a.shape[2:]), 1, 0)
+        tcia = per_state(eng.calc_tau_cia(0, WAVE, cia["CIA_WAVEN"], cia["CIA_TEMP"], cia["CIA_FRAC"], cia["NPARA"], cia["K_CIA"],
+                                          cia["IPAIRG1"], cia["IPAIRG2"], cia["INORMALT"], cia["INORMAL"], cia["INORMALD"], ID, ISO,
+                                          flat(lay["PP"]), flat(lay["PRESS"]), flat(lay["TEMP"]), flat(lay["FRAC"]),
+                                          flat(lay["TOTAM"]), flat(lay["DELH"]), with_grad=False))
+        td1, tcs = eng.calc_tau_dust(WAVE, SWAVE, KEXT, KSCA, flat(lay["CONT"]))[:2]
+        td1 = np.clip(np.nan_to_num(td1), 0, 1e20)
+        dsum, ssum = np.sum(td1, 2), np.sum(tcs, 2)
+        del td1
+        frac = np.zeros_like(tcs)
+        ii = np.where(ssum > 0.0)
+        frac[ii[0], ii[1], :] = (tcs[ii[0], ii[1], :].T / ssum[ii[0], ii[1]]).T
+        del tcs, ii
+        tdust, tsca, frac = per_state(dsum), per_state(ssum), per_state(frac)
+        ray = torch.empty((ns, Wl, L), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        eng.calc_tau_rayleigh_batch_dev(4, 0, np.ascontiguousarray(lay["TOTAM"]), ray, ID=ID, ISO=ISO,
+                                        VMR=lay["PP"] / lay["PRESS"][:, :, None])
+        eng.synchronize()
+        tray = ray.cpu().numpy(); del ray
+        pk = ContinuumRows(L, ND)
+        for m in range(ns):
+            pk.add_state(tcia[m], tdust[m], tray[m], tsca[m], np.transpose(frac[m], (0, 2, 1)))
+        del tcia, tdust, tray, tsca, frac
+        c1, c2 = 1.1911e-12, 1.439
+        radg = np.stack([np.repeat((c1 * WAVE ** 3 / (np.exp(c2 * WAVE / lay["TEMP"][m, 0]) - 1.0))[:, None], NMU, 1) for m in range(ns)])
+        Y = eng.cirsrad_ck_scatter_batch_rows(0, lay["PRESS"], lay["TEMP"], amount, pk.cont_row, pk.TAUCIA_rows, pk.TAUDUST_rows,
+                                              pk.TAURAY_rows, pk.TAUSCAT_rows, ph, pk.lfrac_rows, radg, sol, emi, azi,
+                                              np.full(Wl, 1.0e-8), 0, np.zeros((Wl, NMU, NMU, NF + 1)), MU, WT, NF, 101, 4, 1,
+                                              wave_slice=(ws, W))
+        info = (eng.last_layer_rows(), eng.last_scatter_cache(), pk.R)
+        Y = torch.as_tensor(Y.reshape(ns, -1), dtype=torch.float64, device=dev)
+        return finite_difference_jacobian_dev(Y, XN, inum, FIX=np.zeros(XN.size, dtype=np.int32)), info
+
+    def times(f, reps):
+        f(); ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t = time.perf_counter(); r = f(); torch.cuda.synchronize(); ts.append(time.perf_counter() - t)
+        return {"median_s": float(np.median(ts)), "min_s": float(min(ts)), "max_s": float(max(ts))}, r
+
+    for part, (ws, we) in (("whole_axis", (0, W)), ("one_rank_of_eight", chunk_range(W, 8, 7))):
+        WAVE = WAVE_all[ws:we]
+        PRESS, TEMP, K = B.torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+        K = K[ws:we].contiguous()
+        eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+        torch.cuda.empty_cache()
+        for NMU, NF in streams:
+            xq, wq = np.polynomial.legendre.leggauss(NMU)
+            MU, WT = 0.5 * (xq + 1.0), 0.5 * wq
+            r = {}
+            if have_fused:
+                from archnemesis_dist_amd.jacobian import jacobian_nemesis_batched
+                from archnemesis_dist_amd.profile_state import ContinuousProfileState
+                from archnemesis_dist_amd.scatter_state import BatchedCKScatterModel
+                st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T", ("DUST", 0)], DUST=DUST)
+                model = BatchedCKScatterModel(eng, st, pr["RADIUS"], ID, ISO, igas, ph, MU, WT, NF, 101, sol, emi, azi,
+                                              np.full(we - ws, 1.0e-8), layering_args=la, IRAY=4, IMIE=1, cia=cia,
+                                              dust=dict(SWAVE=SWAVE, KEXT=KEXT, KSCA=KSCA))
+                if (ws, we) != (0, W):                            # the model on a slice: spectra_batch with the slice's place
+                    whole = model.spectra_batch
+                    model.spectra_batch = lambda X, device=None: whole(X, device, wave_slice=(ws, W))
+                r["fused"], (YN, KK) = times(lambda: jacobian_nemesis_batched(model), n)
+                r["fused_rows"], r["fused_cache"] = list(model.last_rows), list(model.last_cache)
+            if nb > 0:
+                r["by_hand"], ((YN_b, KK_b), info) = times(lambda: by_hand(WAVE, ws, NMU, NF, MU, WT), nb)
+                r["by_hand_gas_rows"], r["by_hand_cache"], r["by_hand_continuum_rows"] = list(info[0]), list(info[1]), info[2]
+                if have_fused:
+                    r["fused_equals_by_hand"] = bool(np.array_equal(YN, YN_b) and np.array_equal(KK, KK_b))
+            res["%s_nmu%d_nf%d" % (part, NMU, NF)] = r
+    out["jacobian_C4_scatter_cont"] = res
 
 
 def bench_next(eng, out, rng):
