@@ -480,6 +480,22 @@ int ansfm_last_merge_order(const ansfm_ctx *cctx, int *applied, int64_t *valid_b
     return ANSFM_OK;
 }
 
+int ansfm_last_merge_suffix(const ansfm_ctx *cctx, int64_t *rows, int64_t *rows_of_list_merges)
+{
+    ansfm_ctx *ctx = const_cast<ansfm_ctx *>(cctx);     // as ansfm_last_merge_rowmajor
+    CHECK_CTX(ctx);
+    if (!rows || !rows_of_list_merges) FAIL(ANSFM_ERR_INVALID, "last_merge_suffix: null argument");
+    *rows = *rows_of_list_merges = 0;
+    if (ctx->d_flag.bytes < kFlagInts * sizeof(int)) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long v[kMergeTotals] = {0, 0, 0, 0};  // walked merges, all merges, pattern bytes, rows walked behind a list phase
+    HIPCHK(hipMemcpyAsync(v, ctx->d_flag.as<int>() + kFlagTileCounter + 8, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *rows = (int64_t)v[3];
+    *rows_of_list_merges = (int64_t)(v[1] - v[0]) * ctx->last_merge_G;
+    return ANSFM_OK;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* launches                                                                                    */
 /* ------------------------------------------------------------------------------------------ */

@@ -89,10 +89,10 @@ using ansfm::FusedRoute;
 using ansfm::LblrtIso;
 
 // ints of ansfm_ctx::d_flag: 0 the upload kernels' flag, 1 "unsorted input", 12 the de-duplication's row counter, 13 the
-// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's three
-// 64-bit totals (row-major merges, all merges, non-zero pattern bytes read), which one memset per launch clears together
+// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's four
+// 64-bit totals (row-major merges, all merges, non-zero pattern bytes read, rows walked behind a list phase), which one memset per launch clears together
 // (merge_launch_begin)
-constexpr int kFlagInts = 32, kFlagTileCounter = 16, kMergeTotals = 3;
+constexpr int kFlagInts = 32, kFlagTileCounter = 16, kMergeTotals = 4;
 static_assert(kFlagTileCounter + 8 + 2 * kMergeTotals <= kFlagInts, "the totals lie inside d_flag");
 
 struct ansfm_ctx {
@@ -128,6 +128,7 @@ struct ansfm_ctx {
         }
     } merge_hint_key;               // source < 0: no launch has written a hint
     long table_generation = 0;      // counts the uploads of a table (ansfm_upload_ktable*)
+    int last_merge_G = 0;              // the g-ordinates of the last forward merge launch (ansfm_last_merge_suffix)
     bool last_merge_ordered = false;   // the last forward merge launch read valid pattern bytes (ansfm_last_merge_order)
     bool have_table = false;
     int grid_f32 = 0, delg_f32 = 0;

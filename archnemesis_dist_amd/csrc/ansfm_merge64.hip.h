@@ -424,10 +424,45 @@ __device__ __forceinline__ void merge_init(double (&R)[NR], int G, const MergeOr
 // the popped order is row-major iff K(i, G-1) < K(i+1, 0) for every i + 1 < G -- the doubles the list itself compares, ties
 // included.  R holds the heads K(i, 0) as merge_init left them: in a lane whose heads were not ascending they are the sorted
 // heads instead, and such a lane fails by itself (passing would put K(i, 0) < K(i, G-1) < R[i+1] for every i, i.e. row i's
-// head among the i + 1 smallest for every i, i.e. the heads ascending).  True when every active lane of the wave passes;
-// lane_passes: this lane's own verdict (the pattern bytes of the wavenumber order, merge_order_inverse).
+// head among the i + 1 smallest for every i, i.e. the heads ascending).  lane_passes: this lane's own verdict (the pattern
+// bytes of the wavenumber order, merge_order_inverse).
+//
+// The partial form (merge_suffix_row): rows i0 .. G-1 are a separable SUFFIX when every key of the rows below i0 is below
+// K(i0, 0) and the rows from i0 on sort row by row.  With M(i) = max over i' <= i of K(i', G-1), the largest key of the rows 0 .. i,
+// that is M(i) < R[i+1] for every i in i0-1 .. G-2 -- boundary i of the test, with the running maximum in the place of K(i, G-1).
+// (A merged operand ascends only up to rounding, so K(i', G-1) <= K(i, G-1) for i' < i is not given; where every boundary
+// passes the K(i, G-1) ascend through the heads between them and M(i) = K(i, G-1): the full verdict is what it was.)
+// It also covers a lane whose heads merge_init_order put in order: the rows 0 .. i have their heads below M(i) < R[i+1], so they
+// are the i + 1 smallest heads, for every i >= i0-1 -- R[i] is row i's own head for every i >= i0 and R[0 .. i0) are the heads
+// of the rows below i0, sorted.  The list merge of those rows then pops its G * i0 keys, all below R[i0], in the order the full
+// merge does, the sentinels of its exhausted rows sink past R[i0 .. G), and what follows is rows i0 .. G-1 row by row.
+// Returns the wave's i0: the upper row of the last boundary that some active lane fails, plus one -- 0 (every lane passes every
+// boundary: the whole merge is walked), or 2 .. G (G: the boundary G-2 fails, no suffix; 1 does not occur).
 template <int NR>
-__device__ __forceinline__ bool merge_rowmajor_test(const double (&R)[NR], int G, const MergeOrient &mo, bool &lane_passes)
+__device__ __forceinline__ int merge_rowmajor_test(const double (&R)[NR], int G, const MergeOrient &mo, bool &lane_passes)
+{
+    const double cl = lds_ld(mo.cbase + (unsigned)(G - 1) * 512u);
+    const unsigned lowc = (unsigned)(G - 1) << mo.csh;
+    bool fail = false;
+    int i0 = 0;
+    double top = 0.0;
+#pragma unroll
+    for (int i = 0; i + 1 < NR; ++i) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(lds_ld(mo.rbase + (unsigned)(i < G ? i : 0) * 512u) + cl);
+        const double last = __longlong_as_double((long long)((b & ~0x7FFULL) | (unsigned long long)(((unsigned)i << mo.rsh) | lowc)));
+        if (i == 0) top = last;
+        else asm("v_max_f64 %0, %1, %2" : "=v"(top) : "v"(top), "v"(last));
+        const bool f = (i + 1 < G) & !(top < R[i + 1]);
+        fail |= f;
+        if (__builtin_amdgcn_ballot_w64(f) != 0) i0 = i + 2;       // the compare's own mask and scalar code
+    }
+    lane_passes = !fail;
+    return i0;
+}
+// The test as the lists shorter than kSuffixMinList run it, which take a merge whole or not at all: K(i, G-1) < R[i+1] for every
+// boundary, every active lane (the same verdict as i0 = 0 above; no running maximum, no row)
+template <int NR>
+__device__ __forceinline__ bool merge_rowmajor_whole(const double (&R)[NR], int G, const MergeOrient &mo, bool &lane_passes)
 {
     const double cl = lds_ld(mo.cbase + (unsigned)(G - 1) * 512u);
     const unsigned lowc = (unsigned)(G - 1) << mo.csh;
@@ -440,6 +475,14 @@ __device__ __forceinline__ bool merge_rowmajor_test(const double (&R)[NR], int G
     }
     lane_passes = !fail;
     return __builtin_amdgcn_ballot_w64(fail) == 0;
+}
+// The shortest suffix that is walked: below it the merge keeps the list to its end (measured)
+constexpr int kSuffixMinRows = 1;
+// The row from which a merge is walked, from the test's i0: 0 the whole merge, G none of it (the list with its peeled tail),
+// between them G * i0 full-length list steps and then the rows i0 .. G-1
+__device__ __forceinline__ int merge_suffix_row(int i0, int G, bool suffix_on)
+{
+    return i0 == 0 || (suffix_on && i0 <= G - kSuffixMinRows) ? i0 : G;
 }
 // The columns j < merge_rowmajor_sure_cols(NR) exist in every launch of list length NR: the launcher takes the smallest list
 // length >= G (merge_list_len: 8, 10, 16, 20, 32) and the division-free walk needs G >= 2.  Saves the guard j < G, nothing else.
@@ -471,19 +514,19 @@ __device__ __forceinline__ void merge_rowmajor_weights(double (&w)[NR], double &
 #pragma unroll
     for (int j = 0; j < NR; ++j) w[j] = lds_ld(wa + (unsigned)(j < merge_rowmajor_sure_cols(NR) || j < G ? j : 0) * 256u);
 }
-// The walk of a merge that merge_rowmajor_test passed, without the list: the same elements in the same order through the same
-// merge_walk_nodiv, so ws ends as the list path leaves it.  Row and column are loop counters, the columns stay in registers
+// The walk of the rows i0 .. G-1 of a merge whose test gave i0 (0: the whole merge; else ws comes from the list phase of the rows
+// below), without the list: the same elements in the same order through the same merge_walk_nodiv, so ws ends as the list path leaves it.  Row and column are loop counters, the columns stay in registers
 // (where the list kept its heads), and the weights and the entry of row i + 1 are read while row i is walked -- nothing
 // depends on a value fetched in the step before.  Two rows per trip: the two sets of weights alternate without a copy.
 template <int NR>
-__device__ __forceinline__ void merge_rowmajor(int G, const MergeOrient &mo, WalkState &ws, double *rec)
+__device__ __forceinline__ void merge_rowmajor(int i0, int G, const MergeOrient &mo, WalkState &ws, double *rec)
 {
     double c[NR], w0[NR], a0;
 #pragma unroll
     for (int j = 0; j < NR; ++j) c[j] = lds_ld(mo.cbase + (unsigned)(j < G ? j : 0) * 512u);
     if constexpr (NR > 20) {
         // arrays of 32 weights beside the 32 columns do not fit the registers of two waves per SIMD: a weight is read for its step
-        for (int i = 0; i < G; ++i) {
+        for (int i = i0; i < G; ++i) {
             const unsigned wa = kLdsWT + ((unsigned)i << 3);
             a0 = lds_ld(mo.rbase + ((unsigned)i << 9));
 #pragma unroll
@@ -498,8 +541,8 @@ __device__ __forceinline__ void merge_rowmajor(int G, const MergeOrient &mo, Wal
         return;
     }
     double w1[NR], a1;
-    merge_rowmajor_weights<NR>(w0, a0, 0, G, mo);
-    for (int i = 0; i < G; i += 2) {
+    merge_rowmajor_weights<NR>(w0, a0, i0, G, mo);
+    for (int i = i0; i < G; i += 2) {
         merge_rowmajor_weights<NR>(w1, a1, i + 1 < G ? i + 1 : i, G, mo);
         merge_rowmajor_row<NR>(a0, c, w0, G, ws, rec);
         if (i + 1 < G) {

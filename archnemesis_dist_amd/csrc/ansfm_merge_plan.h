@@ -33,6 +33,9 @@ constexpr int kFlagLaneRows = 1, kFlagRowMajor = 2;      // k_ck_overlap's argum
 // a further bit of flags, set only with kFlagLaneRows and a table launch, reported by ansfm_last_merge_table_layout and not in the
 // trims: the table is read from its g-fastest copy (OverlapParams::lnKg, load_gas_rows)
 constexpr int kFlagTableGfast = 4;
+// a further bit, never set by default and read by the table kernels only: ANSFM_MERGE_SUFFIX=0, a merge that is not row-major
+// from its first row keeps the head list to its end (merge_suffix_row)
+constexpr int kFlagSuffixOff = 8;
 // The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
 ANSFM_HD constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
 // Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
@@ -59,6 +62,9 @@ inline int merge_list_len(int G)
 }
 // the shortest list at which a launch orders a block's wavenumbers (MergePlan::order)
 constexpr int kMergeOrderMinList = 16;
+// the shortest list whose kernels carry the walk of a list merge's separable top rows (MergePlan::suffix; a compile-time choice of
+// k_ck_overlap by its list length, no bit of flags): measured at C2, G = 10 loses with every kSuffixMinRows (+0.02 ms of 0.98)
+constexpr int kSuffixMinList = 16;
 // f(std::integral_constant<int, D>) at D = merge_list_len(G): how a launcher names the instantiation for a run-time G
 template <class F>
 auto by_list_len(int G, F &&f)
@@ -95,6 +101,7 @@ struct MergeSwitches {
     bool rowmajor_off = false;      // ANSFM_MERGE_ROWMAJOR=0
     bool layout_wave = false;       // ANSFM_TABLE_LAYOUT=wave: read lnK although a g-fastest copy exists
     bool order_off = false;         // ANSFM_MERGE_ORDER=0: a block's wavenumbers in their own order, no pattern bytes written
+    bool suffix_off = false;        // ANSFM_MERGE_SUFFIX=0: no walk of the separable top rows behind a list phase
 };
 // read per launch: a caller may change the environment between two calls
 inline MergeSwitches merge_switches_from_env()
@@ -112,6 +119,7 @@ inline MergeSwitches merge_switches_from_env()
     sw.rowmajor_off = starts("ANSFM_MERGE_ROWMAJOR", '0');
     sw.layout_wave = is("ANSFM_TABLE_LAYOUT", "wave");
     sw.order_off = starts("ANSFM_MERGE_ORDER", '0');
+    sw.suffix_off = starts("ANSFM_MERGE_SUFFIX", '0');
     return sw;
 }
 
@@ -140,6 +148,8 @@ struct MergePlan {
     int opt = 0;
     // its arguments: flags (kFlag*) and the width of a row-mapped tile (1 or kLaneNV; 0 for OPT = 0, which does not read it)
     bool lane_rows = false, rowmajor = false, gfast = false;
+    // a list merge walks its separable top rows (part of the walk: off with it, and with ANSFM_MERGE_SUFFIX=0, kFlagSuffixOff)
+    bool suffix = false;
     int lane_nv = 0, flags = 0;
     // the launch hands a block's wavenumbers out in the order of their last walk patterns and writes this launch's patterns
     // (OverlapParams::hint_in / hint_out, which the launcher sets for such a plan only; no bit of flags or trims)
@@ -210,7 +220,9 @@ inline MergePlan merge_plan(const MergeCall &c, const MergeSwitches &sw)
     // where a list step is dear enough to pay for the ranking and the scattered table runs of every tile: list lengths from 16
     // (measured at C2: G = 16 -2.3 %, G = 20 -3.0 %, but G = 10 +1.4 % with the order against the same kernel without it)
     m.order = m.rowmajor && m.lane_rows && m.lane_nv == 1 && merge_list_len(c.G) >= kMergeOrderMinList && !sw.order_off;
-    m.flags = (m.lane_rows ? kFlagLaneRows : 0) | (m.rowmajor ? kFlagRowMajor : 0) | (m.gfast ? kFlagTableGfast : 0);
+    m.suffix = m.rowmajor && !sw.suffix_off && merge_list_len(c.G) >= kSuffixMinList;
+    m.flags = (m.lane_rows ? kFlagLaneRows : 0) | (m.rowmajor ? kFlagRowMajor : 0) | (m.gfast ? kFlagTableGfast : 0) |
+              (m.rowmajor && sw.suffix_off ? kFlagSuffixOff : 0);
     m.trims = m.opt | (m.lane_rows ? kOptLaneRows : 0) | (m.rowmajor ? kOptRowMajor : 0);
     m.group_width = m.lane_rows ? m.lane_nv : 0;
     return m;

@@ -16,7 +16,7 @@ void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, in
     p.del_g = del_g_dev;
     p.tau = tau;
     p.err_flag = ctx->d_flag.as<int>() + 1;
-    // eight tile queues, then the forward merge's 64-bit totals (ansfm_last_merge_rowmajor, _order): cleared by one memset
+    // eight tile queues, then the forward merge's 64-bit totals (ansfm_last_merge_rowmajor, _order, _suffix): cleared by one memset
     p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + kFlagTileCounter);
     p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
     p.delg_f32 = ctx->delg_f32;
@@ -93,6 +93,7 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     p.scratch = ctx->scratch.as<double>();
     if (m.gfast) p.lnKg = ctx->lnKg.as<double>();
     ctx->last_merge = m;
+    ctx->last_merge_G = G;
     ctx->last_merge_ordered = false;
     ansfm_ctx::MergeHintKey key;
     bool valid = false;

@@ -54,7 +54,11 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
     static_assert(merge_opt_valid(OPT), "OPT == 0 || (OPT & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient)");
     constexpr bool kTable = (OPT & kOptTable) != 0, kOrient = (OPT & kOptOrient) != 0;
     static_assert(!kTable || W32, "the weight table holds float32 products only (launch_overlap)");
-    // flags: the row mapping (kFlagLaneRows) and, with kOptTable only, the list-free walk of row-major merges (kFlagRowMajor);
+    // the table kernels of the lists from kSuffixMinList entries carry the partial form of the walk (merge_suffix_row); the shorter
+    // ones take a merge whole or not at all, with the test and the code they had
+    constexpr bool kSuffix = kTable && NR >= kSuffixMinList;
+    // flags: the row mapping (kFlagLaneRows) and, with kOptTable only, the list-free walk of row-major merges (kFlagRowMajor) and
+    // "no walk of the top rows of a list merge" (kFlagSuffixOff);
     // the instantiations without the table are launched with 0 or 1 and test the word as they always did
     // (lane_rows is only ever compared with 0, and kFlagTableGfast is set only together with kFlagLaneRows)
     const int lane_rows = kTable ? (flags & kFlagLaneRows) : flags;
@@ -63,6 +67,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
     // lane_nv: the wavenumbers of a tile of the row mapping, 1 or kLaneNV (LaneRow); unused without lane_rows
     const unsigned nvs = lane_nv == 1 ? 0u : kLaneNVShift;
     unsigned n_rowmajor = 0, n_merged = 0;              // kOptTable: the merges of this wave that took the walk / all of them
+    unsigned n_suffix = 0;                              // kOptTable: the rows this wave walked behind a list phase
     // kOptTable: the launch orders a block's wavenumbers by the launch before's pattern bytes and writes its own (MergePlan::order)
     const bool ordered = kTable && p.hint_in != nullptr;
     unsigned n_hints = 0;                               // the non-zero pattern bytes this wave read for the blocks whose tile 0 it ran
@@ -150,6 +155,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             else { keepA = (blast <= 0.0); takeB = !keepA && (alast <= 0.0); }
             const bool do_merge = !(takeB | keepA);
             bool walked = false;                        // kOptTable: the merge was walked row by row (wave-uniform where set)
+            int walked_rows = 0;                        // kOptTable: its rows walked behind a list phase (the same in every merging lane)
             if (takeB) {
                 for (int g = 0; g < G; ++g) A[g * kWave + lane] = B[g * kWave + lane];
                 if constexpr (!SORTED) {
@@ -180,21 +186,28 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                 // every instantiation -- same results, other instructions)
                 MergeElem e0, e1;
                 WalkState ws;
+                int i0 = G;                             // kOptTable: the row from which the merge is walked (merge_suffix_row)
                 if constexpr (kTable) {
                     bool lane_passes = false;
-                    if ((flags & kFlagRowMajor) != 0 && merge_rowmajor_test<NR>(R, G, mo, lane_passes)) {
-                        ws = walk_begin(GORD, lane);
-                        merge_rowmajor<NR>(G, mo, ws, rec);
-                        walked = true;
+                    if constexpr (kSuffix) {
+                        if ((flags & kFlagRowMajor) != 0)
+                            i0 = merge_suffix_row(merge_rowmajor_test<NR>(R, G, mo, lane_passes), G, (flags & kFlagSuffixOff) == 0);
+                    } else {
+                        if ((flags & kFlagRowMajor) != 0 && merge_rowmajor_whole<NR>(R, G, mo, lane_passes)) i0 = 0;
                     }
+                    walked = i0 == 0;
+                    if (i0 != 0) walked_rows = G - i0;
                     // (a skipped merge leaves its bit 0; merges beyond the eighth shift their bit out)
                     pattern |= lane_passes && s <= 8 ? 0x100u >> s : 0u;
                 }
-                if (!kTable || !walked) {               // (a constant without the table: those instantiations compile as they did)
+                if (!kTable || i0 != 0) {               // (a constant without the table: those instantiations compile as they did)
                 merge_fetch<W32, SORTED, OPT>(R[0], lane, A, B, DG, e0, PA, PB, mo);
                 ws = walk_begin(GORD, lane);
-                // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel)
-                const int nloop = G * G - (G - 1);
+                // full-length passes for the steps 0 .. G*G - G (an odd number of them), then the peeled ones (merge_peel);
+                // kOptTable, a list phase below the rows that are walked: G * i0 full-length passes, odd or even, and no peel --
+                // the heads of the rows from i0 stay at the tail of R, and the element the last step fetched is theirs
+                const bool partial = kSuffix && i0 < G;
+                const int nloop = partial ? G * i0 : G * G - (G - 1);
                 // ping-pong: no register rotation.  The trips are counted down (one scalar add and one compare per trip)
                 // (kPer is a named local on purpose: with a literal 2 the compiler orders the scalar code of the skip rules
                 // above differently in the OPT = 0 instantiations -- same results, other instructions)
@@ -203,9 +216,19 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                     merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                     merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e1, e0, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
                 }
+                if (!partial || (nloop & 1) != 0)
                 merge_step<NR, W32, false, SORTED, NODIV, NR, OPT>(R, e0, e1, ws, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                if (!partial) {
                 if (((G ^ NR) & 1) != 0) { const MergeElem t = e0; e0 = e1; e1 = t; }   // current element: e1 <-> e0
                 merge_peel<NR - 1, NR, W32, SORTED, NODIV, OPT>(R, e0, e1, ws, G, lane, A, B, DG, GORD, rec, PA, PB, mo);
+                }
+                }
+                if constexpr (kTable) {
+                    // the one call of the walk: the whole merge, or the rows behind a list phase, on the same walk state
+                    if (i0 < G) {
+                        if (i0 == 0) ws = walk_begin(GORD, lane);
+                        merge_rowmajor<NR>(i0, G, mo, ws, rec);
+                    }
                 }
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
@@ -293,6 +316,9 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             if constexpr (kTable) {
                 n_merged += __builtin_amdgcn_ballot_w64(do_merge) != 0 ? 1u : 0u;
                 n_rowmajor += __builtin_amdgcn_ballot_w64(walked) != 0 ? 1u : 0u;
+                // (counted here, where every lane is active: lane 0, which adds the totals up, need not have merged)
+                const unsigned long long some = __builtin_amdgcn_ballot_w64(walked_rows != 0);
+                if (some != 0) n_suffix += (unsigned)__builtin_amdgcn_readlane(walked_rows, __builtin_ctzll(some));
             }
         }
         if constexpr (OPT != 0) {
@@ -317,12 +343,13 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
         }
     }
     if constexpr (kTable) {
-        // the launch's three totals follow the tile counters (merge_params) and are cleared with them; added once per wave
+        // the launch's four totals follow the tile counters (merge_params) and are cleared with them; added once per wave
         unsigned long long *cnt = reinterpret_cast<unsigned long long *>(p.tile_counter + 8);
         if (lane == 0) {
             atomicAdd(cnt, (unsigned long long)n_rowmajor);
             atomicAdd(cnt + 1, (unsigned long long)n_merged);
             if (ordered) atomicAdd(cnt + 2, (unsigned long long)n_hints);
+            if (n_suffix != 0) atomicAdd(cnt + 3, (unsigned long long)n_suffix);
         }
     }
 }

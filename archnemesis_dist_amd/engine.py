@@ -318,6 +318,15 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_last_merge_rowmajor(self._ctx, C.byref(m), C.byref(t)), "last_merge_rowmajor")
         return int(m.value), int(t.value)
 
+    def last_merge_suffix(self):
+        """(rows walked behind a list phase, rows of the merges not walked whole) of the last forward merge launch, counted per
+        wave: a merge whose rows i0 .. G-1 sort row by row above everything in the rows below runs the head list for those
+        rows only and walks the rest (at least two rows; same bits; off with ANSFM_MERGE_SUFFIX=0 and with the walk).
+        (0, 0) for a kernel without the weight table."""
+        r, t = C.c_int64(), C.c_int64()
+        self._check(self._lib.ansfm_last_merge_suffix(self._ctx, C.byref(r), C.byref(t)), "last_merge_suffix")
+        return int(r.value), int(t.value)
+
     def last_merge_order(self):
         """(applied, non-zero bytes) of the last forward merge launch: applied when it handed the wavenumbers of a block out in
         the order of the pattern bytes that the launch before wrote (the same table upload or the seam, W, rows, S and G; the

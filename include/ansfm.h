@@ -90,6 +90,13 @@ int ansfm_last_merge_launch(const ansfm_ctx *ctx, int *waves_per_block, int *tri
  * ansfm_last_merge_rowmajor: the (wave, merge) pairs of the last forward merge launch that took that walk, and all pairs that
  * merged; both 0 for a kernel without bit 1, which does not count.  Copies the two totals from the device (synchronises). */
 int ansfm_last_merge_rowmajor(const ansfm_ctx *ctx, int64_t *merges, int64_t *merges_total);
+/* A merge of such a launch that does not sort row by row from its first row may still do so from a row i0 on, above everything
+ * in the rows below: the wave then runs the head list for the G * i0 elements of those rows and walks the rows i0 .. G-1
+ * (at least two of them; results are the same bit for bit; ANSFM_MERGE_SUFFIX=0 at the call keeps the list to the end).
+ * rows: the rows walked behind a list phase, summed over the (wave, merge) pairs of the last forward merge launch;
+ * rows_of_list_merges: G times the pairs that ansfm_last_merge_rowmajor does not count as walked.  Both 0 for a kernel
+ * without bit 1.  Copies the totals from the device (synchronises). */
+int ansfm_last_merge_suffix(const ansfm_ctx *ctx, int64_t *rows, int64_t *rows_of_list_merges);
 /* The wavenumbers a wave of the last forward merge launch held with bit 32: 1 (64 rows of one wavenumber, the library's choice)
  * or 2 (2 wavenumbers x 32 rows, ANSFM_MERGE_LANES=pairs); 0 without bit 32 (64 wavenumbers of one row).  Reads the context only. */
 int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width);
