@@ -1298,6 +1298,98 @@ int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models,
     return cirsrad_ck_singlescatt_impl(ctx, c, "cirsrad_ck_singlescatt_batch");
 }
 
+// The single-scattering batch with the continuum, the scattering opacity and the layer-mean phase functions formed per distinct
+// layer from the resident sources (k_ss_cont_rows) and read by row (the SS == 2 builds of k_thermal_rt): the stages of
+// cirsrad_ck_singlescatt_impl, one row map for gas opacities and continuum
+int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                            const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                            const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                            const double *lay_cont, int ray_mode, const double *f4, int ncont, const double *phase_fn,
+                                            int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                            const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
+                                            const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                            double *SPECOUT)
+{
+    CHECK_CTX(ctx);
+    const std::string fn = "cirsrad_ck_singlescatt_batch_cont: ";
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
+    bool bad = n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN || !LAYINC || !SCALE ||
+               !EMTEMP || !TSURF || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT || (ISPACE != 0 && ISPACE != 1);
+    for (int m = 0; !bad && m < n_models; ++m) bad = TSURF[m] > 0.0 && !EMISSIVITY;
+    if (bad) FAIL(ANSFM_ERR_INVALID, fn + "bad argument");
+    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
+        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont) || !phase_fn)
+        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (ray_mode = IRAY 0, 1, 2, 4 or 12; the per-layer arrays of every term that is used; phase_fn)");
+    if (!use_dust && !ray_mode) FAIL(ANSFM_ERR_INVALID, fn + "neither aerosols nor Rayleigh scattering: no scattering opacity");
+    if (use_cia && !ctx->cia_on) FAIL(ANSFM_ERR_INVALID, fn + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
+    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, fn + "the CIA source was uploaded for the other ISPACE");
+    if (use_dust && !ctx->dust_n) FAIL(ANSFM_ERR_INVALID, fn + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    if (ncont > 7) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "more than 7 aerosol populations (NumPy sums 8 and more pairwise, the kernel sums in order)");
+    if (ncont != (use_dust ? ctx->dust_n : 0))
+        FAIL(ANSFM_ERR_INVALID, fn + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
+                                    std::to_string(use_dust ? ctx->dust_n : 0) + " populations");
+    if ((size_t)n_models * P > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "at most 65535 (model, path) pairs per call");
+    for (int ip = 0; ip < P; ++ip) {                                 // the RT kernel indexes the layers with these
+        if (NLAYIN[ip] < 1 || NLAYIN[ip] > LIMAX) FAIL(ANSFM_ERR_INVALID, fn + "NLAYIN outside 1 .. LIMAX");
+        for (int j = 0; j < NLAYIN[ip]; ++j)
+            if (LAYINC[(size_t)j * P + ip] < 0 || LAYINC[(size_t)j * P + ip] >= L) FAIL(ANSFM_ERR_INVALID, fn + "LAYINC entry outside the layer range");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    RtCall h;
+    h.ISPACE = ISPACE; h.n_models = n_models; h.L = L; h.lay_press_pa = lay_press_pa; h.lay_temp = lay_temp; h.amount = amount;
+    h.fused_cont = 1; h.use_cia = use_cia ? 1 : 0; h.use_dust = use_dust ? 1 : 0; h.NVMR = use_cia ? ctx->cia_NVMR : 0;
+    h.lay_q = use_cia ? lay_q : nullptr; h.lay_frac = use_cia ? lay_frac : nullptr; h.lay_delh = use_cia ? lay_delh : nullptr;
+    h.lay_cont = use_dust ? lay_cont : nullptr;
+    h.ray_mode = ray_mode; h.ray_totam = (use_cia || ray_mode) ? lay_totam : nullptr; h.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    h.P = P; h.LIMAX = LIMAX; h.NLAYIN = NLAYIN; h.LAYINC = LAYINC; h.SCALE = SCALE; h.EMTEMP = EMTEMP; h.TSURF = TSURF;
+    h.EMISSIVITY = EMISSIVITY; h.BRDF = BRDF; h.SOLFLUX = SOLFLUX; h.SOL_ANG = SOL_ANG; h.EMISS_ANG = EMISS_ANG; h.xfac = xfac;
+    h.SPECOUT = SPECOUT; h.rt_mode = 2;
+    const int W = ctx->W;
+    int rc;
+    RtCall d = stage_call(ctx, h, &rc);
+    if (rc) return rc;
+    const void *pf_dev = nullptr;
+    if ((rc = h2d(ctx, ctx->ss_phase_fn, phase_fn, (size_t)W * P * (ncont + 1) * sizeof(double), &pf_dev))) return rc;
+    if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+    ContCall k;
+    k.ISPACE = ISPACE; k.use_cia = d.use_cia; k.use_dust = d.use_dust; k.ray_mode = ray_mode;
+    k.temp = d.lay_temp; k.q = d.lay_q; k.frac = d.lay_frac; k.totam = d.ray_totam; k.delh = d.lay_delh; k.cont = d.lay_cont; k.f4 = d.ray_f4;
+    GasRows g{DedupRows{n_models * L, d.lay_press_pa, d.lay_temp, d.amount}, n_models, nullptr};
+    if (ctx->dedup && n_models > 1 && !ctx->lblrt) {
+        if ((rc = dedup_rows_cont(ctx, n_models, L, d.lay_press_pa, d.lay_temp, d.amount, k, &g.k))) return rc;
+        g.n_k = 1;
+        g.tau_slot = ctx->dd_slot.as<int32_t>();
+    }
+    const int rows = g.k.rows;
+    ctx->last_rows = rows; ctx->last_dedup = g.tau_slot != nullptr;
+    ctx->last_n = n_models; ctx->last_L = L;
+    if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    if (ctx->is_lbl) rc = gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, false);
+    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, generic); });
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    SsContRows sr;
+    if ((rc = launch_ss_cont_rows(ctx, rows, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, k, P,
+                                  static_cast<const double *>(pf_dev), &sr)))
+        return rc;
+    const size_t nout = (size_t)n_models * W * P * sizeof(double);
+    HIPCHK(ctx->tmp_out.reserve(nout));
+    d.SPECOUT = ctx->tmp_out.as<double>();
+    RtParams r;
+    rt_params_of_call(ctx, d, r);
+    r.tau_slot = g.tau_slot; r.cont = sr.cont; r.sca = sr.sca; r.phase = sr.phase;
+    r.cont_by_row = 1; r.ss_by_row = 1; r.rows = rows;
+    r.mode = 2;
+    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+    if ((rc = launch_rt(ctx, r, n_models))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+    call_recorded(ctx, n_models, L);
+    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return ANSFM_OK;
+}
+
 int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR, int NLAYIN, const double *WAVE,
                              const double *TAUTOT_PATH, const double *dTAUTOT_PATH, int NVMR, const double *TEMP,
                              const double *PRESS, double TSURF, const double *EMISSIVITY, double *SPECOUT, double *dSPECOUT,

@@ -463,6 +463,89 @@ __global__ __launch_bounds__(256) void k_ms_cont_rows(MsContRowsParams p)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The same rows for the single-scattering batch (ansfm_cirsrad_ck_singlescatt_batch_cont), in the layouts its RT kernel reads by
+// row, zero beyond W: the continuum of k_tau_cont_rows, the scattering opacity and the layer-mean phase function of every path
+// (calculate_single_scattering_plane_parallel_spectrum, :4316-4321):
+//     cont[row][w]  = (TAUCIA + TAUDUST) + TAURAY                                      (an absent term is left out)
+//     sca[row][w]   = TAURAY + TAUSCAT,  TAUSCAT = sum_d s_d (raw, in the order of d),  s_d = (ksca_w[d][w] 1e-4) CONT[l][d]
+//     phase[ip][row][w] = num > 0 ? num / (TAURAY + TAUSCAT) : num,
+//                   num = pf[w][ip][0] s_0 + ... + pf[w][ip][ND-1] s_{ND-1} + pf[w][ip][ND] TAURAY
+// with pf = phase_fn [W][P][NDUST + 1] (calc_phase / calc_phase_ray at each path's scattering angle).  Every product is rounded,
+// then added in that order, the first term starting the sum (np.sum over a middle axis adds in order).  A term that is not used
+// is the reference's array of zeros: TAURAY = 0 still adds pf 0 to num (its sign can matter to a zero sum) and 0 to the divisor.
+// ------------------------------------------------------------------------------------------------------------------
+struct SsContRowsParams {
+    ContRowsParams c;           // as k_tau_cont_rows takes it: c.out = cont [rows][Wpad]; c.lay filled by k_cia_rows_prep
+    const double *ksca_w;       // [NDUST][Wpad]
+    const double *phase_fn;     // [W][P][NDUST + 1]
+    double *sca;                // [rows][Wpad]
+    double *phase;              // [P][rows][Wpad]
+    int P;
+};
+
+// One thread per (row, wavenumber), a block within one row (blockIdx.x), coalesced along the wavenumbers.  s_d is formed again
+// for every path: no per-thread array, no scratch memory.
+__global__ __launch_bounds__(256) void k_ss_cont_rows(SsContRowsParams p)
+{
+#pragma clang fp contract(off)
+    const ContRowsParams &c = p.c;
+    const int r = blockIdx.x, w = blockIdx.y * blockDim.x + threadIdx.x;
+    if (w >= c.Wpad) return;
+    const size_t o = (size_t)r * c.Wpad + w, RW = (size_t)c.rows * c.Wpad;
+    if (w >= c.W) {
+        c.out[o] = 0.0; p.sca[o] = 0.0;
+        for (int ip = 0; ip < p.P; ++ip) p.phase[(size_t)ip * RW + o] = 0.0;
+        return;
+    }
+    const int l = c.work ? c.work[r] : r;
+    const double v = c.wave[w];
+    double tau = 0.0, tauscat = 0.0, ray = 0.0;
+    bool any = false;
+    if (c.use_cia) {
+        const CiaLayer cl = c.lay[r];
+        const double x = c.ispace == 0 ? v : 1.e4 / v;             // :4565
+        const double sum1 = cia_sum(c.cia, cl, x, w, c.cia.q + (size_t)l * c.cia.NVMR, nullptr);
+        tau = sum1 * cl.xfac;
+        any = true;
+    }
+    const double *cont = c.NDUST > 0 ? c.cont + (size_t)l * c.NDUST : nullptr;
+    if (c.NDUST > 0) {
+        double dust = 0.0;
+        for (int d = 0; d < c.NDUST; ++d) {
+            const double de = c.kext_w[(size_t)d * c.Wpad + w] * 1.0e-4, ds = p.ksca_w[(size_t)d * c.Wpad + w] * 1.0e-4;
+            double t = de * cont[d];
+            const double s = ds * cont[d];
+            t = (t != t) ? 0.0 : t;                                  // np.nan_to_num; +-inf end at the bounds of the clip
+            t = t > 0.0 ? t : 0.0;                                   // np.clip(., 0, 1e20)  (:3966)
+            t = t < 1.0e20 ? t : 1.0e20;
+            dust = d == 0 ? t : dust + t;
+            tauscat = d == 0 ? s : tauscat + s;
+        }
+        tau = any ? tau + dust : dust;
+        any = true;
+    }
+    if (c.ray_mode) {
+        ray = rayleigh_k(c.ray_mode, c.ispace, v, c.ray_mode == 4 ? c.f4 + (size_t)l * 4 : nullptr) * c.totam[l];
+        tau = any ? tau + ray : ray;
+    }
+    c.out[o] = tau;
+    const double tsca = ray + tauscat;                               // an unused term: the reference's zeros
+    p.sca[o] = tsca;
+    const double *pf = p.phase_fn + (size_t)w * p.P * (c.NDUST + 1);
+    for (int ip = 0; ip < p.P; ++ip, pf += c.NDUST + 1) {
+        double num = 0.0;
+        for (int d = 0; d < c.NDUST; ++d) {
+            const double s = (p.ksca_w[(size_t)d * c.Wpad + w] * 1.0e-4) * cont[d];
+            const double t = pf[d] * s;
+            num = d == 0 ? t : num + t;
+        }
+        const double t = pf[c.NDUST] * ray;
+        num = c.NDUST == 0 ? t : num + t;
+        p.phase[(size_t)ip * RW + o] = num > 0.0 ? num / tsca : num;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The gradients of k_tau_cont_rows' continuum, dTAUCON of calculate_layer_opacity (:3940-3981), from the same resident sources and
 // straight in the layout the gradient RT reads: dcont[m][kpar][l][w] ([n][NPAR][L][Wpad], zero beyond W), NPAR = NVMR + 2 +
 // NDUST.  Row r = m * L + l is layer r of the per-layer arrays (no work list: a gradient call is one state, or a few).

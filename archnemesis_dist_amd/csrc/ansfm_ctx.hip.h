@@ -162,6 +162,7 @@ struct ansfm_ctx {
     DevBuf gscratch, perm, dkbuf, trold_ws, dspec_i, dcont_t, tmp_in2, tmp_out2, lbl_li;
     DevBuf ms_taus, ms_omegas, ms_bnu;   // scattering branch of CIRSrad: TAUTOT / OMEGA (W,G,L) and BB (W,L) in HBM
     DevBuf ms_cont_rows;                 // ansfm_cirsrad_ck_scatter_batch_cont: the rows k_ms_cont_rows forms, TAUCIA / TAUDUST / TAURAY / TAUSCAT [R][W] and the fractions [R][ncont][W]
+    DevBuf ss_cont_rows, ss_phase_fn;    // ansfm_cirsrad_ck_singlescatt_batch_cont: the rows k_ss_cont_rows forms, sca [R][Wpad] and phase [P][R][Wpad]; phase_fn [W][P][ncont + 1]
     DevBuf ms_tauray_l, ms_lfrac_l;      // the continuum by rows: TAURAY / aerosol fractions of a launch's models (the model-by-model route: one model's dense arrays)
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
@@ -288,6 +289,12 @@ int launch_tau_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, con
 // the rows in the layout ansfm_cirsrad_ck_scatter_batch_rows takes, [rows][W] / [rows][NDUST][W]; a term that is not used is null
 struct MsContRows { const double *cia, *dust, *ray, *sca, *lf; };
 int launch_ms_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, MsContRows *out);
+// ansfm_ops.hip: k_cia_rows_prep + k_ss_cont_rows for the single-scattering batch: the continuum into ctx->cont_t [rows][Wpad], the
+// scattering opacity [rows][Wpad] and the layer-mean phase function of the P paths [P][rows][Wpad] into ctx->ss_cont_rows;
+// phase_fn [W][P][NDUST + 1] on the device
+struct SsContRows { const double *cont, *sca, *phase; };
+int launch_ss_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, int P, const double *phase_fn,
+                        SsContRows *out);
 // ansfm_ops.hip: k_dtau_cont_rows for the gradient thermal branch, into ctx->dcont_t [n][NPAR][L][Wpad]: dTAUCON of the n * L
 // layers from the resident sources.  After launch_tau_cont_rows(ctx, n * L, nullptr, c) on the same stream: the CIA records in
 // ctx->cia_lay are that launch's.

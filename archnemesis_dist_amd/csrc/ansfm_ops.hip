@@ -82,6 +82,29 @@ int ansfm::launch_ms_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_row
     return ANSFM_OK;
 }
 
+int ansfm::launch_ss_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, int P, const double *phase_fn,
+                               SsContRows *out)
+{
+    const size_t RW = (size_t)rows * ctx->Wpad;
+    HIPCHK(ctx->cont_t.reserve(RW * sizeof(double)));
+    HIPCHK(ctx->ss_cont_rows.reserve((1 + (size_t)P) * RW * sizeof(double)));
+    SsContRowsParams p;
+    int rc;
+    if ((rc = cont_rows_params(ctx, rows, slot_rows, c, p.c))) return rc;
+    p.c.out = ctx->cont_t.as<double>();
+    p.ksca_w = ctx->dust_ksca.as<double>();
+    p.phase_fn = phase_fn; p.P = P;
+    p.sca = ctx->ss_cont_rows.as<double>(); p.phase = p.sca + RW;
+    if (c.use_cia) {
+        hipLaunchKernelGGL(k_cia_rows_prep, dim3(nblk((size_t)rows, 64)), dim3(64), 0, ctx->stream, p.c);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ss_cont_rows, dim3((unsigned)rows, nblk((size_t)ctx->Wpad, 256)), dim3(256), 0, ctx->stream, p);
+    HIPCHK(hipGetLastError());
+    *out = SsContRows{p.c.out, p.sca, p.phase};
+    return ANSFM_OK;
+}
+
 int ansfm::launch_dtau_cont_rows(ansfm_ctx *ctx, int n_models, int L, int NVMR, int NPAR, const ContCall &c)
 {
     const int rows = n_models * L;

@@ -103,7 +103,9 @@ __device__ __forceinline__ double planck_bb(double a, double c2y, double T)
 // SS: the build for mode 2 on the vertical opacities (p.sca, p.phase with a model axis; CIRSrad's single-scattering branch):
 // the scattering opacity and the phase function of layer j + 1 are fetched with its opacities, ahead of layer j's arithmetic.
 // The other builds keep the run-time p.mode (the array-level seam's p.omega among them) and are not touched by it.
-template <bool BATCH, int PREFIX = 0, bool SS = false>
+// SS == 2: the same on rows (p.ss_by_row: sca [rows][Wpad], phase [P][rows][Wpad], read through the opacity row of the layer like
+// a continuum by row) -- builds of their own, so that the dense SS builds keep their code.
+template <bool BATCH, int PREFIX = 0, int SS = 0>
 __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATCH ? 4 : 1, BATCH ? 4 : 8))) void k_thermal_rt(RtParams p)
 {
     __shared__ double red[kGY][kWave];
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
     // mode 2 (single scattering): ssfac = mu0 / (mu0 + mu) and the solar flux over 4 pi, wave-uniform per path (:6557-6559)
     const double PI_ = 3.141592653589793;
     double ssfac = 0.0, mu0s = 0.0, sflux = 0.0;
-    if (SS || p.mode == 2) {
+    if (SS != 0 || p.mode == 2) {
         const double mu = cos(p.emiss_ang[ip] / 180. * PI_);
         mu0s = cos(p.sol_ang[ip] / 180. * PI_);
         ssfac = mu0s / (mu0s + mu);
@@ -165,9 +167,15 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
     }
     // SS: the scattering opacity and the phase function of layer j, fetched with its opacities
     auto fetch_ss = [&](int j, double sp[2]) {
-        const int lay = (int)m_lay[j];
-        sp[0] = p.sca[((size_t)m * p.L + lay) * p.Wpad + nu];
-        sp[1] = p.phase[(((size_t)m * p.P + ip) * p.L + lay) * p.Wpad + nu];
+        if constexpr (SS == 2) {
+            const size_t ri = (size_t)m_row[j];
+            sp[0] = p.sca[ri * p.Wpad + nu];
+            sp[1] = p.phase[((size_t)ip * p.rows + ri) * p.Wpad + nu];
+        } else {
+            const int lay = (int)m_lay[j];
+            sp[0] = p.sca[((size_t)m * p.L + lay) * p.Wpad + nu];
+            sp[1] = p.phase[(((size_t)m * p.P + ip) * p.L + lay) * p.Wpad + nu];
+        }
     };
     auto scatter_term = [&](int j, int k, double tvk, double tc, double dtr) -> double {
         // (trold - tr) * ssfac * omega * phase * SOLFLUX / (4 pi), in the reference's order of operations (:6577)
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
                 const double t = (tv[k] + tc) * sc;  // :3989, :4006
                 taud[k] += t;
                 const double tr = exp(-taud[k]);
-                if constexpr (SS) {                  // scatter_term on the fetched values, the same order of operations
+                if constexpr (SS != 0) {                  // scatter_term on the fetched values, the same order of operations
                     const double tt = tv[k] + tc;
                     const double om = (tt > 0.0) ? ss[0] / tt : 0.0;
                     spec[k] += (trold[k] - tr) * ssfac * om * ss[1] * sflux / (4. * PI_);
@@ -235,18 +243,18 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
         }
     }
     if (j < nl) fetch(j, tvA, tcA, emA);
-    if constexpr (SS) { if (j < nl) fetch_ss(j, ssA); }
+    if constexpr (SS != 0) { if (j < nl) fetch_ss(j, ssA); }
     for (; j + 1 < nl; j += 2) {                         // ping-pong buffers: no register rotation
         fetch(j + 1, tvB, tcB, emB);
-        if constexpr (SS) { fetch_ss(j + 1, ssB); ss = ssA; }
+        if constexpr (SS != 0) { fetch_ss(j + 1, ssB); ss = ssA; }
         integrate(j, tvA, tcA, emA);
         leave(j);
         if (j + 2 < nl) fetch(j + 2, tvA, tcA, emA);
-        if constexpr (SS) { if (j + 2 < nl) fetch_ss(j + 2, ssA); ss = ssB; }
+        if constexpr (SS != 0) { if (j + 2 < nl) fetch_ss(j + 2, ssA); ss = ssB; }
         integrate(j + 1, tvB, tcB, emB);
         leave(j + 1);
     }
-    if constexpr (SS) ss = ssA;
+    if constexpr (SS != 0) ss = ssA;
     if (j < nl) { integrate(j, tvA, tcA, emA); leave(j); }
     // surface / bottom-of-atmosphere term  (:6354-6365)
     int i1 = (int)(nl / 2.0) - 1;
@@ -279,7 +287,7 @@ __global__ __launch_bounds__(kWave *kGY) __attribute__((amdgpu_waves_per_eu(BATC
         if (g < G) {
             double s = spec[k];
             if (p.mode == 1) s = exp(-taud[k]);                               // :4116, xfac = solar flux when IFORM = 4 (:4119-4127)
-            else if (SS || p.mode == 2) {                                     // :6585-6596: lower boundary whatever the geometry
+            else if (SS != 0 || p.mode == 2) {                                     // :6585-6596: lower boundary whatever the geometry
                 const double ts = p.tsurf[m];
                 double rg;
                 if (ts <= 0.0) rg = planck_bb(a, c2y, p.emtemp[pathbase + (size_t)(nl - 1) * p.P]);

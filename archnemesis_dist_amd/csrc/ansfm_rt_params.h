@@ -40,6 +40,9 @@ struct RtParams {
     const int32_t *jstart;  // [n][P]
     int m0;
     int cont_by_row;
+    // mode 2 on rows (ansfm_cirsrad_ck_singlescatt_batch_cont, the SS == 2 builds): sca [rows][Wpad] and phase [P][rows][Wpad]
+    // addressed like tau; with cont_by_row (or no continuum) a layer is state 0's exactly when its row is
+    int ss_by_row, rows;
 };
 
 constexpr int kMaxPar = 256;   // parameters of dSPECOUT (NVMR + 2 + NDUST): sizes the slot table in the kernel arguments only

@@ -487,6 +487,71 @@ class AnsfmEngine:
         self._check(rc, "cirsrad_ck_singlescatt_batch")
         return out
 
+    def cirsrad_ck_singlescatt_batch_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phase_fn,
+                                          NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG, EMISS_ANG,
+                                          xfac=None, variant=None):
+        """`cirsrad_ck_singlescatt_batch` with taucont, tausca and phase formed inside the call, once per distinct layer, from
+        the resident sources (upload_cia, upload_dust) and the Rayleigh parametrisations
+        (ansfm_cirsrad_ck_singlescatt_batch_cont): q (n, NLAY, NVMR) = PP / PRESS with FRAC, DELH (n, NLAY) switch CIA on (None:
+        off); CONT (n, NLAY, NDUST) switches the aerosols on (None: off; NDUST as uploaded); IRAY 0, 1, 2 or 4 (variant='v':
+        calc_tau_rayleighv) with f4 (n, NLAY, 4) for IRAY 4 (`rayleigh_f4`); TOTAM (n, NLAY) for CIA and Rayleigh; phase_fn
+        (NWAVE, NPATH, NDUST + 1): the phase function of every population and, last, of Rayleigh scattering at each path's
+        scattering angle (ScatterX.calc_phase / calc_phase_ray).  Host arrays; the rest as `cirsrad_ck_singlescatt_batch` ->
+        SPECOUT (n, NWAVE, NPATH), bit-identical to that call on the dense arrays of calc_tau_cia / calc_tau_dust /
+        calc_tau_rayleigh put together as ForwardModel_0.py:3963-3989 and :4316-4321 do."""
+        what = "cirsrad_ck_singlescatt_batch_cont"
+        dims, _ = self.ktable_info()
+        W, S = dims[0], dims[4]
+        lp = _np(lay_press_pa)
+        if lp.ndim != 2:
+            raise ValueError("lay_press_pa must be (n_models, NLAY)")
+        n, L = lp.shape
+        am = _np(amount)
+        if am.shape != (n, S, L):
+            raise ValueError("amount must be (n_models, NGAS, NLAY)")
+        lt = _np(lay_temp)
+        if lt.shape != (n, L):
+            raise ValueError("lay_temp must be (n_models, NLAY)")
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        if NLAYIN.shape != (P,):
+            raise ValueError(f"{what}: NLAYIN must be (NPATH,)")
+        TS = _np(np.atleast_1d(TSURF))
+        if TS.shape != (n,):
+            raise ValueError("TSURF must be (n_models,)")
+        mode = 12 if variant == "v" else int(IRAY)
+        use_cia, use_dust = q is not None, CONT is not None
+        ncont = _np(CONT).shape[-1] if use_dust else 0
+        arrs = {}
+        for name, a, shape in (("q", q, (n, L, getattr(self, "cia_nvmr", -1))), ("FRAC", FRAC, (n, L)), ("TOTAM", TOTAM, (n, L)),
+                               ("DELH", DELH, (n, L)), ("CONT", CONT, (n, L, ncont)), ("f4", f4, (n, L, 4)),
+                               ("phase_fn", phase_fn, (W, P, ncont + 1)), ("SCALE", SCALE, (n, LIMAX, P)),
+                               ("EMTEMP", EMTEMP, (n, LIMAX, P)), ("BRDF", BRDF, (W, P)), ("EMISSIVITY", EMISSIVITY, (W,)),
+                               ("SOLFLUX", SOLFLUX, (W,)), ("xfac", xfac, (W,)), ("SOL_ANG", None if SOL_ANG is None else np.atleast_1d(SOL_ANG), (P,)),
+                               ("EMISS_ANG", None if EMISS_ANG is None else np.atleast_1d(EMISS_ANG), (P,))):
+            a = arrs[name] = None if a is None else _np(a)
+            if a is not None and -1 not in shape and a.shape != shape:
+                raise ValueError(f"{what}: {name} must be {shape}, got {a.shape}")
+        if use_cia and (arrs["FRAC"] is None or arrs["DELH"] is None):
+            raise ValueError(f"{what}: CIA (q given) needs FRAC and DELH")
+        if (use_cia or mode) and arrs["TOTAM"] is None:
+            raise ValueError(f"{what}: CIA and Rayleigh need TOTAM")
+        if mode == 4 and arrs["f4"] is None:
+            raise ValueError(f"{what}: IRAY 4 needs f4 (rayleigh_f4)")
+        if arrs["phase_fn"] is None:
+            raise ValueError(f"{what}: phase_fn (NWAVE, NPATH, NDUST + 1) is needed")
+        out = np.empty((n, W, P))
+        rc = self._lib.ansfm_cirsrad_ck_singlescatt_batch_cont(
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
+            _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont,
+            _ptr(arrs["phase_fn"]), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(arrs["SCALE"]), _ptr(arrs["EMTEMP"]), _ptr(TS),
+            _ptr(arrs["EMISSIVITY"]), _ptr(arrs["BRDF"]), _ptr(arrs["SOLFLUX"]), _ptr(arrs["SOL_ANG"]), _ptr(arrs["EMISS_ANG"]),
+            _ptr(arrs["xfac"]), _ptr(out))
+        self._check(rc, what)
+        return out
+
     def cirsrad_ck_transmission(self, lay_press_pa, lay_temp, amount, taucont, NLAYIN, LAYINC, SCALE, xfac=None):
         """CIRSrad, pure-transmission branch (calculate_transmission_spectrum :4110): SPECOUT (n, W, P) (or (W, P)) =
         xfac * sum_g DELG exp(-sum over the path's layers of TAUTOT_LAYINC)."""

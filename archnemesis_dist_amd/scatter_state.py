@@ -233,3 +233,213 @@ class BatchedCKScatterModel:
         self.last_rows = eng.last_layer_rows()
         self.last_cache = eng.last_scatter_cache()
         return torch.as_tensor(out.reshape(n, -1), dtype=torch.float64, device=dev)
+
+
+# ---- the single-scattering branch -----------------------------------------------------------------------------------------
+def singlescatt_phase_and_sca(TAUCLSCAT, TAURAY, TAUSCAT, phase_fn):
+    """The layer-mean phase function of every path and the scattering opacity of one state as
+    calculate_single_scattering_plane_parallel_spectrum forms them (ForwardModel_0.py:4316-4321): TAUCLSCAT (NWAVE, NLAY,
+    NDUST), TAURAY / TAUSCAT (NWAVE, NLAY), phase_fn (NWAVE, NPATH, NDUST + 1) -> tausca (NWAVE, NLAY), phase (NPATH, NWAVE,
+    NLAY)."""
+    W, L, ND = TAUCLSCAT.shape
+    phase_function = np.transpose(np.asarray(phase_fn, float), (0, 2, 1))            # (NWAVE, NDUST + 1, NPATH), :4272
+    P = phase_function.shape[2]
+    out = np.zeros((P, W, L))
+    for ipath in range(P):
+        phasex = np.zeros((W, ND + 1, L))
+        phasex[:, 0:ND, :] = np.transpose(phase_function[:, 0:ND, ipath] * np.transpose(TAUCLSCAT, axes=(1, 0, 2)), axes=(1, 2, 0))
+        phasex[:, ND, :] = np.transpose(phase_function[:, ND, ipath] * np.transpose(TAURAY))
+        phase = np.sum(phasex, axis=1)
+        phase[phase > 0] = phase[phase > 0] / (TAURAY[phase > 0] + TAUSCAT[phase > 0])
+        out[ipath] = phase
+    return TAURAY + TAUSCAT, out
+
+
+def singlescatt_dense_by_hand(eng, ISPACE, IRAY, ID, ISO, cia, dust, lay, phase_fn):
+    """taucont, tausca (n, NWAVE, NLAY) and phase (n, NPATH, NWAVE, NLAY) of n states at array level: calc_tau_cia / calc_tau_dust
+    / calc_tau_rayleigh over all n * L layers, the sums of calculate_layer_opacity (:3963-3989) and `singlescatt_phase_and_sca`
+    per state -- the route `BatchedCKSingleScatterModel.fused_continuum` replaces.  cia, dust, lay as `continuum_rows_by_hand`
+    takes them; a term that is not used is the reference's array of zeros."""
+    n, L = lay["PRESS"].shape
+    WAVE = eng.WAVE
+    W = WAVE.size
+    flat = lambda a: np.ascontiguousarray(a).reshape((n * L,) + np.shape(a)[2:])
+    cont = None
+    if cia is not None:
+        k = {}
+        for name in ("k_co2", "k_n2n2", "k_n2h2"):                # calc_tau_cia takes them in its own (sorted) order
+            v = cia.get(name)
+            k[name] = None if v is None else (np.asarray(v, float) if int(ISPACE) == 0 else
+                                              np.asarray(v, float)[np.argsort(1.e4 / WAVE)])
+        cont = eng.calc_tau_cia(ISPACE, WAVE, cia["CIA_WAVEN"], cia["CIA_TEMP"], cia["CIA_FRAC"], cia["NPARA"], cia["K_CIA"],
+                                cia["IPAIRG1"], cia["IPAIRG2"], cia["INORMALT"], cia["INORMAL"], cia["INORMALD"], ID, ISO,
+                                flat(lay["PP"]), flat(lay["PRESS"]), flat(lay["TEMP"]), flat(lay["FRAC"]), flat(lay["TOTAM"]),
+                                flat(lay["DELH"]), with_grad=False, **k)                                   # (W, n L)
+    TAUCLSCAT, TAUSCAT = np.zeros((W, n * L, 0)), np.zeros((W, n * L))
+    if dust is not None:
+        td1, TAUCLSCAT = eng.calc_tau_dust(WAVE, dust["SWAVE"], dust["KEXT"], dust["KSCA"], flat(lay["CONT"]))[:2]
+        TAUDUST = np.sum(np.clip(np.nan_to_num(td1), 0, 1e20), 2)                                          # :3966, :3971
+        TAUSCAT = np.sum(TAUCLSCAT, 2)                                                                     # :3972
+        cont = TAUDUST if cont is None else cont + TAUDUST
+    TAURAY = np.zeros((W, n * L))
+    if int(IRAY) != 0:
+        TAURAY = eng.calc_tau_rayleigh(IRAY, ISPACE, WAVE, flat(lay["TOTAM"]), ID=ID, ISO=ISO,
+                                       VMR=flat(lay["PP"] / lay["PRESS"][:, :, None]))[0]
+        cont = TAURAY if cont is None else cont + TAURAY                                                   # (TAUCIA + TAUDUST) + TAURAY
+    P = np.shape(phase_fn)[1]
+    taucont = None if cont is None else np.ascontiguousarray(np.transpose(cont.reshape(W, n, L), (1, 0, 2)))
+    tausca, phase = np.empty((n, W, L)), np.empty((n, P, W, L))
+    for m in range(n):
+        s = slice(m * L, (m + 1) * L)
+        tausca[m], phase[m] = singlescatt_phase_and_sca(TAUCLSCAT[:, s], TAURAY[:, s], TAUSCAT[:, s], phase_fn)
+    return taucont, tausca, phase
+
+
+class BatchedCKSingleScatterModel:
+    """CIRSrad's single-scattering branch (:4251-4336) for n states at once; what `jacobian.jacobian_nemesis_batched` asks of a
+    model.
+
+    eng: AnsfmEngine with the k-table uploaded.  state: ContinuousProfileState of T, ln VMR and ln DUST blocks.  ID / ISO,
+    igas_map, layering_args, ISPACE, IRAY, PARAH2, cia, dust: as BatchedCKScatterModel takes them; geometry: dict(pointing,
+    BOTLAY, ANGLE, EMISS_ANG, IPZEN) of AtmCalc_0 for layering.calc_path, as profile_state.BatchedCKThermalModel takes it.
+    phase_fn (NWAVE, NPATH, NDUST + 1): the phase function of every population and, last, of Rayleigh scattering at each
+    path's scattering angle (ScatterX.calc_phase / calc_phase_ray, :4269-4271 before the transpose).  SOL_ANG / EMISS_ANG: one
+    entry per path; solar (NWAVE); BRDF (NWAVE, NPATH) or None (zeros); TSURF, emissivity (NWAVE; None: 1), xfac (NWAVE) or
+    None.  More than 7 populations and DUST_RENORMALISATION raise NotImplementedError, as in BatchedCKScatterModel."""
+
+    fused_continuum = True    # False: taucont / tausca / phase of all n * NLAY layers at array level (singlescatt_dense_by_hand)
+                              # through cirsrad_ck_singlescatt_batch (same bits)
+
+    def __init__(self, eng, state, RADIUS, ID, ISO, igas_map, phase_fn, SOL_ANG, EMISS_ANG, solar, layering_args=None, geometry=None,
+                 ISPACE=0, IRAY=0, PARAH2=None, cia=None, dust=None, BRDF=None, TSURF=-1.0, emissivity=None, xfac=None,
+                 DUST_RENORMALISATION=None):
+        what = "BatchedCKSingleScatterModel: "
+        if DUST_RENORMALISATION is not None and DUST_RENORMALISATION is not False:
+            raise NotImplementedError(what + "DUST_RENORMALISATION-style rescaling of the aerosol columns is applied by the caller "
+                                             "of calc_tau_dust in the reference and is not built here")
+        self.dust = None if dust is None else dict(dust)
+        has_dust = getattr(state, "has_dust", False)
+        DUST = state.DUST if has_dust else (None if self.dust is None else self.dust.get("DUST"))
+        if has_dust and self.dust is None:
+            raise ValueError(what + "a state with a DUST block needs dust=dict(SWAVE, KEXT, KSCA)")
+        if self.dust is not None:
+            if DUST is None:
+                raise ValueError(what + "no aerosol profiles (a DUST block of the state, or dust['DUST'])")
+            DUST = np.asarray(DUST, float).reshape(state.NPRO, -1)
+            if max(DUST.shape[1], np.shape(self.dust["KEXT"])[1]) > MAX_POPULATIONS:
+                raise NotImplementedError(what + "more than 7 aerosol populations (NumPy sums 8 and more pairwise, the kernels sum "
+                                                 "in order)")
+            if DUST.shape[1] != np.shape(self.dust["KEXT"])[1] or np.shape(self.dust["KSCA"]) != np.shape(self.dust["KEXT"]):
+                raise ValueError(what + "KEXT / KSCA (NWAVE_scatter, NDUST) and DUST (NPRO, NDUST) disagree")
+        self.DUST = DUST
+        self.ISPACE, self.IRAY, self.TSURF = int(ISPACE), int(IRAY), float(TSURF)
+        if self.dust is None and self.IRAY == 0:
+            raise ValueError(what + "neither aerosols nor Rayleigh scattering: no scattering opacity")
+        self.eng, self.state = eng, state
+        self.RADIUS = float(RADIUS)
+        self.ID = np.asarray(ID); self.ISO = np.asarray(ISO)
+        self.igas_map = np.asarray(igas_map, dtype=np.int64)
+        la = dict(NLAY=20, LAYTYP=layering.EQUAL_LOG_PRESSURE, LAYINT=1, LAYHT=0.0, LAYANG=0.0, NINT=101)
+        la.update(layering_args or {})
+        self.lay = la
+        ge = dict(pointing=layering.NADIR, BOTLAY=0, ANGLE=0.0, EMISS_ANG=0.0, IPZEN=layering.IPZEN_BOTTOM)
+        ge.update(geometry or {})
+        self.geo = ge
+        self.cia = None if cia is None else dict(cia)
+        self.PARAH2 = PARAH2
+        self.SOL_ANG, self.EMISS_ANG = (np.atleast_1d(np.asarray(a, float)) for a in (SOL_ANG, EMISS_ANG))
+        dims, _ = eng.ktable_info()
+        self.W = int(dims[0])
+        self.BASEH, self.BASEP = layering.layer_split(self.RADIUS, state.H, state.P, LAYANG=la["LAYANG"], LAYHT=la["LAYHT"],
+                                                      NLAY=la["NLAY"], LAYTYP=la["LAYTYP"])
+        self.NPATH = self._path(np.ones_like(self.BASEH), np.ones_like(self.BASEH)).NPATH
+        ND = 0 if self.DUST is None else self.DUST.shape[1]
+        self.phase_fn = np.ascontiguousarray(phase_fn, dtype=float)
+        if self.phase_fn.shape != (self.W, self.NPATH, ND + 1):
+            raise ValueError(what + "phase_fn must be (NWAVE, NPATH, NDUST + 1) = %s, got %s" % ((self.W, self.NPATH, ND + 1), self.phase_fn.shape))
+        if not (self.SOL_ANG.size == self.EMISS_ANG.size == self.NPATH):
+            raise ValueError(what + "SOL_ANG and EMISS_ANG list one entry per path")
+        self.solar = np.ascontiguousarray(solar, dtype=float)
+        self.emissivity = np.ones(self.W) if emissivity is None else np.ascontiguousarray(emissivity, dtype=float)
+        self.BRDF = np.zeros((self.W, self.NPATH)) if BRDF is None else np.ascontiguousarray(BRDF, dtype=float).reshape(self.W, self.NPATH)
+        self.xfac = None if xfac is None else np.ascontiguousarray(xfac, dtype=float)
+        self._sources_on = False
+        self.last_rows = (0, 0)       # opacity rows computed / (state, layer) pairs, last spectra_batch
+        self.last_shared = False      # the states started their paths from the first state's records, last spectra_batch
+
+    def _path(self, DELH, TEMP):
+        ge = self.geo
+        return layering.calc_path(self.RADIUS, self.BASEH, DELH, TEMP, float(self.state.H[-1]), pointing=ge["pointing"],
+                                  BOTLAY=ge["BOTLAY"], ANGLE=ge["ANGLE"], EMISS_ANG=ge["EMISS_ANG"], IPZEN=ge["IPZEN"])
+
+    # ---- what jacobian_nemesis_batched asks of a model -------------------------------------------------------------
+    def ny(self):
+        """length of a measurement vector of this model (its wavenumbers x paths)"""
+        return self.W * self.NPATH
+
+    def torch_device(self):
+        import torch
+        return torch.device("cuda", self.eng.device)
+
+    # ---- host part: the profiles, layers and paths of n states ----------------------------------------------------
+    def layers(self, X):
+        """X (n, NX) -> dict of per-state layer arrays (Layer_0 attributes after calc_layering), the aerosol columns CONT of
+        every state's own aerosol profiles among them, `amount` (n, NGAS, NLAY) of the table's gases, VMRLAY and the ray path."""
+        st, la = self.state, self.lay
+        prof = st.profiles(X)
+        T, VMR = prof[0], prof[1]
+        n = T.shape[0]
+        DUST = prof[2] if len(prof) > 2 else (None if self.DUST is None else np.repeat(self.DUST[None], n, 0))
+        H = np.repeat(st.H[None], n, 0); P = np.repeat(st.P[None], n, 0)
+        PARAH2 = (self.PARAH2 if self.PARAH2 is None or np.ndim(self.PARAH2) != 1
+                  else np.repeat(np.asarray(self.PARAH2, float)[None], n, 0))
+        out = self.eng.layer_average(self.RADIUS, H, P, T, self.ID, VMR, DUST, PARAH2, self.BASEH, self.BASEP,
+                                     LAYANG=la["LAYANG"], LAYINT=la["LAYINT"], LAYHT=la["LAYHT"], NINT=la["NINT"])
+        names = ("HEIGHT", "PRESS", "TEMP", "TOTAM", "AMOUNT", "PP", "CONT", "FRAC", "DELH", "BASET", "LAYSF")
+        lay = dict(zip(names, out))
+        lay["path"] = self._path(lay["DELH"][0], lay["TEMP"])
+        lay["amount"] = np.ascontiguousarray(np.transpose(lay["AMOUNT"][:, :, self.igas_map], (0, 2, 1))) * SQ_CM_TO_SQ_METER
+        lay["VMRLAY"] = lay["PP"] / lay["PRESS"][:, :, None]
+        return lay
+
+    def upload_sources(self):
+        """Make `cia` / `dust` resident sources of the engine, on the grid of the table it holds now."""
+        eng = self.eng
+        if self.cia is not None:
+            c = self.cia
+            eng.upload_cia(self.ISPACE, None, c["CIA_WAVEN"], c["CIA_TEMP"], c["CIA_FRAC"], c["NPARA"], c["K_CIA"], c["IPAIRG1"],
+                           c["IPAIRG2"], c["INORMALT"], c["INORMAL"], c["INORMALD"], self.ID, self.ISO, k_co2=c.get("k_co2"),
+                           k_n2n2=c.get("k_n2n2"), k_n2h2=c.get("k_n2h2"))
+        if self.dust is not None:
+            eng.upload_dust(self.dust["SWAVE"], self.dust["KEXT"], self.dust["KSCA"])
+        self._sources_on = True
+
+    # ---- device part ----------------------------------------------------------------------------------------------
+    def spectra_batch(self, X, device=None):
+        """Spectra of the n states X (n, NX): torch tensor (n, NY), NY = NWAVE * NPATH (path fastest like SPECOUT), on the
+        engine's device."""
+        import torch
+        eng = self.eng
+        dev = torch.device("cuda", eng.device) if device is None else device
+        lay = self.layers(X)
+        n, L = lay["PRESS"].shape
+        path = lay["path"]
+        cia, dust = self.cia is not None, self.dust is not None
+        rt = (path.NLAYIN, path.LAYINC, np.repeat(path.SCALE[None], n, 0), path.EMTEMP, np.full(n, self.TSURF), self.emissivity,
+              self.BRDF, self.solar, self.SOL_ANG, self.EMISS_ANG)
+        if self.fused_continuum:
+            if not self._sources_on:
+                self.upload_sources()
+            f4 = eng.rayleigh_f4(self.ID, self.ISO, lay["VMRLAY"]) if self.IRAY == 4 else None
+            out = eng.cirsrad_ck_singlescatt_batch_cont(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"],
+                                                        lay["VMRLAY"] if cia else None, lay["FRAC"] if cia else None, lay["TOTAM"],
+                                                        lay["DELH"] if cia else None, lay["CONT"] if dust else None, self.IRAY, f4,
+                                                        self.phase_fn, *rt, xfac=self.xfac)
+        else:
+            taucont, tausca, phase = singlescatt_dense_by_hand(eng, self.ISPACE, self.IRAY, self.ID, self.ISO, self.cia, self.dust,
+                                                               lay, self.phase_fn)
+            out = eng.cirsrad_ck_singlescatt_batch(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"], taucont, tausca, phase,
+                                                   *rt, xfac=self.xfac)
+        self.last_rows = eng.last_layer_rows()
+        self.last_shared = eng.last_rt_shared()
+        return torch.as_tensor(out.reshape(n, -1), dtype=torch.float64, device=dev)

@@ -236,6 +236,35 @@ int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models,
                                        const double *SCALE, const double *EMTEMP, const double *TSURF, const double *EMISSIVITY,
                                        const double *BRDF, const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG,
                                        const double *xfac, double *SPECOUT);
+/* The same batch with taucont, tausca and phase formed inside the call, once per distinct layer, from the context's resident
+ * sources (ansfm_upload_cia, ansfm_upload_dust, which keeps the scattering cross sections too) and the Rayleigh
+ * parametrisations: nothing of size n W L exists on the host or crosses PCIe.  In their place the entry takes the continuum
+ * block of ansfm_cirsrad_ck_thermal_cont_dev as host arrays (use_cia with lay_q [n][L][NVMR], lay_frac, lay_delh [n][L];
+ * use_dust with lay_cont [n][L][ncont]; ray_mode 0 or IRAY 1, 2, 4, 12 with f4 [n][L][4] for mode 4; lay_totam [n][L] for CIA
+ * and Rayleigh) and phase_fn [W][P][ncont + 1]: the phase function of every population and, last, of Rayleigh scattering at
+ * the scattering angle of each path (ScatterX.calc_phase / calc_phase_ray, ForwardModel_0.py:4269-4271 before the transpose).
+ * Per distinct row (k_ss_cont_rows), every term rounded as ansfm_calc_tau_cia / ansfm_calc_tau_dust / ansfm_calc_tau_rayleigh
+ * round it: taucont = (TAUCIA + TAUDUST) + TAURAY with TAUDUST = sum_d clip(nan_to_num(e_d), 0, 1e20); tausca = TAURAY +
+ * TAUSCAT with TAUSCAT = sum_d s_d (raw), s_d = (ksca 1e-4) CONT; phase of path ip = num / (TAURAY + TAUSCAT) where num > 0,
+ * else num, num = sum_d phase_fn[w][ip][d] s_d + phase_fn[w][ip][ncont] TAURAY, added in that order (:4316-4321); a term that
+ * is not used is the reference's zeros.  The result is bit-identical to ansfm_cirsrad_ck_singlescatt_batch on dense arrays
+ * formed that way, with and without ansfm_set_layer_dedup.  One row map serves gas opacities and continuum: a layer is
+ * distinct when it differs from state 0's in pressure, temperature, an amount or a column an opacity is formed from (lay_totam;
+ * f4; lay_q, lay_delh and, for a CIA table with a para-H2 axis, lay_frac; lay_cont), and with at least 4 states a layer counts
+ * as state 0's exactly when its row is state 0's row of that layer -- no array is compared.  ANSFM_ERR_INVALID, before anything
+ * is launched: a source that is used has not been uploaded since the last table, the CIA source was uploaded for the other
+ * ISPACE, ncont is not the number of populations uploaded (0 without use_dust), neither use_dust nor ray_mode (no scattering
+ * opacity), an array of a used term or phase_fn is NULL, NLAYIN outside 1 .. LIMAX or a LAYINC entry outside 0 .. L - 1, and for
+ * the dense entry's reasons.  ANSFM_ERR_UNSUPPORTED: more than 7 populations, n_models * P > 65535.  ansfm_last_layer_rows and
+ * ansfm_last_rt_shared report as for the dense entry. */
+int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                            const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                            const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                            const double *lay_cont, int ray_mode, const double *f4, int ncont, const double *phase_fn,
+                                            int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                            const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
+                                            const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                            double *SPECOUT);
 
 /* ---- fused seam: CIRSrad, ILBL=K_TABLES, IMOD=THERMAL_EMISSION ------------------------------
  * ForwardModel_0.CIRSrad (ForwardModel_0.py:4376-4511) =

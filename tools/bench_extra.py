@@ -18,7 +18,7 @@ def timeit(f, n=3):
 
 
 def main():
-    only = sys.argv[1] if len(sys.argv) > 1 else None       # "grad" | "ms" | "lbl" | "lblrt" | "layer" | "ss"
+    only = sys.argv[1] if len(sys.argv) > 1 else None       # "grad" | "ms" | "lbl" | "lblrt" | "layer" | "ss" | "ss_cont"
     eng = pkg.AnsfmEngine(0)
     out = {}
     rng = np.random.default_rng(0)
@@ -58,6 +58,8 @@ def main():
         bench_cia(eng, out)
     if only == "grad_cont":                                 # 0.1 GB dTAUCON assembled on the host for the route it replaces: on request only
         bench_grad_cont(eng, out)
+    if only == "ss_cont":                                   # 5 GB of host arrays in the array-level route: on request only
+        bench_ss_cont(eng, out, rng)
     if only == "scatter_cont":                              # 13 GB of host arrays in the by-hand route: on request only
         bench_scatter_cont(eng, out)
     print(json.dumps(out, indent=1))
@@ -299,6 +301,87 @@ def bench_ss(eng, out, rng, runs=5):
         res["h2d_pageable_GB_per_s"] = contn.nbytes / 1e9 / float(np.median(th))
         res["upload_estimate_s"] = nbytes / 1e9 / res["h2d_pageable_GB_per_s"]
     out["singlescatt_jacobian_C2"] = res
+
+
+def bench_ss_cont(eng, out, rng, runs=5):
+    """The 201 states of the `ss` workload with real sources: synth_cia, two aerosol populations, IRAY 1, one path.  From the
+    layers of the states on the host,
+      (a) array level: calc_tau_cia / calc_tau_dust / calc_tau_rayleigh over all 20 100 layers, the sums and the phase mix in NumPy
+          (scatter_state.singlescatt_dense_by_hand), then cirsrad_ck_singlescatt_batch on the dense arrays;
+      (b) fused: cirsrad_ck_singlescatt_batch_cont, the three arrays formed per distinct layer inside the call.
+    Medians of `runs` rounds after a warm-up of both, the order of (a) and (b) swapped from round to round.
+        python tools/bench_extra.py ss_cont [runs]"""
+    import torch
+    from archnemesis_dist_amd.jacobian import perturbed_states
+    from archnemesis_dist_amd.profile_state import ContinuousProfileState
+    from archnemesis_dist_amd.scatter_state import BatchedCKSingleScatterModel, singlescatt_dense_by_hand
+    from bench import torch_ktable
+    if len(sys.argv) > 2:
+        runs = int(sys.argv[2])
+    W, G, S, L, NP, NT, ND = 10000, 20, 8, 100, 20, 15, 2
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    PRESS, TEMP, K = torch_ktable(torch, torch.device("cuda", 0), W, G, NP, NT, S, seed=20260704)
+    WAVE = 200.0 + 0.1 * np.arange(W)
+    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+    pr = syn.synth_profiles(100, S + 2, seed=11)
+    zl = np.linspace(0.0, 1.0, 100)
+    DUST = np.stack([2.0e3 * np.exp(-4.0 * zl), 3.0e2 * np.exp(-((zl - 0.4) / 0.1) ** 2) + 1.0e-3], axis=1)
+    SWAVE = np.linspace(0.9 * WAVE[0], 1.1 * WAVE[-1], 12)
+    xs = np.linspace(0.0, 1.0, 12)[:, None]
+    KEXT = 1.0e-9 * (1.0 + 0.6 * np.sin(5.0 * xs + np.arange(ND)[None])) * (1.0 + np.arange(ND)[None])
+    KSCA = 0.7 * KEXT * (1.0 - 0.5 * xs)
+    st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T", ("VMR", 2)])
+    phase_fn = 10.0 ** rng.uniform(-1.5, 0.3, (W, 1, ND + 1))
+    model = BatchedCKSingleScatterModel(eng, st, pr["RADIUS"], pr["ID"], pr["ISO"], list(range(2, S + 2)), phase_fn, [30.0], [20.0],
+                                        10.0 ** rng.uniform(-8, -7, W), layering_args=dict(NLAY=L, LAYINT=1, NINT=101),
+                                        geometry=dict(ANGLE=20.0, EMISS_ANG=20.0), IRAY=1, cia=syn.synth_cia(),
+                                        dust=dict(SWAVE=SWAVE, KEXT=KEXT, KSCA=KSCA, DUST=DUST), BRDF=rng.uniform(0.0, 0.15, (W, 1)),
+                                        emissivity=rng.uniform(0.7, 1.0, W))
+    model.upload_sources()
+    X = perturbed_states(st.XN, 0.05 * st.XN).T
+    lay = model.layers(X)
+    n = X.shape[0]
+    path = lay["path"]
+    rt = (path.NLAYIN, path.LAYINC, np.repeat(path.SCALE[None], n, 0), path.EMTEMP, np.full(n, -1.0), model.emissivity, model.BRDF,
+          model.solar, model.SOL_ANG, model.EMISS_ANG)
+    small = [lay[k] for k in ("PRESS", "TEMP", "amount", "VMRLAY", "FRAC", "TOTAM", "DELH", "CONT")] + [rt[2], rt[3]]
+    info = {}
+
+    def array_level():
+        t = time.perf_counter()
+        d = singlescatt_dense_by_hand(eng, 0, 1, model.ID, model.ISO, model.cia, model.dust, lay, phase_fn)
+        info["a_formation_s"] = time.perf_counter() - t
+        info["a_bytes"] = sum(a.nbytes for a in d) + sum(a.nbytes for a in small[:3] + small[8:])
+        return eng.cirsrad_ck_singlescatt_batch(0, lay["PRESS"], lay["TEMP"], lay["amount"], *d, *rt)
+
+    def fused():
+        return eng.cirsrad_ck_singlescatt_batch_cont(0, lay["PRESS"], lay["TEMP"], lay["amount"], lay["VMRLAY"], lay["FRAC"], lay["TOTAM"],
+                                                     lay["DELH"], lay["CONT"], 1, None, phase_fn, *rt)
+    res = {"what": "numerical Jacobian, single scattering (ISCAT = 3) at C2 size with CIA, two aerosol populations and IRAY 1: %d "
+                   "forward models, W=1e4, L=100, S=8, G=20, one path; host arrays in / out" % n, "forward_models": n, "runs": runs}
+    ref = array_level()
+    res["bit_identical"] = bool(np.array_equal(fused(), ref))
+    ta, tb, fa, ka, kb = [], [], [], [], []
+    for r in range(runs):
+        for which in (("a", "b") if r % 2 == 0 else ("b", "a")):
+            t = time.perf_counter(); (array_level if which == "a" else fused)(); dt = time.perf_counter() - t
+            (ta if which == "a" else tb).append(dt)
+            (ka if which == "a" else kb).append(eng.last_kernel_ms())
+            if which == "a":
+                fa.append(info["a_formation_s"])
+            else:
+                res["fused_rows"] = list(eng.last_layer_rows()); res["fused_rt_shared"] = bool(eng.last_rt_shared())
+    med = lambda v: float(np.median(v))
+    res["array_level_wall_s"] = med(ta); res["array_level_wall_s_all"] = ta
+    res["array_level_formation_s"] = med(fa); res["array_level_dense_entry_s"] = med([a - f for a, f in zip(ta, fa)])
+    res["fused_wall_s"] = med(tb); res["fused_wall_s_all"] = tb
+    res["speedup"] = res["array_level_wall_s"] / res["fused_wall_s"]
+    for tag, ks in (("array_level", ka), ("fused", kb)):
+        res[tag + "_gas_opacity_kernel_ms"] = med([k["overlap_ms"] for k in ks])
+        res[tag + "_rt_kernel_ms"] = med([k["rt_ms"] for k in ks])
+    res["array_level_input_GB"] = info["a_bytes"] / 1e9
+    res["fused_input_GB"] = (sum(a.nbytes for a in small) + phase_fn.nbytes) / 1e9
+    out["singlescatt_jacobian_C2_cont"] = res
 
 
 def bench_maps(eng, out, rng):
