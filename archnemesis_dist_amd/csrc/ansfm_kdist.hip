@@ -39,7 +39,10 @@ __global__ __launch_bounds__(256) void k_kdist_gather(KdistParams p)
                 w = ((y1 - y0) / (x1 - x0)) * (d - x0) + y0;
             }
         }
-        p.keys[o + j] = p.kabs[i0 + j];
+        // np.argsort puts a NaN of either sign last; the radix sort orders by bit pattern, where a NaN with the sign bit
+        // set would come first: every NaN key goes in as the positive quiet NaN
+        const double k = p.kabs[i0 + j];
+        p.keys[o + j] = (k != k) ? __longlong_as_double(0x7ff8000000000000LL) : k;
         p.vals[o + j] = w * p.dv;
     }
 }
@@ -73,13 +76,16 @@ __global__ __launch_bounds__(256) void k_kdist_quantiles(KdistParams p)
     for (int q = tid; q < p.NG; q += 256) {            // np.interp(G_ORD, g_sorted, k_sorted)
         const double x = p.g_ord[q];
         double v;
-        if (x <= g[0]) v = ks[0];
-        else if (x >= g[n - 1]) v = ks[n - 1];
+        // np.interp takes the last node with g <= x: with leading zero weights g begins with a run of zeros, and the
+        // ordinate 0 reads the k of the last of them, not ks[0] -- equality is left to the bisection below.  A single
+        // point is returned whatever its g (np.interp's search never compares against a lone NaN abscissa).
+        if (n == 1 || x >= g[n - 1]) v = ks[n - 1];
+        else if (x < g[0]) v = ks[0];
         else {
             int a = 0, c = n - 1;
             while (c - a > 1) { const int m = (a + c) >> 1; if (g[m] <= x) a = m; else c = m; }
             const double slope = (ks[a + 1] - ks[a]) / (g[a + 1] - g[a]);
-            v = slope * (x - g[a]) + ks[a];
+            v = (x == g[a]) ? ks[a] : slope * (x - g[a]) + ks[a];      // on a node: its k, also next to an infinite one
         }
         p.kout[(size_t)b * p.NG + q] = v;
     }
