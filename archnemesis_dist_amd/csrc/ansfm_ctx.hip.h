@@ -11,6 +11,7 @@
 //   ansfm_lbl.hip      runtime line-by-line
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
+//   ansfm_hgfit.hip    double Henyey-Greenstein fit of phase functions
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
 //   ansfm_transit.hip, ansfm_occultation.hip, ansfm_limb.hip, ansfm_disc.hip  the fused gradient routes, collapsed over the
 //                      paths (transit), with the tangent paths mixed to the geometries (occultation, limb) or with the averaging
@@ -190,6 +191,10 @@ struct ansfm_ctx {
     int mie_block = 0, mie_cap = 0;                      // 0: the defaults (kMieBlockDefault radii, 2^20 radii)
     double mie_ms = 0;                                   // kernel time, blocks and the largest block of the last call
     int mie_blocks = 0, mie_block_radii = 0;
+    // double Henyey-Greenstein fit (ansfm_hg_fit): cos(theta), the phase functions, the results and the per-fit counts and
+    // flags; kernel time of the last call
+    DevBuf hg_st;
+    double hg_ms = 0;
     // surface reflection (ansfm_surface_brdf, ansfm_brdf_matrix): the result, the per-azimuth table, kernel time of the last call
     DevBuf brdf_out, brdf_azi;
     double brdf_ms = 0;

@@ -1309,6 +1309,30 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_mie_last(self._ctx, C.byref(ms), C.byref(nb), C.byref(nr)), "mie_last")
         return ms.value, nb.value, nr.value
 
+    HG_FIT_NPHASE_CAP = 8192               # angles of a phase function ansfm_hg_fit takes
+
+    def hg_fit(self, theta, phase, return_counts=False):
+        """Scatter_0.subfithgm (:1948): the double Henyey-Greenstein fit of phase functions.  theta (nphase,) degrees, phase
+        (nfit, nphase) normalised to 4 pi -> (f, g1, g2, rms), each (nfit,); with return_counts a fifth item, int32
+        (nfit, 2): the calls of mrqminl a fit took and the accepted ones.  ValueError for shapes that do not match, nphase
+        outside 1 .. HG_FIT_NPHASE_CAP, and for a fit whose normal equations are singular (the text names the fit)."""
+        theta = _np(np.atleast_1d(theta)); phase = _np(phase)
+        if theta.ndim != 1 or phase.ndim != 2 or phase.shape[1] != theta.shape[0] or phase.shape[0] < 1:
+            raise ValueError("hg_fit: theta (nphase,), phase (nfit, nphase)")
+        nfit, nphase = phase.shape
+        f, g1, g2, rms = np.empty(nfit), np.empty(nfit), np.empty(nfit), np.empty(nfit)
+        counts = np.zeros((nfit, 2), dtype=np.int32)
+        rc = self._lib.ansfm_hg_fit(self._ctx, nfit, nphase, _ptr(theta), _ptr(phase), _ptr(f), _ptr(g1), _ptr(g2), _ptr(rms),
+                                    _ptr(counts))
+        self._check(rc, "hg_fit")
+        return (f, g1, g2, rms, counts) if return_counts else (f, g1, g2, rms)
+
+    def hg_fit_last(self):
+        """kernel milliseconds of the last hg_fit call"""
+        ms = C.c_double()
+        self._check(self._lib.ansfm_hg_fit_last(self._ctx, C.byref(ms)), "hg_fit_last")
+        return ms.value
+
     SURFACE_NPAR = {1: 1, 2: 10, 3: 2}     # rows of `params` per LowerBoundaryConditionEnum value
 
     def _surface_params(self, what, lowbc, params, zero_ok=False):

@@ -1122,6 +1122,95 @@ def install_gpu_mie(device=0):
     return makephase
 
 
+HG_FIT_MEMO_ENTRIES = 8                # fits the Henyey-Greenstein hook remembers: one per size distribution of the Mie memo
+HG_FIT_NPHASE_CAP = AnsfmEngine.HG_FIT_NPHASE_CAP      # angles of a phase function the engine's hg_fit takes
+
+
+def install_gpu_hg_fit(device=0):
+    """Route the module-level Scatter_0.subfithgm (Scatter_0.py:1948; the class method Scatter_0.makephase resolves the
+    module attribute at call time, :1366) -- the Levenberg-Marquardt fit of (f, g1, g2) to every wavelength's phase function
+    that follows the Mie integration when IMIE = 0 -- through the GPU.  A call the engine refuses (arguments that are not a
+    1-D and a 2-D float64 array of matching shapes, more than HG_FIT_NPHASE_CAP angles, an engine error such as a singular
+    fit) is delegated, so that the reference fails its own way.  The hook remembers the last HG_FIT_MEMO_ENTRIES results under
+    the bytes of (theta, phase), as the Mie hook does with its arguments, and a remembered call returns copies.
+    summary()["routes"] counts `hg fit` and `hg fit (memo)`."""
+    import importlib
+    from collections import OrderedDict
+    from ._lib import AnsfmError
+    sc = importlib.import_module("archnemesis.Scatter_0")
+    eng = get_engine(device)
+    ref_fn = getattr(sc, "_ansfm_reference_subfithgm", None) or sc.subfithgm
+    memo = OrderedDict()
+
+    def subfithgm(theta, phase):
+        f8 = lambda a, ndim: isinstance(a, np.ndarray) and a.dtype == np.float64 and a.ndim == ndim
+        if not (f8(theta, 1) and f8(phase, 2) and phase.shape[1] == theta.shape[0] and phase.shape[0] >= 1 and theta.shape[0] >= 1):
+            _delegate("subfithgm: arguments that are not float64 arrays (nphase,) and (nwave, nphase)")
+            return ref_fn(theta, phase)
+        if theta.shape[0] > HG_FIT_NPHASE_CAP:
+            _delegate("subfithgm: more than %d angles" % HG_FIT_NPHASE_CAP)
+            return ref_fn(theta, phase)
+        args = (np.ascontiguousarray(theta), np.ascontiguousarray(phase))
+        key = tuple((a.shape, a.tobytes()) for a in args)
+        hit = memo.get(key)
+        if hit is not None:
+            memo.move_to_end(key)
+            _route("hg fit (memo)")
+            return tuple(a.copy() for a in hit)
+        try:
+            out = eng.hg_fit(args[0], args[1])
+        except (ValueError, NotImplementedError, AnsfmError):
+            _delegate("subfithgm: a fit the engine gives up on")
+            return ref_fn(theta, phase)
+        _route("hg fit")
+        memo[key] = tuple(np.array(a, dtype=np.float64) for a in out[:4])
+        while len(memo) > HG_FIT_MEMO_ENTRIES:
+            memo.popitem(last=False)
+        return tuple(a.copy() for a in memo[key])
+
+    sc._ansfm_reference_subfithgm = ref_fn
+    sc.subfithgm = subfithgm
+    return subfithgm
+
+
+def aerosol_memo_capacity(variables):
+    """Entries the Mie and the fit memo need so that a staged Jacobian computes every distinct aerosol state once:
+    max(8, 1 + the state-vector elements of the models whose class calls Scatter.makephase).  A staged route walks
+    `for geometry: for state: for averaging point`, so a memo smaller than the distinct aerosol states has dropped the first
+    state when the next geometry asks for it again, and every geometry recomputes them all.  Model 444 carries two
+    size-distribution elements beside its imaginary-index array: more than five of those are more than eight states."""
+    import inspect
+    n = 0
+    for model in getattr(variables, "models", None) or ():
+        try:
+            calls = "makephase" in inspect.getsource(type(model))
+        except (OSError, TypeError):
+            calls = False
+        if calls:
+            n += int(getattr(model, "n_state_vector_entries", 0))
+    return max(MIE_MEMO_ENTRIES, HG_FIT_MEMO_ENTRIES, 1 + n)
+
+
+class raised_memo_capacity:
+    """with raised_memo_capacity(variables): the Mie and fit memos hold aerosol_memo_capacity(variables) entries inside the
+    block and their defaults again after it (a memo that has grown is cut back by its next new entry).  No result changes:
+    a memo only spares the engine a call."""
+
+    def __init__(self, variables):
+        self.variables = variables
+
+    def __enter__(self):
+        global MIE_MEMO_ENTRIES, HG_FIT_MEMO_ENTRIES
+        self.saved = (MIE_MEMO_ENTRIES, HG_FIT_MEMO_ENTRIES)
+        MIE_MEMO_ENTRIES = HG_FIT_MEMO_ENTRIES = aerosol_memo_capacity(self.variables)
+        return self
+
+    def __exit__(self, *exc):
+        global MIE_MEMO_ENTRIES, HG_FIT_MEMO_ENTRIES
+        MIE_MEMO_ENTRIES, HG_FIT_MEMO_ENTRIES = self.saved
+        return False
+
+
 BRDF_MEMO_ENTRIES = 2                  # BRDF matrices the surface hook remembers: no model of the reference retrieves a Hapke
                                        # parameter, and one matrix is 0.18 GB at W = 10^4, NMU = 16, NF = 8
 HAPKE_ATTRS = ("SGLALB", "K", "BS0", "hs", "BC0", "hc", "ROUGHNESS", "G1", "G2", "F")   # calc_Hapke_BRDF's order
@@ -1509,7 +1598,7 @@ def install_all(device=0, oe_linalg=True, ktable_generator=True, forward_model=T
     if forward_model:
         install_gpu_forward_model(device); done.append("install_gpu_forward_model")
     for f in (install_gpu_gradient_maps, install_gpu_scattering_core, install_gpu_line_kernel, install_gpu_pseudo_continuum,
-              install_gpu_mie, install_gpu_surface, install_gpu_layering, install_gpu_convolution, install_gpu_continuum,
+              install_gpu_mie, install_gpu_hg_fit, install_gpu_surface, install_gpu_layering, install_gpu_convolution, install_gpu_continuum,
               install_gpu_table_reader):
         f(device); done.append(f.__name__)
     if oe_linalg:

@@ -44,6 +44,19 @@ IFORM_NORMALISED_RADIANCE = 5          # SpectraUnitEnum.Normalised_radiance
 IFORM_INTEGRATED_RADIANCE = 6          # SpectraUnitEnum.Integrated_radiance
 
 
+def _with_aerosol_memos(route):
+    """A staged route walks `for geometry: for state: for averaging point` and so meets every distinct aerosol state once per
+    geometry: for its duration the Mie and Henyey-Greenstein fit memos hold all of them (forward_model.aerosol_memo_capacity),
+    afterwards their default again."""
+    import functools
+
+    @functools.wraps(route)
+    def wrapped(self, *args, **kwargs):
+        with _fm.raised_memo_capacity(self.Variables):
+            return route(self, *args, **kwargs)
+    return wrapped
+
+
 class JacobianGPU:
     """Mixin: jacobian_nemesis without the joblib fan-out.  Sits in front of CIRSradGPU and the reference class."""
 
@@ -189,6 +202,7 @@ class JacobianGPU:
         self.LayerX.DUST_UNITS_FLAG = self.AtmosphereX.DUST_UNITS_FLAG
         self.calc_path()
 
+    @_with_aerosol_memos
     def _ansfm_staged_route(self, xnx, ixrun, info, disc=False):
         """nemesisfm per state up to CIRSrad, one batched call per (geometry, averaging point), the rest per state.  disc = True
         (jacobian_nemesis(nemesisdisc=True)): nemesisdiscfm (:1609-1716) is the same forward model with the averaging points
@@ -304,6 +318,7 @@ class JacobianGPU:
             out[:, 0] += 0.5 * (lower + upper) * ((base_km[i + 1] - base_km[i]) * 1.0e3)
         return (out + area_disc) / area_star * 100.
 
+    @_with_aerosol_memos
     def _ansfm_staged_limb_route(self, xnx, ixrun, info, kind="L"):
         """jacobian_nemesis(nemesisL=True): every forward model is nemesisLfm (:1254-1368) -- all tangent paths of a state in one
         CIRSrad call.  Its host code runs per state as the reference wrote it (deep copies, subprofretg with the hydrostatic

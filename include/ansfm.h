@@ -1028,6 +1028,26 @@ int ansfm_mie_set_radius_block(ansfm_ctx *ctx, int radii);
 int ansfm_mie_set_radius_cap(ansfm_ctx *ctx, int radii);
 int ansfm_mie_last(const ansfm_ctx *ctx, double *kernel_ms, int32_t *blocks, int32_t *block_radii);
 
+/* ---- Double Henyey-Greenstein fit of a phase function --------------------------------------------------------------------
+ * Scatter_0.subfithgm (Scatter_0.py:1948): what the class method Scatter_0.makephase runs after the Mie integration when
+ * IMIE = 0 (:1366).  theta_deg[nphase], phase[nfit][nphase] (normalised to 4 pi, as makephase hands it over) -> f, g1, g2,
+ * rms[nfit]: per fit a Levenberg-Marquardt chain from (0.5, 0.5, -0.5) against log(phase), with the reference's finite
+ * differences (dx = 0.01 and its sign flips), clips (f in [1e-6, 0.999999], g1 in [0, 0.98], g2 in [-0.98, -0.1]), damping
+ * (alamda from 1000, times 0.9 when accepted, times 1.5 up to 1e36 when not) and stopping rule (more than 5 accepted calls in
+ * a row with a relative change of chisq below 1e-8, or 1000 calls); rms = sqrt(chisq).  counts[nfit][2] (may be NULL): the
+ * calls of mrqminl a fit took and how many were accepted.
+ * One wavefront per fit; the sums over the angles have one order (per lane the angles i, i + 64, ... ascending, then a fixed
+ * tree over the lanes), so a fit's bits do not depend on the fits beside it.  The normal equations are solved by Gaussian
+ * elimination with partial pivoting where the reference inverts the matrix: the results agree to the 1e-8 the stopping rule
+ * defines them to, the counts need not.  A phase function with a 0 or a NaN gives what the reference gives (the start point
+ * and rms = inf or NaN); nothing is checked about the values.
+ * ANSFM_ERR_INVALID, before anything is launched, for nfit outside 1 .. 2^20, nphase outside 1 .. 8192 or a null pointer;
+ * and, naming the fit, where the elimination meets an exact zero pivot (the reference ends in "Singular matrix" there).
+ * ansfm_hg_fit_last: kernel milliseconds of the last call. */
+int ansfm_hg_fit(ansfm_ctx *ctx, int nfit, int nphase, const double *theta_deg, const double *phase, double *f, double *g1,
+                 double *g2, double *rms, int32_t *counts);
+int ansfm_hg_fit_last(const ansfm_ctx *ctx, double *kernel_ms);
+
 /* ---- Surface reflection ----------------------------------------------------------------------------------------------------
  * lowbc takes the values of LowerBoundaryConditionEnum and decides the rows of params[npar][nwave]:
  *   1 LAMBERTIAN  the albedo

@@ -605,6 +605,24 @@ def bench_mie(eng, out, nwave=64, n=5):
     res["host_vs_gpu"] = {"counts_equal": bool(np.array_equal(hc, counts[pick])),
                           "xext_rel": float(np.max(np.abs(xe[pick] / he - 1))), "phas_rel": float(np.max(np.abs(ph[pick] / hp - 1)))}
     out["mie_lognormal_64_wavelengths"] = res
+    # ... and what follows it with IMIE = 0: the double Henyey-Greenstein fit of the 64 phase functions at the 41 angles
+    # (Scatter_0.subfithgm).  Kernel time from hg_fit_last, the median of n calls end to end, the calls of mrqminl per fit,
+    # and the NumPy restatement of tests/hgfit_cases.py on the same 64 fits -- NOT a comparator either.
+    import hgfit_cases as hg
+    run = lambda: eng.hg_fit(thetax, ph, return_counts=True)
+    wall = timeit(run, n)
+    kernel_ms = eng.hg_fit_last()
+    f, g1, g2, rms, calls = run()
+    t = time.perf_counter()
+    host_fit = hg.subfithgm_np(thetax, ph, order="kernel", return_counts=True)
+    host = time.perf_counter() - t
+    dev = hg.deviations((f, g1, g2, rms), host_fit)
+    out["hg_fit_64_wavelengths_41_angles"] = {
+        "end_to_end_ms": 1e3 * wall, "kernel_ms": kernel_ms, "median_of": n, "angles": int(thetax.shape[0]),
+        "calls_min_median_max": [int(calls[:, 0].min()), int(np.median(calls[:, 0])), int(calls[:, 0].max())],
+        "accepted_min_max": [int(calls[:, 1].min()), int(calls[:, 1].max())], "calls_total": int(calls[:, 0].sum()),
+        "host_restatement_s_all_fits_not_a_comparator": host,
+        "host_vs_gpu": {"calls_equal": bool(np.array_equal(host_fit[4], calls)), "params_rel": dev[0], "rms_rel": dev[1]}}
 
 
 def bench_brdf(eng, out, W=10000, NMU=16, NPHI=101, NF=8, n=3, slice_w=16):
