@@ -488,11 +488,27 @@ int ansfm_last_merge_suffix(const ansfm_ctx *cctx, int64_t *rows, int64_t *rows_
     *rows = *rows_of_list_merges = 0;
     if (ctx->d_flag.bytes < kFlagInts * sizeof(int)) return ANSFM_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    unsigned long long v[kMergeTotals] = {0, 0, 0, 0};  // walked merges, all merges, pattern bytes, rows walked behind a list phase
+    unsigned long long v[4] = {0, 0, 0, 0};  // walked merges, all merges, pattern bytes, rows walked behind a list phase
     HIPCHK(hipMemcpyAsync(v, ctx->d_flag.as<int>() + kFlagTileCounter + 8, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     *rows = (int64_t)v[3];
     *rows_of_list_merges = (int64_t)(v[1] - v[0]) * ctx->last_merge_G;
+    return ANSFM_OK;
+}
+
+int ansfm_last_merge_static(const ansfm_ctx *cctx, int64_t *merges, int *valid)
+{
+    ansfm_ctx *ctx = const_cast<ansfm_ctx *>(cctx);     // as ansfm_last_merge_rowmajor
+    CHECK_CTX(ctx);
+    if (!merges || !valid) FAIL(ANSFM_ERR_INVALID, "last_merge_static: null argument");
+    *merges = 0;
+    *valid = ctx->last_merge.static_tables ? 1 : 0;
+    if (ctx->d_flag.bytes < kFlagInts * sizeof(int)) return ANSFM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    unsigned long long v = 0;                           // the fifth total behind the tile counters
+    HIPCHK(hipMemcpyAsync(&v, ctx->d_flag.as<int>() + kFlagTileCounter + 8 + 8, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *merges = (int64_t)v;
     return ANSFM_OK;
 }
 

@@ -90,10 +90,11 @@ using ansfm::FusedRoute;
 using ansfm::LblrtIso;
 
 // ints of ansfm_ctx::d_flag: 0 the upload kernels' flag, 1 "unsorted input", 12 the de-duplication's row counter, 13 the
-// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's four
-// 64-bit totals (row-major merges, all merges, non-zero pattern bytes read, rows walked behind a list phase), which one memset per launch clears together
+// merge redo count; from kFlagTileCounter the merge kernels' eight tile queues and, behind them, the forward merge's five
+// 64-bit totals (row-major merges, all merges, non-zero pattern bytes read, rows walked behind a list phase, merges walked on
+// the static schedule), which one memset per launch clears together
 // (merge_launch_begin)
-constexpr int kFlagInts = 32, kFlagTileCounter = 16, kMergeTotals = 4;
+constexpr int kFlagInts = 40, kFlagTileCounter = 16, kMergeTotals = 5;
 static_assert(kFlagTileCounter + 8 + 2 * kMergeTotals <= kFlagInts, "the totals lie inside d_flag");
 
 struct ansfm_ctx {

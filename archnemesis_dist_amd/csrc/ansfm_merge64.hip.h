@@ -13,7 +13,8 @@
 //             near the front of the list (kOptOrient, MergeOrient).  With float32 weights the pair weight is in addition one
 //             ds_read_b64 of a product table WT[(col << 5) | row] that the waves of one block per CU share (kOptTable); with
 //             float64 weights the walk's gd + DG[i] * DG[j] is compiled as one fma, which no table of products reproduces.
-//             With the table, a wave whose lanes' merges all sort row by row walks them without the list (merge_rowmajor).
+//             With the table, a wave whose lanes' merges all sort row by row walks them without the list (merge_rowmajor), and
+//             from the start of a merge on the launch's static schedule of bin crossings (merge_rowmajor_static).
 // Both forms give the same results bit for bit (tests/test_merge_*.py).  What each piece bought, and the variants that were
 // measured and lost (tools/experiments/r07_merge_retired_variants.patch), is in DESIGN.md section 4.1.
 #pragma once
@@ -550,6 +551,135 @@ __device__ __forceinline__ void merge_rowmajor(int i0, int G, const MergeOrient 
             merge_rowmajor_row<NR>(a1, c, w1, G, ws, rec);
         }
     }
+}
+
+// ---- whole walks on the launch's static schedule (kFlagStatic; MergeStatic in ansfm_merge_plan.h) --------------------------------
+// A wave that walks a WHOLE merge (i0 == 0) starts at gd = 0 and adds WT[i][j] in row-major order in every lane: gd, the verdict
+// gdn >= gnext of every element, the factors gnext - gd and gdn - gnext of a crossing and the bin it closes are the same in
+// every lane, every merge and every tile of the launch.  merge_static_build forms them on the host by the recurrence of
+// merge_walk_nodiv, and the block's prologue copies them into LDS behind the weight table (merge_static_fill).  The walk keeps
+// what is per lane: cv = row + column and kacc = fma(cv, w, kacc), and at a crossing fma(C1, cv, kacc) and C2 * cv -- the
+// operations of merge_walk_nodiv on the doubles it would have formed, so every closed sum has its bits.  No gd, no compare,
+// no exec mask: whether an element closes a bin is a bit of the row's mask, tested by scalar code.
+// The suffix form (0 < i0 < G) keeps merge_rowmajor: its gd comes out of a list phase whose order is per lane, so it is not
+// uniform and no schedule applies.
+// Closed bins stay on chip.  The schedule is valid only if bin b closes in row b or later; entry b of the rows operand has then
+// been read (it is in a register before row b's first element), and A's slot b is free in either orientation: a lane whose
+// rows are a is past it, a lane whose rows are b holds a as its columns, which are in registers from the start of the walk.
+// So the closed sum goes to A[b] un-normalised (one LDS write, no record in global memory) and the kernel's end pass divides
+// in place.  Nothing inside the walk reads scalar memory: the waits stay counted LDS waits.
+constexpr unsigned kStaticRD = 0, kStaticC = kMaxG * 16u, kStaticMask = 2u * kMaxG * 16u;    // byte offsets in the static tables
+static_assert(kStaticMask + kMaxG * 4u == kMergeStaticLds, "the plan's LDS arithmetic");
+__device__ __forceinline__ unsigned merge_static_base(int G) { return kLdsWT + weight_table_bytes(G); }
+typedef __attribute__((address_space(3))) dbl2 lds_dbl2;
+typedef __attribute__((address_space(3))) unsigned lds_uint;
+__device__ __forceinline__ dbl2 lds_ld2(unsigned a) { return *(const lds_dbl2 *)(size_t)a; }
+// n / d from (r, d), r the refined reciprocal of d: fast_div's quotient and residual step on fast_div's own r (merge_static_fill)
+__device__ __forceinline__ double recip_div(double n, dbl2 rd)
+{
+    const double q = n * rd.x;
+    return fma(fma(-rd.y, q, n), rd.x, q);
+}
+// Prologue, lanes of wave 0: (reciprocal, width) of every bin -- v_rcp_f64 and fast_div's two Newton steps, on the device because
+// the hardware reciprocal is not the host's -- and the schedule from the kernel arguments
+__device__ __forceinline__ void merge_static_fill(const OverlapParams &p, int G, int lane)
+{
+    const unsigned sb = merge_static_base(G);
+    if (lane < G) {
+        const double d = p.g_ord[lane + 1] - p.g_ord[lane];
+        double r = __builtin_amdgcn_rcp(d);
+        r = fma(fma(-d, r, 1.0), r, r);
+        r = fma(fma(-d, r, 1.0), r, r);
+        *(lds_dbl2 *)(size_t)(sb + kStaticRD + (unsigned)lane * 16u) = dbl2{r, d};
+    }
+    if (lane < kMaxG) {
+        *(lds_dbl2 *)(size_t)(sb + kStaticC + (unsigned)lane * 16u) = dbl2{p.st.c1[lane], p.st.c2[lane]};
+        *(lds_uint *)(size_t)(sb + kStaticMask + (unsigned)lane * 4u) = p.st.rowmask[lane];
+    }
+}
+struct StaticWalk {
+    double kacc;
+    dbl2 cc;            // (C1, C2) of the next crossing, read when the one before it closed
+    unsigned caddr;     // its LDS address; entry 32 of a G = 32 schedule is read and never used (the masks follow)
+    unsigned oaddr;     // this lane's slot of A for the bin that closes next
+};
+template <bool TEST>
+__device__ __forceinline__ void merge_static_elem(int j, double cv, double w, unsigned mask, StaticWalk &sw)
+{
+    if (TEST && ((mask >> j) & 1u) != 0) {
+        lds_st(sw.oaddr, fma(sw.cc.x, cv, sw.kacc));
+        sw.kacc = sw.cc.y * cv;
+        sw.oaddr += 512u;
+        sw.caddr += 16u;
+        sw.cc = lds_ld2(sw.caddr);
+    } else
+        sw.kacc = fma(cv, w, sw.kacc);
+}
+// One row.  With the Gauss-Legendre weights a row's crossings sit at its first or last column (bin b closes where row b ends,
+// up to rounding), so the columns that every launch of the list length has, the first aside, run straight through unless the mask
+// names one of them; the first and the columns from merge_rowmajor_sure_cols on test their bit.  Lists above 20 read a weight
+// for its step (merge_rowmajor), w is unused there.
+template <int NR>
+__device__ __forceinline__ void merge_static_row(double ai, const double (&c)[NR], const double (&w)[NR], unsigned wa, unsigned mask,
+                                                 int G, StaticWalk &sw)
+{
+    constexpr int kSure = merge_rowmajor_sure_cols(NR);
+    constexpr unsigned kInner = ((1u << kSure) - 1u) & ~1u;
+    const auto weight = [&](int j) { if constexpr (NR > 20) return lds_ld(wa + (unsigned)j * 256u); else return w[j]; };
+    merge_static_elem<true>(0, ai + c[0], weight(0), mask, sw);
+    if ((mask & kInner) == 0) {
+#pragma unroll
+        for (int j = 1; j < kSure; ++j) merge_static_elem<false>(j, ai + c[j], weight(j), mask, sw);
+    } else {
+#pragma unroll
+        for (int j = 1; j < kSure; ++j) merge_static_elem<true>(j, ai + c[j], weight(j), mask, sw);
+    }
+#pragma unroll
+    for (int j = kSure; j < NR; ++j)
+        if (j < G) merge_static_elem<true>(j, ai + c[j], weight(j), mask, sw);
+}
+__device__ __forceinline__ unsigned merge_static_mask(unsigned sb, int i)
+{
+    return *(const lds_uint *)(size_t)(sb + kStaticMask + ((unsigned)i << 2));
+}
+// The whole walk; returns kacc of the open bin.  a_lane: the LDS address of this lane's entry of A's row 0.  The rows are read
+// as merge_rowmajor reads them, a row ahead, and the row's mask with them (one v_readfirstlane when its row begins).
+template <int NR>
+__device__ __forceinline__ double merge_rowmajor_static(int G, const MergeOrient &mo, unsigned a_lane)
+{
+    const unsigned sb = merge_static_base(G);
+    double c[NR], w0[NR], a0;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) c[j] = lds_ld(mo.cbase + (unsigned)(j < G ? j : 0) * 512u);
+    StaticWalk sw;
+    sw.kacc = 0.0;
+    sw.caddr = sb + kStaticC;
+    sw.cc = lds_ld2(sw.caddr);
+    sw.oaddr = a_lane;
+    if constexpr (NR > 20) {
+        for (int i = 0; i < G; ++i) {
+            a0 = lds_ld(mo.rbase + ((unsigned)i << 9));
+            const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)merge_static_mask(sb, i));
+            merge_static_row<NR>(a0, c, c, kLdsWT + ((unsigned)i << 3), m, G, sw);
+        }
+        return sw.kacc;
+    }
+    double w1[NR], a1;
+    unsigned m0 = merge_static_mask(sb, 0), m1;
+    merge_rowmajor_weights<NR>(w0, a0, 0, G, mo);
+    for (int i = 0; i < G; i += 2) {
+        const int i1 = i + 1 < G ? i + 1 : i;
+        m1 = merge_static_mask(sb, i1);
+        merge_rowmajor_weights<NR>(w1, a1, i1, G, mo);
+        merge_static_row<NR>(a0, c, w0, 0u, (unsigned)__builtin_amdgcn_readfirstlane((int)m0), G, sw);
+        if (i + 1 < G) {
+            const int i2 = i + 2 < G ? i + 2 : i;
+            m0 = merge_static_mask(sb, i2);
+            merge_rowmajor_weights<NR>(w0, a0, i2, G, mo);
+            merge_static_row<NR>(a1, c, w1, 0u, (unsigned)__builtin_amdgcn_readfirstlane((int)m1), G, sw);
+        }
+    }
+    return sw.kacc;
 }
 
 // Per-lane insertion sort of one LDS column (values ascending, stable) carrying the original index of every

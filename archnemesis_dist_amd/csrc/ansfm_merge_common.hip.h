@@ -112,6 +112,9 @@ struct OverlapParams {
     // two buffers, so that no wave reads a byte that a wave of the same launch wrote
     const unsigned char *hint_in;
     unsigned char *hint_out;
+    // the static schedule of a whole row-major walk (merge_static_build); read only by a launch with kFlagStatic, which copies
+    // it into LDS in its prologue
+    MergeStatic st;
 };
 // The g-fastest copy of the table (k_table_gfast builds it from lnK): the G ordinates of one (p, T, gas, wavenumber) lie as one
 // run of Gs doubles, G rounded up to even so that every run starts 16-byte aligned and is read as Gs / 2 pairs; the pad

@@ -1,9 +1,11 @@
 // ansfm_merge_plan.h -- how a forward merge is launched, decided on the host from integers alone: the constants the merge
 // kernels and their launchers share, the switches of the environment (MergeSwitches), the facts of one call (MergeCall) and
 // the plan that follows from the two (merge_plan -> MergePlan: which k_ck_overlap, its block, LDS, grid and arguments, and
-// what ansfm_last_merge_* report).  No HIP header: a plain C++17 compiler builds it (tests/host/merge_plan_main.cpp); the
+// what ansfm_last_merge_* report), and the static schedule of a whole row-major walk, formed from the call's weights
+// (merge_g_ord, merge_static_build -> MergeStatic; tests/host/merge_static_main.cpp).  No HIP header: a plain C++17 compiler builds it (tests/host/merge_plan_main.cpp); the
 // kernel headers include it for the constants.  DESIGN.md 4.1, "The launch plan".
 #pragma once
+#include <float.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,6 +38,10 @@ constexpr int kFlagTableGfast = 4;
 // a further bit, never set by default and read by the table kernels only: ANSFM_MERGE_SUFFIX=0, a merge that is not row-major
 // from its first row keeps the head list to its end (merge_suffix_row)
 constexpr int kFlagSuffixOff = 8;
+// two further bits, read by the table kernels of the lists from kStaticMinList entries only and not in the trims: the launch
+// carries a valid static schedule of the whole walk (MergeStatic; its tables and the reciprocals of the bin widths follow the
+// weight table in LDS), and ANSFM_MERGE_STATIC=0, a whole walk keeps the per-lane step (merge_rowmajor) all the same
+constexpr int kFlagStatic = 16, kFlagStaticOff = 32;
 // The only values instantiated: key repack, early exit and orientation travel together, the table is on top of them
 ANSFM_HD constexpr bool merge_opt_valid(int opt) { return opt == 0 || (opt & ~kOptTable) == (kOptBfi | kOptExit | kOptOrient); }
 // Rows of doubles per wave: a[G], b[G] and the sentinel column b[G]; with kOptOrient also a[G] = "huge", the sentinel column of a
@@ -65,6 +71,76 @@ constexpr int kMergeOrderMinList = 16;
 // the shortest list whose kernels carry the walk of a list merge's separable top rows (MergePlan::suffix; a compile-time choice of
 // k_ck_overlap by its list length, no bit of flags): measured at C2, G = 10 loses with every kSuffixMinRows (+0.02 ms of 0.98)
 constexpr int kSuffixMinList = 16;
+// the shortest list whose kernels carry the static schedule of a whole walk and the reciprocal table (MergePlan::static_tables;
+// a compile-time choice as kSuffixMinList is: at G = 10 every fixed cost per merge has lost so far)
+constexpr int kStaticMinList = 16;
+// LDS of the static tables behind the weight table: (reciprocal, width) of every bin, the two factors of every crossing, and
+// the crossing columns of every row as a bit mask
+constexpr size_t kMergeStaticLds = (size_t)kMaxG * 16 + (size_t)kMaxG * 16 + (size_t)kMaxG * 4;
+
+// g_ord = [0, cumsum(del_g)], g_ord[ng] = 1 (ForwardModel_0.py:6141-6143); float32 cumsum when DELG is.  G + 2 entries
+inline void merge_g_ord(const double *del_g, int G, bool delg_f32, double *g_ord)
+{
+    double acc = 0.0;
+    float accf = 0.0f;
+    g_ord[0] = 0.0;
+    for (int g = 0; g < G; ++g) {
+        if (delg_f32) { accf += (float)del_g[g]; g_ord[g + 1] = (double)accf; }
+        else { acc += del_g[g]; g_ord[g + 1] = acc; }
+    }
+    g_ord[G] = 1.0;
+    g_ord[G + 1] = __builtin_nan("");           // never crossed: merge_walk compares with an ordered >=
+}
+
+// ---- the static schedule of a whole row-major walk (merge_rowmajor_static) ---------------------------------------------------
+// A wave that walks a whole merge row by row meets the weights WT[i][j] in row-major order whatever its lanes hold (WT is
+// symmetric, so neither does the lanes' orientation matter): the cumulative weight gd of merge_walk_nodiv, the verdict
+// gdn >= gnext of every element, the two factors of a crossing and the bin it closes are functions of del_g and g_ord alone.
+// They are formed here, once per launch, by the walk's own recurrence in the walk's own operations (IEEE adds, subtractions and
+// ordered compares of doubles; the one multiplication is the float32 product the kernel's WT prologue forms), so the kernel
+// takes them as constants and the sums it forms are the ones merge_walk_nodiv forms, bit for bit.
+struct MergeStatic {
+    unsigned rowmask[kMaxG];        // bit j of rowmask[i]: element (i, j) closes a bin
+    double c1[kMaxG], c2[kMaxG];    // crossing n, in walk order, closes bin n: gnext - gd and gdn - gnext
+    double gd_end, last_width;      // the final gd, and gd - g_ord[G - 1]: the divisor of the open last bin
+    int nbins;                      // bins closed
+    int valid;                      // the schedule may replace the walk
+};
+// g_ord: G + 2 entries as merge_params forms them, g_ord[G + 1] = NaN.  Valid means: every float32 factor and product is zero or
+// a normal number (what the host and the device round alike whatever their denormal modes), and bin b closes in row b or later --
+// then row b's entry of the rows operand has been read when the closed sum takes its slot.  The arrays are
+// filled either way; NaN weights cross nothing (the compare is ordered) and leave the schedule invalid.
+inline void merge_static_build(const double *del_g, const double *g_ord, int G, MergeStatic &s)
+{
+    memset(&s, 0, sizeof s);
+    if (G < 2 || G > kMaxG) return;
+    const auto plain = [](float v) { const float m = v < 0.0f ? -v : v; return v == 0.0f || (m >= FLT_MIN && m <= FLT_MAX); };
+    bool ok = true;
+    double gd = 0.0;
+    int ig = 0;
+    for (int i = 0; i < G; ++i) {
+        for (int j = 0; j < G; ++j) {
+            const float fi = (float)del_g[i], fj = (float)del_g[j];
+            const float wf = fi * fj;
+            ok = ok && plain(fi) && plain(fj) && plain(wf);
+            const double w = (double)wf;
+            const double gdn = gd + w;
+            // an element closes at most one bin; ordered: g_ord[G + 1] is NaN (the guard keeps a caller's table without it in range)
+            if (ig < G && gdn >= g_ord[ig + 1]) {
+                ok = ok && ig <= i;
+                s.rowmask[i] |= 1u << j;
+                s.c1[ig] = g_ord[ig + 1] - gd;
+                s.c2[ig] = gdn - g_ord[ig + 1];
+                ++ig;
+            }
+            gd = gdn;
+        }
+    }
+    s.nbins = ig;
+    s.gd_end = gd;
+    s.last_width = gd - g_ord[G - 1];
+    s.valid = ok ? 1 : 0;
+}
 // f(std::integral_constant<int, D>) at D = merge_list_len(G): how a launcher names the instantiation for a run-time G
 template <class F>
 auto by_list_len(int G, F &&f)
@@ -102,6 +178,7 @@ struct MergeSwitches {
     bool layout_wave = false;       // ANSFM_TABLE_LAYOUT=wave: read lnK although a g-fastest copy exists
     bool order_off = false;         // ANSFM_MERGE_ORDER=0: a block's wavenumbers in their own order, no pattern bytes written
     bool suffix_off = false;        // ANSFM_MERGE_SUFFIX=0: no walk of the separable top rows behind a list phase
+    bool static_off = false;        // ANSFM_MERGE_STATIC=0: a whole walk steps per lane although the launch has a static schedule
 };
 // read per launch: a caller may change the environment between two calls
 inline MergeSwitches merge_switches_from_env()
@@ -120,6 +197,7 @@ inline MergeSwitches merge_switches_from_env()
     sw.layout_wave = is("ANSFM_TABLE_LAYOUT", "wave");
     sw.order_off = starts("ANSFM_MERGE_ORDER", '0');
     sw.suffix_off = starts("ANSFM_MERGE_SUFFIX", '0');
+    sw.static_off = starts("ANSFM_MERGE_STATIC", '0');
     return sw;
 }
 
@@ -139,6 +217,7 @@ struct MergeCall {
     bool gfast_copy = false;
     int table_W = 0, table_Wpad = 0, table_G = 0, table_S = 0;
     size_t lds32 = 0;           // dynamic LDS of k_ck_overlap32 at this G and weight type (overlap32_lds_bytes)
+    bool static_valid = false;  // merge_static_build found a valid schedule for the call's del_g
 };
 
 struct MergePlan {
@@ -150,6 +229,9 @@ struct MergePlan {
     bool lane_rows = false, rowmajor = false, gfast = false;
     // a list merge walks its separable top rows (part of the walk: off with it, and with ANSFM_MERGE_SUFFIX=0, kFlagSuffixOff)
     bool suffix = false;
+    // the block holds the static tables (kMergeStaticLds: a valid schedule, a table kernel of a list from kStaticMinList entries) and
+    // normalises by the reciprocal table; and its whole walks run on the schedule (off with the walk and with ANSFM_MERGE_STATIC=0)
+    bool static_tables = false, static_walk = false;
     int lane_nv = 0, flags = 0;
     // the launch hands a block's wavenumbers out in the order of their last walk patterns and writes this launch's patterns
     // (OverlapParams::hint_in / hint_out, which the launcher sets for such a plan only; no bit of flags or trims)
@@ -191,7 +273,8 @@ inline MergePlan merge_plan(const MergeCall &c, const MergeSwitches &sw)
     if (table) {
         // one block per CU: the tables once, then as many waves' rows as the CU's 160 KiB hold (7 at G = 20); no more blocks
         // than the tiles need
-        const size_t shared_bytes = kMergeLdsTables + weight_table_bytes(c.G);
+        m.static_tables = c.static_valid && merge_list_len(c.G) >= kStaticMinList;
+        const size_t shared_bytes = kMergeLdsTables + weight_table_bytes(c.G) + (m.static_tables ? kMergeStaticLds : 0);
         const int fit = (int)((kCuLdsBytes - shared_bytes) / wave_bytes);
         m.nwaves = fit < max_per_cu ? fit : max_per_cu;
         m.lds = shared_bytes + (size_t)m.nwaves * wave_bytes;
@@ -221,8 +304,10 @@ inline MergePlan merge_plan(const MergeCall &c, const MergeSwitches &sw)
     // (measured at C2: G = 16 -2.3 %, G = 20 -3.0 %, but G = 10 +1.4 % with the order against the same kernel without it)
     m.order = m.rowmajor && m.lane_rows && m.lane_nv == 1 && merge_list_len(c.G) >= kMergeOrderMinList && !sw.order_off;
     m.suffix = m.rowmajor && !sw.suffix_off && merge_list_len(c.G) >= kSuffixMinList;
+    m.static_walk = m.static_tables && m.rowmajor && !sw.static_off;
     m.flags = (m.lane_rows ? kFlagLaneRows : 0) | (m.rowmajor ? kFlagRowMajor : 0) | (m.gfast ? kFlagTableGfast : 0) |
-              (m.rowmajor && sw.suffix_off ? kFlagSuffixOff : 0);
+              (m.rowmajor && sw.suffix_off ? kFlagSuffixOff : 0) | (m.static_tables ? kFlagStatic : 0) |
+              (m.static_tables && !m.static_walk ? kFlagStaticOff : 0);
     m.trims = m.opt | (m.lane_rows ? kOptLaneRows : 0) | (m.rowmajor ? kOptRowMajor : 0);
     m.group_width = m.lane_rows ? m.lane_nv : 0;
     return m;

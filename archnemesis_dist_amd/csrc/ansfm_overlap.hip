@@ -20,16 +20,7 @@ void merge_params(ansfm_ctx *ctx, OverlapParams &p, const double *kin, int W, in
     p.tile_counter = reinterpret_cast<unsigned int *>(ctx->d_flag.as<int>() + kFlagTileCounter);
     p.W = W; p.Wpad = Wpad; p.G = G; p.NT = ctx->NT; p.S = S; p.L = L; p.n_models = n_models;
     p.delg_f32 = ctx->delg_f32;
-    // g_ord = [0, cumsum(del_g)], g_ord[ng] = 1 (ForwardModel_0.py:6141-6143); float32 cumsum when DELG is
-    double acc = 0.0;
-    float accf = 0.0f;
-    p.g_ord[0] = 0.0;
-    for (int g = 0; g < G; ++g) {
-        if (ctx->delg_f32) { accf += (float)del_g_host[g]; p.g_ord[g + 1] = (double)accf; }
-        else { acc += del_g_host[g]; p.g_ord[g + 1] = acc; }
-    }
-    p.g_ord[G] = 1.0;
-    p.g_ord[G + 1] = __builtin_nan("");        // never crossed: merge_walk compares with an ordered >=
+    merge_g_ord(del_g_host, G, ctx->delg_f32 != 0, p.g_ord);
 }
 
 int merge_launch_begin(ansfm_ctx *ctx, const OverlapParams &p, long grid, std::initializer_list<MergeWorkspace> workspaces)
@@ -86,6 +77,9 @@ int launch_overlap(ansfm_ctx *ctx, bool from_k, const double *kin, int W, int Wp
     c.gfast_copy = ctx->lnKg_bytes != 0 && !ctx->is_lbl;
     c.table_W = ctx->W; c.table_Wpad = ctx->Wpad; c.table_G = ctx->G; c.table_S = ctx->S;
     c.lds32 = overlap32_lds_bytes(G, w32);
+    // the schedule of a whole walk from the launch's own g_ord; the table kernels alone read it (float32 weights)
+    if (w32) merge_static_build(del_g_host, p.g_ord, G, p.st);
+    c.static_valid = p.st.valid != 0;
     const MergePlan m = merge_plan(c, merge_switches_from_env());
 
     const int rc = merge_launch_begin(ctx, p, m.grid, {{&ctx->scratch, m.scratch_bytes_per_block}});

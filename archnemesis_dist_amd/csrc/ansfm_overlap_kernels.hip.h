@@ -57,6 +57,11 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
     // the table kernels of the lists from kSuffixMinList entries carry the partial form of the walk (merge_suffix_row); the shorter
     // ones take a merge whole or not at all, with the test and the code they had
     constexpr bool kSuffix = kTable && NR >= kSuffixMinList;
+    // the table kernels of the lists from kStaticMinList entries carry the static schedule of a whole walk and the reciprocal table
+    // (flags bit kFlagStatic: the launch has a valid schedule and the block its tables; kFlagStaticOff: the walk steps per lane)
+    constexpr bool kStatic = kTable && NR >= kStaticMinList;
+    const bool st_tables = kStatic && (flags & kFlagStatic) != 0;
+    const bool st_walk = kStatic && (flags & (kFlagStatic | kFlagStaticOff)) == kFlagStatic;
     // flags: the row mapping (kFlagLaneRows) and, with kOptTable only, the list-free walk of row-major merges (kFlagRowMajor) and
     // "no walk of the top rows of a list merge" (kFlagSuffixOff);
     // the instantiations without the table are launched with 0 or 1 and test the word as they always did
@@ -68,6 +73,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
     const unsigned nvs = lane_nv == 1 ? 0u : kLaneNVShift;
     unsigned n_rowmajor = 0, n_merged = 0;              // kOptTable: the merges of this wave that took the walk / all of them
     unsigned n_suffix = 0;                              // kOptTable: the rows this wave walked behind a list phase
+    unsigned n_static = 0;                              // kStatic: the merges of this wave walked on the static schedule
     // kOptTable: the launch orders a block's wavenumbers by the launch before's pattern bytes and writes its own (MergePlan::order)
     const bool ordered = kTable && p.hint_in != nullptr;
     unsigned n_hints = 0;                               // the non-zero pattern bytes this wave read for the blocks whose tile 0 it ran
@@ -91,6 +97,12 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             WT[idx] = w;
         }
         A = WT + (G + 1) * 32 + (size_t)wv * merge_wave_rows(G, OPT) * kWave;
+        if constexpr (kStatic) {
+            if (st_tables) {
+                A += kMergeStaticLds / sizeof(double);
+                if (wv == 0) merge_static_fill(p, G, lane);
+            }
+        }
     }
     double *B = A + (kOrient ? G + 1 : G) * kWave;   // G+1 rows
     unsigned char *PA = reinterpret_cast<unsigned char *>(B + (G + 1) * kWave);   // SORTED = false only
@@ -155,6 +167,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             else { keepA = (blast <= 0.0); takeB = !keepA && (alast <= 0.0); }
             const bool do_merge = !(takeB | keepA);
             bool walked = false;                        // kOptTable: the merge was walked row by row (wave-uniform where set)
+            bool walked_static = false;                 // kStatic: ... and on the static schedule
             int walked_rows = 0;                        // kOptTable: its rows walked behind a list phase (the same in every merging lane)
             if (takeB) {
                 for (int g = 0; g < G; ++g) A[g * kWave + lane] = B[g * kWave + lane];
@@ -226,10 +239,42 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                 if constexpr (kTable) {
                     // the one call of the walk: the whole merge, or the rows behind a list phase, on the same walk state
                     if (i0 < G) {
-                        if (i0 == 0) ws = walk_begin(GORD, lane);
-                        merge_rowmajor<NR>(i0, G, mo, ws, rec);
+                        if constexpr (kStatic) walked_static = i0 == 0 && st_walk;
+                        if (!walked_static) {
+                            if (i0 == 0) ws = walk_begin(GORD, lane);
+                            merge_rowmajor<NR>(i0, G, mo, ws, rec);
+                        }
                     }
                 }
+                if constexpr (kStatic) {
+                if (walked_static) {
+                    // ---- the whole walk on the schedule: closed sums into A's slots, divided in place; the open bin as below ----
+                    const unsigned a_lane = lds_addr(A + lane), sb = merge_static_base(G);
+                    const double kacc = merge_rowmajor_static<NR>(G, mo, a_lane);
+                    const int ig = p.st.nbins;
+                    for (int g0 = 0; g0 < G; g0 += kLoadBatch) {
+                        double r[kLoadBatch];
+                        dbl2 rd[kLoadBatch];
+#pragma unroll
+                        for (int k = 0; k < kLoadBatch; ++k) {
+                            const unsigned b = (unsigned)((g0 + k < G) ? g0 + k : G - 1);
+                            r[k] = lds_ld(a_lane + b * 512u);
+                            rd[k] = lds_ld2(sb + kStaticRD + b * 16u);
+                        }
+#pragma unroll
+                        for (int k = 0; k < kLoadBatch; ++k) {
+                            const int b = g0 + k;
+                            if (b < G) {
+                                double outv = 0.0;
+                                if (b < ig) outv = recip_div(r[k], rd[k]);
+                                else if (b == ig) outv = (b == G - 1) ? fast_div(kacc, p.st.last_width) : kacc;
+                                A[b * kWave + lane] = outv;
+                            }
+                        }
+                    }
+                }
+                }
+                if (!walked_static) {
                 if constexpr (NODIV) {
                     // ---- normalise: closed bins by their width; the open one as rank()'s trailing `if ig == ng-1` (:6171) ----
                     const int ig = walk_bins(ws, GORD);
@@ -243,7 +288,11 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                             const int b = g0 + k;
                             if (b < G) {
                                 double outv = 0.0;
-                                if (b < ig) outv = fast_div(r[k], GORD[b + 1] - GORD[b]);
+                                if (b < ig) {
+                                    // the width's reciprocal once per block where the launch carries the table: the same quotient
+                                    if (st_tables) outv = recip_div(r[k], lds_ld2(merge_static_base(G) + kStaticRD + (unsigned)b * 16u));
+                                    else outv = fast_div(r[k], GORD[b + 1] - GORD[b]);
+                                }
                                 else if (b == ig) outv = (b == G - 1) ? fast_div(ws.kacc, ws.gd - GORD[G - 1]) : ws.kacc;
                                 A[b * kWave + lane] = outv;
                             }
@@ -308,6 +357,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
                         if (g0 + k < G) A[(g0 + k) * kWave + lane] = r[k];
                 }
                 }
+                }
                 if constexpr (!SORTED) {   // the merged spectrum is ascending with the plain del_g weights
                     for (int g = 0; g < G; ++g) PA[g * kWave + lane] = (unsigned char)g;
                     alast = A[(G - 1) * kWave + lane];
@@ -316,6 +366,7 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
             if constexpr (kTable) {
                 n_merged += __builtin_amdgcn_ballot_w64(do_merge) != 0 ? 1u : 0u;
                 n_rowmajor += __builtin_amdgcn_ballot_w64(walked) != 0 ? 1u : 0u;
+                if constexpr (kStatic) n_static += __builtin_amdgcn_ballot_w64(walked_static) != 0 ? 1u : 0u;
                 // (counted here, where every lane is active: lane 0, which adds the totals up, need not have merged)
                 const unsigned long long some = __builtin_amdgcn_ballot_w64(walked_rows != 0);
                 if (some != 0) n_suffix += (unsigned)__builtin_amdgcn_readlane(walked_rows, __builtin_ctzll(some));
@@ -343,13 +394,14 @@ void k_ck_overlap(OverlapParams p, int flags, int lane_nv)
         }
     }
     if constexpr (kTable) {
-        // the launch's four totals follow the tile counters (merge_params) and are cleared with them; added once per wave
+        // the launch's five totals follow the tile counters (merge_params) and are cleared with them; added once per wave
         unsigned long long *cnt = reinterpret_cast<unsigned long long *>(p.tile_counter + 8);
         if (lane == 0) {
             atomicAdd(cnt, (unsigned long long)n_rowmajor);
             atomicAdd(cnt + 1, (unsigned long long)n_merged);
             if (ordered) atomicAdd(cnt + 2, (unsigned long long)n_hints);
             if (n_suffix != 0) atomicAdd(cnt + 3, (unsigned long long)n_suffix);
+            if (n_static != 0) atomicAdd(cnt + 4, (unsigned long long)n_static);
         }
     }
 }

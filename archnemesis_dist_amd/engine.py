@@ -327,6 +327,15 @@ class AnsfmEngine:
         self._check(self._lib.ansfm_last_merge_suffix(self._ctx, C.byref(r), C.byref(t)), "last_merge_suffix")
         return int(r.value), int(t.value)
 
+    def last_merge_static(self):
+        """(merges walked on the static schedule, valid) of the last forward merge launch, counted per wave as
+        last_merge_rowmajor counts: a merge that is walked whole closes its bins where del_g alone says, so a launch with
+        float32 weights and G > 10 takes the crossings from a schedule formed on the host (same bits; off with
+        ANSFM_MERGE_STATIC=0 and with the walk).  valid: the launch carried a valid schedule."""
+        m, v = C.c_int64(), C.c_int()
+        self._check(self._lib.ansfm_last_merge_static(self._ctx, C.byref(m), C.byref(v)), "last_merge_static")
+        return int(m.value), bool(v.value)
+
     def last_merge_order(self):
         """(applied, non-zero bytes) of the last forward merge launch: applied when it handed the wavenumbers of a block out in
         the order of the pattern bytes that the launch before wrote (the same table upload or the seam, W, rows, S and G; the

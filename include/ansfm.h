@@ -97,6 +97,13 @@ int ansfm_last_merge_rowmajor(const ansfm_ctx *ctx, int64_t *merges, int64_t *me
  * rows_of_list_merges: G times the pairs that ansfm_last_merge_rowmajor does not count as walked.  Both 0 for a kernel
  * without bit 1.  Copies the totals from the device (synchronises). */
 int ansfm_last_merge_suffix(const ansfm_ctx *ctx, int64_t *rows, int64_t *rows_of_list_merges);
+/* A merge that is walked whole meets the same weights in the same order in every lane, so where its bins close is known from
+ * del_g alone: such a launch (float32 weights, G > 10) takes the crossings from a schedule formed once on the host and keeps the
+ * closed bins on chip (results are the same bit for bit; ANSFM_MERGE_STATIC=0 at the call keeps the per-lane step).
+ * merges: the (wave, merge) pairs of the last forward merge launch walked on the schedule, counted as ansfm_last_merge_rowmajor
+ * counts; valid: 1 when the launch carried a valid schedule (0: del_g gave none, or a kernel that does not carry the form).
+ * Copies the total from the device (synchronises). */
+int ansfm_last_merge_static(const ansfm_ctx *ctx, int64_t *merges, int *valid);
 /* The wavenumbers a wave of the last forward merge launch held with bit 32: 1 (64 rows of one wavenumber, the library's choice)
  * or 2 (2 wavenumbers x 32 rows, ANSFM_MERGE_LANES=pairs); 0 without bit 32 (64 wavenumbers of one row).  Reads the context only. */
 int ansfm_last_merge_group_width(const ansfm_ctx *ctx, int *width);
