@@ -1317,24 +1317,25 @@ int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models,
 // The single-scattering batch with the continuum, the scattering opacity and the layer-mean phase functions formed per distinct
 // layer from the resident sources (k_ss_cont_rows) and read by row (the SS == 2 builds of k_thermal_rt): the stages of
 // cirsrad_ck_singlescatt_impl, one row map for gas opacities and continuum
-int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
-                                            const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
-                                            const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
-                                            const double *lay_cont, int ray_mode, const double *f4, int ncont, const double *phase_fn,
-                                            int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
-                                            const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
-                                            const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
-                                            double *SPECOUT)
+// phase_fn [W][P][ncont + 1] from the host, or alpha_deg [P]: formed in its buffer from the resident phase-function source
+// (ansfm_cirsrad_ck_singlescatt_batch_src); what = the entry's name
+static int cirsrad_ck_singlescatt_cont_impl(ansfm_ctx *ctx, const char *what, int ISPACE, int n_models, int L,
+                                            const double *lay_press_pa, const double *lay_temp, const double *amount, int use_cia,
+                                            const double *lay_q, const double *lay_frac, const double *lay_totam, const double *lay_delh,
+                                            int use_dust, const double *lay_cont, int ray_mode, const double *f4, int ncont,
+                                            const double *phase_fn, const double *alpha_deg, int P, int LIMAX, const int32_t *NLAYIN,
+                                            const int32_t *LAYINC, const double *SCALE, const double *EMTEMP, const double *TSURF,
+                                            const double *EMISSIVITY, const double *BRDF, const double *SOLFLUX, const double *SOL_ANG,
+                                            const double *EMISS_ANG, const double *xfac, double *SPECOUT)
 {
-    CHECK_CTX(ctx);
-    const std::string fn = "cirsrad_ck_singlescatt_batch_cont: ";
+    const std::string fn = std::string(what) + ": ";
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
     bool bad = n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN || !LAYINC || !SCALE ||
                !EMTEMP || !TSURF || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT || (ISPACE != 0 && ISPACE != 1);
     for (int m = 0; !bad && m < n_models; ++m) bad = TSURF[m] > 0.0 && !EMISSIVITY;
     if (bad) FAIL(ANSFM_ERR_INVALID, fn + "bad argument");
     if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
-        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont) || !phase_fn)
+        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont) || (!phase_fn && !alpha_deg))
         FAIL(ANSFM_ERR_INVALID, fn + "bad argument (ray_mode = IRAY 0, 1, 2, 4 or 12; the per-layer arrays of every term that is used; phase_fn)");
     if (!use_dust && !ray_mode) FAIL(ANSFM_ERR_INVALID, fn + "neither aerosols nor Rayleigh scattering: no scattering opacity");
     if (use_cia && !ctx->cia_on) FAIL(ANSFM_ERR_INVALID, fn + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
@@ -1345,6 +1346,8 @@ int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_mo
         FAIL(ANSFM_ERR_INVALID, fn + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
                                     std::to_string(use_dust ? ctx->dust_n : 0) + " populations");
     if ((size_t)n_models * P > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "at most 65535 (model, path) pairs per call");
+    int rc;
+    if (alpha_deg && ((rc = phase_source_check(ctx, fn, ncont)) || (rc = phase_source_angles(ctx, fn, P, alpha_deg)))) return rc;
     for (int ip = 0; ip < P; ++ip) {                                 // the RT kernel indexes the layers with these
         if (NLAYIN[ip] < 1 || NLAYIN[ip] > LIMAX) FAIL(ANSFM_ERR_INVALID, fn + "NLAYIN outside 1 .. LIMAX");
         for (int j = 0; j < NLAYIN[ip]; ++j)
@@ -1361,11 +1364,15 @@ int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_mo
     h.EMISSIVITY = EMISSIVITY; h.BRDF = BRDF; h.SOLFLUX = SOLFLUX; h.SOL_ANG = SOL_ANG; h.EMISS_ANG = EMISS_ANG; h.xfac = xfac;
     h.SPECOUT = SPECOUT; h.rt_mode = 2;
     const int W = ctx->W;
-    int rc;
     RtCall d = stage_call(ctx, h, &rc);
     if (rc) return rc;
     const void *pf_dev = nullptr;
-    if ((rc = h2d(ctx, ctx->ss_phase_fn, phase_fn, (size_t)W * P * (ncont + 1) * sizeof(double), &pf_dev))) return rc;
+    if (alpha_deg) {                                            // phase_fn stays in HBM
+        HIPCHK(ctx->ss_phase_fn.reserve((size_t)W * P * (ncont + 1) * sizeof(double)));
+        if ((rc = launch_phase_source(ctx, P, alpha_deg, nullptr, 1, ctx->ss_phase_fn.as<double>()))) return rc;
+        pf_dev = ctx->ss_phase_fn.p;
+    } else if ((rc = h2d(ctx, ctx->ss_phase_fn, phase_fn, (size_t)W * P * (ncont + 1) * sizeof(double), &pf_dev)))
+        return rc;
     if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     ContCall k;
     k.ISPACE = ISPACE; k.use_cia = d.use_cia; k.use_dust = d.use_dust; k.ray_mode = ray_mode;
@@ -1404,6 +1411,41 @@ int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_mo
     HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return ANSFM_OK;
+}
+
+int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                            const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                            const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                            const double *lay_cont, int ray_mode, const double *f4, int ncont, const double *phase_fn,
+                                            int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                            const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
+                                            const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                            double *SPECOUT)
+{
+    CHECK_CTX(ctx);
+    return cirsrad_ck_singlescatt_cont_impl(ctx, "cirsrad_ck_singlescatt_batch_cont", ISPACE, n_models, L, lay_press_pa, lay_temp, amount,
+                                            use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4, ncont,
+                                            phase_fn, nullptr, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX,
+                                            SOL_ANG, EMISS_ANG, xfac, SPECOUT);
+}
+
+// The same with phase_fn formed on the device: the populations from the resident phase-function source (ansfm_upload_phase) at
+// each path's scattering angle, Rayleigh scattering behind them (k_phase_fn)
+int ansfm_cirsrad_ck_singlescatt_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                           const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                           const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                           const double *lay_cont, int ray_mode, const double *f4, int ncont, const double *alpha_deg,
+                                           int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                           const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
+                                           const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                           double *SPECOUT)
+{
+    CHECK_CTX(ctx);
+    if (!alpha_deg) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_singlescatt_batch_src: bad argument (alpha_deg)");
+    return cirsrad_ck_singlescatt_cont_impl(ctx, "cirsrad_ck_singlescatt_batch_src", ISPACE, n_models, L, lay_press_pa, lay_temp, amount,
+                                            use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4, ncont,
+                                            nullptr, alpha_deg, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX,
+                                            SOL_ANG, EMISS_ANG, xfac, SPECOUT);
 }
 
 int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR, int NLAYIN, const double *WAVE,

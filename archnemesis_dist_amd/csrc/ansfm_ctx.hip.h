@@ -12,6 +12,7 @@
 //   ansfm_ops.hip      gradient maps, ILS convolution, continua, layering, the k-distribution entry
 //   ansfm_mie.hip      Mie theory over size distributions
 //   ansfm_hgfit.hip    double Henyey-Greenstein fit of phase functions
+//   ansfm_phase.hip    aerosol phase functions on the calculation grid (calc_phase, calc_phase_ray) and their resident source
 //   ansfm_surface.hip  surface reflection: the BRDF at points and the BRDF matrix
 //   ansfm_transit.hip, ansfm_occultation.hip, ansfm_limb.hip, ansfm_disc.hip  the fused gradient routes, collapsed over the
 //                      paths (transit), with the tangent paths mixed to the geometries (occultation, limb) or with the averaging
@@ -164,6 +165,7 @@ struct ansfm_ctx {
     DevBuf gscratch, perm, dkbuf, trold_ws, dspec_i, dcont_t, tmp_in2, tmp_out2, lbl_li;
     DevBuf ms_taus, ms_omegas, ms_bnu;   // scattering branch of CIRSrad: TAUTOT / OMEGA (W,G,L) and BB (W,L) in HBM
     DevBuf ms_cont_rows;                 // ansfm_cirsrad_ck_scatter_batch_cont: the rows k_ms_cont_rows forms, TAUCIA / TAUDUST / TAURAY / TAUSCAT [R][W] and the fractions [R][ncont][W]
+    DevBuf ms_phas_src;                  // ansfm_cirsrad_ck_scatter_batch_src: phasarr [ncont][W][2][nth] formed from the phase-function source
     DevBuf ss_cont_rows, ss_phase_fn;    // ansfm_cirsrad_ck_singlescatt_batch_cont: the rows k_ss_cont_rows forms, sca [R][Wpad] and phase [P][R][Wpad]; phase_fn [W][P][ncont + 1]
     DevBuf ms_tauray_l, ms_lfrac_l;      // the continuum by rows: TAURAY / aerosol fractions of a launch's models (the model-by-model route: one model's dense arrays)
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
@@ -196,6 +198,16 @@ struct ansfm_ctx {
     // flags; kernel time of the last call
     DevBuf hg_st;
     double hg_ms = 0;
+    // aerosol phase functions.  phase_src: the resident source on the table's grid (ansfm_upload_phase; a new table clears it) --
+    //   Scatter.WAVE [NWS], Scatter.THETA [NTAB] (IMIE 1), the tables, x_lo / x_hi [W] of every wavenumber's interval, f_w / g1_w /
+    //   g2_w [3][NDUST][Wpad] (IMIE 0), lo [W] (int32); phase_h_theta: Scatter.THETA on the host, for the angle check.
+    // phase_ws: the angles of a launch from the source (theta, mu, cos theta, brackets); phase_call: the staged inputs and the
+    //   result of an array-level call; kernel time of the last such call
+    DevBuf phase_src, phase_ws, phase_call;
+    int phase_n = 0;                        // NDUST of the uploaded phase-function source, 0: none
+    int phase_imie = 0, phase_NWS = 0, phase_NTAB = 0;
+    std::vector<double> phase_h_theta;
+    double phase_ms = 0;
     // surface reflection (ansfm_surface_brdf, ansfm_brdf_matrix): the result, the per-azimuth table, kernel time of the last call
     DevBuf brdf_out, brdf_azi;
     double brdf_ms = 0;
@@ -261,8 +273,9 @@ struct DedupRows {
 struct DedupCols;
 int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
                const DedupCols *cols, DedupRows *out);
-// a table has been uploaded: the continuum sources on the old grid go (dust_n = 0: kext_w and ksca_w alike)
-inline void clear_continuum_sources(ansfm_ctx *ctx) { ctx->cia_on = 0; ctx->dust_n = 0; }
+// a table has been uploaded: the continuum sources on the old grid go (dust_n = 0: kext_w and ksca_w alike), and the
+// phase-function source with them
+inline void clear_continuum_sources(ansfm_ctx *ctx) { ctx->cia_on = 0; ctx->dust_n = 0; ctx->phase_n = 0; }
 // a continuum formed from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust) and the Rayleigh
 // parametrisations: the arrays are device pointers over the n * L layers of the call
 struct ContCall {
@@ -305,6 +318,15 @@ int launch_ss_cont_rows(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, cons
 // layers from the resident sources.  After launch_tau_cont_rows(ctx, n * L, nullptr, c) on the same stream: the CIA records in
 // ctx->cia_lay are that launch's.
 int launch_dtau_cont_rows(ansfm_ctx *ctx, int n_models, int L, int NVMR, int NPAR, const ContCall &c);
+
+// ansfm_phase.hip, for the fused scattering entries.  phase_source_check: ANSFM_ERR_INVALID unless a phase-function source of
+// ncont populations stands; phase_source_angles: the host's checks of the angles of a launch (IMIE 1: inside Scatter.THETA).
+// launch_phase_source: k_phase_fn on the source at theta_deg [nth] (host), on ctx->stream, into out on the device --
+// mu_theta = nullptr: [W][nth][NDUST + ray], ray != 0 with calc_phase_ray behind the populations (phase_fn of the
+// single-scattering batch); mu_theta [nth] (host): phasarr [NDUST][W][2][nth] of the scattering entries
+int phase_source_check(ansfm_ctx *ctx, const std::string &fn, int ncont);
+int phase_source_angles(ansfm_ctx *ctx, const std::string &fn, int nth, const double *theta_deg);
+int launch_phase_source(ansfm_ctx *ctx, int nth, const double *theta_deg, const double *mu_theta, int ray, double *out);
 
 // ansfm_overlap.hip / ansfm_overlapg.hip: k_ck_overlap (or k_ck_overlap32) and k_ck_overlapg over n_models x L layers into tau
 // (and dk); from_k: the array-level seams' k (and dkdT) instead of the table; generic: per-lane sort first (rerun of an unsorted call)

@@ -57,6 +57,9 @@ struct MsCall {
     // (ansfm_cirsrad_ck_scatter_batch_cont): the per-layer arrays [n][L] / [n][L][NVMR | ncont | 4] behind it, host pointers;
     // taucia .. tauscat, lfrac and cont_row are null
     int fused, use_cia, use_dust, ray_mode; const double *lay_q, *lay_frac, *lay_totam, *lay_delh, *lay_cont, *f4;
+    // phasarr formed on the device from the resident phase-function source (ansfm_cirsrad_ck_scatter_batch_src): Scatter.THETA
+    // in degrees and its cosines [nth], host pointers; phasarr is null
+    const double *theta_deg, *mu_theta;
 };
 
 // one model's continuum already on the device, [W][L] / [W][ncont][L] (null = zeros): cirsrad_ck_scatter_impl stages none then
@@ -67,7 +70,7 @@ static int ms_check(ansfm_ctx *ctx, const MsCall &c, const char *fn)
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, std::string(fn) + ": upload a k-table first");
     if (c.n_models <= 0 || c.L <= 0 || !c.lay_press_pa || !c.lay_temp || !c.amount || c.ncont < 0 || c.ngeom <= 0 || c.nmu < 2 ||
         c.nf < 0 || c.nphi <= 0 || !c.radg || !c.sol_angs || !c.emiss_angs || !c.aphis || !c.solar || !c.brdf_matrix || !c.mu1 ||
-        !c.wt1 || !c.SPECOUT || (c.ISPACE != 0 && c.ISPACE != 1) || (c.ncont > 0 && (!c.phasarr || (!c.lfrac && !c.fused) || c.nth < 3)))
+        !c.wt1 || !c.SPECOUT || (c.ISPACE != 0 && c.ISPACE != 1) || (c.ncont > 0 && ((!c.phasarr && !c.theta_deg) || (!c.lfrac && !c.fused) || c.nth < 3)))
         FAIL(ANSFM_ERR_INVALID, std::string(fn) + ": bad argument");
     return ANSFM_OK;
 }
@@ -460,6 +463,11 @@ static int ms_stage(ansfm_ctx *ctx, const MsCall &c, size_t CN, MsStaged &s)
     s.rg = st.up(c.radg, c.n_models * W * c.nmu); s.sol = st.up(c.solar, W);
     s.brdf = st.up(c.brdf_matrix, W * c.nmu * c.nmu * (c.nf + 1)); s.xf = st.up(c.xfac, W);
     s.d_crow = st.up(c.cont_row, CN ? nl : 0);
+    if (st.rc == ANSFM_OK && c.theta_deg && c.ncont > 0) {       // phasarr stays in HBM
+        HIPCHK(ctx->ms_phas_src.reserve((size_t)c.ncont * W * 2 * c.nth * sizeof(double)));
+        s.phas = ctx->ms_phas_src.as<double>();
+        return launch_phase_source(ctx, c.nth, c.theta_deg, c.mu_theta, 0, ctx->ms_phas_src.as<double>());
+    }
     return st.rc;
 }
 
@@ -990,6 +998,48 @@ int ansfm_cirsrad_ck_scatter_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models
     c.fused = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0; c.ray_mode = ray_mode;
     c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_totam = lay_totam; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
     c.f4 = ray_mode == 4 ? f4 : nullptr;
+    return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
+}
+
+int ansfm_cirsrad_ck_scatter_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                       const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                       const double *lay_cont, int ray_mode, const double *f4, int ncont, int nth,
+                                       const double *theta_deg, const double *mu_theta, const double *radg, int ngeom,
+                                       const double *sol_angs, const double *emiss_angs, const double *aphis, const double *solar,
+                                       int lowbc, const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf,
+                                       int nphi, int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
+{
+    CHECK_CTX(ctx);
+    const std::string fn = "cirsrad_ck_scatter_batch_src: ";
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
+    if (W_full != ctx->W || w_begin != 0)
+        FAIL(ANSFM_ERR_UNSUPPORTED, fn + "the whole axis only (a slice's context does not hold the grid the source lives on)");
+    if (!theta_deg || !mu_theta || nth < 3) FAIL(ANSFM_ERR_INVALID, fn + "bad argument (theta_deg, mu_theta [nth], nth >= 3)");
+    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
+        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || !use_dust || !lay_cont)
+        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (use_dust with lay_cont; ray_mode = IRAY 0, 1, 2, 4 or 12; the per-layer arrays of "
+                                     "every term that is used)");
+    if (use_cia && !ctx->cia_on) FAIL(ANSFM_ERR_INVALID, fn + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
+    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, fn + "the CIA source was uploaded for the other ISPACE");
+    if (!ctx->dust_n) FAIL(ANSFM_ERR_INVALID, fn + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    if (ncont != ctx->dust_n)
+        FAIL(ANSFM_ERR_INVALID, fn + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
+                                    std::to_string(ctx->dust_n) + " populations");
+    int rc;
+    if ((rc = phase_source_check(ctx, fn, ncont)) || (rc = phase_source_angles(ctx, fn, nth, theta_deg))) return rc;
+    if ((imie == 0) != (ctx->phase_imie == 0))
+        FAIL(ANSFM_ERR_INVALID, fn + "imie = " + std::to_string(imie) + ", the phase-function source was uploaded with imie = " +
+                                    std::to_string(ctx->phase_imie));
+    for (int t = 1; t < nth; ++t)
+        if (!(theta_deg[t] > theta_deg[t - 1])) FAIL(ANSFM_ERR_INVALID, fn + "theta_deg (Scatter.THETA) must be strictly ascending");
+    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, nullptr, nullptr, nullptr, ncont, nth, nullptr, nullptr,
+             radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT,
+             nullptr, W_full, w_begin, 0, nullptr};
+    c.fused = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = 1; c.ray_mode = ray_mode;
+    c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_totam = lay_totam; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
+    c.f4 = ray_mode == 4 ? f4 : nullptr;
+    c.theta_deg = theta_deg; c.mu_theta = mu_theta;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 

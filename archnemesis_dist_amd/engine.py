@@ -508,7 +508,33 @@ class AnsfmEngine:
         scattering angle (ScatterX.calc_phase / calc_phase_ray).  Host arrays; the rest as `cirsrad_ck_singlescatt_batch` ->
         SPECOUT (n, NWAVE, NPATH), bit-identical to that call on the dense arrays of calc_tau_cia / calc_tau_dust /
         calc_tau_rayleigh put together as ForwardModel_0.py:3963-3989 and :4316-4321 do."""
-        what = "cirsrad_ck_singlescatt_batch_cont"
+        return self._singlescatt_cont("cirsrad_ck_singlescatt_batch_cont", ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH,
+                                      CONT, IRAY, f4, phase_fn, None, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX,
+                                      SOL_ANG, EMISS_ANG, xfac, variant)
+
+    def cirsrad_ck_singlescatt_batch_src(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, alpha_deg,
+                                         NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG, EMISS_ANG,
+                                         xfac=None, variant=None):
+        """`cirsrad_ck_singlescatt_batch_cont` with phase_fn formed on the device from the resident phase-function source
+        (upload_phase) and the Rayleigh formula (ansfm_cirsrad_ck_singlescatt_batch_src): alpha_deg (NPATH,) is each path's
+        scattering angle in degrees, `scattering_angle_deg(SOL_ANG, EMISS_ANG, AZI_ANG)`.  Bit-identical to the `_cont` call with
+        phase_fn put together from `phase_from_source(alpha_deg)` and `calc_phase_ray(alpha_deg)`."""
+        return self._singlescatt_cont("cirsrad_ck_singlescatt_batch_src", ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH,
+                                      CONT, IRAY, f4, None, alpha_deg, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX,
+                                      SOL_ANG, EMISS_ANG, xfac, variant)
+
+    @staticmethod
+    def scattering_angle_deg(SOL_ANG, EMISS_ANG, AZI_ANG):
+        """the scattering angle of each path in degrees, by the expression of ForwardModel_0.py:4265-4270"""
+        sol_ang, emiss_ang, azi_ang = (np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (SOL_ANG, EMISS_ANG, AZI_ANG))
+        calpha = np.sin(sol_ang / 180. * np.pi) * np.sin(emiss_ang / 180. * np.pi) * np.cos(azi_ang / 180. * np.pi - np.pi) - \
+            np.cos(emiss_ang / 180. * np.pi) * np.cos(sol_ang / 180. * np.pi)
+        return np.arccos(calpha) / np.pi * 180.
+
+    def _singlescatt_cont(self, what, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phase_fn, alpha_deg,
+                          NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG, EMISS_ANG, xfac, variant):
+        """the `_cont` entry (phase_fn) or the `_src` entry (alpha_deg)"""
+        src = what.endswith("_src")
         dims, _ = self.ktable_info()
         W, S = dims[0], dims[4]
         lp = _np(lay_press_pa)
@@ -536,7 +562,8 @@ class AnsfmEngine:
         arrs = {}
         for name, a, shape in (("q", q, (n, L, getattr(self, "cia_nvmr", -1))), ("FRAC", FRAC, (n, L)), ("TOTAM", TOTAM, (n, L)),
                                ("DELH", DELH, (n, L)), ("CONT", CONT, (n, L, ncont)), ("f4", f4, (n, L, 4)),
-                               ("phase_fn", phase_fn, (W, P, ncont + 1)), ("SCALE", SCALE, (n, LIMAX, P)),
+                               ("phase_fn", phase_fn, (W, P, ncont + 1)),
+                               ("alpha_deg", None if alpha_deg is None else np.atleast_1d(alpha_deg), (P,)), ("SCALE", SCALE, (n, LIMAX, P)),
                                ("EMTEMP", EMTEMP, (n, LIMAX, P)), ("BRDF", BRDF, (W, P)), ("EMISSIVITY", EMISSIVITY, (W,)),
                                ("SOLFLUX", SOLFLUX, (W,)), ("xfac", xfac, (W,)), ("SOL_ANG", None if SOL_ANG is None else np.atleast_1d(SOL_ANG), (P,)),
                                ("EMISS_ANG", None if EMISS_ANG is None else np.atleast_1d(EMISS_ANG), (P,))):
@@ -549,14 +576,14 @@ class AnsfmEngine:
             raise ValueError(f"{what}: CIA and Rayleigh need TOTAM")
         if mode == 4 and arrs["f4"] is None:
             raise ValueError(f"{what}: IRAY 4 needs f4 (rayleigh_f4)")
-        if arrs["phase_fn"] is None:
-            raise ValueError(f"{what}: phase_fn (NWAVE, NPATH, NDUST + 1) is needed")
+        if arrs["alpha_deg" if src else "phase_fn"] is None:
+            raise ValueError(f"{what}: " + ("alpha_deg (NPATH,)" if src else "phase_fn (NWAVE, NPATH, NDUST + 1)") + " is needed")
         out = np.empty((n, W, P))
-        rc = self._lib.ansfm_cirsrad_ck_singlescatt_batch_cont(
+        rc = getattr(self._lib, "ansfm_" + what)(
             self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
             _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont,
-            _ptr(arrs["phase_fn"]), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(arrs["SCALE"]), _ptr(arrs["EMTEMP"]), _ptr(TS),
-            _ptr(arrs["EMISSIVITY"]), _ptr(arrs["BRDF"]), _ptr(arrs["SOLFLUX"]), _ptr(arrs["SOL_ANG"]), _ptr(arrs["EMISS_ANG"]),
+            _ptr(arrs["alpha_deg" if src else "phase_fn"]), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(arrs["SCALE"]), _ptr(arrs["EMTEMP"]),
+            _ptr(TS), _ptr(arrs["EMISSIVITY"]), _ptr(arrs["BRDF"]), _ptr(arrs["SOLFLUX"]), _ptr(arrs["SOL_ANG"]), _ptr(arrs["EMISS_ANG"]),
             _ptr(arrs["xfac"]), _ptr(out))
         self._check(rc, what)
         return out
@@ -1181,6 +1208,26 @@ class AnsfmEngine:
         f4 (n, NLAY, 4) for IRAY 4 (`rayleigh_f4`); TOTAM (n, NLAY) for CIA and Rayleigh.  Host arrays.  The rest, wave_slice
         included, as `cirsrad_ck_scatter_batch_rows` -> SPECOUT (n, NWAVE, NPATH), bit-identical to that call on the rows of
         calc_tau_cia / calc_tau_dust / calc_tau_rayleigh."""
+        return self._scatter_cont("cirsrad_ck_scatter_batch_cont", ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT,
+                                  IRAY, f4, phasarr, None, None, radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1,
+                                  nf, nphi, iray, imie, xfac, wave_slice, variant)
+
+    def cirsrad_ck_scatter_batch_src(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, theta_deg,
+                                     radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie,
+                                     xfac=None, wave_slice=None, variant=None):
+        """`cirsrad_ck_scatter_batch_cont` with phasarr formed on the device from the resident phase-function source
+        (upload_phase; ansfm_cirsrad_ck_scatter_batch_src): theta_deg (NTHETA,) is Scatter.THETA, ascending; row 1 is
+        np.cos(theta_deg * pi / 180), formed here.  Whole axis only.  Bit-identical to the `_cont` call with
+        `phasarr_from_source(theta_deg)`."""
+        theta = _np(np.atleast_1d(theta_deg))
+        return self._scatter_cont("cirsrad_ck_scatter_batch_src", ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT,
+                                  IRAY, f4, None, theta, _np(np.cos(theta * np.pi / 180)), radg, sol_angs, emiss_angs, aphis, solar,
+                                  lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie, xfac, wave_slice, variant)
+
+    def _scatter_cont(self, what, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phasarr, theta, mu_theta,
+                      radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie, xfac, wave_slice,
+                      variant):
+        """the `_cont` entry (phasarr) or the `_src` entry (theta, mu_theta)"""
         dims, _ = self.ktable_info()
         W, G, S = dims[0], dims[1], dims[4]
         lp = _np(lay_press_pa)
@@ -1196,12 +1243,14 @@ class AnsfmEngine:
         mode = 12 if variant == "v" else int(IRAY)
         use_cia, use_dust = q is not None, CONT is not None
         (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        if theta is not None:                   # the populations are those of the aerosol columns
+            ncont, nth = (_np(CONT).shape[-1] if use_dust else 0), theta.shape[0]
         arrs = {}
         for name, a, shape in (("q", q, (n, L, getattr(self, "cia_nvmr", -1))), ("FRAC", FRAC, (n, L)), ("TOTAM", TOTAM, (n, L)),
                                ("DELH", DELH, (n, L)), ("CONT", CONT, (n, L, ncont)), ("f4", f4, (n, L, 4))):
             a = arrs[name] = None if a is None else _np(a)
             if a is not None and -1 not in shape and a.shape != shape:
-                raise ValueError(f"cirsrad_ck_scatter_batch_cont: {name} must be {shape}, got {a.shape}")
+                raise ValueError(f"{what}: {name} must be {shape}, got {a.shape}")
         if use_cia and (arrs["FRAC"] is None or arrs["DELH"] is None):
             raise ValueError("cirsrad_ck_scatter_batch_cont: CIA (q given) needs FRAC and DELH")
         if (use_cia or mode) and arrs["TOTAM"] is None:
@@ -1217,12 +1266,15 @@ class AnsfmEngine:
         if phasarr is not None and phasarr.shape[1] != W_full:
             raise ValueError("cirsrad_ck_scatter_batch_cont: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
         out = np.empty((n, W, P))
-        rc = self._lib.ansfm_cirsrad_ck_scatter_batch_cont(
-            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
-            _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont, nth,
-            _ptr(phasarr), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu,
-            _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
-        self._check(rc, "cirsrad_ck_scatter_batch_cont")
+        head = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
+                _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont, nth)
+        tail = (_ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu,
+                _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
+        if theta is not None:
+            rc = self._lib.ansfm_cirsrad_ck_scatter_batch_src(*head, _ptr(theta), _ptr(mu_theta), *tail)
+        else:
+            rc = self._lib.ansfm_cirsrad_ck_scatter_batch_cont(*head, _ptr(phasarr), *tail)
+        self._check(rc, what)
         return out
 
     def last_scatter_cache(self):
@@ -1341,6 +1393,73 @@ class AnsfmEngine:
         ms = C.c_double()
         self._check(self._lib.ansfm_hg_fit_last(self._ctx, C.byref(ms)), "hg_fit_last")
         return ms.value
+
+    def _phase_tables(self, what, imie, SWAVE, THETA_TAB, tab):
+        """-> (imie, SWAVE, THETA_TAB or None, tab, NDUST, NTAB) as ansfm_calc_phase / ansfm_upload_phase take them"""
+        imie = int(imie); SWAVE = _np(np.atleast_1d(SWAVE)); tab = _np(tab)
+        if imie not in (0, 1, 2):
+            raise ValueError(f"{what}: imie must be 0 (Henyey-Greenstein), 1 (tabulated) or 2 (Legendre)")
+        if SWAVE.ndim != 1 or tab.ndim != 3 or tab.shape[0 if imie else 1] != SWAVE.shape[0] or (imie == 0 and tab.shape[0] != 3):
+            raise ValueError(f"{what}: tab must be (3, NWAVE_scatter, NDUST) for imie 0, else (NWAVE_scatter, NTAB, NDUST)")
+        THETA_TAB = _np(np.atleast_1d(THETA_TAB)) if imie == 1 else None
+        if imie == 1 and THETA_TAB.shape != (tab.shape[1],):
+            raise ValueError(f"{what}: THETA_TAB must be (NTAB,)")
+        return imie, SWAVE, THETA_TAB, tab, tab.shape[2], (0 if imie == 0 else tab.shape[1])
+
+    def calc_phase(self, imie, SWAVE, THETA_TAB, tab, theta, WAVEC):
+        """Scatter_0.calc_phase (:760) on the GPU: imie 0 with tab = (F, G1, G2) stacked (3, NWAVE_scatter, NDUST), 1 with PHASE
+        (NWAVE_scatter, NTHETA, NDUST) on THETA_TAB, 2 with WLPOL (NWAVE_scatter, NLPOL, NDUST); SWAVE = Scatter.WAVE; theta
+        (nth,) degrees, WAVEC (W,) -> phase (W, nth, NDUST).  ValueError where the reference raises one (the range test, an
+        angle outside THETA_TAB) and for tables that are not ascending."""
+        imie, SWAVE, THETA_TAB, tab, nd, ntab = self._phase_tables("calc_phase", imie, SWAVE, THETA_TAB, tab)
+        theta = _np(np.atleast_1d(theta)); WAVEC = _np(np.atleast_1d(WAVEC))
+        out = np.empty((WAVEC.shape[0], theta.shape[0], nd))
+        rc = self._lib.ansfm_calc_phase(self._ctx, imie, SWAVE.shape[0], _ptr(SWAVE), nd, ntab, _ptr(THETA_TAB), _ptr(tab),
+                                        theta.shape[0], _ptr(theta), WAVEC.shape[0], _ptr(WAVEC), _ptr(out))
+        self._check(rc, "calc_phase")
+        return out
+
+    def calc_phase_ray(self, theta):
+        """Scatter_0.calc_phase_ray (:834): theta (nth,) degrees -> (nth,)"""
+        theta = _np(np.atleast_1d(theta))
+        out = np.empty(theta.shape[0])
+        self._check(self._lib.ansfm_calc_phase_ray(self._ctx, theta.shape[0], _ptr(theta), _ptr(out)), "calc_phase_ray")
+        return out
+
+    def phase_last(self):
+        """kernel milliseconds of the last calc_phase, calc_phase_ray or phase_from_source call"""
+        ms = C.c_double()
+        self._check(self._lib.ansfm_phase_last(self._ctx, C.byref(ms)), "phase_last")
+        return ms.value
+
+    def upload_phase(self, imie, SWAVE, THETA_TAB, tab):
+        """Make the aerosol phase function a resident source on the uploaded table's grid, beside `upload_dust` (arguments as
+        `calc_phase`).  NotImplementedError for more than 7 populations.  A new table clears the source."""
+        imie, SWAVE, THETA_TAB, tab, nd, ntab = self._phase_tables("upload_phase", imie, SWAVE, THETA_TAB, tab)
+        rc = self._lib.ansfm_upload_phase(self._ctx, imie, SWAVE.shape[0], _ptr(SWAVE), nd, ntab, _ptr(THETA_TAB), _ptr(tab))
+        self._check(rc, "upload_phase")
+
+    def phase_source_info(self):
+        """(imie, NDUST) of the resident phase-function source; (-1, 0): none stands"""
+        imie, nd = C.c_int(), C.c_int()
+        self._check(self._lib.ansfm_phase_source_info(self._ctx, C.byref(imie), C.byref(nd)), "phase_source_info")
+        return imie.value, nd.value
+
+    def phase_from_source(self, theta):
+        """phase (NWAVE, nth, NDUST) of the resident source on the table's grid: `calc_phase` with WAVEC = that grid, bit for bit"""
+        theta = _np(np.atleast_1d(theta))
+        out = np.empty((self.ktable_info()[0][0], theta.shape[0], self.phase_source_info()[1]))
+        self._check(self._lib.ansfm_phase_from_source(self._ctx, theta.shape[0], _ptr(theta), _ptr(out)), "phase_from_source")
+        return out
+
+    def phasarr_from_source(self, theta):
+        """the array `cirsrad_ck_scatter_batch_src` forms from the resident source at theta (Scatter.THETA, ascending):
+        PHASE_ARRAY[:, :, :, ::-1] of ForwardModel_0.py:5128-5142, (NDUST, NWAVE, 2, nth)"""
+        theta = _np(np.atleast_1d(theta))
+        out = np.empty((self.phase_source_info()[1], self.ktable_info()[0][0], 2, theta.shape[0]))
+        rc = self._lib.ansfm_phasarr_from_source(self._ctx, theta.shape[0], _ptr(theta), _ptr(_np(np.cos(theta * np.pi / 180))), _ptr(out))
+        self._check(rc, "phasarr_from_source")
+        return out
 
     SURFACE_NPAR = {1: 1, 2: 10, 3: 2}     # rows of `params` per LowerBoundaryConditionEnum value
 

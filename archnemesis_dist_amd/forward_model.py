@@ -1173,6 +1173,63 @@ def install_gpu_hg_fit(device=0):
     return subfithgm
 
 
+def install_gpu_phase(device=0):
+    """Route Scatter_0.calc_phase (Scatter_0.py:760, all three IMIE modes) and calc_phase_ray (:834) through the GPU
+    (AnsfmEngine.calc_phase / calc_phase_ray).  Where the reference raises a ValueError -- its range test, an angle outside
+    Scatter.THETA with IMIE 1 -- the reference's own method is called and raises it, message included.  Delegated (DELEGATED,
+    an error under set_strict(True)): a Scatter.WAVE that is not strictly ascending (interp1d would sort it), arrays that
+    are not float64, and what the engine does not take (more than 7 populations through a resident source).
+    summary()["routes"] counts `phase`.  Not part of install_all: Henyey-Greenstein and Legendre values move by ulps against
+    NumPy's cos and pow, and drop-in tests compare some routes bit for bit (INTEGRATION.md says how to switch it on)."""
+    import importlib
+    from ._lib import AnsfmError
+    sc = importlib.import_module("archnemesis.Scatter_0")
+    cls = sc.Scatter_0
+    eng = get_engine(device)
+    ref_phase = getattr(cls, "_ansfm_reference_calc_phase", None) or cls.calc_phase
+    ref_ray = getattr(cls, "_ansfm_reference_calc_phase_ray", None) or cls.calc_phase_ray
+    f8 = lambda a, ndim: isinstance(a, np.ndarray) and a.dtype == np.float64 and a.ndim == ndim
+
+    def calc_phase(self, Theta, Wave):
+        imie = int(self.IMIE)
+        names = {0: ("F", "G1", "G2"), 1: ("PHASE",), 2: ("WLPOL",)}.get(imie)
+        if names is None:
+            return ref_phase(self, Theta, Wave)             # 'IMIE value not valid'
+        tabs = [getattr(self, n, None) for n in names]
+        SW = getattr(self, "WAVE", None)
+        if not (f8(Theta, 1) and f8(Wave, 1) and f8(SW, 1) and all(f8(t, 2 if imie == 0 else 3) for t in tabs) and
+                (imie != 1 or f8(getattr(self, "THETA", None), 1)) and Theta.size and Wave.size and SW.size >= 2):
+            _delegate("calc_phase: arguments or tables that are not float64 arrays")
+            return ref_phase(self, Theta, Wave)
+        if not np.all(np.diff(SW) > 0) or (imie == 1 and not np.all(np.diff(self.THETA) > 0)):
+            _delegate("calc_phase: a Scatter.WAVE or Scatter.THETA that is not strictly ascending")
+            return ref_phase(self, Theta, Wave)
+        if SW.min() > (1. + 1.0e-6) * Wave.min() or SW.max() < (1. - 1.0e-6) * Wave.max():
+            return ref_phase(self, Theta, Wave)             # the reference's ValueError
+        if imie == 1 and (Theta.min() < self.THETA[0] or Theta.max() > self.THETA[-1] or np.isnan(Theta).any()):
+            return ref_phase(self, Theta, Wave)             # interp1d's ValueError
+        tab = np.array(tabs) if imie == 0 else (tabs[0] if imie == 1 else tabs[0][:, :int(self.NLPOL)])
+        try:
+            out = eng.calc_phase(imie, SW, self.THETA if imie == 1 else None, tab, Theta, Wave)
+        except (ValueError, NotImplementedError, AnsfmError):
+            _delegate("calc_phase: a call the engine does not take")
+            return ref_phase(self, Theta, Wave)
+        _route("phase")
+        return out
+
+    def calc_phase_ray(self, Theta):
+        if not (f8(Theta, 1) and Theta.size):
+            _delegate("calc_phase_ray: an argument that is not a float64 array")
+            return ref_ray(self, Theta)
+        out = eng.calc_phase_ray(Theta)
+        _route("phase")
+        return out
+
+    cls._ansfm_reference_calc_phase, cls._ansfm_reference_calc_phase_ray = ref_phase, ref_ray
+    cls.calc_phase, cls.calc_phase_ray = calc_phase, calc_phase_ray
+    return calc_phase, calc_phase_ray
+
+
 def aerosol_memo_capacity(variables):
     """Entries the Mie and the fit memo need so that a staged Jacobian computes every distinct aerosol state once:
     max(8, 1 + the state-vector elements of the models whose class calls Scatter.makephase).  A staged route walks

@@ -82,6 +82,20 @@ def continuum_rows_by_hand(eng, ISPACE, IRAY, ID, ISO, cia, dust, lay):
     return pk
 
 
+def _phase_source(what, phase_source, dense, dust):
+    """phase_source=(imie, THETA_TAB, tab) of a model -> (imie, THETA_TAB float64, tab float64), or None; it stands in for the
+    dense host array and lives on the aerosol grid dust["SWAVE"]"""
+    if phase_source is None:
+        return None
+    if dense is not None or dust is None:
+        raise ValueError(what + "phase_source replaces the dense phase-function array (pass None) and needs dust=dict(SWAVE, KEXT, KSCA)")
+    imie, theta, tab = phase_source
+    tab = np.ascontiguousarray(tab, dtype=float)
+    if tab.ndim != 3:
+        raise ValueError(what + "phase_source = (imie, THETA_TAB, tab), tab as AnsfmEngine.calc_phase takes it")
+    return int(imie), (None if theta is None else np.ascontiguousarray(theta, dtype=float)), tab
+
+
 class BatchedCKScatterModel:
     """The scattering forward model of n states at once (see the module docstring); what `jacobian.jacobian_nemesis_batched`
     asks of a model.
@@ -93,6 +107,9 @@ class BatchedCKScatterModel:
     phasarr (NDUST, NWAVE, 2, NTHETA) as the engine takes it, MU / WTMU the quadrature, NF, NPHI, IMIE; SOL_ANG / EMISS_ANG /
     AZI_ANG: lists, one entry per geometry; solar (NWAVE); LOWBC and brdf_matrix (NWAVE, NMU, NMU, NF + 1; None: zeros);
     TSURF, emissivity (NWAVE; None: 1) and gasgiant decide the boundary radiance (:5083-5089).
+    phase_source=(imie, THETA, tab) instead of phasarr (pass None): the phase function as a resident source of the engine
+    (upload_phase on dust["SWAVE"], uploaded with the aerosol source; tab as AnsfmEngine.calc_phase takes it, THETA =
+    Scatter.THETA) and phasarr formed on the device (cirsrad_ck_scatter_batch_src).  Whole axis only.
     DUST_RENORMALISATION: the reference rescales the aerosol columns in the caller of calc_tau_dust; anything but None / False
     raises NotImplementedError, as do more than 7 populations."""
 
@@ -101,7 +118,7 @@ class BatchedCKScatterModel:
 
     def __init__(self, eng, state, RADIUS, ID, ISO, igas_map, phasarr, MU, WTMU, NF, NPHI, SOL_ANG, EMISS_ANG, AZI_ANG, solar,
                  layering_args=None, ISPACE=0, IRAY=0, IMIE=0, PARAH2=None, cia=None, dust=None, LOWBC=0, brdf_matrix=None,
-                 TSURF=-1.0, emissivity=None, gasgiant=True, DUST_RENORMALISATION=None):
+                 TSURF=-1.0, emissivity=None, gasgiant=True, DUST_RENORMALISATION=None, phase_source=None):
         if DUST_RENORMALISATION is not None and DUST_RENORMALISATION is not False:
             raise NotImplementedError("BatchedCKScatterModel: DUST_RENORMALISATION-style rescaling of the aerosol columns is applied "
                                       "by the caller of calc_tau_dust in the reference and is not built here")
@@ -140,6 +157,13 @@ class BatchedCKScatterModel:
         NMU = self.MU.size
         self.phasarr = None if phasarr is None else np.ascontiguousarray(phasarr, dtype=float)
         ncont = 0 if self.phasarr is None else self.phasarr.shape[0]
+        self.phase_source = _phase_source("BatchedCKScatterModel: ", phase_source, self.phasarr, self.dust)
+        if self.phase_source is not None:
+            ncont = self.phase_source[2].shape[2]
+            if self.phase_source[1] is None or self.phase_source[1].size < 3:
+                raise ValueError("BatchedCKScatterModel: phase_source needs Scatter.THETA, at least three angles")
+            if (self.phase_source[0] == 0) != (self.IMIE == 0):
+                raise ValueError("BatchedCKScatterModel: phase_source and IMIE disagree about Henyey-Greenstein phase functions")
         if ncont != (0 if self.DUST is None else self.DUST.shape[1]):
             raise ValueError("BatchedCKScatterModel: phasarr (NDUST, NWAVE, 2, NTHETA) lists one phase function per population")
         self.solar = np.ascontiguousarray(solar, dtype=float)
@@ -202,6 +226,8 @@ class BatchedCKScatterModel:
                            k_n2n2=c.get("k_n2n2"), k_n2h2=c.get("k_n2h2"))
         if self.dust is not None:
             eng.upload_dust(self.dust["SWAVE"], self.dust["KEXT"], self.dust["KSCA"])
+        if self.phase_source is not None:
+            eng.upload_phase(self.phase_source[0], self.dust["SWAVE"], self.phase_source[1], self.phase_source[2])
         self._sources_on = True
 
     # ---- device part ----------------------------------------------------------------------------------------------
@@ -215,16 +241,19 @@ class BatchedCKScatterModel:
         lay = self.layers(X)
         n, L = lay["PRESS"].shape
         cia, dust = self.cia is not None, self.dust is not None
-        common = (self.phasarr, self.radg(lay), self.SOL_ANG, self.EMISS_ANG, self.AZI_ANG, self.solar, self.LOWBC, self.brdf_matrix,
+        src = self.phase_source
+        if src is not None and not (self.fused_continuum and wave_slice is None):
+            raise NotImplementedError("BatchedCKScatterModel: phase_source needs the fused continuum and the whole spectral axis")
+        common = (self.phasarr if src is None else src[1], self.radg(lay), self.SOL_ANG, self.EMISS_ANG, self.AZI_ANG, self.solar, self.LOWBC, self.brdf_matrix,
                   self.MU, self.WTMU, self.NF, self.NPHI, self.IRAY, self.IMIE)
         if self.fused_continuum and (cia or dust or self.IRAY != 0):
             if not self._sources_on:
                 self.upload_sources()
             f4 = eng.rayleigh_f4(self.ID, self.ISO, lay["VMRLAY"]) if self.IRAY == 4 else None
-            out = eng.cirsrad_ck_scatter_batch_cont(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"],
-                                                    lay["VMRLAY"] if cia else None, lay["FRAC"] if cia else None, lay["TOTAM"],
-                                                    lay["DELH"] if cia else None, lay["CONT"] if dust else None, self.IRAY, f4,
-                                                    *common, wave_slice=wave_slice)
+            entry = eng.cirsrad_ck_scatter_batch_cont if src is None else eng.cirsrad_ck_scatter_batch_src
+            out = entry(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"], lay["VMRLAY"] if cia else None,
+                        lay["FRAC"] if cia else None, lay["TOTAM"], lay["DELH"] if cia else None, lay["CONT"] if dust else None,
+                        self.IRAY, f4, *common, wave_slice=wave_slice)
         else:
             pk = continuum_rows_by_hand(eng, self.ISPACE, self.IRAY, self.ID, self.ISO, self.cia, self.dust, lay)
             out = eng.cirsrad_ck_scatter_batch_rows(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"], pk.cont_row,
@@ -305,14 +334,17 @@ class BatchedCKSingleScatterModel:
     phase_fn (NWAVE, NPATH, NDUST + 1): the phase function of every population and, last, of Rayleigh scattering at each
     path's scattering angle (ScatterX.calc_phase / calc_phase_ray, :4269-4271 before the transpose).  SOL_ANG / EMISS_ANG: one
     entry per path; solar (NWAVE); BRDF (NWAVE, NPATH) or None (zeros); TSURF, emissivity (NWAVE; None: 1), xfac (NWAVE) or
-    None.  More than 7 populations and DUST_RENORMALISATION raise NotImplementedError, as in BatchedCKScatterModel."""
+    None.  phase_source=(imie, THETA_TAB, tab) with AZI_ANG (one entry per path) instead of phase_fn (pass None): the phase
+    function as a resident source of the engine (upload_phase on dust["SWAVE"], uploaded with the aerosol source) and phase_fn
+    formed on the device at each path's scattering angle (cirsrad_ck_singlescatt_batch_src).
+    More than 7 populations and DUST_RENORMALISATION raise NotImplementedError, as in BatchedCKScatterModel."""
 
     fused_continuum = True    # False: taucont / tausca / phase of all n * NLAY layers at array level (singlescatt_dense_by_hand)
                               # through cirsrad_ck_singlescatt_batch (same bits)
 
     def __init__(self, eng, state, RADIUS, ID, ISO, igas_map, phase_fn, SOL_ANG, EMISS_ANG, solar, layering_args=None, geometry=None,
                  ISPACE=0, IRAY=0, PARAH2=None, cia=None, dust=None, BRDF=None, TSURF=-1.0, emissivity=None, xfac=None,
-                 DUST_RENORMALISATION=None):
+                 DUST_RENORMALISATION=None, phase_source=None, AZI_ANG=None):
         what = "BatchedCKSingleScatterModel: "
         if DUST_RENORMALISATION is not None and DUST_RENORMALISATION is not False:
             raise NotImplementedError(what + "DUST_RENORMALISATION-style rescaling of the aerosol columns is applied by the caller "
@@ -354,8 +386,16 @@ class BatchedCKSingleScatterModel:
                                                       NLAY=la["NLAY"], LAYTYP=la["LAYTYP"])
         self.NPATH = self._path(np.ones_like(self.BASEH), np.ones_like(self.BASEH)).NPATH
         ND = 0 if self.DUST is None else self.DUST.shape[1]
-        self.phase_fn = np.ascontiguousarray(phase_fn, dtype=float)
-        if self.phase_fn.shape != (self.W, self.NPATH, ND + 1):
+        self.phase_fn = None if phase_fn is None else np.ascontiguousarray(phase_fn, dtype=float)
+        self.phase_source = _phase_source(what, phase_source, self.phase_fn, self.dust)
+        self.alpha_deg = None
+        if self.phase_source is not None:
+            if AZI_ANG is None or np.size(AZI_ANG) != self.NPATH or self.phase_source[2].shape[2] != ND:
+                raise ValueError(what + "phase_source needs AZI_ANG, one entry per path, and one phase function per population")
+            self.alpha_deg = eng.scattering_angle_deg(self.SOL_ANG, self.EMISS_ANG, AZI_ANG)
+        elif self.phase_fn is None:
+            raise ValueError(what + "phase_fn (NWAVE, NPATH, NDUST + 1) or phase_source is needed")
+        elif self.phase_fn.shape != (self.W, self.NPATH, ND + 1):
             raise ValueError(what + "phase_fn must be (NWAVE, NPATH, NDUST + 1) = %s, got %s" % ((self.W, self.NPATH, ND + 1), self.phase_fn.shape))
         if not (self.SOL_ANG.size == self.EMISS_ANG.size == self.NPATH):
             raise ValueError(what + "SOL_ANG and EMISS_ANG list one entry per path")
@@ -412,6 +452,8 @@ class BatchedCKSingleScatterModel:
                            k_n2n2=c.get("k_n2n2"), k_n2h2=c.get("k_n2h2"))
         if self.dust is not None:
             eng.upload_dust(self.dust["SWAVE"], self.dust["KEXT"], self.dust["KSCA"])
+        if self.phase_source is not None:
+            eng.upload_phase(self.phase_source[0], self.dust["SWAVE"], self.phase_source[1], self.phase_source[2])
         self._sources_on = True
 
     # ---- device part ----------------------------------------------------------------------------------------------
@@ -427,14 +469,18 @@ class BatchedCKSingleScatterModel:
         cia, dust = self.cia is not None, self.dust is not None
         rt = (path.NLAYIN, path.LAYINC, np.repeat(path.SCALE[None], n, 0), path.EMTEMP, np.full(n, self.TSURF), self.emissivity,
               self.BRDF, self.solar, self.SOL_ANG, self.EMISS_ANG)
+        src = self.phase_source
+        if src is not None and not self.fused_continuum:
+            raise NotImplementedError("BatchedCKSingleScatterModel: phase_source needs the fused continuum")
         if self.fused_continuum:
             if not self._sources_on:
                 self.upload_sources()
             f4 = eng.rayleigh_f4(self.ID, self.ISO, lay["VMRLAY"]) if self.IRAY == 4 else None
-            out = eng.cirsrad_ck_singlescatt_batch_cont(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"],
-                                                        lay["VMRLAY"] if cia else None, lay["FRAC"] if cia else None, lay["TOTAM"],
-                                                        lay["DELH"] if cia else None, lay["CONT"] if dust else None, self.IRAY, f4,
-                                                        self.phase_fn, *rt, xfac=self.xfac)
+            entry = eng.cirsrad_ck_singlescatt_batch_cont if src is None else eng.cirsrad_ck_singlescatt_batch_src
+            out = entry(self.ISPACE, lay["PRESS"], lay["TEMP"], lay["amount"],
+                        lay["VMRLAY"] if cia else None, lay["FRAC"] if cia else None, lay["TOTAM"],
+                        lay["DELH"] if cia else None, lay["CONT"] if dust else None, self.IRAY, f4,
+                        self.phase_fn if src is None else self.alpha_deg, *rt, xfac=self.xfac)
         else:
             taucont, tausca, phase = singlescatt_dense_by_hand(eng, self.ISPACE, self.IRAY, self.ID, self.ISO, self.cia, self.dust,
                                                                lay, self.phase_fn)

@@ -272,6 +272,22 @@ int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_mo
                                             const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
                                             const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
                                             double *SPECOUT);
+/* The same with phase_fn formed on the device (phase_fn [W][P][ncont + 1] is the one per-wavenumber input the entry above still
+ * takes from the host): in its place alpha_deg [P], the scattering angle of each path in degrees, arccos(calpha) / pi * 180 by
+ * the expression of ForwardModel_0.py:4265-4270.  phase_fn[w][ip][0 .. ncont) is the resident phase-function source
+ * (ansfm_upload_phase) at alpha_deg, [ncont] is calc_phase_ray; k_phase_fn writes both into the buffer k_ss_cont_rows reads.
+ * Bit-identical to the entry above called with phase_fn put together from ansfm_phase_from_source and ansfm_calc_phase_ray at
+ * the same angles, with and without ansfm_set_layer_dedup.  ANSFM_ERR_INVALID, before anything is launched, also when no
+ * phase-function source has been uploaded since the last table, when its NDUST is not ncont, or (IMIE 1) for an angle outside
+ * the tabulated ones. */
+int ansfm_cirsrad_ck_singlescatt_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                           const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                           const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                           const double *lay_cont, int ray_mode, const double *f4, int ncont, const double *alpha_deg,
+                                           int P, int LIMAX, const int32_t *NLAYIN, const int32_t *LAYINC, const double *SCALE,
+                                           const double *EMTEMP, const double *TSURF, const double *EMISSIVITY, const double *BRDF,
+                                           const double *SOLFLUX, const double *SOL_ANG, const double *EMISS_ANG, const double *xfac,
+                                           double *SPECOUT);
 
 /* ---- fused seam: CIRSrad, ILBL=K_TABLES, IMOD=THERMAL_EMISSION ------------------------------
  * ForwardModel_0.CIRSrad (ForwardModel_0.py:4376-4511) =
@@ -683,6 +699,24 @@ int ansfm_cirsrad_ck_scatter_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models
                                         const double *emiss_angs, const double *aphis, const double *solar, int lowbc,
                                         const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf, int nphi,
                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
+/* The same with phasarr formed on the device from the resident phase-function source (ansfm_upload_phase): in its place
+ * theta_deg [nth] (Scatter.THETA, strictly ascending) and mu_theta [nth] = np.cos(THETA * pi / 180) from the host, so that row 1
+ * carries NumPy's bits.  k_phase_fn writes PHASE_ARRAY[:, :, :, ::-1] of ForwardModel_0.py:5128-5142 straight into the buffer
+ * the phase-matrix kernels read: with imie == 0 row 0 holds f_w, g1_w, g2_w (np.interp of F, G1, G2 on the table's grid) in its
+ * first three slots and zeros behind, otherwise the source at theta_deg, reversed; row 1 is mu_theta, reversed.
+ * ansfm_phasarr_from_source returns the same array to the host, and the result is bit-identical to the entry above called with
+ * it, for every stream count, with the layer cache on and off.  use_dust must be set.  ANSFM_ERR_UNSUPPORTED: W_full is not the
+ * table's W or w_begin != 0 (a slice's context does not hold the whole grid).  ANSFM_ERR_INVALID, before anything is launched,
+ * also when no phase-function source has been uploaded since the last table, when its NDUST is not ncont, when imie is 0 and
+ * the source's is not (or the reverse), for theta_deg not ascending or (IMIE 1) outside the tabulated angles. */
+int ansfm_cirsrad_ck_scatter_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
+                                       const double *lay_temp, const double *amount, int use_cia, const double *lay_q,
+                                       const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                                       const double *lay_cont, int ray_mode, const double *f4, int ncont, int nth,
+                                       const double *theta_deg, const double *mu_theta, const double *radg, int ngeom,
+                                       const double *sol_angs, const double *emiss_angs, const double *aphis, const double *solar,
+                                       int lowbc, const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf,
+                                       int nphi, int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total);
 /* Spectral windows of phase matrices / Hansen factors in the last scattering call (ansfm_cirsrad_ck_scatter(_batch),
  * ansfm_scloud11wave_core) and the wavenumbers per window: 1 and W when one window covers the axis (always at G > 1). */
@@ -1054,6 +1088,42 @@ int ansfm_mie_last(const ansfm_ctx *ctx, double *kernel_ms, int32_t *blocks, int
 int ansfm_hg_fit(ansfm_ctx *ctx, int nfit, int nphase, const double *theta_deg, const double *phase, double *f, double *g1,
                  double *g2, double *rms, int32_t *counts);
 int ansfm_hg_fit_last(const ansfm_ctx *ctx, double *kernel_ms);
+
+/* ---- Aerosol phase functions on the calculation grid --------------------------------------------------------------------
+ * Scatter_0.calc_phase (Scatter_0.py:760) and calc_phase_ray (:834).  imie selects what tab holds on SWAVE [NWS] (Scatter.WAVE,
+ * strictly ascending, in the units of the calculation grid):
+ *   0 HENYEY_GREENSTEIN     F, G1, G2 as [3][NWS][NDUST]; NTAB and THETA_TAB are ignored (calc_hgphase :699)
+ *   1 MIE_THEORY            PHASE [NWS][NTAB][NDUST] on THETA_TAB [NTAB] (Scatter.THETA), interpolated in angle (interp_phase :732)
+ *   2 LEGENDRE_POLYNOMIALS  WLPOL [NWS][NTAB = NLPOL][NDUST]; THETA_TAB is ignored (calc_lpphase :1060)
+ * ansfm_calc_phase: theta_deg [nth], WAVEC [W] -> phase [W][nth][NDUST].  phase1 on the aerosol grid, then linear along the
+ * wavenumbers with the end intervals extrapolating; both interpolations are interp1d's (searchsorted 'left' clipped to
+ * 1 .. n - 1, slope * (x - x_lo) + y_lo).  One lane per (wavenumber, angle); no expression contracts into an fma, so that the
+ * results differ from NumPy's only where cos and pow do, and imie = 1, which has neither, is the reference bit for bit.
+ * ANSFM_ERR_INVALID, before anything is launched: a null pointer; NWS < 2, nth < 1, W < 1, NDUST < 1, NTAB < 1 (< 2 for imie
+ * 1); SWAVE not strictly ascending; imie 1 with THETA_TAB not strictly ascending or a theta_deg outside it (the reference's
+ * interp1d raises); the reference's range test, SWAVE[0] > (1 + 1e-6) min(WAVEC) or SWAVE[NWS - 1] < (1 - 1e-6) max(WAVEC);
+ * an imie outside 0 .. 2.
+ * ansfm_calc_phase_ray: 0.75 (1 + cos^2 theta) / (4 pi) at theta_deg [nth].
+ * ansfm_phase_last: kernel milliseconds of the last ansfm_calc_phase, ansfm_calc_phase_ray or ansfm_phase_from_source.
+ *
+ * ansfm_upload_phase makes the tables a resident source on the uploaded table's grid, beside ansfm_upload_dust: the tables go
+ * to HBM, every wavenumber's interval (lo, x_lo, x_hi) is found once, and for imie 0 f_w, g1_w, g2_w [NDUST][Wpad] are formed
+ * by np.interp's rule (a node returns its tabulated value, the ends clamp, slope * (x - x_j) + y_j in between: np.interp's
+ * bits).  The range test is made on the table's grid.  NDUST > 7 is ANSFM_ERR_UNSUPPORTED, as for ansfm_upload_dust.  A new
+ * table, a committed line source and ansfm_clear_continuum_sources clear the source.
+ * ansfm_phase_from_source: phase [W][nth][NDUST] on the table's grid, bit-identical to ansfm_calc_phase with WAVEC = that grid.
+ * ansfm_phasarr_from_source: the array ansfm_cirsrad_ck_scatter_batch_src forms (described there), [NDUST][W][2][nth], nth >= 3.
+ * Both: ANSFM_ERR_INVALID without a source, and for the angles as above.
+ * ansfm_phase_source_info: imie and NDUST of the source that stands (-1 and 0: none); a caller sizes the results by it. */
+int ansfm_calc_phase(ansfm_ctx *ctx, int imie, int NWS, const double *SWAVE, int NDUST, int NTAB, const double *THETA_TAB,
+                     const double *tab, int nth, const double *theta_deg, int W, const double *WAVEC, double *phase);
+int ansfm_calc_phase_ray(ansfm_ctx *ctx, int nth, const double *theta_deg, double *phase);
+int ansfm_phase_last(const ansfm_ctx *ctx, double *kernel_ms);
+int ansfm_upload_phase(ansfm_ctx *ctx, int imie, int NWS, const double *SWAVE, int NDUST, int NTAB, const double *THETA_TAB,
+                       const double *tab);
+int ansfm_phase_source_info(const ansfm_ctx *ctx, int *imie, int *NDUST);
+int ansfm_phase_from_source(ansfm_ctx *ctx, int nth, const double *theta_deg, double *phase);
+int ansfm_phasarr_from_source(ansfm_ctx *ctx, int nth, const double *theta_deg, const double *mu_theta, double *phasarr);
 
 /* ---- Surface reflection ----------------------------------------------------------------------------------------------------
  * lowbc takes the values of LowerBoundaryConditionEnum and decides the rows of params[npar][nwave]:

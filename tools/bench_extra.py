@@ -62,7 +62,182 @@ def main():
         bench_ss_cont(eng, out, rng)
     if only == "scatter_cont":                              # 13 GB of host arrays in the by-hand route: on request only
         bench_scatter_cont(eng, out)
+    if only == "phase":                                     # 131 MB of phase functions per population on the host: on request only
+        bench_phase(eng, out, rng)
     print(json.dumps(out, indent=1))
+
+
+def calc_phase_host(imie, SWAVE, THETA_TAB, tab, theta, WAVE):
+    """Scatter_0.calc_phase restated in NumPy (the host route the GPU entries replace): phase1 on the aerosol grid, then
+    interp1d's linear rule along the wavenumbers -> (W, nth, NDUST)"""
+    def lin(x, y, xn):
+        hi = np.clip(np.searchsorted(x, xn, "left"), 1, len(x) - 1); lo = hi - 1
+        ex = (slice(None),) + (None,) * (y.ndim - 1)
+        return ((y[hi] - y[lo]) / (x[hi] - x[lo])[ex]) * (xn - x[lo])[ex] + y[lo]
+    c = np.cos(theta / 180. * np.pi)
+    if imie == 0:
+        F, G1, G2 = (a[:, None, :] for a in tab)
+        cx = c[None, :, None]
+        t1 = (1. - G1 ** 2.) / (1. - 2. * G1 * cx + G1 ** 2.) ** 1.5
+        t2 = (1. - G2 ** 2.) / (1. - 2. * G2 * cx + G2 ** 2.) ** 1.5
+        phase1 = (F * t1 + (1.0 - F) * t2) / (4.0 * np.pi)
+    elif imie == 1:
+        phase1 = np.moveaxis(lin(THETA_TAB, np.moveaxis(tab, 1, 0), theta), 0, 1)
+    else:
+        phase1 = np.zeros((tab.shape[0], theta.size, tab.shape[2]))
+        p0, p1 = np.ones_like(c), c
+        for l in range(tab.shape[1]):
+            pl = p0 if l == 0 else p1
+            if l >= 2:
+                pl = ((2 * l - 1) * c * p1 - (l - 1) * p0) / l
+                p0, p1 = p1, pl
+            phase1 += pl[None, :, None] * tab[:, l, None, :]
+    return lin(SWAVE, phase1, WAVE)
+
+
+def bench_phase(eng, out, rng, n=5):
+    """The aerosol phase function on the calculation grid (41 angles, 2 populations), host route against device route:
+      (a) ansfm_calc_phase per IMIE at W = 1e4 and 2e5: kernel time, end to end with the result copied back, beside the NumPy
+          restatement of Scatter_0.calc_phase on the host;
+      (b) the multiple-scattering batch: cirsrad_ck_scatter_batch_cont with PHASE_ARRAY formed on the host for every call
+          (calc_phase + staging, the parent's route) against cirsrad_ck_scatter_batch_src, 5 streams / NF 2, at C4 size (W = 1e4,
+          G = 20) and on an LBL window (W = 2e5, G = 1), `states` forward models of 100 layers;
+      (c) the same pair for the single-scattering batch (phase_fn at one path's angle) at W = 1e4, 201 states.
+    Medians of n runs after a warm-up.
+        python tools/bench_extra.py phase [a|b|c|all] [states of (b)] [W of the LBL window]"""
+    import torch
+    from bench import torch_ktable
+    from archnemesis_dist_amd.jacobian import perturbed_states
+    from archnemesis_dist_amd.profile_state import ContinuousProfileState
+    from archnemesis_dist_amd.scatter_state import BatchedCKScatterModel, BatchedCKSingleScatterModel
+    part = sys.argv[2] if len(sys.argv) > 2 else "all"
+    states_b = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    W_lbl = int(sys.argv[4]) if len(sys.argv) > 4 else 200000
+    ND, NWS, S, L, NP, NT = 2, 12, 8, 100, 20, 15
+    TH = np.linspace(0.0, 180.0, 41)
+    res = {"angles": 41, "populations": ND, "median_of": n}
+
+    def tables(imie, SWAVE):
+        x = np.linspace(0.0, 1.0, NWS)[:, None] + 0.1 * np.arange(ND)[None]
+        g = 0.3 + 0.5 * x / 1.1
+        if imie == 0:
+            return np.array([0.5 + 0.3 * x / 1.1, g, -0.2 - 0.2 * x / 1.1])
+        if imie == 1:
+            c = np.cos(np.deg2rad(TH))[None, :, None]
+            return (1 - g[:, None] ** 2) / (1 + g[:, None] ** 2 - 2 * g[:, None] * c) ** 1.5 / (4 * np.pi)
+        l = np.arange(36)[None, :, None]
+        return (2 * l + 1) * g[:, None] ** l / (4 * np.pi)
+
+    def grid(W):
+        WAVE = 200.0 + (1000.0 / W) * np.arange(W)
+        return WAVE, np.linspace(0.9 * WAVE[0], 1.1 * WAVE[-1], NWS)
+
+    def phasarr_host(imie, SWAVE, tab, WAVE):
+        """ForwardModel_0.py:5128-5142 on the host"""
+        arr = np.zeros((ND, WAVE.size, 2, TH.size))
+        if imie == 0:
+            for d in range(ND):
+                for k, slot in ((0, -1), (1, -2), (2, -3)):
+                    arr[d, :, 0, slot] = np.interp(WAVE, SWAVE, tab[k][:, d])
+        else:
+            arr[:, :, 0, :] = np.transpose(calc_phase_host(imie, SWAVE, TH, tab, TH, WAVE), (2, 0, 1))
+        arr[:, :, 1, :] = np.cos(TH * np.pi / 180)
+        return np.ascontiguousarray(arr[:, :, :, ::-1])
+
+    if part in ("a", "all"):
+        for W in (10000, 200000):
+            WAVE, SWAVE = grid(W)
+            for imie in (0, 1, 2):
+                tab = np.ascontiguousarray(tables(imie, SWAVE))
+                run = lambda: eng.calc_phase(imie, SWAVE, TH, tab, TH, WAVE)
+                got = run()
+                host = calc_phase_host(imie, SWAVE, TH, tab, TH, WAVE)
+                res["calc_phase_imie%d_W%d" % (imie, W)] = {
+                    "gpu_end_to_end_s": timeit(run, n), "gpu_kernel_ms": eng.phase_last(),
+                    "host_numpy_s": timeit(lambda: calc_phase_host(imie, SWAVE, TH, tab, TH, WAVE), n),
+                    "result_MB": got.nbytes / 1e6,
+                    "max_deviation_over_column_max": float(np.max(np.abs(got - host) / np.abs(host).max(axis=1, keepdims=True)))}
+
+    pr = syn.synth_profiles(100, S + 2, seed=11)
+    zl = np.linspace(0.0, 1.0, 100)
+    DUST = np.stack([2.0e3 * np.exp(-4.0 * zl), 3.0e2 * np.exp(-((zl - 0.4) / 0.1) ** 2) + 1.0e-3], axis=1)
+    xs = np.linspace(0.0, 1.0, NWS)[:, None]
+    KEXT = 1.0e-9 * (1.0 + 0.6 * np.sin(5.0 * xs + np.arange(ND)[None])) * (1.0 + np.arange(ND)[None])
+    KSCA = 0.7 * KEXT * (1.0 - 0.5 * xs)
+    la = dict(NLAY=L, LAYINT=1, NINT=101)
+    args = (pr["RADIUS"], pr["ID"], pr["ISO"], list(range(2, S + 2)))
+    dev = torch.device("cuda", eng.device)
+
+    def pair(make_host, make_src, X):
+        """median seconds of spectra_batch: the model rebuilt with the host-formed array per call against the resident source"""
+        src = make_src()
+        Y = src.spectra_batch(X).cpu().numpy()
+
+        def host():
+            m = make_host()
+            m._sources_on = True                            # the aerosol source is resident already: only the array is formed anew
+            return m.spectra_batch(X)
+        same = bool(np.array_equal(host().cpu().numpy(), Y))
+        t_form = timeit(lambda: make_host(), n)
+        return {"host_route_s": timeit(host, n), "of_which_forming_the_array_s": t_form,
+                "source_route_s": timeit(lambda: src.spectra_batch(X), n), "bit_identical": same}
+
+    if part in ("b", "all"):
+        xq, wq = np.polynomial.legendre.leggauss(5)
+        MU, WT = 0.5 * (xq + 1.0), 0.5 * wq
+        for tag, W, G in (("C4_W1e4_G20", 10000, 20), ("LBL_window_G1", W_lbl, 1)):
+            WAVE, SWAVE = grid(W)
+            PRESS, TEMP, K = torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+            if G == 1:
+                eng.upload_lbltable(K.reshape(W, NP, NT, S).cpu().numpy(), PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE)
+            else:
+                _, delg = syn.gauss_legendre_01(G, as_float32=True)
+                eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32))
+            del K
+            torch.cuda.empty_cache()
+            st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T"])
+            X = np.ascontiguousarray(perturbed_states(st.XN, 0.05 * st.XN).T[:states_b])
+            dust = dict(SWAVE=SWAVE, KEXT=KEXT, KSCA=KSCA, DUST=DUST)
+            for imie in (0, 1):
+                tab = np.ascontiguousarray(tables(imie, SWAVE))
+                geo = (MU, WT, 2, 101, [30.0], [20.0], [45.0], np.full(W, 1.0e-8))
+                kw = dict(layering_args=la, IRAY=1, IMIE=imie, dust=dust)
+                mk_host = lambda: BatchedCKScatterModel(eng, st, *args, phasarr_host(imie, SWAVE, tab, WAVE), *geo, **kw)
+                mk_src = lambda: BatchedCKScatterModel(eng, st, *args, None, *geo, phase_source=(imie, TH, tab), **kw)
+                r = pair(mk_host, mk_src, X)
+                r["states"] = int(X.shape[0]); r["phasarr_MB"] = ND * W * 2 * TH.size * 8 / 1e6
+                res["scatter_batch_%s_imie%d" % (tag, imie)] = r
+
+    if part in ("c", "all"):
+        W, G = 10000, 20
+        WAVE, SWAVE = grid(W)
+        PRESS, TEMP, K = torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+        _, delg = syn.gauss_legendre_01(G, as_float32=True)
+        eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+        st = ContinuousProfileState(pr["H"], pr["P"], pr["T"], pr["VMR"], ["T", ("VMR", 2)])
+        X = np.ascontiguousarray(perturbed_states(st.XN, 0.05 * st.XN).T)
+        dust = dict(SWAVE=SWAVE, KEXT=KEXT, KSCA=KSCA, DUST=DUST)
+        solar, BRDF = 10.0 ** rng.uniform(-8, -7, W), rng.uniform(0.0, 0.15, (W, 1))
+        kw = dict(layering_args=la, geometry=dict(ANGLE=20.0, EMISS_ANG=20.0), IRAY=1, dust=dust, BRDF=BRDF)
+        alpha = eng.scattering_angle_deg([30.0], [20.0], [45.0])
+        ray = 0.75 * (1.0 + np.cos(alpha / 180. * np.pi) ** 2) / (4.0 * np.pi)
+        for imie in (0, 1, 2):
+            tab = np.ascontiguousarray(tables(imie, SWAVE))
+
+            def phase_fn_host():
+                pf = np.zeros((W, 1, ND + 1))
+                pf[:, :, :ND] = calc_phase_host(imie, SWAVE, TH, tab, alpha, WAVE)
+                pf[:, :, ND] = ray
+                return pf
+            mk_host = lambda: BatchedCKSingleScatterModel(eng, st, *args, phase_fn_host(), [30.0], [20.0], solar, **kw)
+            mk_src = lambda: BatchedCKSingleScatterModel(eng, st, *args, None, [30.0], [20.0], solar, phase_source=(imie, TH, tab),
+                                                         AZI_ANG=[45.0], **kw)
+            r = pair(mk_host, mk_src, X)
+            if imie != 1:                                   # cos and pow differ by ulps between NumPy and the device
+                r.pop("bit_identical")
+            r["states"] = int(X.shape[0])
+            res["singlescatt_batch_C2_imie%d" % imie] = r
+    out["phase"] = res
 
 
 def bench_scatter_cont(eng, out, W=10000, n=5):
