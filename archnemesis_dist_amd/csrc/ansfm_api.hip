@@ -670,18 +670,18 @@ int ansfm::dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const d
     return ANSFM_OK;
 }
 
-// The same with the columns behind the continuum of c (device arrays over the n * L layers).  The para-H2 fraction counts only
-// where cia_layer reads it (a table with a para-H2 axis): the scattering batch takes a layer from model 0's doubling results
-// exactly when its row is model 0's, and a column that changes no opacity must not cost that.
+// The same with the columns behind the continuum of c (device arrays over the n * L layers).  Without frac_always the para-H2
+// fraction counts only where cia_layer reads it (a table with a para-H2 axis): the scattering batch takes a layer from model
+// 0's doubling results exactly when its row is model 0's, and a column that changes no opacity must not cost that.
 int ansfm::dedup_rows_cont(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount,
-                           const ContCall &c, DedupRows *out)
+                           const ContCall &c, bool frac_always, DedupRows *out)
 {
     DedupCols x;
     if (c.ray_mode || c.use_cia) x.add(c.totam, 1);
     if (c.ray_mode == 4) x.add(c.f4, 4);
     if (c.use_cia) {
         x.add(c.q, ctx->cia_NVMR); x.add(c.delh, 1);
-        if (ctx->cia_NPARA > 0 || ctx->cia_nfrac > 1) x.add(c.frac, 1);
+        if (frac_always || ctx->cia_NPARA > 0 || ctx->cia_nfrac > 1) x.add(c.frac, 1);
     }
     if (c.use_dust) x.add(c.cont, ctx->dust_n);
     return dedup_rows(ctx, n, L, press, temp, amount, &x, out);
@@ -745,18 +745,20 @@ namespace {
 // What the thermal, transmission, single-scattering and gradient entry points take, under the names and in the layouts of
 // include/ansfm.h.  The extern "C" function fills it once and everything below reads it (as MsCall in ansfm_scatter.hip); what
 // an entry does not take stays null or 0.  The arrays are host or device pointers as the entry says; igas_map is a host
-// pointer always, ray_totam / ray_f4 and the arrays of a fused continuum device pointers in every forward entry (the gradient
-// entry with a fused continuum has a host variant, ansfm_cirsradg_ck_thermal_cont: stage_call uploads them with the rest).
+// pointer always, the arrays of cont the entry's kind as well (stage_call uploads them with the rest).
 struct RtCall {
     int ISPACE = 0, n_models = 1, L = 0;
     const double *lay_press_pa = nullptr, *lay_temp = nullptr, *amount = nullptr;
     const double *taucont = nullptr, *tausca = nullptr, *phase = nullptr, *dtaucon = nullptr;
-    int ray_mode = 0;                       // != 0: the continuum has Rayleigh scattering, formed from the two arrays
-    const double *ray_totam = nullptr, *ray_f4 = nullptr;
-    // ansfm_cirsrad_ck_thermal_cont_dev, ansfm_cirsradg_ck_thermal_cont(_dev): the continuum is (TAUCIA + TAUDUST) + TAURAY (and
-    // its gradients dTAUCON) from the context's resident sources
-    int fused_cont = 0, use_cia = 0, use_dust = 0;
-    const double *lay_q = nullptr, *lay_frac = nullptr, *lay_delh = nullptr, *lay_cont = nullptr;   // the column: ray_totam
+    // the continuum formed inside the call.  fused_cont: (TAUCIA + TAUDUST) + TAURAY (the gradient entries: and dTAUCON; the
+    // single-scattering entries: and the scattering opacity and the phase functions) from the context's resident sources, as
+    // fused_cont_check left it; without it ray_mode, totam and f4 alone: Rayleigh scattering (ansfm_cirsrad_ck_thermal_ray_dev)
+    int fused_cont = 0;
+    ContCall cont;
+    // ansfm_cirsrad_ck_singlescatt_batch_cont / _src: the populations of phase_fn [W][P][ncont + 1] (host), or alpha_deg [P]
+    // (host) to form it from the resident phase-function source
+    int ncont = 0;
+    const double *phase_fn = nullptr, *alpha_deg = nullptr;
     int NVMR = 0, NPAR = 0;
     const int32_t *igas_map = nullptr;
     int P = 0, LIMAX = 0;
@@ -785,31 +787,24 @@ RtCall stage_call(ansfm_ctx *ctx, const RtCall &h, int *rc)
     d.EMISSIVITY = st.up(h.EMISSIVITY, W); d.SOLFLUX = st.up(h.SOLFLUX, W); d.REFLECTANCE = st.up(h.REFLECTANCE, W);
     d.BRDF = st.up(h.BRDF, W * h.P); d.SOL_ANG = st.up(h.SOL_ANG, h.P); d.EMISS_ANG = st.up(h.EMISS_ANG, h.P);
     d.xfac = st.up(h.xfac, W);
-    d.lay_q = st.up(h.lay_q, nl * h.NVMR); d.lay_frac = st.up(h.lay_frac, nl); d.ray_totam = st.up(h.ray_totam, nl);
-    d.lay_delh = st.up(h.lay_delh, nl); d.lay_cont = st.up(h.lay_cont, nl * ctx->dust_n); d.ray_f4 = st.up(h.ray_f4, nl * 4);
+    d.cont = stage_cont(st, h.cont, nl, d.lay_temp);
     *rc = st.rc;
     return d;
 }
 
 // Which (model, layer) opacities a forward call computes: all of them, or (a batch, with de-duplication on) the distinct ones;
-// the columns a call forms its continuum from (Rayleigh: the column and the composition; CIA: the mixing ratios, the para-H2
-// fraction, the column and the thickness; aerosols: their columns) are part of a layer's identity.  De-duplicating
-// synchronises.  Records the outcome for ansfm_last_layer_rows / ansfm_get_taugas.
+// the columns a call forms its continuum from (dedup_rows_cont; frac_always: its rule for the para-H2 fraction) are part of a
+// layer's identity.  De-duplicating synchronises.  Records the outcome for ansfm_last_layer_rows / ansfm_get_taugas.
 struct GasRows {
     DedupRows k;               // the rows handed to the merge kernel
     int n_k;                   // its view: n_k models of k.rows / n_k layers
     const int32_t *tau_slot;   // [n][L] row of every (model, layer), or nullptr: its own
 };
-int gas_rows(ansfm_ctx *ctx, const RtCall &c, GasRows *g)
+int gas_rows(ansfm_ctx *ctx, const RtCall &c, bool frac_always, GasRows *g)
 {
     *g = GasRows{DedupRows{c.n_models * c.L, c.lay_press_pa, c.lay_temp, c.amount}, c.n_models, nullptr};
     if (ctx->dedup && c.n_models > 1 && !ctx->lblrt) {
-        DedupCols x;
-        if (c.ray_mode || c.use_cia) x.add(c.ray_totam, 1);
-        if (c.ray_mode) x.add(c.ray_f4, 4);
-        if (c.use_cia) { x.add(c.lay_q, ctx->cia_NVMR); x.add(c.lay_frac, 1); x.add(c.lay_delh, 1); }
-        if (c.use_dust) x.add(c.lay_cont, ctx->dust_n);
-        const int rc = dedup_rows(ctx, c.n_models, c.L, c.lay_press_pa, c.lay_temp, c.amount, &x, &g->k);
+        const int rc = dedup_rows_cont(ctx, c.n_models, c.L, c.lay_press_pa, c.lay_temp, c.amount, c.cont, frac_always, &g->k);
         if (rc) return rc;
         g->n_k = 1;
         g->tau_slot = ctx->dd_slot.as<int32_t>();
@@ -850,7 +845,7 @@ extern "C" {
 /* ------------------------------------------------------------------------------------------ */
 /* fused CIRSrad (device pointers)                                                             */
 /* ------------------------------------------------------------------------------------------ */
-// c.ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); c.fused_cont:
+// c.cont.ray_mode: the continuum is Rayleigh scattering alone, of the computed rows (ansfm_cirsrad_ck_thermal_ray_dev); c.fused_cont:
 // CIA + aerosols + Rayleigh of the computed rows from the resident sources (ansfm_cirsrad_ck_thermal_cont_dev); c.rt_mode 1:
 // the path transmission (ansfm_cirsrad_ck_transmission); generic: the merge sorts every k-distribution first (the rerun of a
 // call whose table turned out not to be sorted in g)
@@ -866,24 +861,20 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c, bool gen
     HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     GasRows g;
     int rc;
-    if ((rc = gas_rows(ctx, c, &g))) return rc;        // the only synchronisation of this entry point (batches only)
+    if ((rc = gas_rows(ctx, c, true, &g))) return rc;  // the only synchronisation of this entry point (batches only)
     const int rows = g.k.rows;
     if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
     const double *cont_t = nullptr;
     if (c.fused_cont) {
         // CIA, aerosol and Rayleigh opacity of the rows that are computed, from the resident sources
-        ContCall k;
-        k.ISPACE = c.ISPACE; k.use_cia = c.use_cia; k.use_dust = c.use_dust; k.ray_mode = c.ray_mode;
-        k.temp = c.lay_temp; k.q = c.lay_q; k.frac = c.lay_frac; k.totam = c.ray_totam; k.delh = c.lay_delh; k.cont = c.lay_cont;
-        k.f4 = c.ray_f4;
-        if ((rc = launch_tau_cont_rows(ctx, rows, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, k))) return rc;
+        if ((rc = launch_tau_cont_rows(ctx, rows, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, c.cont))) return rc;
         cont_t = ctx->cont_t.as<double>();
-    } else if (c.ray_mode) {
+    } else if (c.cont.ray_mode) {
         // the Rayleigh continuum of the rows that are computed (the distinct layers of the batch), straight in the layout the RT
         // reads: the 201 states of a C3 Jacobian have 696 of them, not 20 100
         HIPCHK(ctx->cont_t.reserve((size_t)rows * Wpad * sizeof(double)));
-        launch_tau_rayleigh_rows(ctx, rows, c.ray_mode, c.ISPACE, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr,
-                                 c.ray_totam, c.ray_f4);
+        launch_tau_rayleigh_rows(ctx, rows, c.cont.ray_mode, c.ISPACE, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr,
+                                 c.cont.totam, c.cont.f4);
         HIPCHK(hipGetLastError());
         cont_t = ctx->cont_t.as<double>();
     } else if (c.taucont) {
@@ -899,7 +890,7 @@ static int cirsrad_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c, bool gen
     rt_params_of_call(ctx, c, r);
     r.tau_slot = g.tau_slot;
     r.cont = cont_t;
-    r.cont_by_row = ((c.ray_mode || c.fused_cont) && g.tau_slot) ? 1 : 0;
+    r.cont_by_row = ((c.cont.ray_mode || c.fused_cont) && g.tau_slot) ? 1 : 0;
     r.mode = c.rt_mode;
     HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
     rc = launch_rt(ctx, r, c.n_models);
@@ -937,7 +928,7 @@ int ansfm_cirsrad_ck_thermal_ray_dev(ansfm_ctx *ctx, int ISPACE, int n_models, i
         FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_ray_dev: bad argument (ray_mode = IRAY 1, 2, 4 or 12 for calc_tau_rayleighv)");
     RtCall c;
     c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
-    c.ray_mode = ray_mode; c.ray_totam = TOTAM; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    c.cont = ContCall{ISPACE, 0, 0, ray_mode, lay_temp, nullptr, nullptr, TOTAM, nullptr, nullptr, ray_mode == 4 ? f4 : nullptr};
     c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
     c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
     c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;
@@ -955,22 +946,12 @@ int ansfm_cirsrad_ck_thermal_cont_dev(ansfm_ctx *ctx, int ISPACE, int n_models, 
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad: upload a k-table first");
-    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
-        (!use_cia && !use_dust && !ray_mode) || ((use_cia || ray_mode) && !lay_totam) ||
-        (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont))
-        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: bad argument (at least one of use_cia, use_dust, ray_mode = IRAY 1, 2, "
-                                "4 or 12; the per-layer arrays of every term that is used)");
-    if (use_cia && !ctx->cia_on)
-        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: no CIA source on this table's grid (ansfm_upload_cia after the table)");
-    if (use_cia && ctx->cia_ispace != ISPACE)
-        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: the CIA source was uploaded for the other ISPACE");
-    if (use_dust && !ctx->dust_n)
-        FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_thermal_cont_dev: no aerosol source on this table's grid (ansfm_upload_dust after the table)");
     RtCall c;
+    const int rc = fused_cont_check(ctx, "cirsrad_ck_thermal_cont_dev: ", ISPACE, lay_temp, use_cia, lay_q, lay_frac, lay_totam, lay_delh,
+                                    use_dust, lay_cont, ray_mode, f4, ContNeed::any_term, &c.cont);
+    if (rc) return rc;
     c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
-    c.fused_cont = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0;
-    c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
-    c.ray_mode = ray_mode; c.ray_totam = lay_totam; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    c.fused_cont = 1;
     c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP;
     c.TSURF = TSURF; c.EMISSIVITY = EMISSIVITY; c.SOLFLUX = SOLFLUX; c.REFLECTANCE = REFLECTANCE; c.SOL_ANG = SOL_ANG;
     c.EMISS_ANG = EMISS_ANG; c.xfac = xfac; c.SPECOUT = SPECOUT;
@@ -1228,15 +1209,60 @@ int ansfm_singlescatt_plane_spectrum(ansfm_ctx *ctx, int ISPACE, int W, int G, i
 
 // CIRSrad's single-scattering branch for n_models states (host pointers; TSURF [n]): the gas opacities of the distinct (model,
 // layer) rows, then mode 2 of k_thermal_rt with the model axis -- the prefix records of state 0 when the batch is de-duplicated
+// ss_bad_args: what both implementations refuse alike about the arguments they share.  ss_gas_stage: the gas opacities of the
+// rows of the staged call d between ev[0] and ev[1] (frac_always: gas_rows').  ss_rt_stage: mode 2 of k_thermal_rt on the
+// continuum, the scattering opacity and the phase functions of s -- by_row: one row of them per gas row, else per (model, layer)
+// -- between ev[2] and ev[3], and SPECOUT [n][W][P] to the host; synchronises.
+static bool ss_bad_args(const RtCall &h)
+{
+    bool bad = h.n_models <= 0 || h.L <= 0 || h.P <= 0 || h.LIMAX <= 0 || !h.lay_press_pa || !h.lay_temp || !h.amount || !h.NLAYIN ||
+               !h.LAYINC || !h.SCALE || !h.EMTEMP || !h.TSURF || !h.SOLFLUX || !h.SOL_ANG || !h.EMISS_ANG || !h.SPECOUT ||
+               (h.ISPACE != 0 && h.ISPACE != 1);
+    for (int m = 0; !bad && m < h.n_models; ++m) bad = h.TSURF[m] > 0.0 && !h.EMISSIVITY;
+    return bad;
+}
+
+static int ss_gas_stage(ansfm_ctx *ctx, const RtCall &d, bool frac_always, GasRows *g)
+{
+    if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
+    int rc;
+    if ((rc = gas_rows(ctx, d, frac_always, g))) return rc;
+    const int rows = g->k.rows, n_k = g->n_k;
+    ctx->last_n = d.n_models; ctx->last_L = d.L;
+    if ((rc = gas_prep(ctx, rows, g->k.press, g->k.temp))) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    if (ctx->is_lbl) rc = gas_tau(ctx, n_k, rows / n_k, g->k.press, g->k.temp, g->k.amount, false);
+    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, n_k, rows / n_k, g->k.press, g->k.temp, g->k.amount, generic); });
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    return ANSFM_OK;
+}
+
+static int ss_rt_stage(ansfm_ctx *ctx, RtCall d, const GasRows &g, const SsContRows &s, bool by_row, double *SPECOUT)
+{
+    const size_t nout = (size_t)d.n_models * ctx->W * d.P * sizeof(double);
+    HIPCHK(ctx->tmp_out.reserve(nout));
+    d.SPECOUT = ctx->tmp_out.as<double>();
+    RtParams r;
+    rt_params_of_call(ctx, d, r);
+    r.tau_slot = g.tau_slot; r.cont = s.cont; r.sca = s.sca; r.phase = s.phase;
+    if (by_row) { r.cont_by_row = 1; r.ss_by_row = 1; r.rows = g.k.rows; }
+    r.mode = d.rt_mode;
+    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+    const int rc = launch_rt(ctx, r, d.n_models);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+    call_recorded(ctx, d.n_models, d.L);
+    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // also: the staged host arrays (TSURF of the single entry) are consumed
+    return ANSFM_OK;
+}
+
 static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const RtCall &h, const char *fn)
 {
     CHECK_CTX(ctx);
     if (!ctx->have_table) { ctx->err = std::string(fn) + ": upload a k-table first"; return ANSFM_ERR_NOTABLE; }
-    bool bad = h.n_models <= 0 || h.L <= 0 || h.P <= 0 || h.LIMAX <= 0 || !h.lay_press_pa || !h.lay_temp || !h.amount || !h.tausca ||
-               !h.phase || !h.NLAYIN || !h.LAYINC || !h.SCALE || !h.EMTEMP || !h.TSURF || !h.SOLFLUX || !h.SOL_ANG || !h.EMISS_ANG ||
-               !h.SPECOUT || (h.ISPACE != 0 && h.ISPACE != 1);
-    for (int m = 0; !bad && m < h.n_models; ++m) bad = h.TSURF[m] > 0.0 && !h.EMISSIVITY;
-    if (bad) { ctx->err = std::string(fn) + ": bad argument"; return ANSFM_ERR_INVALID; }
+    if (ss_bad_args(h) || !h.tausca || !h.phase) { ctx->err = std::string(fn) + ": bad argument"; return ANSFM_ERR_INVALID; }
     if ((size_t)h.n_models * h.P > 65535) { ctx->err = std::string(fn) + ": at most 65535 (model, path) pairs per call"; return ANSFM_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(ctx->device));
     const int W = ctx->W, Wpad = ctx->Wpad, n_models = h.n_models, L = h.L, P = h.P;
@@ -1244,17 +1270,8 @@ static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const RtCall &h, const ch
     int rc;
     RtCall d = stage_call(ctx, h, &rc);
     if (rc) return rc;
-    if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
     GasRows g;
-    if ((rc = gas_rows(ctx, d, &g))) return rc;
-    const int rows = g.k.rows;
-    ctx->last_n = n_models; ctx->last_L = L;
-    if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    if (ctx->is_lbl) rc = gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, false);
-    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, generic); });
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    if ((rc = ss_gas_stage(ctx, d, true, &g))) return rc;
     // reference layouts [n][W][L] -> [n][L][Wpad] (continuum, scattering opacity) and [n][P][W][L] -> [n][P][L][Wpad] (phase)
     const size_t LW = (size_t)L * Wpad;
     HIPCHK(ctx->cont_t.reserve(nl * Wpad * D));
@@ -1268,20 +1285,7 @@ static int cirsrad_ck_singlescatt_impl(ansfm_ctx *ctx, const RtCall &h, const ch
     launch_w_to_last(ctx->stream, (unsigned)n_models, d.tausca, sca_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
     launch_w_to_last(ctx->stream, (unsigned)(n_models * P), d.phase, ph_t, W, Wpad, 1, L, 0, 0.0, WL, LW);
     HIPCHK(hipGetLastError());
-    const size_t nout = (size_t)n_models * W * P * D;
-    HIPCHK(ctx->tmp_out.reserve(nout));
-    d.SPECOUT = ctx->tmp_out.as<double>();
-    RtParams r;
-    rt_params_of_call(ctx, d, r);
-    r.tau_slot = g.tau_slot; r.cont = cont_t; r.sca = sca_t; r.phase = ph_t;
-    r.mode = d.rt_mode;
-    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-    if ((rc = launch_rt(ctx, r, n_models))) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-    call_recorded(ctx, n_models, L);
-    HIPCHK(hipMemcpyAsync(h.SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));      // also: the staged host arrays (TSURF of the single entry) are consumed
-    return ANSFM_OK;
+    return ss_rt_stage(ctx, d, g, SsContRows{cont_t, sca_t, ph_t}, false, h.SPECOUT);
 }
 
 int ansfm_cirsrad_ck_singlescatt(ansfm_ctx *ctx, int ISPACE, int L, const double *lay_press_pa, const double *lay_temp,
@@ -1316,101 +1320,48 @@ int ansfm_cirsrad_ck_singlescatt_batch(ansfm_ctx *ctx, int ISPACE, int n_models,
 
 // The single-scattering batch with the continuum, the scattering opacity and the layer-mean phase functions formed per distinct
 // layer from the resident sources (k_ss_cont_rows) and read by row (the SS == 2 builds of k_thermal_rt): the stages of
-// cirsrad_ck_singlescatt_impl, one row map for gas opacities and continuum
-// phase_fn [W][P][ncont + 1] from the host, or alpha_deg [P]: formed in its buffer from the resident phase-function source
-// (ansfm_cirsrad_ck_singlescatt_batch_src); what = the entry's name
-static int cirsrad_ck_singlescatt_cont_impl(ansfm_ctx *ctx, const char *what, int ISPACE, int n_models, int L,
-                                            const double *lay_press_pa, const double *lay_temp, const double *amount, int use_cia,
-                                            const double *lay_q, const double *lay_frac, const double *lay_totam, const double *lay_delh,
-                                            int use_dust, const double *lay_cont, int ray_mode, const double *f4, int ncont,
-                                            const double *phase_fn, const double *alpha_deg, int P, int LIMAX, const int32_t *NLAYIN,
-                                            const int32_t *LAYINC, const double *SCALE, const double *EMTEMP, const double *TSURF,
-                                            const double *EMISSIVITY, const double *BRDF, const double *SOLFLUX, const double *SOL_ANG,
-                                            const double *EMISS_ANG, const double *xfac, double *SPECOUT)
+// cirsrad_ck_singlescatt_impl, one row map for gas opacities and continuum.  h.cont: the nine arguments as the entry took them
+// (checked here); h.phase_fn [W][P][ncont + 1] from the host, or h.alpha_deg [P]: formed in its buffer from the resident
+// phase-function source (ansfm_cirsrad_ck_singlescatt_batch_src); what = the entry's name
+static int cirsrad_ck_singlescatt_cont_impl(ansfm_ctx *ctx, RtCall h, const char *what)
 {
     const std::string fn = std::string(what) + ": ";
+    const int P = h.P, ncont = h.ncont;
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
-    bool bad = n_models <= 0 || L <= 0 || P <= 0 || LIMAX <= 0 || !lay_press_pa || !lay_temp || !amount || !NLAYIN || !LAYINC || !SCALE ||
-               !EMTEMP || !TSURF || !SOLFLUX || !SOL_ANG || !EMISS_ANG || !SPECOUT || (ISPACE != 0 && ISPACE != 1);
-    for (int m = 0; !bad && m < n_models; ++m) bad = TSURF[m] > 0.0 && !EMISSIVITY;
-    if (bad) FAIL(ANSFM_ERR_INVALID, fn + "bad argument");
-    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
-        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont) || (!phase_fn && !alpha_deg))
-        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (ray_mode = IRAY 0, 1, 2, 4 or 12; the per-layer arrays of every term that is used; phase_fn)");
-    if (!use_dust && !ray_mode) FAIL(ANSFM_ERR_INVALID, fn + "neither aerosols nor Rayleigh scattering: no scattering opacity");
-    if (use_cia && !ctx->cia_on) FAIL(ANSFM_ERR_INVALID, fn + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
-    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, fn + "the CIA source was uploaded for the other ISPACE");
-    if (use_dust && !ctx->dust_n) FAIL(ANSFM_ERR_INVALID, fn + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    if (ss_bad_args(h) || (!h.phase_fn && !h.alpha_deg)) FAIL(ANSFM_ERR_INVALID, fn + "bad argument");
+    const ContCall a = h.cont;
+    int rc = fused_cont_check(ctx, fn, h.ISPACE, h.lay_temp, a.use_cia, a.q, a.frac, a.totam, a.delh, a.use_dust, a.cont, a.ray_mode, a.f4,
+                              ContNeed::scatterer, &h.cont);
+    if (rc) return rc;
     if (ncont > 7) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "more than 7 aerosol populations (NumPy sums 8 and more pairwise, the kernel sums in order)");
-    if (ncont != (use_dust ? ctx->dust_n : 0))
+    if (ncont != (a.use_dust ? ctx->dust_n : 0))
         FAIL(ANSFM_ERR_INVALID, fn + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
-                                    std::to_string(use_dust ? ctx->dust_n : 0) + " populations");
-    if ((size_t)n_models * P > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "at most 65535 (model, path) pairs per call");
-    int rc;
-    if (alpha_deg && ((rc = phase_source_check(ctx, fn, ncont)) || (rc = phase_source_angles(ctx, fn, P, alpha_deg)))) return rc;
+                                    std::to_string(a.use_dust ? ctx->dust_n : 0) + " populations");
+    if ((size_t)h.n_models * P > 65535) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "at most 65535 (model, path) pairs per call");
+    if (h.alpha_deg && ((rc = phase_source_check(ctx, fn, ncont)) || (rc = phase_source_angles(ctx, fn, P, h.alpha_deg)))) return rc;
     for (int ip = 0; ip < P; ++ip) {                                 // the RT kernel indexes the layers with these
-        if (NLAYIN[ip] < 1 || NLAYIN[ip] > LIMAX) FAIL(ANSFM_ERR_INVALID, fn + "NLAYIN outside 1 .. LIMAX");
-        for (int j = 0; j < NLAYIN[ip]; ++j)
-            if (LAYINC[(size_t)j * P + ip] < 0 || LAYINC[(size_t)j * P + ip] >= L) FAIL(ANSFM_ERR_INVALID, fn + "LAYINC entry outside the layer range");
+        if (h.NLAYIN[ip] < 1 || h.NLAYIN[ip] > h.LIMAX) FAIL(ANSFM_ERR_INVALID, fn + "NLAYIN outside 1 .. LIMAX");
+        for (int j = 0; j < h.NLAYIN[ip]; ++j)
+            if (h.LAYINC[(size_t)j * P + ip] < 0 || h.LAYINC[(size_t)j * P + ip] >= h.L) FAIL(ANSFM_ERR_INVALID, fn + "LAYINC entry outside the layer range");
     }
     HIPCHK(hipSetDevice(ctx->device));
-    RtCall h;
-    h.ISPACE = ISPACE; h.n_models = n_models; h.L = L; h.lay_press_pa = lay_press_pa; h.lay_temp = lay_temp; h.amount = amount;
-    h.fused_cont = 1; h.use_cia = use_cia ? 1 : 0; h.use_dust = use_dust ? 1 : 0; h.NVMR = use_cia ? ctx->cia_NVMR : 0;
-    h.lay_q = use_cia ? lay_q : nullptr; h.lay_frac = use_cia ? lay_frac : nullptr; h.lay_delh = use_cia ? lay_delh : nullptr;
-    h.lay_cont = use_dust ? lay_cont : nullptr;
-    h.ray_mode = ray_mode; h.ray_totam = (use_cia || ray_mode) ? lay_totam : nullptr; h.ray_f4 = ray_mode == 4 ? f4 : nullptr;
-    h.P = P; h.LIMAX = LIMAX; h.NLAYIN = NLAYIN; h.LAYINC = LAYINC; h.SCALE = SCALE; h.EMTEMP = EMTEMP; h.TSURF = TSURF;
-    h.EMISSIVITY = EMISSIVITY; h.BRDF = BRDF; h.SOLFLUX = SOLFLUX; h.SOL_ANG = SOL_ANG; h.EMISS_ANG = EMISS_ANG; h.xfac = xfac;
-    h.SPECOUT = SPECOUT; h.rt_mode = 2;
-    const int W = ctx->W;
     RtCall d = stage_call(ctx, h, &rc);
     if (rc) return rc;
+    const size_t npf = (size_t)ctx->W * P * (ncont + 1) * sizeof(double);
     const void *pf_dev = nullptr;
-    if (alpha_deg) {                                            // phase_fn stays in HBM
-        HIPCHK(ctx->ss_phase_fn.reserve((size_t)W * P * (ncont + 1) * sizeof(double)));
-        if ((rc = launch_phase_source(ctx, P, alpha_deg, nullptr, 1, ctx->ss_phase_fn.as<double>()))) return rc;
+    if (h.alpha_deg) {                                          // phase_fn stays in HBM
+        HIPCHK(ctx->ss_phase_fn.reserve(npf));
+        if ((rc = launch_phase_source(ctx, P, h.alpha_deg, nullptr, 1, ctx->ss_phase_fn.as<double>()))) return rc;
         pf_dev = ctx->ss_phase_fn.p;
-    } else if ((rc = h2d(ctx, ctx->ss_phase_fn, phase_fn, (size_t)W * P * (ncont + 1) * sizeof(double), &pf_dev)))
+    } else if ((rc = h2d(ctx, ctx->ss_phase_fn, h.phase_fn, npf, &pf_dev)))
         return rc;
-    if (!ctx->is_lbl) HIPCHK(hipMemsetAsync(ctx->d_flag.as<int>() + 1, 0, sizeof(int), ctx->stream));
-    ContCall k;
-    k.ISPACE = ISPACE; k.use_cia = d.use_cia; k.use_dust = d.use_dust; k.ray_mode = ray_mode;
-    k.temp = d.lay_temp; k.q = d.lay_q; k.frac = d.lay_frac; k.totam = d.ray_totam; k.delh = d.lay_delh; k.cont = d.lay_cont; k.f4 = d.ray_f4;
-    GasRows g{DedupRows{n_models * L, d.lay_press_pa, d.lay_temp, d.amount}, n_models, nullptr};
-    if (ctx->dedup && n_models > 1 && !ctx->lblrt) {
-        if ((rc = dedup_rows_cont(ctx, n_models, L, d.lay_press_pa, d.lay_temp, d.amount, k, &g.k))) return rc;
-        g.n_k = 1;
-        g.tau_slot = ctx->dd_slot.as<int32_t>();
-    }
-    const int rows = g.k.rows;
-    ctx->last_rows = rows; ctx->last_dedup = g.tau_slot != nullptr;
-    ctx->last_n = n_models; ctx->last_L = L;
-    if ((rc = gas_prep(ctx, rows, g.k.press, g.k.temp))) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    if (ctx->is_lbl) rc = gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, false);
-    else rc = rerun_unsorted(ctx, [&](bool generic) { return gas_tau(ctx, g.n_k, rows / g.n_k, g.k.press, g.k.temp, g.k.amount, generic); });
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    GasRows g;
+    if ((rc = ss_gas_stage(ctx, d, false, &g))) return rc;
     SsContRows sr;
-    if ((rc = launch_ss_cont_rows(ctx, rows, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, k, P,
+    if ((rc = launch_ss_cont_rows(ctx, g.k.rows, g.tau_slot ? ctx->dd_work.as<int32_t>() : (const int32_t *)nullptr, d.cont, P,
                                   static_cast<const double *>(pf_dev), &sr)))
         return rc;
-    const size_t nout = (size_t)n_models * W * P * sizeof(double);
-    HIPCHK(ctx->tmp_out.reserve(nout));
-    d.SPECOUT = ctx->tmp_out.as<double>();
-    RtParams r;
-    rt_params_of_call(ctx, d, r);
-    r.tau_slot = g.tau_slot; r.cont = sr.cont; r.sca = sr.sca; r.phase = sr.phase;
-    r.cont_by_row = 1; r.ss_by_row = 1; r.rows = rows;
-    r.mode = 2;
-    HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
-    if ((rc = launch_rt(ctx, r, n_models))) return rc;
-    HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
-    call_recorded(ctx, n_models, L);
-    HIPCHK(hipMemcpyAsync(SPECOUT, ctx->tmp_out.p, nout, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return ANSFM_OK;
+    return ss_rt_stage(ctx, d, g, sr, true, h.SPECOUT);
 }
 
 int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models, int L, const double *lay_press_pa,
@@ -1423,10 +1374,14 @@ int ansfm_cirsrad_ck_singlescatt_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_mo
                                             double *SPECOUT)
 {
     CHECK_CTX(ctx);
-    return cirsrad_ck_singlescatt_cont_impl(ctx, "cirsrad_ck_singlescatt_batch_cont", ISPACE, n_models, L, lay_press_pa, lay_temp, amount,
-                                            use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4, ncont,
-                                            phase_fn, nullptr, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX,
-                                            SOL_ANG, EMISS_ANG, xfac, SPECOUT);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.fused_cont = 1; c.cont = ContCall{ISPACE, use_cia, use_dust, ray_mode, lay_temp, lay_q, lay_frac, lay_totam, lay_delh, lay_cont, f4};
+    c.ncont = ncont; c.phase_fn = phase_fn;
+    c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF;
+    c.EMISSIVITY = EMISSIVITY; c.BRDF = BRDF; c.SOLFLUX = SOLFLUX; c.SOL_ANG = SOL_ANG; c.EMISS_ANG = EMISS_ANG; c.xfac = xfac;
+    c.SPECOUT = SPECOUT; c.rt_mode = 2;
+    return cirsrad_ck_singlescatt_cont_impl(ctx, c, "cirsrad_ck_singlescatt_batch_cont");
 }
 
 // The same with phase_fn formed on the device: the populations from the resident phase-function source (ansfm_upload_phase) at
@@ -1442,10 +1397,14 @@ int ansfm_cirsrad_ck_singlescatt_batch_src(ansfm_ctx *ctx, int ISPACE, int n_mod
 {
     CHECK_CTX(ctx);
     if (!alpha_deg) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_singlescatt_batch_src: bad argument (alpha_deg)");
-    return cirsrad_ck_singlescatt_cont_impl(ctx, "cirsrad_ck_singlescatt_batch_src", ISPACE, n_models, L, lay_press_pa, lay_temp, amount,
-                                            use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4, ncont,
-                                            nullptr, alpha_deg, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX,
-                                            SOL_ANG, EMISS_ANG, xfac, SPECOUT);
+    RtCall c;
+    c.ISPACE = ISPACE; c.n_models = n_models; c.L = L; c.lay_press_pa = lay_press_pa; c.lay_temp = lay_temp; c.amount = amount;
+    c.fused_cont = 1; c.cont = ContCall{ISPACE, use_cia, use_dust, ray_mode, lay_temp, lay_q, lay_frac, lay_totam, lay_delh, lay_cont, f4};
+    c.ncont = ncont; c.alpha_deg = alpha_deg;
+    c.P = P; c.LIMAX = LIMAX; c.NLAYIN = NLAYIN; c.LAYINC = LAYINC; c.SCALE = SCALE; c.EMTEMP = EMTEMP; c.TSURF = TSURF;
+    c.EMISSIVITY = EMISSIVITY; c.BRDF = BRDF; c.SOLFLUX = SOLFLUX; c.SOL_ANG = SOL_ANG; c.EMISS_ANG = EMISS_ANG; c.xfac = xfac;
+    c.SPECOUT = SPECOUT; c.rt_mode = 2;
+    return cirsrad_ck_singlescatt_cont_impl(ctx, c, "cirsrad_ck_singlescatt_batch_src");
 }
 
 int ansfm_thermal_emission_g(ansfm_ctx *ctx, int ISPACE, int W, int G, int NPAR, int NLAYIN, const double *WAVE,
@@ -1568,15 +1527,9 @@ static int cirsradg_ck_thermal_dev_impl(ansfm_ctx *ctx, const RtCall &c)
     HIPCHK(ctx->dspec_i.reserve((size_t)n_models * P * NPAR * LIMAX * Wpad * sizeof(double)));
     int rc;
     const double *cont_t = nullptr, *dcont_t = nullptr;
-    ContCall k;
-    if (c.fused_cont) {
-        // CIA, aerosol and Rayleigh opacity of every layer and their gradients, from the resident sources
-        k.ISPACE = c.ISPACE; k.use_cia = c.use_cia; k.use_dust = c.use_dust; k.ray_mode = c.ray_mode;
-        k.temp = c.lay_temp; k.q = c.lay_q; k.frac = c.lay_frac; k.totam = c.ray_totam; k.delh = c.lay_delh; k.cont = c.lay_cont;
-        k.f4 = c.ray_f4;
-    }
+    // c.fused_cont: CIA, aerosol and Rayleigh opacity of every layer and their gradients, from the resident sources
     if ((rc = grad_gas_stage(ctx, n_models, L, c.lay_press_pa, c.lay_temp, c.amount, c.taucont, c.dtaucon, NPAR, &cont_t, &dcont_t,
-                             c.fused_cont ? &k : nullptr, c.NVMR)))
+                             c.fused_cont ? &c.cont : nullptr, c.NVMR)))
         return rc;
     RtGParams q;
     memset(&q, 0, sizeof q);
@@ -1641,30 +1594,20 @@ static int grad_fused_cont(ansfm_ctx *ctx, RtCall &c, int use_cia, const double 
         FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: a shared gas gradient (ansfm_set_shared_gas_gradient) is pending; the "
                                 "fused continuum forms the Rayleigh term itself (ray_mode).  It has been cancelled.");
     }
-    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
-        (!use_cia && !use_dust && !ray_mode) || ((use_cia || ray_mode) && !lay_totam) ||
-        (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont) || c.NVMR < 0 || c.NPAR < c.NVMR + 2)
-        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: bad argument (at least one of use_cia, use_dust, ray_mode = IRAY 1, 2, 4 "
-                                "or 12; the per-layer arrays of every term that is used; NPAR >= NVMR + 2)");
+    const int rc = fused_cont_check(ctx, "cirsradg_ck_thermal_cont: ", c.ISPACE, c.lay_temp, use_cia, lay_q, lay_frac, lay_totam, lay_delh,
+                                    use_dust, lay_cont, ray_mode, f4, ContNeed::any_term, &c.cont);
+    if (rc) return rc;
+    if (c.NVMR < 0 || c.NPAR < c.NVMR + 2) FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: bad argument (NPAR >= NVMR + 2)");
     if (c.NVMR + 2 > ANSFM_MAX_CONT_GRAD_SLOTS)
         FAIL(ANSFM_ERR_UNSUPPORTED, "cirsradg_ck_thermal_cont: NVMR + 2 <= " + std::to_string(ANSFM_MAX_CONT_GRAD_SLOTS) +
                                         " (the gradient slots of a thread are held in LDS)");
-    if (use_cia && !ctx->cia_on)
-        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: no CIA source on this table's grid (ansfm_upload_cia after the table)");
-    if (use_cia && ctx->cia_ispace != c.ISPACE)
-        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: the CIA source was uploaded for the other ISPACE");
     if (use_cia && (c.NVMR != ctx->cia_NVMR || c.NVMR < 2))
         FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: NVMR is not the number of gases the CIA source was uploaded for (" +
                                     std::to_string(ctx->cia_NVMR) + "; at least 2: calc_tau_cia writes slot NVMR - 2)");
-    if (use_dust && !ctx->dust_n)
-        FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: no aerosol source on this table's grid (ansfm_upload_dust after the table)");
     if (use_dust && c.NPAR != c.NVMR + 2 + ctx->dust_n)
         FAIL(ANSFM_ERR_INVALID, "cirsradg_ck_thermal_cont: NPAR is not NVMR + 2 + NDUST of the uploaded aerosol source (" +
                                     std::to_string(ctx->dust_n) + " populations)");
-    c.fused_cont = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0;
-    c.lay_q = use_cia ? lay_q : nullptr; c.lay_frac = use_cia ? lay_frac : nullptr; c.lay_delh = use_cia ? lay_delh : nullptr;
-    c.lay_cont = use_dust ? lay_cont : nullptr;
-    c.ray_mode = ray_mode; c.ray_totam = (use_cia || ray_mode) ? lay_totam : nullptr; c.ray_f4 = ray_mode == 4 ? f4 : nullptr;
+    c.fused_cont = 1;
     return ANSFM_OK;
 }
 

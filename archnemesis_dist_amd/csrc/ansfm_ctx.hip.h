@@ -276,17 +276,40 @@ int dedup_rows(ansfm_ctx *ctx, int n, int L, const double *press, const double *
 // a table has been uploaded: the continuum sources on the old grid go (dust_n = 0: kext_w and ksca_w alike), and the
 // phase-function source with them
 inline void clear_continuum_sources(ansfm_ctx *ctx) { ctx->cia_on = 0; ctx->dust_n = 0; ctx->phase_n = 0; }
-// a continuum formed from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust) and the Rayleigh
-// parametrisations: the arrays are device pointers over the n * L layers of the call
+// A continuum formed from the context's resident sources (ansfm_upload_cia, ansfm_upload_dust) and the Rayleigh
+// parametrisations: the one record of the arguments use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode
+// and f4 of include/ansfm.h, with the layer temperatures the CIA reads.  RtCall and MsCall carry it with the caller's
+// pointers, a staged copy and the launchers with device pointers over the n * L layers of the call; an array whose term is
+// off is null.  (An entry that checks the arguments further down brace-initialises it: the order of the fields stays.)
 struct ContCall {
     int ISPACE = 0, use_cia = 0, use_dust = 0, ray_mode = 0;
     const double *temp = nullptr, *q = nullptr, *frac = nullptr, *totam = nullptr, *delh = nullptr, *cont = nullptr, *f4 = nullptr;
 };
+// ansfm_ops.hip: what every entry with a fused continuum refuses about those arguments, ANSFM_ERR_INVALID each -- a ray_mode
+// other than IRAY 0, 1, 2, 4 or 12 (calc_tau_rayleighv), mode 4 without f4, a term without its arrays, a term that `need`
+// asks for and the call leaves off, CIA without a resident source or with one of the other ISPACE, aerosols without a
+// resident source -- and the record of a call that passes.  fn: the entry's name and ": ".
+enum class ContNeed {
+    any_term,    // thermal forward and gradient, ansfm_cirsrad_ck_scatter_batch_cont: something must form a continuum
+    scatterer,   // single scattering: aerosols or Rayleigh scattering, or nothing scatters
+    aerosols     // ansfm_cirsrad_ck_scatter_batch_src: the phase functions are those of the aerosol populations
+};
+int fused_cont_check(ansfm_ctx *ctx, const std::string &fn, int ISPACE, const double *lay_temp, int use_cia, const double *lay_q,
+                     const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust, const double *lay_cont,
+                     int ray_mode, const double *f4, ContNeed need, ContCall *out);
+// the record of model m of a batch of L layers each
+inline ContCall cont_of_model(const ansfm_ctx *ctx, ContCall c, size_t m, int L)
+{
+    const auto at = [&](const double *&a, size_t width) { if (a) a += m * L * width; };
+    at(c.temp, 1); at(c.q, ctx->cia_NVMR); at(c.frac, 1); at(c.totam, 1); at(c.delh, 1); at(c.cont, ctx->dust_n); at(c.f4, 4);
+    return c;
+}
 // ansfm_api.hip: dedup_rows with the columns the continuum of c is formed from as part of a layer's identity -- the column
-// (CIA, Rayleigh), the Rayleigh composition (ray_mode 4), the mixing ratios and the thickness (CIA), the para-H2 fraction (a
-// CIA table with a para-H2 axis) and the aerosol columns
+// (CIA, Rayleigh), the Rayleigh composition (ray_mode 4), the mixing ratios and the thickness (CIA), the para-H2 fraction and
+// the aerosol columns.  frac_always: the para-H2 fraction counts whenever CIA is on (the thermal route); otherwise only where
+// cia_layer reads it, a table with a para-H2 axis (the scattering routes)
 int dedup_rows_cont(ansfm_ctx *ctx, int n, int L, const double *press, const double *temp, const double *amount, const ContCall &c,
-                    DedupRows *out);
+                    bool frac_always, DedupRows *out);
 // ansfm_api.hip, what the gradient RT entries and the transit entry (ansfm_transit.hip) share (described where they are
 // defined): the gas stage of a gradient call, the merge slot behind every parameter, the end of a call without a generic rerun
 int grad_gas_stage(ansfm_ctx *ctx, int n_models, int L, const double *lay_press_pa, const double *lay_temp, const double *amount,
@@ -397,5 +420,16 @@ struct Stager {
         return static_cast<const T *>(d);
     }
 };
+
+// The per-layer arrays of a fused continuum through the next six buffers of st, in this order: the record returned has the
+// device copies of h's host arrays over nl = n * L layers and d_temp, the staged layer temperatures, in their place
+inline ContCall stage_cont(Stager &st, ContCall h, size_t nl, const double *d_temp)
+{
+    const ansfm_ctx *ctx = st.ctx;
+    h.temp = d_temp;
+    h.q = st.up(h.q, nl * ctx->cia_NVMR); h.frac = st.up(h.frac, nl); h.totam = st.up(h.totam, nl);
+    h.delh = st.up(h.delh, nl); h.cont = st.up(h.cont, nl * ctx->dust_n); h.f4 = st.up(h.f4, nl * 4);
+    return h;
+}
 
 }  // namespace ansfm

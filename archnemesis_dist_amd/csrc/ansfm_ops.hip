@@ -16,6 +16,33 @@ void ansfm::launch_tau_rayleigh_rows(ansfm_ctx *ctx, int rows, int ray_mode, int
                        ray_mode, ISPACE, ctx->d_wave.as<double>(), slot_rows, ray_totam, ray_f4, ctx->cont_t.as<double>());
 }
 
+int ansfm::fused_cont_check(ansfm_ctx *ctx, const std::string &fn, int ISPACE, const double *lay_temp, int use_cia,
+                            const double *lay_q, const double *lay_frac, const double *lay_totam, const double *lay_delh, int use_dust,
+                            const double *lay_cont, int ray_mode, const double *f4, ContNeed need, ContCall *out)
+{
+    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
+        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont))
+        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (ray_mode = IRAY 0, 1, 2, 4 or 12, f4 with IRAY 4; the per-layer arrays of every "
+                                     "term that is used)");
+    if (need == ContNeed::any_term && !use_cia && !use_dust && !ray_mode)
+        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (at least one of use_cia, use_dust, ray_mode)");
+    if (need == ContNeed::scatterer && !use_dust && !ray_mode)
+        FAIL(ANSFM_ERR_INVALID, fn + "neither aerosols nor Rayleigh scattering: no scattering opacity");
+    if (need == ContNeed::aerosols && !use_dust)
+        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (use_dust: the phase functions are those of the aerosol populations)");
+    if (use_cia && !ctx->cia_on) FAIL(ANSFM_ERR_INVALID, fn + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
+    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, fn + "the CIA source was uploaded for the other ISPACE");
+    if (use_dust && !ctx->dust_n) FAIL(ANSFM_ERR_INVALID, fn + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    ContCall &c = *out;
+    c.ISPACE = ISPACE; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0; c.ray_mode = ray_mode;
+    c.temp = lay_temp;
+    c.q = use_cia ? lay_q : nullptr; c.frac = use_cia ? lay_frac : nullptr; c.delh = use_cia ? lay_delh : nullptr;
+    c.totam = (use_cia || ray_mode) ? lay_totam : nullptr;
+    c.cont = use_dust ? lay_cont : nullptr;
+    c.f4 = ray_mode == 4 ? f4 : nullptr;
+    return ANSFM_OK;
+}
+
 // The arguments of k_cia_rows_prep / k_tau_cont_rows / k_dtau_cont_rows for `rows` rows of the call c, from the context's
 // resident sources; reserves the rows' CIA records
 static int cont_rows_params(ansfm_ctx *ctx, int rows, const int32_t *slot_rows, const ContCall &c, ContRowsParams &p)

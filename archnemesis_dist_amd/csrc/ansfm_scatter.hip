@@ -54,9 +54,9 @@ struct MsCall {
     // tauray / tauscat are then [R][W] and lfrac [R][ncont][W].  cont_row = nullptr: the dense arrays
     int R; const int32_t *cont_row;
     // the continuum formed inside the call from the context's resident sources, once per distinct layer
-    // (ansfm_cirsrad_ck_scatter_batch_cont): the per-layer arrays [n][L] / [n][L][NVMR | ncont | 4] behind it, host pointers;
-    // taucia .. tauscat, lfrac and cont_row are null
-    int fused, use_cia, use_dust, ray_mode; const double *lay_q, *lay_frac, *lay_totam, *lay_delh, *lay_cont, *f4;
+    // (ansfm_cirsrad_ck_scatter_batch_cont): the per-layer arrays [n][L] / [n][L][NVMR | ncont | 4] behind it, host pointers,
+    // as fused_cont_check left them; taucia .. tauscat, lfrac and cont_row are null
+    int fused; ContCall cont;
     // phasarr formed on the device from the resident phase-function source (ansfm_cirsrad_ck_scatter_batch_src): Scatter.THETA
     // in degrees and its cosines [nth], host pointers; phasarr is null
     const double *theta_deg, *mu_theta;
@@ -472,16 +472,11 @@ static int ms_stage(ansfm_ctx *ctx, const MsCall &c, size_t CN, MsStaged &s)
 }
 
 // The per-layer arrays of a fused continuum (c.fused) on the device, staging slots 14 .. 19, as the continuum kernels take them
-// (ContCall); d_temp: the staged layer temperatures [n][L].  An array whose term is not used stays null.
+// (stage_cont); d_temp: the staged layer temperatures [n][L].  An array whose term is not used stays null.
 static int ms_stage_cont(ansfm_ctx *ctx, const MsCall &c, const double *d_temp, ContCall &k)
 {
-    const size_t nl = (size_t)c.n_models * c.L;
     Stager st{ctx, 14};
-    k.ISPACE = c.ISPACE; k.use_cia = c.use_cia; k.use_dust = c.use_dust; k.ray_mode = c.ray_mode;
-    k.temp = d_temp;
-    k.q = st.up(c.use_cia ? c.lay_q : nullptr, nl * ctx->cia_NVMR); k.frac = st.up(c.use_cia ? c.lay_frac : nullptr, nl);
-    k.totam = st.up(c.use_cia || c.ray_mode ? c.lay_totam : nullptr, nl); k.delh = st.up(c.use_cia ? c.lay_delh : nullptr, nl);
-    k.cont = st.up(c.use_dust ? c.lay_cont : nullptr, nl * ctx->dust_n); k.f4 = st.up(c.ray_mode == 4 ? c.f4 : nullptr, nl * 4);
+    k = stage_cont(st, c.cont, (size_t)c.n_models * c.L, d_temp);
     return st.rc;
 }
 
@@ -618,14 +613,8 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
         if (ctx->lblrt) ctx->st_m0 = m;                      // gas_tau reads this model's rows of the state
         if (by_rows) {
             if (fused) {
-                ContCall km = k;                                // this model's layers
-                km.temp += mm * L;
-                if (km.q) km.q += mm * L * ctx->cia_NVMR;
-                for (const double **a : {&km.frac, &km.totam, &km.delh}) if (*a) *a += mm * L;
-                if (km.cont) km.cont += mm * L * ctx->dust_n;
-                if (km.f4) km.f4 += mm * L * 4;
-                MsContRows rw;
-                if ((rc = launch_ms_cont_rows(ctx, L, nullptr, km, &rw))) return rc;
+                MsContRows rw;                                  // this model's layers
+                if ((rc = launch_ms_cont_rows(ctx, L, nullptr, cont_of_model(ctx, k, mm, L), &rw))) return rc;
                 rsrc[0] = rw.cia; rsrc[1] = rw.dust; rsrc[2] = rw.ray; rsrc[3] = rw.sca; rsrc[4] = rw.lf;
             }
             const double *dense[5];
@@ -889,7 +878,7 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
         // one map for both: a layer is distinct when it differs from model 0's in a gas input or in a column the continuum is
         // formed from; the continuum of the distinct rows comes from the resident sources and the row map is the gas rows'
         MsContRows rw;
-        if ((rc = dedup_rows_cont(ctx, n_models, L, s.press, s.temp, s.am, fc, &k)) ||
+        if ((rc = dedup_rows_cont(ctx, n_models, L, s.press, s.temp, s.am, fc, false, &k)) ||
             (rc = launch_ms_cont_rows(ctx, k.rows, ctx->dd_work.as<int32_t>(), fc, &rw)))
             return rc;
         s.cia = rw.cia; s.dust = rw.dust; s.ray = rw.ray; s.sca = rw.sca; s.lf = rw.lf;
@@ -975,29 +964,19 @@ int ansfm_cirsrad_ck_scatter_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models
                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
 {
     CHECK_CTX(ctx);
-    const char *fn = "cirsrad_ck_scatter_batch_cont: ";
-    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, std::string(fn) + "upload a k-table first");
+    const std::string fn = "cirsrad_ck_scatter_batch_cont: ";
+    if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
     if (w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
-        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
-    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
-        (!use_cia && !use_dust && !ray_mode) || ((use_cia || ray_mode) && !lay_totam) ||
-        (use_cia && (!lay_q || !lay_frac || !lay_delh)) || (use_dust && !lay_cont))
-        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "bad argument (at least one of use_cia, use_dust, ray_mode = IRAY 1, 2, 4 or 12; the "
-                                                  "per-layer arrays of every term that is used)");
-    if (use_cia && !ctx->cia_on)
-        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
-    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, std::string(fn) + "the CIA source was uploaded for the other ISPACE");
-    if (use_dust && !ctx->dust_n)
-        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
-    if (ncont != (use_dust ? ctx->dust_n : 0))
-        FAIL(ANSFM_ERR_INVALID, std::string(fn) + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
-                                    std::to_string(use_dust ? ctx->dust_n : 0) + " populations");
+        FAIL(ANSFM_ERR_INVALID, fn + "the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
     MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, nullptr, nullptr, nullptr, ncont, nth, phasarr, nullptr,
              radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT,
-             nullptr, W_full, w_begin, 0, nullptr};
-    c.fused = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = use_dust ? 1 : 0; c.ray_mode = ray_mode;
-    c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_totam = lay_totam; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
-    c.f4 = ray_mode == 4 ? f4 : nullptr;
+             nullptr, W_full, w_begin, 0, nullptr, 1};
+    const int rc = fused_cont_check(ctx, fn, ISPACE, lay_temp, use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode,
+                                    f4, ContNeed::any_term, &c.cont);
+    if (rc) return rc;
+    if (ncont != (use_dust ? ctx->dust_n : 0))
+        FAIL(ANSFM_ERR_INVALID, fn + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
+                                    std::to_string(use_dust ? ctx->dust_n : 0) + " populations");
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 
@@ -1016,29 +995,21 @@ int ansfm_cirsrad_ck_scatter_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models,
     if (W_full != ctx->W || w_begin != 0)
         FAIL(ANSFM_ERR_UNSUPPORTED, fn + "the whole axis only (a slice's context does not hold the grid the source lives on)");
     if (!theta_deg || !mu_theta || nth < 3) FAIL(ANSFM_ERR_INVALID, fn + "bad argument (theta_deg, mu_theta [nth], nth >= 3)");
-    if ((ray_mode != 0 && ray_mode != 1 && ray_mode != 2 && ray_mode != 4 && ray_mode != 12) || (ray_mode == 4 && !f4) ||
-        ((use_cia || ray_mode) && !lay_totam) || (use_cia && (!lay_q || !lay_frac || !lay_delh)) || !use_dust || !lay_cont)
-        FAIL(ANSFM_ERR_INVALID, fn + "bad argument (use_dust with lay_cont; ray_mode = IRAY 0, 1, 2, 4 or 12; the per-layer arrays of "
-                                     "every term that is used)");
-    if (use_cia && !ctx->cia_on) FAIL(ANSFM_ERR_INVALID, fn + "no CIA source on this table's grid (ansfm_upload_cia after the table)");
-    if (use_cia && ctx->cia_ispace != ISPACE) FAIL(ANSFM_ERR_INVALID, fn + "the CIA source was uploaded for the other ISPACE");
-    if (!ctx->dust_n) FAIL(ANSFM_ERR_INVALID, fn + "no aerosol source on this table's grid (ansfm_upload_dust after the table)");
+    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, nullptr, nullptr, nullptr, ncont, nth, nullptr, nullptr,
+             radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT,
+             nullptr, W_full, w_begin, 0, nullptr, 1};
+    int rc = fused_cont_check(ctx, fn, ISPACE, lay_temp, use_cia, lay_q, lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4,
+                              ContNeed::aerosols, &c.cont);
+    if (rc) return rc;
     if (ncont != ctx->dust_n)
         FAIL(ANSFM_ERR_INVALID, fn + "ncont = " + std::to_string(ncont) + " phase functions, the aerosol source has " +
                                     std::to_string(ctx->dust_n) + " populations");
-    int rc;
     if ((rc = phase_source_check(ctx, fn, ncont)) || (rc = phase_source_angles(ctx, fn, nth, theta_deg))) return rc;
     if ((imie == 0) != (ctx->phase_imie == 0))
         FAIL(ANSFM_ERR_INVALID, fn + "imie = " + std::to_string(imie) + ", the phase-function source was uploaded with imie = " +
                                     std::to_string(ctx->phase_imie));
     for (int t = 1; t < nth; ++t)
         if (!(theta_deg[t] > theta_deg[t - 1])) FAIL(ANSFM_ERR_INVALID, fn + "theta_deg (Scatter.THETA) must be strictly ascending");
-    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, nullptr, nullptr, nullptr, nullptr, ncont, nth, nullptr, nullptr,
-             radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray, imie, xfac, SPECOUT,
-             nullptr, W_full, w_begin, 0, nullptr};
-    c.fused = 1; c.use_cia = use_cia ? 1 : 0; c.use_dust = 1; c.ray_mode = ray_mode;
-    c.lay_q = lay_q; c.lay_frac = lay_frac; c.lay_totam = lay_totam; c.lay_delh = lay_delh; c.lay_cont = lay_cont;
-    c.f4 = ray_mode == 4 ? f4 : nullptr;
     c.theta_deg = theta_deg; c.mu_theta = mu_theta;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }

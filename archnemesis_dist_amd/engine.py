@@ -531,6 +531,34 @@ class AnsfmEngine:
             np.cos(emiss_ang / 180. * np.pi) * np.cos(sol_ang / 180. * np.pi)
         return np.arccos(calpha) / np.pi * 180.
 
+    def _fused_cont_args(self, what, n, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant, dev=False, ncont=None):
+        """The continuum formed inside a call from the resident sources, as every entry that has one takes it: use_cia, lay_q,
+        lay_frac, lay_totam, lay_delh, use_dust, lay_cont, ray_mode, f4 of include/ansfm.h for n states of L layers.  q given
+        switches CIA on, CONT the aerosols; ray_mode is IRAY, or 12 for variant='v' (calc_tau_rayleighv).  dev: the arrays are
+        contiguous float64 torch device tensors, else host arrays.  ncont: the populations CONT must have (None: as many as it
+        has).  -> (the nine ctypes arguments, the populations of CONT); ValueError for an array of another shape and for a
+        term without its arrays."""
+        mode = 12 if variant == "v" else int(IRAY)
+        use_cia, use_dust = q is not None, CONT is not None
+        if not dev:
+            q, FRAC, TOTAM, DELH, CONT, f4 = (_np(a) for a in (q, FRAC, TOTAM, DELH, CONT, f4))
+        if ncont is None:
+            ncont = CONT.shape[-1] if use_dust else 0
+        for name, a, dims, shape in (("q", q, "(n_models, NLAY, NVMR of upload_cia)", (n, L, getattr(self, "cia_nvmr", -1))),
+                                     ("FRAC", FRAC, "(n_models, NLAY)", (n, L)), ("TOTAM", TOTAM, "(n_models, NLAY)", (n, L)),
+                                     ("DELH", DELH, "(n_models, NLAY)", (n, L)), ("CONT", CONT, "(n_models, NLAY, NDUST)", (n, L, ncont)),
+                                     ("f4", f4, "(n_models, NLAY, 4)", (n, L, 4))):
+            if a is not None and -1 not in shape and (tuple(a.shape) != shape or (dev and not a.is_contiguous())):
+                raise ValueError(f"{what}: {name} must be {'a contiguous tensor ' if dev else ''}{dims} = {shape}, got {tuple(a.shape)}")
+        if use_cia and (FRAC is None or DELH is None):
+            raise ValueError(f"{what}: CIA (q given) needs FRAC and DELH")
+        if (use_cia or mode) and TOTAM is None:
+            raise ValueError(f"{what}: CIA and Rayleigh need TOTAM")
+        if mode == 4 and f4 is None:
+            raise ValueError(f"{what}: IRAY 4 needs f4 (rayleigh_f4)")
+        return (int(use_cia), _ptr(q), _ptr(FRAC), _ptr(TOTAM), _ptr(DELH), int(use_dust), _ptr(CONT), mode,
+                _ptr(f4) if mode == 4 else None), (ncont if use_dust else 0)
+
     def _singlescatt_cont(self, what, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phase_fn, alpha_deg,
                           NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, BRDF, SOLFLUX, SOL_ANG, EMISS_ANG, xfac, variant):
         """the `_cont` entry (phase_fn) or the `_src` entry (alpha_deg)"""
@@ -556,32 +584,21 @@ class AnsfmEngine:
         TS = _np(np.atleast_1d(TSURF))
         if TS.shape != (n,):
             raise ValueError("TSURF must be (n_models,)")
-        mode = 12 if variant == "v" else int(IRAY)
-        use_cia, use_dust = q is not None, CONT is not None
-        ncont = _np(CONT).shape[-1] if use_dust else 0
+        cont, ncont = self._fused_cont_args(what, n, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant)
         arrs = {}
-        for name, a, shape in (("q", q, (n, L, getattr(self, "cia_nvmr", -1))), ("FRAC", FRAC, (n, L)), ("TOTAM", TOTAM, (n, L)),
-                               ("DELH", DELH, (n, L)), ("CONT", CONT, (n, L, ncont)), ("f4", f4, (n, L, 4)),
-                               ("phase_fn", phase_fn, (W, P, ncont + 1)),
+        for name, a, shape in (("phase_fn", phase_fn, (W, P, ncont + 1)),
                                ("alpha_deg", None if alpha_deg is None else np.atleast_1d(alpha_deg), (P,)), ("SCALE", SCALE, (n, LIMAX, P)),
                                ("EMTEMP", EMTEMP, (n, LIMAX, P)), ("BRDF", BRDF, (W, P)), ("EMISSIVITY", EMISSIVITY, (W,)),
                                ("SOLFLUX", SOLFLUX, (W,)), ("xfac", xfac, (W,)), ("SOL_ANG", None if SOL_ANG is None else np.atleast_1d(SOL_ANG), (P,)),
                                ("EMISS_ANG", None if EMISS_ANG is None else np.atleast_1d(EMISS_ANG), (P,))):
             a = arrs[name] = None if a is None else _np(a)
-            if a is not None and -1 not in shape and a.shape != shape:
+            if a is not None and a.shape != shape:
                 raise ValueError(f"{what}: {name} must be {shape}, got {a.shape}")
-        if use_cia and (arrs["FRAC"] is None or arrs["DELH"] is None):
-            raise ValueError(f"{what}: CIA (q given) needs FRAC and DELH")
-        if (use_cia or mode) and arrs["TOTAM"] is None:
-            raise ValueError(f"{what}: CIA and Rayleigh need TOTAM")
-        if mode == 4 and arrs["f4"] is None:
-            raise ValueError(f"{what}: IRAY 4 needs f4 (rayleigh_f4)")
         if arrs["alpha_deg" if src else "phase_fn"] is None:
             raise ValueError(f"{what}: " + ("alpha_deg (NPATH,)" if src else "phase_fn (NWAVE, NPATH, NDUST + 1)") + " is needed")
         out = np.empty((n, W, P))
         rc = getattr(self._lib, "ansfm_" + what)(
-            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
-            _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont,
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), *cont, ncont,
             _ptr(arrs["alpha_deg" if src else "phase_fn"]), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(arrs["SCALE"]), _ptr(arrs["EMTEMP"]),
             _ptr(TS), _ptr(arrs["EMISSIVITY"]), _ptr(arrs["BRDF"]), _ptr(arrs["SOLFLUX"]), _ptr(arrs["SOL_ANG"]), _ptr(arrs["EMISS_ANG"]),
             _ptr(arrs["xfac"]), _ptr(out))
@@ -919,14 +936,9 @@ class AnsfmEngine:
         lt = _np(np.atleast_2d(_np(lay_temp)))
         am = _np(amount).reshape(n, S, L)
         NVMR, NPAR = int(NVMR), int(NPAR)
-        mode = 12 if variant == "v" else int(IRAY)
-        use_cia, use_dust = q is not None, CONT is not None
         opt = lambda a, shape: None if a is None else _np(a).reshape(shape)
-        qq = opt(q, (n, L, NVMR)); fr = opt(FRAC, (n, L)); tot = opt(TOTAM, (n, L)); dh = opt(DELH, (n, L))
-        co = None if CONT is None else _np(CONT).reshape(n, L, -1)
-        ff = opt(f4, (n, L, 4)) if mode == 4 else None
-        if use_dust and co.shape[2] != getattr(self, "dust_n", co.shape[2]):
-            raise ValueError(what + ": CONT must be (n, NLAY, NDUST) with the NDUST of upload_dust")
+        cont, _ = self._fused_cont_args(what, n, L, opt(q, (n, L, NVMR)), opt(FRAC, (n, L)), opt(TOTAM, (n, L)), opt(DELH, (n, L)),
+                                        opt(CONT, (n, L, -1)), IRAY, opt(f4, (n, L, 4)), variant, ncont=getattr(self, "dust_n", None))
         LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
         if LAYINC.ndim == 1:
             LAYINC = LAYINC[:, None]
@@ -940,9 +952,8 @@ class AnsfmEngine:
         dspec = None if on_dev else np.empty((n, W, NPAR, LIMAX, P))
         self._chain_dspec = None
         rc = self._lib.ansfm_cirsradg_ck_thermal_cont(
-            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(qq), _ptr(fr), _ptr(tot), _ptr(dh),
-            int(use_dust), _ptr(co), mode, _ptr(ff), NVMR, NPAR, _ptr(ig), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET),
-            _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(xfac)), _ptr(spec), _ptr(dspec), _ptr(dts))
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), *cont, NVMR, NPAR, _ptr(ig), P, LIMAX, _ptr(NLAYIN),
+            _ptr(LAYINC), _ptr(SC), _ptr(ET), _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(xfac)), _ptr(spec), _ptr(dspec), _ptr(dts))
         self._check(rc, what)
         if on_dev:
             self._chain_dspec = ("device", W, NPAR, LIMAX, P)
@@ -959,12 +970,8 @@ class AnsfmEngine:
         tensors); asynchronous.  q, FRAC, TOTAM, DELH, CONT, f4 as `cirsrad_ck_thermal_cont_dev` takes them, with the same shape
         checks; SPECOUT (n, W, P), dSPECOUT (n, W, NPAR, LIMAX, P), dTSURF (n, W, P) are filled."""
         what = "cirsradg_ck_thermal_cont_dev"
-        mode = 12 if variant == "v" else int(IRAY)
-        use_cia, use_dust = q is not None, CONT is not None
-        for a, shape in ((q, (n_models, L, getattr(self, "cia_nvmr", -1))), (FRAC, (n_models, L)), (TOTAM, (n_models, L)),
-                         (DELH, (n_models, L)), (CONT, (n_models, L, getattr(self, "dust_n", -1))), (f4, (n_models, L, 4))):
-            if a is not None and -1 not in shape and (tuple(a.shape) != shape or not a.is_contiguous()):
-                raise ValueError(what + ": expected a contiguous tensor of shape %s, got %s" % (shape, tuple(a.shape)))
+        cont, _ = self._fused_cont_args(what, n_models, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant, dev=True,
+                                        ncont=getattr(self, "dust_n", -1))
         W = self.dims[0]
         for a, shape in ((SPECOUT, (n_models, W, P)), (dSPECOUT, (n_models, W, int(NPAR), LIMAX, P)), (dTSURF, (n_models, W, P))):
             if a is None or tuple(a.shape) != shape or not a.is_contiguous():
@@ -972,8 +979,7 @@ class AnsfmEngine:
         ig = _np(igas_map, np.int32)
         self._chain_dspec = None
         rc = self._lib.ansfm_cirsradg_ck_thermal_cont_dev(
-            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), int(use_cia), _ptr(q),
-            _ptr(FRAC), _ptr(TOTAM), _ptr(DELH), int(use_dust), _ptr(CONT), mode, _ptr(f4) if mode == 4 else None, int(NVMR), int(NPAR),
+            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), *cont, int(NVMR), int(NPAR),
             _ptr(ig), int(P), int(LIMAX), _ptr(NLAYIN), _ptr(LAYINC), _ptr(SCALE), _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY),
             _ptr(xfac), _ptr(SPECOUT), _ptr(dSPECOUT), _ptr(dTSURF))
         self._check(rc, what)
@@ -1009,17 +1015,12 @@ class AnsfmEngine:
         NVMR) = PP / PRESS with FRAC, DELH (n, L) switch CIA on (None: off); CONT (n, L, NDUST) after any
         DUST_RENORMALISATION switches the aerosols on (None: off); IRAY 0 or as in cirsrad_ck_thermal_ray_dev with f4 (n,
         L, 4); TOTAM (n, L) for CIA and Rayleigh."""
-        mode = 12 if variant == "v" else int(IRAY)
-        use_cia, use_dust = q is not None, CONT is not None
-        for a, shape in ((q, (n_models, L, getattr(self, "cia_nvmr", -1))), (FRAC, (n_models, L)), (TOTAM, (n_models, L)),
-                         (DELH, (n_models, L)), (CONT, (n_models, L, getattr(self, "dust_n", -1))), (f4, (n_models, L, 4))):
-            if a is not None and -1 not in shape and (tuple(a.shape) != shape or not a.is_contiguous()):
-                raise ValueError("cirsrad_ck_thermal_cont_dev: expected a contiguous tensor of shape %s, got %s" % (shape, tuple(a.shape)))
+        cont, _ = self._fused_cont_args("cirsrad_ck_thermal_cont_dev", n_models, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant, dev=True,
+                                        ncont=getattr(self, "dust_n", -1))
         rc = self._lib.ansfm_cirsrad_ck_thermal_cont_dev(
-            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), int(use_cia), _ptr(q),
-            _ptr(FRAC), _ptr(TOTAM), _ptr(DELH), int(use_dust), _ptr(CONT), mode, _ptr(f4), int(P), int(LIMAX), _ptr(NLAYIN),
-            _ptr(LAYINC), _ptr(SCALE), _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY), _ptr(SOLFLUX), _ptr(REFLECTANCE), _ptr(SOL_ANG),
-            _ptr(EMISS_ANG), _ptr(xfac), _ptr(SPECOUT))
+            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), *cont, int(P), int(LIMAX),
+            _ptr(NLAYIN), _ptr(LAYINC), _ptr(SCALE), _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY), _ptr(SOLFLUX), _ptr(REFLECTANCE),
+            _ptr(SOL_ANG), _ptr(EMISS_ANG), _ptr(xfac), _ptr(SPECOUT))
         self._check(rc, "cirsrad_ck_thermal_cont_dev")
 
     @staticmethod
@@ -1240,34 +1241,20 @@ class AnsfmEngine:
         lt = _np(lay_temp)
         if lt.shape != (n, L):
             raise ValueError("lay_temp must be (n_models, NLAY)")
-        mode = 12 if variant == "v" else int(IRAY)
-        use_cia, use_dust = q is not None, CONT is not None
-        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        (phasarr, npop, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
         if theta is not None:                   # the populations are those of the aerosol columns
-            ncont, nth = (_np(CONT).shape[-1] if use_dust else 0), theta.shape[0]
-        arrs = {}
-        for name, a, shape in (("q", q, (n, L, getattr(self, "cia_nvmr", -1))), ("FRAC", FRAC, (n, L)), ("TOTAM", TOTAM, (n, L)),
-                               ("DELH", DELH, (n, L)), ("CONT", CONT, (n, L, ncont)), ("f4", f4, (n, L, 4))):
-            a = arrs[name] = None if a is None else _np(a)
-            if a is not None and -1 not in shape and a.shape != shape:
-                raise ValueError(f"{what}: {name} must be {shape}, got {a.shape}")
-        if use_cia and (arrs["FRAC"] is None or arrs["DELH"] is None):
-            raise ValueError("cirsrad_ck_scatter_batch_cont: CIA (q given) needs FRAC and DELH")
-        if (use_cia or mode) and arrs["TOTAM"] is None:
-            raise ValueError("cirsrad_ck_scatter_batch_cont: CIA and Rayleigh need TOTAM")
-        if mode == 4 and arrs["f4"] is None:
-            raise ValueError("cirsrad_ck_scatter_batch_cont: IRAY 4 needs f4 (rayleigh_f4)")
-        if ncont > 0 and not use_dust:
-            raise ValueError("cirsrad_ck_scatter_batch_cont: CONT is needed with aerosols (phasarr given)")
+            npop, nth = None, theta.shape[0]
+        elif npop > 0 and CONT is None:
+            raise ValueError(f"{what}: CONT is needed with aerosols (phasarr given)")
+        cont, ncont = self._fused_cont_args(what, n, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant, ncont=npop)
         rg = _np(radg)
         if rg.size != n * W * nmu:
             raise ValueError("radg must be (n_models, NWAVE, NMU)")
         w_begin, W_full = (0, W) if wave_slice is None else (int(v) for v in wave_slice)
         if phasarr is not None and phasarr.shape[1] != W_full:
-            raise ValueError("cirsrad_ck_scatter_batch_cont: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
+            raise ValueError(f"{what}: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
         out = np.empty((n, W, P))
-        head = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(use_cia), _ptr(arrs["q"]), _ptr(arrs["FRAC"]),
-                _ptr(arrs["TOTAM"]), _ptr(arrs["DELH"]), int(use_dust), _ptr(arrs["CONT"]), mode, _ptr(arrs["f4"]), ncont, nth)
+        head = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), *cont, ncont, nth)
         tail = (_ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu,
                 _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
         if theta is not None:
