@@ -38,6 +38,7 @@
 #include "../../include/ansfm.h"
 #pragma GCC visibility pop
 #include "ansfm_merge_plan.h"
+#include "ansfm_ms_variants.h"
 
 namespace ansfm {
 
@@ -170,6 +171,15 @@ struct ansfm_ctx {
     DevBuf ms_tauray_l, ms_lfrac_l;      // the continuum by rows: TAURAY / aerosol fractions of a launch's models (the model-by-model route: one model's dense arrays)
     DevBuf ms_cache, ms_orders, ms_same, ms_pcache, ms_lstart; // batched scattering Jacobian: doubled layers / prefix stacks of model 0, orders cached, layer flags, sweep starts
     long ms_cache_hits = 0, ms_cache_layers = 0;   // (model, layer) pairs taken from the cache / all, last batch call
+    // per-model phase functions of the batch (ansfm_set_phase_variants): the pending setting (host copies, consumed by the next
+    // batched scattering call), the variants' phasarr [V - 1][ncont][W][2][nth] and the small tables (pairs, the models' variants,
+    // the differing components) on the device; (variant, component) pairs integrated and walked / bytes of the variants' phase
+    // matrices and factors in the last batched call (ansfm_last_scatter_variants)
+    ansfm::MsVariantSet ms_pv;
+    DevBuf ms_var_in, ms_var_tab;
+    long ms_var_pairs = 0, ms_var_bytes = 0;
+    hipEvent_t ms_walk_ev[2] = {nullptr, nullptr};   // around the phase matrices and the walk of the last batched call at G > 1
+    bool ms_walk_timed = false;
     long ms_windows = 0, ms_window_w = 0;          // spectral windows of phase matrices / Hansen factors of the last scattering call, their size
     DevBuf hb[25];  // staging buffers of the host-pointer entry points
     // runtime line-by-line: the opacity of a gas, summed in HBM (ansfm_lbl_accum_*); its grid and (T, p) points [2][L]
@@ -237,6 +247,7 @@ struct ansfm_ctx {
         for (FusedRoute *r : {&transit, &occ, &limb, &disc})
             for (hipEvent_t e : r->ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : ms_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ms_walk_ev) if (e) (void)hipEventDestroy(e);
         for (hipStream_t s : {ms_stream, ms_stream2, ms_stream3, own_stream}) if (s) (void)hipStreamDestroy(s);
     }
 };

@@ -100,6 +100,41 @@ __global__ void k_ms_same_cols(int n_models, int W, int X, int L, const double *
         if (__double_as_longlong(a[l]) != __double_as_longlong(b[l])) same[m * L + l] = 0;
 }
 
+// Per-model phase functions (ansfm_set_phase_variants): a layer of model m stays model 0's only if none of the populations
+// whose phase function differs between m's variant and variant 0 (diff [V][ncomp]) is present in it, i.e. its fraction is 0 at
+// every wavenumber -- ms_phase_mix then adds fs pf(c) 0 = +-0 to the sum, which leaves every bit of a non-zero sum as it is as
+// long as the phase matrices are finite.  Where the sum is itself an exact zero before the term (no Rayleigh term, or one that
+// is +-0) the sign of the result could differ between variants; no test has shown it, and the rule would be narrowed if one
+// did.  lfrac [n][W][ncont][L] or, with cont_row, the rows [R][ncont][W].  One thread per (model, wavenumber, population); a
+// non-zero fraction (a NaN included) clears the layer's flag.
+__global__ void k_ms_same_phase(int n_models, int W, int ncont, int L, const int *__restrict__ pvar, const unsigned char *__restrict__ diff,
+                                const double *__restrict__ lfrac, const int32_t *__restrict__ cont_row, unsigned char *__restrict__ same)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t per = (size_t)W * ncont;
+    if (i >= (size_t)(n_models - 1) * per) return;
+    const size_t m = 1 + i / per, w = (i % per) / ncont;
+    const int c = (int)(i % ncont);
+    if (!diff[(size_t)pvar[m] * (ncont + 1) + c]) return;
+    for (int l = 0; l < L; ++l) {
+        const double f = cont_row ? lfrac[((size_t)cont_row[m * L + l] * ncont + c) * W + w] : lfrac[((m * W + w) * ncont + c) * L + l];
+        if (!(f == 0.0)) same[m * L + l] = 0;
+    }
+}
+
+// The components of variants 1 .. V-1 that do not differ from variant 0's (Rayleigh always): their phase matrices and Hansen
+// factors are variant 0's, bit for bit (the walk keeps one history per scatterer), copied here.  Every array of a variant is
+// [..][ncomp][nn], so element idx of a variant belongs to component (idx / nn) % ncomp.  base: variant 0's ppl.
+__global__ void k_ms_variant_fill(int V, int ncomp, int nn, size_t vstride, const unsigned char *__restrict__ diff, double *__restrict__ base)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= vstride) return;
+    const int c = (int)((idx / nn) % ncomp);
+    const double x = base[idx];
+    for (int v = 1; v < V; ++v)
+        if (!diff[(size_t)v * ncomp + c]) base[(size_t)v * vstride + idx] = x;
+}
+
 // One model's dense array from the rows, for the model-by-model route: dst [W][X][L] = rows [R][X][W] at cont_row[l] (X = 1:
 // an opacity, ncont: the fractions).  One thread per (wavenumber, layer, x).
 __global__ __launch_bounds__(128) void k_ms_rows_expand(int W, int X, int L, const int32_t *__restrict__ cont_row_m,

@@ -68,6 +68,16 @@ struct MsParams {
     // and store to sink [ncomp][nmu*nmu].  stn = 0: every step, stride nwin.
     int st0, stn;
     double *sink;
+    // Per-model phase functions in the batch (ansfm_set_phase_variants; the layout is MsVariantPlan's, ansfm_ms_variants.h):
+    // variant v's ppl / pmi / fc lie v * vstride doubles behind variant 0's.  pairs [..][2] = (variant, component): block y of
+    // k_ms_phase / block x of k_ms_hansen_seq works on that pair instead of component y / x, npairs blocks (null: variant 0 alone);
+    // phasarr_var [V - 1][ncont][nwave][2][nth], st_phas doubles apart: the phase functions of variants 1 .. V-1.
+    // The chain kernels know nothing of variants: a launch of the cached chains covers models of ONE variant and gets that
+    // variant's ppl / pmi / fc from the host (ms_run_slabs).
+    const int *pairs;
+    int npairs;
+    const double *phasarr_var;
+    size_t st_phas, vstride;
 };
 
 constexpr int kMsCacheEntry = 528;   // doubles per cached layer: r (256) and t (256) in the MFMA accumulator layout, j (16)

@@ -45,13 +45,19 @@ constexpr int kMsPhaseOrders = 9;     // Fourier orders accumulated per pass ove
 __global__ __launch_bounds__(256) void k_ms_phase(MsParams p)
 {
     extern __shared__ double ctab[];            // [nf + 2][nphi + 1]: cos(ic phi_k); the last row is cos(phi_k)
-    const int wl = blockIdx.x, widx = p.pw0 + wl, comp = blockIdx.y + p.phase_comp0;  // comp == ncont -> Rayleigh; wl: in the window
+    const int wl = blockIdx.x, widx = p.pw0 + wl;                      // wl: in the window
+    // comp == ncont -> Rayleigh.  With a pair list (per-model phase functions) block y is a (variant, component) pair: the
+    // variant's phase function in, its matrices out, the same arithmetic
+    const int var = p.pairs ? p.pairs[2 * blockIdx.y] : 0;
+    const int comp = p.pairs ? p.pairs[2 * blockIdx.y + 1] : blockIdx.y + p.phase_comp0;
     const int n = p.nmu, nn = n * n, tid = threadIdx.x;
     const double pi = 3.141592653589793;
     const double dphi = 2.0 * pi / p.nphi;
     const int jc = comp < p.ncont ? comp : (p.ncont > 0 ? p.ncont - 1 : 0);
-    const double *pfunc = p.phasarr + (((size_t)jc * p.nwave + widx) * 2 + 0) * p.nth;
-    const double *xmu = p.phasarr + (((size_t)jc * p.nwave + widx) * 2 + 1) * p.nth;
+    const double *phas = var > 0 ? p.phasarr_var + (size_t)(var - 1) * p.st_phas : p.phasarr;
+    const double *pfunc = phas + (((size_t)jc * p.nwave + widx) * 2 + 0) * p.nth;
+    const double *xmu = phas + (((size_t)jc * p.nwave + widx) * 2 + 1) * p.nth;
+    double *const oppl = p.ppl + (size_t)var * p.vstride, *const opmi = p.pmi + (size_t)var * p.vstride;
     const int iscat = (comp == p.ncont) ? 0 : (p.imie == 0 ? 2 : 4);
     const int nk = p.nphi + 1;
     const bool tab = p.phase_tab != 0;
@@ -69,8 +75,8 @@ __global__ __launch_bounds__(256) void k_ms_phase(MsParams p)
         const int i = e / n, j = e % n;
         if (i >= nr || j >= nr) {               // beyond the quadrature (a smaller one padded to 16 streams): nothing scatters there
             for (int ic = 0; ic <= p.nf; ++ic) {
-                p.ppl[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
-                p.pmi[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
+                oppl[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
+                opmi[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = 0.0;
             }
             continue;
         }
@@ -118,8 +124,8 @@ __global__ __launch_bounds__(256) void k_ms_phase(MsParams p)
             for (int o = 0; o < kMsPhaseOrders; ++o) {
                 const int ic = ic0 + o;
                 if (ic <= p.nf) {
-                    p.ppl[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = spl[o];
-                    p.pmi[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = smi[o];
+                    oppl[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = spl[o];
+                    opmi[(((size_t)wl * (p.nf + 1) + ic) * p.ncomp + comp) * nn + e] = smi[o];
                 }
             }
         }
@@ -193,7 +199,11 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
     // two waves on the whole chip walk while thousands of chain waves compute: the walk gates the chains of the next
     // g-ordinate, so its waves issue first wherever they share a SIMD
     __builtin_amdgcn_s_setprio(3);
-    const int comp = blockIdx.x + p.hansen_comp0;
+    // with a pair list (per-model phase functions) block x walks a (variant, component) pair on the variant's matrices
+    const int var = p.pairs ? p.pairs[2 * blockIdx.x] : 0;
+    const int comp = p.pairs ? p.pairs[2 * blockIdx.x + 1] : blockIdx.x + p.hansen_comp0;
+    const double *const vppl = p.ppl + (size_t)var * p.vstride, *const vpmi = p.pmi + (size_t)var * p.vstride;
+    double *const vfc = p.fc + (size_t)var * p.vstride;
     const int n = NMU ? NMU : p.nmu, nn = n * n, tid = threadIdx.x;
     const double x1 = 2.0 * 3.141592653589793;
     const int nr = p.nmu_real ? p.nmu_real : n;              // the quadrature's size (a smaller one padded to 16 streams)
@@ -211,8 +221,8 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
     constexpr bool CLAMP = NMU != 0 && !FULL;
     double ring[D][2 * NE];
     auto fetch = [&](int d, int widx) {
-        const double *gppl = p.ppl + (((size_t)widx * (p.nf + 1) + 0) * p.ncomp + comp) * nn;
-        const double *gpmi = p.pmi + (((size_t)widx * (p.nf + 1) + 0) * p.ncomp + comp) * nn;
+        const double *gppl = vppl + (((size_t)widx * (p.nf + 1) + 0) * p.ncomp + comp) * nn;
+        const double *gpmi = vpmi + (((size_t)widx * (p.nf + 1) + 0) * p.ncomp + comp) * nn;
 #pragma unroll
         for (int r = 0; r < NE; ++r) {
             const int e = CLAMP ? min(tid + 64 * r, nn - 1) : tid + 64 * r;
@@ -234,7 +244,7 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
         for (int e = tid; e < nn; e += 64) fc[e] = pfc[e];
     } else if (p.ig0 == 0) { for (int e = tid; e < nn; e += 64) fc[e] = 1.0; }
     else {
-        const double *pfc = p.fc + (((size_t)(p.ig0 - 1) * p.nwin + (p.nwin - 1)) * p.ncomp + comp) * nn;
+        const double *pfc = vfc + (((size_t)(p.ig0 - 1) * p.nwin + (p.nwin - 1)) * p.ncomp + comp) * nn;
         for (int e = tid; e < nn; e += 64) fc[e] = pfc[e];
     }
     const long total = (long)p.ng_launch * p.nwin;
@@ -292,7 +302,7 @@ __global__ __launch_bounds__(64) void k_ms_hansen_seq(MsParams p)
         }
         // outside the store range: the same store to the sink (an address select; the step's arithmetic does not change)
         const int ws = widx - p.st0;
-        double *ofc = (unsigned)ws < (unsigned)sn ? p.fc + (((size_t)ig * sn + ws) * p.ncomp + comp) * nn : p.sink + (size_t)comp * nn;
+        double *ofc = (unsigned)ws < (unsigned)sn ? vfc + (((size_t)ig * sn + ws) * p.ncomp + comp) * nn : p.sink + (size_t)comp * nn;
 #pragma unroll
         for (int r = 0; r < NE; ++r) {           // a fixed number of stores per step (the waits before the ring's slots count them)
             const int e = CLAMP ? min(tid + 64 * r, nn - 1) : tid + 64 * r;

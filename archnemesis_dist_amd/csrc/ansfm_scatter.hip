@@ -60,7 +60,17 @@ struct MsCall {
     // phasarr formed on the device from the resident phase-function source (ansfm_cirsrad_ck_scatter_batch_src): Scatter.THETA
     // in degrees and its cosines [nth], host pointers; phasarr is null
     const double *theta_deg, *mu_theta;
+    // per-model phase functions (ansfm_set_phase_variants): the setting this call consumes, validated by the batch entry; null: none
+    const MsVariantSet *pv;
 };
+
+// The pending per-model phase functions leave the context with the batched call that meets them, whatever becomes of that call
+static MsVariantSet ms_take_variants(ansfm_ctx *ctx)
+{
+    MsVariantSet s = std::move(ctx->ms_pv);
+    ctx->ms_pv = MsVariantSet();
+    return s;
+}
 
 // one model's continuum already on the device, [W][L] / [W][ncont][L] (null = zeros): cirsrad_ck_scatter_impl stages none then
 struct MsDevCont { const double *cia, *dust, *ray, *sca, *lf; };
@@ -160,7 +170,7 @@ static long ms_window_size(long W, int nf, int ncomp, int nmu, const MsKnobs &kn
 // any other size takes the run-time build.  One block per scattering component in use.
 static void ms_launch_hansen(hipStream_t st, const MsParams &pp)
 {
-    const dim3 hg((unsigned)(pp.ncont + (pp.iray > 0 ? 1 : 0))), hb(64);
+    const dim3 hg((unsigned)(pp.pairs ? pp.npairs : pp.ncont + (pp.iray > 0 ? 1 : 0))), hb(64);   // pairs: one block per (variant, component)
     switch (pp.nmu) {
     case 16: hipLaunchKernelGGL(k_ms_hansen_seq<16>, hg, hb, 0, st, pp); break;
     case 4: hipLaunchKernelGGL(k_ms_hansen_seq<4>, hg, hb, 0, st, pp); break;
@@ -175,6 +185,10 @@ static void ms_launch_hansen(hipStream_t st, const MsParams &pp)
 static void ms_launch_phase(hipStream_t st, const MsParams &pw)
 {
     const size_t lds = pw.phase_tab ? (size_t)(pw.nf + 2) * (pw.nphi + 1) * sizeof(double) : 0;
+    if (pw.pairs) {                                             // every (variant, component) pair, Rayleigh among them, in one launch
+        if (pw.npairs > 0) hipLaunchKernelGGL(k_ms_phase, dim3((unsigned)pw.nwin, (unsigned)pw.npairs), dim3(256), lds, st, pw);
+        return;
+    }
     if (pw.ncont > 0) hipLaunchKernelGGL(k_ms_phase, dim3((unsigned)pw.nwin, (unsigned)pw.ncont), dim3(256), lds, st, pw);
     if (pw.iray > 0) {
         MsParams pr = pw;
@@ -608,6 +622,11 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
         const size_t mm = m;
         MsCall cm = c;
         cm.n_models = 1;
+        // per-model phase functions: the model's variant; the walk of the model before stands only where it had the same one
+        const int var = c.pv ? c.pv->phase_of[mm] : 0, var_before = (c.pv && m > 0) ? c.pv->phase_of[mm - 1] : 0;
+        const bool reuse = m > 0 && var == var_before;
+        if (var > 0) cm.phasarr = c.pv->phasarr.data() + (size_t)(var - 1) * c.ncont * W * 2 * c.nth;
+        cm.pv = nullptr;
         cm.lay_press_pa += mm * L; cm.lay_temp += mm * L; cm.amount += mm * S * L;
         cm.radg += mm * W * c.nmu; cm.SPECOUT += mm * W * c.ngeom;
         if (ctx->lblrt) ctx->st_m0 = m;                      // gas_tau reads this model's rows of the state
@@ -628,11 +647,11 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
             }
             HIPCHK(hipGetLastError());
             const MsDevCont dc{dense[0], dense[1], dense[2], dense[3], dense[4]};
-            rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0, &dc);
+            rc = cirsrad_ck_scatter_impl(ctx, cm, kn, reuse, &dc);
         } else {
             for (const double **a : {&cm.taucia, &cm.taudust, &cm.tauray, &cm.tauscat}) if (*a) *a += mm * WL;
             if (cm.lfrac) cm.lfrac += mm * WL * ncont;
-            rc = cirsrad_ck_scatter_impl(ctx, cm, kn, m > 0);
+            rc = cirsrad_ck_scatter_impl(ctx, cm, kn, reuse);
         }
         ctx->st_m0 = -1;
         if (rc) return rc;
@@ -642,10 +661,11 @@ static int ms_batch_by_model(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn)
 }
 
 // Which layers equal model 0's in EVERY input, and where a model's adding sweep may start.  Reads ctx->dd_slot (dedup_rows), the
-// staged continuum or cont_row, and c.radg on the host.  Leaves same[n][L] in ctx->ms_same (*same), the sweep starts [n] and the
-// launch order [n] in ctx->ms_lstart, the ms_cache_* counters and *npre, the prefix stacks per model; synchronises the stream.
-static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, const MsStaged &s, bool lookup, unsigned char **same_out,
-                          int *npre_out)
+// staged continuum or cont_row, d_pvar [n] / d_diff [V][ncomp] (per-model phase functions; null: none) and c.radg on the host.
+// Leaves same[n][L] in ctx->ms_same (*same), the sweep starts [n] and the launch order [n] in ctx->ms_lstart and *ids_out, the
+// ms_cache_* counters and *npre, the prefix stacks per model; synchronises the stream.
+static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, const MsStaged &s, bool lookup, const int *d_pvar,
+                          const unsigned char *d_diff, unsigned char **same_out, int *npre_out, std::vector<int> *ids_out)
 {
     const int W = ctx->W, L = c.L, n_models = c.n_models, ncont = c.ncont;
     const size_t nl = (size_t)n_models * L;
@@ -662,6 +682,10 @@ static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, co
     if (s.lf && ncont > 0 && !by_rows)
         hipLaunchKernelGGL(k_ms_same_cols, dim3(nblk((size_t)(n_models - 1) * W * ncont, 128)), dim3(128), 0, ctx->stream,
                            n_models, W, ncont, L, s.lf, same);
+    // per-model phase functions: a layer that scatters through a population whose phase function changed is the model's own
+    if (d_pvar && s.lf && ncont > 0)
+        hipLaunchKernelGGL(k_ms_same_phase, dim3(nblk((size_t)(n_models - 1) * W * ncont, 128)), dim3(128), 0, ctx->stream, n_models, W,
+                           ncont, L, d_pvar, d_diff, s.lf, s.d_crow, same);
     HIPCHK(hipGetLastError());
     // where a model's adding sweep may start: below its first changed layer (in sweep order: bottom first when the paths look
     // down, top first when they look up) the stack equals model 0's, kept after every kMsPrefixStep-th layer
@@ -686,7 +710,12 @@ static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, co
     // about the same time (position 0 of the list is unused: model 0 has its own launch)
     std::vector<int> ids((size_t)n_models, 0);
     for (int m = 0; m < n_models; ++m) ids[m] = m;
-    std::stable_sort(ids.begin() + 1, ids.end(), [&](int a, int b) { return lstart[a] < lstart[b]; });
+    // (per-model phase functions: by variant first -- a launch of the cached chains covers one variant, ms_run_slabs)
+    auto var_of = [&](int m) { return c.pv ? c.pv->phase_of[(size_t)m] : 0; };
+    std::stable_sort(ids.begin() + 1, ids.end(), [&](int a, int b) {
+        return var_of(a) != var_of(b) ? var_of(a) < var_of(b) : lstart[a] < lstart[b];
+    });
+    *ids_out = ids;
     HIPCHK(ctx->ms_lstart.reserve((size_t)2 * n_models * sizeof(int)));
     HIPCHK(hipMemcpyAsync(ctx->ms_lstart.p, lstart.data(), (size_t)n_models * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->ms_lstart.as<int>() + n_models, ids.data(), (size_t)n_models * sizeof(int), hipMemcpyHostToDevice,
@@ -695,20 +724,59 @@ static int ms_same_layers(ansfm_ctx *ctx, const MsCall &c, const MsKnobs &kn, co
     return ANSFM_OK;
 }
 
+// Per-model phase functions: the plan (which components differ, the pairs of the two launches, the layout), the variants'
+// phasarr and the small tables on the device.  Reads c.pv (validated) and c.phasarr on the host and p's sizes; leaves vp, p.pairs /
+// npairs / phasarr_var / st_phas / vstride, *d_pvar [n] (the models' variants), *d_diff [V][ncomp] and the ms_var_* counters;
+// synchronises the stream.
+// ANSFM_ERR_UNSUPPORTED when the variants' phase functions find no room.
+static int ms_stage_variants(ansfm_ctx *ctx, const MsCall &c, MsVariantPlan &vp, MsParams &p, const int **d_pvar, const unsigned char **d_diff)
+{
+    const MsVariantSet &pv = *c.pv;
+    const size_t D = sizeof(double), I = sizeof(int);
+    vp = ms_variants_plan(pv.V, c.ncont, c.iray, (size_t)ctx->W, c.nth, c.nf, p.nmu, ctx->G, c.phasarr, pv.phasarr.data());
+    if (ctx->ms_var_in.reserve(pv.phasarr.size() * D) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter_batch: no memory for the phase functions of " + std::to_string(pv.V) + " variants");
+    }
+    const size_t n_int = (size_t)2 * vp.npairs + c.n_models;
+    HIPCHK(ctx->ms_var_tab.reserve(n_int * I + vp.diff.size()));
+    char *tab = ctx->ms_var_tab.as<char>();
+    HIPCHK(hipMemcpyAsync(ctx->ms_var_in.p, pv.phasarr.data(), pv.phasarr.size() * D, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab, vp.pairs.data(), (size_t)2 * vp.npairs * I, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab + (size_t)2 * vp.npairs * I, pv.phase_of.data(), (size_t)c.n_models * I, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(tab + n_int * I, vp.diff.data(), vp.diff.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));                  // vp's vectors may move
+    p.pairs = reinterpret_cast<const int *>(tab); p.npairs = vp.npairs; *d_pvar = p.pairs + 2 * vp.npairs;
+    p.phasarr_var = ctx->ms_var_in.as<double>(); p.st_phas = vp.st_phas; p.vstride = vp.vstride;
+    *d_diff = reinterpret_cast<const unsigned char *>(tab + n_int * I);
+    ctx->ms_var_pairs = vp.npairs - vp.npairs0; ctx->ms_var_bytes = (long)vp.bytes_variants();
+    return ANSFM_OK;
+}
+
 // G > 1: the phase matrices of the whole axis and the whole walk in one launch, ahead of the slabs -- they do not depend on the
 // model.  The walk continues from g to g + 1 over the whole axis, so a slice walks all of it too: its factors kept, the rest of
 // the steps into a sink.  Reads p (sizes, phasarr); leaves ctx->misc zeroed and filled, p.ppl / p.pmi at the slice's first
 // wavenumber and p.fc.
-static int ms_walk_axis(ansfm_ctx *ctx, const MsCall &c, const MsRoute &r, MsParams &p)
+// vp (per-model phase functions; p.pairs / phasarr_var set by ms_stage_variants): the buffers of every variant, one behind the
+// other; the pairs that differ from variant 0 join variant 0's components in the two launches, the rest is copied from variant 0.
+static int ms_walk_axis(ansfm_ctx *ctx, const MsCall &c, const MsRoute &r, const MsVariantPlan *vp, MsParams &p)
 {
     const int W = ctx->W, G = ctx->G;
     const bool sliced = c.W_full != W;
     const size_t D = sizeof(double), nn = (size_t)p.nmu * p.nmu;
     const size_t per_w = (size_t)(c.nf + 1) * p.ncomp * nn, nph = (size_t)c.W_full * per_w, nfc = (size_t)G * W * p.ncomp * nn;
-    const size_t misc_n = 2 * nph + nfc + (sliced ? (size_t)p.ncomp * nn : 0);
+    const size_t misc_0 = 2 * nph + nfc + (sliced ? (size_t)p.ncomp * nn : 0), misc_n = vp ? vp->total : misc_0;
+    if (vp && (vp->nph != nph || vp->nfc != nfc || sliced)) FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch: the phase variants' plan does not fit the call");
+    if (vp && ctx->misc.reserve(misc_n * D) != hipSuccess) {
+        (void)hipGetLastError();
+        FAIL(ANSFM_ERR_UNSUPPORTED, "cirsrad_ck_scatter_batch: no memory for the phase matrices and Hansen factors of " +
+                                        std::to_string(vp->V) + " phase-function variants (" + std::to_string(misc_n * D) + " bytes)");
+    }
     HIPCHK(ctx->misc.reserve(misc_n * D));
-    HIPCHK(hipMemsetAsync(ctx->misc.p, 0, misc_n * D, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->misc.p, 0, misc_0 * D, ctx->stream));          // (a variant is written whole: its pairs, then the copy)
     p.ppl = ctx->misc.as<double>(); p.pmi = p.ppl + nph; p.fc = p.pmi + nph;
+    for (hipEvent_t &e : ctx->ms_walk_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ctx->ms_walk_ev[0], ctx->stream));
     if (r.ncomp_run > 0) {
         MsParams pw = p;
         pw.nwave = c.W_full; pw.nwin = c.W_full;
@@ -717,6 +785,13 @@ static int ms_walk_axis(ansfm_ctx *ctx, const MsCall &c, const MsRoute &r, MsPar
         ms_launch_hansen(ctx->stream, pw);
         HIPCHK(hipGetLastError());
     }
+    if (vp && vp->V > 1) {
+        hipLaunchKernelGGL(k_ms_variant_fill, dim3(nblk(vp->vstride, 256)), dim3(256), 0, ctx->stream, vp->V, vp->ncomp, (int)nn, vp->vstride,
+                           ctx->ms_var_tab.as<unsigned char>() + ((size_t)2 * vp->npairs + c.n_models) * sizeof(int), p.ppl);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ctx->ms_walk_ev[1], ctx->stream));
+    ctx->ms_walk_timed = true;
     p.ppl += (size_t)c.w_begin * per_w; p.pmi += (size_t)c.w_begin * per_w;
     return ANSFM_OK;
 }
@@ -815,7 +890,10 @@ static int ms_wire_batch(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, con
 // Slab by slab (G = 1: its phase matrices and walk first): the optics and the ordinary chain of model 0, which also fills the
 // cache, then models 1 .. n-1 in chunks: the adding sweep over cached layers, changed layers computed in place.  Leaves
 // rad [model][ngeom][G][W] in ctx->tmp_out or, below 16 streams, every order in ctx->tmp_in2.
-static int ms_run_slabs(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, const MsRoute &r, const MsSlabs &sl, MsParams &p)
+// Per-model phase functions: ids is sorted by variant, a launch ends where the variant changes and reads that variant's phase
+// matrices and factors -- the chain kernels are the ones every other batch runs.
+static int ms_run_slabs(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, const MsRoute &r, const MsSlabs &sl, const std::vector<int> &ids,
+                        MsParams &p)
 {
     const int W = ctx->W, L = c.L, n_models = c.n_models, w_begin = c.w_begin;
     int rc;
@@ -840,11 +918,20 @@ static int ms_run_slabs(ansfm_ctx *ctx, const MsCall &c, const MsStaged &s, cons
         ms_launch_optics(ctx->stream, o, (int)w0, wc, 0, 1, nullptr);
         p.m0 = 0; p.n_launch = 1;
         if ((rc = ms_launch_chain<1>(ctx, r.chain, ctx->stream, p))) return rc;
-        for (int m0 = 1; m0 < n_models; m0 += sl.mchunk) {
-            const int nm = std::min(sl.mchunk, n_models - m0);
+        for (int m0 = 1, nm; m0 < n_models; m0 += nm) {
+            nm = std::min(sl.mchunk, n_models - m0);
+            MsParams pl = p;
+            if (c.pv) {
+                const int v = c.pv->phase_of[(size_t)ids[m0]];
+                int k = 1;
+                while (k < nm && c.pv->phase_of[(size_t)ids[m0 + k]] == v) ++k;
+                nm = k;
+                const size_t vo = (size_t)v * p.vstride;
+                pl.ppl += vo; pl.pmi += vo; pl.fc += vo;
+            }
             ms_launch_optics(ctx->stream, o, (int)w0, wc, m0, nm, p.model_ids);
-            p.m0 = m0; p.n_launch = nm;
-            if ((rc = ms_launch_chain<2>(ctx, r.chain, ctx->stream, p))) return rc;
+            pl.m0 = m0; pl.n_launch = nm;
+            if ((rc = ms_launch_chain<2>(ctx, r.chain, ctx->stream, pl))) return rc;
         }
     }
     return ANSFM_OK;
@@ -857,6 +944,16 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
     const int W = ctx->W, G = ctx->G, L = c.L, n_models = c.n_models;
     const bool by_rows = c.cont_row != nullptr || c.fused;
     ctx->ms_cache_hits = 0; ctx->ms_cache_layers = (long)n_models * L;
+    ctx->ms_var_pairs = 0; ctx->ms_var_bytes = 0; ctx->ms_walk_timed = false;
+    if (c.pv) {                                                  // per-model phase functions: refusals before anything is launched
+        const std::string fn = "cirsrad_ck_scatter_batch: the pending phase variants (ansfm_set_phase_variants) ";
+        if (c.W_full != W) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "meet a slice of the spectral axis");
+        if (G == 1) FAIL(ANSFM_ERR_UNSUPPORTED, fn + "meet a table of one g-ordinate (the windowed walk)");
+        std::string why;
+        if (ms_variants_validate(*c.pv, n_models, c.ncont, c.nth, &why)) FAIL(ANSFM_ERR_INVALID, fn + "do not fit the call: " + why);
+        if (c.pv->phasarr.size() != (size_t)(c.pv->V - 1) * c.ncont * W * 2 * c.nth)
+            FAIL(ANSFM_ERR_INVALID, fn + "were set on a table of another width");
+    }
     // (a runtime line source has its own row map, which the (p, T, amount) comparison of the layer cache does not see)
     const bool use_cache = n_models > 1 && ctx->dedup && kn.layer_cache && !ctx->lblrt;      // any stream count
     if (!use_cache && c.W_full != W)
@@ -887,16 +984,21 @@ static int cirsrad_ck_scatter_batch_impl(ansfm_ctx *ctx, const MsCall &c, const 
         return rc;
     if ((rc = gas_opacity(ctx, k.rows, k.press, k.temp, k.amount))) return rc;
     ctx->last_n = n_models; ctx->last_L = L; ctx->last_rows = k.rows; ctx->last_dedup = 1;
+    MsVariantPlan vp;
+    const unsigned char *d_diff = nullptr;
+    const int *d_pvar = nullptr;
+    if (c.pv && (rc = ms_stage_variants(ctx, c, vp, p, &d_pvar, &d_diff))) return rc;
     unsigned char *same;
     int npre;
-    if ((rc = ms_same_layers(ctx, c, kn, s, p.lookup, &same, &npre))) return rc;
+    std::vector<int> ids;                                       // the launch order of models 1 .. n-1
+    if ((rc = ms_same_layers(ctx, c, kn, s, p.lookup, d_pvar, d_diff, &same, &npre, &ids))) return rc;
     p.phasarr = s.phas; p.radg = s.rg; p.solar = s.sol;
     p.brdf = s.brdf; p.tauray = d_tauray; p.lfrac = s.lf;
     if (p.nmu_real && (rc = ms_pad_inputs(ctx, c.nmu, (size_t)n_models * W, (size_t)W, c.nf, &p.radg, &p.brdf))) return rc;
-    if (G > 1 && (rc = ms_walk_axis(ctx, c, r, p))) return rc;
+    if (G > 1 && (rc = ms_walk_axis(ctx, c, r, c.pv ? &vp : nullptr, p))) return rc;
     MsSlabs sl;
     if ((rc = ms_plan_slabs(ctx, c, kn, r, npre, p, sl)) || (rc = ms_wire_batch(ctx, c, s, r, same, npre, sl, p)) ||
-        (rc = ms_run_slabs(ctx, c, s, r, sl, p)))
+        (rc = ms_run_slabs(ctx, c, s, r, sl, ids, p)))
         return rc;
     // below 16 streams every Fourier order was worked through: k_ms_fourier applies the reference's convergence break per model
     return ms_gquad(ctx, n_models, c.ngeom, s.xf, c.SPECOUT, nullptr, r.chain == MsChain::mfma16 ? nullptr : &p);
@@ -911,9 +1013,11 @@ int ansfm_cirsrad_ck_scatter_batch(ansfm_ctx *ctx, int ISPACE, int n_models, int
                                    int iray, int imie, const double *xfac, double *SPECOUT)
 {
     CHECK_CTX(ctx);
-    const MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat, ncont, nth, phasarr,
-                   lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray,
-                   imie, xfac, SPECOUT, nullptr, ctx->W, 0};
+    const MsVariantSet pv = ms_take_variants(ctx);
+    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat, ncont, nth, phasarr,
+             lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray,
+             imie, xfac, SPECOUT, nullptr, ctx->W, 0};
+    c.pv = pv.armed() ? &pv : nullptr;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 
@@ -926,12 +1030,14 @@ int ansfm_cirsrad_ck_scatter_batch_slice(ansfm_ctx *ctx, int ISPACE, int n_model
                                          int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
 {
     CHECK_CTX(ctx);
+    const MsVariantSet pv = ms_take_variants(ctx);              // (refused below unless the slice is the whole axis)
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter_batch_slice: upload a k-table first");
     if (w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
         FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_slice: the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
-    const MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat, ncont, nth, phasarr,
-                   lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray,
-                   imie, xfac, SPECOUT, nullptr, W_full, w_begin};
+    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia, taudust, tauray, tauscat, ncont, nth, phasarr,
+             lfrac, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf, nphi, iray,
+             imie, xfac, SPECOUT, nullptr, W_full, w_begin};
+    c.pv = pv.armed() ? &pv : nullptr;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 
@@ -945,12 +1051,14 @@ int ansfm_cirsrad_ck_scatter_batch_rows(ansfm_ctx *ctx, int ISPACE, int n_models
                                         int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin)
 {
     CHECK_CTX(ctx);
+    const MsVariantSet pv = ms_take_variants(ctx);
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, "cirsrad_ck_scatter_batch_rows: upload a k-table first");
     if (!cont_row || w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
         FAIL(ANSFM_ERR_INVALID, "cirsrad_ck_scatter_batch_rows: no cont_row, the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
-    const MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia_rows, taudust_rows, tauray_rows, tauscat_rows, ncont,
-                   nth, phasarr, lfrac_rows, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf,
-                   nphi, iray, imie, xfac, SPECOUT, nullptr, W_full, w_begin, R, cont_row};
+    MsCall c{ISPACE, n_models, L, lay_press_pa, lay_temp, amount, taucia_rows, taudust_rows, tauray_rows, tauscat_rows, ncont,
+             nth, phasarr, lfrac_rows, radg, ngeom, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, nmu, mu1, wt1, nf,
+             nphi, iray, imie, xfac, SPECOUT, nullptr, W_full, w_begin, R, cont_row};
+    c.pv = pv.armed() ? &pv : nullptr;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
 }
 
@@ -965,6 +1073,8 @@ int ansfm_cirsrad_ck_scatter_batch_cont(ansfm_ctx *ctx, int ISPACE, int n_models
 {
     CHECK_CTX(ctx);
     const std::string fn = "cirsrad_ck_scatter_batch_cont: ";
+    if (ms_take_variants(ctx).armed())
+        FAIL(ANSFM_ERR_UNSUPPORTED, fn + "pending phase variants (ansfm_set_phase_variants): the resident aerosol source has no model axis");
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
     if (w_begin < 0 || (long)w_begin + ctx->W > (long)W_full || (ncont > 0 && !phasarr))
         FAIL(ANSFM_ERR_INVALID, fn + "the table is not a slice [w_begin, w_begin + W) of W_full, or no phasarr");
@@ -991,6 +1101,8 @@ int ansfm_cirsrad_ck_scatter_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models,
 {
     CHECK_CTX(ctx);
     const std::string fn = "cirsrad_ck_scatter_batch_src: ";
+    if (ms_take_variants(ctx).armed())
+        FAIL(ANSFM_ERR_UNSUPPORTED, fn + "pending phase variants (ansfm_set_phase_variants): the resident aerosol source has no model axis");
     if (!ctx->have_table) FAIL(ANSFM_ERR_NOTABLE, fn + "upload a k-table first");
     if (W_full != ctx->W || w_begin != 0)
         FAIL(ANSFM_ERR_UNSUPPORTED, fn + "the whole axis only (a slice's context does not hold the grid the source lives on)");
@@ -1012,6 +1124,41 @@ int ansfm_cirsrad_ck_scatter_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models,
         if (!(theta_deg[t] > theta_deg[t - 1])) FAIL(ANSFM_ERR_INVALID, fn + "theta_deg (Scatter.THETA) must be strictly ascending");
     c.theta_deg = theta_deg; c.mu_theta = mu_theta;
     return cirsrad_ck_scatter_batch_impl(ctx, c, MsKnobs());
+}
+
+int ansfm_set_phase_variants(ansfm_ctx *ctx, int n_models, int V, const int32_t *phase_of, int ncont, int nth,
+                             const double *phasarr_variants)
+{
+    CHECK_CTX(ctx);
+    ctx->ms_pv = MsVariantSet();
+    if (V <= 1 || !phase_of || !phasarr_variants) return ANSFM_OK;
+    if (!ctx->have_table || n_models <= 0 || ncont <= 0 || nth < 3)
+        FAIL(ANSFM_ERR_INVALID, "set_phase_variants: upload a table first; n_models > 0, ncont > 0, nth >= 3");
+    MsVariantSet s;
+    s.n_models = n_models; s.V = V; s.ncont = ncont; s.nth = nth;
+    s.phase_of.assign(phase_of, phase_of + n_models);
+    s.phasarr.assign(phasarr_variants, phasarr_variants + (size_t)(V - 1) * ncont * ctx->W * 2 * nth);
+    ctx->ms_pv = std::move(s);
+    return ANSFM_OK;
+}
+
+int ansfm_last_scatter_variants(const ansfm_ctx *cctx, int64_t *pairs, int64_t *bytes, double *walk_ms)
+{
+    ansfm_ctx *ctx = const_cast<ansfm_ctx *>(cctx);
+    CHECK_CTX(ctx);
+    if (pairs) *pairs = ctx->ms_var_pairs;
+    if (bytes) *bytes = ctx->ms_var_bytes;
+    if (walk_ms) {
+        *walk_ms = -1.0;
+        if (ctx->ms_walk_timed) {
+            float t = 0.f;
+            HIPCHK(hipSetDevice(ctx->device));
+            HIPCHK(hipEventSynchronize(ctx->ms_walk_ev[1]));
+            HIPCHK(hipEventElapsedTime(&t, ctx->ms_walk_ev[0], ctx->ms_walk_ev[1]));
+            *walk_ms = t;
+        }
+    }
+    return ANSFM_OK;
 }
 
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total)

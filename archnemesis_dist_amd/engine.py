@@ -58,6 +58,9 @@ class _PcArgs:
 
 
 class AnsfmEngine:
+    # `cirsrad_ck_scatter_batch` / `_rows` take phase_of / phasarr_variants (callers tell this engine from older ones and doubles)
+    scatter_phase_variants = True
+
     def __init__(self, device=0):
         self._lib = _lib.load()
         self._ctx = C.c_void_p()
@@ -707,6 +710,47 @@ class AnsfmEngine:
         finally:
             self._lib.ansfm_set_shared_gas_gradient(self._ctx, 0, None)
 
+    @contextlib.contextmanager
+    def _phase_variants(self, what, W, phase_of, phasarr_variants):
+        """Arms the per-model phase functions (ansfm_set_phase_variants), or nothing for None, for the batched scattering call
+        made inside the block.  The library copies the arrays and forgets the setting with the call that meets it; leaving
+        the block cancels it if no call was reached."""
+        if phase_of is None and phasarr_variants is None:
+            yield
+            return
+        if phase_of is None or phasarr_variants is None:
+            raise ValueError(what + ": phase_of and phasarr_variants go together")
+        po = np.asarray(phase_of)
+        if po.ndim != 1 or po.dtype.kind not in "iu":
+            raise ValueError(what + ": phase_of must be an integer array (n_models,)")
+        po = _np(po, np.int32)
+        pv = _np(phasarr_variants)
+        if pv.ndim != 5 or pv.shape[2] != W or pv.shape[3] != 2:
+            raise ValueError(what + f": phasarr_variants must be (V - 1, NDUST, NWAVE = {W}, 2, NTHETA), got {pv.shape}")
+        if pv.shape[0] == 0:                    # V = 1: variant 0 alone, the plain call
+            yield
+            return
+        self._check(self._lib.ansfm_set_phase_variants(self._ctx, po.shape[0], pv.shape[0] + 1, _ptr(po), pv.shape[1], pv.shape[4],
+                                                       _ptr(pv)), "set_phase_variants")
+        try:
+            yield
+        finally:
+            self._lib.ansfm_set_phase_variants(self._ctx, 0, 1, None, 0, 0, None)
+
+    def last_scatter_variants(self):
+        """((variant, population) pairs whose phase matrices and Hansen factors were formed beside variant 0's, bytes of the
+        buffers of variants 1 .. V-1) of the last batched scatter call; (0, 0) without phase variants"""
+        a = C.c_int64(); b = C.c_int64()
+        self._check(self._lib.ansfm_last_scatter_variants(self._ctx, C.byref(a), C.byref(b), None), "last_scatter_variants")
+        return int(a.value), int(b.value)
+
+    def last_scatter_walk_ms(self):
+        """milliseconds the phase matrices and the Hansen walk of the last batched scatter call took on the device (variants'
+        pairs and their copy included); -1.0 when that call had no such stage of its own (one g-ordinate, model by model)"""
+        t = C.c_double()
+        self._check(self._lib.ansfm_last_scatter_variants(self._ctx, None, None, C.byref(t)), "last_scatter_variants")
+        return float(t.value)
+
     def _last3(self, fn, what):
         info = (C.c_double * 3)()
         self._check(fn(self._ctx, C.byref(info)), what)
@@ -1114,7 +1158,7 @@ class AnsfmEngine:
 
     def cirsrad_ck_scatter_batch(self, ISPACE, lay_press_pa, lay_temp, amount, TAUCIA, TAUDUST, TAURAY, TAUSCAT, phasarr, lfrac,
                                  radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie,
-                                 xfac=None, wave_slice=None):
+                                 xfac=None, wave_slice=None, phase_of=None, phasarr_variants=None):
         """The scattering branch of CIRSrad for the n forward models of a numerical Jacobian (ansfm_cirsrad_ck_scatter_batch):
         lay_press_pa / lay_temp (n, NLAY), amount (n, NGAS, NLAY), TAUCIA / TAUDUST / TAURAY / TAUSCAT (n, NWAVE, NLAY) or None,
         lfrac (n, NWAVE, NDUST, NLAY), radg (n, NWAVE, NMU); the rest as `cirsrad_ck_scatter` -> SPECOUT (n, NWAVE, NPATH).
@@ -1123,7 +1167,13 @@ class AnsfmEngine:
         wave_slice = (w_begin, W_full): the uploaded table is the slice [w_begin, w_begin + NWAVE) of a W_full axis
         (ansfm_cirsrad_ck_scatter_batch_slice).  phasarr then covers the whole axis, (NDUST, W_full, 2, NTHETA); every other
         per-wavenumber input and the result cover the slice.  The slices side by side equal the call over the whole axis, bit
-        for bit."""
+        for bit.
+
+        phase_of (n,) int and phasarr_variants (V - 1, NDUST, NWAVE, 2, NTHETA): per-model phase functions
+        (ansfm_set_phase_variants).  Model m runs with variant phase_of[m]; variant 0 is phasarr and phase_of[0] must be 0.
+        Every spectrum has the bits of `cirsrad_ck_scatter` with that model's phase function; a layer stays model 0's where none
+        of the changed populations is present (lfrac == 0).  Whole axis and more than one g-ordinate only: NotImplementedError
+        with wave_slice or an LBL table, and when the variants' buffers find no room."""
         dims, _ = self.ktable_info()
         W, G, S = dims[0], dims[1], dims[4]
         lp = _np(lay_press_pa); n, L = lp.shape
@@ -1139,24 +1189,27 @@ class AnsfmEngine:
                 _ptr(nwl(TAUDUST)), _ptr(nwl(TAURAY)), _ptr(nwl(TAUSCAT)), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol),
                 _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf),
                 int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out))
-        if wave_slice is None:
-            self._check(self._lib.ansfm_cirsrad_ck_scatter_batch(*args), "cirsrad_ck_scatter_batch")
+        with self._phase_variants("cirsrad_ck_scatter_batch", W, phase_of, phasarr_variants):
+            if wave_slice is None:
+                self._check(self._lib.ansfm_cirsrad_ck_scatter_batch(*args), "cirsrad_ck_scatter_batch")
+                return out
+            w_begin, W_full = (int(v) for v in wave_slice)
+            if phasarr is not None and phasarr.shape[1] != W_full:
+                raise ValueError("cirsrad_ck_scatter_batch: with wave_slice, phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
+            self._check(self._lib.ansfm_cirsrad_ck_scatter_batch_slice(*args, W_full, w_begin), "cirsrad_ck_scatter_batch_slice")
             return out
-        w_begin, W_full = (int(v) for v in wave_slice)
-        if phasarr is not None and phasarr.shape[1] != W_full:
-            raise ValueError("cirsrad_ck_scatter_batch: with wave_slice, phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
-        self._check(self._lib.ansfm_cirsrad_ck_scatter_batch_slice(*args, W_full, w_begin), "cirsrad_ck_scatter_batch_slice")
-        return out
 
     def cirsrad_ck_scatter_batch_rows(self, ISPACE, lay_press_pa, lay_temp, amount, cont_row, TAUCIA_rows, TAUDUST_rows, TAURAY_rows,
                                       TAUSCAT_rows, phasarr, lfrac_rows, radg, sol_angs, emiss_angs, aphis, solar, lowbc,
-                                      brdf_matrix, mu1, wt1, nf, nphi, iray, imie, xfac=None, wave_slice=None):
+                                      brdf_matrix, mu1, wt1, nf, nphi, iray, imie, xfac=None, wave_slice=None, phase_of=None,
+                                      phasarr_variants=None):
         """`cirsrad_ck_scatter_batch` with the continuum once per distinct layer (ansfm_cirsrad_ck_scatter_batch_rows):
         cont_row (n, NLAY) int, the continuum row of every (model, layer); TAUCIA_rows / TAUDUST_rows / TAURAY_rows / TAUSCAT_rows
         (R, NWAVE) or None and lfrac_rows (R, NDUST, NWAVE), wavenumber fastest (`continuum_rows.ContinuumRows` packs them).
         The rest, wave_slice included, as `cirsrad_ck_scatter_batch` -> SPECOUT (n, NWAVE, NPATH), bit-identical to that call
         with the expanded arrays.  A layer is taken from model 0's doubling results when its gas inputs are model 0's and
-        cont_row[m, l] == cont_row[0, l]."""
+        cont_row[m, l] == cont_row[0, l] -- and, with phase_of / phasarr_variants (as in `cirsrad_ck_scatter_batch`), when the
+        layer's lfrac row is 0 for every population whose phase function differs from model 0's."""
         dims, _ = self.ktable_info()
         W, G, S = dims[0], dims[1], dims[4]
         lp = _np(lay_press_pa)
@@ -1191,12 +1244,13 @@ class AnsfmEngine:
         if phasarr is not None and phasarr.shape[1] != W_full:
             raise ValueError("cirsrad_ck_scatter_batch_rows: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
         out = np.empty((n, W, P))
-        rc = self._lib.ansfm_cirsrad_ck_scatter_batch_rows(
-            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(R), _ptr(cr), _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
-            _ptr(rows[3]), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)),
-            int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie),
-            _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
-        self._check(rc, "cirsrad_ck_scatter_batch_rows")
+        with self._phase_variants("cirsrad_ck_scatter_batch_rows", W, phase_of, phasarr_variants):
+            rc = self._lib.ansfm_cirsrad_ck_scatter_batch_rows(
+                self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(R), _ptr(cr), _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
+                _ptr(rows[3]), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)),
+                int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie),
+                _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
+            self._check(rc, "cirsrad_ck_scatter_batch_rows")
         return out
 
     def cirsrad_ck_scatter_batch_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phasarr,

@@ -250,7 +250,7 @@ class JacobianGPU:
                     if rec is None:
                         rec = self._ansfm_scatter_inputs()
                         if rec is not None and hasattr(eng, "cirsrad_ck_scatter_batch_rows"):
-                            self._ansfm_pack_scatter(rec, packers[IAV])
+                            self._ansfm_pack_scatter(rec, packers[IAV], variants=self._ansfm_phase_variants(eng))
                     if rec is None:
                         rec = self._ansfm_singlescatt_inputs(eng)
                     if rec is None:                  # a CIRSrad branch without a batch axis: this state runs on its own
@@ -518,21 +518,41 @@ class JacobianGPU:
         return rec
 
     @staticmethod
-    def _ansfm_scatter_key(r):
-        """States that may share one batched scattering call: everything without a model axis in ansfm_cirsrad_ck_scatter_batch"""
+    def _ansfm_phase_variants(eng):
+        """The engine's batched scattering entries take per-model phase functions (phase_of / phasarr_variants)"""
+        return bool(getattr(eng, "scatter_phase_variants", False))
+
+    @staticmethod
+    def _ansfm_scatter_key(r, variants=False):
+        """States that may share one batched scattering call: everything without a model axis in ansfm_cirsrad_ck_scatter_batch.
+        variants: the engine gives the phase function a model axis (ansfm_set_phase_variants), so PHASE's bytes leave the key
+        -- its shape and IMIE stay -- and states that differ in an aerosol's phase function share a call."""
         b = lambda a: np.ascontiguousarray(a, dtype=np.float64).tobytes()
-        return ("scatter", r["ISPACE"], r["lp"].shape, r["PHASE"].shape, b(r["PHASE"]), b(r["SOL_ANG"]), b(r["EMISS_ANG"]),
-                b(r["AZI_ANG"]), b(r["solar"]), r["LOWBC"], b(r["BRDF"]), b(r["MU"]), b(r["WTMU"]), r["NF"], r["NPHI"], r["IRAY"],
-                r["IMIE"])
+        return ("scatter", r["ISPACE"], r["lp"].shape, r["PHASE"].shape, b"variants" if variants else b(r["PHASE"]), b(r["SOL_ANG"]),
+                b(r["EMISS_ANG"]), b(r["AZI_ANG"]), b(r["solar"]), r["LOWBC"], b(r["BRDF"]), b(r["MU"]), b(r["WTMU"]), r["NF"], r["NPHI"],
+                r["IRAY"], r["IMIE"])
+
+    @staticmethod
+    def _ansfm_phase_groups(recs, ks):
+        """The PHASE arrays of the states ks de-duplicated by bytes, in order of first appearance -> (phase_of (n,) int32, the
+        distinct arrays); variant 0 is the first state's"""
+        seen, arrays, phase_of = {}, [], []
+        for k in ks:
+            a = np.ascontiguousarray(recs[k]["PHASE"], dtype=np.float64)
+            v = seen.setdefault(a.tobytes(), len(arrays))
+            if v == len(arrays):
+                arrays.append(a)
+            phase_of.append(v)
+        return np.asarray(phase_of, dtype=np.int32), arrays
 
     _SCATTER_CONTINUUM = ("TAUCIA", "TAUDUST", "TAURAY", "TAUSCAT", "FRAC")
 
-    def _ansfm_pack_scatter(self, rec, packers):
+    def _ansfm_pack_scatter(self, rec, packers, variants=False):
         """A staged scattering record joins the packer of its group (`packers`: group key -> ContinuumRows, one dict per
         batched call): its five continuum arrays are kept once per distinct layer and leave the record, which remembers the
         packer and its position in it.  The group then goes through cirsrad_ck_scatter_batch_rows."""
         from .continuum_rows import ContinuumRows
-        key = self._ansfm_scatter_key(rec)
+        key = self._ansfm_scatter_key(rec, variants)
         pk = packers.get(key)
         if pk is None:
             pk = packers[key] = ContinuumRows(rec["lp"].shape[0], rec["PHASE"].shape[0])
@@ -578,7 +598,7 @@ class JacobianGPU:
             if "alone" in r:
                 out[k] = np.asarray(r["alone"]).reshape(W, -1)
             elif r.get("scatter"):
-                groups.setdefault(r.get("key") or self._ansfm_scatter_key(r), []).append(k)
+                groups.setdefault(r.get("key") or self._ansfm_scatter_key(r, self._ansfm_phase_variants(eng)), []).append(k)
             elif r.get("transmission"):
                 groups.setdefault(self._ansfm_transmission_key(r), []).append(k)
             elif r.get("singlescatt"):
@@ -592,27 +612,47 @@ class JacobianGPU:
             st = lambda name: np.stack([recs[k][name] for k in ks])
             if key[0] == "scatter":
                 # the NX + 1 multiple-scattering forward models the reference runs when ISCAT != THERMAL_EMISSION (:2251-2252)
+                cont = None
                 if "rows" in r0:             # packed while staged (_ansfm_pack_scatter): the group is the packer's states, in order
                     pk = r0["rows"][0]
                     if [recs[k]["rows"] for k in ks] != [(pk, j) for j in range(pk.n_states)]:
                         raise RuntimeError("staged scattering records and their packer disagree")
-                    cont_row, cia, dust, ray, sca, frac = pk.rows()
-                    spec = eng.cirsrad_ck_scatter_batch_rows(r0["ISPACE"], st("lp"), st("lt"), st("f_gas"), cont_row, cia, dust, ray, sca,
-                                                             r0["PHASE"], frac, st("RADGROUND"), r0["SOL_ANG"], r0["EMISS_ANG"], r0["AZI_ANG"], r0["solar"],
-                                                             r0["LOWBC"], r0["BRDF"], r0["MU"], r0["WTMU"], r0["NF"], r0["NPHI"],
-                                                             r0["IRAY"], r0["IMIE"])
+                    cont = pk.rows()
+
+                def run(sub, pos, **kw):
+                    """the states sub (positions pos of the group) in one call, the first one's PHASE as phasarr"""
+                    q0 = recs[sub[0]]
+                    sk = lambda name: np.stack([recs[k][name] for k in sub])
+                    tail = (q0["SOL_ANG"], q0["EMISS_ANG"], q0["AZI_ANG"], q0["solar"], q0["LOWBC"], q0["BRDF"], q0["MU"], q0["WTMU"],
+                            q0["NF"], q0["NPHI"], q0["IRAY"], q0["IMIE"])
+                    if cont is not None:     # a part of the group reads the group's rows through its own lines of cont_row
+                        spec = eng.cirsrad_ck_scatter_batch_rows(q0["ISPACE"], sk("lp"), sk("lt"), sk("f_gas"), cont[0][pos], *cont[1:5],
+                                                                 q0["PHASE"], cont[5], sk("RADGROUND"), *tail, **kw)
+                    else:
+                        spec = eng.cirsrad_ck_scatter_batch(q0["ISPACE"], sk("lp"), sk("lt"), sk("f_gas"), sk("TAUCIA"), sk("TAUDUST"),
+                                                            sk("TAURAY"), sk("TAUSCAT"), q0["PHASE"], sk("FRAC"), sk("RADGROUND"), *tail, **kw)
+                    spec = np.asarray(spec).reshape(len(sub), W, -1)
+                    cached = (0, 0)
+                    if hasattr(eng, "last_scatter_cache"):
+                        cached = eng.last_scatter_cache()     # layers of models 1.. taken from model 0's doublings / all of them
+                    for j, k in enumerate(sub):
+                        out[k] = spec[j]
+                    return cached
+
+                nlay = int(r0["lp"].shape[0])
+                calls = None
+                phase_of, phases = self._ansfm_phase_groups(recs, ks)
+                if len(phases) > 1:          # only with an engine that takes variants: otherwise PHASE's bytes are in the key
+                    try:
+                        calls = [run(ks, slice(None), phase_of=phase_of, phasarr_variants=np.stack(phases[1:]))]
+                    except NotImplementedError:               # a slice, an LBL table, no room: one call per phase function, as before
+                        calls = [run([k for k, v in zip(ks, phase_of) if v == i], np.flatnonzero(phase_of == i))
+                                 for i in range(len(phases))]
                 else:
-                    spec = eng.cirsrad_ck_scatter_batch(r0["ISPACE"], st("lp"), st("lt"), st("f_gas"), st("TAUCIA"), st("TAUDUST"),
-                                                        st("TAURAY"), st("TAUSCAT"), r0["PHASE"], st("FRAC"), st("RADGROUND"),
-                                                        r0["SOL_ANG"], r0["EMISS_ANG"], r0["AZI_ANG"], r0["solar"], r0["LOWBC"], r0["BRDF"],
-                                                        r0["MU"], r0["WTMU"], r0["NF"], r0["NPHI"], r0["IRAY"], r0["IMIE"])
-                spec = np.asarray(spec).reshape(len(ks), W, -1)
+                    calls = [run(ks, slice(None))]
                 if hasattr(eng, "last_scatter_cache"):
-                    a, b = eng.last_scatter_cache()           # layers of models 1.. taken from model 0's doublings / all of them
-                    nlay = int(r0["lp"].shape[0])
-                    rc += (b - a) + nlay; rt += b + nlay
-                for j, k in enumerate(ks):
-                    out[k] = spec[j]
+                    for a, b in calls:
+                        rc += (b - a) + nlay; rt += b + nlay
                 continue
             if key[0] == "transmission":
                 spec = eng.cirsrad_ck_transmission(st("lp"), st("lt"), st("f_gas"), st("taucont"), r0["NLAYIN"], r0["LAYINC"],

@@ -717,6 +717,41 @@ int ansfm_cirsrad_ck_scatter_batch_src(ansfm_ctx *ctx, int ISPACE, int n_models,
                                        const double *sol_angs, const double *emiss_angs, const double *aphis, const double *solar,
                                        int lowbc, const double *brdf_matrix, int nmu, const double *mu1, const double *wt1, int nf,
                                        int nphi, int iray, int imie, const double *xfac, double *SPECOUT, int W_full, int w_begin);
+/* Per-model phase functions inside the batch: the states of a Jacobian that change an aerosol population's phase function
+ * (a size distribution or a refractive index, Models/PreRTModels/model_444.py) join the batch instead of running on their own.
+ * A pending setting in the style of ansfm_set_shared_gas_gradient: phase_of [n_models] (host) names the variant of every model,
+ * 0 <= phase_of < V; variant 0 is the phasarr argument of the consuming call and phase_of[0] must be 0; phasarr_variants
+ * [V - 1][ncont][W][2][nth] (host, W = the uploaded table's width) holds variants 1 .. V-1.  THE LIBRARY COPIES BOTH ARRAYS AT
+ * SET TIME: the caller may free them as soon as this returns.  The setting arms the NEXT ansfm_cirsrad_ck_scatter_batch or
+ * ansfm_cirsrad_ck_scatter_batch_rows call on the whole axis and is then forgotten, whether that call succeeds or fails; V <= 1
+ * or a NULL array cancels it.  Every spectrum has the bits of a separate ansfm_cirsrad_ck_scatter call of that model with its
+ * variant's phasarr.
+ * Per variant the components whose [W][2][nth] block differs from variant 0's in any bit are found on the host; only those
+ * (variant, component) pairs are integrated (k_ms_phase) and walked (k_ms_hansen_seq), in the same two launches as variant 0's
+ * components -- the walk keeps one history per scatterer, so an unchanged component, Rayleigh always, has variant 0's matrices
+ * and factors bit for bit and is copied on the device.  A variant's matrices and factors keep variant 0's layout, one variant
+ * behind the other (V times the bytes of one; ansfm_last_scatter_variants reports the pairs beyond variant 0's and the bytes
+ * of variants 1 .. V-1 in the last batched call, and in walk_ms the time between two events around the phase-matrix launch,
+ * the walk and the copy of that call -- with or without variants; -1 when the call had none, as at G = 1), reserved before
+ * the layer cache is sized.
+ * A layer of model m counts as model 0's only if, besides the rules above, no population whose phase function differs between
+ * m's variant and variant 0 is present in it: its fraction lfrac is 0 at every wavenumber (the layer's lfrac row in the rows
+ * form).  The mixing sum then gains a term fs P 0 = +-0, which changes no bit of a non-zero sum; where the sum before the term
+ * is an exact zero its sign could differ between variants -- not observed in any test; the rule would be narrowed if it were.
+ * THE RULE ASSUMES FINITE PHASE MATRICES (0 times an infinity or a NaN is a NaN).  A model that shares every layer is legal.
+ * The model-by-model route (ansfm_set_layer_dedup(ctx, 0), ANSFM_MS_LAYER_CACHE=0) hands each model its variant's phasarr.
+ * The consuming call returns, before anything is launched,
+ *   ANSFM_ERR_INVALID      n_models, ncont or nth differ from the call's (or the table's width changed since the setting),
+ *                          a phase_of entry is outside [0, V), phase_of[0] != 0;
+ *   ANSFM_ERR_UNSUPPORTED  the call is a slice (W_full != W_local), the table has one g-ordinate (G = 1: the windowed walk with
+ *                          carries), or the entry is ansfm_cirsrad_ck_scatter_batch_cont / _src (their resident aerosol
+ *                          source has no model axis for the cross sections, so a size-distribution state cannot be expressed);
+ * and ANSFM_ERR_UNSUPPORTED later when the variants' buffers cannot be reserved: the caller then groups its states by phase
+ * function as before.  ansfm_set_phase_variants itself: ANSFM_ERR_INVALID without a table or for n_models <= 0, ncont <= 0,
+ * nth < 3. */
+int ansfm_set_phase_variants(ansfm_ctx *ctx, int n_models, int V, const int32_t *phase_of, int ncont, int nth,
+                             const double *phasarr_variants);
+int ansfm_last_scatter_variants(const ansfm_ctx *ctx, int64_t *pairs, int64_t *bytes, double *walk_ms);
 int ansfm_last_scatter_cache(const ansfm_ctx *ctx, int64_t *layers_from_cache, int64_t *layers_total);
 /* Spectral windows of phase matrices / Hansen factors in the last scattering call (ansfm_cirsrad_ck_scatter(_batch),
  * ansfm_scloud11wave_core) and the wavenumbers per window: 1 and W when one window covers the axis (always at G > 1). */

@@ -64,6 +64,8 @@ def main():
         bench_scatter_cont(eng, out)
     if only == "phase":                                     # 131 MB of phase functions per population on the host: on request only
         bench_phase(eng, out, rng)
+    if only == "ms_phase":                                  # 0.3 GB of phase functions on the host, tens of GB of variants on the device
+        bench_ms_phase(eng, out)
     print(json.dumps(out, indent=1))
 
 
@@ -367,6 +369,107 @@ def bench_scatter_cont(eng, out, W=10000, n=5):
                     r["fused_equals_by_hand"] = bool(np.array_equal(YN, YN_b) and np.array_equal(KK, KK_b))
             res["%s_nmu%d_nf%d" % (part, NMU, NF)] = r
     out["jacobian_C4_scatter_cont"] = res
+
+
+def bench_ms_phase(eng, out, W=10000, n=2):
+    """C4-size scattering Jacobian with aerosol states (W = 1e4, G = 20, 100 layers, 8 gases, two aerosol populations and
+    Rayleigh): 201 profile states (the base, one layer's temperature each, one layer's gas amount each) plus 20 states that
+    change population 0's phase function -- 20 variants -- and its opacity in the 10 layers that hold it; 16 streams / NF 8 and
+    5 / NF 2.
+      (a) variants: ONE cirsrad_ck_scatter_batch_rows call of the 221 states with phase_of / phasarr_variants;
+      (b) parent:   what a checkout without the keywords does for the same states -- one batched call of the 201 states that
+          share the phase function plus one batched call of one model per aerosol state.  Runs on such a checkout too ((a) is
+          left out there).
+        python tools/bench_extra.py ms_phase [W] [repeats] [5|16: that stream count only]"""
+    import torch
+    import bench as B
+    if len(sys.argv) > 2:
+        W = int(sys.argv[2])
+    n = int(sys.argv[3]) if len(sys.argv) > 3 else n
+    streams = [(16, 8), (5, 2)] if len(sys.argv) <= 4 else [s for s in [(16, 8), (5, 2)] if s[0] == int(sys.argv[4])]
+    dev = torch.device("cuda", eng.device)
+    G, S, L, NP, NT, ND, NV, LAYERS = 20, 8, 100, 20, 15, 2, 20, range(40, 50)
+    rng = np.random.default_rng(20261021)
+    _, delg = syn.gauss_legendre_01(G, as_float32=True)
+    WAVE = 200.0 + (1000.0 / W) * np.arange(W)
+    PRESS, TEMP, K = B.torch_ktable(torch, dev, W, G, NP, NT, S, seed=20260704)
+    eng.upload_ktable(K, PRESS.astype(np.float32), TEMP.astype(np.float32), WAVE, delg.astype(np.float32)); del K
+    torch.cuda.empty_cache()
+    atm = syn.synth_atmosphere(L, S, seed=2)
+    lay_p, lay_t, amount = atm["lay_press_pa"][0], atm["lay_temp"][0], atm["amount"][0]
+    # the continuum by rows: the base's 100 layers, then 10 rows per aerosol state
+    R = L + NV * len(LAYERS)
+    sc = np.zeros((R, ND, W))                                               # scattering opacity by population
+    sc[:L, 1] = 10.0 ** rng.uniform(-4, -2, (L, W))
+    for l in LAYERS:
+        sc[l, 0] = 10.0 ** rng.uniform(-3, -1.5, W)
+    cia = np.zeros((R, W)); ray = np.zeros((R, W))
+    cia[:L] = 10.0 ** rng.uniform(-5, -2, (L, W)); ray[:L] = 10.0 ** rng.uniform(-6, -3, (L, W))
+    n_prof, ns = 2 * L + 1, 2 * L + 1 + NV
+    cont_row = np.tile(np.arange(L, dtype=np.int32), (ns, 1))
+    for j in range(NV):
+        rows = L + j * len(LAYERS) + np.arange(len(LAYERS))
+        sc[rows] = sc[list(LAYERS)]; sc[rows, 0] *= 1.0 + 0.02 * (j + 1)
+        cia[rows] = cia[list(LAYERS)]; ray[rows] = ray[list(LAYERS)]
+        cont_row[n_prof + j, list(LAYERS)] = rows
+    sca = sc.sum(axis=1)
+    dust = sca * 1.2
+    frac = np.where(sca[:, None, :] > 0, sc / np.where(sca > 0, sca, 1.0)[:, None, :], 0.0)
+    del sc
+    lp = np.tile(lay_p, (ns, 1)); lt = np.tile(lay_t, (ns, 1)); am = np.tile(amount, (ns, 1, 1))
+    for k in range(L):
+        lt[1 + k, k] *= 1.01
+        am[1 + L + k, k % S, k] *= 1.05
+    TH = np.linspace(0.0, 180.0, 41); cth = np.cos(np.deg2rad(TH))
+    hg = lambda g: (1 - g * g) / (1 + g * g - 2 * g * cth) ** 1.5 / (4 * np.pi)
+
+    def phasarr(g0):
+        ph = np.zeros((ND, W, 2, TH.size))
+        ph[0, :, 0, :] = hg(g0)[None]; ph[1, :, 0, :] = hg(0.3)[None]; ph[:, :, 1, :] = cth[None, None]
+        return np.ascontiguousarray(ph[:, :, :, ::-1])
+    ph = [phasarr(0.6)] + [phasarr(0.6 + 0.01 * (j + 1)) for j in range(NV)]
+    phase_of = np.concatenate([np.zeros(n_prof, dtype=np.int32), 1 + np.arange(NV, dtype=np.int32)])
+    have = bool(getattr(eng, "scatter_phase_variants", False))
+    res = {"W": W, "G": G, "S": S, "L": L, "states": ns, "variants": NV, "layers_with_the_changed_population": len(LAYERS),
+           "median_of": n}
+
+    def times(f):
+        f(); ts = []
+        for _ in range(n):
+            torch.cuda.synchronize(); t = time.perf_counter(); r = f(); torch.cuda.synchronize(); ts.append(time.perf_counter() - t)
+        return {"median_s": float(np.median(ts)), "min_s": float(min(ts)), "max_s": float(max(ts))}, r
+
+    for NMU, NF in streams:
+        xq, wq = np.polynomial.legendre.leggauss(NMU)
+        MU, WT = 0.5 * (xq + 1.0), 0.5 * wq
+        c1, c2 = 1.1911e-12, 1.439
+        radg = np.repeat((c1 * WAVE ** 3 / (np.exp(c2 * WAVE / lay_t[0]) - 1.0))[:, None], NMU, 1)
+        tail = ([30.0], [20.0], [45.0], np.full(W, 1.0e-8), 0, np.zeros((W, NMU, NMU, NF + 1)), MU, WT, NF, 101, 1, 1)
+
+        def call(sel, phasarr0, **kw):
+            return eng.cirsrad_ck_scatter_batch_rows(0, lp[sel], lt[sel], am[sel], cont_row[sel], cia, dust, ray, sca, phasarr0, frac,
+                                                     np.tile(radg, (len(lp[sel]), 1, 1)), *tail, **kw)
+
+        def parent():
+            parts = [call(slice(0, n_prof), ph[0])]
+            walk = [eng.last_scatter_walk_ms()] if have else []
+            for j in range(NV):
+                parts.append(call(slice(n_prof + j, n_prof + j + 1), ph[1 + j]))
+            return np.concatenate(parts), walk
+
+        r = {}
+        r["parent_route"], (Yp, walk_p) = times(parent)
+        if walk_p:
+            r["parent_route_walk_ms_of_the_201_state_call"] = walk_p[0]
+        if have:
+            def variants():
+                Y = call(slice(None), ph[0], phase_of=phase_of, phasarr_variants=np.stack(ph[1:]))
+                return Y, eng.last_scatter_cache(), eng.last_scatter_variants(), eng.last_scatter_walk_ms()
+            r["variants"], (Yv, cache, (pairs, nbytes), walk_ms) = times(variants)
+            r["variants_cache"], r["variants_pairs"], r["variants_buffer_bytes"], r["variants_walk_ms"] = list(cache), pairs, nbytes, walk_ms
+            r["variants_equal_parent_route"] = bool(np.array_equal(Yv, Yp))
+        res["nmu%d_nf%d" % (NMU, NF)] = r
+    out["jacobian_C4_ms_phase"] = res
 
 
 def bench_next(eng, out, rng):
