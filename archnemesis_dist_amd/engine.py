@@ -30,6 +30,11 @@ def _ptr(a):
     return C.c_void_p(a.data_ptr())  # torch tensor
 
 
+def _ray_mode(IRAY, variant):
+    """ray_mode of include/ansfm.h: IRAY, or 12 for variant='v' (calc_tau_rayleighv)"""
+    return 12 if variant == "v" else int(IRAY)
+
+
 def _fingerprint(a):
     """Identity of a result array handed back to the caller: address, shape and a few sampled values, to recognise
     "the array I returned" when it comes back as the next step's input.  Arrays that have a device twin are handed out
@@ -392,6 +397,91 @@ class AnsfmEngine:
         return out
 
     # ---- fused CIRSrad (batch) ----------------------------------------------------------------
+    def _layer_args(self, what, lay_press_pa, lay_temp, amount, taucont=None, dtaucon=None, NPAR=None, *, model_axis, dims=None):
+        """The layer arrays of a CIRSrad entry as the library takes them -> n, L, single, lp (n, L), lt (n, L), am (n, NGAS, L),
+        tc (n, NWAVE, L) or None, dtc (n, NWAVE, NPAR, L) or None, contiguous float64.  model_axis: "optional" -- a leading
+        model axis or none (single: there was none, and the results drop it again); "required" -- lay_press_pa (n, L), and
+        lay_temp and amount exactly (n, L) and (n, NGAS, L); "none" -- one model, lay_press_pa (L,).  dims: those of the table
+        where the entry asks `ktable_info()` for them, else `self.dims`."""
+        dims = self.dims if dims is None else dims
+        W, S = dims[0], dims[4]
+        lp, lt, am = _np(lay_press_pa), _np(lay_temp), _np(amount)
+        single = lp.ndim == 1
+        if model_axis == "required":
+            if lp.ndim != 2:
+                raise ValueError(f"{what}: lay_press_pa must be (n_models, NLAY)")
+            n, L = lp.shape
+            if lt.shape != (n, L):
+                raise ValueError(f"{what}: lay_temp must be (n_models, NLAY)")
+            if am.shape != (n, S, L):
+                raise ValueError(f"{what}: amount must be (n_models, NGAS, NLAY)")
+        else:
+            if model_axis == "none" and not single:
+                raise ValueError(what + ": one model, lay_press_pa (NLAY,)")
+            lp = np.atleast_2d(lp); n, L = lp.shape
+            lt = lt.reshape(1, L) if model_axis == "none" else np.atleast_2d(lt)
+            am = am.reshape(n, S, L)
+        tc = None if taucont is None else _np(taucont).reshape(n, W, L)
+        dtc = None if dtaucon is None else _np(dtaucon).reshape(n, W, int(NPAR), L)
+        return n, L, single, lp, lt, am, tc, dtc
+
+    @staticmethod
+    def _path_args(what, NLAYIN, LAYINC, SCALE=None, EMTEMP=None, TSURF=None, n=1, exact=False):
+        """The path arrays of a CIRSrad entry -> int32 NLAYIN (P,) and LAYINC (LIMAX, P) (a 1-D LAYINC is one path), LIMAX, P,
+        and, where given, SCALE / EMTEMP (n, LIMAX, P) and TSURF (n,).  SCALE / EMTEMP are read as a stack of (LIMAX, P)
+        blocks, whatever their shape (`reshape(-1, LIMAX, P)`): one block serves every model, n blocks are the models'.
+        exact: only the shapes (LIMAX, P) and (n, LIMAX, P) are taken, so a transposed array is refused, not reread.
+        ValueError where NLAYIN is not (P,): the library reads P entries of it."""
+        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
+        if LAYINC.ndim == 1:
+            LAYINC = LAYINC[:, None]
+        LIMAX, P = LAYINC.shape
+        if NLAYIN.shape != (P,):
+            raise ValueError(f"{what}: NLAYIN must be (NPATH,)")
+
+        def over(name, a):
+            if a is None:
+                return None
+            a = _np(a)
+            if exact and a.shape not in ((LIMAX, P), (n, LIMAX, P)):
+                raise ValueError(f"{what}: {name} must be {(n, LIMAX, P)} or {(LIMAX, P)}, got {a.shape}")
+            return _np(np.broadcast_to(a.reshape(-1, LIMAX, P), (n, LIMAX, P)))
+        TS = None if TSURF is None else _np(np.broadcast_to(np.atleast_1d(_np(TSURF)), (n,)))
+        return NLAYIN, LAYINC, LIMAX, P, over("SCALE", SCALE), over("EMTEMP", EMTEMP), TS
+
+    @staticmethod
+    def _per_model_tsurf(what, TSURF, n):
+        TS = _np(np.atleast_1d(TSURF))
+        if TS.shape != (n,):
+            raise ValueError(f"{what}: TSURF must be (n_models,)")
+        return TS
+
+    def _gradient_result(self, single, spec, dspec, dts=None, device_chain=None):
+        """What a `cirsradg_ck_*` entry with a model axis hands back, and the chain to map2pro: device_chain (W, NPAR, LIMAX,
+        P) where dSPECOUT stayed on the device (dspec is None); else one model's dSPECOUT has a device twin, so the host array
+        goes out read-only and is recognised when it comes back.  The caller cleared the chain before the library call."""
+        if device_chain is not None:
+            self._chain_dspec = ("device",) + tuple(device_chain)
+        elif spec.shape[0] == 1:
+            dspec.flags.writeable = False
+            self._chain_dspec = _fingerprint(dspec[0])
+        out = (spec, dspec) if dts is None else (spec, dspec, dts)
+        return tuple(None if a is None else a[0] for a in out) if single else out
+
+    def _fused_gradient_call(self, what, L, dtau_every_gas, gradients_on_device, gshape, args, outs):
+        """One body for the fused one-model routes (transit, occultation, limb, disc): args are the library's arguments
+        between ctx and the outputs, outs the host outputs before the gradient, gshape (W, NPAR, L) or (W, NPAR, L, Q) the
+        gradient's.  Clears the chain, calls with dtau_every_gas armed, and arms ("device", W, NPAR, L, Q) where the gradient
+        stayed on the device.  -> (*outs, gradient or None)"""
+        grad = None if gradients_on_device else np.empty(gshape)
+        with self._shared_gas_gradient(what, dtau_every_gas, L):
+            self._chain_dspec = None
+            rc = getattr(self._lib, "ansfm_" + what)(self._ctx, *args, *(_ptr(o) for o in outs), _ptr(grad))
+        self._check(rc, what)
+        if gradients_on_device:
+            self._chain_dspec = ("device",) + tuple(gshape) + (() if len(gshape) == 4 else (1,))
+        return (*outs, grad)
+
     def calc_thermal_emission_spectrumg(self, ISPACE, WAVE, TAUTOT_PATH, dTAUTOT_PATH, NVMR, TEMP, PRESS, TSURF, EMISSIVITY):
         """ForwardModel_0.calc_thermal_emission_spectrumg (:6380), same arguments -> SPECOUT (NWAVE, NG),
         dSPECOUT (NWAVE, NG, NPAR, NLAYIN), dTSURF (NWAVE, NG)."""
@@ -410,27 +500,16 @@ class AnsfmEngine:
                            TSURF, EMISSIVITY=None, SOLFLUX=None, REFLECTANCE=None, SOL_ANG=None, EMISS_ANG=None,
                            xfac=None):
         """Host arrays; leading model axis optional.  Returns SPECOUT (n,W,P) (or (W,P))."""
-        W, G, NP, NT, S = self.dims
-        lay_press_pa = _np(lay_press_pa)
-        single = lay_press_pa.ndim == 1
-        lp = np.atleast_2d(lay_press_pa); n, L = lp.shape
-        lt = _np(np.atleast_2d(_np(lay_temp)))
-        am = _np(amount).reshape(n, S, L)
-        tc = None if taucont is None else _np(taucont).reshape(n, W, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(np.broadcast_to(_np(SCALE).reshape(-1, LIMAX, P), (n, LIMAX, P)))
-        ET = _np(np.broadcast_to(_np(EMTEMP).reshape(-1, LIMAX, P), (n, LIMAX, P)))
-        TS = _np(np.broadcast_to(np.atleast_1d(_np(TSURF)), (n,)))
+        what, W = "cirsrad_ck_thermal", self.dims[0]
+        n, L, single, lp, lt, am, tc, _ = self._layer_args(what, lay_press_pa, lay_temp, amount, taucont, model_axis="optional")
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, TS = self._path_args(what, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, n)
         out = np.empty((n, W, P))
         rc = self._lib.ansfm_cirsrad_ck_thermal(
             self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), P, LIMAX, _ptr(NLAYIN),
             _ptr(LAYINC), _ptr(SC), _ptr(ET), _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(SOLFLUX)),
             _ptr(_np(REFLECTANCE)), _ptr(None if SOL_ANG is None else _np(np.atleast_1d(SOL_ANG))),
             _ptr(None if EMISS_ANG is None else _np(np.atleast_1d(EMISS_ANG))), _ptr(_np(xfac)), _ptr(out))
-        self._check(rc, "cirsrad_ck_thermal")
+        self._check(rc, what)
         return out[0] if single else out
 
     def calc_singlescatt_plane_spectrum(self, ISPACE, WAVE, TAUTOT_PATH, TEMP, OMEGA, PHASE, TSURF, EMISSIVITY, BRDF, SOLFLUX,
@@ -451,16 +530,13 @@ class AnsfmEngine:
         (NPATH, NWAVE, NLAY), BRDF (NWAVE, NPATH) -> SPECOUT (NWAVE, NPATH)."""
         W, G, NP, NT, S = self.dims
         lp = _np(lay_press_pa); L = lp.shape[0]
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, _ = self._path_args("cirsrad_ck_singlescatt", NLAYIN, LAYINC, SCALE, EMTEMP)
         out = np.empty((W, P))
         rc = self._lib.ansfm_cirsrad_ck_singlescatt(
             self._ctx, int(ISPACE), L, _ptr(lp), _ptr(_np(lay_temp)), _ptr(_np(amount).reshape(S, L)),
             _ptr(None if taucont is None else _np(taucont).reshape(W, L)), _ptr(_np(tausca).reshape(W, L)),
-            _ptr(_np(phase).reshape(P, W, L)), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(_np(SCALE).reshape(LIMAX, P)),
-            _ptr(_np(EMTEMP).reshape(LIMAX, P)), float(TSURF), _ptr(_np(EMISSIVITY)), _ptr(_np(BRDF).reshape(W, P)),
+            _ptr(_np(phase).reshape(P, W, L)), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), float(TSURF),
+            _ptr(_np(EMISSIVITY)), _ptr(_np(BRDF).reshape(W, P)),
             _ptr(_np(SOLFLUX)), _ptr(_np(np.atleast_1d(SOL_ANG))), _ptr(_np(np.atleast_1d(EMISS_ANG))), _ptr(_np(xfac)), _ptr(out))
         self._check(rc, "cirsrad_ck_singlescatt")
         return out
@@ -474,29 +550,17 @@ class AnsfmEngine:
         Only the distinct (model, layer) gas opacities are computed (`last_layer_rows()`), and every state starts each path
         from the record model 0 left after the last layer the two have in common (`last_rt_shared()`).  The same numbers as n
         `cirsrad_ck_singlescatt` calls, bit for bit."""
-        W, G, NP, NT, S = self.dims
-        lp = _np(lay_press_pa)
-        if lp.ndim != 2:
-            raise ValueError("lay_press_pa must be (n_models, NLAY)")
-        n, L = lp.shape
-        am = _np(amount)
-        if am.shape != (n, S, L):
-            raise ValueError("amount must be (n_models, NGAS, NLAY)")
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        TS = _np(np.atleast_1d(TSURF))
-        if TS.shape != (n,):
-            raise ValueError("TSURF must be (n_models,)")
+        what, W = "cirsrad_ck_singlescatt_batch", self.dims[0]
+        n, L, _, lp, lt, am, tc, _ = self._layer_args(what, lay_press_pa, lay_temp, amount, taucont, model_axis="required")
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, _ = self._path_args(what, NLAYIN, LAYINC, SCALE, EMTEMP, n=n)
+        TS = self._per_model_tsurf(what, TSURF, n)
         out = np.empty((n, W, P))
         rc = self._lib.ansfm_cirsrad_ck_singlescatt_batch(
-            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(_np(lay_temp).reshape(n, L)), _ptr(am),
-            _ptr(None if taucont is None else _np(taucont).reshape(n, W, L)), _ptr(_np(tausca).reshape(n, W, L)),
-            _ptr(_np(phase).reshape(n, P, W, L)), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(_np(SCALE).reshape(n, LIMAX, P)),
-            _ptr(_np(EMTEMP).reshape(n, LIMAX, P)), _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(BRDF).reshape(W, P)),
-            _ptr(_np(SOLFLUX)), _ptr(_np(np.atleast_1d(SOL_ANG))), _ptr(_np(np.atleast_1d(EMISS_ANG))), _ptr(_np(xfac)), _ptr(out))
-        self._check(rc, "cirsrad_ck_singlescatt_batch")
+            self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(_np(tausca).reshape(n, W, L)),
+            _ptr(_np(phase).reshape(n, P, W, L)), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), _ptr(TS),
+            _ptr(_np(EMISSIVITY)), _ptr(_np(BRDF).reshape(W, P)), _ptr(_np(SOLFLUX)), _ptr(_np(np.atleast_1d(SOL_ANG))),
+            _ptr(_np(np.atleast_1d(EMISS_ANG))), _ptr(_np(xfac)), _ptr(out))
+        self._check(rc, what)
         return out
 
     def cirsrad_ck_singlescatt_batch_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phase_fn,
@@ -541,7 +605,7 @@ class AnsfmEngine:
         contiguous float64 torch device tensors, else host arrays.  ncont: the populations CONT must have (None: as many as it
         has).  -> (the nine ctypes arguments, the populations of CONT); ValueError for an array of another shape and for a
         term without its arrays."""
-        mode = 12 if variant == "v" else int(IRAY)
+        mode = _ray_mode(IRAY, variant)
         use_cia, use_dust = q is not None, CONT is not None
         if not dev:
             q, FRAC, TOTAM, DELH, CONT, f4 = (_np(a) for a in (q, FRAC, TOTAM, DELH, CONT, f4))
@@ -567,31 +631,15 @@ class AnsfmEngine:
         """the `_cont` entry (phase_fn) or the `_src` entry (alpha_deg)"""
         src = what.endswith("_src")
         dims, _ = self.ktable_info()
-        W, S = dims[0], dims[4]
-        lp = _np(lay_press_pa)
-        if lp.ndim != 2:
-            raise ValueError("lay_press_pa must be (n_models, NLAY)")
-        n, L = lp.shape
-        am = _np(amount)
-        if am.shape != (n, S, L):
-            raise ValueError("amount must be (n_models, NGAS, NLAY)")
-        lt = _np(lay_temp)
-        if lt.shape != (n, L):
-            raise ValueError("lay_temp must be (n_models, NLAY)")
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        if NLAYIN.shape != (P,):
-            raise ValueError(f"{what}: NLAYIN must be (NPATH,)")
-        TS = _np(np.atleast_1d(TSURF))
-        if TS.shape != (n,):
-            raise ValueError("TSURF must be (n_models,)")
+        W = dims[0]
+        n, L, _, lp, lt, am, _, _ = self._layer_args(what, lay_press_pa, lay_temp, amount, model_axis="required", dims=dims)
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, _ = self._path_args(what, NLAYIN, LAYINC, SCALE, EMTEMP, n=n, exact=True)
+        TS = self._per_model_tsurf(what, TSURF, n)
         cont, ncont = self._fused_cont_args(what, n, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant)
         arrs = {}
         for name, a, shape in (("phase_fn", phase_fn, (W, P, ncont + 1)),
-                               ("alpha_deg", None if alpha_deg is None else np.atleast_1d(alpha_deg), (P,)), ("SCALE", SCALE, (n, LIMAX, P)),
-                               ("EMTEMP", EMTEMP, (n, LIMAX, P)), ("BRDF", BRDF, (W, P)), ("EMISSIVITY", EMISSIVITY, (W,)),
+                               ("alpha_deg", None if alpha_deg is None else np.atleast_1d(alpha_deg), (P,)),
+                               ("BRDF", BRDF, (W, P)), ("EMISSIVITY", EMISSIVITY, (W,)),
                                ("SOLFLUX", SOLFLUX, (W,)), ("xfac", xfac, (W,)), ("SOL_ANG", None if SOL_ANG is None else np.atleast_1d(SOL_ANG), (P,)),
                                ("EMISS_ANG", None if EMISS_ANG is None else np.atleast_1d(EMISS_ANG), (P,))):
             a = arrs[name] = None if a is None else _np(a)
@@ -602,7 +650,7 @@ class AnsfmEngine:
         out = np.empty((n, W, P))
         rc = getattr(self._lib, "ansfm_" + what)(
             self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), *cont, ncont,
-            _ptr(arrs["alpha_deg" if src else "phase_fn"]), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(arrs["SCALE"]), _ptr(arrs["EMTEMP"]),
+            _ptr(arrs["alpha_deg" if src else "phase_fn"]), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET),
             _ptr(TS), _ptr(arrs["EMISSIVITY"]), _ptr(arrs["BRDF"]), _ptr(arrs["SOLFLUX"]), _ptr(arrs["SOL_ANG"]), _ptr(arrs["EMISS_ANG"]),
             _ptr(arrs["xfac"]), _ptr(out))
         self._check(rc, what)
@@ -611,22 +659,13 @@ class AnsfmEngine:
     def cirsrad_ck_transmission(self, lay_press_pa, lay_temp, amount, taucont, NLAYIN, LAYINC, SCALE, xfac=None):
         """CIRSrad, pure-transmission branch (calculate_transmission_spectrum :4110): SPECOUT (n, W, P) (or (W, P)) =
         xfac * sum_g DELG exp(-sum over the path's layers of TAUTOT_LAYINC)."""
-        W, G, NP, NT, S = self.dims
-        lay_press_pa = _np(lay_press_pa)
-        single = lay_press_pa.ndim == 1
-        lp = np.atleast_2d(lay_press_pa); n, L = lp.shape
-        lt = _np(np.atleast_2d(_np(lay_temp)))
-        am = _np(amount).reshape(n, S, L)
-        tc = None if taucont is None else _np(taucont).reshape(n, W, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(np.broadcast_to(_np(SCALE).reshape(-1, LIMAX, P), (n, LIMAX, P)))
+        what, W = "cirsrad_ck_transmission", self.dims[0]
+        n, L, single, lp, lt, am, tc, _ = self._layer_args(what, lay_press_pa, lay_temp, amount, taucont, model_axis="optional")
+        NLAYIN, LAYINC, LIMAX, P, SC, _, _ = self._path_args(what, NLAYIN, LAYINC, SCALE, n=n)
         out = np.empty((n, W, P))
         rc = self._lib.ansfm_cirsrad_ck_transmission(self._ctx, n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), P, LIMAX, _ptr(NLAYIN),
                                                      _ptr(LAYINC), _ptr(SC), _ptr(_np(xfac)), _ptr(out))
-        self._check(rc, "cirsrad_ck_transmission")
+        self._check(rc, what)
         return out[0] if single else out
 
     def cirsradg_ck_transmission(self, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map, NLAYIN,
@@ -634,51 +673,30 @@ class AnsfmEngine:
         """CIRSrad(return_grad=True), pure-transmission branch (:4110-4131, :4504-4507): SPECOUT (n, W, P) and
         dSPECOUT (n, W, NPAR, LIMAX, P) = -sum_g DELG xfac exp(-tau_path) dTAUTOT_LAYINC (leading axis dropped for a
         single model).  dTSURF of this branch is zero."""
-        W, G, NP, NT, S = self.dims
-        lay_press_pa = _np(lay_press_pa)
-        single = lay_press_pa.ndim == 1
-        lp = np.atleast_2d(lay_press_pa); n, L = lp.shape
-        lt = _np(np.atleast_2d(_np(lay_temp)))
-        am = _np(amount).reshape(n, S, L)
-        tc = None if taucont is None else _np(taucont).reshape(n, W, L)
-        dtc = None if dtaucon is None else _np(dtaucon).reshape(n, W, NPAR, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(np.broadcast_to(_np(SCALE).reshape(-1, LIMAX, P), (n, LIMAX, P)))
+        what, W = "cirsradg_ck_transmission", self.dims[0]
+        n, L, single, lp, lt, am, tc, dtc = self._layer_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR,
+                                                             model_axis="optional")
+        NLAYIN, LAYINC, LIMAX, P, SC, _, _ = self._path_args(what, NLAYIN, LAYINC, SCALE, n=n)
         ig = _np(igas_map, np.int32)
         spec = np.empty((n, W, P)); dspec = np.empty((n, W, NPAR, LIMAX, P))
+        self._chain_dspec = None
         rc = self._lib.ansfm_cirsradg_ck_transmission(
             self._ctx, n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
             _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(_np(xfac)), _ptr(spec), _ptr(dspec))
-        self._check(rc, "cirsradg_ck_transmission")
-        self._chain_dspec = None
-        if n == 1:
-            dspec.flags.writeable = False
-            self._chain_dspec = _fingerprint(dspec[0])
-        return (spec[0], dspec[0]) if single else (spec, dspec)
+        self._check(rc, what)
+        return self._gradient_result(single, spec, dspec)
 
-    def _one_model_layers(self, what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE):
-        """The layer and path arrays of a fused one-model call as the library takes them:
-        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC."""
-        W, G, NP, NT, S = self.dims
-        lp = _np(lay_press_pa)
-        if lp.ndim != 1:
-            raise ValueError(what + ": one model, lay_press_pa (NLAY,)")
-        L = lp.shape[0]
-        lt = _np(lay_temp).reshape(L)
-        am = _np(amount).reshape(S, L)
-        tc = None if taucont is None else _np(taucont).reshape(W, L)
-        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, NPAR, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(SCALE).reshape(LIMAX, P)
-        if NLAYIN.shape != (P,):
-            raise ValueError(what + ": NLAYIN must be (NPATH,)")
-        return lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC
+    def _one_model_args(self, what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map):
+        """-> L and the library's arguments L .. igas_map of a fused one-model route"""
+        _, L, _, lp, lt, am, tc, dtc = self._layer_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, model_axis="none")
+        return L, (L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(_np(igas_map, np.int32)))
+
+    def _one_model_paths(self, what, NLAYIN, LAYINC, SCALE, EMTEMP=None, emission=False):
+        """-> P and the library's arguments P .. SCALE of a fused one-model route; emission: .. EMTEMP, which is then needed"""
+        if emission and EMTEMP is None:
+            raise ValueError(what + ": EMTEMP (LIMAX, NPATH) is needed")
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, _ = self._path_args(what, NLAYIN, LAYINC, SCALE, EMTEMP)
+        return P, (P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC)) + ((_ptr(ET),) if emission else ())
 
     @staticmethod
     def _mix_rows(what, mix, P):
@@ -693,6 +711,12 @@ class AnsfmEngine:
             raise ValueError(what + ": a dense mix must be (NGEOM, NPATH)")
         nz = Cm != 0.0
         return _np(np.concatenate([[0], np.cumsum(nz.sum(axis=1))]), np.int32), _np(np.nonzero(nz)[1], np.int32), _np(Cm[nz])
+
+    def _mix_args(self, what, mix, P, xfac):
+        """-> Q and the library's arguments Q, mix_ptr, mix_path, mix_val, xfac of a route that mixes paths to geometries"""
+        mptr, mpath, mval = self._mix_rows(what, mix, P)
+        xf = None if xfac is None else _np(xfac).reshape(self.dims[0])
+        return mptr.size - 1, (mptr.size - 1, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf))
 
     @contextlib.contextmanager
     def _shared_gas_gradient(self, what, dtau_every_gas, L, n=1, only=""):
@@ -768,22 +792,11 @@ class AnsfmEngine:
         320 layers or paths."""
         what = "cirsradg_ck_transit"
         W = self.dims[0]
-        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC = self._one_model_layers(
-            what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE)
-        L = lp.shape[0]
+        L, layers = self._one_model_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map)
+        P, paths = self._one_model_paths(what, NLAYIN, LAYINC, SCALE)
         cw = _np(path_weight).reshape(P)
-        ig = _np(igas_map, np.int32)
-        area = np.empty(W); trans = np.empty((W, P))
-        darea = None if gradients_on_device else np.empty((W, int(NPAR), L))
-        with self._shared_gas_gradient(what, dtau_every_gas, L):
-            self._chain_dspec = None
-            rc = self._lib.ansfm_cirsradg_ck_transit(
-                self._ctx, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
-                _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(cw), _ptr(area), _ptr(trans), _ptr(darea))
-        self._check(rc, what)
-        if gradients_on_device:
-            self._chain_dspec = ("device", W, int(NPAR), L, 1)
-        return area, trans, darea
+        return self._fused_gradient_call(what, L, dtau_every_gas, gradients_on_device, (W, int(NPAR), L),
+                                         (*layers, *paths, _ptr(cw)), (np.empty(W), np.empty((W, P))))
 
     def transit_last(self):
         """(scratch bytes beyond the gas stage, k_transit_sens ms, k_transit_grad ms) of the last cirsradg_ck_transit call"""
@@ -803,25 +816,11 @@ class AnsfmEngine:
         dMOD cannot be reserved."""
         what = "cirsradg_ck_occultation"
         W = self.dims[0]
-        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC = self._one_model_layers(
-            what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE)
-        L = lp.shape[0]
-        mptr, mpath, mval = self._mix_rows(what, mix, P)
-        Q = mptr.size - 1
-        xf = None if xfac is None else _np(xfac).reshape(W)
-        ig = _np(igas_map, np.int32)
-        mod = np.empty((W, Q)); trans = np.empty((W, P))
-        dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
-        with self._shared_gas_gradient(what, dtau_every_gas, L):
-            self._chain_dspec = None
-            rc = self._lib.ansfm_cirsradg_ck_occultation(
-                self._ctx, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
-                _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf), _ptr(mod), _ptr(trans),
-                _ptr(dmod))
-        self._check(rc, what)
-        if gradients_on_device:
-            self._chain_dspec = ("device", W, int(NPAR), L, Q)
-        return mod, trans, dmod
+        L, layers = self._one_model_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map)
+        P, paths = self._one_model_paths(what, NLAYIN, LAYINC, SCALE)
+        Q, mixing = self._mix_args(what, mix, P, xfac)
+        return self._fused_gradient_call(what, L, dtau_every_gas, gradients_on_device, (W, int(NPAR), L, Q),
+                                         (*layers, *paths, *mixing), (np.empty((W, Q)), np.empty((W, P))))
 
     def occultation_last(self):
         """(scratch bytes beyond the gas stage and dMOD, k_occ_paths ms, k_occ_grad ms) of the last cirsradg_ck_occultation call"""
@@ -839,26 +838,11 @@ class AnsfmEngine:
         scratch cannot be reserved."""
         what = "cirsradg_ck_limb"
         W = self.dims[0]
-        lp, lt, am, tc, dtc, NLAYIN, LAYINC, LIMAX, P, SC = self._one_model_layers(
-            what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR, NLAYIN, LAYINC, SCALE)
-        L = lp.shape[0]
-        ET = _np(EMTEMP).reshape(LIMAX, P)
-        mptr, mpath, mval = self._mix_rows(what, mix, P)
-        Q = mptr.size - 1
-        xf = None if xfac is None else _np(xfac).reshape(W)
-        ig = _np(igas_map, np.int32)
-        mod = np.empty((W, Q)); spec = np.empty((W, P))
-        dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
-        with self._shared_gas_gradient(what, dtau_every_gas, L):
-            self._chain_dspec = None
-            rc = self._lib.ansfm_cirsradg_ck_limb(
-                self._ctx, int(ISPACE), L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), P, LIMAX,
-                _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf), _ptr(mod),
-                _ptr(spec), _ptr(dmod))
-        self._check(rc, what)
-        if gradients_on_device:
-            self._chain_dspec = ("device", W, int(NPAR), L, Q)
-        return mod, spec, dmod
+        L, layers = self._one_model_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map)
+        P, paths = self._one_model_paths(what, NLAYIN, LAYINC, SCALE, EMTEMP, emission=True)
+        Q, mixing = self._mix_args(what, mix, P, xfac)
+        return self._fused_gradient_call(what, L, dtau_every_gas, gradients_on_device, (W, int(NPAR), L, Q),
+                                         (int(ISPACE), *layers, *paths, *mixing), (np.empty((W, Q)), np.empty((W, P))))
 
     def limb_last(self):
         """(scratch bytes beyond the gas stage and dMOD, k_limb_planck + k_limb_sens ms, k_limb_grad ms) of the last
@@ -876,15 +860,8 @@ class AnsfmEngine:
         8 W NPAR L Q bytes on the device.  ValueError for TSURF > 0 without EMISSIVITY, a LAYINC outside the layers or a bad mix;
         NotImplementedError above 160 layers or when dMOD or the scratch cannot be reserved."""
         what = "cirsradg_ck_disc"
-        W, G, NP, NT, S = self.dims
-        lp = _np(lay_press_pa)
-        if lp.ndim != 1:
-            raise ValueError(what + ": one model, lay_press_pa (NLAY,)")
-        L = lp.shape[0]
-        lt = _np(lay_temp).reshape(L)
-        am = _np(amount).reshape(S, L)
-        tc = None if taucont is None else _np(taucont).reshape(W, L)
-        dtc = None if dtaucon is None else _np(dtaucon).reshape(W, int(NPAR), L)
+        W = self.dims[0]
+        L, layers = self._one_model_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NVMR, NPAR, igas_map)
         LAYINC = _np(LAYINC, np.int32).reshape(-1)
         N = LAYINC.shape[0]
         ET = _np(EMTEMP).reshape(-1)
@@ -896,23 +873,12 @@ class AnsfmEngine:
         P = SC.shape[1]
         if mix is None:
             raise ValueError(what + ": mix is required (disc.average_mix)")
-        mptr, mpath, mval = self._mix_rows(what, mix, P)
-        Q = mptr.size - 1
-        xf = None if xfac is None else _np(xfac).reshape(W)
+        Q, mixing = self._mix_args(what, mix, P, xfac)
         em = None if EMISSIVITY is None else _np(EMISSIVITY).reshape(W)
-        ig = _np(igas_map, np.int32)
-        mod = np.empty((W, Q)); spec = np.empty((W, P)); dts = np.empty((W, Q))
-        dmod = None if gradients_on_device else np.empty((W, int(NPAR), L, Q))
-        with self._shared_gas_gradient(what, dtau_every_gas, L):
-            self._chain_dspec = None
-            rc = self._lib.ansfm_cirsradg_ck_disc(
-                self._ctx, int(ISPACE), L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR), _ptr(ig), N,
-                _ptr(LAYINC), _ptr(ET), P, _ptr(SC), float(TSURF), _ptr(em), Q, _ptr(mptr), _ptr(mpath), _ptr(mval), _ptr(xf),
-                _ptr(mod), _ptr(spec), _ptr(dts), _ptr(dmod))
-        self._check(rc, what)
-        if gradients_on_device:
-            self._chain_dspec = ("device", W, int(NPAR), L, Q)
-        return mod, spec, dts, dmod
+        return self._fused_gradient_call(
+            what, L, dtau_every_gas, gradients_on_device, (W, int(NPAR), L, Q),
+            (int(ISPACE), *layers, N, _ptr(LAYINC), _ptr(ET), P, _ptr(SC), float(TSURF), _ptr(em), *mixing),
+            (np.empty((W, Q)), np.empty((W, P)), np.empty((W, Q))))
 
     def disc_last(self):
         """(scratch bytes beyond the gas stage and dMOD, k_disc_planck + k_disc_sens ms, k_disc_grad ms) of the last
@@ -926,39 +892,22 @@ class AnsfmEngine:
         (leading axis dropped for a single model).  gradients_on_device (single model): dSPECOUT is not copied to the host
         (None is returned in its place); `map2pro(None, ...)` takes it from the device.  dtau_every_gas (W, L), single
         model: added to dTAUCON of every gas parameter (the Rayleigh term, :3955-3957) without building the NVMR copies."""
-        W, G, NP, NT, S = self.dims
-        lay_press_pa = _np(lay_press_pa)
-        single = lay_press_pa.ndim == 1
-        lp = np.atleast_2d(lay_press_pa); n, L = lp.shape
-        lt = _np(np.atleast_2d(_np(lay_temp)))
-        am = _np(amount).reshape(n, S, L)
-        tc = None if taucont is None else _np(taucont).reshape(n, W, L)
-        dtc = None if dtaucon is None else _np(dtaucon).reshape(n, W, NPAR, L)
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(np.broadcast_to(_np(SCALE).reshape(-1, LIMAX, P), (n, LIMAX, P)))
-        ET = _np(np.broadcast_to(_np(EMTEMP).reshape(-1, LIMAX, P), (n, LIMAX, P)))
-        TS = _np(np.broadcast_to(np.atleast_1d(_np(TSURF)), (n,)))
+        what, W = "cirsradg_ck_thermal", self.dims[0]
+        n, L, single, lp, lt, am, tc, dtc = self._layer_args(what, lay_press_pa, lay_temp, amount, taucont, dtaucon, NPAR,
+                                                             model_axis="optional")
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, TS = self._path_args(what, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, n)
         ig = _np(igas_map, np.int32)
         on_dev = bool(gradients_on_device) and n == 1
         spec = np.empty((n, W, P)); dts = np.empty((n, W, P))
         dspec = None if on_dev else np.empty((n, W, NPAR, LIMAX, P))
-        with self._shared_gas_gradient("cirsradg_ck_thermal", dtau_every_gas, L, n, " for a single model"):
+        with self._shared_gas_gradient(what, dtau_every_gas, L, n, " for a single model"):
+            self._chain_dspec = None
             rc = self._lib.ansfm_cirsradg_ck_thermal(
                 self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(tc), _ptr(dtc), int(NVMR), int(NPAR),
                 _ptr(ig), P, LIMAX, _ptr(NLAYIN), _ptr(LAYINC), _ptr(SC), _ptr(ET), _ptr(TS), _ptr(_np(EMISSIVITY)),
                 _ptr(_np(xfac)), _ptr(spec), _ptr(dspec), _ptr(dts))
-        self._check(rc, "cirsradg_ck_thermal")
-        self._chain_dspec = None
-        if on_dev:
-            self._chain_dspec = ("device", W, int(NPAR), LIMAX, P)
-            return (spec[0], None, dts[0]) if single else (spec, None, dts)
-        if n == 1:                       # device copy usable by map2pro: hand the host array out read-only
-            dspec.flags.writeable = False
-            self._chain_dspec = _fingerprint(dspec[0])
-        return (spec[0], dspec[0], dts[0]) if single else (spec, dspec, dts)
+        self._check(rc, what)
+        return self._gradient_result(single, spec, dspec, dts, (W, int(NPAR), LIMAX, P) if on_dev else None)
 
     def cirsradg_ck_thermal_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, NVMR, NPAR,
                                  igas_map, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY=None, xfac=None,
@@ -973,23 +922,13 @@ class AnsfmEngine:
         resident, an NVMR other than the CIA source's, an NPAR other than NVMR + 2 + the aerosol source's NDUST;
         NotImplementedError for NVMR > 46."""
         what = "cirsradg_ck_thermal_cont"
-        W, G, NP, NT, S = self.dims
-        lay_press_pa = _np(lay_press_pa)
-        single = lay_press_pa.ndim == 1
-        lp = np.atleast_2d(lay_press_pa); n, L = lp.shape
-        lt = _np(np.atleast_2d(_np(lay_temp)))
-        am = _np(amount).reshape(n, S, L)
+        W = self.dims[0]
+        n, L, single, lp, lt, am, _, _ = self._layer_args(what, lay_press_pa, lay_temp, amount, model_axis="optional")
         NVMR, NPAR = int(NVMR), int(NPAR)
         opt = lambda a, shape: None if a is None else _np(a).reshape(shape)
         cont, _ = self._fused_cont_args(what, n, L, opt(q, (n, L, NVMR)), opt(FRAC, (n, L)), opt(TOTAM, (n, L)), opt(DELH, (n, L)),
                                         opt(CONT, (n, L, -1)), IRAY, opt(f4, (n, L, 4)), variant, ncont=getattr(self, "dust_n", None))
-        LAYINC = _np(LAYINC, np.int32); NLAYIN = _np(np.atleast_1d(NLAYIN), np.int32)
-        if LAYINC.ndim == 1:
-            LAYINC = LAYINC[:, None]
-        LIMAX, P = LAYINC.shape
-        SC = _np(np.broadcast_to(_np(SCALE).reshape(-1, LIMAX, P), (n, LIMAX, P)))
-        ET = _np(np.broadcast_to(_np(EMTEMP).reshape(-1, LIMAX, P), (n, LIMAX, P)))
-        TS = _np(np.broadcast_to(np.atleast_1d(_np(TSURF)), (n,)))
+        NLAYIN, LAYINC, LIMAX, P, SC, ET, TS = self._path_args(what, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, n)
         ig = _np(igas_map, np.int32)
         on_dev = bool(gradients_on_device) and n == 1
         spec = np.empty((n, W, P)); dts = np.empty((n, W, P))
@@ -999,13 +938,7 @@ class AnsfmEngine:
             self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), *cont, NVMR, NPAR, _ptr(ig), P, LIMAX, _ptr(NLAYIN),
             _ptr(LAYINC), _ptr(SC), _ptr(ET), _ptr(TS), _ptr(_np(EMISSIVITY)), _ptr(_np(xfac)), _ptr(spec), _ptr(dspec), _ptr(dts))
         self._check(rc, what)
-        if on_dev:
-            self._chain_dspec = ("device", W, NPAR, LIMAX, P)
-            return (spec[0], None, dts[0]) if single else (spec, None, dts)
-        if n == 1:                       # device copy usable by map2pro: hand the host array out read-only
-            dspec.flags.writeable = False
-            self._chain_dspec = _fingerprint(dspec[0])
-        return (spec[0], dspec[0], dts[0]) if single else (spec, dspec, dts)
+        return self._gradient_result(single, spec, dspec, dts, (W, NPAR, LIMAX, P) if on_dev else None)
 
     def cirsradg_ck_thermal_cont_dev(self, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4,
                                      NVMR, NPAR, igas_map, P, LIMAX, NLAYIN, LAYINC, SCALE, EMTEMP, TSURF, EMISSIVITY, xfac, SPECOUT,
@@ -1044,11 +977,11 @@ class AnsfmEngine:
                                    EMISS_ANG, xfac, SPECOUT, variant=None):
         """cirsrad_ck_thermal_dev for a batch whose continuum is Rayleigh scattering alone: TOTAM (n, L) and, IRAY 4,
         f4 (n, L, 4) (see rayleigh_f4) are device tensors; the continuum is formed per distinct layer inside the call."""
-        mode = 12 if variant == "v" else int(IRAY)
         rc = self._lib.ansfm_cirsrad_ck_thermal_ray_dev(
-            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount), mode, _ptr(TOTAM),
-            _ptr(f4), int(P), int(LIMAX), _ptr(NLAYIN), _ptr(LAYINC), _ptr(SCALE), _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY),
-            _ptr(SOLFLUX), _ptr(REFLECTANCE), _ptr(SOL_ANG), _ptr(EMISS_ANG), _ptr(xfac), _ptr(SPECOUT))
+            self._ctx, int(ISPACE), int(n_models), int(L), _ptr(lay_press_pa), _ptr(lay_temp), _ptr(amount),
+            _ray_mode(IRAY, variant), _ptr(TOTAM), _ptr(f4), int(P), int(LIMAX), _ptr(NLAYIN), _ptr(LAYINC), _ptr(SCALE),
+            _ptr(EMTEMP), _ptr(TSURF), _ptr(EMISSIVITY), _ptr(SOLFLUX), _ptr(REFLECTANCE), _ptr(SOL_ANG), _ptr(EMISS_ANG),
+            _ptr(xfac), _ptr(SPECOUT))
         self._check(rc, "cirsrad_ck_thermal_ray_dev")
 
     def cirsrad_ck_thermal_cont_dev(self, ISPACE, n_models, L, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY,
@@ -1123,6 +1056,23 @@ class AnsfmEngine:
         mu1 = _np(mu1)
         return (phasarr, ncont, nth), (sol, emi, aph, sol.shape[0]), (mu1, mu1.shape[0])
 
+    def _scatter_batch_common(self, what, lay_press_pa, lay_temp, amount, phasarr, radg, sol_angs, emiss_angs, aphis, mu1,
+                              wave_slice, whole_axis=True):
+        """What the batched scattering entries share -> W, (n, L, lp, lt, am), the three groups of `_scatter_common`, radg,
+        (W_full, w_begin).  The layers carry a model axis; radg holds n NWAVE NMU values; phasarr covers the axis wave_slice =
+        (w_begin, W_full) names -- the table's own without one, where whole_axis=False leaves that to the library."""
+        dims, _ = self.ktable_info()
+        W = dims[0]
+        n, L, _, lp, lt, am, _, _ = self._layer_args(what, lay_press_pa, lay_temp, amount, model_axis="required", dims=dims)
+        phase, geom, (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        rg = _np(radg)
+        if rg.size != n * W * nmu:
+            raise ValueError(f"{what}: radg must be (n_models, NWAVE, NMU)")
+        w_begin, W_full = (0, W) if wave_slice is None else (int(v) for v in wave_slice)
+        if phase[0] is not None and (whole_axis or wave_slice is not None) and phase[0].shape[1] != W_full:
+            raise ValueError(f"{what}: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
+        return W, (n, L, lp, lt, am), phase, geom, (mu1, nmu), rg, (W_full, w_begin)
+
     def cirsrad_ck_scatter(self, ISPACE, lay_press_pa, lay_temp, amount, TAUCIA, TAUDUST, TAURAY, TAUSCAT, phasarr, lfrac,
                            radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie,
                            xfac=None, return_spec_g=False):
@@ -1174,30 +1124,22 @@ class AnsfmEngine:
         Every spectrum has the bits of `cirsrad_ck_scatter` with that model's phase function; a layer stays model 0's where none
         of the changed populations is present (lfrac == 0).  Whole axis and more than one g-ordinate only: NotImplementedError
         with wave_slice or an LBL table, and when the variants' buffers find no room."""
-        dims, _ = self.ktable_info()
-        W, G, S = dims[0], dims[1], dims[4]
-        lp = _np(lay_press_pa); n, L = lp.shape
-        am = _np(amount)
-        if am.shape != (n, S, L):
-            raise ValueError("amount must be (n_models, NGAS, NLAY)")
+        what = "cirsrad_ck_scatter_batch"
+        W, (n, L, lp, lt, am), (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu), rg, axis = self._scatter_batch_common(
+            what, lay_press_pa, lay_temp, amount, phasarr, radg, sol_angs, emiss_angs, aphis, mu1, wave_slice, whole_axis=False)
         nwl = lambda a: None if a is None else _np(a).reshape(n, W, L)
-        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
-        lf =None if lfrac is None else _np(lfrac).reshape(n, W, ncont, L)
-        rg = _np(radg).reshape(n, W, nmu)
+        lf = None if lfrac is None else _np(lfrac).reshape(n, W, ncont, L)
         out = np.empty((n, W, P))
-        args = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(_np(lay_temp).reshape(n, L)), _ptr(am), _ptr(nwl(TAUCIA)),
+        args = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), _ptr(nwl(TAUCIA)),
                 _ptr(nwl(TAUDUST)), _ptr(nwl(TAURAY)), _ptr(nwl(TAUSCAT)), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol),
                 _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf),
                 int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out))
-        with self._phase_variants("cirsrad_ck_scatter_batch", W, phase_of, phasarr_variants):
+        with self._phase_variants(what, W, phase_of, phasarr_variants):
             if wave_slice is None:
-                self._check(self._lib.ansfm_cirsrad_ck_scatter_batch(*args), "cirsrad_ck_scatter_batch")
-                return out
-            w_begin, W_full = (int(v) for v in wave_slice)
-            if phasarr is not None and phasarr.shape[1] != W_full:
-                raise ValueError("cirsrad_ck_scatter_batch: with wave_slice, phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
-            self._check(self._lib.ansfm_cirsrad_ck_scatter_batch_slice(*args, W_full, w_begin), "cirsrad_ck_scatter_batch_slice")
-            return out
+                self._check(self._lib.ansfm_cirsrad_ck_scatter_batch(*args), what)
+            else:
+                self._check(self._lib.ansfm_cirsrad_ck_scatter_batch_slice(*args, *axis), what + "_slice")
+        return out
 
     def cirsrad_ck_scatter_batch_rows(self, ISPACE, lay_press_pa, lay_temp, amount, cont_row, TAUCIA_rows, TAUDUST_rows, TAURAY_rows,
                                       TAUSCAT_rows, phasarr, lfrac_rows, radg, sol_angs, emiss_angs, aphis, solar, lowbc,
@@ -1210,24 +1152,14 @@ class AnsfmEngine:
         with the expanded arrays.  A layer is taken from model 0's doubling results when its gas inputs are model 0's and
         cont_row[m, l] == cont_row[0, l] -- and, with phase_of / phasarr_variants (as in `cirsrad_ck_scatter_batch`), when the
         layer's lfrac row is 0 for every population whose phase function differs from model 0's."""
-        dims, _ = self.ktable_info()
-        W, G, S = dims[0], dims[1], dims[4]
-        lp = _np(lay_press_pa)
-        if lp.ndim != 2:
-            raise ValueError("lay_press_pa must be (n_models, NLAY)")
-        n, L = lp.shape
-        am = _np(amount)
-        if am.shape != (n, S, L):
-            raise ValueError("amount must be (n_models, NGAS, NLAY)")
-        lt = _np(lay_temp)
-        if lt.shape != (n, L):
-            raise ValueError("lay_temp must be (n_models, NLAY)")
+        what = "cirsrad_ck_scatter_batch_rows"
+        W, (n, L, lp, lt, am), (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu), rg, axis = self._scatter_batch_common(
+            what, lay_press_pa, lay_temp, amount, phasarr, radg, sol_angs, emiss_angs, aphis, mu1, wave_slice)
         cr = np.asarray(cont_row)
         if cr.shape != (n, L) or cr.dtype.kind not in "iu":
             raise ValueError("cont_row must be an integer array (n_models, NLAY)")
         cr = _np(cr, np.int32)
-        (phasarr, ncont, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
-        rows =[None if a is None else _np(a) for a in (TAUCIA_rows, TAUDUST_rows, TAURAY_rows, TAUSCAT_rows)]
+        rows = [None if a is None else _np(a) for a in (TAUCIA_rows, TAUDUST_rows, TAURAY_rows, TAUSCAT_rows)]
         lf = None if lfrac_rows is None or ncont == 0 else _np(lfrac_rows)
         if ncont > 0 and lf is None:
             raise ValueError("lfrac_rows is needed with aerosols (phasarr given)")
@@ -1237,20 +1169,14 @@ class AnsfmEngine:
                 raise ValueError(f"{name} must be (R, NWAVE) = ({R}, {W}), got {a.shape}")
         if lf is not None and lf.shape != (R, ncont, W):
             raise ValueError(f"lfrac_rows must be (R, NDUST, NWAVE) = ({R}, {ncont}, {W}), got {lf.shape}")
-        rg = _np(radg)
-        if rg.size != n * W * nmu:
-            raise ValueError("radg must be (n_models, NWAVE, NMU)")
-        w_begin, W_full = (0, W) if wave_slice is None else (int(v) for v in wave_slice)
-        if phasarr is not None and phasarr.shape[1] != W_full:
-            raise ValueError("cirsrad_ck_scatter_batch_rows: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
         out = np.empty((n, W, P))
-        with self._phase_variants("cirsrad_ck_scatter_batch_rows", W, phase_of, phasarr_variants):
+        with self._phase_variants(what, W, phase_of, phasarr_variants):
             rc = self._lib.ansfm_cirsrad_ck_scatter_batch_rows(
                 self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), int(R), _ptr(cr), _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
                 _ptr(rows[3]), ncont, nth, _ptr(phasarr), _ptr(lf), _ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)),
                 int(lowbc), _ptr(_np(brdf_matrix)), nmu, _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie),
-                _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
-            self._check(rc, "cirsrad_ck_scatter_batch_rows")
+                _ptr(_np(xfac)), _ptr(out), *axis)
+            self._check(rc, what)
         return out
 
     def cirsrad_ck_scatter_batch_cont(self, ISPACE, lay_press_pa, lay_temp, amount, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, phasarr,
@@ -1283,34 +1209,17 @@ class AnsfmEngine:
                       radg, sol_angs, emiss_angs, aphis, solar, lowbc, brdf_matrix, mu1, wt1, nf, nphi, iray, imie, xfac, wave_slice,
                       variant):
         """the `_cont` entry (phasarr) or the `_src` entry (theta, mu_theta)"""
-        dims, _ = self.ktable_info()
-        W, G, S = dims[0], dims[1], dims[4]
-        lp = _np(lay_press_pa)
-        if lp.ndim != 2:
-            raise ValueError("lay_press_pa must be (n_models, NLAY)")
-        n, L = lp.shape
-        am = _np(amount)
-        if am.shape != (n, S, L):
-            raise ValueError("amount must be (n_models, NGAS, NLAY)")
-        lt = _np(lay_temp)
-        if lt.shape != (n, L):
-            raise ValueError("lay_temp must be (n_models, NLAY)")
-        (phasarr, npop, nth), (sol, emi, aph, P), (mu1, nmu) = self._scatter_common(phasarr, sol_angs, emiss_angs, aphis, mu1)
+        W, (n, L, lp, lt, am), (phasarr, npop, nth), (sol, emi, aph, P), (mu1, nmu), rg, axis = self._scatter_batch_common(
+            what, lay_press_pa, lay_temp, amount, phasarr, radg, sol_angs, emiss_angs, aphis, mu1, wave_slice)
         if theta is not None:                   # the populations are those of the aerosol columns
             npop, nth = None, theta.shape[0]
         elif npop > 0 and CONT is None:
             raise ValueError(f"{what}: CONT is needed with aerosols (phasarr given)")
         cont, ncont = self._fused_cont_args(what, n, L, q, FRAC, TOTAM, DELH, CONT, IRAY, f4, variant, ncont=npop)
-        rg = _np(radg)
-        if rg.size != n * W * nmu:
-            raise ValueError("radg must be (n_models, NWAVE, NMU)")
-        w_begin, W_full = (0, W) if wave_slice is None else (int(v) for v in wave_slice)
-        if phasarr is not None and phasarr.shape[1] != W_full:
-            raise ValueError(f"{what}: phasarr must cover the whole axis (NDUST, W_full, 2, NTHETA)")
         out = np.empty((n, W, P))
         head = (self._ctx, int(ISPACE), n, L, _ptr(lp), _ptr(lt), _ptr(am), *cont, ncont, nth)
         tail = (_ptr(rg), P, _ptr(sol), _ptr(emi), _ptr(aph), _ptr(_np(solar)), int(lowbc), _ptr(_np(brdf_matrix)), nmu,
-                _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out), W_full, w_begin)
+                _ptr(mu1), _ptr(_np(wt1)), int(nf), int(nphi), int(iray), int(imie), _ptr(_np(xfac)), _ptr(out), *axis)
         if theta is not None:
             rc = self._lib.ansfm_cirsrad_ck_scatter_batch_src(*head, _ptr(theta), _ptr(mu_theta), *tail)
         else:
